@@ -14,10 +14,13 @@ configs[1] (its line is quoted in README.md), `--total-images 250000` configs[4]
 `--embed-only --total-images 1000000` configs[3]; `--scaling weak` keeps --images-per-gpu images PER GPU instead;
 `--prec fp32` runs the parity embedding (f32 MFMA, <= 1e-4 of the fp32 restatement) instead of the bf16 one.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.  PyTorch is used for device buffers, barriers and the all-gather only.
+A plain run sets up, warms up, times K steps and prints the headline figure.  --full adds what the headline does not need: the
+untimed profiling passes behind the `roofline*` objects, the CPU baseline and the `parity` checks against oracle/.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) so that two builds can be compared.
 """
 import argparse
 import json
@@ -153,6 +156,26 @@ def layerwise_roofline_seconds(batch):
     return sum(max(f / (PEAK_BF16_TFLOPS * 1e12), b / (PEAK_HBM_GBS * 1e9)) for f, b in lay)
 
 
+DUMP_ROWS = 4096  # embedding rows --dump-outputs writes: 32 MiB at D = 2048, the bulk of its 64 MB
+
+
+def dump_outputs(out_dir, E, cid=None, mrank=None, nc=None):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array.  E (n x 2048 fp32 on the device,
+    800 MB at 100 000 images) is written as a fixed sample: DUMP_ROWS rows drawn with a fixed seed, their indices beside them.  The
+    clustering outputs are written whole, in float64 so that every index is exact (16 bytes per image: 4 MB at configs[4]'s 250 000)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = E.shape[0]
+    rows = np.sort(np.random.default_rng(20250217).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    arrays = {"embedding_rows": rows.astype(np.float64),
+              "embeddings_sample": E[torch.from_numpy(rows).to(E.device)].float().cpu().numpy()}
+    if cid is not None:
+        arrays.update(cluster_id=np.asarray(cid, np.float64), member_rank=np.asarray(mrank, np.float64), n_clusters=np.array([nc], np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,7 +190,12 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--min-size", type=int, default=5)
     ap.add_argument("--max-size", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the parity checks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed profiling passes (roofline objects), the CPU baseline and the parity "
+                         "checks against oracle/; off by default: a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--embed-only", action="store_true", help="configs[3]: embed throughput without clustering")
     ap.add_argument("--overlap", action="store_true",
                     help="N=1: run the distance rows of already-embedded images on a side stream beside the later forward passes "
@@ -189,6 +217,8 @@ def main():
                     help="exact: centroid recompute, cluster ids bit-identical to the reference (default); "
                          "lw: MFMA distance tile + Lance-Williams rows (fast, not bit-identical)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
 
     import torch
     import torch.distributed as dist
@@ -245,6 +275,7 @@ def main():
             keep["E_full"] = E_local
             cid, mrank, nc = ctx.embed_cluster_dev(imgs.data_ptr(), n_local, E_local.data_ptr(), args.min_size, args.max_size, PREC, update,
                                                    overlap=args.overlap)
+            keep.update(cid=cid, mrank=mrank, nc=nc)
             st = ctx.last_stage_ms()
             result.update(embed_ms=st["embed_ms"], dist_ms=st["dist_ms"], merge_ms=st["merge_ms"], n_clusters=nc, merges=len(ctx.last_merges()),
                           dropped=int((cid < 0).sum()))
@@ -262,6 +293,7 @@ def main():
             torch.cuda.synchronize()
             result["allgather_ms"] = (time.perf_counter() - t0) * 1e3
         if args.embed_only:
+            keep["E_full"] = E_full
             return
         if world > 1 and args.update == "exact" and (args.tiles == "distributed"):
             # the initial distance matrix is built on ALL ranks (area-balanced runs of tile rows), every span goes to rank 0's
@@ -272,6 +304,7 @@ def main():
             if rank == 0:
                 keep["E_full"] = E_full
                 cid, mrank, nc = res
+                keep.update(cid=cid, mrank=mrank, nc=nc)
                 st = ctx.last_stage_ms()
                 total_ms = (time.perf_counter() - t0) * 1e3
                 result.update(dist_ms=total_ms - st["merge_ms"], merge_ms=st["merge_ms"], n_clusters=nc, merges=len(ctx.last_merges()),
@@ -279,6 +312,7 @@ def main():
         elif rank == 0:
             keep["E_full"] = E_full  # rank 0 re-uses the gathered matrix for the untimed profiling pass (no second collective)
             cid, mrank, nc = ctx.cluster_dev(E_full.data_ptr(), n_total, DIM, args.min_size, args.max_size, update)
+            keep.update(cid=cid, mrank=mrank, nc=nc)
             st = ctx.last_stage_ms()
             result.update(dist_ms=st["dist_ms"], merge_ms=st["merge_ms"], n_clusters=nc, merges=len(ctx.last_merges()),
                           dropped=int((cid < 0).sum()))
@@ -298,10 +332,12 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     elapsed = D.max_over_ranks(elapsed, dev if args.dist_backend == "nccl" else None)
+    if rank == 0 and args.dump_outputs:  # before anything below writes into E_local again
+        dump_outputs(args.dump_outputs, keep["E_full"], keep.get("cid"), keep.get("mrank"), keep.get("nc"))
     # The timed steps keep two forward passes in flight on two streams, where single launches cannot be bracketed with
     # events.  One extra, UNTIMED embedding pass over the same images runs the identical kernels on one stream with a HIP
     # event pair around every conv launch (on the engine's own stream) for the roofline object.
-    if rank == 0:
+    if rank == 0 and args.full:
         conv_mask = (1 << _lib.K_CONV) | (1 << _lib.K_CONV64)
         ctx.prof_reset()
         ctx.prof_enable(conv_mask)
@@ -317,9 +353,9 @@ def main():
 
     upd = dist_prof = rowmin_prof = None
     c128 = c64 = None
-    if rank == 0:
+    if rank == 0 and args.full:
         c128, c64 = ctx.prof_query(_lib.K_CONV), ctx.prof_query(_lib.K_CONV64)
-    if rank == 0 and not args.embed_only and args.update == "exact":
+    if rank == 0 and args.full and not args.embed_only and args.update == "exact":
         # The timed steps replay the merge loop from a hipGraph, where single launches cannot be bracketed with events.
         # One extra, UNTIMED clustering pass over the same E runs the identical kernels eagerly with a HIP event pair around
         # every ward_update_exact_kernel launch (on the engine's stream) to get that kernel's average duration.
@@ -335,10 +371,36 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / max(args.steps, 1) * 1e3
         value = n_total * args.steps / elapsed
+        name, ncu, hbm = ctx.device_info()
+        out = {
+            "metric": "images/sec (embed+Ward)" if not args.embed_only else "images/sec (embed only)",
+            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "bf16" if args.prec == "bf16" else "f32", "data": "synthetic",
+            "config": {"workload": (("%s: %d synthetic 224x224x3 images (structured, seed 20250217; %d on this rank), ResNet50-v1 " + args.prec +
+                                     " batch=%d -> 2048-d pooled E%s")
+                                    % ("configs[3] (embed only)" if args.embed_only and n_total == 1000000
+                                       else "embed only, custom size" if args.embed_only
+                                       else "the metric's size (configs[2]'s N=100000) on %d GPU%s" % (world, "s" if world > 1 else "") if n_total == 100000
+                                       else "configs[4] (250 GB distance matrix on GPU0)" if n_total == 250000
+                                       else "configs[1]" if n_total == 10000 and world == 1 else "custom size",
+                                       n_total, n_local, args.batch,
+                                       "" if args.embed_only else ((" -> RCCL all-gather of E -> distance rows (matrix-core lower bounds) on all ranks, sent to rank 0 piecewise (point-to-point) and laid into its matrix"
+                                                                     if args.update == "exact" and (args.tiles == "distributed")
+                                                                     else " -> RCCL all-gather of E -> rank 0 builds the whole distance matrix itself (matrix-core bounds)") if world > 1 else "")))
+                                   + ("" if args.embed_only else " -> Ward min=%d max=%d (merge loop on GPU0) -> cluster ids on host" % (args.min_size, args.max_size)),
+                       "n_images_total": n_total, "embed_dim": DIM, "weights": "synthetic seed 1", "device": name,
+                       "ward_update": "none (embed only)" if args.embed_only else "exact (ids bit-identical to the reference; new clusters' rows: Lance-Williams lower bounds, evaluated exactly on demand)" if (args.update == "exact" and (args.ward_dist == "lwbound" or (args.ward_dist == "auto" and n_total >= 4096))) else "exact (ids bit-identical to the reference)" if args.update == "exact"
+                       else "lw (MFMA distance tile + Lance-Williams, not bit-identical)"},
+            "stages_ms_last_step": {k: round(v, 3) for k, v in result.items() if k.endswith("_ms")},
+            "stages_note": ("N=1: embed_ms includes the distance rows that ran beside the forward passes on a side stream; dist_ms is what was left "
+                            "(tables, centroid transpose, initial row minima)" if world == 1 and not args.embed_only and args.overlap else ""),
+            "ward": {k: v for k, v in result.items() if not k.endswith("_ms")},
+        }
+    if rank == 0 and args.full:
         # conv_igemm_kernel<BF16,128> (all Cout>=128 convolutions)
         avg_us = c128["ms"] * 1e3 / max(c128["launches"], 1)
         achieved = c128["flops"] / max(c128["ms"], 1e-9) / 1e9  # TFLOP/s
-        name, ncu, hbm = ctx.device_info()
         # HBM traffic of the same kernels from the PMC counters (FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE, two
         # separate `rocprofv3 --kernel-trace --pmc ... -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline` passes:
         # scratch/collect_profiles.sh).  The counters cannot be read while this run is being timed, so the per-launch means are
@@ -446,33 +508,8 @@ def main():
         conv_ms_timed = c128["ms"] * result.get("embed_ms", 0.0) / max(result.get("embed_ms_single_stream", 0.0), 1e-9)
         ward_dominates = ward_roof is not None and upd["ms"] > conv_ms_timed
         roof = ward_roof if ward_dominates else conv_roof
-        out = {
-            "metric": "images/sec (embed+Ward)" if not args.embed_only else "images/sec (embed only)",
-            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "bf16" if args.prec == "bf16" else "f32", "data": "synthetic",
-            "config": {"workload": (("%s: %d synthetic 224x224x3 images (structured, seed 20250217; %d on this rank), ResNet50-v1 " + args.prec +
-                                     " batch=%d -> 2048-d pooled E%s")
-                                    % ("configs[3] (embed only)" if args.embed_only and n_total == 1000000
-                                       else "embed only, custom size" if args.embed_only
-                                       else "the metric's size (configs[2]'s N=100000) on %d GPU%s" % (world, "s" if world > 1 else "") if n_total == 100000
-                                       else "configs[4] (250 GB distance matrix on GPU0)" if n_total == 250000
-                                       else "configs[1]" if n_total == 10000 and world == 1 else "custom size",
-                                       n_total, n_local, args.batch,
-                                       "" if args.embed_only else ((" -> RCCL all-gather of E -> distance rows (matrix-core lower bounds) on all ranks, sent to rank 0 piecewise (point-to-point) and laid into its matrix"
-                                                                     if args.update == "exact" and (args.tiles == "distributed")
-                                                                     else " -> RCCL all-gather of E -> rank 0 builds the whole distance matrix itself (matrix-core bounds)") if world > 1 else "")))
-                                   + ("" if args.embed_only else " -> Ward min=%d max=%d (merge loop on GPU0) -> cluster ids on host" % (args.min_size, args.max_size)),
-                       "n_images_total": n_total, "embed_dim": DIM, "weights": "synthetic seed 1", "device": name,
-                       "ward_update": "none (embed only)" if args.embed_only else "exact (ids bit-identical to the reference; new clusters' rows: Lance-Williams lower bounds, evaluated exactly on demand)" if (args.update == "exact" and (args.ward_dist == "lwbound" or (args.ward_dist == "auto" and n_total >= 4096))) else "exact (ids bit-identical to the reference)" if args.update == "exact"
-                       else "lw (MFMA distance tile + Lance-Williams, not bit-identical)"},
-            "stages_ms_last_step": {k: round(v, 3) for k, v in result.items() if k.endswith("_ms")},
-            "stages_note": ("N=1: embed_ms includes the distance rows that ran beside the forward passes on a side stream; dist_ms is what was left "
-                            "(tables, centroid transpose, initial row minima)" if world == 1 and not args.embed_only and args.overlap else ""),
-            "ward": {k: v for k, v in result.items() if not k.endswith("_ms")},
-            "roofline": roof,
-            ("roofline_conv" if ward_dominates else "roofline_ward_update"): (conv_roof if ward_dominates else ward_roof),
-        }
+        out["roofline"] = roof
+        out["roofline_conv" if ward_dominates else "roofline_ward_update"] = conv_roof if ward_dominates else ward_roof
         if dist_prof and dist_prof["launches"]:
             # ComputeInitialDistanceMatrix as matrix-core lower bounds: one launch per clustering call
             i8 = ctx.last_ward_layout()[2]
@@ -503,6 +540,7 @@ def main():
                            "(bf16 ResNet embeddings) through both bound modes against oracle/ward_fast.c incl. every merge value; the fp32 embedding path on 4 images "
                            "(tolerance 1e-4 of the output scale).  The timed steps above run the bf16 embedding (configs[1]) and the same exact Ward path.")
             out["parity"] = par
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
