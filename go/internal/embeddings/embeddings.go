@@ -99,7 +99,8 @@ func GenerateEmbedding(appCtx *AppContext, imagePath string) ([]float32, error) 
 }
 
 // GetImageEmbeddingsBatch is the batched fast path workflow.createEmbeddings should call instead of one goroutine per
-// image: images are n*224*224*3 u8 RGB (already resized), the result is n x 2048 (pooled) fp32.
+// image: images are n*224*224*3 u8 RGB (already resized), the result is n x 2048 (pooled) fp32.  It uses C.ICL_PREC_BF16; a caller
+// that needs the fp32 parity bound (<= 1e-4) at a multiple of the fp32 rate passes C.ICL_PREC_BF16X3 (split bf16) instead.
 func GetImageEmbeddingsBatch(appCtx *AppContext, rgb []byte, n int) ([]float32, error) {
 	out := make([]float32, n*int(C.ICL_HEAD_POOLED))
 	if n == 0 {

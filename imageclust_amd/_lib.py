@@ -14,7 +14,7 @@ SO_PATH = os.environ.get("ICL_SO_PATH") or os.path.join(_HERE, "libimageclust_hi
 ICL_OK = 0
 ICL_ERR_ARG, ICL_ERR_CONSTRAINT, ICL_ERR_HIP, ICL_ERR_NOMODEL, ICL_ERR_IO, ICL_ERR_UNSUPPORTED, ICL_ERR_OVERSIZE, ICL_ERR_NOMEM = range(1, 9)
 HEAD_POOLED, HEAD_DENSE0 = 2048, 1000
-PREC_FP32, PREC_BF16 = 0, 1
+PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 2  # PREC_BF16X3: split bf16 (hi + lo pairs, three bf16 MFMAs per product), within the fp32 parity bound
 UPDATE_EXACT, UPDATE_LW = 0, 1
 SYNTH_NOISE, SYNTH_STRUCTURED = 0, 1
 TILES_AUTO, TILES_LOCAL, TILES_DISTRIBUTED = 0, 1, 2

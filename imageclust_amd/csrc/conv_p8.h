@@ -74,10 +74,14 @@ __device__ __forceinline__ void p8_dma(const i32x4_t &srd, const unsigned (&voff
 // and raise the tile's flag; the workgroups [tiles, 2 tiles) take the first half, wait for the flag, form own + partner -- one fixed order,
 // so the result does not depend on timing or on the batch -- and run the epilogue.  The writers have the lower block indices, i.e. all of them
 // are dispatched before any waiter: a waiter never holds a CU its writer needs.
-template <int MW, int NWV, bool TAPS, bool DUAL, bool SPLIT = false>
+// X3 (ICL_PREC_BF16X3): operands in the split bf16 layout (mfma_tile.h, BF16X3; the caller passes Cin, Cin2 and K in bf16 elements, i.e.
+// doubled), so the staging is the bf16 kernel's; fragment slot s = 0 is hi and s = 1 is lo of the same 32 k, the MFMA segment issues
+// wh.xh, wl.xh, wh.xl (24 MFMAs instead of 16, same fragments, same barriers: the LDS hazards above are unchanged), the epilogue writes hi / lo.
+template <int MW, int NWV, bool TAPS, bool DUAL, bool SPLIT = false, bool X3 = false>
 __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
 {
     static_assert(!(SPLIT && DUAL), "the split form covers single-operand layers");
+    static_assert(!(SPLIT && X3), "the split form is bf16 only");
     typedef p8_geom<MW, NWV> G;
     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
     constexpr int PX = G::PX, PW = G::PW;
@@ -200,12 +204,21 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
         __builtin_amdgcn_s_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (X3) { // (w slot, x slot) = (hi, hi), (lo, hi), (hi, lo); 8 independent accumulators between dependent MFMAs
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
+            for (int u = 0; u < 3; ++u)
 #pragma unroll
-            for (int m = 0; m < 4; ++m)
+                for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) acc[hx * 4 + m][hw * 2 + n] = mfma16(wf[n][s], xf[m][s], acc[hx * 4 + m][hw * 2 + n]);
+                    for (int n = 0; n < 2; ++n) acc[hx * 4 + m][hw * 2 + n] = mfma16(wf[n][u == 1], xf[m][u == 2], acc[hx * 4 + m][hw * 2 + n]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) acc[hx * 4 + m][hw * 2 + n] = mfma16(wf[n][s], xf[m][s], acc[hx * 4 + m][hw * 2 + n]);
+        }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
     };
@@ -317,6 +330,9 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     elem *Yg = (elem *)p.Y;
     const elem *Rg = (const elem *)p.R;
     const int cbl = (q & 1) * 16 + (q >> 1) * 8; // this lane's first channel inside a pair of accumulator tiles (32 channels)
+    // row stride and (X3) the split layout's position of channel c: hi at c + (c & ~31), lo 32 elements further
+    const int64_t yld = X3 ? 2 * (int64_t)p.Cout : (int64_t)p.Cout;
+    auto ycol = [&](int c) { return X3 ? c + (c & ~31) : c; };
     float sc[2][8], sh[2][8];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -328,8 +344,8 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     }
 #pragma unroll
     for (int hx = 0; hx < 2; ++hx) {
-        uint4 rv[4][2];
-        if (Rg) { // the 8 residual chunks of this half are requested before any arithmetic
+        uint4 rv[4][2], rl[2];
+        if (Rg && !X3) { // the 8 residual chunks of this half are requested before any arithmetic (X3: 4 per pixel row, below -- registers)
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int64_t mrow = (int64_t)m0 + wr * 128 + hx * 64 + m * 16 + l15;
@@ -341,6 +357,14 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int64_t mrow = (int64_t)m0 + wr * 128 + hx * 64 + m * 16 + l15;
+            if (X3 && Rg) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const elem *r = Rg + mrow * yld + ycol(n0 + wc * 64 + i * 32 + cbl);
+                    rv[m][i] = mrow < p.M ? *reinterpret_cast<const uint4 *>(r) : make_uint4(0, 0, 0, 0);
+                    rl[i] = mrow < p.M ? *reinterpret_cast<const uint4 *>(r + 32) : make_uint4(0, 0, 0, 0);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const f32x4 ta = acc[hx * 4 + m][2 * i], tb = acc[hx * 4 + m][2 * i + 1];
@@ -355,18 +379,34 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
                 for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[i][e] + sh[i][e];
                 if (Rg) {
                     const elem *re = reinterpret_cast<const elem *>(&rv[m][i]);
+                    if constexpr (X3) {
+                        const elem *rle = reinterpret_cast<const elem *>(&rl[i]);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += BF16::to_f(re[e]);
+                        for (int e = 0; e < 8; ++e) v[e] += BF16::to_f(re[e]) + BF16::to_f(rle[e]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] += BF16::to_f(re[e]);
+                    }
                 }
                 if (p.relu) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.0f);
                 }
-                uint4 ov;
+                uint4 ov, ol;
                 elem *oe = reinterpret_cast<elem *>(&ov);
+                if constexpr (X3) {
+                    elem *ole = reinterpret_cast<elem *>(&ol);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) oe[e] = BF16::from_f(v[e]);
-                if (mrow < p.M) *reinterpret_cast<uint4 *>(Yg + mrow * p.Cout + n0 + wc * 64 + i * 32 + cbl) = ov;
+                    for (int e = 0; e < 8; ++e) BF16X3::split(v[e], oe[e], ole[e]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) oe[e] = BF16::from_f(v[e]);
+                }
+                elem *yo = Yg + mrow * yld + ycol(n0 + wc * 64 + i * 32 + cbl);
+                if (mrow < p.M) {
+                    *reinterpret_cast<uint4 *>(yo) = ov;
+                    if (X3) *reinterpret_cast<uint4 *>(yo + 32) = ol;
+                }
             }
         }
     }
@@ -439,7 +479,7 @@ static int conv_p8_split_scratch(icl_ctx *ctx, hipStream_t strm, int tiles, conv
     return ICL_OK;
 }
 
-template <int MW, int NWV>
+template <int MW, int NWV, bool X3>
 static void launch_conv_p8_t(icl_ctx *ctx, conv_args &a)
 {
     typedef p8_geom<MW, NWV> G;
@@ -447,7 +487,7 @@ static void launch_conv_p8_t(icl_ctx *ctx, conv_args &a)
     a.gx = (int)icl_ceil_div(a.M, G::BM);
     a.gy = a.Cout / G::BN;
     const bool taps = a.KH * a.KW > 1 || a.pad != 0;
-    if constexpr (NWV == 4) {
+    if constexpr (NWV == 4 && !X3) { // (the split form is bf16 only: under BF16X3 it is ignored)
         if (conv_p8_split_eligible(ctx, a) && conv_p8_split_scratch(ctx, strm, a.gx * a.gy, a) == ICL_OK) {
             const dim3 grid2((unsigned)(2 * a.gx * a.gy));
             if (taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, true>), grid2, dim3(512), 0, strm, a);
@@ -457,12 +497,13 @@ static void launch_conv_p8_t(icl_ctx *ctx, conv_args &a)
         }
     }
     const dim3 grid((unsigned)(a.gx * a.gy));
-    if (a.X2) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, true>), grid, dim3(512), 0, strm, a);
-    else if (taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false>), grid, dim3(512), 0, strm, a);
-    else hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, false>), grid, dim3(512), 0, strm, a);
+    if (a.X2) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, true, false, X3>), grid, dim3(512), 0, strm, a);
+    else if (taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, false, X3>), grid, dim3(512), 0, strm, a);
+    else hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, false, false, X3>), grid, dim3(512), 0, strm, a);
 }
+template <bool X3 = false>
 static void launch_conv_p8(icl_ctx *ctx, conv_args &a)
 {
-    if (conv_p8_layout(a) == 1) launch_conv_p8_t<2, 4>(ctx, a);
-    else launch_conv_p8_t<4, 2>(ctx, a);
+    if (conv_p8_layout(a) == 1) launch_conv_p8_t<2, 4, X3>(ctx, a);
+    else launch_conv_p8_t<4, 2, X3>(ctx, a);
 }

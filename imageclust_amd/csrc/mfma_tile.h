@@ -44,6 +44,29 @@ struct F32 {
     }
 };
 
+// split bf16 (ICL_PREC_BF16X3): every fp32 operand v is stored as hi = bf16(v), lo = bf16(v - hi), interleaved per 32-element chunk --
+// one 128-byte LDS row / one 64-element K-step holds [hi of 32 k | lo of the same 32 k], so a tensor of C fp32 channels is a bf16 tensor of
+// 2 C "channels" and the staging (LDS-DMA, swizzle, buffer descriptors) of the bf16 kernels serves it unchanged.  Only the MFMA sweep
+// differs: slot s (hi) is paired with slot s + 4 (lo), three products wh.xh + wl.xh + wh.xl in fp32 (the dropped wl.xl and the split's
+// remainder are both <= 2^-16 of a product).  Epilogues write hi / lo of the fp32 result and read a residual as hi + lo.
+struct BF16X3 : BF16 {
+    // element offset of real channel c (c % 8 == 0: the start of a 16-byte chunk) in a pixel row of the split layout; lo = hi + 32
+    __device__ static __forceinline__ int off(int c) { return c + (c & ~31); }
+    __device__ static __forceinline__ void split(float v, uint16_t &h, uint16_t &l)
+    {
+        h = from_f(v);
+        l = from_f(v - to_f(h));
+    }
+    __device__ static __forceinline__ void mma3(const uint4 &wh, const uint4 &wl, const uint4 &xh, const uint4 &xl, f32x16 &acc)
+    {
+        mma(wh, xh, acc);
+        mma(wl, xh, acc);
+        mma(wh, xl, acc);
+    }
+};
+template <typename T> struct is_x3 { static constexpr bool value = false; };
+template <> struct is_x3<BF16X3> { static constexpr bool value = true; };
+
 #define CV_BM 128
 #define CV_ROWB 128 /* bytes per LDS row = one k-step of one tile row: 64 bf16 or 32 f32 */
 
@@ -91,6 +114,29 @@ __device__ __forceinline__ void conv_mma_kstep(const unsigned char *wsm, const u
                                                f32x16 (&acc)[BN / 64][2])
 {
     constexpr int NT = BN / 64;
+    if constexpr (is_x3<T>::value) { // 32 real k per step: slots 2s + fh (hi) and 2s + 4 + fh (lo)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            uint4 wf[NT][2], xf[2][2];
+#pragma unroll
+            for (int a = 0; a < NT; ++a) {
+                const int row = wn * (BN / 2) + a * 32 + fr;
+#pragma unroll
+                for (int l = 0; l < 2; ++l) wf[a][l] = *reinterpret_cast<const uint4 *>(wsm + row * CV_ROWB + (lds_swz(row, 2 * s + 4 * l + fh) << 4));
+            }
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int row = wm * 64 + b * 32 + fr;
+#pragma unroll
+                for (int l = 0; l < 2; ++l) xf[b][l] = *reinterpret_cast<const uint4 *>(xsm + row * CV_ROWB + (lds_swz(row, 2 * s + 4 * l + fh) << 4));
+            }
+#pragma unroll
+            for (int a = 0; a < NT; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) T::mma3(wf[a][0], wf[a][1], xf[b][0], xf[b][1], acc[a][b]);
+        }
+        return;
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         uint4 wf[NT], xf[2];

@@ -64,7 +64,13 @@ template <typename T, int BN>
 struct conv_resid {
     static constexpr int NPASS = 64 / (256 / (BN / T::KE));
     uint4 v[2][NPASS];
+    uint4 lo[is_x3<T>::value ? 2 : 1][is_x3<T>::value ? NPASS : 1]; // BF16X3: the lo halves
 };
+// a tensor's row stride and the element offset of real channel c in a row: the split bf16 layout (BF16X3) holds 2 elements per channel
+template <typename T>
+__device__ __forceinline__ int64_t act_ld(int C) { return is_x3<T>::value ? 2 * (int64_t)C : (int64_t)C; }
+template <typename T>
+__device__ __forceinline__ int act_off(int c) { return is_x3<T>::value ? c + (c & ~31) : c; }
 template <typename T, int BN, bool FULL>
 __device__ __forceinline__ void conv_resid_load(const conv_args &p, conv_resid<T, BN> &r, int64_t m0, int n0, int tid)
 {
@@ -72,21 +78,27 @@ __device__ __forceinline__ void conv_resid_load(const conv_args &p, conv_resid<T
     constexpr int CPR = BN / T::KE, RPP = 256 / CPR, NPASS = 64 / RPP;
     const elem *Rg = (const elem *)p.R;
     const int nl = (tid % CPR) * T::KE;
+    constexpr bool X3 = is_x3<T>::value;
     if (!Rg) {
 #pragma unroll
         for (int half = 0; half < 2; ++half)
 #pragma unroll
-            for (int i = 0; i < NPASS; ++i) r.v[half][i] = make_uint4(0, 0, 0, 0);
+            for (int i = 0; i < NPASS; ++i) {
+                r.v[half][i] = make_uint4(0, 0, 0, 0);
+                if (X3) r.lo[X3 ? half : 0][X3 ? i : 0] = make_uint4(0, 0, 0, 0);
+            }
         return;
     }
-    const elem *r0 = Rg + (m0 + tid / CPR) * p.Cout + n0 + nl; // one 64-bit row address, then uniform strides
-    const int64_t pstride = (int64_t)RPP * p.Cout;
+    const elem *r0 = Rg + (m0 + tid / CPR) * act_ld<T>(p.Cout) + act_off<T>(n0 + nl); // one 64-bit row address, then uniform strides
+    const int64_t pstride = (int64_t)RPP * act_ld<T>(p.Cout);
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
             const int64_t m = m0 + half * 64 + tid / CPR + i * RPP;
-            r.v[half][i] = (FULL || m < p.M) ? *reinterpret_cast<const uint4 *>(r0 + (half * NPASS + i) * pstride) : make_uint4(0, 0, 0, 0);
+            const bool in = FULL || m < p.M;
+            r.v[half][i] = in ? *reinterpret_cast<const uint4 *>(r0 + (half * NPASS + i) * pstride) : make_uint4(0, 0, 0, 0);
+            if (X3) r.lo[X3 ? half : 0][X3 ? i : 0] = in ? *reinterpret_cast<const uint4 *>(r0 + (half * NPASS + i) * pstride + 32) : make_uint4(0, 0, 0, 0);
         }
 }
 
@@ -106,7 +118,10 @@ __device__ __forceinline__ void conv_epilogue(const conv_args &p, unsigned char 
     constexpr int RPP = 256 / CPR;    // tile rows covered per pass
     constexpr int NPASS = 64 / RPP;   // passes per 64-row half tile
     const int nl = (tid % CPR) * T::KE;
-    elem *Yfull = Yg + (m0 + tid / CPR) * p.Cout + n0 + nl;
+    constexpr bool X3 = is_x3<T>::value;
+    const int64_t yld = act_ld<T>(p.Cout);
+    const int ycol = act_off<T>(n0 + nl);
+    elem *Yfull = Yg + (m0 + tid / CPR) * yld + ycol;
     float sc[T::KE], sh[T::KE];
 #pragma unroll
     for (int q = 0; q < T::KE; q += 4) {
@@ -120,15 +135,19 @@ __device__ __forceinline__ void conv_epilogue(const conv_args &p, unsigned char 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         // all residual loads of the lane for this half are issued before any arithmetic
-        uint4 rv[NPASS];
+        uint4 rv[NPASS], rl[X3 ? NPASS : 1];
         if (PRE) {
 #pragma unroll
-            for (int i = 0; i < NPASS; ++i) rv[i] = pre.v[half][i];
+            for (int i = 0; i < NPASS; ++i) {
+                rv[i] = pre.v[half][i];
+                if (X3) rl[X3 ? i : 0] = pre.lo[X3 ? half : 0][X3 ? i : 0];
+            }
         } else if (Rg) {
 #pragma unroll
             for (int i = 0; i < NPASS; ++i) {
                 const int64_t m = row_m(half * 64 + tid / CPR + i * RPP);
-                rv[i] = m < p.M ? *reinterpret_cast<const uint4 *>(Rg + m * p.Cout + n0 + nl) : make_uint4(0, 0, 0, 0);
+                rv[i] = m < p.M ? *reinterpret_cast<const uint4 *>(Rg + m * yld + ycol) : make_uint4(0, 0, 0, 0);
+                if (X3) rl[X3 ? i : 0] = m < p.M ? *reinterpret_cast<const uint4 *>(Rg + m * yld + ycol + 32) : make_uint4(0, 0, 0, 0);
             }
         }
         if (half) __syncthreads(); // everybody finished reading the first half
@@ -163,21 +182,33 @@ __device__ __forceinline__ void conv_epilogue(const conv_args &p, unsigned char 
             }
             if (Rg) {
                 const elem *re = reinterpret_cast<const elem *>(&rv[i]);
+                if constexpr (X3) {
+                    const elem *rle = reinterpret_cast<const elem *>(&rl[i]);
 #pragma unroll
-                for (int q = 0; q < T::KE; ++q) v[q] += T::to_f(re[q]);
+                    for (int q = 0; q < T::KE; ++q) v[q] += T::to_f(re[q]) + T::to_f(rle[q]);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < T::KE; ++q) v[q] += T::to_f(re[q]);
+                }
             }
             if (p.relu) {
 #pragma unroll
                 for (int q = 0; q < T::KE; ++q) v[q] = fmaxf(v[q], 0.0f);
             }
-            uint4 ov;
+            uint4 ov, ol;
             elem *oe = reinterpret_cast<elem *>(&ov);
+            if constexpr (X3) {
+                elem *ole = reinterpret_cast<elem *>(&ol);
 #pragma unroll
-            for (int q = 0; q < T::KE; ++q) oe[q] = T::from_f(v[q]);
-            if (FULL && !TILE2D) // whole tile inside M: one 64-bit row address, then uniform strides
-                *reinterpret_cast<uint4 *>(Yfull + (int64_t)(half * NPASS + i) * ((int64_t)RPP * p.Cout)) = ov;
-            else
-                *reinterpret_cast<uint4 *>(Yg + m * p.Cout + n0 + nl) = ov;
+                for (int q = 0; q < T::KE; ++q) T::split(v[q], oe[q], ole[q]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < T::KE; ++q) oe[q] = T::from_f(v[q]);
+            }
+            elem *yo = (FULL && !TILE2D) ? Yfull + (int64_t)(half * NPASS + i) * ((int64_t)RPP * yld) // whole tile inside M: one 64-bit row address, then uniform strides
+                                         : Yg + m * yld + ycol;
+            *reinterpret_cast<uint4 *>(yo) = ov;
+            if (X3) *reinterpret_cast<uint4 *>(yo + 32) = ol;
         }
     }
 }
@@ -441,6 +472,28 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const conv_args p, in
             __syncthreads(); // ... and are visible to every wave; the weight buffer read at step ks-1 is free
             if (ks + AHEAD < nk) stage_w(kof(ks + AHEAD), (ks + AHEAD) % HALO_WS);
             const unsigned char *wsm = smem + halo_bytes + 512 + (ks % HALO_WS) * WST;
+            if constexpr (is_x3<T>::value) { // split bf16: slot 2s + fh (hi) with slot 2s + 4 + fh (lo), three products (mfma_tile.h)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    uint4 wf[NT][2], xf[2][2];
+#pragma unroll
+                    for (int a = 0; a < NT; ++a) {
+                        const int row = wn * (BN / 2) + a * 32 + fr;
+#pragma unroll
+                        for (int l = 0; l < 2; ++l) wf[a][l] = *reinterpret_cast<const uint4 *>(wsm + row * CV_ROWB + (lds_swz(row, 2 * s + 4 * l + fh) << 4));
+                    }
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const int px = abase[b][kh] + kw;
+#pragma unroll
+                        for (int l = 0; l < 2; ++l) xf[b][l] = *reinterpret_cast<const uint4 *>(smem + px * CV_ROWB + (lds_swz(px, 2 * s + 4 * l + fh) << 4));
+                    }
+#pragma unroll
+                    for (int a = 0; a < NT; ++a)
+#pragma unroll
+                        for (int b = 0; b < 2; ++b) T::mma3(wf[a][0], wf[a][1], xf[b][0], xf[b][1], acc[a][b]);
+                }
+            } else
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 uint4 wf[NT], xf[2];
@@ -688,7 +741,12 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const typename T::elem *__
         const int c = (int)(t % C);
         const int64_t b = t / C;
         float s = 0.0f;
-        for (int i = 0; i < HW; ++i) s += T::to_f(in[(b * HW + i) * C + c]);
+        if constexpr (is_x3<T>::value) { // split bf16: hi + lo of every position
+            const typename T::elem *q = in + b * HW * 2 * C + c + (c & ~31);
+            for (int i = 0; i < HW; ++i) s += T::to_f(q[(int64_t)i * 2 * C]) + T::to_f(q[(int64_t)i * 2 * C + 32]);
+        } else {
+            for (int i = 0; i < HW; ++i) s += T::to_f(in[(b * HW + i) * C + c]);
+        }
         out[b * out_ld + c] = s / (float)HW;
     }
 }
@@ -721,10 +779,10 @@ __global__ __launch_bounds__(256) void fc_kernel(const float *__restrict__ x, co
 struct conv_layer {
     icl_conv_rec rec;
     int K = 0, cin_eff = 0; // cin_eff: channel count seen by the kernel (160 for the lowered stem)
-    void *w[2] = {nullptr, nullptr}; // [ICL_PREC_FP32], [ICL_PREC_BF16]
+    void *w[3] = {nullptr, nullptr, nullptr}; // [ICL_PREC_FP32], [ICL_PREC_BF16], [ICL_PREC_BF16X3] (split layout: host_split32)
     float *scale = nullptr, *shift = nullptr;
     // block-0 c3 only: [Cout][mid + cin] = [W3*scale3 | Wds*scale_ds] and shift3 + shift_ds (downsample fused in)
-    void *wfused[2] = {nullptr, nullptr};
+    void *wfused[3] = {nullptr, nullptr, nullptr};
     float *shift_fused = nullptr;
     // stage 1 only (bneck56_kernel): bf16(W * scale), the BatchNorm scale folded into the weights before rounding
     void *wfold = nullptr;
@@ -850,7 +908,7 @@ void icl_model_free(icl_ctx *ctx)
     icl_model *m = ctx->model;
     if (!m) return;
     for (auto &c : m->conv) {
-        for (void *p : {c.w[0], c.w[1], (void *)c.scale, (void *)c.shift, c.wfused[0], c.wfused[1], (void *)c.shift_fused, c.wfold})
+        for (void *p : {c.w[0], c.w[1], c.w[2], (void *)c.scale, (void *)c.shift, c.wfused[0], c.wfused[1], c.wfused[2], (void *)c.shift_fused, c.wfold})
             if (p) (void)hipFree(p);
     }
     for (void *p : {(void *)m->fcw, (void *)m->fcb, m->zero, (void *)m->ones})
@@ -864,6 +922,20 @@ void icl_model_free(icl_ctx *ctx)
     }
     delete m;
     ctx->model = nullptr;
+}
+
+// The split bf16 layout of ICL_PREC_BF16X3 (mfma_tile.h, BF16X3): every run of 32 consecutive fp32 values v (a channel chunk of a pixel, or
+// 32 k of a weight row: rows are whole chunks) becomes 64 bf16, [hi = bf16(v) of the 32 | lo = bf16(v - hi) of the same 32].  n % 32 == 0.
+static void host_split32(const float *src, size_t n, uint16_t *dst)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const uint16_t h = host_bf16(src[i]);
+        uint32_t u = (uint32_t)h << 16;
+        float hf;
+        memcpy(&hf, &u, 4);
+        dst[(i & ~(size_t)31) * 2 + (i & 31)] = h;
+        dst[(i & ~(size_t)31) * 2 + 32 + (i & 31)] = host_bf16(src[i] - hf);
+    }
 }
 
 static int upload(icl_ctx *ctx, void **dst, const void *src, size_t bytes)
@@ -925,6 +997,11 @@ extern "C" int icl_model_load_blob(icl_ctx *ctx, const void *blob, int64_t bytes
         for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e]);
         ICL_TRY(upload(ctx, &L.w[ICL_PREC_FP32], wf.data(), wf.size() * 4));
         ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16], wb.data(), wb.size() * 2));
+        if (i > 0) { // (the BF16X3 stem runs in fp32: ICL_PREC_FP32 weights)
+            wb.resize(2 * wf.size());
+            host_split32(wf.data(), wf.size(), wb.data());
+            ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
+        }
         // BatchNormalization folded to y = x*scale + shift, conv bias folded into shift
         sc.resize(cout);
         sh.resize(cout);
@@ -971,6 +1048,9 @@ extern "C" int icl_model_load_blob(icl_ctx *ctx, const void *blob, int64_t bytes
         conv_layer &L = m->conv[i];
         ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_FP32], wf.data(), wf.size() * 4));
         ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16], wb.data(), wb.size() * 2));
+        wb.resize(2 * wf.size());
+        host_split32(wf.data(), wf.size(), wb.data());
+        ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
         ICL_TRY(upload(ctx, (void **)&L.shift_fused, sh.data(), (size_t)cout * 4));
     }
     {
@@ -1060,9 +1140,19 @@ static void launch_conv_variant(icl_ctx *ctx, conv_args &a, int nst_lds)
 // plain two-stage loop (one k-step staged ahead) for A/B comparisons.  Deeper rings (three / four stages, one workgroup
 // per CU), 128x64 tiles for the 128-wide layers, weights in registers and dedicated loader waves were all measured
 // slower.
+// BF16X3: a is given in real channels; the kernels see the split layout as bf16 tensors of twice the channels (Cin, Cin2 and K doubled,
+// Cout -- the rows of the weights and of the accumulator tile -- unchanged).  Every layer goes to conv_p8_kernel or the 128 x 128 kernels,
+// chosen by shape as for bf16; conv_wr_kernel has no split form ("Split bf16").
 template <typename T>
 static int launch_conv_t(icl_ctx *ctx, conv_args a)
 {
+    constexpr bool X3 = is_x3<T>::value;
+    const double flops = 2.0 * (double)a.M * a.Cout * a.K;
+    if (X3) {
+        a.Cin *= 2;
+        a.Cin2 *= 2;
+        a.K *= 2;
+    }
     a.gx = (int)icl_ceil_div(a.M, CV_BM);
     const int nk = a.K / T::BK;
     static const int mode = [] { // ICL_CONV_MODE (A/B measurements): 0 = plain two-stage loop, 2 = no halo kernel for the 3x3 layers
@@ -1071,7 +1161,7 @@ static int launch_conv_t(icl_ctx *ctx, conv_args a)
     }();
     const bool early = mode != 0;
     const bool wide = a.Cout % 128 == 0;
-    icl_prof_scope ps(ctx, wide ? ICL_K_CONV : ICL_K_CONV64, 2.0 * (double)a.M * a.Cout * a.K, 0.0);
+    icl_prof_scope ps(ctx, wide ? ICL_K_CONV : ICL_K_CONV64, flops, 0.0);
     // the HBM-bound c3 layers of the identity bottlenecks: weights in registers, streaming tiles (conv_wr.h)
     if (std::is_same<T, BF16>::value && ctx->conv_wr && conv_wr_eligible(a, ctx->conv_p8)) {
         launch_conv_wr(ctx, a);
@@ -1080,8 +1170,8 @@ static int launch_conv_t(icl_ctx *ctx, conv_args a)
         return ICL_OK;
     }
     // the K-heavy layers: 256 x 256 tiles on the deep-pipelined loop (conv_p8.h)
-    if (std::is_same<T, BF16>::value && conv_p8_eligible(a, ctx->conv_p8)) {
-        launch_conv_p8(ctx, a);
+    if ((std::is_same<T, BF16>::value || X3) && conv_p8_eligible(a, ctx->conv_p8)) {
+        launch_conv_p8<X3>(ctx, a);
         ++ctx->conv_launches[0];
         ICL_HIP(ctx, hipGetLastError());
         return ICL_OK;
@@ -1113,6 +1203,12 @@ static int launch_conv_t(icl_ctx *ctx, conv_args a)
     return ICL_OK;
 }
 
+static int launch_conv_prec(icl_ctx *ctx, int prec, const conv_args &a)
+{
+    return prec == ICL_PREC_BF16 ? launch_conv_t<BF16>(ctx, a) : prec == ICL_PREC_BF16X3 ? launch_conv_t<BF16X3>(ctx, a) : launch_conv_t<F32>(ctx, a);
+}
+static bool prec_ok(int prec) { return prec == ICL_PREC_FP32 || prec == ICL_PREC_BF16 || prec == ICL_PREC_BF16X3; }
+
 static int launch_conv(icl_ctx *ctx, int prec, const conv_layer &L, const void *X, void *Y, const void *R, int relu, int B)
 {
     conv_args a;
@@ -1136,11 +1232,11 @@ static int launch_conv(icl_ctx *ctx, int prec, const conv_layer &L, const void *
     a.pad = L.rec.pad;
     a.M = (int64_t)B * a.Ho * a.Wo;
     a.K = a.KH * a.KW * a.Cin;
-    const int bk = prec == ICL_PREC_BF16 ? BF16::BK : F32::BK;
+    const int bk = prec == ICL_PREC_BF16 ? BF16::BK : F32::BK; // (BF16X3: 32 real channels per k-step, as F32)
     if (a.M >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv: %lld output pixels exceed the kernel's 32-bit pixel index", (long long)a.M);
     if (a.Cin % bk || a.Cout % 64 || a.K != L.K)
         return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv shape cin=%d cout=%d k=%d not supported by the implicit-GEMM kernel", a.Cin, a.Cout, a.KH);
-    return prec == ICL_PREC_BF16 ? launch_conv_t<BF16>(ctx, a) : launch_conv_t<F32>(ctx, a);
+    return launch_conv_prec(ctx, prec, a);
 }
 
 static inline float host_from_bf16(uint16_t v)
@@ -1150,13 +1246,21 @@ static inline float host_from_bf16(uint16_t v)
     memcpy(&f, &u, 4);
     return f;
 }
+// host_split32 undone: dst[i] = hi + lo in fp32
+static void host_join32(const uint16_t *src, size_t n, float *dst)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const size_t j = (i & ~(size_t)31) * 2 + (i & 31);
+        dst[i] = host_from_bf16(src[j]) + host_from_bf16(src[j + 32]);
+    }
+}
 
 extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int Cin, const float *w, int Cout, int k,
                                 int stride, int pad, const float *scale, const float *shift, const float *residual, int relu, float *y)
 {
     if (!ctx || !x || !w || !scale || !shift || !y || B < 1 || H < 1 || k < 1 || stride < 1 || pad < 0)
         return icl_fail(ctx, ICL_ERR_ARG, "icl_conv2d_fused: bad argument");
-    if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
+    if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
     if (Cin % 64 || Cout % 64) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_fused needs Cin %% 64 == 0 and Cout %% 64 == 0");
     const int Ho = (H + 2 * pad - k) / stride + 1;
     if (Ho < 1) return icl_fail(ctx, ICL_ERR_ARG, "empty output");
@@ -1175,6 +1279,10 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
             std::vector<uint16_t> t(n);
             for (size_t i = 0; i < n; ++i) t[i] = host_bf16(src[i]);
             ICL_HIP(ctx, hipMemcpy(*dst, t.data(), n * 2, hipMemcpyHostToDevice));
+        } else if (prec == ICL_PREC_BF16X3) { // hi / lo pairs: the same bytes as fp32
+            std::vector<uint16_t> t(2 * n);
+            host_split32(src, n, t.data());
+            ICL_HIP(ctx, hipMemcpy(*dst, t.data(), n * 4, hipMemcpyHostToDevice));
         } else {
             ICL_HIP(ctx, hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
         }
@@ -1195,7 +1303,7 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
         a.X2 = nullptr; a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
         a.B = B; a.H = a.W = H; a.Cin = Cin; a.Ho = a.Wo = Ho; a.Cout = Cout; a.KH = a.KW = k; a.stride = stride; a.pad = pad;
         a.relu = relu; a.M = (int64_t)B * Ho * Ho; a.K = k * k * Cin;
-        rc = prec == ICL_PREC_BF16 ? launch_conv_t<BF16>(ctx, a) : launch_conv_t<F32>(ctx, a);
+        rc = launch_conv_prec(ctx, prec, a);
     }
     if (!rc) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -1204,6 +1312,10 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
                 std::vector<uint16_t> t(ny);
                 e = hipMemcpy(t.data(), dy, ny * 2, hipMemcpyDeviceToHost);
                 for (size_t i = 0; i < ny; ++i) y[i] = host_from_bf16(t[i]);
+            } else if (prec == ICL_PREC_BF16X3) {
+                std::vector<uint16_t> t(2 * ny);
+                e = hipMemcpy(t.data(), dy, ny * 4, hipMemcpyDeviceToHost);
+                host_join32(t.data(), ny, y);
             } else {
                 e = hipMemcpy(y, dy, ny * 4, hipMemcpyDeviceToHost);
             }
@@ -1244,7 +1356,7 @@ static int launch_conv_fused_ds(icl_ctx *ctx, int prec, const conv_layer &c3, co
     a.K = a.Cin + a.Cin2;
     const int bk = prec == ICL_PREC_BF16 ? BF16::BK : F32::BK;
     if (a.Cin % bk || a.Cin2 % bk || a.Cout % 128) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused downsample shape not supported");
-    return prec == ICL_PREC_BF16 ? launch_conv_t<BF16>(ctx, a) : launch_conv_t<F32>(ctx, a);
+    return launch_conv_prec(ctx, prec, a);
 }
 
 // ICL_FUSE (A/B measurements and the fused == unfused tests): bit 0 stem + maxpool in one launch, bit 1 the identity
@@ -1272,18 +1384,21 @@ static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B
         hipLaunchKernelGGL(stem2_pool_kernel, dim3(grid), dim3(256), stem2_lds_bytes(), strm, d_img, (const uint16_t *)L0.wfold, L0.shift, (uint16_t *)pooled, nunits);
         return;
     }
-    icl_lds_optin(ctx, (const void *)stem_pool_kernel<T>, (int)stem_pool_lds_bytes<T>());
+    // BF16X3: the f32 stem (236 MFLOP per image), its pooled output written in the split layout
+    constexpr bool SPLIT = is_x3<T>::value;
+    typedef typename std::conditional<SPLIT, F32, T>::type TS;
+    icl_lds_optin(ctx, (const void *)stem_pool_kernel<TS, SPLIT>, (int)stem_pool_lds_bytes<TS>());
     conv_args a;
     const conv_layer &L = m->conv[0];
-    a.X = nullptr; a.Wt = L.w[prec]; a.Y = pooled; a.R = nullptr; a.scale = L.scale; a.shift = L.shift; a.zero = m->zero;
+    a.X = nullptr; a.Wt = L.w[SPLIT ? ICL_PREC_FP32 : prec]; a.Y = pooled; a.R = nullptr; a.scale = L.scale; a.shift = L.shift; a.zero = m->zero;
     a.B = B; a.H = a.W = 224; a.Cin = 3; a.Ho = a.Wo = 112; a.Cout = 64; a.KH = a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
     a.M = (int64_t)B * 112 * 112; a.K = STEM_K; a.gx = B * SP_STRIPS * SP_TILES; a.gy = 1;
     a.X2 = nullptr; a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
     icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
     const int nunits = B * SP_STRIPS;
-    const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_pool_lds_bytes<T>()));
+    const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_pool_lds_bytes<TS>()));
     const unsigned grid = (unsigned)std::min<int64_t>(nunits, (int64_t)per_cu * ctx->prop.multiProcessorCount);
-    hipLaunchKernelGGL((stem_pool_kernel<T>), dim3(grid), dim3(256), stem_pool_lds_bytes<T>(), strm, d_img, a, nunits);
+    hipLaunchKernelGGL((stem_pool_kernel<TS, SPLIT>), dim3(grid), dim3(256), stem_pool_lds_bytes<TS>(), strm, d_img, a, nunits);
 }
 
 // One stage-1 bottleneck in one launch (bf16): c1 -> c2 -> c3 (+ residual x | + downsample branch ds) + ReLU.
@@ -1345,9 +1460,9 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
     const int grid = 256 * 8;
     elem *x = (elem *)m->buf[lane][0], *t1 = (elem *)m->buf[lane][1], *t2 = (elem *)m->buf[lane][2], *ds = (elem *)m->buf[lane][3],
          *y = (elem *)m->buf[lane][4];
-    if (fuse_mask() & 1) {
+    if ((fuse_mask() & 1) || is_x3<T>::value) { // (BF16X3 has the fused stem only)
         launch_stem_pool<T>(ctx, prec, d_img, B, x, strm); // conv0 + BN + ReLU + maxpool: the 112x112 tensor stays on the CU
-    } else {
+    } else if constexpr (!is_x3<T>::value) {
         {
             icl_lds_optin(ctx, (const void *)stem_conv_kernel<T>, (int)stem_lds_bytes<T>());
             conv_args a;
@@ -1387,7 +1502,7 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
     }
     float *pooled = head == ICL_HEAD_POOLED ? d_out : m->pooled[lane];
     {
-        icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * 49.0 * 2048.0 * sizeof(elem));
+        icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * 49.0 * 2048.0 * (is_x3<T>::value ? 4 : sizeof(elem)));
         hipLaunchKernelGGL((avgpool_kernel<T>), dim3((unsigned)icl_ceil_div((int64_t)B * 2048, 256)), dim3(256), 0, strm, x, B, 49,
                            ICL_FEAT_DIM, pooled, (int64_t)ICL_FEAT_DIM);
     }
@@ -1405,7 +1520,7 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
 extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, float *out)
 {
     if (!ctx || !img || !out || B < 1) return icl_fail(ctx, ICL_ERR_ARG, "icl_stem_pool: bad argument");
-    if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
+    if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
     return no_throw(ctx, "icl_stem_pool", [&]() -> int {
         std::lock_guard<std::mutex> lk(ctx->mu);
         icl_device_guard g(ctx->device);
@@ -1419,6 +1534,7 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
         if (!rc && hipMemcpy(dimg, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) rc = icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
         if (!rc) {
             if (prec == ICL_PREC_BF16) launch_stem_pool<BF16>(ctx, prec, dimg, B, dy, ctx->stream);
+            else if (prec == ICL_PREC_BF16X3) launch_stem_pool<BF16X3>(ctx, prec, dimg, B, dy, ctx->stream);
             else launch_stem_pool<F32>(ctx, prec, dimg, B, dy, ctx->stream);
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1427,6 +1543,10 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
                     std::vector<uint16_t> t(ny);
                     e = hipMemcpy(t.data(), dy, ny * 2, hipMemcpyDeviceToHost);
                     for (size_t i = 0; i < ny; ++i) out[i] = host_from_bf16(t[i]);
+                } else if (prec == ICL_PREC_BF16X3) {
+                    std::vector<uint16_t> t(2 * ny);
+                    e = hipMemcpy(t.data(), dy, ny * 4, hipMemcpyDeviceToHost);
+                    host_join32(t.data(), ny, out);
                 } else {
                     e = hipMemcpy(out, dy, ny * 4, hipMemcpyDeviceToHost);
                 }
@@ -1522,7 +1642,7 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
 {
     if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
     if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
-    if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16) return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32 or ICL_PREC_BF16");
+    if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32, ICL_PREC_BF16 or ICL_PREC_BF16X3");
     if (n == 0) return ICL_OK;
     const int batch = (int)std::min<int64_t>(ctx->batch, n);
     // Two forward passes in flight on two streams (each its own activation workspace): batches stay at the configured
@@ -1564,6 +1684,7 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
         if (ev) ICL_HIP(ctx, hipEventSynchronize(ev)); // batch bi-DEPTH has finished
         else ICL_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         const int rc = prec == ICL_PREC_BF16 ? forward_batch<BF16>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm)
+                     : prec == ICL_PREC_BF16X3 ? forward_batch<BF16X3>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm)
                                              : forward_batch<F32>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm);
         if (rc) return rc;
         ICL_HIP(ctx, hipEventRecord(ev, strm));
@@ -1933,7 +2054,7 @@ extern "C" int icl_set_file_options(icl_ctx *ctx, int prec, int window_us, int m
 {
     const bool fail_next = (prec & ICL_FILE_FAIL_NEXT_LEADER) != 0;
     prec &= ~ICL_FILE_FAIL_NEXT_LEADER;
-    if (!ctx || (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16) || window_us < 0 || max_batch < 1 || max_batch > 4096)
+    if (!ctx || !prec_ok(prec) || window_us < 0 || max_batch < 1 || max_batch > 4096)
         return icl_fail(ctx, ICL_ERR_ARG, "icl_set_file_options: bad argument");
     icl_file_batcher *b = file_batcher(ctx);
     std::lock_guard<std::mutex> lk(b->m);

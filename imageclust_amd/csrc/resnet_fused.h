@@ -89,7 +89,8 @@ static constexpr size_t stem_pool_lds_bytes()
            2 * 16 * 64 * sizeof(typename T::elem);
 }
 
-template <typename T>
+// SPLIT (ICL_PREC_BF16X3, T = F32): the f32 stem, its pooled output written in the split bf16 layout (mfma_tile.h, BF16X3)
+template <typename T, bool SPLIT = false>
 __global__ __launch_bounds__(256) void stem_pool_kernel(const uint8_t *__restrict__ img, const conv_args p, int nunits)
 {
     typedef typename T::elem elem;
@@ -290,10 +291,22 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const uint8_t *__restric
                         }
                     }
                 }
-                elem o[T::KE];
+                const int64_t opix = (b * 56 + 4 * t + pr) * 56 + 7 * s + pc;
+                if constexpr (SPLIT) {
+                    static_assert(T::KE == 4, "4 fp32 channels per lane");
+                    uint16_t oh[4], ol[4];
 #pragma unroll
-                for (int e = 0; e < T::KE; ++e) o[e] = T::from_f(best[e]);
-                *reinterpret_cast<uint4 *>(Yg + ((b * 56 + 4 * t + pr) * 56 + 7 * s + pc) * 64 + ch * T::KE) = *reinterpret_cast<const uint4 *>(o);
+                    for (int e = 0; e < 4; ++e) BF16X3::split(best[e], oh[e], ol[e]);
+                    const int c = ch * 4;
+                    uint16_t *yo = reinterpret_cast<uint16_t *>(p.Y) + opix * 128 + c + (c & ~31);
+                    *reinterpret_cast<uint2 *>(yo) = *reinterpret_cast<const uint2 *>(oh);
+                    *reinterpret_cast<uint2 *>(yo + 32) = *reinterpret_cast<const uint2 *>(ol);
+                } else {
+                    elem o[T::KE];
+#pragma unroll
+                    for (int e = 0; e < T::KE; ++e) o[e] = T::from_f(best[e]);
+                    *reinterpret_cast<uint4 *>(Yg + opix * 64 + ch * T::KE) = *reinterpret_cast<const uint4 *>(o);
+                }
             }
         }
         if (!has_next) break;

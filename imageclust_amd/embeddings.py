@@ -107,7 +107,10 @@ GenerateEmbedding = GetImageEmbedding  # the name BASELINE.json's north_star use
 
 
 def GetImageEmbeddingsBatch(appCtx: AppContext, images_u8: np.ndarray, prec: int = _lib.PREC_BF16) -> np.ndarray:
-    """Batched fast path behind the same Net: n x 224 x 224 x 3 u8 RGB -> n x Head fp32."""
+    """Batched fast path behind the same Net: n x 224 x 224 x 3 u8 RGB -> n x Head fp32.
+
+    prec: _lib.PREC_BF16 (default; fastest, ~4e-3 relative L2 from fp32), _lib.PREC_BF16X3 (split bf16: three bf16 MFMAs per product,
+    within the 1e-4 fp32 parity bound at a multiple of the fp32 rate) or _lib.PREC_FP32 (f32 MFMA, the reference's arithmetic)."""
     return appCtx.Net.ctx.embed_u8(images_u8, appCtx.Head, prec)
 
 

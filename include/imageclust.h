@@ -39,8 +39,12 @@ enum {
 
 enum { ICL_HEAD_POOLED = 2048, /* global-average-pool vector (north_star) */
        ICL_HEAD_DENSE0 = 1000  /* "resnetv17_dense0_fwd" (embeddings.go:140) */ };
-enum { ICL_PREC_FP32 = 0, /* f32 MFMA, parity mode (<=1e-4 vs the fp32 restatement) */
-       ICL_PREC_BF16 = 1  /* bf16 MFMA with fp32 accumulate, throughput mode */ };
+enum { ICL_PREC_FP32 = 0,  /* f32 MFMA, parity mode (<=1e-4 vs the fp32 restatement) */
+       ICL_PREC_BF16 = 1,  /* bf16 MFMA with fp32 accumulate, throughput mode */
+       ICL_PREC_BF16X3 = 2 /* split bf16: operands as hi + lo bf16 pairs, three bf16 MFMAs per product (wh.xh + wl.xh + wh.xl) with fp32
+                              accumulate; meets the parity bound (<=1e-4 vs the fp32 restatement; ~7e-6 measured).  33.1k img/s at batch 256,
+                              2.2x ICL_PREC_FP32 (profiles/r06_embed_prec_rate.json).
+                              Holds a third copy of the conv weights (~100 MB more device memory per context); ignores ICL_CONV_SPLIT */ };
 enum { ICL_UPDATE_EXACT = 0, /* centroid recompute, bit-identical to clustering.go:76-96 */
        ICL_UPDATE_LW = 1     /* MFMA distance tile + Lance-Williams rows: fast, NOT bit-identical */ };
 enum { ICL_SYNTH_NOISE = 0, ICL_SYNTH_STRUCTURED = 1 };
@@ -85,7 +89,7 @@ int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *out);
 /* icl_embed_file is what GetImageEmbedding(appCtx, path) binds to, and workflow.go:156-175 calls that from one goroutine per
  * image.  Concurrent callers are coalesced: each decodes / resizes its own file, then one forward pass serves everything
  * that queued up within window_us (or max_batch images).  prec selects ICL_PREC_FP32 (default: rows equal the one-at-a-time
- * result bit for bit) or ICL_PREC_BF16.  window_us = 0 disables waiting (a lone caller runs at once).
+ * result bit for bit), ICL_PREC_BF16X3 or ICL_PREC_BF16.  window_us = 0 disables waiting (a lone caller runs at once).
  * prec | ICL_FILE_FAIL_NEXT_LEADER: the next batch leader fails with ICL_ERR_NOMEM right after it has taken its queued requests --
  * every caller of that batch gets the error, nobody is left waiting (the recovery path of the queue, exercised by the test suite). */
 enum { ICL_FILE_FAIL_NEXT_LEADER = 0x100 };
@@ -126,7 +130,7 @@ int icl_conv_stats(icl_ctx *ctx, int64_t *p8_launches, int64_t *other_launches);
 /* One fused convolution layer of the engine (the unit every ResNet50 conv is lowered to), host buffers:
  * y = relu?( conv(x, w) * scale[c] + shift[c] (+ residual) ).  x: [B][H][H][Cin] NHWC fp32, w: [Cout][Cin][k][k]
  * (OIHW, as in the ONNX initializer), residual / y: [B][Ho][Ho][Cout] NHWC fp32.  Needs Cin % 64 == 0 and
- * Cout % 64 == 0.  Operands are rounded to bf16 when prec == ICL_PREC_BF16. */
+ * Cout % 64 == 0.  Operands are rounded to bf16 when prec == ICL_PREC_BF16, split into hi + lo bf16 pairs when prec == ICL_PREC_BF16X3. */
 int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int Cin, const float *w, int Cout, int k,
                      int stride, int pad, const float *scale, const float *shift, const float *residual, int relu,
                      float *y);
