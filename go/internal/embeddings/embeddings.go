@@ -112,3 +112,48 @@ func GetImageEmbeddingsBatch(appCtx *AppContext, rgb []byte, n int) ([]float32, 
 	}
 	return out, nil
 }
+
+// GetImageEmbeddings embeds a list of image files in one call (icl_embed_files): the per-file loop of workflow.go:149-185
+// without one goroutine per file.  Row i belongs to paths[i] (head ICL_HEAD_DENSE0, prec ICL_PREC_FP32: the values
+// GetImageEmbedding returns); errs[i] is nil or the error of file i, whose row is nil.  threads 0: up to 16 host decode threads.
+func GetImageEmbeddings(appCtx *AppContext, paths []string) ([][]float32, []error) {
+	n := len(paths)
+	rows, errs := make([][]float32, n), make([]error, n)
+	if n == 0 {
+		return rows, errs
+	}
+	cpaths := make([]*C.char, n)
+	for i, p := range paths {
+		cpaths[i] = C.CString(p)
+		defer C.free(unsafe.Pointer(cpaths[i]))
+	}
+	cpathv := (**C.char)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(cpathv))
+	copy(unsafe.Slice(cpathv, n), cpaths)
+	head := int(C.ICL_HEAD_DENSE0)
+	out := make([]float32, n*head)
+	status := make([]C.int32_t, n)
+	rc := C.icl_embed_files(appCtx.Net.ctx, cpathv, C.int64_t(n), C.ICL_HEAD_DENSE0, C.ICL_PREC_FP32, 0,
+		(*C.float)(unsafe.Pointer(&out[0])), &status[0])
+	msg := C.GoString(C.icl_last_error(appCtx.Net.ctx))
+	for i := range paths {
+		switch {
+		case status[i] != C.ICL_OK:
+			errs[i] = fmt.Errorf("failed to read image: %s (code %d)", paths[i], int(status[i]))
+		case rc != C.ICL_OK && !anyFailed(status):
+			errs[i] = fmt.Errorf("%s", msg)
+		default:
+			rows[i] = out[i*head : (i+1)*head : (i+1)*head]
+		}
+	}
+	return rows, errs
+}
+
+func anyFailed(status []C.int32_t) bool {
+	for _, s := range status {
+		if s != C.ICL_OK {
+			return true
+		}
+	}
+	return false
+}

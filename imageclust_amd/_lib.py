@@ -59,6 +59,10 @@ SYMBOLS = [
     ("icl_resize_u8", _int, [_vp, _i32, _i32, _vp, _i32, _i32]),
     ("icl_decode_image_file", _int, [C.c_char_p, _vp, _i64, _pi32, _pi32]),
     ("icl_load_image_224", _int, [C.c_char_p, _vp]),
+    ("icl_load_images_224_dev", _int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    ("icl_embed_files", _int, [_vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
+    ("icl_embed_files_dev", _int, [_vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
+    ("icl_last_ingest_stats", _int, [_vp, _pi64, _pi64, _pi64, _pd]),
     ("icl_set_batch", _int, [_vp, _int]),
     ("icl_set_conv_options", _int, [_vp, _int]),
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
@@ -310,6 +314,53 @@ class Context:
         out = np.empty(head, np.float32)
         check(self.h, self.L.icl_embed_file(self.h, os.fsencode(path), head, out.ctypes.data))
         return out
+
+    def _files_call(self, fn, paths, *args):
+        """Runs a batched file entry point; per-file failures come back in status (the call's code names the lowest failed index)."""
+        enc = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        status = np.zeros(len(enc), np.int32)
+        rc = fn(self.h, arr, len(enc), *args, status.ctypes.data)
+        failed = np.flatnonzero(status)
+        if rc != ICL_OK and not (failed.size and status[failed[0]] == rc):
+            check(self.h, rc)
+        return status
+
+    def load_images_224_dev(self, paths, d_out, threads=0):
+        """icl_load_images_224_dev: n x 224x224x3 u8 rows into device memory d_out -> status (int32[n]); failed rows are zero."""
+        return self._files_call(self.L.icl_load_images_224_dev, paths, threads, _vp(d_out))
+
+    def load_images_224(self, paths, threads=0):
+        """icl_load_images_224_dev through a device buffer -> (n x 224 x 224 x 3 u8, status)."""
+        n = len(paths)
+        out = np.zeros((n, 224, 224, 3), np.uint8)
+        d = self.malloc(max(1, n) * IMG_BYTES)
+        try:
+            status = self.load_images_224_dev(paths, d, threads)
+            if n:
+                self.d2h(out, d)
+        finally:
+            self.free(d)
+        return out, status
+
+    def embed_files(self, paths, head=HEAD_POOLED, prec=PREC_BF16, threads=0):
+        """icl_embed_files -> (E n x head fp32, status int32[n]); rows of failed files are NaN."""
+        out = np.empty((len(paths), head), np.float32)
+        status = self._files_call(self.L.icl_embed_files, paths, head, prec, threads, out.ctypes.data)
+        return out, status
+
+    def embed_files_dev(self, paths, d_out, head=HEAD_POOLED, prec=PREC_BF16, threads=0):
+        """icl_embed_files_dev: n x head fp32 rows into device memory d_out -> status (int32[n])."""
+        return self._files_call(self.L.icl_embed_files_dev, paths, head, prec, threads, _vp(d_out))
+
+    def last_ingest_stats(self):
+        g, h, u, s = _i64(), _i64(), _i64(), C.c_double()
+        check(self.h, self.L.icl_last_ingest_stats(self.h, C.byref(g), C.byref(h), C.byref(u), C.byref(s)))
+        return {"gpu_jpegs": g.value, "host_files": h.value, "upload_bytes": u.value, "host_decode_s": s.value}
+
+    def last_error(self):
+        msg = self.L.icl_last_error(self.h)
+        return msg.decode() if msg else ""
 
     def set_file_options(self, prec=PREC_FP32, window_us=2000, max_batch=256):
         """How icl_embed_file coalesces concurrent callers (workflow.go:156-175: one goroutine per image)."""

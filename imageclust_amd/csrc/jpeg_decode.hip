@@ -9,8 +9,11 @@
 // spectral selection + successive approximation, ITU T.81 annex G) Huffman streams, interleaved or one scan per
 // component, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 sampling, restart intervals, JFIF / Adobe-transform markers.
 // Every scan decodes into per-component coefficient arrays; dequantisation + IDCT run once after the last scan.
+// Two stages (jpeg_stage.h): stage A parses the file and runs the entropy decoder (every check of a hostile file is made
+// here); stage B dequantises, runs the IDCT, upsamples the chroma and converts the colour.  jpeg_gpu.hip runs stage B on the GPU.
 // Arithmetic coding, lossless, 12-bit and CMYK return ICL_ERR_UNSUPPORTED.
 #include "icl_common.h"
+#include "jpeg_stage.h"
 
 #include <cstring>
 #include <new>
@@ -49,13 +52,10 @@ struct huff_table {
     }
 };
 
-struct component {
-    int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0;
-    int wblocks = 0, hblocks = 0; // padded to whole MCUs
-    int dw = 0, dh = 0;           // downsampled_width / _height (real samples)
+// the entropy decoder's view of a component: the stage-A output (icl_jpeg_component, jpeg_stage.h) plus scan state
+struct component : icl_jpeg_component {
+    int td = 0, ta = 0;
     int pred = 0;
-    std::vector<uint8_t> plane;   // wblocks*8 x hblocks*8
-    std::vector<int16_t> coefs;   // wblocks*hblocks blocks of 64, natural order, NOT dequantised
 };
 
 struct bit_reader {
@@ -217,8 +217,8 @@ void idct_islow(const int *coef, uint8_t *out, int stride)
 
 } // namespace
 
-#define ICL_JPEG_MAX_PIXELS (64LL << 20)
-static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient);
+static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J);
+static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb);
 
 // Decodes a JPEG file held in memory to interleaved RGB.  rgb is resized to w*h*3.  No C++ exception may cross the C ABI
 // (cgo / ctypes would std::terminate the host process): allocation failures become status codes here.
@@ -228,7 +228,36 @@ int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *p
 {
     orient = 1;
     try {
-        return jpeg_decode_impl(ctx, data, len, path, rgb, W, H, orient);
+        icl_jpeg_coefs J;
+        const int rc = jpeg_stage_a_impl(ctx, data, len, path, J);
+        W = J.W;
+        H = J.H;
+        if (rc) return rc;
+        orient = J.orient;
+        return jpeg_stage_b_impl(J, rgb);
+    } catch (const std::bad_alloc &) {
+        return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
+    } catch (...) {
+        return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Decoder error", path);
+    }
+}
+
+int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J)
+{
+    J.orient = 1;
+    try {
+        return jpeg_stage_a_impl(ctx, data, len, path, J);
+    } catch (const std::bad_alloc &) {
+        return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
+    } catch (...) {
+        return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Decoder error", path);
+    }
+}
+
+int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, std::vector<uint8_t> &rgb)
+{
+    try {
+        return jpeg_stage_b_impl(J, rgb);
     } catch (const std::bad_alloc &) {
         return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
     } catch (...) {
@@ -264,14 +293,17 @@ static int exif_orientation(const uint8_t *s, size_t sl)
     return 1;
 }
 
-static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient)
+// Stage A: markers, tables, frame and scan headers, and every scan's entropy-coded data into J.comp[c].coefs.
+static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J)
 {
+    int &W = J.W, &H = J.H, &orient = J.orient;
     auto fail = [&](int code, const char *what) { return icl_fail(ctx, code, "failed to read image: %s. %s", path, what); };
     if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return fail(ICL_ERR_IO, "Not a JPEG stream");
     uint16_t qt[4][64];
     bool qt_ok[4] = {false, false, false, false};
     huff_table dc[4], ac[4];
     component comp[3];
+    for (int c = 0; c < 3; ++c) comp[c].coefs.swap(J.comp[c].coefs); // decode into J's arrays (a reused J keeps their capacity)
     int ncomp = 0, restart = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0, nscans = 0;
     bool have_sof = false, adobe = false, progressive = false;
     int adobe_transform = -1;
@@ -543,26 +575,41 @@ static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const
         pos += seglen;
     }
     if (!have_sof || nscans == 0) return fail(ICL_ERR_IO, "The image file might be corrupt or unreadable");
-    // dequantise + inverse DCT, once, after the last scan
     for (int c = 0; c < ncomp; ++c) {
         component &k = comp[c];
         if (k.tq > 3 || !qt_ok[k.tq]) return fail(ICL_ERR_IO, "Missing table");
+        memcpy(J.qt[c], qt[k.tq], sizeof J.qt[c]); // the table as it stands after the last scan (what dequantisation uses)
+        J.comp[c].swap_from(k);
+    }
+    J.ncomp = ncomp;
+    J.is_rgb = ncomp == 3 && ((adobe && adobe_transform == 0) || (!adobe && comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B'));
+    return ICL_OK;
+}
+
+// Stage B: dequantise + inverse DCT (once, after the last scan), chroma upsampling, colour conversion.
+static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb)
+{
+    const int W = J.W, H = J.H, ncomp = J.ncomp;
+    std::vector<uint8_t> plane[3]; // wblocks*8 x hblocks*8 per component
+    for (int c = 0; c < ncomp; ++c) {
+        const icl_jpeg_component &k = J.comp[c];
         const size_t stride = (size_t)k.wblocks * 8;
-        k.plane.assign(stride * k.hblocks * 8, 0);
+        plane[c].assign(stride * k.hblocks * 8, 0);
         int coef[64];
         for (int by = 0; by < k.hblocks; ++by)
             for (int bx = 0; bx < k.wblocks; ++bx) {
                 const int16_t *cf = k.coefs.data() + ((size_t)by * k.wblocks + bx) * 64;
-                for (int i = 0; i < 64; ++i) coef[i] = cf[i] * qt[k.tq][i];
-                idct_islow(coef, k.plane.data() + (size_t)by * 8 * stride + (size_t)bx * 8, (int)stride);
+                for (int i = 0; i < 64; ++i) coef[i] = cf[i] * J.qt[c][i];
+                idct_islow(coef, plane[c].data() + (size_t)by * 8 * stride + (size_t)bx * 8, (int)stride);
             }
     }
+    const icl_jpeg_component *comp = J.comp;
     rgb.assign((size_t)W * H * 3, 0);
     if (ncomp == 1) {
         const size_t stride = (size_t)comp[0].wblocks * 8;
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
-                const uint8_t g = comp[0].plane[y * stride + x];
+                const uint8_t g = plane[0][y * stride + x];
                 uint8_t *o = &rgb[((size_t)y * W + x) * 3];
                 o[0] = o[1] = o[2] = g;
             }
@@ -572,12 +619,13 @@ static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const
     const int hs = comp[0].h, vs = comp[0].v;
     std::vector<uint8_t> up[2];
     for (int c = 1; c <= 2; ++c) {
-        const component &k = comp[c];
+        const icl_jpeg_component &k = comp[c];
         const size_t stride = (size_t)k.wblocks * 8;
         std::vector<uint8_t> &o = up[c - 1];
         o.assign((size_t)W * H, 0);
         const int dw = k.dw, dh = k.dh;
-        auto in = [&](int r) -> const uint8_t * { return k.plane.data() + (size_t)std::min(std::max(r, 0), dh - 1) * stride; };
+        const uint8_t *pl = plane[c].data();
+        auto in = [&](int r) -> const uint8_t * { return pl + (size_t)std::min(std::max(r, 0), dh - 1) * stride; };
         if (hs == 1 && vs == 1) {
             for (int y = 0; y < H; ++y) memcpy(&o[(size_t)y * W], in(y), (size_t)W);
         } else if (hs == 2 && vs == 1) {
@@ -623,7 +671,7 @@ static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const
         }
     }
     // colour conversion (jdcolor.c): fixed-point YCbCr -> RGB, or pass-through for Adobe transform 0
-    const bool is_rgb = (adobe && adobe_transform == 0) || (!adobe && comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B');
+    const bool is_rgb = J.is_rgb;
     int cr_r[256], cb_b[256], cr_g[256], cb_g[256];
     for (int i = 0; i < 256; ++i) {
         const int x = i - 128;
@@ -635,7 +683,7 @@ static int jpeg_decode_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const
     const size_t ystride = (size_t)comp[0].wblocks * 8;
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
-            const int Y = comp[0].plane[y * ystride + x], cb = up[0][(size_t)y * W + x], cr = up[1][(size_t)y * W + x];
+            const int Y = plane[0][y * ystride + x], cb = up[0][(size_t)y * W + x], cr = up[1][(size_t)y * W + x];
             uint8_t *o = &rgb[((size_t)y * W + x) * 3];
             if (is_rgb) {
                 o[0] = (uint8_t)Y; o[1] = (uint8_t)cb; o[2] = (uint8_t)cr;

@@ -1,0 +1,773 @@
+// jpeg_gpu.hip -- batched image-file ingest: the host keeps the serial part of JPEG decoding (parsing + Huffman decoding,
+// stage A of jpeg_decode.hip), the GPU rebuilds the pixels (stage B: dequantisation, islow IDCT, fancy upsampling, YCbCr->RGB)
+// together with the EXIF orientation and the 224x224 resize, bit-identical to the host path (icl_load_image_224).
+//
+// Data per slab (one pinned host buffer, uploaded in three copies on the context's stream):
+//   ingest_image[nimg]  one per output row: kind, sizes, orientation, plane offsets, the host-computed resize tables
+//   ingest_plane[np]    one per JPEG component: block range, payload offsets, quantisation table
+//   payload             per component: uint32 block offsets (nblocks + 1), then the int16 coefficients of every block in
+//                       zig-zag order up to its last non-zero one; PNG / PPM / fallback images as finished 224x224x3 rows
+// Kernels: jpeg_idct_kernel (one thread per 8x8 block -> u8 planes in a scratch), jpeg_gather_resize_kernel (one thread per
+// output pixel: reads the 2x2 source pixels of the resize through the orientation map, upsamples the chroma at those
+// positions only, converts the colour and resizes).  Nothing is built at full-resolution RGB.
+#include "icl_common.h"
+#include "jpeg_stage.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <thread>
+
+bool icl_is_png(const uint8_t *data, size_t len);                                                         // png_decode.hip
+int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out); // resnet.hip
+
+namespace {
+
+constexpr int OUTW = ICL_IMG_W, OUTH = ICL_IMG_H;
+enum { KIND_FAILED = 0, KIND_JPEG = 1, KIND_HOST = 2 };
+
+struct ingest_image {
+    int32_t kind;
+    int32_t W, H;   // decoded size
+    int32_t ow, oh; // size after the EXIF orientation (the resize's source)
+    int32_t orient, ncomp, hs, vs, is_rgb, area;
+    int32_t cw, chh;          // chroma samples per row / rows (dw, dh of components 1 and 2)
+    int32_t ystride, yrows;   // luma plane: wblocks*8 x hblocks*8
+    int32_t cstride, crows;   // chroma planes
+    int32_t pad_;
+    int64_t yplane, cplane[2]; // byte offsets in the plane scratch
+    int64_t host_off;          // KIND_HOST: byte offset of the finished image in the payload
+    int32_t xofs[OUTW], yofs[OUTH];
+    int16_t xa[OUTW * 2], ya[OUTH * 2];
+};
+
+struct ingest_plane {
+    int64_t first_block; // flat block index over the slab
+    int64_t plane_off, plane_bytes;
+    int64_t offs_off, coef_off; // payload byte offsets
+    int32_t nblocks, wblocks;
+    uint32_t ncoef;
+    int32_t pad_;
+    uint16_t qt[64]; // natural order
+};
+
+__constant__ uint8_t c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t h_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+__device__ __forceinline__ int clamp8d(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+constexpr int IDCT_THREADS = 64;
+constexpr int IDCT_SLOT = 65; // ints per thread in LDS (odd stride: no bank conflicts between the threads' slots)
+
+// IJG jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2), the same integer arithmetic as jpeg_decode.hip idct_islow:
+// one thread per block; the dequantised coefficients are scattered from zig-zag order into the thread's LDS slot.
+__global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const ingest_plane *__restrict__ planes, int nplanes, const uint8_t *__restrict__ payload,
+                                                                 int64_t payload_bytes, uint8_t *__restrict__ scratch, int64_t scratch_bytes, int64_t total_blocks)
+{
+    __shared__ int lds[IDCT_THREADS * IDCT_SLOT];
+    int *coef = lds + threadIdx.x * IDCT_SLOT;
+    const int64_t g = (int64_t)blockIdx.x * IDCT_THREADS + threadIdx.x;
+    if (g >= total_blocks) return;
+    int lo = 0, hi = nplanes - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (planes[mid].first_block <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const ingest_plane &P = planes[lo];
+    const int64_t b = g - P.first_block;
+    if (b < 0 || b >= P.nblocks || P.wblocks <= 0) return;
+    // every offset was computed and validated on the host; these checks keep the kernel inside its buffers regardless
+    if (P.offs_off < 0 || P.offs_off + ((int64_t)P.nblocks + 1) * 4 > payload_bytes || P.coef_off < 0 || P.coef_off + (int64_t)P.ncoef * 2 > payload_bytes) return;
+    const int64_t stride = (int64_t)P.wblocks * 8, by = b / P.wblocks, bx = b - by * P.wblocks;
+    const int64_t o = P.plane_off + by * 8 * stride + bx * 8;
+    if (P.plane_off < 0 || P.plane_off + P.plane_bytes > scratch_bytes || (by * 8 + 7) * stride + bx * 8 + 8 > P.plane_bytes) return;
+    const uint32_t *offs = (const uint32_t *)(payload + P.offs_off);
+    const uint32_t o0 = offs[b], o1 = offs[b + 1];
+    const int cnt = (o1 >= o0 && o1 - o0 <= 64 && o1 <= P.ncoef) ? (int)(o1 - o0) : 0;
+    const int16_t *cf = (const int16_t *)(payload + P.coef_off) + o0;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) coef[i] = 0;
+    for (int i = 0; i < cnt; ++i) {
+        const int z = c_zigzag[i];
+        coef[z] = (int)cf[i] * (int)P.qt[z];
+    }
+    constexpr int CB = 13, P1 = 2;
+    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299, F1_847 = 15137,
+                  F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
+    auto descale = [](long x, int n) { return (int)((x + (1L << (n - 1))) >> n); };
+    int ws[64];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int *in = coef + c;
+        int *w = ws + c;
+        long z2 = in[16], z3 = in[48];
+        long z1 = (z2 + z3) * F0_541;
+        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
+        z2 = in[0];
+        z3 = in[32];
+        long tmp0 = (z2 + z3) * (1L << CB), tmp1 = (z2 - z3) * (1L << CB);
+        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+        tmp0 = in[56];
+        tmp1 = in[40];
+        tmp2 = in[24];
+        tmp3 = in[8];
+        z1 = tmp0 + tmp3;
+        z2 = tmp1 + tmp2;
+        z3 = tmp0 + tmp2;
+        long z4 = tmp1 + tmp3;
+        const long z5 = (z3 + z4) * F1_175;
+        tmp0 *= F0_298;
+        tmp1 *= F2_053;
+        tmp2 *= F3_072;
+        tmp3 *= F1_501;
+        z1 *= -F0_899;
+        z2 *= -F2_562;
+        z3 *= -F1_961;
+        z4 *= -F0_390;
+        z3 += z5;
+        z4 += z5;
+        tmp0 += z1 + z3;
+        tmp1 += z2 + z4;
+        tmp2 += z2 + z3;
+        tmp3 += z1 + z4;
+        // (the host's all-AC-zero shortcut writes dc << PASS1_BITS: exactly what these formulas give for zero AC terms)
+        w[0] = descale(tmp10 + tmp3, CB - P1);
+        w[56] = descale(tmp10 - tmp3, CB - P1);
+        w[8] = descale(tmp11 + tmp2, CB - P1);
+        w[48] = descale(tmp11 - tmp2, CB - P1);
+        w[16] = descale(tmp12 + tmp1, CB - P1);
+        w[40] = descale(tmp12 - tmp1, CB - P1);
+        w[24] = descale(tmp13 + tmp0, CB - P1);
+        w[32] = descale(tmp13 - tmp0, CB - P1);
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int *w = ws + 8 * r;
+        long z2 = w[2], z3 = w[6];
+        long z1 = (z2 + z3) * F0_541;
+        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
+        long tmp0 = ((long)w[0] + w[4]) * (1L << CB), tmp1 = ((long)w[0] - w[4]) * (1L << CB);
+        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+        tmp0 = w[7];
+        tmp1 = w[5];
+        tmp2 = w[3];
+        tmp3 = w[1];
+        z1 = tmp0 + tmp3;
+        z2 = tmp1 + tmp2;
+        z3 = tmp0 + tmp2;
+        long z4 = tmp1 + tmp3;
+        const long z5 = (z3 + z4) * F1_175;
+        tmp0 *= F0_298;
+        tmp1 *= F2_053;
+        tmp2 *= F3_072;
+        tmp3 *= F1_501;
+        z1 *= -F0_899;
+        z2 *= -F2_562;
+        z3 *= -F1_961;
+        z4 *= -F0_390;
+        z3 += z5;
+        z4 += z5;
+        tmp0 += z1 + z3;
+        tmp1 += z2 + z4;
+        tmp2 += z2 + z3;
+        tmp3 += z1 + z4;
+        constexpr int S = CB + P1 + 3;
+        const uint32_t p0 = clamp8d(descale(tmp10 + tmp3, S) + 128), p7 = clamp8d(descale(tmp10 - tmp3, S) + 128);
+        const uint32_t p1 = clamp8d(descale(tmp11 + tmp2, S) + 128), p6 = clamp8d(descale(tmp11 - tmp2, S) + 128);
+        const uint32_t p2 = clamp8d(descale(tmp12 + tmp1, S) + 128), p5 = clamp8d(descale(tmp12 - tmp1, S) + 128);
+        const uint32_t p3 = clamp8d(descale(tmp13 + tmp0, S) + 128), p4 = clamp8d(descale(tmp13 - tmp0, S) + 128);
+        uint2 v;
+        v.x = p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
+        v.y = p4 | (p5 << 8) | (p6 << 16) | (p7 << 24);
+        *(uint2 *)(scratch + o + r * stride) = v; // plane offsets and strides are multiples of 8
+    }
+}
+
+// one chroma sample of the upsampled (full-resolution) plane at (X, y): jpeg_decode.hip's h1v1 / h2v1 / h2v2 "fancy" rules
+__device__ __forceinline__ int chroma_at(const ingest_image &D, const uint8_t *pl, int X, int y)
+{
+    const int dw = D.cw, dh = D.chh;
+    auto row = [&](int r) -> const uint8_t * { return pl + (int64_t)min(max(r, 0), dh - 1) * D.cstride; };
+    if (D.hs == 1) return row(y)[min(X, dw - 1)];
+    const int i = min(X >> 1, dw - 1);
+    if (D.vs == 1) {
+        const uint8_t *p = row(y);
+        if (X & 1) return i >= dw - 1 ? p[dw - 1] : (p[i] * 3 + p[i + 1] + 2) >> 2;
+        return i == 0 ? p[0] : (p[i] * 3 + p[i - 1] + 1) >> 2;
+    }
+    const int r = y >> 1;
+    const uint8_t *p0 = row(r), *p1 = row((y & 1) ? r + 1 : r - 1); // nearer / further input row
+    auto cs = [&](int k) { return p0[k] * 3 + p1[k]; };
+    if (X & 1) return i >= dw - 1 ? (cs(dw - 1) * 4 + 7) >> 4 : (cs(i) * 3 + cs(i + 1) + 7) >> 4;
+    return i == 0 ? (cs(0) * 4 + 8) >> 4 : (cs(i) * 3 + cs(i - 1) + 8) >> 4;
+}
+
+// RGB of pixel (x, y) of the ORIENTED image (apply_exif_orientation's destination -> source map, resnet.hip)
+__device__ __forceinline__ void rgb_at(const ingest_image &D, const uint8_t *scratch, int x, int y, int &R, int &G, int &B)
+{
+    const int sw = D.W, sh = D.H;
+    int sx, sy;
+    switch (D.orient) {
+    case 2: sx = sw - 1 - x; sy = y; break;
+    case 3: sx = sw - 1 - x; sy = sh - 1 - y; break;
+    case 4: sx = x; sy = sh - 1 - y; break;
+    case 5: sx = y; sy = x; break;
+    case 6: sx = y; sy = sh - 1 - x; break;
+    case 7: sx = sw - 1 - y; sy = sh - 1 - x; break;
+    case 8: sx = sw - 1 - y; sy = x; break;
+    default: sx = x; sy = y; break;
+    }
+    sx = min(max(sx, 0), sw - 1);
+    sy = min(max(sy, 0), sh - 1);
+    const int Y = scratch[D.yplane + (int64_t)sy * D.ystride + sx];
+    if (D.ncomp == 1) { R = G = B = Y; return; }
+    const int cb = chroma_at(D, scratch + D.cplane[0], sx, sy), cr = chroma_at(D, scratch + D.cplane[1], sx, sy);
+    if (D.is_rgb) { R = Y; G = cb; B = cr; return; }
+    // jdcolor.c fixed-point tables, evaluated in place (integer arithmetic: identical to the host's table entries)
+    const int xr = cr - 128, xb = cb - 128;
+    R = clamp8d(Y + ((91881 * xr + 32768) >> 16));
+    G = clamp8d(Y + ((-22554 * xb + 32768 + -46802 * xr) >> 16));
+    B = clamp8d(Y + ((116130 * xb + 32768) >> 16));
+}
+
+// one thread per output pixel of one image: cv::resize INTER_LINEAR (OpenCV's two-pass fixed-point rounding) or, for an exact
+// 2x2 decimation, INTER_AREA -- resnet.hip resize_bilinear_u8, with its offset / weight tables computed on the host
+__global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_image *__restrict__ imgs, const uint8_t *__restrict__ payload, int64_t payload_bytes,
+                                                                 const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= OUTW * OUTH) return;
+    const ingest_image &D = imgs[blockIdx.y];
+    uint8_t *o = dst + (int64_t)blockIdx.y * ICL_IMG_BYTES + (int64_t)p * 3;
+    if (D.kind == KIND_HOST) {
+        if (D.host_off >= 0 && D.host_off + ICL_IMG_BYTES <= payload_bytes) {
+            const uint8_t *s = payload + D.host_off + (int64_t)p * 3;
+            o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+        } else {
+            o[0] = o[1] = o[2] = 0;
+        }
+        return;
+    }
+    if (D.kind != KIND_JPEG) { o[0] = o[1] = o[2] = 0; return; }
+    const int dx = p % OUTW, dy = p / OUTW;
+    int r[4], g[4], b[4];
+    if (D.area) {
+        rgb_at(D, scratch, 2 * dx, 2 * dy, r[0], g[0], b[0]);
+        rgb_at(D, scratch, 2 * dx + 1, 2 * dy, r[1], g[1], b[1]);
+        rgb_at(D, scratch, 2 * dx, 2 * dy + 1, r[2], g[2], b[2]);
+        rgb_at(D, scratch, 2 * dx + 1, 2 * dy + 1, r[3], g[3], b[3]);
+        o[0] = (uint8_t)((r[0] + r[1] + r[2] + r[3] + 2) >> 2);
+        o[1] = (uint8_t)((g[0] + g[1] + g[2] + g[3] + 2) >> 2);
+        o[2] = (uint8_t)((b[0] + b[1] + b[2] + b[3] + 2) >> 2);
+        return;
+    }
+    const int sx = min(max(D.xofs[dx], 0), D.ow - 1), sx1 = min(sx + 1, D.ow - 1);
+    const int sy = min(max(D.yofs[dy], 0), D.oh - 1), sy1 = min(sy + 1, D.oh - 1);
+    rgb_at(D, scratch, sx, sy, r[0], g[0], b[0]);
+    rgb_at(D, scratch, sx1, sy, r[1], g[1], b[1]);
+    rgb_at(D, scratch, sx, sy1, r[2], g[2], b[2]);
+    rgb_at(D, scratch, sx1, sy1, r[3], g[3], b[3]);
+    const int a0 = D.xa[dx * 2], a1 = D.xa[dx * 2 + 1], b0 = D.ya[dy * 2], b1 = D.ya[dy * 2 + 1];
+    auto mix = [&](int t0, int t1, int t2, int t3) {
+        const int row0 = t0 * a0 + t1 * a1, row1 = t2 * a0 + t3 * a1;
+        return (uint8_t)((((b0 * (row0 >> 4)) >> 16) + ((b1 * (row1 >> 4)) >> 16) + 2) >> 2);
+    };
+    o[0] = mix(r[0], r[1], r[2], r[3]);
+    o[1] = mix(g[0], g[1], g[2], g[3]);
+    o[2] = mix(b[0], b[1], b[2], b[3]);
+}
+
+__global__ void fill_nan_rows_kernel(float *out, const int32_t *rows, int nrows, int head)
+{
+    const int r = blockIdx.y;
+    if (r >= nrows) return;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < head; i += gridDim.x * 256) out[(int64_t)rows[r] * head + i] = __int_as_float(0x7fc00000);
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+
+constexpr int64_t SLAB_IMAGES = 256;                 // output rows per slab (the forward pass's batch)
+constexpr int64_t SLAB_PAYLOAD = 128ll << 20;        // coefficient / finished-image bytes per slab (pinned, two of them)
+constexpr int64_t SLAB_SCRATCH = 768ll << 20;        // u8 planes of one slab on the device
+constexpr int64_t HDR_BYTES = SLAB_IMAGES * (int64_t)sizeof(ingest_image) + 3 * SLAB_IMAGES * (int64_t)sizeof(ingest_plane);
+
+static int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+
+struct comp_meta {
+    int32_t wblocks, hblocks, dw, dh;
+    int64_t offs_off, coef_off; // within the file's packed buffer
+    uint32_t ncoef;
+};
+
+struct file_result { // what a worker hands the slab builder for one file
+    int kind = KIND_FAILED;
+    int rc = ICL_OK;
+    std::string err;
+    int W = 0, H = 0, ncomp = 0, hs = 1, vs = 1, is_rgb = 0, orient = 1;
+    uint16_t qt[3][64];
+    comp_meta cm[3];
+    std::vector<uint8_t> packed; // KIND_JPEG: the components' block offsets + coefficients; KIND_HOST: the 224x224x3 image
+    int64_t plane_bytes = 0;
+};
+
+static int64_t plane_bytes_of(const icl_jpeg_component &k) { return (int64_t)k.wblocks * 8 * k.hblocks * 8; }
+
+// Stage-A output -> the compact per-block form: uint32 offsets (nblocks + 1) and the zig-zag coefficients up to each block's
+// last non-zero one.  Returns false when the image does not fit one slab (it then takes the host path).
+static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint32_t> &offs)
+{
+    int64_t total = 0, planes = 0;
+    uint32_t ncoef[3] = {0, 0, 0};
+    for (int c = 0; c < J.ncomp; ++c) {
+        const icl_jpeg_component &k = J.comp[c];
+        const int64_t nb = (int64_t)k.wblocks * k.hblocks;
+        planes += plane_bytes_of(k);
+        uint64_t nc = 0;
+        for (int64_t b = 0; b < nb; ++b) {
+            const int16_t *cf = k.coefs.data() + b * 64;
+            int e = 63;
+            while (e >= 0 && cf[h_zigzag[e]] == 0) --e;
+            nc += (uint64_t)(e + 1);
+        }
+        if (nc > 0xffffffffull) return false;
+        ncoef[c] = (uint32_t)nc;
+        total += align16((nb + 1) * 4) + align16((int64_t)nc * 2);
+    }
+    if (total > SLAB_PAYLOAD || planes > SLAB_SCRATCH) return false;
+    r.packed.resize((size_t)total);
+    r.plane_bytes = planes;
+    int64_t pos = 0;
+    for (int c = 0; c < J.ncomp; ++c) {
+        const icl_jpeg_component &k = J.comp[c];
+        const int64_t nb = (int64_t)k.wblocks * k.hblocks;
+        comp_meta &m = r.cm[c];
+        m.wblocks = k.wblocks;
+        m.hblocks = k.hblocks;
+        m.dw = k.dw;
+        m.dh = k.dh;
+        m.ncoef = ncoef[c];
+        m.offs_off = pos;
+        m.coef_off = pos + align16((nb + 1) * 4);
+        offs.resize((size_t)nb + 1);
+        int16_t *out = (int16_t *)(r.packed.data() + m.coef_off);
+        uint32_t at = 0;
+        for (int64_t b = 0; b < nb; ++b) {
+            const int16_t *cf = k.coefs.data() + b * 64;
+            int e = 63;
+            while (e >= 0 && cf[h_zigzag[e]] == 0) --e;
+            offs[(size_t)b] = at;
+            for (int i = 0; i <= e; ++i) out[at + i] = cf[h_zigzag[i]];
+            at += (uint32_t)(e + 1);
+        }
+        offs[(size_t)nb] = at;
+        memcpy(r.packed.data() + m.offs_off, offs.data(), ((size_t)nb + 1) * 4);
+        pos = m.coef_off + align16((int64_t)m.ncoef * 2);
+        memcpy(r.qt[c], J.qt[c], sizeof r.qt[c]);
+    }
+    r.W = J.W;
+    r.H = J.H;
+    r.ncomp = J.ncomp;
+    r.hs = J.comp[0].h;
+    r.vs = J.comp[0].v;
+    r.is_rgb = J.is_rgb ? 1 : 0;
+    r.orient = J.orient;
+    return true;
+}
+
+static void host_finish(const char *path, std::vector<uint8_t> &rgb, int w, int h, file_result &r)
+{
+    r.packed.resize((size_t)ICL_IMG_BYTES);
+    icl_resize_u8_host(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
+    r.kind = KIND_HOST;
+}
+
+// One file, on a worker thread: stage A for a JPEG the GPU takes, the whole host path for everything else.  Status codes and
+// messages are those of icl_load_image_224 (read_image, resnet.hip).
+static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32_t> &offs, file_result &r)
+{
+    auto fail_from_tls = [&](int rc) {
+        r.kind = KIND_FAILED;
+        r.rc = rc;
+        r.err = icl_last_error(nullptr);
+    };
+    try {
+        std::vector<uint8_t> file;
+        bool jpeg = false;
+        if (FILE *f = fopen(path, "rb")) {
+            unsigned char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            const size_t got = fread(magic, 1, 8, f);
+            jpeg = !(got == 8 && icl_is_png(magic, 8)) && got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8;
+            if (jpeg) {
+                fseek(f, 0, SEEK_END);
+                const long sz = ftell(f);
+                fseek(f, 0, SEEK_SET);
+                file.resize((size_t)std::max<long>(sz, 0));
+                const bool ok = sz > 0 && fread(file.data(), 1, file.size(), f) == file.size();
+                if (!ok) jpeg = false; // let the host path report it
+            }
+            fclose(f);
+        }
+        if (jpeg) {
+            const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), path, J);
+            if (rc) return fail_from_tls(rc);
+            if (pack_jpeg(J, r, offs)) {
+                r.kind = KIND_JPEG;
+                return;
+            }
+            // too large for one slab: stage B on the host (the file has already been through stage A)
+            std::vector<uint8_t> rgb;
+            int w = J.W, h = J.H;
+            const int rc2 = icl_jpeg_stage_b(nullptr, J, path, rgb);
+            if (rc2) return fail_from_tls(rc2);
+            icl_apply_exif_orientation(rgb, w, h, J.orient);
+            return host_finish(path, rgb, w, h, r);
+        }
+        std::vector<uint8_t> rgb;
+        int w = 0, h = 0;
+        const int rc = icl_read_image_host(nullptr, path, rgb, w, h);
+        if (rc) return fail_from_tls(rc);
+        host_finish(path, rgb, w, h, r);
+    } catch (const std::bad_alloc &) {
+        r.kind = KIND_FAILED;
+        r.rc = ICL_ERR_NOMEM;
+        r.err = std::string("failed to read image: ") + path + ". Out of host memory while decoding";
+    } catch (...) {
+        r.kind = KIND_FAILED;
+        r.rc = ICL_ERR_IO;
+        r.err = std::string("failed to read image: ") + path + ". Decoder error";
+    }
+}
+
+} // namespace
+
+// Buffers of the batched file path, kept by the context between calls (freed by icl_destroy).
+struct icl_ingest_ws {
+    uint8_t *h_slab[2] = {nullptr, nullptr}; // pinned: header (images + planes) then payload
+    hipEvent_t ev_up[2] = {nullptr, nullptr};
+    uint8_t *d_hdr = nullptr, *d_payload = nullptr, *d_scratch = nullptr, *d_img = nullptr;
+    float *d_emb = nullptr;
+    int32_t *d_rows = nullptr;
+    int emb_head = 0;
+    ~icl_ingest_ws()
+    {
+        for (int q = 0; q < 2; ++q) {
+            if (h_slab[q]) (void)hipHostFree(h_slab[q]);
+            if (ev_up[q]) (void)hipEventDestroy(ev_up[q]);
+        }
+        for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_emb, (void *)d_rows})
+            if (p) (void)hipFree(p);
+    }
+};
+
+void icl_ingest_free(icl_ctx *ctx)
+{
+    delete ctx->ingest;
+    ctx->ingest = nullptr;
+}
+
+static int ingest_ws(icl_ctx *ctx, icl_ingest_ws *&ws)
+{
+    if (!ctx->ingest) {
+        std::unique_ptr<icl_ingest_ws> w(new icl_ingest_ws());
+        for (int q = 0; q < 2; ++q) {
+            if (hipHostMalloc((void **)&w->h_slab[q], (size_t)(HDR_BYTES + SLAB_PAYLOAD), hipHostMallocDefault) != hipSuccess) {
+                w->h_slab[q] = nullptr;
+                return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: pinned staging slab");
+            }
+            ICL_HIP(ctx, hipEventCreateWithFlags(&w->ev_up[q], hipEventDisableTiming));
+        }
+        if (hipMalloc((void **)&w->d_hdr, (size_t)HDR_BYTES) != hipSuccess || hipMalloc((void **)&w->d_payload, (size_t)SLAB_PAYLOAD) != hipSuccess ||
+            hipMalloc((void **)&w->d_scratch, (size_t)SLAB_SCRATCH) != hipSuccess ||
+            hipMalloc((void **)&w->d_img, (size_t)SLAB_IMAGES * ICL_IMG_BYTES) != hipSuccess ||
+            hipMalloc((void **)&w->d_rows, (size_t)SLAB_IMAGES * 4) != hipSuccess)
+            return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: device buffers");
+        ctx->ingest = w.release();
+    }
+    ws = ctx->ingest;
+    return ICL_OK;
+}
+
+// The pipeline behind icl_load_images_224_dev and icl_embed_files[_dev].  mode 0: u8 rows into d_u8; 1: embeddings into host
+// `out`; 2: embeddings into device d_out.
+static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
+                        int32_t *status, const char *what)
+{
+    icl_ingest_ws *ws = nullptr;
+    ICL_TRY(ingest_ws(ctx, ws));
+    if (mode && ws->emb_head < head) {
+        if (ws->d_emb) (void)hipFree(ws->d_emb);
+        ws->d_emb = nullptr;
+        ws->emb_head = 0;
+        if (hipMalloc((void **)&ws->d_emb, (size_t)SLAB_IMAGES * head * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: embedding buffer");
+        ws->emb_head = head;
+    }
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(n, threads > 0 ? threads : (int)std::min(16u, hw)));
+
+    // ---- workers: claim files in order, at most one slab's worth of rows (and bytes) ahead of the slab builder ----
+    std::vector<std::unique_ptr<file_result>> res((size_t)n);
+    std::mutex m;
+    std::condition_variable cv;
+    int64_t next_claim = 0, next_pack = 0, pending_bytes = 0;
+    bool stop = false, worker_oom = false;
+    std::atomic<int64_t> decode_ns{0};
+    const int64_t window = 2 * SLAB_IMAGES, byte_budget = 2 * SLAB_PAYLOAD;
+    auto worker = [&]() {
+        icl_jpeg_coefs J;
+        std::vector<uint32_t> offs;
+        for (;;) {
+            int64_t i;
+            {
+                std::unique_lock<std::mutex> lk(m);
+                cv.wait(lk, [&] { return stop || next_claim >= n || next_claim == next_pack || (next_claim < next_pack + window && pending_bytes < byte_budget); });
+                if (stop || next_claim >= n) return;
+                i = next_claim++;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            std::unique_ptr<file_result> r(new (std::nothrow) file_result());
+            if (r) process_file(paths[i], J, offs, *r);
+            decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+            std::lock_guard<std::mutex> lk(m);
+            if (!r) { // no memory for even the result: the call fails (the slab builder waits for this row)
+                worker_oom = true;
+                stop = true;
+            } else {
+                pending_bytes += (int64_t)r->packed.size();
+                res[(size_t)i] = std::move(r);
+            }
+            cv.notify_all();
+        }
+    };
+    std::vector<std::thread> pool;
+    struct joiner {
+        std::vector<std::thread> &p;
+        std::mutex &m;
+        std::condition_variable &cv;
+        bool &stop;
+        ~joiner()
+        {
+            {
+                std::lock_guard<std::mutex> lk(m);
+                stop = true;
+            }
+            cv.notify_all();
+            for (auto &t : p)
+                if (t.joinable()) t.join();
+        }
+    } jn{pool, m, cv, stop};
+    for (int t = 0; t < nthr; ++t) pool.emplace_back(worker);
+
+    // ---- slab builder (this thread): rows in file order, double-buffered pinned slabs, everything on ctx->stream ----
+    int64_t gpu_jpegs = 0, host_files = 0, upload = 0;
+    std::vector<int32_t> failed_rows;
+    for (int64_t k = 0; next_pack < n; ++k) {
+        uint8_t *hs = ws->h_slab[k & 1];
+        ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[k & 1])); // the upload that last read this slab has finished
+        ingest_image *imgs = (ingest_image *)hs;
+        ingest_plane *pls = (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image));
+        uint8_t *pay = hs + HDR_BYTES;
+        const int64_t first = next_pack;
+        int nimg = 0, npl = 0;
+        int64_t used = 0, scratch_used = 0, blocks = 0;
+        failed_rows.clear();
+        while (next_pack < n && nimg < SLAB_IMAGES) {
+            std::unique_ptr<file_result> r;
+            {
+                std::unique_lock<std::mutex> lk(m);
+                cv.wait(lk, [&] { return res[(size_t)next_pack] != nullptr || worker_oom; });
+                if (worker_oom) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", what);
+                file_result &q = *res[(size_t)next_pack];
+                const int64_t need = q.kind == KIND_FAILED ? 0 : align16((int64_t)q.packed.size());
+                if (nimg > 0 && (used + need > SLAB_PAYLOAD || scratch_used + align16(q.plane_bytes) > SLAB_SCRATCH)) break;
+                r = std::move(res[(size_t)next_pack]);
+                pending_bytes -= (int64_t)r->packed.size();
+                ++next_pack;
+                cv.notify_all();
+            }
+            const int64_t row = first + nimg;
+            ingest_image &D = imgs[nimg];
+            memset(&D, 0, offsetof(ingest_image, xofs));
+            D.kind = r->kind;
+            if (status) status[row] = r->rc;
+            if (r->kind == KIND_FAILED) {
+                failed_rows.push_back(nimg);
+                std::lock_guard<std::mutex> lk(m);
+                res[(size_t)row].reset(r.release()); // kept for the error report
+            } else if (r->kind == KIND_HOST) {
+                D.host_off = used;
+                memcpy(pay + used, r->packed.data(), (size_t)ICL_IMG_BYTES);
+                used += align16(ICL_IMG_BYTES);
+                ++host_files;
+            } else {
+                // sizes were produced by stage A + pack_jpeg on this host; re-check what the kernels rely on
+                D.W = r->W;
+                D.H = r->H;
+                D.orient = r->orient;
+                D.ncomp = r->ncomp;
+                D.hs = r->hs;
+                D.vs = r->vs;
+                D.is_rgb = r->is_rgb;
+                const bool swap = r->orient >= 5 && r->orient <= 8;
+                D.ow = swap ? r->H : r->W;
+                D.oh = swap ? r->W : r->H;
+                D.area = D.ow == 2 * OUTW && D.oh == 2 * OUTH;
+                icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
+                icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
+                memcpy(pay + used, r->packed.data(), r->packed.size());
+                for (int c = 0; c < r->ncomp; ++c) {
+                    const comp_meta &cm = r->cm[c];
+                    ingest_plane &P = pls[npl++];
+                    P.first_block = blocks;
+                    P.nblocks = cm.wblocks * cm.hblocks;
+                    P.wblocks = cm.wblocks;
+                    P.ncoef = cm.ncoef;
+                    P.offs_off = used + cm.offs_off;
+                    P.coef_off = used + cm.coef_off;
+                    P.plane_off = scratch_used;
+                    P.plane_bytes = (int64_t)cm.wblocks * 8 * cm.hblocks * 8;
+                    memcpy(P.qt, r->qt[c], sizeof P.qt);
+                    blocks += P.nblocks;
+                    if (c == 0) {
+                        D.yplane = P.plane_off;
+                        D.ystride = cm.wblocks * 8;
+                        D.yrows = cm.hblocks * 8;
+                    } else {
+                        D.cplane[c - 1] = P.plane_off;
+                        D.cstride = cm.wblocks * 8;
+                        D.crows = cm.hblocks * 8;
+                        D.cw = cm.dw;
+                        D.chh = cm.dh;
+                    }
+                    scratch_used += align16(P.plane_bytes);
+                }
+                const bool ok = D.W >= 1 && D.H >= 1 && D.W <= D.ystride && D.H <= D.yrows &&
+                                (D.ncomp == 1 || (D.cw >= 1 && D.chh >= 1 && D.cw <= D.cstride && D.chh <= D.crows)) &&
+                                scratch_used <= SLAB_SCRATCH && used + (int64_t)r->packed.size() <= SLAB_PAYLOAD;
+                if (!ok) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, paths[row]);
+                used += align16((int64_t)r->packed.size());
+                ++gpu_jpegs;
+            }
+            ++nimg;
+        }
+        // ---- upload + rebuild (+ forward pass) of this slab ----
+        hipStream_t st = ctx->stream;
+        ingest_image *d_imgs = (ingest_image *)ws->d_hdr;
+        ingest_plane *d_pls = (ingest_plane *)(ws->d_hdr + SLAB_IMAGES * sizeof(ingest_image));
+        ICL_HIP(ctx, hipMemcpyAsync(d_imgs, imgs, (size_t)nimg * sizeof(ingest_image), hipMemcpyHostToDevice, st));
+        if (npl) ICL_HIP(ctx, hipMemcpyAsync(d_pls, pls, (size_t)npl * sizeof(ingest_plane), hipMemcpyHostToDevice, st));
+        if (used) ICL_HIP(ctx, hipMemcpyAsync(ws->d_payload, pay, (size_t)used, hipMemcpyHostToDevice, st));
+        ICL_HIP(ctx, hipEventRecord(ws->ev_up[k & 1], st));
+        upload += (int64_t)nimg * (int64_t)sizeof(ingest_image) + (int64_t)npl * (int64_t)sizeof(ingest_plane) + used;
+        if (blocks) {
+            hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)icl_ceil_div(blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, npl,
+                               (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, ws->d_scratch, (int64_t)SLAB_SCRATCH, blocks);
+            ICL_HIP(ctx, hipGetLastError());
+        }
+        uint8_t *dst = mode == 0 ? d_u8 + first * ICL_IMG_BYTES : ws->d_img;
+        hipLaunchKernelGGL(jpeg_gather_resize_kernel, dim3((unsigned)icl_ceil_div(OUTW * OUTH, 256), (unsigned)nimg), dim3(256), 0, st, d_imgs,
+                           (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, dst);
+        ICL_HIP(ctx, hipGetLastError());
+        if (mode) {
+            float *d_dst = mode == 2 ? out + first * head : ws->d_emb;
+            ICL_TRY(icl_embed_dev_locked(ctx, ws->d_img, nimg, head, prec, d_dst)); // (ends with the stream synchronised)
+            if (!failed_rows.empty()) {
+                if (mode == 1) {
+                    ICL_HIP(ctx, hipMemcpyAsync(out + first * head, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
+                    ICL_HIP(ctx, hipStreamSynchronize(st));
+                    for (int32_t j : failed_rows) std::fill(out + (first + j) * head, out + (first + j + 1) * head, std::nanf(""));
+                } else {
+                    ICL_HIP(ctx, hipMemcpyAsync(ws->d_rows, failed_rows.data(), failed_rows.size() * 4, hipMemcpyHostToDevice, st));
+                    hipLaunchKernelGGL(fill_nan_rows_kernel, dim3((unsigned)icl_ceil_div(head, 256), (unsigned)failed_rows.size()), dim3(256), 0, st,
+                                       d_dst, (const int32_t *)ws->d_rows, (int)failed_rows.size(), head);
+                    ICL_HIP(ctx, hipGetLastError());
+                    ICL_HIP(ctx, hipStreamSynchronize(st)); // failed_rows is reused by the next slab
+                }
+            } else if (mode == 1) {
+                ICL_HIP(ctx, hipMemcpyAsync(out + first * head, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
+                ICL_HIP(ctx, hipStreamSynchronize(st));
+            }
+        }
+    }
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // ---- report ----
+    {
+        std::lock_guard<std::mutex> lk(m);
+        stop = true;
+    }
+    cv.notify_all();
+    for (auto &t : pool) t.join();
+    ctx->ingest_stats[0] = gpu_jpegs;
+    ctx->ingest_stats[1] = host_files;
+    ctx->ingest_stats[2] = upload;
+    ctx->ingest_decode_s = (double)decode_ns.load() * 1e-9;
+    for (int64_t i = 0; i < n; ++i)
+        if (res[(size_t)i] && res[(size_t)i]->kind == KIND_FAILED)
+            return icl_fail(ctx, res[(size_t)i]->rc ? res[(size_t)i]->rc : ICL_ERR_IO, "%s: file %lld of %lld: %s", what, (long long)i, (long long)n,
+                            res[(size_t)i]->err.c_str());
+    return ICL_OK;
+}
+
+extern "C" int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, uint8_t *d_out, int32_t *status)
+{
+    if (!ctx || n < 0 || (n && (!paths || !d_out)) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: bad argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: paths[%lld] is NULL", (long long)i);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return no_throw(ctx, "icl_load_images_224_dev", [&]() -> int {
+        ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
+        ctx->ingest_decode_s = 0;
+        if (n == 0) return ICL_OK;
+        return ingest_files(ctx, paths, n, threads, 0, d_out, 0, 0, nullptr, status, "icl_load_images_224_dev");
+    });
+}
+
+static int embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *out, int32_t *status, bool dev,
+                       const char *what)
+{
+    if (!ctx || n < 0 || (n && (!paths || !out)) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
+    if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16 && prec != ICL_PREC_BF16X3)
+        return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32, ICL_PREC_BF16 or ICL_PREC_BF16X3");
+    for (int64_t i = 0; i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
+    return no_throw(ctx, what, [&]() -> int {
+        ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
+        ctx->ingest_decode_s = 0;
+        if (n == 0) return ICL_OK;
+        return ingest_files(ctx, paths, n, threads, dev ? 2 : 1, nullptr, head, prec, out, status, what);
+    });
+}
+
+extern "C" int icl_embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *out, int32_t *status)
+{
+    return embed_files(ctx, paths, n, head, prec, threads, out, status, false, "icl_embed_files");
+}
+
+extern "C" int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *d_out, int32_t *status)
+{
+    return embed_files(ctx, paths, n, head, prec, threads, d_out, status, true, "icl_embed_files_dev");
+}
+
+extern "C" int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes, double *host_decode_s)
+{
+    if (!ctx) return ICL_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (gpu_jpegs) *gpu_jpegs = ctx->ingest_stats[0];
+    if (host_files) *host_files = ctx->ingest_stats[1];
+    if (upload_bytes) *upload_bytes = ctx->ingest_stats[2];
+    if (host_decode_s) *host_decode_s = ctx->ingest_decode_s;
+    return ICL_OK;
+}

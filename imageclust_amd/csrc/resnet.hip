@@ -1808,6 +1808,23 @@ extern "C" int icl_preprocess_u8(const uint8_t *hwc, float *nchw)
     return ICL_OK;
 }
 
+// source offsets and 11-bit weights of one axis of cv::resize(INTER_LINEAR) (float / double arithmetic: jpeg_gpu.hip uploads these
+// host-computed tables rather than recomputing them on the device)
+static void resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al)
+{
+    const double scale = (double)sn / dn;
+    for (int d = 0; d < dn; ++d) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)std::floor(f);
+        f -= s;
+        if (s < 0) { f = 0; s = 0; }
+        if (s >= sn - 1) { f = 0; s = sn - 1; }
+        ofs[d] = s;
+        al[(size_t)d * 2] = (short)std::lrint((1.f - f) * 2048.f);
+        al[(size_t)d * 2 + 1] = (short)std::lrint(f * 2048.f);
+    }
+}
+
 // cv::resize(INTER_LINEAR) for 8-bit images: half-pixel centres, 11-bit fixed-point coefficients, the two-pass
 // rounding of OpenCV's HResizeLinear/VResizeLinear<uchar> (embeddings.go:69 resizes every image to 224x224).
 static void resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh)
@@ -1828,21 +1845,8 @@ static void resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst,
     }
     std::vector<int> xofs((size_t)dw), yofs((size_t)dh);
     std::vector<short> xa((size_t)dw * 2), ya((size_t)dh * 2);
-    auto coeffs = [](int dn, int sn, std::vector<int> &ofs, std::vector<short> &al) {
-        const double scale = (double)sn / dn;
-        for (int d = 0; d < dn; ++d) {
-            float f = (float)((d + 0.5) * scale - 0.5);
-            int s = (int)std::floor(f);
-            f -= s;
-            if (s < 0) { f = 0; s = 0; }
-            if (s >= sn - 1) { f = 0; s = sn - 1; }
-            ofs[(size_t)d] = s;
-            al[(size_t)d * 2] = (short)std::lrint((1.f - f) * 2048.f);
-            al[(size_t)d * 2 + 1] = (short)std::lrint(f * 2048.f);
-        }
-    };
-    coeffs(dw, sw, xofs, xa);
-    coeffs(dh, sh, yofs, ya);
+    resize_coeffs(dw, sw, xofs.data(), xa.data());
+    resize_coeffs(dh, sh, yofs.data(), ya.data());
     std::vector<int> row0((size_t)dw * cn), row1((size_t)dw * cn);
     auto hrow = [&](int sy, std::vector<int> &out) {
         const uint8_t *S = src + (size_t)sy * sw * cn;
@@ -1956,6 +1960,12 @@ static int read_image(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb,
     fclose(f);
     return read_ppm(ctx, path, rgb, w, h);
 }
+
+// the batched file pipeline (jpeg_gpu.hip) shares the host path
+int icl_read_image_host(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h) { return read_image(ctx, path, rgb, w, h); }
+void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient) { apply_exif_orientation(rgb, w, h, orient); }
+void icl_resize_u8_host(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh) { resize_bilinear_u8(src, sw, sh, dst, dw, dh); }
+void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al) { resize_coeffs(dn, sn, ofs, al); }
 
 // No C++ exception may cross the C ABI (cgo / ctypes would terminate the host process): the ingest entry points allocate
 // buffers whose sizes come from files (no_throw: icl_common.h).

@@ -114,6 +114,15 @@ def GetImageEmbeddingsBatch(appCtx: AppContext, images_u8: np.ndarray, prec: int
     return appCtx.Net.ctx.embed_u8(images_u8, appCtx.Head, prec)
 
 
+def GetImageEmbeddingsFromFiles(appCtx: AppContext, paths: List[str], prec: int = _lib.PREC_BF16, head: int = 2048, threads: int = 0):
+    """Batched GetImageEmbedding over image files (workflow.go:149-185 without one goroutine per file) -> (E, status).
+
+    E is len(paths) x head fp32, row i for paths[i]; status[i] is 0 or the ICL_ERR_* code of file i, whose row is NaN.  Host threads
+    (0: up to 16) parse the JPEGs and run their entropy decoders; the GPU rebuilds the pixels and resizes them (icl_embed_files),
+    with results equal to GetImageEmbeddingsBatch on the PreprocessImage outputs.  PNG and PPM files are decoded on the host."""
+    return appCtx.Net.ctx.embed_files(list(paths), head, prec, threads)
+
+
 # ---- label vectors (embeddings.go:166-236): host-side glue, no GPU work -------------------------------------------
 def GenerateLabelVector(labels: List[str], labelSet: Dict[str, int]) -> np.ndarray:
     """embeddings.go:166-174: one-hot over the full label set; unknown labels are ignored."""

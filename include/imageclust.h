@@ -107,6 +107,28 @@ int icl_preprocess_u8(const uint8_t *hwc_rgb, float *nchw);
 int icl_preprocess_file(const char *path, float *nchw);
 /* The resize step alone (embeddings.go:69) on an interleaved u8 RGB image: cv::resize(src, dst, (dw, dh), 0, 0, INTER_LINEAR). */
 int icl_resize_u8(const uint8_t *src_rgb, int32_t sw, int32_t sh, uint8_t *dst_rgb, int32_t dw, int32_t dh);
+/* ---- batched file ingest: replaces the per-file decode of GetImageEmbedding (embeddings.go:46-116) as workflow.go:149-185 calls it ----
+ * paths[0..n): JPEG / PNG / PPM files, as icl_load_image_224 reads them.  threads: host decode threads
+ * (0 = min(16, hardware threads)).  status[i] = ICL_OK or the ICL_ERR_* code of file i (may be NULL).
+ * Returns ICL_OK when every file was read, else ICL_ERR_IO / _UNSUPPORTED naming the LOWEST failed
+ * index in icl_last_error; rows of failed files are NaN.  Row i always belongs to paths[i].
+ * Host workers parse each JPEG and run its entropy decoder (stage A); the GPU dequantises, runs the islow IDCT, upsamples the
+ * chroma, converts the colour, applies the EXIF orientation and resizes to 224x224, bit-identical to icl_load_image_224.  PNG, PPM
+ * and JPEGs too large for one staging slab are decoded and resized on the host.  Output does not depend on threads.
+ * icl_load_images_224_dev: d_out (device, on the context's stream) gets n x 224x224x3 u8 RGB rows, each equal to what
+ * icl_load_image_224 gives for its file; a failed file's row is left all ZERO (the u8 form of "NaN").  No model needed. */
+int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads,
+                            uint8_t *d_out /* n x 224x224x3 */, int32_t *status);
+/* replaces the loop of GetImageEmbedding calls of workflow.go:149-185: out (host) is n x head fp32, each row equal to icl_embed_u8 on
+ * the icl_load_image_224 output of its file; rows of failed files are NaN.  The _dev variant writes d_out on the device. */
+int icl_embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec,
+                    int32_t threads, float *out, int32_t *status);
+int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec,
+                        int32_t threads, float *d_out, int32_t *status);
+/* what the last files call did: JPEGs rebuilt on the GPU, files decoded on the host (PNG, PPM, fallbacks),
+ * bytes uploaded, host thread-seconds spent in stage A / host decode */
+int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes,
+                          double *host_decode_s);
 int icl_set_batch(icl_ctx *ctx, int batch); /* embed batch size, 1..1024 */
 /* Which bf16 convolution launches take the deep-pipelined 256 x 256 x 64 kernel (conv_p8_kernel: LDS-DMA kept in flight across raw
  * barriers, counted vmcnt, staggered wave groups) instead of the 128 x 128 two-stage kernels: ICL_CONV_P8_OFF never, ICL_CONV_P8_AUTO
