@@ -249,3 +249,92 @@ func PerformClusteringWithConstraints(embeddings [][]float32, productReferenceID
 	log.Printf("Clustering successful. Formed %d valid clusters.", len(clusterMap))
 	return clusterMap, true
 }
+
+// ClusteringJob is one PerformClusteringWithConstraints call of a batch.
+type ClusteringJob struct {
+	Embeddings          [][]float32
+	ProductReferenceIDs []string
+	MinSize, MaxSize    int
+}
+
+// ClusteringResult is what PerformClusteringWithConstraints returns for one job.
+type ClusteringResult struct {
+	Clusters map[int][]string
+	OK       bool
+}
+
+// PerformClusteringWithConstraintsBatch runs many independent PerformClusteringWithConstraints calls (exact mode) in one
+// icl_cluster_many call; result j equals PerformClusteringWithConstraints(jobs[j]...).
+func PerformClusteringWithConstraintsBatch(jobs []ClusteringJob) []ClusteringResult {
+	out := make([]ClusteringResult, len(jobs))
+	if len(jobs) == 0 {
+		return out
+	}
+	e, err := engine()
+	if err != nil {
+		log.Printf("Clustering engine error: %v", err)
+		return out
+	}
+	np := len(jobs)
+	eoff := make([]int64, np)
+	n := make([]int32, np)
+	d := make([]int32, np)
+	mn := make([]int32, np)
+	mx := make([]int32, np)
+	total, rows := 0, 0
+	for j, job := range jobs {
+		n[j] = int32(len(job.Embeddings))
+		if n[j] > 0 {
+			d[j] = int32(len(job.Embeddings[0]))
+		}
+		mn[j], mx[j] = int32(job.MinSize), int32(job.MaxSize)
+		eoff[j] = int64(total)
+		total += (int(n[j])*int(d[j]) + 3) / 4 * 4 // each problem on a 16-byte boundary
+		rows += int(n[j])
+	}
+	flat := make([]float32, total+1) // [][]float32 cannot cross cgo: one contiguous buffer
+	for j, job := range jobs {
+		for i, row := range job.Embeddings {
+			copy(flat[int(eoff[j])+i*int(d[j]):], row)
+		}
+	}
+	cid := make([]int32, rows+1)
+	rank := make([]int32, rows+1)
+	nc := make([]int32, np)
+	nm := make([]int32, np)
+	st := make([]int32, np)
+	for j := range st {
+		st[j] = -1 // stays -1 when the call fails before the problems run (a bad argument, no device memory)
+	}
+	rc := C.icl_cluster_many(e, C.int32_t(np), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(len(flat)),
+		(*C.int64_t)(unsafe.Pointer(&eoff[0])), (*C.int32_t)(unsafe.Pointer(&n[0])), (*C.int32_t)(unsafe.Pointer(&d[0])),
+		(*C.int32_t)(unsafe.Pointer(&mn[0])), (*C.int32_t)(unsafe.Pointer(&mx[0])), (*C.int32_t)(unsafe.Pointer(&cid[0])),
+		(*C.int32_t)(unsafe.Pointer(&rank[0])), (*C.int32_t)(unsafe.Pointer(&nc[0])), (*C.int32_t)(unsafe.Pointer(&nm[0])), nil,
+		(*C.int32_t)(unsafe.Pointer(&st[0])))
+	if rc != C.ICL_OK {
+		log.Printf("Clustering batch: %s", C.GoString(C.icl_last_error(e)))
+	}
+	off := 0
+	for j, job := range jobs {
+		if st[j] == C.ICL_OK {
+			clusterMap := make(map[int][]string, int(nc[j]))
+			sizes := make([]int, int(nc[j]))
+			for i := 0; i < int(n[j]); i++ {
+				if c := cid[off+i]; c >= 0 {
+					sizes[c]++
+				}
+			}
+			for c, s := range sizes {
+				clusterMap[c] = make([]string, s)
+			}
+			for i := 0; i < int(n[j]); i++ {
+				if c := cid[off+i]; c >= 0 {
+					clusterMap[int(c)][rank[off+i]] = job.ProductReferenceIDs[i]
+				}
+			}
+			out[j] = ClusteringResult{Clusters: clusterMap, OK: true}
+		}
+		off += int(n[j])
+	}
+	return out
+}

@@ -100,6 +100,8 @@ SYMBOLS = [
     ("icl_cluster_prefilled_dev", _int, [_vp, _vp, _i64, _i32, _i32, _i32, _int, _i64, _i64, _vp, _vp, _pi32]),
     ("icl_cluster", _int, [_vp, _vp, _i64, _i32, _i32, _i32, _int, _vp, _vp, _pi32]),
     ("icl_cluster_dev", _int, [_vp, _vp, _i64, _i32, _i32, _i32, _int, _vp, _vp, _pi32]),
+    ("icl_cluster_many", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
+    ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_last_merges", _i64, [_vp, _vp, _i64]),
     ("icl_last_merge_values", _i64, [_vp, _vp, _i64]),
     ("icl_distance_mfma_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i64]),
@@ -153,6 +155,41 @@ def check(ctx_handle, rc):
     if rc != ICL_OK:
         msg = load().icl_last_error(ctx_handle)
         raise ICLError(rc, msg.decode() if msg else "")
+
+
+def _unpack_many(pk, cid, rank, nc, nm, st, mg):
+    out = []
+    for p in range(len(pk["n"])):
+        a, b = int(pk["img_off"][p]), int(pk["img_off"][p + 1])
+        r = (cid[a:b].copy(), rank[a:b].copy(), int(nc[p]), int(st[p]))
+        if mg is not None:
+            r += (mg[2 * a:2 * a + 2 * int(nm[p])].reshape(-1, 2).copy(),)
+        out.append(r)
+    return out
+
+
+def pack_many(problems):
+    """The arguments of icl_cluster_many for problems = [(E, min_size, max_size), ...]: one float32 buffer holding every problem's rows,
+    each problem starting on a 16-byte boundary (the kernels' float4 loads then read its rows in place) -> dict(E, e_off, n, d, min_size,
+    max_size, img_off); problem p's images are [img_off[p], img_off[p + 1]) of the outputs."""
+    mats, off, pos = [], [], 0
+    for E, _, _ in problems:
+        E = np.asarray(E, np.float32)
+        if E.ndim != 2:
+            raise ValueError("each problem's E must be 2-D, got shape %s" % (E.shape,))
+        off.append(pos)
+        mats.append(E)
+        pos += (E.size + 3) // 4 * 4
+    if len(mats) == 1 and mats[0].size and mats[0].flags.c_contiguous:
+        buf = mats[0].reshape(-1)  # one problem: its own rows, not a copy
+    else:
+        buf = np.zeros(max(pos, 1), np.float32)
+        for E, o in zip(mats, off):
+            buf[o:o + E.size] = E.ravel()
+    n = np.array([E.shape[0] for E in mats], np.int32)
+    return dict(E=buf, e_off=np.array(off, np.int64), n=n, d=np.array([E.shape[1] for E in mats], np.int32),
+                min_size=np.array([int(p[1]) for p in problems], np.int32), max_size=np.array([int(p[2]) for p in problems], np.int32),
+                img_off=np.concatenate([[0], np.cumsum(n, dtype=np.int64)]))
 
 
 class Context:
@@ -458,6 +495,45 @@ class Context:
         check(self.h, self.L.icl_cluster(self.h, E.ctypes.data if E.size else None, n, d, min_size, max_size, update,
                                          cid.ctypes.data, rank.ctypes.data, C.byref(nc)))
         return cid[:n], rank[:n], nc.value
+
+    def cluster_many(self, problems, want_merges=False, raise_on_error=False):
+        """Many independent exact-mode cluster() calls in one (icl_cluster_many): problems = [(E, min_size, max_size), ...] -> a list of
+        (cluster_id, member_rank, n_clusters, status) per problem, each equal to what cluster() gives for that problem alone (status:
+        ICL_OK or the problem's error code, with rows of -1); want_merges=True appends the problem's merge log (n_merges x 2 creation
+        ids, as last_merges()).  raise_on_error=True raises the lowest failed problem's error instead."""
+        pk = pack_many(problems)
+        nprob = len(problems)
+        rows = int(pk["img_off"][-1])
+        cid = np.full(max(rows, 1), -1, np.int32)
+        rank = np.full(max(rows, 1), -1, np.int32)
+        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
+        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
+        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        rc = self.L.icl_cluster_many(self.h, nprob, pk["E"].ctypes.data, pk["E"].size, pk["e_off"].ctypes.data, pk["n"].ctypes.data,
+                                     pk["d"].ctypes.data, pk["min_size"].ctypes.data, pk["max_size"].ctypes.data, cid.ctypes.data,
+                                     rank.ctypes.data, nc.ctypes.data, nm.ctypes.data, mg.ctypes.data if want_merges else None, st.ctypes.data)
+        if rc != ICL_OK and (raise_on_error or (st[:nprob] < 0).any()):
+            check(self.h, rc)  # an argument or device error: no per-problem results
+        return _unpack_many(pk, cid, rank, nc, nm, st, mg)
+
+    def cluster_many_dev(self, d_E, e_len, e_off, n, d, min_size, max_size, want_merges=False):
+        """icl_cluster_many_dev on a device buffer of e_len floats; per-problem arrays as pack_many() gives them.  Same result as cluster_many()."""
+        pk = dict(e_off=np.ascontiguousarray(e_off, np.int64), n=np.ascontiguousarray(n, np.int32), d=np.ascontiguousarray(d, np.int32),
+                  min_size=np.ascontiguousarray(min_size, np.int32), max_size=np.ascontiguousarray(max_size, np.int32))
+        nprob = len(pk["n"])
+        pk["img_off"] = np.concatenate([[0], np.cumsum(pk["n"], dtype=np.int64)])
+        rows = int(pk["img_off"][-1])
+        cid = np.full(max(rows, 1), -1, np.int32)
+        rank = np.full(max(rows, 1), -1, np.int32)
+        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
+        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
+        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        rc = self.L.icl_cluster_many_dev(self.h, nprob, _vp(d_E), int(e_len), pk["e_off"].ctypes.data, pk["n"].ctypes.data, pk["d"].ctypes.data,
+                                         pk["min_size"].ctypes.data, pk["max_size"].ctypes.data, cid.ctypes.data, rank.ctypes.data,
+                                         nc.ctypes.data, nm.ctypes.data, mg.ctypes.data if want_merges else None, st.ctypes.data)
+        if rc != ICL_OK and (st[:nprob] < 0).any():
+            check(self.h, rc)
+        return _unpack_many(pk, cid, rank, nc, nm, st, mg)
 
     def cluster_dev(self, d_E, n, d, min_size, max_size, update=UPDATE_EXACT):
         cid = np.full(max(n, 1), -1, np.int32)

@@ -137,6 +137,27 @@ def PerformClusteringWithConstraints(embeddings, productReferenceIDs: List[str],
     return clusters_as_map(cid, rank, productReferenceIDs), True
 
 
+def PerformClusteringWithConstraintsMany(jobs, ctx: Optional[_lib.Context] = None) -> List[Tuple[Optional[Dict[int, List[str]]], bool]]:
+    """Many PerformClusteringWithConstraints calls in one (icl_cluster_many, exact mode): jobs = [(embeddings, productReferenceIDs,
+    minSize, maxSize), ...] -> [(map, ok), ...], each entry what PerformClusteringWithConstraints returns for that job."""
+    ctx = ctx or default_context()
+    probs = []
+    for emb, _, mn, mx in jobs:
+        E = np.asarray(emb, np.float32)
+        if E.ndim != 2:
+            E = E.reshape(len(emb), -1)
+        probs.append((E, mn, mx))
+    out = []
+    for (_, ids, _, _), (cid, rank, _, st) in zip(jobs, ctx.cluster_many(probs)):
+        if st == _lib.ICL_ERR_CONSTRAINT:
+            out.append((None, False))
+        elif st != _lib.ICL_OK:
+            raise _lib.ICLError(st, "icl_cluster_many: a problem failed with code %d" % st)
+        else:
+            out.append((clusters_as_map(cid, rank, ids), True))
+    return out
+
+
 def clusters_as_map(cluster_id, member_rank, ids) -> Dict[int, List[str]]:
     """Canonical (cluster_id, member_rank) -> map[int][]string of clustering.go:265-280."""
     out: Dict[int, List[str]] = {}

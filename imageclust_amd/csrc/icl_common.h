@@ -29,6 +29,7 @@ struct icl_pending_event {
 struct icl_model;  // resnet.hip
 struct icl_ward_ws; // ward.hip
 struct icl_ingest_ws; // jpeg_gpu.hip
+struct icl_many_ws; // ward_many.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -113,6 +114,7 @@ struct icl_ctx {
     int64_t *ward_rowoff = nullptr; // row offsets of the packed triangle for ranks that only compute distance rows (ward.hip)
     int64_t ward_rowoff_n = 0;
     void *file_batcher = nullptr; // icl_embed_file's coalescing queue (resnet.hip)
+    icl_many_ws *many = nullptr; // workspace of icl_cluster_many (ward_many.hip; created on first use)
     icl_ingest_ws *ingest = nullptr; // buffers of the batched file path (jpeg_gpu.hip; created on first use)
     int64_t ingest_stats[3] = {0, 0, 0}; // last batched file call: JPEGs rebuilt on the GPU, files decoded on the host, bytes uploaded
     double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode
@@ -167,6 +169,7 @@ void icl_model_free(icl_ctx *ctx);
 void icl_ward_free(icl_ctx *ctx);
 void icl_file_batcher_free(icl_ctx *ctx);
 void icl_ingest_free(icl_ctx *ctx);
+void icl_many_free(icl_ctx *ctx);
 
 static inline int64_t icl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -38,6 +38,7 @@
 
 #include "icl_common.h"
 #include "mfma_tile.h"
+#include "ward_value.h" // ward_sqdist_thread, ward_pair_value, ward_scale, ward_merge_elem (shared with ward_many.hip)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #include <algorithm>
@@ -688,55 +689,6 @@ __device__ __forceinline__ float wupper(float L, int a, int b, const wrefine &rf
         E = rf.ceps * ns;
     return (L * (1.0f + 3.0f * g) + 2.0001f * E + 2e-30f) * (1.0f + 2.0f * g);
 }
-// sum_k fl(fl(x_k - y_k)^2), strictly in k order, by ONE thread (d % 4 == 0): eight 16-byte loads of each row are in flight before
-// the first of them is used -- the loads depend on nothing, but issued one k-group at a time each waits for the round trip of the
-// previous one (a row pair took ~100 us that way)
-__device__ __forceinline__ float ward_sqdist_thread(const float *__restrict__ x, const float *__restrict__ y, int d)
-{
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *y4 = reinterpret_cast<const float4 *>(y);
-    const int ng = d >> 2;
-    float s = 0.0f;
-    int g = 0;
-    for (; g + 8 <= ng; g += 8) {
-        float4 xv[8], yv[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            xv[q] = x4[g + q];
-            yv[q] = y4[g + q];
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            float df = xv[q].x - yv[q].x; // clustering.go:139
-            float p = df * df;            // :154 product (rounded)
-            s = s + p;                    // :154 sum (rounded), strictly in k order
-            df = xv[q].y - yv[q].y;
-            p = df * df;
-            s = s + p;
-            df = xv[q].z - yv[q].z;
-            p = df * df;
-            s = s + p;
-            df = xv[q].w - yv[q].w;
-            p = df * df;
-            s = s + p;
-        }
-    }
-    for (; g < ng; ++g) {
-        const float4 xv = x4[g], yv = y4[g];
-        float df = xv.x - yv.x;
-        float p = df * df;
-        s = s + p;
-        df = xv.y - yv.y;
-        p = df * df;
-        s = s + p;
-        df = xv.z - yv.z;
-        p = df * df;
-        s = s + p;
-        df = xv.w - yv.w;
-        p = df * df;
-        s = s + p;
-    }
-    return s;
-}
 // WardDistance of two SINGLETONS from their embeddings (clustering.go:136-157 with sizes 1, 1): sequential, unfused fp32
 __device__ __forceinline__ float ward_singleton_pair(const float *__restrict__ E, int d, int a, int b)
 {
@@ -756,23 +708,6 @@ __device__ __forceinline__ float ward_singleton_pair(const float *__restrict__ E
     return (num / den) * s;                              // :144
 }
 
-// WardDistance of two clusters from their centroids (clustering.go:136-157): what the exact update kernels compute per entry
-__device__ __forceinline__ float ward_pair_value(const float *__restrict__ x, const float *__restrict__ y, int d, int sx, int sy)
-{
-    float s = 0.0f;
-    if ((d & 3) == 0) {
-        s = ward_sqdist_thread(x, y, d);
-    } else {
-        for (int k = 0; k < d; ++k) {
-            const float df = x[k] - y[k];
-            const float p = df * df;
-            s = s + p;
-        }
-    }
-    const float num = (float)((int64_t)sx * (int64_t)sy); // :142
-    const float den = (float)(sx + sy);                    // :143
-    return (num / den) * s;                                // :144
-}
 // The same sum by a whole wave (d % 4 == 0; call with all 64 lanes active; the result is wave-uniform): the lanes load 64 k-groups
 // at a time (two coalesced 1 KB loads), form the rounded squares fl(fl(x_k - y_k)^2) side by side and park them in the wave's
 // 1 KB of LDS; the running sum then takes them strictly in k order from broadcast 16-byte reads -- the only serial part is the
@@ -825,12 +760,6 @@ __device__ __forceinline__ float ward_sqdist_wave(const float *__restrict__ x, c
     return s;
 }
 // where the centroid of cluster `id` stands during the merge loop (singletons of a singleton row: straight from E)
-__device__ __forceinline__ float ward_scale(float s, int sx, int sy)
-{
-    const float num = (float)((int64_t)sx * (int64_t)sy); // :142
-    const float den = (float)(sx + sy);                    // :143
-    return (num / den) * s;                                // :144
-}
 // centroid and size of cluster `id` for an exact evaluation: singletons straight from E, merged clusters (only in rows of lb mode) from Crow
 __device__ __forceinline__ const float *wcent(const wrefine &rf, int id)
 {
@@ -1796,10 +1725,7 @@ __global__ __launch_bounds__(1024) void ward_finish_kernel(int64_t n, int d, int
     float *ra = Crow + (int64_t)slot_a * d;
     const float *rb = Crow + (int64_t)slot_b * d;
     for (int k = threadIdx.x; k < d; k += blockDim.x) {
-        const float pa = fa * ra[k];
-        const float pb = fb * rb[k];
-        const float sm = pa + pb;
-        const float cv = sm / fs;
+        const float cv = ward_merge_elem(fa, ra[k], fb, rb[k], fs);
         cnew[k] = cv;
         ra[k] = cv;                        // the new cluster inherits a's slot
         CT[ct4_off(k >> 2, S, slot_a) + (k & 3)] = cv;
@@ -2751,10 +2677,10 @@ __global__ __launch_bounds__(WB_FD_THREADS) void ward_finish_data_kernel(int d, 
             const int j = c0 + q < np ? c0 + q : 0;
             const float fa = (float)pk_sa[j], fb = (float)pk_sb[j], fs = (float)(pk_sa[j] + pk_sb[j]);
             float4 o;
-            { const float pa = fa * av.x; const float pb = fb * bv.x; const float sm = pa + pb; o.x = sm / fs; }
-            { const float pa = fa * av.y; const float pb = fb * bv.y; const float sm = pa + pb; o.y = sm / fs; }
-            { const float pa = fa * av.z; const float pb = fb * bv.z; const float sm = pa + pb; o.z = sm / fs; }
-            { const float pa = fa * av.w; const float pb = fb * bv.w; const float sm = pa + pb; o.w = sm / fs; }
+            o.x = ward_merge_elem(fa, av.x, fb, bv.x, fs);
+            o.y = ward_merge_elem(fa, av.y, fb, bv.y, fs);
+            o.z = ward_merge_elem(fa, av.z, fb, bv.z, fs);
+            o.w = ward_merge_elem(fa, av.w, fb, bv.w, fs);
             return o;
         };
         auto st_pp = [&](int q, const float4 &o0, const float4 &o1) { // picks c0+q (even) and c0+q+1: rows of cnewK + their interleaved image
@@ -4682,10 +4608,10 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
                 for (int j = 0; j < WB_K; ++j) {
                     if (j < np) {
                         float4 o;
-                        { const float pa = fa[j] * av[j].x; const float pb = fb[j] * bv[j].x; const float sm = pa + pb; o.x = sm / fs[j]; }
-                        { const float pa = fa[j] * av[j].y; const float pb = fb[j] * bv[j].y; const float sm = pa + pb; o.y = sm / fs[j]; }
-                        { const float pa = fa[j] * av[j].z; const float pb = fb[j] * bv[j].z; const float sm = pa + pb; o.z = sm / fs[j]; }
-                        { const float pa = fa[j] * av[j].w; const float pb = fb[j] * bv[j].w; const float sm = pa + pb; o.w = sm / fs[j]; }
+                        o.x = ward_merge_elem(fa[j], av[j].x, fb[j], bv[j].x, fs[j]);
+                        o.y = ward_merge_elem(fa[j], av[j].y, fb[j], bv[j].y, fs[j]);
+                        o.z = ward_merge_elem(fa[j], av[j].z, fb[j], bv[j].z, fs[j]);
+                        o.w = ward_merge_elem(fa[j], av[j].w, fb[j], bv[j].w, fs[j]);
                         reinterpret_cast<float4 *>(cnewK + j * cn_stride)[g] = o;
                     }
                 }
@@ -4701,10 +4627,7 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
 #pragma unroll
             for (int j = 0; j < WB_K; ++j) {
                 if (j < np) {
-                    const float pa = fa[j] * av[j];
-                    const float pb = fb[j] * bv[j];
-                    const float sm = pa + pb;
-                    cnewK[j * cn_stride + k] = sm / fs[j];
+                    cnewK[j * cn_stride + k] = ward_merge_elem(fa[j], av[j], fb[j], bv[j], fs[j]);
                 }
             }
         }
@@ -5019,8 +4942,9 @@ extern "C" int icl_find_closest(icl_ctx *ctx, const float *D, int64_t n, int64_t
 // Build the reference's final cluster list from the merge log (clustering.go:265-280 and SURVEY.md 8a C11):
 // surviving singletons in index order, then merged clusters in creation order; members of Merge(a,b) are
 // a's then b's (:31); clusters below min_size are dropped and consume no id.
-static int assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const std::vector<int32_t> &pairs,
-                      int64_t nmerge, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters)
+// (Also ward_many.hip's rule, whichever route a problem takes.)
+int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const std::vector<int32_t> &pairs,
+                        int64_t nmerge, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters)
 {
     const int64_t M = n + nmerge;
     std::vector<int32_t> left((size_t)M, -1), right((size_t)M, -1), size((size_t)M, 1);
@@ -5619,7 +5543,7 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
     ctx->last_merge_ms = ms12;
     icl_prof_collect(ctx);
     shg.ok = true; // the merge loop is over: nobody waits for this replica any more
-    int rc = assign_ids(ctx, n, min_size, max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
+    int rc = icl_ward_assign_ids(ctx, n, min_size, max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
     ctx->last_merges.swap(pairs);
     return rc;
 }
@@ -5771,6 +5695,15 @@ extern "C" int icl_cluster_prefilled_dev(icl_ctx *ctx, const float *d_E, int64_t
     });
 }
 
+// icl_cluster_many's problems above its cap (ward_many.hip), ctx->mu held: exact mode on the whole GPU; *merges receives the merge log
+int icl_ward_cluster_exact(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int32_t *cluster_id,
+                           int32_t *member_rank, int32_t *n_clusters, std::vector<int32_t> *merges)
+{
+    const int rc = cluster_locked(ctx, d_E, n, d, min_size, max_size, ICL_UPDATE_EXACT, cluster_id, member_rank, n_clusters);
+    merges->assign(ctx->last_merges.begin(), ctx->last_merges.end());
+    return rc;
+}
+
 extern "C" int icl_set_ward_options(icl_ctx *ctx, int dist_mode)
 {
     if (!ctx || dist_mode < ICL_DIST_AUTO || dist_mode > ICL_DIST_LWBOUND) return icl_fail(ctx, ICL_ERR_ARG, "icl_set_ward_options: bad argument");
@@ -5893,10 +5826,7 @@ __global__ void merge_centroid_kernel(const float *__restrict__ ca, float fa, co
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= d) return;
-    const float pa = fa * ca[k];
-    const float pb = fb * cb[k];
-    const float s = pa + pb;
-    out[k] = s / fs;
+    out[k] = ward_merge_elem(fa, ca[k], fb, cb[k], fs);
 }
 
 extern "C" int icl_merge_centroid(icl_ctx *ctx, const float *ca, int64_t sa, const float *cb, int64_t sb, int32_t d, float *out)

@@ -258,6 +258,26 @@ int icl_cluster(icl_ctx *ctx, const float *E, int64_t n, int32_t d, int32_t min_
                 int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters);
 int icl_cluster_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size,
                     int update, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters);
+/* Many independent PerformClusteringWithConstraints calls (clustering.go:198-284) in one, exact mode only -- the serving pattern of
+ * the reference, where every request clusters its own few hundred images.  Problem p clusters n[p] rows of d[p] floats that start at
+ * float offset e_off[p] of E (rows contiguous); E holds e_len floats and every problem's rows must lie inside it.  Problem p's images
+ * occupy [img_off(p), img_off(p) + n[p]) of cluster_id / member_rank, where img_off(p) = n[0] + ... + n[p-1].  Per problem, the results
+ * are exactly what icl_cluster(E_p, n[p], d[p], min_size[p], max_size[p], ICL_UPDATE_EXACT) gives: cluster_id, member_rank,
+ * n_clusters[p] and the merge log, bit for bit.  status[p] = ICL_OK or that problem's error (ICL_ERR_CONSTRAINT for the reference's
+ * (nil,false)); a failed problem's rows are -1 and its n_clusters[p] and n_merges[p] are 0.  merges (may be NULL): problem p's merge
+ * log, pairs of creation ids as icl_last_merges gives them, at offset 2*img_off(p); n_merges[p] holds its length in pairs.
+ * Returns ICL_OK when every problem succeeded; otherwise the code of the LOWEST failed problem, which icl_last_error names.  A bad
+ * argument (null pointer, nprob < 0, e_len < 0, negative n or d, rows outside E) returns ICL_ERR_ARG and writes nothing.  Problems of
+ * up to 256 rows run together, one workgroup each (ward_many.hip); larger ones, and a lone small one, run one at a time on the whole
+ * GPU, as icl_cluster does.
+ * The call leaves what icl_last_merges, icl_last_merge_values and icl_last_ward_* report about the last icl_cluster unchanged.
+ * The _dev variant takes E (e_len floats) on the context's device; everything else stays in host memory. */
+int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *n, const int32_t *d,
+                     const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters,
+                     int32_t *n_merges, int32_t *merges, int32_t *status);
+int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *n, const int32_t *d,
+                         const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters,
+                         int32_t *n_merges, int32_t *merges, int32_t *status);
 /* workflow.go:84-94 on one GPU in one call: embed n resident images (2048-d pooled head, into d_E: device, n x 2048) and
  * cluster them.  flags & ICL_FUSE_OVERLAP: the distance rows of already-embedded images are computed on a side stream of the
  * context while later batches embed (same kernels, same results as icl_embed_u8_dev + icl_cluster_dev, bit for bit). */
