@@ -1,0 +1,217 @@
+// image_io.hip -- host-side image ingest: PreprocessImage (/root/reference/internal/embeddings/embeddings.go:46-116), i.e.
+// gocv.IMRead(IMReadColor) for the formats this build decodes (JPEG: jpeg_decode.hip, PNG: png_decode.hip, binary PPM here),
+// cv::imread's EXIF orientation, the OpenCV-compatible 8-bit resize to 224x224 and the RGB/255 NCHW blob.  The pixel arithmetic
+// lives in ingest_pixels.h, shared with the GPU rebuild of the batched file path (jpeg_gpu.hip), which also calls the file
+// reader, the orientation and the resize (tables) below (jpeg_stage.h).
+#include "icl_common.h"
+#include "ingest_pixels.h"
+#include "jpeg_stage.h"
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+bool icl_is_png(const uint8_t *data, size_t len); // png_decode.hip
+int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H);
+
+extern "C" int icl_preprocess_u8(const uint8_t *hwc, float *nchw)
+{
+    if (!hwc || !nchw) return ICL_ERR_ARG;
+    const float sc = (float)(1.0 / 255.0);
+    for (int y = 0; y < ICL_IMG_H; ++y)
+        for (int x = 0; x < ICL_IMG_W; ++x)
+            for (int c = 0; c < 3; ++c) nchw[((size_t)c * ICL_IMG_H + y) * ICL_IMG_W + x] = (float)hwc[((size_t)y * ICL_IMG_W + x) * 3 + c] * sc;
+    return ICL_OK;
+}
+
+// source offsets and 11-bit weights of one axis of cv::resize(INTER_LINEAR) (float / double arithmetic: jpeg_gpu.hip uploads these
+// host-computed tables rather than recomputing them on the device)
+void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al)
+{
+    const double scale = (double)sn / dn;
+    for (int d = 0; d < dn; ++d) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)std::floor(f);
+        f -= s;
+        if (s < 0) { f = 0; s = 0; }
+        if (s >= sn - 1) { f = 0; s = sn - 1; }
+        ofs[d] = s;
+        al[(size_t)d * 2] = (short)std::lrint((1.f - f) * 2048.f);
+        al[(size_t)d * 2 + 1] = (short)std::lrint(f * 2048.f);
+    }
+}
+
+// cv::resize(INTER_LINEAR) for 8-bit RGB images: half-pixel centres, 11-bit fixed-point coefficients, OpenCV's two-pass rounding,
+// or INTER_AREA for an exact 2x2 decimation (embeddings.go:69 resizes every image to 224x224)
+void icl_resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh)
+{
+    const int cn = 3;
+    if (icl_resize_is_area(sw, sh, dw, dh)) {
+        for (int y = 0; y < dh; ++y) {
+            const uint8_t *r0 = src + (size_t)(2 * y) * sw * cn, *r1 = r0 + (size_t)sw * cn;
+            for (int x = 0; x < dw; ++x)
+                for (int c = 0; c < cn; ++c)
+                    dst[((size_t)y * dw + x) * cn + c] = icl_area_mean(r0[(2 * x) * cn + c], r0[(2 * x + 1) * cn + c], r1[(2 * x) * cn + c], r1[(2 * x + 1) * cn + c]);
+        }
+        return;
+    }
+    std::vector<int32_t> xofs((size_t)dw), yofs((size_t)dh);
+    std::vector<int16_t> xa((size_t)dw * 2), ya((size_t)dh * 2);
+    icl_resize_coeffs(dw, sw, xofs.data(), xa.data());
+    icl_resize_coeffs(dh, sh, yofs.data(), ya.data());
+    for (int dy = 0; dy < dh; ++dy) {
+        const int sy = yofs[(size_t)dy], sy1 = std::min(sy + 1, sh - 1);
+        const uint8_t *r0 = src + (size_t)sy * sw * cn, *r1 = src + (size_t)sy1 * sw * cn;
+        const int b0 = ya[(size_t)dy * 2], b1 = ya[(size_t)dy * 2 + 1];
+        for (int dx = 0; dx < dw; ++dx) {
+            const int sx = xofs[(size_t)dx], sx1 = std::min(sx + 1, sw - 1);
+            const int a0 = xa[(size_t)dx * 2], a1 = xa[(size_t)dx * 2 + 1];
+            for (int c = 0; c < cn; ++c)
+                dst[((size_t)dy * dw + dx) * cn + c] = icl_resize_linear(r0[sx * cn + c], r0[sx1 * cn + c], r1[sx * cn + c], r1[sx1 * cn + c], a0, a1, b0, b1);
+        }
+    }
+}
+
+static int read_ppm(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
+    auto token = [&](int &v) -> bool {
+        int c;
+        do {
+            c = fgetc(f);
+            if (c == '#')
+                while (c != '\n' && c != EOF) c = fgetc(f);
+        } while (c == ' ' || c == '\n' || c == '\r' || c == '\t');
+        if (c < '0' || c > '9') return false;
+        v = 0;
+        while (c >= '0' && c <= '9') {
+            v = v * 10 + (c - '0');
+            c = fgetc(f);
+        }
+        return true;
+    };
+    int maxv = 0;
+    bool ok = fgetc(f) == 'P' && fgetc(f) == '6' && token(w) && token(h) && token(maxv) && maxv == 255 && w > 0 && h > 0 && w <= 16384 && h <= 16384;
+    if (ok) {
+        rgb.resize((size_t)w * h * 3);
+        ok = fread(rgb.data(), 1, rgb.size(), f) == rgb.size();
+    }
+    fclose(f);
+    if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Only JPEG (Huffman; baseline or progressive), PNG and binary PPM (P6, maxval 255) are decoded by this build", path);
+    return ICL_OK;
+}
+
+// cv::imread rotates / mirrors the decoded pixels by the file's EXIF orientation (icl_exif_source, ingest_pixels.h)
+void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient)
+{
+    if (orient <= 1 || orient > 8) return;
+    const int sw = w, sh = h;
+    const bool swap = icl_exif_swaps_axes(orient);
+    const int dw = swap ? sh : sw, dh = swap ? sw : sh;
+    std::vector<uint8_t> out((size_t)dw * dh * 3);
+    for (int y = 0; y < dh; ++y)
+        for (int x = 0; x < dw; ++x) {
+            int sx, sy;
+            icl_exif_source(orient, sw, sh, x, y, sx, sy);
+            memcpy(&out[((size_t)y * dw + x) * 3], &rgb[((size_t)sy * sw + sx) * 3], 3);
+        }
+    rgb.swap(out);
+    w = dw;
+    h = dh;
+}
+
+int icl_image_file_read(const char *path, std::vector<uint8_t> &file)
+{
+    std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "rb"), fclose);
+    if (!f) return ICL_IMAGE_UNREADABLE;
+    unsigned char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const size_t got = fread(magic, 1, 8, f.get());
+    int fmt = ICL_IMAGE_PPM;
+    if (got == 8 && icl_is_png(magic, 8)) fmt = ICL_IMAGE_PNG;
+    else if (got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8) fmt = ICL_IMAGE_JPEG;
+    if (fmt == ICL_IMAGE_PPM) return fmt; // read_ppm parses the file itself
+    fseek(f.get(), 0, SEEK_END);
+    const long sz = ftell(f.get());
+    fseek(f.get(), 0, SEEK_SET);
+    file.resize((size_t)std::max<long>(sz, 0));
+    return sz > 0 && fread(file.data(), 1, file.size(), f.get()) == file.size() ? fmt : ICL_IMAGE_UNREADABLE;
+}
+
+int icl_image_decode(icl_ctx *ctx, const char *path, int fmt, const std::vector<uint8_t> &file, std::vector<uint8_t> &rgb, int &w, int &h)
+{
+    switch (fmt) {
+    case ICL_IMAGE_PNG: return icl_png_decode(ctx, file.data(), file.size(), path, rgb, w, h);
+    case ICL_IMAGE_JPEG: {
+        int orient = 1;
+        ICL_TRY(icl_jpeg_decode(ctx, file.data(), file.size(), path, rgb, w, h, orient));
+        icl_apply_exif_orientation(rgb, w, h, orient);
+        return ICL_OK;
+    }
+    case ICL_IMAGE_PPM: return read_ppm(ctx, path, rgb, w, h);
+    default: return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
+    }
+}
+
+// IMRead(IMReadColor) of embeddings.go:50
+static int read_image(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
+{
+    std::vector<uint8_t> file;
+    const int fmt = icl_image_file_read(path, file);
+    return icl_image_decode(ctx, path, fmt, file, rgb, w, h);
+}
+
+int icl_read_image_224(icl_ctx *ctx, const char *path, uint8_t *out)
+{
+    std::vector<uint8_t> px;
+    int w = 0, h = 0;
+    ICL_TRY(read_image(ctx, path, px, w, h));
+    icl_resize_bilinear_u8(px.data(), w, h, out, ICL_IMG_W, ICL_IMG_H);
+    return ICL_OK;
+}
+
+// No C++ exception may cross the C ABI (cgo / ctypes would terminate the host process): the ingest entry points allocate
+// buffers whose sizes come from files (no_throw: icl_common.h).
+extern "C" int icl_decode_image_file(const char *path, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h)
+{
+    if (!path || !w || !h) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: bad argument");
+    return no_throw(nullptr, "icl_decode_image_file", [&]() -> int {
+        std::vector<uint8_t> px;
+        int iw = 0, ih = 0;
+        ICL_TRY(read_image(nullptr, path, px, iw, ih));
+        *w = iw;
+        *h = ih;
+        if (rgb) {
+            if (cap_bytes < (int64_t)px.size()) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: buffer too small");
+            memcpy(rgb, px.data(), px.size());
+        }
+        return ICL_OK;
+    });
+}
+
+extern "C" int icl_load_image_224(const char *path, uint8_t *out)
+{
+    if (!path || !out) return icl_fail(nullptr, ICL_ERR_ARG, "icl_load_image_224: bad argument");
+    return no_throw(nullptr, "icl_load_image_224", [&]() -> int { return icl_read_image_224(nullptr, path, out); });
+}
+
+// cv::resize on an arbitrary u8 RGB image (the resize step of PreprocessImage alone; tests pin it to hand-derived vectors)
+extern "C" int icl_resize_u8(const uint8_t *src, int32_t sw, int32_t sh, uint8_t *dst, int32_t dw, int32_t dh)
+{
+    if (!src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1) return icl_fail(nullptr, ICL_ERR_ARG, "icl_resize_u8: bad argument");
+    return no_throw(nullptr, "icl_resize_u8", [&]() -> int {
+        icl_resize_bilinear_u8(src, sw, sh, dst, dw, dh);
+        return ICL_OK;
+    });
+}
+
+// PreprocessImage(imagePath) (embeddings.go:46-116): file -> the 1x3x224x224 fp32 NCHW blob.
+extern "C" int icl_preprocess_file(const char *path, float *nchw)
+{
+    if (!path || !nchw) return icl_fail(nullptr, ICL_ERR_ARG, "icl_preprocess_file: bad argument");
+    return no_throw(nullptr, "icl_preprocess_file", [&]() -> int {
+        std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
+        ICL_TRY(icl_read_image_224(nullptr, path, img.data()));
+        return icl_preprocess_u8(img.data(), nchw);
+    });
+}

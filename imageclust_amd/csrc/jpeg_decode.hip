@@ -3,16 +3,18 @@
 // Replaces gocv.IMRead(imagePath, IMReadColor) in PreprocessImage
 //   (/root/reference/internal/embeddings/embeddings.go:50), i.e. OpenCV imgcodecs -> libjpeg(-turbo) with its default
 // settings: integer "islow" IDCT, "fancy" (triangle) chroma upsampling and the fixed-point YCbCr->RGB tables.  Those
-// three algorithms are public (IJG libjpeg: jidctint.c, jdsample.c, jdcolor.c) and are restated here so that decoded
-// pixels are bit-identical to libjpeg-turbo's (checked against Pillow's bundled libjpeg-turbo in
+// three algorithms are public (IJG libjpeg: jidctint.c, jdsample.c, jdcolor.c) and are restated in ingest_pixels.h so that
+// decoded pixels are bit-identical to libjpeg-turbo's (checked against Pillow's bundled libjpeg-turbo in
 // tests/test_jpeg_decode.py).  Supported: 8-bit baseline / extended sequential (SOF0, SOF1) and PROGRESSIVE (SOF2:
 // spectral selection + successive approximation, ITU T.81 annex G) Huffman streams, interleaved or one scan per
 // component, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 sampling, restart intervals, JFIF / Adobe-transform markers.
 // Every scan decodes into per-component coefficient arrays; dequantisation + IDCT run once after the last scan.
 // Two stages (jpeg_stage.h): stage A parses the file and runs the entropy decoder (every check of a hostile file is made
-// here); stage B dequantises, runs the IDCT, upsamples the chroma and converts the colour.  jpeg_gpu.hip runs stage B on the GPU.
+// here); stage B dequantises, runs the IDCT, upsamples the chroma and converts the colour.  jpeg_gpu.hip runs stage B on the GPU
+// with the same per-sample rules (ingest_pixels.h).
 // Arithmetic coding, lossless, 12-bit and CMYK return ICL_ERR_UNSUPPORTED.
 #include "icl_common.h"
+#include "ingest_pixels.h"
 #include "jpeg_stage.h"
 
 #include <cstring>
@@ -111,107 +113,23 @@ inline int huff_decode(bit_reader &br, const huff_table &t)
 
 inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
-const uint8_t zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-inline uint8_t clamp8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
-// IJG jidctint.c jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2.  coef is dequantized, natural order.
+// IJG jidctint.c jpeg_idct_islow (ingest_pixels.h) on one block.  coef is dequantised, natural order.
 void idct_islow(const int *coef, uint8_t *out, int stride)
 {
-    constexpr int CB = 13, P1 = 2;
-    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299, F1_847 = 15137,
-                  F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
-    auto descale = [](long x, int n) { return (int)((x + (1L << (n - 1))) >> n); };
-    int ws[64];
+    int ws[64], px[8];
     for (int c = 0; c < 8; ++c) {
         const int *in = coef + c;
-        int *w = ws + c;
-        if (!(in[8] | in[16] | in[24] | in[32] | in[40] | in[48] | in[56])) {
-            const int dc = in[0] * (1 << P1);
-            for (int r = 0; r < 8; ++r) w[8 * r] = dc;
+        if (!(in[8] | in[16] | in[24] | in[32] | in[40] | in[48] | in[56])) { // all AC terms zero: the column is dc << PASS1_BITS
+            const int dc = in[0] * (1 << ICL_IDCT_P1);
+            for (int r = 0; r < 8; ++r) ws[c + 8 * r] = dc;
             continue;
         }
-        long z2 = in[16], z3 = in[48];
-        long z1 = (z2 + z3) * F0_541;
-        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-        z2 = in[0];
-        z3 = in[32];
-        long tmp0 = (z2 + z3) * (1L << CB), tmp1 = (z2 - z3) * (1L << CB);
-        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = in[56];
-        tmp1 = in[40];
-        tmp2 = in[24];
-        tmp3 = in[8];
-        z1 = tmp0 + tmp3;
-        z2 = tmp1 + tmp2;
-        z3 = tmp0 + tmp2;
-        long z4 = tmp1 + tmp3;
-        const long z5 = (z3 + z4) * F1_175;
-        tmp0 *= F0_298;
-        tmp1 *= F2_053;
-        tmp2 *= F3_072;
-        tmp3 *= F1_501;
-        z1 *= -F0_899;
-        z2 *= -F2_562;
-        z3 *= -F1_961;
-        z4 *= -F0_390;
-        z3 += z5;
-        z4 += z5;
-        tmp0 += z1 + z3;
-        tmp1 += z2 + z4;
-        tmp2 += z2 + z3;
-        tmp3 += z1 + z4;
-        w[0] = descale(tmp10 + tmp3, CB - P1);
-        w[56] = descale(tmp10 - tmp3, CB - P1);
-        w[8] = descale(tmp11 + tmp2, CB - P1);
-        w[48] = descale(tmp11 - tmp2, CB - P1);
-        w[16] = descale(tmp12 + tmp1, CB - P1);
-        w[40] = descale(tmp12 - tmp1, CB - P1);
-        w[24] = descale(tmp13 + tmp0, CB - P1);
-        w[32] = descale(tmp13 - tmp0, CB - P1);
+        icl_idct_islow_col(in, ws + c);
     }
     for (int r = 0; r < 8; ++r) {
-        const int *w = ws + 8 * r;
+        icl_idct_islow_row(ws + 8 * r, px);
         uint8_t *o = out + (size_t)r * stride;
-        long z2 = w[2], z3 = w[6];
-        long z1 = (z2 + z3) * F0_541;
-        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-        long tmp0 = ((long)w[0] + w[4]) * (1L << CB), tmp1 = ((long)w[0] - w[4]) * (1L << CB);
-        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = w[7];
-        tmp1 = w[5];
-        tmp2 = w[3];
-        tmp3 = w[1];
-        z1 = tmp0 + tmp3;
-        z2 = tmp1 + tmp2;
-        z3 = tmp0 + tmp2;
-        long z4 = tmp1 + tmp3;
-        const long z5 = (z3 + z4) * F1_175;
-        tmp0 *= F0_298;
-        tmp1 *= F2_053;
-        tmp2 *= F3_072;
-        tmp3 *= F1_501;
-        z1 *= -F0_899;
-        z2 *= -F2_562;
-        z3 *= -F1_961;
-        z4 *= -F0_390;
-        z3 += z5;
-        z4 += z5;
-        tmp0 += z1 + z3;
-        tmp1 += z2 + z4;
-        tmp2 += z2 + z3;
-        tmp3 += z1 + z4;
-        constexpr int S = CB + P1 + 3;
-        // range_limit[(x) & RANGE_MASK] of libjpeg == clamp(x + 128) for every value a legal stream can produce
-        o[0] = clamp8(descale(tmp10 + tmp3, S) + 128);
-        o[7] = clamp8(descale(tmp10 - tmp3, S) + 128);
-        o[1] = clamp8(descale(tmp11 + tmp2, S) + 128);
-        o[6] = clamp8(descale(tmp11 - tmp2, S) + 128);
-        o[2] = clamp8(descale(tmp12 + tmp1, S) + 128);
-        o[5] = clamp8(descale(tmp12 - tmp1, S) + 128);
-        o[3] = clamp8(descale(tmp13 + tmp0, S) + 128);
-        o[4] = clamp8(descale(tmp13 - tmp0, S) + 128);
+        for (int k = 0; k < 8; ++k) o[k] = (uint8_t)px[k];
     }
 }
 
@@ -223,7 +141,7 @@ static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb)
 // Decodes a JPEG file held in memory to interleaved RGB.  rgb is resized to w*h*3.  No C++ exception may cross the C ABI
 // (cgo / ctypes would std::terminate the host process): allocation failures become status codes here.
 // orient receives the EXIF orientation tag (1..8; 1 when absent): cv::imread applies it after decoding (embeddings.go:50
-// passes IMReadColor without IMREAD_IGNORE_ORIENTATION), the caller does the same (resnet.hip apply_exif_orientation).
+// passes IMReadColor without IMREAD_IGNORE_ORIENTATION), the caller does the same (image_io.hip icl_apply_exif_orientation).
 int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient)
 {
     orient = 1;
@@ -328,7 +246,7 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                 ++i;
                 if (tq > 3 || i + (pq ? 128 : 64) > sl) return fail(ICL_ERR_IO, "Bad quantization table");
                 for (int k = 0; k < 64; ++k) {
-                    qt[tq][zigzag[k]] = pq ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
+                    qt[tq][icl_zigzag[k]] = pq ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
                     i += pq ? 2 : 1;
                 }
                 qt_ok[tq] = true;
@@ -450,7 +368,7 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                         }
                         i += r;
                         if (i > 63) return false;
-                        cf[zigzag[i]] = (int16_t)extend(br.get(sz), sz);
+                        cf[icl_zigzag[i]] = (int16_t)extend(br.get(sz), sz);
                         ++i;
                     }
                     return true;
@@ -480,7 +398,7 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                         }
                         i += r;
                         if (i > Se) return false;
-                        cf[zigzag[i]] = (int16_t)(extend(br.get(sz), sz) * (1 << Al));
+                        cf[icl_zigzag[i]] = (int16_t)(extend(br.get(sz), sz) * (1 << Al));
                         ++i;
                     }
                     return true;
@@ -506,19 +424,19 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                         }
                         // skip r ZERO-history coefficients (ZRL: 16), refining the non-zero ones passed on the way
                         for (; i <= Se; ++i) {
-                            int16_t &c = cf[zigzag[i]];
+                            int16_t &c = cf[icl_zigzag[i]];
                             if (c != 0) refine(c);
                             else if (--r < 0) break;
                         }
                         if (sv) {
                             if (i > Se) return false;
-                            cf[zigzag[i]] = (int16_t)sv;
+                            cf[icl_zigzag[i]] = (int16_t)sv;
                         }
                     }
                 }
                 if (eobrun > 0) {
                     for (; i <= Se; ++i) {
-                        int16_t &c = cf[zigzag[i]];
+                        int16_t &c = cf[icl_zigzag[i]];
                         if (c != 0) refine(c);
                     }
                     --eobrun;
@@ -615,83 +533,49 @@ static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb)
             }
         return ICL_OK;
     }
-    // chroma upsampling (jdsample.c): h2v1 / h2v2 "fancy" triangle filters, or none
-    const int hs = comp[0].h, vs = comp[0].v;
-    std::vector<uint8_t> up[2];
-    for (int c = 1; c <= 2; ++c) {
-        const icl_jpeg_component &k = comp[c];
-        const size_t stride = (size_t)k.wblocks * 8;
-        std::vector<uint8_t> &o = up[c - 1];
-        o.assign((size_t)W * H, 0);
-        const int dw = k.dw, dh = k.dh;
-        const uint8_t *pl = plane[c].data();
-        auto in = [&](int r) -> const uint8_t * { return pl + (size_t)std::min(std::max(r, 0), dh - 1) * stride; };
-        if (hs == 1 && vs == 1) {
-            for (int y = 0; y < H; ++y) memcpy(&o[(size_t)y * W], in(y), (size_t)W);
-        } else if (hs == 2 && vs == 1) {
-            std::vector<uint8_t> row((size_t)dw * 2 + 2);
-            for (int y = 0; y < H; ++y) {
-                const uint8_t *p = in(y);
-                if (dw == 1) { row[0] = row[1] = p[0]; }
-                else {
-                    row[0] = p[0];
-                    row[1] = (uint8_t)((p[0] * 3 + p[1] + 2) >> 2);
-                    for (int i = 1; i < dw - 1; ++i) {
-                        row[2 * i] = (uint8_t)((p[i] * 3 + p[i - 1] + 1) >> 2);
-                        row[2 * i + 1] = (uint8_t)((p[i] * 3 + p[i + 1] + 2) >> 2);
-                    }
-                    row[2 * (dw - 1)] = (uint8_t)((p[dw - 1] * 3 + p[dw - 2] + 1) >> 2);
-                    row[2 * (dw - 1) + 1] = p[dw - 1];
+    // chroma upsampling (jdsample.c "fancy" rules, one output row at a time) and colour conversion (jdcolor.c), or pass-through
+    // for Adobe transform 0
+    const int hs = comp[0].h, vs = comp[0].v, dw = comp[1].dw, dh = comp[1].dh;
+    const size_t ystride = (size_t)comp[0].wblocks * 8, cstride = (size_t)comp[1].wblocks * 8;
+    std::vector<uint8_t> up[2] = {std::vector<uint8_t>((size_t)W + 1), std::vector<uint8_t>((size_t)W + 1)}; // 2 * dw <= W + 1
+    std::vector<int> cs((size_t)dw);
+    for (int y = 0; y < H; ++y) {
+        for (int c = 0; c < 2; ++c) {
+            const uint8_t *pl = plane[c + 1].data();
+            uint8_t *o = up[c].data();
+            if (hs == 1) {
+                memcpy(o, pl + (size_t)y * cstride, (size_t)W);
+            } else if (vs == 1) {
+                const uint8_t *p = pl + (size_t)y * cstride;
+                auto col = [&](int k) { return (int)p[k]; };
+                for (int i = 0; i < dw; ++i) {
+                    o[2 * i] = (uint8_t)icl_fancy_h2<1>(col, dw, 2 * i);
+                    o[2 * i + 1] = (uint8_t)icl_fancy_h2<1>(col, dw, 2 * i + 1);
                 }
-                memcpy(&o[(size_t)y * W], row.data(), (size_t)W);
-            }
-        } else { // h2v2
-            std::vector<int> cs0((size_t)dw), cs1((size_t)dw);
-            std::vector<uint8_t> row((size_t)dw * 2 + 2);
-            for (int y = 0; y < H; ++y) {
-                const int r = y >> 1;
-                const uint8_t *p0 = in(r), *p1 = in((y & 1) ? r + 1 : r - 1); // nearer / further input row
-                int *cs = cs0.data();
-                for (int i = 0; i < dw; ++i) cs[i] = p0[i] * 3 + p1[i];
-                if (dw == 1) {
-                    row[0] = (uint8_t)((cs[0] * 4 + 8) >> 4);
-                    row[1] = (uint8_t)((cs[0] * 4 + 7) >> 4);
-                } else {
-                    row[0] = (uint8_t)((cs[0] * 4 + 8) >> 4);
-                    row[1] = (uint8_t)((cs[0] * 3 + cs[1] + 7) >> 4);
-                    for (int i = 1; i < dw - 1; ++i) {
-                        row[2 * i] = (uint8_t)((cs[i] * 3 + cs[i - 1] + 8) >> 4);
-                        row[2 * i + 1] = (uint8_t)((cs[i] * 3 + cs[i + 1] + 7) >> 4);
-                    }
-                    row[2 * (dw - 1)] = (uint8_t)((cs[dw - 1] * 3 + cs[dw - 2] + 8) >> 4);
-                    row[2 * (dw - 1) + 1] = (uint8_t)((cs[dw - 1] * 4 + 7) >> 4);
+            } else {
+                int r0, r1;
+                icl_fancy_rows(y, dh, r0, r1);
+                const uint8_t *p0 = pl + (size_t)r0 * cstride, *p1 = pl + (size_t)r1 * cstride;
+                for (int i = 0; i < dw; ++i) cs[(size_t)i] = icl_fancy_colsum(p0[i], p1[i]);
+                auto col = [&](int k) { return cs[(size_t)k]; };
+                for (int i = 0; i < dw; ++i) {
+                    o[2 * i] = (uint8_t)icl_fancy_h2<2>(col, dw, 2 * i);
+                    o[2 * i + 1] = (uint8_t)icl_fancy_h2<2>(col, dw, 2 * i + 1);
                 }
-                memcpy(&o[(size_t)y * W], row.data(), (size_t)W);
             }
         }
-    }
-    // colour conversion (jdcolor.c): fixed-point YCbCr -> RGB, or pass-through for Adobe transform 0
-    const bool is_rgb = J.is_rgb;
-    int cr_r[256], cb_b[256], cr_g[256], cb_g[256];
-    for (int i = 0; i < 256; ++i) {
-        const int x = i - 128;
-        cr_r[i] = (int)((91881L * x + 32768) >> 16);   // FIX(1.40200)
-        cb_b[i] = (int)((116130L * x + 32768) >> 16);  // FIX(1.77200)
-        cr_g[i] = (int)(-46802L * x);                  // FIX(0.71414)
-        cb_g[i] = (int)(-22554L * x + 32768);          // FIX(0.34414)
-    }
-    const size_t ystride = (size_t)comp[0].wblocks * 8;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            const int Y = plane[0][y * ystride + x], cb = up[0][(size_t)y * W + x], cr = up[1][(size_t)y * W + x];
-            uint8_t *o = &rgb[((size_t)y * W + x) * 3];
-            if (is_rgb) {
+        const uint8_t *Yr = plane[0].data() + (size_t)y * ystride;
+        uint8_t *o = &rgb[(size_t)y * W * 3];
+        for (int x = 0; x < W; ++x, o += 3) {
+            const int Y = Yr[x], cb = up[0][(size_t)x], cr = up[1][(size_t)x];
+            if (J.is_rgb) {
                 o[0] = (uint8_t)Y; o[1] = (uint8_t)cb; o[2] = (uint8_t)cr;
             } else {
-                o[0] = clamp8(Y + cr_r[cr]);
-                o[1] = clamp8(Y + ((cb_g[cb] + cr_g[cr]) >> 16));
-                o[2] = clamp8(Y + cb_b[cb]);
+                int R, G, B;
+                icl_ycc_to_rgb(Y, cb, cr, R, G, B);
+                o[0] = (uint8_t)R; o[1] = (uint8_t)G; o[2] = (uint8_t)B;
             }
         }
+    }
     return ICL_OK;
 }

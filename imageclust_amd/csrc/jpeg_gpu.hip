@@ -11,6 +11,7 @@
 // output pixel: reads the 2x2 source pixels of the resize through the orientation map, upsamples the chroma at those
 // positions only, converts the colour and resizes).  Nothing is built at full-resolution RGB.
 #include "icl_common.h"
+#include "ingest_pixels.h"
 #include "jpeg_stage.h"
 
 #include <algorithm>
@@ -22,7 +23,6 @@
 #include <new>
 #include <thread>
 
-bool icl_is_png(const uint8_t *data, size_t len);                                                         // png_decode.hip
 int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out); // resnet.hip
 
 namespace {
@@ -55,20 +55,11 @@ struct ingest_plane {
     uint16_t qt[64]; // natural order
 };
 
-__constant__ uint8_t c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-const uint8_t h_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-__device__ __forceinline__ int clamp8d(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
 constexpr int IDCT_THREADS = 64;
 constexpr int IDCT_SLOT = 65; // ints per thread in LDS (odd stride: no bank conflicts between the threads' slots)
 
-// IJG jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2), the same integer arithmetic as jpeg_decode.hip idct_islow:
-// one thread per block; the dequantised coefficients are scattered from zig-zag order into the thread's LDS slot.
+// IJG jidctint.c jpeg_idct_islow (ingest_pixels.h, as in host stage B): one thread per block; the dequantised coefficients are
+// scattered from zig-zag order into the thread's LDS slot.
 __global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const ingest_plane *__restrict__ planes, int nplanes, const uint8_t *__restrict__ payload,
                                                                  int64_t payload_bytes, uint8_t *__restrict__ scratch, int64_t scratch_bytes, int64_t total_blocks)
 {
@@ -97,150 +88,46 @@ __global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const ingest_pl
 #pragma unroll
     for (int i = 0; i < 64; ++i) coef[i] = 0;
     for (int i = 0; i < cnt; ++i) {
-        const int z = c_zigzag[i];
+        const int z = icl_zigzag[i];
         coef[z] = (int)cf[i] * (int)P.qt[z];
     }
-    constexpr int CB = 13, P1 = 2;
-    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299, F1_847 = 15137,
-                  F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
-    auto descale = [](long x, int n) { return (int)((x + (1L << (n - 1))) >> n); };
     int ws[64];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int *in = coef + c;
-        int *w = ws + c;
-        long z2 = in[16], z3 = in[48];
-        long z1 = (z2 + z3) * F0_541;
-        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-        z2 = in[0];
-        z3 = in[32];
-        long tmp0 = (z2 + z3) * (1L << CB), tmp1 = (z2 - z3) * (1L << CB);
-        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = in[56];
-        tmp1 = in[40];
-        tmp2 = in[24];
-        tmp3 = in[8];
-        z1 = tmp0 + tmp3;
-        z2 = tmp1 + tmp2;
-        z3 = tmp0 + tmp2;
-        long z4 = tmp1 + tmp3;
-        const long z5 = (z3 + z4) * F1_175;
-        tmp0 *= F0_298;
-        tmp1 *= F2_053;
-        tmp2 *= F3_072;
-        tmp3 *= F1_501;
-        z1 *= -F0_899;
-        z2 *= -F2_562;
-        z3 *= -F1_961;
-        z4 *= -F0_390;
-        z3 += z5;
-        z4 += z5;
-        tmp0 += z1 + z3;
-        tmp1 += z2 + z4;
-        tmp2 += z2 + z3;
-        tmp3 += z1 + z4;
-        // (the host's all-AC-zero shortcut writes dc << PASS1_BITS: exactly what these formulas give for zero AC terms)
-        w[0] = descale(tmp10 + tmp3, CB - P1);
-        w[56] = descale(tmp10 - tmp3, CB - P1);
-        w[8] = descale(tmp11 + tmp2, CB - P1);
-        w[48] = descale(tmp11 - tmp2, CB - P1);
-        w[16] = descale(tmp12 + tmp1, CB - P1);
-        w[40] = descale(tmp12 - tmp1, CB - P1);
-        w[24] = descale(tmp13 + tmp0, CB - P1);
-        w[32] = descale(tmp13 - tmp0, CB - P1);
-    }
+    for (int c = 0; c < 8; ++c) icl_idct_islow_col(coef + c, ws + c); // branch-free (the host's all-AC-zero shortcut gives the same values)
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-        const int *w = ws + 8 * r;
-        long z2 = w[2], z3 = w[6];
-        long z1 = (z2 + z3) * F0_541;
-        long tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-        long tmp0 = ((long)w[0] + w[4]) * (1L << CB), tmp1 = ((long)w[0] - w[4]) * (1L << CB);
-        const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = w[7];
-        tmp1 = w[5];
-        tmp2 = w[3];
-        tmp3 = w[1];
-        z1 = tmp0 + tmp3;
-        z2 = tmp1 + tmp2;
-        z3 = tmp0 + tmp2;
-        long z4 = tmp1 + tmp3;
-        const long z5 = (z3 + z4) * F1_175;
-        tmp0 *= F0_298;
-        tmp1 *= F2_053;
-        tmp2 *= F3_072;
-        tmp3 *= F1_501;
-        z1 *= -F0_899;
-        z2 *= -F2_562;
-        z3 *= -F1_961;
-        z4 *= -F0_390;
-        z3 += z5;
-        z4 += z5;
-        tmp0 += z1 + z3;
-        tmp1 += z2 + z4;
-        tmp2 += z2 + z3;
-        tmp3 += z1 + z4;
-        constexpr int S = CB + P1 + 3;
-        const uint32_t p0 = clamp8d(descale(tmp10 + tmp3, S) + 128), p7 = clamp8d(descale(tmp10 - tmp3, S) + 128);
-        const uint32_t p1 = clamp8d(descale(tmp11 + tmp2, S) + 128), p6 = clamp8d(descale(tmp11 - tmp2, S) + 128);
-        const uint32_t p2 = clamp8d(descale(tmp12 + tmp1, S) + 128), p5 = clamp8d(descale(tmp12 - tmp1, S) + 128);
-        const uint32_t p3 = clamp8d(descale(tmp13 + tmp0, S) + 128), p4 = clamp8d(descale(tmp13 - tmp0, S) + 128);
+        int px[8];
+        icl_idct_islow_row(ws + 8 * r, px);
         uint2 v;
-        v.x = p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
-        v.y = p4 | (p5 << 8) | (p6 << 16) | (p7 << 24);
+        v.x = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+        v.y = (uint32_t)px[4] | ((uint32_t)px[5] << 8) | ((uint32_t)px[6] << 16) | ((uint32_t)px[7] << 24);
         *(uint2 *)(scratch + o + r * stride) = v; // plane offsets and strides are multiples of 8
     }
 }
 
-// one chroma sample of the upsampled (full-resolution) plane at (X, y): jpeg_decode.hip's h1v1 / h2v1 / h2v2 "fancy" rules
+// the chroma sample at (X, y) of the full-resolution image from D's chroma plane pl (fancy upsampling: ingest_pixels.h)
 __device__ __forceinline__ int chroma_at(const ingest_image &D, const uint8_t *pl, int X, int y)
 {
-    const int dw = D.cw, dh = D.chh;
-    auto row = [&](int r) -> const uint8_t * { return pl + (int64_t)min(max(r, 0), dh - 1) * D.cstride; };
-    if (D.hs == 1) return row(y)[min(X, dw - 1)];
-    const int i = min(X >> 1, dw - 1);
-    if (D.vs == 1) {
-        const uint8_t *p = row(y);
-        if (X & 1) return i >= dw - 1 ? p[dw - 1] : (p[i] * 3 + p[i + 1] + 2) >> 2;
-        return i == 0 ? p[0] : (p[i] * 3 + p[i - 1] + 1) >> 2;
-    }
-    const int r = y >> 1;
-    const uint8_t *p0 = row(r), *p1 = row((y & 1) ? r + 1 : r - 1); // nearer / further input row
-    auto cs = [&](int k) { return p0[k] * 3 + p1[k]; };
-    if (X & 1) return i >= dw - 1 ? (cs(dw - 1) * 4 + 7) >> 4 : (cs(i) * 3 + cs(i + 1) + 7) >> 4;
-    return i == 0 ? (cs(0) * 4 + 8) >> 4 : (cs(i) * 3 + cs(i - 1) + 8) >> 4;
+    return icl_fancy_upsample(pl, D.cstride, D.cw, D.chh, D.hs, D.vs, X, y);
 }
 
-// RGB of pixel (x, y) of the ORIENTED image (apply_exif_orientation's destination -> source map, resnet.hip)
+// RGB of pixel (x, y) of the ORIENTED image: the orientation map, fancy upsampling of the chroma at that pixel only, colour conversion
 __device__ __forceinline__ void rgb_at(const ingest_image &D, const uint8_t *scratch, int x, int y, int &R, int &G, int &B)
 {
     const int sw = D.W, sh = D.H;
     int sx, sy;
-    switch (D.orient) {
-    case 2: sx = sw - 1 - x; sy = y; break;
-    case 3: sx = sw - 1 - x; sy = sh - 1 - y; break;
-    case 4: sx = x; sy = sh - 1 - y; break;
-    case 5: sx = y; sy = x; break;
-    case 6: sx = y; sy = sh - 1 - x; break;
-    case 7: sx = sw - 1 - y; sy = sh - 1 - x; break;
-    case 8: sx = sw - 1 - y; sy = x; break;
-    default: sx = x; sy = y; break;
-    }
+    icl_exif_source(D.orient, sw, sh, x, y, sx, sy);
     sx = min(max(sx, 0), sw - 1);
     sy = min(max(sy, 0), sh - 1);
     const int Y = scratch[D.yplane + (int64_t)sy * D.ystride + sx];
     if (D.ncomp == 1) { R = G = B = Y; return; }
     const int cb = chroma_at(D, scratch + D.cplane[0], sx, sy), cr = chroma_at(D, scratch + D.cplane[1], sx, sy);
     if (D.is_rgb) { R = Y; G = cb; B = cr; return; }
-    // jdcolor.c fixed-point tables, evaluated in place (integer arithmetic: identical to the host's table entries)
-    const int xr = cr - 128, xb = cb - 128;
-    R = clamp8d(Y + ((91881 * xr + 32768) >> 16));
-    G = clamp8d(Y + ((-22554 * xb + 32768 + -46802 * xr) >> 16));
-    B = clamp8d(Y + ((116130 * xb + 32768) >> 16));
+    icl_ycc_to_rgb(Y, cb, cr, R, G, B);
 }
 
 // one thread per output pixel of one image: cv::resize INTER_LINEAR (OpenCV's two-pass fixed-point rounding) or, for an exact
-// 2x2 decimation, INTER_AREA -- resnet.hip resize_bilinear_u8, with its offset / weight tables computed on the host
+// 2x2 decimation, INTER_AREA (ingest_pixels.h), with the offset / weight tables computed on the host (icl_resize_coeffs)
 __global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_image *__restrict__ imgs, const uint8_t *__restrict__ payload, int64_t payload_bytes,
                                                                  const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst)
 {
@@ -265,9 +152,9 @@ __global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_im
         rgb_at(D, scratch, 2 * dx + 1, 2 * dy, r[1], g[1], b[1]);
         rgb_at(D, scratch, 2 * dx, 2 * dy + 1, r[2], g[2], b[2]);
         rgb_at(D, scratch, 2 * dx + 1, 2 * dy + 1, r[3], g[3], b[3]);
-        o[0] = (uint8_t)((r[0] + r[1] + r[2] + r[3] + 2) >> 2);
-        o[1] = (uint8_t)((g[0] + g[1] + g[2] + g[3] + 2) >> 2);
-        o[2] = (uint8_t)((b[0] + b[1] + b[2] + b[3] + 2) >> 2);
+        o[0] = icl_area_mean(r[0], r[1], r[2], r[3]);
+        o[1] = icl_area_mean(g[0], g[1], g[2], g[3]);
+        o[2] = icl_area_mean(b[0], b[1], b[2], b[3]);
         return;
     }
     const int sx = min(max(D.xofs[dx], 0), D.ow - 1), sx1 = min(sx + 1, D.ow - 1);
@@ -277,13 +164,9 @@ __global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_im
     rgb_at(D, scratch, sx, sy1, r[2], g[2], b[2]);
     rgb_at(D, scratch, sx1, sy1, r[3], g[3], b[3]);
     const int a0 = D.xa[dx * 2], a1 = D.xa[dx * 2 + 1], b0 = D.ya[dy * 2], b1 = D.ya[dy * 2 + 1];
-    auto mix = [&](int t0, int t1, int t2, int t3) {
-        const int row0 = t0 * a0 + t1 * a1, row1 = t2 * a0 + t3 * a1;
-        return (uint8_t)((((b0 * (row0 >> 4)) >> 16) + ((b1 * (row1 >> 4)) >> 16) + 2) >> 2);
-    };
-    o[0] = mix(r[0], r[1], r[2], r[3]);
-    o[1] = mix(g[0], g[1], g[2], g[3]);
-    o[2] = mix(b[0], b[1], b[2], b[3]);
+    o[0] = icl_resize_linear(r[0], r[1], r[2], r[3], a0, a1, b0, b1);
+    o[1] = icl_resize_linear(g[0], g[1], g[2], g[3], a0, a1, b0, b1);
+    o[2] = icl_resize_linear(b[0], b[1], b[2], b[3], a0, a1, b0, b1);
 }
 
 __global__ void fill_nan_rows_kernel(float *out, const int32_t *rows, int nrows, int head)
@@ -335,7 +218,7 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
         for (int64_t b = 0; b < nb; ++b) {
             const int16_t *cf = k.coefs.data() + b * 64;
             int e = 63;
-            while (e >= 0 && cf[h_zigzag[e]] == 0) --e;
+            while (e >= 0 && cf[icl_zigzag[e]] == 0) --e;
             nc += (uint64_t)(e + 1);
         }
         if (nc > 0xffffffffull) return false;
@@ -363,9 +246,9 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
         for (int64_t b = 0; b < nb; ++b) {
             const int16_t *cf = k.coefs.data() + b * 64;
             int e = 63;
-            while (e >= 0 && cf[h_zigzag[e]] == 0) --e;
+            while (e >= 0 && cf[icl_zigzag[e]] == 0) --e;
             offs[(size_t)b] = at;
-            for (int i = 0; i <= e; ++i) out[at + i] = cf[h_zigzag[i]];
+            for (int i = 0; i <= e; ++i) out[at + i] = cf[icl_zigzag[i]];
             at += (uint32_t)(e + 1);
         }
         offs[(size_t)nb] = at;
@@ -383,15 +266,8 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
     return true;
 }
 
-static void host_finish(const char *path, std::vector<uint8_t> &rgb, int w, int h, file_result &r)
-{
-    r.packed.resize((size_t)ICL_IMG_BYTES);
-    icl_resize_u8_host(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
-    r.kind = KIND_HOST;
-}
-
 // One file, on a worker thread: stage A for a JPEG the GPU takes, the whole host path for everything else.  Status codes and
-// messages are those of icl_load_image_224 (read_image, resnet.hip).
+// messages are those of icl_load_image_224 (image_io.hip).
 static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32_t> &offs, file_result &r)
 {
     auto fail_from_tls = [&](int rc) {
@@ -400,23 +276,10 @@ static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32
         r.err = icl_last_error(nullptr);
     };
     try {
-        std::vector<uint8_t> file;
-        bool jpeg = false;
-        if (FILE *f = fopen(path, "rb")) {
-            unsigned char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const size_t got = fread(magic, 1, 8, f);
-            jpeg = !(got == 8 && icl_is_png(magic, 8)) && got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8;
-            if (jpeg) {
-                fseek(f, 0, SEEK_END);
-                const long sz = ftell(f);
-                fseek(f, 0, SEEK_SET);
-                file.resize((size_t)std::max<long>(sz, 0));
-                const bool ok = sz > 0 && fread(file.data(), 1, file.size(), f) == file.size();
-                if (!ok) jpeg = false; // let the host path report it
-            }
-            fclose(f);
-        }
-        if (jpeg) {
+        std::vector<uint8_t> file, rgb;
+        int w = 0, h = 0;
+        const int fmt = icl_image_file_read(path, file);
+        if (fmt == ICL_IMAGE_JPEG) {
             const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), path, J);
             if (rc) return fail_from_tls(rc);
             if (pack_jpeg(J, r, offs)) {
@@ -424,18 +287,18 @@ static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32
                 return;
             }
             // too large for one slab: stage B on the host (the file has already been through stage A)
-            std::vector<uint8_t> rgb;
-            int w = J.W, h = J.H;
+            w = J.W;
+            h = J.H;
             const int rc2 = icl_jpeg_stage_b(nullptr, J, path, rgb);
             if (rc2) return fail_from_tls(rc2);
             icl_apply_exif_orientation(rgb, w, h, J.orient);
-            return host_finish(path, rgb, w, h, r);
+        } else { // PNG, PPM, or a file that cannot be read: the host path decodes it or reports why not
+            const int rc = icl_image_decode(nullptr, path, fmt, file, rgb, w, h);
+            if (rc) return fail_from_tls(rc);
         }
-        std::vector<uint8_t> rgb;
-        int w = 0, h = 0;
-        const int rc = icl_read_image_host(nullptr, path, rgb, w, h);
-        if (rc) return fail_from_tls(rc);
-        host_finish(path, rgb, w, h, r);
+        r.packed.resize((size_t)ICL_IMG_BYTES);
+        icl_resize_bilinear_u8(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
+        r.kind = KIND_HOST;
     } catch (const std::bad_alloc &) {
         r.kind = KIND_FAILED;
         r.rc = ICL_ERR_NOMEM;
@@ -616,10 +479,10 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
                 D.hs = r->hs;
                 D.vs = r->vs;
                 D.is_rgb = r->is_rgb;
-                const bool swap = r->orient >= 5 && r->orient <= 8;
+                const bool swap = icl_exif_swaps_axes(r->orient);
                 D.ow = swap ? r->H : r->W;
                 D.oh = swap ? r->W : r->H;
-                D.area = D.ow == 2 * OUTW && D.oh == 2 * OUTH;
+                D.area = icl_resize_is_area(D.ow, D.oh, OUTW, OUTH);
                 icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
                 icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
                 memcpy(pay + used, r->packed.data(), r->packed.size());

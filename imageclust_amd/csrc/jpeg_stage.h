@@ -1,7 +1,8 @@
-// jpeg_stage.h -- the two stages of the host JPEG decoder (jpeg_decode.hip) and the GPU rebuild of stage B (jpeg_gpu.hip).
+// jpeg_stage.h -- the two stages of the host JPEG decoder (jpeg_decode.hip), the GPU rebuild of stage B (jpeg_gpu.hip) and the
+// host ingest path around them (image_io.hip).
 //
 // Stage A parses the file and runs the entropy decoder: what it leaves is everything the pixel rebuild needs.  Stage B is
-// the integer pixel work: dequantisation, the islow IDCT, fancy chroma upsampling and the YCbCr->RGB conversion.
+// the integer pixel work: dequantisation, the islow IDCT, fancy chroma upsampling and the YCbCr->RGB conversion (ingest_pixels.h).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -38,8 +39,20 @@ int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *
 // Stage B on the host: interleaved RGB, W*H*3 (before the EXIF orientation).
 int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, std::vector<uint8_t> &rgb);
 
-// resnet.hip: the host ingest path the batched file pipeline falls back to, and the resize tables it shares with the GPU
-int icl_read_image_host(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h);
+// Stage A then stage B (the host decoder in one call).  orient receives the EXIF orientation (1..8; 1 when absent).
+int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient);
+
+// image_io.hip: the host ingest path.  The batched file path (jpeg_gpu.hip) reads and sniffs files, and decodes what the GPU does not
+// take, through it; the icl_embed_file batcher (resnet.hip) reads and resizes through it.
+enum { ICL_IMAGE_UNREADABLE = -1, ICL_IMAGE_PPM = 0, ICL_IMAGE_PNG = 1, ICL_IMAGE_JPEG = 2 };
+// Opens path and tells its format by the first bytes (PNG signature, JPEG SOI; anything else goes to the PPM reader).  A PNG or
+// JPEG is read whole into `file`.  ICL_IMAGE_UNREADABLE: the file cannot be opened, or a PNG / JPEG cannot be read whole.
+int icl_image_file_read(const char *path, std::vector<uint8_t> &file);
+// IMRead(IMReadColor) of what icl_image_file_read returned: interleaved RGB, w*h*3, the EXIF orientation applied.  Every status
+// code and message of the host path comes from here.
+int icl_image_decode(icl_ctx *ctx, const char *path, int fmt, const std::vector<uint8_t> &file, std::vector<uint8_t> &rgb, int &w, int &h);
+// read + decode + cv::resize to the 224x224x3 u8 image (icl_load_image_224)
+int icl_read_image_224(icl_ctx *ctx, const char *path, uint8_t *out);
 void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient);
-void icl_resize_u8_host(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
+void icl_resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
 void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al); // cv::resize INTER_LINEAR source offsets + 11-bit weights

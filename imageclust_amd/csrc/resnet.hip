@@ -1,8 +1,9 @@
 // resnet.hip -- hand-written ResNet50-v1 forward for gfx950: the embedding half of the hot path.
 //
-// Replaces LoadPretrainedModelONNX / PreprocessImage / GetImageEmbedding
-//   (/root/reference/internal/embeddings/embeddings.go:28-43, :46-116, :119-163), i.e. the OpenCV-DNN forward
+// Replaces LoadPretrainedModelONNX / GetImageEmbedding
+//   (/root/reference/internal/embeddings/embeddings.go:28-43, :119-163), i.e. the OpenCV-DNN forward
 // of resnet50-v1-7.onnx that the reference reaches through gocv (batch 1, CPU, serialised by NetMutex :133).
+// PreprocessImage (:46-116) is image_io.hip.
 //
 // Layout: activations NHWC (channels contiguous) in bf16 (throughput) or f32 (parity); weights re-packed once
 // at load to [Cout][KH][KW][Cin] so every implicit-GEMM K-chunk is a contiguous run of input channels of ONE
@@ -14,6 +15,7 @@
 // the MFMA step and the epilogue but gathers its A tile straight from the u8 image (K = 147 padded to 192), which also
 // performs the reference's RGB/255 scaling (embeddings.go:96).
 #include "icl_common.h"
+#include "jpeg_stage.h"
 #include "mfma_tile.h"
 
 #include <algorithm>
@@ -1795,232 +1797,6 @@ extern "C" int icl_embed_u8(icl_ctx *ctx, const uint8_t *img, int64_t n, int hea
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// host-side image ingest (embeddings.go:46-116): binary PPM decode + OpenCV-compatible 8-bit bilinear resize
-// ------------------------------------------------------------------------------------------------------------
-extern "C" int icl_preprocess_u8(const uint8_t *hwc, float *nchw)
-{
-    if (!hwc || !nchw) return ICL_ERR_ARG;
-    const float sc = (float)(1.0 / 255.0);
-    for (int y = 0; y < ICL_IMG_H; ++y)
-        for (int x = 0; x < ICL_IMG_W; ++x)
-            for (int c = 0; c < 3; ++c) nchw[((size_t)c * ICL_IMG_H + y) * ICL_IMG_W + x] = (float)hwc[((size_t)y * ICL_IMG_W + x) * 3 + c] * sc;
-    return ICL_OK;
-}
-
-// source offsets and 11-bit weights of one axis of cv::resize(INTER_LINEAR) (float / double arithmetic: jpeg_gpu.hip uploads these
-// host-computed tables rather than recomputing them on the device)
-static void resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al)
-{
-    const double scale = (double)sn / dn;
-    for (int d = 0; d < dn; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f -= s;
-        if (s < 0) { f = 0; s = 0; }
-        if (s >= sn - 1) { f = 0; s = sn - 1; }
-        ofs[d] = s;
-        al[(size_t)d * 2] = (short)std::lrint((1.f - f) * 2048.f);
-        al[(size_t)d * 2 + 1] = (short)std::lrint(f * 2048.f);
-    }
-}
-
-// cv::resize(INTER_LINEAR) for 8-bit images: half-pixel centres, 11-bit fixed-point coefficients, the two-pass
-// rounding of OpenCV's HResizeLinear/VResizeLinear<uchar> (embeddings.go:69 resizes every image to 224x224).
-static void resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh)
-{
-    const int cn = 3;
-    if (sw == 2 * dw && sh == 2 * dh) {
-        // cv::resize switches INTER_LINEAR to INTER_AREA for an exact 2x2 decimation ("if (interpolation == INTER_LINEAR &&
-        // is_area_fast && iscale_x == 2 && iscale_y == 2) interpolation = INTER_AREA"); ResizeAreaFast on 8-bit data is the
-        // rounded mean of the 2x2 block: (a + b + c + d + 2) >> 2
-        for (int y = 0; y < dh; ++y) {
-            const uint8_t *r0 = src + (size_t)(2 * y) * sw * cn, *r1 = r0 + (size_t)sw * cn;
-            for (int x = 0; x < dw; ++x)
-                for (int c = 0; c < cn; ++c)
-                    dst[((size_t)y * dw + x) * cn + c] =
-                        (uint8_t)((r0[(2 * x) * cn + c] + r0[(2 * x + 1) * cn + c] + r1[(2 * x) * cn + c] + r1[(2 * x + 1) * cn + c] + 2) >> 2);
-        }
-        return;
-    }
-    std::vector<int> xofs((size_t)dw), yofs((size_t)dh);
-    std::vector<short> xa((size_t)dw * 2), ya((size_t)dh * 2);
-    resize_coeffs(dw, sw, xofs.data(), xa.data());
-    resize_coeffs(dh, sh, yofs.data(), ya.data());
-    std::vector<int> row0((size_t)dw * cn), row1((size_t)dw * cn);
-    auto hrow = [&](int sy, std::vector<int> &out) {
-        const uint8_t *S = src + (size_t)sy * sw * cn;
-        for (int dx = 0; dx < dw; ++dx) {
-            const int sx = xofs[(size_t)dx], sx1 = std::min(sx + 1, sw - 1);
-            for (int c = 0; c < cn; ++c) out[(size_t)dx * cn + c] = S[sx * cn + c] * xa[(size_t)dx * 2] + S[sx1 * cn + c] * xa[(size_t)dx * 2 + 1];
-        }
-    };
-    for (int dy = 0; dy < dh; ++dy) {
-        const int sy = yofs[(size_t)dy], sy1 = std::min(sy + 1, sh - 1);
-        hrow(sy, row0);
-        hrow(sy1, row1);
-        const int b0 = ya[(size_t)dy * 2], b1 = ya[(size_t)dy * 2 + 1];
-        for (int i = 0; i < dw * cn; ++i)
-            dst[(size_t)dy * dw * cn + i] = (uint8_t)((((b0 * (row0[(size_t)i] >> 4)) >> 16) + ((b1 * (row1[(size_t)i] >> 4)) >> 16) + 2) >> 2);
-    }
-}
-
-static int read_ppm(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
-    auto token = [&](int &v) -> bool {
-        int c;
-        do {
-            c = fgetc(f);
-            if (c == '#')
-                while (c != '\n' && c != EOF) c = fgetc(f);
-        } while (c == ' ' || c == '\n' || c == '\r' || c == '\t');
-        if (c < '0' || c > '9') return false;
-        v = 0;
-        while (c >= '0' && c <= '9') {
-            v = v * 10 + (c - '0');
-            c = fgetc(f);
-        }
-        return true;
-    };
-    int maxv = 0;
-    bool ok = fgetc(f) == 'P' && fgetc(f) == '6' && token(w) && token(h) && token(maxv) && maxv == 255 && w > 0 && h > 0 && w <= 16384 && h <= 16384;
-    if (ok) {
-        rgb.resize((size_t)w * h * 3);
-        ok = fread(rgb.data(), 1, rgb.size(), f) == rgb.size();
-    }
-    fclose(f);
-    if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Only JPEG (Huffman; baseline or progressive), PNG and binary PPM (P6, maxval 255) are decoded by this build", path);
-    return ICL_OK;
-}
-
-int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient); // jpeg_decode.hip
-bool icl_is_png(const uint8_t *data, size_t len);                                                                                                  // png_decode.hip
-int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H);
-
-// cv::imread rotates / mirrors the decoded pixels by the file's EXIF orientation (OpenCV ExifTransform): 2 mirror
-// horizontally, 3 rotate 180, 4 mirror vertically, 5 transpose, 6 rotate 90 clockwise, 7 transverse, 8 rotate 90 counter-clockwise.
-static void apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient)
-{
-    if (orient <= 1 || orient > 8) return;
-    const int sw = w, sh = h;
-    const bool swap = orient >= 5;
-    const int dw = swap ? sh : sw, dh = swap ? sw : sh;
-    std::vector<uint8_t> out((size_t)dw * dh * 3);
-    for (int y = 0; y < dh; ++y)
-        for (int x = 0; x < dw; ++x) {
-            int sx, sy; // source pixel of destination (x, y)
-            switch (orient) {
-            case 2: sx = sw - 1 - x; sy = y; break;
-            case 3: sx = sw - 1 - x; sy = sh - 1 - y; break;
-            case 4: sx = x; sy = sh - 1 - y; break;
-            case 5: sx = y; sy = x; break;
-            case 6: sx = y; sy = sh - 1 - x; break;
-            case 7: sx = sw - 1 - y; sy = sh - 1 - x; break;
-            default: sx = sw - 1 - y; sy = x; break; // 8
-            }
-            memcpy(&out[((size_t)y * dw + x) * 3], &rgb[((size_t)sy * sw + sx) * 3], 3);
-        }
-    rgb.swap(out);
-    w = dw;
-    h = dh;
-}
-
-// IMRead(IMReadColor) of embeddings.go:50 for the formats this build decodes: JPEG, PNG, binary PPM.
-static int read_image(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
-    unsigned char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const size_t got = fread(magic, 1, 8, f);
-    if (got == 8 && icl_is_png(magic, 8)) {
-        fseek(f, 0, SEEK_END);
-        const long sz = ftell(f);
-        fseek(f, 0, SEEK_SET);
-        std::vector<uint8_t> file((size_t)std::max<long>(sz, 0));
-        const bool ok = sz > 0 && fread(file.data(), 1, file.size(), f) == file.size();
-        fclose(f);
-        if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path);
-        return icl_png_decode(ctx, file.data(), file.size(), path, rgb, w, h);
-    }
-    if (got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8) {
-        fseek(f, 0, SEEK_END);
-        const long sz = ftell(f);
-        fseek(f, 0, SEEK_SET);
-        std::vector<uint8_t> file((size_t)std::max<long>(sz, 0));
-        const bool ok = sz > 0 && fread(file.data(), 1, file.size(), f) == file.size();
-        fclose(f);
-        if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path);
-        int orient = 1;
-        ICL_TRY(icl_jpeg_decode(ctx, file.data(), file.size(), path, rgb, w, h, orient));
-        apply_exif_orientation(rgb, w, h, orient);
-        return ICL_OK;
-    }
-    fclose(f);
-    return read_ppm(ctx, path, rgb, w, h);
-}
-
-// the batched file pipeline (jpeg_gpu.hip) shares the host path
-int icl_read_image_host(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h) { return read_image(ctx, path, rgb, w, h); }
-void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient) { apply_exif_orientation(rgb, w, h, orient); }
-void icl_resize_u8_host(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh) { resize_bilinear_u8(src, sw, sh, dst, dw, dh); }
-void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al) { resize_coeffs(dn, sn, ofs, al); }
-
-// No C++ exception may cross the C ABI (cgo / ctypes would terminate the host process): the ingest entry points allocate
-// buffers whose sizes come from files (no_throw: icl_common.h).
-extern "C" int icl_decode_image_file(const char *path, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h)
-{
-    if (!path || !w || !h) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: bad argument");
-    return no_throw(nullptr, "icl_decode_image_file", [&]() -> int {
-        std::vector<uint8_t> px;
-        int iw = 0, ih = 0;
-        ICL_TRY(read_image(nullptr, path, px, iw, ih));
-        *w = iw;
-        *h = ih;
-        if (rgb) {
-            if (cap_bytes < (int64_t)px.size()) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: buffer too small");
-            memcpy(rgb, px.data(), px.size());
-        }
-        return ICL_OK;
-    });
-}
-
-extern "C" int icl_load_image_224(const char *path, uint8_t *out)
-{
-    if (!path || !out) return icl_fail(nullptr, ICL_ERR_ARG, "icl_load_image_224: bad argument");
-    return no_throw(nullptr, "icl_load_image_224", [&]() -> int {
-        std::vector<uint8_t> px;
-        int w = 0, h = 0;
-        ICL_TRY(read_image(nullptr, path, px, w, h));
-        resize_bilinear_u8(px.data(), w, h, out, ICL_IMG_W, ICL_IMG_H);
-        return ICL_OK;
-    });
-}
-
-// cv::resize on an arbitrary u8 RGB image (the resize step of PreprocessImage alone; tests pin it to hand-derived vectors)
-extern "C" int icl_resize_u8(const uint8_t *src, int32_t sw, int32_t sh, uint8_t *dst, int32_t dw, int32_t dh)
-{
-    if (!src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1) return icl_fail(nullptr, ICL_ERR_ARG, "icl_resize_u8: bad argument");
-    return no_throw(nullptr, "icl_resize_u8", [&]() -> int {
-        resize_bilinear_u8(src, sw, sh, dst, dw, dh);
-        return ICL_OK;
-    });
-}
-
-// PreprocessImage(imagePath) (embeddings.go:46-116): file -> the 1x3x224x224 fp32 NCHW blob.
-extern "C" int icl_preprocess_file(const char *path, float *nchw)
-{
-    if (!path || !nchw) return icl_fail(nullptr, ICL_ERR_ARG, "icl_preprocess_file: bad argument");
-    return no_throw(nullptr, "icl_preprocess_file", [&]() -> int {
-        std::vector<uint8_t> px, img((size_t)ICL_IMG_BYTES);
-        int w = 0, h = 0;
-        ICL_TRY(read_image(nullptr, path, px, w, h));
-        resize_bilinear_u8(px.data(), w, h, img.data(), ICL_IMG_W, ICL_IMG_H);
-        return icl_preprocess_u8(img.data(), nchw);
-    });
-}
-
 // ---- GetImageEmbedding(path) from N goroutines (workflow.go:156-175) -------------------------------------------------
 // The reference serialises its batch-1 forward passes behind NetMutex (embeddings.go:133).  Here concurrent callers are
 // COALESCED: every caller decodes and resizes its own file in parallel, then joins a per-context queue; the first one
@@ -2106,10 +1882,8 @@ extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *o
             }
         };
         inflight_guard ig(b);
-        std::vector<uint8_t> rgb, img((size_t)ICL_IMG_BYTES);
-        int w = 0, h = 0;
-        ICL_TRY(read_image(ctx, path, rgb, w, h)); // decode + resize run on the caller's thread, in parallel with other callers
-        resize_bilinear_u8(rgb.data(), w, h, img.data(), ICL_IMG_W, ICL_IMG_H);
+        std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
+        ICL_TRY(icl_read_image_224(ctx, path, img.data())); // decode + resize run on the caller's thread, in parallel with other callers
         icl_file_req me;
         me.img = img.data();
         me.out = out;
