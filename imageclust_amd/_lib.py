@@ -23,6 +23,7 @@ CONV_P8_OFF, CONV_P8_AUTO, CONV_P8_ALL = 0, 1, 2
 CONV_SPLIT = 16
 ROWS_SINGLE, ROWS_EXACT_BATCH, ROWS_LW_BOUND, ROWS_LW_FAST = 0, 1, 2, 3
 FILE_FAIL_NEXT_LEADER = 0x100
+ENTROPY_HOST, ENTROPY_GPU = 0, 1  # icl_set_ingest_options: where the Huffman decoder of a qualifying baseline JPEG runs
 K_CONV, K_DIST_EXACT, K_DIST_MFMA, K_ROWMIN, K_UPDATE, K_EMBED_OTHER, K_CONV64 = range(7)
 K_NAMES = ["conv_igemm_kernel<*,128>", "ward_dist_exact_kernel", "dist_mfma_kernel", "row_argmin_*_kernel",
            "ward_update_exact_kernel", "embed_other", "conv_igemm_kernel<*,64>"]
@@ -63,6 +64,10 @@ SYMBOLS = [
     ("icl_embed_files", _int, [_vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
     ("icl_embed_files_dev", _int, [_vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
     ("icl_last_ingest_stats", _int, [_vp, _pi64, _pi64, _pi64, _pd]),
+    ("icl_set_ingest_options", _int, [_vp, _int]),
+    ("icl_last_entropy_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
+    ("icl_jpeg_coefs_files", _int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
+    ("icl_jpeg_coefs_file_host", _int, [C.c_char_p, _int, _vp, _i64, _pi64, _vp]),
     ("icl_set_batch", _int, [_vp, _int]),
     ("icl_set_conv_options", _int, [_vp, _int]),
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
@@ -394,6 +399,27 @@ class Context:
         g, h, u, s = _i64(), _i64(), _i64(), C.c_double()
         check(self.h, self.L.icl_last_ingest_stats(self.h, C.byref(g), C.byref(h), C.byref(u), C.byref(s)))
         return {"gpu_jpegs": g.value, "host_files": h.value, "upload_bytes": u.value, "host_decode_s": s.value}
+
+    def set_ingest_options(self, entropy=ENTROPY_HOST):
+        """icl_set_ingest_options: ENTROPY_GPU decodes qualifying baseline JPEGs' Huffman streams on the GPU (same rows, statuses, messages)."""
+        check(self.h, self.L.icl_set_ingest_options(self.h, entropy))
+
+    def last_entropy_stats(self):
+        a, b, c, d = _i64(), _i64(), _i64(), _i64()
+        check(self.h, self.L.icl_last_entropy_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"gpu_entropy_jpegs": a.value, "host_entropy_jpegs": b.value, "redone_on_host": c.value, "stream_bytes": d.value}
+
+    def jpeg_coefs_files(self, paths, entropy=ENTROPY_HOST):
+        """icl_jpeg_coefs_files (test hook) -> ([int16 coefficients of file i, components 0, 1, 2 in natural order], state int32[n]):
+        state 1 = decoded (and, on the GPU, accepted), 0 = rejected by the GPU check, -1 = does not qualify for the GPU decoder."""
+        enc = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        off = np.zeros(len(enc) + 1, np.int64)
+        state = np.zeros(len(enc), np.int32)
+        check(self.h, self.L.icl_jpeg_coefs_files(self.h, arr, len(enc), entropy, None, 0, off.ctypes.data, state.ctypes.data))
+        buf = np.zeros(max(1, int(off[-1])), np.int16)
+        check(self.h, self.L.icl_jpeg_coefs_files(self.h, arr, len(enc), entropy, buf.ctypes.data, buf.size, off.ctypes.data, state.ctypes.data))
+        return [buf[off[i]:off[i + 1]] for i in range(len(enc))], state
 
     def last_error(self):
         msg = self.L.icl_last_error(self.h)
@@ -754,6 +780,21 @@ def resize_u8(img, dw, dh):
     if rc:
         raise ICLError(rc, "icl_resize_u8")
     return out
+
+
+def jpeg_coefs_file_host(path, sub_bits=0):
+    """icl_jpeg_coefs_file_host (no GPU): the quantised coefficients of a JPEG by host stage A (sub_bits == 0) or by stage A0 and the GPU
+    entropy decoder's schedule run as a host loop over subsequences of sub_bits bits -> (int16 array, info dict); info["state"]: 1 =
+    decoded / accepted, 0 = rejected, -1 = does not qualify."""
+    L = load()
+    need = _i64()
+    info = np.zeros(8, np.int32)
+    rc = L.icl_jpeg_coefs_file_host(os.fsencode(path), sub_bits, None, 0, C.byref(need), info.ctypes.data)
+    check(None, rc)
+    out = np.zeros(max(1, need.value), np.int16)
+    check(None, L.icl_jpeg_coefs_file_host(os.fsencode(path), sub_bits, out.ctypes.data, out.size, C.byref(need), info.ctypes.data))
+    keys = ["state", "ncomp", "blocks0", "blocks1", "blocks2", "rounds", "nsub", "nintervals"]
+    return out[:need.value], dict(zip(keys, (int(v) for v in info)))
 
 
 def load_image_224(path):

@@ -118,6 +118,8 @@ struct icl_ctx {
     icl_ingest_ws *ingest = nullptr; // buffers of the batched file path (jpeg_gpu.hip; created on first use)
     int64_t ingest_stats[3] = {0, 0, 0}; // last batched file call: JPEGs rebuilt on the GPU, files decoded on the host, bytes uploaded
     double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode
+    int entropy_mode = 0;                 // icl_set_ingest_options: ICL_ENTROPY_HOST / ICL_ENTROPY_GPU (environment: ICL_JPEG_ENTROPY=gpu)
+    int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
     std::vector<int32_t> last_merges; // pairs
     std::vector<float> last_merge_vals; // Ward distance of each merged pair

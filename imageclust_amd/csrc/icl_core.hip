@@ -67,6 +67,7 @@ extern "C" int icl_create(int device, icl_ctx **out)
         const int v = atoi(e8);
         if (v >= ICL_CONV_P8_OFF && v <= ICL_CONV_P8_ALL) c->conv_p8 = v;
     }
+    if (const char *ej = getenv("ICL_JPEG_ENTROPY")) c->entropy_mode = strcmp(ej, "gpu") == 0 ? ICL_ENTROPY_GPU : ICL_ENTROPY_HOST;
     *out = c;
     return ICL_OK;
 }

@@ -195,6 +195,60 @@ extern "C" int icl_load_image_224(const char *path, uint8_t *out)
     return no_throw(nullptr, "icl_load_image_224", [&]() -> int { return icl_read_image_224(nullptr, path, out); });
 }
 
+// Test hook without a GPU: the quantised coefficients of a JPEG by host stage A (sub_bits == 0), or by stage A0 + the GPU entropy
+// decoder's schedule run as a host loop (jpeg_entropy.h, icl_je_host_decode).
+extern "C" int icl_jpeg_coefs_file_host(const char *path, int sub_bits, int16_t *coefs, int64_t cap, int64_t *need, int32_t *info)
+{
+    if (!path || !need || !info || sub_bits < 0) return icl_fail(nullptr, ICL_ERR_ARG, "icl_jpeg_coefs_file_host: bad argument");
+    return no_throw(nullptr, "icl_jpeg_coefs_file_host", [&]() -> int {
+        std::vector<uint8_t> file;
+        if (icl_image_file_read(path, file) != ICL_IMAGE_JPEG) return icl_fail(nullptr, ICL_ERR_IO, "icl_jpeg_coefs_file_host: %s is not a readable JPEG", path);
+        icl_jpeg_coefs J;
+        std::vector<int16_t> own[3];
+        const std::vector<int16_t> *cf[3] = {&own[0], &own[1], &own[2]};
+        int rounds = 0, nsub = 0, nint = 0, state = 1;
+        if (sub_bits == 0) {
+            ICL_TRY(icl_jpeg_stage_a(nullptr, file.data(), file.size(), path, J));
+            for (int c = 0; c < 3; ++c) cf[c] = &J.comp[c].coefs;
+        } else {
+            icl_jpeg_a0 A;
+            bool qualifies = false, accepted = false;
+            const int rc = icl_jpeg_stage_a0(file.data(), file.size(), path, sub_bits, J, A, qualifies);
+            if (rc == ICL_ERR_ARG) return icl_fail(nullptr, rc, "icl_jpeg_coefs_file_host: sub_bits must be a multiple of 32, at least 64");
+            if (!qualifies) {
+                state = -1;
+            } else {
+                icl_je_host_decode(A, own, accepted, rounds);
+                state = accepted ? 1 : 0;
+                nsub = (int)A.scan.nsub;
+                nint = A.scan.nintervals;
+            }
+        }
+        int64_t total = 0;
+        info[0] = state;
+        info[1] = state == -1 ? 0 : J.ncomp;
+        for (int c = 0; c < 3; ++c) {
+            const int64_t nb = state == 1 && c < J.ncomp ? (int64_t)J.comp[c].wblocks * J.comp[c].hblocks : 0;
+            info[2 + c] = (int32_t)nb;
+            total += nb * 64;
+        }
+        info[5] = rounds;
+        info[6] = nsub;
+        info[7] = nint;
+        *need = total;
+        if (coefs && cap >= total) {
+            int64_t at = 0;
+            for (int c = 0; c < 3; ++c) {
+                const int64_t ne = (int64_t)info[2 + c] * 64;
+                if (ne && (int64_t)cf[c]->size() != ne) return icl_fail(nullptr, ICL_ERR_IO, "icl_jpeg_coefs_file_host: inconsistent coefficient count");
+                if (ne) memcpy(coefs + at, cf[c]->data(), (size_t)ne * 2);
+                at += ne;
+            }
+        }
+        return ICL_OK;
+    });
+}
+
 // cv::resize on an arbitrary u8 RGB image (the resize step of PreprocessImage alone; tests pin it to hand-derived vectors)
 extern "C" int icl_resize_u8(const uint8_t *src, int32_t sw, int32_t sh, uint8_t *dst, int32_t dw, int32_t dh)
 {

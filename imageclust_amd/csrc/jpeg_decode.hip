@@ -15,6 +15,7 @@
 // Arithmetic coding, lossless, 12-bit and CMYK return ICL_ERR_UNSUPPORTED.
 #include "icl_common.h"
 #include "ingest_pixels.h"
+#include "jpeg_entropy.h"
 #include "jpeg_stage.h"
 
 #include <cstring>
@@ -133,9 +134,65 @@ void idct_islow(const int *coef, uint8_t *out, int stride)
     }
 }
 
+void copy_table(const huff_table &t, icl_je_table &o)
+{
+    memcpy(o.fast, t.fast, sizeof o.fast);
+    memcpy(o.mincode, t.mincode, sizeof o.mincode);
+    memcpy(o.maxcode, t.maxcode, sizeof o.maxcode);
+    memcpy(o.valptr, t.valptr, sizeof o.valptr);
+    memcpy(o.vals, t.vals, sizeof o.vals);
+    o.mincode[0] = o.maxcode[0] = o.valptr[0] = 0; // (index 0 is never built, never read)
+}
+
+// The entropy-coded segment as bit_reader::fill sees it: FF 00 -> FF; an RSTn ends an interval; the first FF followed by anything else
+// (or the end of the data) ends the segment.  Every interval is padded with zeros to whole subsequences of sb bytes.  Returns where
+// the segment ended.
+const uint8_t *split_stream(const uint8_t *q, const uint8_t *e, size_t sb, icl_jpeg_a0 &A)
+{
+    std::vector<uint8_t> &st = A.stream;
+    st.clear();
+    A.intervals.clear();
+    st.reserve((size_t)(e - q) + sb);
+    size_t istart = 0;
+    uint32_t first_sub = 0;
+    auto close_interval = [&]() {
+        const size_t nbytes = st.size() - istart;
+        const size_t nsub = std::max<size_t>(1, (nbytes + sb - 1) / sb);
+        A.intervals.push_back(icl_je_interval{first_sub, (uint32_t)(nbytes * 8)});
+        first_sub += (uint32_t)nsub;
+        st.resize(istart + nsub * sb, 0);
+        istart = st.size();
+    };
+    for (;;) {
+        const uint8_t *ff = q < e ? (const uint8_t *)memchr(q, 0xFF, (size_t)(e - q)) : nullptr;
+        if (!ff) {
+            if (q < e) st.insert(st.end(), q, e);
+            q = e;
+            break;
+        }
+        st.insert(st.end(), q, ff);
+        q = ff;
+        if (q + 1 < e && q[1] == 0x00) {
+            st.push_back(0xFF);
+            q += 2;
+        } else if (q + 1 < e && q[1] >= 0xD0 && q[1] <= 0xD7) {
+            close_interval();
+            q += 2;
+        } else {
+            break;
+        }
+    }
+    close_interval();
+    A.scan.nsub = first_sub;
+    return q;
+}
+
 } // namespace
 
-static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J);
+// a0 != nullptr: stage A0.  The same marker loop, but the first scan of a file the GPU entropy decoder takes is not decoded:
+// its tables, geometry and unstuffed stream go to *a0.  Returns A0_NOT_QUALIFIED for every other file.
+constexpr int A0_NOT_QUALIFIED = -1;
+static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J, icl_jpeg_a0 *a0 = nullptr, int sub_bits = 0);
 static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb);
 
 // Decodes a JPEG file held in memory to interleaved RGB.  rgb is resized to w*h*3.  No C++ exception may cross the C ABI
@@ -169,6 +226,183 @@ int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *
         return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
     } catch (...) {
         return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Decoder error", path);
+    }
+}
+
+int icl_jpeg_stage_a0(const uint8_t *data, size_t len, const char *path, int sub_bits, icl_jpeg_coefs &J, icl_jpeg_a0 &A, bool &qualifies)
+{
+    qualifies = false;
+    J.orient = 1;
+    if (sub_bits < 64 || sub_bits % 32 != 0 || sub_bits > (1 << 20)) return ICL_ERR_ARG;
+    try {
+        const int rc = jpeg_stage_a_impl(nullptr, data, len, path, J, &A, sub_bits);
+        if (rc == A0_NOT_QUALIFIED) return ICL_OK;
+        qualifies = rc == ICL_OK;
+        return rc;
+    } catch (...) {
+        return ICL_ERR_NOMEM;
+    }
+}
+
+namespace {
+
+struct host_fetch {
+    const uint8_t *s;
+    size_t nwords;
+    uint32_t operator()(uint32_t w) const
+    {
+        if (w >= nwords) return 0;
+        uint32_t v;
+        memcpy(&v, s + 4 * (size_t)w, 4);
+        return __builtin_bswap32(v);
+    }
+};
+
+struct host_sink { // coefficients as stage A stores them: natural order, the DC value as (int16_t) of the int predictor
+    const icl_je_scan &S;
+    std::vector<int16_t> *coefs;
+    int64_t first;
+    uint32_t pred[3];
+    int64_t cur = -1;
+    int cur_c = 0;
+    int16_t *base = nullptr;
+    int16_t *at(uint32_t k)
+    {
+        if ((int64_t)k != cur) {
+            int64_t idx;
+            cur = k;
+            base = icl_je_block_place(S, first + k, cur_c, idx) ? coefs[cur_c].data() + idx * 64 : nullptr;
+        }
+        return base;
+    }
+    void dc(uint32_t k, int, int diff) // the component is the one of the block's place
+    {
+        if (int16_t *b = at(k)) {
+            pred[cur_c] += (uint32_t)diff;
+            b[0] = (int16_t)(int32_t)pred[cur_c];
+        }
+    }
+    void ac(uint32_t k, int z, int v)
+    {
+        if (int16_t *b = at(k)) b[icl_zigzag[z & 63]] = (int16_t)v;
+    }
+};
+
+} // namespace
+
+void icl_je_host_decode(const icl_jpeg_a0 &A, std::vector<int16_t> coefs[3], bool &accepted, int &rounds)
+{
+    const icl_je_scan &S = A.scan;
+    const uint32_t nsub = S.nsub, sb = (uint32_t)S.sub_bits;
+    const int nluma = S.ncomp == 1 ? 1 : S.hs * S.vs;
+    accepted = false;
+    rounds = 0;
+    if (nsub == 0 || A.intervals.empty() || A.stream.size() < (size_t)nsub * (sb / 8)) return;
+    host_fetch fetch{A.stream.data(), A.stream.size() / 4};
+    std::vector<icl_je_sub> sub(nsub);
+    std::vector<uint32_t> ivl(nsub);
+    for (size_t k = 0; k < A.intervals.size(); ++k) {
+        const uint32_t a = A.intervals[k].first_sub, b = k + 1 < A.intervals.size() ? A.intervals[k + 1].first_sub : nsub;
+        for (uint32_t i = a; i < b && i < nsub; ++i) ivl[i] = (uint32_t)k;
+    }
+    auto decode = [&](uint32_t i, auto &sink) {
+        const icl_je_interval &I = A.intervals[ivl[i]];
+        const uint32_t j = i - I.first_sub, start = j * sb, end = std::min<uint64_t>((uint64_t)start + sb, I.nbits);
+        icl_je_result r;
+        icl_je_decode_sub(A.tables, S.ncomp, nluma, S.bpm, S.uniform != 0, fetch, I.first_sub * (sb / 32), I.nbits, start, (uint32_t)end, sub[i].entry_p, sub[i].entry_bz, r, sink);
+        sub[i].exit_p = r.p;
+        sub[i].exit_bz = r.bz;
+        sub[i].n = r.n;
+        sub[i].flags = r.flags;
+        for (int q = 0; q < 6; ++q) sub[i].dcsum[q] = r.dcsum[q];
+    };
+    // ---- the synchronisation launches: workgroups of ICL_JE_WG subsequences, rounds inside, boundaries between launches ----
+    const uint32_t nwg = (nsub + ICL_JE_WG - 1) / ICL_JE_WG;
+    std::vector<uint32_t> bound[2] = {std::vector<uint32_t>(2 * (size_t)nwg), std::vector<uint32_t>(2 * (size_t)nwg)};
+    std::vector<uint32_t> todo, np, nbz;
+    icl_je_no_sink none;
+    for (int l = 0; l < ICL_JE_LAUNCHES; ++l)
+        for (uint32_t wg = 0; wg < nwg; ++wg) {
+            const uint32_t lo = wg * ICL_JE_WG, hi = std::min(nsub, lo + ICL_JE_WG);
+            for (uint32_t i = lo; i < hi; ++i) {
+                const uint32_t j = i - A.intervals[ivl[i]].first_sub;
+                if (l == 0) { // the guess: a block starts at the subsequence's first bit (true for j == 0)
+                    sub[i].entry_p = j * sb;
+                    sub[i].entry_bz = 0;
+                    decode(i, none);
+                } else if (i == lo && j > 0 && wg > 0) {
+                    const uint32_t p = bound[(l - 1) & 1][2 * (wg - 1)], bz = bound[(l - 1) & 1][2 * (wg - 1) + 1];
+                    if (p != sub[i].entry_p || bz != sub[i].entry_bz) {
+                        sub[i].entry_p = p;
+                        sub[i].entry_bz = bz;
+                        decode(i, none);
+                    }
+                }
+            }
+            for (int r = 1; r <= ICL_JE_ROUNDS; ++r) {
+                todo.clear();
+                np.clear();
+                nbz.clear();
+                for (uint32_t i = lo + 1; i < hi; ++i)
+                    if (i != A.intervals[ivl[i]].first_sub && (sub[i].entry_p != sub[i - 1].exit_p || sub[i].entry_bz != sub[i - 1].exit_bz)) {
+                        todo.push_back(i);
+                        np.push_back(sub[i - 1].exit_p);
+                        nbz.push_back(sub[i - 1].exit_bz);
+                    }
+                if (todo.empty()) break;
+                rounds = std::max(rounds, r);
+                for (size_t t = 0; t < todo.size(); ++t) {
+                    sub[todo[t]].entry_p = np[t];
+                    sub[todo[t]].entry_bz = nbz[t];
+                }
+                for (uint32_t i : todo) decode(i, none);
+            }
+            bound[l & 1][2 * wg] = sub[hi - 1].exit_p;
+            bound[l & 1][2 * wg + 1] = sub[hi - 1].exit_bz;
+        }
+    // ---- check + prefix sums ----
+    bool ok = icl_je_scan_ok(S);
+    int64_t blocks = 0;
+    uint32_t pred[3] = {0, 0, 0};
+    for (uint32_t i = 0; i < nsub && ok; ++i) {
+        const uint32_t k = ivl[i];
+        const icl_je_interval &I = A.intervals[k];
+        const uint32_t j = i - I.first_sub;
+        if (j == 0) pred[0] = pred[1] = pred[2] = 0;
+        sub[i].first_block = (uint32_t)blocks;
+        for (int c = 0; c < 3; ++c) sub[i].dcpred[c] = (int32_t)pred[c];
+        ok = ok && blocks < ((int64_t)1 << 31) && icl_je_sub_ok(S, k, j, sub[i], i ? sub[i - 1].exit_p : 0, i ? sub[i - 1].exit_bz : 0);
+        const bool last = i + 1 == nsub || ivl[i + 1] != k;
+        if (last) ok = ok && icl_je_interval_end_ok(I.nbits, sub[i]);
+        blocks += sub[i].n;
+        for (int q = 0; q < S.bpm && q < 6; ++q) pred[icl_je_phase_comp(S.ncomp, nluma, S.bpm, sub[i].first_block, q)] += (uint32_t)sub[i].dcsum[q];
+    }
+    ok = ok && icl_je_total_ok(S, blocks);
+    if (!ok) return;
+    // ---- write pass ----
+    for (int c = 0; c < 3; ++c) coefs[c].assign(c < S.ncomp ? (size_t)S.wblocks[c] * S.hblocks[c] * 64 : 0, 0);
+    for (uint32_t i = 0; i < nsub; ++i) {
+        host_sink sink{S, coefs, (int64_t)sub[i].first_block, {(uint32_t)sub[i].dcpred[0], (uint32_t)sub[i].dcpred[1], (uint32_t)sub[i].dcpred[2]}};
+        decode(i, sink);
+    }
+    accepted = true;
+}
+
+// stage A0 + host loop on a file in memory (the sanitizer harness under scratch/asan_jpeg/): 1 accepted, 0 rejected, -1 does not qualify
+int icl_jpeg_entropy_host_check(const uint8_t *data, size_t len, const char *path)
+{
+    try {
+        icl_jpeg_coefs J;
+        icl_jpeg_a0 A;
+        std::vector<int16_t> coefs[3];
+        bool qualifies = false, accepted = false;
+        int rounds = 0;
+        (void)icl_jpeg_stage_a0(data, len, path, ICL_JE_SUB_BITS, J, A, qualifies);
+        if (!qualifies) return -1;
+        icl_je_host_decode(A, coefs, accepted, rounds);
+        return accepted ? 1 : 0;
+    } catch (...) {
+        return -1;
     }
 }
 
@@ -212,7 +446,7 @@ static int exif_orientation(const uint8_t *s, size_t sl)
 }
 
 // Stage A: markers, tables, frame and scan headers, and every scan's entropy-coded data into J.comp[c].coefs.
-static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J)
+static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J, icl_jpeg_a0 *a0, int sub_bits)
 {
     int &W = J.W, &H = J.H, &orient = J.orient;
     auto fail = [&](int code, const char *what) { return icl_fail(ctx, code, "failed to read image: %s. %s", path, what); };
@@ -222,6 +456,8 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
     huff_table dc[4], ac[4];
     component comp[3];
     for (int c = 0; c < 3; ++c) comp[c].coefs.swap(J.comp[c].coefs); // decode into J's arrays (a reused J keeps their capacity)
+    if (a0)
+        for (int c = 0; c < 3; ++c) comp[c].coefs.clear(); // stage A0 leaves no coefficients
     int ncomp = 0, restart = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0, nscans = 0;
     bool have_sof = false, adobe = false, progressive = false;
     int adobe_transform = -1;
@@ -309,7 +545,7 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                 k.hblocks = mcuy * k.v;
                 k.dw = (W * k.h + hmax - 1) / hmax;
                 k.dh = (H * k.v + vmax - 1) / vmax;
-                k.coefs.assign((size_t)k.wblocks * k.hblocks * 64, 0);
+                if (!a0) k.coefs.assign((size_t)k.wblocks * k.hblocks * 64, 0);
             }
             have_sof = true;
         } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
@@ -347,6 +583,37 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
                 const bool need_dc = Ss == 0 && Ah == 0, need_ac = Se > 0;
                 if (k.td > 3 || k.ta > 3 || (need_dc && !dc[k.td].present) || (need_ac && !ac[k.ta].present)) return fail(ICL_ERR_IO, "Missing table");
                 comp[sc[i]].pred = 0;
+            }
+            if (a0) { // stage A0: one sequential scan that carries all components in frame order, or the file takes the usual route
+                if (progressive || nscans > 0 || ns != ncomp || len >= ((size_t)1 << 28)) return A0_NOT_QUALIFIED;
+                for (int i = 0; i < ns; ++i)
+                    if (sc[i] != i) return A0_NOT_QUALIFIED;
+                icl_je_scan &S = a0->scan;
+                S = icl_je_scan();
+                S.ncomp = ncomp;
+                S.hs = comp[0].h;
+                S.vs = comp[0].v;
+                S.bpm = ncomp == 1 ? 1 : S.hs * S.vs + 2;
+                S.mcux = mcux;
+                S.mcuy = mcuy;
+                S.restart = restart;
+                S.sub_bits = sub_bits;
+                for (int c = 0; c < ncomp; ++c) {
+                    S.wblocks[c] = comp[c].wblocks;
+                    S.hblocks[c] = comp[c].hblocks;
+                    copy_table(dc[comp[c].td], a0->tables[2 * c]);
+                    copy_table(ac[comp[c].ta], a0->tables[2 * c + 1]);
+                }
+                S.uniform = ncomp == 3 ? 1 : 0;
+                for (int c = 1; c < ncomp; ++c)
+                    if (memcmp(&a0->tables[0], &a0->tables[2 * c], sizeof(icl_je_table)) || memcmp(&a0->tables[1], &a0->tables[2 * c + 1], sizeof(icl_je_table))) S.uniform = 0;
+                const uint8_t *q = split_stream(data + pos + seglen, data + len, (size_t)sub_bits / 8, *a0);
+                S.nintervals = (int32_t)a0->intervals.size();
+                ++nscans;
+                // continue at the marker that ended the entropy-coded segment (the search of the decoding branch below, from the segment's end)
+                while (q + 1 < data + len && !(q[0] == 0xFF && q[1] != 0x00 && !(q[1] >= 0xD0 && q[1] <= 0xD7) && q[1] != 0xFF)) ++q;
+                pos = (size_t)(q - data);
+                continue;
             }
             bit_reader br{data + pos + seglen, data + len};
             int eobrun = 0;

@@ -28,7 +28,7 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
 namespace {
 
 constexpr int OUTW = ICL_IMG_W, OUTH = ICL_IMG_H;
-enum { KIND_FAILED = 0, KIND_JPEG = 1, KIND_HOST = 2 };
+enum { KIND_FAILED = 0, KIND_JPEG = 1, KIND_HOST = 2, KIND_JSTREAM = 3 }; // (KIND_JSTREAM: a JPEG as bit stream; the kernels see it as KIND_JPEG)
 
 struct ingest_image {
     int32_t kind;
@@ -57,6 +57,23 @@ struct ingest_plane {
 
 constexpr int IDCT_THREADS = 64;
 constexpr int IDCT_SLOT = 65; // ints per thread in LDS (odd stride: no bank conflicts between the threads' slots)
+
+// columns, rows, and the block's 8 x 8 pixels into its plane (shared by the two input forms below)
+__device__ __forceinline__ void idct_store(const int *coef, uint8_t *dst, int64_t stride)
+{
+    int ws[64];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) icl_idct_islow_col(coef + c, ws + c); // branch-free (the host's all-AC-zero shortcut gives the same values)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        int px[8];
+        icl_idct_islow_row(ws + 8 * r, px);
+        uint2 v;
+        v.x = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+        v.y = (uint32_t)px[4] | ((uint32_t)px[5] << 8) | ((uint32_t)px[6] << 16) | ((uint32_t)px[7] << 24);
+        *(uint2 *)(dst + r * stride) = v; // plane offsets and strides are multiples of 8
+    }
+}
 
 // IJG jidctint.c jpeg_idct_islow (ingest_pixels.h, as in host stage B): one thread per block; the dequantised coefficients are
 // scattered from zig-zag order into the thread's LDS slot.
@@ -91,18 +108,43 @@ __global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const ingest_pl
         const int z = icl_zigzag[i];
         coef[z] = (int)cf[i] * (int)P.qt[z];
     }
-    int ws[64];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) icl_idct_islow_col(coef + c, ws + c); // branch-free (the host's all-AC-zero shortcut gives the same values)
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        int px[8];
-        icl_idct_islow_row(ws + 8 * r, px);
-        uint2 v;
-        v.x = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
-        v.y = (uint32_t)px[4] | ((uint32_t)px[5] << 8) | ((uint32_t)px[6] << 16) | ((uint32_t)px[7] << 24);
-        *(uint2 *)(scratch + o + r * stride) = v; // plane offsets and strides are multiples of 8
+    idct_store(coef, scratch + o, stride);
+}
+
+// The dense-input form for planes whose coefficients were decoded on the GPU (jpeg_huff_gpu.hip): 64 int16 per block in natural order
+// at byte offset coef_off of `dense` (such a plane has offs_off == -1, which the packed-input kernel above skips).
+__global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_dense_kernel(const ingest_plane *__restrict__ planes, int nplanes, const int16_t *__restrict__ dense,
+                                                                       int64_t dense_bytes, uint8_t *__restrict__ scratch, int64_t scratch_bytes, int64_t total_blocks)
+{
+    __shared__ int lds[IDCT_THREADS * IDCT_SLOT];
+    int *coef = lds + threadIdx.x * IDCT_SLOT;
+    const int64_t g = (int64_t)blockIdx.x * IDCT_THREADS + threadIdx.x;
+    if (g >= total_blocks) return;
+    int lo = 0, hi = nplanes - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (planes[mid].first_block <= g) lo = mid;
+        else hi = mid - 1;
     }
+    const ingest_plane &P = planes[lo];
+    const int64_t b = g - P.first_block;
+    if (b < 0 || b >= P.nblocks || P.wblocks <= 0 || P.offs_off != -1) return;
+    if (P.coef_off < 0 || (P.coef_off & 15) || P.coef_off + (int64_t)P.nblocks * 128 > dense_bytes) return;
+    const int64_t stride = (int64_t)P.wblocks * 8, by = b / P.wblocks, bx = b - by * P.wblocks;
+    const int64_t o = P.plane_off + by * 8 * stride + bx * 8;
+    if (P.plane_off < 0 || P.plane_off + P.plane_bytes > scratch_bytes || (by * 8 + 7) * stride + bx * 8 + 8 > P.plane_bytes) return;
+    const uint4 *cf = (const uint4 *)((const uint8_t *)dense + P.coef_off + b * 128);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const uint4 v = cf[q];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            coef[q * 8 + 2 * e] = (int)(int16_t)(w[e] & 0xffffu) * (int)P.qt[q * 8 + 2 * e];
+            coef[q * 8 + 2 * e + 1] = (int)(int16_t)(w[e] >> 16) * (int)P.qt[q * 8 + 2 * e + 1];
+        }
+    }
+    idct_store(coef, scratch + o, stride);
 }
 
 // the chroma sample at (X, y) of the full-resolution image from D's chroma plane pl (fancy upsampling: ingest_pixels.h)
@@ -179,9 +221,13 @@ __global__ void fill_nan_rows_kernel(float *out, const int32_t *rows, int nrows,
 // ---- host side -------------------------------------------------------------------------------------------------------
 
 constexpr int64_t SLAB_IMAGES = 256;                 // output rows per slab (the forward pass's batch)
-constexpr int64_t SLAB_PAYLOAD = 128ll << 20;        // coefficient / finished-image bytes per slab (pinned, two of them)
+constexpr int64_t SLAB_PAYLOAD = 128ll << 20;        // coefficient / stream / finished-image bytes per slab (pinned, two of them)
 constexpr int64_t SLAB_SCRATCH = 768ll << 20;        // u8 planes of one slab on the device
-constexpr int64_t HDR_BYTES = SLAB_IMAGES * (int64_t)sizeof(ingest_image) + 3 * SLAB_IMAGES * (int64_t)sizeof(ingest_plane);
+constexpr int64_t SLAB_COEF = 2 * SLAB_SCRATCH;      // ICL_ENTROPY_GPU: dense int16 coefficients of one slab (two bytes per plane sample)
+constexpr int64_t SLAB_SUBS = SLAB_PAYLOAD / (ICL_JE_SUB_BITS / 8); // ... subsequences of one slab
+constexpr int64_t SLAB_WGS = SLAB_SUBS / ICL_JE_WG + SLAB_IMAGES;   // ... workgroups (every image rounds up)
+constexpr int64_t HDR_SCANS = SLAB_IMAGES * (int64_t)sizeof(ingest_image) + 3 * SLAB_IMAGES * (int64_t)sizeof(ingest_plane); // offset of the scan descriptors
+constexpr int64_t HDR_BYTES = HDR_SCANS + SLAB_IMAGES * (int64_t)sizeof(icl_je_scan);
 
 static int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
@@ -198,11 +244,34 @@ struct file_result { // what a worker hands the slab builder for one file
     int W = 0, H = 0, ncomp = 0, hs = 1, vs = 1, is_rgb = 0, orient = 1;
     uint16_t qt[3][64];
     comp_meta cm[3];
-    std::vector<uint8_t> packed; // KIND_JPEG: the components' block offsets + coefficients; KIND_HOST: the 224x224x3 image
+    // KIND_JPEG: the components' block offsets + coefficients; KIND_HOST: the 224x224x3 image; KIND_JSTREAM: Huffman tables, restart
+    // intervals, unstuffed stream (scan holds their offsets within this buffer)
+    std::vector<uint8_t> packed;
+    icl_je_scan scan;
     int64_t plane_bytes = 0;
+    bool host_entropy = false; // a JPEG whose entropy decoder ran on the host
 };
 
 static int64_t plane_bytes_of(const icl_jpeg_component &k) { return (int64_t)k.wblocks * 8 * k.hblocks * 8; }
+
+static void frame_meta(const icl_jpeg_coefs &J, file_result &r)
+{
+    for (int c = 0; c < J.ncomp; ++c) {
+        const icl_jpeg_component &k = J.comp[c];
+        r.cm[c].wblocks = k.wblocks;
+        r.cm[c].hblocks = k.hblocks;
+        r.cm[c].dw = k.dw;
+        r.cm[c].dh = k.dh;
+        memcpy(r.qt[c], J.qt[c], sizeof r.qt[c]);
+    }
+    r.W = J.W;
+    r.H = J.H;
+    r.ncomp = J.ncomp;
+    r.hs = J.comp[0].h;
+    r.vs = J.comp[0].v;
+    r.is_rgb = J.is_rgb ? 1 : 0;
+    r.orient = J.orient;
+}
 
 // Stage-A output -> the compact per-block form: uint32 offsets (nblocks + 1) and the zig-zag coefficients up to each block's
 // last non-zero one.  Returns false when the image does not fit one slab (it then takes the host path).
@@ -228,15 +297,12 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
     if (total > SLAB_PAYLOAD || planes > SLAB_SCRATCH) return false;
     r.packed.resize((size_t)total);
     r.plane_bytes = planes;
+    frame_meta(J, r);
     int64_t pos = 0;
     for (int c = 0; c < J.ncomp; ++c) {
         const icl_jpeg_component &k = J.comp[c];
         const int64_t nb = (int64_t)k.wblocks * k.hblocks;
         comp_meta &m = r.cm[c];
-        m.wblocks = k.wblocks;
-        m.hblocks = k.hblocks;
-        m.dw = k.dw;
-        m.dh = k.dh;
         m.ncoef = ncoef[c];
         m.offs_off = pos;
         m.coef_off = pos + align16((nb + 1) * 4);
@@ -254,22 +320,43 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
         offs[(size_t)nb] = at;
         memcpy(r.packed.data() + m.offs_off, offs.data(), ((size_t)nb + 1) * 4);
         pos = m.coef_off + align16((int64_t)m.ncoef * 2);
-        memcpy(r.qt[c], J.qt[c], sizeof r.qt[c]);
     }
-    r.W = J.W;
-    r.H = J.H;
-    r.ncomp = J.ncomp;
-    r.hs = J.comp[0].h;
-    r.vs = J.comp[0].v;
-    r.is_rgb = J.is_rgb ? 1 : 0;
-    r.orient = J.orient;
     return true;
 }
 
-// One file, on a worker thread: stage A for a JPEG the GPU takes, the whole host path for everything else.  Status codes and
-// messages are those of icl_load_image_224 (image_io.hip).
-static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32_t> &offs, file_result &r)
+// Stage-A0 output -> one buffer: tables, intervals, stream (each on a 16-byte boundary).  Returns false when the image does not fit one slab.
+static bool pack_stream(const icl_jpeg_coefs &J, const icl_jpeg_a0 &A, file_result &r)
 {
+    int64_t planes = 0;
+    for (int c = 0; c < J.ncomp; ++c) planes += align16(plane_bytes_of(J.comp[c]));
+    const int64_t tb = align16((int64_t)(2 * J.ncomp) * (int64_t)sizeof(icl_je_table)), ib = align16((int64_t)A.intervals.size() * (int64_t)sizeof(icl_je_interval));
+    const int64_t sbytes = (int64_t)A.scan.nsub * (A.scan.sub_bits / 8);
+    if ((int64_t)A.stream.size() != sbytes || tb + ib + sbytes > SLAB_PAYLOAD || planes > SLAB_SCRATCH || (int64_t)A.scan.nsub > SLAB_SUBS) return false;
+    r.packed.resize((size_t)(tb + ib + sbytes));
+    memcpy(r.packed.data(), A.tables, (size_t)(2 * J.ncomp) * sizeof(icl_je_table));
+    memcpy(r.packed.data() + tb, A.intervals.data(), A.intervals.size() * sizeof(icl_je_interval));
+    memcpy(r.packed.data() + tb + ib, A.stream.data(), (size_t)sbytes);
+    r.scan = A.scan;
+    r.scan.tables_off = 0;
+    r.scan.intervals_off = tb;
+    r.scan.stream_off = tb + ib;
+    r.plane_bytes = planes;
+    frame_meta(J, r);
+    return true;
+}
+
+struct worker_state { // buffers a worker reuses from file to file
+    icl_jpeg_coefs J;
+    icl_jpeg_a0 A;
+    std::vector<uint32_t> offs;
+};
+
+// One file, on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
+// qualifies), stage A for every other JPEG the GPU takes, the whole host path for everything else.  Status codes and messages are
+// those of icl_load_image_224 (image_io.hip).
+static void process_file(const char *path, worker_state &ws, int entropy, file_result &r)
+{
+    icl_jpeg_coefs &J = ws.J;
     auto fail_from_tls = [&](int rc) {
         r.kind = KIND_FAILED;
         r.rc = rc;
@@ -280,9 +367,18 @@ static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32
         int w = 0, h = 0;
         const int fmt = icl_image_file_read(path, file);
         if (fmt == ICL_IMAGE_JPEG) {
+            if (entropy == ICL_ENTROPY_GPU) {
+                bool qualifies = false;
+                (void)icl_jpeg_stage_a0(file.data(), file.size(), path, ICL_JE_SUB_BITS, J, ws.A, qualifies); // (an error: the usual route reports it)
+                if (qualifies && pack_stream(J, ws.A, r)) {
+                    r.kind = KIND_JSTREAM;
+                    return;
+                }
+            }
+            r.host_entropy = true;
             const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), path, J);
             if (rc) return fail_from_tls(rc);
-            if (pack_jpeg(J, r, offs)) {
+            if (pack_jpeg(J, r, ws.offs)) {
                 r.kind = KIND_JPEG;
                 return;
             }
@@ -314,19 +410,28 @@ static void process_file(const char *path, icl_jpeg_coefs &J, std::vector<uint32
 
 // Buffers of the batched file path, kept by the context between calls (freed by icl_destroy).
 struct icl_ingest_ws {
-    uint8_t *h_slab[2] = {nullptr, nullptr}; // pinned: header (images + planes) then payload
+    uint8_t *h_slab[2] = {nullptr, nullptr}; // pinned: header (images + planes + scans) then payload
     hipEvent_t ev_up[2] = {nullptr, nullptr};
     uint8_t *d_hdr = nullptr, *d_payload = nullptr, *d_scratch = nullptr, *d_img = nullptr;
     float *d_emb = nullptr;
     int32_t *d_rows = nullptr;
     int emb_head = 0;
+    // ICL_ENTROPY_GPU (allocated on first use)
+    int16_t *d_coef = nullptr;
+    icl_je_sub *d_sub = nullptr;
+    uint32_t *d_bound = nullptr;
+    int32_t *d_accepted = nullptr;
+    int32_t *h_accepted = nullptr; // pinned: one flag per stream image of a call
+    int64_t h_accepted_cap = 0;
     ~icl_ingest_ws()
     {
         for (int q = 0; q < 2; ++q) {
             if (h_slab[q]) (void)hipHostFree(h_slab[q]);
             if (ev_up[q]) (void)hipEventDestroy(ev_up[q]);
         }
-        for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_emb, (void *)d_rows})
+        if (h_accepted) (void)hipHostFree(h_accepted);
+        for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_emb, (void *)d_rows, (void *)d_coef, (void *)d_sub, (void *)d_bound,
+                        (void *)d_accepted})
             if (p) (void)hipFree(p);
     }
 };
@@ -359,13 +464,178 @@ static int ingest_ws(icl_ctx *ctx, icl_ingest_ws *&ws)
     return ICL_OK;
 }
 
-// The pipeline behind icl_load_images_224_dev and icl_embed_files[_dev].  mode 0: u8 rows into d_u8; 1: embeddings into host
-// `out`; 2: embeddings into device d_out.
-static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
-                        int32_t *status, const char *what)
+// the buffers of the GPU entropy decoder; room for the accepted flags of a call with n files
+static int entropy_ws(icl_ctx *ctx, icl_ingest_ws *ws, int64_t n)
+{
+    if (!ws->d_coef) {
+        if (hipMalloc((void **)&ws->d_coef, (size_t)SLAB_COEF) != hipSuccess || hipMalloc((void **)&ws->d_sub, (size_t)SLAB_SUBS * sizeof(icl_je_sub)) != hipSuccess ||
+            hipMalloc((void **)&ws->d_bound, (size_t)SLAB_WGS * 4 * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc((void **)&ws->d_accepted, (size_t)SLAB_IMAGES * 4) != hipSuccess)
+            return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: device buffers of the entropy decoder");
+    }
+    if (ws->h_accepted_cap < n) {
+        if (ws->h_accepted) (void)hipHostFree(ws->h_accepted);
+        ws->h_accepted = nullptr;
+        ws->h_accepted_cap = 0;
+        const int64_t cap = std::max<int64_t>(n, 4096);
+        if (hipHostMalloc((void **)&ws->h_accepted, (size_t)cap * 4, hipHostMallocDefault) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: pinned flags");
+        ws->h_accepted_cap = cap;
+    }
+    return ICL_OK;
+}
+
+namespace {
+
+// what the slab builder has placed so far
+struct slab_fill {
+    int nimg = 0, npl = 0, nscan = 0, npacked = 0, ndense = 0;
+    int64_t used = 0, scratch_used = 0, blocks = 0, coef_used = 0 /* bytes */, subs = 0, wgs = 0;
+};
+
+// One KIND_JPEG / KIND_JSTREAM result into the slab: image descriptor, planes, payload, and (stream) the scan descriptor.
+static bool place_jpeg(const file_result &r, slab_fill &F, ingest_image &D, ingest_plane *pls, icl_je_scan *scans, uint8_t *pay)
+{
+    const bool stream = r.kind == KIND_JSTREAM;
+    D.kind = KIND_JPEG;
+    D.W = r.W;
+    D.H = r.H;
+    D.orient = r.orient;
+    D.ncomp = r.ncomp;
+    D.hs = r.hs;
+    D.vs = r.vs;
+    D.is_rgb = r.is_rgb;
+    const bool swap = icl_exif_swaps_axes(r.orient);
+    D.ow = swap ? r.H : r.W;
+    D.oh = swap ? r.W : r.H;
+    D.area = icl_resize_is_area(D.ow, D.oh, OUTW, OUTH);
+    icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
+    icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
+    if (F.used + (int64_t)r.packed.size() > SLAB_PAYLOAD) return false;
+    memcpy(pay + F.used, r.packed.data(), r.packed.size());
+    icl_je_scan *S = nullptr;
+    if (stream) {
+        if (F.nscan >= SLAB_IMAGES) return false;
+        S = &scans[F.nscan];
+        *S = r.scan;
+        S->tables_off += F.used;
+        S->intervals_off += F.used;
+        S->stream_off += F.used;
+        S->sub_first = F.subs;
+        S->wg_first = F.wgs;
+        F.subs += S->nsub;
+        F.wgs += icl_ceil_div(S->nsub, ICL_JE_WG);
+        if (F.subs > SLAB_SUBS || F.wgs > SLAB_WGS) return false;
+        ++F.nscan;
+    }
+    for (int c = 0; c < r.ncomp; ++c) {
+        const comp_meta &cm = r.cm[c];
+        ingest_plane &P = pls[F.npl++];
+        P.first_block = F.blocks;
+        P.nblocks = cm.wblocks * cm.hblocks;
+        P.wblocks = cm.wblocks;
+        P.plane_off = F.scratch_used;
+        P.plane_bytes = (int64_t)cm.wblocks * 8 * cm.hblocks * 8;
+        if (stream) { // dense coefficients, written by the GPU decoder
+            P.ncoef = 0;
+            P.offs_off = -1;
+            P.coef_off = F.coef_used;
+            S->coef_off[c] = F.coef_used / 2;
+            F.coef_used += align16((int64_t)P.nblocks * 128);
+            ++F.ndense;
+        } else {
+            P.ncoef = cm.ncoef;
+            P.offs_off = F.used + cm.offs_off;
+            P.coef_off = F.used + cm.coef_off;
+            ++F.npacked;
+        }
+        memcpy(P.qt, r.qt[c], sizeof P.qt);
+        F.blocks += P.nblocks;
+        if (c == 0) {
+            D.yplane = P.plane_off;
+            D.ystride = cm.wblocks * 8;
+            D.yrows = cm.hblocks * 8;
+        } else {
+            D.cplane[c - 1] = P.plane_off;
+            D.cstride = cm.wblocks * 8;
+            D.crows = cm.hblocks * 8;
+            D.cw = cm.dw;
+            D.chh = cm.dh;
+        }
+        F.scratch_used += align16(P.plane_bytes);
+    }
+    // sizes were produced by stage A / A0 + pack_* on this host; re-check what the kernels rely on
+    const bool ok = D.W >= 1 && D.H >= 1 && D.W <= D.ystride && D.H <= D.yrows && (D.ncomp == 1 || (D.cw >= 1 && D.chh >= 1 && D.cw <= D.cstride && D.chh <= D.crows)) &&
+                    F.scratch_used <= SLAB_SCRATCH && F.coef_used <= SLAB_COEF;
+    F.used += align16((int64_t)r.packed.size());
+    return ok;
+}
+
+// upload of a filled slab and its kernels up to the planes: (entropy decode,) IDCT
+static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, uint8_t *hs, const slab_fill &F, int64_t &upload)
+{
+    hipStream_t st = ctx->stream;
+    ingest_image *imgs = (ingest_image *)hs;
+    ingest_plane *pls = (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image));
+    ingest_image *d_imgs = (ingest_image *)ws->d_hdr;
+    ingest_plane *d_pls = (ingest_plane *)(ws->d_hdr + SLAB_IMAGES * sizeof(ingest_image));
+    icl_je_scan *d_scans = (icl_je_scan *)(ws->d_hdr + HDR_SCANS);
+    if (F.nimg) ICL_HIP(ctx, hipMemcpyAsync(d_imgs, imgs, (size_t)F.nimg * sizeof(ingest_image), hipMemcpyHostToDevice, st));
+    if (F.npl) ICL_HIP(ctx, hipMemcpyAsync(d_pls, pls, (size_t)F.npl * sizeof(ingest_plane), hipMemcpyHostToDevice, st));
+    if (F.nscan) ICL_HIP(ctx, hipMemcpyAsync(d_scans, hs + HDR_SCANS, (size_t)F.nscan * sizeof(icl_je_scan), hipMemcpyHostToDevice, st));
+    if (F.used) ICL_HIP(ctx, hipMemcpyAsync(ws->d_payload, hs + HDR_BYTES, (size_t)F.used, hipMemcpyHostToDevice, st));
+    upload += (int64_t)F.nimg * (int64_t)sizeof(ingest_image) + (int64_t)F.npl * (int64_t)sizeof(ingest_plane) + (int64_t)F.nscan * (int64_t)sizeof(icl_je_scan) + F.used;
+    if (F.nscan) {
+        ICL_HIP(ctx, hipMemsetAsync(ws->d_coef, 0, (size_t)F.coef_used, st)); // blocks end at their EOB: the rest of a block is zero
+        icl_je_slab s;
+        s.d_scans = d_scans;
+        s.nscans = F.nscan;
+        s.d_payload = ws->d_payload;
+        s.payload_bytes = SLAB_PAYLOAD;
+        s.d_sub = ws->d_sub;
+        s.nsub_cap = SLAB_SUBS;
+        s.d_bound = ws->d_bound;
+        s.nwg_cap = SLAB_WGS;
+        s.total_wgs = F.wgs;
+        s.d_accepted = ws->d_accepted;
+        s.d_coef = ws->d_coef;
+        s.coef_elems = SLAB_COEF / 2;
+        ICL_TRY(icl_je_decode_slab(ctx, st, s));
+    }
+    if (F.npacked) {
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, F.npl, (const uint8_t *)ws->d_payload,
+                           (int64_t)SLAB_PAYLOAD, ws->d_scratch, (int64_t)SLAB_SCRATCH, F.blocks);
+        ICL_HIP(ctx, hipGetLastError());
+    }
+    if (F.ndense) {
+        hipLaunchKernelGGL(jpeg_idct_dense_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, F.npl,
+                           (const int16_t *)ws->d_coef, (int64_t)SLAB_COEF, ws->d_scratch, (int64_t)SLAB_SCRATCH, F.blocks);
+        ICL_HIP(ctx, hipGetLastError());
+    }
+    return ICL_OK;
+}
+
+struct file_fail {
+    int64_t index;
+    int rc;
+    std::string err;
+};
+
+struct ingest_totals {
+    int64_t gpu_jpegs = 0, host_files = 0, upload = 0, decode_ns = 0;
+    int64_t gpu_entropy = 0, host_entropy = 0, stream_bytes = 0;
+};
+
+} // namespace
+
+// One pass of the pipeline behind icl_load_images_224_dev and icl_embed_files[_dev].  mode 0: u8 rows into d_u8; 1: embeddings into
+// host `out`; 2: embeddings into device d_out.  Per-file failures go to `fails` (and status[]); rejected receives the rows whose GPU
+// entropy decode was not accepted (their output rows are to be redone by a pass with ICL_ENTROPY_HOST).
+static int ingest_pass(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out, int32_t *status,
+                       const char *what, int entropy, std::vector<file_fail> &fails, std::vector<int64_t> &rejected, ingest_totals &tot)
 {
     icl_ingest_ws *ws = nullptr;
     ICL_TRY(ingest_ws(ctx, ws));
+    if (entropy == ICL_ENTROPY_GPU) ICL_TRY(entropy_ws(ctx, ws, n));
     if (mode && ws->emb_head < head) {
         if (ws->d_emb) (void)hipFree(ws->d_emb);
         ws->d_emb = nullptr;
@@ -385,8 +655,7 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
     std::atomic<int64_t> decode_ns{0};
     const int64_t window = 2 * SLAB_IMAGES, byte_budget = 2 * SLAB_PAYLOAD;
     auto worker = [&]() {
-        icl_jpeg_coefs J;
-        std::vector<uint32_t> offs;
+        std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state());
         for (;;) {
             int64_t i;
             {
@@ -396,8 +665,8 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
                 i = next_claim++;
             }
             const auto t0 = std::chrono::steady_clock::now();
-            std::unique_ptr<file_result> r(new (std::nothrow) file_result());
-            if (r) process_file(paths[i], J, offs, *r);
+            std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
+            if (r) process_file(paths[i], *wst, entropy, *r);
             decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
             std::lock_guard<std::mutex> lk(m);
             if (!r) { // no memory for even the result: the call fails (the slab builder waits for this row)
@@ -430,19 +699,19 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
     for (int t = 0; t < nthr; ++t) pool.emplace_back(worker);
 
     // ---- slab builder (this thread): rows in file order, double-buffered pinned slabs, everything on ctx->stream ----
-    int64_t gpu_jpegs = 0, host_files = 0, upload = 0;
     std::vector<int32_t> failed_rows;
+    std::vector<int64_t> stream_rows; // the row of every stream image of the call, in the order of h_accepted
     for (int64_t k = 0; next_pack < n; ++k) {
         uint8_t *hs = ws->h_slab[k & 1];
         ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[k & 1])); // the upload that last read this slab has finished
         ingest_image *imgs = (ingest_image *)hs;
         ingest_plane *pls = (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image));
+        icl_je_scan *scans = (icl_je_scan *)(hs + HDR_SCANS);
         uint8_t *pay = hs + HDR_BYTES;
         const int64_t first = next_pack;
-        int nimg = 0, npl = 0;
-        int64_t used = 0, scratch_used = 0, blocks = 0;
+        slab_fill F;
         failed_rows.clear();
-        while (next_pack < n && nimg < SLAB_IMAGES) {
+        while (next_pack < n && F.nimg < SLAB_IMAGES) {
             std::unique_ptr<file_result> r;
             {
                 std::unique_lock<std::mutex> lk(m);
@@ -450,91 +719,45 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
                 if (worker_oom) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", what);
                 file_result &q = *res[(size_t)next_pack];
                 const int64_t need = q.kind == KIND_FAILED ? 0 : align16((int64_t)q.packed.size());
-                if (nimg > 0 && (used + need > SLAB_PAYLOAD || scratch_used + align16(q.plane_bytes) > SLAB_SCRATCH)) break;
+                const int64_t nsubs = q.kind == KIND_JSTREAM ? (int64_t)q.scan.nsub : 0;
+                if (F.nimg > 0 && (F.used + need > SLAB_PAYLOAD || F.scratch_used + align16(q.plane_bytes) > SLAB_SCRATCH || F.subs + nsubs > SLAB_SUBS)) break;
                 r = std::move(res[(size_t)next_pack]);
                 pending_bytes -= (int64_t)r->packed.size();
                 ++next_pack;
                 cv.notify_all();
             }
-            const int64_t row = first + nimg;
-            ingest_image &D = imgs[nimg];
+            const int64_t row = first + F.nimg;
+            ingest_image &D = imgs[F.nimg];
             memset(&D, 0, offsetof(ingest_image, xofs));
             D.kind = r->kind;
             if (status) status[row] = r->rc;
             if (r->kind == KIND_FAILED) {
-                failed_rows.push_back(nimg);
-                std::lock_guard<std::mutex> lk(m);
-                res[(size_t)row].reset(r.release()); // kept for the error report
+                failed_rows.push_back(F.nimg);
+                fails.push_back(file_fail{row, r->rc ? r->rc : ICL_ERR_IO, r->err});
             } else if (r->kind == KIND_HOST) {
-                D.host_off = used;
-                memcpy(pay + used, r->packed.data(), (size_t)ICL_IMG_BYTES);
-                used += align16(ICL_IMG_BYTES);
-                ++host_files;
+                D.host_off = F.used;
+                memcpy(pay + F.used, r->packed.data(), (size_t)ICL_IMG_BYTES);
+                F.used += align16(ICL_IMG_BYTES);
+                ++tot.host_files;
             } else {
-                // sizes were produced by stage A + pack_jpeg on this host; re-check what the kernels rely on
-                D.W = r->W;
-                D.H = r->H;
-                D.orient = r->orient;
-                D.ncomp = r->ncomp;
-                D.hs = r->hs;
-                D.vs = r->vs;
-                D.is_rgb = r->is_rgb;
-                const bool swap = icl_exif_swaps_axes(r->orient);
-                D.ow = swap ? r->H : r->W;
-                D.oh = swap ? r->W : r->H;
-                D.area = icl_resize_is_area(D.ow, D.oh, OUTW, OUTH);
-                icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
-                icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
-                memcpy(pay + used, r->packed.data(), r->packed.size());
-                for (int c = 0; c < r->ncomp; ++c) {
-                    const comp_meta &cm = r->cm[c];
-                    ingest_plane &P = pls[npl++];
-                    P.first_block = blocks;
-                    P.nblocks = cm.wblocks * cm.hblocks;
-                    P.wblocks = cm.wblocks;
-                    P.ncoef = cm.ncoef;
-                    P.offs_off = used + cm.offs_off;
-                    P.coef_off = used + cm.coef_off;
-                    P.plane_off = scratch_used;
-                    P.plane_bytes = (int64_t)cm.wblocks * 8 * cm.hblocks * 8;
-                    memcpy(P.qt, r->qt[c], sizeof P.qt);
-                    blocks += P.nblocks;
-                    if (c == 0) {
-                        D.yplane = P.plane_off;
-                        D.ystride = cm.wblocks * 8;
-                        D.yrows = cm.hblocks * 8;
-                    } else {
-                        D.cplane[c - 1] = P.plane_off;
-                        D.cstride = cm.wblocks * 8;
-                        D.crows = cm.hblocks * 8;
-                        D.cw = cm.dw;
-                        D.chh = cm.dh;
-                    }
-                    scratch_used += align16(P.plane_bytes);
+                if (!place_jpeg(*r, F, D, pls, scans, pay)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, paths[row]);
+                ++tot.gpu_jpegs;
+                if (r->kind == KIND_JSTREAM) {
+                    stream_rows.push_back(row);
+                    tot.stream_bytes += (int64_t)r->scan.nsub * (ICL_JE_SUB_BITS / 8);
                 }
-                const bool ok = D.W >= 1 && D.H >= 1 && D.W <= D.ystride && D.H <= D.yrows &&
-                                (D.ncomp == 1 || (D.cw >= 1 && D.chh >= 1 && D.cw <= D.cstride && D.chh <= D.crows)) &&
-                                scratch_used <= SLAB_SCRATCH && used + (int64_t)r->packed.size() <= SLAB_PAYLOAD;
-                if (!ok) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, paths[row]);
-                used += align16((int64_t)r->packed.size());
-                ++gpu_jpegs;
             }
-            ++nimg;
+            if (r->host_entropy) ++tot.host_entropy; // (whatever became of it: stage A ran, or tried to)
+            ++F.nimg;
         }
         // ---- upload + rebuild (+ forward pass) of this slab ----
         hipStream_t st = ctx->stream;
+        const int nimg = F.nimg;
         ingest_image *d_imgs = (ingest_image *)ws->d_hdr;
-        ingest_plane *d_pls = (ingest_plane *)(ws->d_hdr + SLAB_IMAGES * sizeof(ingest_image));
-        ICL_HIP(ctx, hipMemcpyAsync(d_imgs, imgs, (size_t)nimg * sizeof(ingest_image), hipMemcpyHostToDevice, st));
-        if (npl) ICL_HIP(ctx, hipMemcpyAsync(d_pls, pls, (size_t)npl * sizeof(ingest_plane), hipMemcpyHostToDevice, st));
-        if (used) ICL_HIP(ctx, hipMemcpyAsync(ws->d_payload, pay, (size_t)used, hipMemcpyHostToDevice, st));
+        ICL_TRY(run_slab_decode(ctx, ws, hs, F, tot.upload));
         ICL_HIP(ctx, hipEventRecord(ws->ev_up[k & 1], st));
-        upload += (int64_t)nimg * (int64_t)sizeof(ingest_image) + (int64_t)npl * (int64_t)sizeof(ingest_plane) + used;
-        if (blocks) {
-            hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)icl_ceil_div(blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, npl,
-                               (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, ws->d_scratch, (int64_t)SLAB_SCRATCH, blocks);
-            ICL_HIP(ctx, hipGetLastError());
-        }
+        if (F.nscan) // the flags are read after the call's last synchronisation
+            ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted + (stream_rows.size() - (size_t)F.nscan), ws->d_accepted, (size_t)F.nscan * 4, hipMemcpyDeviceToHost, st));
         uint8_t *dst = mode == 0 ? d_u8 + first * ICL_IMG_BYTES : ws->d_img;
         hipLaunchKernelGGL(jpeg_gather_resize_kernel, dim3((unsigned)icl_ceil_div(OUTW * OUTH, 256), (unsigned)nimg), dim3(256), 0, st, d_imgs,
                            (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, dst);
@@ -561,21 +784,76 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
         }
     }
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // ---- report ----
     {
         std::lock_guard<std::mutex> lk(m);
         stop = true;
     }
     cv.notify_all();
     for (auto &t : pool) t.join();
-    ctx->ingest_stats[0] = gpu_jpegs;
-    ctx->ingest_stats[1] = host_files;
-    ctx->ingest_stats[2] = upload;
-    ctx->ingest_decode_s = (double)decode_ns.load() * 1e-9;
-    for (int64_t i = 0; i < n; ++i)
-        if (res[(size_t)i] && res[(size_t)i]->kind == KIND_FAILED)
-            return icl_fail(ctx, res[(size_t)i]->rc ? res[(size_t)i]->rc : ICL_ERR_IO, "%s: file %lld of %lld: %s", what, (long long)i, (long long)n,
-                            res[(size_t)i]->err.c_str());
+    tot.decode_ns += decode_ns.load();
+    for (size_t q = 0; q < stream_rows.size(); ++q) {
+        if (ws->h_accepted[q]) ++tot.gpu_entropy;
+        else rejected.push_back(stream_rows[q]);
+    }
+    return ICL_OK;
+}
+
+// The pipeline: one pass in the context's entropy mode; the images the GPU entropy check rejected are then redone by a pass in
+// ICL_ENTROPY_HOST mode over those files alone (rows do not depend on the batch they are rebuilt or embedded in), which also produces
+// their status codes and messages.
+static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
+                        int32_t *status, const char *what)
+{
+    std::vector<file_fail> fails;
+    std::vector<int64_t> rejected;
+    ingest_totals tot;
+    ICL_TRY(ingest_pass(ctx, paths, n, threads, mode, d_u8, head, prec, out, status, what, ctx->entropy_mode, fails, rejected, tot));
+    const int64_t nrej = (int64_t)rejected.size();
+    if (nrej) {
+        std::vector<const char *> rp((size_t)nrej);
+        for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = paths[rejected[(size_t)q]];
+        std::vector<int32_t> rstatus((size_t)nrej, 0);
+        std::vector<file_fail> rfails;
+        std::vector<int64_t> none;
+        const size_t row_bytes = mode == 0 ? (size_t)ICL_IMG_BYTES : (size_t)head * 4;
+        std::vector<float> h_tmp;
+        struct dev_tmp {
+            void *p = nullptr;
+            ~dev_tmp()
+            {
+                if (p) (void)hipFree(p);
+            }
+        } d_tmp;
+        if (mode == 1) h_tmp.resize((size_t)nrej * head);
+        else if (hipMalloc(&d_tmp.p, (size_t)nrej * row_bytes) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: device buffer of the repair pass", what);
+        ICL_TRY(ingest_pass(ctx, rp.data(), nrej, threads, mode, (uint8_t *)d_tmp.p, head, prec, mode == 1 ? h_tmp.data() : (float *)d_tmp.p, rstatus.data(), what,
+                            ICL_ENTROPY_HOST, rfails, none, tot));
+        for (int64_t q = 0; q < nrej; ++q) {
+            const int64_t row = rejected[(size_t)q];
+            if (status) status[row] = rstatus[(size_t)q];
+            if (mode == 1) memcpy(out + row * head, h_tmp.data() + q * head, row_bytes);
+            else
+                ICL_HIP(ctx, hipMemcpyAsync(mode == 0 ? (void *)(d_u8 + row * ICL_IMG_BYTES) : (void *)(out + row * head), (const uint8_t *)d_tmp.p + (size_t)q * row_bytes,
+                                            row_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (file_fail &f : rfails) fails.push_back(file_fail{rejected[(size_t)f.index], f.rc, f.err});
+        tot.gpu_jpegs -= nrej;     // (the first pass counted them; the repair pass counts what became of them)
+        tot.host_entropy -= nrej;  // they are reported as redone, not as routed to the host
+    }
+    // ---- report ----
+    ctx->ingest_stats[0] = tot.gpu_jpegs;
+    ctx->ingest_stats[1] = tot.host_files;
+    ctx->ingest_stats[2] = tot.upload;
+    ctx->ingest_decode_s = (double)tot.decode_ns * 1e-9;
+    ctx->entropy_stats[0] = tot.gpu_entropy;
+    ctx->entropy_stats[1] = tot.host_entropy;
+    ctx->entropy_stats[2] = nrej;
+    ctx->entropy_stats[3] = tot.stream_bytes;
+    const file_fail *lowest = nullptr;
+    for (const file_fail &f : fails)
+        if (!lowest || f.index < lowest->index) lowest = &f;
+    if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
     return ICL_OK;
 }
 
@@ -588,6 +866,7 @@ extern "C" int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, i
     icl_device_guard g(ctx->device);
     return no_throw(ctx, "icl_load_images_224_dev", [&]() -> int {
         ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
+        ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
         ctx->ingest_decode_s = 0;
         if (n == 0) return ICL_OK;
         return ingest_files(ctx, paths, n, threads, 0, d_out, 0, 0, nullptr, status, "icl_load_images_224_dev");
@@ -608,6 +887,7 @@ static int embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int he
     if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
     return no_throw(ctx, what, [&]() -> int {
         ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
+        ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
         ctx->ingest_decode_s = 0;
         if (n == 0) return ICL_OK;
         return ingest_files(ctx, paths, n, threads, dev ? 2 : 1, nullptr, head, prec, out, status, what);
@@ -633,4 +913,98 @@ extern "C" int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *
     if (upload_bytes) *upload_bytes = ctx->ingest_stats[2];
     if (host_decode_s) *host_decode_s = ctx->ingest_decode_s;
     return ICL_OK;
+}
+
+extern "C" int icl_set_ingest_options(icl_ctx *ctx, int entropy_mode)
+{
+    if (!ctx || (entropy_mode != ICL_ENTROPY_HOST && entropy_mode != ICL_ENTROPY_GPU))
+        return icl_fail(ctx, ICL_ERR_ARG, "icl_set_ingest_options: entropy_mode must be ICL_ENTROPY_HOST or ICL_ENTROPY_GPU");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->entropy_mode = entropy_mode;
+    return ICL_OK;
+}
+
+extern "C" int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, int64_t *host_entropy_jpegs, int64_t *redone_on_host, int64_t *stream_bytes)
+{
+    if (!ctx) return ICL_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (gpu_entropy_jpegs) *gpu_entropy_jpegs = ctx->entropy_stats[0];
+    if (host_entropy_jpegs) *host_entropy_jpegs = ctx->entropy_stats[1];
+    if (redone_on_host) *redone_on_host = ctx->entropy_stats[2];
+    if (stream_bytes) *stream_bytes = ctx->entropy_stats[3];
+    return ICL_OK;
+}
+
+// Test hook: the quantised coefficients of each file as stage A leaves them, by host stage A or by the GPU entropy decoder (one
+// single-image slab per file through the pipeline's own placement and launch code).
+extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap, int64_t *offsets, int32_t *state)
+{
+    if (!ctx || n < 0 || (n && !paths) || !offsets || !state || cap < 0 || (entropy_mode != ICL_ENTROPY_HOST && entropy_mode != ICL_ENTROPY_GPU))
+        return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: bad argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: paths[%lld] is NULL", (long long)i);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return no_throw(ctx, "icl_jpeg_coefs_files", [&]() -> int {
+        icl_ingest_ws *ws = nullptr;
+        if (entropy_mode == ICL_ENTROPY_GPU) {
+            ICL_TRY(ingest_ws(ctx, ws));
+            ICL_TRY(entropy_ws(ctx, ws, 1));
+        }
+        std::unique_ptr<worker_state> wst(new worker_state());
+        int64_t at = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            offsets[i] = at;
+            state[i] = -1;
+            if (entropy_mode == ICL_ENTROPY_HOST) {
+                std::vector<uint8_t> file;
+                if (icl_image_file_read(paths[i], file) != ICL_IMAGE_JPEG) return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: %s is not a readable JPEG", paths[i]);
+                const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), paths[i], wst->J);
+                if (rc) return icl_fail(ctx, rc, "icl_jpeg_coefs_files: %s", icl_last_error(nullptr));
+                state[i] = 1;
+                for (int c = 0; c < wst->J.ncomp; ++c) {
+                    const std::vector<int16_t> &cf = wst->J.comp[c].coefs;
+                    if (coefs) {
+                        if (at + (int64_t)cf.size() > cap) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: buffer too small");
+                        memcpy(coefs + at, cf.data(), cf.size() * 2);
+                    }
+                    at += (int64_t)cf.size();
+                }
+                continue;
+            }
+            file_result r;
+            process_file(paths[i], *wst, ICL_ENTROPY_GPU, r);
+            if (r.kind != KIND_JSTREAM) continue; // does not qualify (or cannot be read at all)
+            int64_t total = 0;
+            for (int c = 0; c < r.ncomp; ++c) total += (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
+            state[i] = 0;
+            if (coefs) {
+                if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: buffer too small");
+                uint8_t *hs = ws->h_slab[0];
+                ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
+                ingest_image *imgs = (ingest_image *)hs;
+                icl_je_scan *scans = (icl_je_scan *)(hs + HDR_SCANS);
+                slab_fill F;
+                memset(&imgs[0], 0, offsetof(ingest_image, xofs));
+                if (!place_jpeg(r, F, imgs[0], (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image)), scans, hs + HDR_BYTES))
+                    return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: inconsistent JPEG geometry for %s", paths[i]);
+                F.nimg = 1;
+                int64_t upload = 0;
+                ICL_TRY(run_slab_decode(ctx, ws, hs, F, upload));
+                ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
+                ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, 4, hipMemcpyDeviceToHost, ctx->stream));
+                ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                state[i] = ws->h_accepted[0] ? 1 : 0;
+                int64_t o = at;
+                for (int c = 0; c < r.ncomp && state[i] == 1; ++c) {
+                    const int64_t ne = (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
+                    ICL_HIP(ctx, hipMemcpy(coefs + o, ws->d_coef + scans[0].coef_off[c], (size_t)ne * 2, hipMemcpyDeviceToHost));
+                    o += ne;
+                }
+            }
+            at += total; // (a rejected file keeps its range; its contents are not written)
+        }
+        offsets[n] = at;
+        return ICL_OK;
+    });
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "icl_common.h"
+#include "jpeg_entropy.h"
 
 #define ICL_JPEG_MAX_PIXELS (64LL << 20)
 
@@ -41,6 +42,40 @@ int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, st
 
 // Stage A then stage B (the host decoder in one call).  orient receives the EXIF orientation (1..8; 1 when absent).
 int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient);
+
+// Stage A0: what a host worker does for a JPEG whose entropy decoder runs on the GPU (jpeg_huff_gpu.hip) -- the marker loop of stage A,
+// stopped at the first scan: frame, tables in force, restart interval and the unstuffed entropy-coded segment, cut at its RSTn markers.
+struct icl_jpeg_a0 {
+    icl_je_scan scan;       // geometry; the placement fields are left to the caller
+    icl_je_table tables[6]; // component c: DC table, AC table
+    std::vector<icl_je_interval> intervals;
+    std::vector<uint8_t> stream; // scan.nsub subsequences of scan.sub_bits bits (every interval zero-padded to whole subsequences)
+};
+// qualifies = false (with ICL_OK or an error code): the file takes the usual route (stage A or the host decoders), which also produces
+// its status and message.  Qualifying: SOF0 / SOF1, one scan with all components in frame order.  On success J holds everything stage A
+// leaves except the coefficients (their arrays are empty).
+int icl_jpeg_stage_a0(const uint8_t *data, size_t len, const char *path, int sub_bits, icl_jpeg_coefs &J, icl_jpeg_a0 &A, bool &qualifies);
+// The GPU decoder's schedule as a plain host loop over subsequences (the same decode step and checks, jpeg_entropy.h): launches x
+// workgroups x rounds, then the chain / cleanliness check, then (accepted images only) the coefficients as stage A leaves them.
+// rounds receives the largest number of rounds a workgroup needed until no entry state changed.
+void icl_je_host_decode(const icl_jpeg_a0 &A, std::vector<int16_t> coefs[3], bool &accepted, int &rounds);
+
+// jpeg_huff_gpu.hip: the decode of one slab's scans on the GPU.  d_scans[nscans] (placement fields filled: offsets into d_payload, sub_first,
+// wg_first ascending, coef_off into d_coef) -> d_accepted[nscans], and the accepted images' coefficients in d_coef (zero-filled by the caller).
+struct icl_je_slab {
+    const icl_je_scan *d_scans;
+    int nscans;
+    const uint8_t *d_payload;
+    int64_t payload_bytes;
+    icl_je_sub *d_sub;
+    int64_t nsub_cap;
+    uint32_t *d_bound; // 2 arrays of 2 * nwg_cap words: the workgroups' last exit states of alternate launches
+    int64_t nwg_cap, total_wgs;
+    int32_t *d_accepted;
+    int16_t *d_coef;
+    int64_t coef_elems;
+};
+int icl_je_decode_slab(icl_ctx *ctx, hipStream_t st, const icl_je_slab &s);
 
 // image_io.hip: the host ingest path.  The batched file path (jpeg_gpu.hip) reads and sniffs files, and decodes what the GPU does not
 // take, through it; the icl_embed_file batcher (resnet.hip) reads and resizes through it.

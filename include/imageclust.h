@@ -129,6 +129,33 @@ int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int h
  * bytes uploaded, host thread-seconds spent in stage A / host decode */
 int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes,
                           double *host_decode_s);
+/* ---- entropy decoding on the GPU (opt-in) ----
+ * ICL_ENTROPY_HOST (default): host workers run stage A (parsing + Huffman decoding) of every JPEG, as described above.
+ * ICL_ENTROPY_GPU: for a sequential Huffman JPEG (SOF0 / SOF1, 8 bit) whose ONE scan carries all components (1, or 3 at 4:4:4 / 4:2:2 /
+ * 4:2:0; with or without restart interval) a host worker only parses the markers and unstuffs the entropy-coded segment; kernels decode
+ * it in fixed-size subsequences and accept the result only when the chain of subsequence states is consistent and the stream is clean,
+ * which makes it the sequential decode.  Every other file, and every image the check rejects (damaged, truncated, odd streams), takes the
+ * ICL_ENTROPY_HOST route; rows, status codes and messages are identical in both modes.  The environment variable ICL_JPEG_ENTROPY=gpu
+ * selects ICL_ENTROPY_GPU when the context is created. */
+enum { ICL_ENTROPY_HOST = 0, ICL_ENTROPY_GPU = 1 };
+int icl_set_ingest_options(icl_ctx *ctx, int entropy_mode);
+/* what the last files call did with its JPEGs: entropy-decoded on the GPU and accepted, entropy-decoded by host stage A because of the
+ * routing rule (progressive, one scan per component, too large, or ICL_ENTROPY_HOST), rejected by the GPU check and redone by the host
+ * route, bytes of unstuffed stream uploaded */
+int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, int64_t *host_entropy_jpegs, int64_t *redone_on_host,
+                           int64_t *stream_bytes);
+/* Test hooks: the quantised coefficients as stage A leaves them (per component 0, 1, 2: wblocks x hblocks blocks of 64 int16 in natural
+ * order, not dequantised).  state[i] / info[0]: 1 = decoded and accepted, 0 = rejected by the chain / cleanliness check (no
+ * coefficients), -1 = the file does not qualify for the GPU decoder (no coefficients; never with ICL_ENTROPY_HOST).
+ * icl_jpeg_coefs_files: file i's coefficients go to coefs[offsets[i] .. offsets[i + 1]) (host memory, cap elements); entropy_mode
+ * chooses host stage A or the GPU decoder.  With coefs == NULL only offsets[0..n] are computed (and with ICL_ENTROPY_GPU nothing is
+ * decoded: state is 0 for every qualifying file).  A rejected file keeps its range, unwritten.  A file stage A cannot read fails the call.
+ * icl_jpeg_coefs_file_host: no GPU.  sub_bits == 0: host stage A; otherwise stage A0 and the GPU decoder's schedule as a host loop over
+ * subsequences of sub_bits bits (a multiple of 32).  *need receives the element count; coefs may be NULL.  info[8]: state, components,
+ * blocks of component 0, 1, 2, rounds the slowest workgroup needed, subsequences, restart intervals. */
+int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
+                         int64_t *offsets /* n + 1 */, int32_t *state /* n */);
+int icl_jpeg_coefs_file_host(const char *path, int sub_bits, int16_t *coefs, int64_t cap, int64_t *need, int32_t *info /* 8 */);
 int icl_set_batch(icl_ctx *ctx, int batch); /* embed batch size, 1..1024 */
 /* Which bf16 convolution launches take the deep-pipelined 256 x 256 x 64 kernel (conv_p8_kernel: LDS-DMA kept in flight across raw
  * barriers, counted vmcnt, staggered wave groups) instead of the 128 x 128 two-stage kernels: ICL_CONV_P8_OFF never, ICL_CONV_P8_AUTO

@@ -92,6 +92,9 @@ def rate_embed_files(ctx, paths):
     assert (status == 0).all()
     st = ctx.last_ingest_stats()
     assert st["gpu_jpegs"] == len(paths), st
+    if ENTROPY["mode"] != "host":  # the GPU decoder must have taken (and accepted) every file when it is on
+        es = ctx.last_entropy_stats()
+        assert es["gpu_entropy_jpegs"] in (0, len(paths)) and es["redone_on_host"] == 0, es
     return len(paths) / dt, st
 
 
@@ -102,9 +105,42 @@ def rate_embed_u8(ctx, imgs):
     return imgs.shape[0] / (time.perf_counter() - t0)
 
 
-def corpus_rates(ctx, name, paths, mean_bytes, trace_only):
+ENTROPY = {"mode": "host", "reps": 3}
+
+
+def images_per_slab(w, h, payload_bytes_per_file):
+    """The slab builder's limits (jpeg_gpu.hip) for 4:2:0 files of one size: 256 rows, 128 MiB of payload, 768 MiB of u8 planes."""
+    mx, my = -(-w // 16), -(-h // 16)
+    planes = mx * 16 * my * 16 + 2 * (mx * 8 * my * 8)
+    return int(min(256, (128 << 20) // max(1, payload_bytes_per_file), (768 << 20) // planes))
+
+
+def entropy_ab(ctx, paths, w, h):
+    """host and gpu entropy modes alternating on the same files: files/s per mode and repetition, host ms per file (stage A / A0),
+    bytes uploaded and stream bytes per file.  The yardstick is the host mode of the same run."""
+    out = {"host": [], "gpu": []}
+    for mode, flag in (("host", _lib.ENTROPY_HOST), ("gpu", _lib.ENTROPY_GPU)):  # warm-up of both modes
+        ctx.set_ingest_options(flag)
+        ctx.embed_files(paths[:64], HEAD, PREC, THREADS)
+    for _ in range(ENTROPY["reps"]):
+        for mode, flag in (("host", _lib.ENTROPY_HOST), ("gpu", _lib.ENTROPY_GPU)):
+            ctx.set_ingest_options(flag)
+            r, st = rate_embed_files(ctx, paths)
+            es = ctx.last_entropy_stats()
+            out[mode].append({"files_per_s": round(r, 1), "host_ms_per_file": round(st["host_decode_s"] / len(paths) * 1e3, 3),
+                              "upload_bytes_per_file": round(st["upload_bytes"] / len(paths)), "stream_bytes_per_file": round(es["stream_bytes"] / len(paths)),
+                              "gpu_entropy_jpegs": es["gpu_entropy_jpegs"], "redone_on_host": es["redone_on_host"],
+                              "images_per_slab": images_per_slab(w, h, round(st["upload_bytes"] / len(paths)))})
+    ctx.set_ingest_options(_lib.ENTROPY_HOST)
+    return out
+
+
+def corpus_rates(ctx, name, paths, mean_bytes, trace_only, w=0, h=0):
     warm(paths)
     out = {"files": len(paths), "mean_jpeg_bytes": round(mean_bytes)}
+    if ENTROPY["mode"] == "both":
+        out["entropy_ab"] = entropy_ab(ctx, paths, w, h)
+        return out
     ctx.embed_files(paths[:64], HEAD, PREC, THREADS)  # warm-up: code objects, pinned slabs, workspace
     if trace_only:
         r, st = rate_embed_files(ctx, paths)
@@ -133,9 +169,15 @@ def main():
     ap.add_argument("--n12mp", type=int, default=512)
     ap.add_argument("--trace-only", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--entropy", choices=["host", "gpu", "both"], default="host",
+                    help="where the JPEG Huffman decoder runs; both: the two modes alternate on the same files (--reps times each)")
+    ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     ctx = _lib.Context(0)
     ctx.load_synthetic(1)
+    ENTROPY["mode"], ENTROPY["reps"] = args.entropy, args.reps
+    if args.entropy == "gpu":
+        ctx.set_ingest_options(_lib.ENTROPY_GPU)
     res = {"head": HEAD, "prec": "bf16", "threads": THREADS}
     tmp = tempfile.mkdtemp(prefix="icl_files_rate_")
     try:
@@ -145,7 +187,7 @@ def main():
             d = os.path.join(tmp, name)
             os.makedirs(d)
             paths, mean_bytes = make_corpus(d, n, w, h, seed)
-            res[name] = corpus_rates(ctx, name, paths, mean_bytes, args.trace_only)
+            res[name] = corpus_rates(ctx, name, paths, mean_bytes, args.trace_only, w, h)
             shutil.rmtree(d, ignore_errors=True)
             print(name, json.dumps(res[name]), flush=True)
     finally:
