@@ -77,3 +77,35 @@ func LastError() string {
 	}
 	return C.GoString(C.icl_last_error(ctx))
 }
+
+// Mid-size route of icl_cluster_many (problems of 257 to 2048 rows, one workgroup each): icl_set_many_options' modes.
+const (
+	ManyMidAuto = int(C.ICL_MANY_MID_AUTO)
+	ManyMidOff  = int(C.ICL_MANY_MID_OFF)
+	ManyMidOn   = int(C.ICL_MANY_MID_ON)
+)
+
+// SetManyOptions chooses when PerformClusteringWithConstraintsBatch's mid-size problems take that route (same results in every mode).
+func SetManyOptions(midMode int) error {
+	raw, e := Ctx()
+	if e != nil {
+		return e
+	}
+	if rc := C.icl_set_many_options((*C.icl_ctx)(raw), C.int(midMode)); rc != C.ICL_OK {
+		return fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return nil
+}
+
+// LastManyStats reports the problems of the last icl_cluster_many call by route, and the groups its mid-size problems ran in.
+func LastManyStats() (small, mid, large, midGroups int64, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return 0, 0, 0, 0, e
+	}
+	var a, b, c, d C.int64_t
+	if rc := C.icl_last_many_stats((*C.icl_ctx)(raw), &a, &b, &c, &d); rc != C.ICL_OK {
+		return 0, 0, 0, 0, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return int64(a), int64(b), int64(c), int64(d), nil
+}

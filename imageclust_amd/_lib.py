@@ -23,6 +23,7 @@ CONV_P8_OFF, CONV_P8_AUTO, CONV_P8_ALL = 0, 1, 2
 CONV_SPLIT = 16
 ROWS_SINGLE, ROWS_EXACT_BATCH, ROWS_LW_BOUND, ROWS_LW_FAST = 0, 1, 2, 3
 FILE_FAIL_NEXT_LEADER = 0x100
+MANY_MID_AUTO, MANY_MID_OFF, MANY_MID_ON = 0, 1, 2  # icl_set_many_options: the mid-size route (257 to 2048 rows) of icl_cluster_many
 ENTROPY_HOST, ENTROPY_GPU = 0, 1  # icl_set_ingest_options: where the Huffman decoder of a qualifying baseline JPEG runs
 K_CONV, K_DIST_EXACT, K_DIST_MFMA, K_ROWMIN, K_UPDATE, K_EMBED_OTHER, K_CONV64 = range(7)
 K_NAMES = ["conv_igemm_kernel<*,128>", "ward_dist_exact_kernel", "dist_mfma_kernel", "row_argmin_*_kernel",
@@ -107,6 +108,8 @@ SYMBOLS = [
     ("icl_cluster_dev", _int, [_vp, _vp, _i64, _i32, _i32, _i32, _int, _vp, _vp, _pi32]),
     ("icl_cluster_many", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
+    ("icl_set_many_options", _int, [_vp, _int]),
+    ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_last_merges", _i64, [_vp, _vp, _i64]),
     ("icl_last_merge_values", _i64, [_vp, _vp, _i64]),
     ("icl_distance_mfma_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i64]),
@@ -541,6 +544,17 @@ class Context:
         if rc != ICL_OK and (raise_on_error or (st[:nprob] < 0).any()):
             check(self.h, rc)  # an argument or device error: no per-problem results
         return _unpack_many(pk, cid, rank, nc, nm, st, mg)
+
+    def set_many_options(self, mid_mode=MANY_MID_AUTO):
+        """icl_set_many_options: whether cluster_many runs problems of 257 to 2048 rows one workgroup each (MANY_MID_ON), never
+        (MANY_MID_OFF), or when the call holds enough of them for that to win (MANY_MID_AUTO).  Same results in every mode."""
+        check(self.h, self.L.icl_set_many_options(self.h, mid_mode))
+
+    def last_many_stats(self):
+        """Problems of the last cluster_many[_dev] call by route, and the number of groups its mid-size problems ran in."""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.h, self.L.icl_last_many_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"small": a.value, "mid": b.value, "large": c.value, "mid_groups": d.value}
 
     def cluster_many_dev(self, d_E, e_len, e_off, n, d, min_size, max_size, want_merges=False):
         """icl_cluster_many_dev on a device buffer of e_len floats; per-problem arrays as pack_many() gives them.  Same result as cluster_many()."""

@@ -115,6 +115,8 @@ struct icl_ctx {
     int64_t ward_rowoff_n = 0;
     void *file_batcher = nullptr; // icl_embed_file's coalescing queue (resnet.hip)
     icl_many_ws *many = nullptr; // workspace of icl_cluster_many (ward_many.hip; created on first use)
+    int many_mid = 0;                 // icl_set_many_options: ICL_MANY_MID_AUTO / _OFF / _ON (environment: ICL_MANY_MID=auto|off|on)
+    int64_t many_stats[4] = {0, 0, 0, 0}; // last icl_cluster_many[_dev]: problems on the small, mid and large-N routes, mid-route groups
     icl_ingest_ws *ingest = nullptr; // buffers of the batched file path (jpeg_gpu.hip; created on first use)
     int64_t ingest_stats[3] = {0, 0, 0}; // last batched file call: JPEGs rebuilt on the GPU, files decoded on the host, bytes uploaded
     double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode

@@ -305,6 +305,17 @@ int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len,
 int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *n, const int32_t *d,
                          const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters,
                          int32_t *n_merges, int32_t *merges, int32_t *status);
+/* Problems of 257 to 2048 rows (above the small route's cap) can also run one workgroup each, in groups whose workspace stays under a
+ * budget (the mid-size route of ward_many.hip; the same results, bit for bit).  ICL_MANY_MID_AUTO (default) takes that route when the
+ * call holds enough such problems for it to beat the large-N engine (measured crossover counts), ICL_MANY_MID_OFF never, ICL_MANY_MID_ON
+ * always, a lone problem included.  The environment variable ICL_MANY_MID=auto|off|on sets the default of new contexts;
+ * ICL_MANY_MID_WS_MB overrides the group budget (read once per process).  Returns ICL_ERR_ARG for a null context or an unknown mode. */
+#define ICL_MANY_MID_AUTO 0
+#define ICL_MANY_MID_OFF 1
+#define ICL_MANY_MID_ON 2
+int icl_set_many_options(icl_ctx *ctx, int mid_mode);
+/* problems of the last icl_cluster_many[_dev] call by route, and the number of mid-route groups it was run in (any pointer may be NULL) */
+int icl_last_many_stats(icl_ctx *ctx, int64_t *small, int64_t *mid, int64_t *large, int64_t *mid_groups);
 /* workflow.go:84-94 on one GPU in one call: embed n resident images (2048-d pooled head, into d_E: device, n x 2048) and
  * cluster them.  flags & ICL_FUSE_OVERLAP: the distance rows of already-embedded images are computed on a side stream of the
  * context while later batches embed (same kernels, same results as icl_embed_u8_dev + icl_cluster_dev, bit for bit). */

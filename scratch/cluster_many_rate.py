@@ -9,8 +9,15 @@ appended 0/1 label columns (one-hot), min 3 / max 6, exact mode.
 Every call returns after the stream is idle (the library synchronises before it hands back results).  Warm-up calls first; spreads
 are over repeats.  Prints and writes one JSON object.
 
+--n-lo / --n-hi change the range of n and --mid the context's mid-size route (icl_set_many_options); the defaults are the run above.
+--mid-table measures the mid-size route (problems of 257 to 2048 rows, one workgroup each) against the large-N engine instead: per
+band of n and batch size, ICL_MANY_MID_OFF and ICL_MANY_MID_ON alternate in one process on the same problems (one untimed call of
+each first), E from host memory and E on the device; the rates, their spreads and what ICL_MANY_MID_AUTO chose go to the JSON.
+
     python scratch/cluster_many_rate.py --out OUT.json
     python scratch/cluster_many_rate.py --trace-only        # (a) once, e.g. under rocprofv3 --kernel-trace --stats
+    python scratch/cluster_many_rate.py --mid-table --out OUT.json
+    python scratch/cluster_many_rate.py --trace-only --mid on --problems 256 --n-lo 513 --n-hi 1024
 """
 import argparse
 import json
@@ -83,6 +90,58 @@ def threads_cluster(ctx, probs):
         t.join()
 
 
+MID_MODES = {"auto": _lib.MANY_MID_AUTO, "off": _lib.MANY_MID_OFF, "on": _lib.MANY_MID_ON}
+BANDS = [(257, 512, (1, 2, 4, 8, 16, 64, 256, 1024)), (513, 1024, (1, 2, 4, 8, 16, 64, 256)), (1025, 2048, (1, 2, 4, 8, 16, 64, 256))]
+
+
+def mid_table(ctx, reps, bands, out_path):
+    """OFF against ON per (band, batch size): alternating in one process on the same problems, the context warmed by one untimed call of
+    each mode.  A rate's spread is (max - min) / 2 over its repetitions."""
+    cells = []
+
+    def rate(xs, count):
+        r = np.asarray([count / t for t in xs])
+        return dict(median=float(np.median(r)), min=float(r.min()), max=float(r.max()), spread=float((r.max() - r.min()) / 2), reps=int(r.size))
+
+    for lo, hi, sizes in bands:
+        probs_all = problems(max(sizes), 20261016 + lo, lo, hi)
+        for bs in sizes:
+            probs = probs_all[:bs]
+            pk = _lib.pack_many(probs)
+            dE = ctx.malloc(pk["E"].nbytes)
+            ctx.h2d(dE, pk["E"])
+            host = lambda: ctx.cluster_many(probs)
+            dev = lambda: ctx.cluster_many_dev(dE, pk["E"].size, pk["e_off"], pk["n"], pk["d"], pk["min_size"], pk["max_size"])
+            t = {("off", "host"): [], ("on", "host"): [], ("off", "dev"): [], ("on", "dev"): []}
+            for mode in ("off", "on"):  # untimed: workspace, code objects
+                ctx.set_many_options(MID_MODES[mode])
+                host()
+                dev()
+            for _ in range(reps):
+                for mode in ("off", "on"):
+                    ctx.set_many_options(MID_MODES[mode])
+                    t[(mode, "host")] += timed(host, 1)
+                    t[(mode, "dev")] += timed(dev, 1)
+            ctx.set_many_options(MID_MODES["auto"])
+            host()
+            auto = ctx.last_many_stats()
+            ctx.free(dE)
+            cell = dict(band=[lo, hi], batch=bs, mean_n=float(np.mean([p[0].shape[0] for p in probs])),
+                        auto_took_mid=auto["mid"] > 0, auto_stats=auto)
+            for (mode, where), xs in t.items():
+                cell["%s_%s_problems_per_s" % (mode, where)] = rate(xs, bs)
+            for where in ("host", "dev"):
+                a, b = cell["off_%s_problems_per_s" % where], cell["on_%s_problems_per_s" % where]
+                margin = a["spread"] + b["spread"]
+                cell["%s_winner" % where] = "on" if b["median"] - a["median"] > margin else "off" if a["median"] - b["median"] > margin else "within spreads"
+            cells.append(cell)
+            print(json.dumps(cell), flush=True)
+            if out_path:  # (kept up to date: a long run that is cut short leaves its finished cells)
+                with open(out_path, "w") as f:
+                    f.write(json.dumps(dict(device="MI355X (1 GCD)", d="1000 + L, L in [0, 200] one-hot label columns", min_size=3, max_size=6,
+                                            reps=reps, cells=cells), indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--problems", type=int, default=4096)
@@ -90,12 +149,27 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace-only", action="store_true")
     ap.add_argument("--out")
+    ap.add_argument("--n-lo", type=int, default=8)
+    ap.add_argument("--n-hi", type=int, default=256)
+    ap.add_argument("--mid", choices=sorted(MID_MODES), default="auto", help="the mid-size route of the context (icl_set_many_options)")
+    ap.add_argument("--mid-table", action="store_true")
+    ap.add_argument("--bands", default="0,1,2", help="--mid-table: which of the bands [257, 512], [513, 1024], [1025, 2048]")
+    ap.add_argument("--batches", help="--mid-table: these batch sizes (comma-separated) instead of the standard ones")
     a = ap.parse_args()
-    probs = problems(a.problems, 20261016)
     ctx = _lib.Context(0)
+    if a.mid_table:
+        bands = [BANDS[int(b)] for b in a.bands.split(",")]
+        if a.batches:
+            bands = [(lo, hi, tuple(int(x) for x in a.batches.split(","))) for lo, hi, _ in bands]
+        mid_table(ctx, max(a.reps, 3), bands, a.out)
+        ctx.close()
+        return
+    probs = problems(a.problems, 20261016, a.n_lo, a.n_hi)
+    ctx.set_many_options(MID_MODES[a.mid])
     if a.trace_only:
         ctx.cluster_many(probs[:64])
         ctx.cluster_many(probs)
+        print(json.dumps(ctx.last_many_stats()))
         ctx.close()
         return
     res = ctx.cluster_many(probs)  # warm-up (workspace, code objects)
@@ -131,7 +205,7 @@ def main():
     ctx.close()
     nb = len(base)
     out = dict(
-        device="MI355X (1 GCD)", problems=a.problems, baseline_problems=nb, n_range=[8, 256], d="1000 + L, L in [0, 200] one-hot label columns",
+        device="MI355X (1 GCD)", problems=a.problems, baseline_problems=nb, n_range=[a.n_lo, a.n_hi], mid=a.mid, d="1000 + L, L in [0, 200] one-hot label columns",
         min_size=3, max_size=6, mean_n=float(np.mean([p[0].shape[0] for p in probs])), mean_d=float(np.mean([p[0].shape[1] for p in probs])),
         a_cluster_many_problems_per_s=stats([a.problems / t for t in ta]),
         a_dev_cluster_many_problems_per_s=stats([a.problems / t for t in tad]),
