@@ -73,6 +73,18 @@ struct icl_sk_slot { // scratch of the split convolution launches of one stream 
     int cap = 0, epoch = 0;
 };
 
+// Everything the last icl_cluster reports about its merge loop (cluster_locked, ward.hip, writes it; the icl_last_* entry points read
+// it).  One value, so that a call which must leave the reports alone (icl_cluster_many) saves and restores all of them.
+struct icl_ward_report {
+    std::vector<int32_t> merges;   // pairs (icl_last_merges)
+    std::vector<float> merge_vals; // Ward distance of each merged pair (icl_last_merge_values)
+    int64_t bound_viol = 0;        // icl_last_ward_bound_violations
+    int32_t mode[2] = {0, 0};      // icl_last_ward_mode: which update kernel the merge loop ran (ICL_ROWS_*), whether the initial matrix held bounds
+    int64_t layout[3] = {0, 0, 0}; // complete rows (columns by creation id)?, row pitch in floats, int8 bounds? (icl_last_ward_layout)
+    int64_t stats[4] = {0, 0, 0, 0}; // merges, steps, single-pick steps, sum of live clusters over steps (icl_last_ward_stats)
+    double dist_ms = 0, merge_ms = 0; // icl_last_timings
+};
+
 struct icl_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -100,12 +112,9 @@ struct icl_ctx {
     icl_prof_slot prof[ICL_K_NCLASS];
     std::vector<icl_pending_event> pending;
     std::vector<hipEvent_t> event_pool;
-    double last_embed_ms = 0, last_dist_ms = 0, last_merge_ms = 0;
-    int64_t ward_bound_viol = 0; // icl_last_ward_bound_violations
-    int32_t ward_mode[2] = {0, 0}; // icl_last_ward_mode: which update kernel the last merge loop ran (ICL_ROWS_*), whether the initial matrix held bounds
+    double last_embed_ms = 0;
+    icl_ward_report last; // of the last icl_cluster
     int64_t ward_wide_fail_n = 0; // smallest n at which the 8 n^2-byte matrix could not be allocated on this device (0: never failed)
-    int64_t ward_layout[3] = {0, 0, 0}; // last merge loop: complete rows (columns by creation id)?, row pitch in floats, int8 bounds? (icl_last_ward_layout)
-    int64_t ward_stats[4] = {0, 0, 0, 0}; // merges, steps, single-pick steps, sum of live clusters over steps
     // subsystems
     icl_model *model = nullptr;
     icl_ward_ws *ward = nullptr;
@@ -123,8 +132,6 @@ struct icl_ctx {
     int entropy_mode = 0;                 // icl_set_ingest_options: ICL_ENTROPY_HOST / ICL_ENTROPY_GPU (environment: ICL_JPEG_ENTROPY=gpu)
     int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
-    std::vector<int32_t> last_merges; // pairs
-    std::vector<float> last_merge_vals; // Ward distance of each merged pair
 };
 
 int icl_fail(icl_ctx *ctx, int code, const char *fmt, ...);

@@ -282,8 +282,8 @@ extern "C" int icl_last_stage_ms(icl_ctx *ctx, double *embed_ms, double *dist_ms
 {
     if (!ctx) return ICL_ERR_ARG;
     if (embed_ms) *embed_ms = ctx->last_embed_ms;
-    if (dist_ms) *dist_ms = ctx->last_dist_ms;
-    if (merge_ms) *merge_ms = ctx->last_merge_ms;
+    if (dist_ms) *dist_ms = ctx->last.dist_ms;
+    if (merge_ms) *merge_ms = ctx->last.merge_ms;
     return ICL_OK;
 }
 

@@ -5080,7 +5080,7 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
     if (update != ICL_UPDATE_EXACT && update != ICL_UPDATE_LW) return icl_fail(ctx, ICL_ERR_ARG, "unknown update mode %d", update);
     const bool lw = update == ICL_UPDATE_LW;
     if (n >= (1LL << 30)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "n too large");
-    ctx->last_merges.clear();
+    ctx->last.merges.clear();
     *n_clusters = 0;
     const int64_t T = n - k; // merges needed for len(clusters) == k (clustering.go:220)
     if (n == 0) return ICL_OK;
@@ -5503,48 +5503,48 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
                 hst.B.dbg[0] * 0.01 / hst.B.steps, hst.B.dbg[7] * 0.01 / hst.B.steps, (double)hst.B.dbg[6] / hst.B.steps, hst.B.dbg[1] * 0.01 / hst.B.steps, hst.B.dbg[2] * 0.01 / hst.B.steps,
                 hst.B.dbg[3] * 0.01 / hst.B.steps, hst.B.dbg2[0] * 0.01 / hst.B.steps, hst.B.dbg[4] * 0.01 / hst.B.steps, hst.B.dbg[5] * 0.01 / hst.B.steps);
 #endif
-    ctx->ward_bound_viol = (int64_t)hst.bound_viol;
-    ctx->ward_mode[0] = !batched ? ICL_ROWS_SINGLE : lw ? ICL_ROWS_LW_FAST : lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH; // what the loop just run WAS (icl_last_ward_mode)
-    ctx->ward_mode[1] = use_bound ? 1 : 0;
-    ctx->ward_layout[0] = rf.wide;
-    ctx->ward_layout[1] = w->ld;
-    ctx->ward_layout[2] = rf.ex ? 1 : 0;
-    ctx->ward_stats[0] = nmerge;
+    ctx->last.bound_viol = (int64_t)hst.bound_viol;
+    ctx->last.mode[0] = !batched ? ICL_ROWS_SINGLE : lw ? ICL_ROWS_LW_FAST : lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH; // what the loop just run WAS (icl_last_ward_mode)
+    ctx->last.mode[1] = use_bound ? 1 : 0;
+    ctx->last.layout[0] = rf.wide;
+    ctx->last.layout[1] = w->ld;
+    ctx->last.layout[2] = rf.ex ? 1 : 0;
+    ctx->last.stats[0] = nmerge;
     if (batched) {
         // steps = launches that carried work: the first finish picks without committing, every later one commits >= 1
-        ctx->ward_stats[1] = hst.B.steps;
-        ctx->ward_stats[2] = hst.B.slow;
-        ctx->ward_stats[3] = (int64_t)hst.B.sum_live;
+        ctx->last.stats[1] = hst.B.steps;
+        ctx->last.stats[2] = hst.B.slow;
+        ctx->last.stats[3] = (int64_t)hst.B.sum_live;
         if (prof_update) { // algorithmic work of the launches just profiled (n_live is only known on the device)
             ctx->prof[ICL_K_UPDATE].flops += (lw ? 8.0 : lbm ? 16.0 : 3.0 * d) * (double)hst.B.sum_live_nb;
             ctx->prof[ICL_K_UPDATE].bytes += (lw || lbm) ? (rf.wide ? 16.0 : 12.0) * (double)hst.B.sum_live_nb : // (complete rows: the entry is written twice)
                                               4.0 * d * (double)hst.B.sum_live + 4.0 * (double)hst.B.sum_live_nb;
         }
     } else {
-        ctx->ward_stats[1] = nmerge;
-        ctx->ward_stats[2] = nmerge;
-        ctx->ward_stats[3] = (int64_t)nmerge * n - (int64_t)nmerge * (nmerge + 1) / 2;
+        ctx->last.stats[1] = nmerge;
+        ctx->last.stats[2] = nmerge;
+        ctx->last.stats[3] = (int64_t)nmerge * n - (int64_t)nmerge * (nmerge + 1) / 2;
     }
     std::vector<int32_t> pairs((size_t)(2 * nmerge)), trip((size_t)(3 * nmerge));
-    ctx->last_merge_vals.assign((size_t)nmerge, 0.0f);
+    ctx->last.merge_vals.assign((size_t)nmerge, 0.0f);
     if (nmerge) {
         ICL_HIP(ctx, hipMemcpyAsync(trip.data(), w->merges, (size_t)(3 * nmerge) * 4, hipMemcpyDeviceToHost, ctx->stream));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int64_t q = 0; q < nmerge; ++q) {
             pairs[(size_t)(2 * q)] = trip[(size_t)(3 * q)];
             pairs[(size_t)(2 * q + 1)] = trip[(size_t)(3 * q + 1)];
-            memcpy(&ctx->last_merge_vals[(size_t)q], &trip[(size_t)(3 * q + 2)], 4);
+            memcpy(&ctx->last.merge_vals[(size_t)q], &trip[(size_t)(3 * q + 2)], 4);
         }
     }
     float ms01 = 0, ms12 = 0;
     (void)hipEventElapsedTime(&ms01, e0, e1);
     (void)hipEventElapsedTime(&ms12, e1, e2);
-    ctx->last_dist_ms = ms01;
-    ctx->last_merge_ms = ms12;
+    ctx->last.dist_ms = ms01;
+    ctx->last.merge_ms = ms12;
     icl_prof_collect(ctx);
     shg.ok = true; // the merge loop is over: nobody waits for this replica any more
     int rc = icl_ward_assign_ids(ctx, n, min_size, max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
-    ctx->last_merges.swap(pairs);
+    ctx->last.merges.swap(pairs);
     return rc;
 }
 
@@ -5700,7 +5700,7 @@ int icl_ward_cluster_exact(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d,
                            int32_t *member_rank, int32_t *n_clusters, std::vector<int32_t> *merges)
 {
     const int rc = cluster_locked(ctx, d_E, n, d, min_size, max_size, ICL_UPDATE_EXACT, cluster_id, member_rank, n_clusters);
-    merges->assign(ctx->last_merges.begin(), ctx->last_merges.end());
+    merges->assign(ctx->last.merges.begin(), ctx->last.merges.end());
     return rc;
 }
 
@@ -6012,38 +6012,38 @@ extern "C" int64_t icl_last_merge_values(icl_ctx *ctx, float *vals, int64_t cap)
 {
     if (!ctx) return -1;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const int64_t nm = (int64_t)ctx->last_merge_vals.size();
+    const int64_t nm = (int64_t)ctx->last.merge_vals.size();
     if (vals)
-        for (int64_t t = 0; t < nm && t < cap; ++t) vals[t] = ctx->last_merge_vals[(size_t)t];
+        for (int64_t t = 0; t < nm && t < cap; ++t) vals[t] = ctx->last.merge_vals[(size_t)t];
     return nm;
 }
 
 extern "C" int icl_last_ward_stats(icl_ctx *ctx, int64_t *merges, int64_t *steps, int64_t *single_pick_steps, int64_t *sum_live)
 {
     if (!ctx) return ICL_ERR_ARG;
-    if (merges) *merges = ctx->ward_stats[0];
-    if (steps) *steps = ctx->ward_stats[1];
-    if (single_pick_steps) *single_pick_steps = ctx->ward_stats[2];
-    if (sum_live) *sum_live = ctx->ward_stats[3];
+    if (merges) *merges = ctx->last.stats[0];
+    if (steps) *steps = ctx->last.stats[1];
+    if (single_pick_steps) *single_pick_steps = ctx->last.stats[2];
+    if (sum_live) *sum_live = ctx->last.stats[3];
     return ICL_OK;
 }
 
-extern "C" int64_t icl_last_ward_bound_violations(icl_ctx *ctx) { return ctx ? ctx->ward_bound_viol : -1; }
+extern "C" int64_t icl_last_ward_bound_violations(icl_ctx *ctx) { return ctx ? ctx->last.bound_viol : -1; }
 
 extern "C" int icl_last_ward_layout(icl_ctx *ctx, int32_t *complete_rows, int64_t *row_pitch, int32_t *int8_bounds)
 {
     if (!ctx) return ICL_ERR_ARG;
-    if (complete_rows) *complete_rows = ctx->ward_layout[0] ? 1 : 0;
-    if (row_pitch) *row_pitch = ctx->ward_layout[1];
-    if (int8_bounds) *int8_bounds = ctx->ward_layout[2] ? 1 : 0;
+    if (complete_rows) *complete_rows = ctx->last.layout[0] ? 1 : 0;
+    if (row_pitch) *row_pitch = ctx->last.layout[1];
+    if (int8_bounds) *int8_bounds = ctx->last.layout[2] ? 1 : 0;
     return ICL_OK;
 }
 
 extern "C" int icl_last_ward_mode(icl_ctx *ctx, int32_t *row_mode, int32_t *init_bounds)
 {
     if (!ctx) return ICL_ERR_ARG;
-    if (row_mode) *row_mode = ctx->ward_mode[0];
-    if (init_bounds) *init_bounds = ctx->ward_mode[1];
+    if (row_mode) *row_mode = ctx->last.mode[0];
+    if (init_bounds) *init_bounds = ctx->last.mode[1];
     return ICL_OK;
 }
 
@@ -6051,11 +6051,11 @@ extern "C" int64_t icl_last_merges(icl_ctx *ctx, int32_t *pairs, int64_t cap_pai
 {
     if (!ctx) return -1;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const int64_t nm = (int64_t)ctx->last_merges.size() / 2;
+    const int64_t nm = (int64_t)ctx->last.merges.size() / 2;
     if (pairs)
         for (int64_t t = 0; t < std::min(nm, cap_pairs); ++t) {
-            pairs[2 * t] = ctx->last_merges[(size_t)(2 * t)];
-            pairs[2 * t + 1] = ctx->last_merges[(size_t)(2 * t + 1)];
+            pairs[2 * t] = ctx->last.merges[(size_t)(2 * t)];
+            pairs[2 * t + 1] = ctx->last.merges[(size_t)(2 * t + 1)];
         }
     return nm;
 }

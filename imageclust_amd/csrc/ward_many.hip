@@ -2,20 +2,23 @@
 // icl_cluster_many / icl_cluster_many_dev (include/imageclust.h).  The serving pattern of the reference: every request clusters its
 // own few hundred images (d = 1000 + labels), so a loaded server holds many small problems at once.  DESIGN.md "Many small problems".
 //
-//   * ward_many_init_kernel: one launch over (problem, 256-pair tile) writes every problem's exact lower triangle
-//     (ComputeInitialDistanceMatrix, clustering.go:61-73) into one workspace, one thread per pair.
-//   * ward_many_merge_kernel: ONE WORKGROUP PER PROBLEM, largest problems first.  The workgroup keeps its triangle in LDS when it
-//     fits (n <= 281 with the per-slot arrays, WM_LDS_MAX; the launch's dynamic LDS is that of the largest such problem of the batch),
-//     else in the global workspace, plus a per-row (min, argmin) cache, the sizes and the creation ids.  Each step selects the
-//     lexicographic minimum of (value, larger creation id, smaller creation id) over the live, size-compatible pairs -- the
-//     reference's first strict minimum in row-major order with its MaxFloat32 ban (ward.hip's header) -- forms the
-//     merged centroid (clustering.go:37-40) and the new cluster's row exactly (:76-96), and rescans a row only when its cached
-//     partner died.  Workgroups share nothing and never wait for each other: no flags, no spins, so the launch is correct
-//     whatever the number of workgroups resident at a time.
-//   * ward_many_mid_init_kernel / ward_many_mid_merge_kernel: the mid-size route, cap < n <= WMM_CAP rows, again one workgroup per
-//     problem with nothing shared between workgroups (see there); the host runs these problems in groups under a workspace budget.
-//   * Problems above WMM_CAP rows, a lone small problem, and mid-size problems the policy leaves there (icl_set_many_options) go
-//     through ward.hip's large-N engine (icl_ward_cluster_exact) inside the same call, one at a time.
+// Device.  Two routes, each an init kernel and a merge kernel with ONE WORKGROUP PER PROBLEM in the merge, largest problems first;
+// workgroups share nothing and never wait for each other (no flags, no spins), so a launch is correct whatever the number of
+// workgroups resident at a time.
+//   * What both merge kernels share is said once: wm_slots (the per-slot LDS arrays: a per-row (min, argmin) cache, sizes, creation
+//     ids; wm_slots_bytes, wm_carve), wm_block_min<WAVES>, and the first half of a step -- wm_select_pair: the lexicographic minimum of
+//     (value, larger creation id, smaller creation id) over the live, size-compatible pairs, the reference's first strict minimum in
+//     row-major order with its MaxFloat32 ban (ward.hip's header); wm_merge_pair: the log entry, the merged centroid
+//     (clustering.go:37-40), sizes, ids, keys.
+//   * What differs stays apart.  Small route (n <= cap): ward_many_init_kernel writes every problem's exact lower triangle
+//     (ComputeInitialDistanceMatrix, clustering.go:61-73), one thread per pair; ward_many_merge_kernel keeps the triangle in LDS when it
+//     fits (n <= 281, WM_LDS_MAX), forms the new cluster's row exactly (:76-96), one row per thread, and a thread rescans a row whose
+//     cached partner died.  Mid route (cap < n <= WMM_CAP): see "the mid-size route" below.
+// Host.  cluster_many_locked runs the stages wm_classify (k, status, wm_route of every problem), wm_make_plan (launch groups --
+// wm_group: the small route is one, the mid route's are cut under a workspace budget -- and the workspace layout), wm_enqueue (uploads,
+// aligned copies, wm_run_group per group, one read-back of the one log slab), the large-N problems (ward.hip's
+// icl_ward_cluster_exact: above WMM_CAP rows, a lone small problem, mid-size problems the policy leaves there, icl_set_many_options),
+// wm_collect.  What the two routes' groups do differently on the host is the table wm_kind.
 // Cluster ids and member ranks come from the merge log by ward.hip's rule (icl_ward_assign_ids) whichever route a problem took.
 #pragma clang fp contract(off)
 
@@ -53,8 +56,34 @@ struct wm_prob {
 static_assert(sizeof(wm_prob) % 8 == 0, "wm_prob is an array element");
 
 __host__ __device__ static inline int64_t wm_tri_len(int64_t n) { return n * (n - 1) / 2; }
-// LDS bytes of the merge kernel for a problem of n rows: per-slot arrays, reduction scratch, the triangle when it is kept there
-__host__ __device__ static inline int64_t wm_meta_bytes(int64_t n) { return (n * 20 + 64 * 3 + 15) / 16 * 16; }
+
+// The per-slot state both merge kernels keep in LDS, in this order; wm_slots_bytes and wm_carve are its only description.
+struct wm_slots {
+    uint64_t *rkey; // row t's best key (UINT64_MAX: none)
+    int32_t *rarg;  // ... and the slot of its partner
+    int32_t *sz;    // size of slot s's cluster, 0 when the slot is dead
+    int32_t *cid;   // creation id of slot s's cluster: singleton i -> i, t-th merge -> n + t
+    uint64_t *red_k; // reduction scratch of wm_block_min, one entry per wave (8-byte aligned: an odd n is padded by one slot)
+    int32_t *red_r;
+};
+#define WM_SLOT_BYTES 20 // rkey + rarg + sz + cid of one slot
+__host__ __device__ static inline int64_t wm_slots_bytes(int64_t n, int waves) { return (n + (n & 1)) * WM_SLOT_BYTES + waves * 12; }
+__device__ __forceinline__ wm_slots wm_carve(unsigned char *base, int n, int waves)
+{
+    wm_slots S;
+    S.rkey = reinterpret_cast<uint64_t *>(base);
+    S.rarg = reinterpret_cast<int32_t *>(S.rkey + n);
+    S.sz = S.rarg + n;
+    S.cid = S.sz + n;
+    S.red_k = reinterpret_cast<uint64_t *>(S.cid + n + (n & 1));
+    S.red_r = reinterpret_cast<int32_t *>(S.red_k + waves);
+    return S;
+}
+// LDS bytes of the small merge kernel for a problem of n rows: the slots (the route has always reserved 192 bytes behind the 20 n of
+// the arrays; the triangle's place depends on it), then the triangle when it is kept there
+#define WM_META_TAIL 192
+static_assert(WM_META_TAIL >= WM_SLOT_BYTES + WM_WAVES * 12, "wm_meta_bytes(n) >= wm_slots_bytes(n, WM_WAVES)");
+__host__ __device__ static inline int64_t wm_meta_bytes(int64_t n) { return (n * WM_SLOT_BYTES + WM_META_TAIL + 15) / 16 * 16; }
 static inline int64_t wm_lds_bytes(int64_t n, bool tri) { return wm_meta_bytes(n) + (tri ? wm_tri_len(n) * 4 : 0); }
 
 // ComputeInitialDistanceMatrix (clustering.go:61-73) of every problem: block b covers pairs [pair0[b], pair0[b] + 256) of problem prob[b]
@@ -81,7 +110,8 @@ __device__ __forceinline__ uint64_t wm_key(float v, int ca, int cb)
     return ((uint64_t)__float_as_uint(v) << 32) | (hi << 16) | lo;
 }
 
-// block-wide minimum of (key, slot); every thread returns it
+// block-wide minimum of (key, slot) over WAVES waves; every thread returns it
+template <int WAVES>
 __device__ __forceinline__ void wm_block_min(uint64_t &k, int &r, uint64_t *sk, int *sr)
 {
 #pragma unroll
@@ -102,7 +132,7 @@ __device__ __forceinline__ void wm_block_min(uint64_t &k, int &r, uint64_t *sk, 
     k = sk[0];
     r = sr[0];
 #pragma unroll
-    for (int q = 1; q < WM_WAVES; ++q)
+    for (int q = 1; q < WAVES; ++q)
         if (sk[q] < k) {
             k = sk[q];
             r = sr[q];
@@ -110,17 +140,68 @@ __device__ __forceinline__ void wm_block_min(uint64_t &k, int &r, uint64_t *sk, 
     __syncthreads(); // the scratch is free for the next reduction
 }
 
+// centroid row of the cluster living in slot s: its embedding while it is a singleton, else the merged centroid written into the slot
+__device__ __forceinline__ const float *wm_cent(const wm_prob &p, const int32_t *cid, int s)
+{
+    return (cid[s] >= p.n ? p.C : p.E) + (int64_t)s * p.d;
+}
+
+// First half of a merge step, the same on both routes: the reference's selection order and merge rule.
+// FindClosestClusters (clustering.go:119-133) over the row caches: the slots of position i (the later cluster, shi) and of j (slo).
+// false: (-1, -1), "No more clusters to merge" (:224-227).  Two barriers (wm_block_min's).
+template <int THREADS>
+__device__ __forceinline__ bool wm_select_pair(const wm_slots S, int n, int &shi, int &slo)
+{
+    uint64_t bk = ~0ull;
+    int br = -1;
+    for (int t = threadIdx.x; t < n; t += THREADS)
+        if (S.rkey[t] < bk) {
+            bk = S.rkey[t];
+            br = t;
+        }
+    wm_block_min<THREADS / 64>(bk, br, S.red_k, S.red_r);
+    if (bk == ~0ull) return false;
+    const int bu = S.rarg[br];
+    shi = S.cid[br] > S.cid[bu] ? br : bu;
+    slo = shi == br ? bu : br;
+    return true;
+}
+
+// The merge itself: log entry, MergeClusters(clusters[i], clusters[j]) (:236, :37-40) into the centroid row of slot slo, where the new
+// cluster lives (shi dies), then sizes, ids and keys.  Returns the new cluster's size.  One barrier inside; the caller's next
+// barrier publishes the bookkeeping.
+template <int THREADS>
+__device__ __forceinline__ int wm_merge_pair(const wm_prob &p, const wm_slots S, int step, int shi, int slo)
+{
+    const int sa = S.sz[shi], sb = S.sz[slo];
+    if (threadIdx.x == 0) {
+        p.log[2 * step] = S.cid[shi];
+        p.log[2 * step + 1] = S.cid[slo];
+    }
+    {
+        const float fa = (float)sa, fb = (float)sb, fs = (float)(sa + sb);
+        const float *ca = wm_cent(p, S.cid, shi), *cb = wm_cent(p, S.cid, slo);
+        float *out = p.C + (int64_t)slo * p.d;
+        for (int k = threadIdx.x; k < p.d; k += THREADS) out[k] = ward_merge_elem(fa, ca[k], fb, cb[k], fs); // (each k read, then written, by one thread)
+    }
+    __syncthreads(); // every thread has read the old sizes, ids and centroids
+    if (threadIdx.x == 0) {
+        S.sz[shi] = 0;
+        S.rkey[shi] = ~0ull;
+        S.sz[slo] = sa + sb;
+        S.cid[slo] = p.n + step;
+    }
+    return sa + sb;
+}
+
 __global__ __launch_bounds__(WM_THREADS) void ward_many_merge_kernel(const wm_prob *__restrict__ P, const int32_t *__restrict__ order)
 {
     extern __shared__ __align__(16) unsigned char wm_lds[];
     const wm_prob p = P[order[blockIdx.x]];
     const int n = p.n, d = p.d, maxs = p.max_size;
-    uint64_t *rkey = reinterpret_cast<uint64_t *>(wm_lds); // row t's best key (UINT64_MAX: none)
-    int32_t *rarg = reinterpret_cast<int32_t *>(rkey + n); // ... and the slot of its partner
-    int32_t *sz = rarg + n;                                 // size of slot s's cluster, 0 when the slot is dead
-    int32_t *cid = sz + n;                                  // creation id of slot s's cluster: singleton i -> i, t-th merge -> n + t
-    uint64_t *red_k = reinterpret_cast<uint64_t *>(cid + n + (n & 1)); // (8-byte aligned)
-    int32_t *red_r = reinterpret_cast<int32_t *>(red_k + WM_WAVES);
+    const wm_slots S = wm_carve(wm_lds, n, WM_WAVES);
+    uint64_t *const rkey = S.rkey;
+    int32_t *const rarg = S.rarg, *const sz = S.sz, *const cid = S.cid;
     float *tri = p.tri;
     if (p.lds_tri) {
         float *lt = reinterpret_cast<float *>(wm_lds + wm_meta_bytes(n));
@@ -133,9 +214,7 @@ __global__ __launch_bounds__(WM_THREADS) void ward_many_merge_kernel(const wm_pr
         cid[t] = t;
     }
     __syncthreads();
-    const float *E = p.E;
-    float *Cw = p.C;
-    auto cent = [&](int s) -> const float * { return (cid[s] >= n ? Cw : E) + (int64_t)s * d; };
+    auto cent = [&](int s) { return wm_cent(p, cid, s); };
     auto at = [&](int a, int b) -> float & { return a > b ? tri[a * (a - 1) / 2 + b] : tri[b * (b - 1) / 2 + a]; };
     // row t's minimum over every live, size-compatible partner below MaxFloat32 (NaN never is: clustering.go:126)
     auto scan = [&](int t) {
@@ -160,42 +239,12 @@ __global__ __launch_bounds__(WM_THREADS) void ward_many_merge_kernel(const wm_pr
     __syncthreads();
     int step = 0;
     for (; step < p.T; ++step) {
-        // FindClosestClusters (clustering.go:119-133) over the row caches
-        uint64_t bk = ~0ull;
-        int br = -1;
-        for (int t = threadIdx.x; t < n; t += WM_THREADS)
-            if (rkey[t] < bk) {
-                bk = rkey[t];
-                br = t;
-            }
-        wm_block_min(bk, br, red_k, red_r);
-        if (bk == ~0ull) break; // (-1, -1): "No more clusters to merge" (:224-227)
-        const int bu = rarg[br];
-        const int shi = cid[br] > cid[bu] ? br : bu, slo = shi == br ? bu : br; // position i (the later cluster) and j
-        const int sa = sz[shi], sb = sz[slo];
-        const int sn = slo; // the new cluster lives in the slot of the earlier one; shi dies
-        if (threadIdx.x == 0) {
-            p.log[2 * step] = cid[shi];
-            p.log[2 * step + 1] = cid[slo];
-        }
-        // MergeClusters(clusters[i], clusters[j]) (:236, :37-40) into slot sn's centroid row (each k read, then written, by one thread)
-        {
-            const float fa = (float)sa, fb = (float)sb, fs = (float)(sa + sb);
-            const float *ca = cent(shi), *cb = cent(slo);
-            float *out = Cw + (int64_t)sn * d;
-            for (int k = threadIdx.x; k < d; k += WM_THREADS) out[k] = ward_merge_elem(fa, ca[k], fb, cb[k], fs);
-        }
-        __syncthreads(); // every thread has read the old sizes, ids and centroids
-        if (threadIdx.x == 0) {
-            sz[shi] = 0;
-            rkey[shi] = ~0ull;
-            sz[sn] = sa + sb;
-            cid[sn] = n + step;
-        }
+        int shi, slo;
+        if (!wm_select_pair<WM_THREADS>(S, n, shi, slo)) break;
+        const int sn = slo, snew = wm_merge_pair<WM_THREADS>(p, S, step, shi, slo), cnew = n + step;
         __syncthreads();
         // UpdateDistanceMatrix (:76-96): WardDistance(clusters[t], newCluster) for every live t; the owner of row t updates its cache
-        const int snew = sa + sb, cnew = n + step;
-        const float *cn = Cw + (int64_t)sn * d;
+        const float *cn = p.C + (int64_t)sn * d;
         uint64_t nk = ~0ull;
         int nr = -1;
         uint32_t stale = 0; // rows of this thread whose cached partner just died
@@ -217,7 +266,7 @@ __global__ __launch_bounds__(WM_THREADS) void ward_many_merge_kernel(const wm_pr
                 rarg[t] = sn;
             }
         }
-        wm_block_min(nk, nr, red_k, red_r); // (its barriers also publish the new row)
+        wm_block_min<WM_WAVES>(nk, nr, S.red_k, S.red_r); // (its barriers also publish the new row)
         if (threadIdx.x == 0) {
             rkey[sn] = nk;
             rarg[sn] = nr;
@@ -260,11 +309,12 @@ static_assert(WMM_KC % 4 == 0 && (2 * WMM_BUF * 4) % 16 == 0, "the centroid chun
 #define WMI_TILE 64
 #define WMI_KC 16
 
-// LDS bytes of the mid merge kernel: two chunk buffers, two centroid chunks, the per-slot arrays (20 B per row), reduction scratch,
-// two counters, the list of rows to evaluate and the list of rows to rescan
+#define WMM_CHUNK_BYTES ((2 * WMM_BUF + 2 * WMM_KC) * 4) // two chunk buffers, two chunks of the new centroid
+// LDS bytes of the mid merge kernel: the chunk buffers, the slots, two counters, the list of rows to evaluate and the list of rows to
+// rescan (uint16_t each)
 __host__ __device__ static inline int64_t wmm_lds_bytes(int64_t n)
 {
-    return ((2 * WMM_BUF + 2 * WMM_KC) * 4 + (n + (n & 1)) * 20 + WMM_WAVES * 12 + 8 + n * 4 + 15) / 16 * 16;
+    return (WMM_CHUNK_BYTES + wm_slots_bytes(n, WMM_WAVES) + 8 + n * 4 + 15) / 16 * 16;
 }
 
 // ComputeInitialDistanceMatrix (clustering.go:61-73) into the full square: block b computes the 64 x 64 pairs (i, j) of tile
@@ -342,35 +392,6 @@ __global__ __launch_bounds__(256) void ward_many_mid_init_kernel(const wm_prob *
         }
 }
 
-// block-wide minimum of (key, slot) over WMM_THREADS threads; every thread returns it
-__device__ __forceinline__ void wmm_block_min(uint64_t &k, int &r, uint64_t *sk, int *sr)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const uint64_t ok = __shfl_xor(k, off);
-        const int orr = __shfl_xor(r, off);
-        if (ok < k) {
-            k = ok;
-            r = orr;
-        }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sk[w] = k;
-        sr[w] = r;
-    }
-    __syncthreads();
-    k = sk[0];
-    r = sr[0];
-#pragma unroll
-    for (int q = 1; q < WMM_WAVES; ++q)
-        if (sk[q] < k) {
-            k = sk[q];
-            r = sr[q];
-        }
-    __syncthreads(); // the scratch is free for the next reduction
-}
-
 // the threads of a wave for which f holds append t to list (order within the list is arbitrary: every use of it is per row)
 __device__ __forceinline__ void wmm_append(bool f, int t, int32_t *count, uint16_t *list)
 {
@@ -390,13 +411,10 @@ __global__ __launch_bounds__(WMM_THREADS) void ward_many_mid_merge_kernel(const 
     const int n = p.n, d = p.d, maxs = p.max_size, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *buf = reinterpret_cast<float *>(wm_lds);                     // two chunk buffers: row r of the pass at r * WMM_STRIDE
     float *cbuf = buf + 2 * WMM_BUF;                                    // two chunks of the new centroid
-    uint64_t *rkey = reinterpret_cast<uint64_t *>(cbuf + 2 * WMM_KC);   // row t's best key (UINT64_MAX: none)
-    int32_t *rarg = reinterpret_cast<int32_t *>(rkey + n);              // ... and the slot of its partner
-    int32_t *sz = rarg + n;                                             // size of slot s's cluster, 0 when the slot is dead
-    int32_t *cid = sz + n;                                              // creation id of slot s's cluster
-    uint64_t *red_k = reinterpret_cast<uint64_t *>(cid + n + (n & 1)); // (8-byte aligned)
-    int32_t *red_r = reinterpret_cast<int32_t *>(red_k + WMM_WAVES);
-    int32_t *cnt = red_r + WMM_WAVES;                                   // [0] rows to evaluate, [1] rows to rescan
+    const wm_slots S = wm_carve(wm_lds + WMM_CHUNK_BYTES, n, WMM_WAVES);
+    uint64_t *const rkey = S.rkey;
+    int32_t *const rarg = S.rarg, *const sz = S.sz, *const cid = S.cid;
+    int32_t *cnt = reinterpret_cast<int32_t *>(wm_lds + WMM_CHUNK_BYTES + wm_slots_bytes(n, WMM_WAVES));                               // [0] rows to evaluate, [1] rows to rescan
     uint16_t *ev = reinterpret_cast<uint16_t *>(cnt + 2);
     uint16_t *stl = ev + n;
     float *M = p.tri; // entry (a, b) at a n + b, both orders written
@@ -405,9 +423,7 @@ __global__ __launch_bounds__(WMM_THREADS) void ward_many_mid_merge_kernel(const 
         cid[t] = t;
     }
     __syncthreads();
-    const float *E = p.E;
-    float *Cw = p.C;
-    auto cent = [&](int s) -> const float * { return (cid[s] >= n ? Cw : E) + (int64_t)s * d; };
+    auto cent = [&](int s) { return wm_cent(p, cid, s); };
     // row t's minimum over every live, size-compatible partner below MaxFloat32 (NaN never is: clustering.go:126), by one wave
     auto scan = [&](int t) {
         uint64_t best = ~0ull;
@@ -445,45 +461,14 @@ __global__ __launch_bounds__(WMM_THREADS) void ward_many_mid_merge_kernel(const 
     const int nch = (d + WMM_KC - 1) / WMM_KC;
     int step = 0;
     for (; step < p.T; ++step) {
-        // FindClosestClusters (clustering.go:119-133) over the row caches
-        uint64_t bk = ~0ull;
-        int br = -1;
-        for (int t = tid; t < n; t += WMM_THREADS)
-            if (rkey[t] < bk) {
-                bk = rkey[t];
-                br = t;
-            }
-        wmm_block_min(bk, br, red_k, red_r);
-        if (bk == ~0ull) break; // (-1, -1): "No more clusters to merge" (:224-227)
-        const int bu = rarg[br];
-        const int shi = cid[br] > cid[bu] ? br : bu, slo = shi == br ? bu : br; // position i (the later cluster) and j
-        const int sa = sz[shi], sb = sz[slo];
-        const int sn = slo; // the new cluster lives in the slot of the earlier one; shi dies
-        if (tid == 0) {
-            p.log[2 * step] = cid[shi];
-            p.log[2 * step + 1] = cid[slo];
-        }
-        // MergeClusters(clusters[i], clusters[j]) (:236, :37-40) into slot sn's centroid row (each k read, then written, by one thread)
-        {
-            const float fa = (float)sa, fb = (float)sb, fs = (float)(sa + sb);
-            const float *ca = cent(shi), *cb = cent(slo);
-            float *out = Cw + (int64_t)sn * d;
-            for (int k = tid; k < d; k += WMM_THREADS) out[k] = ward_merge_elem(fa, ca[k], fb, cb[k], fs);
-        }
-        __syncthreads(); // every thread has read the old sizes, ids and centroids
-        if (tid == 0) {
-            sz[shi] = 0;
-            rkey[shi] = ~0ull;
-            sz[sn] = sa + sb;
-            cid[sn] = n + step;
-            cnt[0] = 0;
-            cnt[1] = 0;
-        }
+        int shi, slo;
+        if (!wm_select_pair<WMM_THREADS>(S, n, shi, slo)) break;
+        const int sn = slo, snew = wm_merge_pair<WMM_THREADS>(p, S, step, shi, slo), cnew = n + step;
+        if (tid == 0) cnt[0] = cnt[1] = 0;
         __syncthreads();
         // UpdateDistanceMatrix (:76-96).  Every live row t: banned pairs get MaxFloat32 and are never evaluated (:228-234); the
         // others go on the list of rows to evaluate; rows whose cached partner just died go on the list of rows to rescan.
-        const int snew = sa + sb, cnew = n + step;
-        const float *cn = Cw + (int64_t)sn * d;
+        const float *cn = p.C + (int64_t)sn * d;
         float *Mn = M + (int64_t)sn * n;
         for (int t0 = 0; t0 < n; t0 += WMM_THREADS) {
             const int t = t0 + tid;
@@ -613,7 +598,7 @@ __global__ __launch_bounds__(WMM_THREADS) void ward_many_mid_merge_kernel(const 
                 }
             }
         }
-        wmm_block_min(nk, nr, red_k, red_r); // (its barriers also publish the new row and column)
+        wm_block_min<WMM_WAVES>(nk, nr, S.red_k, S.red_r); // (its barriers also publish the new row and column)
         if (tid == 0) {
             rkey[sn] = nk;
             rarg[sn] = nr;
@@ -640,10 +625,9 @@ static int64_t wm_cap()
     return cap;
 }
 
-// The mid route's workspace per problem (centroids + the square matrix, 256-byte aligned pieces) and the budget a group of them
-// stays under: ICL_MANY_MID_WS_MB (read once per process; for A/B runs and tests), else WMM_WS_DEFAULT.
+// The budget a group of mid-route problems stays under with its centroids and square matrices (wm_data_bytes): ICL_MANY_MID_WS_MB
+// (read once per process; for A/B runs and tests), else WMM_WS_DEFAULT.
 #define WMM_WS_DEFAULT ((size_t)8 << 30)
-static size_t wmm_ws_bytes(int64_t n, int64_t d) { return ((size_t)(n * d * 4) + 255) / 256 * 256 + ((size_t)(n * n * 4) + 255) / 256 * 256; }
 static size_t wmm_budget()
 {
     static const size_t b = [] {
@@ -735,33 +719,281 @@ static int wm_check_args(icl_ctx *ctx, const char *what, int32_t nprob, const fl
     return ICL_OK;
 }
 
-// the last icl_cluster's reports (icl_last_merges, icl_last_merge_values, icl_last_ward_*): a problem on the large-N route must not change them
+// the last icl_cluster's reports (icl_ctx::last): a problem on the large-N route must not change them
 struct wm_last_guard {
     icl_ctx *c;
-    std::vector<int32_t> merges;
-    std::vector<float> vals;
-    int64_t viol, layout[3], stats[4];
-    int32_t mode[2];
-    double dist_ms, merge_ms;
-    explicit wm_last_guard(icl_ctx *ctx) : c(ctx), merges(ctx->last_merges), vals(ctx->last_merge_vals), viol(ctx->ward_bound_viol),
-                                           dist_ms(ctx->last_dist_ms), merge_ms(ctx->last_merge_ms)
-    {
-        memcpy(layout, ctx->ward_layout, sizeof layout);
-        memcpy(stats, ctx->ward_stats, sizeof stats);
-        memcpy(mode, ctx->ward_mode, sizeof mode);
-    }
-    ~wm_last_guard()
-    {
-        c->last_merges.swap(merges);
-        c->last_merge_vals.swap(vals);
-        c->ward_bound_viol = viol;
-        memcpy(c->ward_layout, layout, sizeof layout);
-        memcpy(c->ward_stats, stats, sizeof stats);
-        memcpy(c->ward_mode, mode, sizeof mode);
-        c->last_dist_ms = dist_ms;
-        c->last_merge_ms = merge_ms;
-    }
+    icl_ward_report saved;
+    explicit wm_last_guard(icl_ctx *ctx) : c(ctx), saved(std::move(ctx->last)) {}
+    ~wm_last_guard() { c->last = std::move(saved); }
 };
+
+// WM_NONE: nothing to merge, or the constraints cannot be met; WM_SMALL: n <= cap, the small kernels; WM_LARGE: ward.hip's large-N
+// engine, one problem at a time; WM_MID: cap < n <= WMM_CAP, the mid kernels
+enum wm_route : int8_t { WM_NONE, WM_SMALL, WM_LARGE, WM_MID };
+
+// What differs between the two one-workgroup routes.  init_blocks lists the init kernel's blocks for table entry g: (g, pair0) per 256
+// pairs of the triangle, or (g, ti << 16 | tj) per pair of 64-row tiles, ti >= tj.  Both init kernels take (table, block problems,
+// block arguments) and both merge kernels (table, order): pointers only, so one launch call serves either.
+struct wm_kind {
+    int64_t (*mat_bytes)(int64_t n);
+    void (*init_blocks)(int32_t g, int64_t n, std::vector<int32_t> &prob, std::vector<int64_t> &arg);
+    int arg_bytes; // of one init-block argument on the device
+    bool (*lds_tri)(int64_t n);
+    int64_t (*lds_bytes)(int64_t n); // dynamic LDS of the merge kernel
+    const void *init_fn, *merge_fn;
+    unsigned init_threads, merge_threads;
+};
+static const wm_kind wm_kind_small = {
+    [](int64_t n) { return wm_tri_len(n) * 4; },
+    [](int32_t g, int64_t n, std::vector<int32_t> &prob, std::vector<int64_t> &arg) {
+        for (int64_t q = 0; q < wm_tri_len(n); q += WM_THREADS) prob.push_back(g), arg.push_back(q);
+    },
+    8,
+    [](int64_t n) { return wm_lds_bytes(n, true) <= WM_LDS_MAX; },
+    [](int64_t n) { return wm_lds_bytes(n, wm_lds_bytes(n, true) <= WM_LDS_MAX); },
+    (const void *)ward_many_init_kernel, (const void *)ward_many_merge_kernel, WM_THREADS, WM_THREADS,
+};
+static const wm_kind wm_kind_mid = {
+    [](int64_t n) { return n * n * 4; },
+    [](int32_t g, int64_t n, std::vector<int32_t> &prob, std::vector<int64_t> &arg) {
+        const int32_t nt = (int32_t)((n + WMI_TILE - 1) / WMI_TILE);
+        for (int32_t ti = 0; ti < nt; ++ti)
+            for (int32_t tj = 0; tj <= ti; ++tj) prob.push_back(g), arg.push_back(ti << 16 | tj);
+    },
+    4,
+    [](int64_t) { return false; },
+    [](int64_t n) { return wmm_lds_bytes(n); },
+    (const void *)ward_many_mid_init_kernel, (const void *)ward_many_mid_merge_kernel, 256, WMM_THREADS,
+};
+
+// centroids + matrix of one problem in a group's data region (256-byte aligned pieces)
+static size_t wm_data_bytes(const wm_kind &k, int64_t n, int64_t d)
+{
+    wm_layout R;
+    R.take((size_t)(n * d * 4));
+    R.take((size_t)k.mat_bytes(n));
+    return R.off;
+}
+
+// A launch group: problems that run as one init launch and one merge launch, one workgroup each in the merge.  The small route is one
+// group with a data region of its own; the mid route's groups use one shared region one after the other (the launches are ordered on
+// the stream).
+struct wm_group {
+    const wm_kind *kind = nullptr;
+    std::vector<int32_t> probs; // largest first
+    std::vector<int32_t> blk_prob;
+    std::vector<int64_t> blk_arg;
+    size_t data_bytes = 0;
+    size_t o_head = 0, o_data = 0; // in the workspace; the head: [problem table] [init-block arguments] [order] [init-block problems]
+    std::vector<unsigned char> head;
+    size_t head_bytes() const { return sizeof(wm_prob) * probs.size() + (size_t)kind->arg_bytes * blk_arg.size() + 4 * (probs.size() + blk_prob.size()); }
+};
+
+// the per-problem arguments of both entry points
+struct wm_args {
+    int32_t nprob;
+    const int64_t *e_off;
+    const int32_t *n, *d, *min_size, *max_size;
+};
+
+struct wm_plan {
+    std::vector<int64_t> img, k; // first image of problem p; clusters CalculateOptimalClusters asks for
+    std::vector<int32_t> st;
+    std::vector<std::string> why;
+    std::vector<wm_route> route;
+    bool need_e = false;
+    std::vector<wm_group> groups; // the small group (if any), then the mid groups
+    std::vector<int64_t> log_at;  // problem p's log in the slab: 2 (n - k) ids, the count at 2 n
+    int64_t log_ints = 0;
+    std::vector<size_t> o_al; // problems whose rows the float4 loads cannot read in place: a 16-byte aligned copy
+    size_t o_e = 0, o_logs = 0, ws_bytes = 0;
+};
+
+// k, status and route of every problem; many_stats
+static void wm_classify(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
+{
+    const int64_t cap = wm_cap();
+    const int32_t nprob = A.nprob;
+    pl.img.assign(nprob + 1, 0);
+    pl.k.assign(nprob, 0);
+    pl.why.resize(nprob);
+    pl.st.assign(nprob, ICL_OK);
+    pl.route.assign(nprob, WM_NONE);
+    for (int32_t p = 0; p < nprob; ++p) {
+        pl.img[p + 1] = pl.img[p] + A.n[p];
+        if (icl_calc_optimal_clusters(A.n[p], A.min_size[p], A.max_size[p], &pl.k[p]) != ICL_OK) { // clustering.go:203-207
+            pl.st[p] = ICL_ERR_CONSTRAINT;
+            char b[200];
+            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%d), minSize (%d), and maxSize (%d)", A.n[p],
+                     A.min_size[p], A.max_size[p]);
+            pl.why[p] = b;
+        }
+    }
+    auto mid_size = [&](int32_t p) { return A.n[p] > cap && A.n[p] <= WMM_CAP; };
+    int64_t mid_band[WMM_BANDS] = {};
+    for (int32_t p = 0; p < nprob; ++p) {
+        if (pl.st[p] != ICL_OK || A.n[p] - pl.k[p] <= 0) continue;
+        pl.route[p] = A.n[p] <= cap ? WM_SMALL : WM_LARGE;
+        if (pl.route[p] == WM_SMALL) small.push_back(p);
+        if (mid_size(p)) ++mid_band[wmm_band(A.n[p])];
+        pl.need_e = pl.need_e || (int64_t)A.n[p] * A.d[p] > 0;
+    }
+    if ((int64_t)small.size() < WM_MIN_BATCH) {
+        for (int32_t p : small) pl.route[p] = WM_LARGE;
+        small.clear();
+    }
+    if (ctx->many_mid != ICL_MANY_MID_OFF)
+        for (int32_t p = 0; p < nprob; ++p)
+            if (pl.route[p] == WM_LARGE && mid_size(p) && (ctx->many_mid == ICL_MANY_MID_ON || wmm_auto_takes(A.n[p], mid_band))) {
+                pl.route[p] = WM_MID;
+                mid.push_back(p);
+            }
+    ctx->many_stats[0] = (int64_t)small.size();
+    ctx->many_stats[1] = (int64_t)mid.size();
+    ctx->many_stats[2] = std::count(pl.route.begin(), pl.route.end(), WM_LARGE);
+}
+
+// the launch groups (the mid route's under the budget; a group holds at least one problem) and the workspace:
+// [uploaded E] [aligned copies] [logs, counts] [head of every group] [the small group's data] [the mid groups' shared data]
+static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t e_len, std::vector<int32_t> &small, std::vector<int32_t> &mid, wm_plan &pl)
+{
+    auto larger = [&](int32_t a, int32_t b) { return A.n[a] > A.n[b]; }; // largest first, within and across groups
+    std::stable_sort(small.begin(), small.end(), larger);
+    std::stable_sort(mid.begin(), mid.end(), larger);
+    auto add = [&](const wm_kind &kind, const std::vector<int32_t> &ps, size_t budget) {
+        for (int32_t p : ps) {
+            const size_t need = wm_data_bytes(kind, A.n[p], A.d[p]);
+            if (pl.groups.empty() || pl.groups.back().kind != &kind || pl.groups.back().data_bytes + need > budget) {
+                pl.groups.emplace_back();
+                pl.groups.back().kind = &kind;
+            }
+            wm_group &g = pl.groups.back();
+            kind.init_blocks((int32_t)g.probs.size(), A.n[p], g.blk_prob, g.blk_arg);
+            g.probs.push_back(p);
+            g.data_bytes += need;
+        }
+    };
+    add(wm_kind_small, small, SIZE_MAX);
+    add(wm_kind_mid, mid, wmm_budget());
+    ctx->many_stats[3] = (int64_t)pl.groups.size() - (small.empty() ? 0 : 1);
+    wm_layout L;
+    pl.o_e = upload_e && pl.need_e ? L.take((size_t)e_len * 4) : 0;
+    pl.o_al.assign(A.nprob, SIZE_MAX);
+    pl.log_at.assign(A.nprob, 0);
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        if (pl.route[p] && A.d[p] % 4 == 0 && A.n[p] && A.e_off[p] % 4 != 0) pl.o_al[p] = L.take((size_t)A.n[p] * A.d[p] * 4);
+        if (pl.route[p] == WM_SMALL || pl.route[p] == WM_MID) {
+            pl.log_at[p] = pl.log_ints;
+            pl.log_ints += 2 * (int64_t)A.n[p] + 1; // 2 (n - k) ids + the count
+        }
+    }
+    pl.o_logs = L.take(4 * (size_t)std::max<int64_t>(pl.log_ints, 1));
+    size_t shared = 0;
+    for (wm_group &g : pl.groups) {
+        g.o_head = L.take(g.head_bytes());
+        if (g.kind == &wm_kind_small) g.o_data = L.take(g.data_bytes);
+        else shared = std::max(shared, g.data_bytes);
+    }
+    const size_t o_shared = L.take(shared);
+    for (wm_group &g : pl.groups)
+        if (g.kind != &wm_kind_small) g.o_data = o_shared;
+    pl.ws_bytes = L.off;
+}
+
+// the group's head (problem table with device addresses, init blocks, order) uploaded, then one init launch and one merge launch
+static int wm_run_group(icl_ctx *ctx, const wm_args &A, const wm_plan &pl, wm_group &g, char *ws, const std::vector<const float *> &rowsE)
+{
+    const size_t G = g.probs.size(), o_arg = sizeof(wm_prob) * G, o_ord = o_arg + (size_t)g.kind->arg_bytes * g.blk_arg.size();
+    g.head.resize(g.head_bytes());
+    wm_prob *tab = reinterpret_cast<wm_prob *>(g.head.data());
+    int32_t *ord = reinterpret_cast<int32_t *>(g.head.data() + o_ord);
+    wm_layout R; // the problems' places in the group's data region
+    int64_t lds = 0;
+    for (size_t i = 0; i < G; ++i) {
+        const int32_t p = g.probs[i];
+        float *C = (float *)(ws + g.o_data + R.take((size_t)A.n[p] * A.d[p] * 4));
+        float *mat = (float *)(ws + g.o_data + R.take((size_t)g.kind->mat_bytes(A.n[p])));
+        int32_t *log = (int32_t *)(ws + pl.o_logs) + pl.log_at[p];
+        tab[i] = wm_prob{rowsE[p], C, mat, A.n[p], A.d[p], A.max_size[p], (int32_t)(A.n[p] - pl.k[p]), log, log + 2 * (int64_t)A.n[p],
+                         g.kind->lds_tri(A.n[p]) ? 1 : 0, 0};
+        ord[i] = (int32_t)i; // (probs is sorted: largest first)
+        lds = std::max(lds, g.kind->lds_bytes(A.n[p]));
+    }
+    for (size_t b = 0; b < g.blk_arg.size(); ++b) // (the low arg_bytes of a little-endian int64_t)
+        memcpy(g.head.data() + o_arg + (size_t)g.kind->arg_bytes * b, &g.blk_arg[b], g.kind->arg_bytes);
+    if (!g.blk_prob.empty()) memcpy(ord + G, g.blk_prob.data(), 4 * g.blk_prob.size());
+    const char *tab_d = ws + g.o_head, *arg_d = tab_d + o_arg, *ord_d = tab_d + o_ord, *blk_d = ord_d + 4 * G;
+    ICL_HIP(ctx, hipMemcpyAsync(ws + g.o_head, g.head.data(), g.head.size(), hipMemcpyHostToDevice, ctx->stream));
+    void *init_args[] = {&tab_d, &blk_d, &arg_d}, *merge_args[] = {&tab_d, &ord_d};
+    if (!g.blk_prob.empty())
+        ICL_HIP(ctx, hipLaunchKernel(g.kind->init_fn, dim3((unsigned)g.blk_prob.size()), dim3(g.kind->init_threads), init_args, 0, ctx->stream));
+    icl_lds_optin(ctx, g.kind->merge_fn, WM_LDS_MAX);
+    ICL_HIP(ctx, hipLaunchKernel(g.kind->merge_fn, dim3((unsigned)G), dim3(g.kind->merge_threads), merge_args, (size_t)lds, ctx->stream));
+    return ICL_OK;
+}
+
+// uploads, aligned copies, every group's launches, the read-back of the log slab: all on ctx->stream, not waited for
+static int wm_enqueue(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const float *d_E, const float *h_E, int64_t e_len, std::vector<const float *> &rowsE,
+                      std::vector<int32_t> &slab)
+{
+    char *ws = nullptr;
+    ICL_TRY(wm_ensure(ctx, pl.ws_bytes, &ws));
+    if (h_E && pl.need_e) {
+        ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_e, h_E, (size_t)e_len * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_E = (const float *)(ws + pl.o_e);
+    }
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        if (!pl.route[p]) continue;
+        rowsE[p] = d_E + A.e_off[p];
+        if (pl.o_al[p] != SIZE_MAX) {
+            ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_al[p], rowsE[p], (size_t)A.n[p] * A.d[p] * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            rowsE[p] = (const float *)(ws + pl.o_al[p]);
+        }
+    }
+    for (wm_group &g : pl.groups) ICL_TRY(wm_run_group(ctx, A, pl, g, ws, rowsE));
+    slab.resize((size_t)std::max<int64_t>(pl.log_ints, 1));
+    if (pl.log_ints) ICL_HIP(ctx, hipMemcpyAsync(slab.data(), ws + pl.o_logs, 4 * (size_t)pl.log_ints, hipMemcpyDeviceToHost, ctx->stream));
+    return ICL_OK;
+}
+
+// ids from the merge logs (clustering.go:265-280, ward.hip's rule), merge logs, statuses; the lowest failed problem's error
+static int wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, std::vector<std::vector<int32_t>> &big_log,
+                      int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
+{
+    std::vector<int32_t> pairs;
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        int32_t *cid = cluster_id + pl.img[p], *rank = member_rank + pl.img[p];
+        int64_t nm = 0;
+        if (pl.route[p] == WM_LARGE) {
+            pairs.swap(big_log[p]);
+            nm = (int64_t)pairs.size() / 2;
+        } else if (pl.route[p] != WM_NONE) {
+            const int32_t *lg = slab.data() + pl.log_at[p];
+            nm = lg[2 * (int64_t)A.n[p]];
+            pairs.assign(lg, lg + 2 * nm);
+        } else
+            pairs.clear();
+        if (pl.st[p] == ICL_OK && pl.route[p] != WM_LARGE) {
+            const int rc = icl_ward_assign_ids(ctx, A.n[p], A.min_size[p], A.max_size[p], pairs, nm, cid, rank, &n_clusters[p]);
+            if (rc != ICL_OK) {
+                pl.st[p] = rc;
+                pl.why[p] = ctx->err;
+            }
+        }
+        if (pl.st[p] != ICL_OK) {
+            std::fill(cid, cid + A.n[p], -1);
+            std::fill(rank, rank + A.n[p], -1);
+            n_clusters[p] = 0;
+            nm = 0;
+        }
+        n_merges[p] = (int32_t)nm;
+        if (merges && nm) memcpy(merges + 2 * pl.img[p], pairs.data(), 8 * (size_t)nm);
+        status[p] = pl.st[p];
+    }
+    for (int32_t p = 0; p < A.nprob; ++p)
+        if (pl.st[p] != ICL_OK) return icl_fail(ctx, pl.st[p], "icl_cluster_many: problem %d: %s", p, pl.why[p].c_str());
+    return ICL_OK;
+}
 
 // Both entry points, after the argument check, with ctx->mu held.  d_E: the embeddings on the device (e_len floats); h_E: the host copy
 // (icl_cluster_many), uploaded into the workspace here, or nullptr.
@@ -769,270 +1001,34 @@ static int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, co
                                const int32_t *n, const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id,
                                int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
 {
-    const int64_t cap = wm_cap();
-    std::vector<int64_t> img(nprob + 1, 0), k(nprob, 0);
-    std::vector<std::string> why(nprob);
-    std::vector<int32_t> st(nprob, ICL_OK);
-    for (int32_t p = 0; p < nprob; ++p) {
-        img[p + 1] = img[p] + n[p];
-        if (icl_calc_optimal_clusters(n[p], min_size[p], max_size[p], &k[p]) != ICL_OK) { // clustering.go:203-207
-            st[p] = ICL_ERR_CONSTRAINT;
-            char b[200];
-            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%d), minSize (%d), and maxSize (%d)", n[p], min_size[p],
-                     max_size[p]);
-            why[p] = b;
-        }
-    }
-    // routes: 0 nothing to merge (or failed), 1 the small kernels, 2 the large-N engine, 3 the mid-size kernels
-    std::vector<int8_t> route(nprob, 0);
-    std::vector<int32_t> gpu; // problems of route 1
-    std::vector<int32_t> mid; // problems of route 3
-    bool need_e = false;
-    int64_t mid_band[WMM_BANDS] = {};
-    for (int32_t p = 0; p < nprob; ++p) {
-        if (st[p] != ICL_OK || n[p] - k[p] <= 0) continue;
-        route[p] = n[p] <= cap ? 1 : 2;
-        if (route[p] == 1) gpu.push_back(p);
-        if (n[p] > cap && n[p] <= WMM_CAP) ++mid_band[wmm_band(n[p])];
-        need_e = need_e || (int64_t)n[p] * d[p] > 0;
-    }
-    if ((int64_t)gpu.size() < WM_MIN_BATCH) {
-        for (int32_t p : gpu) route[p] = 2;
-        gpu.clear();
-    }
-    if (ctx->many_mid != ICL_MANY_MID_OFF)
-        for (int32_t p = 0; p < nprob; ++p)
-            if (route[p] == 2 && n[p] > cap && n[p] <= WMM_CAP && (ctx->many_mid == ICL_MANY_MID_ON || wmm_auto_takes(n[p], mid_band))) {
-                route[p] = 3;
-                mid.push_back(p);
-            }
-    std::stable_sort(mid.begin(), mid.end(), [&](int32_t a, int32_t b) { return n[a] > n[b]; }); // largest first, within and across groups
-    // groups of mid problems whose centroids and matrices fit the budget together (a group holds at least one problem)
-    const int32_t NM = (int32_t)mid.size();
-    std::vector<int32_t> grp_at(1, 0); // group q: mid[grp_at[q] .. grp_at[q + 1])
-    size_t mid_ws = 0;
+    const wm_args A = {nprob, e_off, n, d, min_size, max_size};
+    wm_plan pl;
     {
-        size_t cur = 0;
-        for (int32_t g = 0; g < NM; ++g) {
-            const size_t need = wmm_ws_bytes(n[mid[g]], d[mid[g]]);
-            if (g > grp_at.back() && cur + need > wmm_budget()) {
-                grp_at.push_back(g);
-                cur = 0;
-            }
-            cur += need;
-            mid_ws = std::max(mid_ws, cur);
-        }
-        if (NM) grp_at.push_back(NM);
-    }
-    const int32_t NG = (int32_t)grp_at.size() - 1;
-    ctx->many_stats[0] = (int64_t)gpu.size();
-    ctx->many_stats[1] = NM;
-    ctx->many_stats[2] = 0;
-    for (int32_t p = 0; p < nprob; ++p) ctx->many_stats[2] += route[p] == 2;
-    ctx->many_stats[3] = NG;
-    // workspace: [uploaded E] [aligned copies] [problem table] [order] [init blocks] [logs, counts] [centroids] [triangles]
-    wm_layout L;
-    const size_t o_e = h_E && need_e ? L.take((size_t)e_len * 4) : 0;
-    std::vector<size_t> o_al(nprob, SIZE_MAX); // problems whose rows the float4 loads cannot read in place: a 16-byte aligned copy
-    for (int32_t p = 0; p < nprob; ++p)
-        if (route[p] && d[p] % 4 == 0 && n[p] && e_off[p] % 4 != 0) o_al[p] = L.take((size_t)n[p] * d[p] * 4);
-    const int32_t G = (int32_t)gpu.size();
-    std::vector<int32_t> blk_prob;
-    std::vector<int64_t> blk_pair0;
-    for (int32_t g = 0; g < G; ++g)
-        for (int64_t q = 0; q < wm_tri_len(n[gpu[g]]); q += WM_THREADS) {
-            blk_prob.push_back(g);
-            blk_pair0.push_back(q);
-        }
-    const size_t o_tab = L.take(sizeof(wm_prob) * std::max(G, 1)), o_ord = L.take(4 * (size_t)std::max(G, 1));
-    const size_t o_bp = L.take(4 * std::max<size_t>(blk_prob.size(), 1)), o_bq = L.take(8 * std::max<size_t>(blk_pair0.size(), 1));
-    std::vector<size_t> o_log(G), o_c(G), o_t(G);
-    int64_t log_ints = 0;
-    for (int32_t g = 0; g < G; ++g) log_ints += 2 * (int64_t)n[gpu[g]] + 1; // 2 (n - k) ids + the count
-    const size_t o_logs = L.take(4 * (size_t)std::max<int64_t>(log_ints, 1));
-    for (int32_t g = 0; g < G; ++g) {
-        const int32_t p = gpu[g];
-        o_c[g] = L.take((size_t)n[p] * d[p] * 4);
-        o_t[g] = L.take((size_t)wm_tri_len(n[p]) * 4);
-    }
-    // the mid route: [problem table] [order] [init blocks] [logs, counts] of every group, then one region of centroids and matrices
-    // that the groups use one after the other (the launches are ordered on the stream)
-    std::vector<int32_t> mblk_prob, mblk_tile;
-    std::vector<size_t> mblk_at(NG + 1, 0);
-    for (int32_t q = 0; q < NG; ++q) {
-        for (int32_t g = grp_at[q]; g < grp_at[q + 1]; ++g) {
-            const int32_t nt = (n[mid[g]] + WMI_TILE - 1) / WMI_TILE;
-            for (int32_t ti = 0; ti < nt; ++ti)
-                for (int32_t tj = 0; tj <= ti; ++tj) {
-                    mblk_prob.push_back(g);
-                    mblk_tile.push_back(ti << 16 | tj);
-                }
-        }
-        mblk_at[q + 1] = mblk_prob.size();
-    }
-    const size_t o_mtab = L.take(sizeof(wm_prob) * std::max(NM, 1)), o_mord = L.take(4 * (size_t)std::max(NM, 1));
-    const size_t o_mbp = L.take(4 * std::max<size_t>(mblk_prob.size(), 1)), o_mbt = L.take(4 * std::max<size_t>(mblk_tile.size(), 1));
-    int64_t mlog_ints = 0;
-    for (int32_t g = 0; g < NM; ++g) mlog_ints += 2 * (int64_t)n[mid[g]] + 1;
-    const size_t o_mlogs = L.take(4 * (size_t)std::max<int64_t>(mlog_ints, 1));
-    const size_t o_mws = L.take(mid_ws);
-    char *ws = nullptr;
-    ICL_TRY(wm_ensure(ctx, L.off, &ws));
-    if (h_E && need_e) {
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_e, h_E, (size_t)e_len * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_E = (const float *)(ws + o_e);
+        std::vector<int32_t> small, mid;
+        wm_classify(ctx, A, pl, small, mid);
+        wm_make_plan(ctx, A, h_E != nullptr, e_len, small, mid, pl);
     }
     std::vector<const float *> rowsE(nprob, nullptr);
-    for (int32_t p = 0; p < nprob; ++p) {
-        if (!route[p]) continue;
-        rowsE[p] = d_E + e_off[p];
-        if (o_al[p] != SIZE_MAX) {
-            ICL_HIP(ctx, hipMemcpyAsync(ws + o_al[p], rowsE[p], (size_t)n[p] * d[p] * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            rowsE[p] = (const float *)(ws + o_al[p]);
-        }
-    }
-    std::vector<int32_t> hlog((size_t)std::max<int64_t>(log_ints, 1));
-    std::vector<int64_t> log_at(G);
-    if (G) {
-        std::vector<wm_prob> tab(G);
-        int64_t at = 0, lds = 0;
-        for (int32_t g = 0; g < G; ++g) {
-            const int32_t p = gpu[g];
-            wm_prob &w = tab[g];
-            w.E = rowsE[p];
-            w.C = (float *)(ws + o_c[g]);
-            w.tri = (float *)(ws + o_t[g]);
-            w.n = n[p];
-            w.d = d[p];
-            w.max_size = max_size[p];
-            w.T = (int32_t)(n[p] - k[p]);
-            log_at[g] = at;
-            w.log = (int32_t *)(ws + o_logs) + at;
-            w.nm = w.log + 2 * (int64_t)n[p];
-            at += 2 * (int64_t)n[p] + 1;
-            w.lds_tri = wm_lds_bytes(n[p], true) <= WM_LDS_MAX ? 1 : 0;
-            w.pad = 0;
-            lds = std::max(lds, wm_lds_bytes(n[p], w.lds_tri != 0));
-        }
-        std::vector<int32_t> ord(G);
-        std::iota(ord.begin(), ord.end(), 0);
-        std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return n[gpu[a]] > n[gpu[b]]; }); // largest problems first
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_tab, tab.data(), sizeof(wm_prob) * G, hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_ord, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice, ctx->stream));
-        if (!blk_prob.empty()) {
-            ICL_HIP(ctx, hipMemcpyAsync(ws + o_bp, blk_prob.data(), 4 * blk_prob.size(), hipMemcpyHostToDevice, ctx->stream));
-            ICL_HIP(ctx, hipMemcpyAsync(ws + o_bq, blk_pair0.data(), 8 * blk_pair0.size(), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(ward_many_init_kernel, dim3((unsigned)blk_prob.size()), dim3(WM_THREADS), 0, ctx->stream, (const wm_prob *)(ws + o_tab),
-                               (const int32_t *)(ws + o_bp), (const int64_t *)(ws + o_bq));
-            ICL_HIP(ctx, hipGetLastError());
-        }
-        icl_lds_optin(ctx, (const void *)ward_many_merge_kernel, WM_LDS_MAX);
-        hipLaunchKernelGGL(ward_many_merge_kernel, dim3((unsigned)G), dim3(WM_THREADS), (unsigned)lds, ctx->stream, (const wm_prob *)(ws + o_tab),
-                           (const int32_t *)(ws + o_ord));
-        ICL_HIP(ctx, hipGetLastError());
-        ICL_HIP(ctx, hipMemcpyAsync(hlog.data(), ws + o_logs, 4 * (size_t)log_ints, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    std::vector<int32_t> hmlog((size_t)std::max<int64_t>(mlog_ints, 1));
-    std::vector<int64_t> mlog_at(NM);
-    std::vector<wm_prob> mtab(NM);
-    std::vector<int32_t> mord(NM);
-    if (NM) {
-        int64_t at = 0;
-        for (int32_t q = 0; q < NG; ++q) {
-            wm_layout R; // this group's share of the reused region
-            for (int32_t g = grp_at[q]; g < grp_at[q + 1]; ++g) {
-                const int32_t p = mid[g];
-                wm_prob &w = mtab[g];
-                w.E = rowsE[p];
-                w.C = (float *)(ws + o_mws + R.take((size_t)n[p] * d[p] * 4));
-                w.tri = (float *)(ws + o_mws + R.take((size_t)n[p] * n[p] * 4));
-                w.n = n[p];
-                w.d = d[p];
-                w.max_size = max_size[p];
-                w.T = (int32_t)(n[p] - k[p]);
-                mlog_at[g] = at;
-                w.log = (int32_t *)(ws + o_mlogs) + at;
-                w.nm = w.log + 2 * (int64_t)n[p];
-                at += 2 * (int64_t)n[p] + 1;
-                w.lds_tri = 0;
-                w.pad = 0;
-                mord[g] = g; // (mid is sorted: largest first)
-            }
-        }
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_mtab, mtab.data(), sizeof(wm_prob) * NM, hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_mord, mord.data(), 4 * (size_t)NM, hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_mbp, mblk_prob.data(), 4 * mblk_prob.size(), hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipMemcpyAsync(ws + o_mbt, mblk_tile.data(), 4 * mblk_tile.size(), hipMemcpyHostToDevice, ctx->stream));
-        icl_lds_optin(ctx, (const void *)ward_many_mid_merge_kernel, WM_LDS_MAX);
-        for (int32_t q = 0; q < NG; ++q) { // one init launch and one merge launch per group
-            const size_t nb = mblk_at[q + 1] - mblk_at[q];
-            hipLaunchKernelGGL(ward_many_mid_init_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const wm_prob *)(ws + o_mtab),
-                               (const int32_t *)(ws + o_mbp) + mblk_at[q], (const int32_t *)(ws + o_mbt) + mblk_at[q]);
-            ICL_HIP(ctx, hipGetLastError());
-            const int64_t lds = wmm_lds_bytes(n[mid[grp_at[q]]]); // the group's largest problem
-            hipLaunchKernelGGL(ward_many_mid_merge_kernel, dim3((unsigned)(grp_at[q + 1] - grp_at[q])), dim3(WMM_THREADS), (unsigned)lds, ctx->stream,
-                               (const wm_prob *)(ws + o_mtab), (const int32_t *)(ws + o_mord) + grp_at[q]);
-            ICL_HIP(ctx, hipGetLastError());
-        }
-        ICL_HIP(ctx, hipMemcpyAsync(hmlog.data(), ws + o_mlogs, 4 * (size_t)mlog_ints, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    std::vector<int32_t> slab;
+    ICL_TRY(wm_enqueue(ctx, A, pl, d_E, h_E, e_len, rowsE, slab));
     // the large-N route, one problem at a time, behind the launches above (its reports of the last icl_cluster are restored)
     std::vector<std::vector<int32_t>> big_log(nprob);
     {
         wm_last_guard keep(ctx);
         for (int32_t p = 0; p < nprob; ++p) {
-            if (route[p] != 2) continue;
+            if (pl.route[p] != WM_LARGE) continue;
             int32_t nc = 0;
-            const int rc = icl_ward_cluster_exact(ctx, rowsE[p], n[p], d[p], min_size[p], max_size[p], cluster_id + img[p], member_rank + img[p], &nc,
-                                                  &big_log[p]);
+            const int rc = icl_ward_cluster_exact(ctx, rowsE[p], n[p], d[p], min_size[p], max_size[p], cluster_id + pl.img[p], member_rank + pl.img[p],
+                                                  &nc, &big_log[p]);
             n_clusters[p] = nc;
             if (rc != ICL_OK) {
-                st[p] = rc;
-                why[p] = ctx->err;
+                pl.st[p] = rc;
+                pl.why[p] = ctx->err;
             }
         }
     }
-    if (G || NM) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> mid_of(NM ? nprob : 0, -1); // problem -> its place in mid
-    for (int32_t g = 0; g < NM; ++g) mid_of[mid[g]] = g;
-    // ids from the merge logs (clustering.go:265-280, ward.hip's rule), merge logs, statuses
-    std::vector<int32_t> pairs;
-    for (int32_t p = 0, g = 0; p < nprob; ++p) {
-        int32_t *cid = cluster_id + img[p], *rank = member_rank + img[p];
-        int64_t nm = 0;
-        if (route[p] == 1) {
-            const int32_t *lg = hlog.data() + log_at[g++];
-            nm = lg[2 * (int64_t)n[p]];
-            pairs.assign(lg, lg + 2 * nm);
-        } else if (route[p] == 3) {
-            const int32_t *lg = hmlog.data() + mlog_at[mid_of[p]];
-            nm = lg[2 * (int64_t)n[p]];
-            pairs.assign(lg, lg + 2 * nm);
-        } else if (route[p] == 2) {
-            pairs.swap(big_log[p]);
-            nm = (int64_t)pairs.size() / 2;
-        } else
-            pairs.clear();
-        if (st[p] == ICL_OK && route[p] != 2) {
-            const int rc = icl_ward_assign_ids(ctx, n[p], min_size[p], max_size[p], pairs, nm, cid, rank, &n_clusters[p]);
-            if (rc != ICL_OK) {
-                st[p] = rc;
-                why[p] = ctx->err;
-            }
-        }
-        if (st[p] != ICL_OK) {
-            std::fill(cid, cid + n[p], -1);
-            std::fill(rank, rank + n[p], -1);
-            n_clusters[p] = 0;
-            nm = 0;
-        }
-        n_merges[p] = (int32_t)nm;
-        if (merges && nm) memcpy(merges + 2 * img[p], pairs.data(), 8 * (size_t)nm);
-        status[p] = st[p];
-    }
-    for (int32_t p = 0; p < nprob; ++p)
-        if (st[p] != ICL_OK) return icl_fail(ctx, st[p], "icl_cluster_many: problem %d: %s", p, why[p].c_str());
-    return ICL_OK;
+    if (!pl.groups.empty()) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return wm_collect(ctx, A, pl, slab, big_log, cluster_id, member_rank, n_clusters, n_merges, merges, status);
 }
 
 extern "C" int icl_set_many_options(icl_ctx *ctx, int mid_mode)

@@ -5,13 +5,13 @@ import ctypes as C
 import os
 import subprocess
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 from tests import ward_cases as WC
+from tests.many_cases import oracles, same_as_cluster, same_as_oracle, same_reports, same_results, serving_problems, ward_reports
 
 pytestmark = pytest.mark.gpu
 
@@ -25,64 +25,19 @@ def ctx():
     c.close()
 
 
-def serving_problems(count, seed, n_lo=2, n_hi=256, dup_every=0):
-    """The reference's request shape (workflow.Run): n images, d = 1000 dense0 columns + L one-hot label columns, min 3 / max 6.
-    Every other problem has an odd d; every dup_every-th problem is one row repeated."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for p in range(count):
-        n = int(rng.integers(n_lo, n_hi + 1))
-        L = int(rng.integers(0, 201))
-        if (1000 + L) % 2 != p % 2:
-            L = L + 1 if L < 200 else L - 1
-        d = 1000 + L
-        dense = np.abs(rng.standard_normal((1, 1000))).astype(np.float32) + 0.3 * rng.standard_normal((n, 1000)).astype(np.float32)
-        lab = np.zeros((n, L), np.float32)
-        if L:
-            lab[np.arange(n), rng.integers(0, L, n)] = 1.0
-        E = np.concatenate([dense, lab], axis=1).astype(np.float32)
-        if dup_every and p % dup_every == dup_every - 1:
-            E[:] = E[0]
-        out.append((np.ascontiguousarray(E), 3, 6))
-    return out
-
-
-def same_as_oracle(r, ref, what):
-    cid, rank, nc, st, log = r
-    if not ref["ok"]:
-        from imageclust_amd import _lib
-
-        assert st == _lib.ICL_ERR_CONSTRAINT, what
-        assert (cid == -1).all() and (rank == -1).all() and nc == 0 and len(log) == 0, what
-        return
-    assert st == 0, what
-    assert np.array_equal(cid, ref["cluster_id"]) and np.array_equal(rank, ref["member_rank"]) and nc == ref["n_clusters"], what
-    assert np.array_equal(log, ref["log"][:, 2:4].astype(np.int32)), what
-
-
 def test_every_small_case_in_one_call(ctx):
-    from imageclust_amd import _lib
-
     cases = WC.small_cases()
     res = ctx.cluster_many([(E, mn, mx) for _, E, mn, mx in cases], want_merges=True)
     assert len(res) == len(cases)
     for (name, E, mn, mx), r in zip(cases, res):
         same_as_oracle(r, O.cluster(E, mn, mx, want_log=True), name)
-        try:
-            cid, rank, nc = ctx.cluster(E, mn, mx)
-        except _lib.ICLError as e:
-            assert e.code == r[3], name
-            continue
-        assert np.array_equal(cid, r[0]) and np.array_equal(rank, r[1]) and nc == r[2], name
-        assert np.array_equal(ctx.last_merges(), r[4]), name
+        same_as_cluster(ctx, (E, mn, mx), r, name)
 
 
 def test_reference_shape_2000_problems(ctx):
     probs = serving_problems(2000, 20261016, dup_every=50)
     res = ctx.cluster_many(probs, want_merges=True)
-    with ThreadPoolExecutor(16) as ex:  # (the oracle's C call releases the GIL)
-        refs = list(ex.map(lambda pr: O.cluster_fast(pr[0], pr[1], pr[2], want_log=True), probs))
-    for p, (pr, r, ref) in enumerate(zip(probs, res, refs)):
+    for p, (pr, r, ref) in enumerate(zip(probs, res, oracles(probs))):
         same_as_oracle(r, ref, "problem %d (n %d, d %d)" % (p, pr[0].shape[0], pr[0].shape[1]))
 
 
@@ -92,16 +47,13 @@ def test_result_does_not_depend_on_the_batch(ctx):
     perm = np.random.default_rng(1).permutation(len(probs))
     shuf = ctx.cluster_many([probs[i] for i in perm], want_merges=True)
     for j, i in enumerate(perm):
-        for a, b in zip(base[i], shuf[j]):
-            assert np.array_equal(a, b), i
+        same_results(base[i], shuf[j], i)
     for i in range(0, len(probs), 5):
         alone = ctx.cluster_many([probs[i]], want_merges=True)[0]
-        for a, b in zip(base[i], alone):
-            assert np.array_equal(a, b), i
+        same_results(base[i], alone, i)
     copies = ctx.cluster_many([probs[3]] * 1000, want_merges=True)
     for r in copies:
-        for a, b in zip(base[3], r):
-            assert np.array_equal(a, b)
+        same_results(base[3], r, "copies")
 
 
 def test_failed_problems_and_bad_arguments(ctx):
@@ -150,9 +102,8 @@ def test_mixed_routes(ctx):
     probs.insert(123, (big, 3, 6))
     res = ctx.cluster_many(probs, want_merges=True)
     for p, (pr, r) in enumerate(zip(probs, res)):
-        cid, rank, nc = ctx.cluster(pr[0], pr[1], pr[2])
-        assert r[3] == 0 and np.array_equal(cid, r[0]) and np.array_equal(rank, r[1]) and nc == r[2], p
-        assert np.array_equal(ctx.last_merges(), r[4]), p
+        assert r[3] == 0, p
+        same_as_cluster(ctx, pr, r, p)
 
 
 def test_dev_equals_host_and_last_merges_unchanged(ctx):
@@ -170,20 +121,13 @@ def test_dev_equals_host_and_last_merges_unchanged(ctx):
     finally:
         ctx.free(dE)
     for p, (a, b) in enumerate(zip(host, dev)):
-        for x, y in zip(a, b):
-            assert np.array_equal(x, y), p
+        same_results(a, b, p)
 
     E1 = WC.mog(90, 16, 4)
     ctx.cluster(E1, 3, 6)
-    before, vals = ctx.last_merges(), ctx.last_merge_values()
-    stats = (C.c_int64 * 4)()
-    L = ctx.L
-    L.icl_last_ward_stats(ctx.h, C.byref(stats, 0), C.byref(stats, 8), C.byref(stats, 16), C.byref(stats, 24))
-    s0 = list(stats)
+    before = ward_reports(ctx)
     ctx.cluster_many(probs)
-    assert np.array_equal(ctx.last_merges(), before) and np.array_equal(ctx.last_merge_values(), vals)
-    L.icl_last_ward_stats(ctx.h, C.byref(stats, 0), C.byref(stats, 8), C.byref(stats, 16), C.byref(stats, 24))
-    assert list(stats) == s0
+    same_reports(ward_reports(ctx), before)
 
 
 def test_python_api_many_equals_single(ctx):
@@ -199,23 +143,15 @@ def test_python_api_many_equals_single(ctx):
 
 
 _CHILD = """
-import numpy as np
 from imageclust_amd import _lib
 from oracle import oracle as O
 from tests import ward_cases as WC
+from tests.many_cases import not_as_oracle
 ctx = _lib.Context(0)
 cases = WC.small_cases()
-res = ctx.cluster_many([(E, mn, mx) for _, E, mn, mx in cases], want_merges=True)
-bad = []
-for (name, E, mn, mx), (cid, rank, nc, st, log) in zip(cases, res):
-    ref = O.cluster(E, mn, mx, want_log=True)
-    if not ref["ok"]:
-        ok = st == _lib.ICL_ERR_CONSTRAINT and (cid == -1).all() and nc == 0
-    else:
-        ok = (st == 0 and np.array_equal(cid, ref["cluster_id"]) and np.array_equal(rank, ref["member_rank"]) and nc == ref["n_clusters"]
-              and np.array_equal(log, ref["log"][:, 2:4].astype(np.int32)))
-    if not ok:
-        bad.append(name)
+probs = [(E, mn, mx) for _, E, mn, mx in cases]
+res = ctx.cluster_many(probs, want_merges=True)
+bad = not_as_oracle(probs, res, [O.cluster(E, mn, mx, want_log=True) for E, mn, mx in probs], [c[0] for c in cases])
 ctx.close()
 print("BAD", bad)
 """

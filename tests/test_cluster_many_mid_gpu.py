@@ -1,18 +1,15 @@
 """The mid-size route of icl_cluster_many (ward_many.hip: problems of 257 to 2048 rows, one workgroup each, run in groups under a
 workspace budget; icl_set_many_options).  Bar: that of test_cluster_many_gpu.py -- every problem's cluster ids, member ranks,
 cluster count, status and merge log equal oracle.cluster_fast's, BIT-EXACT, and icl_cluster's on the problem alone."""
-import ctypes as C
 import os
 import subprocess
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from oracle import oracle as O
 from tests import ward_cases as WC
-from tests.test_cluster_many_gpu import same_as_oracle, serving_problems
+from tests.many_cases import oracles, same_as_cluster, same_as_oracle, same_reports, same_results, serving_problems, ward_reports
 
 pytestmark = pytest.mark.gpu
 
@@ -33,28 +30,6 @@ def mid_on(ctx):
     ctx.set_many_options(_lib.MANY_MID_ON)
     yield ctx
     ctx.set_many_options(_lib.MANY_MID_AUTO)
-
-
-def oracles(probs):
-    with ThreadPoolExecutor(16) as ex:  # (the oracle's C call releases the GIL)
-        return list(ex.map(lambda pr: O.cluster_fast(pr[0], pr[1], pr[2], want_log=True), probs))
-
-
-def same_as_cluster(ctx, pr, r, what):
-    from imageclust_amd import _lib
-
-    try:
-        cid, rank, nc = ctx.cluster(pr[0], pr[1], pr[2])
-    except _lib.ICLError as e:
-        assert e.code == r[3], what
-        return
-    assert r[3] == 0 and np.array_equal(cid, r[0]) and np.array_equal(rank, r[1]) and nc == r[2], what
-    assert np.array_equal(ctx.last_merges(), r[4]), what
-
-
-def same_results(a, b, what):
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y), what
 
 
 def test_reference_shape_200_mid_problems(mid_on):
@@ -192,16 +167,10 @@ def test_dev_equals_host_and_last_merges_unchanged(mid_on):
 
     E1 = WC.mog(90, 16, 4)
     ctx.cluster(E1, 3, 6)
-    before, vals = ctx.last_merges(), ctx.last_merge_values()
-    stats = (C.c_int64 * 4)()
-    L = ctx.L
-    L.icl_last_ward_stats(ctx.h, C.byref(stats, 0), C.byref(stats, 8), C.byref(stats, 16), C.byref(stats, 24))
-    s0 = list(stats)
+    before = ward_reports(ctx)
     ctx.cluster_many(probs)
     assert ctx.last_many_stats()["mid"] == 13
-    assert np.array_equal(ctx.last_merges(), before) and np.array_equal(ctx.last_merge_values(), vals)
-    L.icl_last_ward_stats(ctx.h, C.byref(stats, 0), C.byref(stats, 8), C.byref(stats, 16), C.byref(stats, 24))
-    assert list(stats) == s0
+    same_reports(ward_reports(ctx), before)
 
 
 def test_python_api_many_takes_the_route(mid_on):
@@ -225,24 +194,15 @@ def test_set_many_options_rejects_unknown_modes(ctx):
 
 
 _CHILD = """
-import numpy as np
-from concurrent.futures import ThreadPoolExecutor
 from imageclust_amd import _lib
-from oracle import oracle as O
-from tests.test_cluster_many_gpu import serving_problems
+from tests.many_cases import not_as_oracle, oracles, serving_problems
 ctx = _lib.Context(0)
 assert ctx.last_many_stats() == {"small": 0, "mid": 0, "large": 0, "mid_groups": 0}
 probs = serving_problems(24, 26, n_lo=1500, n_hi=1500)
 res = ctx.cluster_many(probs, want_merges=True)   # (ICL_MANY_MID=on: the context's default)
 stats = ctx.last_many_stats()
-with ThreadPoolExecutor(16) as ex:
-    refs = list(ex.map(lambda pr: O.cluster_fast(pr[0], pr[1], pr[2], want_log=True), probs))
-bad = []
-for p, ((cid, rank, nc, st, log), ref) in enumerate(zip(res, refs)):
-    ok = (ref["ok"] and st == 0 and np.array_equal(cid, ref["cluster_id"]) and np.array_equal(rank, ref["member_rank"]) and nc == ref["n_clusters"]
-          and np.array_equal(log, ref["log"][:, 2:4].astype(np.int32)))
-    if not ok:
-        bad.append(p)
+refs = oracles(probs)
+bad = not_as_oracle(probs, res, refs) + [p for p, ref in enumerate(refs) if not ref["ok"]]
 ctx.close()
 print("BAD", bad)
 print("STATS", stats["mid"], stats["mid_groups"])
