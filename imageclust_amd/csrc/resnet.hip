@@ -1440,13 +1440,13 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
         unsigned long long h[16];
         (void)hipStreamSynchronize(strm);
         (void)hipMemcpy(h, dbg, sizeof h, hipMemcpyDeviceToHost);
-        const char *fn[8] = {"carry+conv1", "wait E", "dma+t1 epi", "wait C", "conv2+t2 epi", "wait x", "wait D", ""};
-        const char *bn[8] = {"t2 reads + side wait", "ST reads + t2 MFMAs", "DMA issue", "side MFMAs + epilogue", "read-back + stores", "barrier waits", "", ""};
-        const int nsteps = ((B / a.ngroups) * (a.H + 1) + 7) / 8;
+        const char *fn[8] = BN56_FRONT_SEGMENTS;
+        const char *bn[8] = BN56_BACK_SEGMENTS;
+        const int nsteps = ((B / a.ngroups) * (a.H + 1) + BN56_ROWS - 1) / BN56_ROWS;
         fprintf(stderr, "[bn56 %s] cycles per step (steps %d):\n  front:", ds ? "ds" : "id", nsteps);
-        for (int k = 0; k < 7; ++k) fprintf(stderr, " %s %.0f |", fn[k], (double)h[k] / nsteps);
+        for (int k = 0; k < 8 && fn[k][0]; ++k) fprintf(stderr, " %s %.0f |", fn[k], (double)h[k] / nsteps);
         fprintf(stderr, "\n  back :");
-        for (int k = 0; k < 7; ++k) fprintf(stderr, " %s %.0f |", bn[k], (double)h[8 + k] / nsteps);
+        for (int k = 0; k < 8 && bn[k][0]; ++k) fprintf(stderr, " %s %.0f |", bn[k], (double)h[8 + k] / nsteps);
         fprintf(stderr, "\n");
     }
 #endif

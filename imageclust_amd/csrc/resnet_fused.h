@@ -488,20 +488,37 @@ __global__ __launch_bounds__(256) void stem2_pool_kernel(const uint8_t *__restri
 //       back  waves 4..7 (W3: rows 64b .. 64b+63):     conv3 + residual / downsample + ReLU + stores of step j-1
 //     so on each SIMD an MFMA-heavy wave runs beside an epilogue-heavy one (alone on its SIMD a wave is bound by instruction issue:
 //     ~10 vector / scalar instructions per 16-cycle MFMA; measured 13.7 us per step for the one-wave-per-SIMD form of this kernel).
-//   * A workgroup owns a strip of 14 output columns of a run of images and walks it top to bottom in steps of 8 rows.  The
-//     images of a run are stacked with ONE zero row between them (a "virtual" row index v: image v / (H+1), row v % (H+1),
-//     row H = padding), so the walk never restarts: step j brings the x tile of virtual rows S+8j .. S+8j+7 (16 columns:
-//     the strip + one halo column each side) in by LDS-DMA, conv1 turns it into 8 new rows of t1 behind the two rows kept
+//   * A workgroup owns a strip of 14 output columns of a run of images and walks it top to bottom in steps of BN56_ROWS = 4 rows.
+//     The images of a run are stacked with ONE zero row between them (a "virtual" row index v: image v / (H+1), row v % (H+1),
+//     row H = padding), so the walk never restarts: step j brings the x tile of virtual rows S+4j .. S+4j+3 (16 columns:
+//     the strip + one halo column each side) in by LDS-DMA, conv1 turns it into 4 new rows of t1 behind the two rows kept
 //     from the previous step (no halo recompute along y, 16/14 along x), conv2 produces t2 for the virtual rows
-//     S+8j-1 .. S+8j+6 from the 10 t1 rows, conv3 (+ residual from L2 / + downsample operand straight from global memory into
-//     the B fragments) writes y.  t1 and t2 never leave the CU; HBM sees x once and y once.
-//   * The x tile of step j+1 is requested as soon as conv1 of step j has consumed the buffer and lands behind conv2.
+//     S+4j-1 .. S+4j+2 from the 6 t1 rows, conv3 (+ residual / + downsample operand, both B fragments read from the x tiles in
+//     LDS) writes y.  t1 and t2 never leave the CU; every byte of x is read from global memory ONCE, by the front waves' DMA.
 //   * Three workgroup barriers per step (D: t2 / x tile complete, E: conv1 has read the x tile and the kept t1 rows are moved,
-//     C: t1 written); the back waves join them between the halves of their work.
-//   k order per output element: channels ascending for the 1x1s, (row, kw, channel) for the 3x3, [t2 | x] for DS: fixed,
-//   so results do not depend on the batch or on the strip decomposition.
+//     C: t1 written); the back waves work on one half of their step (a "quarter": 2 rows) between D and E and on the other
+//     between C and D.
+//   * The x tiles form a RING OF THREE slots (tile j lives in slot j % 3), because the back waves need x one step after conv1:
+//     the outputs of step j-1 are the virtual rows S+4(j-1)-1 .. S+4(j-1)+2 = row 3 of tile j-2 and rows 0..2 of tile j-1.
+//     Iteration j, in barrier order  D(j-1) | E(j) | C(j) | D(j):
+//         front   conv1 reads tile j          | DMA of tile j+1 issued, t1 written | conv2, vmcnt(0)  |
+//         back    quarter 1: tile j-2 row 3,  |                                    | quarter 2: tile  |
+//                 tile j-1 row 0              |                                    | j-1 rows 1, 2    |
+//     Slot (j+1) % 3 == (j-2) % 3, written by the DMA behind E(j):
+//       WAR  its last reader is the back waves' quarter 1 of iteration j (tile j-2, row 3).  Those ds_reads retire before the
+//            back wave arrives at E(j) (bn56_barrier waits for lgkmcnt(0)), and no DMA is issued before every wave has arrived.
+//            (conv1 read tile j-2 two steps ago; quarter 1 / 2 of iteration j-1 read its rows 0..2 before D(j-1).)
+//       RAW  every front wave waits for vmcnt(0) -- its own pieces -- before it arrives at D(j); the first readers of tile j+1
+//            (conv1 of step j+1, quarter 1 of iteration j+2) run behind D(j) / D(j+1).
+//     Slot (j-1) % 3 and slot j % 3 are only read in iteration j: the next write to slot (j-1) % 3 is tile j+2, issued behind
+//     E(j+1), i.e. after D(j), which quarter 2 of iteration j precedes; the next write to slot j % 3 is tile j+3.
+//     Nothing is carried in registers across a barrier and no wait is counted: the back waves issue no loads from global memory.
+//     (Iteration 1 reads "tile -1" from slot 2, which nothing has written: that row is the padding row above the run, never stored.
+//     Whatever LDS held there, NaN patterns included, stays in that row: a B column of the MFMA is one pixel, and columns do not mix.)
+//   k order per output element: channels ascending for the 1x1s, (row, kw, channel) for the 3x3, [t2 | x] for conv3: fixed,
+//   so results do not depend on the batch, on the strip decomposition or on the step height.
 // ------------------------------------------------------------------------------------------------------------
-// in-kernel segment timers for tuning (a separate diagnostic build: -DBN56_TIMERS; scratch/bn56_timers.py prints them)
+// in-kernel segment timers for tuning (a separate diagnostic build: -DBN56_TIMERS; launch_bneck56 prints them when BN56_PRINT is set)
 #ifdef BN56_TIMERS
 #define BN56_STAMP(k)                                                                              \
     do {                                                                                           \
@@ -517,6 +534,9 @@ __global__ __launch_bounds__(256) void stem2_pool_kernel(const uint8_t *__restri
 #define BN56_TIMER_FLUSH(role)                                                                     \
     if (p.dbg && blockIdx.x == 0 && w == 0 && lane == 0)                                            \
         for (int k__ = 0; k__ < 8; ++k__) p.dbg[(role)*8 + k__] = tacc[k__]
+// segment names, in stamp order (launch_bneck56 prints them)
+#define BN56_FRONT_SEGMENTS {"carry+conv1", "wait E", "dma+t1 epi", "wait C", "conv2+t2 epi", "wait x", "wait D", ""}
+#define BN56_BACK_SEGMENTS {"t2 + side reads", "MFMAs + epilogue", "read-back + stores", "barrier waits", "", "", "", ""}
 #else
 #define BN56_STAMP(k)
 #define BN56_TIMER_DECL
@@ -538,18 +558,22 @@ struct bneck_args {
 #endif
 };
 
-#define BN56_COLS 14                         /* output columns per strip */
-#define BN56_T1_BYTES (11 * 16 * 128)        /* 10 rows of t1 (2 kept + 8 new) + 1 row of slack for the garbage columns' taps */
-#define BN56_T2_BYTES (128 * 128)
+#define BN56_COLS 14                                 /* output columns per strip */
+#define BN56_ROWS 4                                  /* virtual rows per step: one x tile, 4 new t1 rows, 4 t2 rows, two quarters of output */
+#define BN56_ROW_BYTES (16 * 128)                    /* one tile row: 16 pixels x 64 channels */
+#define BN56_XCH_BYTES (BN56_ROWS * BN56_ROW_BYTES)  /* one 64-channel chunk of an x tile */
+#define BN56_T1_BYTES ((2 + BN56_ROWS + 1) * BN56_ROW_BYTES) /* t1: 2 kept rows + the new ones + 1 row of slack for the garbage columns' taps */
+#define BN56_T2_BYTES (BN56_ROWS * BN56_ROW_BYTES)
+#define BN56_OT_BYTES (2 * BN56_ROW_BYTES)           /* a back wave's output tile: one quarter = 2 rows of its 64 channels */
 
 template <bool DS>
 static constexpr size_t bneck56_lds_bytes()
 {
-    return (size_t)(DS ? 1 : 4) * 128 * 128 + BN56_T1_BYTES + 2 * BN56_T2_BYTES + 4 * 8192; // x tile, t1, t2[2], the back waves' side / output tiles
+    return (size_t)3 * (DS ? 1 : 4) * BN56_XCH_BYTES + BN56_T1_BYTES + 2 * BN56_T2_BYTES + 4 * BN56_OT_BYTES; // ring of 3 x tiles, t1, t2[2], the back waves' output tiles
 }
 
 // workgroup barrier that waits for this wave's LDS traffic only (the front waves' LDS-DMA stays in flight across it; their own
-// counted wait covers it before the barrier that publishes the tile)
+// vmcnt(0) covers it before the barrier that publishes the tile)
 __device__ __forceinline__ void bn56_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // (image, row) of a virtual row cursor, advanced without divisions (VH = H + 1 rows per image, row H = padding)
 struct bn56_row {
@@ -568,13 +592,16 @@ struct bn56_row {
 template <bool DS>
 __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
 {
+    static_assert(BN56_ROWS == 4, "the quarters below are rows {-1, 0} and {1, 2} of a 4-row step");
     constexpr int CIN = DS ? 64 : 256;
     constexpr int NCH = CIN / 64;       // 64-channel chunks of x
     constexpr int K3 = DS ? 128 : 64;   // conv3's K: [t2 | x] or t2
+    constexpr int RB = BN56_ROW_BYTES;
+    constexpr unsigned SLOT = NCH * BN56_XCH_BYTES; // one x tile
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *XT = smem;                       // [NCH][128 pixels][128 B], swizzled
-    unsigned char *T1 = smem + NCH * 16384;         // [11 rows][16 columns][128 B], swizzled
-    unsigned char *T2 = T1 + BN56_T1_BYTES;         // [2][128 pixels][128 B], swizzled
+    unsigned char *XT = smem;                       // [3 slots][NCH][64 pixels][128 B], swizzled
+    unsigned char *T1 = smem + 3 * SLOT;            // [7 rows][16 columns][128 B], swizzled
+    unsigned char *T2 = T1 + BN56_T1_BYTES;         // [2][64 pixels][128 B], swizzled
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = wid & 3;
@@ -582,9 +609,9 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
     const int H = p.H, Wd = p.W, VH = H + 1;
     const int strip = (int)blockIdx.x % p.nstrips, grp = (int)blockIdx.x / p.nstrips;
     const int b0 = (int)(((int64_t)grp * p.B) / p.ngroups), b1 = (int)(((int64_t)(grp + 1) * p.B) / p.ngroups);
-    if (b0 >= b1) return;
+    if (b0 >= b1) return; // (workgroup-uniform: no wave of this workgroup reaches a barrier)
     const int c0 = strip * BN56_COLS;
-    const int nsteps = ((b1 - b0) * VH + 7) / 8;
+    const int nsteps = ((b1 - b0) * VH + BN56_ROWS - 1) / BN56_ROWS;
     // B-fragment reads: pixel px = 16 * row + column; (px >> 1) & 7 depends on the column only, so a lane's swizzled byte
     // offset inside a pixel row is fixed and every (row, chunk) is an immediate offset
     const int swc = (r16 >> 1) & 7;
@@ -613,9 +640,9 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
         // t1 / t2 stores: this lane's 4 channels 16w + 4q .. of pixel (row, r16): 8 bytes in slot 2w + (q >> 1)
         const unsigned toff = (unsigned)(r16 * 128 + ((((2 * w + (q >> 1)) ^ swc) & 7) << 4) + 8 * (q & 1));
         const bool col_in = (unsigned)(c0 - 1 + r16) < (unsigned)Wd; // t1 column of this lane inside the image
-        // LDS-DMA roles: wave w fills the tile rows 2w, 2w+1 (pieces of 8 pixels x 128 B): piece i of a row = columns 8i ..
+        // LDS-DMA roles: wave w fills the tile row w (pieces of 8 pixels x 128 B): piece i of a row = columns 8i ..
         const int dcol = lane >> 3, dps = lane & 7;
-        const unsigned xt_wave = __builtin_amdgcn_readfirstlane(lds_addr_of(smem) + (unsigned)w * 4096u);
+        const unsigned xt_wave = __builtin_amdgcn_readfirstlane(lds_addr_of(smem) + (unsigned)w * (unsigned)RB);
         const i32x4_t xsrd = bn56_srd(p.X, (unsigned)((size_t)p.B * H * Wd * CIN * 2));
         const unsigned xrow_bytes = (unsigned)(Wd * CIN * 2);
         unsigned dvoff[2]; // byte offset of this lane's source chunk inside an image row (channel chunk 0), or out of range: column outside the image
@@ -624,89 +651,87 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
             const int c = 8 * i + dcol, col = c0 - 1 + c;
             dvoff[i] = (unsigned)col < (unsigned)Wd ? (unsigned)(col * CIN + ((dps ^ (c >> 1)) & 7) * 8) * 2u : BN56_OOB;
         }
-        auto stage_x = [&](bn56_row t) { // the tile rows 2w, 2w+1 of the x tile whose row 2w is the virtual row t
+        auto stage_x = [&](const bn56_row &t, unsigned slot) { // the tile row w of the x tile at byte offset `slot`; t = its virtual row
+            const bool rok = t.b < b1 && t.r < H;
+            const unsigned soff = rok ? (unsigned)t.p * xrow_bytes : 0u;
 #pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const bool rok = t.b < b1 && t.r < H;
-                const unsigned soff = rok ? (unsigned)t.p * xrow_bytes : 0u;
+            for (int i = 0; i < 2; ++i) {
+                const unsigned vo = rok ? dvoff[i] : BN56_OOB;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const unsigned vo = rok ? dvoff[i] : BN56_OOB;
-#pragma unroll
-                    for (int ch = 0; ch < NCH; ++ch) bload_lds16_asm(xsrd, vo, soff + (unsigned)(128 * ch), xt_wave + (unsigned)(ch * 16384 + (2 * rr + i) * 1024));
-                }
-                t.step(VH);
+                for (int ch = 0; ch < NCH; ++ch) bload_lds16_asm(xsrd, vo, soff + (unsigned)(128 * ch), xt_wave + slot + (unsigned)(ch * BN56_XCH_BYTES + i * 1024));
             }
         };
-        bn56_row cur{b0, 0, b0 * H}; // virtual row S + 8j: the first new t1 row of step j
-        bn56_row dma = cur;          // ... + 2w: this wave's first DMA row
-        for (int i = 0; i < 2 * w; ++i) dma.step(VH);
+        bn56_row cur{b0, 0, b0 * H}; // virtual row S + 4j: the first new t1 row of step j
+        bn56_row dma = cur;          // ... + w: this wave's DMA row
+        for (int i = 0; i < w; ++i) dma.step(VH);
         reinterpret_cast<uint4 *>(T1)[tid] = make_uint4(0, 0, 0, 0); // the two kept t1 rows of step 0: padding
-        stage_x(dma);
+        stage_x(dma, 0u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         bn56_barrier(); // D
+        unsigned xs = 0u; // byte offset of slot j % 3
         BN56_TIMER_DECL;
         BN56_TIMER_START;
 #pragma unroll 1
         for (int j = 0; j < nsteps; ++j) {
-            // ---- conv1: t1[rows 2..9] = relu(W1' . x + shift1).  The 8 B fragments of the next k-step are requested before the
+            // ---- conv1: t1[rows 2..5] = relu(W1' . x + shift1).  The 4 B fragments of the k-step after next are requested before the
             // MFMAs of this one (alone, hipcc keeps two fragments in flight and every MFMA group waits out an LDS round trip)
-            f32x4 a1[8];
+            f32x4 a1[BN56_ROWS];
             {
-                // units of 4 fragments (one k-step, four tile rows), requested two units ahead of their MFMAs
-                constexpr int NU = NCH * 4;
+                // units of 4 fragments (one k-step, the four tile rows), requested two units ahead of their MFMAs
+                constexpr int NU = NCH * 2;
+                const unsigned char *Xc = XT + xs;
                 uint4 f[3][4];
-                auto ld = [&](int u, uint4 (&d)[4]) {
-                    const int kk = u >> 1, m0 = 4 * (u & 1);
+                auto ld = [&](int kk, uint4 (&d)[4]) {
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) d[m] = *reinterpret_cast<const uint4 *>(XT + (kk >> 1) * 16384 + (m0 + m) * 2048 + xoff[kk & 1]);
+                    for (int m = 0; m < 4; ++m) d[m] = *reinterpret_cast<const uint4 *>(Xc + (kk >> 1) * BN56_XCH_BYTES + m * RB + xoff[kk & 1]);
                 };
                 ld(0, f[0]);
                 ld(1, f[1]);
 #pragma unroll
-                for (int u = 0; u < NU; ++u) {
-                    if (u + 2 < NU) ld(u + 2, f[(u + 2) % 3]);
+                for (int kk = 0; kk < NU; ++kk) {
+                    if (kk + 2 < NU) ld(kk + 2, f[(kk + 2) % 3]);
                     __builtin_amdgcn_sched_barrier(0);
-                    const int kk = u >> 1, m0 = 4 * (u & 1);
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) a1[m0 + m] = mfma16(w1r[kk], f[u % 3][m], kk == 0 ? h1 : a1[m0 + m]);
+                    for (int m = 0; m < 4; ++m) a1[m] = mfma16(w1r[kk], f[kk % 3][m], kk == 0 ? h1 : a1[m]);
                 }
             }
             BN56_STAMP(0); // conv1
-            bn56_barrier(); // E: every front wave has read the x tile; the kept rows are in place
+            bn56_barrier(); // E: every front wave has read x tile j, every back wave row 3 of tile j-2; the kept rows are in place
             BN56_STAMP(1); // wait at E
-            for (int i = 0; i < 8; ++i) dma.step(VH);
-            if (j + 1 < nsteps) stage_x(dma);
+            for (int i = 0; i < BN56_ROWS; ++i) dma.step(VH);
+            const unsigned xn = xs + SLOT == 3 * SLOT ? 0u : xs + SLOT; // slot (j + 1) % 3: tile j-2 until now
+            if (j + 1 < nsteps) stage_x(dma, xn);
             {
                 bn56_row t = cur;
 #pragma unroll
-                for (int m = 0; m < 8; ++m) {
+                for (int m = 0; m < BN56_ROWS; ++m) {
                     const bool ok = t.b < b1 && t.r < H && col_in; // conv2 pads t1 with zeros, not with relu(shift1)
                     uint2 o;
                     o.x = ok ? pack_relu_bf16x2(a1[m][0], a1[m][1]) : 0u;
                     o.y = ok ? pack_relu_bf16x2(a1[m][2], a1[m][3]) : 0u;
-                    *reinterpret_cast<uint2 *>(T1 + (2 + m) * 2048 + toff) = o;
+                    *reinterpret_cast<uint2 *>(T1 + (2 + m) * RB + toff) = o;
                     t.step(VH);
                 }
                 cur = t;
             }
             BN56_STAMP(2); // DMA issue + t1 epilogue
-            bn56_barrier(); // C: t1 rows 2..9 are written
+            bn56_barrier(); // C: t1 rows 2..5 are written
             BN56_STAMP(3); // wait at C
             // ---- conv2: t2 = relu(W2' * t1 + shift2): every t1 fragment (row R, kw, k half) is read once and feeds the taps kh = R - m;
-            // the 6 fragments of row R + 1 are requested before the MFMAs of row R
-            f32x4 a2[8];
+            // the 3 fragments of the next unit are requested before the MFMAs of this one
+            f32x4 a2[BN56_ROWS];
             {
                 // units of 3 fragments (t1 row R, k half ks, kw = 0..2: up to 9 MFMAs), requested one unit ahead
+                constexpr int NU = 2 * (BN56_ROWS + 2);
                 uint4 f[2][3];
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) f[0][kw] = *reinterpret_cast<const uint4 *>(T1 + t1off[kw][0]);
 #pragma unroll
-                for (int u = 0; u < 20; ++u) {
+                for (int u = 0; u < NU; ++u) {
                     const int R = u >> 1, ks = u & 1;
-                    if (u + 1 < 20) {
+                    if (u + 1 < NU) {
 #pragma unroll
-                        for (int kw = 0; kw < 3; ++kw) f[(u + 1) & 1][kw] = *reinterpret_cast<const uint4 *>(T1 + ((u + 1) >> 1) * 2048 + t1off[kw][(u + 1) & 1]);
+                        for (int kw = 0; kw < 3; ++kw) f[(u + 1) & 1][kw] = *reinterpret_cast<const uint4 *>(T1 + ((u + 1) >> 1) * RB + t1off[kw][(u + 1) & 1]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -714,26 +739,27 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
 #pragma unroll
                         for (int kh = 0; kh < 3; ++kh) {
                             const int m = R - kh;
-                            if (m >= 0 && m < 8) a2[m] = mfma16(w2r[(kh * 3 + kw) * 2 + ks], f[u & 1][kw], (kh == 0 && kw == 0 && ks == 0) ? h2 : a2[m]);
+                            if (m >= 0 && m < BN56_ROWS) a2[m] = mfma16(w2r[(kh * 3 + kw) * 2 + ks], f[u & 1][kw], (kh == 0 && kw == 0 && ks == 0) ? h2 : a2[m]);
                         }
                 }
             }
             unsigned char *T2w = T2 + (j & 1) * BN56_T2_BYTES;
 #pragma unroll
-            for (int m = 0; m < 8; ++m) {
+            for (int m = 0; m < BN56_ROWS; ++m) {
                 uint2 o;
                 o.x = pack_relu_bf16x2(a2[m][0], a2[m][1]);
                 o.y = pack_relu_bf16x2(a2[m][2], a2[m][3]);
-                *reinterpret_cast<uint2 *>(T2w + m * 2048 + toff) = o;
+                *reinterpret_cast<uint2 *>(T2w + m * RB + toff) = o;
             }
             BN56_STAMP(4); // conv2 + t2 epilogue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's pieces of the next x tile have landed
             BN56_STAMP(5); // wait for the x tile
-            bn56_barrier(); // D: t2[j & 1] and the next x tile are complete; every front wave has read t1
+            bn56_barrier(); // D: t2[j & 1] and x tile j+1 are complete; every front wave has read t1
             BN56_STAMP(6); // wait at D
-            // keep the last two t1 rows for the next step (rows 8, 9 -> 0, 1: same swizzle, the pixel index moves by 128); the next
+            // keep the last two t1 rows for the next step (rows 4, 5 -> 0, 1: same swizzle, the pixel index moves by 64); the next
             // step's t1 rows are written behind its barrier E
-            reinterpret_cast<uint4 *>(T1)[tid] = reinterpret_cast<const uint4 *>(T1 + 16384)[tid];
+            reinterpret_cast<uint4 *>(T1)[tid] = reinterpret_cast<const uint4 *>(T1 + BN56_ROWS * RB)[tid];
+            xs = xn;
         }
         BN56_TIMER_FLUSH(0);
         // the back waves still work on the last step: join its two barriers (E, C)
@@ -741,14 +767,23 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
         bn56_barrier();
     } else {
         // =========================================== back waves: conv3 + residual / downsample + ReLU + stores ===========================================
-        // A wave works on QUARTERS of a step's tile (2 rows = 32 pixels) through two wave-private LDS tiles of [32 pixels][128 B]:
-        //   ST  the operand that comes from global memory for those pixels -- identity: the residual x[pixel][64w .. 64w+63];
-        //       DS: x[pixel][0 .. 63], the downsample branch's B operand -- brought in by LDS-DMA (pieces of 8 pixels x 128 B:
-        //       every piece is 8 whole 128-byte lines), one quarter ahead.  Both enter the accumulator through the matrix core: DS
-        //       with the downsample weights, identity with a 0 / 1 selector as the A operand (x * 1.0 + acc in fp32 is the plain
-        //       fp32 add, and it costs one MFMA per 16 x 16 outputs instead of 2 vector instructions per output);
-        //   OT  the quarter's outputs, written in the accumulator layout (8 bytes per lane) and read back as 16-byte chunks with 8
-        //       consecutive lanes on one pixel's 128 bytes, so every global store instruction covers 8 whole lines.
+        // A wave works on QUARTERS of its 64 output channels (2 rows = 32 pixels).  Its operands are all in LDS:
+        //   t2       the quarter's two rows of t2[(j-1) & 1];
+        //   side     the operand from x for those pixels -- identity: the residual x[pixel][64w .. 64w+63], i.e. chunk w of the x
+        //            tile; DS: x[pixel][0 .. 63], the downsample branch's B operand, the tile's only chunk.  It is the B-fragment
+        //            shape conv1 reads, one column to the right: output pixel r16 is image column c0 + r16 = tile column r16 + 1
+        //            (the tile starts at the halo column c0 - 1), so the lane offsets carry the swizzle of column r16 + 1.  For
+        //            r16 = 15 that is "column 16", pixel 0 of the next tile row (or the bytes behind the tile): garbage, like
+        //            r16 = 14's halo column, in the two output columns that are never stored.  LDS banks: the 16 lanes of a
+        //            ds_read_b128 group are the columns 1 .. 16 at one logical chunk k: columns 2i, 2i+1 share the physical chunk
+        //            k ^ i and lie 128 B apart (the two halves of the 64 banks); columns 1 and 16 both have chunk k ^ 0, in the odd
+        //            and the even half (16 * 128 = 0 mod 256): 16 distinct 16-byte bank groups, conflict-free, as xoff's.
+        //            Both side operands enter the accumulator through the matrix core: DS with the downsample weights, identity
+        //            with a 0 / 1 selector as the A operand (x * 1.0 + acc in fp32 is the plain fp32 add, and it costs one MFMA
+        //            per 16 x 16 outputs instead of 2 vector instructions per output);
+        //   OT       (wave-private) the quarter's outputs, written in the accumulator layout (8 bytes per lane) and read back as
+        //            16-byte chunks with 8 consecutive lanes on one pixel's 128 bytes, so every global store instruction covers 8
+        //            whole lines.
         // (With the accumulator layout on the global side -- adjacent lanes on pixels 512 B apart, 8 bytes each -- the CU's
         // address path took 64 line look-ups per instruction and 6 000 cycles per step segment: stamped)
         constexpr int NW3 = DS ? 4 : 2; // k-steps of conv3's weights per 16-channel group: [t2 | x] or t2
@@ -772,50 +807,42 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
             const float4 t = *reinterpret_cast<const float4 *>(p.sh3 + 64 * w + 16 * g + 4 * q);
             h3[g] = f32x4{t.x, t.y, t.z, t.w};
         }
-        unsigned char *ST = T2 + 2 * BN56_T2_BYTES + w * 8192, *OT = ST + 4096;
-        const unsigned st_lds = __builtin_amdgcn_readfirstlane(lds_addr_of(ST));
+        unsigned char *OT = T2 + 2 * BN56_T2_BYTES + w * BN56_OT_BYTES;
+        const unsigned char *XS = XT + (DS ? 0 : w) * BN56_XCH_BYTES; // this wave's chunk of slot 0
+        unsigned soff[2]; // side fragment: tile column r16 + 1
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) soff[ks] = (unsigned)((r16 + 1) * 128 + ((((4 * ks + q) ^ ((r16 + 1) >> 1)) & 7) << 4));
         // accumulator-layout offsets inside a quarter tile: pixel (mm, r16), this lane's 4 channels 16g + 4q ..
         unsigned aoff[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) aoff[g] = (unsigned)(r16 * 128 + ((((2 * g + (q >> 1)) ^ swc) & 7) << 4) + 8 * (q & 1));
-        // line-layout roles (DMA pieces and the output read-back): lane -> pixel column 8i + (lane >> 3), physical 16-byte slot lane & 7
+        // line-layout roles (the output read-back): lane -> pixel column 8i + (lane >> 3), physical 16-byte slot lane & 7
         const int lcol = lane >> 3, lps = lane & 7;
-        const i32x4_t xsrd = bn56_srd(p.X, (unsigned)((size_t)p.B * H * Wd * CIN * 2)), ysrd = bn56_srd(p.Y, (unsigned)((size_t)p.B * H * Wd * 256 * 2));
-        const unsigned xrow_bytes = (unsigned)(Wd * CIN * 2), yrow_bytes = (unsigned)(Wd * 256 * 2);
-        const unsigned xbase = (unsigned)((c0 * CIN + (DS ? 0 : 64 * w)) * 2), ybase = (unsigned)((c0 * 256 + 64 * w) * 2);
-        unsigned xvoff[2], yvoff[2]; // this lane's byte offsets from a row's first strip pixel: source chunk / destination chunk (out of range: no such output column)
+        const i32x4_t ysrd = bn56_srd(p.Y, (unsigned)((size_t)p.B * H * Wd * 256 * 2));
+        const unsigned yrow_bytes = (unsigned)(Wd * 256 * 2);
+        const unsigned ybase = (unsigned)((c0 * 256 + 64 * w) * 2);
+        unsigned yvoff[2]; // this lane's byte offsets from a row's first strip pixel (out of range: no such output column)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c = 8 * i + lcol, chunk = (lps ^ (c >> 1)) & 7;
             const bool ok = c < BN56_COLS && c0 + c < Wd;
-            xvoff[i] = ok ? (unsigned)(c * CIN + chunk * 8) * 2u : BN56_OOB;
             yvoff[i] = ok ? (unsigned)(c * 256 + chunk * 8) * 2u : BN56_OOB;
         }
         auto row_ok = [&](const bn56_row &t) { return t.b >= b0 && t.b < b1 && t.r < H; };
-        auto stage_side = [&](bn56_row t) { // the quarter whose first row is t -> ST (4 pieces)
-#pragma unroll
-            for (int mm = 0; mm < 2; ++mm) {
-                const bool rok = row_ok(t);
-                const unsigned soff = rok ? (unsigned)t.p * xrow_bytes + xbase : 0u;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) bload_lds16_asm(xsrd, rok ? xvoff[i] : BN56_OOB, soff, st_lds + (unsigned)((2 * mm + i) * 1024));
-                t.step(VH);
-            }
-        };
         BN56_TIMER_DECL;
-        auto quarter = [&](const unsigned char *T2q, bn56_row t0, bn56_row tnext) { // T2q: the quarter's two t2 rows
+        // T2q: the quarter's two t2 rows; S0, S1: the x-tile rows (this wave's chunk) of its two rows; t0: its first virtual row
+        auto quarter = [&](const unsigned char *T2q, const unsigned char *S0, const unsigned char *S1, bn56_row t0) {
             uint4 tb[2][2], xb[2][2];
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) tb[mm][ks] = *reinterpret_cast<const uint4 *>(T2q + mm * 2048 + xoff[ks]);
-            // the side operand of this quarter has landed once only the 4 stores of the previous quarter are younger
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            BN56_STAMP(0); // t2 fragment reads + wait for the side operand
+                for (int ks = 0; ks < 2; ++ks) tb[mm][ks] = *reinterpret_cast<const uint4 *>(T2q + mm * RB + xoff[ks]);
 #pragma unroll
-            for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) xb[mm][ks] = *reinterpret_cast<const uint4 *>(ST + mm * 2048 + xoff[ks]);
+            for (int ks = 0; ks < 2; ++ks) {
+                xb[0][ks] = *reinterpret_cast<const uint4 *>(S0 + soff[ks]);
+                xb[1][ks] = *reinterpret_cast<const uint4 *>(S1 + soff[ks]);
+            }
+            BN56_STAMP(0); // t2 + side fragment reads
             f32x4 a3[4][2];
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm)
@@ -824,11 +851,6 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
                     a3[g][mm] = mfma16(w3r[g * NW3 + 0], tb[mm][0], h3[g]); // shift: the chain's C operand
                     a3[g][mm] = mfma16(w3r[g * NW3 + 1], tb[mm][1], a3[g][mm]);
                 }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // ST is read: the next quarter's side operand may land
-            __builtin_amdgcn_sched_barrier(0);
-            BN56_STAMP(1); // ST reads + the t2 part's MFMAs
-            stage_side(tnext); // (rows beyond the run: every lane out of range, the instruction count stays exact)
-            BN56_STAMP(2); // DMA issue
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
@@ -847,56 +869,51 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
                     uint2 o;
                     o.x = pack_relu_bf16x2(a3[g][mm][0], a3[g][mm][1]);
                     o.y = pack_relu_bf16x2(a3[g][mm][2], a3[g][mm][3]);
-                    *reinterpret_cast<uint2 *>(OT + mm * 2048 + aoff[g]) = o;
+                    *reinterpret_cast<uint2 *>(OT + mm * RB + aoff[g]) = o;
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's OT writes are done (the tile is private to the wave)
             __builtin_amdgcn_sched_barrier(0);
-            BN56_STAMP(3); // side part's MFMAs + epilogue into OT
+            BN56_STAMP(1); // MFMAs + epilogue into OT
             bn56_row t = t0;
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm) {
                 const bool rok = row_ok(t);
-                const unsigned soff = rok ? (unsigned)t.p * yrow_bytes + ybase : 0u;
+                const unsigned so = rok ? (unsigned)t.p * yrow_bytes + ybase : 0u;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const uint4 v = *reinterpret_cast<const uint4 *>(OT + (2 * mm + i) * 1024 + lane * 16);
-                    bstore16_asm(ysrd, rok ? yvoff[i] : BN56_OOB, soff, v);
+                    bstore16_asm(ysrd, rok ? yvoff[i] : BN56_OOB, so, v);
                 }
                 t.step(VH);
             }
-            BN56_STAMP(4); // OT read-back + stores
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // OT is read: the next quarter may overwrite it
+            BN56_STAMP(2); // OT read-back + stores
         };
         bn56_row out{b0 - 1, H, b0 * H}; // virtual row S - 1 (the padding row above the run): the first output row of step 0
         bn56_barrier(); // D (prologue)
-        // iteration 0: the front waves compute step 0; request the first quarter's side operand meanwhile
-        stage_side(out);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bstore16_asm(ysrd, BN56_OOB, 0u, make_uint4(0, 0, 0, 0)); // the first quarter's counted wait expects 4 stores behind its DMA
+        // iteration 0: the front waves compute step 0
         bn56_barrier(); // E
         bn56_barrier(); // C
         bn56_barrier(); // D: t2[0] is complete
+        unsigned xp = 2 * SLOT, xc = 0u; // byte offsets of slot (j - 2) % 3 and slot (j - 1) % 3
         BN56_TIMER_START;
 #pragma unroll 1
-        for (int j = 1; j <= nsteps; ++j) { // outputs of step j - 1
+        for (int j = 1; j <= nsteps; ++j) { // outputs of step j - 1: row 3 of tile j-2, rows 0..2 of tile j-1
             const unsigned char *T2r = T2 + ((j - 1) & 1) * BN56_T2_BYTES;
-            bn56_row r1 = out, r2, r3, r4;
+            bn56_row r1 = out;
             r1.step(VH); r1.step(VH);
-            r2 = r1; r2.step(VH); r2.step(VH);
-            r3 = r2; r3.step(VH); r3.step(VH);
-            r4 = r3; r4.step(VH); r4.step(VH);
-            quarter(T2r, out, r1);
-            bn56_barrier(); // E
-            BN56_STAMP(5); // wait at E
-            quarter(T2r + 2 * 2048, r1, r2);
+            quarter(T2r, XS + xp + 3 * RB, XS + xc, out);
+            bn56_barrier(); // E: behind it the DMA of tile j+1 overwrites slot (j - 2) % 3
             bn56_barrier(); // C
-            BN56_STAMP(5); // wait at C
-            quarter(T2r + 4 * 2048, r2, r3);
-            quarter(T2r + 6 * 2048, r3, r4);
-            out = r4;
+            BN56_STAMP(3); // wait at E, C
+            quarter(T2r + 2 * RB, XS + xc + RB, XS + xc + 2 * RB, r1);
+            out = r1;
+            out.step(VH); out.step(VH);
+            xp = xc;
+            xc = xc + SLOT == 3 * SLOT ? 0u : xc + SLOT;
             if (j < nsteps) bn56_barrier(); // D (the front waves' last D belongs to step nsteps - 1; their two trailing barriers pair with this iteration's E, C)
-            BN56_STAMP(5); // wait at D
+            BN56_STAMP(3); // wait at D
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         BN56_TIMER_FLUSH(1);
     }
 }
