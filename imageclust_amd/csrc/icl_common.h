@@ -26,7 +26,7 @@ struct icl_pending_event {
     int kclass;
 };
 
-struct icl_model;  // resnet.hip
+struct icl_model;  // resnet_model.h
 struct icl_ward_ws; // ward.hip
 struct icl_ingest_ws; // jpeg_gpu.hip
 struct icl_many_ws; // ward_many.hip
@@ -122,7 +122,7 @@ struct icl_ctx {
     int shard_rank = 0;
     int64_t *ward_rowoff = nullptr; // row offsets of the packed triangle for ranks that only compute distance rows (ward.hip)
     int64_t ward_rowoff_n = 0;
-    void *file_batcher = nullptr; // icl_embed_file's coalescing queue (resnet.hip)
+    void *file_batcher = nullptr; // icl_embed_file's coalescing queue (embed_file.hip)
     icl_many_ws *many = nullptr; // workspace of icl_cluster_many (ward_many.hip; created on first use)
     int many_mid = 0;                 // icl_set_many_options: ICL_MANY_MID_AUTO / _OFF / _ON (environment: ICL_MANY_MID=auto|off|on)
     int64_t many_stats[4] = {0, 0, 0, 0}; // last icl_cluster_many[_dev]: problems on the small, mid and large-N routes, mid-route groups

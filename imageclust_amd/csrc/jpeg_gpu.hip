@@ -13,6 +13,7 @@
 #include "icl_common.h"
 #include "ingest_pixels.h"
 #include "jpeg_stage.h"
+#include "resnet_model.h" // icl_embed_dev_locked
 
 #include <algorithm>
 #include <atomic>
@@ -22,8 +23,6 @@
 #include <memory>
 #include <new>
 #include <thread>
-
-int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out); // resnet.hip
 
 namespace {
 

@@ -78,7 +78,7 @@ struct icl_je_slab {
 int icl_je_decode_slab(icl_ctx *ctx, hipStream_t st, const icl_je_slab &s);
 
 // image_io.hip: the host ingest path.  The batched file path (jpeg_gpu.hip) reads and sniffs files, and decodes what the GPU does not
-// take, through it; the icl_embed_file batcher (resnet.hip) reads and resizes through it.
+// take, through it; the icl_embed_file batcher (embed_file.hip) reads and resizes through it.
 enum { ICL_IMAGE_UNREADABLE = -1, ICL_IMAGE_PPM = 0, ICL_IMAGE_PNG = 1, ICL_IMAGE_JPEG = 2 };
 // Opens path and tells its format by the first bytes (PNG signature, JPEG SOI; anything else goes to the PPM reader).  A PNG or
 // JPEG is read whole into `file`.  ICL_IMAGE_UNREADABLE: the file cannot be opened, or a PNG / JPEG cannot be read whole.

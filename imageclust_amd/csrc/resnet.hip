@@ -3,7 +3,8 @@
 // Replaces LoadPretrainedModelONNX / GetImageEmbedding
 //   (/root/reference/internal/embeddings/embeddings.go:28-43, :119-163), i.e. the OpenCV-DNN forward
 // of resnet50-v1-7.onnx that the reference reaches through gocv (batch 1, CPU, serialised by NetMutex :133).
-// PreprocessImage (:46-116) is image_io.hip.
+// PreprocessImage (:46-116) is image_io.hip.  This unit holds the kernels, the launch dispatch, the forward pass and the embed drivers;
+// the model and its loader are model.hip, icl_embed_file's coalescing queue is embed_file.hip, what they share is resnet_model.h.
 //
 // Layout: activations NHWC (channels contiguous) in bf16 (throughput) or f32 (parity); weights re-packed once
 // at load to [Cout][KH][KW][Cin] so every implicit-GEMM K-chunk is a contiguous run of input channels of ONE
@@ -15,20 +16,16 @@
 // the MFMA step and the epilogue but gathers its A tile straight from the u8 image (K = 147 padded to 192), which also
 // performs the reference's RGB/255 scaling (embeddings.go:96).
 #include "icl_common.h"
-#include "jpeg_stage.h"
 #include "mfma_tile.h"
+#include "resnet_model.h"
 
 #include <algorithm>
 #include <cmath>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
 #include <new>
 #include <thread>
 #include <type_traits>
 #include <vector>
-
-#define ICL_MAX_LANES 4 /* forward passes in flight (ICL_EMBED_STREAMS) */
 
 struct conv_args {
     const void *X;      // [B][H][W][Cin]
@@ -776,358 +773,8 @@ __global__ __launch_bounds__(256) void fc_kernel(const float *__restrict__ x, co
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// model (host)
-// ------------------------------------------------------------------------------------------------------------
-struct conv_layer {
-    icl_conv_rec rec;
-    int K = 0, cin_eff = 0; // cin_eff: channel count seen by the kernel (160 for the lowered stem)
-    void *w[3] = {nullptr, nullptr, nullptr}; // [ICL_PREC_FP32], [ICL_PREC_BF16], [ICL_PREC_BF16X3] (split layout: host_split32)
-    float *scale = nullptr, *shift = nullptr;
-    // block-0 c3 only: [Cout][mid + cin] = [W3*scale3 | Wds*scale_ds] and shift3 + shift_ds (downsample fused in)
-    void *wfused[3] = {nullptr, nullptr, nullptr};
-    float *shift_fused = nullptr;
-    // stage 1 only (bneck56_kernel): bf16(W * scale), the BatchNorm scale folded into the weights before rounding
-    void *wfold = nullptr;
-};
-
-struct icl_model {
-    conv_layer conv[ICL_RESNET50_NCONV];
-    int nconv = 0;
-    float *fcw = nullptr, *fcb = nullptr;
-    // activation workspace
-    void *buf[ICL_MAX_LANES][5] = {}; // one activation workspace per forward pass in flight
-    float *pooled[ICL_MAX_LANES] = {};
-    hipStream_t xstream[ICL_MAX_LANES] = {}; // lanes 2.. (lane 0 = ctx->stream, lane 1 = ctx->stream2)
-    hipEvent_t xjoin[ICL_MAX_LANES] = {};
-    int ws_lanes = 0;
-    void *zero = nullptr; // 256 zero bytes: LDS-DMA source for padded taps
-    float *ones = nullptr; // [2048] scale of the fused layers (their BN scale is folded into the weights)
-    int ws_batch = 0, ws_prec = -1;
-};
-
-static int resnet50_topology(icl_conv_rec *out)
-{
-    static const int nblocks[4] = {3, 4, 6, 3};
-    int n = 0;
-    out[n++] = icl_conv_rec{3, 64, 7, 2, 3, 224, 112, 0, 0, 0};
-    int h = 56, cin = 64;
-    for (int s = 0; s < 4; ++s) {
-        const int cout = 256 << s, mid = cout / 4;
-        for (int b = 0; b < nblocks[s]; ++b) {
-            const int stride = (b == 0 && s > 0) ? 2 : 1, ho = h / stride;
-            out[n++] = icl_conv_rec{cin, mid, 1, stride, 0, h, ho, 1, s + 1, b};
-            out[n++] = icl_conv_rec{mid, mid, 3, 1, 1, ho, ho, 2, s + 1, b};
-            out[n++] = icl_conv_rec{mid, cout, 1, 1, 0, ho, ho, 3, s + 1, b};
-            if (b == 0) out[n++] = icl_conv_rec{cin, cout, 1, stride, 0, h, ho, 4, s + 1, b};
-            cin = cout;
-            h = ho;
-        }
-    }
-    return n;
-}
-
-static int64_t blob_floats(const icl_blob_header &h)
-{
-    icl_conv_rec t[ICL_RESNET50_NCONV];
-    const int n = resnet50_topology(t);
-    int64_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        tot += (int64_t)t[i].cout * t[i].cin * t[i].k * t[i].k + 4 * (int64_t)t[i].cout;
-        if (h.has_bias[i]) tot += t[i].cout;
-    }
-    return tot + (int64_t)ICL_FC_OUT * ICL_FEAT_DIM + ICL_FC_OUT;
-}
-
-static void default_header(icl_blob_header &h)
-{
-    memset(&h, 0, sizeof h);
-    h.magic = ICL_BLOB_MAGIC;
-    h.version = ICL_BLOB_VERSION;
-    h.bn_eps = 1e-5f;
-    h.n_conv = ICL_RESNET50_NCONV;
-    icl_conv_rec t[ICL_RESNET50_NCONV];
-    const int n = resnet50_topology(t);
-    // Gluon resnet50_v1: the bottleneck's 1x1 convs carry a bias, 3x3 / stem / downsample do not
-    for (int i = 0; i < n; ++i) h.has_bias[i] = (t[i].role == 1 || t[i].role == 3) ? 1 : 0;
-}
-
-extern "C" int64_t icl_synthetic_blob_bytes(void)
-{
-    icl_blob_header h;
-    default_header(h);
-    return (int64_t)sizeof(h) + 4 * blob_floats(h);
-}
-
-// counter-based generator: element e of the blob draws from splitmix64(seed, e)
-struct synth_rng {
-    uint64_t seed, ctr = 0;
-    double uni() { return (double)(icl_splitmix64(seed ^ (0xD1B54A32D192ED03ull * ++ctr)) >> 11) * (1.0 / 9007199254740992.0); }
-    double normal()
-    {
-        const double u1 = uni(), u2 = uni();
-        return std::sqrt(-2.0 * std::log(u1 > 1e-300 ? u1 : 1e-300)) * std::cos(6.283185307179586476925 * u2);
-    }
-};
-
-extern "C" int icl_synthetic_blob(uint64_t seed, void *blob, int64_t bytes)
-{
-    if (!blob || bytes != icl_synthetic_blob_bytes()) return icl_fail(nullptr, ICL_ERR_ARG, "icl_synthetic_blob: need a %lld-byte buffer", (long long)icl_synthetic_blob_bytes());
-    icl_blob_header h;
-    default_header(h);
-    memcpy(blob, &h, sizeof h);
-    float *p = (float *)((char *)blob + sizeof h);
-    icl_conv_rec t[ICL_RESNET50_NCONV];
-    const int n = resnet50_topology(t);
-    synth_rng g{seed};
-    for (int i = 0; i < n; ++i) {
-        const int64_t nw = (int64_t)t[i].cout * t[i].cin * t[i].k * t[i].k;
-        const double sd = std::sqrt(2.0 / ((double)t[i].cin * t[i].k * t[i].k)); // He init
-        for (int64_t e = 0; e < nw; ++e) *p++ = (float)(sd * g.normal());
-        if (h.has_bias[i])
-            for (int c = 0; c < t[i].cout; ++c) *p++ = (float)(0.01 * g.normal());
-        for (int c = 0; c < t[i].cout; ++c) *p++ = (float)(0.5 + g.uni());      // gamma ~ U(0.5,1.5)
-        for (int c = 0; c < t[i].cout; ++c) *p++ = (float)(0.1 * g.normal());   // beta
-        for (int c = 0; c < t[i].cout; ++c) *p++ = (float)(0.1 * g.normal());   // running mean
-        for (int c = 0; c < t[i].cout; ++c) *p++ = (float)(0.5 + g.uni());      // running var ~ U(0.5,1.5)
-    }
-    const double fsd = std::sqrt(1.0 / ICL_FEAT_DIM);
-    for (int64_t e = 0; e < (int64_t)ICL_FC_OUT * ICL_FEAT_DIM; ++e) *p++ = (float)(fsd * g.normal());
-    for (int e = 0; e < ICL_FC_OUT; ++e) *p++ = 0.0f;
-    return ICL_OK;
-}
-
-static inline uint16_t host_bf16(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-void icl_model_free(icl_ctx *ctx)
-{
-    icl_model *m = ctx->model;
-    if (!m) return;
-    for (auto &c : m->conv) {
-        for (void *p : {c.w[0], c.w[1], c.w[2], (void *)c.scale, (void *)c.shift, c.wfused[0], c.wfused[1], c.wfused[2], (void *)c.shift_fused, c.wfold})
-            if (p) (void)hipFree(p);
-    }
-    for (void *p : {(void *)m->fcw, (void *)m->fcb, m->zero, (void *)m->ones})
-        if (p) (void)hipFree(p);
-    for (int l = 0; l < ICL_MAX_LANES; ++l) {
-        for (void *b : m->buf[l])
-            if (b) (void)hipFree(b);
-        if (m->pooled[l]) (void)hipFree(m->pooled[l]);
-        if (m->xstream[l]) (void)hipStreamDestroy(m->xstream[l]);
-        if (m->xjoin[l]) (void)hipEventDestroy(m->xjoin[l]);
-    }
-    delete m;
-    ctx->model = nullptr;
-}
-
-// The split bf16 layout of ICL_PREC_BF16X3 (mfma_tile.h, BF16X3): every run of 32 consecutive fp32 values v (a channel chunk of a pixel, or
-// 32 k of a weight row: rows are whole chunks) becomes 64 bf16, [hi = bf16(v) of the 32 | lo = bf16(v - hi) of the same 32].  n % 32 == 0.
-static void host_split32(const float *src, size_t n, uint16_t *dst)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const uint16_t h = host_bf16(src[i]);
-        uint32_t u = (uint32_t)h << 16;
-        float hf;
-        memcpy(&hf, &u, 4);
-        dst[(i & ~(size_t)31) * 2 + (i & 31)] = h;
-        dst[(i & ~(size_t)31) * 2 + 32 + (i & 31)] = host_bf16(src[i] - hf);
-    }
-}
-
-static int upload(icl_ctx *ctx, void **dst, const void *src, size_t bytes)
-{
-    ICL_HIP(ctx, hipMalloc(dst, bytes));
-    ICL_HIP(ctx, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return ICL_OK;
-}
-
-extern "C" int icl_model_load_blob(icl_ctx *ctx, const void *blob, int64_t bytes)
-{
-    if (!ctx || !blob) return icl_fail(ctx, ICL_ERR_ARG, "icl_model_load_blob: bad argument");
-    if (bytes < (int64_t)sizeof(icl_blob_header)) return icl_fail(ctx, ICL_ERR_IO, "weight blob too small");
-    icl_blob_header h;
-    memcpy(&h, blob, sizeof h);
-    if (h.magic != ICL_BLOB_MAGIC || h.version != ICL_BLOB_VERSION || h.n_conv != ICL_RESNET50_NCONV)
-        return icl_fail(ctx, ICL_ERR_IO, "not an ICLW v%u ResNet50 blob", ICL_BLOB_VERSION);
-    if (bytes != (int64_t)sizeof h + 4 * blob_floats(h))
-        return icl_fail(ctx, ICL_ERR_IO, "weight blob has %lld bytes, expected %lld", (long long)bytes, (long long)(sizeof h + 4 * blob_floats(h)));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    icl_device_guard g(ctx->device);
-    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    icl_model_free(ctx);
-    icl_model *m = new icl_model();
-    ctx->model = m;
-    icl_conv_rec t[ICL_RESNET50_NCONV];
-    m->nconv = resnet50_topology(t);
-    const float *p = (const float *)((const char *)blob + sizeof h);
-    std::vector<float> wf;
-    std::vector<uint16_t> wb;
-    std::vector<float> sc, sh;
-    std::vector<std::vector<float>> hw((size_t)m->nconv), hsc((size_t)m->nconv), hsh((size_t)m->nconv); // host copies for the fusion below
-    for (int i = 0; i < m->nconv; ++i) {
-        conv_layer &L = m->conv[i];
-        L.rec = t[i];
-        const int cin = t[i].cin, cout = t[i].cout, k = t[i].k;
-        const float *W = p;
-        p += (int64_t)cout * cin * k * k;
-        const float *bias = nullptr;
-        if (h.has_bias[i]) {
-            bias = p;
-            p += cout;
-        }
-        const float *gamma = p, *beta = p + cout, *mean = p + 2 * cout, *var = p + 3 * cout;
-        p += 4 * (int64_t)cout;
-        // re-pack OIHW -> [cout][kh][kw][cin] (stem: K padded 147 -> 160)
-        L.cin_eff = (i == 0) ? STEM_K : cin;
-        L.K = (i == 0) ? STEM_K : cin * k * k;
-        wf.assign((size_t)cout * L.K, 0.0f);
-        for (int co = 0; co < cout; ++co)
-            for (int c = 0; c < cin; ++c)
-                for (int a = 0; a < k; ++a)
-                    for (int b = 0; b < k; ++b) {
-                        // stem: filter rows padded to 24 k-slots (stem_conv_kernel); others: [kh][kw][cin]
-                        const size_t kk = (i == 0) ? (size_t)a * STEM_ROWK + (size_t)b * 3 + c : ((size_t)a * k + b) * cin + c;
-                        wf[(size_t)co * L.K + kk] = W[(((size_t)co * cin + c) * k + a) * k + b];
-                    }
-        wb.resize(wf.size());
-        for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e]);
-        ICL_TRY(upload(ctx, &L.w[ICL_PREC_FP32], wf.data(), wf.size() * 4));
-        ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16], wb.data(), wb.size() * 2));
-        if (i > 0) { // (the BF16X3 stem runs in fp32: ICL_PREC_FP32 weights)
-            wb.resize(2 * wf.size());
-            host_split32(wf.data(), wf.size(), wb.data());
-            ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
-        }
-        // BatchNormalization folded to y = x*scale + shift, conv bias folded into shift
-        sc.resize(cout);
-        sh.resize(cout);
-        for (int c = 0; c < cout; ++c) {
-            const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)h.bn_eps);
-            sc[c] = (float)s;
-            sh[c] = (float)((double)beta[c] - (double)mean[c] * s + (bias ? (double)bias[c] * s : 0.0));
-        }
-        ICL_TRY(upload(ctx, (void **)&L.scale, sc.data(), (size_t)cout * 4));
-        ICL_TRY(upload(ctx, (void **)&L.shift, sh.data(), (size_t)cout * 4));
-        if (i == 0) { // stem2_pool_kernel: [64][kh][8 kw slots][4 channel slots] = bf16(W * scale), zero in the padding
-            std::vector<uint16_t> ws((size_t)64 * ST2_K, 0);
-            for (int co = 0; co < 64; ++co)
-                for (int c = 0; c < 3; ++c)
-                    for (int a = 0; a < 7; ++a)
-                        for (int b = 0; b < 7; ++b)
-                            ws[(size_t)co * ST2_K + (size_t)a * 32 + (size_t)b * 4 + c] = host_bf16(W[(((size_t)co * 3 + c) * 7 + a) * 7 + b] * sc[(size_t)co]);
-            ICL_TRY(upload(ctx, &L.wfold, ws.data(), ws.size() * 2));
-        }
-        if (t[i].stage == 1 && t[i].role >= 1 && t[i].role <= 3) { // the fused stage-1 bottleneck takes its BN scales inside the weights
-            for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e] * sc[e / (size_t)L.K]);
-            ICL_TRY(upload(ctx, &L.wfold, wb.data(), wb.size() * 2));
-        }
-        if (t[i].block == 0 && (t[i].role == 3 || t[i].role == 4)) {
-            hw[(size_t)i] = wf;
-            hsc[(size_t)i] = sc;
-            hsh[(size_t)i] = sh;
-        }
-    }
-    // fuse each stage's downsample branch into block 0's last conv: y = relu(W3'.t2 + Wds'.x_strided + (sh3 + sh_ds))
-    for (int i = 0; i < m->nconv; ++i) {
-        if (!(t[i].block == 0 && t[i].role == 3)) continue;
-        const int ids = i + 1; // canonical order: c1, c2, c3, ds
-        const int cout = t[i].cout, k1 = t[i].cin, k2 = t[ids].cin, kk = k1 + k2;
-        wf.assign((size_t)cout * kk, 0.0f);
-        sh.resize((size_t)cout);
-        for (int co = 0; co < cout; ++co) {
-            for (int c = 0; c < k1; ++c) wf[(size_t)co * kk + c] = hw[(size_t)i][(size_t)co * k1 + c] * hsc[(size_t)i][(size_t)co];
-            for (int c = 0; c < k2; ++c) wf[(size_t)co * kk + k1 + c] = hw[(size_t)ids][(size_t)co * k2 + c] * hsc[(size_t)ids][(size_t)co];
-            sh[(size_t)co] = hsh[(size_t)i][(size_t)co] + hsh[(size_t)ids][(size_t)co];
-        }
-        wb.resize(wf.size());
-        for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e]);
-        conv_layer &L = m->conv[i];
-        ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_FP32], wf.data(), wf.size() * 4));
-        ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16], wb.data(), wb.size() * 2));
-        wb.resize(2 * wf.size());
-        host_split32(wf.data(), wf.size(), wb.data());
-        ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
-        ICL_TRY(upload(ctx, (void **)&L.shift_fused, sh.data(), (size_t)cout * 4));
-    }
-    {
-        std::vector<float> one(2048, 1.0f);
-        ICL_TRY(upload(ctx, (void **)&m->ones, one.data(), one.size() * 4));
-    }
-    ICL_TRY(upload(ctx, (void **)&m->fcw, p, (size_t)ICL_FC_OUT * ICL_FEAT_DIM * 4));
-    p += (int64_t)ICL_FC_OUT * ICL_FEAT_DIM;
-    ICL_TRY(upload(ctx, (void **)&m->fcb, p, (size_t)ICL_FC_OUT * 4));
-    ICL_HIP(ctx, hipMalloc(&m->zero, 256));
-    ICL_HIP(ctx, hipMemset(m->zero, 0, 256));
-    return ICL_OK;
-}
-
-extern "C" int icl_model_load_synthetic(icl_ctx *ctx, uint64_t seed)
-{
-    if (!ctx) return ICL_ERR_ARG;
-    const int64_t nb = icl_synthetic_blob_bytes();
-    std::vector<char> blob((size_t)nb);
-    ICL_TRY(icl_synthetic_blob(seed, blob.data(), nb));
-    return icl_model_load_blob(ctx, blob.data(), nb);
-}
-
-int icl_onnx_to_blob(icl_ctx *ctx, const char *path, std::vector<char> &blob); // onnx_reader.hip
-
-extern "C" int icl_model_load_onnx(icl_ctx *ctx, const char *path)
-{
-    // LoadPretrainedModelONNX (embeddings.go:28-43): read the graph's initializers, validate the topology, upload.
-    if (!ctx || !path) return icl_fail(ctx, ICL_ERR_ARG, "icl_model_load_onnx: bad argument");
-    std::vector<char> blob;
-    ICL_TRY(icl_onnx_to_blob(ctx, path, blob));
-    return icl_model_load_blob(ctx, blob.data(), (int64_t)blob.size());
-}
-
-// ------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------
-static int ensure_ws(icl_ctx *ctx, int batch, int prec, int lanes)
-{
-    icl_model *m = ctx->model;
-    if (m->ws_batch >= batch && m->ws_prec == prec && m->ws_lanes >= lanes) return ICL_OK;
-    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream2));
-    for (int l = 2; l < lanes; ++l)
-        if (!m->xstream[l]) {
-            ICL_HIP(ctx, hipStreamCreateWithFlags(&m->xstream[l], hipStreamNonBlocking));
-            ICL_HIP(ctx, hipEventCreateWithFlags(&m->xjoin[l], hipEventDisableTiming));
-        }
-    for (int l = 0; l < ICL_MAX_LANES; ++l) {
-        if (m->xstream[l]) ICL_HIP(ctx, hipStreamSynchronize(m->xstream[l]));
-        for (auto &b : m->buf[l])
-            if (b) {
-                (void)hipFree(b);
-                b = nullptr;
-            }
-        if (m->pooled[l]) (void)hipFree(m->pooled[l]);
-        m->pooled[l] = nullptr;
-    }
-    m->ws_batch = 0;
-    m->ws_lanes = 0;
-    const size_t es = prec == ICL_PREC_BF16 ? 2 : 4;
-    const size_t act = (size_t)batch * 802816 * es; // 112*112*64 == 56*56*256: the largest activation
-    for (int l = 0; l < lanes; ++l) {
-        for (auto &b : m->buf[l]) {
-            hipError_t e = hipMalloc(&b, act);
-            if (e != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "activation workspace (%zu B): %s", act, hipGetErrorString(e));
-        }
-        ICL_HIP(ctx, hipMalloc((void **)&m->pooled[l], (size_t)batch * ICL_FEAT_DIM * 4));
-    }
-    m->ws_batch = batch;
-    m->ws_prec = prec;
-    m->ws_lanes = lanes;
-    return ICL_OK;
-}
-
 template <typename T, int BN, bool DUAL, int NST, bool EARLY = false>
 static void launch_conv_variant(icl_ctx *ctx, conv_args &a, int nst_lds)
 {
@@ -1207,54 +854,86 @@ static int launch_conv_t(icl_ctx *ctx, conv_args a)
 
 static int launch_conv_prec(icl_ctx *ctx, int prec, const conv_args &a)
 {
-    return prec == ICL_PREC_BF16 ? launch_conv_t<BF16>(ctx, a) : prec == ICL_PREC_BF16X3 ? launch_conv_t<BF16X3>(ctx, a) : launch_conv_t<F32>(ctx, a);
+    return with_prec(prec, [&](auto t) { return launch_conv_t<decltype(t)>(ctx, a); });
 }
-static bool prec_ok(int prec) { return prec == ICL_PREC_FP32 || prec == ICL_PREC_BF16 || prec == ICL_PREC_BF16X3; }
+
+// A plain k x k convolution over square B x H x H x Cin images: no second operand; the launchers set the tile counts (gx, gy) and
+// the split-form fields.
+static inline conv_args conv_plain(const void *X, const void *Wt, void *Y, const void *R, const float *scale, const float *shift, const void *zero, int B,
+                                   int H, int Cin, int Cout, int k, int stride, int pad, int relu)
+{
+    conv_args a = {};
+    a.X = X; a.Wt = Wt; a.Y = Y; a.R = R; a.scale = scale; a.shift = shift; a.zero = zero;
+    a.B = B; a.H = a.W = H; a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = k; a.stride = stride; a.pad = pad; a.relu = relu;
+    a.Ho = a.Wo = (H + 2 * pad - k) / stride + 1;
+    a.M = (int64_t)B * a.Ho * a.Wo;
+    a.K = k * k * Cin;
+    return a;
+}
+// ... plus a 1x1 / stride2 convolution over X2 ([B][H2][H2][Cin2]) accumulated into the same tiles: K = [k*k*Cin of X | Cin2 of X2]
+static inline void conv_add_operand(conv_args &a, const void *X2, int H2, int Cin2, int stride2)
+{
+    a.X2 = X2; a.H2 = a.W2 = H2; a.Cin2 = Cin2; a.stride2 = stride2;
+    a.K += Cin2;
+}
+// the 7x7/2 stem of the loaded model (Y: the 112 x 112 x 64 tensor, or the pooled one of the fused kernels), gx work units
+static inline conv_args conv_stem(const icl_model *m, const void *Wt, void *Y, int B, int gx)
+{
+    const conv_layer &L = m->conv[0];
+    conv_args a = conv_plain(nullptr, Wt, Y, nullptr, L.scale, L.shift, m->zero, B, 224, 3, 64, 7, 2, 3, 1);
+    a.K = STEM_K; // 147 padded: 7 filter rows of STEM_ROWK k slots
+    a.gx = gx;
+    a.gy = 1;
+    return a;
+}
 
 static int launch_conv(icl_ctx *ctx, int prec, const conv_layer &L, const void *X, void *Y, const void *R, int relu, int B)
 {
-    conv_args a;
-    a.X = X;
-    a.Wt = L.w[prec];
-    a.Y = Y;
-    a.R = R;
-    a.scale = L.scale;
-    a.shift = L.shift;
-    a.zero = ctx->model->zero;
-    a.X2 = nullptr;
-    a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
-    a.B = B;
-    a.relu = relu;
-    a.Cout = L.rec.cout;
-    a.H = a.W = L.rec.hin;
-    a.Ho = a.Wo = L.rec.hout;
-    a.Cin = L.rec.cin;
-    a.KH = a.KW = L.rec.k;
-    a.stride = L.rec.stride;
-    a.pad = L.rec.pad;
-    a.M = (int64_t)B * a.Ho * a.Wo;
-    a.K = a.KH * a.KW * a.Cin;
-    const int bk = prec == ICL_PREC_BF16 ? BF16::BK : F32::BK; // (BF16X3: 32 real channels per k-step, as F32)
+    const icl_conv_rec &r = L.rec;
+    const conv_args a = conv_plain(X, L.w[prec], Y, R, L.scale, L.shift, ctx->model->zero, B, r.hin, r.cin, r.cout, r.k, r.stride, r.pad, relu);
     if (a.M >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv: %lld output pixels exceed the kernel's 32-bit pixel index", (long long)a.M);
-    if (a.Cin % bk || a.Cout % 64 || a.K != L.K)
+    if (a.Ho != r.hout || a.Cin % prec_bk(prec) || a.Cout % 64 || a.K != L.K)
         return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv shape cin=%d cout=%d k=%d not supported by the implicit-GEMM kernel", a.Cin, a.Cout, a.KH);
     return launch_conv_prec(ctx, prec, a);
 }
 
-static inline float host_from_bf16(uint16_t v)
+// ---- per-layer entry points of the parity tests: host tensors in, host tensors out -----------------------------------------
+// a device allocation that lives as long as its scope
+struct dev_buf {
+    void *p = nullptr;
+    dev_buf() = default;
+    dev_buf(const dev_buf &) = delete;
+    dev_buf &operator=(const dev_buf &) = delete;
+    ~dev_buf() { if (p) (void)hipFree(p); }
+};
+// n fp32 values in the storage format of prec: rounded to bf16, split into hi / lo pairs (host_split32: the bytes of fp32), or as they are
+static int to_dev(icl_ctx *ctx, int prec, const float *src, size_t n, dev_buf &dst)
 {
-    uint32_t u = (uint32_t)v << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// host_split32 undone: dst[i] = hi + lo in fp32
-static void host_join32(const uint16_t *src, size_t n, float *dst)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const size_t j = (i & ~(size_t)31) * 2 + (i & 31);
-        dst[i] = host_from_bf16(src[j]) + host_from_bf16(src[j + 32]);
+    ICL_HIP(ctx, hipMalloc(&dst.p, n * prec_act_bytes(prec)));
+    if (prec == ICL_PREC_FP32) {
+        ICL_HIP(ctx, hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
+        return ICL_OK;
     }
+    std::vector<uint16_t> t(prec == ICL_PREC_BF16X3 ? 2 * n : n);
+    if (prec == ICL_PREC_BF16X3) host_split32(src, n, t.data());
+    else
+        for (size_t i = 0; i < n; ++i) t[i] = host_bf16(src[i]);
+    ICL_HIP(ctx, hipMemcpy(dst.p, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+    return ICL_OK;
+}
+// ... and back (the stream that wrote src has been synchronised)
+static int from_dev(icl_ctx *ctx, int prec, const dev_buf &src, size_t n, float *dst)
+{
+    if (prec == ICL_PREC_FP32) {
+        ICL_HIP(ctx, hipMemcpy(dst, src.p, n * 4, hipMemcpyDeviceToHost));
+        return ICL_OK;
+    }
+    std::vector<uint16_t> t(prec == ICL_PREC_BF16X3 ? 2 * n : n);
+    ICL_HIP(ctx, hipMemcpy(t.data(), src.p, t.size() * 2, hipMemcpyDeviceToHost));
+    if (prec == ICL_PREC_BF16X3) host_join32(t.data(), n, dst);
+    else
+        for (size_t i = 0; i < n; ++i) dst[i] = host_from_bf16(t[i]);
+    return ICL_OK;
 }
 
 extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int Cin, const float *w, int Cout, int k,
@@ -1266,97 +945,40 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
     if (Cin % 64 || Cout % 64) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_fused needs Cin %% 64 == 0 and Cout %% 64 == 0");
     const int Ho = (H + 2 * pad - k) / stride + 1;
     if (Ho < 1) return icl_fail(ctx, ICL_ERR_ARG, "empty output");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    icl_device_guard g(ctx->device);
-    const size_t es = prec == ICL_PREC_BF16 ? 2 : 4;
-    const size_t nx = (size_t)B * H * H * Cin, nw = (size_t)Cout * Cin * k * k, ny = (size_t)B * Ho * Ho * Cout;
-    std::vector<float> wp(nw);
-    for (int co = 0; co < Cout; ++co)
-        for (int c = 0; c < Cin; ++c)
-            for (int a = 0; a < k; ++a)
-                for (int b = 0; b < k; ++b) wp[(size_t)co * Cin * k * k + ((size_t)a * k + b) * Cin + c] = w[(((size_t)co * Cin + c) * k + a) * k + b];
-    auto to_dev = [&](const float *src, size_t n, void **dst) -> int {
-        ICL_HIP(ctx, hipMalloc(dst, n * es));
-        if (prec == ICL_PREC_BF16) {
-            std::vector<uint16_t> t(n);
-            for (size_t i = 0; i < n; ++i) t[i] = host_bf16(src[i]);
-            ICL_HIP(ctx, hipMemcpy(*dst, t.data(), n * 2, hipMemcpyHostToDevice));
-        } else if (prec == ICL_PREC_BF16X3) { // hi / lo pairs: the same bytes as fp32
-            std::vector<uint16_t> t(2 * n);
-            host_split32(src, n, t.data());
-            ICL_HIP(ctx, hipMemcpy(*dst, t.data(), n * 4, hipMemcpyHostToDevice));
-        } else {
-            ICL_HIP(ctx, hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
+    return no_throw(ctx, "icl_conv2d_fused", [&]() -> int {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        const size_t nx = (size_t)B * H * H * Cin, nw = (size_t)Cout * Cin * k * k, ny = (size_t)B * Ho * Ho * Cout;
+        std::vector<float> wp(nw);
+        for (int co = 0; co < Cout; ++co)
+            for (int c = 0; c < Cin; ++c)
+                for (int a = 0; a < k; ++a)
+                    for (int b = 0; b < k; ++b) wp[(size_t)co * Cin * k * k + ((size_t)a * k + b) * Cin + c] = w[(((size_t)co * Cin + c) * k + a) * k + b];
+        dev_buf dx, dw, dr, dy, dz, dsc, dsh;
+        ICL_TRY(to_dev(ctx, prec, x, nx, dx));
+        if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: zero page");
+        ICL_TRY(to_dev(ctx, prec, wp.data(), nw, dw));
+        if (residual) ICL_TRY(to_dev(ctx, prec, residual, ny, dr));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, scale, (size_t)Cout, dsc));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, shift, (size_t)Cout, dsh));
+        if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: output alloc");
+        int rc = launch_conv_prec(ctx, prec, conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, H, Cin, Cout, k, stride, pad, relu));
+        if (!rc) {
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            rc = e == hipSuccess ? from_dev(ctx, prec, dy, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_fused: %s", hipGetErrorString(e));
         }
-        return ICL_OK;
-    };
-    void *dx = nullptr, *dw = nullptr, *dr = nullptr, *dy = nullptr, *dz = nullptr;
-    float *dsc = nullptr, *dsh = nullptr;
-    int rc = to_dev(x, nx, &dx);
-    if (!rc && (hipMalloc(&dz, 256) != hipSuccess || hipMemset(dz, 0, 256) != hipSuccess)) rc = icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: zero page");
-    if (!rc) rc = to_dev(wp.data(), nw, &dw);
-    if (!rc && residual) rc = to_dev(residual, ny, &dr);
-    if (!rc) rc = upload(ctx, (void **)&dsc, scale, (size_t)Cout * 4);
-    if (!rc) rc = upload(ctx, (void **)&dsh, shift, (size_t)Cout * 4);
-    if (!rc && hipMalloc(&dy, ny * es) != hipSuccess) rc = icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: output alloc");
-    if (!rc) {
-        conv_args a;
-        a.X = dx; a.Wt = dw; a.Y = dy; a.R = dr; a.scale = dsc; a.shift = dsh; a.zero = dz;
-        a.X2 = nullptr; a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
-        a.B = B; a.H = a.W = H; a.Cin = Cin; a.Ho = a.Wo = Ho; a.Cout = Cout; a.KH = a.KW = k; a.stride = stride; a.pad = pad;
-        a.relu = relu; a.M = (int64_t)B * Ho * Ho; a.K = k * k * Cin;
-        rc = launch_conv_prec(ctx, prec, a);
-    }
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) {
-            if (prec == ICL_PREC_BF16) {
-                std::vector<uint16_t> t(ny);
-                e = hipMemcpy(t.data(), dy, ny * 2, hipMemcpyDeviceToHost);
-                for (size_t i = 0; i < ny; ++i) y[i] = host_from_bf16(t[i]);
-            } else if (prec == ICL_PREC_BF16X3) {
-                std::vector<uint16_t> t(2 * ny);
-                e = hipMemcpy(t.data(), dy, ny * 4, hipMemcpyDeviceToHost);
-                host_join32(t.data(), ny, y);
-            } else {
-                e = hipMemcpy(y, dy, ny * 4, hipMemcpyDeviceToHost);
-            }
-        }
-        if (e != hipSuccess) rc = icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_fused: %s", hipGetErrorString(e));
-    }
-    for (void *q : {dx, dw, dr, dy, dz, (void *)dsc, (void *)dsh})
-        if (q) (void)hipFree(q);
-    icl_prof_collect(ctx);
-    return rc;
+        icl_prof_collect(ctx);
+        return rc;
+    });
 }
 
 // Block 0 of a stage: y = relu(bn3(conv3(t2)) + bn_ds(conv_ds(x))) as ONE dual-operand launch (BN scales folded into
 // the concatenated weights): the downsample tensor is never written to or read back from HBM.
 static int launch_conv_fused_ds(icl_ctx *ctx, int prec, const conv_layer &c3, const conv_layer &ds, const void *t2, const void *x, void *y, int B)
 {
-    conv_args a;
-    a.X = t2;
-    a.Wt = c3.wfused[prec];
-    a.Y = y;
-    a.R = nullptr;
-    a.scale = ctx->model->ones;
-    a.shift = c3.shift_fused;
-    a.zero = ctx->model->zero;
-    a.B = B;
-    a.relu = 1;
-    a.Cout = c3.rec.cout;
-    a.H = a.W = a.Ho = a.Wo = c3.rec.hout;
-    a.Cin = c3.rec.cin;
-    a.KH = a.KW = 1;
-    a.stride = 1;
-    a.pad = 0;
-    a.X2 = x;
-    a.H2 = a.W2 = ds.rec.hin;
-    a.Cin2 = ds.rec.cin;
-    a.stride2 = ds.rec.stride;
-    a.M = (int64_t)B * a.Ho * a.Wo;
-    a.K = a.Cin + a.Cin2;
-    const int bk = prec == ICL_PREC_BF16 ? BF16::BK : F32::BK;
+    conv_args a = conv_plain(t2, c3.wfused[prec], y, nullptr, ctx->model->ones, c3.shift_fused, ctx->model->zero, B, c3.rec.hout, c3.rec.cin, c3.rec.cout, 1, 1, 0, 1);
+    conv_add_operand(a, x, ds.rec.hin, ds.rec.cin, ds.rec.stride);
+    const int bk = prec_bk(prec);
     if (a.Cin % bk || a.Cin2 % bk || a.Cout % 128) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused downsample shape not supported");
     return launch_conv_prec(ctx, prec, a);
 }
@@ -1390,12 +1012,7 @@ static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B
     constexpr bool SPLIT = is_x3<T>::value;
     typedef typename std::conditional<SPLIT, F32, T>::type TS;
     icl_lds_optin(ctx, (const void *)stem_pool_kernel<TS, SPLIT>, (int)stem_pool_lds_bytes<TS>());
-    conv_args a;
-    const conv_layer &L = m->conv[0];
-    a.X = nullptr; a.Wt = L.w[SPLIT ? ICL_PREC_FP32 : prec]; a.Y = pooled; a.R = nullptr; a.scale = L.scale; a.shift = L.shift; a.zero = m->zero;
-    a.B = B; a.H = a.W = 224; a.Cin = 3; a.Ho = a.Wo = 112; a.Cout = 64; a.KH = a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
-    a.M = (int64_t)B * 112 * 112; a.K = STEM_K; a.gx = B * SP_STRIPS * SP_TILES; a.gy = 1;
-    a.X2 = nullptr; a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
+    const conv_args a = conv_stem(m, m->conv[0].w[SPLIT ? ICL_PREC_FP32 : prec], pooled, B, B * SP_STRIPS * SP_TILES);
     icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
     const int nunits = B * SP_STRIPS;
     const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_pool_lds_bytes<TS>()));
@@ -1403,19 +1020,11 @@ static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B
     hipLaunchKernelGGL((stem_pool_kernel<TS, SPLIT>), dim3(grid), dim3(256), stem_pool_lds_bytes<TS>(), strm, d_img, a, nunits);
 }
 
-// One stage-1 bottleneck in one launch (bf16): c1 -> c2 -> c3 (+ residual x | + downsample branch ds) + ReLU.
-static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &c2, const conv_layer &c3, const conv_layer *ds, const void *x, void *y,
-                          int B, hipStream_t strm)
+// One stage-1 bottleneck in one launch (bf16): c1 -> c2 -> c3 (+ residual x | + downsample branch ds) + ReLU.  a: tensors, weights
+// and B, H, W; the grid is decided here.
+static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, hipStream_t strm)
 {
-    bneck_args a;
-    a.X = (const uint16_t *)x;
-    a.Y = (uint16_t *)y;
-    a.W1 = (const uint16_t *)c1.wfold;
-    a.W2 = (const uint16_t *)c2.wfold;
-    a.W3 = (const uint16_t *)(ds ? c3.wfused[ICL_PREC_BF16] : c3.wfold);
-    a.sh1 = c1.shift; a.sh2 = c2.shift;
-    a.sh3 = ds ? c3.shift_fused : c3.shift;
-    a.B = B; a.H = c2.rec.hin; a.W = c2.rec.hin;
+    const int B = a.B;
     if ((int64_t)B * a.H * a.W * 512 >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused bottleneck: batch of %d images exceeds the 32-bit buffer offsets", B);
     a.nstrips = (a.W + BN56_COLS - 1) / BN56_COLS;
     a.ngroups = std::max(1, std::min(B, ctx->prop.multiProcessorCount / a.nstrips));
@@ -1425,7 +1034,7 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     a.dbg = dbg;
 #endif
     const double px = (double)B * a.H * a.W;
-    icl_prof_scope ps(ctx, ICL_K_CONV, 2.0 * px * (64.0 * c1.rec.cin + 64.0 * 576 + 256.0 * (ds ? 128 : 64)), 0.0);
+    icl_prof_scope ps(ctx, ICL_K_CONV, 2.0 * px * (64.0 * (ds ? 64 : 256) + 64.0 * 576 + 256.0 * (ds ? 128 : 64)), 0.0);
     const dim3 grid((unsigned)(a.nstrips * a.ngroups));
     if (ds) {
         icl_lds_optin(ctx, (const void *)bneck56_kernel<true>, (int)bneck56_lds_bytes<true>());
@@ -1453,6 +1062,21 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     return ICL_OK;
 }
 
+static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &c2, const conv_layer &c3, const conv_layer *ds, const void *x, void *y,
+                          int B, hipStream_t strm)
+{
+    bneck_args a = {};
+    a.X = (const uint16_t *)x;
+    a.Y = (uint16_t *)y;
+    a.W1 = (const uint16_t *)c1.wfold;
+    a.W2 = (const uint16_t *)c2.wfold;
+    a.W3 = (const uint16_t *)(ds ? c3.wfused[ICL_PREC_BF16] : c3.wfold);
+    a.sh1 = c1.shift; a.sh2 = c2.shift;
+    a.sh3 = ds ? c3.shift_fused : c3.shift;
+    a.B = B; a.H = c2.rec.hin; a.W = c2.rec.hin;
+    return launch_bneck56_args(ctx, a, ds != nullptr, strm);
+}
+
 template <typename T>
 static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, int head, float *d_out, int lane, hipStream_t strm)
 {
@@ -1467,12 +1091,7 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
     } else if constexpr (!is_x3<T>::value) {
         {
             icl_lds_optin(ctx, (const void *)stem_conv_kernel<T>, (int)stem_lds_bytes<T>());
-            conv_args a;
-            const conv_layer &L = m->conv[0];
-            a.X = nullptr; a.Wt = L.w[prec]; a.Y = y; a.R = nullptr; a.scale = L.scale; a.shift = L.shift; a.zero = m->zero;
-            a.B = B; a.H = a.W = 224; a.Cin = 3; a.Ho = a.Wo = 112; a.Cout = 64; a.KH = a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
-            a.M = (int64_t)B * 112 * 112; a.K = STEM_K; a.gx = B * 98; a.gy = 1; // 8x16-pixel tiles: 14 x 7 per image
-            a.X2 = nullptr; a.H2 = a.W2 = a.Cin2 = a.stride2 = 0;
+            const conv_args a = conv_stem(m, m->conv[0].w[prec], y, B, B * 98); // 8x16-pixel tiles: 14 x 7 per image
             icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
             const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_lds_bytes<T>()));
             const unsigned stem_grid = (unsigned)std::min<int64_t>(a.gx, (int64_t)per_cu * ctx->prop.multiProcessorCount);
@@ -1527,36 +1146,15 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
         std::lock_guard<std::mutex> lk(ctx->mu);
         icl_device_guard g(ctx->device);
         if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
-        const size_t es = prec == ICL_PREC_BF16 ? 2 : 4, ny = (size_t)B * 56 * 56 * 64;
-        uint8_t *dimg = nullptr;
-        void *dy = nullptr;
-        int rc = ICL_OK;
-        if (hipMalloc((void **)&dimg, (size_t)B * ICL_IMG_BYTES) != hipSuccess || hipMalloc(&dy, ny * es) != hipSuccess)
-            rc = icl_fail(ctx, ICL_ERR_NOMEM, "icl_stem_pool: device buffers");
-        if (!rc && hipMemcpy(dimg, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) rc = icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
-        if (!rc) {
-            if (prec == ICL_PREC_BF16) launch_stem_pool<BF16>(ctx, prec, dimg, B, dy, ctx->stream);
-            else if (prec == ICL_PREC_BF16X3) launch_stem_pool<BF16X3>(ctx, prec, dimg, B, dy, ctx->stream);
-            else launch_stem_pool<F32>(ctx, prec, dimg, B, dy, ctx->stream);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) {
-                if (prec == ICL_PREC_BF16) {
-                    std::vector<uint16_t> t(ny);
-                    e = hipMemcpy(t.data(), dy, ny * 2, hipMemcpyDeviceToHost);
-                    for (size_t i = 0; i < ny; ++i) out[i] = host_from_bf16(t[i]);
-                } else if (prec == ICL_PREC_BF16X3) {
-                    std::vector<uint16_t> t(2 * ny);
-                    e = hipMemcpy(t.data(), dy, ny * 4, hipMemcpyDeviceToHost);
-                    host_join32(t.data(), ny, out);
-                } else {
-                    e = hipMemcpy(out, dy, ny * 4, hipMemcpyDeviceToHost);
-                }
-            }
-            if (e != hipSuccess) rc = icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
-        }
-        if (dimg) (void)hipFree(dimg);
-        if (dy) (void)hipFree(dy);
+        const size_t ny = (size_t)B * 56 * 56 * 64;
+        dev_buf dimg, dy;
+        if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess || hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess)
+            return icl_fail(ctx, ICL_ERR_NOMEM, "icl_stem_pool: device buffers");
+        if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
+        with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, ctx->stream); });
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        const int rc = e == hipSuccess ? from_dev(ctx, prec, dy, ny, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
         icl_prof_collect(ctx);
         return rc;
     });
@@ -1581,69 +1179,46 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
         icl_device_guard g(ctx->device);
         const size_t nx = (size_t)B * H * W * Cin, ny = (size_t)B * H * W * 256;
         const int K3 = has_ds ? 128 : 64;
-        std::vector<uint16_t> hx(nx), hw1((size_t)64 * Cin), hw2((size_t)64 * 576), hw3((size_t)256 * K3);
-        for (size_t i = 0; i < nx; ++i) hx[i] = host_bf16(x[i]);
         // every BatchNorm scale goes into the weights before they are rounded, as icl_model_load_blob does for stage 1
-        for (size_t i = 0; i < hw1.size(); ++i) hw1[i] = host_bf16(w1[i] * sc1[i / (size_t)Cin]);
+        std::vector<float> f1((size_t)64 * Cin), f2((size_t)64 * 576), f3((size_t)256 * K3), h3(256);
+        for (size_t i = 0; i < f1.size(); ++i) f1[i] = w1[i] * sc1[i / (size_t)Cin];
         for (int co = 0; co < 64; ++co)
             for (int c = 0; c < 64; ++c)
                 for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) hw2[(size_t)co * 576 + ((size_t)a * 3 + b) * 64 + c] = host_bf16(w2[(((size_t)co * 64 + c) * 3 + a) * 3 + b] * sc2[co]);
-        std::vector<float> h3(256);
+                    for (int b = 0; b < 3; ++b) f2[(size_t)co * 576 + ((size_t)a * 3 + b) * 64 + c] = w2[(((size_t)co * 64 + c) * 3 + a) * 3 + b] * sc2[co];
         for (int co = 0; co < 256; ++co) {
-            for (int c = 0; c < 64; ++c) hw3[(size_t)co * K3 + c] = host_bf16(w3[(size_t)co * 64 + c] * sc3[co]);
+            for (int c = 0; c < 64; ++c) f3[(size_t)co * K3 + c] = w3[(size_t)co * 64 + c] * sc3[co];
             if (has_ds)
-                for (int c = 0; c < 64; ++c) hw3[(size_t)co * 128 + 64 + c] = host_bf16(wds[(size_t)co * 64 + c] * scds[co]);
+                for (int c = 0; c < 64; ++c) f3[(size_t)co * 128 + 64 + c] = wds[(size_t)co * 64 + c] * scds[co];
             h3[co] = has_ds ? sh3[co] + shds[co] : sh3[co];
         }
-        void *dx = nullptr, *dy = nullptr, *dw1 = nullptr, *dw2 = nullptr, *dw3 = nullptr, *dz = nullptr;
-        float *d1h = nullptr, *d2h = nullptr, *d3h = nullptr;
-        int rc = upload(ctx, &dx, hx.data(), nx * 2);
-        if (!rc) rc = upload(ctx, &dw1, hw1.data(), hw1.size() * 2);
-        if (!rc) rc = upload(ctx, &dw2, hw2.data(), hw2.size() * 2);
-        if (!rc) rc = upload(ctx, &dw3, hw3.data(), hw3.size() * 2);
-        if (!rc) rc = upload(ctx, (void **)&d1h, sh1, 64 * 4);
-        if (!rc) rc = upload(ctx, (void **)&d2h, sh2, 64 * 4);
-        if (!rc) rc = upload(ctx, (void **)&d3h, h3.data(), 256 * 4);
-        if (!rc && hipMalloc(&dy, ny * 2) != hipSuccess) rc = icl_fail(ctx, ICL_ERR_NOMEM, "icl_bottleneck56: output alloc");
+        dev_buf dx, dy, dw1, dw2, dw3, d1h, d2h, d3h;
+        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, x, nx, dx));
+        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f1.data(), f1.size(), dw1));
+        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f2.data(), f2.size(), dw2));
+        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f3.data(), f3.size(), dw3));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, sh1, 64, d1h));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, sh2, 64, d2h));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, h3.data(), 256, d3h));
+        if (hipMalloc(&dy.p, ny * 2) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_bottleneck56: output alloc");
+        bneck_args a = {};
+        a.X = (const uint16_t *)dx.p; a.Y = (uint16_t *)dy.p; a.W1 = (const uint16_t *)dw1.p; a.W2 = (const uint16_t *)dw2.p; a.W3 = (const uint16_t *)dw3.p;
+        a.sh1 = (const float *)d1h.p; a.sh2 = (const float *)d2h.p; a.sh3 = (const float *)d3h.p;
+        a.B = B; a.H = H; a.W = W;
+        int rc = launch_bneck56_args(ctx, a, has_ds, ctx->stream); // the launch code of the forward pass
         if (!rc) {
-            bneck_args a;
-            a.X = (const uint16_t *)dx; a.Y = (uint16_t *)dy; a.W1 = (const uint16_t *)dw1; a.W2 = (const uint16_t *)dw2; a.W3 = (const uint16_t *)dw3;
-            a.sh1 = d1h; a.sh2 = d2h; a.sh3 = d3h;
-#ifdef BN56_TIMERS
-            a.dbg = nullptr;
-#endif
-            a.B = B; a.H = H; a.W = W;
-            a.nstrips = (W + BN56_COLS - 1) / BN56_COLS;
-            a.ngroups = std::max(1, std::min(B, ctx->prop.multiProcessorCount / a.nstrips));
-            const dim3 grid((unsigned)(a.nstrips * a.ngroups));
-            if (has_ds) {
-                icl_lds_optin(ctx, (const void *)bneck56_kernel<true>, (int)bneck56_lds_bytes<true>());
-                hipLaunchKernelGGL((bneck56_kernel<true>), grid, dim3(512), bneck56_lds_bytes<true>(), ctx->stream, a);
-            } else {
-                icl_lds_optin(ctx, (const void *)bneck56_kernel<false>, (int)bneck56_lds_bytes<false>());
-                hipLaunchKernelGGL((bneck56_kernel<false>), grid, dim3(512), bneck56_lds_bytes<false>(), ctx->stream, a);
-            }
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            std::vector<uint16_t> t(ny);
-            if (e == hipSuccess) e = hipMemcpy(t.data(), dy, ny * 2, hipMemcpyDeviceToHost);
-            if (e == hipSuccess)
-                for (size_t i = 0; i < ny; ++i) y[i] = host_from_bf16(t[i]);
-            else rc = icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: %s", hipGetErrorString(e));
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            rc = e == hipSuccess ? from_dev(ctx, ICL_PREC_BF16, dy, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: %s", hipGetErrorString(e));
         }
-        for (void *q : {dx, dy, dw1, dw2, dw3, dz, (void *)d1h, (void *)d2h, (void *)d3h})
-            if (q) (void)hipFree(q);
+        icl_prof_collect(ctx);
         return rc;
     });
 }
 
-int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out); // also called by icl_embed_cluster_dev (ward.hip)
-static int embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out) { return icl_embed_dev_locked(ctx, d_img, n, head, prec, d_out); }
 int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out)
 {
     if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
-    if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
+    if (!head_ok(head)) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
     if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32, ICL_PREC_BF16 or ICL_PREC_BF16X3");
     if (n == 0) return ICL_OK;
     const int batch = (int)std::min<int64_t>(ctx->batch, n);
@@ -1656,12 +1231,34 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
     }();
     int lanes = (ctx->prof_mask || lanes_env < 2) ? 1 : std::min(lanes_env, ICL_MAX_LANES);
     lanes = (int)std::min<int64_t>(lanes, (n + batch - 1) / batch);
-    ICL_TRY(ensure_ws(ctx, batch, prec, lanes));
-    hipEvent_t e0, e1;
+    ICL_TRY(icl_model_ensure_ws(ctx, batch, prec, lanes));
+    // whatever the exit: the events of this call are destroyed and no launch stream stays selected
+    constexpr int DEPTH = 16;
+    hipEvent_t ring[DEPTH + 2] = {}; // one per batch in flight, then the two that time the call
+    hipEvent_t &e0 = ring[DEPTH], &e1 = ring[DEPTH + 1];
+    struct exit_guard {
+        icl_ctx *c;
+        hipEvent_t *r;
+        ~exit_guard()
+        {
+            c->cur_stream = nullptr;
+            for (int q = 0; q < DEPTH + 2; ++q) if (r[q]) (void)hipEventDestroy(r[q]);
+        }
+    } eg{ctx, ring};
     ICL_HIP(ctx, hipEventCreate(&e0));
     ICL_HIP(ctx, hipEventCreate(&e1));
     ICL_HIP(ctx, hipEventRecord(e0, ctx->stream));
     auto lane_stream = [&](int l) { return l == 0 ? ctx->stream : l == 1 ? ctx->stream2 : ctx->model->xstream[l]; };
+    auto join = [&]() -> hipError_t { // the main stream waits for every side stream; the first error, after trying them all
+        hipError_t first = hipSuccess;
+        for (int l = 1; l < lanes; ++l) {
+            hipEvent_t ej = l == 1 ? ctx->ev_join : ctx->model->xjoin[l];
+            hipError_t e = hipEventRecord(ej, lane_stream(l));
+            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ej, 0);
+            if (first == hipSuccess) first = e;
+        }
+        return first;
+    };
     if (lanes > 1) { // fork: the side streams start after everything already queued on the main stream
         ICL_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         for (int l = 1; l < lanes; ++l) ICL_HIP(ctx, hipStreamWaitEvent(lane_stream(l), ctx->ev_fork, 0));
@@ -1671,12 +1268,6 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
     // bounded however many images a call embeds -- unbounded, a 100 000-image call had 21 500 launches outstanding, which
     // `rocprofv3 --pmc` does not survive (SIGSEGV in the tool once several thousand counter-instrumented dispatches are pending;
     // 2 200 are fine, 8 600 are not: profiles/README.md).
-    constexpr int DEPTH = 16;
-    hipEvent_t ring[DEPTH] = {};
-    struct ring_guard {
-        hipEvent_t *r;
-        ~ring_guard() { for (int q = 0; q < DEPTH; ++q) if (r[q]) (void)hipEventDestroy(r[q]); }
-    } rg{ring};
     int64_t bi = 0;
     for (int64_t i = 0; i < n; i += batch, ++bi) {
         const int B = (int)std::min<int64_t>(batch, n - i);
@@ -1685,36 +1276,22 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
         hipEvent_t &ev = ring[bi % DEPTH];
         if (ev) ICL_HIP(ctx, hipEventSynchronize(ev)); // batch bi-DEPTH has finished
         else ICL_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        const int rc = prec == ICL_PREC_BF16 ? forward_batch<BF16>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm)
-                     : prec == ICL_PREC_BF16X3 ? forward_batch<BF16X3>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm)
-                                             : forward_batch<F32>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm);
-        if (rc) return rc;
+        ICL_TRY(with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm); }));
         ICL_HIP(ctx, hipEventRecord(ev, strm));
         if (ctx->embed_hook) { // rows [i, i + B) of d_out are complete once ev has fired
             const int hrc = ctx->embed_hook(i, B, ev);
-            if (hrc) { // (leave the lanes the way a completed loop does: no launch stream left selected, the side streams joined)
-                ctx->cur_stream = nullptr;
-                for (int l = 1; l < lanes; ++l) {
-                    hipEvent_t ej = l == 1 ? ctx->ev_join : ctx->model->xjoin[l];
-                    if (hipEventRecord(ej, lane_stream(l)) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ej, 0);
-                }
+            if (hrc) { // (leave the lanes the way a completed loop does: the side streams joined)
+                (void)join();
                 return hrc;
             }
         }
     }
-    ctx->cur_stream = nullptr;
-    for (int l = 1; l < lanes; ++l) { // join
-        hipEvent_t ej = l == 1 ? ctx->ev_join : ctx->model->xjoin[l];
-        ICL_HIP(ctx, hipEventRecord(ej, lane_stream(l)));
-        ICL_HIP(ctx, hipStreamWaitEvent(ctx->stream, ej, 0));
-    }
+    ICL_HIP(ctx, join());
     ICL_HIP(ctx, hipEventRecord(e1, ctx->stream));
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     ctx->last_embed_ms = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     icl_prof_collect(ctx);
     return ICL_OK;
 }
@@ -1724,13 +1301,13 @@ extern "C" int icl_embed_u8_dev(icl_ctx *ctx, const uint8_t *d_img, int64_t n, i
     if (!ctx || n < 0 || (n && (!d_img || !d_out))) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_u8_dev: bad argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    return embed_dev_locked(ctx, d_img, n, head, prec, d_out);
+    return icl_embed_dev_locked(ctx, d_img, n, head, prec, d_out);
 }
 
 extern "C" int icl_embed_u8(icl_ctx *ctx, const uint8_t *img, int64_t n, int head, int prec, float *out)
 {
     if (!ctx || n < 0 || (n && (!img || !out))) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_u8: bad argument");
-    if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
+    if (!head_ok(head)) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
     if (n == 0) return ICL_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
@@ -1783,7 +1360,7 @@ extern "C" int icl_embed_u8(icl_ctx *ctx, const uint8_t *img, int64_t n, int hea
                 e_up = upload(inext, dst);
             }
         }
-        rc = embed_dev_locked(ctx, d_img[k & 1], cnt, head, prec, d_out);
+        rc = icl_embed_dev_locked(ctx, d_img[k & 1], cnt, head, prec, d_out);
         total_ms += ctx->last_embed_ms;
         if (rc == ICL_OK) {
             e = hipMemcpyAsync(out + i * head, d_out, (size_t)cnt * head * 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -1797,167 +1374,3 @@ extern "C" int icl_embed_u8(icl_ctx *ctx, const uint8_t *img, int64_t n, int hea
     return rc;
 }
 
-// ---- GetImageEmbedding(path) from N goroutines (workflow.go:156-175) -------------------------------------------------
-// The reference serialises its batch-1 forward passes behind NetMutex (embeddings.go:133).  Here concurrent callers are
-// COALESCED: every caller decodes and resizes its own file in parallel, then joins a per-context queue; the first one
-// to arrive becomes the leader, waits a short window (or until a full batch has gathered), runs ONE forward pass over
-// everything queued and hands each caller its row.  fp32 rows do not depend on what else is in the batch (every output
-// pixel is its own in-order sum), so results equal the one-at-a-time path bit for bit.
-struct icl_file_req {
-    const uint8_t *img;
-    float *out;
-    int head;
-    int rc = ICL_OK;
-    bool done = false;
-    std::string err;
-};
-struct icl_file_batcher {
-    std::mutex m;
-    std::condition_variable cv;
-    std::vector<icl_file_req *> pending;
-    bool leader = false;
-    int inflight = 0; // callers inside icl_embed_file (decoding, queued or being served): a leader stops waiting once all of them are queued
-    int prec = ICL_PREC_FP32;
-    int window_us = 2000;
-    int max_batch = 256;
-    bool fail_next = false; // ICL_FILE_FAIL_NEXT_LEADER: the next batch leader gives up right after taking its requests
-    int64_t batches = 0, images = 0; // statistics (icl_file_batch_stats)
-};
-static icl_file_batcher *file_batcher(icl_ctx *ctx)
-{
-    static std::mutex gm;
-    std::lock_guard<std::mutex> lk(gm);
-    if (!ctx->file_batcher) ctx->file_batcher = new icl_file_batcher();
-    return (icl_file_batcher *)ctx->file_batcher;
-}
-void icl_file_batcher_free(icl_ctx *ctx)
-{
-    delete (icl_file_batcher *)ctx->file_batcher;
-    ctx->file_batcher = nullptr;
-}
-
-extern "C" int icl_set_file_options(icl_ctx *ctx, int prec, int window_us, int max_batch)
-{
-    const bool fail_next = (prec & ICL_FILE_FAIL_NEXT_LEADER) != 0;
-    prec &= ~ICL_FILE_FAIL_NEXT_LEADER;
-    if (!ctx || !prec_ok(prec) || window_us < 0 || max_batch < 1 || max_batch > 4096)
-        return icl_fail(ctx, ICL_ERR_ARG, "icl_set_file_options: bad argument");
-    icl_file_batcher *b = file_batcher(ctx);
-    std::lock_guard<std::mutex> lk(b->m);
-    b->fail_next = fail_next;
-    b->prec = prec;
-    b->window_us = window_us;
-    b->max_batch = max_batch;
-    return ICL_OK;
-}
-
-extern "C" int icl_file_batch_stats(icl_ctx *ctx, int64_t *batches, int64_t *images)
-{
-    if (!ctx) return ICL_ERR_ARG;
-    icl_file_batcher *b = file_batcher(ctx);
-    std::lock_guard<std::mutex> lk(b->m);
-    if (batches) *batches = b->batches;
-    if (images) *images = b->images;
-    return ICL_OK;
-}
-
-extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *out)
-{
-    if (!ctx || !path || !out) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_file: bad argument");
-    if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
-    return no_throw(ctx, "icl_embed_file", [&]() -> int {
-        icl_file_batcher *b = file_batcher(ctx);
-        struct inflight_guard { // counts this caller in from before it queues until it leaves, whatever the exit
-            icl_file_batcher *b;
-            explicit inflight_guard(icl_file_batcher *bb) : b(bb)
-            {
-                std::lock_guard<std::mutex> g(b->m);
-                ++b->inflight;
-            }
-            ~inflight_guard()
-            {
-                std::lock_guard<std::mutex> g(b->m);
-                --b->inflight;
-                b->cv.notify_all();
-            }
-        };
-        inflight_guard ig(b);
-        std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
-        ICL_TRY(icl_read_image_224(ctx, path, img.data())); // decode + resize run on the caller's thread, in parallel with other callers
-        icl_file_req me;
-        me.img = img.data();
-        me.out = out;
-        me.head = head;
-        std::unique_lock<std::mutex> lk(b->m);
-        b->pending.push_back(&me);
-        b->cv.notify_all(); // a waiting leader re-checks whether its batch is full / everybody who entered is queued
-        while (!me.done) {
-            if (b->leader) { // someone else is collecting or running a batch: wait for my row (or for the leadership)
-                b->cv.wait(lk);
-                continue;
-            }
-            b->leader = true;
-            // From here on this thread owes every request it takes a result: whatever goes wrong (bad_alloc in the slab copies,
-            // an exception out of the forward pass) each taken request is completed with an error, the leadership is given up and
-            // everybody is woken -- a leader that left with `leader` still set would block every later caller for good.
-            std::vector<icl_file_req *> take;
-            auto finish = [&](int rc, const char *why) { // lock held
-                for (icl_file_req *r : take)
-                    if (!r->done) {
-                        if (rc != ICL_OK) {
-                            r->rc = rc;
-                            try {
-                                r->err = why;
-                            } catch (...) {
-                            }
-                        }
-                        r->done = true;
-                    }
-                b->leader = false;
-                b->cv.notify_all(); // followers pick up their rows; one of the still-pending callers becomes the next leader
-            };
-            try {
-                // the window only matters while other callers are still decoding: a lone caller (or the last of a burst) runs at once
-                if (b->window_us > 0)
-                    b->cv.wait_for(lk, std::chrono::microseconds(b->window_us),
-                                   [&] { return (int)b->pending.size() >= b->max_batch || (int)b->pending.size() >= b->inflight; });
-                take.swap(b->pending);
-                if ((int)take.size() > b->max_batch) {
-                    b->pending.assign(take.begin() + b->max_batch, take.end());
-                    take.resize((size_t)b->max_batch);
-                }
-                const int prec = b->prec;
-                const bool give_up = b->fail_next; // icl_set_file_options(ICL_FILE_FAIL_NEXT_LEADER): one leader fails as if out of memory
-                b->fail_next = false;
-                lk.unlock();
-                if (give_up) throw std::bad_alloc();
-                for (int hd : {ICL_HEAD_POOLED, ICL_HEAD_DENSE0}) { // one forward pass per requested head
-                    std::vector<icl_file_req *> grp;
-                    for (icl_file_req *r : take)
-                        if (r->head == hd) grp.push_back(r);
-                    if (grp.empty()) continue;
-                    std::vector<uint8_t> slab(grp.size() * (size_t)ICL_IMG_BYTES);
-                    std::vector<float> res(grp.size() * (size_t)hd);
-                    for (size_t i = 0; i < grp.size(); ++i) memcpy(&slab[i * (size_t)ICL_IMG_BYTES], grp[i]->img, (size_t)ICL_IMG_BYTES);
-                    const int rc = icl_embed_u8(ctx, slab.data(), (int64_t)grp.size(), hd, prec, res.data());
-                    const std::string err = rc ? ctx->err : std::string();
-                    for (size_t i = 0; i < grp.size(); ++i) {
-                        grp[i]->rc = rc;
-                        grp[i]->err = err;
-                        if (rc == ICL_OK) memcpy(grp[i]->out, &res[i * (size_t)hd], (size_t)hd * 4);
-                    }
-                }
-                lk.lock();
-                b->batches += 1;
-                b->images += (int64_t)take.size();
-                finish(ICL_OK, "");
-            } catch (...) {
-                if (!lk.owns_lock()) lk.lock();
-                if (take.empty()) take.swap(b->pending); // failed before the batch was cut: nobody may be left waiting for this leader
-                finish(ICL_ERR_NOMEM, "icl_embed_file: the batch leader ran out of memory");
-            }
-        }
-        if (me.rc != ICL_OK) return icl_fail(ctx, me.rc, "%s", me.err.c_str());
-        return ICL_OK;
-    });
-}

@@ -9,6 +9,7 @@
 //                     launch: reads the block input once, writes the block output once (1 645 -> 822 MB per block).
 #pragma once
 #include "mfma_tile.h"
+#include "resnet_model.h" // STEM_K, STEM_ROWK, ST2_K: the weight layouts the loader packs
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -74,8 +75,6 @@ __device__ __forceinline__ uint32_t pack_relu_bf16x2(float a, float b)
 // the next one.  Pooling takes the maximum of the ROUNDED conv outputs (rounding is monotonic: equal to rounding the
 // maximum), so the result is bit-identical to conv0 -> store -> maxpool_kernel in both precisions.
 // ------------------------------------------------------------------------------------------------------------
-#define STEM_K 192
-#define STEM_ROWK 24         /* k slots per filter row (21 used) */
 #define STEM_PW 120          /* patch row stride in bytes: 1 (alignment) + 37 pixels * 3 = 112, + slack for the padded slots, 4-aligned */
 #define STEM_PH 21
 #define SP_STRIPS 8
@@ -328,7 +327,6 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const uint8_t *__restric
 // owns the output channels 16w .. 16w+15 for all 128 pixels of a tile; the shift is the accumulator's initial value.
 // Tile walk, carried conv row and pooling as in stem_pool_kernel.  Pixels are byte / 255 rounded to bf16, as before.
 // ------------------------------------------------------------------------------------------------------------
-#define ST2_K 224            /* 7 filter rows x 8 kw slots x 4 channel slots */
 #define ST2_PW 40            /* patch row: 37 pixels used (+ the kw padding's reach), 8 bytes each */
 #define ST2_RAWW 120         /* raw u8 patch row stride (as STEM_PW) */
 static constexpr size_t stem2_lds_bytes()

@@ -38,6 +38,7 @@
 
 #include "icl_common.h"
 #include "mfma_tile.h"
+#include "resnet_model.h" // icl_embed_dev_locked
 #include "ward_value.h" // ward_sqdist_thread, ward_pair_value, ward_scale, ward_merge_elem (shared with ward_many.hip)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -5730,7 +5731,6 @@ extern "C" int icl_cluster_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_
 // stream as soon as the batch that completes them has been enqueued (behind its event), and run on the vector ALUs beside the
 // later batches' MFMA kernels.  Results are those of icl_embed_u8_dev + icl_cluster_dev, bit for bit: the same kernels compute
 // the same rows, only earlier.  d_E (device, n x 2048) receives the pooled embeddings.
-int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head, int prec, float *d_out); // resnet.hip
 extern "C" int icl_embed_cluster_dev(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int prec, int32_t min_size, int32_t max_size, int update, int flags,
                                      float *d_E, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters)
 {

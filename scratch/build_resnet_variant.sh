@@ -4,4 +4,4 @@ name=$1; shift
 mkdir -p /root/repo/scratch/so
 cd /root/repo/imageclust_amd/csrc && make -s >/dev/null 2>&1
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -I../../include "$@" -c resnet.hip -o /tmp/resnet_$name.o 2>&1 | grep -E "error"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../../scratch/so/lib_$name.so icl_core.o ward.o /tmp/resnet_$name.o distance_mfma.o distance_i8.o onnx_reader.o jpeg_decode.o png_decode.o multi_gpu.o && ls -la ../../scratch/so/lib_$name.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../../scratch/so/lib_$name.so $(ls *.o | grep -v "^resnet\.o$") /tmp/resnet_$name.o && ls -la ../../scratch/so/lib_$name.so

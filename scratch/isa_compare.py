@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""Compare two device-only assembly listings kernel by kernel: isa_compare.py parent.s branch.s [more.s ...]
+
+For every .amdhsa_kernel of the first two files: the text from the kernel's label to the end of the function (every s_endpgm) and the
+.amdhsa_* descriptor block (registers, LDS, scratch) must be the same text.  Emission order is ignored.  Every further
+file must hold no kernel at all (host-only units).  Exit status 1 on any difference.
+
+The listings come from
+  hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include --cuda-device-only -S UNIT.hip -o UNIT.s
+run in imageclust_amd/csrc.
+"""
+import re
+import sys
+
+
+def kernels(path):
+    lines = open(path).read().split("\n")
+    out = {}
+    label = {ln.split(";")[0].strip(): i for i, ln in enumerate(lines) if ln[:1] not in (" ", "\t", "")}
+    for i, ln in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
+        if not m:
+            continue
+        name = m.group(1)
+        j = i
+        while not lines[j].strip().startswith(".end_amdhsa_kernel"):
+            j += 1
+        desc = "\n".join(x.strip() for x in lines[i:j + 1])
+        a = label[name + ":"]
+        b = a
+        while not lines[b].startswith(".Lfunc_end"):  # past the last s_endpgm of the function
+            b += 1
+        # block labels carry the function's emission index (.LBB<index>_<block>): drop the index, keep everything else
+        out[name] = (re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b])), desc)
+    return out
+
+
+def main():
+    pa, pb, rest = sys.argv[1], sys.argv[2], sys.argv[3:]
+    A, B = kernels(pa), kernels(pb)
+    bad = 0
+    print("%s: %d kernels, %s: %d kernels, same names: %s" % (pa, len(A), pb, len(B), sorted(A) == sorted(B)))
+    for name in sorted(set(A) | set(B)):
+        if name not in A or name not in B:
+            verdict = "only in " + (pa if name in A else pb)
+        else:
+            verdict = "identical" if A[name] == B[name] else "differs (%s)" % ("code" if A[name][0] != B[name][0] else "descriptor")
+        bad += verdict != "identical"
+        print("  %-9s %s" % (verdict, name))
+    for p in rest:
+        n = len(kernels(p))
+        bad += n != 0
+        print("%s: %d kernels (host-only unit: expected 0)" % (p, n))
+    print("ALL IDENTICAL" if not bad else "%d DIFFERENCES" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
