@@ -147,7 +147,7 @@ struct ward_batch_state {
     unsigned long long dbg[8], dbg_t0, dbg2[3], dbg3[4], dbg4[4], dbg5[4], dbg6[8], dbg7[4]; // in-kernel stage timers
     unsigned long long rf_stat[8];   // distance bounds: scans that found a bound on top, collecting passes, evaluation rounds, entries evaluated: [0..3] merge loop, [4..7] initial row minima
 #endif
-    int32_t blk_next, blk_pad;       // the persistent main workgroups' block counter (zeroed every step by ward_interleave_kernel)
+    int32_t blk_next, blk_pad;       // the persistent main workgroups' block counter (zeroed every step by ward_interleave_kernel / ward_finish_data_kernel)
     // phase A of the spare workgroups (each scans ONE slice of the row caches): matched rows, candidate streams, flags
     int32_t pa_flag[WB_R], pa_cnt[WB_R];           // pa_flag[wg] == epoch: slice wg has been published
     int32_t pa_rows[WB_R][WB_PA_CAP];              // rows of the slice whose cached partner is a member of the batch
@@ -170,6 +170,23 @@ struct ward_state {
     unsigned int bound_viol; // exact values found below the lower bound they replace (wcheck_bound): must stay 0
     float lb_g1, lb_delta2;  // lb mode (ward_update_lb_kernel): the constants of ward_lb_value, set by ward_lb_consts_kernel from the data's norms
     ward_batch_state B;      // batched exact mode
+};
+
+// Key of the workspace's captured graph: every launch argument the captured steps carry BY VALUE that can differ between two calls which keep
+// the workspace (same n, d and row pitch -- every buffer address, grid and LDS size follows from those).  A replay under a stale key would be a
+// wrong clustering, not an error.  Built by ward_graph_ensure from the call's plan and wrefine record.
+struct ward_graph_key {
+    int rows = -1;             // ICL_ROWS_*: which kernels a step launches ...
+    bool lw = false;           // ... and the update mode (the one-merge-per-step loop reports one row mode for both)
+    int max_size = -1;         // (with the row mode it also decides whether the launches carry the packed column words)
+    const float *E = nullptr;  // the embeddings' address (scans that evaluate flagged entries); null: the rows hold values only
+    float ceps = -1.0f;
+    const void *ex = nullptr;  // which kind of bounds the scans' upper bounds are made for (wrefine::ex)
+    const void *stat = nullptr; // wrefine::stat (ICL_WARD_TIMERS builds: ICL_WARD_STATS is read per call)
+    bool operator==(const ward_graph_key &o) const
+    {
+        return rows == o.rows && lw == o.lw && max_size == o.max_size && E == o.E && ceps == o.ceps && ex == o.ex && stat == o.stat;
+    }
 };
 
 struct icl_ward_ws {
@@ -210,11 +227,7 @@ struct icl_ward_ws {
     int64_t *fc_out = nullptr;
     // hipGraph of GRAPH_STEPS merge steps (all step-varying state lives in device memory, so one capture replays)
     hipGraphExec_t graph_exec = nullptr;
-    int graph_max_size = -1;
-    int graph_lw = -1;
-    const float *graph_E = nullptr; // the captured launches carry the embeddings' address (scans that evaluate flagged entries): part of the graph's key
-    float graph_ceps = -1.0f;
-    const void *graph_ex = nullptr; // ... and which kind of bounds the scans' upper bounds are made for (wrefine::ex)
+    ward_graph_key graph_key;  // what graph_exec was captured for
     size_t upd_attr_bytes = 0; // the kernels' > 64 KB dynamic-LDS opt-in made on this context's device
     bool wx_attr = false;
 };
@@ -4662,38 +4675,48 @@ __global__ __launch_bounds__(256) void ward_unpack_span_kernel(const float *__re
     }
 }
 
+// ICL_WARD_BATCH=0 (read once per process): the one-merge-per-step pipeline, kept as the witness of the parity tests
+static bool ward_batch_env()
+{
+    static const bool on = [] {
+        const char *e = getenv("ICL_WARD_BATCH");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
+// Do the rows of ComputeInitialDistanceMatrix this context computes hold matrix-core lower bounds (flagged entries, made exact on demand by
+// the row scans) or exact values?  ONE rule for the clustering call (its own rows) and for icl_ward_distance_rows_dev (rows computed for another
+// GPU's matrix): every context of a job must carry the same icl_set_ward_options.
+static bool ward_rows_use_bound(const icl_ctx *ctx, int64_t n, int d)
+{
+    return d >= 1 && d <= 8192 && n < (1LL << 29) && (ctx->ward_dist >= 2 || (ctx->ward_dist == 0 && n >= 4096));
+}
+// May the bound-rows loop run (ICL_DIST_LWBOUND: the rows of new clusters are Lance-Williams lower bounds too, ward_update_lb_kernel)?  It needs the
+// bounds of the initial matrix, whole k-groups and the batched loop on one GPU (auto: wherever the bounds of the initial matrix are; ICL_DIST_BOUND
+// keeps exact rows).  ONE rule for the matrix layout (ward_wide_alloc) and for the loop (ward_make_plan, which also needs the packed column words).
+static bool ward_lb_rows(const icl_ctx *ctx, int64_t n, int d)
+{
+    return ward_rows_use_bound(ctx, n, d) && (ctx->ward_dist == ICL_DIST_LWBOUND || ctx->ward_dist == ICL_DIST_AUTO) && (d & 3) == 0 && !ctx->shard && ward_batch_env();
+}
+
 // COMPLETE ROWS (round 5): should the matrix of this (context, n, d) have one column per CREATION ID (row pitch 2 n + 4 instead of n: 8 n^2 bytes
 // instead of 4 n^2)?  The bound-rows loop then keeps every row complete -- row x holds the pair (x, y) for EVERY live y, older or younger -- so the
 // Lance-Williams recurrence reads two contiguous rows instead of walking a column of the matrix (ward_update_lb_kernel).  ONE rule from the
 // context's options, n and d alone, so that icl_ward_prepare / icl_ward_unpack_spans_dev / the clustering call agree on the pitch: wherever the
 // bound-rows loop may run (ward_rows_use_bound, one GPU, whole k-groups) and the wider matrix takes at most half of the device's memory
 // (n <= ~134 000 on 288 GB; ICL_WARD_WIDE=0 keeps the 4 n^2 layout -- tests and A/B runs --, =1 lifts the memory rule).
-static bool ward_rows_use_bound(const icl_ctx *ctx, int64_t n, int d);
-static bool ward_batch_env();
 static bool ward_wide_alloc(const icl_ctx *ctx, int64_t n, int d)
 {
     const char *e = getenv("ICL_WARD_WIDE");
     if (e && e[0] == '0') return false;
     if (ctx->ward_wide_fail_n > 0 && n >= ctx->ward_wide_fail_n) return false; // (the wider matrix did not fit at this size before: ward_ensure)
-    if (!(ward_rows_use_bound(ctx, n, d) && (ctx->ward_dist == ICL_DIST_LWBOUND || ctx->ward_dist == ICL_DIST_AUTO) && (d & 3) == 0 && !ctx->shard && ward_batch_env())) return false;
+    if (!ward_lb_rows(ctx, n, d)) return false;
     const int64_t M = (2 * n + 4 + 63) / 64 * 64;
     const double bytes = 4.0 * (double)(n + WB_KMAX) * (double)M;
     return (e && e[0] == '1') || bytes <= 0.5 * (double)ctx->prop.totalGlobalMem;
 }
 
-static int ward_ensure_impl(icl_ctx *ctx, int64_t n, int d);
-// (the 8 n^2-byte layout is a preference, not a requirement: should its allocation fail -- other tenants on the device -- the 4 n^2 one is taken,
-// and the context remembers the size so that prepare / unpack / cluster keep agreeing on the pitch)
-static int ward_ensure(icl_ctx *ctx, int64_t n, int d)
-{
-    int rc = ward_ensure_impl(ctx, n, d);
-    if (rc == ICL_ERR_NOMEM && ward_wide_alloc(ctx, n, d)) {
-        (void)hipGetLastError();
-        ctx->ward_wide_fail_n = n;
-        rc = ward_ensure_impl(ctx, n, d);
-    }
-    return rc;
-}
 static int ward_ensure_impl(icl_ctx *ctx, int64_t n, int d)
 {
     if (!ctx->ward) ctx->ward = new icl_ward_ws();
@@ -4768,6 +4791,18 @@ static int ward_ensure_impl(icl_ctx *ctx, int64_t n, int d)
         w->capD = d;
     }
     return ICL_OK;
+}
+// (the 8 n^2-byte layout is a preference, not a requirement: should its allocation fail -- other tenants on the device -- the 4 n^2 one is taken,
+// and the context remembers the size so that prepare / unpack / cluster keep agreeing on the pitch)
+static int ward_ensure(icl_ctx *ctx, int64_t n, int d)
+{
+    int rc = ward_ensure_impl(ctx, n, d);
+    if (rc == ICL_ERR_NOMEM && ward_wide_alloc(ctx, n, d)) {
+        (void)hipGetLastError();
+        ctx->ward_wide_fail_n = n;
+        rc = ward_ensure_impl(ctx, n, d);
+    }
+    return rc;
 }
 
 // A rank that only computes distance rows needs the row-offset table, not the 8 n^2-byte triangle.
@@ -4991,26 +5026,6 @@ int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_s
     return rc;
 }
 
-// own_lo / own_hi: rows of the initial distance matrix this call computes itself (whole 128-row tile rows; everything by
-// default).  The other rows must already sit in the matrix (icl_ward_unpack_spans_dev): the multi-GPU paths compute them on
-// the other GPUs, and this GPU reads them over xGMI.
-// ICL_WARD_BATCH=0 (read once per process): the one-merge-per-step pipeline, kept as the witness of the parity tests
-static bool ward_batch_env()
-{
-    static const bool on = [] {
-        const char *e = getenv("ICL_WARD_BATCH");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Do the rows of ComputeInitialDistanceMatrix this context computes hold matrix-core lower bounds (flagged entries, made exact on demand by
-// the row scans) or exact values?  ONE rule for the clustering call (its own rows) and for icl_ward_distance_rows_dev (rows computed for another
-// GPU's matrix): every context of a job must carry the same icl_set_ward_options.
-static bool ward_rows_use_bound(const icl_ctx *ctx, int64_t n, int d)
-{
-    return d >= 1 && d <= 8192 && n < (1LL << 29) && (ctx->ward_dist >= 2 || (ctx->ward_dist == 0 && n >= 4096));
-}
 // error constants of the bound (DESIGN.md section 3 "The bound"): ceps = (gamma / 2 + 16 u)(1 + 64 u), gam = (1 + u)^(D + 2) - 1, both rounded up
 static void ward_bound_consts(int d, int K, float *ceps, float *gam)
 {
@@ -5071,129 +5086,206 @@ __global__ __launch_bounds__(256) void ward_symmetrize_kernel(float *__restrict_
 // spare workgroups of a batched update launch (see WB_R)
 static int ward_nspare(const icl_ctx *ctx, bool lb_rows, bool sharded) { return (lb_rows && !sharded && ctx->prop.multiProcessorCount >= 256) ? WB_NSP_LB : WB_NSP_X; }
 
-static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update,
-                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int64_t own_lo = 0, int64_t own_hi = -1)
+// ---- the clustering call's host driver: cluster_locked (below) = ward_check_args -> ward_make_plan -> ward_init_ws -> ward_fill -> ward_run_single /
+// ward_run_batched -> ward_collect; every decision of a call is made once, in its ward_plan.
+// hip_guard releases a HIP resource on every way out of a scope (ICL_HIP / ICL_TRY / icl_fail return early)
+template <class T, hipError_t (*Release)(T)> struct hip_guard {
+    T p = nullptr;
+    ~hip_guard() { if (p) (void)Release(p); }
+};
+using ev_guard = hip_guard<hipEvent_t, hipEventDestroy>;
+using dev_guard = hip_guard<void *, hipFree>;
+using pin_guard = hip_guard<void *, hipHostFree>;
+// what one clustering call holds beside the workspace: all of it until cluster_locked returns (a hipFree / hipHostFree in mid-call would wait for the device)
+struct ward_call {
+    struct shard_guard { // a replica of a sharded group call that leaves early releases the replicas waiting for it (icl_ward_shard::wait)
+        icl_ward_shard *s = nullptr;
+        bool ok = false;
+        ~shard_guard() { if (s && !ok) s->fail(); }
+    } shard;
+    ev_guard e0, e1, e2, ev[2]; // call start, distance stage enqueued, merge loop enqueued; the batched loop's two state snapshots ...
+    pin_guard pin;              // ... and their pinned memory
+    dev_guard ec, pq;           // distance bounds: the centred copy of E, the integer GEMM's scratch
+};
+
+constexpr int GRAPH_STEPS = 64;
+enum { WARD_FILL_EXACT, WARD_FILL_BOUND_F32, WARD_FILL_BOUND_I8, WARD_FILL_FAST }; // how a call fills its own rows of the initial matrix
+struct ward_plan {
+    int64_t n, T, own_lo, own_hi; // T: merges needed for len(clusters) == k (clustering.go:220); [own_lo, own_hi): rows of the initial matrix this call computes
+    int d, max_size;
+    bool lw, batched;             // ICL_UPDATE_LW; the batched loops (ICL_WARD_BATCH): exact centroid chains, or Lance-Williams rows (lw)
+    bool use_bound, lbm, wide;    // own rows hold flagged lower bounds; the bound-rows loop (new rows are Lance-Williams lower bounds too); complete rows (ward_wide_alloc)
+    int rows, fill;               // ICL_ROWS_* (icl_last_ward_mode); WARD_FILL_*: what the call WANTS -- should the int8 scratch not fit, ward_fill takes the f32 GEMM
+    bool use_rowub;               // the integer GEMM's epilogue leaves every row's smallest upper bound for the initial minima (ICL_DIST_ROWUB=0: A/B switch, they make their own first pass)
+    // the row scans read size + creation id of a column as ONE word (w->mpk; null: off) when 2 n + 4 creation ids fit beside the bits of max_size
+    // (not in FAST mode: the packed scans compare (value bits, id) keys, which needs values >= +0 -- exact Ward values are, the MFMA estimates need not be)
+    int pk_bits;
+    uint32_t *mpk;
+    icl_ward_shard *sh;           // strip-sharded loop (a group's replicas, multi_gpu.hip): this replica's main workgroups take the blocks == sh_rank (mod sh_n)
+    int sh_n, sh_rank, nsp;
+    int32_t *fdrec;               // the express step's data phase runs in ward_finish_data_kernel from a record the finish kernel leaves behind cnewI (null: it does not)
+    bool prof_update, use_graph;
+    // launch shapes.  One merge per step: 64 slots per workgroup + preselect + compaction workgroups; LDS = new centroid image + p ring
+    // batched: main workgroups are persistent, at most one per CU (they draw blocks from a counter), fewer when the input has fewer blocks; lb: WL_U creation ids per lane
+    unsigned upd_blocks, lw_blocks, wx_blocks, lw_blocks_b, lb_blocks, fd_blocks, il_blocks, pull_blocks;
+    int dqp, dqb;
+    size_t upd_lds, wx_lds;
+};
+
+static int ward_check_args(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, int update)
 {
     int64_t k = 0;
     if (icl_calc_optimal_clusters(n, min_size, max_size, &k) != ICL_OK)
         return icl_fail(ctx, ICL_ERR_CONSTRAINT, "cannot satisfy cluster size constraints with total items (%lld), minSize (%d), and maxSize (%d)",
                         (long long)n, min_size, max_size);
     if (update != ICL_UPDATE_EXACT && update != ICL_UPDATE_LW) return icl_fail(ctx, ICL_ERR_ARG, "unknown update mode %d", update);
-    const bool lw = update == ICL_UPDATE_LW;
     if (n >= (1LL << 30)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "n too large");
-    ctx->last.merges.clear();
-    *n_clusters = 0;
-    const int64_t T = n - k; // merges needed for len(clusters) == k (clustering.go:220)
-    if (n == 0) return ICL_OK;
-    // a replica of a sharded group call that leaves early releases the replicas waiting for it (icl_ward_shard::wait)
-    struct shard_guard {
-        icl_ward_shard *s;
-        bool ok = false;
-        ~shard_guard() { if (s && !ok) s->fail(); }
-    } shg{ctx->shard};
-    ICL_TRY(ward_ensure(ctx, n, d));
-    icl_ward_ws *w = ctx->ward;
-    // the row scans read size + creation id of a column as ONE word when 2 n + 4 creation ids fit beside the bits of max_size
-    const int pk_bits = max_size >= 1 ? 32 - __builtin_clz((unsigned)max_size) : 32;
-    // (not in FAST mode: the packed scans compare (value bits, id) keys, which needs values >= +0 -- exact Ward values are, the MFMA estimates need not be)
-    uint32_t *mpk = (!lw && pk_bits < 32 && (uint64_t)(2 * n + 4) <= (1ull << (32 - pk_bits))) ? w->mpk : nullptr;
-    // every early return below (ICL_HIP / ICL_TRY / icl_fail) releases these through the guards' destructors
-    struct ev_guard {
-        hipEvent_t e = nullptr;
-        ~ev_guard() { if (e) (void)hipEventDestroy(e); }
-    } g0, g1, g2, gv0, gv1;
-    struct pin_guard {
-        void *p = nullptr;
-        ~pin_guard() { if (p) (void)hipHostFree(p); }
-    } gpin;
-    ICL_HIP(ctx, hipEventCreate(&g0.e));
-    ICL_HIP(ctx, hipEventCreate(&g1.e));
-    ICL_HIP(ctx, hipEventCreate(&g2.e));
-    hipEvent_t &e0 = g0.e, &e1 = g1.e, &e2 = g2.e;
-    ICL_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    return ICL_OK;
+}
 
-    {
-        const int64_t cnt = std::max(std::max(w->S, w->M), w->ld);
-        hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)icl_ceil_div(cnt, 256)), dim3(256), 0, ctx->stream, n, w->S, w->M, w->ld,
-                           w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->st, (int32_t)T, mpk, pk_bits);
-        if (d > 0) {
-            hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)icl_ceil_div(w->S, 32), (unsigned)icl_ceil_div((d + 3) / 4, 32)), dim3(256), 0,
-                               ctx->stream, d_E, n, d, w->S, w->CT);
-            ICL_HIP(ctx, hipMemcpyAsync(w->Crow, d_E, (size_t)n * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        ICL_HIP(ctx, hipGetLastError());
-    }
-    // ComputeInitialDistanceMatrix (clustering.go:217) into the singleton rows: exact tile, or the MFMA tile in FAST mode
+// (arguments that passed ward_check_args, n > 0, the workspace of ward_ensure(ctx, n, d) in place)
+static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi, ward_plan *out)
+{
+    const icl_ward_ws *w = ctx->ward;
+    ward_plan p{};
+    int64_t k = 0;
+    (void)icl_calc_optimal_clusters(n, min_size, max_size, &k);
+    p.n = n, p.T = n - k, p.d = d, p.max_size = max_size;
+    p.lw = update == ICL_UPDATE_LW;
+    p.batched = ward_batch_env();
     if (own_hi < 0) own_hi = n;
     if (own_lo < 0 || own_lo > own_hi || own_hi > n || own_lo % DT_TILE || (own_hi % DT_TILE && own_hi != n))
         return icl_fail(ctx, ICL_ERR_ARG, "own rows [%lld, %lld) must be whole 128-row tile rows of [0, %lld)", (long long)own_lo, (long long)own_hi, (long long)n);
-    // Exact mode, the rows this call computes itself: by default PROVEN LOWER BOUNDS from the matrix cores, made exact on demand by
-    // the row scans (distance_mfma.hip "Distance BOUNDS", scan_row_refine above); ctx->ward_dist == 1 (icl_set_ward_options) or shapes
-    // the bound does not cover: every value by ward_dist_exact_kernel.  Rows deposited by other GPUs are values.
+    if (p.lw && (own_lo != 0 || own_hi != n)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "FAST mode builds the whole distance matrix on one GPU");
+    p.own_lo = own_lo, p.own_hi = own_hi;
+    p.pk_bits = max_size >= 1 ? 32 - __builtin_clz((unsigned)max_size) : 32;
+    p.mpk = (!p.lw && p.pk_bits < 32 && (uint64_t)(2 * n + 4) <= (1ull << (32 - p.pk_bits))) ? w->mpk : nullptr;
+    // Exact mode, the rows this call computes itself: by default PROVEN LOWER BOUNDS from the matrix cores, made exact on demand by the row scans (distance_mfma.hip
+    // "Distance BOUNDS", scan_row_refine above); ctx->ward_dist == 1 (icl_set_ward_options) or shapes the bound does not cover: every value by ward_dist_exact_kernel.
+    p.use_bound = !p.lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
+    p.lbm = p.use_bound && p.mpk && ward_lb_rows(ctx, n, d);
+    p.wide = p.lbm && w->wide_alloc;
+    p.rows = !p.batched ? ICL_ROWS_SINGLE : p.lw ? ICL_ROWS_LW_FAST : p.lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH;
+    p.fill = p.lw ? WARD_FILL_FAST : WARD_FILL_EXACT;
+    if (p.use_bound) {
+        // the bounds themselves: from the integer GEMM (distance_i8.hip: exact int8 matrix-core arithmetic on a fixed-point image of the rows, 3x
+        // faster and tighter) where this call fills the whole matrix itself and D <= 2048; from the f32 fmaf-chain GEMM otherwise -- rows
+        // delivered by other GPUs carry that kind (icl_ward_distance_rows_dev), and one matrix holds one kind (ICL_DIST_I8=0: A/B runs, tests)
+        const char *e8 = getenv("ICL_DIST_I8"), *eru = getenv("ICL_DIST_ROWUB");
+        p.fill = (own_lo == 0 && own_hi == n && icl_dist_i8_usable(n, d) && !(e8 && e8[0] == '0')) ? WARD_FILL_BOUND_I8 : WARD_FILL_BOUND_F32;
+        p.use_rowub = !(eru && eru[0] == '0');
+    }
+    p.sh = p.lw ? nullptr : ctx->shard;
+    p.sh_n = p.sh ? p.sh->G : 1, p.sh_rank = p.sh ? ctx->shard_rank : 0;
+    p.nsp = ward_nspare(ctx, p.lbm, ctx->shard != nullptr);
+    p.fdrec = (!p.lw && (d & 3) == 0) ? reinterpret_cast<int32_t *>(w->cnewI + 16 * w->cn_stride) : nullptr;
+    p.prof_update = (ctx->prof_mask >> ICL_K_UPDATE) & 1;
+    p.use_graph = !(p.batched && p.sh) && !p.prof_update && p.T >= 2 * GRAPH_STEPS;
+    p.upd_blocks = (unsigned)(w->S / 64) + 2;
+    p.lw_blocks = (unsigned)icl_ceil_div(w->S, UPD_THREADS) + 1;
+    p.dqp = (int)upd_groups(d), p.dqb = (int)wb_groups(d);
+    p.upd_lds = (size_t)(p.dqp + UPD_PAD_G) * 16 + (size_t)2 * UPD_SG * 64 * 16;
+    p.wx_lds = (size_t)WX_R * WX_STAGE_F4 * 16;
+    p.wx_blocks = (unsigned)std::min<int64_t>(icl_ceil_div(w->S / 64, p.sh_n), (int64_t)ctx->prop.multiProcessorCount) + 2 + p.nsp;
+    p.lw_blocks_b = (unsigned)icl_ceil_div(w->S, WB_THREADS) + 2 + p.nsp;
+    p.lb_blocks = (unsigned)icl_ceil_div(w->M, WL_SLOTS * WL_U) + 2 + p.nsp;
+    p.fd_blocks = (unsigned)icl_ceil_div((WB_K / 2) * w->cn_stride, WB_FD_THREADS);
+    p.il_blocks = (unsigned)icl_ceil_div((WB_K / 2) * w->cn_stride, 256);
+    p.pull_blocks = (unsigned)std::min<int64_t>(w->S / 64, 2048);
+    *out = p;
+    return ICL_OK;
+}
+
+// the tables of a fresh run on the workspace (T = 0, no packed words: callers that only want the singleton rows addressable through rowoff)
+static void ward_launch_init(icl_ward_ws *w, int64_t n, int64_t T, uint32_t *mpk, int pk_bits, hipStream_t strm)
+{
+    const int64_t cnt = std::max(std::max(w->S, w->M), w->ld);
+    hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)icl_ceil_div(cnt, 256)), dim3(256), 0, strm, n, w->S, w->M, w->ld,
+                       w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->st, (int32_t)T, mpk, pk_bits);
+}
+static int ward_init_ws(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const float *d_E)
+{
+    ward_launch_init(w, p.n, p.T, p.mpk, p.pk_bits, ctx->stream);
+    if (p.d > 0) {
+        hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)icl_ceil_div(w->S, 32), (unsigned)icl_ceil_div((p.d + 3) / 4, 32)), dim3(256), 0, ctx->stream, d_E, p.n, p.d, w->S, w->CT);
+        ICL_HIP(ctx, hipMemcpyAsync(w->Crow, d_E, (size_t)p.n * p.d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ICL_HIP(ctx, hipGetLastError());
+    return ICL_OK;
+}
+
+// ---- the bounds prologue, shared by the clustering call (the workspace's buffers) and icl_ward_distance_rows_dev / the bounds check (temporaries):
+// E - mu in K = d rounded up to 32 columns, the centred norms and the bound's error constants; then the f32 bounds of a run of rows.  Two
+// functions because the clustering call's ward_lb_consts_kernel launch and its integer-GEMM alternative sit between the two.
+struct ward_centred {
+    double *colsum;   // [icl_dist_colsum_doubles(d)]
+    float *ec, *nrm;  // [n][K], [n]
+    const void *zero; // 256 zero bytes
+    int K;            // filled by ward_centre, like ceps and gam
+    float ceps, gam;
+};
+static int ward_bound_K(int d) { return (d + 31) / 32 * 32; }
+static int ward_centre(icl_ctx *ctx, const float *d_E, int64_t n, int d, ward_centred *b)
+{
+    b->K = ward_bound_K(d);
+    ward_bound_consts(d, b->K, &b->ceps, &b->gam);
+    return icl_dist_center_launch(ctx, d_E, n, d, b->K, b->colsum, b->ec, b->nrm, ctx->stream);
+}
+static int ward_bounds_f32(icl_ctx *ctx, const ward_centred &b, int64_t n, float *D, const int64_t *rowoff, int64_t row_lo, int64_t row_hi)
+{
+    return icl_dist_bound_launch(ctx, b.ec, b.nrm, b.zero, n, b.K, b.ceps, b.gam, D, rowoff, row_lo / DT_TILE, icl_ceil_div(row_hi, DT_TILE), ctx->stream);
+}
+
+// ComputeInitialDistanceMatrix (clustering.go:217) into the singleton rows -- exact tile, bounds, or the MFMA tile in FAST mode --, the check of foreign rows, the
+// initial row minima and the complete rows' mirror; *prf receives the record the merge loop's scans evaluate bounds with.  The rows outside [own_lo, own_hi) (whole
+// 128-row tile rows; none by default) must already sit in the matrix (icl_ward_unpack_spans_dev): the multi-GPU paths compute them on the other GPUs.
+static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const float *d_E, ward_call &c, wrefine *prf)
+{
+    const int64_t n = p.n, own_lo = p.own_lo, own_hi = p.own_hi;
+    const int d = p.d;
     wrefine rf{nullptr, nullptr, 0, 0, 0.0f, 0.0f, nullptr, 0.0f};
-    bool lbm = false;
     bool have_rowub = false; // the bounds kernel has left every row's smallest upper bound (w->rowub)
-    struct free_guard {
-        void *p = nullptr;
-        ~free_guard() { if (p) (void)hipFree(p); }
-    } g_ec, g_pq;
-    const bool use_bound = !lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
-    if (lw) {
-        if (own_lo != 0 || own_hi != n) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "FAST mode builds the whole distance matrix on one GPU");
+    if (p.fill == WARD_FILL_FAST) {
         ICL_TRY(icl_dist_mfma_launch(ctx, d_E, n, d, w->Dtri, w->rowoff, 0));
-    } else if (use_bound) {
-        const int K = (d + 31) / 32 * 32;
-        if (hipMalloc(&g_ec.p, (size_t)n * K * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "centred copy of E (%lld x %d floats)", (long long)n, K);
-        float ceps, gam;
-        ward_bound_consts(d, K, &ceps, &gam);
-        unsigned long long *stat = nullptr;
+    } else if (p.use_bound) {
+        if (hipMalloc(&c.ec.p, (size_t)n * ward_bound_K(d) * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "centred copy of E (%lld x %d floats)", (long long)n, ward_bound_K(d));
+        ward_centred b{w->colsum, (float *)c.ec.p, w->nrm, w->zero};
+        ICL_TRY(ward_centre(ctx, d_E, n, d, &b));
+        rf = wrefine{d_E, w->nrm, n, d, b.ceps, b.gam, nullptr, 0.0f};
 #ifdef ICL_WARD_TIMERS
-        if (getenv("ICL_WARD_STATS")) stat = &w->st->B.rf_stat[0];
+        if (getenv("ICL_WARD_STATS")) rf.stat = &w->st->B.rf_stat[0];
 #endif
-        rf = wrefine{d_E, w->nrm, n, d, ceps, gam, stat, 0.0f};
         rf.viol = &w->st->bound_viol;
-        ICL_TRY(icl_dist_center_launch(ctx, d_E, n, d, K, w->colsum, (float *)g_ec.p, w->nrm, ctx->stream));
-        // lb mode (ICL_DIST_LWBOUND): the rows of new clusters are Lance-Williams lower bounds too (ward_update_lb_kernel); needs the packed
-        // column words, whole k-groups, the batched loop on one GPU
-        // (auto: wherever the bounds of the initial matrix are; ICL_DIST_BOUND keeps exact rows)
-        lbm = (ctx->ward_dist == ICL_DIST_LWBOUND || ctx->ward_dist == ICL_DIST_AUTO) && mpk && (d & 3) == 0 && !ctx->shard && ward_batch_env();
-        if (lbm) {
+        if (p.lbm) { // needs the packed column words, whole k-groups, the batched loop on one GPU (ward_lb_rows)
             rf.Crow = w->Crow;
             rf.id_slot = w->id_slot;
             rf.asz = w->asz;
             rf.lb = 1;
-            if (w->wide_alloc) { // complete rows, columns by creation id (ward_wide_alloc)
+            if (p.wide) { // complete rows, columns by creation id (ward_wide_alloc)
                 rf.wide = 1;
                 rf.Dm = w->Dtri;
                 rf.rom = w->rowoff;
             }
-            hipLaunchKernelGGL(ward_lb_consts_kernel, dim3(1), dim3(1024), 0, ctx->stream, w->nrm, w->colsum, n, d, max_size, w->st);
+            hipLaunchKernelGGL(ward_lb_consts_kernel, dim3(1), dim3(1024), 0, ctx->stream, w->nrm, w->colsum, n, d, p.max_size, w->st);
         }
-        // the bounds themselves: from the integer GEMM (distance_i8.hip: exact int8 matrix-core arithmetic on a fixed-point image of the rows, 3x
-        // faster and tighter) where this call fills the whole matrix itself and D <= 2048; from the f32 fmaf-chain GEMM otherwise -- rows
-        // delivered by other GPUs carry that kind (icl_ward_distance_rows_dev), and one matrix holds one kind (ICL_DIST_I8=0: A/B runs, tests)
-        const char *e8 = getenv("ICL_DIST_I8");
-        bool i8 = own_lo == 0 && own_hi == n && icl_dist_i8_usable(n, d) && !(e8 && e8[0] == '0');
-        if (i8 && hipMalloc(&g_pq.p, icl_dist_i8_pq_bytes(n, d)) != hipSuccess) { // (3 D bytes per row of scratch: should it not fit beside a 250 GB matrix -- the f32 GEMM needs none)
+        bool i8 = p.fill == WARD_FILL_BOUND_I8;
+        if (i8 && hipMalloc(&c.pq.p, icl_dist_i8_pq_bytes(n, d)) != hipSuccess) { // (3 D bytes per row of scratch: should it not fit beside a 250 GB matrix -- the f32 GEMM needs none)
             (void)hipGetLastError();
-            g_pq.p = nullptr;
+            c.pq.p = nullptr;
             i8 = false;
         }
-        const char *eru = getenv("ICL_DIST_ROWUB"); // (A/B switch: 0 = the initial minima make their own first pass)
-        const bool use_rowub = !(eru && eru[0] == '0');
         if (i8) {
             rf.l1 = w->bl1;
             rf.ex = w->bex;
-            ICL_TRY(icl_dist_bound_i8_launch(ctx, (const float *)g_ec.p, w->nrm, n, d, K, rf.gam, g_pq.p, w->bl1, w->bex, w->Dtri, w->rowoff, ctx->stream, use_rowub ? w->rowub : nullptr));
-            have_rowub = use_rowub;
+            ICL_TRY(icl_dist_bound_i8_launch(ctx, b.ec, w->nrm, n, d, b.K, rf.gam, c.pq.p, w->bl1, w->bex, w->Dtri, w->rowoff, ctx->stream, p.use_rowub ? w->rowub : nullptr));
+            have_rowub = p.use_rowub;
         } else
-        ICL_TRY(icl_dist_bound_launch(ctx, (const float *)g_ec.p, w->nrm, w->zero, n, K, rf.ceps, rf.gam, w->Dtri, w->rowoff, own_lo / DT_TILE,
-                                      icl_ceil_div(own_hi, DT_TILE), ctx->stream));
+            ICL_TRY(ward_bounds_f32(ctx, b, n, w->Dtri, w->rowoff, own_lo, own_hi));
     } else
         ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, w->Dtri, w->rowoff, 0, 0, own_lo / DT_TILE, icl_ceil_div(own_hi, DT_TILE)));
     // (rows computed on other GPUs were laid out into the matrix by icl_ward_unpack_spans_dev before this call: flagged bounds under the same rule
     // as the rows above -- icl_ward_distance_rows_dev -- so the scans below treat them like this GPU's own)
-    if (!use_bound && !lw && (own_lo > 0 || own_hi < n)) { // foreign rows taken as VALUES: a flagged entry would be read as a negative distance
+    if (!p.use_bound && !p.lw && (own_lo > 0 || own_hi < n)) { // foreign rows taken as VALUES: a flagged entry would be read as a negative distance
         ICL_HIP(ctx, hipMemsetAsync(&w->st->foreign_flag, 0, sizeof(int32_t), ctx->stream));
         hipLaunchKernelGGL(ward_foreign_flag_kernel, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, ctx->stream, w->Dtri, w->ld, n, own_lo, own_hi, &w->st->foreign_flag);
         int32_t found = 0;
@@ -5214,238 +5306,197 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
         // dependent additions, ~12 us whatever their number --, so the kernel is bound by rows in flight per CU, not by a row's scan rate
         // (dist_ms at N = 100 000: 187 -> 174 ms)
         hipLaunchKernelGGL(row_argmin_tri_kernel, dim3((int)std::min<int64_t>(n, 256 * 256)), dim3(256), 0, ctx->stream, w->Dtri, w->rowoff, w->asz, w->msz, w->mcid,
-                           max_size, n, w->rowmin, w->rownn, rf_init, have_rowub ? w->rowub : nullptr);
+                           p.max_size, n, w->rowmin, w->rownn, rf_init, have_rowub ? w->rowub : nullptr);
         if (rf.wide) { // (on a side stream beside the minima kernel: no gain, 94.7 against 93.6 ms for the stage; from the bounds kernel's epilogue: 12 ms against this kernel's 7.8)
             const unsigned nt64 = (unsigned)icl_ceil_div(n, 64);
             hipLaunchKernelGGL(ward_symmetrize_kernel, dim3(nt64, nt64), dim3(256), 0, ctx->stream, w->Dtri, w->ld, n);
         }
         ICL_HIP(ctx, hipGetLastError());
     }
-    ICL_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    *prf = rf;
+    return ICL_OK;
+}
 
-    // Merge loop: preselect(0), finish(0), then T steps of { update(t) with preselect(t+1) riding along } -> finish(t+1).  Every step-varying quantity lives in device memory
-    // (ward_state), so the launches are identical and steps past the target / past "no pair left" are no-ops:
-    // the loop is captured ONCE into a hipGraph of GRAPH_STEPS steps and replayed (launch-bound inner loop).
-    const unsigned upd_blocks = (unsigned)(w->S / 64) + 2; // 64 slots per workgroup + preselect + compaction workgroups
-    const int dqp = (int)upd_groups(d);
-    const size_t upd_lds = (size_t)(dqp + UPD_PAD_G) * 16 + (size_t)2 * UPD_SG * 64 * 16; // new centroid image + p ring
-    const bool batch_env = ward_batch_env();
-    if (!batch_env && upd_lds > 64 * 1024 && w->upd_attr_bytes < upd_lds) { // one-merge-per-step pipeline only; per context, i.e. per device
+// ---- the merge loop's steps.  Every step-varying quantity lives in device memory (ward_state), so the launches of a step are identical from
+// step to step and steps past the target / past "no pair left" are no-ops: GRAPH_STEPS of them are captured ONCE into a hipGraph and replayed
+// (launch-bound inner loop).  t: the step's number where the host knows it (the profile's work estimate; icl_prof_scope is a no-op unless
+// ICL_K_UPDATE is profiled, and a profiled call captures nothing).
+typedef void (*ward_step_fn)(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, int64_t t);
+
+// w->graph_exec = GRAPH_STEPS steps of `step` for this call's key (kept from the last call where the key is the same)
+static int ward_graph_ensure(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, ward_step_fn step)
+{
+    const ward_graph_key key{p.rows, p.lw, p.max_size, rf.E, rf.ceps, rf.ex, rf.stat};
+    if (w->graph_exec && w->graph_key == key) return ICL_OK;
+    if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
+    w->graph_exec = nullptr;
+    hipGraph_t graph = nullptr;
+    ICL_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    for (int g = 0; g < GRAPH_STEPS; ++g) step(ctx, w, p, rf, 0);
+    ICL_HIP(ctx, hipStreamEndCapture(ctx->stream, &graph));
+    hipError_t ge = hipGraphInstantiate(&w->graph_exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ge != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ge));
+    w->graph_key = key;
+    return ICL_OK;
+}
+
+// One merge per step (ICL_WARD_BATCH=0): preselect(0), finish(0), then T steps of { update(t) with preselect(t+1) riding along } -> finish(t+1).
+static void ward_finish_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p)
+{
+    hipLaunchKernelGGL(ward_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, p.n, p.d, w->S, w->CT, w->Crow, w->cnew, w->slot_id,
+                       w->id_slot, w->asz, w->rowmin, w->rownn, w->merges, w->rowoff, w->mcol, w->msz, w->mcid, w->ld, w->st);
+}
+// one step: update(t) [with preselect(t+1) as one of its workgroups] -> finish(t+1)
+static void ward_step_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, int64_t t)
+{
+    {
+        icl_prof_scope ps(ctx, ICL_K_UPDATE, 3.0 * (double)(p.n - t - 1) * p.d, 4.0 * (double)(p.n - t - 1) * p.d + 4.0 * (double)(p.n - t - 1));
+        if (p.lw)
+            hipLaunchKernelGGL(ward_update_lw_kernel, dim3(p.lw_blocks), dim3(UPD_THREADS), 0, ctx->stream, w->slot_id, w->asz, w->rowoff, w->mcol, w->msz,
+                               w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn);
+        else
+            hipLaunchKernelGGL(ward_update_exact_kernel, dim3(p.upd_blocks), dim3(UPD_THREADS), p.upd_lds, ctx->stream, p.d, p.dqp, w->S, w->CT, w->Crow,
+                               w->cnew, w->slot_id, w->asz, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, rf);
+    }
+    ward_finish_single(ctx, w, p);
+}
+static int ward_run_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf)
+{
+    if (p.upd_lds > 64 * 1024 && w->upd_attr_bytes < p.upd_lds) { // per context, i.e. per device
         hipFuncAttributes fa;
         ICL_HIP(ctx, hipFuncGetAttributes(&fa, (const void *)ward_update_exact_kernel));
-        if (upd_lds + fa.sharedSizeBytes > 160 * 1024) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "embedding dimension %d too large for the update kernel's LDS image", d);
-        ICL_HIP(ctx, hipFuncSetAttribute((const void *)ward_update_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)upd_lds));
-        w->upd_attr_bytes = upd_lds;
+        if (p.upd_lds + fa.sharedSizeBytes > 160 * 1024) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "embedding dimension %d too large for the update kernel's LDS image", p.d);
+        ICL_HIP(ctx, hipFuncSetAttribute((const void *)ward_update_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.upd_lds));
+        w->upd_attr_bytes = p.upd_lds;
     }
-    auto finish = [&]() {
-        hipLaunchKernelGGL(ward_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, d, w->S, w->CT, w->Crow, w->cnew, w->slot_id,
-                           w->id_slot, w->asz, w->rowmin, w->rownn, w->merges, w->rowoff, w->mcol, w->msz, w->mcid, w->ld, w->st);
-    };
-    const unsigned lw_blocks = (unsigned)icl_ceil_div(w->S, UPD_THREADS) + 1;
-    auto launch_update = [&]() {
-        if (lw) {
-            hipLaunchKernelGGL(ward_update_lw_kernel, dim3(lw_blocks), dim3(UPD_THREADS), 0, ctx->stream, w->slot_id, w->asz, w->rowoff, w->mcol, w->msz,
-                               w->mcid, w->Dtri, w->st, max_size, n, w->rowmin, w->rownn);
-            return;
-        }
-        hipLaunchKernelGGL(ward_update_exact_kernel, dim3(upd_blocks), dim3(UPD_THREADS), upd_lds, ctx->stream, d, dqp, w->S, w->CT, w->Crow,
-                           w->cnew, w->slot_id, w->asz, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, max_size, n, w->rowmin, w->rownn, rf);
-    };
-    // one step: update(t) [with preselect(t+1) as one of its workgroups] -> finish(t+1)
-    auto enqueue_step = [&](int64_t t, bool prof) {
-        if (prof) {
-            icl_prof_scope ps(ctx, ICL_K_UPDATE, 3.0 * (double)(n - t - 1) * d, 4.0 * (double)(n - t - 1) * d + 4.0 * (double)(n - t - 1));
-            launch_update();
-        } else {
-            launch_update();
-        }
-        finish();
-    };
-    const bool prof_update = (ctx->prof_mask >> ICL_K_UPDATE) & 1;
-    constexpr int GRAPH_STEPS = 64;
-    const bool batched = batch_env; // both modes: exact centroid chains, or Lance-Williams rows (lw)
-    ward_state hst;
-    if (batched) {
-        // Batched exact mode: each step attempts up to WB_K independent merges, so the number of steps is data
-        // dependent (between T/WB_K and T).  Steps are enqueued in chunks of GRAPH_STEPS; the state is read back after
-        // each chunk, one chunk behind the launches so the queue never drains.
-        const int dqb = (int)wb_groups(d);
-        const size_t wx_lds_bytes = (size_t)WX_R * WX_STAGE_F4 * 16;
-        // strip-sharded loop (a group's replicas, multi_gpu.hip): this replica's main workgroups take the blocks == sh_rank (mod sh_n)
-        icl_ward_shard *sh = lw ? nullptr : ctx->shard;
-        const int nsp = ward_nspare(ctx, lbm, ctx->shard != nullptr);
-        const unsigned lw_blocks_b = (unsigned)icl_ceil_div(w->S, WB_THREADS) + 2 + nsp;
-        const int sh_n = sh ? sh->G : 1, sh_rank = sh ? ctx->shard_rank : 0;
-        // main workgroups: persistent, at most one per CU (they draw blocks from a counter); fewer when the input has fewer blocks
-        const unsigned wx_blocks = (unsigned)std::min<int64_t>(icl_ceil_div(w->S / 64, sh_n), (int64_t)ctx->prop.multiProcessorCount) + 2 + nsp;
-        if (!w->wx_attr) { // per context, i.e. per device: a group drives one context per GPU
-            ICL_HIP(ctx, hipFuncSetAttribute((const void *)ward_update_batch2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wx_lds_bytes)); // + ~7 KB of static arrays of the spare / preselection roles
-            w->wx_attr = true;
-        }
-        // the express step's data phase runs in ward_finish_data_kernel from a record the finish kernel leaves behind cnewI
-        int32_t *fdrec = (!lw && (d & 3) == 0) ? reinterpret_cast<int32_t *>(w->cnewI + 16 * w->cn_stride) : nullptr;
-        auto finish_b = [&]() {
-            if (lbm) { // the bound-rows loop: no slot table, centroids by creation id
-                hipLaunchKernelGGL((ward_finish_lb_kernel<WL_K>), dim3(1), dim3(WB_FIN_THREADS), 0, ctx->stream, n, w->asz, w->rowmin, w->rownn, w->merges, w->Dtri,
-                                   w->rowoff, w->mcol, w->msz, w->mcid, w->ld, max_size, w->st, rf, mpk);
-                return;
-            }
-            hipLaunchKernelGGL(ward_finish_batch_kernel, dim3(1), dim3(WB_FIN_THREADS), 0, ctx->stream, n, d, w->S, w->CT, w->Crow, w->cnew, w->cn_stride,
-                               w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->merges, w->Dtri, w->rowoff, w->mcol, w->msz, w->mcid, w->ld, max_size,
-                               w->st, lw ? 1 : 0, fdrec, rf, mpk);
-            if (fdrec) // the express step's data phase on several CUs, the pair-interleaved copy of the new centroids, the block counter reset
-                hipLaunchKernelGGL(ward_finish_data_kernel, dim3((unsigned)icl_ceil_div((WB_K / 2) * w->cn_stride, WB_FD_THREADS)), dim3(WB_FD_THREADS), 0,
-                                   ctx->stream, d, w->S, w->CT, w->Crow, w->cnew, w->cnewI, w->cn_stride, fdrec, w->st);
-            else if (!lw) // (d % 4 != 0) the pair-interleaved copy of the centroids the finish kernel has just written + the block counter reset
-                hipLaunchKernelGGL(ward_interleave_kernel, dim3((unsigned)icl_ceil_div((WB_K / 2) * w->cn_stride, 256)), dim3(256), 0, ctx->stream, w->cnew,
-                                   w->cn_stride, w->cnewI, w->st);
-        };
-        const unsigned lb_blocks = (unsigned)icl_ceil_div(w->M, WL_SLOTS * WL_U) + 2 + nsp; // (WL_U creation ids per lane)
-        auto update_b = [&]() {
-            if (lbm) {
-                hipLaunchKernelGGL(ward_update_lb_kernel, dim3(lb_blocks), dim3(WL_THREADS), 0, ctx->stream, w->S, w->slot_id, w->asz, w->rowoff, w->mcol, w->msz,
-                                   w->mcid, w->Dtri, w->st, max_size, n, w->rowmin, w->rownn, rf, mpk, nsp);
-                return;
-            }
-            if (lw) {
-                hipLaunchKernelGGL(ward_update_batch_lw_kernel, dim3(lw_blocks_b), dim3(WB_THREADS), 0, ctx->stream, w->S, w->slot_id, w->asz, w->rowoff,
-                                   w->mcol, w->msz, w->mcid, w->Dtri, w->st, max_size, n, w->rowmin, w->rownn, nsp);
-                return;
-            }
-            hipLaunchKernelGGL(ward_update_batch2_kernel, dim3(wx_blocks), dim3(WX_THREADS), wx_lds_bytes, ctx->stream, d, dqb, w->S, w->CT, w->Crow,
-                               w->cnew, w->cnewI, w->cn_stride, w->slot_id, w->id_slot, w->asz, w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, max_size, n,
-                               w->rowmin, w->rownn, rf, mpk, sh_rank, sh_n, nsp);
-        };
-        auto step_b = [&](bool prof) {
-            if (prof) {
-                // n_live is only known on the device: the profile records launches, bytes are attributed by the caller
-                icl_prof_scope ps(ctx, ICL_K_UPDATE, 0.0, 0.0);
-                update_b();
-            } else {
-                update_b();
-            }
-            finish_b();
-        };
-        finish_b(); // first batch: one pick by the plain lazy selection
-        ward_peers peers{};
-        if (sh) { // every replica's matrix is known to every replica before the first pull
-            sh->D[sh_rank] = w->Dtri;
-            if (!sh->wait()) return icl_fail(ctx, ICL_ERR_HIP, "sharded merge loop: another replica failed");
-            for (int r = 0; r < sh_n; ++r) peers.D[r] = sh->D[r];
-        }
-        int64_t sh_step = 0;
-        // one step of the sharded loop: [the peers have pulled step t - 1] -> update (own blocks) -> every replica's update is complete -> pull the
-        // other blocks' entries -> finish.  TWO cross-replica orderings per step, each an event per replica with a host barrier between record
-        // and wait (nobody waits on an event that has not been recorded yet):
-        //   ev   "my update launch of step t is complete"  -> the peers' pulls of step t read rows that are final;
-        //   evp  "my pull of step t is complete"           -> the peers' update launches of step t + 1 may overwrite those rows.  Needed because
-        //        row storage follows the creation id: picks a replica's finish(t) rolled back get the SAME rows again in step t + 1, so without
-        //        this wait a fast replica's update(t + 1) could rewrite entries a slow replica's pull(t) is still reading (until
-        //        round 5 this was benign only because finish never consumes rolled-back rows -- an invariant nobody enforced).
-        auto step_sharded = [&]() -> bool {
-            if (sh_step > 0)
-                for (int r = 0; r < sh_n; ++r)
-                    if (r != sh_rank && hipStreamWaitEvent(ctx->stream, sh->evp[r][(sh_step - 1) & 1], 0) != hipSuccess) return false;
-            update_b();
-            hipEvent_t mine = sh->ev[sh_rank][sh_step & 1];
-            if (hipEventRecord(mine, ctx->stream) != hipSuccess) return false;
-            if (!sh->wait()) return false; // (host side: every replica has recorded its event before anybody waits on it)
-            for (int r = 0; r < sh_n; ++r)
-                if (r != sh_rank && hipStreamWaitEvent(ctx->stream, sh->ev[r][sh_step & 1], 0) != hipSuccess) return false;
-            hipLaunchKernelGGL(ward_pull_rows_kernel, dim3((unsigned)std::min<int64_t>(w->S / 64, 2048)), dim3(64), 0, ctx->stream, peers, sh_n, sh_rank, w->Dtri,
-                               w->slot_id, w->asz, w->mcol, w->rowoff, w->st, max_size, n);
-            if (hipEventRecord(sh->evp[sh_rank][sh_step & 1], ctx->stream) != hipSuccess) return false;
-            finish_b();
-            if (!sh->wait()) return false; // every replica has recorded "pull complete" before the next step waits on it
-            ++sh_step;
-            return true;
-        };
-        const bool use_graph = !sh && !prof_update && T >= 2 * GRAPH_STEPS;
-        if (use_graph && (!w->graph_exec || w->graph_max_size != max_size || w->graph_lw != (lw ? 3 : lbm ? 4 : 2) || w->graph_E != rf.E || w->graph_ceps != rf.ceps || w->graph_ex != (const void *)rf.ex)) {
-            if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
-            w->graph_exec = nullptr;
-            hipGraph_t graph = nullptr;
-            ICL_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            for (int g = 0; g < GRAPH_STEPS; ++g) step_b(false);
-            ICL_HIP(ctx, hipStreamEndCapture(ctx->stream, &graph));
-            hipError_t ge = hipGraphInstantiate(&w->graph_exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ge != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ge));
-            w->graph_max_size = max_size;
-            w->graph_lw = lw ? 3 : lbm ? 4 : 2;
-            w->graph_E = rf.E;
-            w->graph_ceps = rf.ceps;
-            w->graph_ex = (const void *)rf.ex;
-        }
-        ICL_HIP(ctx, hipHostMalloc(&gpin.p, 2 * sizeof(ward_state), hipHostMallocDefault));
-        ward_state *hpin = (ward_state *)gpin.p; // two pinned snapshots
-        ICL_HIP(ctx, hipEventCreateWithFlags(&gv0.e, hipEventDisableTiming));
-        ICL_HIP(ctx, hipEventCreateWithFlags(&gv1.e, hipEventDisableTiming));
-        hipEvent_t evs[2] = {gv0.e, gv1.e};
-        auto finished = [&](const ward_state &h) { return h.done || h.t >= T; };
-        int rc_b = ICL_OK;
-        int64_t chunk = 0;
-        const int64_t max_chunks = 2 * (T / GRAPH_STEPS) + 8; // every step commits at least one merge until the end (slack: a safety bound, not a schedule)
-        bool fin = T == 0;
-        while (!fin && chunk < max_chunks) {
-            if (use_graph) {
-                if (hipGraphLaunch(w->graph_exec, ctx->stream) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
-            } else if (sh) {
-                bool ok_s = true;
-                for (int g = 0; g < GRAPH_STEPS && ok_s; ++g) ok_s = step_sharded();
-                if (!ok_s) { rc_b = ICL_ERR_HIP; break; }
-            } else {
-                for (int g = 0; g < GRAPH_STEPS; ++g) step_b(prof_update);
-            }
-            const int sl = (int)(chunk & 1);
-            if (hipMemcpyAsync(&hpin[sl], w->st, sizeof(ward_state), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipEventRecord(evs[sl], ctx->stream) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
-            if (chunk >= 1) { // look at the chunk before this one while this one runs
-                if (hipEventSynchronize(evs[sl ^ 1]) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
-                fin = finished(hpin[sl ^ 1]);
-            }
-            ++chunk;
-        }
-        if (rc_b == ICL_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc_b = ICL_ERR_HIP;
-        if (rc_b != ICL_OK) return icl_fail(ctx, ICL_ERR_HIP, "batched merge loop: %s", hipGetErrorString(hipGetLastError()));
-    } else {
-    hipLaunchKernelGGL(ward_presel_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, w->asz, w->rowmin, w->rownn, w->Dtri, w->rowoff, w->msz, w->mcid,
-                       max_size, w->st, rf); // merge 0 has no update in front of it
-    finish();
-    if (prof_update || T < 2 * GRAPH_STEPS) {
-        for (int64_t t = 0; t < T; ++t) enqueue_step(t, prof_update);
-    } else {
-        if (!w->graph_exec || w->graph_max_size != max_size || w->graph_lw != (int)lw || w->graph_E != rf.E || w->graph_ceps != rf.ceps || w->graph_ex != (const void *)rf.ex) {
-            if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
-            w->graph_exec = nullptr;
-            hipGraph_t graph = nullptr;
-            ICL_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            for (int g = 0; g < GRAPH_STEPS; ++g) enqueue_step(0, false);
-            ICL_HIP(ctx, hipStreamEndCapture(ctx->stream, &graph));
-            hipError_t ge = hipGraphInstantiate(&w->graph_exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ge != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ge));
-            w->graph_max_size = max_size;
-            w->graph_lw = (int)lw;
-            w->graph_E = rf.E;
-            w->graph_ceps = rf.ceps;
-            w->graph_ex = (const void *)rf.ex;
-        }
-        for (int64_t t = 0; t < T; t += GRAPH_STEPS) ICL_HIP(ctx, hipGraphLaunch(w->graph_exec, ctx->stream));
-    }
-    }
-    ICL_HIP(ctx, hipGetLastError());
-    ICL_HIP(ctx, hipEventRecord(e2, ctx->stream));
+    hipLaunchKernelGGL(ward_presel_kernel, dim3(1), dim3(1024), 0, ctx->stream, p.n, w->asz, w->rowmin, w->rownn, w->Dtri, w->rowoff, w->msz, w->mcid,
+                       p.max_size, w->st, rf); // merge 0 has no update in front of it
+    ward_finish_single(ctx, w, p);
+    if (p.use_graph) {
+        ICL_TRY(ward_graph_ensure(ctx, w, p, rf, ward_step_single));
+        for (int64_t t = 0; t < p.T; t += GRAPH_STEPS) ICL_HIP(ctx, hipGraphLaunch(w->graph_exec, ctx->stream));
+    } else
+        for (int64_t t = 0; t < p.T; ++t) ward_step_single(ctx, w, p, rf, t);
+    return ICL_OK;
+}
 
-    ICL_HIP(ctx, hipMemcpyAsync(&hst, w->st, sizeof hst, hipMemcpyDeviceToHost, ctx->stream));
-    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // The loop ends when len(clusters) == k or no mergeable pair is left (clustering.go:220-225).  Anything else -- the chunk
-    // budget of the batched loop ran out, a replay did nothing -- is an engine failure, never a shorter clustering.
-    if (!(hst.done || hst.t >= T))
-        return icl_fail(ctx, ICL_ERR_HIP, "merge loop did not converge: %d of %lld merges after the step budget (engine bug, not a property of the input)",
-                        hst.t, (long long)T);
-    const int64_t nmerge = hst.t;
+// Batched: each step attempts up to WB_K independent merges, so the number of steps is data dependent (between T/WB_K and T).
+static void ward_finish_batch(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf)
+{
+    if (p.lbm) { // the bound-rows loop: no slot table, centroids by creation id
+        hipLaunchKernelGGL((ward_finish_lb_kernel<WL_K>), dim3(1), dim3(WB_FIN_THREADS), 0, ctx->stream, p.n, w->asz, w->rowmin, w->rownn, w->merges, w->Dtri,
+                           w->rowoff, w->mcol, w->msz, w->mcid, w->ld, p.max_size, w->st, rf, p.mpk);
+        return;
+    }
+    hipLaunchKernelGGL(ward_finish_batch_kernel, dim3(1), dim3(WB_FIN_THREADS), 0, ctx->stream, p.n, p.d, w->S, w->CT, w->Crow, w->cnew, w->cn_stride, w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->merges,
+                       w->Dtri, w->rowoff, w->mcol, w->msz, w->mcid, w->ld, p.max_size, w->st, p.lw ? 1 : 0, p.fdrec, rf, p.mpk);
+    if (p.fdrec) // the express step's data phase on several CUs, the pair-interleaved copy of the new centroids, the block counter reset
+        hipLaunchKernelGGL(ward_finish_data_kernel, dim3(p.fd_blocks), dim3(WB_FD_THREADS), 0, ctx->stream, p.d, w->S, w->CT, w->Crow, w->cnew, w->cnewI, w->cn_stride, p.fdrec, w->st);
+    else if (!p.lw) // (d % 4 != 0) the pair-interleaved copy of the centroids the finish kernel has just written + the block counter reset
+        hipLaunchKernelGGL(ward_interleave_kernel, dim3(p.il_blocks), dim3(256), 0, ctx->stream, w->cnew, w->cn_stride, w->cnewI, w->st);
+}
+static void ward_update_batch(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf)
+{
+    if (p.lbm)
+        hipLaunchKernelGGL(ward_update_lb_kernel, dim3(p.lb_blocks), dim3(WL_THREADS), 0, ctx->stream, w->S, w->slot_id, w->asz, w->rowoff, w->mcol, w->msz,
+                           w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, rf, p.mpk, p.nsp);
+    else if (p.lw)
+        hipLaunchKernelGGL(ward_update_batch_lw_kernel, dim3(p.lw_blocks_b), dim3(WB_THREADS), 0, ctx->stream, w->S, w->slot_id, w->asz, w->rowoff,
+                           w->mcol, w->msz, w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, p.nsp);
+    else
+        hipLaunchKernelGGL(ward_update_batch2_kernel, dim3(p.wx_blocks), dim3(WX_THREADS), p.wx_lds, ctx->stream, p.d, p.dqb, w->S, w->CT, w->Crow, w->cnew, w->cnewI, w->cn_stride, w->slot_id, w->id_slot, w->asz,
+                           w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, rf, p.mpk, p.sh_rank, p.sh_n, p.nsp);
+}
+static void ward_step_batch(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, int64_t)
+{
+    {
+        icl_prof_scope ps(ctx, ICL_K_UPDATE, 0.0, 0.0); // n_live is only known on the device: the profile records launches, ward_collect attributes the work
+        ward_update_batch(ctx, w, p, rf);
+    }
+    ward_finish_batch(ctx, w, p, rf);
+}
+// one step of the sharded loop: [the peers have pulled step t - 1] -> update (own blocks) -> every replica's update is complete -> pull the
+// other blocks' entries -> finish.  TWO cross-replica orderings per step, each an event per replica with a host barrier between record
+// and wait (nobody waits on an event that has not been recorded yet):
+//   ev   "my update launch of step t is complete"  -> the peers' pulls of step t read rows that are final;
+//   evp  "my pull of step t is complete"           -> the peers' update launches of step t + 1 may overwrite those rows.  Needed because
+//        row storage follows the creation id: picks a replica's finish(t) rolled back get the SAME rows again in step t + 1, so without
+//        this wait a fast replica's update(t + 1) could rewrite entries a slow replica's pull(t) is still reading (until
+//        round 5 this was benign only because finish never consumes rolled-back rows -- an invariant nobody enforced).
+static bool ward_step_sharded(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, const ward_peers &peers, int64_t sh_step)
+{
+    icl_ward_shard *sh = p.sh;
+    const int sh_n = p.sh_n, sh_rank = p.sh_rank;
+    if (sh_step > 0)
+        for (int r = 0; r < sh_n; ++r)
+            if (r != sh_rank && hipStreamWaitEvent(ctx->stream, sh->evp[r][(sh_step - 1) & 1], 0) != hipSuccess) return false;
+    ward_update_batch(ctx, w, p, rf);
+    hipEvent_t mine = sh->ev[sh_rank][sh_step & 1];
+    if (hipEventRecord(mine, ctx->stream) != hipSuccess) return false;
+    if (!sh->wait()) return false; // (host side: every replica has recorded its event before anybody waits on it)
+    for (int r = 0; r < sh_n; ++r)
+        if (r != sh_rank && hipStreamWaitEvent(ctx->stream, sh->ev[r][sh_step & 1], 0) != hipSuccess) return false;
+    hipLaunchKernelGGL(ward_pull_rows_kernel, dim3(p.pull_blocks), dim3(64), 0, ctx->stream, peers, sh_n, sh_rank, w->Dtri, w->slot_id, w->asz, w->mcol, w->rowoff, w->st, p.max_size, p.n);
+    if (hipEventRecord(sh->evp[sh_rank][sh_step & 1], ctx->stream) != hipSuccess) return false;
+    ward_finish_batch(ctx, w, p, rf);
+    return sh->wait(); // every replica has recorded "pull complete" before the next step waits on it
+}
+// Steps are enqueued in chunks of GRAPH_STEPS; the state is read back after each chunk, one chunk behind the launches so the queue never drains.
+static int ward_run_batched(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, ward_call &c)
+{
+    icl_ward_shard *sh = p.sh;
+    if (!w->wx_attr) { // per context, i.e. per device: a group drives one context per GPU
+        ICL_HIP(ctx, hipFuncSetAttribute((const void *)ward_update_batch2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.wx_lds)); // + ~7 KB of static arrays of the spare / preselection roles
+        w->wx_attr = true;
+    }
+    ward_finish_batch(ctx, w, p, rf); // first batch: one pick by the plain lazy selection
+    ward_peers peers{};
+    if (sh) { // every replica's matrix is known to every replica before the first pull
+        sh->D[p.sh_rank] = w->Dtri;
+        if (!sh->wait()) return icl_fail(ctx, ICL_ERR_HIP, "sharded merge loop: another replica failed");
+        for (int r = 0; r < p.sh_n; ++r) peers.D[r] = sh->D[r];
+    }
+    int64_t sh_step = 0;
+    if (p.use_graph) ICL_TRY(ward_graph_ensure(ctx, w, p, rf, ward_step_batch));
+    ICL_HIP(ctx, hipHostMalloc(&c.pin.p, 2 * sizeof(ward_state), hipHostMallocDefault));
+    ward_state *hpin = (ward_state *)c.pin.p; // two pinned snapshots
+    ICL_HIP(ctx, hipEventCreateWithFlags(&c.ev[0].p, hipEventDisableTiming));
+    ICL_HIP(ctx, hipEventCreateWithFlags(&c.ev[1].p, hipEventDisableTiming));
+    int rc_b = ICL_OK;
+    int64_t chunk = 0;
+    const int64_t max_chunks = 2 * (p.T / GRAPH_STEPS) + 8; // every step commits at least one merge until the end (slack: a safety bound, not a schedule)
+    bool fin = p.T == 0;
+    while (!fin && chunk < max_chunks) {
+        if (p.use_graph) {
+            if (hipGraphLaunch(w->graph_exec, ctx->stream) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
+        } else if (sh) {
+            bool ok_s = true;
+            for (int g = 0; g < GRAPH_STEPS && ok_s; ++g) ok_s = ward_step_sharded(ctx, w, p, rf, peers, sh_step++);
+            if (!ok_s) { rc_b = ICL_ERR_HIP; break; }
+        } else {
+            for (int g = 0; g < GRAPH_STEPS; ++g) ward_step_batch(ctx, w, p, rf, 0);
+        }
+        const int sl = (int)(chunk & 1);
+        if (hipMemcpyAsync(&hpin[sl], w->st, sizeof(ward_state), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipEventRecord(c.ev[sl].p, ctx->stream) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
+        if (chunk >= 1) { // look at the chunk before this one while this one runs
+            if (hipEventSynchronize(c.ev[sl ^ 1].p) != hipSuccess) { rc_b = ICL_ERR_HIP; break; }
+            fin = hpin[sl ^ 1].done || hpin[sl ^ 1].t >= p.T;
+        }
+        ++chunk;
+    }
+    if (rc_b == ICL_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc_b = ICL_ERR_HIP;
+    if (rc_b != ICL_OK) return icl_fail(ctx, ICL_ERR_HIP, "batched merge loop: %s", hipGetErrorString(hipGetLastError()));
+    return ICL_OK;
+}
+
+// ICL_WARD_TIMERS builds, ICL_WARD_STATS set: the in-kernel timers and counters of the loop just run
+static void ward_timers_report(const ward_state &hst, const ward_plan &p, const wrefine &rf)
+{
 #ifdef ICL_WARD_TIMERS
+    const bool batched = p.batched, lw = p.lw;
+    const int64_t n = p.n;
     if (batched && getenv("ICL_WARD_STATS"))
         fprintf(stderr, "[icl] batched ward: merges %d steps %d commits %d single-pick steps %d general-path steps %d\n", hst.t, hst.B.steps, hst.B.commits,
                 hst.B.slow, hst.B.general);
@@ -5504,27 +5555,44 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
                 hst.B.dbg[0] * 0.01 / hst.B.steps, hst.B.dbg[7] * 0.01 / hst.B.steps, (double)hst.B.dbg[6] / hst.B.steps, hst.B.dbg[1] * 0.01 / hst.B.steps, hst.B.dbg[2] * 0.01 / hst.B.steps,
                 hst.B.dbg[3] * 0.01 / hst.B.steps, hst.B.dbg2[0] * 0.01 / hst.B.steps, hst.B.dbg[4] * 0.01 / hst.B.steps, hst.B.dbg[5] * 0.01 / hst.B.steps);
 #endif
+}
+
+// The state read back: the convergence check, the merge log, ctx->last, the profile attribution and the reference's cluster list.
+static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, ward_call &c, int32_t min_size, int32_t *cluster_id,
+                        int32_t *member_rank, int32_t *n_clusters)
+{
+    ward_state hst;
+    ICL_HIP(ctx, hipMemcpyAsync(&hst, w->st, sizeof hst, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // The loop ends when len(clusters) == k or no mergeable pair is left (clustering.go:220-225).  Anything else -- the chunk
+    // budget of the batched loop ran out, a replay did nothing -- is an engine failure, never a shorter clustering.
+    if (!(hst.done || hst.t >= p.T))
+        return icl_fail(ctx, ICL_ERR_HIP, "merge loop did not converge: %d of %lld merges after the step budget (engine bug, not a property of the input)",
+                        hst.t, (long long)p.T);
+    const int64_t nmerge = hst.t;
+    ward_timers_report(hst, p, rf);
     ctx->last.bound_viol = (int64_t)hst.bound_viol;
-    ctx->last.mode[0] = !batched ? ICL_ROWS_SINGLE : lw ? ICL_ROWS_LW_FAST : lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH; // what the loop just run WAS (icl_last_ward_mode)
-    ctx->last.mode[1] = use_bound ? 1 : 0;
+    ctx->last.mode[0] = p.rows; // what the loop just run WAS (icl_last_ward_mode)
+    ctx->last.mode[1] = p.use_bound ? 1 : 0;
     ctx->last.layout[0] = rf.wide;
     ctx->last.layout[1] = w->ld;
-    ctx->last.layout[2] = rf.ex ? 1 : 0;
+    ctx->last.layout[2] = rf.ex ? 1 : 0; // (what RAN: ward_fill may have fallen back to the f32 GEMM)
     ctx->last.stats[0] = nmerge;
-    if (batched) {
+    if (p.batched) {
         // steps = launches that carried work: the first finish picks without committing, every later one commits >= 1
         ctx->last.stats[1] = hst.B.steps;
         ctx->last.stats[2] = hst.B.slow;
         ctx->last.stats[3] = (int64_t)hst.B.sum_live;
-        if (prof_update) { // algorithmic work of the launches just profiled (n_live is only known on the device)
-            ctx->prof[ICL_K_UPDATE].flops += (lw ? 8.0 : lbm ? 16.0 : 3.0 * d) * (double)hst.B.sum_live_nb;
-            ctx->prof[ICL_K_UPDATE].bytes += (lw || lbm) ? (rf.wide ? 16.0 : 12.0) * (double)hst.B.sum_live_nb : // (complete rows: the entry is written twice)
-                                              4.0 * d * (double)hst.B.sum_live + 4.0 * (double)hst.B.sum_live_nb;
+        if (p.prof_update) { // algorithmic work of the launches just profiled (n_live is only known on the device)
+            const bool lwrows = p.rows != ICL_ROWS_EXACT_BATCH; // Lance-Williams rows, values or bounds
+            ctx->prof[ICL_K_UPDATE].flops += (p.rows == ICL_ROWS_LW_FAST ? 8.0 : lwrows ? 16.0 : 3.0 * p.d) * (double)hst.B.sum_live_nb;
+            ctx->prof[ICL_K_UPDATE].bytes += lwrows ? (rf.wide ? 16.0 : 12.0) * (double)hst.B.sum_live_nb : // (complete rows: the entry is written twice)
+                                                      4.0 * p.d * (double)hst.B.sum_live + 4.0 * (double)hst.B.sum_live_nb;
         }
     } else {
         ctx->last.stats[1] = nmerge;
         ctx->last.stats[2] = nmerge;
-        ctx->last.stats[3] = (int64_t)nmerge * n - (int64_t)nmerge * (nmerge + 1) / 2;
+        ctx->last.stats[3] = (int64_t)nmerge * p.n - (int64_t)nmerge * (nmerge + 1) / 2;
     }
     std::vector<int32_t> pairs((size_t)(2 * nmerge)), trip((size_t)(3 * nmerge));
     ctx->last.merge_vals.assign((size_t)nmerge, 0.0f);
@@ -5538,15 +5606,42 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
         }
     }
     float ms01 = 0, ms12 = 0;
-    (void)hipEventElapsedTime(&ms01, e0, e1);
-    (void)hipEventElapsedTime(&ms12, e1, e2);
+    (void)hipEventElapsedTime(&ms01, c.e0.p, c.e1.p);
+    (void)hipEventElapsedTime(&ms12, c.e1.p, c.e2.p);
     ctx->last.dist_ms = ms01;
     ctx->last.merge_ms = ms12;
     icl_prof_collect(ctx);
-    shg.ok = true; // the merge loop is over: nobody waits for this replica any more
-    int rc = icl_ward_assign_ids(ctx, n, min_size, max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
+    c.shard.ok = true; // the merge loop is over: nobody waits for this replica any more
+    int rc = icl_ward_assign_ids(ctx, p.n, min_size, p.max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
     ctx->last.merges.swap(pairs);
     return rc;
+}
+
+static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update,
+                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int64_t own_lo = 0, int64_t own_hi = -1)
+{
+    ICL_TRY(ward_check_args(ctx, n, min_size, max_size, update));
+    ctx->last.merges.clear();
+    *n_clusters = 0;
+    if (n == 0) return ICL_OK;
+    ward_call c;
+    c.shard.s = ctx->shard;
+    ICL_TRY(ward_ensure(ctx, n, d));
+    icl_ward_ws *w = ctx->ward;
+    ward_plan p;
+    ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p));
+    ICL_HIP(ctx, hipEventCreate(&c.e0.p));
+    ICL_HIP(ctx, hipEventCreate(&c.e1.p));
+    ICL_HIP(ctx, hipEventCreate(&c.e2.p));
+    ICL_HIP(ctx, hipEventRecord(c.e0.p, ctx->stream));
+    ICL_TRY(ward_init_ws(ctx, w, p, d_E));
+    wrefine rf;
+    ICL_TRY(ward_fill(ctx, w, p, d_E, c, &rf));
+    ICL_HIP(ctx, hipEventRecord(c.e1.p, ctx->stream));
+    ICL_TRY(p.batched ? ward_run_batched(ctx, w, p, rf, c) : ward_run_single(ctx, w, p, rf));
+    ICL_HIP(ctx, hipGetLastError());
+    ICL_HIP(ctx, hipEventRecord(c.e2.p, ctx->stream));
+    return ward_collect(ctx, w, p, rf, c, min_size, cluster_id, member_rank, n_clusters);
 }
 
 // ---- distance tiles over several GPUs ("tiles computed on 8 GPUs, scattered to GPU0 over xGMI") ----------
@@ -5598,21 +5693,16 @@ extern "C" int icl_ward_distance_rows_dev(icl_ctx *ctx, const float *d_E, int64_
         // the same proven lower bounds the clustering GPU puts into its own rows (0.15 s / G of f32 MFMA at n = 100 000 instead of 0.49 s / G of exact
         // vector arithmetic): E - mu and the centred norms are recomputed here -- deterministic kernels on the same E give every GPU the same mu, norms
         // and constants, so the flagged entries mean on the clustering GPU exactly what they mean here
-        const int K = (d + 31) / 32 * 32;
-        struct tmp_guard {
-            void *ec = nullptr, *nrm = nullptr, *cs = nullptr, *zero = nullptr;
-            ~tmp_guard() { for (void *p : {ec, nrm, cs, zero}) if (p) (void)hipFree(p); }
-        } t;
-        if (hipMalloc(&t.ec, (size_t)n * K * 4) != hipSuccess || hipMalloc(&t.nrm, (size_t)n * 4) != hipSuccess || hipMalloc(&t.cs, icl_dist_colsum_doubles(K) * 8) != hipSuccess ||
-            hipMalloc(&t.zero, 256) != hipSuccess)
+        const int K = ward_bound_K(d);
+        dev_guard ec, nrm, cs, zero;
+        if (hipMalloc(&ec.p, (size_t)n * K * 4) != hipSuccess || hipMalloc(&nrm.p, (size_t)n * 4) != hipSuccess || hipMalloc(&cs.p, icl_dist_colsum_doubles(K) * 8) != hipSuccess ||
+            hipMalloc(&zero.p, 256) != hipSuccess)
             return icl_fail(ctx, ICL_ERR_NOMEM, "icl_ward_distance_rows_dev: centred copy of E (%lld x %d floats)", (long long)n, K);
-        ICL_HIP(ctx, hipMemsetAsync(t.zero, 0, 256, ctx->stream));
-        float ceps, gam;
-        ward_bound_consts(d, K, &ceps, &gam);
-        ICL_TRY(icl_dist_center_launch(ctx, d_E, n, d, K, (double *)t.cs, (float *)t.ec, (float *)t.nrm, ctx->stream));
-        ICL_TRY(icl_dist_bound_launch(ctx, (const float *)t.ec, (const float *)t.nrm, t.zero, n, K, ceps, gam, d_span - tri_rowoff(row_lo), ctx->ward_rowoff,
-                                      row_lo / DT_TILE, icl_ceil_div(row_hi, DT_TILE), ctx->stream));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ICL_HIP(ctx, hipMemsetAsync(zero.p, 0, 256, ctx->stream));
+        ward_centred b{(double *)cs.p, (float *)ec.p, (float *)nrm.p, zero.p};
+        ICL_TRY(ward_centre(ctx, d_E, n, d, &b));
+        ICL_TRY(ward_bounds_f32(ctx, b, n, d_span - tri_rowoff(row_lo), ctx->ward_rowoff, row_lo, row_hi));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (before the temporaries go)
         return ICL_OK;
     }
     ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, d_span - tri_rowoff(row_lo), ctx->ward_rowoff, 0, 0, row_lo / DT_TILE,
@@ -5758,11 +5848,7 @@ extern "C" int icl_embed_cluster_dev(icl_ctx *ctx, const uint8_t *d_img, int64_t
     // same kernel again on the main stream, after s3 has drained: same values)
     ICL_HIP(ctx, hipEventRecord(ctx->ev_s3, ctx->stream));
     ICL_HIP(ctx, hipStreamWaitEvent(s3, ctx->ev_s3, 0)); // whatever was queued on the main stream (an earlier cluster call) comes first
-    {
-        const int64_t cnt = std::max(std::max(w->S, w->M), w->ld);
-        hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)icl_ceil_div(cnt, 256)), dim3(256), 0, s3, n, w->S, w->M, w->ld,
-                           w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->st, (int32_t)0, (uint32_t *)nullptr, 0);
-    }
+    ward_launch_init(w, n, 0, nullptr, 0, s3);
     int64_t next_tr = 0;
     const int64_t ntr = icl_ceil_div(n, DT_TILE);
     ctx->embed_hook = [&](int64_t first, int64_t cnt, hipEvent_t ev) -> int {
@@ -5904,10 +5990,7 @@ extern "C" int icl_update_distance_matrix(icl_ctx *ctx, const float *D, int64_t 
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     const int64_t lo = std::min(r1, r2), hi = std::max(r1, r2), m1 = n - 1;
-    struct dev_guard {
-        void *p = nullptr;
-        ~dev_guard() { if (p) (void)hipFree(p); }
-    } gD, gC, gS, gO;
+    dev_guard gD, gC, gS, gO;
     ICL_HIP(ctx, hipMalloc(&gD.p, (size_t)(n * ld) * 4));
     ICL_HIP(ctx, hipMalloc(&gC.p, (size_t)std::max<int64_t>(m1 * d, 1) * 4));
     ICL_HIP(ctx, hipMalloc(&gS.p, (size_t)m1 * 4));
@@ -5963,32 +6046,24 @@ extern "C" int icl_distance_bounds_check_dev(icl_ctx *ctx, const float *d_E, int
     icl_device_guard g(ctx->device);
     ICL_TRY(ward_ensure(ctx, n, d));
     icl_ward_ws *w = ctx->ward;
-    struct free_guard {
-        void *p = nullptr;
-        ~free_guard() { if (p) (void)hipFree(p); }
-    } g_ec, g_pq, g_x, g_cnt;
-    const int K = (d + 31) / 32 * 32;
+    dev_guard g_ec, g_pq, g_x, g_cnt;
+    const int K = ward_bound_K(d);
     const bool i8 = kind == 2 || (kind == 0 && icl_dist_i8_usable(n, d));
     if (i8 && !icl_dist_i8_usable(n, d)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "the integer distance GEMM covers D <= 2048");
     if (hipMalloc(&g_ec.p, (size_t)n * K * 4) != hipSuccess || hipMalloc(&g_x.p, (size_t)w->dtri_floats * 4) != hipSuccess || hipMalloc(&g_cnt.p, 64) != hipSuccess ||
         (i8 && hipMalloc(&g_pq.p, icl_dist_i8_pq_bytes(n, d)) != hipSuccess))
         return icl_fail(ctx, ICL_ERR_NOMEM, "icl_distance_bounds_check_dev: scratch for %lld rows", (long long)n);
     ICL_HIP(ctx, hipMemsetAsync(g_cnt.p, 0, 64, ctx->stream));
-    {
-        const int64_t cnt = std::max(std::max(w->S, w->M), w->ld);
-        hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)icl_ceil_div(cnt, 256)), dim3(256), 0, ctx->stream, n, w->S, w->M, w->ld, w->slot_id, w->id_slot, w->asz, w->rowmin,
-                           w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->st, (int32_t)0, (uint32_t *)nullptr, 0);
-    }
-    float ceps, gam;
-    ward_bound_consts(d, K, &ceps, &gam);
-    wrefine rf{d_E, w->nrm, n, d, ceps, gam, nullptr, 0.0f};
-    ICL_TRY(icl_dist_center_launch(ctx, d_E, n, d, K, w->colsum, (float *)g_ec.p, w->nrm, ctx->stream));
+    ward_launch_init(w, n, 0, nullptr, 0, ctx->stream);
+    ward_centred b{w->colsum, (float *)g_ec.p, w->nrm, w->zero};
+    ICL_TRY(ward_centre(ctx, d_E, n, d, &b));
+    wrefine rf{d_E, w->nrm, n, d, b.ceps, b.gam, nullptr, 0.0f};
     if (i8) {
         rf.l1 = w->bl1;
         rf.ex = w->bex;
-        ICL_TRY(icl_dist_bound_i8_launch(ctx, (const float *)g_ec.p, w->nrm, n, d, K, gam, g_pq.p, w->bl1, w->bex, w->Dtri, w->rowoff, ctx->stream, nullptr));
+        ICL_TRY(icl_dist_bound_i8_launch(ctx, b.ec, w->nrm, n, d, K, b.gam, g_pq.p, w->bl1, w->bex, w->Dtri, w->rowoff, ctx->stream, nullptr));
     } else
-        ICL_TRY(icl_dist_bound_launch(ctx, (const float *)g_ec.p, w->nrm, w->zero, n, K, ceps, gam, w->Dtri, w->rowoff, 0, icl_ceil_div(n, DT_TILE), ctx->stream));
+        ICL_TRY(ward_bounds_f32(ctx, b, n, w->Dtri, w->rowoff, 0, n));
     ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, (float *)g_x.p, w->rowoff, 0, 0, 0, icl_ceil_div(n, DT_TILE)));
     unsigned long long *cnt = (unsigned long long *)g_cnt.p;
     double *sums = (double *)((char *)g_cnt.p + 32);

@@ -569,6 +569,60 @@ def test_context_reuse_different_shapes(ctx):
         same_as_oracle(ctx, mog(n, d, n), 2, 6)
 
 
+def test_graph_replay_across_calls_on_one_context(ctx):
+    """One context, one shape (n = 400, d = 8): the workspace and its captured graph of merge steps survive from call to call, and
+    every call needs >= 128 merges (267, 278, 200, 330 for the constraints below), so each one replays a graph.  Consecutive calls
+    change ONE field of the graph's key at a time -- max_size, the Ward options (row mode, bounds or values in the matrix), the
+    embeddings, the update mode -- and a graph replayed under a stale key would cluster wrongly without any error: after every
+    exact call ids, member order and merge log against the literal oracle, merge values bit for bit against the fast one."""
+    from imageclust_amd import _lib
+
+    single = os.environ.get("ICL_WARD_BATCH", "")[:1] == "0"
+    E, E2 = WC.mog(400, 8, 7), WC.mog(400, 8, 8)
+    want = {}
+
+    def exact(X, mn, mx, opt):
+        key = (X is E2, mn, mx)
+        if key not in want:
+            want[key] = (O.cluster(X, mn, mx, want_log=True), O.cluster_fast(X, mn, mx, lazy_ban=False))
+        r, f = want[key]
+        assert r["ok"] and f["ok"] and r["merges"] >= 128
+        ctx.set_ward_options(opt)
+        cid, rank, nc = ctx.cluster(X, mn, mx)
+        what = "options %d, E%d, min %d, max %d" % (opt, 1 + (X is E2), mn, mx)
+        m = ctx.last_merges()
+        assert len(m) == r["merges"], what
+        assert np.array_equal(m, r["log"][:, 2:4].astype(np.int32)), what + ": merge sequence differs"
+        assert np.array_equal(ctx.last_merge_values().view(np.uint32), f["vals"].view(np.uint32)), what + ": Ward values of the merged pairs"
+        assert np.array_equal(cid, r["cluster_id"]) and np.array_equal(rank, r["member_rank"]) and nc == r["n_clusters"], what
+        assert ctx.last_ward_bound_violations() == 0, what
+        rows = _lib.ROWS_SINGLE if single else _lib.ROWS_LW_BOUND if opt == 4 else _lib.ROWS_EXACT_BATCH
+        assert ctx.last_ward_mode() == (rows, opt in (2, 4)), what
+
+    try:
+        for mx in (6, 9, 6):  # max_size
+            exact(E, 2, mx, 0)
+        for opt in (1, 2, 4, 0):  # exact rows on values, exact rows on bounds, bound rows, auto (values below n = 4096)
+            exact(E, 2, 6, opt)
+        for opt in (2, 4):  # other embeddings of the same shape, with bounds in the matrix (the scans then read E)
+            exact(E, 2, 6, opt)
+            exact(E2, 2, 6, opt)
+            exact(E, 2, 6, opt)
+        exact(E2, 1, 400, 0)
+        exact(E, 3, 50, 0)
+        ctx.set_ward_options(0)
+        cid, rank, nc = ctx.cluster(E, 3, 50, _lib.UPDATE_LW)  # FAST mode: what tests/test_fast_mode_gpu.py asserts of it
+        kept = cid[cid >= 0]
+        counts = np.bincount(kept)
+        assert counts.min() >= 3 and counts.max() <= 50
+        assert sorted(set(kept.tolist())) == list(range(nc))
+        assert ctx.last_ward_mode() == (_lib.ROWS_SINGLE if single else _lib.ROWS_LW_FAST, False)
+        exact(E, 3, 50, 0)
+        exact(E, 3, 50, 4)
+    finally:
+        ctx.set_ward_options(0)
+
+
 def test_cluster_property_sizes_at_scale(ctx):
     """Config-2-sized clustering (N=10000, D=2048): size-independent properties."""
     E = mog(10000, 2048, 20250217, k=500)
