@@ -74,6 +74,8 @@ SYMBOLS = [
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
     ("icl_conv_split_launches", _int, [_vp, _vp]),
     ("icl_conv2d_fused", _int, [_vp, _int, _vp, _int, _int, _int, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp]),
+    ("icl_conv2d_dual", _int, [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _int, _int, _vp, _vp, _int, _vp]),
+    ("icl_embed_taps", _int, [_vp, _int, _vp, _int, _int, _vp]),
     ("icl_stem_pool", _int, [_vp, _int, _vp, _int, _vp]),
     ("icl_bottleneck56", _int, [_vp, _vp, _int, _int, _int, _int] + [_vp] * 13),
     ("icl_calc_optimal_clusters", _int, [_i64, _i64, _i64, _pi64]),
@@ -464,6 +466,28 @@ class Context:
                                               1 if relu else 0, y.ctypes.data))
         return y
 
+    def conv2d_dual(self, x_nhwc, w1, x2_nhwc, w2, stride2, scale, shift, relu=True, prec=PREC_FP32):
+        """The dual-operand launch of block 0 of stages 2-4 (icl_conv2d_dual): x [B][Ho][Ho][Cin] . w1 [Cout][Cin] +
+        x2[:, ::stride2, ::stride2] [B][H2][H2][Cin2] . w2 [Cout][Cin2], then scale, shift and ReLU -> [B][Ho][Ho][Cout]."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        x, x2, w1, w2, sc, sh = f(x_nhwc), f(x2_nhwc), f(w1), f(w2), f(scale), f(shift)
+        B, Ho, _, Cin = x.shape
+        _, H2, _, Cin2 = x2.shape
+        Cout = w1.shape[0]
+        assert x2.shape[0] == B and w1.shape == (Cout, Cin) and w2.shape == (Cout, Cin2) and sc.shape == (Cout,) and sh.shape == (Cout,)
+        y = np.empty((B, Ho, Ho, Cout), np.float32)
+        check(self.h, self.L.icl_conv2d_dual(self.h, prec, x.ctypes.data, B, Ho, Cin, w1.ctypes.data, x2.ctypes.data, H2, Cin2, w2.ctypes.data,
+                                             int(stride2), Cout, sc.ctypes.data, sh.ctypes.data, 1 if relu else 0, y.ctypes.data))
+        return y
+
+    def embed_taps(self, imgs, tap, prec=PREC_FP32):
+        """The forward pass of the loaded model on one batch, ended at a tap (icl_embed_taps): the tensor after the stem + maxpool
+        (tap 0) or after bottleneck tap (1..16) as fp32 NHWC."""
+        a = np.ascontiguousarray(imgs, np.uint8).reshape(-1, IMG_BYTES)
+        out = np.empty((a.shape[0],) + tap_shape(tap), np.float32)
+        check(self.h, self.L.icl_embed_taps(self.h, prec, a.ctypes.data, a.shape[0], int(tap), out.ctypes.data))
+        return out
+
     def stem_pool(self, imgs, prec=PREC_FP32):
         """conv0 + BN + ReLU + maxpool of the loaded model in one launch: [B][56][56][64] fp32."""
         a = np.ascontiguousarray(imgs, np.uint8).reshape(-1, IMG_BYTES)
@@ -817,6 +841,16 @@ def load_image_224(path):
     if rc:
         raise ICLError(rc, (load().icl_last_error(None) or b"").decode())
     return out
+
+
+def tap_shape(tap):
+    """(H, W, C) of the tensor icl_embed_taps returns for a tap: 56 x 56 x 64 after the stem, then [3, 4, 6, 3] bottlenecks per stage."""
+    if not 0 <= tap <= 16:
+        raise ValueError("tap must be 0..16")
+    if tap == 0:
+        return (56, 56, 64)
+    stage = sum(tap > e for e in (3, 7, 13))
+    return (56 >> stage, 56 >> stage, 256 << stage)
 
 
 def synth_images(seed, first, n, mode=SYNTH_NOISE):

@@ -922,14 +922,14 @@ static int to_dev(icl_ctx *ctx, int prec, const float *src, size_t n, dev_buf &d
     return ICL_OK;
 }
 // ... and back (the stream that wrote src has been synchronised)
-static int from_dev(icl_ctx *ctx, int prec, const dev_buf &src, size_t n, float *dst)
+static int from_dev(icl_ctx *ctx, int prec, const void *src, size_t n, float *dst)
 {
     if (prec == ICL_PREC_FP32) {
-        ICL_HIP(ctx, hipMemcpy(dst, src.p, n * 4, hipMemcpyDeviceToHost));
+        ICL_HIP(ctx, hipMemcpy(dst, src, n * 4, hipMemcpyDeviceToHost));
         return ICL_OK;
     }
     std::vector<uint16_t> t(prec == ICL_PREC_BF16X3 ? 2 * n : n);
-    ICL_HIP(ctx, hipMemcpy(t.data(), src.p, t.size() * 2, hipMemcpyDeviceToHost));
+    ICL_HIP(ctx, hipMemcpy(t.data(), src, t.size() * 2, hipMemcpyDeviceToHost));
     if (prec == ICL_PREC_BF16X3) host_join32(t.data(), n, dst);
     else
         for (size_t i = 0; i < n; ++i) dst[i] = host_from_bf16(t[i]);
@@ -965,7 +965,49 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
         int rc = launch_conv_prec(ctx, prec, conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, H, Cin, Cout, k, stride, pad, relu));
         if (!rc) {
             const hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? from_dev(ctx, prec, dy, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_fused: %s", hipGetErrorString(e));
+            rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_fused: %s", hipGetErrorString(e));
+        }
+        icl_prof_collect(ctx);
+        return rc;
+    });
+}
+
+// The dual-operand launch of launch_conv_fused_ds on the caller's tensors: a 1x1 convolution over x plus a 1x1 / stride2 convolution over
+// x2 accumulated into the same tiles, weights concatenated per output row as [w1 | w2]; the kernel is chosen by launch_conv_prec as in
+// the forward pass (icl_set_conv_options).  No residual: the production launch has none.
+extern "C" int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, int Ho, int Cin, const float *w1, const float *x2, int H2, int Cin2,
+                               const float *w2, int stride2, int Cout, const float *scale, const float *shift, int relu, float *y)
+{
+    if (!ctx || !x || !w1 || !x2 || !w2 || !scale || !shift || !y || B < 1 || Ho < 1 || H2 < 1 || stride2 < 1 || Cin < 1 || Cin2 < 1 || Cout < 1)
+        return icl_fail(ctx, ICL_ERR_ARG, "icl_conv2d_dual: bad argument");
+    if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
+    if ((int64_t)(Ho - 1) * stride2 >= H2) return icl_fail(ctx, ICL_ERR_ARG, "icl_conv2d_dual: output pixel %d reads row %lld of a %d-row second operand", Ho - 1, (long long)(Ho - 1) * stride2, H2);
+    if (Cin % 64 || Cin2 % 64 || Cout % 128) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_dual needs Cin %% 64 == 0, Cin2 %% 64 == 0 and Cout %% 128 == 0");
+    if ((int64_t)B * Ho * Ho >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_dual: %lld output pixels exceed the kernel's 32-bit pixel index", (long long)B * Ho * Ho);
+    return no_throw(ctx, "icl_conv2d_dual", [&]() -> int {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        const int K = Cin + Cin2;
+        const size_t nx = (size_t)B * Ho * Ho * Cin, nx2 = (size_t)B * H2 * H2 * Cin2, nw = (size_t)Cout * K, ny = (size_t)B * Ho * Ho * Cout;
+        std::vector<float> wp(nw);
+        for (int co = 0; co < Cout; ++co) {
+            memcpy(&wp[(size_t)co * K], w1 + (size_t)co * Cin, (size_t)Cin * 4);
+            memcpy(&wp[(size_t)co * K + Cin], w2 + (size_t)co * Cin2, (size_t)Cin2 * 4);
+        }
+        dev_buf dx, dx2, dw, dy, dz, dsc, dsh;
+        ICL_TRY(to_dev(ctx, prec, x, nx, dx));
+        ICL_TRY(to_dev(ctx, prec, x2, nx2, dx2));
+        if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_dual: zero page");
+        ICL_TRY(to_dev(ctx, prec, wp.data(), nw, dw));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, scale, (size_t)Cout, dsc));
+        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, shift, (size_t)Cout, dsh));
+        if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_dual: output alloc");
+        conv_args a = conv_plain(dx.p, dw.p, dy.p, nullptr, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, Ho, Cin, Cout, 1, 1, 0, relu);
+        conv_add_operand(a, dx2.p, H2, Cin2, stride2);
+        int rc = launch_conv_prec(ctx, prec, a);
+        if (!rc) {
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_dual: %s", hipGetErrorString(e));
         }
         icl_prof_collect(ctx);
         return rc;
@@ -1077,8 +1119,11 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     return launch_bneck56_args(ctx, a, ds != nullptr, strm);
 }
 
+// tap >= 0 (icl_embed_taps): the pass ends after the stem + maxpool (0) or after bottleneck `tap` (1..16) and *tap_x is the buffer that
+// holds that tensor; nothing else differs.
 template <typename T>
-static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, int head, float *d_out, int lane, hipStream_t strm)
+static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, int head, float *d_out, int lane, hipStream_t strm, int tap = -1,
+                         const void **tap_x = nullptr)
 {
     typedef typename T::elem elem;
     icl_model *m = ctx->model;
@@ -1103,7 +1148,7 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
         }
     }
     int ci = 1;
-    while (ci < m->nconv) {
+    for (int blk = 0; ci < m->nconv && blk != tap; ++blk) {
         const conv_layer &c1 = m->conv[ci], &c2 = m->conv[ci + 1], &c3 = m->conv[ci + 2];
         const bool has_ds = c1.rec.block == 0;
         if (prec == ICL_PREC_BF16 && c1.rec.stage == 1 && (fuse_mask() & (has_ds ? 4 : 2))) { // the whole bottleneck in one launch
@@ -1120,6 +1165,11 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
             ICL_TRY(launch_conv(ctx, prec, c3, t2, y, x, 1, B)); // relu(bn(conv) + residual)
         std::swap(x, y);
         ci += has_ds ? 4 : 3;
+    }
+    if (tap >= 0) {
+        *tap_x = x;
+        ICL_HIP(ctx, hipGetLastError());
+        return ICL_OK;
     }
     float *pooled = head == ICL_HEAD_POOLED ? d_out : m->pooled[lane];
     {
@@ -1154,7 +1204,7 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
         with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, ctx->stream); });
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        const int rc = e == hipSuccess ? from_dev(ctx, prec, dy, ny, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
+        const int rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
         icl_prof_collect(ctx);
         return rc;
     });
@@ -1208,8 +1258,41 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
         int rc = launch_bneck56_args(ctx, a, has_ds, ctx->stream); // the launch code of the forward pass
         if (!rc) {
             const hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? from_dev(ctx, ICL_PREC_BF16, dy, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: %s", hipGetErrorString(e));
+            rc = e == hipSuccess ? from_dev(ctx, ICL_PREC_BF16, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: %s", hipGetErrorString(e));
         }
+        icl_prof_collect(ctx);
+        return rc;
+    });
+}
+
+// The forward pass of the loaded model up to a tap, for the per-block parity tests: forward_batch on lane 0 for ONE batch of B images
+// (B <= the context's batch), ended after the stem + maxpool (tap 0: [B][56][56][64]) or after bottleneck `tap` (1..16, the 16th is
+// [B][7][7][2048]); out receives that tensor as fp32 NHWC.
+extern "C" int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *img, int B, int tap, float *out)
+{
+    if (!ctx || !img || !out || B < 1 || tap < 0 || tap > 16) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_taps: bad argument");
+    if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
+    return no_throw(ctx, "icl_embed_taps", [&]() -> int {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
+        if (B > ctx->batch) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_taps: %d images exceed the batch of %d", B, ctx->batch);
+        ICL_TRY(icl_model_ensure_ws(ctx, B, prec, 1));
+        int H = 56, C = 64; // the tapped tensor: the output of the block's last convolution
+        for (int i = 1, blk = 0; i < ctx->model->nconv && blk < tap; ++i)
+            if (ctx->model->conv[i].rec.role == 3) {
+                H = ctx->model->conv[i].rec.hout;
+                C = ctx->model->conv[i].rec.cout;
+                ++blk;
+            }
+        dev_buf dimg;
+        if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_embed_taps: image buffer");
+        if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: upload");
+        const void *x = nullptr;
+        int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, ICL_HEAD_POOLED, nullptr, 0, ctx->stream, tap, &x); });
+        ctx->cur_stream = nullptr;
+        const hipError_t e = hipStreamSynchronize(ctx->stream); // (also after a failed launch: dimg is freed on return)
+        if (!rc) rc = e == hipSuccess ? from_dev(ctx, prec, x, (size_t)B * H * H * C, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: %s", hipGetErrorString(e));
         icl_prof_collect(ctx);
         return rc;
     });

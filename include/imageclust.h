@@ -184,6 +184,19 @@ int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int C
                      int stride, int pad, const float *scale, const float *shift, const float *residual, int relu,
                      float *y);
 
+/* The dual-operand launch that computes block 0 of stages 2-4 (a bottleneck's last 1x1 convolution and its downsample branch in one
+ * launch), host buffers, for the parity tests: y = relu?( (x . w1 + x2[:, ::stride2, ::stride2] . w2) * scale[c] + shift[c] ).
+ * x: [B][Ho][Ho][Cin], w1: [Cout][Cin], x2: [B][H2][H2][Cin2], w2: [Cout][Cin2], y: [B][Ho][Ho][Cout], all fp32, NHWC.  Needs
+ * (Ho - 1) * stride2 < H2 (ICL_ERR_ARG otherwise), Cin % 64 == 0, Cin2 % 64 == 0 and Cout % 128 == 0 (ICL_ERR_UNSUPPORTED).  The kernel
+ * is chosen as in the forward pass (icl_set_conv_options); operands are stored as icl_conv2d_fused stores them. */
+int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, int Ho, int Cin, const float *w1, const float *x2, int H2, int Cin2,
+                    const float *w2, int stride2, int Cout, const float *scale, const float *shift, int relu, float *y);
+/* The forward pass of the loaded model on ONE batch of B images (B <= icl_set_batch's batch), ended at a tap, for the per-block parity
+ * tests: out receives, as fp32 NHWC, the tensor the pass holds after the stem + maxpool (tap 0: [B][56][56][64]) or after bottleneck
+ * tap (1..16: [B][56][56][256] x 3, [B][28][28][512] x 4, [B][14][14][1024] x 6, [B][7][7][2048] x 3).  Same kernels, order and
+ * buffers as icl_embed_u8. */
+int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *hwc_rgb, int B, int tap, float *out);
+
 /* The two cross-layer fusions of the forward pass (the reference's OpenCV-DNN fuses layers inside Net.Forward,
  * embeddings.go:141), exposed one at a time for the per-layer parity tests, host buffers:
  * icl_stem_pool: conv0 7x7/2 + BN + ReLU + maxpool 3x3/2 of the LOADED model in one launch.  img: B x 224x224x3 u8 HWC RGB,

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import resnet_blocks as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -51,14 +52,9 @@ def ref_conv_hw(x_nhwc, w, scale, shift, stride, pad, relu):
 
 
 def conv0_of_blob(blob):
-    """conv0's weights and folded BatchNorm out of the ICLW blob (include/icl_model_format.h: 80-byte header, then W, gamma,
-    beta, mean, var; conv0 carries no bias)."""
-    p = np.frombuffer(blob, np.float32, offset=80)
-    eps = float(np.frombuffer(blob, np.float32, count=1, offset=8)[0])
-    w = p[:64 * 3 * 49].reshape(64, 3, 7, 7)
-    g, be, mu, var = (p[64 * 147 + i * 64:64 * 147 + (i + 1) * 64].astype(np.float64) for i in range(4))
-    s = g / np.sqrt(var + eps)
-    return w.copy(), s.astype(np.float32), (be - mu * s).astype(np.float32)
+    """conv0's weights and folded BatchNorm out of the ICLW blob (include/icl_model_format.h), by the blob reader of the per-block tests."""
+    L0 = RB.read_blob(blob).layers[0]
+    return L0.W.copy(), L0.scale, L0.shift
 
 
 def ref_maxpool(y_nhwc):
