@@ -109,3 +109,106 @@ func LastManyStats() (small, mid, large, midGroups int64, err error) {
 	}
 	return int64(a), int64(b), int64(c), int64(d), nil
 }
+
+// Request is one workflow.Run call's input as icl_cluster_requests takes it: the image files, each image's label columns within
+// the request's label set (GenerateLabelVector's indices; -1 for a label the set does not hold) and the size constraints.
+type Request struct {
+	Paths   []string
+	Labels  [][]int32 // per image
+	NLabels int       // len(LabelSet)
+	MinSize int
+	MaxSize int
+}
+
+// RequestResult is one request's outcome: Status is ICL_OK, ICL_ERR_CONSTRAINT (the reference's (nil,false)) or the code of its
+// lowest failed file; ClusterID / MemberRank are per image (-1 rows when the request failed).
+type RequestResult struct {
+	Status     int
+	ClusterID  []int32
+	MemberRank []int32
+	NClusters  int
+}
+
+// ClusterRequests runs createEmbeddings + PerformClusteringWithConstraints (workflow.go:84-94) for every request in ONE engine
+// call (icl_cluster_requests): the combined embeddings are assembled on the GPU and never cross PCIe.  head: ICL_HEAD_DENSE0 or
+// ICL_HEAD_POOLED; prec: ICL_PREC_*; threads: host decode threads (0 = up to 16).  The returned error names the lowest failed
+// request; the results of the others are valid beside it.
+func ClusterRequests(reqs []Request, head, prec, threads int) ([]RequestResult, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, e
+	}
+	if len(reqs) == 0 {
+		return nil, nil
+	}
+	var paths []*C.char
+	defer func() {
+		for _, p := range paths {
+			C.free(unsafe.Pointer(p))
+		}
+	}()
+	n := make([]C.int32_t, len(reqs))
+	nl := make([]C.int32_t, len(reqs))
+	mn := make([]C.int32_t, len(reqs))
+	mx := make([]C.int32_t, len(reqs))
+	off := []C.int64_t{0}
+	idx := []C.int32_t{}
+	for r, q := range reqs {
+		if len(q.Labels) != len(q.Paths) {
+			return nil, fmt.Errorf("request %d: %d paths, %d label lists", r, len(q.Paths), len(q.Labels))
+		}
+		n[r], nl[r], mn[r], mx[r] = C.int32_t(len(q.Paths)), C.int32_t(q.NLabels), C.int32_t(q.MinSize), C.int32_t(q.MaxSize)
+		for i, p := range q.Paths {
+			paths = append(paths, C.CString(p))
+			for _, j := range q.Labels[i] {
+				idx = append(idx, C.int32_t(j))
+			}
+			off = append(off, C.int64_t(len(idx)))
+		}
+	}
+	rows := len(paths)
+	cid := make([]C.int32_t, rows+1)
+	rank := make([]C.int32_t, rows+1)
+	nc := make([]C.int32_t, len(reqs))
+	nm := make([]C.int32_t, len(reqs))
+	st := make([]C.int32_t, len(reqs))
+	for r := range st {
+		st[r] = -1 // stays -1 when the call fails before the requests run
+	}
+	paths = append(paths, nil) // (never read: keeps &paths[0] valid for a call without images)
+	idx = append(idx, 0)
+	rc := C.icl_cluster_requests((*C.icl_ctx)(raw), C.int32_t(len(reqs)), (**C.char)(unsafe.Pointer(&paths[0])), &n[0], &nl[0], &off[0], &idx[0],
+		&mn[0], &mx[0], C.int(head), C.int(prec), C.int32_t(threads), &cid[0], &rank[0], &nc[0], &nm[0], nil, &st[0], nil, nil)
+	paths = paths[:rows]
+	var callErr error
+	if rc != C.ICL_OK {
+		callErr = fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		if st[0] < 0 { // still the -1 put there: an argument or device error, status untouched (imageclust.h), no per-request results
+			return nil, callErr
+		}
+	}
+	out := make([]RequestResult, len(reqs))
+	at := 0
+	for r, q := range reqs {
+		k := len(q.Paths)
+		out[r] = RequestResult{Status: int(st[r]), NClusters: int(nc[r]), ClusterID: make([]int32, k), MemberRank: make([]int32, k)}
+		for i := 0; i < k; i++ {
+			out[r].ClusterID[i], out[r].MemberRank[i] = int32(cid[at+i]), int32(rank[at+i])
+		}
+		at += k
+	}
+	return out, callErr
+}
+
+// LastRequestsMs reports the stage wall times of the last ClusterRequests: files -> embedding rows, assembly, clustering.
+func LastRequestsMs() (embedMs, assembleMs, clusterMs float64, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return 0, 0, 0, e
+	}
+	var a, b, c C.double
+	if rc := C.icl_last_requests_ms((*C.icl_ctx)(raw), &a, &b, &c); rc != C.ICL_OK {
+		return 0, 0, 0, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return float64(a), float64(b), float64(c), nil
+}

@@ -112,6 +112,9 @@ SYMBOLS = [
     ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
+    ("icl_requests_layout", _int, [_i32, _vp, _vp, _int, _vp, _vp, _pi64]),
+    ("icl_cluster_requests", _int, [_vp, _i32] + [_vp] * 7 + [_int, _int, _i32] + [_vp] * 8),
+    ("icl_last_requests_ms", _int, [_vp, _pd, _pd, _pd]),
     ("icl_last_merges", _i64, [_vp, _vp, _i64]),
     ("icl_last_merge_values", _i64, [_vp, _vp, _i64]),
     ("icl_distance_mfma_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i64]),
@@ -200,6 +203,46 @@ def pack_many(problems):
     return dict(E=buf, e_off=np.array(off, np.int64), n=n, d=np.array([E.shape[1] for E in mats], np.int32),
                 min_size=np.array([int(p[1]) for p in problems], np.int32), max_size=np.array([int(p[2]) for p in problems], np.int32),
                 img_off=np.concatenate([[0], np.cumsum(n, dtype=np.int64)]))
+
+
+def requests_layout(n, n_labels, head=HEAD_DENSE0):
+    """icl_requests_layout (host only): where each request's combined rows live -> (e_off int64[nreq], d int32[nreq], e_len):
+    d[r] = head + n_labels[r], e_off[r] = sum of n[q] * d[q] over q < r."""
+    n = np.ascontiguousarray(n, np.int32)
+    n_labels = np.ascontiguousarray(n_labels, np.int32)
+    if n.shape != n_labels.shape or n.ndim != 1:
+        raise ValueError("n and n_labels must be 1-D and of one length")
+    e_off, d, e_len = np.zeros(max(len(n), 1), np.int64), np.zeros(max(len(n), 1), np.int32), _i64()
+    rc = load().icl_requests_layout(len(n), n.ctypes.data, n_labels.ctypes.data, head, e_off.ctypes.data, d.ctypes.data, C.byref(e_len))
+    if rc != ICL_OK:
+        raise ICLError(rc, "icl_requests_layout: bad argument")
+    return e_off[:len(n)], d[:len(n)], int(e_len.value)
+
+
+def pack_requests(requests, head=HEAD_DENSE0):
+    """The arguments of icl_cluster_requests (host only) for requests = [(paths, labels_per_image, n_labels, min_size, max_size), ...],
+    labels_per_image[i] being image i's list of column indices within the request's label set (-1: a label the set does not hold; an empty
+    list and duplicates are fine) -> dict(paths, n, n_labels, label_off, label_idx, min_size, max_size, img_off, e_off, d, e_len)."""
+    paths, n, nl, off, idx, mn, mx = [], [], [], [0], [], [], []
+    for r, (ps, labels, n_labels, lo, hi) in enumerate(requests):
+        if len(labels) != len(ps):
+            raise ValueError("request %d: %d paths, %d label lists" % (r, len(ps), len(labels)))
+        paths += list(ps)
+        n.append(len(ps))
+        nl.append(int(n_labels))
+        for li in labels:
+            li = [int(j) for j in li]
+            if any(j < -1 or j >= int(n_labels) for j in li):
+                raise ValueError("request %d: label index outside [-1, %d)" % (r, n_labels))
+            idx += li
+            off.append(len(idx))
+        mn.append(int(lo))
+        mx.append(int(hi))
+    n = np.array(n, np.int32)
+    e_off, d, e_len = requests_layout(n, nl, head)
+    return dict(paths=paths, n=n, n_labels=np.array(nl, np.int32), label_off=np.array(off, np.int64), label_idx=np.array(idx, np.int32),
+                min_size=np.array(mn, np.int32), max_size=np.array(mx, np.int32),
+                img_off=np.concatenate([[0], np.cumsum(n, dtype=np.int64)]), e_off=e_off, d=d, e_len=e_len)
 
 
 class Context:
@@ -579,6 +622,42 @@ class Context:
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         check(self.h, self.L.icl_last_many_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"small": a.value, "mid": b.value, "large": c.value, "mid_groups": d.value}
+
+    def cluster_requests(self, requests, head=HEAD_DENSE0, prec=PREC_FP32, threads=0, want_merges=False, want_E=False):
+        """icl_cluster_requests: workflow.Run for many requests in one call, requests as pack_requests() takes them -> a list of
+        (cluster_id, member_rank, n_clusters, status[, merge log][, E]) per request, as cluster_many() gives them; status is ICL_OK,
+        ICL_ERR_CONSTRAINT or the code of the request's lowest failed file (rows of -1 then).  want_E=True appends the request's combined
+        rows (n x d float32).  self.last_file_status holds every image's code afterwards and self.last_requests_rc the call's own (the lowest
+        failed request's; last_error() names it).  Raises for an argument or device error."""
+        pk = pack_requests(requests, head)
+        nreq, rows = len(pk["n"]), int(pk["img_off"][-1])
+        enc = [os.fsencode(p) for p in pk["paths"]]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        cid = np.full(max(rows, 1), -1, np.int32)
+        rank = np.full(max(rows, 1), -1, np.int32)
+        nc, nm = np.zeros(max(nreq, 1), np.int32), np.zeros(max(nreq, 1), np.int32)
+        st = np.full(max(nreq, 1), -1, np.int32)  # left untouched (imageclust.h) when the call fails with a code that is no request's own
+        fst = np.zeros(max(rows, 1), np.int32)
+        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        E = np.zeros(max(pk["e_len"], 1), np.float32) if want_E else None
+        ptr = lambda a: a.ctypes.data
+        rc = self.L.icl_cluster_requests(self.h, nreq, arr, ptr(pk["n"]), ptr(pk["n_labels"]), ptr(pk["label_off"]), ptr(pk["label_idx"]),
+                                         ptr(pk["min_size"]), ptr(pk["max_size"]), head, prec, threads, ptr(cid), ptr(rank), ptr(nc), ptr(nm),
+                                         ptr(mg) if want_merges else None, ptr(st), ptr(fst), ptr(E) if want_E else None)
+        if rc != ICL_OK and (st[:nreq] < 0).any():
+            check(self.h, rc)
+        self.last_file_status, self.last_requests_rc = fst[:rows].copy(), rc
+        out = _unpack_many(pk, cid, rank, nc, nm, st, mg)
+        if want_E:
+            out = [r + (E[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)
+                   for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]
+        return out
+
+    def last_requests_ms(self):
+        """Stage wall times of the last cluster_requests: files -> embedding rows, assembly, clustering (ms)."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        check(self.h, self.L.icl_last_requests_ms(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"embed_ms": a.value, "assemble_ms": b.value, "cluster_ms": c.value}
 
     def cluster_many_dev(self, d_E, e_len, e_off, n, d, min_size, max_size, want_merges=False):
         """icl_cluster_many_dev on a device buffer of e_len floats; per-problem arrays as pack_many() gives them.  Same result as cluster_many()."""

@@ -30,6 +30,7 @@ struct icl_model;  // resnet_model.h
 struct icl_ward_ws; // ward.hip
 struct icl_ingest_ws; // jpeg_gpu.hip
 struct icl_many_ws; // ward_many.hip
+struct icl_requests_ws; // requests.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -131,6 +132,8 @@ struct icl_ctx {
     double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode
     int entropy_mode = 0;                 // icl_set_ingest_options: ICL_ENTROPY_HOST / ICL_ENTROPY_GPU (environment: ICL_JPEG_ENTROPY=gpu)
     int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
+    icl_requests_ws *requests = nullptr; // device buffers and stage events of icl_cluster_requests (requests.hip; created on first use)
+    double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
@@ -181,6 +184,26 @@ void icl_ward_free(icl_ctx *ctx);
 void icl_file_batcher_free(icl_ctx *ctx);
 void icl_ingest_free(icl_ctx *ctx);
 void icl_many_free(icl_ctx *ctx);
+void icl_requests_free(icl_ctx *ctx);
+
+// The two batched halves icl_cluster_requests (requests.hip) joins; both expect ctx->mu held and the context's device selected.
+// Each tells its caller apart what the return code alone cannot: "the list was processed and an item of it failed" from "the call stopped".
+struct icl_item_failure { // the lowest failed file / problem of a call that ran to its end (index -1: none failed)
+    int64_t index = -1;
+    int rc = ICL_OK;
+    std::string why; // the item's own reason, without the caller's prefix
+};
+// jpeg_gpu.hip: the file pipeline behind icl_load_images_224_dev (mode 0) and icl_embed_files[_dev] (mode 1: embeddings into host `out`,
+// 2: into device `out`).  Returns the code of the lowest failed file (status[] carries every file's, failed rows are NaN) after the whole
+// list has been processed -- lowest (may be NULL) then names that file -- or the error that stopped it (lowest->index stays -1).
+int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
+                 int32_t *status, const char *what, icl_item_failure *lowest = nullptr);
+// ward_many.hip: icl_cluster_many[_dev] after the argument check (d_E on the device, or h_E on the host and uploaded there).  Returns the
+// code of the lowest failed problem once every problem has its results -- lowest (may be NULL) then names it -- or the error that
+// stopped the call (lowest->index stays -1; the per-problem outputs are not valid).
+int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off, const int32_t *n,
+                        const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
+                        int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest = nullptr);
 
 static inline int64_t icl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -84,6 +84,7 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     icl_file_batcher_free(ctx);
     icl_ingest_free(ctx);
     icl_many_free(ctx);
+    icl_requests_free(ctx);
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

@@ -799,9 +799,9 @@ static int ingest_pass(icl_ctx *ctx, const char *const *paths, int64_t n, int32_
 
 // The pipeline: one pass in the context's entropy mode; the images the GPU entropy check rejected are then redone by a pass in
 // ICL_ENTROPY_HOST mode over those files alone (rows do not depend on the batch they are rebuilt or embedded in), which also produces
-// their status codes and messages.
-static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
-                        int32_t *status, const char *what)
+// their status codes and messages.  (Declared in icl_common.h: icl_cluster_requests, requests.hip, calls it with mode 2.)
+int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
+                 int32_t *status, const char *what, icl_item_failure *lowest_out)
 {
     std::vector<file_fail> fails;
     std::vector<int64_t> rejected;
@@ -852,6 +852,7 @@ static int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32
     const file_fail *lowest = nullptr;
     for (const file_fail &f : fails)
         if (!lowest || f.index < lowest->index) lowest = &f;
+    if (lowest && lowest_out) *lowest_out = icl_item_failure{lowest->index, lowest->rc, lowest->err};
     if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
     return ICL_OK;
 }

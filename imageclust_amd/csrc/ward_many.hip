@@ -958,7 +958,8 @@ static int wm_enqueue(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const float *
 
 // ids from the merge logs (clustering.go:265-280, ward.hip's rule), merge logs, statuses; the lowest failed problem's error
 static int wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, std::vector<std::vector<int32_t>> &big_log,
-                      int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
+                      int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
+                      icl_item_failure *lowest)
 {
     std::vector<int32_t> pairs;
     for (int32_t p = 0; p < A.nprob; ++p) {
@@ -991,15 +992,19 @@ static int wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::ve
         status[p] = pl.st[p];
     }
     for (int32_t p = 0; p < A.nprob; ++p)
-        if (pl.st[p] != ICL_OK) return icl_fail(ctx, pl.st[p], "icl_cluster_many: problem %d: %s", p, pl.why[p].c_str());
+        if (pl.st[p] != ICL_OK) {
+            if (lowest) *lowest = icl_item_failure{p, pl.st[p], pl.why[p]};
+            return icl_fail(ctx, pl.st[p], "icl_cluster_many: problem %d: %s", p, pl.why[p].c_str());
+        }
     return ICL_OK;
 }
 
 // Both entry points, after the argument check, with ctx->mu held.  d_E: the embeddings on the device (e_len floats); h_E: the host copy
-// (icl_cluster_many), uploaded into the workspace here, or nullptr.
-static int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
+// (icl_cluster_many), uploaded into the workspace here, or nullptr.  (Declared in icl_common.h: icl_cluster_requests, requests.hip, is the
+// third caller.)
+int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
                                const int32_t *n, const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id,
-                               int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
+                               int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest)
 {
     const wm_args A = {nprob, e_off, n, d, min_size, max_size};
     wm_plan pl;
@@ -1028,7 +1033,7 @@ static int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, co
         }
     }
     if (!pl.groups.empty()) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return wm_collect(ctx, A, pl, slab, big_log, cluster_id, member_rank, n_clusters, n_merges, merges, status);
+    return wm_collect(ctx, A, pl, slab, big_log, cluster_id, member_rank, n_clusters, n_merges, merges, status, lowest);
 }
 
 extern "C" int icl_set_many_options(icl_ctx *ctx, int mid_mode)

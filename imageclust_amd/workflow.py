@@ -1,0 +1,47 @@
+"""Host-side mirror of the reference's internal/workflow/workflow.go over the HIP engine: workflow.Run (:84-94) for a queue of requests.
+
+The reference serves one request at a time: createEmbeddings (:149-185) embeds every image and appends its one-hot label vector
+(GenerateLabelVector + CombineEmbeddings), then PerformClusteringWithConstraints (:89) clusters the combined rows.  RunRequests does that
+for many requests in ONE engine call (icl_cluster_requests): the files are decoded and embedded in slabs, the combined rows are assembled
+on the GPU and clustered there, one workgroup per request; only cluster ids come back.  No CPU fallback.
+"""
+from typing import Dict, List, Optional, Sequence, Tuple
+
+from . import _lib
+from .clustering import clusters_as_map
+from .embeddings import AppContext
+
+Request = Tuple[Sequence[str], Sequence[str], Sequence[Sequence[str]], Dict[str, int], int, int]
+
+
+def LabelIndices(labels: Sequence[str], labelSet: Dict[str, int]) -> List[int]:
+    """The columns GenerateLabelVector (embeddings.go:166-174) sets for one image: labelSet[label], or -1 for a label the set does not
+    hold (:169, ignored by the engine)."""
+    return [int(labelSet.get(label, -1)) for label in labels]
+
+
+def PackRequests(requests: Sequence[Request]):
+    """requests -> what _lib.pack_requests takes: (paths, label indices per image, len(labelSet), minSize, maxSize) per request."""
+    out = []
+    for r, (paths, ids, labels_per_image, labelSet, minSize, maxSize) in enumerate(requests):
+        if len(ids) != len(paths) or len(labels_per_image) != len(paths):
+            raise ValueError("request %d: %d paths, %d ids, %d label lists" % (r, len(paths), len(ids), len(labels_per_image)))
+        out.append((list(paths), [LabelIndices(labels, labelSet) for labels in labels_per_image], len(labelSet), minSize, maxSize))
+    return out
+
+
+def RunRequests(appCtx: AppContext, requests: Sequence[Request], prec: int = _lib.PREC_FP32, threads: int = 0,
+                statuses: Optional[List[int]] = None) -> List[Tuple[Optional[Dict[int, List[str]]], bool]]:
+    """workflow.go:84-94 for every request = (paths, ids, labels_per_image, labelSet, minSize, maxSize) -> [(map cluster id -> member ids,
+    ok), ...], each entry what PerformClusteringWithConstraints returns for that request's combined embeddings: (None, False) when the
+    constraints cannot be met -- and when one of the request's files cannot be read (workflow.go:162-181 fails the request; the others
+    are unaffected).  `statuses`, when given, receives every request's ICL_* code."""
+    if appCtx.Net is None or appCtx.Net.Empty():
+        raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunRequests: no model loaded")
+    res = appCtx.Net.ctx.cluster_requests(PackRequests(requests), appCtx.Head, prec, threads)
+    out = []
+    for (_, ids, _, _, _, _), (cid, rank, _, st) in zip(requests, res):
+        if statuses is not None:
+            statuses.append(int(st))
+        out.append((clusters_as_map(cid, rank, list(ids)), True) if st == _lib.ICL_OK else (None, False))
+    return out

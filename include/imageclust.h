@@ -329,6 +329,43 @@ int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t 
 int icl_set_many_options(icl_ctx *ctx, int mid_mode);
 /* problems of the last icl_cluster_many[_dev] call by route, and the number of mid-route groups it was run in (any pointer may be NULL) */
 int icl_last_many_stats(icl_ctx *ctx, int64_t *small, int64_t *mid, int64_t *large, int64_t *mid_groups);
+/* ---- a queue of requests, files to cluster ids: replaces workflow.Run (workflow.go:84-94) for nreq requests in ONE call ----
+ * Request r is n[r] image files with labels.  Every image gets its embedding row (GetImageEmbedding; head, prec as icl_embed_files), a one-hot
+ * vector over the request's label set is appended (GenerateLabelVector + CombineEmbeddings, embeddings.go:166-183: d[r] = head + n_labels[r]
+ * columns) and the combined rows are clustered (PerformClusteringWithConstraints, exact mode).  The combined rows are assembled on the GPU
+ * (requests.hip) and stay there between the two halves.
+ * icl_requests_layout (host only, no GPU): where request r's rows live in E and how wide they are: d[r] = head + n_labels[r],
+ * e_off[r] = sum over q < r of n[q] * d[q] (rows contiguous, requests back to back), *e_len = the total number of floats.  Any output may be NULL.
+ * ICL_ERR_ARG (nothing written) for nreq < 0, head < 0, a null input, a negative n / n_labels or a row length beyond int32.
+ * icl_cluster_requests: paths lists all images, request after request (sum of n[r] entries).  Image i's labels are
+ * label_idx[label_off[i] .. label_off[i + 1]): columns within its request's label set; -1 = "label not in the set" (embeddings.go:169) is
+ * ignored, a column listed twice is set once.  Outputs use the icl_cluster_many layout: request r's images occupy [img_off(r), img_off(r) +
+ * n[r]) of cluster_id / member_rank, img_off(r) = n[0] + ... + n[r-1], and its merge log (merges may be NULL) starts at 2 * img_off(r) with
+ * n_merges[r] pairs.  For every request whose files were all read the results -- ids, ranks, n_clusters[r], merge log, and its rows of E_out --
+ * are bit for bit those of icl_embed_files(head, prec) on its paths, CombineEmbeddings on the host, then icl_cluster_many on those rows.
+ * status[r] = ICL_OK, ICL_ERR_CONSTRAINT for the reference's (nil,false), or -- a request with a file that cannot be read fails as a whole
+ * (workflow.go:162-181) -- the code of its lowest failed file; a failed request's rows are -1 and its n_clusters[r] and n_merges[r] are 0.
+ * Requests with a failed file are left out of the clustering launches; the others are unaffected.  file_status (may be NULL): every image's
+ * code, as icl_embed_files gives it.  E_out (host, e_len floats of icl_requests_layout, may be NULL): the combined rows of every request,
+ * with NaN in the embedding part of failed files.
+ * Returns ICL_OK when every request succeeded; otherwise the code of the LOWEST failed request, which icl_last_error names together with
+ * the file where there is one.  ICL_ERR_ARG (nothing written): a null pointer, nreq < 0, a negative n / n_labels, label_off decreasing or
+ * starting below 0, a label index outside [-1, n_labels[r]), an unknown head / prec, threads < 0.  ICL_ERR_NOMODEL before anything runs.
+ * Every ICL_* code is >= 0, and status is written only together with the per-request results: when the call returns a code that is not a
+ * request's own failure (ICL_ERR_ARG, ICL_ERR_NOMODEL, a device or memory error that stopped it) status and every other output's per-request
+ * meaning are void and status itself is left untouched -- a caller that pre-fills status with -1 finds the -1 still there.
+ * The context's mutex is held once for the whole call; icl_set_ingest_options, icl_set_many_options, icl_set_batch and icl_set_conv_options
+ * apply as they do to icl_embed_files and icl_cluster_many; icl_last_ingest_stats, icl_last_entropy_stats and icl_last_many_stats report this
+ * call afterwards; what icl_last_merges and icl_last_ward_* report about the last icl_cluster stays unchanged.
+ * icl_last_requests_ms: wall times (ms, HIP events on the context stream) of the last icl_cluster_requests: files -> embedding rows,
+ * assembly of the combined rows, clustering (any pointer may be NULL). */
+int icl_requests_layout(int32_t nreq, const int32_t *n, const int32_t *n_labels, int head, int64_t *e_off /* nreq */, int32_t *d /* nreq */,
+                        int64_t *e_len);
+int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *const *paths, const int32_t *n, const int32_t *n_labels,
+                         const int64_t *label_off /* sum n[r] + 1 */, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size,
+                         int head, int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
+                         int32_t *merges, int32_t *status /* nreq */, int32_t *file_status /* sum n[r] */, float *E_out);
+int icl_last_requests_ms(icl_ctx *ctx, double *embed_ms, double *assemble_ms, double *cluster_ms);
 /* workflow.go:84-94 on one GPU in one call: embed n resident images (2048-d pooled head, into d_E: device, n x 2048) and
  * cluster them.  flags & ICL_FUSE_OVERLAP: the distance rows of already-embedded images are computed on a side stream of the
  * context while later batches embed (same kernels, same results as icl_embed_u8_dev + icl_cluster_dev, bit for bit). */
