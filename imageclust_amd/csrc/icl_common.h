@@ -168,6 +168,15 @@ struct icl_device_guard {
     }
 };
 
+// hip_guard releases a HIP resource on every way out of a scope (ICL_HIP / ICL_TRY / icl_fail return early)
+template <class T, hipError_t (*Release)(T)> struct hip_guard {
+    T p = nullptr;
+    ~hip_guard() { if (p) (void)Release(p); }
+};
+using ev_guard = hip_guard<hipEvent_t, hipEventDestroy>;
+using dev_guard = hip_guard<void *, hipFree>;
+using pin_guard = hip_guard<void *, hipHostFree>;
+
 // Profiling bracket: when enabled records two events around a launch and attributes algorithmic work.
 struct icl_prof_scope {
     icl_ctx *c;
@@ -193,11 +202,28 @@ struct icl_item_failure { // the lowest failed file / problem of a call that ran
     int rc = ICL_OK;
     std::string why; // the item's own reason, without the caller's prefix
 };
-// jpeg_gpu.hip: the file pipeline behind icl_load_images_224_dev (mode 0) and icl_embed_files[_dev] (mode 1: embeddings into host `out`,
-// 2: into device `out`).  Returns the code of the lowest failed file (status[] carries every file's, failed rows are NaN) after the whole
-// list has been processed -- lowest (may be NULL) then names that file -- or the error that stopped it (lowest->index stays -1).
-int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
-                 int32_t *status, const char *what, icl_item_failure *lowest = nullptr);
+// Where the file pipeline leaves its rows: u8 images on the device (icl_load_images_224_dev), embeddings on the host (icl_embed_files)
+// or on the device (icl_embed_files_dev, icl_cluster_requests).  head and prec belong to the embedding sinks.
+struct ingest_sink {
+    enum kind_t { U8_DEV, EMB_HOST, EMB_DEV } kind;
+    void *dst;
+    int head, prec;
+    bool embeds() const { return kind != U8_DEV; }
+    size_t row_bytes() const { return embeds() ? (size_t)head * 4 : (size_t)ICL_IMG_BYTES; }
+    void *row(int64_t i) const { return (uint8_t *)dst + (size_t)i * row_bytes(); }
+};
+// jpeg_gpu.hip: the file pipeline behind those entry points: one ingest_pass in the context's entropy mode (per slab: slab_collect ->
+// run_slab_decode -> slab_deliver), then a repair pass in host mode over the files the GPU entropy check rejected.  Returns the code of
+// the lowest failed file (status[] carries every file's; failed rows are zero (u8) or NaN) after the whole list has been processed --
+// lowest (may be NULL) then names that file -- or the error that stopped it (lowest->index stays -1).
+int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
+                 icl_item_failure *lowest = nullptr);
+static inline void icl_ingest_stats_reset(icl_ctx *ctx) // what a batched file call reports (icl_last_ingest_stats, icl_last_entropy_stats)
+{
+    ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
+    ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
+    ctx->ingest_decode_s = 0;
+}
 // ward_many.hip: icl_cluster_many[_dev] after the argument check (d_E on the device, or h_E on the host and uploaded there).  Returns the
 // code of the lowest failed problem once every problem has its results -- lowest (may be NULL) then names it -- or the error that
 // stopped the call (lowest->index stays -1; the per-problem outputs are not valid).

@@ -10,7 +10,13 @@
 // Kernels: jpeg_idct_kernel (one thread per 8x8 block -> u8 planes in a scratch), jpeg_gather_resize_kernel (one thread per
 // output pixel: reads the 2x2 source pixels of the resize through the orientation map, upsamples the chroma at those
 // positions only, converts the colour and resizes).  Nothing is built at full-resolution RGB.
+//
+// Host driver: ingest_files = one ingest_pass in the context's entropy mode + a repair pass in host mode over the files the GPU entropy
+// check rejected.  ingest_pass = ingest_buffers, then per slab slab_collect (rows in file order from the worker threads' ingest_feed,
+// ingest_feed.h, into a pinned slab; slab_fill::fits says when a slab is full) -> run_slab_decode (upload, entropy decode, IDCT) ->
+// slab_deliver (gather / resize, forward pass, NaN rows of failed files, into the call's ingest_sink), then tally_accepted.
 #include "icl_common.h"
+#include "ingest_feed.h"
 #include "ingest_pixels.h"
 #include "jpeg_stage.h"
 #include "resnet_model.h" // icl_embed_dev_locked
@@ -227,6 +233,22 @@ constexpr int64_t SLAB_SUBS = SLAB_PAYLOAD / (ICL_JE_SUB_BITS / 8); // ... subse
 constexpr int64_t SLAB_WGS = SLAB_SUBS / ICL_JE_WG + SLAB_IMAGES;   // ... workgroups (every image rounds up)
 constexpr int64_t HDR_SCANS = SLAB_IMAGES * (int64_t)sizeof(ingest_image) + 3 * SLAB_IMAGES * (int64_t)sizeof(ingest_plane); // offset of the scan descriptors
 constexpr int64_t HDR_BYTES = HDR_SCANS + SLAB_IMAGES * (int64_t)sizeof(icl_je_scan);
+// slab_fill::fits (below) tests rows, payload, scratch and subsequences; the other limits follow from those:
+static_assert(SLAB_COEF == 2 * SLAB_SCRATCH, "a stream plane's dense coefficients are two bytes per plane sample: coef_used <= 2 * scratch_used");
+static_assert(SLAB_WGS == SLAB_SUBS / ICL_JE_WG + SLAB_IMAGES, "sum of ceil(nsub_i / WG) over k <= SLAB_IMAGES scans <= floor(sum nsub_i / WG) + k");
+// (scans: at most one per row, SLAB_IMAGES of them in the header; planes: at most three per row, 3 * SLAB_IMAGES in the header)
+
+// the parts of a slab: its header (HDR_BYTES: images, planes, scan descriptors) and its payload, in pinned host or in device memory
+struct slab_view {
+    ingest_image *imgs;
+    ingest_plane *planes;
+    icl_je_scan *scans;
+    uint8_t *payload;
+    slab_view(uint8_t *hdr, uint8_t *pay)
+        : imgs((ingest_image *)hdr), planes((ingest_plane *)(hdr + SLAB_IMAGES * sizeof(ingest_image))), scans((icl_je_scan *)(hdr + HDR_SCANS)), payload(pay)
+    {
+    }
+};
 
 static int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
@@ -422,6 +444,8 @@ struct icl_ingest_ws {
     int32_t *d_accepted = nullptr;
     int32_t *h_accepted = nullptr; // pinned: one flag per stream image of a call
     int64_t h_accepted_cap = 0;
+    slab_view host(int q) const { return slab_view(h_slab[q], h_slab[q] + HDR_BYTES); }
+    slab_view dev() const { return slab_view(d_hdr, d_payload); }
     ~icl_ingest_ws()
     {
         for (int q = 0; q < 2; ++q) {
@@ -489,12 +513,20 @@ namespace {
 struct slab_fill {
     int nimg = 0, npl = 0, nscan = 0, npacked = 0, ndense = 0;
     int64_t used = 0, scratch_used = 0, blocks = 0, coef_used = 0 /* bytes */, subs = 0, wgs = 0;
+    // What a slab holds: does r still fit behind what has been placed?  (A result alone always does: pack_jpeg / pack_stream saw to it.)
+    bool fits(const file_result &r) const
+    {
+        const int64_t pay = r.kind == KIND_FAILED ? 0 : align16((int64_t)r.packed.size()), nsub = r.kind == KIND_JSTREAM ? (int64_t)r.scan.nsub : 0;
+        return nimg < SLAB_IMAGES && used + pay <= SLAB_PAYLOAD && scratch_used + align16(r.plane_bytes) <= SLAB_SCRATCH && subs + nsub <= SLAB_SUBS;
+    }
 };
 
 // One KIND_JPEG / KIND_JSTREAM result into the slab: image descriptor, planes, payload, and (stream) the scan descriptor.
-static bool place_jpeg(const file_result &r, slab_fill &F, ingest_image &D, ingest_plane *pls, icl_je_scan *scans, uint8_t *pay)
+static bool place_jpeg(const file_result &r, slab_fill &F, const slab_view &S)
 {
+    if (!F.fits(r)) return false;
     const bool stream = r.kind == KIND_JSTREAM;
+    ingest_image &D = S.imgs[F.nimg];
     D.kind = KIND_JPEG;
     D.W = r.W;
     D.H = r.H;
@@ -509,26 +541,22 @@ static bool place_jpeg(const file_result &r, slab_fill &F, ingest_image &D, inge
     D.area = icl_resize_is_area(D.ow, D.oh, OUTW, OUTH);
     icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
     icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
-    if (F.used + (int64_t)r.packed.size() > SLAB_PAYLOAD) return false;
-    memcpy(pay + F.used, r.packed.data(), r.packed.size());
-    icl_je_scan *S = nullptr;
+    memcpy(S.payload + F.used, r.packed.data(), r.packed.size());
+    icl_je_scan *sc = nullptr;
     if (stream) {
-        if (F.nscan >= SLAB_IMAGES) return false;
-        S = &scans[F.nscan];
-        *S = r.scan;
-        S->tables_off += F.used;
-        S->intervals_off += F.used;
-        S->stream_off += F.used;
-        S->sub_first = F.subs;
-        S->wg_first = F.wgs;
-        F.subs += S->nsub;
-        F.wgs += icl_ceil_div(S->nsub, ICL_JE_WG);
-        if (F.subs > SLAB_SUBS || F.wgs > SLAB_WGS) return false;
-        ++F.nscan;
+        sc = &S.scans[F.nscan++];
+        *sc = r.scan;
+        sc->tables_off += F.used;
+        sc->intervals_off += F.used;
+        sc->stream_off += F.used;
+        sc->sub_first = F.subs;
+        sc->wg_first = F.wgs;
+        F.subs += sc->nsub;
+        F.wgs += icl_ceil_div(sc->nsub, ICL_JE_WG);
     }
     for (int c = 0; c < r.ncomp; ++c) {
         const comp_meta &cm = r.cm[c];
-        ingest_plane &P = pls[F.npl++];
+        ingest_plane &P = S.planes[F.npl++];
         P.first_block = F.blocks;
         P.nblocks = cm.wblocks * cm.hblocks;
         P.wblocks = cm.wblocks;
@@ -538,7 +566,7 @@ static bool place_jpeg(const file_result &r, slab_fill &F, ingest_image &D, inge
             P.ncoef = 0;
             P.offs_off = -1;
             P.coef_off = F.coef_used;
-            S->coef_off[c] = F.coef_used / 2;
+            sc->coef_off[c] = F.coef_used / 2;
             F.coef_used += align16((int64_t)P.nblocks * 128);
             ++F.ndense;
         } else {
@@ -564,29 +592,25 @@ static bool place_jpeg(const file_result &r, slab_fill &F, ingest_image &D, inge
     }
     // sizes were produced by stage A / A0 + pack_* on this host; re-check what the kernels rely on
     const bool ok = D.W >= 1 && D.H >= 1 && D.W <= D.ystride && D.H <= D.yrows && (D.ncomp == 1 || (D.cw >= 1 && D.chh >= 1 && D.cw <= D.cstride && D.chh <= D.crows)) &&
-                    F.scratch_used <= SLAB_SCRATCH && F.coef_used <= SLAB_COEF;
+                    F.scratch_used <= SLAB_SCRATCH && F.coef_used <= SLAB_COEF && F.wgs <= SLAB_WGS;
     F.used += align16((int64_t)r.packed.size());
     return ok;
 }
 
 // upload of a filled slab and its kernels up to the planes: (entropy decode,) IDCT
-static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, uint8_t *hs, const slab_fill &F, int64_t &upload)
+static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, const slab_view &H, const slab_fill &F, int64_t &upload)
 {
     hipStream_t st = ctx->stream;
-    ingest_image *imgs = (ingest_image *)hs;
-    ingest_plane *pls = (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image));
-    ingest_image *d_imgs = (ingest_image *)ws->d_hdr;
-    ingest_plane *d_pls = (ingest_plane *)(ws->d_hdr + SLAB_IMAGES * sizeof(ingest_image));
-    icl_je_scan *d_scans = (icl_je_scan *)(ws->d_hdr + HDR_SCANS);
-    if (F.nimg) ICL_HIP(ctx, hipMemcpyAsync(d_imgs, imgs, (size_t)F.nimg * sizeof(ingest_image), hipMemcpyHostToDevice, st));
-    if (F.npl) ICL_HIP(ctx, hipMemcpyAsync(d_pls, pls, (size_t)F.npl * sizeof(ingest_plane), hipMemcpyHostToDevice, st));
-    if (F.nscan) ICL_HIP(ctx, hipMemcpyAsync(d_scans, hs + HDR_SCANS, (size_t)F.nscan * sizeof(icl_je_scan), hipMemcpyHostToDevice, st));
-    if (F.used) ICL_HIP(ctx, hipMemcpyAsync(ws->d_payload, hs + HDR_BYTES, (size_t)F.used, hipMemcpyHostToDevice, st));
+    const slab_view D = ws->dev();
+    if (F.nimg) ICL_HIP(ctx, hipMemcpyAsync(D.imgs, H.imgs, (size_t)F.nimg * sizeof(ingest_image), hipMemcpyHostToDevice, st));
+    if (F.npl) ICL_HIP(ctx, hipMemcpyAsync(D.planes, H.planes, (size_t)F.npl * sizeof(ingest_plane), hipMemcpyHostToDevice, st));
+    if (F.nscan) ICL_HIP(ctx, hipMemcpyAsync(D.scans, H.scans, (size_t)F.nscan * sizeof(icl_je_scan), hipMemcpyHostToDevice, st));
+    if (F.used) ICL_HIP(ctx, hipMemcpyAsync(D.payload, H.payload, (size_t)F.used, hipMemcpyHostToDevice, st));
     upload += (int64_t)F.nimg * (int64_t)sizeof(ingest_image) + (int64_t)F.npl * (int64_t)sizeof(ingest_plane) + (int64_t)F.nscan * (int64_t)sizeof(icl_je_scan) + F.used;
     if (F.nscan) {
         ICL_HIP(ctx, hipMemsetAsync(ws->d_coef, 0, (size_t)F.coef_used, st)); // blocks end at their EOB: the rest of a block is zero
         icl_je_slab s;
-        s.d_scans = d_scans;
+        s.d_scans = D.scans;
         s.nscans = F.nscan;
         s.d_payload = ws->d_payload;
         s.payload_bytes = SLAB_PAYLOAD;
@@ -601,12 +625,12 @@ static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, uint8_t *hs, const s
         ICL_TRY(icl_je_decode_slab(ctx, st, s));
     }
     if (F.npacked) {
-        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, F.npl, (const uint8_t *)ws->d_payload,
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, D.planes, F.npl, (const uint8_t *)ws->d_payload,
                            (int64_t)SLAB_PAYLOAD, ws->d_scratch, (int64_t)SLAB_SCRATCH, F.blocks);
         ICL_HIP(ctx, hipGetLastError());
     }
     if (F.ndense) {
-        hipLaunchKernelGGL(jpeg_idct_dense_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, d_pls, F.npl,
+        hipLaunchKernelGGL(jpeg_idct_dense_kernel, dim3((unsigned)icl_ceil_div(F.blocks, IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, D.planes, F.npl,
                            (const int16_t *)ws->d_coef, (int64_t)SLAB_COEF, ws->d_scratch, (int64_t)SLAB_SCRATCH, F.blocks);
         ICL_HIP(ctx, hipGetLastError());
     }
@@ -624,219 +648,194 @@ struct ingest_totals {
     int64_t gpu_entropy = 0, host_entropy = 0, stream_bytes = 0;
 };
 
-} // namespace
+struct ingest_job { // the list a pass works on, and its caller
+    const char *const *paths;
+    int64_t n;
+    int32_t threads;
+    int32_t *status; // may be NULL
+    const char *what;
+};
 
-// One pass of the pipeline behind icl_load_images_224_dev and icl_embed_files[_dev].  mode 0: u8 rows into d_u8; 1: embeddings into
-// host `out`; 2: embeddings into device d_out.  Per-file failures go to `fails` (and status[]); rejected receives the rows whose GPU
-// entropy decode was not accepted (their output rows are to be redone by a pass with ICL_ENTROPY_HOST).
-static int ingest_pass(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out, int32_t *status,
-                       const char *what, int entropy, std::vector<file_fail> &fails, std::vector<int64_t> &rejected, ingest_totals &tot)
+struct pass_result {
+    std::vector<file_fail> fails;     // per-file failures (also in status[])
+    std::vector<int64_t> rejected;    // rows whose GPU entropy decode was not accepted: to be redone by a pass with ICL_ENTROPY_HOST
+    std::vector<int64_t> stream_rows; // the row of every stream image of the pass, in the order of h_accepted
+};
+
+struct slab_rows { // what slab_collect leaves the stages behind it
+    int64_t first = 0; // the list's row of the slab's first image
+    slab_fill F;
+    std::vector<int32_t> failed; // slab rows of the failed files
+};
+
+using file_feed = ingest_feed<file_result>;
+
+// the workspace, the entropy decoder's buffers where the pass decodes on the GPU, the slab's embedding rows where the sink is on the host
+static int ingest_buffers(icl_ctx *ctx, const ingest_sink &sink, int entropy, int64_t n, icl_ingest_ws *&ws)
 {
-    icl_ingest_ws *ws = nullptr;
     ICL_TRY(ingest_ws(ctx, ws));
     if (entropy == ICL_ENTROPY_GPU) ICL_TRY(entropy_ws(ctx, ws, n));
-    if (mode && ws->emb_head < head) {
+    if (sink.embeds() && ws->emb_head < sink.head) {
         if (ws->d_emb) (void)hipFree(ws->d_emb);
         ws->d_emb = nullptr;
         ws->emb_head = 0;
-        if (hipMalloc((void **)&ws->d_emb, (size_t)SLAB_IMAGES * head * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: embedding buffer");
-        ws->emb_head = head;
-    }
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(n, threads > 0 ? threads : (int)std::min(16u, hw)));
-
-    // ---- workers: claim files in order, at most one slab's worth of rows (and bytes) ahead of the slab builder ----
-    std::vector<std::unique_ptr<file_result>> res((size_t)n);
-    std::mutex m;
-    std::condition_variable cv;
-    int64_t next_claim = 0, next_pack = 0, pending_bytes = 0;
-    bool stop = false, worker_oom = false;
-    std::atomic<int64_t> decode_ns{0};
-    const int64_t window = 2 * SLAB_IMAGES, byte_budget = 2 * SLAB_PAYLOAD;
-    auto worker = [&]() {
-        std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state());
-        for (;;) {
-            int64_t i;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv.wait(lk, [&] { return stop || next_claim >= n || next_claim == next_pack || (next_claim < next_pack + window && pending_bytes < byte_budget); });
-                if (stop || next_claim >= n) return;
-                i = next_claim++;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
-            if (r) process_file(paths[i], *wst, entropy, *r);
-            decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-            std::lock_guard<std::mutex> lk(m);
-            if (!r) { // no memory for even the result: the call fails (the slab builder waits for this row)
-                worker_oom = true;
-                stop = true;
-            } else {
-                pending_bytes += (int64_t)r->packed.size();
-                res[(size_t)i] = std::move(r);
-            }
-            cv.notify_all();
-        }
-    };
-    std::vector<std::thread> pool;
-    struct joiner {
-        std::vector<std::thread> &p;
-        std::mutex &m;
-        std::condition_variable &cv;
-        bool &stop;
-        ~joiner()
-        {
-            {
-                std::lock_guard<std::mutex> lk(m);
-                stop = true;
-            }
-            cv.notify_all();
-            for (auto &t : p)
-                if (t.joinable()) t.join();
-        }
-    } jn{pool, m, cv, stop};
-    for (int t = 0; t < nthr; ++t) pool.emplace_back(worker);
-
-    // ---- slab builder (this thread): rows in file order, double-buffered pinned slabs, everything on ctx->stream ----
-    std::vector<int32_t> failed_rows;
-    std::vector<int64_t> stream_rows; // the row of every stream image of the call, in the order of h_accepted
-    for (int64_t k = 0; next_pack < n; ++k) {
-        uint8_t *hs = ws->h_slab[k & 1];
-        ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[k & 1])); // the upload that last read this slab has finished
-        ingest_image *imgs = (ingest_image *)hs;
-        ingest_plane *pls = (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image));
-        icl_je_scan *scans = (icl_je_scan *)(hs + HDR_SCANS);
-        uint8_t *pay = hs + HDR_BYTES;
-        const int64_t first = next_pack;
-        slab_fill F;
-        failed_rows.clear();
-        while (next_pack < n && F.nimg < SLAB_IMAGES) {
-            std::unique_ptr<file_result> r;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv.wait(lk, [&] { return res[(size_t)next_pack] != nullptr || worker_oom; });
-                if (worker_oom) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", what);
-                file_result &q = *res[(size_t)next_pack];
-                const int64_t need = q.kind == KIND_FAILED ? 0 : align16((int64_t)q.packed.size());
-                const int64_t nsubs = q.kind == KIND_JSTREAM ? (int64_t)q.scan.nsub : 0;
-                if (F.nimg > 0 && (F.used + need > SLAB_PAYLOAD || F.scratch_used + align16(q.plane_bytes) > SLAB_SCRATCH || F.subs + nsubs > SLAB_SUBS)) break;
-                r = std::move(res[(size_t)next_pack]);
-                pending_bytes -= (int64_t)r->packed.size();
-                ++next_pack;
-                cv.notify_all();
-            }
-            const int64_t row = first + F.nimg;
-            ingest_image &D = imgs[F.nimg];
-            memset(&D, 0, offsetof(ingest_image, xofs));
-            D.kind = r->kind;
-            if (status) status[row] = r->rc;
-            if (r->kind == KIND_FAILED) {
-                failed_rows.push_back(F.nimg);
-                fails.push_back(file_fail{row, r->rc ? r->rc : ICL_ERR_IO, r->err});
-            } else if (r->kind == KIND_HOST) {
-                D.host_off = F.used;
-                memcpy(pay + F.used, r->packed.data(), (size_t)ICL_IMG_BYTES);
-                F.used += align16(ICL_IMG_BYTES);
-                ++tot.host_files;
-            } else {
-                if (!place_jpeg(*r, F, D, pls, scans, pay)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, paths[row]);
-                ++tot.gpu_jpegs;
-                if (r->kind == KIND_JSTREAM) {
-                    stream_rows.push_back(row);
-                    tot.stream_bytes += (int64_t)r->scan.nsub * (ICL_JE_SUB_BITS / 8);
-                }
-            }
-            if (r->host_entropy) ++tot.host_entropy; // (whatever became of it: stage A ran, or tried to)
-            ++F.nimg;
-        }
-        // ---- upload + rebuild (+ forward pass) of this slab ----
-        hipStream_t st = ctx->stream;
-        const int nimg = F.nimg;
-        ingest_image *d_imgs = (ingest_image *)ws->d_hdr;
-        ICL_TRY(run_slab_decode(ctx, ws, hs, F, tot.upload));
-        ICL_HIP(ctx, hipEventRecord(ws->ev_up[k & 1], st));
-        if (F.nscan) // the flags are read after the call's last synchronisation
-            ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted + (stream_rows.size() - (size_t)F.nscan), ws->d_accepted, (size_t)F.nscan * 4, hipMemcpyDeviceToHost, st));
-        uint8_t *dst = mode == 0 ? d_u8 + first * ICL_IMG_BYTES : ws->d_img;
-        hipLaunchKernelGGL(jpeg_gather_resize_kernel, dim3((unsigned)icl_ceil_div(OUTW * OUTH, 256), (unsigned)nimg), dim3(256), 0, st, d_imgs,
-                           (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, dst);
-        ICL_HIP(ctx, hipGetLastError());
-        if (mode) {
-            float *d_dst = mode == 2 ? out + first * head : ws->d_emb;
-            ICL_TRY(icl_embed_dev_locked(ctx, ws->d_img, nimg, head, prec, d_dst)); // (ends with the stream synchronised)
-            if (!failed_rows.empty()) {
-                if (mode == 1) {
-                    ICL_HIP(ctx, hipMemcpyAsync(out + first * head, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
-                    ICL_HIP(ctx, hipStreamSynchronize(st));
-                    for (int32_t j : failed_rows) std::fill(out + (first + j) * head, out + (first + j + 1) * head, std::nanf(""));
-                } else {
-                    ICL_HIP(ctx, hipMemcpyAsync(ws->d_rows, failed_rows.data(), failed_rows.size() * 4, hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(fill_nan_rows_kernel, dim3((unsigned)icl_ceil_div(head, 256), (unsigned)failed_rows.size()), dim3(256), 0, st,
-                                       d_dst, (const int32_t *)ws->d_rows, (int)failed_rows.size(), head);
-                    ICL_HIP(ctx, hipGetLastError());
-                    ICL_HIP(ctx, hipStreamSynchronize(st)); // failed_rows is reused by the next slab
-                }
-            } else if (mode == 1) {
-                ICL_HIP(ctx, hipMemcpyAsync(out + first * head, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
-                ICL_HIP(ctx, hipStreamSynchronize(st));
-            }
-        }
-    }
-    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    {
-        std::lock_guard<std::mutex> lk(m);
-        stop = true;
-    }
-    cv.notify_all();
-    for (auto &t : pool) t.join();
-    tot.decode_ns += decode_ns.load();
-    for (size_t q = 0; q < stream_rows.size(); ++q) {
-        if (ws->h_accepted[q]) ++tot.gpu_entropy;
-        else rejected.push_back(stream_rows[q]);
+        if (hipMalloc((void **)&ws->d_emb, (size_t)SLAB_IMAGES * sink.head * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: embedding buffer");
+        ws->emb_head = sink.head;
     }
     return ICL_OK;
 }
 
-// The pipeline: one pass in the context's entropy mode; the images the GPU entropy check rejected are then redone by a pass in
-// ICL_ENTROPY_HOST mode over those files alone (rows do not depend on the batch they are rebuilt or embedded in), which also produces
-// their status codes and messages.  (Declared in icl_common.h: icl_cluster_requests, requests.hip, calls it with mode 2.)
-int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, int mode, uint8_t *d_u8, int head, int prec, float *out,
-                 int32_t *status, const char *what, icl_item_failure *lowest_out)
+// Rows from the feed, in file order, into the pinned slab S until it is full or the list ends: status, failures, totals, stream rows.
+static int slab_collect(icl_ctx *ctx, const ingest_job &job, file_feed &feed, const slab_view &S, slab_rows &R, pass_result &res, ingest_totals &tot)
 {
-    std::vector<file_fail> fails;
-    std::vector<int64_t> rejected;
-    ingest_totals tot;
-    ICL_TRY(ingest_pass(ctx, paths, n, threads, mode, d_u8, head, prec, out, status, what, ctx->entropy_mode, fails, rejected, tot));
-    const int64_t nrej = (int64_t)rejected.size();
-    if (nrej) {
-        std::vector<const char *> rp((size_t)nrej);
-        for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = paths[rejected[(size_t)q]];
-        std::vector<int32_t> rstatus((size_t)nrej, 0);
-        std::vector<file_fail> rfails;
-        std::vector<int64_t> none;
-        const size_t row_bytes = mode == 0 ? (size_t)ICL_IMG_BYTES : (size_t)head * 4;
-        std::vector<float> h_tmp;
-        struct dev_tmp {
-            void *p = nullptr;
-            ~dev_tmp()
-            {
-                if (p) (void)hipFree(p);
+    R.first = feed.taken();
+    R.F = slab_fill();
+    R.failed.clear();
+    slab_fill &F = R.F;
+    while (feed.taken() < job.n && F.nimg < SLAB_IMAGES) {
+        const file_result *next = feed.peek();
+        if (!next) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", job.what);
+        if (F.nimg > 0 && !F.fits(*next)) break;
+        const std::unique_ptr<file_result> r = feed.take();
+        const int64_t row = R.first + F.nimg;
+        ingest_image &D = S.imgs[F.nimg];
+        memset(&D, 0, offsetof(ingest_image, xofs));
+        D.kind = r->kind;
+        if (job.status) job.status[row] = r->rc;
+        if (r->kind == KIND_FAILED) {
+            R.failed.push_back(F.nimg);
+            res.fails.push_back(file_fail{row, r->rc ? r->rc : ICL_ERR_IO, r->err});
+        } else if (r->kind == KIND_HOST) {
+            D.host_off = F.used;
+            memcpy(S.payload + F.used, r->packed.data(), (size_t)ICL_IMG_BYTES);
+            F.used += align16(ICL_IMG_BYTES);
+            ++tot.host_files;
+        } else {
+            if (!place_jpeg(*r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", job.what, job.paths[row]);
+            ++tot.gpu_jpegs;
+            if (r->kind == KIND_JSTREAM) {
+                res.stream_rows.push_back(row);
+                tot.stream_bytes += (int64_t)r->scan.nsub * (ICL_JE_SUB_BITS / 8);
             }
-        } d_tmp;
-        if (mode == 1) h_tmp.resize((size_t)nrej * head);
-        else if (hipMalloc(&d_tmp.p, (size_t)nrej * row_bytes) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: device buffer of the repair pass", what);
-        ICL_TRY(ingest_pass(ctx, rp.data(), nrej, threads, mode, (uint8_t *)d_tmp.p, head, prec, mode == 1 ? h_tmp.data() : (float *)d_tmp.p, rstatus.data(), what,
-                            ICL_ENTROPY_HOST, rfails, none, tot));
-        for (int64_t q = 0; q < nrej; ++q) {
-            const int64_t row = rejected[(size_t)q];
-            if (status) status[row] = rstatus[(size_t)q];
-            if (mode == 1) memcpy(out + row * head, h_tmp.data() + q * head, row_bytes);
-            else
-                ICL_HIP(ctx, hipMemcpyAsync(mode == 0 ? (void *)(d_u8 + row * ICL_IMG_BYTES) : (void *)(out + row * head), (const uint8_t *)d_tmp.p + (size_t)q * row_bytes,
-                                            row_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        if (r->host_entropy) ++tot.host_entropy; // (whatever became of it: stage A ran, or tried to)
+        ++F.nimg;
+    }
+    return ICL_OK;
+}
+
+// The decoded slab into the sink: gather / resize to u8 rows, and for an embedding sink the forward pass, NaN in the rows of the failed
+// files, and the download of a host sink's rows.
+static int slab_deliver(icl_ctx *ctx, icl_ingest_ws *ws, const ingest_sink &sink, const slab_rows &R)
+{
+    hipStream_t st = ctx->stream;
+    const int nimg = R.F.nimg, head = sink.head;
+    uint8_t *d_img = sink.embeds() ? ws->d_img : (uint8_t *)sink.row(R.first);
+    hipLaunchKernelGGL(jpeg_gather_resize_kernel, dim3((unsigned)icl_ceil_div(OUTW * OUTH, 256), (unsigned)nimg), dim3(256), 0, st, ws->dev().imgs,
+                       (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, d_img);
+    ICL_HIP(ctx, hipGetLastError());
+    if (!sink.embeds()) return ICL_OK;
+    float *d_dst = sink.kind == ingest_sink::EMB_DEV ? (float *)sink.row(R.first) : ws->d_emb;
+    ICL_TRY(icl_embed_dev_locked(ctx, ws->d_img, nimg, head, sink.prec, d_dst)); // (ends with the stream synchronised)
+    if (sink.kind == ingest_sink::EMB_HOST) {
+        float *out = (float *)sink.row(R.first);
+        ICL_HIP(ctx, hipMemcpyAsync(out, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
+        ICL_HIP(ctx, hipStreamSynchronize(st));
+        for (int32_t j : R.failed) std::fill(out + (int64_t)j * head, out + (int64_t)(j + 1) * head, std::nanf(""));
+    } else if (!R.failed.empty()) {
+        ICL_HIP(ctx, hipMemcpyAsync(ws->d_rows, R.failed.data(), R.failed.size() * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(fill_nan_rows_kernel, dim3((unsigned)icl_ceil_div(head, 256), (unsigned)R.failed.size()), dim3(256), 0, st, d_dst,
+                           (const int32_t *)ws->d_rows, (int)R.failed.size(), head);
+        ICL_HIP(ctx, hipGetLastError());
+        ICL_HIP(ctx, hipStreamSynchronize(st)); // R.failed is reused by the next slab
+    }
+    return ICL_OK;
+}
+
+// the accepted flags of the pass's stream images (downloaded slab by slab; read after the pass's last synchronisation)
+static void tally_accepted(const icl_ingest_ws *ws, pass_result &res, ingest_totals &tot)
+{
+    for (size_t q = 0; q < res.stream_rows.size(); ++q) {
+        if (ws->h_accepted[q]) ++tot.gpu_entropy;
+        else res.rejected.push_back(res.stream_rows[q]);
+    }
+}
+
+// One pass of the pipeline over job's files into sink: worker threads decode the files (at most two slabs' worth of rows and payload
+// bytes ahead), this thread builds the slabs in file order, double-buffered in pinned memory, with everything on ctx->stream.
+static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &sink, int entropy, pass_result &res, ingest_totals &tot)
+{
+    icl_ingest_ws *ws = nullptr;
+    ICL_TRY(ingest_buffers(ctx, sink, entropy, job.n, ws));
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(job.n, job.threads > 0 ? job.threads : (int)std::min(16u, hw)));
+    std::atomic<int64_t> decode_ns{0};
+    auto decode = [&](int64_t i) -> std::unique_ptr<file_result> {
+        thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state()); // a worker's buffers, from file to file
+        const auto t0 = std::chrono::steady_clock::now();
+        std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
+        if (r) process_file(job.paths[i], *wst, entropy, *r);
+        decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        return r;
+    };
+    {
+        file_feed feed(job.n, nthr, 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, decode, [](const file_result &r) { return (int64_t)r.packed.size(); });
+        slab_rows R;
+        for (int64_t k = 0; feed.taken() < job.n; ++k) {
+            const int q = (int)(k & 1);
+            ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[q])); // the upload that last read this slab has finished
+            const slab_view S = ws->host(q);
+            ICL_TRY(slab_collect(ctx, job, feed, S, R, res, tot));
+            ICL_TRY(run_slab_decode(ctx, ws, S, R.F, tot.upload));
+            ICL_HIP(ctx, hipEventRecord(ws->ev_up[q], ctx->stream));
+            if (R.F.nscan) // the flags are read after the pass's last synchronisation
+                ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted + (res.stream_rows.size() - (size_t)R.F.nscan), ws->d_accepted, (size_t)R.F.nscan * 4, hipMemcpyDeviceToHost,
+                                            ctx->stream));
+            ICL_TRY(slab_deliver(ctx, ws, sink, R));
         }
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (file_fail &f : rfails) fails.push_back(file_fail{rejected[(size_t)f.index], f.rc, f.err});
+    } // (the feed has joined its workers: decode_ns is complete)
+    tot.decode_ns += decode_ns.load();
+    tally_accepted(ws, res, tot);
+    return ICL_OK;
+}
+
+} // namespace
+
+// The pipeline (declared in icl_common.h): one pass in the context's entropy mode; the images the GPU entropy check rejected are then
+// redone by a pass in ICL_ENTROPY_HOST mode over those files alone into a sink of the same kind on a temporary (rows do not depend on
+// the batch they are rebuilt or embedded in), which also produces their status codes and messages.
+int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
+                 icl_item_failure *lowest_out)
+{
+    pass_result res;
+    ingest_totals tot;
+    ICL_TRY(ingest_pass(ctx, ingest_job{paths, n, threads, status, what}, sink, ctx->entropy_mode, res, tot));
+    const int64_t nrej = (int64_t)res.rejected.size();
+    if (nrej) {
+        std::vector<const char *> rp((size_t)nrej);
+        for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = paths[res.rejected[(size_t)q]];
+        std::vector<int32_t> rstatus((size_t)nrej, 0);
+        pass_result rres;
+        std::vector<float> h_tmp;
+        dev_guard d_tmp;
+        ingest_sink tmp = sink;
+        if (sink.kind == ingest_sink::EMB_HOST) {
+            h_tmp.resize((size_t)nrej * sink.head);
+            tmp.dst = h_tmp.data();
+        } else {
+            if (hipMalloc(&d_tmp.p, (size_t)nrej * sink.row_bytes()) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: device buffer of the repair pass", what);
+            tmp.dst = d_tmp.p;
+        }
+        ICL_TRY(ingest_pass(ctx, ingest_job{rp.data(), nrej, threads, rstatus.data(), what}, tmp, ICL_ENTROPY_HOST, rres, tot));
+        for (int64_t q = 0; q < nrej; ++q) {
+            const int64_t row = res.rejected[(size_t)q];
+            if (status) status[row] = rstatus[(size_t)q];
+            if (sink.kind == ingest_sink::EMB_HOST) memcpy(sink.row(row), tmp.row(q), sink.row_bytes());
+            else ICL_HIP(ctx, hipMemcpyAsync(sink.row(row), tmp.row(q), sink.row_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (file_fail &f : rres.fails) res.fails.push_back(file_fail{res.rejected[(size_t)f.index], f.rc, f.err});
         tot.gpu_jpegs -= nrej;     // (the first pass counted them; the repair pass counts what became of them)
         tot.host_entropy -= nrej;  // they are reported as redone, not as routed to the host
     }
@@ -850,7 +849,7 @@ int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t thre
     ctx->entropy_stats[2] = nrej;
     ctx->entropy_stats[3] = tot.stream_bytes;
     const file_fail *lowest = nullptr;
-    for (const file_fail &f : fails)
+    for (const file_fail &f : res.fails)
         if (!lowest || f.index < lowest->index) lowest = &f;
     if (lowest && lowest_out) *lowest_out = icl_item_failure{lowest->index, lowest->rc, lowest->err};
     if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
@@ -865,11 +864,9 @@ extern "C" int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, i
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return no_throw(ctx, "icl_load_images_224_dev", [&]() -> int {
-        ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
-        ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
-        ctx->ingest_decode_s = 0;
+        icl_ingest_stats_reset(ctx);
         if (n == 0) return ICL_OK;
-        return ingest_files(ctx, paths, n, threads, 0, d_out, 0, 0, nullptr, status, "icl_load_images_224_dev");
+        return ingest_files(ctx, paths, n, threads, ingest_sink{ingest_sink::U8_DEV, d_out, 0, 0}, status, "icl_load_images_224_dev");
     });
 }
 
@@ -886,11 +883,9 @@ static int embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int he
     icl_device_guard g(ctx->device);
     if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
     return no_throw(ctx, what, [&]() -> int {
-        ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
-        ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
-        ctx->ingest_decode_s = 0;
+        icl_ingest_stats_reset(ctx);
         if (n == 0) return ICL_OK;
-        return ingest_files(ctx, paths, n, threads, dev ? 2 : 1, nullptr, head, prec, out, status, what);
+        return ingest_files(ctx, paths, n, threads, ingest_sink{dev ? ingest_sink::EMB_DEV : ingest_sink::EMB_HOST, out, head, prec}, status, what);
     });
 }
 
@@ -980,17 +975,14 @@ extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int6
             state[i] = 0;
             if (coefs) {
                 if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: buffer too small");
-                uint8_t *hs = ws->h_slab[0];
                 ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
-                ingest_image *imgs = (ingest_image *)hs;
-                icl_je_scan *scans = (icl_je_scan *)(hs + HDR_SCANS);
+                const slab_view S = ws->host(0);
                 slab_fill F;
-                memset(&imgs[0], 0, offsetof(ingest_image, xofs));
-                if (!place_jpeg(r, F, imgs[0], (ingest_plane *)(hs + SLAB_IMAGES * sizeof(ingest_image)), scans, hs + HDR_BYTES))
-                    return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: inconsistent JPEG geometry for %s", paths[i]);
+                memset(&S.imgs[0], 0, offsetof(ingest_image, xofs));
+                if (!place_jpeg(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: inconsistent JPEG geometry for %s", paths[i]);
                 F.nimg = 1;
                 int64_t upload = 0;
-                ICL_TRY(run_slab_decode(ctx, ws, hs, F, upload));
+                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload));
                 ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
                 ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, 4, hipMemcpyDeviceToHost, ctx->stream));
                 ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -998,7 +990,7 @@ extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int6
                 int64_t o = at;
                 for (int c = 0; c < r.ncomp && state[i] == 1; ++c) {
                     const int64_t ne = (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
-                    ICL_HIP(ctx, hipMemcpy(coefs + o, ws->d_coef + scans[0].coef_off[c], (size_t)ne * 2, hipMemcpyDeviceToHost));
+                    ICL_HIP(ctx, hipMemcpy(coefs + o, ws->d_coef + S.scans[0].coef_off[c], (size_t)ne * 2, hipMemcpyDeviceToHost));
                     o += ne;
                 }
             }

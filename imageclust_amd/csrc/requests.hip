@@ -5,7 +5,7 @@
 // rows (PerformClusteringWithConstraints).  Both batched halves exist -- ingest_files (jpeg_gpu.hip) turns paths into dense rows on the
 // device, cluster_many_locked (ward_many.hip) clusters many problems of exactly this shape -- and this file joins them with one kernel:
 //
-//   paths --ingest_files, mode 2--> dense [n_total][head] --requests_assemble_kernel--> E (request r: n[r] rows of d[r] = head + L[r]
+//   paths --ingest_files, EMB_DEV sink--> dense [n_total][head] --requests_assemble_kernel--> E (request r: n[r] rows of d[r] = head + L[r]
 //   floats at e_off[r], rows contiguous, requests back to back: icl_requests_layout) --cluster_many_locked--> ids, ranks, merge logs
 //
 // The combined rows never leave the device in between (E_out, when asked for, is a copy for the caller).  A request one of whose files
@@ -187,7 +187,7 @@ static int cluster_requests_locked(icl_ctx *ctx, int32_t nreq, const char *const
     icl_item_failure bad_file; // the call's lowest failed file
     ICL_HIP(ctx, hipEventRecord(ev[0], st));
     if (rows) {
-        const int rc = ingest_files(ctx, paths, rows, threads, 2, nullptr, head, prec, d_dense, fstat.data(), what, &bad_file);
+        const int rc = ingest_files(ctx, paths, rows, threads, ingest_sink{ingest_sink::EMB_DEV, d_dense, head, prec}, fstat.data(), what, &bad_file);
         if (rc != ICL_OK && bad_file.index < 0) return rc; // not a file's failure: the pipeline stopped
     }
     ICL_HIP(ctx, hipEventRecord(ev[1], st));
@@ -290,9 +290,7 @@ extern "C" int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *cons
         std::lock_guard<std::mutex> lk(ctx->mu);
         icl_device_guard g(ctx->device);
         if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
-        ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
-        ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
-        ctx->ingest_decode_s = 0;
+        icl_ingest_stats_reset(ctx);
         ctx->many_stats[0] = ctx->many_stats[1] = ctx->many_stats[2] = ctx->many_stats[3] = 0;
         ctx->requests_ms[0] = ctx->requests_ms[1] = ctx->requests_ms[2] = 0;
         if (nreq == 0) return ICL_OK;

@@ -5088,14 +5088,6 @@ static int ward_nspare(const icl_ctx *ctx, bool lb_rows, bool sharded) { return 
 
 // ---- the clustering call's host driver: cluster_locked (below) = ward_check_args -> ward_make_plan -> ward_init_ws -> ward_fill -> ward_run_single /
 // ward_run_batched -> ward_collect; every decision of a call is made once, in its ward_plan.
-// hip_guard releases a HIP resource on every way out of a scope (ICL_HIP / ICL_TRY / icl_fail return early)
-template <class T, hipError_t (*Release)(T)> struct hip_guard {
-    T p = nullptr;
-    ~hip_guard() { if (p) (void)Release(p); }
-};
-using ev_guard = hip_guard<hipEvent_t, hipEventDestroy>;
-using dev_guard = hip_guard<void *, hipFree>;
-using pin_guard = hip_guard<void *, hipHostFree>;
 // what one clustering call holds beside the workspace: all of it until cluster_locked returns (a hipFree / hipHostFree in mid-call would wait for the device)
 struct ward_call {
     struct shard_guard { // a replica of a sharded group call that leaves early releases the replicas waiting for it (icl_ward_shard::wait)
