@@ -88,9 +88,15 @@ ICL_PX void icl_idct_islow_row(const int *w, int px[8])
     for (int k = 0; k < 8; ++k) px[k] = icl_clamp8(icl_idct_descale(o[k], ICL_IDCT_CB + ICL_IDCT_P1 + 3) + 128);
 }
 
-// ---- jdsample.c "fancy" (triangle) chroma upsampling: 2x horizontally (h2v1) or 2x both ways (h2v2) ----
-// the nearer and the further input row of output row y for h2v2: y / 2, and the row above it (even y) or below it (odd y); rows
-// above the first and below the last repeat the edge row
+// ---- jdsample.c chroma upsampling with libjpeg's default settings: "fancy" (triangle) filters 2x horizontally (h2v1), 2x both ways
+// (h2v2) and 2x vertically (h1v2); plain replication (int_upsample) for every other factor, of which 4x1 and 1x4 are decoded ----
+// the luma sampling factors (chroma 1x1) these rules cover: 4:4:4, 4:2:2, 4:2:0, 4:4:0 (1x2) and 4:1:1 (4x1, or 1x4 after a rotation)
+ICL_PX bool icl_luma_sampling_ok(int hs, int vs)
+{
+    return (hs == 1 && (vs == 1 || vs == 2 || vs == 4)) || (hs == 2 && (vs == 1 || vs == 2)) || (hs == 4 && vs == 1);
+}
+// the nearer and the further input row of output row y for h2v2 and h1v2: y / 2, and the row above it (even y) or below it (odd y);
+// rows above the first and below the last repeat the edge row
 ICL_PX void icl_fancy_rows(int y, int dh, int &nearer, int &further)
 {
     auto cl = [&](int r) { return r < 0 ? 0 : (r > dh - 1 ? dh - 1 : r); };
@@ -114,20 +120,28 @@ ICL_PX int icl_fancy_h2(const Col &col, int dw, int X)
     return i == 0 ? blend(col(0), col(0), 0) : blend(col(i), col(i - 1), 0);
 }
 
+// h1v2: a 3:1 blend of the two rows with no horizontal filter; the bias is 1 in the upper (even y) and 2 in the lower row of a pair
+ICL_PX int icl_fancy_v2(int nearer, int further, int y) { return (nearer * 3 + further + 1 + (y & 1)) >> 2; }
+
 // Sample (X, y) of the full-resolution plane, from a chroma plane of dw x dh samples whose row r starts at pl + r * stride;
-// hs x vs is the luma's sampling factor: 1x1 (no upsampling), 2x1 (h2v1) or 2x2 (h2v2).
+// hs x vs is the luma's sampling factor (icl_luma_sampling_ok): 1x1 (no upsampling), 2x1 (h2v1), 2x2 (h2v2), 1x2 (h1v2), or 4x1 /
+// 1x4 (int_upsample: chroma sample (X / 4, y) or (X, y / 4), neither direction smoothed).
 ICL_PX int icl_fancy_upsample(const uint8_t *pl, int64_t stride, int dw, int dh, int hs, int vs, int X, int y)
 {
     auto row = [&](int r) { return pl + (int64_t)(r < 0 ? 0 : (r > dh - 1 ? dh - 1 : r)) * stride; };
-    if (hs == 1) return row(y)[X < dw - 1 ? X : dw - 1];
-    if (vs == 1) {
+    auto colx = [&](int x) { return x < dw - 1 ? x : dw - 1; };
+    if (hs == 2 && vs == 1) {
         const uint8_t *p = row(y);
         return icl_fancy_h2<1>([&](int k) { return (int)p[k]; }, dw, X);
     }
-    int r0, r1;
-    icl_fancy_rows(y, dh, r0, r1);
-    const uint8_t *p0 = row(r0), *p1 = row(r1);
-    return icl_fancy_h2<2>([&](int k) { return icl_fancy_colsum(p0[k], p1[k]); }, dw, X);
+    if (vs == 2) {
+        int r0, r1;
+        icl_fancy_rows(y, dh, r0, r1);
+        const uint8_t *p0 = row(r0), *p1 = row(r1);
+        if (hs == 1) return icl_fancy_v2(p0[colx(X)], p1[colx(X)], y);
+        return icl_fancy_h2<2>([&](int k) { return icl_fancy_colsum(p0[k], p1[k]); }, dw, X);
+    }
+    return row(vs == 4 ? y >> 2 : y)[colx(hs == 4 ? X >> 2 : X)]; // 1x1, 4x1, 1x4
 }
 
 // ---- jdcolor.c ycc_rgb_convert: fixed-point YCbCr -> RGB (the products of its four tables, evaluated in place) ----

@@ -7,17 +7,19 @@
 // decoded pixels are bit-identical to libjpeg-turbo's (checked against Pillow's bundled libjpeg-turbo in
 // tests/test_jpeg_decode.py).  Supported: 8-bit baseline / extended sequential (SOF0, SOF1) and PROGRESSIVE (SOF2:
 // spectral selection + successive approximation, ITU T.81 annex G) Huffman streams, interleaved or one scan per
-// component, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 sampling, restart intervals, JFIF / Adobe-transform markers.
+// component, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0 / 4:1:1 sampling (luma 1x1, 2x1, 2x2, 1x2, 4x1 or 1x4 over 1x1 chroma),
+// restart intervals, JFIF / Adobe-transform markers.
 // Every scan decodes into per-component coefficient arrays; dequantisation + IDCT run once after the last scan.
 // Two stages (jpeg_stage.h): stage A parses the file and runs the entropy decoder (every check of a hostile file is made
 // here); stage B dequantises, runs the IDCT, upsamples the chroma and converts the colour.  jpeg_gpu.hip runs stage B on the GPU
 // with the same per-sample rules (ingest_pixels.h).
-// Arithmetic coding, lossless, 12-bit and CMYK return ICL_ERR_UNSUPPORTED.
+// Arithmetic coding, lossless, 12-bit, CMYK and every other sampling (4:1:0, subsampled luma, ...) return ICL_ERR_UNSUPPORTED.
 #include "icl_common.h"
 #include "ingest_pixels.h"
 #include "jpeg_entropy.h"
 #include "jpeg_stage.h"
 
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -529,9 +531,13 @@ static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, cons
             }
             if (ncomp == 1) comp[0].h = comp[0].v = 1;
             if (ncomp == 3) {
-                const bool ok = comp[1].h == 1 && comp[1].v == 1 && comp[2].h == 1 && comp[2].v == 1 && (comp[0].h == 1 || comp[0].h == 2) &&
-                                (comp[0].v == 1 || comp[0].v == 2) && !(comp[0].h == 1 && comp[0].v == 2);
-                if (!ok) return fail(ICL_ERR_UNSUPPORTED, "Only 4:4:4, 4:2:2 and 4:2:0 chroma sampling is decoded");
+                const bool ok = comp[1].h == 1 && comp[1].v == 1 && comp[2].h == 1 && comp[2].v == 1 && icl_luma_sampling_ok(comp[0].h, comp[0].v);
+                if (!ok) {
+                    char what[160];
+                    snprintf(what, sizeof what, "Sampling %dx%d,%dx%d,%dx%d is not decoded (only luma 1x1, 2x1, 2x2, 1x2, 4x1 or 1x4 over 1x1 chroma)", comp[0].h,
+                             comp[0].v, comp[1].h, comp[1].v, comp[2].h, comp[2].v);
+                    return fail(ICL_ERR_UNSUPPORTED, what);
+                }
             }
             for (int c = 0; c < ncomp; ++c) {
                 hmax = std::max(hmax, comp[c].h);
@@ -800,8 +806,8 @@ static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb)
             }
         return ICL_OK;
     }
-    // chroma upsampling (jdsample.c "fancy" rules, one output row at a time) and colour conversion (jdcolor.c), or pass-through
-    // for Adobe transform 0
+    // chroma upsampling (jdsample.c rules of ingest_pixels.h, one output row at a time) and colour conversion (jdcolor.c), or
+    // pass-through for Adobe transform 0
     const int hs = comp[0].h, vs = comp[0].v, dw = comp[1].dw, dh = comp[1].dh;
     const size_t ystride = (size_t)comp[0].wblocks * 8, cstride = (size_t)comp[1].wblocks * 8;
     std::vector<uint8_t> up[2] = {std::vector<uint8_t>((size_t)W + 1), std::vector<uint8_t>((size_t)W + 1)}; // 2 * dw <= W + 1
@@ -810,15 +816,17 @@ static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb)
         for (int c = 0; c < 2; ++c) {
             const uint8_t *pl = plane[c + 1].data();
             uint8_t *o = up[c].data();
-            if (hs == 1) {
+            if (hs == 1 && vs == 1) {
                 memcpy(o, pl + (size_t)y * cstride, (size_t)W);
-            } else if (vs == 1) {
+            } else if (hs == 2 && vs == 1) {
                 const uint8_t *p = pl + (size_t)y * cstride;
                 auto col = [&](int k) { return (int)p[k]; };
                 for (int i = 0; i < dw; ++i) {
                     o[2 * i] = (uint8_t)icl_fancy_h2<1>(col, dw, 2 * i);
                     o[2 * i + 1] = (uint8_t)icl_fancy_h2<1>(col, dw, 2 * i + 1);
                 }
+            } else if (hs != 2) { // 1x2, 4x1, 1x4: no horizontal filter, the per-sample rule as the GPU applies it
+                for (int x = 0; x < W; ++x) o[x] = (uint8_t)icl_fancy_upsample(pl, (int64_t)cstride, dw, dh, hs, vs, x, y);
             } else {
                 int r0, r1;
                 icl_fancy_rows(y, dh, r0, r1);

@@ -50,7 +50,7 @@ struct sub_view {
 __device__ __forceinline__ bool scan_usable(const icl_je_scan &S, int64_t payload_bytes, int64_t nsub_cap, int64_t nwg_cap)
 {
     if (S.sub_bits != ICL_JE_SUB_BITS || (S.ncomp != 1 && S.ncomp != 3) || S.nsub < 1 || S.nintervals < 1) return false;
-    if (S.ncomp == 3 && (S.hs < 1 || S.hs > 2 || S.vs < 1 || S.vs > 2)) return false;
+    if (S.ncomp == 3 && !icl_luma_sampling_ok(S.hs, S.vs)) return false;
     if (S.bpm != (S.ncomp == 1 ? 1 : S.hs * S.vs + 2)) return false;
     const int64_t nwg = ((int64_t)S.nsub + ICL_JE_WG - 1) / ICL_JE_WG;
     if (S.tables_off < 0 || (S.tables_off & 3) || S.tables_off + (int64_t)(2 * S.ncomp) * (int64_t)sizeof(icl_je_table) > payload_bytes) return false;
@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(ICL_JE_WG) jpeg_huff_check_kernel(const icl_je
         }
         return x;
     };
-    const int ncomp = S.ncomp, nluma = ncomp == 1 ? 1 : S.hs * S.vs, bpm = S.bpm; // (bpm is 1, 3, 4 or 6: scan_usable)
+    const int ncomp = S.ncomp, nluma = ncomp == 1 ? 1 : S.hs * S.vs, bpm = S.bpm; // (bpm is 1, 3, 4 or 6: scan_usable; 4 is 2x1 or 1x2, 6 is 2x2, 4x1 or 1x4)
     __shared__ uint32_t s_total;
     // pass 1: this chunk's blocks; exclusive scan over the 256 chunks
     {

@@ -35,7 +35,7 @@ struct icl_jpeg_coefs {
 };
 
 // Stage A.  Every check of a hostile file is made here; on success J holds a decodable image (1 or 3 components,
-// 4:4:4 / 4:2:2 / 4:2:0, at most ICL_JPEG_MAX_PIXELS).  J may be reused across calls (its coefficient arrays keep their capacity).
+// luma 1x1 / 2x1 / 2x2 / 1x2 / 4x1 / 1x4 over 1x1 chroma, at most ICL_JPEG_MAX_PIXELS).  J may be reused across calls (its coefficient arrays keep their capacity).
 int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J);
 // Stage B on the host: interleaved RGB, W*H*3 (before the EXIF orientation).
 int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, std::vector<uint8_t> &rgb);

@@ -87,7 +87,7 @@ int icl_embed_u8_dev(icl_ctx *ctx, const uint8_t *d_hwc_rgb, int64_t n, int head
  * (embeddings.go:69), then as icl_embed_u8 with n = 1, fp32. */
 int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *out);
 /* icl_embed_file is what GetImageEmbedding(appCtx, path) binds to, and workflow.go:156-175 calls that from one goroutine per
- * image.  Concurrent callers are coalesced: each decodes / resizes its own file, then one forward pass serves everything
+ * image.  The file is read as icl_load_image_224 reads it (JPEG samplings: see icl_decode_image_file).  Concurrent callers are coalesced: each decodes / resizes its own file, then one forward pass serves everything
  * that queued up within window_us (or max_batch images).  prec selects ICL_PREC_FP32 (default: rows equal the one-at-a-time
  * result bit for bit), ICL_PREC_BF16X3 or ICL_PREC_BF16.  window_us = 0 disables waiting (a lone caller runs at once).
  * prec | ICL_FILE_FAIL_NEXT_LEADER: the next batch leader fails with ICL_ERR_NOMEM right after it has taken its queued requests --
@@ -96,7 +96,11 @@ enum { ICL_FILE_FAIL_NEXT_LEADER = 0x100 };
 int icl_set_file_options(icl_ctx *ctx, int prec, int window_us, int max_batch);
 int icl_file_batch_stats(icl_ctx *ctx, int64_t *batches, int64_t *images); /* forward passes run / images served by icl_embed_file */
 /* Image ingest on the host (embeddings.go:50-82): decode a file (baseline or progressive Huffman JPEG, PNG, or binary PPM) to interleaved RGB.
- * With rgb == NULL only *w / *h are returned.  cap_bytes must be >= w*h*3. */
+ * With rgb == NULL only *w / *h are returned.  cap_bytes must be >= w*h*3.
+ * JPEG: 8 bit, 1 component, or 3 with 1x1 chroma and luma sampling 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0), 1x2 (4:4:0: a 4:2:2 file after a
+ * lossless 90-degree rotation), 4x1 or 1x4 (4:1:1, either way up); pixels are libjpeg-turbo's with its default settings.  Any other
+ * sampling (4:1:0, subsampled luma, ...), CMYK, arithmetic coding, lossless and 12 bit return ICL_ERR_UNSUPPORTED; for a sampling the
+ * message names the factors found.  Every file entry point below reads JPEGs through this decoder's frame header. */
 int icl_decode_image_file(const char *path, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h);
 /* decode + cv::resize(INTER_LINEAR)-compatible resize to 224x224 (embeddings.go:50,69): out is 224*224*3 u8 RGB. */
 int icl_load_image_224(const char *path, uint8_t *out);
@@ -108,7 +112,8 @@ int icl_preprocess_file(const char *path, float *nchw);
 /* The resize step alone (embeddings.go:69) on an interleaved u8 RGB image: cv::resize(src, dst, (dw, dh), 0, 0, INTER_LINEAR). */
 int icl_resize_u8(const uint8_t *src_rgb, int32_t sw, int32_t sh, uint8_t *dst_rgb, int32_t dw, int32_t dh);
 /* ---- batched file ingest: replaces the per-file decode of GetImageEmbedding (embeddings.go:46-116) as workflow.go:149-185 calls it ----
- * paths[0..n): JPEG / PNG / PPM files, as icl_load_image_224 reads them.  threads: host decode threads
+ * paths[0..n): JPEG / PNG / PPM files, as icl_load_image_224 reads them (every JPEG sampling icl_decode_image_file lists is rebuilt on
+ * the GPU: 4:4:4, 4:2:2, 4:2:0, 4:4:0 and 4:1:1 files all count under gpu_jpegs).  threads: host decode threads
  * (0 = min(16, hardware threads)).  status[i] = ICL_OK or the ICL_ERR_* code of file i (may be NULL).
  * Returns ICL_OK when every file was read, else ICL_ERR_IO / _UNSUPPORTED naming the LOWEST failed
  * index in icl_last_error; rows of failed files are NaN.  Row i always belongs to paths[i].
@@ -132,7 +137,7 @@ int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files,
 /* ---- entropy decoding on the GPU (opt-in) ----
  * ICL_ENTROPY_HOST (default): host workers run stage A (parsing + Huffman decoding) of every JPEG, as described above.
  * ICL_ENTROPY_GPU: for a sequential Huffman JPEG (SOF0 / SOF1, 8 bit) whose ONE scan carries all components (1, or 3 at 4:4:4 / 4:2:2 /
- * 4:2:0; with or without restart interval) a host worker only parses the markers and unstuffs the entropy-coded segment; kernels decode
+ * 4:2:0 / 4:4:0 / 4:1:1, i.e. every sampling the host decoder reads: 3, 4 or 6 blocks per MCU; with or without restart interval) a host worker only parses the markers and unstuffs the entropy-coded segment; kernels decode
  * it in fixed-size subsequences and accept the result only when the chain of subsequence states is consistent and the stream is clean,
  * which makes it the sequential decode.  Every other file, and every image the check rejects (damaged, truncated, odd streams), takes the
  * ICL_ENTROPY_HOST route; rows, status codes and messages are identical in both modes.  The environment variable ICL_JPEG_ENTROPY=gpu
