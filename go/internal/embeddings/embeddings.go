@@ -93,6 +93,24 @@ func GetImageEmbedding(appCtx *AppContext, imagePath string) ([]float32, error) 
 	return out, nil
 }
 
+// GetImageEmbeddingBytes is GetImageEmbedding for an image the caller holds as encoded bytes (models.UploadedImage.Data): the bytes are
+// decoded in place (cgo pins the slice for the call; it must not be changed meanwhile), no temporary file is written, and the call
+// joins the same coalescing queue as GetImageEmbedding (icl_embed_image_mem).
+func GetImageEmbeddingBytes(appCtx *AppContext, data []byte) ([]float32, error) {
+	if appCtx.Net.Empty() {
+		return nil, fmt.Errorf("failed to generate embedding for image: (in memory, %d bytes)", len(data))
+	}
+	out := make([]float32, C.ICL_HEAD_DENSE0)
+	var p *C.uint8_t // (an empty slice stays NULL / 0: the engine reports "empty image buffer")
+	if len(data) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&data[0]))
+	}
+	if rc := C.icl_embed_image_mem(appCtx.Net.ctx, p, C.int64_t(len(data)), C.ICL_HEAD_DENSE0, (*C.float)(unsafe.Pointer(&out[0]))); rc != C.ICL_OK {
+		return nil, fmt.Errorf("%s", C.GoString(C.icl_last_error(appCtx.Net.ctx)))
+	}
+	return out, nil
+}
+
 // GenerateEmbedding is the name BASELINE.json's north_star uses for GetImageEmbedding.
 func GenerateEmbedding(appCtx *AppContext, imagePath string) ([]float32, error) {
 	return GetImageEmbedding(appCtx, imagePath)

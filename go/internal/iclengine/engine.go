@@ -200,6 +200,94 @@ func ClusterRequests(reqs []Request, head, prec, threads int) ([]RequestResult, 
 	return out, callErr
 }
 
+// RequestBytes is Request for a caller that holds the encoded images (models.UploadedImage.Data, workflow.go:66) instead of files.
+type RequestBytes struct {
+	Images  [][]byte  // each the bytes of a JPEG / PNG / PPM file; an empty one fails that image, not the call
+	Labels  [][]int32 // per image
+	NLabels int
+	MinSize int
+	MaxSize int
+}
+
+// ClusterRequestsBytes is ClusterRequests over images held in memory (icl_cluster_requests_mem): nothing is written to disk for the
+// engine's sake.  The slices are handed to C in place: they are pinned for the duration of the call and must not be changed until
+// it returns.  The pointer and length arrays live in C memory (a Go slice of Go pointers must not cross cgo).  Results, statuses and
+// the returned error are ClusterRequests' on the same bytes; a message names an image as "image <i> (in memory, <n> bytes)".
+func ClusterRequestsBytes(reqs []RequestBytes, head, prec, threads int) ([]RequestResult, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, e
+	}
+	if len(reqs) == 0 {
+		return nil, nil
+	}
+	rows := 0
+	for r, q := range reqs {
+		if len(q.Labels) != len(q.Images) {
+			return nil, fmt.Errorf("request %d: %d images, %d label lists", r, len(q.Images), len(q.Labels))
+		}
+		rows += len(q.Images)
+	}
+	ptrSize := C.size_t(unsafe.Sizeof(uintptr(0)))
+	datav := (**C.uint8_t)(C.calloc(C.size_t(rows+1), ptrSize))
+	defer C.free(unsafe.Pointer(datav))
+	bytesv := (*C.int64_t)(C.calloc(C.size_t(rows+1), 8))
+	defer C.free(unsafe.Pointer(bytesv))
+	data, size := unsafe.Slice(datav, rows+1), unsafe.Slice(bytesv, rows+1)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	n := make([]C.int32_t, len(reqs))
+	nl := make([]C.int32_t, len(reqs))
+	mn := make([]C.int32_t, len(reqs))
+	mx := make([]C.int32_t, len(reqs))
+	off := []C.int64_t{0}
+	idx := []C.int32_t{}
+	at := 0
+	for r, q := range reqs {
+		n[r], nl[r], mn[r], mx[r] = C.int32_t(len(q.Images)), C.int32_t(q.NLabels), C.int32_t(q.MinSize), C.int32_t(q.MaxSize)
+		for i, img := range q.Images {
+			if len(img) > 0 { // (an empty image stays NULL / 0: the engine reports it as that image's failure)
+				pin.Pin(&img[0])
+				data[at], size[at] = (*C.uint8_t)(unsafe.Pointer(&img[0])), C.int64_t(len(img))
+			}
+			at++
+			for _, j := range q.Labels[i] {
+				idx = append(idx, C.int32_t(j))
+			}
+			off = append(off, C.int64_t(len(idx)))
+		}
+	}
+	cid := make([]C.int32_t, rows+1)
+	rank := make([]C.int32_t, rows+1)
+	nc := make([]C.int32_t, len(reqs))
+	nm := make([]C.int32_t, len(reqs))
+	st := make([]C.int32_t, len(reqs))
+	for r := range st {
+		st[r] = -1 // stays -1 when the call fails before the requests run
+	}
+	idx = append(idx, 0)
+	rc := C.icl_cluster_requests_mem((*C.icl_ctx)(raw), C.int32_t(len(reqs)), datav, bytesv, &n[0], &nl[0], &off[0], &idx[0],
+		&mn[0], &mx[0], C.int(head), C.int(prec), C.int32_t(threads), &cid[0], &rank[0], &nc[0], &nm[0], nil, &st[0], nil, nil)
+	var callErr error
+	if rc != C.ICL_OK {
+		callErr = fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		if st[0] < 0 { // an argument or device error: status untouched (imageclust.h), no per-request results
+			return nil, callErr
+		}
+	}
+	out := make([]RequestResult, len(reqs))
+	at = 0
+	for r, q := range reqs {
+		k := len(q.Images)
+		out[r] = RequestResult{Status: int(st[r]), NClusters: int(nc[r]), ClusterID: make([]int32, k), MemberRank: make([]int32, k)}
+		for i := 0; i < k; i++ {
+			out[r].ClusterID[i], out[r].MemberRank[i] = int32(cid[at+i]), int32(rank[at+i])
+		}
+		at += k
+	}
+	return out, callErr
+}
+
 // LastRequestsMs reports the stage wall times of the last ClusterRequests: files -> embedding rows, assembly, clustering.
 func LastRequestsMs() (embedMs, assembleMs, clusterMs float64, err error) {
 	raw, e := Ctx()

@@ -69,6 +69,15 @@ SYMBOLS = [
     ("icl_last_entropy_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_jpeg_coefs_files", _int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
     ("icl_jpeg_coefs_file_host", _int, [C.c_char_p, _int, _vp, _i64, _pi64, _vp]),
+    ("icl_decode_image_mem", _int, [_vp, _i64, _vp, _i64, _pi32, _pi32]),
+    ("icl_load_image_224_mem", _int, [_vp, _i64, _vp]),
+    ("icl_preprocess_mem", _int, [_vp, _i64, _vp]),
+    ("icl_embed_image_mem", _int, [_vp, _vp, _i64, _int, _vp]),
+    ("icl_load_images_224_mem_dev", _int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    ("icl_embed_images_mem", _int, [_vp, _vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
+    ("icl_embed_images_mem_dev", _int, [_vp, _vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
+    ("icl_cluster_requests_mem", _int, [_vp, _i32] + [_vp] * 8 + [_int, _int, _i32] + [_vp] * 8),
+    ("icl_jpeg_coefs_mem", _int, [_vp, _vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
     ("icl_set_batch", _int, [_vp, _int]),
     ("icl_set_conv_options", _int, [_vp, _int]),
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
@@ -205,6 +214,35 @@ def pack_many(problems):
                 img_off=np.concatenate([[0], np.cumsum(n, dtype=np.int64)]))
 
 
+def _byte_view(buf):
+    """(address, length, keep-alive) of an encoded image held as bytes / bytearray / memoryview / contiguous numpy.uint8, or of None (an
+    empty source: address 0).  Nothing is copied: the address is the object's own buffer, and the keep-alive reference is held by the
+    caller for as long as the library may read it."""
+    if buf is None:
+        return 0, 0, None
+    if isinstance(buf, np.ndarray):
+        if buf.dtype != np.uint8 or not buf.flags.c_contiguous:
+            raise TypeError("an image buffer must be contiguous uint8")
+        a = buf
+    else:
+        m = buf if isinstance(buf, memoryview) else memoryview(buf)
+        if not m.c_contiguous or m.itemsize != 1:
+            raise TypeError("an image buffer must be contiguous bytes")
+        if m.nbytes == 0:
+            return 0, 0, None
+        a = np.frombuffer(m, np.uint8)  # a view of the same memory (read-only for bytes)
+    return (a.ctypes.data if a.size else 0), int(a.size), a
+
+
+def _byte_arrays(bufs):
+    """The data / bytes arrays of a batched memory call -> (void*[n], int64[n], n, keep-alive list)."""
+    views = [_byte_view(b) for b in bufs]
+    n = len(views)
+    data = (C.c_void_p * max(1, n))(*[v[0] or None for v in views])
+    size = (C.c_int64 * max(1, n))(*[v[1] for v in views])
+    return data, size, n, [v[2] for v in views]
+
+
 def requests_layout(n, n_labels, head=HEAD_DENSE0):
     """icl_requests_layout (host only): where each request's combined rows live -> (e_off int64[nreq], d int32[nreq], e_len):
     d[r] = head + n_labels[r], e_off[r] = sum of n[q] * d[q] over q < r."""
@@ -226,7 +264,7 @@ def pack_requests(requests, head=HEAD_DENSE0):
     paths, n, nl, off, idx, mn, mx = [], [], [], [0], [], [], []
     for r, (ps, labels, n_labels, lo, hi) in enumerate(requests):
         if len(labels) != len(ps):
-            raise ValueError("request %d: %d paths, %d label lists" % (r, len(ps), len(labels)))
+            raise ValueError("request %d: %d images, %d label lists" % (r, len(ps), len(labels)))
         paths += list(ps)
         n.append(len(ps))
         nl.append(int(n_labels))
@@ -415,6 +453,64 @@ class Context:
         if rc != ICL_OK and not (failed.size and status[failed[0]] == rc):
             check(self.h, rc)
         return status
+
+    def embed_image_mem(self, data, head=HEAD_DENSE0):
+        """icl_embed_image_mem: embed_file for an image held in memory (the same coalescing queue)."""
+        p, n, keep = _byte_view(data)
+        out = np.empty(head, np.float32)
+        check(self.h, self.L.icl_embed_image_mem(self.h, _vp(p), n, head, out.ctypes.data))
+        del keep
+        return out
+
+    def _mem_call(self, fn, bufs, *args):
+        """_files_call for the memory twins: bufs are the encoded images (bytes / bytearray / memoryview / contiguous numpy.uint8; None or
+        an empty buffer is that image's own failure).  The buffers are read in place and stay referenced until the call has returned."""
+        data, size, n, keep = _byte_arrays(bufs)
+        status = np.zeros(n, np.int32)
+        rc = fn(self.h, data, size, n, *args, status.ctypes.data)
+        del keep
+        failed = np.flatnonzero(status)
+        if rc != ICL_OK and not (failed.size and status[failed[0]] == rc):
+            check(self.h, rc)
+        return status
+
+    def load_images_224_mem_dev(self, bufs, d_out, threads=0):
+        """icl_load_images_224_mem_dev: load_images_224_dev for images held in memory."""
+        return self._mem_call(self.L.icl_load_images_224_mem_dev, bufs, threads, _vp(d_out))
+
+    def load_images_224_mem(self, bufs, threads=0):
+        """icl_load_images_224_mem_dev through a device buffer -> (n x 224 x 224 x 3 u8, status)."""
+        n = len(bufs)
+        out = np.zeros((n, 224, 224, 3), np.uint8)
+        d = self.malloc(max(1, n) * IMG_BYTES)
+        try:
+            status = self.load_images_224_mem_dev(bufs, d, threads)
+            if n:
+                self.d2h(out, d)
+        finally:
+            self.free(d)
+        return out, status
+
+    def embed_images_mem(self, bufs, head=HEAD_POOLED, prec=PREC_BF16, threads=0):
+        """icl_embed_images_mem -> (E n x head fp32, status int32[n]); rows of failed images are NaN."""
+        out = np.empty((len(bufs), head), np.float32)
+        status = self._mem_call(self.L.icl_embed_images_mem, bufs, head, prec, threads, out.ctypes.data)
+        return out, status
+
+    def embed_images_mem_dev(self, bufs, d_out, head=HEAD_POOLED, prec=PREC_BF16, threads=0):
+        """icl_embed_images_mem_dev: n x head fp32 rows into device memory d_out -> status (int32[n])."""
+        return self._mem_call(self.L.icl_embed_images_mem_dev, bufs, head, prec, threads, _vp(d_out))
+
+    def jpeg_coefs_mem(self, bufs, entropy=ENTROPY_HOST):
+        """icl_jpeg_coefs_mem (test hook): jpeg_coefs_files for JPEGs held in memory."""
+        data, size, n, keep = _byte_arrays(bufs)
+        off = np.zeros(n + 1, np.int64)
+        state = np.zeros(n, np.int32)
+        check(self.h, self.L.icl_jpeg_coefs_mem(self.h, data, size, n, entropy, None, 0, off.ctypes.data, state.ctypes.data))
+        buf = np.zeros(max(1, int(off[-1])), np.int16)
+        check(self.h, self.L.icl_jpeg_coefs_mem(self.h, data, size, n, entropy, buf.ctypes.data, buf.size, off.ctypes.data, state.ctypes.data))
+        del keep
+        return [buf[off[i]:off[i + 1]] for i in range(n)], state
 
     def load_images_224_dev(self, paths, d_out, threads=0):
         """icl_load_images_224_dev: n x 224x224x3 u8 rows into device memory d_out -> status (int32[n]); failed rows are zero."""
@@ -630,9 +726,22 @@ class Context:
         rows (n x d float32).  self.last_file_status holds every image's code afterwards and self.last_requests_rc the call's own (the lowest
         failed request's; last_error() names it).  Raises for an argument or device error."""
         pk = pack_requests(requests, head)
-        nreq, rows = len(pk["n"]), int(pk["img_off"][-1])
         enc = [os.fsencode(p) for p in pk["paths"]]
         arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        return self._requests_call(self.L.icl_cluster_requests, pk, (arr,), head, prec, threads, want_merges, want_E)
+
+    def cluster_requests_mem(self, requests, head=HEAD_DENSE0, prec=PREC_FP32, threads=0, want_merges=False, want_E=False):
+        """icl_cluster_requests_mem: cluster_requests with each request's images held in memory -- requests = [(buffers, labels_per_image,
+        n_labels, min_size, max_size), ...], buffers as embed_images_mem takes them.  Same return value and attributes."""
+        pk = pack_requests(requests, head)
+        data, size, _, keep = _byte_arrays(pk["paths"])
+        try:
+            return self._requests_call(self.L.icl_cluster_requests_mem, pk, (data, size), head, prec, threads, want_merges, want_E)
+        finally:
+            del keep
+
+    def _requests_call(self, fn, pk, images, head, prec, threads, want_merges, want_E):
+        nreq, rows = len(pk["n"]), int(pk["img_off"][-1])
         cid = np.full(max(rows, 1), -1, np.int32)
         rank = np.full(max(rows, 1), -1, np.int32)
         nc, nm = np.zeros(max(nreq, 1), np.int32), np.zeros(max(nreq, 1), np.int32)
@@ -641,7 +750,7 @@ class Context:
         mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
         E = np.zeros(max(pk["e_len"], 1), np.float32) if want_E else None
         ptr = lambda a: a.ctypes.data
-        rc = self.L.icl_cluster_requests(self.h, nreq, arr, ptr(pk["n"]), ptr(pk["n_labels"]), ptr(pk["label_off"]), ptr(pk["label_idx"]),
+        rc = fn(self.h, nreq, *images, ptr(pk["n"]), ptr(pk["n_labels"]), ptr(pk["label_off"]), ptr(pk["label_idx"]),
                                          ptr(pk["min_size"]), ptr(pk["max_size"]), head, prec, threads, ptr(cid), ptr(rank), ptr(nc), ptr(nm),
                                          ptr(mg) if want_merges else None, ptr(st), ptr(fst), ptr(E) if want_E else None)
         if rc != ICL_OK and (st[:nreq] < 0).any():
@@ -876,6 +985,44 @@ def onnx_to_blob(path):
     rc = L.icl_onnx_to_blob_file(os.fsencode(path), out.ctypes.data, out.nbytes, C.byref(n))
     if rc:
         raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    return out
+
+
+def decode_image_mem(data):
+    """icl_decode_image_mem: decode_image_file for an image held in memory -> h x w x 3 u8 RGB."""
+    L = load()
+    p, n, keep = _byte_view(data)
+    w, h = _i32(), _i32()
+    rc = L.icl_decode_image_mem(_vp(p), n, None, 0, C.byref(w), C.byref(h))
+    if rc:
+        raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    out = np.empty((h.value, w.value, 3), np.uint8)
+    rc = L.icl_decode_image_mem(_vp(p), n, out.ctypes.data, out.nbytes, C.byref(w), C.byref(h))
+    del keep
+    if rc:
+        raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    return out
+
+
+def load_image_224_mem(data):
+    """icl_load_image_224_mem: load_image_224 for an image held in memory."""
+    p, n, keep = _byte_view(data)
+    out = np.empty((224, 224, 3), np.uint8)
+    rc = load().icl_load_image_224_mem(_vp(p), n, out.ctypes.data)
+    del keep
+    if rc:
+        raise ICLError(rc, (load().icl_last_error(None) or b"").decode())
+    return out
+
+
+def preprocess_mem(data):
+    """icl_preprocess_mem: preprocess_file for an image held in memory -> (1, 3, 224, 224) fp32 NCHW."""
+    p, n, keep = _byte_view(data)
+    out = np.empty((1, 3, 224, 224), np.float32)
+    rc = load().icl_preprocess_mem(_vp(p), n, out.ctypes.data)
+    del keep
+    if rc:
+        raise ICLError(rc, (load().icl_last_error(None) or b"").decode())
     return out
 
 

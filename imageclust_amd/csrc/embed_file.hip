@@ -73,11 +73,11 @@ extern "C" int icl_file_batch_stats(icl_ctx *ctx, int64_t *batches, int64_t *ima
     return ICL_OK;
 }
 
-extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *out)
+// One caller of the queue, with its image as a file or as a memory source (icl_embed_file / icl_embed_image_mem: a batch may mix them).
+static int embed_one(icl_ctx *ctx, const ingest_src &src, int head, float *out, const char *what)
 {
-    if (!ctx || !path || !out) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_file: bad argument");
     if (!head_ok(head)) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
-    return no_throw(ctx, "icl_embed_file", [&]() -> int {
+    return no_throw(ctx, what, [&]() -> int {
         icl_file_batcher *b = file_batcher(ctx);
         struct inflight_guard { // counts this caller in from before it queues until it leaves, whatever the exit
             icl_file_batcher *b;
@@ -95,7 +95,7 @@ extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *o
         };
         inflight_guard ig(b);
         std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
-        ICL_TRY(icl_read_image_224(ctx, path, img.data())); // decode + resize run on the caller's thread, in parallel with other callers
+        ICL_TRY(icl_read_image_224(ctx, src, img.data())); // decode + resize run on the caller's thread, in parallel with other callers
         icl_file_req me;
         me.img = img.data();
         me.out = out;
@@ -172,4 +172,16 @@ extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *o
         if (me.rc != ICL_OK) return icl_fail(ctx, me.rc, "%s", me.err.c_str());
         return ICL_OK;
     });
+}
+
+extern "C" int icl_embed_file(icl_ctx *ctx, const char *path, int head, float *out)
+{
+    if (!ctx || !path || !out) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_file: bad argument");
+    return embed_one(ctx, ingest_src{path, nullptr, 0, 0}, head, out, "icl_embed_file");
+}
+
+extern "C" int icl_embed_image_mem(icl_ctx *ctx, const uint8_t *data, int64_t bytes, int head, float *out)
+{
+    if (!ctx || !out) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_image_mem: bad argument");
+    return embed_one(ctx, ingest_src{nullptr, data, bytes, 0}, head, out, "icl_embed_image_mem");
 }

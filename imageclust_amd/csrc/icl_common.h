@@ -212,11 +212,35 @@ struct ingest_sink {
     size_t row_bytes() const { return embeds() ? (size_t)head * 4 : (size_t)ICL_IMG_BYTES; }
     void *row(int64_t i) const { return (uint8_t *)dst + (size_t)i * row_bytes(); }
 };
-// jpeg_gpu.hip: the file pipeline behind those entry points: one ingest_pass in the context's entropy mode (per slab: slab_collect ->
-// run_slab_decode -> slab_deliver), then a repair pass in host mode over the files the GPU entropy check rejected.  Returns the code of
-// the lowest failed file (status[] carries every file's; failed rows are zero (u8) or NaN) after the whole list has been processed --
-// lowest (may be NULL) then names that file -- or the error that stopped it (lowest->index stays -1).
-int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
+// One image of an ingest call: a file (path != NULL), or the caller's own bytes (path == NULL: data[0 .. bytes), used in place, never
+// copied).  A memory source stays owned by the caller and must remain valid and unchanged until the call returns: the repair pass of
+// ingest_files reads it a second time.  data == NULL or bytes <= 0 is that image's own failure (ICL_ERR_IO, "empty image buffer"), as a
+// missing file is.  index is the image's place in the caller's list: it names a memory source in messages.
+struct ingest_src {
+    const char *path;
+    const uint8_t *data;
+    int64_t bytes;
+    int64_t index;
+};
+// What a message calls the source: its path, or "image <index> (in memory, <bytes> bytes)" written into buf (image_io.hip).
+const char *ingest_src_name(const ingest_src &s, char *buf, size_t cap);
+static inline std::vector<ingest_src> ingest_path_srcs(const char *const *paths, int64_t n)
+{
+    std::vector<ingest_src> v((size_t)n);
+    for (int64_t i = 0; i < n; ++i) v[(size_t)i] = ingest_src{paths[i], nullptr, 0, i};
+    return v;
+}
+static inline std::vector<ingest_src> ingest_mem_srcs(const uint8_t *const *data, const int64_t *bytes, int64_t n)
+{
+    std::vector<ingest_src> v((size_t)n);
+    for (int64_t i = 0; i < n; ++i) v[(size_t)i] = ingest_src{nullptr, data[i], bytes[i], i};
+    return v;
+}
+// jpeg_gpu.hip: the ingest pipeline behind those entry points: one ingest_pass in the context's entropy mode (per slab: slab_collect ->
+// run_slab_decode -> slab_deliver), then a repair pass in host mode over the images the GPU entropy check rejected.  Returns the code of
+// the lowest failed image (status[] carries every image's; failed rows are zero (u8) or NaN) after the whole list has been processed --
+// lowest (may be NULL) then names that image -- or the error that stopped it (lowest->index stays -1).
+int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
                  icl_item_failure *lowest = nullptr);
 static inline void icl_ingest_stats_reset(icl_ctx *ctx) // what a batched file call reports (icl_last_ingest_stats, icl_last_entropy_stats)
 {

@@ -72,33 +72,68 @@ void icl_resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, in
     }
 }
 
-static int read_ppm(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
+// the two byte sources of the PPM reader: a file read as it goes, or a memory source's buffer (never read past its end)
+struct ppm_file {
+    FILE *f;
+    int get() { return fgetc(f); }
+    bool holds(size_t) const { return true; } // (the read tells)
+    bool read(uint8_t *dst, size_t n) { return fread(dst, 1, n, f) == n; }
+};
+struct ppm_mem {
+    const uint8_t *p, *end;
+    int get() { return p < end ? (int)*p++ : EOF; }
+    bool holds(size_t n) const { return (size_t)(end - p) >= n; }
+    bool read(uint8_t *dst, size_t n)
+    {
+        if (!holds(n)) return false;
+        memcpy(dst, p, n);
+        p += n;
+        return true;
+    }
+};
+
+template <class S> static bool ppm_parse(S &s, std::vector<uint8_t> &rgb, int &w, int &h)
 {
-    FILE *f = fopen(path, "rb");
-    if (!f) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
     auto token = [&](int &v) -> bool {
         int c;
         do {
-            c = fgetc(f);
+            c = s.get();
             if (c == '#')
-                while (c != '\n' && c != EOF) c = fgetc(f);
+                while (c != '\n' && c != EOF) c = s.get();
         } while (c == ' ' || c == '\n' || c == '\r' || c == '\t');
         if (c < '0' || c > '9') return false;
         v = 0;
         while (c >= '0' && c <= '9') {
+            if (v > (1 << 24)) return false; // (far above every accepted value: no overflow on a long run of digits)
             v = v * 10 + (c - '0');
-            c = fgetc(f);
+            c = s.get();
         }
         return true;
     };
     int maxv = 0;
-    bool ok = fgetc(f) == 'P' && fgetc(f) == '6' && token(w) && token(h) && token(maxv) && maxv == 255 && w > 0 && h > 0 && w <= 16384 && h <= 16384;
+    bool ok = s.get() == 'P' && s.get() == '6' && token(w) && token(h) && token(maxv) && maxv == 255 && w > 0 && h > 0 && w <= 16384 && h <= 16384 &&
+              s.holds((size_t)w * h * 3);
     if (ok) {
         rgb.resize((size_t)w * h * 3);
-        ok = fread(rgb.data(), 1, rgb.size(), f) == rgb.size();
+        ok = s.read(rgb.data(), rgb.size());
     }
-    fclose(f);
-    if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Only JPEG (Huffman; baseline or progressive), PNG and binary PPM (P6, maxval 255) are decoded by this build", path);
+    return ok;
+}
+
+static int read_ppm(icl_ctx *ctx, const ingest_src &src, const char *name, const uint8_t *data, size_t len, std::vector<uint8_t> &rgb, int &w, int &h)
+{
+    bool ok;
+    if (src.path) {
+        FILE *f = fopen(src.path, "rb");
+        if (!f) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", name); // embeddings.go:52
+        ppm_file s{f};
+        ok = ppm_parse(s, rgb, w, h);
+        fclose(f);
+    } else {
+        ppm_mem s{data, data + len};
+        ok = ppm_parse(s, rgb, w, h);
+    }
+    if (!ok) return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Only JPEG (Huffman; baseline or progressive), PNG and binary PPM (P6, maxval 255) are decoded by this build", name);
     return ICL_OK;
 }
 
@@ -121,15 +156,21 @@ void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int o
     h = dh;
 }
 
+// the format rule of files and memory sources alike, on the first (up to) 8 bytes
+static int sniff_format(const uint8_t *magic, size_t got)
+{
+    if (got == 8 && icl_is_png(magic, 8)) return ICL_IMAGE_PNG;
+    if (got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8) return ICL_IMAGE_JPEG;
+    return ICL_IMAGE_PPM;
+}
+
 int icl_image_file_read(const char *path, std::vector<uint8_t> &file)
 {
     std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "rb"), fclose);
     if (!f) return ICL_IMAGE_UNREADABLE;
     unsigned char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const size_t got = fread(magic, 1, 8, f.get());
-    int fmt = ICL_IMAGE_PPM;
-    if (got == 8 && icl_is_png(magic, 8)) fmt = ICL_IMAGE_PNG;
-    else if (got >= 2 && magic[0] == 0xFF && magic[1] == 0xD8) fmt = ICL_IMAGE_JPEG;
+    const int fmt = sniff_format(magic, got);
     if (fmt == ICL_IMAGE_PPM) return fmt; // read_ppm parses the file itself
     fseek(f.get(), 0, SEEK_END);
     const long sz = ftell(f.get());
@@ -138,61 +179,105 @@ int icl_image_file_read(const char *path, std::vector<uint8_t> &file)
     return sz > 0 && fread(file.data(), 1, file.size(), f.get()) == file.size() ? fmt : ICL_IMAGE_UNREADABLE;
 }
 
-int icl_image_decode(icl_ctx *ctx, const char *path, int fmt, const std::vector<uint8_t> &file, std::vector<uint8_t> &rgb, int &w, int &h)
+const char *ingest_src_name(const ingest_src &s, char *buf, size_t cap)
+{
+    if (s.path) return s.path;
+    snprintf(buf, cap, "image %lld (in memory, %lld bytes)", (long long)s.index, (long long)(s.data && s.bytes > 0 ? s.bytes : 0));
+    return buf;
+}
+
+int icl_image_src_read(const ingest_src &src, std::vector<uint8_t> &file, const uint8_t *&data, size_t &len)
+{
+    data = nullptr;
+    len = 0;
+    if (src.path) {
+        const int fmt = icl_image_file_read(src.path, file);
+        data = file.data();
+        len = file.size();
+        return fmt;
+    }
+    if (!src.data || src.bytes <= 0) return ICL_IMAGE_EMPTY;
+    data = src.data;
+    len = (size_t)src.bytes;
+    return sniff_format(data, std::min<size_t>(len, 8));
+}
+
+int icl_image_decode(icl_ctx *ctx, const ingest_src &src, const char *name, int fmt, const uint8_t *data, size_t len, std::vector<uint8_t> &rgb, int &w, int &h)
 {
     switch (fmt) {
-    case ICL_IMAGE_PNG: return icl_png_decode(ctx, file.data(), file.size(), path, rgb, w, h);
+    case ICL_IMAGE_PNG: return icl_png_decode(ctx, data, len, name, rgb, w, h);
     case ICL_IMAGE_JPEG: {
         int orient = 1;
-        ICL_TRY(icl_jpeg_decode(ctx, file.data(), file.size(), path, rgb, w, h, orient));
+        ICL_TRY(icl_jpeg_decode(ctx, data, len, name, rgb, w, h, orient));
         icl_apply_exif_orientation(rgb, w, h, orient);
         return ICL_OK;
     }
-    case ICL_IMAGE_PPM: return read_ppm(ctx, path, rgb, w, h);
-    default: return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", path); // embeddings.go:52
+    case ICL_IMAGE_PPM: return read_ppm(ctx, src, name, data, len, rgb, w, h);
+    case ICL_IMAGE_EMPTY: return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. empty image buffer", name);
+    default: return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. The image file might be corrupt or unreadable", name); // embeddings.go:52
     }
 }
 
 // IMRead(IMReadColor) of embeddings.go:50
-static int read_image(icl_ctx *ctx, const char *path, std::vector<uint8_t> &rgb, int &w, int &h)
+static int read_image(icl_ctx *ctx, const ingest_src &src, std::vector<uint8_t> &rgb, int &w, int &h)
 {
     std::vector<uint8_t> file;
-    const int fmt = icl_image_file_read(path, file);
-    return icl_image_decode(ctx, path, fmt, file, rgb, w, h);
+    const uint8_t *data;
+    size_t len;
+    char nbuf[96];
+    const int fmt = icl_image_src_read(src, file, data, len);
+    return icl_image_decode(ctx, src, ingest_src_name(src, nbuf, sizeof nbuf), fmt, data, len, rgb, w, h);
 }
 
-int icl_read_image_224(icl_ctx *ctx, const char *path, uint8_t *out)
+int icl_read_image_224(icl_ctx *ctx, const ingest_src &src, uint8_t *out)
 {
     std::vector<uint8_t> px;
     int w = 0, h = 0;
-    ICL_TRY(read_image(ctx, path, px, w, h));
+    ICL_TRY(read_image(ctx, src, px, w, h));
     icl_resize_bilinear_u8(px.data(), w, h, out, ICL_IMG_W, ICL_IMG_H);
     return ICL_OK;
 }
 
 // No C++ exception may cross the C ABI (cgo / ctypes would terminate the host process): the ingest entry points allocate
 // buffers whose sizes come from files (no_throw: icl_common.h).
-extern "C" int icl_decode_image_file(const char *path, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h)
+static int decode_image(const ingest_src &src, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h, const char *what)
 {
-    if (!path || !w || !h) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: bad argument");
-    return no_throw(nullptr, "icl_decode_image_file", [&]() -> int {
+    return no_throw(nullptr, what, [&]() -> int {
         std::vector<uint8_t> px;
         int iw = 0, ih = 0;
-        ICL_TRY(read_image(nullptr, path, px, iw, ih));
+        ICL_TRY(read_image(nullptr, src, px, iw, ih));
         *w = iw;
         *h = ih;
         if (rgb) {
-            if (cap_bytes < (int64_t)px.size()) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: buffer too small");
+            if (cap_bytes < (int64_t)px.size()) return icl_fail(nullptr, ICL_ERR_ARG, "%s: buffer too small", what);
             memcpy(rgb, px.data(), px.size());
         }
         return ICL_OK;
     });
 }
 
+extern "C" int icl_decode_image_file(const char *path, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h)
+{
+    if (!path || !w || !h) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_file: bad argument");
+    return decode_image(ingest_src{path, nullptr, 0, 0}, rgb, cap_bytes, w, h, "icl_decode_image_file");
+}
+
+extern "C" int icl_decode_image_mem(const uint8_t *data, int64_t bytes, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h)
+{
+    if (!w || !h) return icl_fail(nullptr, ICL_ERR_ARG, "icl_decode_image_mem: bad argument");
+    return decode_image(ingest_src{nullptr, data, bytes, 0}, rgb, cap_bytes, w, h, "icl_decode_image_mem");
+}
+
 extern "C" int icl_load_image_224(const char *path, uint8_t *out)
 {
     if (!path || !out) return icl_fail(nullptr, ICL_ERR_ARG, "icl_load_image_224: bad argument");
-    return no_throw(nullptr, "icl_load_image_224", [&]() -> int { return icl_read_image_224(nullptr, path, out); });
+    return no_throw(nullptr, "icl_load_image_224", [&]() -> int { return icl_read_image_224(nullptr, ingest_src{path, nullptr, 0, 0}, out); });
+}
+
+extern "C" int icl_load_image_224_mem(const uint8_t *data, int64_t bytes, uint8_t *out)
+{
+    if (!out) return icl_fail(nullptr, ICL_ERR_ARG, "icl_load_image_224_mem: bad argument");
+    return no_throw(nullptr, "icl_load_image_224_mem", [&]() -> int { return icl_read_image_224(nullptr, ingest_src{nullptr, data, bytes, 0}, out); });
 }
 
 // Test hook without a GPU: the quantised coefficients of a JPEG by host stage A (sub_bits == 0), or by stage A0 + the GPU entropy
@@ -260,12 +345,23 @@ extern "C" int icl_resize_u8(const uint8_t *src, int32_t sw, int32_t sh, uint8_t
 }
 
 // PreprocessImage(imagePath) (embeddings.go:46-116): file -> the 1x3x224x224 fp32 NCHW blob.
+static int preprocess(const ingest_src &src, float *nchw, const char *what)
+{
+    return no_throw(nullptr, what, [&]() -> int {
+        std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
+        ICL_TRY(icl_read_image_224(nullptr, src, img.data()));
+        return icl_preprocess_u8(img.data(), nchw);
+    });
+}
+
 extern "C" int icl_preprocess_file(const char *path, float *nchw)
 {
     if (!path || !nchw) return icl_fail(nullptr, ICL_ERR_ARG, "icl_preprocess_file: bad argument");
-    return no_throw(nullptr, "icl_preprocess_file", [&]() -> int {
-        std::vector<uint8_t> img((size_t)ICL_IMG_BYTES);
-        ICL_TRY(icl_read_image_224(nullptr, path, img.data()));
-        return icl_preprocess_u8(img.data(), nchw);
-    });
+    return preprocess(ingest_src{path, nullptr, 0, 0}, nchw, "icl_preprocess_file");
+}
+
+extern "C" int icl_preprocess_mem(const uint8_t *data, int64_t bytes, float *nchw)
+{
+    if (!nchw) return icl_fail(nullptr, ICL_ERR_ARG, "icl_preprocess_mem: bad argument");
+    return preprocess(ingest_src{nullptr, data, bytes, 0}, nchw, "icl_preprocess_mem");
 }

@@ -372,12 +372,14 @@ struct worker_state { // buffers a worker reuses from file to file
     std::vector<uint32_t> offs;
 };
 
-// One file, on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
+// One image (a file, or a memory source read in place: icl_image_src_read), on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
 // qualifies), stage A for every other JPEG the GPU takes, the whole host path for everything else.  Status codes and messages are
 // those of icl_load_image_224 (image_io.hip).
-static void process_file(const char *path, worker_state &ws, int entropy, file_result &r)
+static void process_file(const ingest_src &src, worker_state &ws, int entropy, file_result &r)
 {
     icl_jpeg_coefs &J = ws.J;
+    char nbuf[96];
+    const char *path = ingest_src_name(src, nbuf, sizeof nbuf); // what the messages call the image
     auto fail_from_tls = [&](int rc) {
         r.kind = KIND_FAILED;
         r.rc = rc;
@@ -386,18 +388,20 @@ static void process_file(const char *path, worker_state &ws, int entropy, file_r
     try {
         std::vector<uint8_t> file, rgb;
         int w = 0, h = 0;
-        const int fmt = icl_image_file_read(path, file);
+        const uint8_t *data;
+        size_t len;
+        const int fmt = icl_image_src_read(src, file, data, len);
         if (fmt == ICL_IMAGE_JPEG) {
             if (entropy == ICL_ENTROPY_GPU) {
                 bool qualifies = false;
-                (void)icl_jpeg_stage_a0(file.data(), file.size(), path, ICL_JE_SUB_BITS, J, ws.A, qualifies); // (an error: the usual route reports it)
+                (void)icl_jpeg_stage_a0(data, len, path, ICL_JE_SUB_BITS, J, ws.A, qualifies); // (an error: the usual route reports it)
                 if (qualifies && pack_stream(J, ws.A, r)) {
                     r.kind = KIND_JSTREAM;
                     return;
                 }
             }
             r.host_entropy = true;
-            const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), path, J);
+            const int rc = icl_jpeg_stage_a(nullptr, data, len, path, J);
             if (rc) return fail_from_tls(rc);
             if (pack_jpeg(J, r, ws.offs)) {
                 r.kind = KIND_JPEG;
@@ -409,8 +413,8 @@ static void process_file(const char *path, worker_state &ws, int entropy, file_r
             const int rc2 = icl_jpeg_stage_b(nullptr, J, path, rgb);
             if (rc2) return fail_from_tls(rc2);
             icl_apply_exif_orientation(rgb, w, h, J.orient);
-        } else { // PNG, PPM, or a file that cannot be read: the host path decodes it or reports why not
-            const int rc = icl_image_decode(nullptr, path, fmt, file, rgb, w, h);
+        } else { // PNG, PPM, or a file that cannot be read / an empty buffer: the host path decodes it or reports why not
+            const int rc = icl_image_decode(nullptr, src, path, fmt, data, len, rgb, w, h);
             if (rc) return fail_from_tls(rc);
         }
         r.packed.resize((size_t)ICL_IMG_BYTES);
@@ -649,7 +653,7 @@ struct ingest_totals {
 };
 
 struct ingest_job { // the list a pass works on, and its caller
-    const char *const *paths;
+    const ingest_src *srcs;
     int64_t n;
     int32_t threads;
     int32_t *status; // may be NULL
@@ -711,7 +715,10 @@ static int slab_collect(icl_ctx *ctx, const ingest_job &job, file_feed &feed, co
             F.used += align16(ICL_IMG_BYTES);
             ++tot.host_files;
         } else {
-            if (!place_jpeg(*r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", job.what, job.paths[row]);
+            if (!place_jpeg(*r, F, S)) {
+                char nbuf[96];
+                return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", job.what, ingest_src_name(job.srcs[row], nbuf, sizeof nbuf));
+            }
             ++tot.gpu_jpegs;
             if (r->kind == KIND_JSTREAM) {
                 res.stream_rows.push_back(row);
@@ -774,7 +781,7 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
         thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state()); // a worker's buffers, from file to file
         const auto t0 = std::chrono::steady_clock::now();
         std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
-        if (r) process_file(job.paths[i], *wst, entropy, *r);
+        if (r) process_file(job.srcs[i], *wst, entropy, *r);
         decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
         return r;
     };
@@ -803,18 +810,18 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
 } // namespace
 
 // The pipeline (declared in icl_common.h): one pass in the context's entropy mode; the images the GPU entropy check rejected are then
-// redone by a pass in ICL_ENTROPY_HOST mode over those files alone into a sink of the same kind on a temporary (rows do not depend on
+// redone by a pass in ICL_ENTROPY_HOST mode over those sources alone (a memory source is read again from the caller's buffer) into a sink of the same kind on a temporary (rows do not depend on
 // the batch they are rebuilt or embedded in), which also produces their status codes and messages.
-int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
+int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
                  icl_item_failure *lowest_out)
 {
     pass_result res;
     ingest_totals tot;
-    ICL_TRY(ingest_pass(ctx, ingest_job{paths, n, threads, status, what}, sink, ctx->entropy_mode, res, tot));
+    ICL_TRY(ingest_pass(ctx, ingest_job{srcs, n, threads, status, what}, sink, ctx->entropy_mode, res, tot));
     const int64_t nrej = (int64_t)res.rejected.size();
     if (nrej) {
-        std::vector<const char *> rp((size_t)nrej);
-        for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = paths[res.rejected[(size_t)q]];
+        std::vector<ingest_src> rp((size_t)nrej); // (each keeps its index in the caller's list: messages name it)
+        for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = srcs[res.rejected[(size_t)q]];
         std::vector<int32_t> rstatus((size_t)nrej, 0);
         pass_result rres;
         std::vector<float> h_tmp;
@@ -856,28 +863,45 @@ int ingest_files(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t thre
     return ICL_OK;
 }
 
+// what ICL_ERR_ARG covers for a list of memory sources (an empty or NULL entry is that image's own failure)
+static bool mem_list_ok(const uint8_t *const *data, const int64_t *bytes, int64_t n) { return n >= 0 && (n == 0 || (data && bytes)); }
+
+static int load_images_224_dev(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int32_t threads, uint8_t *d_out,
+                               int32_t *status, const char *what)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return no_throw(ctx, what, [&]() -> int {
+        icl_ingest_stats_reset(ctx);
+        if (n == 0) return ICL_OK;
+        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        return ingest_files(ctx, srcs.data(), n, threads, ingest_sink{ingest_sink::U8_DEV, d_out, 0, 0}, status, what);
+    });
+}
+
 extern "C" int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, uint8_t *d_out, int32_t *status)
 {
     if (!ctx || n < 0 || (n && (!paths || !d_out)) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: bad argument");
     for (int64_t i = 0; i < n; ++i)
         if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: paths[%lld] is NULL", (long long)i);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    icl_device_guard g(ctx->device);
-    return no_throw(ctx, "icl_load_images_224_dev", [&]() -> int {
-        icl_ingest_stats_reset(ctx);
-        if (n == 0) return ICL_OK;
-        return ingest_files(ctx, paths, n, threads, ingest_sink{ingest_sink::U8_DEV, d_out, 0, 0}, status, "icl_load_images_224_dev");
-    });
+    return load_images_224_dev(ctx, false, paths, nullptr, nullptr, n, threads, d_out, status, "icl_load_images_224_dev");
 }
 
-static int embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *out, int32_t *status, bool dev,
-                       const char *what)
+extern "C" int icl_load_images_224_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int32_t threads, uint8_t *d_out, int32_t *status)
 {
-    if (!ctx || n < 0 || (n && (!paths || !out)) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (!ctx || !mem_list_ok(data, bytes, n) || (n && !d_out) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_mem_dev: bad argument");
+    return load_images_224_dev(ctx, true, nullptr, data, bytes, n, threads, d_out, status, "icl_load_images_224_mem_dev");
+}
+
+// mem: memory sources (data, bytes); otherwise files (paths)
+static int embed_files(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec,
+                       int32_t threads, float *out, int32_t *status, bool dev, const char *what)
+{
+    if (!ctx || n < 0 || (n && !out) || threads < 0 || (mem ? !mem_list_ok(data, bytes, n) : (n && !paths))) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
     if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
     if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16 && prec != ICL_PREC_BF16X3)
         return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32, ICL_PREC_BF16 or ICL_PREC_BF16X3");
-    for (int64_t i = 0; i < n; ++i)
+    for (int64_t i = 0; !mem && i < n; ++i)
         if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
@@ -885,18 +909,31 @@ static int embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int he
     return no_throw(ctx, what, [&]() -> int {
         icl_ingest_stats_reset(ctx);
         if (n == 0) return ICL_OK;
-        return ingest_files(ctx, paths, n, threads, ingest_sink{dev ? ingest_sink::EMB_DEV : ingest_sink::EMB_HOST, out, head, prec}, status, what);
+        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        return ingest_files(ctx, srcs.data(), n, threads, ingest_sink{dev ? ingest_sink::EMB_DEV : ingest_sink::EMB_HOST, out, head, prec}, status, what);
     });
 }
 
 extern "C" int icl_embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *out, int32_t *status)
 {
-    return embed_files(ctx, paths, n, head, prec, threads, out, status, false, "icl_embed_files");
+    return embed_files(ctx, false, paths, nullptr, nullptr, n, head, prec, threads, out, status, false, "icl_embed_files");
 }
 
 extern "C" int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *d_out, int32_t *status)
 {
-    return embed_files(ctx, paths, n, head, prec, threads, d_out, status, true, "icl_embed_files_dev");
+    return embed_files(ctx, false, paths, nullptr, nullptr, n, head, prec, threads, d_out, status, true, "icl_embed_files_dev");
+}
+
+extern "C" int icl_embed_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec, int32_t threads, float *out,
+                                    int32_t *status)
+{
+    return embed_files(ctx, true, nullptr, data, bytes, n, head, prec, threads, out, status, false, "icl_embed_images_mem");
+}
+
+extern "C" int icl_embed_images_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec, int32_t threads, float *d_out,
+                                        int32_t *status)
+{
+    return embed_files(ctx, true, nullptr, data, bytes, n, head, prec, threads, d_out, status, true, "icl_embed_images_mem_dev");
 }
 
 extern "C" int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes, double *host_decode_s)
@@ -930,17 +967,14 @@ extern "C" int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, 
     return ICL_OK;
 }
 
-// Test hook: the quantised coefficients of each file as stage A leaves them, by host stage A or by the GPU entropy decoder (one
-// single-image slab per file through the pipeline's own placement and launch code).
-extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap, int64_t *offsets, int32_t *state)
+// the body of icl_jpeg_coefs_files / _mem after the argument check
+static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs,
+                      int64_t cap, int64_t *offsets, int32_t *state, const char *what)
 {
-    if (!ctx || n < 0 || (n && !paths) || !offsets || !state || cap < 0 || (entropy_mode != ICL_ENTROPY_HOST && entropy_mode != ICL_ENTROPY_GPU))
-        return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: bad argument");
-    for (int64_t i = 0; i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: paths[%lld] is NULL", (long long)i);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    return no_throw(ctx, "icl_jpeg_coefs_files", [&]() -> int {
+    return no_throw(ctx, what, [&]() -> int {
+        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
         icl_ingest_ws *ws = nullptr;
         if (entropy_mode == ICL_ENTROPY_GPU) {
             ICL_TRY(ingest_ws(ctx, ws));
@@ -951,16 +985,20 @@ extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int6
         for (int64_t i = 0; i < n; ++i) {
             offsets[i] = at;
             state[i] = -1;
+            char nbuf[96];
+            const char *name = ingest_src_name(srcs[i], nbuf, sizeof nbuf);
             if (entropy_mode == ICL_ENTROPY_HOST) {
                 std::vector<uint8_t> file;
-                if (icl_image_file_read(paths[i], file) != ICL_IMAGE_JPEG) return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: %s is not a readable JPEG", paths[i]);
-                const int rc = icl_jpeg_stage_a(nullptr, file.data(), file.size(), paths[i], wst->J);
-                if (rc) return icl_fail(ctx, rc, "icl_jpeg_coefs_files: %s", icl_last_error(nullptr));
+                const uint8_t *jd;
+                size_t jn;
+                if (icl_image_src_read(srcs[i], file, jd, jn) != ICL_IMAGE_JPEG) return icl_fail(ctx, ICL_ERR_IO, "%s: %s is not a readable JPEG", what, name);
+                const int rc = icl_jpeg_stage_a(nullptr, jd, jn, name, wst->J);
+                if (rc) return icl_fail(ctx, rc, "%s: %s", what, icl_last_error(nullptr));
                 state[i] = 1;
                 for (int c = 0; c < wst->J.ncomp; ++c) {
                     const std::vector<int16_t> &cf = wst->J.comp[c].coefs;
                     if (coefs) {
-                        if (at + (int64_t)cf.size() > cap) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: buffer too small");
+                        if (at + (int64_t)cf.size() > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small", what);
                         memcpy(coefs + at, cf.data(), cf.size() * 2);
                     }
                     at += (int64_t)cf.size();
@@ -968,18 +1006,18 @@ extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int6
                 continue;
             }
             file_result r;
-            process_file(paths[i], *wst, ICL_ENTROPY_GPU, r);
+            process_file(srcs[i], *wst, ICL_ENTROPY_GPU, r);
             if (r.kind != KIND_JSTREAM) continue; // does not qualify (or cannot be read at all)
             int64_t total = 0;
             for (int c = 0; c < r.ncomp; ++c) total += (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
             state[i] = 0;
             if (coefs) {
-                if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: buffer too small");
+                if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small", what);
                 ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
                 const slab_view S = ws->host(0);
                 slab_fill F;
                 memset(&S.imgs[0], 0, offsetof(ingest_image, xofs));
-                if (!place_jpeg(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "icl_jpeg_coefs_files: inconsistent JPEG geometry for %s", paths[i]);
+                if (!place_jpeg(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, name);
                 F.nimg = 1;
                 int64_t upload = 0;
                 ICL_TRY(run_slab_decode(ctx, ws, S, F, upload));
@@ -999,4 +1037,26 @@ extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int6
         offsets[n] = at;
         return ICL_OK;
     });
+}
+
+static bool coefs_args_ok(icl_ctx *ctx, int64_t n, int entropy_mode, int64_t cap, const int64_t *offsets, const int32_t *state)
+{
+    return ctx && n >= 0 && offsets && state && cap >= 0 && (entropy_mode == ICL_ENTROPY_HOST || entropy_mode == ICL_ENTROPY_GPU);
+}
+
+// Test hook: the quantised coefficients of each file as stage A leaves them, by host stage A or by the GPU entropy decoder (one
+// single-image slab per file through the pipeline's own placement and launch code).
+extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap, int64_t *offsets, int32_t *state)
+{
+    if (!coefs_args_ok(ctx, n, entropy_mode, cap, offsets, state) || (n && !paths)) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: bad argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: paths[%lld] is NULL", (long long)i);
+    return jpeg_coefs(ctx, false, paths, nullptr, nullptr, n, entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_files");
+}
+
+extern "C" int icl_jpeg_coefs_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
+                                  int64_t *offsets, int32_t *state)
+{
+    if (!coefs_args_ok(ctx, n, entropy_mode, cap, offsets, state) || !mem_list_ok(data, bytes, n)) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_mem: bad argument");
+    return jpeg_coefs(ctx, true, nullptr, data, bytes, n, entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_mem");
 }

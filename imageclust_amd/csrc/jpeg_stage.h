@@ -79,15 +79,19 @@ int icl_je_decode_slab(icl_ctx *ctx, hipStream_t st, const icl_je_slab &s);
 
 // image_io.hip: the host ingest path.  The batched file path (jpeg_gpu.hip) reads and sniffs files, and decodes what the GPU does not
 // take, through it; the icl_embed_file batcher (embed_file.hip) reads and resizes through it.
-enum { ICL_IMAGE_UNREADABLE = -1, ICL_IMAGE_PPM = 0, ICL_IMAGE_PNG = 1, ICL_IMAGE_JPEG = 2 };
+enum { ICL_IMAGE_EMPTY = -2, ICL_IMAGE_UNREADABLE = -1, ICL_IMAGE_PPM = 0, ICL_IMAGE_PNG = 1, ICL_IMAGE_JPEG = 2 };
 // Opens path and tells its format by the first bytes (PNG signature, JPEG SOI; anything else goes to the PPM reader).  A PNG or
 // JPEG is read whole into `file`.  ICL_IMAGE_UNREADABLE: the file cannot be opened, or a PNG / JPEG cannot be read whole.
 int icl_image_file_read(const char *path, std::vector<uint8_t> &file);
-// IMRead(IMReadColor) of what icl_image_file_read returned: interleaved RGB, w*h*3, the EXIF orientation applied.  Every status
-// code and message of the host path comes from here.
-int icl_image_decode(icl_ctx *ctx, const char *path, int fmt, const std::vector<uint8_t> &file, std::vector<uint8_t> &rgb, int &w, int &h);
-// read + decode + cv::resize to the 224x224x3 u8 image (icl_load_image_224)
-int icl_read_image_224(icl_ctx *ctx, const char *path, uint8_t *out);
+// The bytes of a source (ingest_src, icl_common.h) and their format: a file through icl_image_file_read (data / len then point into
+// `file`), a memory source by the same sniffing rule on the caller's buffer, which data / len then name as they stand (no copy;
+// ICL_IMAGE_EMPTY for data == NULL or bytes <= 0).
+int icl_image_src_read(const ingest_src &src, std::vector<uint8_t> &file, const uint8_t *&data, size_t &len);
+// IMRead(IMReadColor) of what icl_image_src_read returned: interleaved RGB, w*h*3, the EXIF orientation applied.  Every status
+// code and message of the host path comes from here; name (ingest_src_name) is what the messages call the source.
+int icl_image_decode(icl_ctx *ctx, const ingest_src &src, const char *name, int fmt, const uint8_t *data, size_t len, std::vector<uint8_t> &rgb, int &w, int &h);
+// read + decode + cv::resize to the 224x224x3 u8 image (icl_load_image_224, icl_load_image_224_mem)
+int icl_read_image_224(icl_ctx *ctx, const ingest_src &src, uint8_t *out);
 void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient);
 void icl_resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
 void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al); // cv::resize INTER_LINEAR source offsets + 11-bit weights

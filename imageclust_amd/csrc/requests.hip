@@ -118,12 +118,12 @@ extern "C" int icl_requests_layout(int32_t nreq, const int32_t *n, const int32_t
     return ICL_OK;
 }
 
-// what ICL_ERR_ARG covers: nothing is written when it fails
-static int rq_check_args(icl_ctx *ctx, int32_t nreq, const char *const *paths, const int32_t *n, const int32_t *n_labels, const int64_t *label_off,
+// what ICL_ERR_ARG covers: nothing is written when it fails.  The images are files (paths) or, for icl_cluster_requests_mem, memory
+// sources (mem; data, bytes: an empty or NULL entry is that image's own failure, a null array the call's).
+static int rq_check_args(icl_ctx *ctx, const char *what, int32_t nreq, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, const int32_t *n, const int32_t *n_labels, const int64_t *label_off,
                          const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head, int prec, int32_t threads,
                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *status)
 {
-    const char *what = "icl_cluster_requests";
     if (!ctx) return icl_fail(ctx, ICL_ERR_ARG, "%s: null context", what);
     if (nreq < 0 || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: nreq %d, threads %d", what, nreq, threads);
     if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "%s: head must be 2048 or 1000", what);
@@ -139,8 +139,9 @@ static int rq_check_args(icl_ctx *ctx, int32_t nreq, const char *const *paths, c
         rows += n[r];
     }
     if (rows >= ((int64_t)1 << 30)) return icl_fail(ctx, ICL_ERR_ARG, "%s: %lld images in all", what, (long long)rows);
-    if (rows && (!paths || !cluster_id || !member_rank)) return icl_fail(ctx, ICL_ERR_ARG, "%s: null paths / cluster_id / member_rank", what);
-    for (int64_t i = 0; i < rows; ++i)
+    if (rows && mem && (!data || !bytes || !cluster_id || !member_rank)) return icl_fail(ctx, ICL_ERR_ARG, "%s: null data / bytes / cluster_id / member_rank", what);
+    if (rows && !mem && (!paths || !cluster_id || !member_rank)) return icl_fail(ctx, ICL_ERR_ARG, "%s: null paths / cluster_id / member_rank", what);
+    for (int64_t i = 0; !mem && i < rows; ++i)
         if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
     if (label_off[0] < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: label_off[0] is %lld", what, (long long)label_off[0]);
     for (int64_t i = 0; i < rows; ++i)
@@ -158,12 +159,11 @@ static int rq_check_args(icl_ctx *ctx, int32_t nreq, const char *const *paths, c
 }
 
 // ctx->mu held, device selected, a model loaded, nreq > 0
-static int cluster_requests_locked(icl_ctx *ctx, int32_t nreq, const char *const *paths, const int32_t *n, const int32_t *n_labels,
+static int cluster_requests_locked(icl_ctx *ctx, const char *what, int32_t nreq, const ingest_src *srcs, const int32_t *n, const int32_t *n_labels,
                                    const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
                                    int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
                                    int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
 {
-    const char *what = "icl_cluster_requests";
     std::vector<int64_t> e_off((size_t)nreq), img((size_t)nreq + 1, 0);
     std::vector<int32_t> d((size_t)nreq);
     int64_t e_len = 0;
@@ -187,7 +187,7 @@ static int cluster_requests_locked(icl_ctx *ctx, int32_t nreq, const char *const
     icl_item_failure bad_file; // the call's lowest failed file
     ICL_HIP(ctx, hipEventRecord(ev[0], st));
     if (rows) {
-        const int rc = ingest_files(ctx, paths, rows, threads, ingest_sink{ingest_sink::EMB_DEV, d_dense, head, prec}, fstat.data(), what, &bad_file);
+        const int rc = ingest_files(ctx, srcs, rows, threads, ingest_sink{ingest_sink::EMB_DEV, d_dense, head, prec}, fstat.data(), what, &bad_file);
         if (rc != ICL_OK && bad_file.index < 0) return rc; // not a file's failure: the pipeline stopped
     }
     ICL_HIP(ctx, hipEventRecord(ev[1], st));
@@ -279,14 +279,15 @@ static int cluster_requests_locked(icl_ctx *ctx, int32_t nreq, const char *const
     return ICL_OK;
 }
 
-extern "C" int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *const *paths, const int32_t *n, const int32_t *n_labels,
-                                    const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
-                                    int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
-                                    int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
+// both entry points: paths, or (mem) data / bytes
+static int cluster_requests(icl_ctx *ctx, const char *what, int32_t nreq, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, const int32_t *n,
+                            const int32_t *n_labels, const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
+                            int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges,
+                            int32_t *status, int32_t *file_status, float *E_out)
 {
-    return no_throw(ctx, "icl_cluster_requests", [&]() -> int {
-        ICL_TRY(rq_check_args(ctx, nreq, paths, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id, member_rank,
-                              n_clusters, n_merges, status));
+    return no_throw(ctx, what, [&]() -> int {
+        ICL_TRY(rq_check_args(ctx, what, nreq, mem, paths, data, bytes, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
+                              member_rank, n_clusters, n_merges, status));
         std::lock_guard<std::mutex> lk(ctx->mu);
         icl_device_guard g(ctx->device);
         if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
@@ -294,9 +295,30 @@ extern "C" int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *cons
         ctx->many_stats[0] = ctx->many_stats[1] = ctx->many_stats[2] = ctx->many_stats[3] = 0;
         ctx->requests_ms[0] = ctx->requests_ms[1] = ctx->requests_ms[2] = 0;
         if (nreq == 0) return ICL_OK;
-        return cluster_requests_locked(ctx, nreq, paths, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
+        int64_t rows = 0;
+        for (int32_t r = 0; r < nreq; ++r) rows += n[r];
+        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, rows) : ingest_path_srcs(paths, rows);
+        return cluster_requests_locked(ctx, what, nreq, srcs.data(), n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
                                        member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
     });
+}
+
+extern "C" int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *const *paths, const int32_t *n, const int32_t *n_labels,
+                                    const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
+                                    int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
+                                    int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
+{
+    return cluster_requests(ctx, "icl_cluster_requests", nreq, false, paths, nullptr, nullptr, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
+                            cluster_id, member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
+}
+
+extern "C" int icl_cluster_requests_mem(icl_ctx *ctx, int32_t nreq, const uint8_t *const *data, const int64_t *bytes, const int32_t *n, const int32_t *n_labels,
+                                        const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
+                                        int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
+                                        int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
+{
+    return cluster_requests(ctx, "icl_cluster_requests_mem", nreq, true, nullptr, data, bytes, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
+                            cluster_id, member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
 }
 
 extern "C" int icl_last_requests_ms(icl_ctx *ctx, double *embed_ms, double *assemble_ms, double *cluster_ms)

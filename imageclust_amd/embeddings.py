@@ -103,6 +103,21 @@ def GetImageEmbedding(appCtx: AppContext, imagePath: str):
     return emb, None
 
 
+def GetImageEmbeddingBytes(appCtx: AppContext, data):
+    """GetImageEmbedding for an image the caller holds as encoded bytes (models.UploadedImage.Data: bytes / bytearray / memoryview /
+    contiguous numpy.uint8) -> (embedding []float32, err).  The bytes are decoded in place -- no temporary file -- and the call joins
+    the same coalescing queue as GetImageEmbedding (icl_embed_image_mem)."""
+    if appCtx.Net is None or appCtx.Net.Empty():
+        return None, "failed to generate embedding for image: (in memory)"
+    try:
+        emb = appCtx.Net.ctx.embed_image_mem(data, appCtx.Head)
+    except _lib.ICLError as e:
+        return None, str(e)
+    if emb.size == 0:
+        return None, "embedding is empty for image: (in memory)"
+    return emb, None
+
+
 GenerateEmbedding = GetImageEmbedding  # the name BASELINE.json's north_star uses for the same function
 
 

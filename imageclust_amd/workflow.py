@@ -30,6 +30,15 @@ def PackRequests(requests: Sequence[Request]):
     return out
 
 
+def _results(requests_ids, res, statuses):
+    out = []
+    for ids, (cid, rank, _, st) in zip(requests_ids, res):
+        if statuses is not None:
+            statuses.append(int(st))
+        out.append((clusters_as_map(cid, rank, list(ids)), True) if st == _lib.ICL_OK else (None, False))
+    return out
+
+
 def RunRequests(appCtx: AppContext, requests: Sequence[Request], prec: int = _lib.PREC_FP32, threads: int = 0,
                 statuses: Optional[List[int]] = None) -> List[Tuple[Optional[Dict[int, List[str]]], bool]]:
     """workflow.go:84-94 for every request = (paths, ids, labels_per_image, labelSet, minSize, maxSize) -> [(map cluster id -> member ids,
@@ -39,9 +48,25 @@ def RunRequests(appCtx: AppContext, requests: Sequence[Request], prec: int = _li
     if appCtx.Net is None or appCtx.Net.Empty():
         raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunRequests: no model loaded")
     res = appCtx.Net.ctx.cluster_requests(PackRequests(requests), appCtx.Head, prec, threads)
-    out = []
-    for (_, ids, _, _, _, _), (cid, rank, _, st) in zip(requests, res):
-        if statuses is not None:
-            statuses.append(int(st))
-        out.append((clusters_as_map(cid, rank, list(ids)), True) if st == _lib.ICL_OK else (None, False))
-    return out
+    return _results([r[1] for r in requests], res, statuses)
+
+
+UploadedRequest = Tuple[Sequence[Tuple[str, bytes]], Sequence[Sequence[str]], Dict[str, int], int, int]
+
+
+def RunUploaded(appCtx: AppContext, requests: Sequence[UploadedRequest], prec: int = _lib.PREC_FP32, threads: int = 0,
+                statuses: Optional[List[int]] = None) -> List[Tuple[Optional[Dict[int, List[str]]], bool]]:
+    """workflow.Run(uploadedImages) (workflow.go:66-94) for every request = (uploaded, labels_per_image, labelSet, minSize, maxSize),
+    `uploaded` a list of (Filename, Data) pairs as models.UploadedImage holds them.  The bytes go to the engine as they are
+    (icl_cluster_requests_mem): nothing is written to a temporary directory (workflow.go:120-127 does that for gocv.IMRead's sake).  Image
+    i of a request gets the id "img_<i>" processImages assigns (workflow.go:140).  Returns what RunRequests returns."""
+    if appCtx.Net is None or appCtx.Net.Empty():
+        raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunUploaded: no model loaded")
+    packed, ids = [], []
+    for r, (uploaded, labels_per_image, labelSet, minSize, maxSize) in enumerate(requests):
+        if len(labels_per_image) != len(uploaded):
+            raise ValueError("request %d: %d images, %d label lists" % (r, len(uploaded), len(labels_per_image)))
+        packed.append(([data for _, data in uploaded], [LabelIndices(labels, labelSet) for labels in labels_per_image], len(labelSet), minSize, maxSize))
+        ids.append(["img_%d" % i for i in range(len(uploaded))])
+    res = appCtx.Net.ctx.cluster_requests_mem(packed, appCtx.Head, prec, threads)
+    return _results(ids, res, statuses)

@@ -371,6 +371,39 @@ int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *const *paths, c
                          int head, int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
                          int32_t *merges, int32_t *status /* nreq */, int32_t *file_status /* sum n[r] */, float *E_out);
 int icl_last_requests_ms(icl_ctx *ctx, double *embed_ms, double *assemble_ms, double *cluster_ms);
+/* ---- images from memory: the twins of the path calls above for callers that hold the encoded bytes (workflow.go:66: workflow.Run receives
+ * models.UploadedImage{Filename, Data}; the reference writes them to a temporary directory, :120-127, only because gocv.IMRead wants a name) ----
+ * An image is data[0 .. bytes): the bytes of a JPEG / PNG / PPM file, decoded in place by the decoders the path calls use; nothing is copied
+ * or written to disk.  THE BUFFERS STAY OWNED BY THE CALLER AND MUST REMAIN VALID AND UNCHANGED UNTIL THE CALL RETURNS (the batched calls may
+ * read an image twice: an image the GPU entropy check rejects is decoded again from the same buffer).  Nothing past data[bytes - 1] is read.
+ * Outputs, layout, row ownership (row i belongs to image i), status codes, NaN / zero rows of failed images and the statistics calls are
+ * those of the path twin; for the same bytes the results are equal bit for bit.  An error message names a memory image as
+ * "image <index> (in memory, <bytes> bytes)" where the path call names the path (index 0 for the single-image calls).  data == NULL or
+ * bytes <= 0 is that IMAGE's failure (ICL_ERR_IO, "empty image buffer"), as a missing file is for a path call.  ICL_ERR_ARG (nothing written)
+ * is for the call's own arguments: a null data or bytes ARRAY with n > 0, n < 0, and whatever the path twin rejects.
+ * icl_decode_image_mem / icl_load_image_224_mem / icl_preprocess_mem: icl_decode_image_file / icl_load_image_224 / icl_preprocess_file (host only).
+ * icl_embed_image_mem: icl_embed_file; it joins the SAME coalescing queue (a batch may mix path and memory callers; icl_set_file_options,
+ * icl_file_batch_stats and ICL_FILE_FAIL_NEXT_LEADER apply alike).
+ * icl_load_images_224_mem_dev / icl_embed_images_mem / icl_embed_images_mem_dev: icl_load_images_224_dev / icl_embed_files / icl_embed_files_dev;
+ * icl_last_ingest_stats and icl_last_entropy_stats report the call afterwards.
+ * icl_cluster_requests_mem: icl_cluster_requests with data / bytes (sum of n[r] entries, request after request) in place of paths.
+ * icl_jpeg_coefs_mem: icl_jpeg_coefs_files (test hook). */
+int icl_decode_image_mem(const uint8_t *data, int64_t bytes, uint8_t *rgb, int64_t cap_bytes, int32_t *w, int32_t *h);
+int icl_load_image_224_mem(const uint8_t *data, int64_t bytes, uint8_t *out);
+int icl_preprocess_mem(const uint8_t *data, int64_t bytes, float *nchw);
+int icl_embed_image_mem(icl_ctx *ctx, const uint8_t *data, int64_t bytes, int head, float *out);
+int icl_load_images_224_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int32_t threads,
+                                uint8_t *d_out /* n x 224x224x3 */, int32_t *status);
+int icl_embed_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec,
+                         int32_t threads, float *out, int32_t *status);
+int icl_embed_images_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec,
+                             int32_t threads, float *d_out, int32_t *status);
+int icl_cluster_requests_mem(icl_ctx *ctx, int32_t nreq, const uint8_t *const *data, const int64_t *bytes, const int32_t *n, const int32_t *n_labels,
+                             const int64_t *label_off /* sum n[r] + 1 */, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size,
+                             int head, int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
+                             int32_t *merges, int32_t *status /* nreq */, int32_t *file_status /* sum n[r] */, float *E_out);
+int icl_jpeg_coefs_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
+                       int64_t *offsets /* n + 1 */, int32_t *state /* n */);
 /* workflow.go:84-94 on one GPU in one call: embed n resident images (2048-d pooled head, into d_E: device, n x 2048) and
  * cluster them.  flags & ICL_FUSE_OVERLAP: the distance rows of already-embedded images are computed on a side stream of the
  * context while later batches embed (same kernels, same results as icl_embed_u8_dev + icl_cluster_dev, bit for bit). */
