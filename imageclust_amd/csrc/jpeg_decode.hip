@@ -1,4 +1,4 @@
-// jpeg_decode.hip -- host-only baseline JPEG decoder for the image-ingest step of the hot path.
+// jpeg_decode.hip -- host-only JPEG decoder (baseline and progressive) for the image-ingest step of the hot path.
 //
 // Replaces gocv.IMRead(imagePath, IMReadColor) in PreprocessImage
 //   (/root/reference/internal/embeddings/embeddings.go:50), i.e. OpenCV imgcodecs -> libjpeg(-turbo) with its default
@@ -55,12 +55,6 @@ struct huff_table {
             code <<= 1;
         }
     }
-};
-
-// the entropy decoder's view of a component: the stage-A output (icl_jpeg_component, jpeg_stage.h) plus scan state
-struct component : icl_jpeg_component {
-    int td = 0, ta = 0;
-    int pred = 0;
 };
 
 struct bit_reader {
@@ -191,27 +185,15 @@ const uint8_t *split_stream(const uint8_t *q, const uint8_t *e, size_t sb, icl_j
 
 } // namespace
 
-// a0 != nullptr: stage A0.  The same marker loop, but the first scan of a file the GPU entropy decoder takes is not decoded:
-// its tables, geometry and unstuffed stream go to *a0.  Returns A0_NOT_QUALIFIED for every other file.
-constexpr int A0_NOT_QUALIFIED = -1;
+constexpr int A0_NOT_QUALIFIED = -1; // stage A0's parser on a file the GPU entropy decoder does not take (stage_a below)
 static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J, icl_jpeg_a0 *a0 = nullptr, int sub_bits = 0);
 static int jpeg_stage_b_impl(const icl_jpeg_coefs &J, std::vector<uint8_t> &rgb);
 
-// Decodes a JPEG file held in memory to interleaved RGB.  rgb is resized to w*h*3.  No C++ exception may cross the C ABI
-// (cgo / ctypes would std::terminate the host process): allocation failures become status codes here.
-// orient receives the EXIF orientation tag (1..8; 1 when absent): cv::imread applies it after decoding (embeddings.go:50
-// passes IMReadColor without IMREAD_IGNORE_ORIENTATION), the caller does the same (image_io.hip icl_apply_exif_orientation).
-int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient)
+// No C++ exception may cross the C ABI (cgo / ctypes would std::terminate the host process): allocation failures become status codes here.
+template <class F> static int guarded(icl_ctx *ctx, const char *path, F body)
 {
-    orient = 1;
     try {
-        icl_jpeg_coefs J;
-        const int rc = jpeg_stage_a_impl(ctx, data, len, path, J);
-        W = J.W;
-        H = J.H;
-        if (rc) return rc;
-        orient = J.orient;
-        return jpeg_stage_b_impl(J, rgb);
+        return body();
     } catch (const std::bad_alloc &) {
         return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
     } catch (...) {
@@ -219,16 +201,27 @@ int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *p
     }
 }
 
+// Decodes a JPEG file held in memory to interleaved RGB.  rgb is resized to w*h*3.
+// orient receives the EXIF orientation tag (1..8; 1 when absent): cv::imread applies it after decoding (embeddings.go:50
+// passes IMReadColor without IMREAD_IGNORE_ORIENTATION), the caller does the same (image_io.hip icl_apply_exif_orientation).
+int icl_jpeg_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H, int &orient)
+{
+    orient = 1;
+    return guarded(ctx, path, [&]() -> int {
+        icl_jpeg_coefs J;
+        const int rc = jpeg_stage_a_impl(ctx, data, len, path, J);
+        W = J.W;
+        H = J.H;
+        if (rc) return rc;
+        orient = J.orient;
+        return jpeg_stage_b_impl(J, rgb);
+    });
+}
+
 int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J)
 {
     J.orient = 1;
-    try {
-        return jpeg_stage_a_impl(ctx, data, len, path, J);
-    } catch (const std::bad_alloc &) {
-        return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
-    } catch (...) {
-        return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Decoder error", path);
-    }
+    return guarded(ctx, path, [&]() -> int { return jpeg_stage_a_impl(ctx, data, len, path, J); });
 }
 
 int icl_jpeg_stage_a0(const uint8_t *data, size_t len, const char *path, int sub_bits, icl_jpeg_coefs &J, icl_jpeg_a0 &A, bool &qualifies)
@@ -410,13 +403,7 @@ int icl_jpeg_entropy_host_check(const uint8_t *data, size_t len, const char *pat
 
 int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, std::vector<uint8_t> &rgb)
 {
-    try {
-        return jpeg_stage_b_impl(J, rgb);
-    } catch (const std::bad_alloc &) {
-        return icl_fail(ctx, ICL_ERR_NOMEM, "failed to read image: %s. Out of host memory while decoding", path);
-    } catch (...) {
-        return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. Decoder error", path);
-    }
+    return guarded(ctx, path, [&]() -> int { return jpeg_stage_b_impl(J, rgb); });
 }
 
 // EXIF (APP1 "Exif\0\0" + TIFF header): orientation tag 0x0112 of IFD0, 1..8; anything malformed reads as 1.
@@ -447,334 +434,430 @@ static int exif_orientation(const uint8_t *s, size_t sl)
     return 1;
 }
 
-// Stage A: markers, tables, frame and scan headers, and every scan's entropy-coded data into J.comp[c].coefs.
-static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J, icl_jpeg_a0 *a0, int sub_bits)
+namespace {
+
+// Where the marker loop goes on after a scan: the next real marker (FF followed by anything but 00, RSTn or another FF) at or after q,
+// or the last byte when there is none.  split_stream ends the entropy-coded segment earlier or at the same place, at the first FF not
+// followed by 00 or RSTn: from there this search also passes FF FF fill bytes and whatever a damaged file holds before its next marker.
+const uint8_t *ecs_end(const uint8_t *q, const uint8_t *end)
 {
-    int &W = J.W, &H = J.H, &orient = J.orient;
-    auto fail = [&](int code, const char *what) { return icl_fail(ctx, code, "failed to read image: %s. %s", path, what); };
-    if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return fail(ICL_ERR_IO, "Not a JPEG stream");
+    while (q + 1 < end && !(q[0] == 0xFF && q[1] != 0x00 && !(q[1] >= 0xD0 && q[1] <= 0xD7) && q[1] != 0xFF)) ++q;
+    return q;
+}
+
+// a validated scan header: the frame's components it carries, its spectral band and successive-approximation bits
+struct scan_header {
+    int ns = 0, sc[3] = {0, 0, 0};
+    int Ss = 0, Se = 0, Ah = 0, Al = 0;
+};
+
+// what a scan header sets for a frame component, and its DC predictor
+struct comp_scan {
+    int td = 0, ta = 0;
+    int pred = 0;
+};
+
+// The entropy decoder of one scan.  One block of the scan into the coefficient array, by the scan's kind (T.81 F.2.2 sequential, G.1.2
+// progressive; the AC refinement pass follows the structure of IJG jdphuff.c decode_mcu_AC_refine); false: corrupt data.
+struct scan_state {
+    bit_reader br;
+    const huff_table *dc, *ac; // the four tables of each class
+    int Ss, Se, Al;
+    int eobrun = 0;
+
+    bool sequential(comp_scan &k, int16_t *cf)
+    {
+        const int t = huff_decode(br, dc[k.td]);
+        if (t < 0 || t > 15) return false;
+        k.pred += t ? extend(br.get(t), t) : 0;
+        cf[0] = (int16_t)k.pred;
+        for (int i = 1; i < 64;) {
+            const int rs = huff_decode(br, ac[k.ta]);
+            if (rs < 0) return false;
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz == 0) {
+                if (r == 15) { i += 16; continue; }
+                break;
+            }
+            i += r;
+            if (i > 63) return false;
+            cf[icl_zigzag[i]] = (int16_t)extend(br.get(sz), sz);
+            ++i;
+        }
+        return true;
+    }
+    bool dc_first(comp_scan &k, int16_t *cf)
+    {
+        const int t = huff_decode(br, dc[k.td]);
+        if (t < 0 || t > 15) return false;
+        k.pred += t ? extend(br.get(t), t) : 0;
+        cf[0] = (int16_t)(k.pred * (1 << Al));
+        return true;
+    }
+    bool dc_refine(comp_scan &, int16_t *cf) // one more bit
+    {
+        if (br.get(1)) cf[0] = (int16_t)(cf[0] | (1 << Al));
+        return true;
+    }
+    bool ac_first(comp_scan &k, int16_t *cf)
+    {
+        if (eobrun > 0) { --eobrun; return true; }
+        for (int i = Ss; i <= Se;) {
+            const int rs = huff_decode(br, ac[k.ta]);
+            if (rs < 0) return false;
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz == 0) {
+                if (r == 15) { i += 16; continue; }
+                eobrun = (1 << r) - 1;
+                if (r) eobrun += br.get(r);
+                break;
+            }
+            i += r;
+            if (i > Se) return false;
+            cf[icl_zigzag[i]] = (int16_t)(extend(br.get(sz), sz) * (1 << Al));
+            ++i;
+        }
+        return true;
+    }
+    bool ac_refine(comp_scan &k, int16_t *cf)
+    {
+        const int p1 = 1 << Al, m1 = -(1 << Al);
+        int i = Ss;
+        auto refine = [&](int16_t &c) {
+            if (br.get(1) && (c & p1) == 0) c = (int16_t)(c + (c >= 0 ? p1 : m1));
+        };
+        if (eobrun == 0) {
+            for (; i <= Se; ++i) {
+                const int rs = huff_decode(br, ac[k.ta]);
+                if (rs < 0) return false;
+                int r = rs >> 4, sv = rs & 15;
+                if (sv) {
+                    if (sv != 1) return false;
+                    sv = br.get(1) ? p1 : m1;
+                } else if (r != 15) { // EOBr: the rest of this block (and eobrun-1 more) only gets correction bits
+                    eobrun = 1 << r;
+                    if (r) eobrun += br.get(r);
+                    break;
+                }
+                // skip r ZERO-history coefficients (ZRL: 16), refining the non-zero ones passed on the way
+                for (; i <= Se; ++i) {
+                    int16_t &c = cf[icl_zigzag[i]];
+                    if (c != 0) refine(c);
+                    else if (--r < 0) break;
+                }
+                if (sv) {
+                    if (i > Se) return false;
+                    cf[icl_zigzag[i]] = (int16_t)sv;
+                }
+            }
+        }
+        if (eobrun > 0) {
+            for (; i <= Se; ++i) {
+                int16_t &c = cf[icl_zigzag[i]];
+                if (c != 0) refine(c);
+            }
+            --eobrun;
+        }
+        return true;
+    }
+};
+
+// Stage A: markers, tables, frame and scan headers, and every scan's entropy-coded data into J.comp[c].coefs.  The parser owns what
+// holds from one marker to the next; each marker's member reads its segment (s, sl) alone.  Frame geometry, W / H and the orientation
+// go to J as they are read (no caller reads J after a failure); ncomp, qt and is_rgb are committed at the end.
+// a0 != nullptr: stage A0.  The same marker loop, but the first scan of a file the GPU entropy decoder takes is not decoded:
+// its tables, geometry and unstuffed stream go to *a0.  Returns A0_NOT_QUALIFIED for every other file.
+struct stage_a {
+    icl_ctx *ctx; // the call: where messages go, what they call the image, its bytes, where the result goes
+    const char *path;
+    const uint8_t *data;
+    size_t len;
+    icl_jpeg_coefs &J;
+    icl_jpeg_a0 *a0;
+    int sub_bits;
+    // what holds from one marker to the next
     uint16_t qt[4][64];
     bool qt_ok[4] = {false, false, false, false};
     huff_table dc[4], ac[4];
-    component comp[3];
-    for (int c = 0; c < 3; ++c) comp[c].coefs.swap(J.comp[c].coefs); // decode into J's arrays (a reused J keeps their capacity)
-    if (a0)
-        for (int c = 0; c < 3; ++c) comp[c].coefs.clear(); // stage A0 leaves no coefficients
+    comp_scan comp[3];
     int ncomp = 0, restart = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0, nscans = 0;
     bool have_sof = false, adobe = false, progressive = false;
     int adobe_transform = -1;
-    size_t pos = 2;
-    W = H = 0;
-    while (pos + 4 <= len) {
-        if (data[pos] != 0xFF) { ++pos; continue; }
-        const int m = data[pos + 1];
-        if (m == 0xFF) { ++pos; continue; }
-        pos += 2;
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9) break;
-        if (pos + 2 > len) break;
-        const size_t seglen = ((size_t)data[pos] << 8) | data[pos + 1];
-        if (seglen < 2 || pos + seglen > len) return fail(ICL_ERR_IO, "The image file might be corrupt or unreadable");
-        const uint8_t *s = data + pos + 2;
-        const size_t sl = seglen - 2;
-        if (m == 0xDB) { // DQT
-            size_t i = 0;
-            while (i < sl) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                ++i;
-                if (tq > 3 || i + (pq ? 128 : 64) > sl) return fail(ICL_ERR_IO, "Bad quantization table");
-                for (int k = 0; k < 64; ++k) {
-                    qt[tq][icl_zigzag[k]] = pq ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
-                    i += pq ? 2 : 1;
-                }
-                qt_ok[tq] = true;
+
+    int fail(int code, const char *what) const { return icl_fail(ctx, code, "failed to read image: %s. %s", path, what); }
+
+    int dqt(const uint8_t *s, size_t sl)
+    {
+        size_t i = 0;
+        while (i < sl) {
+            const int pq = s[i] >> 4, tq = s[i] & 15;
+            ++i;
+            if (tq > 3 || i + (pq ? 128 : 64) > sl) return fail(ICL_ERR_IO, "Bad quantization table");
+            for (int k = 0; k < 64; ++k) {
+                qt[tq][icl_zigzag[k]] = pq ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
+                i += pq ? 2 : 1;
             }
-        } else if (m == 0xC4) { // DHT
-            size_t i = 0;
-            while (i + 17 <= sl) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 3) return fail(ICL_ERR_IO, "Bad Huffman table");
-                huff_table &t = tc ? ac[th] : dc[th];
-                int total = 0;
-                t.bits[0] = 0;
-                for (int l = 1; l <= 16; ++l) { t.bits[l] = s[i + l]; total += t.bits[l]; }
-                i += 17;
-                if (total > 256 || i + total > sl) return fail(ICL_ERR_IO, "Bad Huffman table");
-                // the counts must form a prefix code (as IJG jdhuff.c checks): at every length the codes handed out so
-                // far fit in l bits -- otherwise build()'s lookahead index runs past fast[512] (over-subscribed table)
-                for (int l = 1, code = 0; l <= 16; ++l) {
-                    code += t.bits[l];
-                    if (code > (1 << l)) return fail(ICL_ERR_IO, "Bad Huffman table");
-                    code <<= 1;
-                }
-                memcpy(t.vals, s + i, (size_t)total);
-                i += total;
-                t.present = true;
-                t.build();
-            }
-        } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) { // SOF0 / SOF1 / SOF2
-            if (have_sof) return fail(ICL_ERR_IO, "Second frame header");
-            if (sl < 6 || s[0] != 8) return fail(ICL_ERR_UNSUPPORTED, "Only 8-bit JPEG is decoded");
-            progressive = m == 0xC2;
-            H = (s[1] << 8) | s[2];
-            W = (s[3] << 8) | s[4];
-            ncomp = s[5];
-            if ((ncomp != 1 && ncomp != 3) || sl < (size_t)(6 + 3 * ncomp) || W <= 0 || H <= 0 || W > 32768 || H > 32768)
-                return fail(ICL_ERR_UNSUPPORTED, "Only 1- or 3-component JPEG is decoded");
-            // sizes come from the file: bound what they make us allocate (coefficients + planes + RGB, ~11 B per pixel)
-            if ((int64_t)W * H > ICL_JPEG_MAX_PIXELS) return fail(ICL_ERR_UNSUPPORTED, "JPEG larger than 64 Mpixel is not decoded");
-            for (int c = 0; c < ncomp; ++c) {
-                comp[c].id = s[6 + 3 * c];
-                comp[c].h = s[7 + 3 * c] >> 4;
-                comp[c].v = s[7 + 3 * c] & 15;
-                comp[c].tq = s[8 + 3 * c];
-            }
-            if (ncomp == 1) comp[0].h = comp[0].v = 1;
-            if (ncomp == 3) {
-                const bool ok = comp[1].h == 1 && comp[1].v == 1 && comp[2].h == 1 && comp[2].v == 1 && icl_luma_sampling_ok(comp[0].h, comp[0].v);
-                if (!ok) {
-                    char what[160];
-                    snprintf(what, sizeof what, "Sampling %dx%d,%dx%d,%dx%d is not decoded (only luma 1x1, 2x1, 2x2, 1x2, 4x1 or 1x4 over 1x1 chroma)", comp[0].h,
-                             comp[0].v, comp[1].h, comp[1].v, comp[2].h, comp[2].v);
-                    return fail(ICL_ERR_UNSUPPORTED, what);
-                }
-            }
-            for (int c = 0; c < ncomp; ++c) {
-                hmax = std::max(hmax, comp[c].h);
-                vmax = std::max(vmax, comp[c].v);
-            }
-            mcux = (W + 8 * hmax - 1) / (8 * hmax);
-            mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-            for (int c = 0; c < ncomp; ++c) {
-                component &k = comp[c];
-                k.wblocks = mcux * k.h;
-                k.hblocks = mcuy * k.v;
-                k.dw = (W * k.h + hmax - 1) / hmax;
-                k.dh = (H * k.v + vmax - 1) / vmax;
-                if (!a0) k.coefs.assign((size_t)k.wblocks * k.hblocks * 64, 0);
-            }
-            have_sof = true;
-        } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            return fail(ICL_ERR_UNSUPPORTED, "Lossless / hierarchical / arithmetic-coded JPEG is not decoded by this build");
-        } else if (m == 0xDD) {
-            if (sl >= 2) restart = (s[0] << 8) | s[1];
-        } else if (m == 0xE1) {
-            if (orient == 1) orient = exif_orientation(s, sl); // the first APP1/Exif segment decides, as in OpenCV's ExifReader
-        } else if (m == 0xEE) {
-            if (sl >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; }
-        } else if (m == 0xDA) { // SOS: one scan (a baseline file has one or ncomp of them, a progressive file many)
-            if (!have_sof) return fail(ICL_ERR_IO, "Scan before frame header");
-            if (sl < 1) return fail(ICL_ERR_IO, "Bad scan header");
-            const int ns = s[0];
-            if (ns < 1 || ns > ncomp || sl < (size_t)(1 + 2 * ns + 3)) return fail(ICL_ERR_IO, "Bad scan header");
-            int sc[3];
-            for (int i = 0; i < ns; ++i) {
-                int ci = -1;
-                for (int c = 0; c < ncomp; ++c)
-                    if (comp[c].id == s[1 + 2 * i]) ci = c;
-                if (ci < 0) return fail(ICL_ERR_IO, "Bad scan component");
-                comp[ci].td = s[2 + 2 * i] >> 4;
-                comp[ci].ta = s[2 + 2 * i] & 15;
-                sc[i] = ci;
-            }
-            const int Ss = s[1 + 2 * ns], Se = s[2 + 2 * ns], Ah = s[3 + 2 * ns] >> 4, Al = s[3 + 2 * ns] & 15;
-            if (progressive) {
-                const bool ok = Ss <= Se && Se <= 63 && Al <= 13 && (Ss == 0 ? Se == 0 : ns == 1) && (Ah == 0 || Ah == Al + 1);
-                if (!ok) return fail(ICL_ERR_IO, "Bad progressive scan parameters");
-            } else if (Ss != 0 || Se != 63 || Ah != 0 || Al != 0) {
-                return fail(ICL_ERR_IO, "Bad sequential scan parameters");
-            }
-            for (int i = 0; i < ns; ++i) {
-                const component &k = comp[sc[i]];
-                const bool need_dc = Ss == 0 && Ah == 0, need_ac = Se > 0;
-                if (k.td > 3 || k.ta > 3 || (need_dc && !dc[k.td].present) || (need_ac && !ac[k.ta].present)) return fail(ICL_ERR_IO, "Missing table");
-                comp[sc[i]].pred = 0;
-            }
-            if (a0) { // stage A0: one sequential scan that carries all components in frame order, or the file takes the usual route
-                if (progressive || nscans > 0 || ns != ncomp || len >= ((size_t)1 << 28)) return A0_NOT_QUALIFIED;
-                for (int i = 0; i < ns; ++i)
-                    if (sc[i] != i) return A0_NOT_QUALIFIED;
-                icl_je_scan &S = a0->scan;
-                S = icl_je_scan();
-                S.ncomp = ncomp;
-                S.hs = comp[0].h;
-                S.vs = comp[0].v;
-                S.bpm = ncomp == 1 ? 1 : S.hs * S.vs + 2;
-                S.mcux = mcux;
-                S.mcuy = mcuy;
-                S.restart = restart;
-                S.sub_bits = sub_bits;
-                for (int c = 0; c < ncomp; ++c) {
-                    S.wblocks[c] = comp[c].wblocks;
-                    S.hblocks[c] = comp[c].hblocks;
-                    copy_table(dc[comp[c].td], a0->tables[2 * c]);
-                    copy_table(ac[comp[c].ta], a0->tables[2 * c + 1]);
-                }
-                S.uniform = ncomp == 3 ? 1 : 0;
-                for (int c = 1; c < ncomp; ++c)
-                    if (memcmp(&a0->tables[0], &a0->tables[2 * c], sizeof(icl_je_table)) || memcmp(&a0->tables[1], &a0->tables[2 * c + 1], sizeof(icl_je_table))) S.uniform = 0;
-                const uint8_t *q = split_stream(data + pos + seglen, data + len, (size_t)sub_bits / 8, *a0);
-                S.nintervals = (int32_t)a0->intervals.size();
-                ++nscans;
-                // continue at the marker that ended the entropy-coded segment (the search of the decoding branch below, from the segment's end)
-                while (q + 1 < data + len && !(q[0] == 0xFF && q[1] != 0x00 && !(q[1] >= 0xD0 && q[1] <= 0xD7) && q[1] != 0xFF)) ++q;
-                pos = (size_t)(q - data);
-                continue;
-            }
-            bit_reader br{data + pos + seglen, data + len};
-            int eobrun = 0;
-            // one block of one scan into the coefficient array (T.81 F.2.2 sequential, G.1.2 progressive; the
-            // refinement pass follows the structure of IJG jdphuff.c decode_mcu_AC_refine)
-            auto decode_block = [&](component &k, int16_t *cf) -> bool {
-                if (!progressive) {
-                    const int t = huff_decode(br, dc[k.td]);
-                    if (t < 0 || t > 15) return false;
-                    k.pred += t ? extend(br.get(t), t) : 0;
-                    cf[0] = (int16_t)k.pred;
-                    for (int i = 1; i < 64;) {
-                        const int rs = huff_decode(br, ac[k.ta]);
-                        if (rs < 0) return false;
-                        const int r = rs >> 4, sz = rs & 15;
-                        if (sz == 0) {
-                            if (r == 15) { i += 16; continue; }
-                            break;
-                        }
-                        i += r;
-                        if (i > 63) return false;
-                        cf[icl_zigzag[i]] = (int16_t)extend(br.get(sz), sz);
-                        ++i;
-                    }
-                    return true;
-                }
-                if (Ss == 0) {
-                    if (Ah == 0) { // DC first
-                        const int t = huff_decode(br, dc[k.td]);
-                        if (t < 0 || t > 15) return false;
-                        k.pred += t ? extend(br.get(t), t) : 0;
-                        cf[0] = (int16_t)(k.pred * (1 << Al));
-                    } else if (br.get(1)) { // DC refinement: one more bit
-                        cf[0] = (int16_t)(cf[0] | (1 << Al));
-                    }
-                    return true;
-                }
-                if (Ah == 0) { // AC first
-                    if (eobrun > 0) { --eobrun; return true; }
-                    for (int i = Ss; i <= Se;) {
-                        const int rs = huff_decode(br, ac[k.ta]);
-                        if (rs < 0) return false;
-                        const int r = rs >> 4, sz = rs & 15;
-                        if (sz == 0) {
-                            if (r == 15) { i += 16; continue; }
-                            eobrun = (1 << r) - 1;
-                            if (r) eobrun += br.get(r);
-                            break;
-                        }
-                        i += r;
-                        if (i > Se) return false;
-                        cf[icl_zigzag[i]] = (int16_t)(extend(br.get(sz), sz) * (1 << Al));
-                        ++i;
-                    }
-                    return true;
-                }
-                // AC refinement
-                const int p1 = 1 << Al, m1 = -(1 << Al);
-                int i = Ss;
-                auto refine = [&](int16_t &c) {
-                    if (br.get(1) && (c & p1) == 0) c = (int16_t)(c + (c >= 0 ? p1 : m1));
-                };
-                if (eobrun == 0) {
-                    for (; i <= Se; ++i) {
-                        const int rs = huff_decode(br, ac[k.ta]);
-                        if (rs < 0) return false;
-                        int r = rs >> 4, sv = rs & 15;
-                        if (sv) {
-                            if (sv != 1) return false;
-                            sv = br.get(1) ? p1 : m1;
-                        } else if (r != 15) { // EOBr: the rest of this block (and eobrun-1 more) only gets correction bits
-                            eobrun = 1 << r;
-                            if (r) eobrun += br.get(r);
-                            break;
-                        }
-                        // skip r ZERO-history coefficients (ZRL: 16), refining the non-zero ones passed on the way
-                        for (; i <= Se; ++i) {
-                            int16_t &c = cf[icl_zigzag[i]];
-                            if (c != 0) refine(c);
-                            else if (--r < 0) break;
-                        }
-                        if (sv) {
-                            if (i > Se) return false;
-                            cf[icl_zigzag[i]] = (int16_t)sv;
-                        }
-                    }
-                }
-                if (eobrun > 0) {
-                    for (; i <= Se; ++i) {
-                        int16_t &c = cf[icl_zigzag[i]];
-                        if (c != 0) refine(c);
-                    }
-                    --eobrun;
-                }
-                return true;
-            };
-            auto do_restart = [&]() -> bool {
-                const uint8_t *q = br.p; // byte-align, expect RSTn
-                while (q + 1 < br.end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
-                if (q + 1 >= br.end) return false;
-                br.p = q + 2;
-                br.reset();
-                for (int c = 0; c < ncomp; ++c) comp[c].pred = 0;
-                eobrun = 0;
-                return true;
-            };
-            int rst_left = restart;
-            if (ns == 1) { // non-interleaved: the component's own block raster, one block per "MCU"
-                component &k = comp[sc[0]];
-                const int bw = (k.dw + 7) / 8, bh = (k.dh + 7) / 8;
-                for (int by = 0; by < bh; ++by)
-                    for (int bx = 0; bx < bw; ++bx) {
-                        if (restart && rst_left == 0) {
-                            if (!do_restart()) return fail(ICL_ERR_IO, "Missing restart marker");
-                            rst_left = restart;
-                        }
-                        if (!decode_block(k, k.coefs.data() + ((size_t)by * k.wblocks + bx) * 64)) return fail(ICL_ERR_IO, "Corrupt JPEG data");
-                        if (restart) --rst_left;
-                    }
-            } else {
-                for (int my = 0; my < mcuy; ++my)
-                    for (int mx = 0; mx < mcux; ++mx) {
-                        if (restart && rst_left == 0) {
-                            if (!do_restart()) return fail(ICL_ERR_IO, "Missing restart marker");
-                            rst_left = restart;
-                        }
-                        for (int i = 0; i < ns; ++i) {
-                            component &k = comp[sc[i]];
-                            for (int by = 0; by < k.v; ++by)
-                                for (int bx = 0; bx < k.h; ++bx)
-                                    if (!decode_block(k, k.coefs.data() + ((size_t)(my * k.v + by) * k.wblocks + (mx * k.h + bx)) * 64))
-                                        return fail(ICL_ERR_IO, "Corrupt JPEG data");
-                        }
-                        if (restart) --rst_left;
-                    }
-            }
-            ++nscans;
-            // continue at the marker that ended the entropy-coded segment
-            const uint8_t *q = br.p;
-            while (q + 1 < data + len && !(q[0] == 0xFF && q[1] != 0x00 && !(q[1] >= 0xD0 && q[1] <= 0xD7) && q[1] != 0xFF)) ++q;
-            pos = (size_t)(q - data);
-            continue;
+            qt_ok[tq] = true;
         }
-        pos += seglen;
+        return ICL_OK;
     }
-    if (!have_sof || nscans == 0) return fail(ICL_ERR_IO, "The image file might be corrupt or unreadable");
-    for (int c = 0; c < ncomp; ++c) {
-        component &k = comp[c];
-        if (k.tq > 3 || !qt_ok[k.tq]) return fail(ICL_ERR_IO, "Missing table");
-        memcpy(J.qt[c], qt[k.tq], sizeof J.qt[c]); // the table as it stands after the last scan (what dequantisation uses)
-        J.comp[c].swap_from(k);
+
+    int dht(const uint8_t *s, size_t sl)
+    {
+        size_t i = 0;
+        while (i + 17 <= sl) {
+            const int tc = s[i] >> 4, th = s[i] & 15;
+            if (tc > 1 || th > 3) return fail(ICL_ERR_IO, "Bad Huffman table");
+            huff_table &t = tc ? ac[th] : dc[th];
+            int total = 0;
+            t.bits[0] = 0;
+            for (int l = 1; l <= 16; ++l) { t.bits[l] = s[i + l]; total += t.bits[l]; }
+            i += 17;
+            if (total > 256 || i + total > sl) return fail(ICL_ERR_IO, "Bad Huffman table");
+            // the counts must form a prefix code (as IJG jdhuff.c checks): at every length the codes handed out so
+            // far fit in l bits -- otherwise build()'s lookahead index runs past fast[512] (over-subscribed table)
+            for (int l = 1, code = 0; l <= 16; ++l) {
+                code += t.bits[l];
+                if (code > (1 << l)) return fail(ICL_ERR_IO, "Bad Huffman table");
+                code <<= 1;
+            }
+            memcpy(t.vals, s + i, (size_t)total);
+            i += total;
+            t.present = true;
+            t.build();
+        }
+        return ICL_OK;
     }
-    J.ncomp = ncomp;
-    J.is_rgb = ncomp == 3 && ((adobe && adobe_transform == 0) || (!adobe && comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B'));
-    return ICL_OK;
+
+    int sof(int m, const uint8_t *s, size_t sl) // SOF0 / SOF1 / SOF2
+    {
+        int &W = J.W, &H = J.H;
+        icl_jpeg_component *k = J.comp;
+        if (have_sof) return fail(ICL_ERR_IO, "Second frame header");
+        if (sl < 6 || s[0] != 8) return fail(ICL_ERR_UNSUPPORTED, "Only 8-bit JPEG is decoded");
+        progressive = m == 0xC2;
+        H = (s[1] << 8) | s[2];
+        W = (s[3] << 8) | s[4];
+        ncomp = s[5];
+        if ((ncomp != 1 && ncomp != 3) || sl < (size_t)(6 + 3 * ncomp) || W <= 0 || H <= 0 || W > 32768 || H > 32768)
+            return fail(ICL_ERR_UNSUPPORTED, "Only 1- or 3-component JPEG is decoded");
+        // sizes come from the file: bound what they make us allocate (coefficients + planes + RGB, ~11 B per pixel)
+        if ((int64_t)W * H > ICL_JPEG_MAX_PIXELS) return fail(ICL_ERR_UNSUPPORTED, "JPEG larger than 64 Mpixel is not decoded");
+        for (int c = 0; c < ncomp; ++c) {
+            k[c].id = s[6 + 3 * c];
+            k[c].h = s[7 + 3 * c] >> 4;
+            k[c].v = s[7 + 3 * c] & 15;
+            k[c].tq = s[8 + 3 * c];
+        }
+        if (ncomp == 1) k[0].h = k[0].v = 1;
+        if (ncomp == 3 && !(k[1].h == 1 && k[1].v == 1 && k[2].h == 1 && k[2].v == 1 && icl_luma_sampling_ok(k[0].h, k[0].v))) {
+            char what[160];
+            snprintf(what, sizeof what, "Sampling %dx%d,%dx%d,%dx%d is not decoded (only luma 1x1, 2x1, 2x2, 1x2, 4x1 or 1x4 over 1x1 chroma)", k[0].h, k[0].v,
+                     k[1].h, k[1].v, k[2].h, k[2].v);
+            return fail(ICL_ERR_UNSUPPORTED, what);
+        }
+        for (int c = 0; c < ncomp; ++c) {
+            hmax = std::max(hmax, k[c].h);
+            vmax = std::max(vmax, k[c].v);
+        }
+        mcux = (W + 8 * hmax - 1) / (8 * hmax);
+        mcuy = (H + 8 * vmax - 1) / (8 * vmax);
+        for (int c = 0; c < ncomp; ++c) {
+            k[c].wblocks = mcux * k[c].h;
+            k[c].hblocks = mcuy * k[c].v;
+            k[c].dw = (W * k[c].h + hmax - 1) / hmax;
+            k[c].dh = (H * k[c].v + vmax - 1) / vmax;
+            if (!a0) k[c].coefs.assign((size_t)k[c].wblocks * k[c].hblocks * 64, 0);
+        }
+        have_sof = true;
+        return ICL_OK;
+    }
+
+    void dri(const uint8_t *s, size_t sl)
+    {
+        if (sl >= 2) restart = (s[0] << 8) | s[1];
+    }
+    void app1(const uint8_t *s, size_t sl) // the first APP1/Exif segment decides, as in OpenCV's ExifReader
+    {
+        if (J.orient == 1) J.orient = exif_orientation(s, sl);
+    }
+    void app14(const uint8_t *s, size_t sl)
+    {
+        if (sl >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; }
+    }
+
+    // SOS: one scan (a baseline file has one or ncomp of them, a progressive file many).  The entropy-coded segment follows the header
+    // at s + sl; next receives the marker that ended it.
+    int sos(const uint8_t *s, size_t sl, const uint8_t *&next)
+    {
+        if (!have_sof) return fail(ICL_ERR_IO, "Scan before frame header");
+        if (sl < 1) return fail(ICL_ERR_IO, "Bad scan header");
+        scan_header h;
+        h.ns = s[0];
+        if (h.ns < 1 || h.ns > ncomp || sl < (size_t)(1 + 2 * h.ns + 3)) return fail(ICL_ERR_IO, "Bad scan header");
+        for (int i = 0; i < h.ns; ++i) {
+            int ci = -1;
+            for (int c = 0; c < ncomp; ++c)
+                if (J.comp[c].id == s[1 + 2 * i]) ci = c;
+            if (ci < 0) return fail(ICL_ERR_IO, "Bad scan component");
+            comp[ci].td = s[2 + 2 * i] >> 4;
+            comp[ci].ta = s[2 + 2 * i] & 15;
+            h.sc[i] = ci;
+        }
+        h.Ss = s[1 + 2 * h.ns];
+        h.Se = s[2 + 2 * h.ns];
+        h.Ah = s[3 + 2 * h.ns] >> 4;
+        h.Al = s[3 + 2 * h.ns] & 15;
+        if (progressive) {
+            const bool ok = h.Ss <= h.Se && h.Se <= 63 && h.Al <= 13 && (h.Ss == 0 ? h.Se == 0 : h.ns == 1) && (h.Ah == 0 || h.Ah == h.Al + 1);
+            if (!ok) return fail(ICL_ERR_IO, "Bad progressive scan parameters");
+        } else if (h.Ss != 0 || h.Se != 63 || h.Ah != 0 || h.Al != 0) {
+            return fail(ICL_ERR_IO, "Bad sequential scan parameters");
+        }
+        for (int i = 0; i < h.ns; ++i) {
+            comp_scan &k = comp[h.sc[i]];
+            const bool need_dc = h.Ss == 0 && h.Ah == 0, need_ac = h.Se > 0;
+            if (k.td > 3 || k.ta > 3 || (need_dc && !dc[k.td].present) || (need_ac && !ac[k.ta].present)) return fail(ICL_ERR_IO, "Missing table");
+            k.pred = 0;
+        }
+        const int rc = a0 ? capture_scan(h, s + sl, next) : decode_scan(h, s + sl, next);
+        if (rc == ICL_OK) ++nscans;
+        return rc;
+    }
+
+    // stage A0: one sequential scan that carries all components in frame order, or the file takes the usual route
+    int capture_scan(const scan_header &h, const uint8_t *ecs, const uint8_t *&next)
+    {
+        if (progressive || nscans > 0 || h.ns != ncomp || len >= ((size_t)1 << 28)) return A0_NOT_QUALIFIED;
+        for (int i = 0; i < h.ns; ++i)
+            if (h.sc[i] != i) return A0_NOT_QUALIFIED;
+        icl_je_scan &S = a0->scan;
+        S = icl_je_scan();
+        S.ncomp = ncomp;
+        S.hs = J.comp[0].h;
+        S.vs = J.comp[0].v;
+        S.bpm = ncomp == 1 ? 1 : S.hs * S.vs + 2;
+        S.mcux = mcux;
+        S.mcuy = mcuy;
+        S.restart = restart;
+        S.sub_bits = sub_bits;
+        for (int c = 0; c < ncomp; ++c) {
+            S.wblocks[c] = J.comp[c].wblocks;
+            S.hblocks[c] = J.comp[c].hblocks;
+            copy_table(dc[comp[c].td], a0->tables[2 * c]);
+            copy_table(ac[comp[c].ta], a0->tables[2 * c + 1]);
+        }
+        S.uniform = ncomp == 3 ? 1 : 0;
+        for (int c = 1; c < ncomp; ++c)
+            if (memcmp(&a0->tables[0], &a0->tables[2 * c], sizeof(icl_je_table)) || memcmp(&a0->tables[1], &a0->tables[2 * c + 1], sizeof(icl_je_table))) S.uniform = 0;
+        const uint8_t *q = split_stream(ecs, data + len, (size_t)sub_bits / 8, *a0);
+        S.nintervals = (int32_t)a0->intervals.size();
+        next = ecs_end(q, data + len);
+        return ICL_OK;
+    }
+
+    // the decoder of the scan's kind, chosen once, over all its blocks
+    int decode_scan(const scan_header &h, const uint8_t *ecs, const uint8_t *&next)
+    {
+        scan_state S{bit_reader{ecs, data + len}, dc, ac, h.Ss, h.Se, h.Al};
+        int rc;
+        if (!progressive) rc = walk<&scan_state::sequential>(h, S);
+        else if (h.Ss == 0) rc = h.Ah == 0 ? walk<&scan_state::dc_first>(h, S) : walk<&scan_state::dc_refine>(h, S);
+        else rc = h.Ah == 0 ? walk<&scan_state::ac_first>(h, S) : walk<&scan_state::ac_refine>(h, S);
+        if (rc == ICL_OK) next = ecs_end(S.br.p, data + len);
+        return rc;
+    }
+
+    // The scan's MCUs in order, with the restart step between intervals.  An interleaved scan (ns > 1) walks the frame's MCUs, h x v
+    // blocks of each component; a scan of one component walks that component's own block raster, one block per "MCU".
+    template <bool (scan_state::*Block)(comp_scan &, int16_t *)> int walk(const scan_header &h, scan_state &S)
+    {
+        const bool own = h.ns == 1;
+        const icl_jpeg_component &k0 = J.comp[h.sc[0]];
+        const int ny = own ? (k0.dh + 7) / 8 : mcuy, nx = own ? (k0.dw + 7) / 8 : mcux;
+        int rst_left = restart;
+        for (int my = 0; my < ny; ++my)
+            for (int mx = 0; mx < nx; ++mx) {
+                if (restart && rst_left == 0) {
+                    if (!next_interval(S)) return fail(ICL_ERR_IO, "Missing restart marker");
+                    rst_left = restart;
+                }
+                for (int i = 0; i < h.ns; ++i) {
+                    icl_jpeg_component &k = J.comp[h.sc[i]];
+                    const int bh = own ? 1 : k.v, bw = own ? 1 : k.h;
+                    for (int by = 0; by < bh; ++by)
+                        for (int bx = 0; bx < bw; ++bx)
+                            if (!(S.*Block)(comp[h.sc[i]], k.coefs.data() + ((size_t)(my * bh + by) * k.wblocks + (mx * bw + bx)) * 64))
+                                return fail(ICL_ERR_IO, "Corrupt JPEG data");
+                }
+                if (restart) --rst_left;
+            }
+        return ICL_OK;
+    }
+
+    bool next_interval(scan_state &S) // byte-align, expect RSTn
+    {
+        const uint8_t *q = S.br.p;
+        while (q + 1 < S.br.end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
+        if (q + 1 >= S.br.end) return false;
+        S.br.p = q + 2;
+        S.br.reset();
+        for (int c = 0; c < ncomp; ++c) comp[c].pred = 0;
+        S.eobrun = 0;
+        return true;
+    }
+
+    int run()
+    {
+        if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return fail(ICL_ERR_IO, "Not a JPEG stream");
+        if (a0)
+            for (int c = 0; c < 3; ++c) J.comp[c].coefs.clear(); // stage A0 leaves no coefficients
+        J.W = J.H = 0;
+        size_t pos = 2;
+        while (pos + 4 <= len) {
+            if (data[pos] != 0xFF) { ++pos; continue; }
+            const int m = data[pos + 1];
+            if (m == 0xFF) { ++pos; continue; }
+            pos += 2;
+            if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+            if (m == 0xD9) break;
+            if (pos + 2 > len) break;
+            const size_t seglen = ((size_t)data[pos] << 8) | data[pos + 1];
+            if (seglen < 2 || pos + seglen > len) return fail(ICL_ERR_IO, "The image file might be corrupt or unreadable");
+            const uint8_t *s = data + pos + 2, *next = data + pos + seglen;
+            const size_t sl = seglen - 2;
+            int rc = ICL_OK;
+            switch (m) {
+            case 0xDB: rc = dqt(s, sl); break;
+            case 0xC4: rc = dht(s, sl); break;
+            case 0xC0: case 0xC1: case 0xC2: rc = sof(m, s, sl); break;
+            case 0xDD: dri(s, sl); break;
+            case 0xE1: app1(s, sl); break;
+            case 0xEE: app14(s, sl); break;
+            case 0xDA: rc = sos(s, sl, next); break;
+            default:
+                if (m >= 0xC3 && m <= 0xCF && m != 0xC8 && m != 0xCC)
+                    rc = fail(ICL_ERR_UNSUPPORTED, "Lossless / hierarchical / arithmetic-coded JPEG is not decoded by this build");
+            }
+            if (rc) return rc;
+            pos = (size_t)(next - data);
+        }
+        if (!have_sof || nscans == 0) return fail(ICL_ERR_IO, "The image file might be corrupt or unreadable");
+        for (int c = 0; c < ncomp; ++c) {
+            if (J.comp[c].tq > 3 || !qt_ok[J.comp[c].tq]) return fail(ICL_ERR_IO, "Missing table");
+            memcpy(J.qt[c], qt[J.comp[c].tq], sizeof J.qt[c]); // the table as it stands after the last scan (what dequantisation uses)
+        }
+        J.ncomp = ncomp;
+        J.is_rgb = ncomp == 3 && ((adobe && adobe_transform == 0) || (!adobe && J.comp[0].id == 'R' && J.comp[1].id == 'G' && J.comp[2].id == 'B'));
+        return ICL_OK;
+    }
+};
+
+} // namespace
+
+static int jpeg_stage_a_impl(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J, icl_jpeg_a0 *a0, int sub_bits)
+{
+    return stage_a{ctx, path, data, len, J, a0, sub_bits}.run();
 }
 
 // Stage B: dequantise + inverse DCT (once, after the last scan), chroma upsampling, colour conversion.

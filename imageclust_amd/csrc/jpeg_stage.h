@@ -18,12 +18,6 @@ struct icl_jpeg_component {
     int wblocks = 0, hblocks = 0; // padded to whole MCUs
     int dw = 0, dh = 0;           // downsampled_width / _height (real samples)
     std::vector<int16_t> coefs;   // wblocks*hblocks blocks of 64, natural order, NOT dequantised
-    void swap_from(icl_jpeg_component &o)
-    {
-        id = o.id; h = o.h; v = o.v; tq = o.tq;
-        wblocks = o.wblocks; hblocks = o.hblocks; dw = o.dw; dh = o.dh;
-        coefs.swap(o.coefs);
-    }
 };
 
 struct icl_jpeg_coefs {
@@ -35,7 +29,10 @@ struct icl_jpeg_coefs {
 };
 
 // Stage A.  Every check of a hostile file is made here; on success J holds a decodable image (1 or 3 components,
-// luma 1x1 / 2x1 / 2x2 / 1x2 / 4x1 / 1x4 over 1x1 chroma, at most ICL_JPEG_MAX_PIXELS).  J may be reused across calls (its coefficient arrays keep their capacity).
+// luma 1x1 / 2x1 / 2x2 / 1x2 / 4x1 / 1x4 over 1x1 chroma, at most ICL_JPEG_MAX_PIXELS).  J may be reused across calls: the scans decode
+// straight into its coefficient arrays, which keep their capacity whether a call succeeds or fails.  After a failure J holds whatever
+// the parser had read by then (frame geometry included); only a successful call leaves a J to read, and
+// then comp[0 .. ncomp-1] alone: a component at index ncomp or above is unspecified (it may hold an earlier file's).
 int icl_jpeg_stage_a(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, icl_jpeg_coefs &J);
 // Stage B on the host: interleaved RGB, W*H*3 (before the EXIF orientation).
 int icl_jpeg_stage_b(icl_ctx *ctx, const icl_jpeg_coefs &J, const char *path, std::vector<uint8_t> &rgb);
