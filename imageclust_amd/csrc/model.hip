@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <vector>
@@ -127,6 +128,79 @@ void icl_model_free(icl_ctx *ctx)
     ctx->model = nullptr;
 }
 
+// ---- the ICLW blob loader: parse a layer, pack it (resnet_pack.h), upload it ------------------------------------------------------------
+// one convolution's tensors in the blob: W (OIHW), bias (null without), then the BatchNorm's gamma, beta, running mean and variance
+struct blob_layer {
+    const float *W, *bias, *gamma, *beta, *mean, *var;
+};
+// a cursor over the blob's floats (their count is checked against the topology before the first read)
+struct blob_cursor {
+    const float *p;
+    const float *take(int64_t n) { return (p += n) - n; }
+    blob_layer layer(const icl_conv_rec &r, bool has_bias) // (a braced list is evaluated left to right: the blob's order)
+    {
+        return blob_layer{take((int64_t)r.cout * r.cin * r.k * r.k), has_bias ? take(r.cout) : nullptr, take(r.cout), take(r.cout), take(r.cout), take(r.cout)};
+    }
+};
+// a convolution as packed on the host: the fp32 weight rows in the kernels' layout and the folded BatchNorm
+struct packed_conv {
+    std::vector<float> w, scale, shift;
+};
+
+// One convolution: weights in every precision's storage, scale and shift, and the scale-folded bf16 copy of the fused kernels.
+// Leaves the packed fp32 form in pk.
+static int load_conv(icl_ctx *ctx, conv_layer &L, const icl_conv_rec &r, const blob_layer &b, float bn_eps, packed_conv &pk)
+{
+    const bool stem = r.role == 0;
+    L.rec = r;
+    L.K = stem ? STEM_K : r.cin * r.k * r.k;
+    if (stem) pack_stem_rows(b.W, pk.w);
+    else pack_ohwi(b.W, r.cout, r.cin, r.k, pk.w);
+    pack_bn_fold(b.gamma, b.beta, b.mean, b.var, b.bias, bn_eps, r.cout, pk.scale, pk.shift);
+    for (int prec : {ICL_PREC_FP32, ICL_PREC_BF16, ICL_PREC_BF16X3}) {
+        if (stem && prec == ICL_PREC_BF16X3) continue; // (the BF16X3 stem runs in fp32: ICL_PREC_FP32 weights)
+        ICL_TRY(upload_as(ctx, prec, &L.w[prec], pk.w.data(), pk.w.size()));
+    }
+    ICL_TRY(upload_as(ctx, ICL_PREC_FP32, (void **)&L.scale, pk.scale.data(), pk.scale.size()));
+    ICL_TRY(upload_as(ctx, ICL_PREC_FP32, (void **)&L.shift, pk.shift.data(), pk.shift.size()));
+    if (stem) { // stem2_pool_kernel
+        std::vector<uint16_t> ws;
+        pack_stem2(b.W, pk.scale.data(), ws);
+        ICL_TRY(upload(ctx, &L.wfold, ws.data(), ws.size() * 2));
+    }
+    if (r.stage == 1 && r.role >= 1 && r.role <= 3) { // the fused stage-1 bottleneck takes its BN scales inside the weights
+        std::vector<float> wf;
+        pack_row_scale(pk.w.data(), pk.scale.data(), r.cout, L.K, wf);
+        ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &L.wfold, wf.data(), wf.size()));
+    }
+    return ICL_OK;
+}
+
+// A stage's downsample branch fused into block 0's last convolution L3: y = relu(W3'.t2 + Wds'.x_strided + (sh3 + sh_ds))
+static int load_fused_ds(icl_ctx *ctx, conv_layer &L3, const packed_conv &c3, int k1, const packed_conv &ds, int k2)
+{
+    const int cout = L3.rec.cout;
+    std::vector<float> w3, wds, wf, sh((size_t)cout);
+    pack_row_scale(c3.w.data(), c3.scale.data(), cout, k1, w3);
+    pack_row_scale(ds.w.data(), ds.scale.data(), cout, k2, wds);
+    pack_row_concat(w3.data(), k1, wds.data(), k2, cout, wf);
+    for (int co = 0; co < cout; ++co) sh[(size_t)co] = c3.shift[(size_t)co] + ds.shift[(size_t)co];
+    for (int prec : {ICL_PREC_FP32, ICL_PREC_BF16, ICL_PREC_BF16X3}) ICL_TRY(upload_as(ctx, prec, &L3.wfused[prec], wf.data(), wf.size()));
+    return upload_as(ctx, ICL_PREC_FP32, (void **)&L3.shift_fused, sh.data(), sh.size());
+}
+
+// the dense head, and the constant pages of the kernels
+static int load_head(icl_ctx *ctx, icl_model *m, blob_cursor &cur)
+{
+    const std::vector<float> one(2048, 1.0f);
+    ICL_TRY(upload_as(ctx, ICL_PREC_FP32, (void **)&m->ones, one.data(), one.size()));
+    ICL_TRY(upload_as(ctx, ICL_PREC_FP32, (void **)&m->fcw, cur.take((int64_t)ICL_FC_OUT * ICL_FEAT_DIM), (size_t)ICL_FC_OUT * ICL_FEAT_DIM));
+    ICL_TRY(upload_as(ctx, ICL_PREC_FP32, (void **)&m->fcb, cur.take(ICL_FC_OUT), (size_t)ICL_FC_OUT));
+    ICL_HIP(ctx, hipMalloc(&m->zero, 256));
+    ICL_HIP(ctx, hipMemset(m->zero, 0, 256));
+    return ICL_OK;
+}
+
 extern "C" int icl_model_load_blob(icl_ctx *ctx, const void *blob, int64_t bytes)
 {
     if (!ctx || !blob) return icl_fail(ctx, ICL_ERR_ARG, "icl_model_load_blob: bad argument");
@@ -147,105 +221,15 @@ extern "C" int icl_model_load_blob(icl_ctx *ctx, const void *blob, int64_t bytes
         icl_model *m = own.get();
         icl_conv_rec t[ICL_RESNET50_NCONV];
         m->nconv = resnet50_topology(t);
-        const float *p = (const float *)((const char *)blob + sizeof h);
-        std::vector<float> wf;
-        std::vector<uint16_t> wb;
-        std::vector<float> sc, sh;
-        std::vector<std::vector<float>> hw((size_t)m->nconv), hsc((size_t)m->nconv), hsh((size_t)m->nconv); // host copies for the fusion below
+        blob_cursor cur{(const float *)((const char *)blob + sizeof h)};
+        packed_conv pk, src[4][2]; // src[stage - 1]: block 0's last convolution and its downsample layer, kept for the fusion below
         for (int i = 0; i < m->nconv; ++i) {
-            conv_layer &L = m->conv[i];
-            L.rec = t[i];
-            const int cin = t[i].cin, cout = t[i].cout, k = t[i].k;
-            const float *W = p;
-            p += (int64_t)cout * cin * k * k;
-            const float *bias = nullptr;
-            if (h.has_bias[i]) {
-                bias = p;
-                p += cout;
-            }
-            const float *gamma = p, *beta = p + cout, *mean = p + 2 * cout, *var = p + 3 * cout;
-            p += 4 * (int64_t)cout;
-            // re-pack OIHW -> [cout][kh][kw][cin] (stem: K padded 147 -> 160)
-            L.cin_eff = (i == 0) ? STEM_K : cin;
-            L.K = (i == 0) ? STEM_K : cin * k * k;
-            wf.assign((size_t)cout * L.K, 0.0f);
-            for (int co = 0; co < cout; ++co)
-                for (int c = 0; c < cin; ++c)
-                    for (int a = 0; a < k; ++a)
-                        for (int b = 0; b < k; ++b) {
-                            // stem: filter rows padded to 24 k-slots (stem_conv_kernel); others: [kh][kw][cin]
-                            const size_t kk = (i == 0) ? (size_t)a * STEM_ROWK + (size_t)b * 3 + c : ((size_t)a * k + b) * cin + c;
-                            wf[(size_t)co * L.K + kk] = W[(((size_t)co * cin + c) * k + a) * k + b];
-                        }
-            wb.resize(wf.size());
-            for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e]);
-            ICL_TRY(upload(ctx, &L.w[ICL_PREC_FP32], wf.data(), wf.size() * 4));
-            ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16], wb.data(), wb.size() * 2));
-            if (i > 0) { // (the BF16X3 stem runs in fp32: ICL_PREC_FP32 weights)
-                wb.resize(2 * wf.size());
-                host_split32(wf.data(), wf.size(), wb.data());
-                ICL_TRY(upload(ctx, &L.w[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
-            }
-            // BatchNormalization folded to y = x*scale + shift, conv bias folded into shift
-            sc.resize(cout);
-            sh.resize(cout);
-            for (int c = 0; c < cout; ++c) {
-                const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)h.bn_eps);
-                sc[c] = (float)s;
-                sh[c] = (float)((double)beta[c] - (double)mean[c] * s + (bias ? (double)bias[c] * s : 0.0));
-            }
-            ICL_TRY(upload(ctx, (void **)&L.scale, sc.data(), (size_t)cout * 4));
-            ICL_TRY(upload(ctx, (void **)&L.shift, sh.data(), (size_t)cout * 4));
-            if (i == 0) { // stem2_pool_kernel: [64][kh][8 kw slots][4 channel slots] = bf16(W * scale), zero in the padding
-                std::vector<uint16_t> ws((size_t)64 * ST2_K, 0);
-                for (int co = 0; co < 64; ++co)
-                    for (int c = 0; c < 3; ++c)
-                        for (int a = 0; a < 7; ++a)
-                            for (int b = 0; b < 7; ++b)
-                                ws[(size_t)co * ST2_K + (size_t)a * 32 + (size_t)b * 4 + c] = host_bf16(W[(((size_t)co * 3 + c) * 7 + a) * 7 + b] * sc[(size_t)co]);
-                ICL_TRY(upload(ctx, &L.wfold, ws.data(), ws.size() * 2));
-            }
-            if (t[i].stage == 1 && t[i].role >= 1 && t[i].role <= 3) { // the fused stage-1 bottleneck takes its BN scales inside the weights
-                for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e] * sc[e / (size_t)L.K]);
-                ICL_TRY(upload(ctx, &L.wfold, wb.data(), wb.size() * 2));
-            }
-            if (t[i].block == 0 && (t[i].role == 3 || t[i].role == 4)) {
-                hw[(size_t)i] = wf;
-                hsc[(size_t)i] = sc;
-                hsh[(size_t)i] = sh;
-            }
+            const bool kept = t[i].block == 0 && t[i].role >= 3;
+            ICL_TRY(load_conv(ctx, m->conv[i], t[i], cur.layer(t[i], h.has_bias[i] != 0), h.bn_eps, kept ? src[t[i].stage - 1][t[i].role - 3] : pk));
         }
-        // fuse each stage's downsample branch into block 0's last conv: y = relu(W3'.t2 + Wds'.x_strided + (sh3 + sh_ds))
-        for (int i = 0; i < m->nconv; ++i) {
-            if (!(t[i].block == 0 && t[i].role == 3)) continue;
-            const int ids = i + 1; // canonical order: c1, c2, c3, ds
-            const int cout = t[i].cout, k1 = t[i].cin, k2 = t[ids].cin, kk = k1 + k2;
-            wf.assign((size_t)cout * kk, 0.0f);
-            sh.resize((size_t)cout);
-            for (int co = 0; co < cout; ++co) {
-                for (int c = 0; c < k1; ++c) wf[(size_t)co * kk + c] = hw[(size_t)i][(size_t)co * k1 + c] * hsc[(size_t)i][(size_t)co];
-                for (int c = 0; c < k2; ++c) wf[(size_t)co * kk + k1 + c] = hw[(size_t)ids][(size_t)co * k2 + c] * hsc[(size_t)ids][(size_t)co];
-                sh[(size_t)co] = hsh[(size_t)i][(size_t)co] + hsh[(size_t)ids][(size_t)co];
-            }
-            wb.resize(wf.size());
-            for (size_t e = 0; e < wf.size(); ++e) wb[e] = host_bf16(wf[e]);
-            conv_layer &L = m->conv[i];
-            ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_FP32], wf.data(), wf.size() * 4));
-            ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16], wb.data(), wb.size() * 2));
-            wb.resize(2 * wf.size());
-            host_split32(wf.data(), wf.size(), wb.data());
-            ICL_TRY(upload(ctx, &L.wfused[ICL_PREC_BF16X3], wb.data(), wb.size() * 2));
-            ICL_TRY(upload(ctx, (void **)&L.shift_fused, sh.data(), (size_t)cout * 4));
-        }
-        {
-            std::vector<float> one(2048, 1.0f);
-            ICL_TRY(upload(ctx, (void **)&m->ones, one.data(), one.size() * 4));
-        }
-        ICL_TRY(upload(ctx, (void **)&m->fcw, p, (size_t)ICL_FC_OUT * ICL_FEAT_DIM * 4));
-        p += (int64_t)ICL_FC_OUT * ICL_FEAT_DIM;
-        ICL_TRY(upload(ctx, (void **)&m->fcb, p, (size_t)ICL_FC_OUT * 4));
-        ICL_HIP(ctx, hipMalloc(&m->zero, 256));
-        ICL_HIP(ctx, hipMemset(m->zero, 0, 256));
+        for (int i = 0; i < m->nconv; ++i) // canonical order: c1, c2, c3, ds
+            if (t[i].block == 0 && t[i].role == 3) ICL_TRY(load_fused_ds(ctx, m->conv[i], src[t[i].stage - 1][0], t[i].cin, src[t[i].stage - 1][1], t[i + 1].cin));
+        ICL_TRY(load_head(ctx, m, cur));
         ctx->model = own.release();
         return ICL_OK;
     });

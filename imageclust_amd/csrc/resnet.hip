@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <thread>
 #include <type_traits>
@@ -906,34 +907,48 @@ struct dev_buf {
     dev_buf &operator=(const dev_buf &) = delete;
     ~dev_buf() { if (p) (void)hipFree(p); }
 };
-// n fp32 values in the storage format of prec: rounded to bf16, split into hi / lo pairs (host_split32: the bytes of fp32), or as they are
-static int to_dev(icl_ctx *ctx, int prec, const float *src, size_t n, dev_buf &dst)
-{
-    ICL_HIP(ctx, hipMalloc(&dst.p, n * prec_act_bytes(prec)));
-    if (prec == ICL_PREC_FP32) {
-        ICL_HIP(ctx, hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
-        return ICL_OK;
-    }
-    std::vector<uint16_t> t(prec == ICL_PREC_BF16X3 ? 2 * n : n);
-    if (prec == ICL_PREC_BF16X3) host_split32(src, n, t.data());
-    else
-        for (size_t i = 0; i < n; ++i) t[i] = host_bf16(src[i]);
-    ICL_HIP(ctx, hipMemcpy(dst.p, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    return ICL_OK;
-}
-// ... and back (the stream that wrote src has been synchronised)
+// n values in the storage format of prec back to fp32 (unpack_storage; the stream that wrote src has been synchronised).  The other
+// direction is upload_as (resnet_model.h), the loader's own.
 static int from_dev(icl_ctx *ctx, int prec, const void *src, size_t n, float *dst)
 {
-    if (prec == ICL_PREC_FP32) {
-        ICL_HIP(ctx, hipMemcpy(dst, src, n * 4, hipMemcpyDeviceToHost));
-        return ICL_OK;
-    }
-    std::vector<uint16_t> t(prec == ICL_PREC_BF16X3 ? 2 * n : n);
+    std::vector<uint16_t> t(pack_storage_bytes(prec, n) / 2);
     ICL_HIP(ctx, hipMemcpy(t.data(), src, t.size() * 2, hipMemcpyDeviceToHost));
-    if (prec == ICL_PREC_BF16X3) host_join32(t.data(), n, dst);
-    else
-        for (size_t i = 0; i < n; ++i) dst[i] = host_from_bf16(t[i]);
+    unpack_storage(prec, t.data(), n, dst);
     return ICL_OK;
+}
+// the 256 zero bytes the convolution kernels read for padded taps (the loaded model has its own: icl_model::zero)
+static int zero_page(icl_ctx *ctx, const char *who, dev_buf &dz)
+{
+    if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: zero page", who);
+    return ICL_OK;
+}
+// What the body of an entry point leaves to run_entry: the device buffers it made, which live until the output has been copied back,
+// and that output: n values in the storage of prec, written on ctx->stream.
+struct entry_io {
+    std::deque<dev_buf> bufs;
+    dev_buf &buf() { return bufs.emplace_back(); }
+    const void *out = nullptr;
+    int prec = ICL_PREC_FP32;
+    size_t n = 0;
+    void returns(int p, const void *d, size_t count) { prec = p; out = d; n = count; }
+};
+// The scaffold of the five entry points: under ctx->mu and on the context's device (with a model loaded, where the body needs one), the
+// body uploads and launches on ctx->stream; the stream is synchronised whatever the body returned (its buffers are freed on return),
+// the output goes to y as fp32 and the profile events are collected.
+template <typename F>
+static int run_entry(icl_ctx *ctx, const char *who, bool need_model, float *y, F &&body)
+{
+    return no_throw(ctx, who, [&]() -> int {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        if (need_model && !ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
+        entry_io io;
+        int rc = body(io);
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (!rc) rc = e == hipSuccess ? from_dev(ctx, io.prec, io.out, io.n, y) : icl_fail(ctx, ICL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+        icl_prof_collect(ctx);
+        return rc;
+    });
 }
 
 extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int Cin, const float *w, int Cout, int k,
@@ -945,30 +960,20 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
     if (Cin % 64 || Cout % 64) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_fused needs Cin %% 64 == 0 and Cout %% 64 == 0");
     const int Ho = (H + 2 * pad - k) / stride + 1;
     if (Ho < 1) return icl_fail(ctx, ICL_ERR_ARG, "empty output");
-    return no_throw(ctx, "icl_conv2d_fused", [&]() -> int {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        const size_t nx = (size_t)B * H * H * Cin, nw = (size_t)Cout * Cin * k * k, ny = (size_t)B * Ho * Ho * Cout;
-        std::vector<float> wp(nw);
-        for (int co = 0; co < Cout; ++co)
-            for (int c = 0; c < Cin; ++c)
-                for (int a = 0; a < k; ++a)
-                    for (int b = 0; b < k; ++b) wp[(size_t)co * Cin * k * k + ((size_t)a * k + b) * Cin + c] = w[(((size_t)co * Cin + c) * k + a) * k + b];
-        dev_buf dx, dw, dr, dy, dz, dsc, dsh;
-        ICL_TRY(to_dev(ctx, prec, x, nx, dx));
-        if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: zero page");
-        ICL_TRY(to_dev(ctx, prec, wp.data(), nw, dw));
-        if (residual) ICL_TRY(to_dev(ctx, prec, residual, ny, dr));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, scale, (size_t)Cout, dsc));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, shift, (size_t)Cout, dsh));
+    return run_entry(ctx, "icl_conv2d_fused", false, y, [&](entry_io &io) -> int {
+        const size_t nx = (size_t)B * H * H * Cin, ny = (size_t)B * Ho * Ho * Cout;
+        std::vector<float> wp;
+        pack_ohwi(w, Cout, Cin, k, wp);
+        dev_buf &dx = io.buf(), &dw = io.buf(), &dr = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
+        ICL_TRY(upload_as(ctx, prec, &dx.p, x, nx));
+        ICL_TRY(zero_page(ctx, "icl_conv2d_fused", dz));
+        ICL_TRY(upload_as(ctx, prec, &dw.p, wp.data(), wp.size()));
+        if (residual) ICL_TRY(upload_as(ctx, prec, &dr.p, residual, ny));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsc.p, scale, (size_t)Cout));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsh.p, shift, (size_t)Cout));
         if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: output alloc");
-        int rc = launch_conv_prec(ctx, prec, conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, H, Cin, Cout, k, stride, pad, relu));
-        if (!rc) {
-            const hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_fused: %s", hipGetErrorString(e));
-        }
-        icl_prof_collect(ctx);
-        return rc;
+        io.returns(prec, dy.p, ny);
+        return launch_conv_prec(ctx, prec, conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, H, Cin, Cout, k, stride, pad, relu));
     });
 }
 
@@ -984,33 +989,22 @@ extern "C" int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, in
     if ((int64_t)(Ho - 1) * stride2 >= H2) return icl_fail(ctx, ICL_ERR_ARG, "icl_conv2d_dual: output pixel %d reads row %lld of a %d-row second operand", Ho - 1, (long long)(Ho - 1) * stride2, H2);
     if (Cin % 64 || Cin2 % 64 || Cout % 128) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_dual needs Cin %% 64 == 0, Cin2 %% 64 == 0 and Cout %% 128 == 0");
     if ((int64_t)B * Ho * Ho >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv2d_dual: %lld output pixels exceed the kernel's 32-bit pixel index", (long long)B * Ho * Ho);
-    return no_throw(ctx, "icl_conv2d_dual", [&]() -> int {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        const int K = Cin + Cin2;
-        const size_t nx = (size_t)B * Ho * Ho * Cin, nx2 = (size_t)B * H2 * H2 * Cin2, nw = (size_t)Cout * K, ny = (size_t)B * Ho * Ho * Cout;
-        std::vector<float> wp(nw);
-        for (int co = 0; co < Cout; ++co) {
-            memcpy(&wp[(size_t)co * K], w1 + (size_t)co * Cin, (size_t)Cin * 4);
-            memcpy(&wp[(size_t)co * K + Cin], w2 + (size_t)co * Cin2, (size_t)Cin2 * 4);
-        }
-        dev_buf dx, dx2, dw, dy, dz, dsc, dsh;
-        ICL_TRY(to_dev(ctx, prec, x, nx, dx));
-        ICL_TRY(to_dev(ctx, prec, x2, nx2, dx2));
-        if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_dual: zero page");
-        ICL_TRY(to_dev(ctx, prec, wp.data(), nw, dw));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, scale, (size_t)Cout, dsc));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, shift, (size_t)Cout, dsh));
+    return run_entry(ctx, "icl_conv2d_dual", false, y, [&](entry_io &io) -> int {
+        const size_t nx = (size_t)B * Ho * Ho * Cin, nx2 = (size_t)B * H2 * H2 * Cin2, ny = (size_t)B * Ho * Ho * Cout;
+        std::vector<float> wp;
+        pack_row_concat(w1, Cin, w2, Cin2, Cout, wp);
+        dev_buf &dx = io.buf(), &dx2 = io.buf(), &dw = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
+        ICL_TRY(upload_as(ctx, prec, &dx.p, x, nx));
+        ICL_TRY(upload_as(ctx, prec, &dx2.p, x2, nx2));
+        ICL_TRY(zero_page(ctx, "icl_conv2d_dual", dz));
+        ICL_TRY(upload_as(ctx, prec, &dw.p, wp.data(), wp.size()));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsc.p, scale, (size_t)Cout));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsh.p, shift, (size_t)Cout));
         if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_dual: output alloc");
         conv_args a = conv_plain(dx.p, dw.p, dy.p, nullptr, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, Ho, Cin, Cout, 1, 1, 0, relu);
         conv_add_operand(a, dx2.p, H2, Cin2, stride2);
-        int rc = launch_conv_prec(ctx, prec, a);
-        if (!rc) {
-            const hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_conv2d_dual: %s", hipGetErrorString(e));
-        }
-        icl_prof_collect(ctx);
-        return rc;
+        io.returns(prec, dy.p, ny);
+        return launch_conv_prec(ctx, prec, a);
     });
 }
 
@@ -1192,21 +1186,16 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
 {
     if (!ctx || !img || !out || B < 1) return icl_fail(ctx, ICL_ERR_ARG, "icl_stem_pool: bad argument");
     if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
-    return no_throw(ctx, "icl_stem_pool", [&]() -> int {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
+    return run_entry(ctx, "icl_stem_pool", true, out, [&](entry_io &io) -> int {
         const size_t ny = (size_t)B * 56 * 56 * 64;
-        dev_buf dimg, dy;
+        dev_buf &dimg = io.buf(), &dy = io.buf();
         if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess || hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess)
             return icl_fail(ctx, ICL_ERR_NOMEM, "icl_stem_pool: device buffers");
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
         with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, ctx->stream); });
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        const int rc = e == hipSuccess ? from_dev(ctx, prec, dy.p, ny, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
-        icl_prof_collect(ctx);
-        return rc;
+        io.returns(prec, dy.p, ny);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? ICL_OK : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
     });
 }
 
@@ -1224,44 +1213,36 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
     if (has_ds && (!scds || !shds)) return icl_fail(ctx, ICL_ERR_ARG, "icl_bottleneck56: downsample scale / shift missing");
     if (Cin != (has_ds ? 64 : 256)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_bottleneck56: Cin must be 256 (identity) or 64 (downsample branch)");
     if ((int64_t)B * H * W * 512 >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_bottleneck56: tensor exceeds the kernel's 32-bit buffer offsets");
-    return no_throw(ctx, "icl_bottleneck56", [&]() -> int {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
+    return run_entry(ctx, "icl_bottleneck56", false, y, [&](entry_io &io) -> int {
         const size_t nx = (size_t)B * H * W * Cin, ny = (size_t)B * H * W * 256;
-        const int K3 = has_ds ? 128 : 64;
-        // every BatchNorm scale goes into the weights before they are rounded, as icl_model_load_blob does for stage 1
-        std::vector<float> f1((size_t)64 * Cin), f2((size_t)64 * 576), f3((size_t)256 * K3), h3(256);
-        for (size_t i = 0; i < f1.size(); ++i) f1[i] = w1[i] * sc1[i / (size_t)Cin];
-        for (int co = 0; co < 64; ++co)
-            for (int c = 0; c < 64; ++c)
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) f2[(size_t)co * 576 + ((size_t)a * 3 + b) * 64 + c] = w2[(((size_t)co * 64 + c) * 3 + a) * 3 + b] * sc2[co];
-        for (int co = 0; co < 256; ++co) {
-            for (int c = 0; c < 64; ++c) f3[(size_t)co * K3 + c] = w3[(size_t)co * 64 + c] * sc3[co];
-            if (has_ds)
-                for (int c = 0; c < 64; ++c) f3[(size_t)co * 128 + 64 + c] = wds[(size_t)co * 64 + c] * scds[co];
-            h3[co] = has_ds ? sh3[co] + shds[co] : sh3[co];
+        // the loader's packing of stage 1: every BatchNorm scale goes into the weights before they are rounded; the downsample form
+        // concatenates [W3 * s3 | Wds * sds] and adds the two shifts
+        std::vector<float> f1, p2, f2, f3, fds, f3ds, h3(sh3, sh3 + 256);
+        pack_row_scale(w1, sc1, 64, Cin, f1);
+        pack_ohwi(w2, 64, 64, 3, p2);
+        pack_row_scale(p2.data(), sc2, 64, 576, f2);
+        pack_row_scale(w3, sc3, 256, 64, f3);
+        if (has_ds) {
+            pack_row_scale(wds, scds, 256, 64, fds);
+            pack_row_concat(f3.data(), 64, fds.data(), 64, 256, f3ds);
+            for (int co = 0; co < 256; ++co) h3[(size_t)co] = sh3[co] + shds[co];
         }
-        dev_buf dx, dy, dw1, dw2, dw3, d1h, d2h, d3h;
-        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, x, nx, dx));
-        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f1.data(), f1.size(), dw1));
-        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f2.data(), f2.size(), dw2));
-        ICL_TRY(to_dev(ctx, ICL_PREC_BF16, f3.data(), f3.size(), dw3));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, sh1, 64, d1h));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, sh2, 64, d2h));
-        ICL_TRY(to_dev(ctx, ICL_PREC_FP32, h3.data(), 256, d3h));
+        const std::vector<float> &w3p = has_ds ? f3ds : f3;
+        dev_buf &dx = io.buf(), &dy = io.buf(), &dw1 = io.buf(), &dw2 = io.buf(), &dw3 = io.buf(), &d1h = io.buf(), &d2h = io.buf(), &d3h = io.buf();
+        ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dx.p, x, nx));
+        ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dw1.p, f1.data(), f1.size()));
+        ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dw2.p, f2.data(), f2.size()));
+        ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dw3.p, w3p.data(), w3p.size()));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d1h.p, sh1, 64));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d2h.p, sh2, 64));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d3h.p, h3.data(), 256));
         if (hipMalloc(&dy.p, ny * 2) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_bottleneck56: output alloc");
         bneck_args a = {};
         a.X = (const uint16_t *)dx.p; a.Y = (uint16_t *)dy.p; a.W1 = (const uint16_t *)dw1.p; a.W2 = (const uint16_t *)dw2.p; a.W3 = (const uint16_t *)dw3.p;
         a.sh1 = (const float *)d1h.p; a.sh2 = (const float *)d2h.p; a.sh3 = (const float *)d3h.p;
         a.B = B; a.H = H; a.W = W;
-        int rc = launch_bneck56_args(ctx, a, has_ds, ctx->stream); // the launch code of the forward pass
-        if (!rc) {
-            const hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? from_dev(ctx, ICL_PREC_BF16, dy.p, ny, y) : icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: %s", hipGetErrorString(e));
-        }
-        icl_prof_collect(ctx);
-        return rc;
+        io.returns(ICL_PREC_BF16, dy.p, ny);
+        return launch_bneck56_args(ctx, a, has_ds, ctx->stream); // the launch code of the forward pass
     });
 }
 
@@ -1272,10 +1253,7 @@ extern "C" int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *img, int B,
 {
     if (!ctx || !img || !out || B < 1 || tap < 0 || tap > 16) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_taps: bad argument");
     if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
-    return no_throw(ctx, "icl_embed_taps", [&]() -> int {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
+    return run_entry(ctx, "icl_embed_taps", true, out, [&](entry_io &io) -> int {
         if (B > ctx->batch) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_taps: %d images exceed the batch of %d", B, ctx->batch);
         ICL_TRY(icl_model_ensure_ws(ctx, B, prec, 1));
         int H = 56, C = 64; // the tapped tensor: the output of the block's last convolution
@@ -1285,16 +1263,14 @@ extern "C" int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *img, int B,
                 C = ctx->model->conv[i].rec.cout;
                 ++blk;
             }
-        dev_buf dimg;
+        dev_buf &dimg = io.buf();
         if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_embed_taps: image buffer");
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: upload");
         const void *x = nullptr;
-        int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, ICL_HEAD_POOLED, nullptr, 0, ctx->stream, tap, &x); });
+        const int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, ICL_HEAD_POOLED, nullptr, 0, ctx->stream, tap, &x); });
         ctx->cur_stream = nullptr;
-        const hipError_t e = hipStreamSynchronize(ctx->stream); // (also after a failed launch: dimg is freed on return)
-        if (!rc) rc = e == hipSuccess ? from_dev(ctx, prec, x, (size_t)B * H * H * C, out) : icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: %s", hipGetErrorString(e));
-        icl_prof_collect(ctx);
-        return rc;
+        io.returns(prec, x, (size_t)B * H * H * C);
+        return rc; // (run_entry synchronises also after a failed launch: dimg is freed on its return)
     });
 }
 

@@ -9,7 +9,7 @@
 //                     launch: reads the block input once, writes the block output once (1 645 -> 822 MB per block).
 #pragma once
 #include "mfma_tile.h"
-#include "resnet_model.h" // STEM_K, STEM_ROWK, ST2_K: the weight layouts the loader packs
+#include "resnet_model.h" // (resnet_pack.h:) STEM_K, STEM_ROWK, ST2_K, the weight layouts the loader packs
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -1,21 +1,17 @@
 // resnet_model.h -- what the embedding units share (host only: no kernel, no device code): the loaded model (model.hip fills it,
-// resnet.hip runs it), the weight-layout constants the packer and the kernels must agree on, the host bf16 conversions and the
-// precision dispatch.
+// resnet.hip runs it), the precision dispatch and the uploads.  The weight layouts, their constants (STEM_K, STEM_ROWK, ST2_K) and
+// the host bf16 conversions are defined once, in resnet_pack.h.
 #pragma once
 #include "mfma_tile.h" // element traits (F32, BF16, BF16X3)
-
-#include <cstring>
+#include "resnet_pack.h"
 
 #define ICL_MAX_LANES 4 /* forward passes in flight (ICL_EMBED_STREAMS) */
 
-// weight layouts of the stem kernels (resnet.hip, resnet_fused.h) as icl_model_load_blob packs them
-#define STEM_K 192   /* stem_conv_kernel / stem_pool_kernel: K = 147 padded, 7 filter rows of STEM_ROWK k slots + zeros */
-#define STEM_ROWK 24 /* k slots per filter row (21 used) */
-#define ST2_K 224    /* stem2_pool_kernel: 7 filter rows x 8 kw slots x 4 channel slots */
+static_assert(PACK_FP32 == ICL_PREC_FP32 && PACK_BF16 == ICL_PREC_BF16 && PACK_BF16X3 == ICL_PREC_BF16X3, "resnet_pack.h numbers the storage formats as imageclust.h");
 
 struct conv_layer {
     icl_conv_rec rec;
-    int K = 0, cin_eff = 0; // cin_eff: channel count seen by the kernel (160 for the lowered stem)
+    int K = 0; // k of a weight row: cin * k * k, STEM_K for the stem
     void *w[3] = {nullptr, nullptr, nullptr}; // [ICL_PREC_FP32], [ICL_PREC_BF16], [ICL_PREC_BF16X3] (split layout: host_split32)
     float *scale = nullptr, *shift = nullptr;
     // block-0 c3 only: [Cout][mid + cin] = [W3*scale3 | Wds*scale_ds] and shift3 + shift_ds (downsample fused in)
@@ -68,44 +64,15 @@ struct prec_host {
 static inline size_t prec_act_bytes(int prec) { return with_prec(prec, [](auto t) { return prec_host<decltype(t)>::act_bytes; }); }
 static inline int prec_bk(int prec) { return with_prec(prec, [](auto t) { return prec_host<decltype(t)>::bk; }); }
 
-// ---- host bf16 ------------------------------------------------------------------------------------------------------
-static inline uint16_t host_bf16(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float host_from_bf16(uint16_t v)
-{
-    uint32_t u = (uint32_t)v << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// The split bf16 layout of ICL_PREC_BF16X3 (mfma_tile.h, BF16X3): every run of 32 consecutive fp32 values v (a channel chunk of a pixel, or
-// 32 k of a weight row: rows are whole chunks) becomes 64 bf16, [hi = bf16(v) of the 32 | lo = bf16(v - hi) of the same 32].  n % 32 == 0.
-static inline void host_split32(const float *src, size_t n, uint16_t *dst)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const uint16_t h = host_bf16(src[i]);
-        dst[(i & ~(size_t)31) * 2 + (i & 31)] = h;
-        dst[(i & ~(size_t)31) * 2 + 32 + (i & 31)] = host_bf16(src[i] - host_from_bf16(h));
-    }
-}
-// host_split32 undone: dst[i] = hi + lo in fp32
-static inline void host_join32(const uint16_t *src, size_t n, float *dst)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const size_t j = (i & ~(size_t)31) * 2 + (i & 31);
-        dst[i] = host_from_bf16(src[j]) + host_from_bf16(src[j + 32]);
-    }
-}
-
 static inline int upload(icl_ctx *ctx, void **dst, const void *src, size_t bytes)
 {
     ICL_HIP(ctx, hipMalloc(dst, bytes));
     ICL_HIP(ctx, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     return ICL_OK;
+}
+// n fp32 values in the storage format of prec (pack_storage) into a new allocation *dst
+static inline int upload_as(icl_ctx *ctx, int prec, void **dst, const float *src, size_t n)
+{
+    std::vector<uint16_t> buf;
+    return upload(ctx, dst, pack_storage(prec, src, n, buf), pack_storage_bytes(prec, n));
 }

@@ -96,6 +96,19 @@ def test_every_block_matches_oracle_variant_blob(vnet, imgs, prec, stage):
     vnet.check_stage(imgs, stage, prec, what="variant ")
 
 
+def test_loader_and_bottleneck56_pack_alike(vnet, imgs):
+    """Stage 1, bf16: the pass on the loader's wfold / wfused / shift_fused and icl_bottleneck56 on the same block's raw weights with
+    the folded scales and shifts run one kernel on one input, with weights from the same packer functions (resnet_pack.h): equal bits."""
+    for t in (1, 2, 3):
+        c = vnet.blocks[t - 1]
+        ds = {} if len(c) == 3 else dict(wds=c[3].W.reshape(256, -1), bnds=(c[3].scale, c[3].shift))
+        y = vnet.ctx.bottleneck56(vnet.tap(imgs, t - 1, "bf16"), c[0].W.reshape(64, -1), (c[0].scale, c[0].shift), c[1].W, (c[1].scale, c[1].shift),
+                                  c[2].W.reshape(256, 64), (c[2].scale, c[2].shift), **ds)
+        assert (t == 1) == bool(ds)
+        assert np.array_equal(vnet.tap(imgs, t, "bf16"), y), "block %d: first difference at %s" % (
+            t, tuple(int(v[0]) for v in np.nonzero(vnet.tap(imgs, t, "bf16") != y)))
+
+
 @pytest.mark.parametrize("prec", PRECS)
 def test_tap0_is_the_stem(net, vnet, L, imgs, prec):
     assert np.array_equal(net.tap(imgs, 0, prec), net.ctx.stem_pool(imgs, PREC(L, prec)))
