@@ -138,6 +138,7 @@ SYMBOLS = [
     ("icl_last_ward_layout", _int, [_vp, _vp, _vp, _vp]),
     ("icl_distance_bounds_check_dev", _int, [_vp, _vp, C.c_int64, C.c_int32, _int, _vp, _vp, _vp, _vp, _vp]),
     ("icl_last_ward_bound_violations", _i64, [_vp]),
+    ("icl_ward_dump_pairs_dev", _int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("icl_version", C.c_char_p, []),
 ]
 
@@ -397,6 +398,24 @@ class Context:
         check(self.h, self.L.icl_distance_bounds_check_dev(self.h, C.c_void_p(t.data_ptr()), n, d, kind, C.byref(a), C.byref(b), C.byref(u), C.byref(g), C.byref(v)))
         pairs = n * (n - 1) / 2
         return {"below": a.value, "above": b.value, "unflagged": u.value, "mean_gap": g.value / pairs, "mean_val": v.value / pairs}
+
+    def ward_dump_pairs(self, ids, d):
+        """The working matrix of the last cluster() call for the pairs of the creation ids `ids` (include/imageclust.h icl_ward_dump_pairs_dev):
+        dict(ids, sizes [L], centroids [L][d], row_filled [L], entries / mirror [L][L] uint32 (raw bits, sign bit = lower bound), lb_g1, lb_delta2
+        (float32), row_mode, complete_rows, n, d, merges, max_size)."""
+        import numpy as np
+
+        ids = np.ascontiguousarray(ids, np.int32)
+        L = len(ids)
+        sizes, filled, info = np.zeros(L, np.int32), np.zeros(L, np.int32), np.zeros(6, np.int32)
+        cent = np.zeros((L, d), np.float32)
+        ent, mir = np.zeros((L, L), np.uint32), np.zeros((L, L), np.uint32)
+        g1, d2 = C.c_float(0), C.c_float(0)
+        check(self.h, self.L.icl_ward_dump_pairs_dev(self.h, ids.ctypes.data, L, d, sizes.ctypes.data, cent.ctypes.data, filled.ctypes.data, ent.ctypes.data,
+                                                     mir.ctypes.data, C.byref(g1), C.byref(d2), info.ctypes.data))
+        return {"ids": ids, "sizes": sizes, "centroids": cent, "row_filled": filled.astype(bool), "entries": ent, "mirror": mir,
+                "lb_g1": np.float32(g1.value), "lb_delta2": np.float32(d2.value), "row_mode": int(info[0]), "complete_rows": bool(info[1]),
+                "n": int(info[2]), "d": int(info[3]), "merges": int(info[4]), "max_size": int(info[5])}
 
     # -- model / embed --------------------------------------------------------------------------------
     def load_synthetic(self, seed=1):

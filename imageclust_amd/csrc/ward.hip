@@ -230,6 +230,15 @@ struct icl_ward_ws {
     ward_graph_key graph_key;  // what graph_exec was captured for
     size_t upd_attr_bytes = 0; // the kernels' > 64 KB dynamic-LDS opt-in made on this context's device
     bool wx_attr = false;
+    // what the tables and the matrix above hold, for the test hook icl_ward_dump_pairs_dev: the shape of the clustering call that ran last on this
+    // workspace.  state 0: none (fresh workspace, or something re-initialised the tables since: ward_launch_init), 1: a finished call the hook can
+    // read, 2: a finished call it cannot (FAST mode, a replica of a sharded group)
+    struct {
+        int state = 0;
+        int64_t n = 0;
+        int d = 0, max_size = 0, rows = 0;
+        bool lbm = false, wide = false;
+    } dump;
 };
 
 void icl_ward_free(icl_ctx *ctx)
@@ -5192,6 +5201,7 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
 static void ward_launch_init(icl_ward_ws *w, int64_t n, int64_t T, uint32_t *mpk, int pk_bits, hipStream_t strm)
 {
     const int64_t cnt = std::max(std::max(w->S, w->M), w->ld);
+    w->dump.state = 0; // the last call's tables are gone
     hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)icl_ceil_div(cnt, 256)), dim3(256), 0, strm, n, w->S, w->M, w->ld,
                        w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->st, (int32_t)T, mpk, pk_bits);
 }
@@ -5633,7 +5643,13 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
     ICL_TRY(p.batched ? ward_run_batched(ctx, w, p, rf, c) : ward_run_single(ctx, w, p, rf));
     ICL_HIP(ctx, hipGetLastError());
     ICL_HIP(ctx, hipEventRecord(c.e2.p, ctx->stream));
-    return ward_collect(ctx, w, p, rf, c, min_size, cluster_id, member_rank, n_clusters);
+    const int rc = ward_collect(ctx, w, p, rf, c, min_size, cluster_id, member_rank, n_clusters);
+    if (rc == ICL_OK) { // (icl_ward_dump_pairs_dev reads the workspace as this call leaves it)
+        w->dump.state = (p.lw || p.sh) ? 2 : 1;
+        w->dump.n = n, w->dump.d = d, w->dump.max_size = max_size, w->dump.rows = p.rows;
+        w->dump.lbm = p.lbm, w->dump.wide = rf.wide != 0;
+    }
+    return rc;
 }
 
 // ---- distance tiles over several GPUs ("tiles computed on 8 GPUs, scattered to GPU0 over xGMI") ----------
@@ -6071,6 +6087,100 @@ extern "C" int icl_distance_bounds_check_dev(icl_ctx *ctx, const float *d_E, int
     if (unflagged) *unflagged = (int64_t)hc[2];
     if (sum_gap) *sum_gap = hs[0];
     if (sum_val) *sum_val = hs[1];
+    return ICL_OK;
+    });
+}
+
+// ---- test hook: the working matrix as the last clustering call left it, for the pairs of a list of creation ids --------------------------------
+// The oracle comparisons see one entry per merge (the pair that won) and icl_last_ward_bound_violations the entries a scan happened to make
+// exact; this entry point hands EVERY entry of the chosen clusters' pairs to the host (tests/ward_final_check.py), with the sizes and centroids
+// the engine holds, read the way the kernels read them:
+//   entry (p, q): row of the larger creation id -- recycled columns: at mcol[smaller] (tri_at); complete rows: at column = the smaller id;
+//   mirror (complete rows only): row of the SMALLER id at column = the larger id, the copy ward_update_lb_kernel's contiguous reads take;
+//   centroid: Crow[creation id] in the bound-rows loop (ward_finish_lb_kernel keeps no slot table), Crow[id_slot[id]] in the exact-rows loops.
+// Items [0, L*L): pairs; [L*L, L*L + L*d): centroid elements; then L sizes.  Read-only on the workspace.
+__global__ __launch_bounds__(256) void ward_dump_pairs_kernel(const int32_t *__restrict__ ids, int64_t L, int d, int by_id, int wide, int64_t S,
+                                                             const float *__restrict__ Dtri, const int64_t *__restrict__ rowoff,
+                                                             const int32_t *__restrict__ mcol, const int32_t *__restrict__ id_slot,
+                                                             const int32_t *__restrict__ asz, const float *__restrict__ Crow,
+                                                             uint32_t *__restrict__ ent, uint32_t *__restrict__ mir, float *__restrict__ cent,
+                                                             int32_t *__restrict__ sizes)
+{
+    const int64_t npair = L * L, ncent = L * (int64_t)d, total = npair + ncent + L;
+    for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (int64_t)gridDim.x * blockDim.x) {
+        if (it < npair) {
+            const int p = ids[it / L], q = ids[it % L];
+            const int hi = p > q ? p : q, lo = p > q ? q : p;
+            uint32_t e = 0u, m = 0u;
+            if (p != q) {
+                e = __float_as_uint(Dtri[rowoff[hi] + (wide ? lo : mcol[lo])]);
+                if (wide) m = __float_as_uint(Dtri[rowoff[lo] + hi]);
+            }
+            ent[it] = e;
+            mir[it] = m;
+        } else if (it < npair + ncent) {
+            const int64_t c = it - npair;
+            const int id = ids[c / d];
+            const int64_t slot = by_id ? id : id_slot[id];
+            cent[c] = (slot >= 0 && slot < S) ? Crow[slot * d + c % d] : 0.0f; // (a dead cluster of the exact-rows loops has no slot any more)
+        } else {
+            sizes[it - npair - ncent] = asz[ids[it - npair - ncent]];
+        }
+    }
+}
+
+extern "C" int icl_ward_dump_pairs_dev(icl_ctx *ctx, const int32_t *ids, int64_t L, int32_t d_expected, int32_t *sizes, float *centroids, int32_t *row_filled,
+                                       uint32_t *entries, uint32_t *mirror, float *lb_g1, float *lb_delta2, int32_t *info)
+{
+    return no_throw(ctx, "icl_ward_dump_pairs_dev", [&]() -> int {
+    if (!ctx || !ids || L < 1 || L > 32768 || !sizes || !centroids || !row_filled || !entries || !mirror || !info)
+        return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: bad argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    icl_ward_ws *w = ctx->ward;
+    if (!w || w->dump.state == 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: no finished icl_cluster[_dev] call on this context's workspace");
+    if (w->dump.state != 1) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_ward_dump_pairs_dev: FAST mode and sharded group calls are not covered");
+    const int64_t n = w->dump.n;
+    const int d = w->dump.d;
+    if (d_expected != d) return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: the last call clustered %d-dimensional rows, the caller's buffers are for %d", d, d_expected);
+    ward_state hst;
+    ICL_HIP(ctx, hipMemcpyAsync(&hst, w->st, sizeof hst, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // Every cluster in the merge log had its row written BEFORE its merge was committed in the batched loops (update(k) fills the rows of the
+    // tentative picks, finish(k) commits a prefix of them: ward_finish_lb_kernel / ward_finish_batch_kernel (2)); the one-merge-per-step loop commits
+    // first (ward_finish_kernel) and fills the row in the update launch behind it, so there the cluster of a still valid `cur` record would be
+    // unfilled -- the loop always ends with a finish that clears it (t >= target or no pair left).
+    const int64_t ids_end = n + hst.t;
+    for (int64_t i = 0; i < L; ++i) {
+        if (ids[i] < 0 || ids[i] >= ids_end)
+            return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: id %d outside the %lld creation ids of the last call", ids[i], (long long)ids_end);
+        row_filled[i] = !(w->dump.rows == ICL_ROWS_SINGLE && hst.cur_valid && ids[i] == hst.cur_c);
+    }
+    const int64_t dd = d > 0 ? d : 1;
+    dev_guard g_ids, g_ent, g_mir, g_cent, g_sz;
+    if (hipMalloc(&g_ids.p, (size_t)L * 4) != hipSuccess || hipMalloc(&g_ent.p, (size_t)(L * L) * 4) != hipSuccess || hipMalloc(&g_mir.p, (size_t)(L * L) * 4) != hipSuccess ||
+        hipMalloc(&g_cent.p, (size_t)(L * dd) * 4) != hipSuccess || hipMalloc(&g_sz.p, (size_t)L * 4) != hipSuccess)
+        return icl_fail(ctx, ICL_ERR_NOMEM, "icl_ward_dump_pairs_dev: scratch for %lld ids", (long long)L);
+    ICL_HIP(ctx, hipMemcpyAsync(g_ids.p, ids, (size_t)L * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t total = L * L + L * d + L;
+    hipLaunchKernelGGL(ward_dump_pairs_kernel, dim3((unsigned)std::min<int64_t>(icl_ceil_div(total, 256), 8192)), dim3(256), 0, ctx->stream, (const int32_t *)g_ids.p, L, d,
+                       w->dump.lbm ? 1 : 0, w->dump.wide ? 1 : 0, std::max(w->S, w->M), (const float *)w->Dtri, (const int64_t *)w->rowoff, (const int32_t *)w->mcol,
+                       (const int32_t *)w->id_slot, (const int32_t *)w->asz, (const float *)w->Crow, (uint32_t *)g_ent.p, (uint32_t *)g_mir.p, (float *)g_cent.p,
+                       (int32_t *)g_sz.p);
+    ICL_HIP(ctx, hipGetLastError());
+    ICL_HIP(ctx, hipMemcpyAsync(entries, g_ent.p, (size_t)(L * L) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipMemcpyAsync(mirror, g_mir.p, (size_t)(L * L) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d > 0) ICL_HIP(ctx, hipMemcpyAsync(centroids, g_cent.p, (size_t)(L * d) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipMemcpyAsync(sizes, g_sz.p, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (lb_g1) *lb_g1 = w->dump.lbm ? hst.lb_g1 : 0.0f; // (only the bound-rows loop sets them: ward_lb_consts_kernel)
+    if (lb_delta2) *lb_delta2 = w->dump.lbm ? hst.lb_delta2 : 0.0f;
+    info[0] = w->dump.rows;
+    info[1] = w->dump.wide ? 1 : 0;
+    info[2] = (int32_t)n;
+    info[3] = d;
+    info[4] = hst.t;
+    info[5] = w->dump.max_size;
     return ICL_OK;
     });
 }

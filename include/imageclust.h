@@ -489,6 +489,22 @@ int64_t icl_last_ward_bound_violations(icl_ctx *ctx);
  * values (the bounds' mean tightness).  The merge loop itself only meets the few entries near a row's minimum. */
 int icl_distance_bounds_check_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int kind, int64_t *below, int64_t *above, int64_t *unflagged,
                                   double *sum_gap, double *sum_val);
+/* Test hook for the matrix the merge loop works on ("every entry of the final matrix"): the Ward workspace exactly as the last
+ * icl_cluster[_dev] call on this context left it, for the L creation ids the caller names (the test derives the live set from the merge log; the
+ * engine's own idea of who is alive is not used).  Nothing in the workspace is changed.  Host outputs:
+ *   sizes [L], centroids [L][d]: what the engine holds for the cluster (a singleton's centroid is its embedding row);
+ *   row_filled [L]: 1 when the cluster's row of the matrix was written (derived from the loop's step state; every loop ends with all rows filled);
+ *   entries [L][L]: the raw 32 bits of the entry of the pair (ids[i], ids[j]), sign bit (= "lower bound, not a value") included, read the way
+ *     the kernels read it; 0 on the diagonal;
+ *   mirror [L][L]: the second copy the complete-rows layout keeps in the row of the pair's OLDER cluster; all 0 in the recycled-column layout;
+ *   lb_g1, lb_delta2: the constants of the Lance-Williams bound the call used (0 unless row mode ICL_ROWS_LW_BOUND);
+ *   info [6]: row mode (ICL_ROWS_*), complete_rows, n, d, merges done, max_size of that call.
+ * ICL_ROWS_EXACT_BATCH and ICL_ROWS_LW_BOUND (both layouts) are covered and tested; ICL_ROWS_SINGLE takes the same path (no test runs it); ICL_ERR_ARG without a finished call on the workspace
+ * (or after anything that re-initialised it, icl_distance_bounds_check_dev for one), for an id outside [0, n + merges) or a d (the row length
+ * the centroids buffer was sized for) that is not the last call's; ICL_ERR_UNSUPPORTED
+ * after a FAST-mode call or on a context of a sharded group. */
+int icl_ward_dump_pairs_dev(icl_ctx *ctx, const int32_t *ids, int64_t L, int32_t d, int32_t *sizes, float *centroids, int32_t *row_filled, uint32_t *entries,
+                            uint32_t *mirror, float *lb_g1, float *lb_delta2, int32_t *info);
 
 const char *icl_version(void);
 

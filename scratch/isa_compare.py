@@ -30,8 +30,9 @@ def kernels(path):
         b = a
         while not lines[b].startswith(".Lfunc_end"):  # past the last s_endpgm of the function
             b += 1
-        # block labels carry the function's emission index (.LBB<index>_<block>): drop the index, keep everything else
-        out[name] = (re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b])), desc)
+        # block labels carry the function's emission index (.LBB<index>_<block>), and so do the loop comments that name them (BB<index>_<block>):
+        # drop the index, keep everything else
+        out[name] = (re.sub(r"\bBB\d+_", "BB_", re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b]))), desc)
     return out
 
 
