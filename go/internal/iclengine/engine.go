@@ -300,3 +300,92 @@ func LastRequestsMs() (embedMs, assembleMs, clusterMs float64, err error) {
 	}
 	return float64(a), float64(b), float64(c), nil
 }
+
+// The limits of resizeImageIfNeeded (internal/rekognition/rekognition.go: MaxImageSize, and the box it resizes into).
+const (
+	MaxImageSize = 5 * 1024 * 1024
+	MaxImageDim  = 2048
+)
+
+// DownsizeImage is resizeImageIfNeeded (rekognition.go:173-259) on the host (icl_downsize_image_mem): an image of at most MaxImageSize
+// bytes comes back as it is, a larger one decoded, resized into the 2048 box -- with the reference's rows / columns swap: a 4000x3000
+// landscape photo becomes 1536 wide x 2048 high -- and written as a JPEG at quality 95, once more at half the size if it is still too
+// large.  No GPU is touched.
+func DownsizeImage(data []byte) ([]byte, error) {
+	if len(data) == 0 {
+		return nil, fmt.Errorf("empty image buffer")
+	}
+	var need C.int64_t
+	p := (*C.uint8_t)(unsafe.Pointer(&data[0]))
+	out := make([]byte, len(data)) // (a downsized image is rarely larger than its source; a second call only if it is)
+	for try := 0; try < 2; try++ {
+		rc := C.icl_downsize_image_mem(p, C.int64_t(len(data)), MaxImageSize, MaxImageDim, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.int64_t(len(out)), &need, nil)
+		if rc == C.ICL_OK {
+			return out[:need], nil
+		}
+		if rc != C.ICL_ERR_ARG || int(need) <= len(out) {
+			break
+		}
+		out = make([]byte, int(need))
+	}
+	return nil, fmt.Errorf("%s", C.GoString(C.icl_last_error(nil)))
+}
+
+// DownsizeImages is DownsizeImage over a list in one call (icl_downsize_images_mem): JPEGs above the limit are rebuilt, resized and
+// encoded on the GPU.  Result i is image i's, byte-equal to DownsizeImage's; status[i] != 0 marks an image that failed alone (its
+// result is empty), and the returned error then names the lowest failed index.  The slices are handed to C in place.
+func DownsizeImages(images [][]byte, threads int) (out [][]byte, status []int32, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, nil, e
+	}
+	n := len(images)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	ptrSize := C.size_t(unsafe.Sizeof(uintptr(0)))
+	datav := (**C.uint8_t)(C.calloc(C.size_t(n+1), ptrSize))
+	defer C.free(unsafe.Pointer(datav))
+	bytesv := (*C.int64_t)(C.calloc(C.size_t(n+1), 8))
+	defer C.free(unsafe.Pointer(bytesv))
+	data, size := unsafe.Slice(datav, n+1), unsafe.Slice(bytesv, n+1)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	capBytes := int64(1)
+	for i, img := range images {
+		if len(img) > 0 {
+			pin.Pin(&img[0])
+			data[i], size[i] = (*C.uint8_t)(unsafe.Pointer(&img[0])), C.int64_t(len(img))
+			capBytes += int64(len(img))
+		}
+	}
+	st := make([]C.int32_t, n)
+	off := make([]C.int64_t, n+1)
+	var buf []byte
+	var rc C.int
+	for try := 0; try < 2; try++ { // (an output is rarely larger than its input; the call says what it needs when one is)
+		buf = make([]byte, capBytes)
+		rc = C.icl_downsize_images_mem((*C.icl_ctx)(raw), datav, bytesv, C.int64_t(n), MaxImageSize, MaxImageDim, C.int32_t(threads),
+			(*C.uint8_t)(unsafe.Pointer(&buf[0])), C.int64_t(capBytes), &off[0], &st[0])
+		if rc == C.ICL_ERR_ARG && int64(off[n]) > capBytes {
+			capBytes = int64(off[n])
+			continue
+		}
+		break
+	}
+	if rc != C.ICL_OK {
+		err = fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		failed := false
+		for _, s := range st {
+			failed = failed || s != 0
+		}
+		if !failed { // an argument or device error: no per-image results
+			return nil, nil, err
+		}
+	}
+	out, status = make([][]byte, n), make([]int32, n)
+	for i := range images {
+		out[i], status[i] = buf[off[i]:off[i+1]], int32(st[i])
+	}
+	return out, status, err
+}

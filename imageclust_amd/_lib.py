@@ -29,6 +29,7 @@ K_CONV, K_DIST_EXACT, K_DIST_MFMA, K_ROWMIN, K_UPDATE, K_EMBED_OTHER, K_CONV64 =
 K_NAMES = ["conv_igemm_kernel<*,128>", "ward_dist_exact_kernel", "dist_mfma_kernel", "row_argmin_*_kernel",
            "ward_update_exact_kernel", "embed_other", "conv_igemm_kernel<*,64>"]
 IMG_BYTES = 224 * 224 * 3
+MAX_IMAGE_SIZE, MAX_IMAGE_DIM = 5 * 1024 * 1024, 2048  # rekognition.go: MaxImageSize, and the box resizeImageIfNeeded resizes into
 
 # every symbol include/imageclust.h declares: (name, restype, argtypes)
 _vp, _i64, _i32, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_int
@@ -78,6 +79,14 @@ SYMBOLS = [
     ("icl_embed_images_mem_dev", _int, [_vp, _vp, _vp, _i64, _int, _int, _i32, _vp, _vp]),
     ("icl_cluster_requests_mem", _int, [_vp, _i32] + [_vp] * 8 + [_int, _int, _i32] + [_vp] * 8),
     ("icl_jpeg_coefs_mem", _int, [_vp, _vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
+    ("icl_jpeg_encode_bound", _i64, [_i32, _i32]),
+    ("icl_jpeg_encode_rgb", _int, [_vp, _i32, _i32, _i32, _vp, _i64, _pi64]),
+    ("icl_jpeg_encode_rgb_dev", _int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp]),
+    ("icl_downsize_image_file", _int, [C.c_char_p, _i64, _i32, _vp, _i64, _pi64, _vp]),
+    ("icl_downsize_image_mem", _int, [_vp, _i64, _i64, _i32, _vp, _i64, _pi64, _vp]),
+    ("icl_downsize_images", _int, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    ("icl_downsize_images_mem", _int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    ("icl_last_downsize_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64, _pi64, _pi64, _vp]),
     ("icl_set_batch", _int, [_vp, _int]),
     ("icl_set_conv_options", _int, [_vp, _int]),
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
@@ -530,6 +539,83 @@ class Context:
         check(self.h, self.L.icl_jpeg_coefs_mem(self.h, data, size, n, entropy, buf.ctypes.data, buf.size, off.ctypes.data, state.ctypes.data))
         del keep
         return [buf[off[i]:off[i + 1]] for i in range(n)], state
+
+    # ---- the label service's downsizer and its JPEG encoder (rekognition.go:173-259) ----
+    def jpeg_encode(self, rgb, quality=95):
+        """icl_jpeg_encode_rgb (host): h x w x 3 u8 RGB -> the bytes of the JPEG file libjpeg's defaults write at this quality."""
+        return jpeg_encode(rgb, quality)
+
+    def jpeg_encode_dev(self, images, quality=95):
+        """icl_jpeg_encode_rgb_dev: a list of h x w x 3 u8 RGB images of any sizes, uploaded and encoded in one call -> list of bytes."""
+        imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
+        n = len(imgs)
+        w = np.array([a.shape[1] for a in imgs], np.int32)
+        h = np.array([a.shape[0] for a in imgs], np.int32)
+        offs = np.zeros(n + 1, np.int64)
+        for i, a in enumerate(imgs):
+            offs[i + 1] = offs[i] + ((a.nbytes + 15) & ~15)
+        flat = np.zeros(max(16, int(offs[-1])), np.uint8)
+        for i, a in enumerate(imgs):
+            flat[offs[i]:offs[i] + a.nbytes] = a.reshape(-1)
+        cap = sum(int(self.L.icl_jpeg_encode_bound(int(w[i]), int(h[i]))) for i in range(n))
+        out = np.zeros(max(1, cap), np.uint8)
+        out_off = np.zeros(n + 1, np.int64)
+        d = self.malloc(flat.nbytes)
+        try:
+            self.h2d(d, flat)
+            check(self.h, self.L.icl_jpeg_encode_rgb_dev(self.h, _vp(d), offs.ctypes.data, w.ctypes.data, h.ctypes.data, n, quality,
+                                                         out.ctypes.data, 0, out.nbytes, out_off.ctypes.data))
+        finally:
+            self.free(d)
+        return [out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)]
+
+    def downsize_image(self, path, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM):
+        return downsize_image(path, max_bytes, max_dim)
+
+    def downsize_image_mem(self, data, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM):
+        return downsize_image_mem(data, max_bytes, max_dim)
+
+    def _downsize_many(self, call, n, sizes_in):
+        status = np.zeros(n, np.int32)
+        out_off = np.zeros(n + 1, np.int64)
+        cap = max(1, int(sum(sizes_in)))  # (an output is never larger than... only a guess: the call says what it needs)
+        for _ in range(2):
+            out = np.zeros(cap, np.uint8)
+            rc = call(out.ctypes.data, out.nbytes, out_off.ctypes.data, status.ctypes.data)
+            if rc == ICL_ERR_ARG and int(out_off[-1]) > cap:
+                cap = int(out_off[-1])
+                continue
+            break
+        failed = np.flatnonzero(status)
+        if rc != ICL_OK and not (failed.size and status[failed[0]] == rc):
+            check(self.h, rc)
+        return [out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)], status
+
+    def downsize_images(self, paths, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM, threads=0):
+        """icl_downsize_images -> (list of bytes, status int32[n]); a failed image has an empty entry."""
+        enc = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        sizes = [os.path.getsize(p) if os.path.exists(p) else 0 for p in paths]
+        return self._downsize_many(lambda o, c, oo, st: self.L.icl_downsize_images(self.h, arr, len(enc), max_bytes, max_dim, threads, o, c, oo, st),
+                                   len(enc), sizes)
+
+    def downsize_images_mem(self, bufs, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM, threads=0):
+        """icl_downsize_images_mem: downsize_images for images held in memory."""
+        data, size, n, keep = _byte_arrays(bufs)
+        r = self._downsize_many(lambda o, c, oo, st: self.L.icl_downsize_images_mem(self.h, data, size, n, max_bytes, max_dim, threads, o, c, oo, st),
+                                n, [int(size[i]) for i in range(n)])
+        del keep
+        return r
+
+    def last_downsize_stats(self):
+        """icl_last_downsize_stats of the last batched downsize call."""
+        v = [C.c_int64(0) for _ in range(6)]
+        ms = np.zeros(3, np.float64)
+        check(self.h, self.L.icl_last_downsize_stats(self.h, *[C.byref(x) for x in v], ms.ctypes.data))
+        keys = ["passthrough", "gpu_rebuilt", "host_decoded", "second_attempts", "bytes_in", "bytes_out"]
+        d = {k: x.value for k, x in zip(keys, v)}
+        d["stage_ms"] = {"host_decode": float(ms[0]), "gpu": float(ms[1]), "download": float(ms[2])}
+        return d
 
     def load_images_224_dev(self, paths, d_out, threads=0):
         """icl_load_images_224_dev: n x 224x224x3 u8 rows into device memory d_out -> status (int32[n]); failed rows are zero."""
@@ -1021,6 +1107,63 @@ def decode_image_mem(data):
     if rc:
         raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
     return out
+
+
+def jpeg_encode(rgb, quality=95):
+    """icl_jpeg_encode_rgb (no GPU): h x w x 3 u8 RGB -> the bytes of the JPEG file libjpeg's defaults write at this quality."""
+    L = load()
+    a = np.ascontiguousarray(rgb, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("jpeg_encode wants an h x w x 3 array")
+    h, w = a.shape[:2]
+    n = _i64()
+    rc = L.icl_jpeg_encode_rgb(a.ctypes.data, w, h, quality, None, 0, C.byref(n))
+    if rc:
+        raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    out = np.empty(n.value, np.uint8)
+    rc = L.icl_jpeg_encode_rgb(a.ctypes.data, w, h, quality, out.ctypes.data, out.nbytes, C.byref(n))
+    if rc:
+        raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    return out.tobytes()
+
+
+def jpeg_encode_bound(w, h):
+    return int(load().icl_jpeg_encode_bound(w, h))
+
+
+def _downsize_one(call, want_info, guess):
+    """One call into a buffer of the input's size (a downsized image is rarely larger than its source); a second only if it was too small."""
+    L = load()
+    n = _i64()
+    info = np.zeros(6, np.int32)
+    out = np.empty(max(1, guess), np.uint8)
+    rc = call(out.ctypes.data, out.nbytes, C.byref(n), info.ctypes.data)
+    if rc == ICL_ERR_ARG and n.value > out.nbytes:
+        out = np.empty(n.value, np.uint8)
+        rc = call(out.ctypes.data, out.nbytes, C.byref(n), info.ctypes.data)
+    if rc:
+        raise ICLError(rc, (L.icl_last_error(None) or b"").decode())
+    data = out[:n.value].tobytes()
+    if not want_info:
+        return data
+    keys = ["passthrough", "width", "height", "new_width", "new_height", "attempts"]
+    return data, {k: int(v) for k, v in zip(keys, info)}
+
+
+def downsize_image(path, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM, want_info=False):
+    """icl_downsize_image_file (no GPU): resizeImageIfNeeded (rekognition.go:173-259) with its limits as arguments -> bytes."""
+    L = load()
+    guess = os.path.getsize(path) if os.path.exists(path) else 0
+    return _downsize_one(lambda o, c, n, i: L.icl_downsize_image_file(os.fsencode(path), max_bytes, max_dim, o, c, n, i), want_info, guess)
+
+
+def downsize_image_mem(data, max_bytes=MAX_IMAGE_SIZE, max_dim=MAX_IMAGE_DIM, want_info=False):
+    """icl_downsize_image_mem: downsize_image for an image held in memory."""
+    L = load()
+    p, nb, keep = _byte_view(data)
+    r = _downsize_one(lambda o, c, n, i: L.icl_downsize_image_mem(_vp(p), nb, max_bytes, max_dim, o, c, n, i), want_info, nb)
+    del keep
+    return r
 
 
 def load_image_224_mem(data):

@@ -31,6 +31,7 @@ struct icl_ward_ws; // ward.hip
 struct icl_ingest_ws; // jpeg_gpu.hip
 struct icl_many_ws; // ward_many.hip
 struct icl_requests_ws; // requests.hip
+struct icl_jenc_ws; // jpeg_encode_gpu.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -134,6 +135,9 @@ struct icl_ctx {
     int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
     icl_requests_ws *requests = nullptr; // device buffers and stage events of icl_cluster_requests (requests.hip; created on first use)
     double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
+    icl_jenc_ws *jenc = nullptr;         // buffers of the GPU JPEG encoder (jpeg_encode_gpu.hip; created on first use)
+    int64_t downsize_stats[6] = {0, 0, 0, 0, 0, 0}; // last icl_downsize_images[_mem]: passthrough, GPU-rebuilt, host-decoded, second attempts, bytes in, bytes out
+    double downsize_ms[3] = {0, 0, 0};              // ... host decode (thread-ms), GPU rebuild + encode, download + copy (icl_last_downsize_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
@@ -194,6 +198,7 @@ void icl_file_batcher_free(icl_ctx *ctx);
 void icl_ingest_free(icl_ctx *ctx);
 void icl_many_free(icl_ctx *ctx);
 void icl_requests_free(icl_ctx *ctx);
+void icl_jenc_free(icl_ctx *ctx);
 
 // The two batched halves icl_cluster_requests (requests.hip) joins; both expect ctx->mu held and the context's device selected.
 // Each tells its caller apart what the return code alone cannot: "the list was processed and an item of it failed" from "the call stopped".

@@ -15,6 +15,8 @@
 // check rejected.  ingest_pass = ingest_buffers, then per slab slab_collect (rows in file order from the worker threads' ingest_feed,
 // ingest_feed.h, into a pinned slab; slab_fill::fits says when a slab is full) -> run_slab_decode (upload, entropy decode, IDCT) ->
 // slab_deliver (gather / resize, forward pass, NaN rows of failed files, into the call's ingest_sink), then tally_accepted.
+// The batched downsizer at the end of the file (icl_downsize_images[_mem]) drives the same stages up to the planes, then a gather / resize
+// at each image's own size and the JPEG encoder (jpeg_encode_gpu.hip).
 #include "icl_common.h"
 #include "ingest_feed.h"
 #include "ingest_pixels.h"
@@ -375,11 +377,12 @@ struct worker_state { // buffers a worker reuses from file to file
 // One image (a file, or a memory source read in place: icl_image_src_read), on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
 // qualifies), stage A for every other JPEG the GPU takes, the whole host path for everything else.  Status codes and messages are
 // those of icl_load_image_224 (image_io.hip).
-static void process_file(const ingest_src &src, worker_state &ws, int entropy, file_result &r)
+// finish_host(rgb, w, h) turns a host-decoded image into the result's KIND_HOST payload (or fails it: it returns false after icl_fail).
+template <class FinishHost>
+static void process_file_with(const ingest_src &src, const char *path /* what the messages call the image */, worker_state &ws, int entropy, file_result &r,
+                              const FinishHost &finish_host)
 {
     icl_jpeg_coefs &J = ws.J;
-    char nbuf[96];
-    const char *path = ingest_src_name(src, nbuf, sizeof nbuf); // what the messages call the image
     auto fail_from_tls = [&](int rc) {
         r.kind = KIND_FAILED;
         r.rc = rc;
@@ -417,8 +420,7 @@ static void process_file(const ingest_src &src, worker_state &ws, int entropy, f
             const int rc = icl_image_decode(nullptr, src, path, fmt, data, len, rgb, w, h);
             if (rc) return fail_from_tls(rc);
         }
-        r.packed.resize((size_t)ICL_IMG_BYTES);
-        icl_resize_bilinear_u8(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
+        if (!finish_host(rgb, w, h)) return fail_from_tls(ICL_ERR_ARG);
         r.kind = KIND_HOST;
     } catch (const std::bad_alloc &) {
         r.kind = KIND_FAILED;
@@ -429,6 +431,16 @@ static void process_file(const ingest_src &src, worker_state &ws, int entropy, f
         r.rc = ICL_ERR_IO;
         r.err = std::string("failed to read image: ") + path + ". Decoder error";
     }
+}
+
+static void process_file(const ingest_src &src, worker_state &ws, int entropy, file_result &r)
+{
+    char nbuf[96];
+    process_file_with(src, ingest_src_name(src, nbuf, sizeof nbuf), ws, entropy, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
+        r.packed.resize((size_t)ICL_IMG_BYTES);
+        icl_resize_bilinear_u8(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
+        return true;
+    });
 }
 
 } // namespace
@@ -1059,4 +1071,442 @@ extern "C" int icl_jpeg_coefs_mem(icl_ctx *ctx, const uint8_t *const *data, cons
 {
     if (!coefs_args_ok(ctx, n, entropy_mode, cap, offsets, state) || !mem_list_ok(data, bytes, n)) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_mem: bad argument");
     return jpeg_coefs(ctx, true, nullptr, data, bytes, n, entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_mem");
+}
+
+// ---- the batched downsizer: resizeImageIfNeeded (rekognition.go:173-259) over a list, icl_downsize_images[_mem] ------------------------
+// Per image a worker thread measures the bytes (at or under the limit: passed through), and otherwise does what process_file does for the
+// ingest calls; the slab's JPEGs go through run_slab_decode to their planes, jpeg_gather_resize_var_kernel takes planes to RGB at each
+// image's own new size, host-decoded images arrive as resized RGB, and the encoder (jpeg_encode_gpu.hip) codes the slab's RGB.  The coded
+// sizes come back once per slab; images still above the limit get a second pass at half the size from the planes still held.
+namespace {
+
+struct dz_image { // one image of the variable-size gather
+    int32_t img;       // its ingest_image in the slab
+    int32_t nw, nh, area;
+    int64_t rgb_off;   // where its RGB goes in the RGB scratch
+    int64_t tab_off;   // its tables in the table buffer: int32 xofs[nw], yofs[nh], then int16 xa[2 nw], ya[2 nh]
+};
+
+// jpeg_gather_resize_kernel for an output size of the image's own: one thread per output pixel, tables from the table buffer
+__global__ void __launch_bounds__(256) jpeg_gather_resize_var_kernel(const ingest_image *__restrict__ imgs, const dz_image *__restrict__ dz, const uint8_t *__restrict__ tabs,
+                                                                     int64_t tab_bytes, const uint8_t *__restrict__ scratch, uint8_t *__restrict__ rgb, int64_t rgb_bytes)
+{
+    const dz_image &Z = dz[blockIdx.y];
+    const ingest_image &D = imgs[Z.img];
+    const int64_t npx = (int64_t)Z.nw * Z.nh;
+    if (D.kind != KIND_JPEG || Z.rgb_off < 0 || Z.rgb_off + npx * 3 > rgb_bytes || Z.tab_off < 0 || Z.tab_off + ((int64_t)Z.nw + Z.nh) * 8 > tab_bytes) return;
+    const int32_t *xofs = (const int32_t *)(tabs + Z.tab_off), *yofs = xofs + Z.nw;
+    const int16_t *xa = (const int16_t *)(yofs + Z.nh), *ya = xa + 2 * Z.nw;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npx; p += (int64_t)gridDim.x * 256) {
+        const int dy = (int)(p / Z.nw), dx = (int)(p - (int64_t)dy * Z.nw);
+        uint8_t *o = rgb + Z.rgb_off + p * 3;
+        int r[4], g[4], b[4];
+        if (Z.area) {
+            rgb_at(D, scratch, 2 * dx, 2 * dy, r[0], g[0], b[0]);
+            rgb_at(D, scratch, 2 * dx + 1, 2 * dy, r[1], g[1], b[1]);
+            rgb_at(D, scratch, 2 * dx, 2 * dy + 1, r[2], g[2], b[2]);
+            rgb_at(D, scratch, 2 * dx + 1, 2 * dy + 1, r[3], g[3], b[3]);
+            o[0] = icl_area_mean(r[0], r[1], r[2], r[3]);
+            o[1] = icl_area_mean(g[0], g[1], g[2], g[3]);
+            o[2] = icl_area_mean(b[0], b[1], b[2], b[3]);
+            continue;
+        }
+        const int sx = min(max(xofs[dx], 0), D.ow - 1), sx1 = min(sx + 1, D.ow - 1);
+        const int sy = min(max(yofs[dy], 0), D.oh - 1), sy1 = min(sy + 1, D.oh - 1);
+        rgb_at(D, scratch, sx, sy, r[0], g[0], b[0]);
+        rgb_at(D, scratch, sx1, sy, r[1], g[1], b[1]);
+        rgb_at(D, scratch, sx, sy1, r[2], g[2], b[2]);
+        rgb_at(D, scratch, sx1, sy1, r[3], g[3], b[3]);
+        const int a0 = xa[dx * 2], a1 = xa[dx * 2 + 1], b0 = ya[dy * 2], b1 = ya[dy * 2 + 1];
+        o[0] = icl_resize_linear(r[0], r[1], r[2], r[3], a0, a1, b0, b1);
+        o[1] = icl_resize_linear(g[0], g[1], g[2], g[3], a0, a1, b0, b1);
+        o[2] = icl_resize_linear(b[0], b[1], b[2], b[3], a0, a1, b0, b1);
+    }
+}
+
+constexpr int64_t DZ_RGB_BUDGET = 1ll << 30; // resized RGB of one slab on the device
+enum { DZ_PASS = 0, DZ_FAILED, DZ_GPU, DZ_HOST, DZ_DONE };
+
+struct dz_result { // what a worker hands the slab builder for one image
+    int type = DZ_FAILED;
+    file_result fr;             // DZ_GPU: as for the ingest calls; DZ_HOST: fr.packed is the resized RGB; DZ_FAILED: rc, err
+    std::vector<uint8_t> bytes; // DZ_PASS of a file (a memory source is copied from the caller's buffer); DZ_DONE: the finished file
+    std::vector<uint8_t> orig;  // DZ_HOST: the decoded image, for a second attempt
+    int ow = 0, oh = 0, nw = 0, nh = 0;
+    int attempts = 0; // DZ_DONE
+    int64_t in_bytes = 0;
+    int64_t held() const { return (int64_t)(fr.packed.size() + bytes.size() + orig.size()); }
+};
+
+static void dz_process(const ingest_src &src, worker_state &ws, int entropy, int64_t max_bytes, int max_dim, dz_result &z)
+{
+    char nbuf[96];
+    const char *name = ingest_src_name(src, nbuf, sizeof nbuf);
+    file_result &r = z.fr;
+    auto fail_from_tls = [&](int rc) {
+        z.type = DZ_FAILED;
+        r.kind = KIND_FAILED;
+        r.rc = rc;
+        r.err = icl_last_error(nullptr);
+    };
+    try {
+        const uint8_t *data = nullptr;
+        size_t len = 0;
+        const int rc = icl_src_bytes(src, name, z.bytes, data, len);
+        if (rc) return fail_from_tls(rc);
+        z.in_bytes = (int64_t)len;
+        if ((int64_t)len <= max_bytes) {
+            z.type = DZ_PASS;
+            return;
+        }
+        const ingest_src mem{nullptr, data, (int64_t)len, src.index};
+        // what cannot go through a slab is done here, start to end, by the host call
+        auto whole_on_host = [&]() {
+            int32_t info[6];
+            std::vector<uint8_t> out;
+            const int rc2 = icl_downsize_src(src, max_bytes, max_dim, out, info);
+            if (rc2) return fail_from_tls(rc2);
+            z.bytes.swap(out);
+            z.attempts = info[5];
+            z.type = DZ_DONE;
+        };
+        auto too_large = [&](int nw, int nh) { return (int64_t)nw * nh * 3 > SLAB_PAYLOAD / 4 || icl_jenc_blocks(nw, nh) > icl_jenc_max_batch_blocks() / 4; };
+        bool oversize = false;
+        process_file_with(mem, name, ws, entropy, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
+            if (icl_downsize_dims_checked(name, w, h, max_dim, z.nw, z.nh)) return false;
+            if (too_large(z.nw, z.nh)) {
+                oversize = true;
+                return true;
+            }
+            z.ow = w;
+            z.oh = h;
+            r.packed.resize((size_t)z.nw * z.nh * 3);
+            icl_resize_bilinear_u8(rgb.data(), w, h, r.packed.data(), z.nw, z.nh);
+            z.orig.swap(rgb);
+            return true;
+        });
+        if (r.kind == KIND_FAILED) {
+            z.type = DZ_FAILED;
+            return;
+        }
+        if (oversize) return whole_on_host();
+        if (r.kind == KIND_HOST) {
+            z.type = DZ_HOST;
+            z.bytes.clear();
+            z.bytes.shrink_to_fit();
+            return;
+        }
+        const bool swap = icl_exif_swaps_axes(r.orient);
+        z.ow = swap ? r.H : r.W;
+        z.oh = swap ? r.W : r.H;
+        if (icl_downsize_dims_checked(name, z.ow, z.oh, max_dim, z.nw, z.nh)) return fail_from_tls(ICL_ERR_ARG);
+        if (too_large(z.nw, z.nh)) return whole_on_host();
+        z.type = DZ_GPU;
+        z.bytes.clear();
+        z.bytes.shrink_to_fit();
+    } catch (const std::bad_alloc &) {
+        z.type = DZ_FAILED;
+        r.kind = KIND_FAILED;
+        r.rc = ICL_ERR_NOMEM;
+        r.err = std::string("failed to read image: ") + name + ". Out of host memory while decoding";
+    } catch (...) {
+        z.type = DZ_FAILED;
+        r.kind = KIND_FAILED;
+        r.rc = ICL_ERR_IO;
+        r.err = std::string("failed to read image: ") + name + ". Decoder error";
+    }
+}
+
+struct dz_entry { // one image of a slab, in list order
+    int64_t row;
+    std::unique_ptr<dz_result> z;
+    int img = -1, scan = -1; // DZ_GPU: its ingest_image; its place among the slab's stream images (-1: entropy-decoded on the host)
+    int slot[2] = {-1, -1};  // its file in the first / second encoder batch
+};
+
+struct dz_ws { // device buffers of the call
+    dev_guard d_dz, d_tabs, d_rgb;
+    int64_t dz_cap = 0, tabs_cap = 0, rgb_cap = 0;
+};
+
+static int dz_grow(icl_ctx *ctx, dev_guard &g, int64_t &cap, int64_t need)
+{
+    if (cap >= need) return ICL_OK;
+    if (g.p) (void)hipFree(g.p);
+    g.p = nullptr;
+    cap = 0;
+    if (hipMalloc(&g.p, (size_t)need) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "downsize: device buffer of %lld bytes", (long long)need);
+    cap = need;
+    return ICL_OK;
+}
+
+// One encoder batch over the entries `which` of a slab at attempt a (0: nw x nh, 1: half of it): gather / upload their RGB, encode, and
+// bring the files to the host.  files / off: the batch's files; entry e's is slot[a].
+static int dz_encode_pass(icl_ctx *ctx, icl_ingest_ws *ws, dz_ws &B, std::vector<dz_entry> &E, const std::vector<int> &which, int a, std::vector<uint8_t> &files,
+                          std::vector<int64_t> &off)
+{
+    hipStream_t st = ctx->stream;
+    std::vector<dz_image> dz;
+    std::vector<uint8_t> tabs;
+    std::vector<icl_jenc_item> items;
+    std::vector<std::vector<uint8_t>> host_rgb; // second attempt of host-decoded images
+    int64_t rgb_used = 0, max_px = 0;
+    for (int e : which) {
+        dz_entry &X = E[(size_t)e];
+        const dz_result &z = *X.z;
+        const int nw = a ? z.nw / 2 : z.nw, nh = a ? z.nh / 2 : z.nh;
+        X.slot[a] = (int)items.size();
+        items.push_back(icl_jenc_item{rgb_used, nw, nh});
+        if (z.type == DZ_GPU) {
+            dz_image Z;
+            Z.img = X.img;
+            Z.nw = nw;
+            Z.nh = nh;
+            Z.area = icl_resize_is_area(z.ow, z.oh, nw, nh) ? 1 : 0;
+            Z.rgb_off = rgb_used;
+            Z.tab_off = (int64_t)tabs.size();
+            tabs.resize(tabs.size() + (size_t)align16(((int64_t)nw + nh) * 8));
+            int32_t *xofs = (int32_t *)(tabs.data() + Z.tab_off), *yofs = xofs + nw;
+            int16_t *xa = (int16_t *)(yofs + nh), *ya = xa + 2 * nw;
+            icl_resize_coeffs(nw, z.ow, xofs, xa);
+            icl_resize_coeffs(nh, z.oh, yofs, ya);
+            dz.push_back(Z);
+            max_px = std::max(max_px, (int64_t)nw * nh);
+        }
+        rgb_used += align16((int64_t)nw * nh * 3);
+    }
+    ICL_TRY(dz_grow(ctx, B.d_rgb, B.rgb_cap, std::max<int64_t>(rgb_used, 16)));
+    size_t k = 0;
+    for (int e : which) { // host-decoded images: their RGB as it stands
+        const dz_result &z = *E[(size_t)e].z;
+        const icl_jenc_item &it = items[k++];
+        if (z.type != DZ_HOST) continue;
+        const uint8_t *src = z.fr.packed.data();
+        if (a) {
+            host_rgb.emplace_back((size_t)it.w * it.h * 3);
+            icl_resize_bilinear_u8(z.orig.data(), z.ow, z.oh, host_rgb.back().data(), it.w, it.h);
+            src = host_rgb.back().data();
+        }
+        ICL_HIP(ctx, hipMemcpyAsync((uint8_t *)B.d_rgb.p + it.rgb_off, src, (size_t)it.w * it.h * 3, hipMemcpyHostToDevice, st));
+    }
+    if (!dz.empty()) {
+        ICL_TRY(dz_grow(ctx, B.d_dz, B.dz_cap, (int64_t)(dz.size() * sizeof(dz_image))));
+        ICL_TRY(dz_grow(ctx, B.d_tabs, B.tabs_cap, (int64_t)tabs.size()));
+        ICL_HIP(ctx, hipMemcpyAsync(B.d_dz.p, dz.data(), dz.size() * sizeof(dz_image), hipMemcpyHostToDevice, st));
+        ICL_HIP(ctx, hipMemcpyAsync(B.d_tabs.p, tabs.data(), tabs.size(), hipMemcpyHostToDevice, st));
+        const unsigned gx = (unsigned)std::min<int64_t>(icl_ceil_div(max_px, 256), 8192);
+        hipLaunchKernelGGL(jpeg_gather_resize_var_kernel, dim3(gx, (unsigned)dz.size()), dim3(256), 0, st, (const ingest_image *)ws->dev().imgs, (const dz_image *)B.d_dz.p,
+                           (const uint8_t *)B.d_tabs.p, (int64_t)tabs.size(), (const uint8_t *)ws->d_scratch, (uint8_t *)B.d_rgb.p, B.rgb_cap);
+        ICL_HIP(ctx, hipGetLastError());
+    }
+    ICL_HIP(ctx, hipStreamSynchronize(st)); // (the host vectors above go out of scope; the encoder synchronises anyway)
+    const uint8_t *d_files = nullptr;
+    ICL_TRY(icl_jenc_run(ctx, (const uint8_t *)B.d_rgb.p, items.data(), (int64_t)items.size(), ICL_DOWNSIZE_QUALITY, &d_files, off));
+    files.resize((size_t)std::max<int64_t>(off.back(), 1));
+    if (off.back()) ICL_HIP(ctx, hipMemcpy(files.data(), d_files, (size_t)off.back(), hipMemcpyDeviceToHost));
+    return ICL_OK;
+}
+
+static int downsize_images_locked(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int64_t max_bytes, int max_dim, int32_t threads, uint8_t *out, int64_t cap,
+                                  int64_t *out_off, int32_t *status, const char *what)
+{
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    for (int q = 0; q < 6; ++q) ctx->downsize_stats[q] = 0;
+    ctx->downsize_ms[0] = ctx->downsize_ms[1] = ctx->downsize_ms[2] = 0;
+    out_off[0] = 0;
+    if (n == 0) return ICL_OK;
+    const int entropy = ctx->entropy_mode;
+    icl_ingest_ws *ws = nullptr;
+    ICL_TRY(ingest_ws(ctx, ws));
+    if (entropy == ICL_ENTROPY_GPU) ICL_TRY(entropy_ws(ctx, ws, SLAB_IMAGES));
+    dz_ws B;
+    int64_t at = 0, npass = 0, ngpu = 0, nhost = 0, nsecond = 0, bytes_in = 0;
+    std::vector<file_fail> fails;
+    auto deliver = [&](int64_t row, const uint8_t *p, int64_t len) {
+        out_off[row] = at;
+        if (out && len && at + len <= cap) memcpy(out + at, p, (size_t)len);
+        at += len;
+    };
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(n, threads > 0 ? threads : (int)std::min(16u, hw)));
+    std::atomic<int64_t> decode_ns{0};
+    auto decode = [&](int64_t i) -> std::unique_ptr<dz_result> {
+        thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state());
+        const auto t0 = clk::now();
+        std::unique_ptr<dz_result> z(wst ? new (std::nothrow) dz_result() : nullptr);
+        if (z) dz_process(srcs[i], *wst, entropy, max_bytes, max_dim, *z);
+        decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(clk::now() - t0).count();
+        return z;
+    };
+    {
+        ingest_feed<dz_result> feed(n, nthr, 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, decode, [](const dz_result &z) { return z.held(); });
+        std::vector<dz_entry> E;
+        std::vector<uint8_t> files[2];
+        std::vector<int64_t> off[2];
+        for (int64_t k = 0; feed.taken() < n; ++k) {
+            const int q = (int)(k & 1);
+            ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[q]));
+            const slab_view S = ws->host(q);
+            slab_fill F;
+            E.clear();
+            int64_t rgb = 0, blocks = 0, coded = 0, finished = 0;
+            // ---- collect: images in list order until the slab, the RGB scratch or the encoder's batch is full.  Finished results
+            // (passed-through files, whole-on-host outputs) leave the feed's byte budget when they are taken and wait in E for their
+            // turn: a round ends once it holds 2 * SLAB_PAYLOAD of them, so a long run of small files is delivered as it goes ----
+            while (feed.taken() < n) {
+                const dz_result *next = feed.peek();
+                if (!next) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", what);
+                if (next->type == DZ_GPU || next->type == DZ_HOST) {
+                    const int64_t r3 = align16((int64_t)next->nw * next->nh * 3), nb = icl_jenc_blocks(next->nw, next->nh);
+                    const bool room = rgb + r3 <= DZ_RGB_BUDGET && blocks + nb <= icl_jenc_max_batch_blocks() && coded < icl_jenc_max_batch_images() &&
+                                      (next->type == DZ_HOST || (F.nimg < SLAB_IMAGES && F.fits(next->fr)));
+                    if (!room && rgb > 0) break;
+                    rgb += r3;
+                    blocks += nb;
+                    ++coded;
+                } else {
+                    if (finished > 2 * SLAB_PAYLOAD && !E.empty()) break;
+                    finished += (int64_t)next->bytes.size();
+                }
+                dz_entry X;
+                X.row = feed.taken();
+                X.z = feed.take();
+                if (X.z->type == DZ_GPU) {
+                    memset(&S.imgs[F.nimg], 0, offsetof(ingest_image, xofs));
+                    X.img = F.nimg;
+                    X.scan = X.z->fr.kind == KIND_JSTREAM ? F.nscan : -1;
+                    if (!place_jpeg(X.z->fr, F, S)) {
+                        char nbuf[96];
+                        return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, ingest_src_name(srcs[X.row], nbuf, sizeof nbuf));
+                    }
+                    ++F.nimg;
+                }
+                E.push_back(std::move(X));
+            }
+            // ---- planes, first attempt, second attempt ----
+            const auto t_gpu = clk::now();
+            std::vector<int> first, second;
+            for (size_t e = 0; e < E.size(); ++e)
+                if (E[e].z->type == DZ_GPU || E[e].z->type == DZ_HOST) first.push_back((int)e);
+            if (F.nimg) {
+                int64_t upload = 0;
+                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload));
+                ICL_HIP(ctx, hipEventRecord(ws->ev_up[q], ctx->stream));
+                if (F.nscan) ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, (size_t)F.nscan * 4, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            if (!first.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, E, first, 0, files[0], off[0])); // (synchronises: h_accepted is there)
+            auto accepted = [&](const dz_entry &X) { return X.scan < 0 || ws->h_accepted[X.scan] != 0; };
+            for (int e : first) {
+                const dz_entry &X = E[(size_t)e];
+                const int64_t len = off[0][(size_t)X.slot[0] + 1] - off[0][(size_t)X.slot[0]];
+                if (accepted(X) && len > max_bytes && X.z->nw / 2 >= 1 && X.z->nh / 2 >= 1) second.push_back(e);
+            }
+            if (!second.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, E, second, 1, files[1], off[1]));
+            ctx->downsize_ms[1] += ms_since(t_gpu);
+            // ---- deliver in list order ----
+            const auto t_out = clk::now();
+            for (dz_entry &X : E) {
+                dz_result &z = *X.z;
+                bytes_in += z.in_bytes;
+                if (status) status[X.row] = z.type == DZ_FAILED ? (z.fr.rc ? z.fr.rc : ICL_ERR_IO) : ICL_OK;
+                if (z.type == DZ_GPU && !accepted(X)) { // the GPU entropy check rejected its stream: the host call redoes it and reports what it finds
+                    int32_t info[6];
+                    const int rc = icl_downsize_src(srcs[X.row], max_bytes, max_dim, z.bytes, info);
+                    if (rc) {
+                        z.type = DZ_FAILED;
+                        z.fr.rc = rc;
+                        z.fr.err = icl_last_error(nullptr);
+                        if (status) status[X.row] = rc;
+                    } else {
+                        z.type = DZ_DONE;
+                        z.attempts = info[5];
+                    }
+                }
+                switch (z.type) {
+                case DZ_PASS: {
+                    const ingest_src &s = srcs[X.row];
+                    deliver(X.row, s.path ? z.bytes.data() : s.data, z.in_bytes);
+                    ++npass;
+                    break;
+                }
+                case DZ_DONE:
+                    deliver(X.row, z.bytes.data(), (int64_t)z.bytes.size());
+                    ++nhost;
+                    nsecond += z.attempts == 2;
+                    break;
+                case DZ_GPU:
+                case DZ_HOST: {
+                    const int a = X.slot[1] >= 0 ? 1 : 0;
+                    const int64_t lo = off[a][(size_t)X.slot[a]], hi = off[a][(size_t)X.slot[a] + 1];
+                    deliver(X.row, files[a].data() + lo, hi - lo);
+                    (z.type == DZ_GPU ? ngpu : nhost) += 1;
+                    nsecond += a;
+                    break;
+                }
+                default:
+                    deliver(X.row, nullptr, 0);
+                    fails.push_back(file_fail{X.row, z.fr.rc ? z.fr.rc : ICL_ERR_IO, z.fr.err});
+                    break;
+                }
+            }
+            ctx->downsize_ms[2] += ms_since(t_out);
+        }
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    out_off[n] = at;
+    ctx->downsize_stats[0] = npass;
+    ctx->downsize_stats[1] = ngpu;
+    ctx->downsize_stats[2] = nhost;
+    ctx->downsize_stats[3] = nsecond;
+    ctx->downsize_stats[4] = bytes_in;
+    ctx->downsize_stats[5] = at;
+    ctx->downsize_ms[0] = (double)decode_ns.load() * 1e-6;
+    if (!out || at > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small (%lld bytes needed)", what, (long long)at);
+    const file_fail *lowest = nullptr;
+    for (const file_fail &f : fails)
+        if (!lowest || f.index < lowest->index) lowest = &f;
+    if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
+    return ICL_OK;
+}
+
+} // namespace
+
+static int downsize_images(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int64_t max_bytes,
+                           int32_t max_dim, int32_t threads, uint8_t *out, int64_t cap, int64_t *out_off, int32_t *status, const char *what)
+{
+    if (!ctx || n < 0 || !out_off || cap < 0 || max_bytes < 0 || max_dim < 1 || threads < 0 || (mem ? !mem_list_ok(data, bytes, n) : (n && !paths)))
+        return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    for (int64_t i = 0; !mem && i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return no_throw(ctx, what, [&]() -> int {
+        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        return downsize_images_locked(ctx, srcs.data(), n, max_bytes, max_dim, threads, out, cap, out_off, status, what);
+    });
+}
+
+extern "C" int icl_downsize_images(icl_ctx *ctx, const char *const *paths, int64_t n, int64_t max_bytes, int32_t max_dim, int32_t threads, uint8_t *out, int64_t cap,
+                                   int64_t *out_off, int32_t *status)
+{
+    return downsize_images(ctx, false, paths, nullptr, nullptr, n, max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images");
+}
+
+extern "C" int icl_downsize_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int64_t max_bytes, int32_t max_dim, int32_t threads,
+                                       uint8_t *out, int64_t cap, int64_t *out_off, int32_t *status)
+{
+    return downsize_images(ctx, true, nullptr, data, bytes, n, max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images_mem");
+}
+
+extern "C" int icl_last_downsize_stats(icl_ctx *ctx, int64_t *passthrough, int64_t *gpu_rebuilt, int64_t *host_decoded, int64_t *second_attempts, int64_t *bytes_in,
+                                       int64_t *bytes_out, double *stage_ms)
+{
+    if (!ctx) return ICL_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int64_t *dst[6] = {passthrough, gpu_rebuilt, host_decoded, second_attempts, bytes_in, bytes_out};
+    for (int q = 0; q < 6; ++q)
+        if (dst[q]) *dst[q] = ctx->downsize_stats[q];
+    for (int q = 0; q < 3 && stage_ms; ++q) stage_ms[q] = ctx->downsize_ms[q];
+    return ICL_OK;
 }

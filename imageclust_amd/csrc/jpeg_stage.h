@@ -92,3 +92,29 @@ int icl_read_image_224(icl_ctx *ctx, const ingest_src &src, uint8_t *out);
 void icl_apply_exif_orientation(std::vector<uint8_t> &rgb, int &w, int &h, int orient);
 void icl_resize_bilinear_u8(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
 void icl_resize_coeffs(int dn, int sn, int32_t *ofs, int16_t *al); // cv::resize INTER_LINEAR source offsets + 11-bit weights
+
+// jpeg_encode.hip: the host JPEG encoder (arithmetic and tables: jpeg_encode_pixels.h) and the two-call delivery of a finished file
+struct icl_jenc_tables;
+void icl_jenc_encode_host(const uint8_t *rgb, int w, int h, const icl_jenc_tables &T, std::vector<uint8_t> &out);
+int64_t icl_jenc_bound(int w, int h);
+int icl_deliver_bytes(const std::vector<uint8_t> &file, uint8_t *out, int64_t cap, int64_t *bytes, const char *what);
+// jpeg_encode.hip: resizeImageIfNeeded (rekognition.go:173-259).  The size rule for an oriented image of R rows and C columns, quirk
+// included (false: newW or newH < 1); the whole host route for one source (info[6]: imageclust.h), which the batched call
+// (jpeg_gpu.hip) also takes for what the GPU does not.
+constexpr int ICL_DOWNSIZE_QUALITY = 95;
+bool icl_downsize_dims(int R, int C, int max_dim, int &newW, int &newH);
+int icl_downsize_dims_checked(const char *name, int w, int h, int max_dim, int &nw, int &nh); // ... of a w x h image; ICL_ERR_ARG names the sizes
+int icl_src_bytes(const ingest_src &src, const char *name, std::vector<uint8_t> &file, const uint8_t *&data, size_t &len); // a source's bytes as they stand
+int icl_downsize_src(const ingest_src &src, int64_t max_bytes, int max_dim, std::vector<uint8_t> &out, int32_t *info);
+// jpeg_encode_gpu.hip: one batch of the GPU encoder (ctx->mu held, device selected): image i is d_rgb + items[i].rgb_off; the files
+// land in the encoder's own device buffer *d_files, file i at off[i] .. off[i + 1] (valid until the next batch).  A batch holds at most
+// icl_jenc_max_batch_blocks() blocks (icl_jenc_blocks of each image) and icl_jenc_max_batch_images() images.  Returns with the stream
+// synchronised.
+struct icl_jenc_item {
+    int64_t rgb_off;
+    int32_t w, h;
+};
+int64_t icl_jenc_max_batch_blocks();
+int64_t icl_jenc_max_batch_images();
+int64_t icl_jenc_blocks(int w, int h);
+int icl_jenc_run(icl_ctx *ctx, const uint8_t *d_rgb, const icl_jenc_item *items, int64_t n, int quality, const uint8_t **d_files, std::vector<int64_t> &off);

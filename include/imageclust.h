@@ -404,6 +404,44 @@ int icl_cluster_requests_mem(icl_ctx *ctx, int32_t nreq, const uint8_t *const *d
                              int32_t *merges, int32_t *status /* nreq */, int32_t *file_status /* sum n[r] */, float *E_out);
 int icl_jpeg_coefs_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
                        int64_t *offsets /* n + 1 */, int32_t *state /* n */);
+/* ---- the label service's downsizer: resizeImageIfNeeded (internal/rekognition/rekognition.go:173-259) and the JPEG encoder it needs ----
+ * icl_jpeg_encode_rgb (host only): interleaved u8 RGB -> a complete JPEG file, the bytes libjpeg(-turbo) writes after jpeg_set_defaults +
+ * jpeg_set_quality(quality, TRUE): baseline SOF0, YCbCr 4:2:0, Annex K Huffman tables, islow DCT, JFIF 1.01 (pinned byte for byte to Pillow;
+ * cv::imwrite(".jpg") makes the same libjpeg calls).  *bytes receives the file's size; out == NULL asks for the size alone; cap < size is
+ * ICL_ERR_ARG with *bytes set.  quality 1..100, 1 <= w, h <= 65535, else ICL_ERR_ARG.
+ * icl_jpeg_encode_bound(w, h): an upper bound on that size for every image and quality (0 for a size the encoder rejects): 625 header and
+ * EOI bytes + per 8x8 block 64 coefficients of at most 27 bits (a 16-bit code + 11 amplitude bits; ZRL and EOB only replace zeros and cost
+ * less), i.e. 216 bytes, doubled for the 0x00 stuffed behind every 0xFF, over the 6 blocks of each 16x16 MCU, + 2 for the padded last byte.
+ * icl_jpeg_encode_rgb_dev: the same files for n resident images in one call on the context's stream.  Image i is d_rgb + offsets[i],
+ * w[i] x h[i]; file i is out[out_off[i] .. out_off[i + 1]) (out_off: host, n + 1).  out_on_device != 0: out is device memory.  cap too
+ * small is ICL_ERR_ARG with out_off filled (out_off[n] is the size needed) and out unspecified.
+ * icl_downsize_image_file / _mem (host only): resizeImageIfNeeded with its limits as arguments (the reference: 5 MiB, 2048).  bytes <=
+ * max_bytes: the input comes back unchanged, undecoded, image or not.  Otherwise IMRead(IMReadColor) (EXIF orientation applied), and with
+ * R rows, C columns: ratio = double(C) / R; R > C ? (newW = max_dim, newH = int(max_dim * ratio)) : (newH = max_dim, newW = int(max_dim /
+ * ratio)) -- THE REFERENCE READS gocv's Size() = [rows, cols] AS (width, height), SO A 4000x3000 LANDSCAPE PHOTO BECOMES 1536 WIDE x 2048 HIGH;
+ * a drop-in keeps that distortion.  cv::resize INTER_LINEAR, JPEG at quality 95; still above max_bytes: once more at newW / 2 x newH / 2 from
+ * the decoded original, returned whatever its size (a halved size of 0 returns the first result).  newW or newH < 1: ICL_ERR_ARG.  A file the
+ * decoders reject returns their code and message.  Two-call size query as above.  info (may be NULL): passthrough (0 / 1), decoded W, H
+ * (after orientation), final newW, newH, attempts (0 for a passthrough).
+ * icl_downsize_images / _mem: the batched form.  Row i belongs to image i: output i is out[out_off[i] .. out_off[i + 1]) and equals
+ * icl_downsize_image_mem's on the same bytes, in both entropy modes and for any threads.  A failed image fails alone (status[i], empty range);
+ * the call returns the code of the lowest failed index.  Images at or under the limit are copied on the host; JPEGs above it are rebuilt on
+ * the GPU from their coefficients (planes -> gather + resize at the new size -> encoder kernels); PNG, PPM and JPEGs too large for a slab
+ * are decoded and resized on the host and encoded on the GPU.  cap too small: ICL_ERR_ARG, out_off[n] is the size needed.
+ * icl_last_downsize_stats: counts of the last batched call (passthrough + gpu_rebuilt + host_decoded + failed == n) and its stage times. */
+int64_t icl_jpeg_encode_bound(int32_t w, int32_t h);
+int icl_jpeg_encode_rgb(const uint8_t *rgb, int32_t w, int32_t h, int32_t quality, uint8_t *out, int64_t cap, int64_t *bytes);
+int icl_jpeg_encode_rgb_dev(icl_ctx *ctx, const uint8_t *d_rgb, const int64_t *offsets, const int32_t *w, const int32_t *h, int64_t n, int32_t quality,
+                            uint8_t *out, int32_t out_on_device, int64_t cap, int64_t *out_off /* n + 1 */);
+int icl_downsize_image_file(const char *path, int64_t max_bytes, int32_t max_dim, uint8_t *out, int64_t cap, int64_t *bytes, int32_t *info /* 6 */);
+int icl_downsize_image_mem(const uint8_t *data, int64_t in_bytes, int64_t max_bytes, int32_t max_dim, uint8_t *out, int64_t cap, int64_t *bytes,
+                           int32_t *info /* 6 */);
+int icl_downsize_images(icl_ctx *ctx, const char *const *paths, int64_t n, int64_t max_bytes, int32_t max_dim, int32_t threads, uint8_t *out,
+                        int64_t cap, int64_t *out_off /* n + 1 */, int32_t *status /* n */);
+int icl_downsize_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int64_t max_bytes, int32_t max_dim,
+                            int32_t threads, uint8_t *out, int64_t cap, int64_t *out_off /* n + 1 */, int32_t *status /* n */);
+int icl_last_downsize_stats(icl_ctx *ctx, int64_t *passthrough, int64_t *gpu_rebuilt, int64_t *host_decoded, int64_t *second_attempts, int64_t *bytes_in,
+                            int64_t *bytes_out, double *stage_ms /* 3: host decode (thread-ms), GPU rebuild + encode, download + copy */);
 /* workflow.go:84-94 on one GPU in one call: embed n resident images (2048-d pooled head, into d_E: device, n x 2048) and
  * cluster them.  flags & ICL_FUSE_OVERLAP: the distance rows of already-embedded images are computed on a side stream of the
  * context while later batches embed (same kernels, same results as icl_embed_u8_dev + icl_cluster_dev, bit for bit). */
