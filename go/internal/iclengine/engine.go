@@ -110,6 +110,39 @@ func LastManyStats() (small, mid, large, midGroups int64, err error) {
 	return int64(a), int64(b), int64(c), int64(d), nil
 }
 
+// Where a qualifying PNG of the batched file calls is inflated and unfiltered: icl_set_png_options' modes.
+const (
+	PNGHost = int(C.ICL_PNG_HOST)
+	PNGGPU  = int(C.ICL_PNG_GPU)
+)
+
+// SetPNGOptions chooses whether the batched file calls (ClusterRequests and the embedding calls behind it) decode qualifying PNGs on the
+// GPU (same rows, status codes and messages in both modes).
+func SetPNGOptions(pngMode int) error {
+	raw, e := Ctx()
+	if e != nil {
+		return e
+	}
+	if rc := C.icl_set_png_options((*C.icl_ctx)(raw), C.int(pngMode)); rc != C.ICL_OK {
+		return fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return nil
+}
+
+// LastPNGStats reports what the last batched file call did with its PNGs: decoded on the GPU, decoded by the host because of the routing
+// rule, rejected by the GPU check and redone by the host, zlib stream bytes uploaded.
+func LastPNGStats() (gpuPNGs, hostPNGs, redoneOnHost, streamBytes int64, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return 0, 0, 0, 0, e
+	}
+	var a, b, c, d C.int64_t
+	if rc := C.icl_last_png_stats((*C.icl_ctx)(raw), &a, &b, &c, &d); rc != C.ICL_OK {
+		return 0, 0, 0, 0, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return int64(a), int64(b), int64(c), int64(d), nil
+}
+
 // Request is one workflow.Run call's input as icl_cluster_requests takes it: the image files, each image's label columns within
 // the request's label set (GenerateLabelVector's indices; -1 for a label the set does not hold) and the size constraints.
 type Request struct {

@@ -24,6 +24,7 @@ CONV_SPLIT = 16
 ROWS_SINGLE, ROWS_EXACT_BATCH, ROWS_LW_BOUND, ROWS_LW_FAST = 0, 1, 2, 3
 FILE_FAIL_NEXT_LEADER = 0x100
 MANY_MID_AUTO, MANY_MID_OFF, MANY_MID_ON = 0, 1, 2  # icl_set_many_options: the mid-size route (257 to 2048 rows) of icl_cluster_many
+PNG_HOST, PNG_GPU = 0, 1  # icl_set_png_options: where a qualifying PNG of a batched file call is inflated and unfiltered
 ENTROPY_HOST, ENTROPY_GPU = 0, 1  # icl_set_ingest_options: where the Huffman decoder of a qualifying baseline JPEG runs
 K_CONV, K_DIST_EXACT, K_DIST_MFMA, K_ROWMIN, K_UPDATE, K_EMBED_OTHER, K_CONV64 = range(7)
 K_NAMES = ["conv_igemm_kernel<*,128>", "ward_dist_exact_kernel", "dist_mfma_kernel", "row_argmin_*_kernel",
@@ -70,6 +71,11 @@ SYMBOLS = [
     ("icl_last_entropy_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_jpeg_coefs_files", _int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
     ("icl_jpeg_coefs_file_host", _int, [C.c_char_p, _int, _vp, _i64, _pi64, _vp]),
+    ("icl_set_png_options", _int, [_vp, _int]),
+    ("icl_last_png_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
+    ("icl_png_raw_files", _int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp]),
+    ("icl_png_raw_file_host", _int, [C.c_char_p, _int, _vp, _i64, _pi64, _vp]),
+    ("icl_png_raw_mem_host", _int, [_vp, _i64, _int, _vp, _i64, _pi64, _vp]),
     ("icl_decode_image_mem", _int, [_vp, _i64, _vp, _i64, _pi32, _pi32]),
     ("icl_load_image_224_mem", _int, [_vp, _i64, _vp]),
     ("icl_preprocess_mem", _int, [_vp, _i64, _vp]),
@@ -670,6 +676,27 @@ class Context:
         check(self.h, self.L.icl_jpeg_coefs_files(self.h, arr, len(enc), entropy, buf.ctypes.data, buf.size, off.ctypes.data, state.ctypes.data))
         return [buf[off[i]:off[i + 1]] for i in range(len(enc))], state
 
+    def set_png_options(self, png=PNG_HOST):
+        """icl_set_png_options: PNG_GPU inflates and unfilters qualifying PNGs of the batched file calls on the GPU (same rows, statuses, messages)."""
+        check(self.h, self.L.icl_set_png_options(self.h, png))
+
+    def last_png_stats(self):
+        a, b, c, d = _i64(), _i64(), _i64(), _i64()
+        check(self.h, self.L.icl_last_png_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"gpu_pngs": a.value, "host_pngs": b.value, "redone_on_host": c.value, "stream_bytes": d.value}
+
+    def png_raw_files(self, paths, stage=0):
+        """icl_png_raw_files (test hook) -> ([uint8 bytes of file i: the inflated stream (stage 0) or the unfiltered scanlines (stage 1)],
+        state int32[n]): state 1 = accepted, 0 = rejected by the GPU check, -1 = does not qualify for the GPU route."""
+        enc = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        off = np.zeros(len(enc) + 1, np.int64)
+        state = np.zeros(len(enc), np.int32)
+        check(self.h, self.L.icl_png_raw_files(self.h, arr, len(enc), stage, None, 0, off.ctypes.data, state.ctypes.data))
+        buf = np.zeros(max(1, int(off[-1])), np.uint8)
+        check(self.h, self.L.icl_png_raw_files(self.h, arr, len(enc), stage, buf.ctypes.data, buf.size, off.ctypes.data, state.ctypes.data))
+        return [buf[off[i]:off[i + 1]] for i in range(len(enc))], state
+
     def last_error(self):
         msg = self.L.icl_last_error(self.h)
         return msg.decode() if msg else ""
@@ -1221,6 +1248,22 @@ def jpeg_coefs_file_host(path, sub_bits=0):
     check(None, L.icl_jpeg_coefs_file_host(os.fsencode(path), sub_bits, out.ctypes.data, out.size, C.byref(need), info.ctypes.data))
     keys = ["state", "ncomp", "blocks0", "blocks1", "blocks2", "rounds", "nsub", "nintervals"]
     return out[:need.value], dict(zip(keys, (int(v) for v in info)))
+
+
+PNG_INFO_KEYS = ["state", "w", "h", "depth", "ctype", "stored", "fixed", "dynamic", "max_code_len", "max_dist", "overlaps", "ring_wraps"]
+
+
+def png_raw_file_host(path, stage=0):
+    """icl_png_raw_file_host (no GPU): the GPU PNG route's schedule run as a host loop -> (uint8 array, info dict).  stage 0: the inflated
+    stream, 1: the unfiltered scanlines (filter bytes kept), 2: RGB by the sample-to-RGB rule.  info["state"]: 1 = accepted, 0 = rejected
+    (no bytes), -1 = does not qualify (no bytes)."""
+    L = load()
+    need = _i64()
+    info = np.zeros(12, np.int32)
+    check(None, L.icl_png_raw_file_host(os.fsencode(path), stage, None, 0, C.byref(need), info.ctypes.data))
+    out = np.zeros(max(1, need.value), np.uint8)
+    check(None, L.icl_png_raw_file_host(os.fsencode(path), stage, out.ctypes.data, out.size, C.byref(need), info.ctypes.data))
+    return out[:need.value], dict(zip(PNG_INFO_KEYS, (int(v) for v in info)))
 
 
 def load_image_224(path):

@@ -133,6 +133,8 @@ struct icl_ctx {
     double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode
     int entropy_mode = 0;                 // icl_set_ingest_options: ICL_ENTROPY_HOST / ICL_ENTROPY_GPU (environment: ICL_JPEG_ENTROPY=gpu)
     int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
+    int png_mode = 0;                     // icl_set_png_options: ICL_PNG_HOST / ICL_PNG_GPU (environment: ICL_PNG_INFLATE=gpu)
+    int64_t png_stats[4] = {0, 0, 0, 0};  // last batched file call: PNGs decoded on the GPU, by the host route, redone on the host, zlib stream bytes
     icl_requests_ws *requests = nullptr; // device buffers and stage events of icl_cluster_requests (requests.hip; created on first use)
     double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
     icl_jenc_ws *jenc = nullptr;         // buffers of the GPU JPEG encoder (jpeg_encode_gpu.hip; created on first use)
@@ -247,10 +249,11 @@ static inline std::vector<ingest_src> ingest_mem_srcs(const uint8_t *const *data
 // lowest (may be NULL) then names that image -- or the error that stopped it (lowest->index stays -1).
 int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
                  icl_item_failure *lowest = nullptr);
-static inline void icl_ingest_stats_reset(icl_ctx *ctx) // what a batched file call reports (icl_last_ingest_stats, icl_last_entropy_stats)
+static inline void icl_ingest_stats_reset(icl_ctx *ctx) // what a batched file call reports (icl_last_ingest_stats, icl_last_entropy_stats, icl_last_png_stats)
 {
     ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
     ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
+    ctx->png_stats[0] = ctx->png_stats[1] = ctx->png_stats[2] = ctx->png_stats[3] = 0;
     ctx->ingest_decode_s = 0;
 }
 // ward_many.hip: icl_cluster_many[_dev] after the argument check (d_E on the device, or h_E on the host and uploaded there).  Returns the

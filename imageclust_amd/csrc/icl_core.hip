@@ -68,6 +68,7 @@ extern "C" int icl_create(int device, icl_ctx **out)
         if (v >= ICL_CONV_P8_OFF && v <= ICL_CONV_P8_ALL) c->conv_p8 = v;
     }
     if (const char *ej = getenv("ICL_JPEG_ENTROPY")) c->entropy_mode = strcmp(ej, "gpu") == 0 ? ICL_ENTROPY_GPU : ICL_ENTROPY_HOST;
+    if (const char *ep = getenv("ICL_PNG_INFLATE")) c->png_mode = strcmp(ep, "gpu") == 0 ? ICL_PNG_GPU : ICL_PNG_HOST;
     if (const char *em = getenv("ICL_MANY_MID"))
         c->many_mid = strcmp(em, "on") == 0 ? ICL_MANY_MID_ON : strcmp(em, "off") == 0 ? ICL_MANY_MID_OFF : ICL_MANY_MID_AUTO;
     *out = c;

@@ -6,13 +6,14 @@
 //   ingest_image[nimg]  one per output row: kind, sizes, orientation, plane offsets, the host-computed resize tables
 //   ingest_plane[np]    one per JPEG component: block range, payload offsets, quantisation table
 //   payload             per component: uint32 block offsets (nblocks + 1), then the int16 coefficients of every block in
-//                       zig-zag order up to its last non-zero one; PNG / PPM / fallback images as finished 224x224x3 rows
+//                       zig-zag order up to its last non-zero one; PNG / PPM / fallback images as finished 224x224x3 rows;
+//                       with ICL_PNG_GPU a qualifying PNG as icl_png_desc + its zlib stream (KIND_PSTREAM; kernels: png_gpu.hip)
 // Kernels: jpeg_idct_kernel (one thread per 8x8 block -> u8 planes in a scratch), jpeg_gather_resize_kernel (one thread per
 // output pixel: reads the 2x2 source pixels of the resize through the orientation map, upsamples the chroma at those
 // positions only, converts the colour and resizes).  Nothing is built at full-resolution RGB.
 //
-// Host driver: ingest_files = one ingest_pass in the context's entropy mode + a repair pass in host mode over the files the GPU entropy
-// check rejected.  ingest_pass = ingest_buffers, then per slab slab_collect (rows in file order from the worker threads' ingest_feed,
+// Host driver: ingest_files = one ingest_pass in the context's entropy and PNG modes (ingest_modes) + a repair pass with both on the host over
+// the files the GPU entropy check or the GPU PNG check (png_gpu.hip) rejected.  ingest_pass = ingest_buffers, then per slab slab_collect (rows in file order from the worker threads' ingest_feed,
 // ingest_feed.h, into a pinned slab; slab_fill::fits says when a slab is full) -> run_slab_decode (upload, entropy decode, IDCT) ->
 // slab_deliver (gather / resize, forward pass, NaN rows of failed files, into the call's ingest_sink), then tally_accepted.
 // The batched downsizer at the end of the file (icl_downsize_images[_mem]) drives the same stages up to the planes, then a gather / resize
@@ -20,7 +21,9 @@
 #include "icl_common.h"
 #include "ingest_feed.h"
 #include "ingest_pixels.h"
+#include "ingest_slab.h"
 #include "jpeg_stage.h"
+#include "png_stage.h"
 #include "resnet_model.h" // icl_embed_dev_locked
 
 #include <algorithm>
@@ -34,23 +37,8 @@
 
 namespace {
 
-constexpr int OUTW = ICL_IMG_W, OUTH = ICL_IMG_H;
-enum { KIND_FAILED = 0, KIND_JPEG = 1, KIND_HOST = 2, KIND_JSTREAM = 3 }; // (KIND_JSTREAM: a JPEG as bit stream; the kernels see it as KIND_JPEG)
-
-struct ingest_image {
-    int32_t kind;
-    int32_t W, H;   // decoded size
-    int32_t ow, oh; // size after the EXIF orientation (the resize's source)
-    int32_t orient, ncomp, hs, vs, is_rgb, area;
-    int32_t cw, chh;          // chroma samples per row / rows (dw, dh of components 1 and 2)
-    int32_t ystride, yrows;   // luma plane: wblocks*8 x hblocks*8
-    int32_t cstride, crows;   // chroma planes
-    int32_t pad_;
-    int64_t yplane, cplane[2]; // byte offsets in the plane scratch
-    int64_t host_off;          // KIND_HOST: byte offset of the finished image in the payload
-    int32_t xofs[OUTW], yofs[OUTH];
-    int16_t xa[OUTW * 2], ya[OUTH * 2];
-};
+constexpr int OUTW = ICL_OUTW, OUTH = ICL_OUTH;
+// (the row kinds and ingest_image: ingest_slab.h)
 
 struct ingest_plane {
     int64_t first_block; // flat block index over the slab
@@ -177,8 +165,16 @@ __device__ __forceinline__ void rgb_at(const ingest_image &D, const uint8_t *scr
 
 // one thread per output pixel of one image: cv::resize INTER_LINEAR (OpenCV's two-pass fixed-point rounding) or, for an exact
 // 2x2 decimation, INTER_AREA (ingest_pixels.h), with the offset / weight tables computed on the host (icl_resize_coeffs)
+// RGB of pixel (x, y) of a KIND_PSTREAM image from its unfiltered scanlines (D: its checked descriptor, icl_png_job)
+__device__ __forceinline__ void png_rgb_at(const icl_png_desc *D, const uint8_t *lines, int x, int y, int &R, int &G, int &B)
+{
+    x = min(max(x, 0), D->w - 1);
+    y = min(max(y, 0), D->h - 1);
+    icl_png_sample_rgb(lines + (int64_t)y * ((int64_t)D->rowb + 1) + 1, x, D->ctype, D->depth, D->pal, R, G, B);
+}
+
 __global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_image *__restrict__ imgs, const uint8_t *__restrict__ payload, int64_t payload_bytes,
-                                                                 const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst)
+                                                                 const uint8_t *__restrict__ scratch, int64_t scratch_bytes, uint8_t *__restrict__ dst)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= OUTW * OUTH) return;
@@ -193,9 +189,35 @@ __global__ void __launch_bounds__(256) jpeg_gather_resize_kernel(const ingest_im
         }
         return;
     }
-    if (D.kind != KIND_JPEG) { o[0] = o[1] = o[2] = 0; return; }
     const int dx = p % OUTW, dy = p / OUTW;
     int r[4], g[4], b[4];
+    if (D.kind == KIND_PSTREAM) { // a PNG's scanlines (png_gpu.hip): the same four samples per output pixel; no EXIF step
+        const icl_png_desc *P = icl_png_job(D, payload, payload_bytes, scratch_bytes);
+        if (!P) { o[0] = o[1] = o[2] = 0; return; }
+        const uint8_t *lines = scratch + D.yplane;
+        if (D.area) {
+            png_rgb_at(P, lines, 2 * dx, 2 * dy, r[0], g[0], b[0]);
+            png_rgb_at(P, lines, 2 * dx + 1, 2 * dy, r[1], g[1], b[1]);
+            png_rgb_at(P, lines, 2 * dx, 2 * dy + 1, r[2], g[2], b[2]);
+            png_rgb_at(P, lines, 2 * dx + 1, 2 * dy + 1, r[3], g[3], b[3]);
+            o[0] = icl_area_mean(r[0], r[1], r[2], r[3]);
+            o[1] = icl_area_mean(g[0], g[1], g[2], g[3]);
+            o[2] = icl_area_mean(b[0], b[1], b[2], b[3]);
+            return;
+        }
+        const int sx = min(max(D.xofs[dx], 0), D.ow - 1), sx1 = min(sx + 1, D.ow - 1);
+        const int sy = min(max(D.yofs[dy], 0), D.oh - 1), sy1 = min(sy + 1, D.oh - 1);
+        png_rgb_at(P, lines, sx, sy, r[0], g[0], b[0]);
+        png_rgb_at(P, lines, sx1, sy, r[1], g[1], b[1]);
+        png_rgb_at(P, lines, sx, sy1, r[2], g[2], b[2]);
+        png_rgb_at(P, lines, sx1, sy1, r[3], g[3], b[3]);
+        const int a0 = D.xa[dx * 2], a1 = D.xa[dx * 2 + 1], b0 = D.ya[dy * 2], b1 = D.ya[dy * 2 + 1];
+        o[0] = icl_resize_linear(r[0], r[1], r[2], r[3], a0, a1, b0, b1);
+        o[1] = icl_resize_linear(g[0], g[1], g[2], g[3], a0, a1, b0, b1);
+        o[2] = icl_resize_linear(b[0], b[1], b[2], b[3], a0, a1, b0, b1);
+        return;
+    }
+    if (D.kind != KIND_JPEG) { o[0] = o[1] = o[2] = 0; return; }
     if (D.area) {
         rgb_at(D, scratch, 2 * dx, 2 * dy, r[0], g[0], b[0]);
         rgb_at(D, scratch, 2 * dx + 1, 2 * dy, r[1], g[1], b[1]);
@@ -236,6 +258,7 @@ constexpr int64_t SLAB_WGS = SLAB_SUBS / ICL_JE_WG + SLAB_IMAGES;   // ... workg
 constexpr int64_t HDR_SCANS = SLAB_IMAGES * (int64_t)sizeof(ingest_image) + 3 * SLAB_IMAGES * (int64_t)sizeof(ingest_plane); // offset of the scan descriptors
 constexpr int64_t HDR_BYTES = HDR_SCANS + SLAB_IMAGES * (int64_t)sizeof(icl_je_scan);
 // slab_fill::fits (below) tests rows, payload, scratch and subsequences; the other limits follow from those:
+static_assert(ICL_PNG_PAYLOAD_CAP == SLAB_PAYLOAD && ICL_PNG_WANT_CAP <= SLAB_SCRATCH, "a qualifying PNG (png_stage.h) alone fits a slab");
 static_assert(SLAB_COEF == 2 * SLAB_SCRATCH, "a stream plane's dense coefficients are two bytes per plane sample: coef_used <= 2 * scratch_used");
 static_assert(SLAB_WGS == SLAB_SUBS / ICL_JE_WG + SLAB_IMAGES, "sum of ceil(nsub_i / WG) over k <= SLAB_IMAGES scans <= floor(sum nsub_i / WG) + k");
 // (scans: at most one per row, SLAB_IMAGES of them in the header; planes: at most three per row, 3 * SLAB_IMAGES in the header)
@@ -273,7 +296,13 @@ struct file_result { // what a worker hands the slab builder for one file
     icl_je_scan scan;
     int64_t plane_bytes = 0;
     bool host_entropy = false; // a JPEG whose entropy decoder ran on the host
+    bool host_png = false;     // a PNG that took the host decoder
 };
+
+struct ingest_modes { // where the serial part of a file's decoding runs: ICL_ENTROPY_*, ICL_PNG_*
+    int entropy, png;
+};
+constexpr ingest_modes MODES_HOST = {ICL_ENTROPY_HOST, ICL_PNG_HOST};
 
 static int64_t plane_bytes_of(const icl_jpeg_component &k) { return (int64_t)k.wblocks * 8 * k.hblocks * 8; }
 
@@ -347,6 +376,26 @@ static bool pack_jpeg(const icl_jpeg_coefs &J, file_result &r, std::vector<uint3
     return true;
 }
 
+// Host stage P0 (icl_png_parse) -> descriptor + zlib stream in one buffer (KIND_PSTREAM).  Returns false when the file does not qualify for
+// the GPU route (its parse fails, it is interlaced, or it does not fit one slab): it then takes the host decoder, which reports what is wrong.
+static bool pack_png(const uint8_t *data, size_t len, file_result &r)
+{
+    icl_png_parsed P;
+    const size_t hdr = sizeof(icl_png_desc);
+    r.packed.assign(hdr, 0);
+    if (icl_png_parse(data, len, P, r.packed) != nullptr || !icl_png_qualifies(P, r.packed.size() - hdr)) {
+        r.packed.clear();
+        return false;
+    }
+    icl_png_desc D;
+    icl_png_describe(P, r.packed.data() + hdr, r.packed.size() - hdr, D);
+    memcpy(r.packed.data(), &D, sizeof D);
+    r.W = (int)P.w;
+    r.H = (int)P.h;
+    r.plane_bytes = (int64_t)P.want;
+    return true;
+}
+
 // Stage-A0 output -> one buffer: tables, intervals, stream (each on a 16-byte boundary).  Returns false when the image does not fit one slab.
 static bool pack_stream(const icl_jpeg_coefs &J, const icl_jpeg_a0 &A, file_result &r)
 {
@@ -375,11 +424,11 @@ struct worker_state { // buffers a worker reuses from file to file
 };
 
 // One image (a file, or a memory source read in place: icl_image_src_read), on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
-// qualifies), stage A for every other JPEG the GPU takes, the whole host path for everything else.  Status codes and messages are
+// qualifies), stage A for every other JPEG the GPU takes, stage P0 for a PNG that qualifies for the GPU route (modes.png == ICL_PNG_GPU), the whole host path for everything else.  Status codes and messages are
 // those of icl_load_image_224 (image_io.hip).
 // finish_host(rgb, w, h) turns a host-decoded image into the result's KIND_HOST payload (or fails it: it returns false after icl_fail).
 template <class FinishHost>
-static void process_file_with(const ingest_src &src, const char *path /* what the messages call the image */, worker_state &ws, int entropy, file_result &r,
+static void process_file_with(const ingest_src &src, const char *path /* what the messages call the image */, worker_state &ws, const ingest_modes &modes, file_result &r,
                               const FinishHost &finish_host)
 {
     icl_jpeg_coefs &J = ws.J;
@@ -395,7 +444,7 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
         size_t len;
         const int fmt = icl_image_src_read(src, file, data, len);
         if (fmt == ICL_IMAGE_JPEG) {
-            if (entropy == ICL_ENTROPY_GPU) {
+            if (modes.entropy == ICL_ENTROPY_GPU) {
                 bool qualifies = false;
                 (void)icl_jpeg_stage_a0(data, len, path, ICL_JE_SUB_BITS, J, ws.A, qualifies); // (an error: the usual route reports it)
                 if (qualifies && pack_stream(J, ws.A, r)) {
@@ -417,6 +466,13 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
             if (rc2) return fail_from_tls(rc2);
             icl_apply_exif_orientation(rgb, w, h, J.orient);
         } else { // PNG, PPM, or a file that cannot be read / an empty buffer: the host path decodes it or reports why not
+            if (fmt == ICL_IMAGE_PNG) {
+                if (modes.png == ICL_PNG_GPU && pack_png(data, len, r)) {
+                    r.kind = KIND_PSTREAM;
+                    return;
+                }
+                r.host_png = true;
+            }
             const int rc = icl_image_decode(nullptr, src, path, fmt, data, len, rgb, w, h);
             if (rc) return fail_from_tls(rc);
         }
@@ -433,10 +489,10 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
     }
 }
 
-static void process_file(const ingest_src &src, worker_state &ws, int entropy, file_result &r)
+static void process_file(const ingest_src &src, worker_state &ws, const ingest_modes &modes, file_result &r)
 {
     char nbuf[96];
-    process_file_with(src, ingest_src_name(src, nbuf, sizeof nbuf), ws, entropy, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
+    process_file_with(src, ingest_src_name(src, nbuf, sizeof nbuf), ws, modes, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
         r.packed.resize((size_t)ICL_IMG_BYTES);
         icl_resize_bilinear_u8(rgb.data(), w, h, r.packed.data(), OUTW, OUTH);
         return true;
@@ -460,6 +516,10 @@ struct icl_ingest_ws {
     int32_t *d_accepted = nullptr;
     int32_t *h_accepted = nullptr; // pinned: one flag per stream image of a call
     int64_t h_accepted_cap = 0;
+    // ICL_PNG_GPU (allocated when the first slab with a PNG stream is built)
+    int32_t *d_png_ok = nullptr;
+    int32_t *h_png_ok = nullptr; // pinned: one flag per row of a call
+    int64_t h_png_ok_cap = 0;
     slab_view host(int q) const { return slab_view(h_slab[q], h_slab[q] + HDR_BYTES); }
     slab_view dev() const { return slab_view(d_hdr, d_payload); }
     ~icl_ingest_ws()
@@ -469,6 +529,8 @@ struct icl_ingest_ws {
             if (ev_up[q]) (void)hipEventDestroy(ev_up[q]);
         }
         if (h_accepted) (void)hipHostFree(h_accepted);
+        if (h_png_ok) (void)hipHostFree(h_png_ok);
+        if (d_png_ok) (void)hipFree(d_png_ok);
         for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_emb, (void *)d_rows, (void *)d_coef, (void *)d_sub, (void *)d_bound,
                         (void *)d_accepted})
             if (p) (void)hipFree(p);
@@ -523,13 +585,32 @@ static int entropy_ws(icl_ctx *ctx, icl_ingest_ws *ws, int64_t n)
     return ICL_OK;
 }
 
+// the buffers of the GPU PNG route; room for the accepted flags of a call with n files
+static int png_ws(icl_ctx *ctx, icl_ingest_ws *ws, int64_t n)
+{
+    if (!ws->d_png_ok && hipMalloc((void **)&ws->d_png_ok, (size_t)SLAB_IMAGES * 4) != hipSuccess) {
+        ws->d_png_ok = nullptr;
+        return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: device buffers of the PNG route");
+    }
+    if (ws->h_png_ok_cap < n) {
+        if (ws->h_png_ok) (void)hipHostFree(ws->h_png_ok);
+        ws->h_png_ok = nullptr;
+        ws->h_png_ok_cap = 0;
+        const int64_t cap = std::max<int64_t>(n, 4096);
+        if (hipHostMalloc((void **)&ws->h_png_ok, (size_t)cap * 4, hipHostMallocDefault) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: pinned flags");
+        ws->h_png_ok_cap = cap;
+    }
+    return ICL_OK;
+}
+
 namespace {
 
 // what the slab builder has placed so far
 struct slab_fill {
-    int nimg = 0, npl = 0, nscan = 0, npacked = 0, ndense = 0;
+    int nimg = 0, npl = 0, nscan = 0, npacked = 0, ndense = 0, npng = 0;
     int64_t used = 0, scratch_used = 0, blocks = 0, coef_used = 0 /* bytes */, subs = 0, wgs = 0;
-    // What a slab holds: does r still fit behind what has been placed?  (A result alone always does: pack_jpeg / pack_stream saw to it.)
+    // What a slab holds: does r still fit behind what has been placed?  (A result alone always does: pack_jpeg / pack_stream / pack_png saw to it;
+    // a PNG stream's "plane" is the `want` bytes of its scanlines.)
     bool fits(const file_result &r) const
     {
         const int64_t pay = r.kind == KIND_FAILED ? 0 : align16((int64_t)r.packed.size()), nsub = r.kind == KIND_JSTREAM ? (int64_t)r.scan.nsub : 0;
@@ -613,8 +694,32 @@ static bool place_jpeg(const file_result &r, slab_fill &F, const slab_view &S)
     return ok;
 }
 
-// upload of a filled slab and its kernels up to the planes: (entropy decode,) IDCT
-static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, const slab_view &H, const slab_fill &F, int64_t &upload)
+// One KIND_PSTREAM result into the slab: image descriptor (resize tables; no EXIF step for PNG), descriptor + zlib stream into the payload,
+// `want` bytes of the scratch for its scanlines.
+static bool place_png(const file_result &r, slab_fill &F, const slab_view &S)
+{
+    if (!F.fits(r) || r.packed.size() < sizeof(icl_png_desc)) return false;
+    ingest_image &D = S.imgs[F.nimg];
+    D.kind = KIND_PSTREAM;
+    D.W = D.ow = r.W;
+    D.H = D.oh = r.H;
+    D.orient = 1;
+    D.area = icl_resize_is_area(D.ow, D.oh, OUTW, OUTH);
+    icl_resize_coeffs(OUTW, D.ow, D.xofs, D.xa);
+    icl_resize_coeffs(OUTH, D.oh, D.yofs, D.ya);
+    memcpy(S.payload + F.used, r.packed.data(), r.packed.size());
+    D.host_off = F.used;
+    D.yplane = F.scratch_used;
+    F.used += align16((int64_t)r.packed.size());
+    F.scratch_used += align16(r.plane_bytes);
+    ++F.npng;
+    // what the kernels rely on, by their own check (the descriptor was made by pack_png on this host)
+    return F.used <= SLAB_PAYLOAD && F.scratch_used <= SLAB_SCRATCH && icl_png_job(D, S.payload, SLAB_PAYLOAD, SLAB_SCRATCH) != nullptr;
+}
+
+// upload of a filled slab and its kernels up to the planes: (entropy decode,) IDCT; (PNG streams: inflate, Adler-32, and with png_stages >= 2
+// the unfilter -- only icl_png_raw_files stops before it)
+static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, const slab_view &H, const slab_fill &F, int64_t &upload, int png_stages = 2)
 {
     hipStream_t st = ctx->stream;
     const slab_view D = ws->dev();
@@ -650,6 +755,8 @@ static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, const slab_view &H, 
                            (const int16_t *)ws->d_coef, (int64_t)SLAB_COEF, ws->d_scratch, (int64_t)SLAB_SCRATCH, F.blocks);
         ICL_HIP(ctx, hipGetLastError());
     }
+    if (F.npng)
+        ICL_TRY(icl_png_decode_slab(ctx, st, D.imgs, F.nimg, (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, ws->d_scratch, (int64_t)SLAB_SCRATCH, ws->d_png_ok, png_stages));
     return ICL_OK;
 }
 
@@ -662,6 +769,7 @@ struct file_fail {
 struct ingest_totals {
     int64_t gpu_jpegs = 0, host_files = 0, upload = 0, decode_ns = 0;
     int64_t gpu_entropy = 0, host_entropy = 0, stream_bytes = 0;
+    int64_t gpu_pngs = 0, host_pngs = 0, png_bytes = 0;
 };
 
 struct ingest_job { // the list a pass works on, and its caller
@@ -676,6 +784,8 @@ struct pass_result {
     std::vector<file_fail> fails;     // per-file failures (also in status[])
     std::vector<int64_t> rejected;    // rows whose GPU entropy decode was not accepted: to be redone by a pass with ICL_ENTROPY_HOST
     std::vector<int64_t> stream_rows; // the row of every stream image of the pass, in the order of h_accepted
+    std::vector<int64_t> png_rejected; // rows whose GPU PNG decode was not accepted: to be redone by a pass with ICL_PNG_HOST
+    std::vector<int64_t> png_rows;     // the row of every PNG stream of the pass (its flag: h_png_ok[row])
 };
 
 struct slab_rows { // what slab_collect leaves the stages behind it
@@ -726,6 +836,14 @@ static int slab_collect(icl_ctx *ctx, const ingest_job &job, file_feed &feed, co
             memcpy(S.payload + F.used, r->packed.data(), (size_t)ICL_IMG_BYTES);
             F.used += align16(ICL_IMG_BYTES);
             ++tot.host_files;
+        } else if (r->kind == KIND_PSTREAM) {
+            if (!place_png(*r, F, S)) {
+                char nbuf[96];
+                return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent PNG geometry for %s", job.what, ingest_src_name(job.srcs[row], nbuf, sizeof nbuf));
+            }
+            ++tot.gpu_pngs;
+            res.png_rows.push_back(row);
+            tot.png_bytes += (int64_t)r->packed.size() - (int64_t)sizeof(icl_png_desc);
         } else {
             if (!place_jpeg(*r, F, S)) {
                 char nbuf[96];
@@ -738,6 +856,7 @@ static int slab_collect(icl_ctx *ctx, const ingest_job &job, file_feed &feed, co
             }
         }
         if (r->host_entropy) ++tot.host_entropy; // (whatever became of it: stage A ran, or tried to)
+        if (r->host_png) ++tot.host_pngs;        // (likewise)
         ++F.nimg;
     }
     return ICL_OK;
@@ -751,7 +870,7 @@ static int slab_deliver(icl_ctx *ctx, icl_ingest_ws *ws, const ingest_sink &sink
     const int nimg = R.F.nimg, head = sink.head;
     uint8_t *d_img = sink.embeds() ? ws->d_img : (uint8_t *)sink.row(R.first);
     hipLaunchKernelGGL(jpeg_gather_resize_kernel, dim3((unsigned)icl_ceil_div(OUTW * OUTH, 256), (unsigned)nimg), dim3(256), 0, st, ws->dev().imgs,
-                       (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, d_img);
+                       (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, (int64_t)SLAB_SCRATCH, d_img);
     ICL_HIP(ctx, hipGetLastError());
     if (!sink.embeds()) return ICL_OK;
     float *d_dst = sink.kind == ingest_sink::EMB_DEV ? (float *)sink.row(R.first) : ws->d_emb;
@@ -778,14 +897,16 @@ static void tally_accepted(const icl_ingest_ws *ws, pass_result &res, ingest_tot
         if (ws->h_accepted[q]) ++tot.gpu_entropy;
         else res.rejected.push_back(res.stream_rows[q]);
     }
+    for (int64_t row : res.png_rows)
+        if (!ws->h_png_ok[row]) res.png_rejected.push_back(row);
 }
 
 // One pass of the pipeline over job's files into sink: worker threads decode the files (at most two slabs' worth of rows and payload
 // bytes ahead), this thread builds the slabs in file order, double-buffered in pinned memory, with everything on ctx->stream.
-static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &sink, int entropy, pass_result &res, ingest_totals &tot)
+static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &sink, const ingest_modes &modes, pass_result &res, ingest_totals &tot)
 {
     icl_ingest_ws *ws = nullptr;
-    ICL_TRY(ingest_buffers(ctx, sink, entropy, job.n, ws));
+    ICL_TRY(ingest_buffers(ctx, sink, modes.entropy, job.n, ws));
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(job.n, job.threads > 0 ? job.threads : (int)std::min(16u, hw)));
     std::atomic<int64_t> decode_ns{0};
@@ -793,7 +914,7 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
         thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state()); // a worker's buffers, from file to file
         const auto t0 = std::chrono::steady_clock::now();
         std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
-        if (r) process_file(job.srcs[i], *wst, entropy, *r);
+        if (r) process_file(job.srcs[i], *wst, modes, *r);
         decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
         return r;
     };
@@ -805,8 +926,11 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
             ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[q])); // the upload that last read this slab has finished
             const slab_view S = ws->host(q);
             ICL_TRY(slab_collect(ctx, job, feed, S, R, res, tot));
+            if (R.F.npng) ICL_TRY(png_ws(ctx, ws, job.n)); // (the first slab of the call that holds a PNG stream)
             ICL_TRY(run_slab_decode(ctx, ws, S, R.F, tot.upload));
             ICL_HIP(ctx, hipEventRecord(ws->ev_up[q], ctx->stream));
+            if (R.F.npng) // one flag per row of the slab, kept under the row's place in the list
+                ICL_HIP(ctx, hipMemcpyAsync(ws->h_png_ok + R.first, ws->d_png_ok, (size_t)R.F.nimg * 4, hipMemcpyDeviceToHost, ctx->stream));
             if (R.F.nscan) // the flags are read after the pass's last synchronisation
                 ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted + (res.stream_rows.size() - (size_t)R.F.nscan), ws->d_accepted, (size_t)R.F.nscan * 4, hipMemcpyDeviceToHost,
                                             ctx->stream));
@@ -821,16 +945,17 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
 
 } // namespace
 
-// The pipeline (declared in icl_common.h): one pass in the context's entropy mode; the images the GPU entropy check rejected are then
-// redone by a pass in ICL_ENTROPY_HOST mode over those sources alone (a memory source is read again from the caller's buffer) into a sink of the same kind on a temporary (rows do not depend on
+// The pipeline (declared in icl_common.h): one pass in the context's entropy and PNG modes; the images the GPU entropy check or the GPU PNG
+// check rejected are then redone by a pass with both modes on the host over those sources alone (a memory source is read again from the caller's buffer) into a sink of the same kind on a temporary (rows do not depend on
 // the batch they are rebuilt or embedded in), which also produces their status codes and messages.
 int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
                  icl_item_failure *lowest_out)
 {
     pass_result res;
     ingest_totals tot;
-    ICL_TRY(ingest_pass(ctx, ingest_job{srcs, n, threads, status, what}, sink, ctx->entropy_mode, res, tot));
-    const int64_t nrej = (int64_t)res.rejected.size();
+    ICL_TRY(ingest_pass(ctx, ingest_job{srcs, n, threads, status, what}, sink, ingest_modes{ctx->entropy_mode, ctx->png_mode}, res, tot));
+    const int64_t nrej_jpeg = (int64_t)res.rejected.size(), nrej_png = (int64_t)res.png_rejected.size(), nrej = nrej_jpeg + nrej_png;
+    res.rejected.insert(res.rejected.end(), res.png_rejected.begin(), res.png_rejected.end()); // (JPEGs first, then PNGs)
     if (nrej) {
         std::vector<ingest_src> rp((size_t)nrej); // (each keeps its index in the caller's list: messages name it)
         for (int64_t q = 0; q < nrej; ++q) rp[(size_t)q] = srcs[res.rejected[(size_t)q]];
@@ -846,7 +971,7 @@ int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t thread
             if (hipMalloc(&d_tmp.p, (size_t)nrej * sink.row_bytes()) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: device buffer of the repair pass", what);
             tmp.dst = d_tmp.p;
         }
-        ICL_TRY(ingest_pass(ctx, ingest_job{rp.data(), nrej, threads, rstatus.data(), what}, tmp, ICL_ENTROPY_HOST, rres, tot));
+        ICL_TRY(ingest_pass(ctx, ingest_job{rp.data(), nrej, threads, rstatus.data(), what}, tmp, MODES_HOST, rres, tot));
         for (int64_t q = 0; q < nrej; ++q) {
             const int64_t row = res.rejected[(size_t)q];
             if (status) status[row] = rstatus[(size_t)q];
@@ -855,8 +980,10 @@ int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t thread
         }
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (file_fail &f : rres.fails) res.fails.push_back(file_fail{res.rejected[(size_t)f.index], f.rc, f.err});
-        tot.gpu_jpegs -= nrej;     // (the first pass counted them; the repair pass counts what became of them)
-        tot.host_entropy -= nrej;  // they are reported as redone, not as routed to the host
+        tot.gpu_jpegs -= nrej_jpeg;    // (the first pass counted them; the repair pass counts what became of them)
+        tot.host_entropy -= nrej_jpeg; // they are reported as redone, not as routed to the host
+        tot.gpu_pngs -= nrej_png;      // (the PNG rejections likewise: the repair pass counts them among host_files)
+        tot.host_pngs -= nrej_png;
     }
     // ---- report ----
     ctx->ingest_stats[0] = tot.gpu_jpegs;
@@ -865,8 +992,12 @@ int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t thread
     ctx->ingest_decode_s = (double)tot.decode_ns * 1e-9;
     ctx->entropy_stats[0] = tot.gpu_entropy;
     ctx->entropy_stats[1] = tot.host_entropy;
-    ctx->entropy_stats[2] = nrej;
+    ctx->entropy_stats[2] = nrej_jpeg;
     ctx->entropy_stats[3] = tot.stream_bytes;
+    ctx->png_stats[0] = tot.gpu_pngs;
+    ctx->png_stats[1] = tot.host_pngs;
+    ctx->png_stats[2] = nrej_png;
+    ctx->png_stats[3] = tot.png_bytes;
     const file_fail *lowest = nullptr;
     for (const file_fail &f : res.fails)
         if (!lowest || f.index < lowest->index) lowest = &f;
@@ -979,6 +1110,73 @@ extern "C" int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, 
     return ICL_OK;
 }
 
+extern "C" int icl_set_png_options(icl_ctx *ctx, int png_mode)
+{
+    if (!ctx || (png_mode != ICL_PNG_HOST && png_mode != ICL_PNG_GPU)) return icl_fail(ctx, ICL_ERR_ARG, "icl_set_png_options: png_mode must be ICL_PNG_HOST or ICL_PNG_GPU");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->png_mode = png_mode;
+    return ICL_OK;
+}
+
+extern "C" int icl_last_png_stats(icl_ctx *ctx, int64_t *gpu_pngs, int64_t *host_pngs, int64_t *redone_on_host, int64_t *stream_bytes)
+{
+    if (!ctx) return ICL_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (gpu_pngs) *gpu_pngs = ctx->png_stats[0];
+    if (host_pngs) *host_pngs = ctx->png_stats[1];
+    if (redone_on_host) *redone_on_host = ctx->png_stats[2];
+    if (stream_bytes) *stream_bytes = ctx->png_stats[3];
+    return ICL_OK;
+}
+
+// Test hook: each file's scanlines as the GPU route leaves them -- inflated (stage 0) or unfiltered (stage 1) -- one single-image slab per
+// file through the pipeline's own placement and launch code.
+extern "C" int icl_png_raw_files(icl_ctx *ctx, const char *const *paths, int64_t n, int stage, uint8_t *raw, int64_t cap, int64_t *offsets, int32_t *state)
+{
+    const char *what = "icl_png_raw_files";
+    if (!ctx || n < 0 || (n && !paths) || !offsets || !state || cap < 0 || (stage != 0 && stage != 1)) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    for (int64_t i = 0; i < n; ++i)
+        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return no_throw(ctx, what, [&]() -> int {
+        const std::vector<ingest_src> srcs = ingest_path_srcs(paths, n);
+        icl_ingest_ws *ws = nullptr;
+        std::unique_ptr<worker_state> wst(new worker_state());
+        int64_t at = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            offsets[i] = at;
+            state[i] = -1;
+            file_result r;
+            process_file(srcs[i], *wst, ingest_modes{ICL_ENTROPY_HOST, ICL_PNG_GPU}, r);
+            if (r.kind != KIND_PSTREAM) continue; // does not qualify (or cannot be read at all)
+            state[i] = 0;
+            const int64_t total = r.plane_bytes;
+            if (raw) {
+                if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small", what);
+                ICL_TRY(ingest_ws(ctx, ws));
+                ICL_TRY(png_ws(ctx, ws, 1));
+                ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
+                const slab_view S = ws->host(0);
+                slab_fill F;
+                memset(&S.imgs[0], 0, offsetof(ingest_image, xofs));
+                if (!place_png(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent PNG geometry for %s", what, paths[i]);
+                F.nimg = 1;
+                int64_t upload = 0;
+                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload, stage == 0 ? 1 : 2));
+                ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
+                ICL_HIP(ctx, hipMemcpyAsync(ws->h_png_ok, ws->d_png_ok, 4, hipMemcpyDeviceToHost, ctx->stream));
+                ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                state[i] = ws->h_png_ok[0] ? 1 : 0;
+                if (state[i] == 1) ICL_HIP(ctx, hipMemcpy(raw + at, ws->d_scratch + S.imgs[0].yplane, (size_t)total, hipMemcpyDeviceToHost));
+            }
+            at += total; // (a rejected file keeps its range; its contents are not written)
+        }
+        offsets[n] = at;
+        return ICL_OK;
+    });
+}
+
 // the body of icl_jpeg_coefs_files / _mem after the argument check
 static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs,
                       int64_t cap, int64_t *offsets, int32_t *state, const char *what)
@@ -1018,7 +1216,7 @@ static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const ui
                 continue;
             }
             file_result r;
-            process_file(srcs[i], *wst, ICL_ENTROPY_GPU, r);
+            process_file(srcs[i], *wst, ingest_modes{ICL_ENTROPY_GPU, ICL_PNG_HOST}, r);
             if (r.kind != KIND_JSTREAM) continue; // does not qualify (or cannot be read at all)
             int64_t total = 0;
             for (int c = 0; c < r.ncomp; ++c) total += (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
@@ -1172,7 +1370,7 @@ static void dz_process(const ingest_src &src, worker_state &ws, int entropy, int
         };
         auto too_large = [&](int nw, int nh) { return (int64_t)nw * nh * 3 > SLAB_PAYLOAD / 4 || icl_jenc_blocks(nw, nh) > icl_jenc_max_batch_blocks() / 4; };
         bool oversize = false;
-        process_file_with(mem, name, ws, entropy, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
+        process_file_with(mem, name, ws, ingest_modes{entropy, ICL_PNG_HOST}, r, [&](std::vector<uint8_t> &rgb, int w, int h) {
             if (icl_downsize_dims_checked(name, w, h, max_dim, z.nw, z.nh)) return false;
             if (too_large(z.nw, z.nh)) {
                 oversize = true;

@@ -15,8 +15,11 @@
 // block that uses them) incomplete, a match may not reach in front of the output.  No C++ exception crosses the C ABI: the
 // callers wrap this in their no_throw guard.
 #include "icl_common.h"
+#include "jpeg_stage.h" // icl_image_file_read
+#include "png_stage.h"
 
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -236,78 +239,93 @@ bool icl_is_png(const uint8_t *data, size_t len)
     return len >= 8 && memcmp(data, sig, 8) == 0;
 }
 
-int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H)
+const char *icl_png_parse(const uint8_t *data, size_t len, icl_png_parsed &P, std::vector<uint8_t> &z)
 {
-    auto fail = [&](const char *why) { return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. PNG: %s", path, why); };
-    if (!icl_is_png(data, len)) return fail("bad signature");
+    if (!icl_is_png(data, len)) return "bad signature";
+    const size_t z0 = z.size();
     size_t pos = 8;
     bool have_ihdr = false, have_iend = false;
     uint32_t w = 0, h = 0;
     int depth = 0, ctype = 0, interlace = 0;
-    uint8_t pal[256][3];
     int npal = 0;
-    std::vector<uint8_t> z;
     while (pos + 12 <= len && !have_iend) {
         const uint32_t clen = be32(data + pos);
-        if (clen > 0x7fffffffu || (size_t)clen > len - pos - 12) return fail("chunk runs past the end of the file");
+        if (clen > 0x7fffffffu || (size_t)clen > len - pos - 12) return "chunk runs past the end of the file";
         const uint8_t *type = data + pos + 4, *body = data + pos + 8;
-        if (crc32_of(type, 4 + (size_t)clen) != be32(body + clen)) return fail("chunk CRC mismatch");
+        if (crc32_of(type, 4 + (size_t)clen) != be32(body + clen)) return "chunk CRC mismatch";
         const bool is = !memcmp(type, "IHDR", 4), ip = !memcmp(type, "PLTE", 4), id = !memcmp(type, "IDAT", 4), ie = !memcmp(type, "IEND", 4);
-        if (!have_ihdr && !is) return fail("IHDR is not the first chunk");
+        if (!have_ihdr && !is) return "IHDR is not the first chunk";
         if (is) {
-            if (have_ihdr || clen != 13) return fail("bad IHDR");
+            if (have_ihdr || clen != 13) return "bad IHDR";
             w = be32(body);
             h = be32(body + 4);
             depth = body[8];
             ctype = body[9];
             interlace = body[12];
-            if (body[10] != 0 || body[11] != 0 || interlace > 1) return fail("unknown compression / filter / interlace method");
+            if (body[10] != 0 || body[11] != 0 || interlace > 1) return "unknown compression / filter / interlace method";
             const bool ok_depth = (ctype == 0 && (depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16)) ||
                                   (ctype == 3 && (depth == 1 || depth == 2 || depth == 4 || depth == 8)) ||
                                   ((ctype == 2 || ctype == 4 || ctype == 6) && (depth == 8 || depth == 16));
-            if (!ok_depth) return fail("colour type / bit depth combination is not in the standard");
-            if (w == 0 || h == 0 || w > 65535u || h > 65535u || (uint64_t)w * h > (64ull << 20)) return fail("image dimensions out of range (limit: 64 Mpx)");
+            if (!ok_depth) return "colour type / bit depth combination is not in the standard";
+            if (w == 0 || h == 0 || w > 65535u || h > 65535u || (uint64_t)w * h > (64ull << 20)) return "image dimensions out of range (limit: 64 Mpx)";
             have_ihdr = true;
         } else if (ip) {
-            if (clen % 3 || clen > 768 || npal) return fail("bad PLTE");
+            if (clen % 3 || clen > 768 || npal) return "bad PLTE";
             npal = (int)(clen / 3);
-            memcpy(pal, body, clen);
+            memcpy(P.pal, body, clen);
         } else if (id) {
             z.insert(z.end(), body, body + clen);
         } else if (ie) {
             have_iend = true;
         } else if (!(type[0] & 0x20)) {
-            return fail("unknown critical chunk");
+            return "unknown critical chunk";
         }
         pos += 12 + (size_t)clen;
     }
-    if (!have_ihdr || !have_iend) return fail("truncated file (no IEND)");
-    if (ctype == 3 && npal == 0) return fail("palette image without PLTE");
-    if (z.size() < 6) return fail("no image data");
+    if (!have_ihdr || !have_iend) return "truncated file (no IEND)";
+    if (ctype == 3 && npal == 0) return "palette image without PLTE";
+    if (z.size() - z0 < 6) return "no image data";
     // zlib wrapper (RFC 1950): CM = 8, window <= 32 KiB, no preset dictionary, header check
-    if ((z[0] & 0x0f) != 8 || (z[0] >> 4) > 7 || (z[1] & 0x20) || (((unsigned)z[0] << 8) | z[1]) % 31 != 0) return fail("bad zlib header");
+    if ((z[z0] & 0x0f) != 8 || (z[z0] >> 4) > 7 || (z[z0 + 1] & 0x20) || (((unsigned)z[z0] << 8) | z[z0 + 1]) % 31 != 0) return "bad zlib header";
     const int channels = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : 4;
-    const size_t bits_px = (size_t)channels * depth, bpp = bits_px >= 8 ? bits_px / 8 : 1;
+    const size_t bits_px = (size_t)channels * depth;
+    P.w = w;
+    P.h = h;
+    P.depth = depth;
+    P.ctype = ctype;
+    P.interlace = interlace;
+    P.npal = npal;
+    P.channels = channels;
+    P.bits_px = bits_px;
+    P.bpp = bits_px >= 8 ? bits_px / 8 : 1;
     // the reduced images of the stream (PNG 8.2): one for a progressive file, the seven Adam7 passes for an interlaced one -- each
     // its own sequence of filtered scanlines; empty passes are absent from the stream
-    struct pass_t {
-        uint32_t xs, ys, dx, dy, pw, ph;
-        size_t rowb, off;
-    } passes[7];
-    int npass = 0;
-    size_t want = 0;
-    {
-        static const uint8_t a7[7][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4}, {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
-        const int np = interlace ? 7 : 1;
-        for (int q = 0; q < np; ++q) {
-            const uint32_t xs = interlace ? a7[q][0] : 0, ys = interlace ? a7[q][1] : 0, dx = interlace ? a7[q][2] : 1, dy = interlace ? a7[q][3] : 1;
-            if (xs >= w || ys >= h) continue;
-            const uint32_t pw = (w - xs + dx - 1) / dx, ph = (h - ys + dy - 1) / dy;
-            const size_t rowb = ((size_t)pw * bits_px + 7) / 8;
-            passes[npass++] = pass_t{xs, ys, dx, dy, pw, ph, rowb, want};
-            want += (size_t)ph * (rowb + 1);
-        }
+    P.npass = 0;
+    P.want = 0;
+    static const uint8_t a7[7][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4}, {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
+    const int np = interlace ? 7 : 1;
+    for (int q = 0; q < np; ++q) {
+        const uint32_t xs = interlace ? a7[q][0] : 0, ys = interlace ? a7[q][1] : 0, dx = interlace ? a7[q][2] : 1, dy = interlace ? a7[q][3] : 1;
+        if (xs >= w || ys >= h) continue;
+        const uint32_t pw = (w - xs + dx - 1) / dx, ph = (h - ys + dy - 1) / dy;
+        const size_t rowb = ((size_t)pw * bits_px + 7) / 8;
+        P.passes[P.npass++] = icl_png_pass{xs, ys, dx, dy, pw, ph, rowb, P.want};
+        P.want += (size_t)ph * (rowb + 1);
     }
+    return nullptr;
+}
+
+int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *path, std::vector<uint8_t> &rgb, int &W, int &H)
+{
+    auto fail = [&](const char *why) { return icl_fail(ctx, ICL_ERR_IO, "failed to read image: %s. PNG: %s", path, why); };
+    icl_png_parsed P;
+    std::vector<uint8_t> z;
+    if (const char *why = icl_png_parse(data, len, P, z)) return fail(why);
+    const uint32_t w = P.w, h = P.h;
+    const int depth = P.depth, ctype = P.ctype, npal = P.npal, channels = P.channels, npass = P.npass;
+    const uint8_t(*pal)[3] = P.pal;
+    const size_t bits_px = P.bits_px, bpp = P.bpp, want = P.want;
+    const icl_png_pass *passes = P.passes;
     std::vector<uint8_t> raw;
     bits_in b{z.data() + 2, z.data() + z.size() - 4};
     if (!inflate_exact(b, raw, want)) return fail("corrupt or truncated DEFLATE stream");
@@ -319,7 +337,7 @@ int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *pa
     const int step = depth == 16 ? 2 : 1; // bytes per sample for depth >= 8
     std::vector<uint8_t> zero(((size_t)w * bits_px + 7) / 8, 0);
     for (int q = 0; q < npass; ++q) {
-        const pass_t &ps = passes[q];
+        const icl_png_pass &ps = passes[q];
         const size_t rowb = ps.rowb;
         // scanline filters (PNG 9.2): Sub, Up, Average, Paeth over bytes, bpp bytes to the left; the line above the first one of a pass is zero
         const uint8_t *prev = zero.data();
@@ -383,4 +401,147 @@ int icl_png_decode(icl_ctx *ctx, const uint8_t *data, size_t len, const char *pa
         }
     }
     return ICL_OK;
+}
+
+// ---- the GPU route's host side: descriptor, and the kernels' schedule rehearsed on the host (png_stage.h) ------------------------------
+
+void icl_png_describe(const icl_png_parsed &P, const uint8_t *z, size_t zbytes, icl_png_desc &D)
+{
+    memset(&D, 0, sizeof D);
+    D.w = (int32_t)P.w;
+    D.h = (int32_t)P.h;
+    D.depth = P.depth;
+    D.ctype = P.ctype;
+    D.rowb = (int32_t)P.passes[0].rowb;
+    D.bpp = (int32_t)P.bpp;
+    D.npal = P.npal;
+    D.zbytes = (int32_t)zbytes;
+    D.want = (int64_t)P.want;
+    D.adler = be32(z + zbytes - 4);
+    memcpy(D.pal, P.pal, (size_t)P.npal * 3);
+}
+
+namespace {
+
+// png_adler_kernel's sum: chunks of ICL_ADLER_CHUNK bytes in any order
+static uint32_t adler_by_chunks(const uint8_t *p, int64_t n)
+{
+    uint32_t sa = 0, sb = 0;
+    const int64_t nchunk = (n + ICL_ADLER_CHUNK - 1) / ICL_ADLER_CHUNK;
+    for (int64_t c = nchunk - 1; c >= 0; --c) { // (backwards: the order does not matter)
+        const int64_t s = c * ICL_ADLER_CHUNK;
+        const int m = (int)(n - s < ICL_ADLER_CHUNK ? n - s : ICL_ADLER_CHUNK);
+        icl_adler_chunk(p + s, m, n - s - m, sa, sb);
+    }
+    return icl_adler_finish(sa, sb, n);
+}
+
+// png_unfilter_kernel's schedule: bands of 64 rows, lane l at pixel t - l at step t; the pixel above comes from lane l - 1's last output
+// (a band's first row: from memory), above-left is the lane's own previous `above`.  false: a filter byte above 4, or a palette index
+// out of range.
+static bool unfilter_by_bands(uint8_t *base, const icl_png_desc &D)
+{
+    const int64_t rowb = D.rowb, pitch = rowb + 1, npx = rowb / D.bpp;
+    const bool check_pal = D.ctype == 3 && D.npal < (1 << D.depth);
+    bool bad = false;
+    for (int64_t r0 = 0; r0 < D.h; r0 += ICL_PNG_LANES) {
+        uint64_t left[ICL_PNG_LANES] = {}, above[ICL_PNG_LANES] = {}, mine[ICL_PNG_LANES] = {}, was[ICL_PNG_LANES];
+        int ft[ICL_PNG_LANES];
+        for (int l = 0; l < ICL_PNG_LANES; ++l) {
+            ft[l] = r0 + l < D.h ? base[(r0 + l) * pitch] : 0;
+            if (ft[l] > 4) {
+                bad = true;
+                ft[l] = 0;
+            }
+        }
+        for (int64_t t = 0; t < npx + ICL_PNG_LANES - 1; ++t) {
+            memcpy(was, mine, sizeof was);
+            for (int l = 0; l < ICL_PNG_LANES; ++l) {
+                const int64_t x = t - l, row = r0 + l;
+                if (row >= D.h || x < 0 || x >= npx) continue;
+                uint8_t *px = base + row * pitch + 1 + x * D.bpp;
+                const uint64_t b = l == 0 ? (row > 0 ? icl_png_load_px(px - pitch, D.bpp) : 0) : was[l - 1];
+                const uint64_t c = x > 0 ? above[l] : 0, a = x > 0 ? left[l] : 0;
+                const uint64_t o = icl_png_unfilter_px(ft[l], D.bpp, icl_png_load_px(px, D.bpp), a, b, c);
+                icl_png_store_px(px, D.bpp, o);
+                if (check_pal && icl_png_pal_bad((uint32_t)(o & 255u), x, D.w, D.depth, D.npal)) bad = true;
+                left[l] = o;
+                above[l] = b;
+                mine[l] = o;
+            }
+        }
+    }
+    return !bad;
+}
+
+} // namespace
+
+void icl_png_host_schedule(const uint8_t *data, size_t len, int stage, std::vector<uint8_t> &raw, int32_t info[12])
+{
+    for (int i = 0; i < 12; ++i) info[i] = 0;
+    info[0] = -1;
+    raw.clear();
+    icl_png_parsed P;
+    std::vector<uint8_t> z;
+    if (icl_png_parse(data, len, P, z) != nullptr || !icl_png_qualifies(P, z.size())) return;
+    icl_png_desc D;
+    icl_png_describe(P, z.data(), z.size(), D);
+    info[0] = 0;
+    info[1] = D.w;
+    info[2] = D.h;
+    info[3] = D.depth;
+    info[4] = D.ctype;
+    std::vector<uint8_t> out((size_t)D.want);
+    std::unique_ptr<icl_png_lds> L(new icl_png_lds);
+    memset(L.get(), 0, sizeof(icl_png_lds));
+    icl_png_inflate_run(*L, z.data(), (int64_t)z.size(), out.data(), D.want, 0, ICL_PNG_LANES, [] {});
+    for (int i = 0; i < ICL_PNG_NCOV; ++i) info[5 + i] = L->cov[i];
+    if (!L->ok || adler_by_chunks(out.data(), D.want) != D.adler) return;
+    if (stage >= 1 && !unfilter_by_bands(out.data(), D)) return;
+    info[0] = 1;
+    if (stage < 2) {
+        raw.swap(out);
+        return;
+    }
+    raw.resize((size_t)D.w * D.h * 3);
+    for (int64_t y = 0; y < D.h; ++y)
+        for (int64_t x = 0; x < D.w; ++x) {
+            int R, G, B;
+            icl_png_sample_rgb(out.data() + y * ((int64_t)D.rowb + 1) + 1, x, D.ctype, D.depth, D.pal, R, G, B);
+            uint8_t *o = raw.data() + ((size_t)y * D.w + x) * 3;
+            o[0] = (uint8_t)R;
+            o[1] = (uint8_t)G;
+            o[2] = (uint8_t)B;
+        }
+}
+
+static int png_raw_host(const uint8_t *data, size_t len, int stage, uint8_t *raw, int64_t cap, int64_t *need, int32_t *info, const char *what)
+{
+    return no_throw(nullptr, what, [&]() -> int {
+        std::vector<uint8_t> out;
+        icl_png_host_schedule(data, len, stage, out, info);
+        *need = (int64_t)out.size();
+        if (raw) {
+            if (cap < (int64_t)out.size()) return icl_fail(nullptr, ICL_ERR_ARG, "%s: buffer too small", what);
+            if (!out.empty()) memcpy(raw, out.data(), out.size());
+        }
+        return ICL_OK;
+    });
+}
+
+// Test hooks without a GPU (imageclust.h)
+extern "C" int icl_png_raw_mem_host(const uint8_t *data, int64_t bytes, int stage, uint8_t *raw, int64_t cap, int64_t *need, int32_t *info)
+{
+    if (!data || bytes < 0 || !need || !info || stage < 0 || stage > 2 || cap < 0) return icl_fail(nullptr, ICL_ERR_ARG, "icl_png_raw_mem_host: bad argument");
+    return png_raw_host(data, (size_t)bytes, stage, raw, cap, need, info, "icl_png_raw_mem_host");
+}
+
+extern "C" int icl_png_raw_file_host(const char *path, int stage, uint8_t *raw, int64_t cap, int64_t *need, int32_t *info)
+{
+    if (!path || !need || !info || stage < 0 || stage > 2 || cap < 0) return icl_fail(nullptr, ICL_ERR_ARG, "icl_png_raw_file_host: bad argument");
+    return no_throw(nullptr, "icl_png_raw_file_host", [&]() -> int {
+        std::vector<uint8_t> file;
+        if (icl_image_file_read(path, file) != ICL_IMAGE_PNG) return icl_fail(nullptr, ICL_ERR_IO, "icl_png_raw_file_host: %s is not a readable PNG", path);
+        return png_raw_host(file.data(), file.size(), stage, raw, cap, need, info, "icl_png_raw_file_host");
+    });
 }

@@ -130,7 +130,8 @@ int icl_embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head,
                     int32_t threads, float *out, int32_t *status);
 int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec,
                         int32_t threads, float *d_out, int32_t *status);
-/* what the last files call did: JPEGs rebuilt on the GPU, files decoded on the host (PNG, PPM, fallbacks),
+/* what the last files call did: JPEGs rebuilt on the GPU, files decoded on the host (PNG, PPM, fallbacks; with ICL_PNG_GPU a PNG
+ * decoded on the GPU is counted by icl_last_png_stats instead),
  * bytes uploaded, host thread-seconds spent in stage A / host decode */
 int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes,
                           double *host_decode_s);
@@ -161,6 +162,37 @@ int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, int64_t *ho
 int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
                          int64_t *offsets /* n + 1 */, int32_t *state /* n */);
 int icl_jpeg_coefs_file_host(const char *path, int sub_bits, int16_t *coefs, int64_t cap, int64_t *need, int32_t *info /* 8 */);
+/* ---- PNG on the GPU (opt-in) ----
+ * ICL_PNG_HOST (default): a host worker decodes a PNG whole (icl_decode_image_file's code) and resizes it; only the 224x224 row is
+ * uploaded.  ICL_PNG_GPU: for a PNG that QUALIFIES -- its chunks parse (signature, CRCs, IHDR, PLTE, IDAT, IEND, zlib header), it is
+ * not Adam7-interlaced, its zlib stream fits one staging slab (128 MiB) and its scanlines, height x (1 + row bytes), are at most 512 MiB
+ * -- a host worker only parses the chunks and copies the zlib stream; kernels inflate it (one workgroup per image), check the
+ * Adler-32, undo the scanline filters and resize from the scanlines.  All five colour types at every legal depth qualify.  The GPU
+ * accepts an image only when the final block ended with exactly the expected byte count from a legal stream (the host decoder's rules),
+ * the Adler-32 matches, every filter byte is 0..4 and no palette index is out of range; every image it rejects, and every file that
+ * does not qualify, takes the ICL_PNG_HOST route, which also owns every status code and message.  Rows, status codes and messages are
+ * identical in both modes.  Counters: a PNG decoded on the GPU is counted in gpu_pngs (icl_last_png_stats) and NOT in host_files
+ * (icl_last_ingest_stats); gpu_jpegs stays JPEG-only.  icl_embed_file, the single-file calls and icl_downsize_images keep PNG on the
+ * host.  The environment variable ICL_PNG_INFLATE=gpu selects ICL_PNG_GPU when the context is created. */
+enum { ICL_PNG_HOST = 0, ICL_PNG_GPU = 1 };
+int icl_set_png_options(icl_ctx *ctx, int png_mode);
+/* what the last files call did with its PNGs: decoded on the GPU and accepted, decoded by the host because of the routing rule (does
+ * not qualify, or ICL_PNG_HOST), rejected by the GPU check and redone by the host route, zlib stream bytes uploaded */
+int icl_last_png_stats(icl_ctx *ctx, int64_t *gpu_pngs, int64_t *host_pngs, int64_t *redone_on_host, int64_t *stream_bytes);
+/* Test hooks.  stage 0: the inflated stream (filter bytes + filtered scanlines); stage 1: after unfiltering (filter bytes kept); the
+ * host hooks also know stage 2: the sample-to-RGB rule on every pixel (w x h x 3).  state[i] / info[0]: 1 accepted, 0 rejected by the
+ * GPU check (no bytes), -1 the file does not qualify (no bytes).
+ * icl_png_raw_files: file i's bytes go to raw[offsets[i] .. offsets[i + 1]) (host memory, cap bytes); one single-image slab per file
+ * through the pipeline's own placement and launch code.  With raw == NULL only offsets[0..n] are computed and nothing is decoded (state
+ * is 0 for every qualifying file).  A rejected file keeps its range, unwritten.
+ * icl_png_raw_file_host / icl_png_raw_mem_host: no GPU; the kernels' schedule run as a host loop over the same __host__ __device__
+ * functions.  *need receives the byte count (0 unless accepted); raw may be NULL.  info[12]: state, w, h, depth, colour type, stored /
+ * fixed / dynamic block counts, longest code length seen, largest match distance, matches with distance < length, matches whose
+ * destination wraps the 32 KiB ring. */
+int icl_png_raw_files(icl_ctx *ctx, const char *const *paths, int64_t n, int stage, uint8_t *raw, int64_t cap, int64_t *offsets /* n + 1 */,
+                      int32_t *state /* n */);
+int icl_png_raw_file_host(const char *path, int stage, uint8_t *raw, int64_t cap, int64_t *need, int32_t *info /* 12 */);
+int icl_png_raw_mem_host(const uint8_t *data, int64_t bytes, int stage, uint8_t *raw, int64_t cap, int64_t *need, int32_t *info /* 12 */);
 int icl_set_batch(icl_ctx *ctx, int batch); /* embed batch size, 1..1024 */
 /* Which bf16 convolution launches take the deep-pipelined 256 x 256 x 64 kernel (conv_p8_kernel: LDS-DMA kept in flight across raw
  * barriers, counted vmcnt, staggered wave groups) instead of the 128 x 128 two-stage kernels: ICL_CONV_P8_OFF never, ICL_CONV_P8_AUTO
