@@ -338,3 +338,21 @@ func PerformClusteringWithConstraintsBatch(jobs []ClusteringJob) []ClusteringRes
 	}
 	return out
 }
+
+// ResumeClustering goes on from clusters that exist (the loop of PerformClusteringWithConstraints, :216-246, started from them instead
+// of from singletons): centroids[i] and sizes[i] describe cluster i -- a new image is a cluster of size 1 with its embedding, a negative
+// size freezes the cluster -- and kTarget > 0 replaces CalculateOptimalClusters.  The result is at seed granularity
+// (iclengine.SeededResult); false on impossible constraints, as the reference's (nil, false).
+func ResumeClustering(centroids [][]float32, sizes []int32, minSize, maxSize, kTarget int) (iclengine.SeededResult, bool) {
+	res, err := iclengine.ClusterManySeeded([]iclengine.SeededProblem{{Centroids: centroids, Sizes: sizes, MinSize: minSize,
+		MaxSize: maxSize, KTarget: kTarget}})
+	if err != nil {
+		log.Printf("Clustering engine error: %v", err)
+		return iclengine.SeededResult{}, false
+	}
+	if res[0].Status != 0 {
+		log.Printf("Seeded clustering failed with status %d: %s", res[0].Status, iclengine.LastError())
+		return res[0], false
+	}
+	return res[0], true
+}

@@ -110,6 +110,107 @@ func LastManyStats() (small, mid, large, midGroups int64, err error) {
 	return int64(a), int64(b), int64(c), int64(d), nil
 }
 
+// SeededProblem is one problem of ClusterManySeeded: Centroids[i] and Sizes[i] describe seed cluster i (a negative size: a frozen
+// cluster of that many items, never merged); KTarget > 0 is the number of clusters to stop at, else CalculateOptimalClusters of the item
+// total decides.
+type SeededProblem struct {
+	Centroids        [][]float32
+	Sizes            []int32
+	MinSize, MaxSize int
+	KTarget          int
+}
+
+// SeededResult is what icl_cluster_many_seeded gives for one problem, at seed granularity: ClusterID[i] (-1: seed i's cluster is below
+// MinSize), SeedRank[i] (its place in the cluster's seed sequence), the merge log as pairs of creation ids (seed i is i, merge t is
+// m + t), and COut: the row of each final cluster's rank-0 seed holds that cluster's centroid, every other row is zero.
+type SeededResult struct {
+	ClusterID, SeedRank []int32
+	NClusters           int
+	Merges              [][2]int32
+	COut                [][]float32
+	Status              int // ICL_OK, ICL_ERR_CONSTRAINT (the reference's (nil,false)), ICL_ERR_UNSUPPORTED
+}
+
+// ClusterManySeeded resumes the clustering loop (clustering.go:216-246) from existing clusters for many problems in one
+// icl_cluster_many_seeded call.  The error is the call's own (a bad argument, the device); a problem's failure is its Status.
+func ClusterManySeeded(probs []SeededProblem) ([]SeededResult, error) {
+	out := make([]SeededResult, len(probs))
+	if len(probs) == 0 {
+		return out, nil
+	}
+	raw, e := Ctx()
+	if e != nil {
+		return nil, e
+	}
+	np := len(probs)
+	eoff := make([]int64, np)
+	m := make([]int32, np)
+	d := make([]int32, np)
+	mn := make([]int32, np)
+	mx := make([]int32, np)
+	kt := make([]int32, np)
+	total, rows := 0, 0
+	for j, pr := range probs {
+		if len(pr.Sizes) != len(pr.Centroids) {
+			return nil, fmt.Errorf("problem %d: %d sizes for %d centroids", j, len(pr.Sizes), len(pr.Centroids))
+		}
+		m[j] = int32(len(pr.Centroids))
+		if m[j] > 0 {
+			d[j] = int32(len(pr.Centroids[0]))
+		}
+		mn[j], mx[j], kt[j] = int32(pr.MinSize), int32(pr.MaxSize), int32(pr.KTarget)
+		eoff[j] = int64(total)
+		total += (int(m[j])*int(d[j]) + 3) / 4 * 4 // each problem on a 16-byte boundary
+		rows += int(m[j])
+	}
+	flat := make([]float32, total+1) // [][]float32 cannot cross cgo: one contiguous buffer
+	cout := make([]float32, total+1)
+	ss := make([]int32, rows+1)
+	at := 0
+	for j, pr := range probs {
+		for i, row := range pr.Centroids {
+			copy(flat[int(eoff[j])+i*int(d[j]):], row)
+		}
+		copy(ss[at:], pr.Sizes)
+		at += int(m[j])
+	}
+	cid := make([]int32, rows+1)
+	rank := make([]int32, rows+1)
+	mg := make([]int32, 2*rows+1)
+	nc := make([]int32, np)
+	nm := make([]int32, np)
+	st := make([]int32, np)
+	for j := range st {
+		st[j] = -1 // stays -1 when the call fails before the problems run
+	}
+	i32 := func(p *int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(p)) }
+	rc := C.icl_cluster_many_seeded((*C.icl_ctx)(raw), C.int32_t(np), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(len(flat)),
+		(*C.int64_t)(unsafe.Pointer(&eoff[0])), i32(&m[0]), i32(&d[0]), i32(&ss[0]), i32(&mn[0]), i32(&mx[0]), i32(&kt[0]), i32(&cid[0]),
+		i32(&rank[0]), i32(&nc[0]), i32(&nm[0]), i32(&mg[0]), i32(&st[0]), (*C.float)(unsafe.Pointer(&cout[0])))
+	for j := range st {
+		if rc != C.ICL_OK && st[j] < 0 {
+			return nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		}
+	}
+	at = 0
+	for j := range probs {
+		r := SeededResult{Status: int(st[j]), NClusters: int(nc[j])}
+		r.ClusterID = append([]int32(nil), cid[at:at+int(m[j])]...)
+		r.SeedRank = append([]int32(nil), rank[at:at+int(m[j])]...)
+		for t := 0; t < int(nm[j]); t++ {
+			r.Merges = append(r.Merges, [2]int32{mg[2*at+2*t], mg[2*at+2*t+1]})
+		}
+		r.COut = make([][]float32, m[j])
+		for i := range r.COut {
+			o := int(eoff[j]) + i*int(d[j])
+			r.COut[i] = append([]float32(nil), cout[o:o+int(d[j])]...)
+		}
+		out[j] = r
+		at += int(m[j])
+	}
+	return out, nil
+}
+
 // Where a qualifying PNG of the batched file calls is inflated and unfiltered: icl_set_png_options' modes.
 const (
 	PNGHost = int(C.ICL_PNG_HOST)

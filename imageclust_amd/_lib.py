@@ -134,6 +134,9 @@ SYMBOLS = [
     ("icl_cluster_dev", _int, [_vp, _vp, _i64, _i32, _i32, _i32, _int, _vp, _vp, _pi32]),
     ("icl_cluster_many", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
+    ("icl_cluster_many_seeded", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
+    ("icl_cluster_many_seeded_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
+    ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_requests_layout", _int, [_i32, _vp, _vp, _int, _vp, _vp, _pi64]),
@@ -919,6 +922,54 @@ class Context:
             check(self.h, rc)
         return _unpack_many(pk, cid, rank, nc, nm, st, mg)
 
+    def cluster_many_seeded(self, problems, want_merges=False, want_centroids=False, raise_on_error=False, dev=False):
+        """icl_cluster_many_seeded: the clustering loop started from existing clusters.  problems = [(C, seed_size, min_size, max_size[,
+        k_target]), ...]: C holds one centroid row per seed, seed_size[i] its item count (negative: frozen, never merged), k_target > 0
+        the number of clusters to stop at (else CalculateOptimalClusters of the item total) -> a list of (cluster_id, seed_rank,
+        n_clusters, status) per problem at seed granularity, as cluster_many() gives them per image; want_merges appends the merge log
+        (seed i has id i, merge t id m + t), want_centroids then appends C_out (m x d: the row of each final cluster's rank-0 seed is
+        the cluster's centroid, every other row zero).  dev=True runs icl_cluster_many_seeded_dev on a device copy (the same result)."""
+        pk = pack_many([(pr[0], pr[2], pr[3]) for pr in problems])
+        nprob, rows = len(problems), int(pk["img_off"][-1])
+        sizes = [np.asarray(pr[1], np.int32).reshape(-1) for pr in problems]
+        for p, sz in enumerate(sizes):
+            if len(sz) != int(pk["n"][p]):
+                raise ValueError("problem %d: %d seed sizes for %d centroid rows" % (p, len(sz), int(pk["n"][p])))
+        ss = np.ascontiguousarray(np.concatenate(sizes + [np.zeros(0, np.int32)]), np.int32)
+        ss = ss if ss.size else np.zeros(1, np.int32)
+        kt = np.array([int(pr[4]) if len(pr) > 4 else 0 for pr in problems] + ([] if nprob else [0]), np.int32)
+        cid = np.full(max(rows, 1), -1, np.int32)
+        rank = np.full(max(rows, 1), -1, np.int32)
+        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
+        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
+        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        co = np.zeros(pk["E"].size, np.float32) if want_centroids else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        tail = (ptr(pk["e_off"]), ptr(pk["n"]), ptr(pk["d"]), ptr(ss), ptr(pk["min_size"]), ptr(pk["max_size"]), ptr(kt), ptr(cid), ptr(rank),
+                ptr(nc), ptr(nm), ptr(mg), ptr(st))
+        if dev:
+            dE, dC = self.malloc(max(pk["E"].nbytes, 4)), self.malloc(max(pk["E"].nbytes, 4)) if want_centroids else None
+            try:
+                self.h2d(dE, pk["E"])
+                if want_centroids:
+                    self.h2d(dC, co)
+                rc = self.L.icl_cluster_many_seeded_dev(self.h, nprob, _vp(dE), pk["E"].size, *tail, _vp(dC) if want_centroids else None)
+                if want_centroids:
+                    self.d2h(co, dC)
+            finally:
+                self.free(dE)
+                if dC is not None:
+                    self.free(dC)
+        else:
+            rc = self.L.icl_cluster_many_seeded(self.h, nprob, ptr(pk["E"]), pk["E"].size, *tail, ptr(co))
+        if rc != ICL_OK and (raise_on_error or (st[:nprob] < 0).any()):
+            check(self.h, rc)  # an argument or device error: no per-problem results
+        out = _unpack_many(pk, cid, rank, nc, nm, st, mg)
+        if want_centroids:
+            out = [r + (co[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)
+                   for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]
+        return out
+
     def cluster_dev(self, d_E, n, d, min_size, max_size, update=UPDATE_EXACT):
         cid = np.full(max(n, 1), -1, np.int32)
         rank = np.full(max(n, 1), -1, np.int32)
@@ -1090,6 +1141,21 @@ def calc_optimal_clusters(total, min_size, max_size):
     k = _i64()
     rc = load().icl_calc_optimal_clusters(total, min_size, max_size, C.byref(k))
     return (k.value, None) if rc == ICL_OK else (0, rc)
+
+
+def seeded_assign_ids(seed_size, min_size, merges):
+    """icl_seeded_assign_ids (host only): seed sizes, minSize and a merge log (pairs of creation ids: seed i is i, merge t is m + t) ->
+    (cluster_id[m], seed_rank[m], n_clusters) by the final-list rule of the seeded call."""
+    ss = np.ascontiguousarray(seed_size, np.int32).reshape(-1)
+    mg = np.ascontiguousarray(merges, np.int32).reshape(-1, 2)
+    m = len(ss)
+    cid, rank, nc = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32), _i32()
+    rc = load().icl_seeded_assign_ids(m, ss.ctypes.data if m else None, int(min_size), mg.ctypes.data if len(mg) else None, len(mg),
+                                      cid.ctypes.data, rank.ctypes.data, C.byref(nc))
+    if rc != ICL_OK:
+        msg = load().icl_last_error(None)
+        raise ICLError(rc, msg.decode() if msg else "")
+    return cid[:m], rank[:m], nc.value
 
 
 def decode_image_file(path):

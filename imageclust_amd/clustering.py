@@ -158,6 +158,141 @@ def PerformClusteringWithConstraintsMany(jobs, ctx: Optional[_lib.Context] = Non
     return out
 
 
+def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_target: int = 0, ctx: Optional[_lib.Context] = None):
+    """The loop of clustering.go:216-246 started from existing clusters (icl_cluster_many_seeded, one problem): centroids[i] and
+    sizes[i] describe seed cluster i, a negative size a frozen one that is never merged; k_target > 0 is the number of clusters to stop
+    at, else CalculateOptimalClusters of the item total decides -> ((cluster_id, seed_rank, n_clusters, merges, C_out), True) at seed
+    granularity -- C_out[i] is the centroid of the final cluster whose first seed is i, zero for every other seed -- or (None, False)
+    on impossible constraints."""
+    ctx = ctx or default_context()
+    C = np.asarray(centroids, np.float32)
+    if C.ndim != 2:
+        C = C.reshape(len(sizes), -1)
+    cid, rank, nc, st, mg, co = ctx.cluster_many_seeded([(C, sizes, minSize, maxSize, k_target)], want_merges=True, want_centroids=True)[0]
+    if st == _lib.ICL_ERR_CONSTRAINT:
+        return None, False
+    if st != _lib.ICL_OK:
+        raise _lib.ICLError(st, ctx.last_error())
+    return (cid, rank, nc, mg, co), True
+
+
+@dataclass
+class HeldCluster:
+    """A cluster a Clustering state holds between calls: member ids in the reference's order, the centroid as the loop left it, the
+    frozen flag, and its id in as_map() (-1: below minSize, so the reference's report drops it -- the state keeps it)."""
+    Members: List[str]
+    Centroid: np.ndarray
+    Frozen: bool = False
+    Id: int = -1
+
+
+class Clustering:
+    """A clustering that can go on: the final clusters of a run -- the dropped ones included -- are kept with sizes and centroids, and
+    recluster() resumes the reference's loop from them (DESIGN.md "Seeded clustering").  Keys name clusters by any of their members' ids.
+
+        state = Clustering.start(embeddings, ids, 3, 6)     # what PerformClusteringWithConstraints computes, kept
+        state.add(more_embeddings, more_ids)                # new images join as singletons
+        state.freeze(["img_4"])                             # the cluster holding img_4 stays as it is
+        state.recluster()
+        state.as_map()
+
+    `engine` replaces the GPU call in tests: engine(C, seed_size, minSize, maxSize, k_target) -> (cluster_id, seed_rank, n_clusters,
+    status, merges, C_out)."""
+
+    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None):
+        self.minSize, self.maxSize = int(minSize), int(maxSize)
+        self.ctx, self.engine = ctx, engine
+        self.clusters: List[HeldCluster] = []
+        self.embeddings: Dict[str, np.ndarray] = {}
+        self.ok = True
+        self.last_merges = np.zeros((0, 2), np.int32)
+
+    @classmethod
+    def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None) -> "Clustering":
+        """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
+        False (and every image is still a singleton) when the constraints cannot be met."""
+        state = cls(minSize, maxSize, ctx, engine)
+        state.add(embeddings, ids)
+        state.recluster()
+        return state
+
+    def add(self, embeddings, ids):
+        """New images, each a singleton seed behind the clusters held so far."""
+        E = np.asarray(embeddings, np.float32)
+        if E.ndim != 2:
+            E = E.reshape(len(ids), -1)
+        if len(E) != len(ids):
+            raise ValueError("%d embeddings for %d ids" % (len(E), len(ids)))
+        for row, key in zip(E, ids):
+            if key in self.embeddings:
+                raise ValueError("id %r is already clustered" % (key,))
+            self.embeddings[key] = np.array(row, np.float32, copy=True)
+            self.clusters.append(HeldCluster([key], self.embeddings[key].copy()))
+
+    def _holding(self, keys) -> List[int]:
+        where = {k: i for i, c in enumerate(self.clusters) for k in c.Members}
+        return sorted({where[k] for k in keys})
+
+    def freeze(self, keys):
+        for i in self._holding(keys):
+            self.clusters[i].Frozen = True
+
+    def unfreeze(self, keys):
+        for i in self._holding(keys):
+            self.clusters[i].Frozen = False
+
+    def dissolve(self, keys):
+        """The clusters holding these ids fall apart: their members become singleton seeds again, in member order, at the end."""
+        gone = self._holding(keys)
+        freed = [k for i in gone for k in self.clusters[i].Members]
+        self.clusters = [c for i, c in enumerate(self.clusters) if i not in set(gone)]
+        self.clusters += [HeldCluster([k], self.embeddings[k].copy()) for k in freed]
+
+    def seeds(self):
+        """The seeded problem the state stands for: (centroids m x d, seed_size m; negative: frozen)."""
+        d = len(next(iter(self.embeddings.values()))) if self.embeddings else 0
+        C = np.stack([c.Centroid for c in self.clusters]).astype(np.float32) if self.clusters else np.zeros((0, d), np.float32)
+        ss = np.array([-len(c.Members) if c.Frozen else len(c.Members) for c in self.clusters], np.int32)
+        return C, ss
+
+    def recluster(self, k_target: int = 0) -> bool:
+        """Resume the loop from the clusters held.  False, with the state as it was, when the constraints cannot be met."""
+        C, ss = self.seeds()
+        if self.engine is not None:
+            cid, rank, nc, st, mg, co = self.engine(C, ss, self.minSize, self.maxSize, k_target)
+        else:
+            ctx = self.ctx or default_context()
+            cid, rank, nc, st, mg, co = ctx.cluster_many_seeded([(C, ss, self.minSize, self.maxSize, k_target)], want_merges=True,
+                                                                want_centroids=True)[0]
+        self.ok = st == _lib.ICL_OK
+        if st == _lib.ICL_ERR_CONSTRAINT:
+            return False
+        if st != _lib.ICL_OK:
+            raise _lib.ICLError(st, "icl_cluster_many_seeded: the problem failed with code %d" % st)
+        # the final list from the merge log: surviving seeds in seed order, then merged clusters in creation order, a's seeds before b's
+        m = len(self.clusters)
+        seq = {i: [i] for i in range(m)}
+        for t, (a, b) in enumerate(np.asarray(mg).reshape(-1, 2)):
+            seq[m + t] = seq.pop(int(a)) + seq.pop(int(b))
+        held = []
+        for c in sorted(seq):
+            first = seq[c][0]
+            # an image's rank: the items of the seeds before its own, plus its place in its own seed
+            members = [k for s in seq[c] for k in self.clusters[s].Members]
+            held.append(HeldCluster(members, np.array(co[first], np.float32, copy=True), c < m and self.clusters[c].Frozen, int(cid[first])))
+        self.clusters = held
+        self.last_merges = np.asarray(mg, np.int32).reshape(-1, 2).copy()
+        return True
+
+    def as_map(self) -> Dict[int, List[str]]:
+        """The reference's map[int][]string (clustering.go:265-280): the kept clusters."""
+        return {c.Id: list(c.Members) for c in self.clusters if c.Id >= 0}
+
+    def assignments(self) -> Dict[str, Tuple[int, int]]:
+        """id -> (cluster id or -1, rank in the cluster's member list or -1)"""
+        return {k: ((c.Id, r) if c.Id >= 0 else (-1, -1)) for c in self.clusters for r, k in enumerate(c.Members)}
+
+
 def clusters_as_map(cluster_id, member_rank, ids) -> Dict[int, List[str]]:
     """Canonical (cluster_id, member_rank) -> map[int][]string of clustering.go:265-280."""
     out: Dict[int, List[str]] = {}

@@ -14,12 +14,16 @@
 //     (ComputeInitialDistanceMatrix, clustering.go:61-73), one thread per pair; ward_many_merge_kernel keeps the triangle in LDS when it
 //     fits (n <= 281, WM_LDS_MAX), forms the new cluster's row exactly (:76-96), one row per thread, and a thread rescans a row whose
 //     cached partner died.  Mid route (cap < n <= WMM_CAP): see "the mid-size route" below.
+//   * The four kernels themselves are in ward_many_kernels.h, included twice: as they are for problems that start from singletons,
+//     and once more for problems that start from SEED clusters (icl_cluster_many_seeded, "seeded clustering" at the end of this file).
 // Host.  cluster_many_locked runs the stages wm_classify (k, status, wm_route of every problem), wm_make_plan (launch groups --
 // wm_group: the small route is one, the mid route's are cut under a workspace budget -- and the workspace layout), wm_enqueue (uploads,
 // aligned copies, wm_run_group per group, one read-back of the one log slab), the large-N problems (ward.hip's
 // icl_ward_cluster_exact: above WMM_CAP rows, a lone small problem, mid-size problems the policy leaves there, icl_set_many_options),
 // wm_collect.  What the two routes' groups do differently on the host is the table wm_kind.
 // Cluster ids and member ranks come from the merge log by ward.hip's rule (icl_ward_assign_ids) whichever route a problem took.
+// The seeded calls run wm_classify_seeded, the same wm_make_plan / wm_enqueue with a seeded wm_args, wm_collect_seeded (ids by the same
+// rule at seed granularity, wm_seeded_ids) and ward_many_cout_kernel for C_out; they never take the large-N engine.
 #pragma clang fp contract(off)
 
 #include "icl_common.h"
@@ -55,6 +59,13 @@ struct wm_prob {
 
 static_assert(sizeof(wm_prob) % 8 == 0, "wm_prob is an array element");
 
+// What a seeded problem (icl_cluster_many_seeded, DESIGN.md "Seeded clustering") has beside its wm_prob, in a table of its own so that
+// the unseeded kernels' table keeps its layout: E holds the n seed centroids, and
+struct wm_seed {
+    const int32_t *size; // n effective sizes >= 1: a seed's item count, or the problem's max_size for a frozen seed (every pair banned)
+    int32_t *fin;        // out, n entries: the creation id of the cluster living in slot s when the loop ended, -1 for a dead slot
+};
+
 __host__ __device__ static inline int64_t wm_tri_len(int64_t n) { return n * (n - 1) / 2; }
 
 // The per-slot state both merge kernels keep in LDS, in this order; wm_slots_bytes and wm_carve are its only description.
@@ -85,22 +96,6 @@ __device__ __forceinline__ wm_slots wm_carve(unsigned char *base, int n, int wav
 static_assert(WM_META_TAIL >= WM_SLOT_BYTES + WM_WAVES * 12, "wm_meta_bytes(n) >= wm_slots_bytes(n, WM_WAVES)");
 __host__ __device__ static inline int64_t wm_meta_bytes(int64_t n) { return (n * WM_SLOT_BYTES + WM_META_TAIL + 15) / 16 * 16; }
 static inline int64_t wm_lds_bytes(int64_t n, bool tri) { return wm_meta_bytes(n) + (tri ? wm_tri_len(n) * 4 : 0); }
-
-// ComputeInitialDistanceMatrix (clustering.go:61-73) of every problem: block b covers pairs [pair0[b], pair0[b] + 256) of problem prob[b]
-__global__ __launch_bounds__(WM_THREADS) void ward_many_init_kernel(const wm_prob *__restrict__ P, const int32_t *__restrict__ blk_prob,
-                                                                    const int64_t *__restrict__ blk_pair0)
-{
-    const wm_prob p = P[blk_prob[blockIdx.x]];
-    const int64_t q = blk_pair0[blockIdx.x] + threadIdx.x;
-    if (q >= wm_tri_len(p.n)) return;
-    int64_t i = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)q)) * 0.5); // row i holds pairs [i (i - 1) / 2, i (i + 1) / 2)
-    while (i * (i - 1) / 2 > q) --i;
-    while ((i + 1) * i / 2 <= q) ++i;
-    const int64_t j = q - i * (i - 1) / 2;
-    float v = ICL_MAXF; // max_size < 2: every pair of singletons is banned (clustering.go:228-234) and never read
-    if (p.max_size >= 2) v = ward_pair_value(p.E + i * p.d, p.E + j * p.d, p.d, 1, 1); // WardDistance(clusters[i], clusters[j]) :66
-    p.tri[q] = v;
-}
 
 // key of an eligible pair: value bits (>= +0, below MaxFloat32), then the larger and the smaller creation id -- unsigned order is the
 // reference's scan order (ward.hip's header)
@@ -194,90 +189,6 @@ __device__ __forceinline__ int wm_merge_pair(const wm_prob &p, const wm_slots S,
     return sa + sb;
 }
 
-__global__ __launch_bounds__(WM_THREADS) void ward_many_merge_kernel(const wm_prob *__restrict__ P, const int32_t *__restrict__ order)
-{
-    extern __shared__ __align__(16) unsigned char wm_lds[];
-    const wm_prob p = P[order[blockIdx.x]];
-    const int n = p.n, d = p.d, maxs = p.max_size;
-    const wm_slots S = wm_carve(wm_lds, n, WM_WAVES);
-    uint64_t *const rkey = S.rkey;
-    int32_t *const rarg = S.rarg, *const sz = S.sz, *const cid = S.cid;
-    float *tri = p.tri;
-    if (p.lds_tri) {
-        float *lt = reinterpret_cast<float *>(wm_lds + wm_meta_bytes(n));
-        const int64_t len = wm_tri_len(n);
-        for (int64_t q = threadIdx.x; q < len; q += WM_THREADS) lt[q] = p.tri[q];
-        tri = lt;
-    }
-    for (int t = threadIdx.x; t < n; t += WM_THREADS) {
-        sz[t] = 1;
-        cid[t] = t;
-    }
-    __syncthreads();
-    auto cent = [&](int s) { return wm_cent(p, cid, s); };
-    auto at = [&](int a, int b) -> float & { return a > b ? tri[a * (a - 1) / 2 + b] : tri[b * (b - 1) / 2 + a]; };
-    // row t's minimum over every live, size-compatible partner below MaxFloat32 (NaN never is: clustering.go:126)
-    auto scan = [&](int t) {
-        uint64_t best = ~0ull;
-        int arg = -1;
-        const int st = sz[t], ct = cid[t];
-        for (int u = 0; u < n; ++u) {
-            const int su = sz[u];
-            if (u == t || su == 0 || st + su > maxs) continue;
-            const float v = at(t, u);
-            if (!(v < ICL_MAXF)) continue;
-            const uint64_t k = wm_key(v, ct, cid[u]);
-            if (k < best) {
-                best = k;
-                arg = u;
-            }
-        }
-        rkey[t] = best;
-        rarg[t] = arg;
-    };
-    for (int t = threadIdx.x; t < n; t += WM_THREADS) scan(t);
-    __syncthreads();
-    int step = 0;
-    for (; step < p.T; ++step) {
-        int shi, slo;
-        if (!wm_select_pair<WM_THREADS>(S, n, shi, slo)) break;
-        const int sn = slo, snew = wm_merge_pair<WM_THREADS>(p, S, step, shi, slo), cnew = n + step;
-        __syncthreads();
-        // UpdateDistanceMatrix (:76-96): WardDistance(clusters[t], newCluster) for every live t; the owner of row t updates its cache
-        const float *cn = p.C + (int64_t)sn * d;
-        uint64_t nk = ~0ull;
-        int nr = -1;
-        uint32_t stale = 0; // rows of this thread whose cached partner just died
-        for (int t = threadIdx.x, m = 0; t < n; t += WM_THREADS, ++m) {
-            if (t == sn || sz[t] == 0) continue;
-            const int st = sz[t];
-            float v = ICL_MAXF; // banned: never selected (:228-234), never evaluated
-            if (st + snew <= maxs) v = ward_pair_value(cent(t), cn, d, st, snew);
-            at(t, sn) = v;
-            const uint64_t k = (st + snew <= maxs && v < ICL_MAXF) ? wm_key(v, cid[t], cnew) : ~0ull;
-            if (k < nk) {
-                nk = k;
-                nr = t;
-            }
-            if (rarg[t] == shi || rarg[t] == slo)
-                stale |= 1u << m;
-            else if (k < rkey[t]) {
-                rkey[t] = k;
-                rarg[t] = sn;
-            }
-        }
-        wm_block_min<WM_WAVES>(nk, nr, S.red_k, S.red_r); // (its barriers also publish the new row)
-        if (threadIdx.x == 0) {
-            rkey[sn] = nk;
-            rarg[sn] = nr;
-        }
-        for (int t = threadIdx.x, m = 0; t < n; t += WM_THREADS, ++m)
-            if (stale >> m & 1u) scan(t);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *p.nm = step;
-}
-
 // ---- the mid-size route: cap < n <= WMM_CAP rows, one workgroup per problem ----------------------------------------------------------
 // The same selection order, ban, merge log and centroid rule as ward_many_merge_kernel; what differs is who does the work:
 //   * the matrix is a full n x n square in the global workspace, written symmetrically, so a row rescan reads contiguous memory and
@@ -317,81 +228,6 @@ __host__ __device__ static inline int64_t wmm_lds_bytes(int64_t n)
     return (WMM_CHUNK_BYTES + wm_slots_bytes(n, WMM_WAVES) + 8 + n * 4 + 15) / 16 * 16;
 }
 
-// ComputeInitialDistanceMatrix (clustering.go:61-73) into the full square: block b computes the 64 x 64 pairs (i, j) of tile
-// (ti, tj), ti >= tj, of problem blk_prob[b]; k-chunks of both row sets are staged in LDS, every thread holds 4 x 4 pairs, and every
-// pair's sum is s = s + fl(fl(x_k - y_k)^2) strictly in k order -- the value ward_pair_value(E_i, E_j, d, 1, 1) returns.
-__global__ __launch_bounds__(256) void ward_many_mid_init_kernel(const wm_prob *__restrict__ P, const int32_t *__restrict__ blk_prob,
-                                                                 const int32_t *__restrict__ blk_tile)
-{
-    __shared__ float A[WMI_TILE * (WMI_KC + 1)], B[WMI_TILE * (WMI_KC + 1)];
-    const wm_prob p = P[blk_prob[blockIdx.x]];
-    const int n = p.n, d = p.d, tid = threadIdx.x;
-    const int i0 = (blk_tile[blockIdx.x] >> 16) * WMI_TILE, j0 = (blk_tile[blockIdx.x] & 0xffff) * WMI_TILE;
-    const int tx = tid & 15, ty = tid >> 4;
-    float s[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0f;
-    if (p.max_size >= 2) {
-        const bool vec = (d & 3) == 0;
-        for (int k0 = 0; k0 < d; k0 += WMI_KC) {
-            const int kc = min(WMI_KC, d - k0);
-            __syncthreads(); // the previous chunk has been added
-            if (vec) { // thread -> (row tid / 4, floats 4 (tid % 4) ...) of both row sets: 16-byte loads, 64 B per row
-                const int r = tid >> 2, kk = (tid & 3) * 4;
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-                if (kk < kc) {
-                    if (i0 + r < n) a = *reinterpret_cast<const float4 *>(p.E + (int64_t)(i0 + r) * d + k0 + kk);
-                    if (j0 + r < n) b = *reinterpret_cast<const float4 *>(p.E + (int64_t)(j0 + r) * d + k0 + kk);
-                }
-                float *pa = A + r * (WMI_KC + 1) + kk, *pb = B + r * (WMI_KC + 1) + kk;
-                pa[0] = a.x, pa[1] = a.y, pa[2] = a.z, pa[3] = a.w;
-                pb[0] = b.x, pb[1] = b.y, pb[2] = b.z, pb[3] = b.w;
-            } else {
-#pragma unroll
-                for (int q = 0; q < WMI_TILE * WMI_KC / 256; ++q) {
-                    const int idx = tid + q * 256, r = idx / WMI_KC, kk = idx % WMI_KC;
-                    float a = 0.f, b = 0.f;
-                    if (kk < kc) {
-                        if (i0 + r < n) a = p.E[(int64_t)(i0 + r) * d + k0 + kk];
-                        if (j0 + r < n) b = p.E[(int64_t)(j0 + r) * d + k0 + kk];
-                    }
-                    A[r * (WMI_KC + 1) + kk] = a;
-                    B[r * (WMI_KC + 1) + kk] = b;
-                }
-            }
-            __syncthreads();
-            for (int k = 0; k < kc; ++k) {
-                float x[4], y[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) x[a] = A[(ty + 16 * a) * (WMI_KC + 1) + k];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) y[b] = B[(tx + 16 * b) * (WMI_KC + 1) + k];
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const float df = x[a] - y[b]; // clustering.go:139
-                        const float pr = df * df;     // :154 product (rounded)
-                        s[a][b] = s[a][b] + pr;       // :154 sum (rounded), strictly in k order
-                    }
-            }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
-            if (i >= n || j >= n || i < j) continue;
-            // max_size < 2: every pair of singletons is banned (clustering.go:228-234) and never read; the diagonal is never read
-            const float v = (p.max_size >= 2 && i != j) ? ward_scale(s[a][b], 1, 1) : ICL_MAXF;
-            p.tri[(int64_t)i * n + j] = v;
-            p.tri[(int64_t)j * n + i] = v;
-        }
-}
-
 // the threads of a wave for which f holds append t to list (order within the list is arbitrary: every use of it is per row)
 __device__ __forceinline__ void wmm_append(bool f, int t, int32_t *count, uint16_t *list)
 {
@@ -404,209 +240,26 @@ __device__ __forceinline__ void wmm_append(bool f, int t, int32_t *count, uint16
     if (f) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)t;
 }
 
-__global__ __launch_bounds__(WMM_THREADS) void ward_many_mid_merge_kernel(const wm_prob *__restrict__ P, const int32_t *__restrict__ order)
+// the kernels: from singletons, then from seeds
+#define WM_SEEDED 0
+#include "ward_many_kernels.h"
+#undef WM_SEEDED
+#define WM_SEEDED 1
+#include "ward_many_kernels.h"
+#undef WM_SEEDED
+
+// C_out of the seeded calls: block b copies row src[b] (d[b] floats: a final cluster's centroid, from a problem's seed rows or its
+// centroid scratch) to out + dst[b], or writes zeros there when src[b] is null
+struct wm_crow {
+    const float *src;
+    int64_t dst;
+    int32_t d, pad;
+};
+__global__ __launch_bounds__(256) void ward_many_cout_kernel(const wm_crow *__restrict__ R, float *__restrict__ out)
 {
-    extern __shared__ __align__(16) unsigned char wm_lds[];
-    const wm_prob p = P[order[blockIdx.x]];
-    const int n = p.n, d = p.d, maxs = p.max_size, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float *buf = reinterpret_cast<float *>(wm_lds);                     // two chunk buffers: row r of the pass at r * WMM_STRIDE
-    float *cbuf = buf + 2 * WMM_BUF;                                    // two chunks of the new centroid
-    const wm_slots S = wm_carve(wm_lds + WMM_CHUNK_BYTES, n, WMM_WAVES);
-    uint64_t *const rkey = S.rkey;
-    int32_t *const rarg = S.rarg, *const sz = S.sz, *const cid = S.cid;
-    int32_t *cnt = reinterpret_cast<int32_t *>(wm_lds + WMM_CHUNK_BYTES + wm_slots_bytes(n, WMM_WAVES));                               // [0] rows to evaluate, [1] rows to rescan
-    uint16_t *ev = reinterpret_cast<uint16_t *>(cnt + 2);
-    uint16_t *stl = ev + n;
-    float *M = p.tri; // entry (a, b) at a n + b, both orders written
-    for (int t = tid; t < n; t += WMM_THREADS) {
-        sz[t] = 1;
-        cid[t] = t;
-    }
-    __syncthreads();
-    auto cent = [&](int s) { return wm_cent(p, cid, s); };
-    // row t's minimum over every live, size-compatible partner below MaxFloat32 (NaN never is: clustering.go:126), by one wave
-    auto scan = [&](int t) {
-        uint64_t best = ~0ull;
-        int arg = -1;
-        const int st = sz[t], ct = cid[t];
-        const float *row = M + (int64_t)t * n;
-        for (int u = lane; u < n; u += 64) {
-            const int su = sz[u];
-            if (u == t || su == 0 || st + su > maxs) continue;
-            const float v = row[u];
-            if (!(v < ICL_MAXF)) continue;
-            const uint64_t k = wm_key(v, ct, cid[u]);
-            if (k < best) {
-                best = k;
-                arg = u;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off; off >>= 1) {
-            const uint64_t ok = __shfl_xor(best, off);
-            const int oa = __shfl_xor(arg, off);
-            if (ok < best) {
-                best = ok;
-                arg = oa;
-            }
-        }
-        if (lane == 0) {
-            rkey[t] = best;
-            rarg[t] = arg;
-        }
-    };
-    for (int t = wave; t < n; t += WMM_WAVES) scan(t);
-    __syncthreads();
-    const bool vec = (d & 3) == 0; // rows are 16-byte aligned then (the host copies a problem whose rows are not)
-    const int nch = (d + WMM_KC - 1) / WMM_KC;
-    int step = 0;
-    for (; step < p.T; ++step) {
-        int shi, slo;
-        if (!wm_select_pair<WMM_THREADS>(S, n, shi, slo)) break;
-        const int sn = slo, snew = wm_merge_pair<WMM_THREADS>(p, S, step, shi, slo), cnew = n + step;
-        if (tid == 0) cnt[0] = cnt[1] = 0;
-        __syncthreads();
-        // UpdateDistanceMatrix (:76-96).  Every live row t: banned pairs get MaxFloat32 and are never evaluated (:228-234); the
-        // others go on the list of rows to evaluate; rows whose cached partner just died go on the list of rows to rescan.
-        const float *cn = p.C + (int64_t)sn * d;
-        float *Mn = M + (int64_t)sn * n;
-        for (int t0 = 0; t0 < n; t0 += WMM_THREADS) {
-            const int t = t0 + tid;
-            const bool live = t < n && t != sn && sz[t] != 0;
-            const bool evalp = live && sz[t] + snew <= maxs;
-            if (live && !evalp) {
-                M[(int64_t)t * n + sn] = ICL_MAXF;
-                Mn[t] = ICL_MAXF;
-            }
-            wmm_append(evalp, t, &cnt[0], ev);
-            wmm_append(live && (rarg[t] == shi || rarg[t] == slo), t, &cnt[1], stl);
-        }
-        __syncthreads();
-        const int ne = cnt[0], ns = cnt[1];
-        uint64_t nk = ~0ull;
-        int nr = -1;
-        for (int r0 = 0; r0 < ne; r0 += WMM_THREADS) { // a pass: WMM_THREADS listed rows, one per thread
-            const int nrows = min(WMM_THREADS, ne - r0);
-            const int my = tid < nrows ? ev[r0 + tid] : -1;
-            float s = 0.0f;
-            // the loads of this thread, the same rows in every chunk: vec, float4 q covers floats 4 (idx % (KC / 4)) ... of row
-            // idx / (KC / 4), idx = tid + q WMM_THREADS; else float q is element idx % KC of row idx / KC
-            const float *src[WMM_KC]; // (vec: the first KC / 4)
-            if (vec) {
-#pragma unroll
-                for (int q = 0; q < WMM_KC / 4; ++q) {
-                    const int idx = tid + q * WMM_THREADS, r = idx / (WMM_KC / 4);
-                    src[q] = r < nrows ? cent(ev[r0 + r]) + (idx % (WMM_KC / 4)) * 4 : nullptr;
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < WMM_KC; ++q) {
-                    const int idx = tid + q * WMM_THREADS, r = idx / WMM_KC;
-                    src[q] = r < nrows ? cent(ev[r0 + r]) + idx % WMM_KC : nullptr;
-                }
-            }
-            float g[WMM_KC];
-            float gc = 0.0f; // threads 0 .. KC - 1: the new centroid's element
-            auto fetch = [&](int c) {
-                const int k0 = c * WMM_KC;
-                if (vec) {
-#pragma unroll
-                    for (int q = 0; q < WMM_KC / 4; ++q) {
-                        const int kk = ((tid + q * WMM_THREADS) % (WMM_KC / 4)) * 4;
-                        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (src[q] && k0 + kk < d) v = *reinterpret_cast<const float4 *>(src[q] + k0);
-                        g[4 * q] = v.x, g[4 * q + 1] = v.y, g[4 * q + 2] = v.z, g[4 * q + 3] = v.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < WMM_KC; ++q) {
-                        const int kk = (tid + q * WMM_THREADS) % WMM_KC;
-                        g[q] = 0.0f;
-                        if (src[q] && k0 + kk < d) g[q] = src[q][k0];
-                    }
-                }
-                if (tid < WMM_KC) gc = k0 + tid < d ? cn[k0 + tid] : 0.0f;
-            };
-            auto stash = [&](int c) {
-                float *b = buf + (c & 1) * WMM_BUF;
-                if (vec) {
-#pragma unroll
-                    for (int q = 0; q < WMM_KC / 4; ++q) {
-                        const int idx = tid + q * WMM_THREADS;
-                        float *o = b + (idx / (WMM_KC / 4)) * WMM_STRIDE + (idx % (WMM_KC / 4)) * 4;
-                        o[0] = g[4 * q], o[1] = g[4 * q + 1], o[2] = g[4 * q + 2], o[3] = g[4 * q + 3];
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < WMM_KC; ++q) {
-                        const int idx = tid + q * WMM_THREADS;
-                        b[(idx / WMM_KC) * WMM_STRIDE + idx % WMM_KC] = g[q];
-                    }
-                }
-                if (tid < WMM_KC) cbuf[(c & 1) * WMM_KC + tid] = gc;
-            };
-            fetch(0);
-            stash(0);
-            __syncthreads();
-            for (int c = 0; c < nch; ++c) {
-                if (c + 1 < nch) fetch(c + 1); // in flight while chunk c is added
-                if (my >= 0) {
-                    const float *rb = buf + (c & 1) * WMM_BUF + tid * WMM_STRIDE;
-                    const float4 *cb4 = reinterpret_cast<const float4 *>(cbuf + (c & 1) * WMM_KC);
-                    const int kc = min(WMM_KC, d - c * WMM_KC);
-                    if (kc == WMM_KC) {
-#pragma unroll
-                        for (int q = 0; q < WMM_KC / 4; ++q) {
-                            const float4 y = cb4[q];
-                            float df = rb[4 * q] - y.x; // clustering.go:139
-                            float pr = df * df;         // :154 product (rounded)
-                            s = s + pr;                 // :154 sum (rounded), strictly in k order
-                            df = rb[4 * q + 1] - y.y;
-                            pr = df * df;
-                            s = s + pr;
-                            df = rb[4 * q + 2] - y.z;
-                            pr = df * df;
-                            s = s + pr;
-                            df = rb[4 * q + 3] - y.w;
-                            pr = df * df;
-                            s = s + pr;
-                        }
-                    } else {
-                        const float *cb = cbuf + (c & 1) * WMM_KC;
-                        for (int q = 0; q < kc; ++q) {
-                            const float df = rb[q] - cb[q];
-                            const float pr = df * df;
-                            s = s + pr;
-                        }
-                    }
-                }
-                if (c + 1 < nch) stash(c + 1); // (that buffer was last read before the previous barrier)
-                __syncthreads();
-            }
-            if (my >= 0) { // WardDistance(clusters[my], newCluster); the owner of the row updates its cache
-                const float v = ward_scale(s, sz[my], snew);
-                M[(int64_t)my * n + sn] = v;
-                Mn[my] = v;
-                const uint64_t k = v < ICL_MAXF ? wm_key(v, cid[my], cnew) : ~0ull;
-                if (k < nk) {
-                    nk = k;
-                    nr = my;
-                }
-                if (rarg[my] != shi && rarg[my] != slo && k < rkey[my]) {
-                    rkey[my] = k;
-                    rarg[my] = sn;
-                }
-            }
-        }
-        wm_block_min<WMM_WAVES>(nk, nr, S.red_k, S.red_r); // (its barriers also publish the new row and column)
-        if (tid == 0) {
-            rkey[sn] = nk;
-            rarg[sn] = nr;
-        }
-        for (int q = wave; q < ns; q += WMM_WAVES) scan(stl[q]);
-        __syncthreads();
-    }
-    if (tid == 0) *p.nm = step;
+    const wm_crow r = R[blockIdx.x];
+    float *o = out + r.dst;
+    for (int k = threadIdx.x; k < r.d; k += 256) o[k] = r.src ? r.src[k] : 0.0f;
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -742,6 +395,7 @@ struct wm_kind {
     int64_t (*lds_bytes)(int64_t n); // dynamic LDS of the merge kernel
     const void *init_fn, *merge_fn;
     unsigned init_threads, merge_threads;
+    bool own_data; // its group has a data region of its own (the small route); else the groups share one, one after the other
 };
 static const wm_kind wm_kind_small = {
     [](int64_t n) { return wm_tri_len(n) * 4; },
@@ -751,7 +405,7 @@ static const wm_kind wm_kind_small = {
     8,
     [](int64_t n) { return wm_lds_bytes(n, true) <= WM_LDS_MAX; },
     [](int64_t n) { return wm_lds_bytes(n, wm_lds_bytes(n, true) <= WM_LDS_MAX); },
-    (const void *)ward_many_init_kernel, (const void *)ward_many_merge_kernel, WM_THREADS, WM_THREADS,
+    (const void *)ward_many_init_kernel, (const void *)ward_many_merge_kernel, WM_THREADS, WM_THREADS, true,
 };
 static const wm_kind wm_kind_mid = {
     [](int64_t n) { return n * n * 4; },
@@ -763,8 +417,17 @@ static const wm_kind wm_kind_mid = {
     4,
     [](int64_t) { return false; },
     [](int64_t n) { return wmm_lds_bytes(n); },
-    (const void *)ward_many_mid_init_kernel, (const void *)ward_many_mid_merge_kernel, 256, WMM_THREADS,
+    (const void *)ward_many_mid_init_kernel, (const void *)ward_many_mid_merge_kernel, 256, WMM_THREADS, false,
 };
+// the seeded instantiations: the same shapes, block lists and LDS; their kernels take the wm_seed table as one more argument
+static wm_kind wm_seeded_kind(wm_kind k, const void *init_fn, const void *merge_fn)
+{
+    k.init_fn = init_fn;
+    k.merge_fn = merge_fn;
+    return k;
+}
+static const wm_kind wm_kind_small_seeded = wm_seeded_kind(wm_kind_small, (const void *)ward_many_init_seeded_kernel, (const void *)ward_many_merge_seeded_kernel);
+static const wm_kind wm_kind_mid_seeded = wm_seeded_kind(wm_kind_mid, (const void *)ward_many_mid_init_seeded_kernel, (const void *)ward_many_mid_merge_seeded_kernel);
 
 // centroids + matrix of one problem in a group's data region (256-byte aligned pieces)
 static size_t wm_data_bytes(const wm_kind &k, int64_t n, int64_t d)
@@ -786,7 +449,11 @@ struct wm_group {
     size_t data_bytes = 0;
     size_t o_head = 0, o_data = 0; // in the workspace; the head: [problem table] [init-block arguments] [order] [init-block problems]
     std::vector<unsigned char> head;
-    size_t head_bytes() const { return sizeof(wm_prob) * probs.size() + (size_t)kind->arg_bytes * blk_arg.size() + 4 * (probs.size() + blk_prob.size()); }
+    bool seeded = false;  // then the head goes on, 8-byte aligned: [wm_seed table] [effective seed sizes, problem after problem]
+    size_t seed_rows = 0; // seeds of all its problems
+    size_t plain_bytes() const { return sizeof(wm_prob) * probs.size() + (size_t)kind->arg_bytes * blk_arg.size() + 4 * (probs.size() + blk_prob.size()); }
+    size_t o_seed() const { return (plain_bytes() + 7) / 8 * 8; }
+    size_t head_bytes() const { return seeded ? o_seed() + sizeof(wm_seed) * probs.size() + 4 * seed_rows : plain_bytes(); }
 };
 
 // the per-problem arguments of both entry points
@@ -794,6 +461,11 @@ struct wm_args {
     int32_t nprob;
     const int64_t *e_off;
     const int32_t *n, *d, *min_size, *max_size;
+    // the seeded calls (n[p] is the number of seeds m): seed_size as the caller gave it, k_target (may be null), and whether C_out is
+    // wanted (then every problem's rows are on the device and a mid-route problem's centroid scratch outlives its group)
+    bool seeded = false;
+    const int32_t *seed_size = nullptr, *k_target = nullptr;
+    bool want_cout = false, cout_host = false;
 };
 
 struct wm_plan {
@@ -807,6 +479,14 @@ struct wm_plan {
     int64_t log_ints = 0;
     std::vector<size_t> o_al; // problems whose rows the float4 loads cannot read in place: a 16-byte aligned copy
     size_t o_e = 0, o_logs = 0, ws_bytes = 0;
+    // seeded calls: every seed's effective size (wm_seed::size), first seed of problem p at img[p], and the problem's clamped max_size
+    // (a pair of unfrozen clusters never holds more than N items, so the clamp bans none of them); with C_out: the centroid scratch of a
+    // mid-route problem outside its group's shared region, every problem's centroid scratch as wm_run_group placed it, the table of
+    // ward_many_cout_kernel and, for the host call, the device copy of C_out
+    std::vector<int32_t> eff, kmax; // (kmax: the max_size the seeded kernels see, clamped to [1, N] so that a frozen seed's size fits)
+    std::vector<size_t> o_c;
+    std::vector<const float *> c_dev;
+    size_t o_crow = 0, o_cout = 0;
 };
 
 // k, status and route of every problem; many_stats
@@ -853,6 +533,63 @@ static void wm_classify(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector
     ctx->many_stats[2] = std::count(pl.route.begin(), pl.route.end(), WM_LARGE);
 }
 
+// The same for a seeded call (DESIGN.md "Seeded clustering"): N = the seeds' items, k = k_target or CalculateOptimalClusters(N), the route
+// by the number of seeds alone -- small up to the cap (a lone problem included), mid up to WMM_CAP whatever icl_set_many_options says,
+// ICL_ERR_UNSUPPORTED above -- and the sizes the kernels see: a frozen seed gets the largest size the ban still refuses.
+static void wm_classify_seeded(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
+{
+    const int64_t cap = wm_cap();
+    const int32_t nprob = A.nprob;
+    pl.img.assign(nprob + 1, 0);
+    pl.k.assign(nprob, 0);
+    pl.why.resize(nprob);
+    pl.st.assign(nprob, ICL_OK);
+    pl.route.assign(nprob, WM_NONE);
+    for (int32_t p = 0; p < nprob; ++p) pl.img[p + 1] = pl.img[p] + A.n[p];
+    pl.eff.assign((size_t)pl.img[nprob], 1);
+    pl.c_dev.assign(nprob, nullptr);
+    pl.kmax.assign(nprob, 1);
+    for (int32_t p = 0; p < nprob; ++p) {
+        const int32_t *ss = A.seed_size + pl.img[p];
+        const int64_t m = A.n[p];
+        int64_t N = 0, big = -1;
+        for (int64_t i = 0; i < m; ++i) {
+            N += std::llabs((long long)ss[i]);
+            if (ss[i] > A.max_size[p] && big < 0) big = i;
+        }
+        char b[200];
+        b[0] = 0;
+        if (N >= ((int64_t)1 << 30)) {
+            pl.st[p] = ICL_ERR_UNSUPPORTED;
+            snprintf(b, sizeof b, "%lld items in all", (long long)N);
+        } else if (big >= 0) { // the reference would split it (clustering.go:251-258)
+            pl.st[p] = ICL_ERR_UNSUPPORTED;
+            snprintf(b, sizeof b, "seed %lld holds %d items, above maxSize (%d), and is not frozen", (long long)big, ss[big], A.max_size[p]);
+        } else if (m > std::max<int64_t>(cap, WMM_CAP)) {
+            pl.st[p] = ICL_ERR_UNSUPPORTED;
+            snprintf(b, sizeof b, "%lld seeds: a seeded problem holds at most %lld", (long long)m, (long long)std::max<int64_t>(cap, WMM_CAP));
+        } else if (A.k_target && A.k_target[p] > 0) {
+            pl.k[p] = A.k_target[p];
+        } else if (icl_calc_optimal_clusters(N, A.min_size[p], A.max_size[p], &pl.k[p]) != ICL_OK) {
+            pl.st[p] = ICL_ERR_CONSTRAINT;
+            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%lld), minSize (%d), and maxSize (%d)", (long long)N,
+                     A.min_size[p], A.max_size[p]);
+        }
+        pl.why[p] = b;
+        if (pl.st[p] != ICL_OK) continue;
+        const int32_t kmax = pl.kmax[p] = (int32_t)std::min<int64_t>(std::max<int64_t>(A.max_size[p], 1), std::max<int64_t>(N, 1));
+        for (int64_t i = 0; i < m; ++i) pl.eff[(size_t)(pl.img[p] + i)] = ss[i] < 0 ? kmax : ss[i];
+        if (m - pl.k[p] <= 0) continue;
+        pl.route[p] = m <= cap ? WM_SMALL : WM_MID;
+        (pl.route[p] == WM_SMALL ? small : mid).push_back(p);
+        pl.need_e = pl.need_e || m * A.d[p] > 0;
+    }
+    if (A.want_cout && pl.img[nprob] > 0) pl.need_e = true;
+    ctx->many_stats[0] = (int64_t)small.size();
+    ctx->many_stats[1] = (int64_t)mid.size();
+    ctx->many_stats[2] = 0;
+}
+
 // the launch groups (the mid route's under the budget; a group holds at least one problem) and the workspace:
 // [uploaded E] [aligned copies] [logs, counts] [head of every group] [the small group's data] [the mid groups' shared data]
 static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t e_len, std::vector<int32_t> &small, std::vector<int32_t> &mid, wm_plan &pl)
@@ -866,15 +603,17 @@ static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t 
             if (pl.groups.empty() || pl.groups.back().kind != &kind || pl.groups.back().data_bytes + need > budget) {
                 pl.groups.emplace_back();
                 pl.groups.back().kind = &kind;
+                pl.groups.back().seeded = A.seeded;
             }
             wm_group &g = pl.groups.back();
             kind.init_blocks((int32_t)g.probs.size(), A.n[p], g.blk_prob, g.blk_arg);
             g.probs.push_back(p);
             g.data_bytes += need;
+            g.seed_rows += (size_t)A.n[p];
         }
     };
-    add(wm_kind_small, small, SIZE_MAX);
-    add(wm_kind_mid, mid, wmm_budget());
+    add(A.seeded ? wm_kind_small_seeded : wm_kind_small, small, SIZE_MAX);
+    add(A.seeded ? wm_kind_mid_seeded : wm_kind_mid, mid, wmm_budget());
     ctx->many_stats[3] = (int64_t)pl.groups.size() - (small.empty() ? 0 : 1);
     wm_layout L;
     pl.o_e = upload_e && pl.need_e ? L.take((size_t)e_len * 4) : 0;
@@ -885,36 +624,52 @@ static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t 
         if (pl.route[p] == WM_SMALL || pl.route[p] == WM_MID) {
             pl.log_at[p] = pl.log_ints;
             pl.log_ints += 2 * (int64_t)A.n[p] + 1; // 2 (n - k) ids + the count
+            if (A.seeded) pl.log_ints += A.n[p];    // ... + the slots' final ids (wm_seed::fin)
         }
+    }
+    pl.o_c.assign(A.nprob, SIZE_MAX);
+    if (A.want_cout) {
+        for (int32_t p : mid) pl.o_c[p] = L.take((size_t)A.n[p] * A.d[p] * 4);
+        pl.o_crow = L.take(sizeof(wm_crow) * (size_t)std::max<int64_t>(pl.img[A.nprob], 1));
+        if (A.cout_host) pl.o_cout = L.take((size_t)std::max<int64_t>(e_len, 1) * 4);
     }
     pl.o_logs = L.take(4 * (size_t)std::max<int64_t>(pl.log_ints, 1));
     size_t shared = 0;
     for (wm_group &g : pl.groups) {
         g.o_head = L.take(g.head_bytes());
-        if (g.kind == &wm_kind_small) g.o_data = L.take(g.data_bytes);
+        if (g.kind->own_data) g.o_data = L.take(g.data_bytes);
         else shared = std::max(shared, g.data_bytes);
     }
     const size_t o_shared = L.take(shared);
     for (wm_group &g : pl.groups)
-        if (g.kind != &wm_kind_small) g.o_data = o_shared;
+        if (!g.kind->own_data) g.o_data = o_shared;
     pl.ws_bytes = L.off;
 }
 
 // the group's head (problem table with device addresses, init blocks, order) uploaded, then one init launch and one merge launch
-static int wm_run_group(icl_ctx *ctx, const wm_args &A, const wm_plan &pl, wm_group &g, char *ws, const std::vector<const float *> &rowsE)
+static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g, char *ws, const std::vector<const float *> &rowsE)
 {
     const size_t G = g.probs.size(), o_arg = sizeof(wm_prob) * G, o_ord = o_arg + (size_t)g.kind->arg_bytes * g.blk_arg.size();
     g.head.resize(g.head_bytes());
     wm_prob *tab = reinterpret_cast<wm_prob *>(g.head.data());
     int32_t *ord = reinterpret_cast<int32_t *>(g.head.data() + o_ord);
+    wm_seed *stab = g.seeded ? reinterpret_cast<wm_seed *>(g.head.data() + g.o_seed()) : nullptr;
+    size_t o_eff = g.o_seed() + sizeof(wm_seed) * G; // (of the next problem's effective sizes, in the head)
     wm_layout R; // the problems' places in the group's data region
     int64_t lds = 0;
     for (size_t i = 0; i < G; ++i) {
         const int32_t p = g.probs[i];
         float *C = (float *)(ws + g.o_data + R.take((size_t)A.n[p] * A.d[p] * 4));
+        if (pl.o_c[p] != SIZE_MAX) C = (float *)(ws + pl.o_c[p]);
+        if (g.seeded) {
+            pl.c_dev[p] = C;
+            memcpy(g.head.data() + o_eff, pl.eff.data() + pl.img[p], 4 * (size_t)A.n[p]);
+            stab[i] = wm_seed{(const int32_t *)(ws + g.o_head + o_eff), (int32_t *)(ws + pl.o_logs) + pl.log_at[p] + 2 * (int64_t)A.n[p] + 1};
+            o_eff += 4 * (size_t)A.n[p];
+        }
         float *mat = (float *)(ws + g.o_data + R.take((size_t)g.kind->mat_bytes(A.n[p])));
         int32_t *log = (int32_t *)(ws + pl.o_logs) + pl.log_at[p];
-        tab[i] = wm_prob{rowsE[p], C, mat, A.n[p], A.d[p], A.max_size[p], (int32_t)(A.n[p] - pl.k[p]), log, log + 2 * (int64_t)A.n[p],
+        tab[i] = wm_prob{rowsE[p], C, mat, A.n[p], A.d[p], g.seeded ? pl.kmax[p] : A.max_size[p], (int32_t)(A.n[p] - pl.k[p]), log, log + 2 * (int64_t)A.n[p],
                          g.kind->lds_tri(A.n[p]) ? 1 : 0, 0};
         ord[i] = (int32_t)i; // (probs is sorted: largest first)
         lds = std::max(lds, g.kind->lds_bytes(A.n[p]));
@@ -924,7 +679,8 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, const wm_plan &pl, wm_gr
     if (!g.blk_prob.empty()) memcpy(ord + G, g.blk_prob.data(), 4 * g.blk_prob.size());
     const char *tab_d = ws + g.o_head, *arg_d = tab_d + o_arg, *ord_d = tab_d + o_ord, *blk_d = ord_d + 4 * G;
     ICL_HIP(ctx, hipMemcpyAsync(ws + g.o_head, g.head.data(), g.head.size(), hipMemcpyHostToDevice, ctx->stream));
-    void *init_args[] = {&tab_d, &blk_d, &arg_d}, *merge_args[] = {&tab_d, &ord_d};
+    const char *seed_d = tab_d + g.o_seed(); // (the seeded kernels' last argument; the others take three and two)
+    void *init_args[] = {&tab_d, &blk_d, &arg_d, &seed_d}, *merge_args[] = {&tab_d, &ord_d, &seed_d};
     if (!g.blk_prob.empty())
         ICL_HIP(ctx, hipLaunchKernel(g.kind->init_fn, dim3((unsigned)g.blk_prob.size()), dim3(g.kind->init_threads), init_args, 0, ctx->stream));
     icl_lds_optin(ctx, g.kind->merge_fn, WM_LDS_MAX);
@@ -1081,5 +837,231 @@ extern "C" int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int
         icl_device_guard g(ctx->device);
         return cluster_many_locked(ctx, nprob, nullptr, E, e_len, e_off, n, d, min_size, max_size, cluster_id, member_rank, n_clusters, n_merges, merges,
                                    status);
+    });
+}
+
+// ---- seeded clustering: resume the loop from existing clusters (DESIGN.md "Seeded clustering") ------------------------------------
+// icl_ward_assign_ids' rule at seed granularity: the final list is the surviving seeds in seed order, then the merged clusters in
+// creation order; a cluster's seeds are a's then b's (a: the pair's first id, clustering.go:31); a cluster whose ITEM count is below
+// min_size is dropped and consumes no id.  finals (may be null): (creation id, rank-0 seed) of every final cluster, dropped ones included.
+static int wm_seeded_ids(int64_t m, const int32_t *seed_size, int32_t min_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
+                         int32_t *seed_rank, int32_t *n_clusters, std::vector<int32_t> *finals, std::string &why)
+{
+    const int64_t M = m + nmerge;
+    std::vector<int32_t> left((size_t)M, -1), right((size_t)M, -1);
+    std::vector<int64_t> size((size_t)M, 0);
+    std::vector<uint8_t> alive((size_t)M, 1);
+    char b[120];
+    for (int64_t i = 0; i < m; ++i) {
+        size[i] = std::llabs((long long)seed_size[i]);
+        if (!size[i]) {
+            snprintf(b, sizeof b, "seed %lld has size 0", (long long)i);
+            why = b;
+            return ICL_ERR_ARG;
+        }
+    }
+    for (int64_t t = 0; t < nmerge; ++t) {
+        const int32_t a = pairs[2 * t], c2 = pairs[2 * t + 1];
+        const int64_t c = m + t;
+        if (a < 0 || c2 < 0 || a >= c || c2 >= c || a == c2 || !alive[a] || !alive[c2]) {
+            snprintf(b, sizeof b, "corrupt merge log at step %lld (%d,%d)", (long long)t, a, c2);
+            why = b;
+            return ICL_ERR_ARG;
+        }
+        left[c] = a;
+        right[c] = c2;
+        size[c] = size[a] + size[c2];
+        alive[a] = alive[c2] = 0;
+    }
+    for (int64_t i = 0; i < m; ++i) cluster_id[i] = seed_rank[i] = -1;
+    int32_t cid = 0;
+    std::vector<int32_t> stack;
+    if (finals) finals->clear();
+    for (int64_t c = 0; c < M; ++c) {
+        if (!alive[c]) continue;
+        if (finals) {
+            int64_t f = c;
+            while (f >= m) f = left[f];
+            finals->push_back((int32_t)c);
+            finals->push_back((int32_t)f);
+        }
+        if (size[c] < min_size) continue; // clustering.go:268-271
+        int32_t rank = 0;
+        stack.assign(1, (int32_t)c);
+        while (!stack.empty()) {
+            const int32_t x = stack.back();
+            stack.pop_back();
+            if (x < m) {
+                cluster_id[x] = cid;
+                seed_rank[x] = rank++;
+            } else {
+                stack.push_back(right[x]); // visited after left: a's seeds first
+                stack.push_back(left[x]);
+            }
+        }
+        ++cid;
+    }
+    *n_clusters = cid;
+    return ICL_OK;
+}
+
+extern "C" int icl_seeded_assign_ids(int32_t m, const int32_t *seed_size, int32_t min_size, const int32_t *merges, int32_t n_merges,
+                                     int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters)
+{
+    return no_throw(nullptr, "icl_seeded_assign_ids", [&]() -> int {
+        if (m < 0 || n_merges < 0 || !n_clusters || (m && (!seed_size || !cluster_id || !seed_rank)) || (n_merges && !merges))
+            return icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: m %d, n_merges %d or a null array", m, n_merges);
+        for (int32_t i = 0; i < m; ++i)
+            if (!seed_size[i]) return icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: seed %d has size 0", i);
+        std::vector<int32_t> cid((size_t)m), rank((size_t)m); // (nothing is written when the log is corrupt)
+        int32_t nc = 0;
+        std::string why;
+        const int rc = wm_seeded_ids(m, seed_size, min_size, merges, n_merges, cid.data(), rank.data(), &nc, nullptr, why);
+        if (rc != ICL_OK) return icl_fail(nullptr, rc, "icl_seeded_assign_ids: %s", why.c_str());
+        if (m) memcpy(cluster_id, cid.data(), 4 * (size_t)m);
+        if (m) memcpy(seed_rank, rank.data(), 4 * (size_t)m);
+        *n_clusters = nc;
+        return ICL_OK;
+    });
+}
+
+// ids from the merge logs, merge logs, statuses and the rows of C_out (crow: one entry per seed of the call, or empty); the lowest
+// failed problem's error
+static int wm_collect_seeded(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, const std::vector<const float *> &rowsE,
+                             int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
+                             std::vector<wm_crow> &crow)
+{
+    std::vector<int32_t> finals, slot;
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        const int64_t m = A.n[p], d = A.d[p];
+        int32_t *cid = cluster_id + pl.img[p], *rank = seed_rank + pl.img[p];
+        const int32_t *lg = pl.route[p] != WM_NONE ? slab.data() + pl.log_at[p] : nullptr;
+        int64_t nm = lg ? lg[2 * m] : 0;
+        if (pl.st[p] == ICL_OK) {
+            const int rc = wm_seeded_ids(m, A.seed_size + pl.img[p], A.min_size[p], lg, nm, cid, rank, &n_clusters[p], &finals, pl.why[p]);
+            if (rc != ICL_OK) pl.st[p] = ICL_ERR_HIP; // (the kernel's own log: the sizes were checked with the arguments)
+        }
+        if (pl.st[p] != ICL_OK) {
+            std::fill(cid, cid + m, -1);
+            std::fill(rank, rank + m, -1);
+            n_clusters[p] = 0;
+            nm = 0;
+            finals.clear();
+        }
+        n_merges[p] = (int32_t)nm;
+        if (merges && nm) memcpy(merges + 2 * pl.img[p], lg, 8 * (size_t)nm);
+        status[p] = pl.st[p];
+        if (crow.empty()) continue;
+        for (int64_t i = 0; i < m; ++i) crow[(size_t)(pl.img[p] + i)] = wm_crow{nullptr, A.e_off[p] + i * d, (int32_t)d, 0};
+        if (lg) { // the slot a merged cluster lives in
+            slot.assign((size_t)(m + nm), -1);
+            const int32_t *fin = lg + 2 * m + 1;
+            for (int64_t s = 0; s < m; ++s)
+                if (fin[s] >= 0 && fin[s] < m + nm) slot[fin[s]] = (int32_t)s;
+        }
+        for (size_t f = 0; f < finals.size(); f += 2) {
+            const int64_t c = finals[f], first = finals[f + 1];
+            const float *src = nullptr;
+            if (c < m) src = rowsE[p] + c * d;
+            else if (slot[c] >= 0) src = pl.c_dev[p] + (int64_t)slot[c] * d;
+            else {
+                pl.st[p] = status[p] = ICL_ERR_HIP;
+                pl.why[p] = "the final state names no slot for a merged cluster";
+            }
+            crow[(size_t)(pl.img[p] + first)].src = src;
+        }
+    }
+    for (int32_t p = 0; p < A.nprob; ++p)
+        if (pl.st[p] != ICL_OK) return icl_fail(ctx, pl.st[p], "icl_cluster_many_seeded: problem %d: %s", p, pl.why[p].c_str());
+    return ICL_OK;
+}
+
+// Both seeded entry points, after the argument check, with ctx->mu held (d_E / h_E as cluster_many_locked takes them; C_out on the
+// device for the _dev call, on the host else, or null)
+static int cluster_many_seeded_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
+                                      const int32_t *m, const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                                      const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
+                                      int32_t *merges, int32_t *status, float *C_out)
+{
+    wm_args A = {nprob, e_off, m, d, min_size, max_size};
+    A.seeded = true;
+    A.seed_size = seed_size;
+    A.k_target = k_target;
+    A.want_cout = C_out != nullptr;
+    A.cout_host = C_out != nullptr && h_E != nullptr;
+    wm_plan pl;
+    {
+        std::vector<int32_t> small, mid;
+        wm_classify_seeded(ctx, A, pl, small, mid);
+        wm_make_plan(ctx, A, h_E != nullptr, e_len, small, mid, pl);
+    }
+    std::vector<const float *> rowsE(nprob, nullptr);
+    std::vector<int32_t> slab;
+    ICL_TRY(wm_enqueue(ctx, A, pl, d_E, h_E, e_len, rowsE, slab));
+    char *ws = (char *)ctx->many->buf;
+    if (A.want_cout) { // a problem that took no route: its rows where the call's E lies on the device
+        const float *base = h_E && pl.need_e ? (const float *)(ws + pl.o_e) : d_E;
+        for (int32_t p = 0; p < nprob; ++p)
+            if (!rowsE[p]) rowsE[p] = base + e_off[p];
+    }
+    if (!pl.groups.empty()) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t rows = pl.img[nprob];
+    std::vector<wm_crow> crow(A.want_cout ? (size_t)rows : 0);
+    const int rc = wm_collect_seeded(ctx, A, pl, slab, rowsE, cluster_id, seed_rank, n_clusters, n_merges, merges, status, crow);
+    if (!crow.empty()) {
+        float *out = A.cout_host ? (float *)(ws + pl.o_cout) : C_out;
+        ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_crow, crow.data(), sizeof(wm_crow) * crow.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (A.cout_host) ICL_HIP(ctx, hipMemsetAsync(out, 0, (size_t)e_len * 4, ctx->stream)); // (the padding between problems)
+        const wm_crow *tab = (const wm_crow *)(ws + pl.o_crow);
+        hipLaunchKernelGGL(ward_many_cout_kernel, dim3((unsigned)crow.size()), dim3(256), 0, ctx->stream, tab, out);
+        ICL_HIP(ctx, hipGetLastError());
+        if (A.cout_host) ICL_HIP(ctx, hipMemcpyAsync(C_out, out, (size_t)e_len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
+}
+
+// the ARG check of the seeded entry points, beyond wm_check_args': nothing is written when it fails
+static int wm_check_seeds(icl_ctx *ctx, const char *what, int32_t nprob, const int32_t *m, const int32_t *seed_size)
+{
+    int64_t rows = 0;
+    for (int32_t p = 0; p < nprob; ++p) rows += m[p];
+    if (rows && !seed_size) return icl_fail(ctx, ICL_ERR_ARG, "%s: null seed_size", what);
+    for (int64_t i = 0; i < rows; ++i)
+        if (!seed_size[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: seed_size[%lld] is 0", what, (long long)i);
+    return ICL_OK;
+}
+
+extern "C" int icl_cluster_many_seeded_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *m,
+                                           const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                                           const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
+                                           int32_t *merges, int32_t *status, float *d_C_out)
+{
+    return no_throw(ctx, "icl_cluster_many_seeded_dev", [&]() -> int {
+        ICL_TRY(wm_check_args(ctx, "icl_cluster_many_seeded_dev", nprob, d_E, e_len, e_off, m, d, min_size, max_size, cluster_id, seed_rank, n_clusters,
+                              n_merges, status));
+        ICL_TRY(wm_check_seeds(ctx, "icl_cluster_many_seeded_dev", nprob, m, seed_size));
+        if (nprob == 0) return ICL_OK;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        return cluster_many_seeded_locked(ctx, nprob, d_E, nullptr, e_len, e_off, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank,
+                                          n_clusters, n_merges, merges, status, d_C_out);
+    });
+}
+
+extern "C" int icl_cluster_many_seeded(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *m,
+                                       const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                                       const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
+                                       int32_t *merges, int32_t *status, float *C_out)
+{
+    return no_throw(ctx, "icl_cluster_many_seeded", [&]() -> int {
+        ICL_TRY(wm_check_args(ctx, "icl_cluster_many_seeded", nprob, E, e_len, e_off, m, d, min_size, max_size, cluster_id, seed_rank, n_clusters,
+                              n_merges, status));
+        ICL_TRY(wm_check_seeds(ctx, "icl_cluster_many_seeded", nprob, m, seed_size));
+        if (nprob == 0) return ICL_OK;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        return cluster_many_seeded_locked(ctx, nprob, nullptr, E, e_len, e_off, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank,
+                                          n_clusters, n_merges, merges, status, C_out);
     });
 }

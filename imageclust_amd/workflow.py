@@ -7,8 +7,10 @@ on the GPU and clustered there, one workgroup per request; only cluster ids come
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
+
 from . import _lib
-from .clustering import clusters_as_map
+from .clustering import Clustering, clusters_as_map
 from .embeddings import AppContext
 
 Request = Tuple[Sequence[str], Sequence[str], Sequence[Sequence[str]], Dict[str, int], int, int]
@@ -70,3 +72,30 @@ def RunUploaded(appCtx: AppContext, requests: Sequence[UploadedRequest], prec: i
         ids.append(["img_%d" % i for i in range(len(uploaded))])
     res = appCtx.Net.ctx.cluster_requests_mem(packed, appCtx.Head, prec, threads)
     return _results(ids, res, statuses)
+
+
+def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int = _lib.PREC_FP32,
+            threads: int = 0) -> Tuple[Optional[Dict[int, List[str]]], bool]:
+    """More images for a request that has been answered: newRequestImages = (paths, ids, labels_per_image, labelSet) with the
+    labelSet of the request `state` came from (the combined rows must be as wide as the state's).  Only the new images are embedded
+    and combined (createEmbeddings, workflow.go:149-185); they join the state as singletons and the loop goes on from the clusters
+    held (Clustering.add, .recluster) -> (state.as_map(), True), or (None, False) when the constraints cannot be met or a file cannot
+    be read (workflow.go:162-181 fails the request; the state is as it was then)."""
+    if appCtx.Net is None or appCtx.Net.Empty():
+        raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunMore: no model loaded")
+    paths, ids, labels_per_image, labelSet = newRequestImages
+    if len(ids) != len(paths) or len(labels_per_image) != len(paths):
+        raise ValueError("%d paths, %d ids, %d label lists" % (len(paths), len(ids), len(labels_per_image)))
+    ctx = appCtx.Net.ctx
+    E, status = ctx.embed_files([str(p) for p in paths], appCtx.Head, prec, threads)
+    if (np.asarray(status) != _lib.ICL_OK).any():
+        return None, False
+    lab = np.zeros((len(paths), len(labelSet)), np.float32)
+    for i, labels in enumerate(labels_per_image):
+        for col in LabelIndices(labels, labelSet):
+            if 0 <= col < len(labelSet):
+                lab[i, col] = 1.0  # GenerateLabelVector (embeddings.go:166-174)
+    state.add(np.concatenate([E, lab], axis=1), list(ids))  # CombineEmbeddings (:177-183)
+    if state.ctx is None and state.engine is None:
+        state.ctx = ctx
+    return (state.as_map(), True) if state.recluster() else (None, False)

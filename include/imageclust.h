@@ -366,6 +366,39 @@ int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t 
 int icl_set_many_options(icl_ctx *ctx, int mid_mode);
 /* problems of the last icl_cluster_many[_dev] call by route, and the number of mid-route groups it was run in (any pointer may be NULL) */
 int icl_last_many_stats(icl_ctx *ctx, int64_t *small, int64_t *mid, int64_t *large, int64_t *mid_groups);
+/* ---- seeded clustering: the loop of clustering.go:216-246 started from existing clusters (DESIGN.md "Seeded clustering") ----
+ * The icl_cluster_many layout with SEEDS in place of images: problem p holds m[p] seed clusters, seed i given by its centroid (row i of
+ * the problem's d[p]-float rows in E) and seed_size[seed_off(p) + i], seed_off(p) = m[0] + ... + m[p-1]: s > 0, a cluster of s items;
+ * s < 0, a FROZEN cluster of -s items (every pair with it is banned from the start: it is never merged, but counts as a cluster and
+ * its items count in N); s == 0 is ICL_ERR_ARG.  N = the items of all seeds.  k = k_target[p] when k_target is not NULL and the entry
+ * is above 0, else CalculateOptimalClusters(N, min_size[p], max_size[p]) (ICL_ERR_CONSTRAINT as the problem's status on its errors);
+ * max(0, m[p] - k) merges are asked for.  The loop is the reference's with the clusters' real sizes: the first strict minimum in
+ * row-major order, the MaxFloat32 ban where the size sum exceeds max_size[p], fp32 values bit for bit.  Creation ids: seed i has id i,
+ * the t-th merge id m[p] + t; merges holds (larger id, smaller id) per merge at offset 2*seed_off(p).  cluster_id / seed_rank
+ * (seed_off layout): the final list is the surviving seeds in seed order, then the merged clusters in creation order; a cluster with
+ * fewer than min_size[p] ITEMS is dropped (its seeds get -1 in both arrays), kept clusters get dense ids; seed_rank is the seed's place
+ * in its cluster's seed sequence (Merge(a, b): a's seeds, then b's, a = the pair's first id).  C_out (may be NULL; the layout of E;
+ * host memory, device memory for _dev): the row of each final cluster's rank-0 seed holds that cluster's centroid exactly as the loop
+ * holds it, kept and dropped clusters alike (a never-merged seed's row is its input row), every other row is zero; the rows of a failed
+ * problem are zero; floats of E between the problems' rows are zero in the host call's C_out and untouched in the _dev call's.
+ * status[p]: ICL_OK, ICL_ERR_CONSTRAINT, or ICL_ERR_UNSUPPORTED for a seed above max_size[p] that is not frozen (the reference
+ * would split it), more than 2048 seeds, or 2^30 items and more.  Problems of m <= 1 succeed with no merge.  Problems of up to 256 seeds
+ * take the small route of ward_many.hip, a lone one included, larger ones the mid-size route whatever icl_set_many_options says.
+ * With every seed_size 1 and no k_target the results are icl_cluster_many's, bit for bit.  The return code, "nothing is written on
+ * ICL_ERR_ARG" and the icl_last_* guarantees are icl_cluster_many's; icl_last_many_stats reports the call. */
+int icl_cluster_many_seeded(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *m, const int32_t *d,
+                            const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size, const int32_t *k_target,
+                            int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
+                            float *C_out);
+int icl_cluster_many_seeded_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *m,
+                                const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                                const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
+                                int32_t *merges, int32_t *status, float *d_C_out);
+/* The id rule above for one problem, on the host (no GPU, no context): m seeds, their sizes (the sign is ignored), min_size and a merge
+ * log of n_merges pairs -> cluster_id[m], seed_rank[m], n_clusters.  ICL_ERR_ARG for a size of 0 or a log that names a cluster that does
+ * not exist (any more); nothing is written then. */
+int icl_seeded_assign_ids(int32_t m, const int32_t *seed_size, int32_t min_size, const int32_t *merges, int32_t n_merges, int32_t *cluster_id,
+                          int32_t *seed_rank, int32_t *n_clusters);
 /* ---- a queue of requests, files to cluster ids: replaces workflow.Run (workflow.go:84-94) for nreq requests in ONE call ----
  * Request r is n[r] image files with labels.  Every image gets its embedding row (GetImageEmbedding; head, prec as icl_embed_files), a one-hot
  * vector over the request's label set is appended (GenerateLabelVector + CombineEmbeddings, embeddings.go:166-183: d[r] = head + n_labels[r]
