@@ -344,8 +344,16 @@ func PerformClusteringWithConstraintsBatch(jobs []ClusteringJob) []ClusteringRes
 // size freezes the cluster -- and kTarget > 0 replaces CalculateOptimalClusters.  The result is at seed granularity
 // (iclengine.SeededResult); false on impossible constraints, as the reference's (nil, false).
 func ResumeClustering(centroids [][]float32, sizes []int32, minSize, maxSize, kTarget int) (iclengine.SeededResult, bool) {
-	res, err := iclengine.ClusterManySeeded([]iclengine.SeededProblem{{Centroids: centroids, Sizes: sizes, MinSize: minSize,
-		MaxSize: maxSize, KTarget: kTarget}})
+	pr := iclengine.SeededProblem{Centroids: centroids, Sizes: sizes, MinSize: minSize, MaxSize: maxSize, KTarget: kTarget}
+	var res []iclengine.SeededResult
+	var err error
+	if len(sizes) > iclengine.ManySeededMax { // above the one-workgroup routes' cap: the large-N engine's seeded call
+		var one iclengine.SeededResult
+		one, err = iclengine.ClusterSeeded(pr)
+		res = []iclengine.SeededResult{one}
+	} else {
+		res, err = iclengine.ClusterManySeeded([]iclengine.SeededProblem{pr})
+	}
 	if err != nil {
 		log.Printf("Clustering engine error: %v", err)
 		return iclengine.SeededResult{}, false

@@ -211,6 +211,56 @@ func ClusterManySeeded(probs []SeededProblem) ([]SeededResult, error) {
 	return out, nil
 }
 
+// ManySeededMax is icl_cluster_many_seeded's cap on the seeds of one problem; ClusterSeeded has none.
+const ManySeededMax = 2048
+
+// ClusterSeeded runs ONE seeded problem on the large-N engine (icl_cluster_seeded: the exact pipeline of ward.hip, any number of seeds).
+// The result is ClusterManySeeded's for the same problem, bit for bit; the merge log comes from icl_last_merges.  The error is the call's
+// own; ICL_ERR_CONSTRAINT and ICL_ERR_UNSUPPORTED are the result's Status.
+func ClusterSeeded(pr SeededProblem) (SeededResult, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return SeededResult{}, e
+	}
+	if len(pr.Sizes) != len(pr.Centroids) {
+		return SeededResult{}, fmt.Errorf("%d sizes for %d centroids", len(pr.Sizes), len(pr.Centroids))
+	}
+	m, d := len(pr.Centroids), 0
+	if m > 0 {
+		d = len(pr.Centroids[0])
+	}
+	flat := make([]float32, m*d+1) // [][]float32 cannot cross cgo: one contiguous buffer
+	cout := make([]float32, m*d+1)
+	for i, row := range pr.Centroids {
+		copy(flat[i*d:], row)
+	}
+	ss := append(append([]int32(nil), pr.Sizes...), 0)
+	cid := make([]int32, m+1)
+	rank := make([]int32, m+1)
+	var nc C.int32_t
+	i32 := func(p *int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(p)) }
+	rc := C.icl_cluster_seeded((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
+		C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cid[0]), i32(&rank[0]), &nc,
+		(*C.float)(unsafe.Pointer(&cout[0])))
+	if rc != C.ICL_OK && rc != C.ICL_ERR_CONSTRAINT && rc != C.ICL_ERR_UNSUPPORTED {
+		return SeededResult{}, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	r := SeededResult{Status: int(rc), NClusters: int(nc), ClusterID: cid[:m], SeedRank: rank[:m]}
+	if rc == C.ICL_OK {
+		nm := int(C.icl_last_merges((*C.icl_ctx)(raw), nil, 0))
+		mg := make([]int32, 2*nm+1)
+		C.icl_last_merges((*C.icl_ctx)(raw), i32(&mg[0]), C.int64_t(nm))
+		for t := 0; t < nm; t++ {
+			r.Merges = append(r.Merges, [2]int32{mg[2*t], mg[2*t+1]})
+		}
+	}
+	r.COut = make([][]float32, m)
+	for i := range r.COut {
+		r.COut[i] = append([]float32(nil), cout[i*d:(i+1)*d]...)
+	}
+	return r, nil
+}
+
 // Where a qualifying PNG of the batched file calls is inflated and unfiltered: icl_set_png_options' modes.
 const (
 	PNGHost = int(C.ICL_PNG_HOST)

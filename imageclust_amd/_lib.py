@@ -136,6 +136,8 @@ SYMBOLS = [
     ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_cluster_many_seeded", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
     ("icl_cluster_many_seeded_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
+    ("icl_cluster_seeded", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
+    ("icl_cluster_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
@@ -969,6 +971,51 @@ class Context:
             out = [r + (co[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)
                    for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]
         return out
+
+    def cluster_seeded(self, C_, seed_size, min_size, max_size, k_target=0, want_centroids=True, dev=False):
+        """icl_cluster_seeded: ONE seeded problem (cluster_many_seeded's semantics) on the large-N engine, any number of seeds -> (cluster_id,
+        seed_rank, n_clusters, status, merges, C_out); C_out is None without want_centroids.  status is ICL_OK, ICL_ERR_CONSTRAINT or
+        ICL_ERR_UNSUPPORTED (rows of -1, C_out zero); every other error raises.  dev=True runs icl_cluster_seeded_dev on a device copy."""
+        Cs = np.ascontiguousarray(C_, np.float32)
+        m, d = Cs.shape
+        ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
+        if len(ss) != m:
+            raise ValueError("%d seed sizes for %d centroid rows" % (len(ss), m))
+        cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
+        nc = _i32()
+        co = np.zeros((m, d), np.float32) if want_centroids else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = (m, d, ptr(ss), int(min_size), int(max_size), int(k_target), cid.ctypes.data, rank.ctypes.data, C.byref(nc))
+        if dev:
+            dE = self.malloc(max(Cs.nbytes, 16))
+            dC = self.malloc(max(Cs.nbytes, 16)) if want_centroids else None
+            try:
+                self.h2d(dE, Cs)
+                rc = self.L.icl_cluster_seeded_dev(self.h, _vp(dE), *args, _vp(dC) if want_centroids else None)
+                if want_centroids and Cs.size and rc in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
+                    self.d2h(co, dC)
+            finally:
+                self.free(dE)
+                if dC is not None:
+                    self.free(dC)
+        else:
+            rc = self.L.icl_cluster_seeded(self.h, Cs.ctypes.data if m else None, *args, ptr(co))
+        if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
+            check(self.h, rc)
+        merges = self.last_merges() if rc == ICL_OK else np.zeros((0, 2), np.int32)
+        return cid[:m], rank[:m], nc.value, rc, merges, co
+
+    def cluster_seeded_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, d_C_out=None):
+        """icl_cluster_seeded_dev on m x d device floats (d_C_out: m x d device floats, or None) -> (cluster_id, seed_rank, n_clusters,
+        status); the log is last_merges()."""
+        ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
+        cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
+        nc = _i32()
+        rc = self.L.icl_cluster_seeded_dev(self.h, _vp(d_C), m, d, ss.ctypes.data if m else None, int(min_size), int(max_size), int(k_target),
+                                           cid.ctypes.data, rank.ctypes.data, C.byref(nc), _vp(d_C_out) if d_C_out is not None else None)
+        if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
+            check(self.h, rc)
+        return cid[:m], rank[:m], nc.value, rc
 
     def cluster_dev(self, d_E, n, d, min_size, max_size, update=UPDATE_EXACT):
         cid = np.full(max(n, 1), -1, np.int32)

@@ -158,8 +158,20 @@ def PerformClusteringWithConstraintsMany(jobs, ctx: Optional[_lib.Context] = Non
     return out
 
 
+MANY_SEEDED_MAX = 2048  # icl_cluster_many_seeded's cap on a problem's seeds; above it the seeded call of the large-N engine runs
+
+
+def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target):
+    """One seeded problem -> (cluster_id, seed_rank, n_clusters, status, merges, C_out): icl_cluster_many_seeded up to its cap,
+    icl_cluster_seeded (ward.hip's exact pipeline, no cap) above."""
+    if len(sizes) > MANY_SEEDED_MAX:
+        return ctx.cluster_seeded(C, sizes, minSize, maxSize, k_target, want_centroids=True)
+    return ctx.cluster_many_seeded([(C, sizes, minSize, maxSize, k_target)], want_merges=True, want_centroids=True)[0]
+
+
 def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_target: int = 0, ctx: Optional[_lib.Context] = None):
-    """The loop of clustering.go:216-246 started from existing clusters (icl_cluster_many_seeded, one problem): centroids[i] and
+    """The loop of clustering.go:216-246 started from existing clusters (icl_cluster_many_seeded, one problem; icl_cluster_seeded above
+    2 048 seeds): centroids[i] and
     sizes[i] describe seed cluster i, a negative size a frozen one that is never merged; k_target > 0 is the number of clusters to stop
     at, else CalculateOptimalClusters of the item total decides -> ((cluster_id, seed_rank, n_clusters, merges, C_out), True) at seed
     granularity -- C_out[i] is the centroid of the final cluster whose first seed is i, zero for every other seed -- or (None, False)
@@ -168,7 +180,7 @@ def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_targ
     C = np.asarray(centroids, np.float32)
     if C.ndim != 2:
         C = C.reshape(len(sizes), -1)
-    cid, rank, nc, st, mg, co = ctx.cluster_many_seeded([(C, sizes, minSize, maxSize, k_target)], want_merges=True, want_centroids=True)[0]
+    cid, rank, nc, st, mg, co = _seeded_call(ctx, C, sizes, minSize, maxSize, k_target)
     if st == _lib.ICL_ERR_CONSTRAINT:
         return None, False
     if st != _lib.ICL_OK:
@@ -262,13 +274,12 @@ class Clustering:
             cid, rank, nc, st, mg, co = self.engine(C, ss, self.minSize, self.maxSize, k_target)
         else:
             ctx = self.ctx or default_context()
-            cid, rank, nc, st, mg, co = ctx.cluster_many_seeded([(C, ss, self.minSize, self.maxSize, k_target)], want_merges=True,
-                                                                want_centroids=True)[0]
+            cid, rank, nc, st, mg, co = _seeded_call(ctx, C, ss, self.minSize, self.maxSize, k_target)
         self.ok = st == _lib.ICL_OK
         if st == _lib.ICL_ERR_CONSTRAINT:
             return False
         if st != _lib.ICL_OK:
-            raise _lib.ICLError(st, "icl_cluster_many_seeded: the problem failed with code %d" % st)
+            raise _lib.ICLError(st, "seeded clustering: the problem failed with code %d" % st)
         # the final list from the merge log: surviving seeds in seed order, then merged clusters in creation order, a's seeds before b's
         m = len(self.clusters)
         seq = {i: [i] for i in range(m)}

@@ -232,7 +232,7 @@ struct icl_ward_ws {
     bool wx_attr = false;
     // what the tables and the matrix above hold, for the test hook icl_ward_dump_pairs_dev: the shape of the clustering call that ran last on this
     // workspace.  state 0: none (fresh workspace, or something re-initialised the tables since: ward_launch_init), 1: a finished call the hook can
-    // read, 2: a finished call it cannot (FAST mode, a replica of a sharded group)
+    // read, 2: a finished call it cannot (FAST mode, a replica of a sharded group, a seeded call: its rows are no singletons)
     struct {
         int state = 0;
         int64_t n = 0;
@@ -1544,6 +1544,11 @@ __global__ void ward_init_kernel(int64_t n, int64_t S, int64_t M, int64_t ld, in
 #endif
     }
 }
+
+// the seeded call's two kernels (icl_cluster_seeded): defined at the end of this file, behind every other kernel
+__global__ void ward_seed_sizes_kernel(int64_t n, const int32_t *__restrict__ eff, int32_t *__restrict__ asz, int32_t *__restrict__ msz, uint32_t *__restrict__ mpk, int szb);
+__global__ void ward_seed_cout_kernel(const int32_t *__restrict__ src, const float *__restrict__ C, const float *__restrict__ Crow, const int32_t *__restrict__ id_slot,
+                                      int64_t n, int d, int64_t S, float *__restrict__ out);
 
 // Centroid store used by the update kernel: CT4[g][slot][4] = centroid(slot)[4g .. 4g+3]  (k-groups of 4 are
 // contiguous per slot, slots contiguous per group): one dwordx4 per lane streams 4 consecutive k of the lane's slot
@@ -5107,9 +5112,18 @@ struct ward_call {
     ev_guard e0, e1, e2, ev[2]; // call start, distance stage enqueued, merge loop enqueued; the batched loop's two state snapshots ...
     pin_guard pin;              // ... and their pinned memory
     dev_guard ec, pq;           // distance bounds: the centred copy of E, the integer GEMM's scratch
+    dev_guard eff;              // a seeded call's effective sizes (ward_seed::d_eff)
 };
 
 constexpr int GRAPH_STEPS = 64;
+// A SEEDED call (icl_cluster_seeded, DESIGN.md "Seeded clustering"): the n rows are seed clusters with sizes of their own.  The kernels see
+// EFFECTIVE sizes -- the seed's items, or max_size for a frozen seed, the largest size the ban still refuses with every partner --, the host
+// keeps the real ones for the final list.  Such a call runs the exact fill and the exact rows only: the bounds are proven for singletons.
+struct ward_seed {
+    const int32_t *h_size; // [n] as the caller gave them (negative: frozen)
+    const int32_t *d_eff;  // [n] on the device: effective sizes
+    int64_t T;             // merges asked for: max(0, n - k), k from k_target or CalculateOptimalClusters(items)
+};
 enum { WARD_FILL_EXACT, WARD_FILL_BOUND_F32, WARD_FILL_BOUND_I8, WARD_FILL_FAST }; // how a call fills its own rows of the initial matrix
 struct ward_plan {
     int64_t n, T, own_lo, own_hi; // T: merges needed for len(clusters) == k (clustering.go:220); [own_lo, own_hi): rows of the initial matrix this call computes
@@ -5126,6 +5140,7 @@ struct ward_plan {
     int sh_n, sh_rank, nsp;
     int32_t *fdrec;               // the express step's data phase runs in ward_finish_data_kernel from a record the finish kernel leaves behind cnewI (null: it does not)
     bool prof_update, use_graph;
+    const ward_seed *seed;        // null: the rows are singletons
     // launch shapes.  One merge per step: 64 slots per workgroup + preselect + compaction workgroups; LDS = new centroid image + p ring
     // batched: main workgroups are persistent, at most one per CU (they draw blocks from a counter), fewer when the input has fewer blocks; lb: WL_U creation ids per lane
     unsigned upd_blocks, lw_blocks, wx_blocks, lw_blocks_b, lb_blocks, fd_blocks, il_blocks, pull_blocks;
@@ -5145,13 +5160,15 @@ static int ward_check_args(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t ma
 }
 
 // (arguments that passed ward_check_args, n > 0, the workspace of ward_ensure(ctx, n, d) in place)
-static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi, ward_plan *out)
+static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi, ward_plan *out,
+                          const ward_seed *seed = nullptr)
 {
     const icl_ward_ws *w = ctx->ward;
     ward_plan p{};
     int64_t k = 0;
     (void)icl_calc_optimal_clusters(n, min_size, max_size, &k);
-    p.n = n, p.T = n - k, p.d = d, p.max_size = max_size;
+    p.n = n, p.T = seed ? seed->T : n - k, p.d = d, p.max_size = max_size;
+    p.seed = seed;
     p.lw = update == ICL_UPDATE_LW;
     p.batched = ward_batch_env();
     if (own_hi < 0) own_hi = n;
@@ -5163,7 +5180,8 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
     p.mpk = (!p.lw && p.pk_bits < 32 && (uint64_t)(2 * n + 4) <= (1ull << (32 - p.pk_bits))) ? w->mpk : nullptr;
     // Exact mode, the rows this call computes itself: by default PROVEN LOWER BOUNDS from the matrix cores, made exact on demand by the row scans (distance_mfma.hip
     // "Distance BOUNDS", scan_row_refine above); ctx->ward_dist == 1 (icl_set_ward_options) or shapes the bound does not cover: every value by ward_dist_exact_kernel.
-    p.use_bound = !p.lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
+    // (a seeded call: exact values whatever the options, n and the workspace's layout say -- the bounds' proofs take num/den = 1/2 and the nrm table)
+    p.use_bound = !seed && !p.lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
     p.lbm = p.use_bound && p.mpk && ward_lb_rows(ctx, n, d);
     p.wide = p.lbm && w->wide_alloc;
     p.rows = !p.batched ? ICL_ROWS_SINGLE : p.lw ? ICL_ROWS_LW_FAST : p.lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH;
@@ -5208,6 +5226,8 @@ static void ward_launch_init(icl_ward_ws *w, int64_t n, int64_t T, uint32_t *mpk
 static int ward_init_ws(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const float *d_E)
 {
     ward_launch_init(w, p.n, p.T, p.mpk, p.pk_bits, ctx->stream);
+    if (p.seed)
+        hipLaunchKernelGGL(ward_seed_sizes_kernel, dim3((unsigned)icl_ceil_div(p.n, 256)), dim3(256), 0, ctx->stream, p.n, p.seed->d_eff, w->asz, w->msz, p.mpk, p.pk_bits);
     if (p.d > 0) {
         hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)icl_ceil_div(w->S, 32), (unsigned)icl_ceil_div((p.d + 3) / 4, 32)), dim3(256), 0, ctx->stream, d_E, p.n, p.d, w->S, w->CT);
         ICL_HIP(ctx, hipMemcpyAsync(w->Crow, d_E, (size_t)p.n * p.d * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -5284,7 +5304,7 @@ static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const flo
         } else
             ICL_TRY(ward_bounds_f32(ctx, b, n, w->Dtri, w->rowoff, own_lo, own_hi));
     } else
-        ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, w->Dtri, w->rowoff, 0, 0, own_lo / DT_TILE, icl_ceil_div(own_hi, DT_TILE)));
+        ICL_TRY(launch_dist_exact_rows(ctx, d_E, p.seed ? p.seed->d_eff : nullptr, n, d, w->Dtri, w->rowoff, 0, 0, own_lo / DT_TILE, icl_ceil_div(own_hi, DT_TILE)));
     // (rows computed on other GPUs were laid out into the matrix by icl_ward_unpack_spans_dev before this call: flagged bounds under the same rule
     // as the rows above -- icl_ward_distance_rows_dev -- so the scans below treat them like this GPU's own)
     if (!p.use_bound && !p.lw && (own_lo > 0 || own_hi < n)) { // foreign rows taken as VALUES: a flagged entry would be read as a negative distance
@@ -5614,7 +5634,8 @@ static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const 
     ctx->last.merge_ms = ms12;
     icl_prof_collect(ctx);
     c.shard.ok = true; // the merge loop is over: nobody waits for this replica any more
-    int rc = icl_ward_assign_ids(ctx, p.n, min_size, p.max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
+    // (a seeded call makes its final list from ctx->last.merges and the seeds' real sizes: cluster_seeded_locked)
+    int rc = p.seed ? ICL_OK : icl_ward_assign_ids(ctx, p.n, min_size, p.max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
     ctx->last.merges.swap(pairs);
     return rc;
 }
@@ -5650,6 +5671,138 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
         w->dump.lbm = p.lbm, w->dump.wide = rf.wide != 0;
     }
     return rc;
+}
+
+// ---- seeded clustering on this engine (icl_cluster_seeded[_dev]; DESIGN.md "Seeded clustering", the large-N route) -----------------------------
+// cluster_locked's twin for ONE problem of m seed clusters with icl_cluster_many_seeded's semantics and no cap on m: the same stages with a
+// ward_seed in the plan.  d_C: the seed centroids on the device; seed_size on the host (no entry 0: checked by the entry points); d_C_out:
+// device, or null.  A problem the call refuses (ICL_ERR_UNSUPPORTED / ICL_ERR_CONSTRAINT) gets rows of -1 and a C_out of zeros, as the many-call's.
+static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                 int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
+{
+    ctx->last.merges.clear();
+    ctx->last.merge_vals.clear();
+    *n_clusters = 0;
+    auto no_loop = [&] { // what the icl_last_* reports say of a call that ran no merge loop
+        ctx->last.bound_viol = 0;
+        ctx->last.mode[0] = ward_batch_env() ? ICL_ROWS_EXACT_BATCH : ICL_ROWS_SINGLE;
+        ctx->last.mode[1] = 0;
+        ctx->last.stats[0] = ctx->last.stats[1] = ctx->last.stats[2] = ctx->last.stats[3] = 0;
+        ctx->last.dist_ms = ctx->last.merge_ms = 0;
+    };
+    const size_t out_bytes = (size_t)m * (size_t)d * 4;
+    auto refuse = [&](int code) {
+        no_loop();
+        std::fill(cluster_id, cluster_id + m, -1);
+        std::fill(seed_rank, seed_rank + m, -1);
+        if (d_C_out && out_bytes && (hipMemsetAsync(d_C_out, 0, out_bytes, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
+            return (int)ICL_ERR_HIP;
+        return code;
+    };
+    int64_t N = 0, big = -1, k = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        N += std::llabs((long long)seed_size[i]);
+        if (seed_size[i] > max_size && big < 0) big = i;
+    }
+    if (ctx->shard) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: not on a replica of a group");
+    if (N >= (1LL << 30)) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: %lld items in all", (long long)N);
+    if (big >= 0) // the reference would split it (clustering.go:251-258)
+        return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: seed %lld holds %d items, above maxSize (%d), and is not frozen", (long long)big,
+                        seed_size[big], max_size);
+    if (k_target > 0) k = k_target;
+    else if (icl_calc_optimal_clusters(N, min_size, max_size, &k) != ICL_OK)
+        return icl_fail(ctx, refuse(ICL_ERR_CONSTRAINT), "cannot satisfy cluster size constraints with total items (%lld), minSize (%d), and maxSize (%d)",
+                        (long long)N, min_size, max_size);
+    // the max_size the kernels see, clamped to [1, N]: no size sum of unfrozen seeds is above N, and a frozen seed's effective size fits the packed words
+    const int32_t kmax = (int32_t)std::min<int64_t>(std::max<int64_t>(max_size, 1), std::max<int64_t>(N, 1));
+    const int64_t T = std::max<int64_t>(0, m - k);
+    ward_call c;
+    icl_ward_ws *w = nullptr;
+    if (T > 0) {
+        std::vector<int32_t> eff((size_t)m);
+        for (int64_t i = 0; i < m; ++i) eff[(size_t)i] = seed_size[i] < 0 ? kmax : seed_size[i];
+        ICL_TRY(ward_ensure(ctx, m, d));
+        w = ctx->ward;
+        if (hipMalloc(&c.eff.p, (size_t)m * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld seed sizes on the device", (long long)m);
+        ICL_HIP(ctx, hipMemcpyAsync(c.eff.p, eff.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (eff leaves scope below)
+        const ward_seed sd{seed_size, (const int32_t *)c.eff.p, T};
+        ward_plan p;
+        ICL_TRY(ward_make_plan(ctx, m, d, min_size, kmax, ICL_UPDATE_EXACT, 0, -1, &p, &sd));
+        ICL_HIP(ctx, hipEventCreate(&c.e0.p));
+        ICL_HIP(ctx, hipEventCreate(&c.e1.p));
+        ICL_HIP(ctx, hipEventCreate(&c.e2.p));
+        ICL_HIP(ctx, hipEventRecord(c.e0.p, ctx->stream));
+        ICL_TRY(ward_init_ws(ctx, w, p, d_C));
+        wrefine rf;
+        ICL_TRY(ward_fill(ctx, w, p, d_C, c, &rf));
+        ICL_HIP(ctx, hipEventRecord(c.e1.p, ctx->stream));
+        ICL_TRY(p.batched ? ward_run_batched(ctx, w, p, rf, c) : ward_run_single(ctx, w, p, rf));
+        ICL_HIP(ctx, hipGetLastError());
+        ICL_HIP(ctx, hipEventRecord(c.e2.p, ctx->stream));
+        ICL_TRY(ward_collect(ctx, w, p, rf, c, min_size, nullptr, nullptr, n_clusters));
+        w->dump.state = 2; // (icl_ward_dump_pairs_dev reads a workspace as singletons)
+    } else // nothing to merge: every seed is a final cluster
+        no_loop();
+    const int64_t nmerge = (int64_t)ctx->last.merges.size() / 2;
+    std::vector<int32_t> finals;
+    std::string why;
+    if (wm_seeded_ids(m, seed_size, min_size, ctx->last.merges.data(), nmerge, cluster_id, seed_rank, n_clusters, &finals, why) != ICL_OK)
+        return icl_fail(ctx, refuse(ICL_ERR_HIP), "icl_cluster_seeded: %s", why.c_str()); // (the engine's own log: the sizes were checked with the arguments)
+    if (d_C_out && out_bytes) {
+        std::vector<int32_t> src((size_t)m, -1);
+        for (size_t f = 0; f < finals.size(); f += 2) src[(size_t)finals[f + 1]] = finals[f];
+        dev_guard g_src;
+        if (hipMalloc(&g_src.p, (size_t)m * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: C_out table of %lld rows", (long long)m);
+        ICL_HIP(ctx, hipMemcpyAsync(g_src.p, src.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(ward_seed_cout_kernel, dim3((unsigned)m), dim3(256), 0, ctx->stream, (const int32_t *)g_src.p, d_C, w ? (const float *)w->Crow : nullptr,
+                           w ? (const int32_t *)w->id_slot : nullptr, m, d, w ? w->S : 0, d_C_out);
+        ICL_HIP(ctx, hipGetLastError());
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return ICL_OK;
+}
+
+// the ARG check of both entry points: nothing is written when it fails
+static int seeded_check_args(icl_ctx *ctx, const char *what, const float *C, int64_t m, int32_t d, const int32_t *seed_size, const int32_t *cluster_id,
+                             const int32_t *seed_rank, const int32_t *n_clusters)
+{
+    if (!ctx || m < 0 || d < 0 || !n_clusters || (m && (!C || !seed_size || !cluster_id || !seed_rank))) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    for (int64_t i = 0; i < m; ++i)
+        if (!seed_size[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: seed_size[%lld] is 0", what, (long long)i);
+    return ICL_OK;
+}
+
+extern "C" int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                      int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
+{
+    return no_throw(ctx, "icl_cluster_seeded_dev", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded_dev", d_C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return cluster_seeded_locked(ctx, d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out);
+    });
+}
+
+extern "C" int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                  int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out)
+{
+    return no_throw(ctx, "icl_cluster_seeded", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded", C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    const size_t bytes = (size_t)m * (size_t)d * 4;
+    dev_guard dC, dO;
+    if (hipMalloc(&dC.p, std::max<size_t>(bytes, 16)) != hipSuccess || (C_out && hipMalloc(&dO.p, std::max<size_t>(bytes, 16)) != hipSuccess))
+        return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld x %d floats on the device", (long long)m, d);
+    if (bytes) ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p);
+    if (C_out && bytes && rc != ICL_ERR_HIP && rc != ICL_ERR_NOMEM) { // (a refused problem's rows are zero)
+        ICL_HIP(ctx, hipMemcpyAsync(C_out, dO.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
+    });
 }
 
 // ---- distance tiles over several GPUs ("tiles computed on 8 GPUs, scattered to GPU0 over xGMI") ----------
@@ -6139,7 +6292,7 @@ extern "C" int icl_ward_dump_pairs_dev(icl_ctx *ctx, const int32_t *ids, int64_t
     icl_device_guard g(ctx->device);
     icl_ward_ws *w = ctx->ward;
     if (!w || w->dump.state == 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: no finished icl_cluster[_dev] call on this context's workspace");
-    if (w->dump.state != 1) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_ward_dump_pairs_dev: FAST mode and sharded group calls are not covered");
+    if (w->dump.state != 1) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_ward_dump_pairs_dev: FAST mode, sharded group calls and seeded calls are not covered");
     const int64_t n = w->dump.n;
     const int d = w->dump.d;
     if (d_expected != d) return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_dump_pairs_dev: the last call clustered %d-dimensional rows, the caller's buffers are for %d", d, d_expected);
@@ -6235,4 +6388,33 @@ extern "C" int64_t icl_last_merges(icl_ctx *ctx, int32_t *pairs, int64_t cap_pai
             pairs[2 * t + 1] = ctx->last.merges[(size_t)(2 * t + 1)];
         }
     return nm;
+}
+
+// ---- the seeded call's kernels ------------------------------------------------------------------------------------------------------------
+// A seeded call's sizes over the tables ward_init_kernel has just written for singletons: seed i (creation id i, slot i, column i) holds eff[i] items.
+__global__ __launch_bounds__(256) void ward_seed_sizes_kernel(int64_t n, const int32_t *__restrict__ eff, int32_t *__restrict__ asz, int32_t *__restrict__ msz,
+                                                              uint32_t *__restrict__ mpk, int szb)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t s = eff[i];
+    asz[i] = s;
+    msz[i] = s;
+    if (mpk) mpk[i] = ((uint32_t)i << szb) | (uint32_t)s;
+}
+
+// C_out of a seeded call, one workgroup per seed row: src[i] = the creation id of the final cluster whose rank-0 seed is i (below n: seed i itself,
+// its input row; else the centroid the exact-rows loops keep in Crow[id_slot[id]]), or -1: a row of zeros.  Crow / id_slot may be null when no id >= n occurs.
+__global__ __launch_bounds__(256) void ward_seed_cout_kernel(const int32_t *__restrict__ src, const float *__restrict__ C, const float *__restrict__ Crow,
+                                                             const int32_t *__restrict__ id_slot, int64_t n, int d, int64_t S, float *__restrict__ out)
+{
+    const int64_t i = blockIdx.x;
+    const int32_t c = src[i];
+    const float *row = nullptr;
+    if (c >= 0 && c < n) row = C + (int64_t)c * d;
+    else if (c >= n) {
+        const int64_t slot = id_slot[c];
+        if (slot >= 0 && slot < S) row = Crow + slot * d;
+    }
+    for (int k = threadIdx.x; k < d; k += blockDim.x) out[i * d + k] = row ? row[k] : 0.0f;
 }

@@ -844,8 +844,9 @@ extern "C" int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int
 // icl_ward_assign_ids' rule at seed granularity: the final list is the surviving seeds in seed order, then the merged clusters in
 // creation order; a cluster's seeds are a's then b's (a: the pair's first id, clustering.go:31); a cluster whose ITEM count is below
 // min_size is dropped and consumes no id.  finals (may be null): (creation id, rank-0 seed) of every final cluster, dropped ones included.
-static int wm_seeded_ids(int64_t m, const int32_t *seed_size, int32_t min_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
-                         int32_t *seed_rank, int32_t *n_clusters, std::vector<int32_t> *finals, std::string &why)
+// (declared in icl_common.h: ward.hip's seeded call, icl_cluster_seeded, applies the same rule)
+int wm_seeded_ids(int64_t m, const int32_t *seed_size, int32_t min_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
+                  int32_t *seed_rank, int32_t *n_clusters, std::vector<int32_t> *finals, std::string &why)
 {
     const int64_t M = m + nmerge;
     std::vector<int32_t> left((size_t)M, -1), right((size_t)M, -1);

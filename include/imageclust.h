@@ -394,6 +394,22 @@ int icl_cluster_many_seeded_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, i
                                 const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
                                 const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
                                 int32_t *merges, int32_t *status, float *d_C_out);
+/* ONE seeded problem on the large-N engine (ward.hip), with no cap on the number of seeds other than memory: the semantics above for a single
+ * problem of m seeds -- C holds the m centroid rows of d floats, seed_size[m] as above, k = k_target when it is above 0 --, the same creation
+ * ids, final list, drop rule and C_out (may be NULL; m x d floats, host memory, device memory for _dev).  The call runs the engine's EXACT
+ * pipeline only -- every entry of the initial matrix by the exact tile with the seeds' sizes, exact rows for new clusters, batched or one merge
+ * per step (ICL_WARD_BATCH=0) -- whatever icl_set_ward_options and m say: the matrix-core bounds and the Lance-Williams bound rows are proven for
+ * singletons.  Returns ICL_OK; ICL_ERR_ARG (nothing written) for a null context or array, m < 0, d < 0 or a size of 0; ICL_ERR_CONSTRAINT for the
+ * reference's (nil,false); ICL_ERR_UNSUPPORTED for a seed above max_size that is not frozen, 2^30 items or more, or a context that is a replica
+ * of a group; ICL_ERR_NOMEM when the workspace (4 m^2 bytes, 8 m^2 where icl_cluster's own layout for m rows is the wider one) does not fit.  On
+ * ICL_ERR_CONSTRAINT / _UNSUPPORTED cluster_id and seed_rank are -1, *n_clusters 0 and C_out zero.  A problem of m <= 1 runs no merge.  As after
+ * icl_cluster, icl_last_merges (the log: (larger id, smaller id) per merge), icl_last_merge_values, icl_last_ward_mode and
+ * icl_last_ward_stats report the call; icl_ward_dump_pairs_dev refuses the workspace a seeded call leaves (ICL_ERR_UNSUPPORTED).  With the
+ * same problem the results equal icl_cluster_many_seeded's, and with every size 1 and no k_target icl_cluster's, bit for bit. */
+int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                       int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out);
+int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                           int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out);
 /* The id rule above for one problem, on the host (no GPU, no context): m seeds, their sizes (the sign is ignored), min_size and a merge
  * log of n_merges pairs -> cluster_id[m], seed_rank[m], n_clusters.  ICL_ERR_ARG for a size of 0 or a log that names a cluster that does
  * not exist (any more); nothing is written then. */
