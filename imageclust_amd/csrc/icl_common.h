@@ -87,6 +87,20 @@ struct icl_ward_report {
     double dist_ms = 0, merge_ms = 0; // icl_last_timings
 };
 
+// What a batched file call counts (ingest_files, jpeg_gpu.hip) and icl_last_ingest_stats / _entropy_stats / _png_stats report.
+struct ingest_totals {
+    int64_t gpu_jpegs = 0, host_files = 0, upload = 0; // JPEGs rebuilt on the GPU, files decoded on the host, bytes uploaded
+    int64_t decode_ns = 0;                             // host thread time in stage A / host decode
+    int64_t gpu_entropy = 0, host_entropy = 0, redone_jpegs = 0, stream_bytes = 0; // JPEGs entropy-decoded on the GPU, by host stage A, redone on the host
+    int64_t gpu_pngs = 0, host_pngs = 0, redone_pngs = 0, png_bytes = 0;           // PNGs decoded on the GPU, by the host route, redone on the host; zlib bytes
+};
+// What icl_downsize_images[_mem] counts (jpeg_gpu.hip) and icl_last_downsize_stats reports.
+struct dz_totals {
+    int64_t passthrough = 0, gpu_rebuilt = 0, host_decoded = 0, second_attempts = 0, bytes_in = 0, bytes_out = 0;
+    int64_t decode_ns = 0;          // host decode, thread time
+    double gpu_ms = 0, out_ms = 0;  // GPU rebuild + encode; download + copy
+};
+
 struct icl_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -129,17 +143,13 @@ struct icl_ctx {
     int many_mid = 0;                 // icl_set_many_options: ICL_MANY_MID_AUTO / _OFF / _ON (environment: ICL_MANY_MID=auto|off|on)
     int64_t many_stats[4] = {0, 0, 0, 0}; // last icl_cluster_many[_dev]: problems on the small, mid and large-N routes, mid-route groups
     icl_ingest_ws *ingest = nullptr; // buffers of the batched file path (jpeg_gpu.hip; created on first use)
-    int64_t ingest_stats[3] = {0, 0, 0}; // last batched file call: JPEGs rebuilt on the GPU, files decoded on the host, bytes uploaded
-    double ingest_decode_s = 0;           // ... host thread-seconds spent in stage A / host decode
+    ingest_totals ingest_last;        // last batched file call (icl_last_ingest_stats, icl_last_entropy_stats, icl_last_png_stats)
     int entropy_mode = 0;                 // icl_set_ingest_options: ICL_ENTROPY_HOST / ICL_ENTROPY_GPU (environment: ICL_JPEG_ENTROPY=gpu)
-    int64_t entropy_stats[4] = {0, 0, 0, 0}; // last batched file call: JPEGs entropy-decoded on the GPU, by host stage A, redone on the host, stream bytes
     int png_mode = 0;                     // icl_set_png_options: ICL_PNG_HOST / ICL_PNG_GPU (environment: ICL_PNG_INFLATE=gpu)
-    int64_t png_stats[4] = {0, 0, 0, 0};  // last batched file call: PNGs decoded on the GPU, by the host route, redone on the host, zlib stream bytes
     icl_requests_ws *requests = nullptr; // device buffers and stage events of icl_cluster_requests (requests.hip; created on first use)
     double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
     icl_jenc_ws *jenc = nullptr;         // buffers of the GPU JPEG encoder (jpeg_encode_gpu.hip; created on first use)
-    int64_t downsize_stats[6] = {0, 0, 0, 0, 0, 0}; // last icl_downsize_images[_mem]: passthrough, GPU-rebuilt, host-decoded, second attempts, bytes in, bytes out
-    double downsize_ms[3] = {0, 0, 0};              // ... host decode (thread-ms), GPU rebuild + encode, download + copy (icl_last_downsize_stats)
+    dz_totals downsize_last;             // last icl_downsize_images[_mem] (icl_last_downsize_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
@@ -231,31 +241,40 @@ struct ingest_src {
 };
 // What a message calls the source: its path, or "image <index> (in memory, <bytes> bytes)" written into buf (image_io.hip).
 const char *ingest_src_name(const ingest_src &s, char *buf, size_t cap);
-static inline std::vector<ingest_src> ingest_path_srcs(const char *const *paths, int64_t n)
-{
-    std::vector<ingest_src> v((size_t)n);
-    for (int64_t i = 0; i < n; ++i) v[(size_t)i] = ingest_src{paths[i], nullptr, 0, i};
-    return v;
-}
-static inline std::vector<ingest_src> ingest_mem_srcs(const uint8_t *const *data, const int64_t *bytes, int64_t n)
-{
-    std::vector<ingest_src> v((size_t)n);
-    for (int64_t i = 0; i < n; ++i) v[(size_t)i] = ingest_src{nullptr, data[i], bytes[i], i};
-    return v;
-}
-// jpeg_gpu.hip: the ingest pipeline behind those entry points: one ingest_pass in the context's entropy mode (per slab: slab_collect ->
-// run_slab_decode -> slab_deliver), then a repair pass in host mode over the images the GPU entropy check rejected.  Returns the code of
+// A caller's list of images as an extern "C" entry point receives it: files (paths) or memory sources (data, bytes).
+struct ingest_list {
+    bool mem;
+    const char *const *paths;
+    const uint8_t *const *data;
+    const int64_t *bytes;
+    int64_t n;
+    static ingest_list files(const char *const *paths, int64_t n) { return ingest_list{false, paths, nullptr, nullptr, n}; }
+    static ingest_list memory(const uint8_t *const *data, const int64_t *bytes, int64_t n) { return ingest_list{true, nullptr, data, bytes, n}; }
+    // What ICL_ERR_ARG covers for a list: NO_ARRAYS for n < 0 or a missing array of a list that is not empty, the index of the first NULL
+    // path, else OK.  (An empty or NULL entry of a memory list is that image's own failure.)
+    enum : int64_t { OK = -1, NO_ARRAYS = -2 };
+    int64_t first_bad() const
+    {
+        if (n < 0 || (n && (mem ? !data || !bytes : !paths))) return NO_ARRAYS;
+        for (int64_t i = 0; !mem && i < n; ++i)
+            if (!paths[i]) return i;
+        return OK;
+    }
+    std::vector<ingest_src> srcs() const // (of a checked list)
+    {
+        std::vector<ingest_src> v((size_t)n);
+        for (int64_t i = 0; i < n; ++i) v[(size_t)i] = mem ? ingest_src{nullptr, data[i], bytes[i], i} : ingest_src{paths[i], nullptr, 0, i};
+        return v;
+    }
+};
+// jpeg_gpu.hip: the ingest pipeline behind those entry points: one ingest_pass in the context's entropy and PNG modes (per slab:
+// slab_collect -> run_slab_decode -> slab_deliver), then a repair pass in host mode over the images the GPU entropy or PNG check rejected.
+// (The batched downsizer of the same file runs its rounds likewise: dz_collect -> dz_rebuild -> dz_deliver.)  Returns the code of
 // the lowest failed image (status[] carries every image's; failed rows are zero (u8) or NaN) after the whole list has been processed --
 // lowest (may be NULL) then names that image -- or the error that stopped it (lowest->index stays -1).
 int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t threads, const ingest_sink &sink, int32_t *status, const char *what,
                  icl_item_failure *lowest = nullptr);
-static inline void icl_ingest_stats_reset(icl_ctx *ctx) // what a batched file call reports (icl_last_ingest_stats, icl_last_entropy_stats, icl_last_png_stats)
-{
-    ctx->ingest_stats[0] = ctx->ingest_stats[1] = ctx->ingest_stats[2] = 0;
-    ctx->entropy_stats[0] = ctx->entropy_stats[1] = ctx->entropy_stats[2] = ctx->entropy_stats[3] = 0;
-    ctx->png_stats[0] = ctx->png_stats[1] = ctx->png_stats[2] = ctx->png_stats[3] = 0;
-    ctx->ingest_decode_s = 0;
-}
+static inline void icl_ingest_stats_reset(icl_ctx *ctx) { ctx->ingest_last = ingest_totals(); } // what a batched file call reports
 // ward_many.hip: icl_cluster_many[_dev] after the argument check (d_E on the device, or h_E on the host and uploaded there).  Returns the
 // code of the lowest failed problem once every problem has its results -- lowest (may be NULL) then names it -- or the error that
 // stopped the call (lowest->index stays -1; the per-problem outputs are not valid).

@@ -16,8 +16,12 @@
 // the files the GPU entropy check or the GPU PNG check (png_gpu.hip) rejected.  ingest_pass = ingest_buffers, then per slab slab_collect (rows in file order from the worker threads' ingest_feed,
 // ingest_feed.h, into a pinned slab; slab_fill::fits says when a slab is full) -> run_slab_decode (upload, entropy decode, IDCT) ->
 // slab_deliver (gather / resize, forward pass, NaN rows of failed files, into the call's ingest_sink), then tally_accepted.
-// The batched downsizer at the end of the file (icl_downsize_images[_mem]) drives the same stages up to the planes, then a gather / resize
-// at each image's own size and the JPEG encoder (jpeg_encode_gpu.hip).
+// The batched downsizer at the end of the file (icl_downsize_images[_mem]) has a driver of the same shape, downsize_images_locked: per
+// round dz_collect (images in list order into a dz_round, the JPEGs placed in the pinned slab; dz_round::admits says when a round is full)
+// -> dz_rebuild (run_slab_decode to the planes, then per attempt a gather / resize at each image's own size and the JPEG encoder,
+// jpeg_encode_gpu.hip) -> dz_deliver (files, statuses, failures and dz_totals in list order).
+// Both drivers share the worker pool (worker_count, feed_worker), the failure capture of a worker (fail_from_tls, decoder_guard), the
+// report of the lowest failed file (report_lowest), and, with the two test hooks, the placement code (slab_of_one).
 #include "icl_common.h"
 #include "ingest_feed.h"
 #include "ingest_pixels.h"
@@ -273,6 +277,8 @@ struct slab_view {
         : imgs((ingest_image *)hdr), planes((ingest_plane *)(hdr + SLAB_IMAGES * sizeof(ingest_image))), scans((icl_je_scan *)(hdr + HDR_SCANS)), payload(pay)
     {
     }
+    // a row's start: its descriptor cleared up to the resize tables (place_* and the collectors fill in what the row's kind needs)
+    void clear_row(int i) const { memset(&imgs[i], 0, offsetof(ingest_image, xofs)); }
 };
 
 static int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
@@ -423,6 +429,33 @@ struct worker_state { // buffers a worker reuses from file to file
     std::vector<uint32_t> offs;
 };
 
+// A worker's failure into its result: the code, and the calling thread's last error text (what icl_fail left there).
+static void fail_from_tls(file_result &r, int rc)
+{
+    r.kind = KIND_FAILED;
+    r.rc = rc;
+    r.err = icl_last_error(nullptr);
+}
+
+// body() on a worker thread; what a decoder throws becomes the failed result r of the image the messages call `name`.  false: it threw.
+template <class Body> static bool decoder_guard(file_result &r, const char *name, const Body &body)
+{
+    auto threw = [&](int rc, const char *why) {
+        r.kind = KIND_FAILED;
+        r.rc = rc;
+        r.err = std::string("failed to read image: ") + name + why;
+        return false;
+    };
+    try {
+        body();
+        return true;
+    } catch (const std::bad_alloc &) {
+        return threw(ICL_ERR_NOMEM, ". Out of host memory while decoding");
+    } catch (...) {
+        return threw(ICL_ERR_IO, ". Decoder error");
+    }
+}
+
 // One image (a file, or a memory source read in place: icl_image_src_read), on a worker thread: stage A0 for a JPEG whose entropy decoder runs on the GPU (entropy == ICL_ENTROPY_GPU and the file
 // qualifies), stage A for every other JPEG the GPU takes, stage P0 for a PNG that qualifies for the GPU route (modes.png == ICL_PNG_GPU), the whole host path for everything else.  Status codes and messages are
 // those of icl_load_image_224 (image_io.hip).
@@ -432,12 +465,7 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
                               const FinishHost &finish_host)
 {
     icl_jpeg_coefs &J = ws.J;
-    auto fail_from_tls = [&](int rc) {
-        r.kind = KIND_FAILED;
-        r.rc = rc;
-        r.err = icl_last_error(nullptr);
-    };
-    try {
+    decoder_guard(r, path, [&]() {
         std::vector<uint8_t> file, rgb;
         int w = 0, h = 0;
         const uint8_t *data;
@@ -454,7 +482,7 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
             }
             r.host_entropy = true;
             const int rc = icl_jpeg_stage_a(nullptr, data, len, path, J);
-            if (rc) return fail_from_tls(rc);
+            if (rc) return fail_from_tls(r, rc);
             if (pack_jpeg(J, r, ws.offs)) {
                 r.kind = KIND_JPEG;
                 return;
@@ -463,7 +491,7 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
             w = J.W;
             h = J.H;
             const int rc2 = icl_jpeg_stage_b(nullptr, J, path, rgb);
-            if (rc2) return fail_from_tls(rc2);
+            if (rc2) return fail_from_tls(r, rc2);
             icl_apply_exif_orientation(rgb, w, h, J.orient);
         } else { // PNG, PPM, or a file that cannot be read / an empty buffer: the host path decodes it or reports why not
             if (fmt == ICL_IMAGE_PNG) {
@@ -474,19 +502,11 @@ static void process_file_with(const ingest_src &src, const char *path /* what th
                 r.host_png = true;
             }
             const int rc = icl_image_decode(nullptr, src, path, fmt, data, len, rgb, w, h);
-            if (rc) return fail_from_tls(rc);
+            if (rc) return fail_from_tls(r, rc);
         }
-        if (!finish_host(rgb, w, h)) return fail_from_tls(ICL_ERR_ARG);
+        if (!finish_host(rgb, w, h)) return fail_from_tls(r, ICL_ERR_ARG);
         r.kind = KIND_HOST;
-    } catch (const std::bad_alloc &) {
-        r.kind = KIND_FAILED;
-        r.rc = ICL_ERR_NOMEM;
-        r.err = std::string("failed to read image: ") + path + ". Out of host memory while decoding";
-    } catch (...) {
-        r.kind = KIND_FAILED;
-        r.rc = ICL_ERR_IO;
-        r.err = std::string("failed to read image: ") + path + ". Decoder error";
-    }
+    });
 }
 
 static void process_file(const ingest_src &src, worker_state &ws, const ingest_modes &modes, file_result &r)
@@ -760,16 +780,68 @@ static int run_slab_decode(icl_ctx *ctx, icl_ingest_ws *ws, const slab_view &H, 
     return ICL_OK;
 }
 
+// One stream result alone in slab 0, through the pipeline's own placement and launch code up to the planes (the test hooks): a
+// KIND_PSTREAM by place_png, a JPEG by place_jpeg.  d_flag / h_flag: the check's flag that applies, downloaded into accepted; the slab is
+// ws->host(0), the stream is synchronised.  `name` is what the messages call the image.
+static int slab_of_one(icl_ctx *ctx, icl_ingest_ws *ws, const file_result &r, int png_stages, const int32_t *d_flag, int32_t *h_flag, const char *what, const char *name,
+                       bool &accepted)
+{
+    ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
+    const slab_view S = ws->host(0);
+    const bool png = r.kind == KIND_PSTREAM;
+    slab_fill F;
+    S.clear_row(0);
+    if (!(png ? place_png(r, F, S) : place_jpeg(r, F, S))) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent %s geometry for %s", what, png ? "PNG" : "JPEG", name);
+    F.nimg = 1;
+    int64_t upload = 0;
+    ICL_TRY(run_slab_decode(ctx, ws, S, F, upload, png_stages));
+    ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
+    ICL_HIP(ctx, hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    accepted = h_flag[0] != 0;
+    return ICL_OK;
+}
+
 struct file_fail {
     int64_t index;
     int rc;
     std::string err;
 };
 
-struct ingest_totals {
-    int64_t gpu_jpegs = 0, host_files = 0, upload = 0, decode_ns = 0;
-    int64_t gpu_entropy = 0, host_entropy = 0, stream_bytes = 0;
-    int64_t gpu_pngs = 0, host_pngs = 0, png_bytes = 0;
+// The report of a call whose list has been processed: the code of the lowest failed file with "<what>: file <index> of <n>: <its reason>"
+// as the context's message (lowest_out, may be NULL, then names that file), or ICL_OK.
+static int report_lowest(icl_ctx *ctx, const std::vector<file_fail> &fails, int64_t n, const char *what, icl_item_failure *lowest_out)
+{
+    const file_fail *lowest = nullptr;
+    for (const file_fail &f : fails)
+        if (!lowest || f.index < lowest->index) lowest = &f;
+    if (!lowest) return ICL_OK;
+    if (lowest_out) *lowest_out = icl_item_failure{lowest->index, lowest->rc, lowest->err};
+    return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
+}
+
+// worker threads of a call over n items: the caller's figure, else up to 16 of the machine's; never more than items, at least one
+static int worker_count(int64_t n, int32_t threads)
+{
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    return (int)std::max<int64_t>(1, std::min<int64_t>(n, threads > 0 ? threads : (int)std::min(16u, hw)));
+}
+
+// The produce function of a call's feed (pass it as std::ref): item(i, state, result) on a worker thread, with the thread's own
+// worker_state, kept from item to item, and a fresh result (nullptr where either cannot be allocated: the feed stops).  decode_ns sums
+// the threads' time in item(); it is complete once the feed has joined its workers.
+template <class R> struct feed_worker {
+    std::function<void(int64_t, worker_state &, R &)> item;
+    std::atomic<int64_t> decode_ns{0};
+    std::unique_ptr<R> operator()(int64_t i)
+    {
+        thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state());
+        const auto t0 = std::chrono::steady_clock::now();
+        std::unique_ptr<R> r(wst ? new (std::nothrow) R() : nullptr);
+        if (r) item(i, *wst, *r);
+        decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        return r;
+    }
 };
 
 struct ingest_job { // the list a pass works on, and its caller
@@ -825,7 +897,7 @@ static int slab_collect(icl_ctx *ctx, const ingest_job &job, file_feed &feed, co
         const std::unique_ptr<file_result> r = feed.take();
         const int64_t row = R.first + F.nimg;
         ingest_image &D = S.imgs[F.nimg];
-        memset(&D, 0, offsetof(ingest_image, xofs));
+        S.clear_row(F.nimg);
         D.kind = r->kind;
         if (job.status) job.status[row] = r->rc;
         if (r->kind == KIND_FAILED) {
@@ -907,19 +979,10 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
 {
     icl_ingest_ws *ws = nullptr;
     ICL_TRY(ingest_buffers(ctx, sink, modes.entropy, job.n, ws));
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(job.n, job.threads > 0 ? job.threads : (int)std::min(16u, hw)));
-    std::atomic<int64_t> decode_ns{0};
-    auto decode = [&](int64_t i) -> std::unique_ptr<file_result> {
-        thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state()); // a worker's buffers, from file to file
-        const auto t0 = std::chrono::steady_clock::now();
-        std::unique_ptr<file_result> r(wst ? new (std::nothrow) file_result() : nullptr);
-        if (r) process_file(job.srcs[i], *wst, modes, *r);
-        decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        return r;
-    };
+    feed_worker<file_result> work{[&](int64_t i, worker_state &wst, file_result &r) { process_file(job.srcs[i], wst, modes, r); }};
     {
-        file_feed feed(job.n, nthr, 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, decode, [](const file_result &r) { return (int64_t)r.packed.size(); });
+        file_feed feed(job.n, worker_count(job.n, job.threads), 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, std::ref(work),
+                       [](const file_result &r) { return (int64_t)r.packed.size(); });
         slab_rows R;
         for (int64_t k = 0; feed.taken() < job.n; ++k) {
             const int q = (int)(k & 1);
@@ -938,7 +1001,7 @@ static int ingest_pass(icl_ctx *ctx, const ingest_job &job, const ingest_sink &s
         }
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     } // (the feed has joined its workers: decode_ns is complete)
-    tot.decode_ns += decode_ns.load();
+    tot.decode_ns += work.decode_ns.load();
     tally_accepted(ws, res, tot);
     return ICL_OK;
 }
@@ -985,108 +1048,86 @@ int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t thread
         tot.gpu_pngs -= nrej_png;      // (the PNG rejections likewise: the repair pass counts them among host_files)
         tot.host_pngs -= nrej_png;
     }
-    // ---- report ----
-    ctx->ingest_stats[0] = tot.gpu_jpegs;
-    ctx->ingest_stats[1] = tot.host_files;
-    ctx->ingest_stats[2] = tot.upload;
-    ctx->ingest_decode_s = (double)tot.decode_ns * 1e-9;
-    ctx->entropy_stats[0] = tot.gpu_entropy;
-    ctx->entropy_stats[1] = tot.host_entropy;
-    ctx->entropy_stats[2] = nrej_jpeg;
-    ctx->entropy_stats[3] = tot.stream_bytes;
-    ctx->png_stats[0] = tot.gpu_pngs;
-    ctx->png_stats[1] = tot.host_pngs;
-    ctx->png_stats[2] = nrej_png;
-    ctx->png_stats[3] = tot.png_bytes;
-    const file_fail *lowest = nullptr;
-    for (const file_fail &f : res.fails)
-        if (!lowest || f.index < lowest->index) lowest = &f;
-    if (lowest && lowest_out) *lowest_out = icl_item_failure{lowest->index, lowest->rc, lowest->err};
-    if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
-    return ICL_OK;
+    tot.redone_jpegs = nrej_jpeg;
+    tot.redone_pngs = nrej_png;
+    ctx->ingest_last = tot;
+    return report_lowest(ctx, res.fails, n, what, lowest_out);
 }
 
-// what ICL_ERR_ARG covers for a list of memory sources (an empty or NULL entry is that image's own failure)
-static bool mem_list_ok(const uint8_t *const *data, const int64_t *bytes, int64_t n) { return n >= 0 && (n == 0 || (data && bytes)); }
-
-static int load_images_224_dev(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int32_t threads, uint8_t *d_out,
-                               int32_t *status, const char *what)
+static int load_images_224_dev(icl_ctx *ctx, const ingest_list &imgs, int32_t threads, uint8_t *d_out, int32_t *status, const char *what)
 {
+    const int64_t n = imgs.n, bad = imgs.first_bad();
+    if (!ctx || bad == ingest_list::NO_ARRAYS || (n && !d_out) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return no_throw(ctx, what, [&]() -> int {
         icl_ingest_stats_reset(ctx);
         if (n == 0) return ICL_OK;
-        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        const std::vector<ingest_src> srcs = imgs.srcs();
         return ingest_files(ctx, srcs.data(), n, threads, ingest_sink{ingest_sink::U8_DEV, d_out, 0, 0}, status, what);
     });
 }
 
 extern "C" int icl_load_images_224_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int32_t threads, uint8_t *d_out, int32_t *status)
 {
-    if (!ctx || n < 0 || (n && (!paths || !d_out)) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: bad argument");
-    for (int64_t i = 0; i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_dev: paths[%lld] is NULL", (long long)i);
-    return load_images_224_dev(ctx, false, paths, nullptr, nullptr, n, threads, d_out, status, "icl_load_images_224_dev");
+    return load_images_224_dev(ctx, ingest_list::files(paths, n), threads, d_out, status, "icl_load_images_224_dev");
 }
 
 extern "C" int icl_load_images_224_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int32_t threads, uint8_t *d_out, int32_t *status)
 {
-    if (!ctx || !mem_list_ok(data, bytes, n) || (n && !d_out) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_load_images_224_mem_dev: bad argument");
-    return load_images_224_dev(ctx, true, nullptr, data, bytes, n, threads, d_out, status, "icl_load_images_224_mem_dev");
+    return load_images_224_dev(ctx, ingest_list::memory(data, bytes, n), threads, d_out, status, "icl_load_images_224_mem_dev");
 }
 
-// mem: memory sources (data, bytes); otherwise files (paths)
-static int embed_files(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec,
-                       int32_t threads, float *out, int32_t *status, bool dev, const char *what)
+static int embed_files(icl_ctx *ctx, const ingest_list &imgs, int head, int prec, int32_t threads, float *out, int32_t *status, bool dev, const char *what)
 {
-    if (!ctx || n < 0 || (n && !out) || threads < 0 || (mem ? !mem_list_ok(data, bytes, n) : (n && !paths))) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    const int64_t n = imgs.n, bad = imgs.first_bad();
+    if (!ctx || bad == ingest_list::NO_ARRAYS || (n && !out) || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
     if (head != ICL_HEAD_POOLED && head != ICL_HEAD_DENSE0) return icl_fail(ctx, ICL_ERR_ARG, "head must be 2048 or 1000");
     if (prec != ICL_PREC_FP32 && prec != ICL_PREC_BF16 && prec != ICL_PREC_BF16X3)
         return icl_fail(ctx, ICL_ERR_ARG, "prec must be ICL_PREC_FP32, ICL_PREC_BF16 or ICL_PREC_BF16X3");
-    for (int64_t i = 0; !mem && i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     if (!ctx->model) return icl_fail(ctx, ICL_ERR_NOMODEL, "no model loaded (call icl_model_load_* first)");
     return no_throw(ctx, what, [&]() -> int {
         icl_ingest_stats_reset(ctx);
         if (n == 0) return ICL_OK;
-        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        const std::vector<ingest_src> srcs = imgs.srcs();
         return ingest_files(ctx, srcs.data(), n, threads, ingest_sink{dev ? ingest_sink::EMB_DEV : ingest_sink::EMB_HOST, out, head, prec}, status, what);
     });
 }
 
 extern "C" int icl_embed_files(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *out, int32_t *status)
 {
-    return embed_files(ctx, false, paths, nullptr, nullptr, n, head, prec, threads, out, status, false, "icl_embed_files");
+    return embed_files(ctx, ingest_list::files(paths, n), head, prec, threads, out, status, false, "icl_embed_files");
 }
 
 extern "C" int icl_embed_files_dev(icl_ctx *ctx, const char *const *paths, int64_t n, int head, int prec, int32_t threads, float *d_out, int32_t *status)
 {
-    return embed_files(ctx, false, paths, nullptr, nullptr, n, head, prec, threads, d_out, status, true, "icl_embed_files_dev");
+    return embed_files(ctx, ingest_list::files(paths, n), head, prec, threads, d_out, status, true, "icl_embed_files_dev");
 }
 
 extern "C" int icl_embed_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec, int32_t threads, float *out,
                                     int32_t *status)
 {
-    return embed_files(ctx, true, nullptr, data, bytes, n, head, prec, threads, out, status, false, "icl_embed_images_mem");
+    return embed_files(ctx, ingest_list::memory(data, bytes, n), head, prec, threads, out, status, false, "icl_embed_images_mem");
 }
 
 extern "C" int icl_embed_images_mem_dev(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int head, int prec, int32_t threads, float *d_out,
                                         int32_t *status)
 {
-    return embed_files(ctx, true, nullptr, data, bytes, n, head, prec, threads, d_out, status, true, "icl_embed_images_mem_dev");
+    return embed_files(ctx, ingest_list::memory(data, bytes, n), head, prec, threads, d_out, status, true, "icl_embed_images_mem_dev");
 }
 
 extern "C" int icl_last_ingest_stats(icl_ctx *ctx, int64_t *gpu_jpegs, int64_t *host_files, int64_t *upload_bytes, double *host_decode_s)
 {
     if (!ctx) return ICL_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (gpu_jpegs) *gpu_jpegs = ctx->ingest_stats[0];
-    if (host_files) *host_files = ctx->ingest_stats[1];
-    if (upload_bytes) *upload_bytes = ctx->ingest_stats[2];
-    if (host_decode_s) *host_decode_s = ctx->ingest_decode_s;
+    if (gpu_jpegs) *gpu_jpegs = ctx->ingest_last.gpu_jpegs;
+    if (host_files) *host_files = ctx->ingest_last.host_files;
+    if (upload_bytes) *upload_bytes = ctx->ingest_last.upload;
+    if (host_decode_s) *host_decode_s = (double)ctx->ingest_last.decode_ns * 1e-9;
     return ICL_OK;
 }
 
@@ -1103,10 +1144,10 @@ extern "C" int icl_last_entropy_stats(icl_ctx *ctx, int64_t *gpu_entropy_jpegs, 
 {
     if (!ctx) return ICL_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (gpu_entropy_jpegs) *gpu_entropy_jpegs = ctx->entropy_stats[0];
-    if (host_entropy_jpegs) *host_entropy_jpegs = ctx->entropy_stats[1];
-    if (redone_on_host) *redone_on_host = ctx->entropy_stats[2];
-    if (stream_bytes) *stream_bytes = ctx->entropy_stats[3];
+    if (gpu_entropy_jpegs) *gpu_entropy_jpegs = ctx->ingest_last.gpu_entropy;
+    if (host_entropy_jpegs) *host_entropy_jpegs = ctx->ingest_last.host_entropy;
+    if (redone_on_host) *redone_on_host = ctx->ingest_last.redone_jpegs;
+    if (stream_bytes) *stream_bytes = ctx->ingest_last.stream_bytes;
     return ICL_OK;
 }
 
@@ -1122,10 +1163,10 @@ extern "C" int icl_last_png_stats(icl_ctx *ctx, int64_t *gpu_pngs, int64_t *host
 {
     if (!ctx) return ICL_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (gpu_pngs) *gpu_pngs = ctx->png_stats[0];
-    if (host_pngs) *host_pngs = ctx->png_stats[1];
-    if (redone_on_host) *redone_on_host = ctx->png_stats[2];
-    if (stream_bytes) *stream_bytes = ctx->png_stats[3];
+    if (gpu_pngs) *gpu_pngs = ctx->ingest_last.gpu_pngs;
+    if (host_pngs) *host_pngs = ctx->ingest_last.host_pngs;
+    if (redone_on_host) *redone_on_host = ctx->ingest_last.redone_pngs;
+    if (stream_bytes) *stream_bytes = ctx->ingest_last.png_bytes;
     return ICL_OK;
 }
 
@@ -1134,13 +1175,14 @@ extern "C" int icl_last_png_stats(icl_ctx *ctx, int64_t *gpu_pngs, int64_t *host
 extern "C" int icl_png_raw_files(icl_ctx *ctx, const char *const *paths, int64_t n, int stage, uint8_t *raw, int64_t cap, int64_t *offsets, int32_t *state)
 {
     const char *what = "icl_png_raw_files";
-    if (!ctx || n < 0 || (n && !paths) || !offsets || !state || cap < 0 || (stage != 0 && stage != 1)) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
-    for (int64_t i = 0; i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    const ingest_list imgs = ingest_list::files(paths, n);
+    const int64_t bad = imgs.first_bad();
+    if (!ctx || bad == ingest_list::NO_ARRAYS || !offsets || !state || cap < 0 || (stage != 0 && stage != 1)) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return no_throw(ctx, what, [&]() -> int {
-        const std::vector<ingest_src> srcs = ingest_path_srcs(paths, n);
+        const std::vector<ingest_src> srcs = imgs.srcs();
         icl_ingest_ws *ws = nullptr;
         std::unique_ptr<worker_state> wst(new worker_state());
         int64_t at = 0;
@@ -1156,19 +1198,10 @@ extern "C" int icl_png_raw_files(icl_ctx *ctx, const char *const *paths, int64_t
                 if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small", what);
                 ICL_TRY(ingest_ws(ctx, ws));
                 ICL_TRY(png_ws(ctx, ws, 1));
-                ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
-                const slab_view S = ws->host(0);
-                slab_fill F;
-                memset(&S.imgs[0], 0, offsetof(ingest_image, xofs));
-                if (!place_png(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent PNG geometry for %s", what, paths[i]);
-                F.nimg = 1;
-                int64_t upload = 0;
-                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload, stage == 0 ? 1 : 2));
-                ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
-                ICL_HIP(ctx, hipMemcpyAsync(ws->h_png_ok, ws->d_png_ok, 4, hipMemcpyDeviceToHost, ctx->stream));
-                ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                state[i] = ws->h_png_ok[0] ? 1 : 0;
-                if (state[i] == 1) ICL_HIP(ctx, hipMemcpy(raw + at, ws->d_scratch + S.imgs[0].yplane, (size_t)total, hipMemcpyDeviceToHost));
+                bool ok = false;
+                ICL_TRY(slab_of_one(ctx, ws, r, stage == 0 ? 1 : 2, ws->d_png_ok, ws->h_png_ok, what, paths[i], ok));
+                state[i] = ok ? 1 : 0;
+                if (ok) ICL_HIP(ctx, hipMemcpy(raw + at, ws->d_scratch + ws->host(0).imgs[0].yplane, (size_t)total, hipMemcpyDeviceToHost));
             }
             at += total; // (a rejected file keeps its range; its contents are not written)
         }
@@ -1177,14 +1210,17 @@ extern "C" int icl_png_raw_files(icl_ctx *ctx, const char *const *paths, int64_t
     });
 }
 
-// the body of icl_jpeg_coefs_files / _mem after the argument check
-static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs,
-                      int64_t cap, int64_t *offsets, int32_t *state, const char *what)
+// the body of icl_jpeg_coefs_files / _mem
+static int jpeg_coefs(icl_ctx *ctx, const ingest_list &imgs, int entropy_mode, int16_t *coefs, int64_t cap, int64_t *offsets, int32_t *state, const char *what)
 {
+    const int64_t n = imgs.n, bad = imgs.first_bad();
+    if (!ctx || bad == ingest_list::NO_ARRAYS || !offsets || !state || cap < 0 || (entropy_mode != ICL_ENTROPY_HOST && entropy_mode != ICL_ENTROPY_GPU))
+        return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return no_throw(ctx, what, [&]() -> int {
-        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
+        const std::vector<ingest_src> srcs = imgs.srcs();
         icl_ingest_ws *ws = nullptr;
         if (entropy_mode == ICL_ENTROPY_GPU) {
             ICL_TRY(ingest_ws(ctx, ws));
@@ -1223,22 +1259,13 @@ static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const ui
             state[i] = 0;
             if (coefs) {
                 if (at + total > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small", what);
-                ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[0]));
-                const slab_view S = ws->host(0);
-                slab_fill F;
-                memset(&S.imgs[0], 0, offsetof(ingest_image, xofs));
-                if (!place_jpeg(r, F, S)) return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, name);
-                F.nimg = 1;
-                int64_t upload = 0;
-                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload));
-                ICL_HIP(ctx, hipEventRecord(ws->ev_up[0], ctx->stream));
-                ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, 4, hipMemcpyDeviceToHost, ctx->stream));
-                ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                state[i] = ws->h_accepted[0] ? 1 : 0;
+                bool ok = false;
+                ICL_TRY(slab_of_one(ctx, ws, r, 2, ws->d_accepted, ws->h_accepted, what, name, ok));
+                state[i] = ok ? 1 : 0;
                 int64_t o = at;
-                for (int c = 0; c < r.ncomp && state[i] == 1; ++c) {
+                for (int c = 0; c < r.ncomp && ok; ++c) {
                     const int64_t ne = (int64_t)r.cm[c].wblocks * r.cm[c].hblocks * 64;
-                    ICL_HIP(ctx, hipMemcpy(coefs + o, ws->d_coef + S.scans[0].coef_off[c], (size_t)ne * 2, hipMemcpyDeviceToHost));
+                    ICL_HIP(ctx, hipMemcpy(coefs + o, ws->d_coef + ws->host(0).scans[0].coef_off[c], (size_t)ne * 2, hipMemcpyDeviceToHost));
                     o += ne;
                 }
             }
@@ -1249,26 +1276,17 @@ static int jpeg_coefs(icl_ctx *ctx, bool mem, const char *const *paths, const ui
     });
 }
 
-static bool coefs_args_ok(icl_ctx *ctx, int64_t n, int entropy_mode, int64_t cap, const int64_t *offsets, const int32_t *state)
-{
-    return ctx && n >= 0 && offsets && state && cap >= 0 && (entropy_mode == ICL_ENTROPY_HOST || entropy_mode == ICL_ENTROPY_GPU);
-}
-
 // Test hook: the quantised coefficients of each file as stage A leaves them, by host stage A or by the GPU entropy decoder (one
 // single-image slab per file through the pipeline's own placement and launch code).
 extern "C" int icl_jpeg_coefs_files(icl_ctx *ctx, const char *const *paths, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap, int64_t *offsets, int32_t *state)
 {
-    if (!coefs_args_ok(ctx, n, entropy_mode, cap, offsets, state) || (n && !paths)) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: bad argument");
-    for (int64_t i = 0; i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_files: paths[%lld] is NULL", (long long)i);
-    return jpeg_coefs(ctx, false, paths, nullptr, nullptr, n, entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_files");
+    return jpeg_coefs(ctx, ingest_list::files(paths, n), entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_files");
 }
 
 extern "C" int icl_jpeg_coefs_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int entropy_mode, int16_t *coefs, int64_t cap,
                                   int64_t *offsets, int32_t *state)
 {
-    if (!coefs_args_ok(ctx, n, entropy_mode, cap, offsets, state) || !mem_list_ok(data, bytes, n)) return icl_fail(ctx, ICL_ERR_ARG, "icl_jpeg_coefs_mem: bad argument");
-    return jpeg_coefs(ctx, true, nullptr, data, bytes, n, entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_mem");
+    return jpeg_coefs(ctx, ingest_list::memory(data, bytes, n), entropy_mode, coefs, cap, offsets, state, "icl_jpeg_coefs_mem");
 }
 
 // ---- the batched downsizer: resizeImageIfNeeded (rekognition.go:173-259) over a list, icl_downsize_images[_mem] ------------------------
@@ -1341,17 +1359,15 @@ static void dz_process(const ingest_src &src, worker_state &ws, int entropy, int
     char nbuf[96];
     const char *name = ingest_src_name(src, nbuf, sizeof nbuf);
     file_result &r = z.fr;
-    auto fail_from_tls = [&](int rc) {
+    auto fail = [&](int rc) {
         z.type = DZ_FAILED;
-        r.kind = KIND_FAILED;
-        r.rc = rc;
-        r.err = icl_last_error(nullptr);
+        fail_from_tls(r, rc);
     };
-    try {
+    const bool done = decoder_guard(r, name, [&]() {
         const uint8_t *data = nullptr;
         size_t len = 0;
         const int rc = icl_src_bytes(src, name, z.bytes, data, len);
-        if (rc) return fail_from_tls(rc);
+        if (rc) return fail(rc);
         z.in_bytes = (int64_t)len;
         if ((int64_t)len <= max_bytes) {
             z.type = DZ_PASS;
@@ -1363,7 +1379,7 @@ static void dz_process(const ingest_src &src, worker_state &ws, int entropy, int
             int32_t info[6];
             std::vector<uint8_t> out;
             const int rc2 = icl_downsize_src(src, max_bytes, max_dim, out, info);
-            if (rc2) return fail_from_tls(rc2);
+            if (rc2) return fail(rc2);
             z.bytes.swap(out);
             z.attempts = info[5];
             z.type = DZ_DONE;
@@ -1397,22 +1413,13 @@ static void dz_process(const ingest_src &src, worker_state &ws, int entropy, int
         const bool swap = icl_exif_swaps_axes(r.orient);
         z.ow = swap ? r.H : r.W;
         z.oh = swap ? r.W : r.H;
-        if (icl_downsize_dims_checked(name, z.ow, z.oh, max_dim, z.nw, z.nh)) return fail_from_tls(ICL_ERR_ARG);
+        if (icl_downsize_dims_checked(name, z.ow, z.oh, max_dim, z.nw, z.nh)) return fail(ICL_ERR_ARG);
         if (too_large(z.nw, z.nh)) return whole_on_host();
         z.type = DZ_GPU;
         z.bytes.clear();
         z.bytes.shrink_to_fit();
-    } catch (const std::bad_alloc &) {
-        z.type = DZ_FAILED;
-        r.kind = KIND_FAILED;
-        r.rc = ICL_ERR_NOMEM;
-        r.err = std::string("failed to read image: ") + name + ". Out of host memory while decoding";
-    } catch (...) {
-        z.type = DZ_FAILED;
-        r.kind = KIND_FAILED;
-        r.rc = ICL_ERR_IO;
-        r.err = std::string("failed to read image: ") + name + ". Decoder error";
-    }
+    });
+    if (!done) z.type = DZ_FAILED;
 }
 
 struct dz_entry { // one image of a slab, in list order
@@ -1505,196 +1512,221 @@ static int dz_encode_pass(icl_ctx *ctx, icl_ingest_ws *ws, dz_ws &B, std::vector
     return ICL_OK;
 }
 
-static int downsize_images_locked(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int64_t max_bytes, int max_dim, int32_t threads, uint8_t *out, int64_t cap,
-                                  int64_t *out_off, int32_t *status, const char *what)
+struct dz_job { // the list a downsize call works on, its limits, where its files go (back to back in out[cap], out_off[n + 1]), and its caller
+    const ingest_src *srcs;
+    int64_t n, max_bytes;
+    int max_dim;
+    uint8_t *out;
+    int64_t cap, *out_off;
+    int32_t *status; // may be NULL
+    const char *what;
+};
+
+// One round of the downsizer: the images one slab, one RGB scratch and one encoder batch take, in list order, with the finished results
+// that lie between them.
+struct dz_round {
+    std::vector<dz_entry> E;
+    slab_fill F;
+    int64_t rgb = 0, blocks = 0, coded = 0; // of the images to encode: resized RGB bytes, encoder blocks, their number
+    int64_t finished = 0;                   // bytes of the finished results (passed-through files, whole-on-host outputs) waiting in E
+    std::vector<uint8_t> files[2];          // the coded files of the first / second encoder batch, off[a][slot] .. off[a][slot + 1]
+    std::vector<int64_t> off[2];
+    void reset() { E.clear(), F = slab_fill(), rgb = blocks = coded = finished = 0; }
+    static int64_t rgb_bytes(const dz_result &z) { return align16((int64_t)z.nw * z.nh * 3); }
+    // Does z, next in the list, still belong to this round?  An image to encode needs room in the RGB scratch, the encoder's batch and
+    // (a JPEG for the GPU) the slab; alone it always fits.  A finished result has left the feed's byte budget and waits in E for its turn:
+    // the round ends once it holds 2 * SLAB_PAYLOAD of them, so a long run of small files is delivered as it goes.
+    bool admits(const dz_result &z) const
+    {
+        if (z.type != DZ_GPU && z.type != DZ_HOST) return !(finished > 2 * SLAB_PAYLOAD && !E.empty());
+        const bool room = rgb + rgb_bytes(z) <= DZ_RGB_BUDGET && blocks + icl_jenc_blocks(z.nw, z.nh) <= icl_jenc_max_batch_blocks() && coded < icl_jenc_max_batch_images() &&
+                          (z.type == DZ_HOST || (F.nimg < SLAB_IMAGES && F.fits(z.fr)));
+        return room || rgb == 0;
+    }
+    // whether the GPU entropy check took X's stream (an image entropy-decoded on the host has none)
+    static bool accepted(const icl_ingest_ws *ws, const dz_entry &X) { return X.scan < 0 || ws->h_accepted[X.scan] != 0; }
+};
+
+// Images from the feed, in list order, into round R until dz_round::admits says it is full or the list ends; the JPEGs the GPU rebuilds
+// are placed in the pinned slab S as they come (passed-through, host-decoded and failed images take no slab row).
+static int dz_collect(icl_ctx *ctx, const dz_job &job, ingest_feed<dz_result> &feed, const slab_view &S, dz_round &R)
+{
+    R.reset();
+    slab_fill &F = R.F;
+    while (feed.taken() < job.n) {
+        const dz_result *next = feed.peek();
+        if (!next) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", job.what);
+        if (!R.admits(*next)) break;
+        if (next->type == DZ_GPU || next->type == DZ_HOST) {
+            R.rgb += dz_round::rgb_bytes(*next);
+            R.blocks += icl_jenc_blocks(next->nw, next->nh);
+            ++R.coded;
+        } else {
+            R.finished += (int64_t)next->bytes.size();
+        }
+        dz_entry X;
+        X.row = feed.taken();
+        X.z = feed.take();
+        if (X.z->type == DZ_GPU) {
+            S.clear_row(F.nimg);
+            X.img = F.nimg;
+            X.scan = X.z->fr.kind == KIND_JSTREAM ? F.nscan : -1;
+            if (!place_jpeg(X.z->fr, F, S)) {
+                char nbuf[96];
+                return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", job.what, ingest_src_name(job.srcs[X.row], nbuf, sizeof nbuf));
+            }
+            ++F.nimg;
+        }
+        R.E.push_back(std::move(X));
+    }
+    return ICL_OK;
+}
+
+// The round's slab to its planes (run_slab_decode; the accepted flags of its streams come back with the first encoder batch, which
+// synchronises), every image to encode through the encoder at its new size, then those still above the limit, whose stream was accepted
+// and that can still be halved, through it again at half that size from the planes still held.  ev_up: recorded behind the slab's upload.
+static int dz_rebuild(icl_ctx *ctx, icl_ingest_ws *ws, dz_ws &B, const slab_view &S, hipEvent_t ev_up, int64_t max_bytes, dz_round &R)
+{
+    std::vector<int> first, second;
+    for (size_t e = 0; e < R.E.size(); ++e)
+        if (R.E[e].z->type == DZ_GPU || R.E[e].z->type == DZ_HOST) first.push_back((int)e);
+    if (R.F.nimg) {
+        int64_t upload = 0;
+        ICL_TRY(run_slab_decode(ctx, ws, S, R.F, upload));
+        ICL_HIP(ctx, hipEventRecord(ev_up, ctx->stream));
+        if (R.F.nscan) ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, (size_t)R.F.nscan * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (!first.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, R.E, first, 0, R.files[0], R.off[0])); // (synchronises: h_accepted is there)
+    for (int e : first) {
+        const dz_entry &X = R.E[(size_t)e];
+        const int64_t len = R.off[0][(size_t)X.slot[0] + 1] - R.off[0][(size_t)X.slot[0]];
+        if (dz_round::accepted(ws, X) && len > max_bytes && X.z->nw / 2 >= 1 && X.z->nh / 2 >= 1) second.push_back(e);
+    }
+    if (!second.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, R.E, second, 1, R.files[1], R.off[1]));
+    return ICL_OK;
+}
+
+// The round's results in list order into the caller's buffer: a passed-through source as it stands, a coded file from the batch of its
+// last attempt, a finished file, nothing for a failed image.  An image whose stream the GPU entropy check rejected is redone here by the
+// host call, which also reports what it finds.  Statuses, failures and the call's totals (tot.bytes_out is where the next file goes).
+static void dz_deliver(const icl_ingest_ws *ws, const dz_job &job, dz_round &R, std::vector<file_fail> &fails, dz_totals &tot)
+{
+    auto deliver = [&](int64_t row, const uint8_t *p, int64_t len) {
+        job.out_off[row] = tot.bytes_out;
+        if (job.out && len && tot.bytes_out + len <= job.cap) memcpy(job.out + tot.bytes_out, p, (size_t)len);
+        tot.bytes_out += len;
+    };
+    for (dz_entry &X : R.E) {
+        dz_result &z = *X.z;
+        tot.bytes_in += z.in_bytes;
+        if (z.type == DZ_GPU && !dz_round::accepted(ws, X)) {
+            int32_t info[6];
+            const int rc = icl_downsize_src(job.srcs[X.row], job.max_bytes, job.max_dim, z.bytes, info);
+            if (rc) {
+                z.type = DZ_FAILED;
+                fail_from_tls(z.fr, rc);
+            } else {
+                z.type = DZ_DONE;
+                z.attempts = info[5];
+            }
+        }
+        if (job.status) job.status[X.row] = z.type == DZ_FAILED ? (z.fr.rc ? z.fr.rc : ICL_ERR_IO) : ICL_OK;
+        switch (z.type) {
+        case DZ_PASS: {
+            const ingest_src &s = job.srcs[X.row];
+            deliver(X.row, s.path ? z.bytes.data() : s.data, z.in_bytes);
+            ++tot.passthrough;
+            break;
+        }
+        case DZ_DONE:
+            deliver(X.row, z.bytes.data(), (int64_t)z.bytes.size());
+            ++tot.host_decoded;
+            tot.second_attempts += z.attempts == 2;
+            break;
+        case DZ_GPU:
+        case DZ_HOST: {
+            const int a = X.slot[1] >= 0 ? 1 : 0;
+            const int64_t lo = R.off[a][(size_t)X.slot[a]], hi = R.off[a][(size_t)X.slot[a] + 1];
+            deliver(X.row, R.files[a].data() + lo, hi - lo);
+            (z.type == DZ_GPU ? tot.gpu_rebuilt : tot.host_decoded) += 1;
+            tot.second_attempts += a;
+            break;
+        }
+        default:
+            deliver(X.row, nullptr, 0);
+            fails.push_back(file_fail{X.row, z.fr.rc ? z.fr.rc : ICL_ERR_IO, z.fr.err});
+            break;
+        }
+    }
+}
+
+// The downsizer's driver: worker threads run dz_process over the list (at most two slabs' worth of images and bytes ahead), this thread
+// runs the rounds in list order, double-buffered in the pinned slabs, with everything on ctx->stream.
+static int downsize_images_locked(icl_ctx *ctx, const dz_job &job, int32_t threads)
 {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    for (int q = 0; q < 6; ++q) ctx->downsize_stats[q] = 0;
-    ctx->downsize_ms[0] = ctx->downsize_ms[1] = ctx->downsize_ms[2] = 0;
-    out_off[0] = 0;
-    if (n == 0) return ICL_OK;
+    ctx->downsize_last = dz_totals();
+    job.out_off[0] = 0;
+    if (job.n == 0) return ICL_OK;
     const int entropy = ctx->entropy_mode;
     icl_ingest_ws *ws = nullptr;
     ICL_TRY(ingest_ws(ctx, ws));
     if (entropy == ICL_ENTROPY_GPU) ICL_TRY(entropy_ws(ctx, ws, SLAB_IMAGES));
     dz_ws B;
-    int64_t at = 0, npass = 0, ngpu = 0, nhost = 0, nsecond = 0, bytes_in = 0;
+    dz_totals tot;
     std::vector<file_fail> fails;
-    auto deliver = [&](int64_t row, const uint8_t *p, int64_t len) {
-        out_off[row] = at;
-        if (out && len && at + len <= cap) memcpy(out + at, p, (size_t)len);
-        at += len;
-    };
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(n, threads > 0 ? threads : (int)std::min(16u, hw)));
-    std::atomic<int64_t> decode_ns{0};
-    auto decode = [&](int64_t i) -> std::unique_ptr<dz_result> {
-        thread_local std::unique_ptr<worker_state> wst(new (std::nothrow) worker_state());
-        const auto t0 = clk::now();
-        std::unique_ptr<dz_result> z(wst ? new (std::nothrow) dz_result() : nullptr);
-        if (z) dz_process(srcs[i], *wst, entropy, max_bytes, max_dim, *z);
-        decode_ns += (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(clk::now() - t0).count();
-        return z;
-    };
+    feed_worker<dz_result> work{[&](int64_t i, worker_state &wst, dz_result &z) { dz_process(job.srcs[i], wst, entropy, job.max_bytes, job.max_dim, z); }};
     {
-        ingest_feed<dz_result> feed(n, nthr, 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, decode, [](const dz_result &z) { return z.held(); });
-        std::vector<dz_entry> E;
-        std::vector<uint8_t> files[2];
-        std::vector<int64_t> off[2];
-        for (int64_t k = 0; feed.taken() < n; ++k) {
+        ingest_feed<dz_result> feed(job.n, worker_count(job.n, threads), 2 * SLAB_IMAGES, 2 * SLAB_PAYLOAD, std::ref(work), [](const dz_result &z) { return z.held(); });
+        dz_round R;
+        for (int64_t k = 0; feed.taken() < job.n; ++k) {
             const int q = (int)(k & 1);
-            ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[q]));
+            ICL_HIP(ctx, hipEventSynchronize(ws->ev_up[q])); // the upload that last read this slab has finished
             const slab_view S = ws->host(q);
-            slab_fill F;
-            E.clear();
-            int64_t rgb = 0, blocks = 0, coded = 0, finished = 0;
-            // ---- collect: images in list order until the slab, the RGB scratch or the encoder's batch is full.  Finished results
-            // (passed-through files, whole-on-host outputs) leave the feed's byte budget when they are taken and wait in E for their
-            // turn: a round ends once it holds 2 * SLAB_PAYLOAD of them, so a long run of small files is delivered as it goes ----
-            while (feed.taken() < n) {
-                const dz_result *next = feed.peek();
-                if (!next) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: out of host memory", what);
-                if (next->type == DZ_GPU || next->type == DZ_HOST) {
-                    const int64_t r3 = align16((int64_t)next->nw * next->nh * 3), nb = icl_jenc_blocks(next->nw, next->nh);
-                    const bool room = rgb + r3 <= DZ_RGB_BUDGET && blocks + nb <= icl_jenc_max_batch_blocks() && coded < icl_jenc_max_batch_images() &&
-                                      (next->type == DZ_HOST || (F.nimg < SLAB_IMAGES && F.fits(next->fr)));
-                    if (!room && rgb > 0) break;
-                    rgb += r3;
-                    blocks += nb;
-                    ++coded;
-                } else {
-                    if (finished > 2 * SLAB_PAYLOAD && !E.empty()) break;
-                    finished += (int64_t)next->bytes.size();
-                }
-                dz_entry X;
-                X.row = feed.taken();
-                X.z = feed.take();
-                if (X.z->type == DZ_GPU) {
-                    memset(&S.imgs[F.nimg], 0, offsetof(ingest_image, xofs));
-                    X.img = F.nimg;
-                    X.scan = X.z->fr.kind == KIND_JSTREAM ? F.nscan : -1;
-                    if (!place_jpeg(X.z->fr, F, S)) {
-                        char nbuf[96];
-                        return icl_fail(ctx, ICL_ERR_IO, "%s: inconsistent JPEG geometry for %s", what, ingest_src_name(srcs[X.row], nbuf, sizeof nbuf));
-                    }
-                    ++F.nimg;
-                }
-                E.push_back(std::move(X));
-            }
-            // ---- planes, first attempt, second attempt ----
+            ICL_TRY(dz_collect(ctx, job, feed, S, R));
             const auto t_gpu = clk::now();
-            std::vector<int> first, second;
-            for (size_t e = 0; e < E.size(); ++e)
-                if (E[e].z->type == DZ_GPU || E[e].z->type == DZ_HOST) first.push_back((int)e);
-            if (F.nimg) {
-                int64_t upload = 0;
-                ICL_TRY(run_slab_decode(ctx, ws, S, F, upload));
-                ICL_HIP(ctx, hipEventRecord(ws->ev_up[q], ctx->stream));
-                if (F.nscan) ICL_HIP(ctx, hipMemcpyAsync(ws->h_accepted, ws->d_accepted, (size_t)F.nscan * 4, hipMemcpyDeviceToHost, ctx->stream));
-            }
-            if (!first.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, E, first, 0, files[0], off[0])); // (synchronises: h_accepted is there)
-            auto accepted = [&](const dz_entry &X) { return X.scan < 0 || ws->h_accepted[X.scan] != 0; };
-            for (int e : first) {
-                const dz_entry &X = E[(size_t)e];
-                const int64_t len = off[0][(size_t)X.slot[0] + 1] - off[0][(size_t)X.slot[0]];
-                if (accepted(X) && len > max_bytes && X.z->nw / 2 >= 1 && X.z->nh / 2 >= 1) second.push_back(e);
-            }
-            if (!second.empty()) ICL_TRY(dz_encode_pass(ctx, ws, B, E, second, 1, files[1], off[1]));
-            ctx->downsize_ms[1] += ms_since(t_gpu);
-            // ---- deliver in list order ----
+            ICL_TRY(dz_rebuild(ctx, ws, B, S, ws->ev_up[q], job.max_bytes, R));
+            tot.gpu_ms += ms_since(t_gpu);
             const auto t_out = clk::now();
-            for (dz_entry &X : E) {
-                dz_result &z = *X.z;
-                bytes_in += z.in_bytes;
-                if (status) status[X.row] = z.type == DZ_FAILED ? (z.fr.rc ? z.fr.rc : ICL_ERR_IO) : ICL_OK;
-                if (z.type == DZ_GPU && !accepted(X)) { // the GPU entropy check rejected its stream: the host call redoes it and reports what it finds
-                    int32_t info[6];
-                    const int rc = icl_downsize_src(srcs[X.row], max_bytes, max_dim, z.bytes, info);
-                    if (rc) {
-                        z.type = DZ_FAILED;
-                        z.fr.rc = rc;
-                        z.fr.err = icl_last_error(nullptr);
-                        if (status) status[X.row] = rc;
-                    } else {
-                        z.type = DZ_DONE;
-                        z.attempts = info[5];
-                    }
-                }
-                switch (z.type) {
-                case DZ_PASS: {
-                    const ingest_src &s = srcs[X.row];
-                    deliver(X.row, s.path ? z.bytes.data() : s.data, z.in_bytes);
-                    ++npass;
-                    break;
-                }
-                case DZ_DONE:
-                    deliver(X.row, z.bytes.data(), (int64_t)z.bytes.size());
-                    ++nhost;
-                    nsecond += z.attempts == 2;
-                    break;
-                case DZ_GPU:
-                case DZ_HOST: {
-                    const int a = X.slot[1] >= 0 ? 1 : 0;
-                    const int64_t lo = off[a][(size_t)X.slot[a]], hi = off[a][(size_t)X.slot[a] + 1];
-                    deliver(X.row, files[a].data() + lo, hi - lo);
-                    (z.type == DZ_GPU ? ngpu : nhost) += 1;
-                    nsecond += a;
-                    break;
-                }
-                default:
-                    deliver(X.row, nullptr, 0);
-                    fails.push_back(file_fail{X.row, z.fr.rc ? z.fr.rc : ICL_ERR_IO, z.fr.err});
-                    break;
-                }
-            }
-            ctx->downsize_ms[2] += ms_since(t_out);
+            dz_deliver(ws, job, R, fails, tot);
+            tot.out_ms += ms_since(t_out);
         }
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    out_off[n] = at;
-    ctx->downsize_stats[0] = npass;
-    ctx->downsize_stats[1] = ngpu;
-    ctx->downsize_stats[2] = nhost;
-    ctx->downsize_stats[3] = nsecond;
-    ctx->downsize_stats[4] = bytes_in;
-    ctx->downsize_stats[5] = at;
-    ctx->downsize_ms[0] = (double)decode_ns.load() * 1e-6;
-    if (!out || at > cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small (%lld bytes needed)", what, (long long)at);
-    const file_fail *lowest = nullptr;
-    for (const file_fail &f : fails)
-        if (!lowest || f.index < lowest->index) lowest = &f;
-    if (lowest) return icl_fail(ctx, lowest->rc, "%s: file %lld of %lld: %s", what, (long long)lowest->index, (long long)n, lowest->err.c_str());
-    return ICL_OK;
+    } // (the feed has joined its workers: decode_ns is complete)
+    tot.decode_ns = work.decode_ns.load();
+    job.out_off[job.n] = tot.bytes_out;
+    ctx->downsize_last = tot;
+    if (!job.out || tot.bytes_out > job.cap) return icl_fail(ctx, ICL_ERR_ARG, "%s: buffer too small (%lld bytes needed)", job.what, (long long)tot.bytes_out);
+    return report_lowest(ctx, fails, job.n, job.what, nullptr);
 }
 
 } // namespace
 
-static int downsize_images(icl_ctx *ctx, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, int64_t n, int64_t max_bytes,
-                           int32_t max_dim, int32_t threads, uint8_t *out, int64_t cap, int64_t *out_off, int32_t *status, const char *what)
+static int downsize_images(icl_ctx *ctx, const ingest_list &imgs, int64_t max_bytes, int32_t max_dim, int32_t threads, uint8_t *out, int64_t cap, int64_t *out_off,
+                           int32_t *status, const char *what)
 {
-    if (!ctx || n < 0 || !out_off || cap < 0 || max_bytes < 0 || max_dim < 1 || threads < 0 || (mem ? !mem_list_ok(data, bytes, n) : (n && !paths)))
-        return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
-    for (int64_t i = 0; !mem && i < n; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    const int64_t bad = imgs.first_bad();
+    if (!ctx || bad == ingest_list::NO_ARRAYS || !out_off || cap < 0 || max_bytes < 0 || max_dim < 1 || threads < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: bad argument", what);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return no_throw(ctx, what, [&]() -> int {
-        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, n) : ingest_path_srcs(paths, n);
-        return downsize_images_locked(ctx, srcs.data(), n, max_bytes, max_dim, threads, out, cap, out_off, status, what);
+        const std::vector<ingest_src> srcs = imgs.srcs();
+        return downsize_images_locked(ctx, dz_job{srcs.data(), imgs.n, max_bytes, max_dim, out, cap, out_off, status, what}, threads);
     });
 }
 
 extern "C" int icl_downsize_images(icl_ctx *ctx, const char *const *paths, int64_t n, int64_t max_bytes, int32_t max_dim, int32_t threads, uint8_t *out, int64_t cap,
                                    int64_t *out_off, int32_t *status)
 {
-    return downsize_images(ctx, false, paths, nullptr, nullptr, n, max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images");
+    return downsize_images(ctx, ingest_list::files(paths, n), max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images");
 }
 
 extern "C" int icl_downsize_images_mem(icl_ctx *ctx, const uint8_t *const *data, const int64_t *bytes, int64_t n, int64_t max_bytes, int32_t max_dim, int32_t threads,
                                        uint8_t *out, int64_t cap, int64_t *out_off, int32_t *status)
 {
-    return downsize_images(ctx, true, nullptr, data, bytes, n, max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images_mem");
+    return downsize_images(ctx, ingest_list::memory(data, bytes, n), max_bytes, max_dim, threads, out, cap, out_off, status, "icl_downsize_images_mem");
 }
 
 extern "C" int icl_last_downsize_stats(icl_ctx *ctx, int64_t *passthrough, int64_t *gpu_rebuilt, int64_t *host_decoded, int64_t *second_attempts, int64_t *bytes_in,
@@ -1702,9 +1734,13 @@ extern "C" int icl_last_downsize_stats(icl_ctx *ctx, int64_t *passthrough, int64
 {
     if (!ctx) return ICL_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int64_t *dst[6] = {passthrough, gpu_rebuilt, host_decoded, second_attempts, bytes_in, bytes_out};
-    for (int q = 0; q < 6; ++q)
-        if (dst[q]) *dst[q] = ctx->downsize_stats[q];
-    for (int q = 0; q < 3 && stage_ms; ++q) stage_ms[q] = ctx->downsize_ms[q];
+    const dz_totals &t = ctx->downsize_last;
+    if (passthrough) *passthrough = t.passthrough;
+    if (gpu_rebuilt) *gpu_rebuilt = t.gpu_rebuilt;
+    if (host_decoded) *host_decoded = t.host_decoded;
+    if (second_attempts) *second_attempts = t.second_attempts;
+    if (bytes_in) *bytes_in = t.bytes_in;
+    if (bytes_out) *bytes_out = t.bytes_out;
+    if (stage_ms) stage_ms[0] = (double)t.decode_ns * 1e-6, stage_ms[1] = t.gpu_ms, stage_ms[2] = t.out_ms;
     return ICL_OK;
 }

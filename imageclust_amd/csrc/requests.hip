@@ -118,9 +118,9 @@ extern "C" int icl_requests_layout(int32_t nreq, const int32_t *n, const int32_t
     return ICL_OK;
 }
 
-// what ICL_ERR_ARG covers: nothing is written when it fails.  The images are files (paths) or, for icl_cluster_requests_mem, memory
-// sources (mem; data, bytes: an empty or NULL entry is that image's own failure, a null array the call's).
-static int rq_check_args(icl_ctx *ctx, const char *what, int32_t nreq, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, const int32_t *n, const int32_t *n_labels, const int64_t *label_off,
+// what ICL_ERR_ARG covers: nothing is written when it fails.  The images (imgs: files or, for icl_cluster_requests_mem, memory sources)
+// number the sum of n[]: imgs.n is set here, once n[] has been checked.
+static int rq_check_args(icl_ctx *ctx, const char *what, int32_t nreq, ingest_list &imgs, const int32_t *n, const int32_t *n_labels, const int64_t *label_off,
                          const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head, int prec, int32_t threads,
                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *status)
 {
@@ -139,10 +139,11 @@ static int rq_check_args(icl_ctx *ctx, const char *what, int32_t nreq, bool mem,
         rows += n[r];
     }
     if (rows >= ((int64_t)1 << 30)) return icl_fail(ctx, ICL_ERR_ARG, "%s: %lld images in all", what, (long long)rows);
-    if (rows && mem && (!data || !bytes || !cluster_id || !member_rank)) return icl_fail(ctx, ICL_ERR_ARG, "%s: null data / bytes / cluster_id / member_rank", what);
-    if (rows && !mem && (!paths || !cluster_id || !member_rank)) return icl_fail(ctx, ICL_ERR_ARG, "%s: null paths / cluster_id / member_rank", what);
-    for (int64_t i = 0; !mem && i < rows; ++i)
-        if (!paths[i]) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)i);
+    imgs.n = rows;
+    const int64_t bad = imgs.first_bad();
+    if (rows && (bad == ingest_list::NO_ARRAYS || !cluster_id || !member_rank))
+        return icl_fail(ctx, ICL_ERR_ARG, imgs.mem ? "%s: null data / bytes / cluster_id / member_rank" : "%s: null paths / cluster_id / member_rank", what);
+    if (bad >= 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: paths[%lld] is NULL", what, (long long)bad);
     if (label_off[0] < 0) return icl_fail(ctx, ICL_ERR_ARG, "%s: label_off[0] is %lld", what, (long long)label_off[0]);
     for (int64_t i = 0; i < rows; ++i)
         if (label_off[i + 1] < label_off[i])
@@ -279,14 +280,14 @@ static int cluster_requests_locked(icl_ctx *ctx, const char *what, int32_t nreq,
     return ICL_OK;
 }
 
-// both entry points: paths, or (mem) data / bytes
-static int cluster_requests(icl_ctx *ctx, const char *what, int32_t nreq, bool mem, const char *const *paths, const uint8_t *const *data, const int64_t *bytes, const int32_t *n,
+// both entry points (imgs: the caller's arrays; its n is found by the argument check)
+static int cluster_requests(icl_ctx *ctx, const char *what, int32_t nreq, ingest_list &imgs, const int32_t *n,
                             const int32_t *n_labels, const int64_t *label_off, const int32_t *label_idx, const int32_t *min_size, const int32_t *max_size, int head,
                             int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges,
                             int32_t *status, int32_t *file_status, float *E_out)
 {
     return no_throw(ctx, what, [&]() -> int {
-        ICL_TRY(rq_check_args(ctx, what, nreq, mem, paths, data, bytes, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
+        ICL_TRY(rq_check_args(ctx, what, nreq, imgs, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
                               member_rank, n_clusters, n_merges, status));
         std::lock_guard<std::mutex> lk(ctx->mu);
         icl_device_guard g(ctx->device);
@@ -295,9 +296,7 @@ static int cluster_requests(icl_ctx *ctx, const char *what, int32_t nreq, bool m
         ctx->many_stats[0] = ctx->many_stats[1] = ctx->many_stats[2] = ctx->many_stats[3] = 0;
         ctx->requests_ms[0] = ctx->requests_ms[1] = ctx->requests_ms[2] = 0;
         if (nreq == 0) return ICL_OK;
-        int64_t rows = 0;
-        for (int32_t r = 0; r < nreq; ++r) rows += n[r];
-        const std::vector<ingest_src> srcs = mem ? ingest_mem_srcs(data, bytes, rows) : ingest_path_srcs(paths, rows);
+        const std::vector<ingest_src> srcs = imgs.srcs();
         return cluster_requests_locked(ctx, what, nreq, srcs.data(), n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads, cluster_id,
                                        member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
     });
@@ -308,7 +307,8 @@ extern "C" int icl_cluster_requests(icl_ctx *ctx, int32_t nreq, const char *cons
                                     int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
                                     int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
 {
-    return cluster_requests(ctx, "icl_cluster_requests", nreq, false, paths, nullptr, nullptr, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
+    ingest_list imgs = ingest_list::files(paths, 0);
+    return cluster_requests(ctx, "icl_cluster_requests", nreq, imgs, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
                             cluster_id, member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
 }
 
@@ -317,7 +317,8 @@ extern "C" int icl_cluster_requests_mem(icl_ctx *ctx, int32_t nreq, const uint8_
                                         int prec, int32_t threads, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges,
                                         int32_t *merges, int32_t *status, int32_t *file_status, float *E_out)
 {
-    return cluster_requests(ctx, "icl_cluster_requests_mem", nreq, true, nullptr, data, bytes, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
+    ingest_list imgs = ingest_list::memory(data, bytes, 0);
+    return cluster_requests(ctx, "icl_cluster_requests_mem", nreq, imgs, n, n_labels, label_off, label_idx, min_size, max_size, head, prec, threads,
                             cluster_id, member_rank, n_clusters, n_merges, merges, status, file_status, E_out);
 }
 
