@@ -364,3 +364,18 @@ func ResumeClustering(centroids [][]float32, sizes []int32, minSize, maxSize, kT
 	}
 	return res[0], true
 }
+
+// NearestClusters answers, before ResumeClustering is asked to recluster: for each query cluster (a new image is a cluster of size 1
+// with its embedding; nil qSizes: all singletons) which of the existing clusters are closest in the loop's own cost, and by how much
+// (iclengine.Nearest -> icl_nearest: WardDistance of :136-157 bit for bit, no distance matrix).  maxSize > 0 leaves out the clusters
+// the loop would refuse to merge the query with (:228).  idx[i] lists up to k positions in `clusters`, nearest first, ties by
+// position; a row with fewer than k candidates ends in -1 (val MaxFloat32).
+func NearestClusters(queries [][]float32, qSizes []int32, clusters []Cluster, k, maxSize int) (idx [][]int32, val [][]float32, err error) {
+	centroids := make([][]float32, len(clusters))
+	sizes := make([]int32, len(clusters))
+	for i, c := range clusters {
+		centroids[i] = c.Centroid
+		sizes[i] = int32(c.Size)
+	}
+	return iclengine.Nearest(queries, qSizes, centroids, sizes, k, maxSize, nil)
+}

@@ -261,6 +261,60 @@ func ClusterSeeded(pr SeededProblem) (SeededResult, error) {
 	return r, nil
 }
 
+// Nearest is icl_nearest: for each query cluster (queries[i], qSizes[i] items; nil sizes: all 1) the k library clusters (library[j],
+// eSizes[j]) of smallest WardDistance, the reference's values bit for bit, ascending by (value, j), NaN last.  exclude (nil: none)
+// names a column per query that is skipped (-1: none; a self-join passes i); maxSize > 0 leaves out the pairs whose sizes add up to
+// more.  idx and val hold k entries per query; a short row ends in idx -1, val MaxFloat32.  No distance matrix is built.
+func Nearest(queries [][]float32, qSizes []int32, library [][]float32, eSizes []int32, k, maxSize int, exclude []int64) (idx [][]int32, val [][]float32, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, nil, e
+	}
+	nq, n, d := len(queries), len(library), 0
+	if nq > 0 {
+		d = len(queries[0])
+	} else if n > 0 {
+		d = len(library[0])
+	}
+	if (qSizes != nil && len(qSizes) != nq) || (eSizes != nil && len(eSizes) != n) || (exclude != nil && len(exclude) != nq) {
+		return nil, nil, fmt.Errorf("sizes or exclude do not match %d queries and %d library rows", nq, n)
+	}
+	if k < 1 {
+		return nil, nil, fmt.Errorf("k must be 1 .. 64, got %d", k)
+	}
+	flatQ := make([]float32, nq*d+1) // [][]float32 cannot cross cgo: one contiguous buffer each
+	flatE := make([]float32, n*d+1)
+	for i, row := range queries {
+		copy(flatQ[i*d:(i+1)*d], row)
+	}
+	for j, row := range library {
+		copy(flatE[j*d:(j+1)*d], row)
+	}
+	fi := make([]int32, nq*k+1)
+	fv := make([]float32, nq*k+1)
+	i32 := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	var ex *C.int64_t
+	if len(exclude) > 0 {
+		ex = (*C.int64_t)(unsafe.Pointer(&exclude[0]))
+	}
+	if rc := C.icl_nearest((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flatQ[0])), i32(qSizes), C.int64_t(nq),
+		(*C.float)(unsafe.Pointer(&flatE[0])), i32(eSizes), C.int64_t(n), C.int32_t(d), C.int32_t(k), C.int32_t(maxSize), ex,
+		(*C.int32_t)(unsafe.Pointer(&fi[0])), (*C.float)(unsafe.Pointer(&fv[0]))); rc != C.ICL_OK {
+		return nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	idx, val = make([][]int32, nq), make([][]float32, nq)
+	for i := range idx {
+		idx[i] = fi[i*k : (i+1)*k : (i+1)*k]
+		val[i] = fv[i*k : (i+1)*k : (i+1)*k]
+	}
+	return idx, val, nil
+}
+
 // Where a qualifying PNG of the batched file calls is inflated and unfiltered: icl_set_png_options' modes.
 const (
 	PNGHost = int(C.ICL_PNG_HOST)

@@ -139,6 +139,11 @@ SYMBOLS = [
     ("icl_cluster_seeded", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
+    ("icl_nearest", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("icl_nearest_dev", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("icl_nearest_from_matrix", _int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    ("icl_set_nearest_options", _int, [_vp, _i32]),
+    ("icl_last_nearest_stats", _int, [_vp, _pi64]),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_requests_layout", _int, [_i32, _vp, _vp, _int, _vp, _vp, _pi64]),
@@ -233,6 +238,45 @@ def pack_many(problems):
     return dict(E=buf, e_off=np.array(off, np.int64), n=n, d=np.array([E.shape[1] for E in mats], np.int32),
                 min_size=np.array([int(p[1]) for p in problems], np.int32), max_size=np.array([int(p[2]) for p in problems], np.int32),
                 img_off=np.concatenate([[0], np.cumsum(n, dtype=np.int64)]))
+
+
+def _nearest_side(n, size, what):
+    """A size array of icl_nearest as contiguous int32[n], or None."""
+    if size is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(size).reshape(-1), np.int32)
+    if len(a) != n:
+        raise ValueError("%d %s entries for %d rows" % (len(a), what, n))
+    return a
+
+
+def _nearest_exclude(nq, exclude):
+    if exclude is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(exclude).reshape(-1), np.int64)
+    if len(a) != nq:
+        raise ValueError("%d exclude entries for %d query rows" % (len(a), nq))
+    return a
+
+
+def nearest_from_matrix(D, k, q_size=None, e_size=None, max_size=0, exclude=None, n=None):
+    """icl_nearest_from_matrix (host only, no GPU): the leave-out and order rules of Context.nearest applied to values the caller holds ->
+    (idx int32[nq][k], val float32[nq][k]).  D is nq x ld float32; n (default ld) columns of each row are pairs.  Raises ICLError(ICL_ERR_ARG)."""
+    D = np.asarray(D, np.float32)
+    if D.ndim != 2:
+        raise ValueError("D must be 2-D")
+    if not D.flags.c_contiguous:
+        D = np.ascontiguousarray(D)
+    nq, ld = D.shape
+    n = ld if n is None else int(n)
+    qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
+    kk = max(int(k), 1)
+    idx, val = np.empty((nq, kk), np.int32), np.empty((nq, kk), np.float32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    rc = load().icl_nearest_from_matrix(ptr(D), nq, n, ld, ptr(qs), ptr(es), int(k), int(max_size), ptr(ex), idx.ctypes.data, val.ctypes.data)
+    if rc != ICL_OK:
+        raise ICLError(rc, "icl_nearest_from_matrix: bad argument")
+    return idx, val
 
 
 def _byte_view(buf):
@@ -797,6 +841,60 @@ class Context:
             sp = sizes.ctypes.data
         check(self.h, self.L.icl_ward_distance_matrix(self.h, Cm.ctypes.data, sp, n, d, D.ctypes.data, n))
         return D
+
+    def nearest(self, Q, E, k, q_size=None, e_size=None, max_size=0, exclude=None, dev=False):
+        """icl_nearest: for each row of Q the k rows of E of smallest WardDistance (sizes q_size / e_size, None: all 1), bit for bit the
+        reference's values, ascending by (value, j), NaN last -> (idx int32[nq][k], val float32[nq][k]); short rows end in idx -1, val
+        MaxFloat32.  exclude[i] (-1: none) names a column row i skips (a self-join passes arange(n)); max_size > 0 leaves out every pair
+        whose sizes add up to more.  dev=True runs icl_nearest_dev on device copies instead of the host entry point."""
+        Qm, Em = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(E, np.float32)
+        if Qm.ndim != 2 or Em.ndim != 2 or Qm.shape[1] != Em.shape[1]:
+            raise ValueError("Q and E must be 2-D with rows of one length, got %s and %s" % (Qm.shape, Em.shape))
+        (nq, d), n = Qm.shape, Em.shape[0]
+        qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
+        kk = max(int(k), 1)
+        idx, val = np.empty((nq, kk), np.int32), np.empty((nq, kk), np.float32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        if not dev:
+            check(self.h, self.L.icl_nearest(self.h, ptr(Qm), ptr(qs), nq, ptr(Em), ptr(es), n, d, int(k), int(max_size), ptr(ex),
+                                             idx.ctypes.data, val.ctypes.data))
+            return idx, val
+        bufs = []
+        try:
+            for a in (Qm, Em, idx, val):
+                bufs.append(self.malloc(max(a.nbytes, 16)))
+            if Qm.size:
+                self.h2d(bufs[0], Qm)
+            if Em.size:
+                self.h2d(bufs[1], Em)
+            self.nearest_dev(bufs[0], nq, bufs[1], n, d, k, bufs[2], bufs[3], qs, es, max_size, ex)
+            if idx.size:
+                self.d2h(idx, bufs[2])
+                self.d2h(val, bufs[3])
+        finally:
+            for p in bufs:
+                self.free(p)
+        return idx, val
+
+    def nearest_dev(self, d_Q, nq, d_E, n, d, k, d_idx, d_val, q_size=None, e_size=None, max_size=0, exclude=None):
+        """icl_nearest_dev: Q (nq x d), E (n x d), idx and val (nq x k) are device pointers; q_size, e_size and exclude host arrays
+        or None.  Enqueued on the context's stream: sync() before reading the outputs through another stream."""
+        qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
+        check(self.h, self.L.icl_nearest_dev(self.h, as_vp(d_Q), ptr(qs), nq, as_vp(d_E), ptr(es), n, d, int(k), int(max_size), ptr(ex),
+                                             as_vp(d_idx), as_vp(d_val)))
+
+    def set_nearest_options(self, column_splits=0):
+        """icl_set_nearest_options: workgroups per band of 128 query rows the library's column tiles are split over (0: the engine decides
+        from nq, n and the CU count).  Same results for every count."""
+        check(self.h, self.L.icl_set_nearest_options(self.h, int(column_splits)))
+
+    def last_nearest_stats(self):
+        """The last nearest[_dev]: column splits used, 128 x 128 tiles run, pairs evaluated, workspace bytes."""
+        info = (C.c_int64 * 4)()
+        check(self.h, self.L.icl_last_nearest_stats(self.h, info))
+        return {"splits": info[0], "tiles": info[1], "pairs": info[2], "workspace_bytes": info[3]}
 
     def merge_centroid(self, ca, sa, cb, sb):
         ca = np.ascontiguousarray(ca, np.float32)

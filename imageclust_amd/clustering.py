@@ -188,6 +188,35 @@ def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_targ
     return (cid, rank, nc, mg, co), True
 
 
+def NearestClusters(queries, q_sizes, centroids, sizes, k: int, maxSize: int = 0, ctx: Optional[_lib.Context] = None):
+    """For each query cluster (centroid queries[i], q_sizes[i] items; None: singletons) the up to k clusters of (centroids, sizes) that are
+    closest in the loop's own cost (icl_nearest): WardDistance of clustering.go:136-157 bit for bit, ascending by (value, index).  maxSize > 0
+    leaves out the pairs the loop would ban (:228) -> (idx int32[nq][k], val float32[nq][k]); a short row ends in idx -1, val MaxFloat32."""
+    ctx = ctx or default_context()
+    return ctx.nearest(queries, centroids, k, q_size=q_sizes, e_size=sizes, max_size=maxSize)
+
+
+def NearDuplicates(embeddings, ids, k: int, threshold: float, ctx: Optional[_lib.Context] = None) -> List[Tuple[str, str, float]]:
+    """Pairs of images whose WardDistance as singletons is at most threshold, from a self-join of the embeddings (icl_nearest with
+    exclude[i] = i, the k nearest of every image) -> [(id_a, id_b, value), ...], a before b in `ids`, each pair once, ordered by position.
+    An image with more than k neighbours under the threshold reports its k nearest; a pair is reported when either side lists it."""
+    ctx = ctx or default_context()
+    E = np.asarray(embeddings, np.float32)
+    if E.ndim != 2:
+        E = E.reshape(len(ids), -1)
+    if len(E) != len(ids):
+        raise ValueError("%d embeddings for %d ids" % (len(E), len(ids)))
+    if len(E) == 0:
+        return []
+    idx, val = ctx.nearest(E, E, k, exclude=np.arange(len(E), dtype=np.int64))
+    found: Dict[Tuple[int, int], float] = {}
+    for i in range(len(E)):
+        for j, v in zip(idx[i], val[i]):
+            if j >= 0 and v <= threshold:  # (NaN fails the comparison)
+                found.setdefault((min(i, int(j)), max(i, int(j))), float(v))
+    return [(ids[a], ids[b], v) for (a, b), v in sorted(found.items())]
+
+
 @dataclass
 class HeldCluster:
     """A cluster a Clustering state holds between calls: member ids in the reference's order, the centroid as the loop left it, the
@@ -209,21 +238,21 @@ class Clustering:
         state.as_map()
 
     `engine` replaces the GPU call in tests: engine(C, seed_size, minSize, maxSize, k_target) -> (cluster_id, seed_rank, n_clusters,
-    status, merges, C_out)."""
+    status, merges, C_out); `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val)."""
 
-    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None):
+    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None):
         self.minSize, self.maxSize = int(minSize), int(maxSize)
-        self.ctx, self.engine = ctx, engine
+        self.ctx, self.engine, self.nearest_engine = ctx, engine, nearest_engine
         self.clusters: List[HeldCluster] = []
         self.embeddings: Dict[str, np.ndarray] = {}
         self.ok = True
         self.last_merges = np.zeros((0, 2), np.int32)
 
     @classmethod
-    def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None) -> "Clustering":
+    def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None) -> "Clustering":
         """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
         False (and every image is still a singleton) when the constraints cannot be met."""
-        state = cls(minSize, maxSize, ctx, engine)
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine)
         state.add(embeddings, ids)
         state.recluster()
         return state
@@ -294,6 +323,25 @@ class Clustering:
         self.clusters = held
         self.last_merges = np.asarray(mg, np.int32).reshape(-1, 2).copy()
         return True
+
+    def nearest(self, embeddings, k: int) -> List[List[Tuple[str, float]]]:
+        """Where add() + recluster() could put new images: for each embedding, taken as a singleton, the up to k held clusters that could
+        take it, nearest first, as (the cluster's first member's id, WardDistance).  Frozen clusters are left out, and so are clusters
+        a new item would push above maxSize (icl_nearest's max_size rule).  The state is not changed."""
+        Q = np.asarray(embeddings, np.float32)
+        if Q.ndim != 2:
+            Q = Q.reshape(len(embeddings), -1)
+        cand = [c for c in self.clusters if not c.Frozen]
+        if not cand or len(Q) == 0:
+            return [[] for _ in range(len(Q))]
+        E = np.stack([c.Centroid for c in cand]).astype(np.float32)
+        es = np.array([len(c.Members) for c in cand], np.int32)
+        qs = np.ones(len(Q), np.int32)
+        if self.nearest_engine is not None:
+            idx, val = self.nearest_engine(Q, E, k, qs, es, self.maxSize)
+        else:
+            idx, val = (self.ctx or default_context()).nearest(Q, E, k, q_size=qs, e_size=es, max_size=self.maxSize)
+        return [[(cand[int(j)].Members[0], float(v)) for j, v in zip(ri, rv) if j >= 0] for ri, rv in zip(idx, val)]
 
     def as_map(self) -> Dict[int, List[str]]:
         """The reference's map[int][]string (clustering.go:265-280): the kept clusters."""

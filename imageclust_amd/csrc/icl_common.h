@@ -32,6 +32,7 @@ struct icl_ingest_ws; // jpeg_gpu.hip
 struct icl_many_ws; // ward_many.hip
 struct icl_requests_ws; // requests.hip
 struct icl_jenc_ws; // jpeg_encode_gpu.hip
+struct icl_nearest_ws; // nearest.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -150,6 +151,9 @@ struct icl_ctx {
     double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
     icl_jenc_ws *jenc = nullptr;         // buffers of the GPU JPEG encoder (jpeg_encode_gpu.hip; created on first use)
     dz_totals downsize_last;             // last icl_downsize_images[_mem] (icl_last_downsize_stats)
+    icl_nearest_ws *nearest = nullptr;   // device copies of sizes / exclude and the partial lists of icl_nearest (nearest.hip; created on first use)
+    int nearest_splits = 0;              // icl_set_nearest_options: column splits per band of query rows (0: the engine decides)
+    int64_t nearest_stats[4] = {0, 0, 0, 0}; // last icl_nearest[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_nearest_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
@@ -211,6 +215,7 @@ void icl_ingest_free(icl_ctx *ctx);
 void icl_many_free(icl_ctx *ctx);
 void icl_requests_free(icl_ctx *ctx);
 void icl_jenc_free(icl_ctx *ctx);
+void icl_nearest_free(icl_ctx *ctx);
 
 // The two batched halves icl_cluster_requests (requests.hip) joins; both expect ctx->mu held and the context's device selected.
 // Each tells its caller apart what the return code alone cannot: "the list was processed and an item of it failed" from "the call stopped".

@@ -415,6 +415,38 @@ int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d,
  * not exist (any more); nothing is written then. */
 int icl_seeded_assign_ids(int32_t m, const int32_t *seed_size, int32_t min_size, const int32_t *merges, int32_t n_merges, int32_t *cluster_id,
                           int32_t *seed_rank, int32_t *n_clusters);
+/* ---- nearest clusters: each query's k library clusters of smallest WardDistance, exact, with no distance matrix (DESIGN.md "Nearest clusters") ----
+ * Q holds nq query centroids and E n library centroids, rows of d floats; q_size[nq] / e_size[n] are the clusters' item counts (NULL: all 1).
+ * VALUE of pair (i, j): WardDistance (clustering.go:136-157) of a cluster of q_size[i] items at Q[i] and one of e_size[j] items at E[j], bit for
+ * bit -- differences, products and the sum each rounded, strictly in k order, then (float(sa*sb) / float(sa+sb)) * s.  With both size arrays
+ * NULL the values are the entries of ComputeInitialDistanceMatrix (:61-73) over the stacked rows.
+ * PAIRS LEFT OUT: j == exclude[i] (exclude may be NULL; -1: none; a self-join -- Q is E -- passes exclude[i] = i), and, when max_size > 0, every
+ * pair with q_size[i] + e_size[j] > max_size: the reference's ban (:228).
+ * ORDER: row i of idx / val (nq x k each) holds the k smallest remaining pairs, ascending by (value, j): values compare as fp32 with `<`, NaN
+ * values sort behind every number, ties (equal numbers, two NaNs) go by j.  The result does not depend on tile order, split count or launch
+ * geometry.  SHORT ROWS: if fewer than k pairs remain the tail is idx = -1, val = MaxFloat32 (the reference's ban value).
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context; Q, idx, val when nq > 0; E when n > 0), k outside
+ * 1..64, d < 1, negative nq or n, n >= 2^31, a size <= 0, or an exclude entry outside [-1, n); nq == 0 or n == 0 is ICL_OK, and with n == 0 every
+ * entry is the tail; ICL_ERR_UNSUPPORTED on a context that is a replica of a group; ICL_ERR_NOMEM when the workspace does not fit.
+ * icl_nearest takes host memory throughout: it uploads, calls the _dev form and downloads.  icl_nearest_dev takes Q, E, idx and val on the
+ * context's device (consumed and written on the context's stream; Q and E 16-byte aligned take the wide loads when d % 4 == 0); q_size, e_size
+ * and exclude stay in host memory and may be reused at return.  No nq x n array exists anywhere: the workspace is the device copies of the
+ * three host arrays plus 8 * nq * k * splits bytes of partial lists when the library's columns are split (splits > 1). */
+int icl_nearest(icl_ctx *ctx, const float *Q, const int32_t *q_size, int64_t nq, const float *E, const int32_t *e_size, int64_t n, int32_t d,
+                int32_t k, int32_t max_size, const int64_t *exclude, int32_t *idx, float *val);
+int icl_nearest_dev(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_E, const int32_t *e_size, int64_t n,
+                    int32_t d, int32_t k, int32_t max_size, const int64_t *exclude, int32_t *d_idx, float *d_val);
+/* The same leave-out and order rules applied to values the caller already holds (host only: no context, no GPU), e.g. the result of
+ * icl_ward_distance_matrix: D[i * ld + j] is pair (i, j)'s value, used as given; the sizes serve the max_size rule alone.  The comparison and
+ * the insertion are the code the device runs (nearest_select.h).  ICL_ERR_ARG, with nothing written, as above and for ld < n. */
+int icl_nearest_from_matrix(const float *D, int64_t nq, int64_t n, int64_t ld, const int32_t *q_size, const int32_t *e_size, int32_t k,
+                            int32_t max_size, const int64_t *exclude, int32_t *idx, float *val);
+/* A workgroup owns a band of 128 query rows; with few bands and a large library the library's 128-column tiles are split over column_splits
+ * workgroups per band and a second kernel merges their partial lists.  0 (default): the engine decides from nq, n and the CU count; a count
+ * above 0 is used as given, up to one tile per split and 1024 splits.  Same results for every count.  ICL_ERR_ARG for a null context or a negative count. */
+int icl_set_nearest_options(icl_ctx *ctx, int32_t column_splits);
+/* The last icl_nearest[_dev] of the context: info = splits used, tiles run, pairs evaluated, workspace bytes (all 0 after a call with nq == 0). */
+int icl_last_nearest_stats(icl_ctx *ctx, int64_t info[4]);
 /* ---- a queue of requests, files to cluster ids: replaces workflow.Run (workflow.go:84-94) for nreq requests in ONE call ----
  * Request r is n[r] image files with labels.  Every image gets its embedding row (GetImageEmbedding; head, prec as icl_embed_files), a one-hot
  * vector over the request's label set is appended (GenerateLabelVector + CombineEmbeddings, embeddings.go:166-183: d[r] = head + n_labels[r]
