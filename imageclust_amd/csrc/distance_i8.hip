@@ -30,6 +30,7 @@
 // barriers, counted vmcnt, staggered wave groups; the int8 instruction takes the same 16 bytes per lane as the bf16 one, and a dot product does
 // not care in which order an instruction walks K as long as both operands are staged alike.  Lower-triangle tiles only.
 #include "icl_common.h"
+#include "distance.h"
 #include "mfma_tile.h"
 
 #include <algorithm>
@@ -147,30 +148,6 @@ struct di8_args {
                          // initial row minima start from -- their first pass over the row is this epilogue (one pass instead of two)
 };
 
-// tile order: bands of 8 tile rows, column by column, then the band's triangular cap (as dbound_band_decode in distance_mfma.hip): the
-// workgroups an XCD runs at the same time share their operand blocks in its L2
-__device__ __forceinline__ void di8_band_decode(int64_t b, int64_t tr_hi, int &ti, int &tj)
-{
-    auto before = [&](int64_t q) { return 32 * q * q + q * 4; };
-    int64_t q = (int64_t)((-4.0 + sqrt(16.0 + 128.0 * (double)b)) / 64.0);
-    while (before(q + 1) <= b) ++q;
-    while (q > 0 && before(q) > b) --q;
-    const int64_t r0 = 8 * q;
-    const int64_t h = tr_hi - r0 < 8 ? tr_hi - r0 : 8;
-    int64_t r = b - before(q);
-    const int64_t rect = h * (r0 + 1);
-    if (r < rect) {
-        tj = (int)(r / h);
-        ti = (int)(r0 + r % h);
-        return;
-    }
-    r -= rect;
-    int a = 1;
-    while ((int64_t)a * (a + 1) / 2 <= r) ++a;
-    ti = (int)(r0 + a);
-    tj = (int)(r0 + 1 + (r - (int64_t)a * (a - 1) / 2));
-}
-
 // E_ab of the header, in double (device side of the proof; ward.hip wupper has the float form for the scans).  sa / sb: 2^e or 0.
 __device__ __forceinline__ double di8_eab(double sa, double sb, double l1a, double l1b, double na, double nb, int d)
 {
@@ -186,7 +163,8 @@ __global__ __launch_bounds__(512) void dist_bound_i8_kernel(const di8_args p)
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 2, wc = wid & 3;
     int ti, tj;
-    di8_band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), p.T, ti, tj);
+    // tile order: dist_tile.h, over all tile rows -- the workgroups an XCD runs at the same time share their operand blocks in its L2
+    tri_band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), 0, p.T, ti, tj);
     ti = __builtin_amdgcn_readfirstlane(ti);
     tj = __builtin_amdgcn_readfirstlane(tj);
     const int64_t m0 = (int64_t)ti * 256, n0 = (int64_t)tj * 256; // X rows = output rows i (P strings), W rows = output columns j (Q strings)
@@ -405,9 +383,7 @@ size_t icl_dist_i8_pq_bytes(int64_t n, int d)
     return (size_t)(n * 3 * Kp) + 256;
 }
 
-// Ec / nrm: dist_center_kernel's centred rows and computed norms.  d_pq: icl_dist_i8_pq_bytes of scratch (the digit strings; free once the
-// stream has passed this launch); d_l1 / d_ex: [n] each, read by the row scans for as long as the matrix holds flagged entries (wupper).
-// Bounds of every pair j < i < n into out / rowoff; d_rowub (may be null): [n] the rows' smallest upper bounds (float bits).  Enqueued on strm.
+// (distance.h says what each argument is)
 int icl_dist_bound_i8_launch(icl_ctx *ctx, const float *d_Ec, const float *d_nrm, int64_t n, int d, int K, float gam, void *d_pq, float *d_l1, int32_t *d_ex,
                              float *d_out, const int64_t *d_rowoff, hipStream_t strm, unsigned int *d_rowub)
 {
@@ -416,8 +392,8 @@ int icl_dist_bound_i8_launch(icl_ctx *ctx, const float *d_Ec, const float *d_nrm
     if (n <= 0) return ICL_OK;
     hipLaunchKernelGGL(dist_quant_kernel, dim3((unsigned)n), dim3(256), 0, strm, d_Ec, n, K, Kp, Q, d_ex, d_l1);
     const int64_t T = icl_ceil_div(n, 256);
-    const int64_t nblocks = T * (T + 1) / 2;
-    if (nblocks > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "distance tile grid too large");
+    int64_t nblocks;
+    ICL_TRY(icl_dist_grid(ctx, 0, T, &nblocks));
     if (d_rowub) ICL_HIP(ctx, hipMemsetAsync(d_rowub, 0x7f, (size_t)n * sizeof(unsigned int), strm)); // 0x7f7f7f7f = 3.39e38: "nothing known"
     di8_args a{Q, d_nrm, d_l1, d_ex, d_out, d_rowoff, n, (int)T, Kp, d, gam, d_rowub};
     const double pairs = 0.5 * (double)n * (double)(n - 1);

@@ -13,6 +13,7 @@
 // |e_i||e_j| per term.  Tiles, LDS image, LDS-DMA staging and the MFMA sweep are the convolution kernel's
 // (mfma_tile.h): 128x128 outputs per workgroup, lower-triangle tiles only.
 #include "icl_common.h"
+#include "distance.h"
 #include "mfma_tile.h"
 
 #include <algorithm>
@@ -51,48 +52,39 @@ struct dist_args {
     int K;
 };
 
-__device__ __forceinline__ void tri_decode32(int64_t b, int &ti, int &tj)
-{
-    int64_t t = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-    while ((t + 1) * (t + 2) / 2 <= b) ++t;
-    while (t * (t + 1) / 2 > b) --t;
-    ti = (int)t;
-    tj = (int)(b - t * (t + 1) / 2);
-}
+// ---- the GEMM tile both kernels below run (the convolution kernel's tile machinery, mfma_tile.h) -------------------------------
+#define DG_BN 128                              /* tile columns (rows are CV_BM = 128) */
+#define DG_STAGE ((DG_BN + CV_BM) * CV_ROWB)   /* bytes of one k-step of both operands; two stages are in flight */
+#define DG_EP_LD (DG_BN + 4)                   /* pitch of the finished fp32 tile, which reuses the stages */
 
-// MODE 0: packed lower triangle j < i at out[rowoff[i] + j];  MODE 1: dense rows, j <= i at out[i*ld + j].
-template <int MODE>
-__global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
+// c[i][j] = sum_k X[i0 + i][k] * W[j0 + j][k] for the 128 x 128 pairs of a tile, left as fp32 at smem[i * DG_EP_LD + j] behind a
+// barrier.  X, W: [n][K] elements of T (K a multiple of T::BK); rows past n read the zero page.  All 256 threads of the workgroup.
+template <typename T>
+__device__ __forceinline__ void dist_gemm_tile(const typename T::elem *X, const typename T::elem *W, int64_t n, int K, const void *zero, int64_t i0,
+                                               int64_t j0, unsigned char *smem)
 {
-    constexpr int BN = 128;
-    constexpr int STAGE = (BN + CV_BM) * CV_ROWB;
-    constexpr int EP_LD = BN + 4;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid & 1, wn = wid >> 1;
-    int ti, tj;
-    tri_decode32(blockIdx.x, ti, tj);
-    const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * BN;
     // staging roles: one LDS-DMA piece = 8 rows x 128 B; "x" rows = i (lane of the MFMA result), "w" rows = j
     const int prow = lane >> 3, ps = lane & 7;
-    const uint16_t *xsrc[4], *wsrc[4];
+    const typename T::elem *xsrc[4], *wsrc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int row = wid * 32 + q * 8 + prow;
         const int64_t ri = i0 + row, rj = j0 + row;
-        xsrc[q] = ri < p.n ? p.A + ri * p.K + lds_swz(row, ps) * 8 : nullptr;
-        wsrc[q] = rj < p.n ? p.B + rj * p.K + lds_swz(row, ps) * 8 : nullptr;
+        xsrc[q] = ri < n ? X + ri * K + lds_swz(row, ps) * T::KE : nullptr;
+        wsrc[q] = rj < n ? W + rj * K + lds_swz(row, ps) * T::KE : nullptr;
     }
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const unsigned wave_off = __builtin_amdgcn_readfirstlane(wid * 32 * CV_ROWB);
     int k0 = 0;
     auto stage = [&](int buf) {
-        const unsigned wdst = smem_base + buf * STAGE + wave_off, xdst = wdst + BN * CV_ROWB;
+        const unsigned wdst = smem_base + buf * DG_STAGE + wave_off, xdst = wdst + DG_BN * CV_ROWB;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) glds16_asm(wsrc[q] ? (const void *)(wsrc[q] + k0) : p.zero, wdst + q * 8 * CV_ROWB);
+        for (int q = 0; q < 4; ++q) glds16_asm(wsrc[q] ? (const void *)(wsrc[q] + k0) : zero, wdst + q * 8 * CV_ROWB);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) glds16_asm(xsrc[q] ? (const void *)(xsrc[q] + k0) : p.zero, xdst + q * 8 * CV_ROWB);
-        k0 += 64;
+        for (int q = 0; q < 4; ++q) glds16_asm(xsrc[q] ? (const void *)(xsrc[q] + k0) : zero, xdst + q * 8 * CV_ROWB);
+        k0 += T::BK;
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    const int nk = p.K / 64;
+    const int nk = K / T::BK;
     stage(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -109,12 +101,12 @@ __global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
     for (int ks = 0; ks < nk; ++ks) {
         const int cur = ks & 1;
         if (ks + 1 < nk) stage(cur ^ 1);
-        const unsigned char *wsm = smem + cur * STAGE;
-        conv_mma_kstep<BF16, BN>(wsm, wsm + BN * CV_ROWB, wm, wn, fr, fh, acc);
+        const unsigned char *wsm = smem + cur * DG_STAGE;
+        conv_mma_kstep<T, DG_BN>(wsm, wsm + DG_BN * CV_ROWB, wm, wn, fr, fh, acc);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    // accumulators (lane = i, register quads = 4 consecutive j) -> fp32 LDS tile [i][j] -> coalesced rows
+    // accumulators (lane = i, register quads = 4 consecutive j) -> fp32 LDS tile [i][j]
     float *ep = reinterpret_cast<float *>(smem);
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -124,25 +116,34 @@ __global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int nl = wn * 64 + a * 32 + 8 * g + 4 * fh;
-                *reinterpret_cast<float4 *>(ep + ml * EP_LD + nl) =
+                *reinterpret_cast<float4 *>(ep + ml * DG_EP_LD + nl) =
                     make_float4(acc[a][b][4 * g + 0], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
             }
     }
     __syncthreads();
-    const int nl = (tid & 31) * 4; // 32 lanes x 4 floats = one 128-wide tile row; 8 rows per pass
+}
+
+// The finished tile as coalesced rows: entry (i, j) = value(nrm[i], nrm[j], c[i][j]).  32 lanes x 4 floats = one 128-wide tile row, 8
+// rows per pass.  MODE 0: packed lower triangle, j < i at out[rowoff[i] + j];  MODE 1: dense rows, j <= i at out[i * ld + j], 0 at j == i.
+template <int MODE, typename F>
+__device__ __forceinline__ void dist_store_rows(const unsigned char *smem, const float *nrm, int64_t n, int64_t i0, int64_t j0, float *out,
+                                                const int64_t *rowoff, int64_t ld, F value)
+{
+    const float *ep = reinterpret_cast<const float *>(smem);
+    const int tid = threadIdx.x, nl = (tid & 31) * 4;
     float nj[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) nj[q] = (j0 + nl + q) < p.n ? p.norms[j0 + nl + q] : 0.0f;
+    for (int q = 0; q < 4; ++q) nj[q] = (j0 + nl + q) < n ? nrm[j0 + nl + q] : 0.0f;
     for (int ml = tid >> 5; ml < CV_BM; ml += 8) {
         const int64_t i = i0 + ml;
-        if (i >= p.n) break;
-        const float ni = p.norms[i];
-        const float4 t = *reinterpret_cast<const float4 *>(ep + ml * EP_LD + nl);
-        const float v[4] = {0.5f * (ni + nj[0]) - t.x, 0.5f * (ni + nj[1]) - t.y, 0.5f * (ni + nj[2]) - t.z, 0.5f * (ni + nj[3]) - t.w};
+        if (i >= n) break;
+        const float ni = nrm[i];
+        const float4 t = *reinterpret_cast<const float4 *>(ep + ml * DG_EP_LD + nl);
+        const float v[4] = {value(ni, nj[0], t.x), value(ni, nj[1], t.y), value(ni, nj[2], t.z), value(ni, nj[3], t.w)};
         const int64_t jb = j0 + nl;
         const int64_t lim = MODE == 0 ? i : i + 1; // columns j < lim are written
-        float *row = MODE == 0 ? p.out + p.rowoff[i] : p.out + i * p.ld;
-        if (jb + 3 < i && ((MODE == 0) || ((p.ld & 3) == 0))) { // strictly below the diagonal: one 16-byte store
+        float *row = MODE == 0 ? out + rowoff[i] : out + i * ld;
+        if (jb + 3 < i && ((MODE == 0) || ((ld & 3) == 0))) { // strictly below the diagonal: one 16-byte store
             *reinterpret_cast<float4 *>(row + jb) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
 #pragma unroll
@@ -152,14 +153,25 @@ __global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
     }
 }
 
+// D~ of the whole triangle in row-major tile order (MODE: dist_store_rows).
+template <int MODE>
+__global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int ti, tj;
+    tri_decode32(blockIdx.x, ti, tj);
+    const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * DG_BN;
+    dist_gemm_tile<BF16>(p.A, p.B, p.n, p.K, p.zero, i0, j0, smem);
+    dist_store_rows<MODE>(smem, p.norms, p.n, i0, j0, p.out, p.rowoff, p.ld, [](float ni, float nj, float c) { return 0.5f * (ni + nj) - c; });
+}
+
 static size_t dist_lds_bytes()
 {
-    const size_t stages = 2 * (size_t)(128 + CV_BM) * CV_ROWB, ep = (size_t)CV_BM * (128 + 4) * 4;
+    const size_t stages = 2 * (size_t)DG_STAGE, ep = (size_t)CV_BM * DG_EP_LD * 4;
     return std::max(stages, ep);
 }
 
-// Shared by icl_distance_mfma_dev and the LW clustering mode (ward.hip).  Scratch (A', B', norms, zero page) is
-// allocated per call and released after the stream drains.
+// Shared by icl_distance_mfma_dev and the LW clustering mode (ward.hip).  Scratch: A', B', norms, the zero page.
 int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float *d_out, const int64_t *d_rowoff, int64_t ld)
 {
     if (n <= 0) return ICL_OK;
@@ -178,8 +190,8 @@ int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float
     icl_lds_optin(ctx, (const void *)dist_mfma_kernel<0>, (int)dist_lds_bytes());
     icl_lds_optin(ctx, (const void *)dist_mfma_kernel<1>, (int)dist_lds_bytes());
     dist_args a{A, B, norms, zero, d_out, d_rowoff, n, ld, K};
-    const int64_t nt = icl_ceil_div(n, CV_BM), nblocks = nt * (nt + 1) / 2;
-    if (nblocks > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "distance tile grid too large");
+    int64_t nblocks;
+    ICL_TRY(icl_dist_grid(ctx, 0, icl_ceil_div(n, CV_BM), &nblocks));
     {
         const double pairs = (double)n * (double)(n + 1) * 0.5;
         icl_prof_scope ps(ctx, ICL_K_DIST_MFMA, 2.0 * pairs * d, 4.0 * pairs + 4.0 * (double)n * d);
@@ -303,133 +315,29 @@ struct dbound_args {
     float ceps, gam; // E_ab = ceps (n_a + n_b); gam = g'
 };
 
-__device__ __forceinline__ void dbound_band_decode(int64_t b, int64_t tr_lo, int64_t tr_hi, int &ti, int &tj)
-{
-    // the tile order of ward_dist_exact_kernel (ward.hip, band_decode): bands of 8 tile rows, column by column, then the cap
-    auto before = [&](int64_t q) { return 32 * q * q + q * (8 * tr_lo + 4); };
-    const double c1 = 8.0 * (double)tr_lo + 4.0;
-    int64_t q = (int64_t)((-c1 + sqrt(c1 * c1 + 128.0 * (double)b)) / 64.0);
-    while (before(q + 1) <= b) ++q;
-    while (q > 0 && before(q) > b) --q;
-    const int64_t r0 = tr_lo + 8 * q;
-    const int64_t h = tr_hi - r0 < 8 ? tr_hi - r0 : 8;
-    int64_t r = b - before(q);
-    const int64_t rect = h * (r0 + 1);
-    if (r < rect) {
-        tj = (int)(r / h);
-        ti = (int)(r0 + r % h);
-        return;
-    }
-    r -= rect;
-    int a = 1;
-    while ((int64_t)a * (a + 1) / 2 <= r) ++a;
-    ti = (int)(r0 + a);
-    tj = (int)(r0 + 1 + (r - (int64_t)a * (a - 1) / 2));
-}
-
-// 128 x 128 pairs per workgroup on v_mfma_f32_32x32x2_f32 (the f32 form of the convolution kernel's tile machinery);
+// 128 x 128 pairs per workgroup on v_mfma_f32_32x32x2_f32 (the f32 form of the tile above), tiles in dist_tile.h's band order;
 // out[rowoff[i] + j] = flagged lower bound of the Ward value of singletons i > j.
 __global__ __launch_bounds__(256) void dist_bound_kernel(const dbound_args p)
 {
-    constexpr int BN = 128;
-    constexpr int STAGE = (BN + CV_BM) * CV_ROWB;
-    constexpr int EP_LD = BN + 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid & 1, wn = wid >> 1;
     int ti, tj;
-    dbound_band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), p.tr_lo, p.tr_hi, ti, tj);
-    const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * BN;
-    const int prow = lane >> 3, ps = lane & 7;
-    const float *xsrc[4], *wsrc[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = wid * 32 + q * 8 + prow;
-        const int64_t ri = i0 + row, rj = j0 + row;
-        xsrc[q] = ri < p.n ? p.Ec + ri * p.K + lds_swz(row, ps) * 4 : nullptr;
-        wsrc[q] = rj < p.n ? p.Ec + rj * p.K + lds_swz(row, ps) * 4 : nullptr;
-    }
-    const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
-    const unsigned wave_off = __builtin_amdgcn_readfirstlane(wid * 32 * CV_ROWB);
-    int k0 = 0;
-    auto stage = [&](int buf) {
-        const unsigned wdst = smem_base + buf * STAGE + wave_off, xdst = wdst + BN * CV_ROWB;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) glds16_asm(wsrc[q] ? (const void *)(wsrc[q] + k0) : p.zero, wdst + q * 8 * CV_ROWB);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) glds16_asm(xsrc[q] ? (const void *)(xsrc[q] + k0) : p.zero, xdst + q * 8 * CV_ROWB);
-        k0 += 32;
-    };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    const int nk = p.K / 32;
-    stage(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int fr = lane & 31, fh = lane >> 5;
-    for (int ks = 0; ks < nk; ++ks) {
-        const int cur = ks & 1;
-        if (ks + 1 < nk) stage(cur ^ 1);
-        const unsigned char *wsm = smem + cur * STAGE;
-        conv_mma_kstep<F32, BN>(wsm, wsm + BN * CV_ROWB, wm, wn, fr, fh, acc);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    float *ep = reinterpret_cast<float *>(smem);
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int ml = wm * 64 + b * 32 + fr;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int nl = wn * 64 + a * 32 + 8 * g + 4 * fh;
-                *reinterpret_cast<float4 *>(ep + ml * EP_LD + nl) =
-                    make_float4(acc[a][b][4 * g + 0], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
-            }
-    }
-    __syncthreads();
-    const int nl = (tid & 31) * 4;
-    float nj[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) nj[q] = (j0 + nl + q) < p.n ? p.nrm[j0 + nl + q] : 0.0f;
-    for (int ml = tid >> 5; ml < CV_BM; ml += 8) {
-        const int64_t i = i0 + ml;
-        if (i >= p.n) break;
-        const float ni = p.nrm[i];
-        const float4 t = *reinterpret_cast<const float4 *>(ep + ml * EP_LD + nl);
-        const float c[4] = {t.x, t.y, t.z, t.w};
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float ns = ni + nj[q];
-            const float T = 0.5f * ns - c[q];
-            // (T - E_ab)(1 - g'), pushed DOWN by 4 u against the three roundings of this expression itself
-            // (p.ceps is E_ab's constant rounded UP on the host, so the computed product is no smaller than E_ab)
-            float L = (T - p.ceps * ns) * (1.0f - p.gam);
-            L = L * (1.0f - 2.4e-7f);
-            L = (L > 1e-30f && ns < 1e37f) ? L : 0.0f; // subnormal range / overflowing norms (also NaN): no claim, the entry is evaluated exactly when it matters
-            v[q] = __uint_as_float(__float_as_uint(L) | 0x80000000u); // sign bit = "lower bound, not a value" (-0.0: bound 0)
-        }
-        const int64_t jb = j0 + nl;
-        float *row = p.out + p.rowoff[i];
-        if (jb + 3 < i) {
-            *reinterpret_cast<float4 *>(row + jb) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (jb + q < i) row[jb + q] = v[q];
-        }
-    }
+    tri_band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), p.tr_lo, p.tr_hi, ti, tj);
+    const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * DG_BN;
+    dist_gemm_tile<F32>(p.Ec, p.Ec, p.n, p.K, p.zero, i0, j0, smem);
+    const float ceps = p.ceps, gam = p.gam;
+    dist_store_rows<0>(smem, p.nrm, p.n, i0, j0, p.out, p.rowoff, 0, [=](float ni, float nj, float c) {
+        const float ns = ni + nj;
+        const float T = 0.5f * ns - c;
+        // (T - E_ab)(1 - g'), pushed DOWN by 4 u against the three roundings of this expression itself
+        // (ceps is E_ab's constant rounded UP on the host, so the computed product is no smaller than E_ab)
+        float L = (T - ceps * ns) * (1.0f - gam);
+        L = L * (1.0f - 2.4e-7f);
+        L = (L > 1e-30f && ns < 1e37f) ? L : 0.0f; // subnormal range / overflowing norms (also NaN): no claim, the entry is evaluated exactly when it matters
+        return __uint_as_float(__float_as_uint(L) | 0x80000000u); // sign bit = "lower bound, not a value" (-0.0: bound 0)
+    });
 }
 
-// Centred copy + norms of E (ws: [n][K] floats + n floats, caller-owned), then the bounds of tile rows [tr_lo, tr_hi) into
-// out / rowoff.  Everything is enqueued on `strm`; nothing is synchronised or freed here.
+// (distance.h says what each launcher takes)
 size_t icl_dist_colsum_doubles(int d) { return (size_t)(1 + DIST_CS_PARTS) * (size_t)std::max(d, 1); }
 int icl_dist_center_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, int K, double *d_colsum, float *d_Ec, float *d_nrm, hipStream_t strm)
 {
@@ -446,8 +354,8 @@ int icl_dist_bound_launch(icl_ctx *ctx, const float *d_Ec, const float *d_nrm, c
                           const int64_t *d_rowoff, int64_t tr_lo, int64_t tr_hi, hipStream_t strm)
 {
     if (tr_hi <= tr_lo) return ICL_OK;
-    const int64_t nblocks = tr_hi * (tr_hi + 1) / 2 - tr_lo * (tr_lo + 1) / 2;
-    if (nblocks > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "distance tile grid too large");
+    int64_t nblocks;
+    ICL_TRY(icl_dist_grid(ctx, tr_lo, tr_hi, &nblocks));
     icl_lds_optin(ctx, (const void *)dist_bound_kernel, (int)dist_lds_bytes());
     dbound_args a{d_Ec, d_nrm, d_zero, d_out, d_rowoff, n, tr_lo, tr_hi, K, ceps, gam};
     const int64_t r_lo = tr_lo * CV_BM, r_hi = std::min<int64_t>(tr_hi * CV_BM, n);

@@ -1,6 +1,7 @@
 // mfma_tile.h -- the shared MFMA tile machinery of libimageclust_hip.so: element traits (bf16 / f32 MFMA step), the
 // swizzled 128-byte-row LDS image, inline-asm LDS-DMA staging, the per-k-step MFMA sweep of a 128 x BN tile and the
-// XCD-aware tile order.  Used by the convolution kernels (resnet.hip) and the MFMA distance tile (distance_mfma.hip).
+// XCD-aware dealing of tiles.  Used by the convolution kernels (resnet.hip) and the distance stage: the GEMM tile of distance_mfma.hip
+// (dist_gemm_tile), and xcd_remap in front of dist_tile.h's band order in ward.hip, distance_mfma.hip and distance_i8.hip.
 #pragma once
 #include "icl_common.h"
 

@@ -15,6 +15,7 @@
 // The process-per-GPU path of bench.py uses the same building blocks (icl_ward_distance_rows_dev / icl_ward_unpack_spans_dev /
 // icl_cluster_prefilled_dev) with RCCL send/recv as the transport.
 #include "icl_common.h"
+#include "distance.h" // icl_dist_i8_usable
 
 #include <cstring>
 #include <new>
@@ -195,7 +196,6 @@ extern "C" int icl_group_embed_u8(icl_group *g, const uint8_t *hwc_rgb, int64_t 
 // (all peers concurrently, one link each) -- or, for a device that is no peer, through a bounded landing buffer --, computes
 // its own run from bounds and runs the exact merge loop.  Nothing is staged on GPU 0.
 static bool group_shards_merges(icl_group *g) { return g->ctx.size() > 1 && g->merge_mode == ICL_MERGE_SHARDED; }
-bool icl_dist_i8_usable(int64_t n, int d); // distance_i8.hip
 static bool group_deals_rows(icl_group *g, int64_t n, int d) // (also: every GPU needs all of E)
 {
     const int parts = (int)g->ctx.size();

@@ -1,8 +1,8 @@
 // nearest.hip -- icl_nearest: for each query row the k library rows of smallest WardDistance, exact, with no distance matrix.
 //
-// Values are the reference's (clustering.go:136-157; ward_value.h), from ward_dist_exact_kernel's scheme (ward.hip) in a rectangular
-// form: 128 query rows x 128 library rows per tile, k-chunks of both operands staged in LDS, an 8 x 8 block of accumulators per
-// thread, each accumulator one strictly sequential chain.  A workgroup owns a BAND of 128 query rows and walks its share of the
+// Values are the reference's (clustering.go:136-157; ward_value.h), from the exact tile ward_dist_exact_kernel (ward.hip) runs, here on
+// a rectangle (ward_exact_tile.h): 128 query rows x 128 library rows per tile, k-chunks of both operands staged in LDS, an 8 x 8 block
+// of accumulators per thread, each accumulator one strictly sequential chain.  A workgroup owns a BAND of 128 query rows and walks its share of the
 // library's column tiles; each row's k best (value, j) stay in LDS from the first tile to the last, a finished tile goes through LDS a
 // quarter at a time into them, and nothing of size nq x n is ever written.  With few bands and a large library the column tiles are
 // SPLIT over several workgroups per band, each leaves a partial list, and nearest_merge_kernel joins them.  What a list keeps and in
@@ -12,15 +12,13 @@
 
 #include "icl_common.h"
 #include "nearest_select.h"
+#include "ward_exact_tile.h" // DT_TILE, DT_KC, DT_LD, ward_exact_tile
 #include "ward_value.h"
 
 #include <algorithm>
 #include <cstring>
 
-#define NR_TILE 128
-#define NR_KC 16
-#define NR_LD (NR_TILE + 4)
-#define NR_STAGE (2 * NR_KC * NR_LD) // floats of the two operand chunks; the finished tile's quarters reuse them
+#define NR_STAGE (2 * DT_KC * DT_LD) // floats of the two operand chunks; the finished tile's quarters reuse them
 #define NR_SUB 64                    // a quarter: 64 rows x 64 columns ...
 #define NR_SUB_LD 65                 // ... at an odd pitch (64 * 65 <= NR_STAGE): the selecting lanes, one per row, hit distinct banks
 #define NR_MERGE_ROWS 64
@@ -28,8 +26,6 @@
 
 static_assert(NR_SUB * NR_SUB_LD <= NR_STAGE, "a quarter tile must fit the operand staging area");
 static_assert(NS_KMAX == 64, "the LDS budget below is worked out for k <= 64");
-
-typedef float nr_f2 __attribute__((ext_vector_type(2)));
 
 struct nr_args {
     const float *Q, *E;
@@ -44,116 +40,40 @@ struct nr_args {
 
 // floats of dynamic LDS: operand chunks, the band's lists (pitch k | 1: a row per lane, distinct banks), per-row counts, the band's
 // row sizes, the tile's column sizes.  k = 64: 84 992 bytes of the 160 KiB.
-static inline size_t nr_lds_bytes(int k) { return (size_t)(NR_STAGE + 2 * NR_TILE * (k | 1) + 3 * NR_TILE) * 4; }
+static inline size_t nr_lds_bytes(int k) { return (size_t)(NR_STAGE + 2 * DT_TILE * (k | 1) + 3 * DT_TILE) * 4; }
 
 __global__ __launch_bounds__(256) void nearest_tile_select_kernel(nr_args a)
 {
     extern __shared__ __attribute__((aligned(16))) float nr_smem[];
-    float(*As)[NR_LD] = reinterpret_cast<float(*)[NR_LD]>(nr_smem);
-    float(*Bs)[NR_LD] = reinterpret_cast<float(*)[NR_LD]>(nr_smem + NR_KC * NR_LD);
+    float(*As)[DT_LD] = reinterpret_cast<float(*)[DT_LD]>(nr_smem);
+    float(*Bs)[DT_LD] = reinterpret_cast<float(*)[DT_LD]>(nr_smem + DT_KC * DT_LD);
     float *sub = nr_smem;
     const int k = a.k, ks = a.k | 1;
     float *lv = nr_smem + NR_STAGE;
-    int32_t *lj = reinterpret_cast<int32_t *>(lv + NR_TILE * ks);
-    int32_t *cnt = lj + NR_TILE * ks;
-    int32_t *qsz = cnt + NR_TILE;
-    int32_t *esz = qsz + NR_TILE;
+    int32_t *lj = reinterpret_cast<int32_t *>(lv + DT_TILE * ks);
+    int32_t *cnt = lj + DT_TILE * ks;
+    int32_t *qsz = cnt + DT_TILE;
+    int32_t *esz = qsz + DT_TILE;
 
     // workgroups of one split are neighbours: the bands that run together read the same library tiles at about the same time
     const int64_t band = (int64_t)blockIdx.x % a.nbands, split = (int64_t)blockIdx.x / a.nbands;
     const int64_t t_lo = split * a.ntiles / a.splits, t_hi = (split + 1) * a.ntiles / a.splits;
-    const int64_t i0 = band * NR_TILE;
+    const int64_t i0 = band * DT_TILE;
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
-    const int lrow = tid >> 2, lk = (tid & 3) * 4; // staging role: 2 rows per operand, 4 consecutive k
-    const int d = a.d;
-    const bool vec = a.vec != 0;
 
-    if (tid < NR_TILE) {
+    if (tid < DT_TILE) {
         cnt[tid] = 0;
         qsz[tid] = (a.qs && i0 + tid < a.nq) ? a.qs[i0 + tid] : 1;
     }
     __syncthreads();
 
     for (int64_t t = t_lo; t < t_hi; ++t) {
-        const int64_t j0 = t * NR_TILE;
-        if (tid < NR_TILE) esz[tid] = (a.es && j0 + tid < a.n) ? a.es[j0 + tid] : 1; // (read after the k loop's barriers)
+        const int64_t j0 = t * DT_TILE;
+        if (tid < DT_TILE) esz[tid] = (a.es && j0 + tid < a.n) ? a.es[j0 + tid] : 1; // (read after the tile's barriers)
 
         float acc[8][8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[r][c] = 0.0f;
-
-        // Rows past nq / n and k past d are staged as zeros.  That is harmless ONLY because every accumulator is its own chain (a
-        // padded row or column meets nobody else's sum, and its pairs are never offered to a list) and a padded k adds
-        // fl((0 - 0)^2) = +0 to a sum that is never below +0: s + 0 == s exactly, NaN and Inf included.
-        float ra[2][4], rb[2][4];
-        auto gload = [&](int kc) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int64_t ri = i0 + lrow + 64 * h, rj = j0 + lrow + 64 * h;
-                const int kk = kc + lk;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { ra[h][q] = 0.0f; rb[h][q] = 0.0f; }
-                if (ri < a.nq) {
-                    if (vec && kk + 3 < d) {
-                        const float4 v = *reinterpret_cast<const float4 *>(a.Q + ri * d + kk);
-                        ra[h][0] = v.x; ra[h][1] = v.y; ra[h][2] = v.z; ra[h][3] = v.w;
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (kk + q < d) ra[h][q] = a.Q[ri * d + kk + q];
-                    }
-                }
-                if (rj < a.n) {
-                    if (vec && kk + 3 < d) {
-                        const float4 v = *reinterpret_cast<const float4 *>(a.E + rj * d + kk);
-                        rb[h][0] = v.x; rb[h][1] = v.y; rb[h][2] = v.z; rb[h][3] = v.w;
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (kk + q < d) rb[h][q] = a.E[rj * d + kk + q];
-                    }
-                }
-            }
-        };
-
-        gload(0);
-        for (int kc = 0; kc < d; kc += NR_KC) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    As[lk + q][lrow + 64 * h] = ra[h][q];
-                    Bs[lk + q][lrow + 64 * h] = rb[h][q];
-                }
-            __syncthreads();
-            if (kc + NR_KC < d) gload(kc + NR_KC);
-#pragma unroll
-            for (int kk = 0; kk < NR_KC; ++kk) {
-                const float4 a0 = *reinterpret_cast<const float4 *>(&As[kk][ty * 4]);
-                const float4 a1 = *reinterpret_cast<const float4 *>(&As[kk][64 + ty * 4]);
-                const float4 b0 = *reinterpret_cast<const float4 *>(&Bs[kk][tx * 4]);
-                const float4 b1 = *reinterpret_cast<const float4 *>(&Bs[kk][64 + tx * 4]);
-                const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                for (int r = 0; r < 8; ++r)
-#pragma unroll
-                    for (int c = 0; c < 8; c += 2) {
-                        const nr_f2 av2 = {av[r], av[r]};
-                        const nr_f2 bv2 = {bv[c], bv[c + 1]};
-                        nr_f2 s2 = {acc[r][c], acc[r][c + 1]};
-                        const nr_f2 df = av2 - bv2; // clustering.go:139
-                        const nr_f2 p = df * df;    // :154 product (rounded)
-                        s2 = s2 + p;                // :154 sum (rounded), strictly in k order
-                        acc[r][c] = s2.x;
-                        acc[r][c + 1] = s2.y;
-                    }
-            }
-            __syncthreads();
-        }
+        ward_exact_tile(a.Q, a.nq, i0, a.E, a.n, j0, a.d, a.vec != 0, As, Bs, acc);
 
         // The finished tile, a quarter at a time: every thread scales its 4 x 4 values of the quarter (clustering.go:142-144) into the
         // staging area, then one lane per row offers the row's 64 values to the row's list.  The selecting lanes are every fourth
@@ -195,7 +115,7 @@ __global__ __launch_bounds__(256) void nearest_tile_select_kernel(nr_args a)
     // the band's lists, short rows with their tails
     float *ov = a.val + (split * a.nq + i0) * k;
     int32_t *oj = a.idx + (split * a.nq + i0) * k;
-    const int rows = (int)(a.nq - i0 < NR_TILE ? a.nq - i0 : NR_TILE);
+    const int rows = (int)(a.nq - i0 < DT_TILE ? a.nq - i0 : DT_TILE);
     for (int e = tid; e < rows * k; e += 256) {
         const int row = e / k, p = e - row * k;
         const bool have = p < cnt[row];
@@ -297,7 +217,7 @@ static int nr_splits(const icl_ctx *ctx, int64_t nbands, int64_t ntiles)
 static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_E, const int32_t *e_size,
                               int64_t n, int32_t d, int32_t k, int32_t max_size, const int64_t *exclude, int32_t *d_idx, float *d_val)
 {
-    const int64_t nbands = icl_ceil_div(nq, NR_TILE), ntiles = icl_ceil_div(n, NR_TILE);
+    const int64_t nbands = icl_ceil_div(nq, DT_TILE), ntiles = icl_ceil_div(n, DT_TILE);
     const int splits = nr_splits(ctx, nbands, ntiles);
     if (nbands * splits > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_nearest: grid too large (nq=%lld)", (long long)nq);
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };

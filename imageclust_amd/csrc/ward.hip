@@ -37,8 +37,10 @@
 #pragma clang fp contract(off)
 
 #include "icl_common.h"
+#include "distance.h" // the launchers of distance_mfma.hip / distance_i8.hip; dist_tile.h: tri_band_decode, the tile count
 #include "mfma_tile.h"
 #include "resnet_model.h" // icl_embed_dev_locked
+#include "ward_exact_tile.h" // DT_TILE, ward_exact_tile (shared with nearest.hip)
 #include "ward_value.h" // ward_sqdist_thread, ward_pair_value, ward_scale, ward_merge_elem (shared with ward_many.hip)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -46,17 +48,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include <cmath>
 #include <cstring>
 #include <type_traits>
-
-int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float *d_out, const int64_t *d_rowoff, int64_t ld); // distance_mfma.hip
-int icl_dist_center_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, int K, double *d_colsum, float *d_Ec, float *d_nrm, hipStream_t strm);
-size_t icl_dist_colsum_doubles(int d); // what d_colsum must hold: the column sums, then the fixed-order partial sums
-int icl_dist_bound_launch(icl_ctx *ctx, const float *d_Ec, const float *d_nrm, const void *d_zero, int64_t n, int K, float ceps, float gam, float *d_out,
-                          const int64_t *d_rowoff, int64_t tr_lo, int64_t tr_hi, hipStream_t strm);
-
-bool icl_dist_i8_usable(int64_t n, int d); // distance_i8.hip: the same bounds from an integer GEMM (exact by construction, 3x faster)
-size_t icl_dist_i8_pq_bytes(int64_t n, int d);
-int icl_dist_bound_i8_launch(icl_ctx *ctx, const float *d_Ec, const float *d_nrm, int64_t n, int d, int K, float gam, void *d_pq, float *d_l1, int32_t *d_ex,
-                             float *d_out, const int64_t *d_rowoff, hipStream_t strm, unsigned int *d_rowub);
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -258,42 +249,9 @@ void icl_ward_free(icl_ctx *ctx)
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// K6x: exact Ward distance tile.  128x128 pairs per workgroup, 8x8 per lane, sequential k, unfused fp32.
+// K6x: exact Ward distance tile.  128x128 pairs per workgroup, 8x8 per lane, sequential k, unfused fp32: the tile body is
+// ward_exact_tile.h's (shared with nearest.hip), the tile order dist_tile.h's (shared with the GEMM kernels).
 // ------------------------------------------------------------------------------------------------------------
-#define DT_TILE 128
-#define DT_KC 16
-#define DT_LD (DT_TILE + 4)
-
-
-// Tile order of a launch over tile rows [tr_lo, tr_hi) (tile row ti holds the tiles tj = 0 .. ti): BANDS of 8 tile rows; inside a
-// band the tiles left of the band's first diagonal tile go column by column -- 8 consecutive tiles share one 128-row panel of X
-// as their column operand, consecutive columns share the band's 8 row panels -- then the band's triangular cap.  With the
-// XCD-aware dealing below, the ~100 tiles an XCD runs at a time touch ~20 panels instead of ~100 (the kernel streams k-chunks,
-// so tiles that run together read the same cache lines at about the same time): the row-major order fetched 21x the
-// algorithmic bytes at N = 100 000 (profiles/r02c_pmc_traffic.json).
-__device__ __forceinline__ void band_decode(int64_t b, int64_t tr_lo, int64_t tr_hi, int &ti, int &tj)
-{
-    auto before = [&](int64_t q) { return 32 * q * q + q * (8 * tr_lo + 4); }; // tiles of the bands in front of band q
-    const double c1 = 8.0 * (double)tr_lo + 4.0;
-    int64_t q = (int64_t)((-c1 + sqrt(c1 * c1 + 128.0 * (double)b)) / 64.0);
-    while (before(q + 1) <= b) ++q;
-    while (q > 0 && before(q) > b) --q;
-    const int64_t r0 = tr_lo + 8 * q;
-    const int64_t h = tr_hi - r0 < 8 ? tr_hi - r0 : 8;
-    int64_t r = b - before(q);
-    const int64_t rect = h * (r0 + 1);
-    if (r < rect) {
-        tj = (int)(r / h);
-        ti = (int)(r0 + r % h);
-        return;
-    }
-    r -= rect; // the cap: row r0 + a holds the columns r0 + 1 .. r0 + a
-    int a = 1;
-    while ((int64_t)a * (a + 1) / 2 <= r) ++a;
-    ti = (int)(r0 + a);
-    tj = (int)(r0 + 1 + (r - (int64_t)a * (a - 1) / 2));
-}
-
 // mode 0: packed lower triangle (rowoff); mode 1: dense symmetric n x n with leading dimension ld.
 template <int MODE>
 __global__ __launch_bounds__(256) void ward_dist_exact_kernel(const float *__restrict__ X, const int32_t *__restrict__ sizes,
@@ -305,94 +263,19 @@ __global__ __launch_bounds__(256) void ward_dist_exact_kernel(const float *__res
     int ti, tj;
     // XCD-aware dealing: workgroups go round-robin over the 8 XCDs (private L2s); each XCD takes a contiguous run of the launch's
     // tiles in band order.  [tr_lo, tr_hi): a run of whole tile rows (the whole triangle, or a rank's share of it)
-    band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), tr_lo, tr_hi, ti, tj);
+    tri_band_decode(xcd_remap((int)blockIdx.x, (int)gridDim.x), tr_lo, tr_hi, ti, tj);
     const int64_t i0 = (int64_t)ti * DT_TILE, j0 = (int64_t)tj * DT_TILE;
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    // staging role: 2 rows per matrix, 4 consecutive k
-    const int lrow = tid >> 2, lk = (tid & 3) * 4;
-    const bool vec = (d & 3) == 0;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
 
     float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+    ward_exact_tile(X, n, i0, X, n, j0, d, (d & 3) == 0, As, Bs, acc);
 
-    float ra[2][4], rb[2][4];
-    auto gload = [&](int kc) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t ri = i0 + lrow + 64 * h, rj = j0 + lrow + 64 * h;
-            const int k = kc + lk;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { ra[h][q] = 0.0f; rb[h][q] = 0.0f; }
-            if (ri < n) {
-                if (vec && k + 3 < d) {
-                    float4 v = *reinterpret_cast<const float4 *>(X + ri * d + k);
-                    ra[h][0] = v.x; ra[h][1] = v.y; ra[h][2] = v.z; ra[h][3] = v.w;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (k + q < d) ra[h][q] = X[ri * d + k + q];
-                }
-            }
-            if (rj < n) {
-                if (vec && k + 3 < d) {
-                    float4 v = *reinterpret_cast<const float4 *>(X + rj * d + k);
-                    rb[h][0] = v.x; rb[h][1] = v.y; rb[h][2] = v.z; rb[h][3] = v.w;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (k + q < d) rb[h][q] = X[rj * d + k + q];
-                }
-            }
-        }
-    };
-
-    gload(0);
-    for (int kc = 0; kc < d; kc += DT_KC) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                As[lk + q][lrow + 64 * h] = ra[h][q];
-                Bs[lk + q][lrow + 64 * h] = rb[h][q];
-            }
-        __syncthreads();
-        if (kc + DT_KC < d) gload(kc + DT_KC);
-#pragma unroll
-        for (int k = 0; k < DT_KC; ++k) {
-            // zero-padded k beyond d contributes (0-0)^2 = +0: s + 0 == s exactly
-            float4 a0 = *reinterpret_cast<const float4 *>(&As[k][ty * 4]);
-            float4 a1 = *reinterpret_cast<const float4 *>(&As[k][64 + ty * 4]);
-            float4 b0 = *reinterpret_cast<const float4 *>(&Bs[k][tx * 4]);
-            float4 b1 = *reinterpret_cast<const float4 *>(&Bs[k][64 + tx * 4]);
-            const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-            for (int a = 0; a < 8; ++a)
-#pragma unroll
-                for (int b = 0; b < 8; b += 2) {
-                    f2 av2 = {av[a], av[a]};
-                    f2 bv2 = {bv[b], bv[b + 1]};
-                    f2 s2 = {acc[a][b], acc[a][b + 1]};
-                    f2 df = av2 - bv2;  // clustering.go:139
-                    f2 p = df * df;     // :154 product (rounded)
-                    s2 = s2 + p;        // :154 sum (rounded)
-                    acc[a][b] = s2.x;
-                    acc[a][b + 1] = s2.y;
-                }
-        }
-        __syncthreads();
-    }
-
-    // epilogue: (float(sa*sb)/float(sa+sb)) * sum   (clustering.go:142-144)
+    // epilogue: (float(sa*sb)/float(sa+sb)) * sum   (clustering.go:142-144, ward_scale)
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
         const int64_t i = i0 + (a < 4 ? ty * 4 + a : 64 + ty * 4 + (a - 4));
         if (i >= n) continue;
-        const int64_t sa = sizes ? sizes[i] : 1;
+        const int sa = sizes ? sizes[i] : 1;
 #pragma unroll
         for (int bh = 0; bh < 2; ++bh) {
             const int64_t jb = j0 + bh * 64 + tx * 4;
@@ -400,10 +283,7 @@ __global__ __launch_bounds__(256) void ward_dist_exact_kernel(const float *__res
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int64_t j = jb + q;
-                const int64_t sb = (sizes && j < n) ? sizes[j] : 1;
-                const float num = (float)(sa * sb);
-                const float den = (float)(sa + sb);
-                v[q] = (num / den) * acc[a][bh * 4 + q];
+                v[q] = ward_scale(acc[a][bh * 4 + q], sa, (sizes && j < n) ? sizes[j] : 1);
             }
             if (MODE == 0) {
                 float *row = out + rowoff[i];
@@ -4876,8 +4756,8 @@ static int launch_dist_exact_rows(icl_ctx *ctx, const float *d_X, const int32_t 
 {
     if (!strm) strm = ctx->stream;
     if (n <= 0 || tr_hi <= tr_lo) return ICL_OK;
-    const int64_t b_lo = tr_lo * (tr_lo + 1) / 2, nblocks = tr_hi * (tr_hi + 1) / 2 - b_lo;
-    if (nblocks > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "distance tile grid too large (n=%lld)", (long long)n);
+    int64_t nblocks;
+    ICL_TRY(icl_dist_grid(ctx, tr_lo, tr_hi, &nblocks));
     const int64_t r_lo = tr_lo * DT_TILE, r_hi = std::min<int64_t>(tr_hi * DT_TILE, n);
     const double pairs = 0.5 * ((double)r_hi * (double)(r_hi - 1) - (double)r_lo * (double)(r_lo - 1));
     icl_prof_scope ps(ctx, ICL_K_DIST_EXACT, pairs * 3.0 * d, 4.0 * r_hi * d + 4.0 * pairs);

@@ -111,7 +111,8 @@ def test_find_closest_matches_oracle_with_ties(ctx, n):
     assert ctx.find_closest(D) == O.find_closest(D)
 
 
-@pytest.mark.parametrize("n,d", [(1, 8), (2, 1), (33, 17), (128, 64), (129, 1000), (300, 2048), (257, 6)])
+@pytest.mark.parametrize("n,d", [(1, 8), (2, 1), (33, 17), (128, 64), (129, 1000), (300, 2048), (257, 6),
+                                 (1153, 6), (1153, 8)])  # ten tile rows: a second band of height 2, its cap, a ragged last tile; scalar and 16-byte loads
 def test_kat7_distance_matrix_bit_exact(ctx, n, d):
     rng = np.random.default_rng(n * 1000 + d)
     E = rng.standard_normal((n, d)).astype(np.float32)
