@@ -14,6 +14,7 @@ import "C"
 import (
 	"fmt"
 	"log"
+	"sort"
 	"unsafe"
 
 	"imageclust/internal/iclengine"
@@ -378,4 +379,70 @@ func NearestClusters(queries [][]float32, qSizes []int32, clusters []Cluster, k,
 		sizes[i] = int32(c.Size)
 	}
 	return iclengine.Nearest(queries, qSizes, centroids, sizes, k, maxSize, nil)
+}
+
+// DuplicatePair is one pair of images whose WardDistance as singletons is at most the threshold: A comes before B in the caller's list.
+type DuplicatePair struct {
+	A, B  string
+	Value float32
+}
+
+// DuplicatePairs lists EVERY pair of images whose WardDistance as singletons is at most threshold (iclengine.PairsWithin ->
+// icl_pairs_within: exact values, no cap on an image's partners, no distance matrix), each pair once, ordered by position.
+func DuplicatePairs(embeddings [][]float32, ids []string, threshold float32) ([]DuplicatePair, error) {
+	if len(embeddings) != len(ids) {
+		return nil, fmt.Errorf("%d embeddings for %d ids", len(embeddings), len(ids))
+	}
+	rowPtr, col, val, err := iclengine.PairsWithin(embeddings, nil, threshold)
+	if err != nil {
+		return nil, err
+	}
+	type at struct {
+		a, b int
+		v    float32
+	}
+	found := make([]at, 0, len(col))
+	for i := range ids {
+		for p := rowPtr[i]; p < rowPtr[i+1]; p++ {
+			found = append(found, at{int(col[p]), i, val[p]})
+		}
+	}
+	sort.Slice(found, func(x, y int) bool { return found[x].a < found[y].a || (found[x].a == found[y].a && found[x].b < found[y].b) })
+	out := make([]DuplicatePair, len(found))
+	for q, f := range found {
+		out[q] = DuplicatePair{A: ids[f.a], B: ids[f.b], Value: f.v}
+	}
+	return out, nil
+}
+
+// DuplicateGroups returns the connected components of DuplicatePairs' graph that have at least two members (iclengine.PairGroups ->
+// icl_pair_groups): members in position order, groups ordered by their first member.
+func DuplicateGroups(embeddings [][]float32, ids []string, threshold float32) ([][]string, error) {
+	if len(embeddings) != len(ids) {
+		return nil, fmt.Errorf("%d embeddings for %d ids", len(embeddings), len(ids))
+	}
+	rowPtr, col, _, err := iclengine.PairsWithin(embeddings, nil, threshold)
+	if err != nil {
+		return nil, err
+	}
+	group, _, err := iclengine.PairGroups(rowPtr, col)
+	if err != nil {
+		return nil, err
+	}
+	at := make(map[int32]int)
+	var out [][]string
+	for i, g := range group { // a group's first member is its smallest index: groups open in order of their first member
+		if g == int32(i) {
+			at[g] = len(out)
+			out = append(out, nil)
+		}
+		out[at[g]] = append(out[at[g]], ids[i])
+	}
+	kept := out[:0]
+	for _, m := range out {
+		if len(m) >= 2 {
+			kept = append(kept, m)
+		}
+	}
+	return kept, nil
 }

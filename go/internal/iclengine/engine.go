@@ -315,6 +315,71 @@ func Nearest(queries [][]float32, qSizes []int32, library [][]float32, eSizes []
 	return idx, val, nil
 }
 
+// PairsWithin is icl_pairs_within: EVERY pair of rows whose WardDistance (sizes[i] items per row; nil: all 1) is at most threshold, the
+// reference's values bit for bit, as a CSR list over the strict lower triangle: col[rowPtr[i]:rowPtr[i+1]] are row i's partners j < i
+// in ascending j, val their values.  No cap on a row's partners and no distance matrix.  The size query and the call proper are both
+// made here.
+func PairsWithin(rows [][]float32, sizes []int32, threshold float32) (rowPtr []int64, col []int32, val []float32, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, nil, nil, e
+	}
+	n, d := len(rows), 0
+	if n > 0 {
+		d = len(rows[0])
+	}
+	if sizes != nil && len(sizes) != n {
+		return nil, nil, nil, fmt.Errorf("%d sizes for %d rows", len(sizes), n)
+	}
+	if n == 0 { // no rows, no row length to pass: the empty list, as the Python mirror returns it
+		return []int64{0}, nil, nil, nil
+	}
+	flat := make([]float32, n*d+1) // [][]float32 cannot cross cgo: one contiguous buffer
+	for i, row := range rows {
+		copy(flat[i*d:(i+1)*d], row)
+	}
+	var sz *C.int32_t
+	if len(sizes) > 0 {
+		sz = (*C.int32_t)(unsafe.Pointer(&sizes[0]))
+	}
+	rowPtr = make([]int64, n+1)
+	total := C.int64_t(-1)
+	call := func(c *C.int32_t, v *C.float, cap int64) C.int {
+		return C.icl_pairs_within((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), sz, C.int64_t(n), C.int32_t(d), C.float(threshold),
+			(*C.int64_t)(unsafe.Pointer(&rowPtr[0])), c, v, C.int64_t(cap), &total)
+	}
+	if rc := call(nil, nil, 0); rc != C.ICL_OK {
+		return nil, nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	t := int64(total)
+	col, val = make([]int32, t+1), make([]float32, t+1)
+	if t > 0 {
+		if rc := call((*C.int32_t)(unsafe.Pointer(&col[0])), (*C.float)(unsafe.Pointer(&val[0])), t); rc != C.ICL_OK {
+			return nil, nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		}
+	}
+	return rowPtr, col[:t], val[:t], nil
+}
+
+// PairGroups is icl_pair_groups (host only): the connected components of the pair graph of a CSR list: group[i] is the smallest index
+// of i's component, nGroups the number of components with at least two members.
+func PairGroups(rowPtr []int64, col []int32) (group []int32, nGroups int, err error) {
+	if len(rowPtr) == 0 {
+		return nil, 0, fmt.Errorf("rowPtr needs n + 1 entries")
+	}
+	n := len(rowPtr) - 1
+	group = make([]int32, n+1)
+	var c *C.int32_t
+	if len(col) > 0 {
+		c = (*C.int32_t)(unsafe.Pointer(&col[0]))
+	}
+	var ng C.int64_t
+	if rc := C.icl_pair_groups(C.int64_t(n), (*C.int64_t)(unsafe.Pointer(&rowPtr[0])), c, (*C.int32_t)(unsafe.Pointer(&group[0])), &ng); rc != C.ICL_OK {
+		return nil, 0, fmt.Errorf("icl_pair_groups: malformed pair list")
+	}
+	return group[:n], int(ng), nil
+}
+
 // Where a qualifying PNG of the batched file calls is inflated and unfiltered: icl_set_png_options' modes.
 const (
 	PNGHost = int(C.ICL_PNG_HOST)

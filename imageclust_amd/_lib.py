@@ -144,6 +144,11 @@ SYMBOLS = [
     ("icl_nearest_from_matrix", _int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     ("icl_set_nearest_options", _int, [_vp, _i32]),
     ("icl_last_nearest_stats", _int, [_vp, _pi64]),
+    ("icl_pairs_within", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_pairs_within_dev", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_pairs_within_from_matrix", _int, [_vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_pair_groups", _int, [_i64, _vp, _vp, _vp, _pi64]),
+    ("icl_last_pairs_stats", _int, [_vp, _pi64]),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_requests_layout", _int, [_i32, _vp, _vp, _int, _vp, _vp, _pi64]),
@@ -277,6 +282,57 @@ def nearest_from_matrix(D, k, q_size=None, e_size=None, max_size=0, exclude=None
     if rc != ICL_OK:
         raise ICLError(rc, "icl_nearest_from_matrix: bad argument")
     return idx, val
+
+
+def _pairs_two_calls(n, call, what, cap=None):
+    """The size query and the call proper of the icl_pairs_within family -> (row_ptr int64[n + 1], col int32[total], val float32[total]).
+    call(row_ptr_address, col_address, val_address, cap, total) -> code; total is a ctypes int64 to pass by reference.  With a cap hint the
+    first call already carries buffers, and a second one follows only when they were too small; ICL_ERR_ARG with total left at -1 is
+    a bad argument."""
+    row_ptr = np.zeros(max(int(n), 0) + 1, np.int64)
+    cap = 0 if cap is None else max(int(cap), 0)
+    while True:
+        col, val, total = np.empty(cap, np.int32), np.empty(cap, np.float32), _i64(-1)
+        rc = call(row_ptr.ctypes.data, col.ctypes.data if cap else None, val.ctypes.data if cap else None, cap, total)
+        if rc == ICL_OK and total.value <= cap:
+            return row_ptr, col[:total.value], val[:total.value]
+        if rc not in (ICL_OK, ICL_ERR_ARG) or total.value <= cap:
+            raise ICLError(rc, "%s: bad argument" % what)
+        cap = total.value  # the size query's answer, or a hint that was too small
+
+
+def pairs_within_from_matrix(D, threshold, n=None):
+    """icl_pairs_within_from_matrix (host only, no GPU): Context.pairs_within's rule and layout applied to values the caller holds: the
+    strict lower triangle of the first n (default: all) rows and columns of D -> (row_ptr, col, val).  Raises ICLError(ICL_ERR_ARG)."""
+    D = np.asarray(D, np.float32)
+    if D.ndim != 2:
+        raise ValueError("D must be 2-D")
+    if not D.flags.c_contiguous:
+        D = np.ascontiguousarray(D)
+    ld = D.shape[1]
+    n = D.shape[0] if n is None else int(n)
+    if n > D.shape[0]:
+        raise ValueError("n = %d rows asked of a matrix of %d" % (n, D.shape[0]))
+    L = load()
+    return _pairs_two_calls(n, lambda rp, c, v, cap, tot: L.icl_pairs_within_from_matrix(D.ctypes.data if D.size else None, n, ld, float(threshold),
+                                                                                        rp, c, v, cap, C.byref(tot)), "icl_pairs_within_from_matrix")
+
+
+def pair_groups(row_ptr, col):
+    """icl_pair_groups (host only): the connected components of the pair graph of a CSR list -> (group int32[n], n_groups): group[i] is the
+    smallest index of i's component, n_groups the number of components of two or more.  Raises ICLError(ICL_ERR_ARG) for a malformed list."""
+    rp = np.ascontiguousarray(np.asarray(row_ptr).reshape(-1), np.int64)
+    if len(rp) < 1:
+        raise ValueError("row_ptr needs n + 1 entries")
+    cl = np.ascontiguousarray(np.asarray(col).reshape(-1), np.int32)
+    n = len(rp) - 1
+    if len(cl) < max(int(rp[-1]), 0):
+        raise ValueError("%d col entries for row_ptr[n] = %d" % (len(cl), rp[-1]))
+    group, ng = np.empty(n, np.int32), _i64(0)
+    rc = load().icl_pair_groups(n, rp.ctypes.data, cl.ctypes.data if cl.size else None, group.ctypes.data if n else None, C.byref(ng))
+    if rc != ICL_OK:
+        raise ICLError(rc, "icl_pair_groups: bad argument")
+    return group, int(ng.value)
 
 
 def _byte_view(buf):
@@ -895,6 +951,57 @@ class Context:
         info = (C.c_int64 * 4)()
         check(self.h, self.L.icl_last_nearest_stats(self.h, info))
         return {"splits": info[0], "tiles": info[1], "pairs": info[2], "workspace_bytes": info[3]}
+
+    def pairs_within(self, E, threshold, size=None, cap=None):
+        """icl_pairs_within: EVERY pair of rows of E whose WardDistance (sizes `size`, None: all 1) is at most threshold, bit for bit the
+        reference's values, as a CSR list over the strict lower triangle -> (row_ptr int64[n + 1], col int32[total], val float32[total]):
+        row i's partners j < i, ascending in j, are col[row_ptr[i]:row_ptr[i + 1]].  NaN values are never listed.  The size query and the
+        call proper are both made here; cap, a guess of the total, saves the query when it is large enough."""
+        Em = np.ascontiguousarray(E, np.float32)
+        if Em.ndim != 2:
+            raise ValueError("E must be 2-D, got %s" % (Em.shape,))
+        n, d = Em.shape
+        sz = _nearest_side(n, size, "size")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        return self._pairs_calls(n, cap, lambda rp, c, v, cp, tot: self.L.icl_pairs_within(self.h, ptr(Em), ptr(sz), n, d, float(threshold),
+                                                                                          rp, c, v, cp, C.byref(tot)))
+
+    def pairs_within_dev(self, d_E, n, d, threshold, size=None, cap=None):
+        """icl_pairs_within_dev on rows that are on the device already (d_E: n x d floats) -> (row_ptr, col, val) on the host, as
+        pairs_within.  col and val live on the device during the call and are downloaded here."""
+        sz = _nearest_side(n, size, "size")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
+
+        def call(rp, c, v, cp, tot):  # c / v: the host arrays of cp entries; the device call gets device buffers of the same length
+            bufs = [self.malloc(cp * 4), self.malloc(cp * 4)] if cp else [None, None]
+            try:
+                rc = self.L.icl_pairs_within_dev(self.h, as_vp(d_E), ptr(sz), n, d, float(threshold), rp, bufs[0], bufs[1], cp, C.byref(tot))
+                if rc == ICL_OK and 0 < tot.value <= cp:
+                    self.sync()
+                    check(self.h, self.L.icl_memcpy_d2h(self.h, c, _vp(bufs[0]), tot.value * 4))
+                    check(self.h, self.L.icl_memcpy_d2h(self.h, v, _vp(bufs[1]), tot.value * 4))
+                return rc
+            finally:
+                for p in bufs:
+                    if p is not None:
+                        self.free(p)
+
+        return self._pairs_calls(n, cap, call)
+
+    def _pairs_calls(self, n, cap, call):
+        try:
+            return _pairs_two_calls(n, call, "icl_pairs_within", cap)
+        except ICLError as e:
+            msg = self.L.icl_last_error(self.h)
+            raise ICLError(e.code, msg.decode() if msg else "") from None
+
+    def last_pairs_stats(self):
+        """The last pairs_within[_dev]: 128 x 128 tiles the count pass ran, tiles with a hit (the fill pass's), pairs evaluated in both
+        passes, workspace bytes."""
+        info = (C.c_int64 * 4)()
+        check(self.h, self.L.icl_last_pairs_stats(self.h, info))
+        return {"tiles": info[0], "hit_tiles": info[1], "pairs": info[2], "workspace_bytes": info[3]}
 
     def merge_centroid(self, ca, sa, cb, sb):
         ca = np.ascontiguousarray(ca, np.float32)

@@ -199,7 +199,8 @@ def NearestClusters(queries, q_sizes, centroids, sizes, k: int, maxSize: int = 0
 def NearDuplicates(embeddings, ids, k: int, threshold: float, ctx: Optional[_lib.Context] = None) -> List[Tuple[str, str, float]]:
     """Pairs of images whose WardDistance as singletons is at most threshold, from a self-join of the embeddings (icl_nearest with
     exclude[i] = i, the k nearest of every image) -> [(id_a, id_b, value), ...], a before b in `ids`, each pair once, ordered by position.
-    An image with more than k neighbours under the threshold reports its k nearest; a pair is reported when either side lists it."""
+    An image with more than k neighbours under the threshold reports its k nearest; a pair is reported when either side lists it.
+    DuplicatePairs is the complete call: every pair under the threshold, however many partners an image has."""
     ctx = ctx or default_context()
     E = np.asarray(embeddings, np.float32)
     if E.ndim != 2:
@@ -215,6 +216,45 @@ def NearDuplicates(embeddings, ids, k: int, threshold: float, ctx: Optional[_lib
             if j >= 0 and v <= threshold:  # (NaN fails the comparison)
                 found.setdefault((min(i, int(j)), max(i, int(j))), float(v))
     return [(ids[a], ids[b], v) for (a, b), v in sorted(found.items())]
+
+
+def _pairs_csr(embeddings, ids, threshold, ctx, engine):
+    """The embeddings as a matrix and their complete pair list (icl_pairs_within; `engine(E, threshold) -> (row_ptr, col, val)` stands in
+    for the GPU call in tests)."""
+    E = np.asarray(embeddings, np.float32)
+    if E.ndim != 2:
+        E = E.reshape(len(ids), -1)
+    if len(E) != len(ids):
+        raise ValueError("%d embeddings for %d ids" % (len(E), len(ids)))
+    if len(E) == 0:
+        return E, (np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
+    if engine is not None:
+        return E, engine(E, threshold)
+    return E, (ctx or default_context()).pairs_within(E, threshold)
+
+
+def DuplicatePairs(embeddings, ids, threshold: float, ctx: Optional[_lib.Context] = None, engine=None) -> List[Tuple[str, str, float]]:
+    """EVERY pair of images whose WardDistance as singletons is at most threshold (icl_pairs_within: exact values, no cap on an image's
+    partners, no distance matrix) -> [(id_a, id_b, value), ...], a before b in `ids`, each pair once, ordered by position: NearDuplicates'
+    shape, but complete.  NaN values are never reported."""
+    _, (row_ptr, col, val) = _pairs_csr(embeddings, ids, threshold, ctx, engine)
+    found = []
+    for i in range(len(row_ptr) - 1):
+        for p in range(int(row_ptr[i]), int(row_ptr[i + 1])):
+            found.append((int(col[p]), i, float(val[p])))
+    found.sort(key=lambda t: (t[0], t[1]))
+    return [(ids[a], ids[b], v) for a, b, v in found]
+
+
+def DuplicateGroups(embeddings, ids, threshold: float, ctx: Optional[_lib.Context] = None, engine=None) -> List[List[str]]:
+    """The connected components of DuplicatePairs' graph with at least two members (icl_pair_groups) -> [[id, ...], ...]: members in
+    position order, groups ordered by their first member."""
+    _, (row_ptr, col, _) = _pairs_csr(embeddings, ids, threshold, ctx, engine)
+    group, _ = _lib.pair_groups(row_ptr, col)
+    members: Dict[int, List[str]] = {}
+    for i, g in enumerate(group):
+        members.setdefault(int(g), []).append(ids[i])
+    return [m for _, m in sorted(members.items()) if len(m) >= 2]
 
 
 @dataclass

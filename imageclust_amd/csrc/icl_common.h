@@ -33,6 +33,7 @@ struct icl_many_ws; // ward_many.hip
 struct icl_requests_ws; // requests.hip
 struct icl_jenc_ws; // jpeg_encode_gpu.hip
 struct icl_nearest_ws; // nearest.hip
+struct icl_pairs_ws; // pairs.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -154,6 +155,8 @@ struct icl_ctx {
     icl_nearest_ws *nearest = nullptr;   // device copies of sizes / exclude and the partial lists of icl_nearest (nearest.hip; created on first use)
     int nearest_splits = 0;              // icl_set_nearest_options: column splits per band of query rows (0: the engine decides)
     int64_t nearest_stats[4] = {0, 0, 0, 0}; // last icl_nearest[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_nearest_stats)
+    icl_pairs_ws *pairs = nullptr;       // row counts, tile flags and row_ptr of icl_pairs_within on the device (pairs.hip; created on first use)
+    int64_t pairs_stats[4] = {0, 0, 0, 0}; // last icl_pairs_within[_dev]: tiles run in pass 1, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
@@ -216,6 +219,7 @@ void icl_many_free(icl_ctx *ctx);
 void icl_requests_free(icl_ctx *ctx);
 void icl_jenc_free(icl_ctx *ctx);
 void icl_nearest_free(icl_ctx *ctx);
+void icl_pairs_free(icl_ctx *ctx);
 
 // The two batched halves icl_cluster_requests (requests.hip) joins; both expect ctx->mu held and the context's device selected.
 // Each tells its caller apart what the return code alone cannot: "the list was processed and an item of it failed" from "the call stopped".

@@ -88,6 +88,7 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     icl_requests_free(ctx);
     icl_jenc_free(ctx);
     icl_nearest_free(ctx);
+    icl_pairs_free(ctx);
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

@@ -447,6 +447,48 @@ int icl_nearest_from_matrix(const float *D, int64_t nq, int64_t n, int64_t ld, c
 int icl_set_nearest_options(icl_ctx *ctx, int32_t column_splits);
 /* The last icl_nearest[_dev] of the context: info = splits used, tiles run, pairs evaluated, workspace bytes (all 0 after a call with nq == 0). */
 int icl_last_nearest_stats(icl_ctx *ctx, int64_t info[4]);
+/* ---- duplicate pairs: every pair of rows whose WardDistance is at most a threshold, exact and complete, no distance matrix (DESIGN.md "Duplicate pairs") ----
+ * E holds n rows of d floats; size[n] are the rows' item counts (NULL: all 1).
+ * VALUE of pair (i, j), j < i < n: WardDistance (clustering.go:136-157) of a cluster of size[i] items at E[i] and one of size[j] items at E[j],
+ * bit for bit -- differences, products and the sum each rounded, strictly in k order, then (float(sa*sb) / float(sa+sb)) * s.  With size NULL
+ * the values are the entries of ComputeInitialDistanceMatrix (:61-73).
+ * PAIR SET: every pair with value <= threshold as an fp32 comparison, however many partners a row has.  A NaN value is never listed; a
+ * threshold of -0.0f admits zero values; +Inf admits everything that is not NaN.  A NaN threshold is ICL_ERR_ARG.
+ * ORDER AND LAYOUT (CSR over the strict lower triangle): col[row_ptr[i] .. row_ptr[i + 1]) are row i's partners j < i in ascending j and val
+ * holds their values at the same places; row_ptr[0] = 0 and *total = row_ptr[n].  Each pair appears once.  The result does not depend on
+ * tile order, launch geometry or the order in which workgroups finish.
+ * CAPACITY: col and val hold cap entries each.  row_ptr (n + 1 entries) and *total are always complete and exact.  If *total > cap the call
+ * returns ICL_ERR_ARG with those two filled and col / val unspecified (icl_jpeg_encode_rgb_dev's convention: ask again with a buffer of
+ * *total entries; a caller tells this case from a bad argument by *total, which a bad argument leaves untouched).  col == NULL && val == NULL
+ * && cap == 0 is the size query and returns ICL_OK.
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context, row_ptr, total; E when n > 1; one of col / val
+ * without the other, or both NULL with cap > 0), d < 1, n < 0, n >= 2^31, a size <= 0, cap < 0, a NaN threshold, or an n whose triangle of
+ * 128 x 128 tiles does not fit one launch (2^31 tiles); n <= 1 is ICL_OK with *total = 0; ICL_ERR_UNSUPPORTED on a context that is a
+ * replica of a group; ICL_ERR_NOMEM when the workspace, or in the host form the device copies of E, col and val, do not fit.
+ * icl_pairs_within takes host memory throughout: it uploads, runs the _dev body and downloads.  icl_pairs_within_dev takes E, col and val on
+ * the context's device (col and val are written on the context's stream; E 16-byte aligned with d % 4 == 0 takes the wide loads, anything
+ * else the scalar loads, with equal results); size and row_ptr stay in host memory, and row_ptr and *total are final at return.
+ * COST: no n x n array exists anywhere.  A count pass evaluates every tile of the triangle once; a fill pass evaluates the tiles that hold
+ * a listed pair a second time.  With rare duplicates that is a negligible share; with threshold = +Inf it is the whole triangle twice.
+ * The fill pass gives each row of tiles to one workgroup, which walks that row's tiles one after the other: a dense result at large n takes
+ * longer than two count passes (the longest row of tiles sets the time; not measured).
+ * The workspace is 4 n bytes of sizes, 4 n of counts, 8 (n + 1) of row_ptr, one byte per tile and 4 bytes per tile row. */
+int icl_pairs_within(icl_ctx *ctx, const float *E, const int32_t *size, int64_t n, int32_t d, float threshold, int64_t *row_ptr, int32_t *col,
+                     float *val, int64_t cap, int64_t *total);
+int icl_pairs_within_dev(icl_ctx *ctx, const float *d_E, const int32_t *size, int64_t n, int32_t d, float threshold, int64_t *row_ptr,
+                         int32_t *d_col, float *d_val, int64_t cap, int64_t *total);
+/* The same pair rule, layout and capacity convention applied to values the caller already holds (host only: no context, no GPU), e.g. the
+ * result of icl_ward_distance_matrix: D[i * ld + j], j < i, is pair (i, j)'s value, used as given; nothing else of D is read.  The
+ * comparison is the code the device runs (pairs_select.h).  ICL_ERR_ARG, with nothing written, as above (D is needed when n > 1) and for ld < n. */
+int icl_pairs_within_from_matrix(const float *D, int64_t n, int64_t ld, float threshold, int64_t *row_ptr, int32_t *col, float *val, int64_t cap,
+                                 int64_t *total);
+/* The connected components of the pair graph a CSR list describes (host only): group[i] is the smallest index of i's component -- an image
+ * with no partner is its own group --, *n_groups the number of components with at least two members.  ICL_ERR_ARG, with nothing written, for
+ * a null pointer that is needed, n < 0, n >= 2^31, row_ptr[0] != 0, a row_ptr that decreases or a col entry of row i outside [0, i). */
+int icl_pair_groups(int64_t n, const int64_t *row_ptr, const int32_t *col, int32_t *group, int64_t *n_groups);
+/* The last icl_pairs_within[_dev] of the context: info = tiles run in the count pass, tiles with a hit, pairs j < i < n evaluated (both
+ * passes; the fill pass counts when it ran), workspace bytes (all 0 after a call with n <= 1). */
+int icl_last_pairs_stats(icl_ctx *ctx, int64_t info[4]);
 /* ---- a queue of requests, files to cluster ids: replaces workflow.Run (workflow.go:84-94) for nreq requests in ONE call ----
  * Request r is n[r] image files with labels.  Every image gets its embedding row (GetImageEmbedding; head, prec as icl_embed_files), a one-hot
  * vector over the request's label set is appended (GenerateLabelVector + CombineEmbeddings, embeddings.go:166-183: d[r] = head + n_labels[r]
