@@ -210,6 +210,18 @@ def check(ctx_handle, rc):
         raise ICLError(rc, msg.decode() if msg else "")
 
 
+def _many_outputs(pk, want_merges):
+    """The output arrays of a many-call over pk's problems: cluster_id, rank, n_clusters, n_merges, status, merge log (or None), in
+    _unpack_many's order.  The statuses stay -1 when the call fails before the problems run (with a code that is no problem's own)."""
+    nprob, rows = len(pk["n"]), int(pk["img_off"][-1])
+    cid = np.full(max(rows, 1), -1, np.int32)
+    rank = np.full(max(rows, 1), -1, np.int32)
+    nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
+    st = np.full(max(nprob, 1), -1, np.int32)
+    mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+    return cid, rank, nc, nm, st, mg
+
+
 def _unpack_many(pk, cid, rank, nc, nm, st, mg):
     out = []
     for p in range(len(pk["n"])):
@@ -1037,18 +1049,18 @@ class Context:
         ids, as last_merges()).  raise_on_error=True raises the lowest failed problem's error instead."""
         pk = pack_many(problems)
         nprob = len(problems)
-        rows = int(pk["img_off"][-1])
-        cid = np.full(max(rows, 1), -1, np.int32)
-        rank = np.full(max(rows, 1), -1, np.int32)
-        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
-        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
-        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        outs = cid, rank, nc, nm, st, mg = _many_outputs(pk, want_merges)
         rc = self.L.icl_cluster_many(self.h, nprob, pk["E"].ctypes.data, pk["E"].size, pk["e_off"].ctypes.data, pk["n"].ctypes.data,
                                      pk["d"].ctypes.data, pk["min_size"].ctypes.data, pk["max_size"].ctypes.data, cid.ctypes.data,
                                      rank.ctypes.data, nc.ctypes.data, nm.ctypes.data, mg.ctypes.data if want_merges else None, st.ctypes.data)
-        if rc != ICL_OK and (raise_on_error or (st[:nprob] < 0).any()):
-            check(self.h, rc)  # an argument or device error: no per-problem results
-        return _unpack_many(pk, cid, rank, nc, nm, st, mg)
+        return self._many_results(rc, pk, outs, raise_on_error)
+
+    def _many_results(self, rc, pk, outs, raise_on_error=False):
+        """What a many-call returns (_unpack_many), from its code and its _many_outputs.  Raises when the code is not a problem's own -- an
+        argument or device error: no per-problem status was written -- or, with raise_on_error, for the lowest failed problem."""
+        if rc != ICL_OK and (raise_on_error or (outs[4][:len(pk["n"])] < 0).any()):
+            check(self.h, rc)
+        return _unpack_many(pk, *outs)
 
     def set_many_options(self, mid_mode=MANY_MID_AUTO):
         """icl_set_many_options: whether cluster_many runs problems of 257 to 2048 rows one workgroup each (MANY_MID_ON), never
@@ -1084,21 +1096,15 @@ class Context:
 
     def _requests_call(self, fn, pk, images, head, prec, threads, want_merges, want_E):
         nreq, rows = len(pk["n"]), int(pk["img_off"][-1])
-        cid = np.full(max(rows, 1), -1, np.int32)
-        rank = np.full(max(rows, 1), -1, np.int32)
-        nc, nm = np.zeros(max(nreq, 1), np.int32), np.zeros(max(nreq, 1), np.int32)
-        st = np.full(max(nreq, 1), -1, np.int32)  # left untouched (imageclust.h) when the call fails with a code that is no request's own
+        outs = cid, rank, nc, nm, st, mg = _many_outputs(pk, want_merges)
         fst = np.zeros(max(rows, 1), np.int32)
-        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
         E = np.zeros(max(pk["e_len"], 1), np.float32) if want_E else None
         ptr = lambda a: a.ctypes.data
         rc = fn(self.h, nreq, *images, ptr(pk["n"]), ptr(pk["n_labels"]), ptr(pk["label_off"]), ptr(pk["label_idx"]),
                                          ptr(pk["min_size"]), ptr(pk["max_size"]), head, prec, threads, ptr(cid), ptr(rank), ptr(nc), ptr(nm),
                                          ptr(mg) if want_merges else None, ptr(st), ptr(fst), ptr(E) if want_E else None)
-        if rc != ICL_OK and (st[:nreq] < 0).any():
-            check(self.h, rc)
+        out = self._many_results(rc, pk, outs)
         self.last_file_status, self.last_requests_rc = fst[:rows].copy(), rc
-        out = _unpack_many(pk, cid, rank, nc, nm, st, mg)
         if want_E:
             out = [r + (E[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)
                    for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]
@@ -1116,18 +1122,11 @@ class Context:
                   min_size=np.ascontiguousarray(min_size, np.int32), max_size=np.ascontiguousarray(max_size, np.int32))
         nprob = len(pk["n"])
         pk["img_off"] = np.concatenate([[0], np.cumsum(pk["n"], dtype=np.int64)])
-        rows = int(pk["img_off"][-1])
-        cid = np.full(max(rows, 1), -1, np.int32)
-        rank = np.full(max(rows, 1), -1, np.int32)
-        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
-        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
-        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        outs = cid, rank, nc, nm, st, mg = _many_outputs(pk, want_merges)
         rc = self.L.icl_cluster_many_dev(self.h, nprob, _vp(d_E), int(e_len), pk["e_off"].ctypes.data, pk["n"].ctypes.data, pk["d"].ctypes.data,
                                          pk["min_size"].ctypes.data, pk["max_size"].ctypes.data, cid.ctypes.data, rank.ctypes.data,
                                          nc.ctypes.data, nm.ctypes.data, mg.ctypes.data if want_merges else None, st.ctypes.data)
-        if rc != ICL_OK and (st[:nprob] < 0).any():
-            check(self.h, rc)
-        return _unpack_many(pk, cid, rank, nc, nm, st, mg)
+        return self._many_results(rc, pk, outs)
 
     def cluster_many_seeded(self, problems, want_merges=False, want_centroids=False, raise_on_error=False, dev=False):
         """icl_cluster_many_seeded: the clustering loop started from existing clusters.  problems = [(C, seed_size, min_size, max_size[,
@@ -1137,7 +1136,7 @@ class Context:
         (seed i has id i, merge t id m + t), want_centroids then appends C_out (m x d: the row of each final cluster's rank-0 seed is
         the cluster's centroid, every other row zero).  dev=True runs icl_cluster_many_seeded_dev on a device copy (the same result)."""
         pk = pack_many([(pr[0], pr[2], pr[3]) for pr in problems])
-        nprob, rows = len(problems), int(pk["img_off"][-1])
+        nprob = len(problems)
         sizes = [np.asarray(pr[1], np.int32).reshape(-1) for pr in problems]
         for p, sz in enumerate(sizes):
             if len(sz) != int(pk["n"][p]):
@@ -1145,11 +1144,7 @@ class Context:
         ss = np.ascontiguousarray(np.concatenate(sizes + [np.zeros(0, np.int32)]), np.int32)
         ss = ss if ss.size else np.zeros(1, np.int32)
         kt = np.array([int(pr[4]) if len(pr) > 4 else 0 for pr in problems] + ([] if nprob else [0]), np.int32)
-        cid = np.full(max(rows, 1), -1, np.int32)
-        rank = np.full(max(rows, 1), -1, np.int32)
-        nc, nm = np.zeros(max(nprob, 1), np.int32), np.zeros(max(nprob, 1), np.int32)
-        st = np.full(max(nprob, 1), -1, np.int32)  # stays -1 when the call fails before the problems run
-        mg = np.zeros(max(2 * rows, 1), np.int32) if want_merges else None
+        outs = cid, rank, nc, nm, st, mg = _many_outputs(pk, want_merges)
         co = np.zeros(pk["E"].size, np.float32) if want_centroids else None
         ptr = lambda a: a.ctypes.data if a is not None else None
         tail = (ptr(pk["e_off"]), ptr(pk["n"]), ptr(pk["d"]), ptr(ss), ptr(pk["min_size"]), ptr(pk["max_size"]), ptr(kt), ptr(cid), ptr(rank),
@@ -1169,9 +1164,7 @@ class Context:
                     self.free(dC)
         else:
             rc = self.L.icl_cluster_many_seeded(self.h, nprob, ptr(pk["E"]), pk["E"].size, *tail, ptr(co))
-        if rc != ICL_OK and (raise_on_error or (st[:nprob] < 0).any()):
-            check(self.h, rc)  # an argument or device error: no per-problem results
-        out = _unpack_many(pk, cid, rank, nc, nm, st, mg)
+        out = self._many_results(rc, pk, outs, raise_on_error)
         if want_centroids:
             out = [r + (co[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)
                    for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]

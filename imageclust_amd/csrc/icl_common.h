@@ -291,11 +291,8 @@ int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const flo
                         const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
                         int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest = nullptr);
 
-// ward_many.hip: the final-list rule of the seeded calls (DESIGN.md "Seeded clustering" item 5) for one problem of m seeds and a log of nmerge
-// (a, b) pairs -> cluster_id[m], seed_rank[m], n_clusters; finals (may be null): (creation id, rank-0 seed) of every final cluster, dropped ones
-// included.  ICL_ERR_ARG with `why` set for a size of 0 or a corrupt log.  Shared by icl_cluster_many_seeded and icl_cluster_seeded (ward.hip).
-int wm_seeded_ids(int64_t m, const int32_t *seed_size, int32_t min_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
-                  int32_t *seed_rank, int32_t *n_clusters, std::vector<int32_t> *finals, std::string &why);
+// the rules every clustering call shares: CalculateOptimalClusters, the admission of a seeded problem, the final cluster list
+#include "ward_seeds.h"
 
 static inline int64_t icl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -4735,19 +4735,7 @@ static int fc_ensure(icl_ctx *ctx, int64_t n)
     return ICL_OK;
 }
 
-extern "C" int icl_calc_optimal_clusters(int64_t total, int64_t min_size, int64_t max_size, int64_t *k)
-{
-    // clustering.go:168-186.  min/max < 1 divide by zero in the reference (implementation-defined int
-    // conversion of +Inf); rejected here.
-    if (!k) return ICL_ERR_ARG;
-    if (min_size < 1 || max_size < 1) return ICL_ERR_CONSTRAINT;
-    if (total < min_size) return ICL_ERR_CONSTRAINT;
-    const int64_t lo = (int64_t)std::ceil((double)total / (double)max_size);
-    const int64_t hi = (int64_t)std::floor((double)total / (double)min_size);
-    if (lo > hi) return ICL_ERR_CONSTRAINT;
-    *k = lo < hi ? (lo + hi) / 2 : lo;
-    return ICL_OK;
-}
+extern "C" int icl_calc_optimal_clusters(int64_t total, int64_t min_size, int64_t max_size, int64_t *k) { return ward_optimal_k(total, min_size, max_size, k); }
 
 // Tile rows [tr_lo, tr_hi) of the lower triangle (tile row ti holds ti+1 tiles of 128 x 128 pairs).  In mode 0 `out` is the
 // address row 0 of the packed triangle WOULD have: a caller that holds only the span of its own rows passes span - rowoff[first row].
@@ -4869,55 +4857,16 @@ extern "C" int icl_find_closest(icl_ctx *ctx, const float *D, int64_t n, int64_t
     });
 }
 
-// Build the reference's final cluster list from the merge log (clustering.go:265-280 and SURVEY.md 8a C11):
-// surviving singletons in index order, then merged clusters in creation order; members of Merge(a,b) are
-// a's then b's (:31); clusters below min_size are dropped and consume no id.
-// (Also ward_many.hip's rule, whichever route a problem takes.)
-int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const std::vector<int32_t> &pairs,
-                        int64_t nmerge, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters)
+// The final cluster list of a call that starts from singletons: ward_final_list (ward_seeds.h) with every row counting one item, and the
+// check of the largest final cluster.  (Also ward_many.hip's, whichever route a problem takes.)
+int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
+                        int32_t *member_rank, int32_t *n_clusters)
 {
-    const int64_t M = n + nmerge;
-    std::vector<int32_t> left((size_t)M, -1), right((size_t)M, -1), size((size_t)M, 1);
-    std::vector<uint8_t> alive((size_t)M, 1);
-    for (int64_t t = 0; t < nmerge; ++t) {
-        const int32_t a = pairs[2 * t], b = pairs[2 * t + 1];
-        const int64_t c = n + t;
-        if (a < 0 || b < 0 || a >= c || b >= c || !alive[a] || !alive[b])
-            return icl_fail(ctx, ICL_ERR_HIP, "corrupt merge log at step %lld (%d,%d)", (long long)t, a, b);
-        left[c] = a;
-        right[c] = b;
-        size[c] = size[a] + size[b];
-        alive[a] = alive[b] = 0;
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        cluster_id[i] = -1;
-        member_rank[i] = -1;
-    }
-    int32_t cid = 0;
-    int rc = ICL_OK;
-    std::vector<int32_t> stack;
-    for (int64_t c = 0; c < M; ++c) {
-        if (!alive[c]) continue;
-        if (size[c] > max_size) rc = icl_fail(ctx, ICL_ERR_OVERSIZE, "cluster of size %d exceeds maxSize %d (splitCluster is not implemented)", size[c], max_size);
-        if (size[c] < min_size) continue; // clustering.go:268-271
-        int32_t rank = 0;
-        stack.clear();
-        stack.push_back((int32_t)c);
-        while (!stack.empty()) {
-            const int32_t x = stack.back();
-            stack.pop_back();
-            if (x < n) {
-                cluster_id[x] = cid;
-                member_rank[x] = rank++;
-            } else {
-                stack.push_back(right[x]); // visited after left: a's members first
-                stack.push_back(left[x]);
-            }
-        }
-        ++cid;
-    }
-    *n_clusters = cid;
-    return rc;
+    const ward_list_result r = ward_final_list(n, nullptr, min_size, pairs, nmerge, cluster_id, member_rank, n_clusters, nullptr);
+    if (r.kind != ward_list_result::OK) return icl_fail(ctx, ICL_ERR_HIP, "%s", ward_list_text(r).c_str());
+    if (r.largest > max_size)
+        return icl_fail(ctx, ICL_ERR_OVERSIZE, "cluster of size %d exceeds maxSize %d (splitCluster is not implemented)", (int)r.largest, max_size);
+    return ICL_OK;
 }
 
 // error constants of the bound (DESIGN.md section 3 "The bound"): ceps = (gamma / 2 + 16 u)(1 + 64 u), gam = (1 + u)^(D + 2) - 1, both rounded up
@@ -4980,9 +4929,10 @@ __global__ __launch_bounds__(256) void ward_symmetrize_kernel(float *__restrict_
 // spare workgroups of a batched update launch (see WB_R)
 static int ward_nspare(const icl_ctx *ctx, bool lb_rows, bool sharded) { return (lb_rows && !sharded && ctx->prop.multiProcessorCount >= 256) ? WB_NSP_LB : WB_NSP_X; }
 
-// ---- the clustering call's host driver: cluster_locked (below) = ward_check_args -> ward_make_plan -> ward_init_ws -> ward_fill -> ward_run_single /
-// ward_run_batched -> ward_collect; every decision of a call is made once, in its ward_plan.
-// what one clustering call holds beside the workspace: all of it until cluster_locked returns (a hipFree / hipHostFree in mid-call would wait for the device)
+// ---- the clustering call's host driver: ward_run_stages (below) = ward_make_plan -> ward_init_ws -> ward_fill -> ward_run_single / ward_run_batched ->
+// ward_collect, for cluster_locked (ward_check_args in front, icl_ward_assign_ids behind) and cluster_seeded_locked (ward_seed_admit in front,
+// ward_final_list behind); every decision of a call is made once, in its ward_plan.
+// what one clustering call holds beside the workspace: all of it until ward_run_stages returns (a hipFree / hipHostFree in mid-call would wait for the device)
 struct ward_call {
     struct shard_guard { // a replica of a sharded group call that leaves early releases the replicas waiting for it (icl_ward_shard::wait)
         icl_ward_shard *s = nullptr;
@@ -5000,9 +4950,9 @@ constexpr int GRAPH_STEPS = 64;
 // EFFECTIVE sizes -- the seed's items, or max_size for a frozen seed, the largest size the ban still refuses with every partner --, the host
 // keeps the real ones for the final list.  Such a call runs the exact fill and the exact rows only: the bounds are proven for singletons.
 struct ward_seed {
-    const int32_t *h_size; // [n] as the caller gave them (negative: frozen)
-    const int32_t *d_eff;  // [n] on the device: effective sizes
-    int64_t T;             // merges asked for: max(0, n - k), k from k_target or CalculateOptimalClusters(items)
+    const int32_t *h_eff; // [n] effective sizes (ward_seed_admit)
+    int64_t T;            // merges asked for: max(0, n - k), k from k_target or CalculateOptimalClusters(items)
+    const int32_t *d_eff; // ... on the device: ward_run_stages' copy (ward_call::eff)
 };
 enum { WARD_FILL_EXACT, WARD_FILL_BOUND_F32, WARD_FILL_BOUND_I8, WARD_FILL_FAST }; // how a call fills its own rows of the initial matrix
 struct ward_plan {
@@ -5459,9 +5409,8 @@ static void ward_timers_report(const ward_state &hst, const ward_plan &p, const 
 #endif
 }
 
-// The state read back: the convergence check, the merge log, ctx->last, the profile attribution and the reference's cluster list.
-static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, ward_call &c, int32_t min_size, int32_t *cluster_id,
-                        int32_t *member_rank, int32_t *n_clusters)
+// The state read back: the convergence check, the merge log, ctx->last and the profile attribution.
+static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf, ward_call &c)
 {
     ward_state hst;
     ICL_HIP(ctx, hipMemcpyAsync(&hst, w->st, sizeof hst, hipMemcpyDeviceToHost, ctx->stream));
@@ -5514,25 +5463,27 @@ static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const 
     ctx->last.merge_ms = ms12;
     icl_prof_collect(ctx);
     c.shard.ok = true; // the merge loop is over: nobody waits for this replica any more
-    // (a seeded call makes its final list from ctx->last.merges and the seeds' real sizes: cluster_seeded_locked)
-    int rc = p.seed ? ICL_OK : icl_ward_assign_ids(ctx, p.n, min_size, p.max_size, pairs, nmerge, cluster_id, member_rank, n_clusters);
-    ctx->last.merges.swap(pairs);
-    return rc;
+    ctx->last.merges.swap(pairs); // (the callers make their final lists from it)
+    return ICL_OK;
 }
 
-static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update,
-                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int64_t own_lo = 0, int64_t own_hi = -1)
+// The stages of one clustering call on n > 0 rows that passed the caller's checks, up to ctx->last (its merges: the log).  seed (may be null):
+// the rows are seed clusters, and max_size is the clamped one (ward_admission::kmax).
+static int ward_run_stages(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi,
+                           ward_seed *seed = nullptr)
 {
-    ICL_TRY(ward_check_args(ctx, n, min_size, max_size, update));
-    ctx->last.merges.clear();
-    *n_clusters = 0;
-    if (n == 0) return ICL_OK;
     ward_call c;
     c.shard.s = ctx->shard;
     ICL_TRY(ward_ensure(ctx, n, d));
     icl_ward_ws *w = ctx->ward;
+    if (seed) {
+        if (hipMalloc(&c.eff.p, (size_t)n * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld seed sizes on the device", (long long)n);
+        ICL_HIP(ctx, hipMemcpyAsync(c.eff.p, seed->h_eff, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_eff is the caller's to free once this returns, whatever it returns)
+        seed->d_eff = (const int32_t *)c.eff.p;
+    }
     ward_plan p;
-    ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p));
+    ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p, seed));
     ICL_HIP(ctx, hipEventCreate(&c.e0.p));
     ICL_HIP(ctx, hipEventCreate(&c.e1.p));
     ICL_HIP(ctx, hipEventCreate(&c.e2.p));
@@ -5544,19 +5495,31 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
     ICL_TRY(p.batched ? ward_run_batched(ctx, w, p, rf, c) : ward_run_single(ctx, w, p, rf));
     ICL_HIP(ctx, hipGetLastError());
     ICL_HIP(ctx, hipEventRecord(c.e2.p, ctx->stream));
-    const int rc = ward_collect(ctx, w, p, rf, c, min_size, cluster_id, member_rank, n_clusters);
-    if (rc == ICL_OK) { // (icl_ward_dump_pairs_dev reads the workspace as this call leaves it)
-        w->dump.state = (p.lw || p.sh) ? 2 : 1;
-        w->dump.n = n, w->dump.d = d, w->dump.max_size = max_size, w->dump.rows = p.rows;
-        w->dump.lbm = p.lbm, w->dump.wide = rf.wide != 0;
-    }
+    ICL_TRY(ward_collect(ctx, w, p, rf, c));
+    // icl_ward_dump_pairs_dev reads the workspace as this call leaves it, and as singletons: 1 where it can
+    w->dump.state = (p.lw || p.sh || seed) ? 2 : 1;
+    w->dump.n = n, w->dump.d = d, w->dump.max_size = max_size, w->dump.rows = p.rows;
+    w->dump.lbm = p.lbm, w->dump.wide = rf.wide != 0;
+    return ICL_OK;
+}
+
+static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update,
+                          int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int64_t own_lo = 0, int64_t own_hi = -1)
+{
+    ICL_TRY(ward_check_args(ctx, n, min_size, max_size, update));
+    ctx->last.merges.clear();
+    *n_clusters = 0;
+    if (n == 0) return ICL_OK;
+    ICL_TRY(ward_run_stages(ctx, d_E, n, d, min_size, max_size, update, own_lo, own_hi));
+    const int rc = icl_ward_assign_ids(ctx, n, min_size, max_size, ctx->last.merges.data(), (int64_t)ctx->last.merges.size() / 2, cluster_id, member_rank, n_clusters);
+    if (rc != ICL_OK) ctx->ward->dump.state = 0; // (no finished call)
     return rc;
 }
 
 // ---- seeded clustering on this engine (icl_cluster_seeded[_dev]; DESIGN.md "Seeded clustering", the large-N route) -----------------------------
-// cluster_locked's twin for ONE problem of m seed clusters with icl_cluster_many_seeded's semantics and no cap on m: the same stages with a
-// ward_seed in the plan.  d_C: the seed centroids on the device; seed_size on the host (no entry 0: checked by the entry points); d_C_out:
-// device, or null.  A problem the call refuses (ICL_ERR_UNSUPPORTED / ICL_ERR_CONSTRAINT) gets rows of -1 and a C_out of zeros, as the many-call's.
+// ONE problem of m seed clusters with icl_cluster_many_seeded's semantics (ward_seed_admit) and no cap on m: ward_run_stages with a ward_seed, the
+// final list from the seeds' real sizes.  d_C: the seed centroids on the device; seed_size on the host (no entry 0: checked by the entry points);
+// d_C_out: device, or null.  A problem the call refuses (ICL_ERR_UNSUPPORTED / ICL_ERR_CONSTRAINT) gets rows of -1 and a C_out of zeros, as the many-call's.
 static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
                                  int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
 {
@@ -5579,56 +5542,23 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
             return (int)ICL_ERR_HIP;
         return code;
     };
-    int64_t N = 0, big = -1, k = 0;
-    for (int64_t i = 0; i < m; ++i) {
-        N += std::llabs((long long)seed_size[i]);
-        if (seed_size[i] > max_size && big < 0) big = i;
-    }
     if (ctx->shard) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: not on a replica of a group");
-    if (N >= (1LL << 30)) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: %lld items in all", (long long)N);
-    if (big >= 0) // the reference would split it (clustering.go:251-258)
-        return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: seed %lld holds %d items, above maxSize (%d), and is not frozen", (long long)big,
-                        seed_size[big], max_size);
-    if (k_target > 0) k = k_target;
-    else if (icl_calc_optimal_clusters(N, min_size, max_size, &k) != ICL_OK)
-        return icl_fail(ctx, refuse(ICL_ERR_CONSTRAINT), "cannot satisfy cluster size constraints with total items (%lld), minSize (%d), and maxSize (%d)",
-                        (long long)N, min_size, max_size);
-    // the max_size the kernels see, clamped to [1, N]: no size sum of unfrozen seeds is above N, and a frozen seed's effective size fits the packed words
-    const int32_t kmax = (int32_t)std::min<int64_t>(std::max<int64_t>(max_size, 1), std::max<int64_t>(N, 1));
-    const int64_t T = std::max<int64_t>(0, m - k);
-    ward_call c;
+    std::vector<int32_t> eff((size_t)m);
+    const ward_admission ad = ward_seed_admit(m, seed_size, min_size, max_size, k_target, eff.data());
+    if (ad.status != ICL_OK) // (the reference's own message goes without the call's name, as icl_cluster's)
+        return icl_fail(ctx, refuse(ad.status), "%s%s", ad.status == ICL_ERR_CONSTRAINT ? "" : "icl_cluster_seeded: ", ad.why.c_str());
     icl_ward_ws *w = nullptr;
-    if (T > 0) {
-        std::vector<int32_t> eff((size_t)m);
-        for (int64_t i = 0; i < m; ++i) eff[(size_t)i] = seed_size[i] < 0 ? kmax : seed_size[i];
-        ICL_TRY(ward_ensure(ctx, m, d));
+    if (m - ad.k > 0) {
+        ward_seed sd{eff.data(), m - ad.k, nullptr};
+        ICL_TRY(ward_run_stages(ctx, d_C, m, d, min_size, ad.kmax, ICL_UPDATE_EXACT, 0, -1, &sd));
         w = ctx->ward;
-        if (hipMalloc(&c.eff.p, (size_t)m * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld seed sizes on the device", (long long)m);
-        ICL_HIP(ctx, hipMemcpyAsync(c.eff.p, eff.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (eff leaves scope below)
-        const ward_seed sd{seed_size, (const int32_t *)c.eff.p, T};
-        ward_plan p;
-        ICL_TRY(ward_make_plan(ctx, m, d, min_size, kmax, ICL_UPDATE_EXACT, 0, -1, &p, &sd));
-        ICL_HIP(ctx, hipEventCreate(&c.e0.p));
-        ICL_HIP(ctx, hipEventCreate(&c.e1.p));
-        ICL_HIP(ctx, hipEventCreate(&c.e2.p));
-        ICL_HIP(ctx, hipEventRecord(c.e0.p, ctx->stream));
-        ICL_TRY(ward_init_ws(ctx, w, p, d_C));
-        wrefine rf;
-        ICL_TRY(ward_fill(ctx, w, p, d_C, c, &rf));
-        ICL_HIP(ctx, hipEventRecord(c.e1.p, ctx->stream));
-        ICL_TRY(p.batched ? ward_run_batched(ctx, w, p, rf, c) : ward_run_single(ctx, w, p, rf));
-        ICL_HIP(ctx, hipGetLastError());
-        ICL_HIP(ctx, hipEventRecord(c.e2.p, ctx->stream));
-        ICL_TRY(ward_collect(ctx, w, p, rf, c, min_size, nullptr, nullptr, n_clusters));
-        w->dump.state = 2; // (icl_ward_dump_pairs_dev reads a workspace as singletons)
     } else // nothing to merge: every seed is a final cluster
         no_loop();
-    const int64_t nmerge = (int64_t)ctx->last.merges.size() / 2;
     std::vector<int32_t> finals;
-    std::string why;
-    if (wm_seeded_ids(m, seed_size, min_size, ctx->last.merges.data(), nmerge, cluster_id, seed_rank, n_clusters, &finals, why) != ICL_OK)
-        return icl_fail(ctx, refuse(ICL_ERR_HIP), "icl_cluster_seeded: %s", why.c_str()); // (the engine's own log: the sizes were checked with the arguments)
+    const ward_list_result r = ward_final_list(m, seed_size, min_size, ctx->last.merges.data(), (int64_t)ctx->last.merges.size() / 2, cluster_id, seed_rank,
+                                               n_clusters, &finals);
+    if (r.kind != ward_list_result::OK) // (the engine's own log: the sizes were checked with the arguments)
+        return icl_fail(ctx, refuse(ICL_ERR_HIP), "icl_cluster_seeded: %s", ward_list_text(r).c_str());
     if (d_C_out && out_bytes) {
         std::vector<int32_t> src((size_t)m, -1);
         for (size_t f = 0; f < finals.size(); f += 2) src[(size_t)finals[f + 1]] = finals[f];

@@ -16,14 +16,16 @@
 //     cached partner died.  Mid route (cap < n <= WMM_CAP): see "the mid-size route" below.
 //   * The four kernels themselves are in ward_many_kernels.h, included twice: as they are for problems that start from singletons,
 //     and once more for problems that start from SEED clusters (icl_cluster_many_seeded, "seeded clustering" at the end of this file).
-// Host.  cluster_many_locked runs the stages wm_classify (k, status, wm_route of every problem), wm_make_plan (launch groups --
-// wm_group: the small route is one, the mid route's are cut under a workspace budget -- and the workspace layout), wm_enqueue (uploads,
-// aligned copies, wm_run_group per group, one read-back of the one log slab), the large-N problems (ward.hip's
-// icl_ward_cluster_exact: above WMM_CAP rows, a lone small problem, mid-size problems the policy leaves there, icl_set_many_options),
-// wm_collect.  What the two routes' groups do differently on the host is the table wm_kind.
-// Cluster ids and member ranks come from the merge log by ward.hip's rule (icl_ward_assign_ids) whichever route a problem took.
-// The seeded calls run wm_classify_seeded, the same wm_make_plan / wm_enqueue with a seeded wm_args, wm_collect_seeded (ids by the same
-// rule at seed granularity, wm_seeded_ids) and ward_many_cout_kernel for C_out; they never take the large-N engine.
+// Host.  Every entry point, seeded or not, is wm_entry (checks, lock, device) around wm_run, which runs the stages wm_classify (k, status,
+// wm_route of every problem), wm_make_plan (launch groups -- wm_group: the small route is one, the mid route's are cut under a workspace
+// budget -- and the workspace layout), wm_enqueue (uploads, aligned copies, wm_run_group per group, one read-back of the one log slab),
+// the large-N problems (ward.hip's icl_ward_cluster_exact: above WMM_CAP rows, a lone small problem, mid-size problems the policy
+// leaves there, icl_set_many_options), wm_collect, wm_cout (C_out, seeded calls only: ward_many_cout_kernel), wm_lowest_failure.
+// What the two routes' groups do differently on the host is the table wm_kind.
+// What a seeded call does differently is in two places: wm_classify takes a problem's k, status and effective sizes from
+// ward_seed_admit (ward_seeds.h, icl_cluster_seeded's rule too) and routes by wm_route_seeded, never to the large-N engine.
+// Cluster ids and ranks come from the merge log by ward_final_list (ward_seeds.h) whichever route a problem took: rows of one item
+// each (through ward.hip's icl_ward_assign_ids), or the seeds with their sizes.
 #pragma clang fp contract(off)
 
 #include "icl_common.h"
@@ -265,8 +267,8 @@ __global__ __launch_bounds__(256) void ward_many_cout_kernel(const wm_crow *__re
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 int icl_ward_cluster_exact(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int32_t *cluster_id,
                            int32_t *member_rank, int32_t *n_clusters, std::vector<int32_t> *merges); // ward.hip (ctx->mu held)
-int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const std::vector<int32_t> &pairs, int64_t nmerge,
-                        int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters); // ward.hip
+int icl_ward_assign_ids(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t max_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
+                        int32_t *member_rank, int32_t *n_clusters); // ward.hip
 
 static int64_t wm_cap()
 {
@@ -456,7 +458,7 @@ struct wm_group {
     size_t head_bytes() const { return seeded ? o_seed() + sizeof(wm_seed) * probs.size() + 4 * seed_rows : plain_bytes(); }
 };
 
-// the per-problem arguments of both entry points
+// the per-problem arguments of every entry point
 struct wm_args {
     int32_t nprob;
     const int64_t *e_off;
@@ -466,6 +468,14 @@ struct wm_args {
     bool seeded = false;
     const int32_t *seed_size = nullptr, *k_target = nullptr;
     bool want_cout = false, cout_host = false;
+    const char *what() const { return seeded ? "icl_cluster_many_seeded" : "icl_cluster_many"; } // (in front of a failed problem's reason)
+};
+// ... and the outputs: rank is member_rank or seed_rank; C_out (seeded calls; may be null) on the device for a _dev call, on the host else;
+// lowest (may be null): see cluster_many_locked in icl_common.h
+struct wm_out {
+    int32_t *cluster_id, *rank, *n_clusters, *n_merges, *merges, *status;
+    float *C_out = nullptr;
+    icl_item_failure *lowest = nullptr;
 };
 
 struct wm_plan {
@@ -487,58 +497,51 @@ struct wm_plan {
     std::vector<size_t> o_c;
     std::vector<const float *> c_dev;
     size_t o_crow = 0, o_cout = 0;
+    std::vector<int32_t> finals; // (creation id, rank-0 seed) of every final cluster (ward_final_list), problem p's from fin_at[p] to fin_at[p + 1]
+    std::vector<size_t> fin_at;
 };
 
-// k, status and route of every problem; many_stats
-static void wm_classify(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
+// The routes of the problems that have something to merge.  From singletons: small up to the cap, else the large-N engine, which also takes
+// a lone small problem; the mid route takes what icl_set_many_options and the band counts give it.
+static void wm_route_plain(const icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
 {
     const int64_t cap = wm_cap();
-    const int32_t nprob = A.nprob;
-    pl.img.assign(nprob + 1, 0);
-    pl.k.assign(nprob, 0);
-    pl.why.resize(nprob);
-    pl.st.assign(nprob, ICL_OK);
-    pl.route.assign(nprob, WM_NONE);
-    for (int32_t p = 0; p < nprob; ++p) {
-        pl.img[p + 1] = pl.img[p] + A.n[p];
-        if (icl_calc_optimal_clusters(A.n[p], A.min_size[p], A.max_size[p], &pl.k[p]) != ICL_OK) { // clustering.go:203-207
-            pl.st[p] = ICL_ERR_CONSTRAINT;
-            char b[200];
-            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%d), minSize (%d), and maxSize (%d)", A.n[p],
-                     A.min_size[p], A.max_size[p]);
-            pl.why[p] = b;
-        }
-    }
     auto mid_size = [&](int32_t p) { return A.n[p] > cap && A.n[p] <= WMM_CAP; };
     int64_t mid_band[WMM_BANDS] = {};
-    for (int32_t p = 0; p < nprob; ++p) {
+    for (int32_t p = 0; p < A.nprob; ++p) {
         if (pl.st[p] != ICL_OK || A.n[p] - pl.k[p] <= 0) continue;
         pl.route[p] = A.n[p] <= cap ? WM_SMALL : WM_LARGE;
         if (pl.route[p] == WM_SMALL) small.push_back(p);
         if (mid_size(p)) ++mid_band[wmm_band(A.n[p])];
-        pl.need_e = pl.need_e || (int64_t)A.n[p] * A.d[p] > 0;
     }
     if ((int64_t)small.size() < WM_MIN_BATCH) {
         for (int32_t p : small) pl.route[p] = WM_LARGE;
         small.clear();
     }
     if (ctx->many_mid != ICL_MANY_MID_OFF)
-        for (int32_t p = 0; p < nprob; ++p)
+        for (int32_t p = 0; p < A.nprob; ++p)
             if (pl.route[p] == WM_LARGE && mid_size(p) && (ctx->many_mid == ICL_MANY_MID_ON || wmm_auto_takes(A.n[p], mid_band))) {
                 pl.route[p] = WM_MID;
                 mid.push_back(p);
             }
-    ctx->many_stats[0] = (int64_t)small.size();
-    ctx->many_stats[1] = (int64_t)mid.size();
-    ctx->many_stats[2] = std::count(pl.route.begin(), pl.route.end(), WM_LARGE);
+}
+// From seeds (DESIGN.md "Seeded clustering"), by the number of seeds alone: small up to the cap (a lone problem included), mid up to
+// wm_seed_limit whatever icl_set_many_options says, never the large-N engine.
+static int64_t wm_seed_limit() { return std::max<int64_t>(wm_cap(), WMM_CAP); }
+static void wm_route_seeded(const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
+{
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        if (pl.st[p] != ICL_OK || A.n[p] - pl.k[p] <= 0) continue;
+        pl.route[p] = A.n[p] <= wm_cap() ? WM_SMALL : WM_MID;
+        (pl.route[p] == WM_SMALL ? small : mid).push_back(p);
+    }
 }
 
-// The same for a seeded call (DESIGN.md "Seeded clustering"): N = the seeds' items, k = k_target or CalculateOptimalClusters(N), the route
-// by the number of seeds alone -- small up to the cap (a lone problem included), mid up to WMM_CAP whatever icl_set_many_options says,
-// ICL_ERR_UNSUPPORTED above -- and the sizes the kernels see: a frozen seed gets the largest size the ban still refuses.
-static void wm_classify_seeded(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
+// k, status and route of every problem; many_stats.  A problem from singletons: k = CalculateOptimalClusters(n) (clustering.go:203-207).  A
+// seeded one: ward_seed_admit (N = the seeds' items, k = k_target or CalculateOptimalClusters(N), the sizes the kernels see), and
+// ICL_ERR_UNSUPPORTED above wm_seed_limit seeds.
+static void wm_classify(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std::vector<int32_t> &small, std::vector<int32_t> &mid)
 {
-    const int64_t cap = wm_cap();
     const int32_t nprob = A.nprob;
     pl.img.assign(nprob + 1, 0);
     pl.k.assign(nprob, 0);
@@ -546,48 +549,37 @@ static void wm_classify_seeded(icl_ctx *ctx, const wm_args &A, wm_plan &pl, std:
     pl.st.assign(nprob, ICL_OK);
     pl.route.assign(nprob, WM_NONE);
     for (int32_t p = 0; p < nprob; ++p) pl.img[p + 1] = pl.img[p] + A.n[p];
-    pl.eff.assign((size_t)pl.img[nprob], 1);
-    pl.c_dev.assign(nprob, nullptr);
-    pl.kmax.assign(nprob, 1);
-    for (int32_t p = 0; p < nprob; ++p) {
-        const int32_t *ss = A.seed_size + pl.img[p];
-        const int64_t m = A.n[p];
-        int64_t N = 0, big = -1;
-        for (int64_t i = 0; i < m; ++i) {
-            N += std::llabs((long long)ss[i]);
-            if (ss[i] > A.max_size[p] && big < 0) big = i;
-        }
-        char b[200];
-        b[0] = 0;
-        if (N >= ((int64_t)1 << 30)) {
-            pl.st[p] = ICL_ERR_UNSUPPORTED;
-            snprintf(b, sizeof b, "%lld items in all", (long long)N);
-        } else if (big >= 0) { // the reference would split it (clustering.go:251-258)
-            pl.st[p] = ICL_ERR_UNSUPPORTED;
-            snprintf(b, sizeof b, "seed %lld holds %d items, above maxSize (%d), and is not frozen", (long long)big, ss[big], A.max_size[p]);
-        } else if (m > std::max<int64_t>(cap, WMM_CAP)) {
-            pl.st[p] = ICL_ERR_UNSUPPORTED;
-            snprintf(b, sizeof b, "%lld seeds: a seeded problem holds at most %lld", (long long)m, (long long)std::max<int64_t>(cap, WMM_CAP));
-        } else if (A.k_target && A.k_target[p] > 0) {
-            pl.k[p] = A.k_target[p];
-        } else if (icl_calc_optimal_clusters(N, A.min_size[p], A.max_size[p], &pl.k[p]) != ICL_OK) {
-            pl.st[p] = ICL_ERR_CONSTRAINT;
-            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%lld), minSize (%d), and maxSize (%d)", (long long)N,
-                     A.min_size[p], A.max_size[p]);
-        }
-        pl.why[p] = b;
-        if (pl.st[p] != ICL_OK) continue;
-        const int32_t kmax = pl.kmax[p] = (int32_t)std::min<int64_t>(std::max<int64_t>(A.max_size[p], 1), std::max<int64_t>(N, 1));
-        for (int64_t i = 0; i < m; ++i) pl.eff[(size_t)(pl.img[p] + i)] = ss[i] < 0 ? kmax : ss[i];
-        if (m - pl.k[p] <= 0) continue;
-        pl.route[p] = m <= cap ? WM_SMALL : WM_MID;
-        (pl.route[p] == WM_SMALL ? small : mid).push_back(p);
-        pl.need_e = pl.need_e || m * A.d[p] > 0;
+    if (A.seeded) {
+        pl.eff.assign((size_t)pl.img[nprob], 1);
+        pl.c_dev.assign(nprob, nullptr);
+        pl.kmax.assign(nprob, 1);
     }
+    for (int32_t p = 0; p < nprob; ++p) {
+        char b[200];
+        if (A.seeded) {
+            ward_admission a = ward_seed_admit(A.n[p], A.seed_size + pl.img[p], A.min_size[p], A.max_size[p], A.k_target ? A.k_target[p] : 0,
+                                               pl.eff.data() + pl.img[p]);
+            if (a.status != ICL_ERR_UNSUPPORTED && A.n[p] > wm_seed_limit()) { // (behind the admission's own refusals, ahead of its constraints)
+                a.status = ICL_ERR_UNSUPPORTED;
+                snprintf(b, sizeof b, "%lld seeds: a seeded problem holds at most %lld", (long long)A.n[p], (long long)wm_seed_limit());
+                a.why = b;
+            }
+            pl.st[p] = a.status, pl.k[p] = a.k, pl.kmax[p] = a.kmax;
+            pl.why[p].swap(a.why);
+        } else if (icl_calc_optimal_clusters(A.n[p], A.min_size[p], A.max_size[p], &pl.k[p]) != ICL_OK) {
+            pl.st[p] = ICL_ERR_CONSTRAINT;
+            snprintf(b, sizeof b, "cannot satisfy cluster size constraints with total items (%d), minSize (%d), and maxSize (%d)", A.n[p],
+                     A.min_size[p], A.max_size[p]);
+            pl.why[p] = b;
+        }
+        pl.need_e = pl.need_e || (pl.st[p] == ICL_OK && A.n[p] - pl.k[p] > 0 && (int64_t)A.n[p] * A.d[p] > 0);
+    }
+    if (A.seeded) wm_route_seeded(A, pl, small, mid);
+    else wm_route_plain(ctx, A, pl, small, mid);
     if (A.want_cout && pl.img[nprob] > 0) pl.need_e = true;
     ctx->many_stats[0] = (int64_t)small.size();
     ctx->many_stats[1] = (int64_t)mid.size();
-    ctx->many_stats[2] = 0;
+    ctx->many_stats[2] = std::count(pl.route.begin(), pl.route.end(), WM_LARGE);
 }
 
 // the launch groups (the mid route's under the budget; a group holds at least one problem) and the workspace:
@@ -712,27 +704,34 @@ static int wm_enqueue(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const float *
     return ICL_OK;
 }
 
-// ids from the merge logs (clustering.go:265-280, ward.hip's rule), merge logs, statuses; the lowest failed problem's error
-static int wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, std::vector<std::vector<int32_t>> &big_log,
-                      int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
-                      icl_item_failure *lowest)
+// Every problem's results: ids from its merge log -- the slab's, or the large-N engine's (big_log; that engine has written the ids) -- by
+// ward_final_list (clustering.go:265-280; from singletons through icl_ward_assign_ids, which checks the largest cluster too), rows of -1 and
+// zero merges for a failed problem, the merge logs, the statuses; a seeded call's final clusters for wm_cout.
+static void wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, const std::vector<std::vector<int32_t>> &big_log,
+                       const wm_out &O)
 {
-    std::vector<int32_t> pairs;
+    std::vector<int32_t> fin;
+    pl.fin_at.assign((size_t)A.nprob + 1, 0);
     for (int32_t p = 0; p < A.nprob; ++p) {
-        int32_t *cid = cluster_id + pl.img[p], *rank = member_rank + pl.img[p];
+        int32_t *cid = O.cluster_id + pl.img[p], *rank = O.rank + pl.img[p];
+        const int32_t *lg = nullptr; // the problem's log, nm pairs
         int64_t nm = 0;
         if (pl.route[p] == WM_LARGE) {
-            pairs.swap(big_log[p]);
-            nm = (int64_t)pairs.size() / 2;
+            lg = big_log[p].data();
+            nm = (int64_t)big_log[p].size() / 2;
         } else if (pl.route[p] != WM_NONE) {
-            const int32_t *lg = slab.data() + pl.log_at[p];
+            lg = slab.data() + pl.log_at[p];
             nm = lg[2 * (int64_t)A.n[p]];
-            pairs.assign(lg, lg + 2 * nm);
-        } else
-            pairs.clear();
+        }
+        fin.clear();
         if (pl.st[p] == ICL_OK && pl.route[p] != WM_LARGE) {
-            const int rc = icl_ward_assign_ids(ctx, A.n[p], A.min_size[p], A.max_size[p], pairs, nm, cid, rank, &n_clusters[p]);
-            if (rc != ICL_OK) {
+            if (A.seeded) {
+                const ward_list_result r = ward_final_list(A.n[p], A.seed_size + pl.img[p], A.min_size[p], lg, nm, cid, rank, &O.n_clusters[p], &fin);
+                if (r.kind != ward_list_result::OK) { // (the kernel's own log: the sizes were checked with the arguments)
+                    pl.st[p] = ICL_ERR_HIP;
+                    pl.why[p] = ward_list_text(r);
+                }
+            } else if (const int rc = icl_ward_assign_ids(ctx, A.n[p], A.min_size[p], A.max_size[p], lg, nm, cid, rank, &O.n_clusters[p])) {
                 pl.st[p] = rc;
                 pl.why[p] = ctx->err;
             }
@@ -740,48 +739,101 @@ static int wm_collect(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::ve
         if (pl.st[p] != ICL_OK) {
             std::fill(cid, cid + A.n[p], -1);
             std::fill(rank, rank + A.n[p], -1);
-            n_clusters[p] = 0;
+            O.n_clusters[p] = 0;
             nm = 0;
+            fin.clear();
         }
-        n_merges[p] = (int32_t)nm;
-        if (merges && nm) memcpy(merges + 2 * pl.img[p], pairs.data(), 8 * (size_t)nm);
-        status[p] = pl.st[p];
+        O.n_merges[p] = (int32_t)nm;
+        if (O.merges && nm) memcpy(O.merges + 2 * pl.img[p], lg, 8 * (size_t)nm);
+        O.status[p] = pl.st[p];
+        pl.finals.insert(pl.finals.end(), fin.begin(), fin.end());
+        pl.fin_at[(size_t)p + 1] = pl.finals.size();
     }
+}
+
+// the lowest failed problem's error, once every problem has its results
+static int wm_lowest_failure(icl_ctx *ctx, const wm_args &A, const wm_plan &pl, icl_item_failure *lowest)
+{
     for (int32_t p = 0; p < A.nprob; ++p)
         if (pl.st[p] != ICL_OK) {
             if (lowest) *lowest = icl_item_failure{p, pl.st[p], pl.why[p]};
-            return icl_fail(ctx, pl.st[p], "icl_cluster_many: problem %d: %s", p, pl.why[p].c_str());
+            return icl_fail(ctx, pl.st[p], "%s: problem %d: %s", A.what(), p, pl.why[p].c_str());
         }
     return ICL_OK;
 }
 
-// Both entry points, after the argument check, with ctx->mu held.  d_E: the embeddings on the device (e_len floats); h_E: the host copy
-// (icl_cluster_many), uploaded into the workspace here, or nullptr.  (Declared in icl_common.h: icl_cluster_requests, requests.hip, is the
-// third caller.)
-int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
-                               const int32_t *n, const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id,
-                               int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest)
+// C_out of a seeded call, after wm_collect: one wm_crow per seed of the call -- the centroid of the final cluster whose rank-0 seed it is
+// (a surviving seed's own row, or the centroid scratch of the slot the merged cluster lives in, wm_seed::fin), zeros else -- and
+// ward_many_cout_kernel.  rowsE: every problem's rows on the device, routed or not.
+static int wm_cout(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, const std::vector<const float *> &rowsE, int64_t e_len,
+                   const wm_out &O)
 {
-    const wm_args A = {nprob, e_off, n, d, min_size, max_size};
+    std::vector<wm_crow> crow((size_t)pl.img[A.nprob]);
+    if (crow.empty()) return ICL_OK;
+    std::vector<int32_t> slot;
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        const int64_t m = A.n[p], d = A.d[p], nm = O.n_merges[p];
+        for (int64_t i = 0; i < m; ++i) crow[(size_t)(pl.img[p] + i)] = wm_crow{nullptr, A.e_off[p] + i * d, (int32_t)d, 0};
+        if (pl.route[p] != WM_NONE) { // the slot a merged cluster lives in
+            const int32_t *fin = slab.data() + pl.log_at[p] + 2 * m + 1;
+            slot.assign((size_t)(m + nm), -1);
+            for (int64_t s = 0; s < m; ++s)
+                if (fin[s] >= 0 && fin[s] < m + nm) slot[fin[s]] = (int32_t)s;
+        }
+        for (size_t f = pl.fin_at[p]; f < pl.fin_at[(size_t)p + 1]; f += 2) {
+            const int64_t c = pl.finals[f], first = pl.finals[f + 1];
+            const float *src = nullptr;
+            if (c < m) src = rowsE[p] + c * d;
+            else if (slot[c] >= 0) src = pl.c_dev[p] + (int64_t)slot[c] * d;
+            else {
+                pl.st[p] = O.status[p] = ICL_ERR_HIP;
+                pl.why[p] = "the final state names no slot for a merged cluster";
+            }
+            crow[(size_t)(pl.img[p] + first)].src = src;
+        }
+    }
+    char *ws = (char *)ctx->many->buf;
+    float *out = A.cout_host ? (float *)(ws + pl.o_cout) : O.C_out;
+    ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_crow, crow.data(), sizeof(wm_crow) * crow.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (A.cout_host) ICL_HIP(ctx, hipMemsetAsync(out, 0, (size_t)e_len * 4, ctx->stream)); // (the padding between problems)
+    const wm_crow *tab = (const wm_crow *)(ws + pl.o_crow);
+    hipLaunchKernelGGL(ward_many_cout_kernel, dim3((unsigned)crow.size()), dim3(256), 0, ctx->stream, tab, out);
+    ICL_HIP(ctx, hipGetLastError());
+    if (A.cout_host) ICL_HIP(ctx, hipMemcpyAsync(O.C_out, out, (size_t)e_len * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICL_OK;
+}
+
+// Every entry point, after the argument check, with ctx->mu held: the stages of this file's header.  d_E: the rows on the device (e_len
+// floats); h_E: the host copy, uploaded into the workspace here, or nullptr.
+static int wm_run(icl_ctx *ctx, wm_args A, const float *d_E, const float *h_E, int64_t e_len, const wm_out &O)
+{
+    A.want_cout = O.C_out != nullptr;
+    A.cout_host = O.C_out != nullptr && h_E != nullptr;
     wm_plan pl;
     {
         std::vector<int32_t> small, mid;
         wm_classify(ctx, A, pl, small, mid);
         wm_make_plan(ctx, A, h_E != nullptr, e_len, small, mid, pl);
     }
-    std::vector<const float *> rowsE(nprob, nullptr);
+    std::vector<const float *> rowsE(A.nprob, nullptr);
     std::vector<int32_t> slab;
     ICL_TRY(wm_enqueue(ctx, A, pl, d_E, h_E, e_len, rowsE, slab));
+    if (A.want_cout) { // a problem that took no route: its rows where the call's E lies on the device
+        const float *base = h_E && pl.need_e ? (const float *)((char *)ctx->many->buf + pl.o_e) : d_E;
+        for (int32_t p = 0; p < A.nprob; ++p)
+            if (!rowsE[p]) rowsE[p] = base + A.e_off[p];
+    }
     // the large-N route, one problem at a time, behind the launches above (its reports of the last icl_cluster are restored)
-    std::vector<std::vector<int32_t>> big_log(nprob);
+    std::vector<std::vector<int32_t>> big_log(A.nprob);
     {
         wm_last_guard keep(ctx);
-        for (int32_t p = 0; p < nprob; ++p) {
+        for (int32_t p = 0; p < A.nprob; ++p) {
             if (pl.route[p] != WM_LARGE) continue;
             int32_t nc = 0;
-            const int rc = icl_ward_cluster_exact(ctx, rowsE[p], n[p], d[p], min_size[p], max_size[p], cluster_id + pl.img[p], member_rank + pl.img[p],
+            const int rc = icl_ward_cluster_exact(ctx, rowsE[p], A.n[p], A.d[p], A.min_size[p], A.max_size[p], O.cluster_id + pl.img[p], O.rank + pl.img[p],
                                                   &nc, &big_log[p]);
-            n_clusters[p] = nc;
+            O.n_clusters[p] = nc;
             if (rc != ICL_OK) {
                 pl.st[p] = rc;
                 pl.why[p] = ctx->err;
@@ -789,7 +841,18 @@ int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const flo
         }
     }
     if (!pl.groups.empty()) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return wm_collect(ctx, A, pl, slab, big_log, cluster_id, member_rank, n_clusters, n_merges, merges, status, lowest);
+    wm_collect(ctx, A, pl, slab, big_log, O);
+    if (A.want_cout) ICL_TRY(wm_cout(ctx, A, pl, slab, rowsE, e_len, O));
+    return wm_lowest_failure(ctx, A, pl, O.lowest);
+}
+
+// (Declared in icl_common.h: icl_cluster_requests, requests.hip, is the third caller.)
+int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
+                               const int32_t *n, const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id,
+                               int32_t *member_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest)
+{
+    return wm_run(ctx, wm_args{nprob, e_off, n, d, min_size, max_size}, d_E, h_E, e_len,
+                  wm_out{cluster_id, member_rank, n_clusters, n_merges, merges, status, nullptr, lowest});
 }
 
 extern "C" int icl_set_many_options(icl_ctx *ctx, int mid_mode)
@@ -812,217 +875,7 @@ extern "C" int icl_last_many_stats(icl_ctx *ctx, int64_t *small, int64_t *mid, i
     return ICL_OK;
 }
 
-extern "C" int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *n,
-                                    const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
-                                    int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
-{
-    return no_throw(ctx, "icl_cluster_many_dev", [&]() -> int {
-        ICL_TRY(wm_check_args(ctx, "icl_cluster_many_dev", nprob, d_E, e_len, e_off, n, d, min_size, max_size, cluster_id, member_rank, n_clusters,
-                              n_merges, status));
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        return cluster_many_locked(ctx, nprob, d_E, nullptr, e_len, e_off, n, d, min_size, max_size, cluster_id, member_rank, n_clusters, n_merges,
-                                   merges, status);
-    });
-}
-
-extern "C" int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *n, const int32_t *d,
-                                const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters,
-                                int32_t *n_merges, int32_t *merges, int32_t *status)
-{
-    return no_throw(ctx, "icl_cluster_many", [&]() -> int {
-        ICL_TRY(wm_check_args(ctx, "icl_cluster_many", nprob, E, e_len, e_off, n, d, min_size, max_size, cluster_id, member_rank, n_clusters, n_merges,
-                              status));
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        return cluster_many_locked(ctx, nprob, nullptr, E, e_len, e_off, n, d, min_size, max_size, cluster_id, member_rank, n_clusters, n_merges, merges,
-                                   status);
-    });
-}
-
-// ---- seeded clustering: resume the loop from existing clusters (DESIGN.md "Seeded clustering") ------------------------------------
-// icl_ward_assign_ids' rule at seed granularity: the final list is the surviving seeds in seed order, then the merged clusters in
-// creation order; a cluster's seeds are a's then b's (a: the pair's first id, clustering.go:31); a cluster whose ITEM count is below
-// min_size is dropped and consumes no id.  finals (may be null): (creation id, rank-0 seed) of every final cluster, dropped ones included.
-// (declared in icl_common.h: ward.hip's seeded call, icl_cluster_seeded, applies the same rule)
-int wm_seeded_ids(int64_t m, const int32_t *seed_size, int32_t min_size, const int32_t *pairs, int64_t nmerge, int32_t *cluster_id,
-                  int32_t *seed_rank, int32_t *n_clusters, std::vector<int32_t> *finals, std::string &why)
-{
-    const int64_t M = m + nmerge;
-    std::vector<int32_t> left((size_t)M, -1), right((size_t)M, -1);
-    std::vector<int64_t> size((size_t)M, 0);
-    std::vector<uint8_t> alive((size_t)M, 1);
-    char b[120];
-    for (int64_t i = 0; i < m; ++i) {
-        size[i] = std::llabs((long long)seed_size[i]);
-        if (!size[i]) {
-            snprintf(b, sizeof b, "seed %lld has size 0", (long long)i);
-            why = b;
-            return ICL_ERR_ARG;
-        }
-    }
-    for (int64_t t = 0; t < nmerge; ++t) {
-        const int32_t a = pairs[2 * t], c2 = pairs[2 * t + 1];
-        const int64_t c = m + t;
-        if (a < 0 || c2 < 0 || a >= c || c2 >= c || a == c2 || !alive[a] || !alive[c2]) {
-            snprintf(b, sizeof b, "corrupt merge log at step %lld (%d,%d)", (long long)t, a, c2);
-            why = b;
-            return ICL_ERR_ARG;
-        }
-        left[c] = a;
-        right[c] = c2;
-        size[c] = size[a] + size[c2];
-        alive[a] = alive[c2] = 0;
-    }
-    for (int64_t i = 0; i < m; ++i) cluster_id[i] = seed_rank[i] = -1;
-    int32_t cid = 0;
-    std::vector<int32_t> stack;
-    if (finals) finals->clear();
-    for (int64_t c = 0; c < M; ++c) {
-        if (!alive[c]) continue;
-        if (finals) {
-            int64_t f = c;
-            while (f >= m) f = left[f];
-            finals->push_back((int32_t)c);
-            finals->push_back((int32_t)f);
-        }
-        if (size[c] < min_size) continue; // clustering.go:268-271
-        int32_t rank = 0;
-        stack.assign(1, (int32_t)c);
-        while (!stack.empty()) {
-            const int32_t x = stack.back();
-            stack.pop_back();
-            if (x < m) {
-                cluster_id[x] = cid;
-                seed_rank[x] = rank++;
-            } else {
-                stack.push_back(right[x]); // visited after left: a's seeds first
-                stack.push_back(left[x]);
-            }
-        }
-        ++cid;
-    }
-    *n_clusters = cid;
-    return ICL_OK;
-}
-
-extern "C" int icl_seeded_assign_ids(int32_t m, const int32_t *seed_size, int32_t min_size, const int32_t *merges, int32_t n_merges,
-                                     int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters)
-{
-    return no_throw(nullptr, "icl_seeded_assign_ids", [&]() -> int {
-        if (m < 0 || n_merges < 0 || !n_clusters || (m && (!seed_size || !cluster_id || !seed_rank)) || (n_merges && !merges))
-            return icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: m %d, n_merges %d or a null array", m, n_merges);
-        for (int32_t i = 0; i < m; ++i)
-            if (!seed_size[i]) return icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: seed %d has size 0", i);
-        std::vector<int32_t> cid((size_t)m), rank((size_t)m); // (nothing is written when the log is corrupt)
-        int32_t nc = 0;
-        std::string why;
-        const int rc = wm_seeded_ids(m, seed_size, min_size, merges, n_merges, cid.data(), rank.data(), &nc, nullptr, why);
-        if (rc != ICL_OK) return icl_fail(nullptr, rc, "icl_seeded_assign_ids: %s", why.c_str());
-        if (m) memcpy(cluster_id, cid.data(), 4 * (size_t)m);
-        if (m) memcpy(seed_rank, rank.data(), 4 * (size_t)m);
-        *n_clusters = nc;
-        return ICL_OK;
-    });
-}
-
-// ids from the merge logs, merge logs, statuses and the rows of C_out (crow: one entry per seed of the call, or empty); the lowest
-// failed problem's error
-static int wm_collect_seeded(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vector<int32_t> &slab, const std::vector<const float *> &rowsE,
-                             int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
-                             std::vector<wm_crow> &crow)
-{
-    std::vector<int32_t> finals, slot;
-    for (int32_t p = 0; p < A.nprob; ++p) {
-        const int64_t m = A.n[p], d = A.d[p];
-        int32_t *cid = cluster_id + pl.img[p], *rank = seed_rank + pl.img[p];
-        const int32_t *lg = pl.route[p] != WM_NONE ? slab.data() + pl.log_at[p] : nullptr;
-        int64_t nm = lg ? lg[2 * m] : 0;
-        if (pl.st[p] == ICL_OK) {
-            const int rc = wm_seeded_ids(m, A.seed_size + pl.img[p], A.min_size[p], lg, nm, cid, rank, &n_clusters[p], &finals, pl.why[p]);
-            if (rc != ICL_OK) pl.st[p] = ICL_ERR_HIP; // (the kernel's own log: the sizes were checked with the arguments)
-        }
-        if (pl.st[p] != ICL_OK) {
-            std::fill(cid, cid + m, -1);
-            std::fill(rank, rank + m, -1);
-            n_clusters[p] = 0;
-            nm = 0;
-            finals.clear();
-        }
-        n_merges[p] = (int32_t)nm;
-        if (merges && nm) memcpy(merges + 2 * pl.img[p], lg, 8 * (size_t)nm);
-        status[p] = pl.st[p];
-        if (crow.empty()) continue;
-        for (int64_t i = 0; i < m; ++i) crow[(size_t)(pl.img[p] + i)] = wm_crow{nullptr, A.e_off[p] + i * d, (int32_t)d, 0};
-        if (lg) { // the slot a merged cluster lives in
-            slot.assign((size_t)(m + nm), -1);
-            const int32_t *fin = lg + 2 * m + 1;
-            for (int64_t s = 0; s < m; ++s)
-                if (fin[s] >= 0 && fin[s] < m + nm) slot[fin[s]] = (int32_t)s;
-        }
-        for (size_t f = 0; f < finals.size(); f += 2) {
-            const int64_t c = finals[f], first = finals[f + 1];
-            const float *src = nullptr;
-            if (c < m) src = rowsE[p] + c * d;
-            else if (slot[c] >= 0) src = pl.c_dev[p] + (int64_t)slot[c] * d;
-            else {
-                pl.st[p] = status[p] = ICL_ERR_HIP;
-                pl.why[p] = "the final state names no slot for a merged cluster";
-            }
-            crow[(size_t)(pl.img[p] + first)].src = src;
-        }
-    }
-    for (int32_t p = 0; p < A.nprob; ++p)
-        if (pl.st[p] != ICL_OK) return icl_fail(ctx, pl.st[p], "icl_cluster_many_seeded: problem %d: %s", p, pl.why[p].c_str());
-    return ICL_OK;
-}
-
-// Both seeded entry points, after the argument check, with ctx->mu held (d_E / h_E as cluster_many_locked takes them; C_out on the
-// device for the _dev call, on the host else, or null)
-static int cluster_many_seeded_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off,
-                                      const int32_t *m, const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
-                                      const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
-                                      int32_t *merges, int32_t *status, float *C_out)
-{
-    wm_args A = {nprob, e_off, m, d, min_size, max_size};
-    A.seeded = true;
-    A.seed_size = seed_size;
-    A.k_target = k_target;
-    A.want_cout = C_out != nullptr;
-    A.cout_host = C_out != nullptr && h_E != nullptr;
-    wm_plan pl;
-    {
-        std::vector<int32_t> small, mid;
-        wm_classify_seeded(ctx, A, pl, small, mid);
-        wm_make_plan(ctx, A, h_E != nullptr, e_len, small, mid, pl);
-    }
-    std::vector<const float *> rowsE(nprob, nullptr);
-    std::vector<int32_t> slab;
-    ICL_TRY(wm_enqueue(ctx, A, pl, d_E, h_E, e_len, rowsE, slab));
-    char *ws = (char *)ctx->many->buf;
-    if (A.want_cout) { // a problem that took no route: its rows where the call's E lies on the device
-        const float *base = h_E && pl.need_e ? (const float *)(ws + pl.o_e) : d_E;
-        for (int32_t p = 0; p < nprob; ++p)
-            if (!rowsE[p]) rowsE[p] = base + e_off[p];
-    }
-    if (!pl.groups.empty()) ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t rows = pl.img[nprob];
-    std::vector<wm_crow> crow(A.want_cout ? (size_t)rows : 0);
-    const int rc = wm_collect_seeded(ctx, A, pl, slab, rowsE, cluster_id, seed_rank, n_clusters, n_merges, merges, status, crow);
-    if (!crow.empty()) {
-        float *out = A.cout_host ? (float *)(ws + pl.o_cout) : C_out;
-        ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_crow, crow.data(), sizeof(wm_crow) * crow.size(), hipMemcpyHostToDevice, ctx->stream));
-        if (A.cout_host) ICL_HIP(ctx, hipMemsetAsync(out, 0, (size_t)e_len * 4, ctx->stream)); // (the padding between problems)
-        const wm_crow *tab = (const wm_crow *)(ws + pl.o_crow);
-        hipLaunchKernelGGL(ward_many_cout_kernel, dim3((unsigned)crow.size()), dim3(256), 0, ctx->stream, tab, out);
-        ICL_HIP(ctx, hipGetLastError());
-        if (A.cout_host) ICL_HIP(ctx, hipMemcpyAsync(C_out, out, (size_t)e_len * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
-}
-
-// the ARG check of the seeded entry points, beyond wm_check_args': nothing is written when it fails
+// The ARG check of the seeded entry points, beyond wm_check_args': nothing is written when it fails
 static int wm_check_seeds(icl_ctx *ctx, const char *what, int32_t nprob, const int32_t *m, const int32_t *seed_size)
 {
     int64_t rows = 0;
@@ -1033,21 +886,45 @@ static int wm_check_seeds(icl_ctx *ctx, const char *what, int32_t nprob, const i
     return ICL_OK;
 }
 
+// The four entry points: the argument checks, the lock, the device, wm_run.  dev: E (and C_out) are on the device.
+static int wm_entry(icl_ctx *ctx, bool dev, const char *what, const wm_args &A, const float *E, int64_t e_len, const wm_out &O)
+{
+    return no_throw(ctx, what, [&]() -> int {
+        ICL_TRY(wm_check_args(ctx, what, A.nprob, E, e_len, A.e_off, A.n, A.d, A.min_size, A.max_size, O.cluster_id, O.rank, O.n_clusters, O.n_merges, O.status));
+        if (A.seeded) {
+            ICL_TRY(wm_check_seeds(ctx, what, A.nprob, A.n, A.seed_size));
+            if (A.nprob == 0) return ICL_OK;
+        }
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        icl_device_guard g(ctx->device);
+        return wm_run(ctx, A, dev ? E : nullptr, dev ? nullptr : E, e_len, O);
+    });
+}
+
+extern "C" int icl_cluster_many_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *n,
+                                    const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
+                                    int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status)
+{
+    return wm_entry(ctx, true, "icl_cluster_many_dev", wm_args{nprob, e_off, n, d, min_size, max_size}, d_E, e_len,
+                    wm_out{cluster_id, member_rank, n_clusters, n_merges, merges, status});
+}
+
+extern "C" int icl_cluster_many(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *n, const int32_t *d,
+                                const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank, int32_t *n_clusters,
+                                int32_t *n_merges, int32_t *merges, int32_t *status)
+{
+    return wm_entry(ctx, false, "icl_cluster_many", wm_args{nprob, e_off, n, d, min_size, max_size}, E, e_len,
+                    wm_out{cluster_id, member_rank, n_clusters, n_merges, merges, status});
+}
+
+// ---- seeded clustering: resume the loop from existing clusters (DESIGN.md "Seeded clustering") ------------------------------------
 extern "C" int icl_cluster_many_seeded_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *m,
                                            const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
                                            const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
                                            int32_t *merges, int32_t *status, float *d_C_out)
 {
-    return no_throw(ctx, "icl_cluster_many_seeded_dev", [&]() -> int {
-        ICL_TRY(wm_check_args(ctx, "icl_cluster_many_seeded_dev", nprob, d_E, e_len, e_off, m, d, min_size, max_size, cluster_id, seed_rank, n_clusters,
-                              n_merges, status));
-        ICL_TRY(wm_check_seeds(ctx, "icl_cluster_many_seeded_dev", nprob, m, seed_size));
-        if (nprob == 0) return ICL_OK;
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        return cluster_many_seeded_locked(ctx, nprob, d_E, nullptr, e_len, e_off, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank,
-                                          n_clusters, n_merges, merges, status, d_C_out);
-    });
+    return wm_entry(ctx, true, "icl_cluster_many_seeded_dev", wm_args{nprob, e_off, m, d, min_size, max_size, true, seed_size, k_target}, d_E, e_len,
+                    wm_out{cluster_id, seed_rank, n_clusters, n_merges, merges, status, d_C_out});
 }
 
 extern "C" int icl_cluster_many_seeded(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *m,
@@ -1055,14 +932,18 @@ extern "C" int icl_cluster_many_seeded(icl_ctx *ctx, int32_t nprob, const float 
                                        const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
                                        int32_t *merges, int32_t *status, float *C_out)
 {
-    return no_throw(ctx, "icl_cluster_many_seeded", [&]() -> int {
-        ICL_TRY(wm_check_args(ctx, "icl_cluster_many_seeded", nprob, E, e_len, e_off, m, d, min_size, max_size, cluster_id, seed_rank, n_clusters,
-                              n_merges, status));
-        ICL_TRY(wm_check_seeds(ctx, "icl_cluster_many_seeded", nprob, m, seed_size));
-        if (nprob == 0) return ICL_OK;
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        return cluster_many_seeded_locked(ctx, nprob, nullptr, E, e_len, e_off, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank,
-                                          n_clusters, n_merges, merges, status, C_out);
+    return wm_entry(ctx, false, "icl_cluster_many_seeded", wm_args{nprob, e_off, m, d, min_size, max_size, true, seed_size, k_target}, E, e_len,
+                    wm_out{cluster_id, seed_rank, n_clusters, n_merges, merges, status, C_out});
+}
+
+// the final-list rule of the seeded calls (ward_final_list) for callers that hold a log of their own
+extern "C" int icl_seeded_assign_ids(int32_t m, const int32_t *seed_size, int32_t min_size, const int32_t *merges, int32_t n_merges,
+                                     int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters)
+{
+    return no_throw(nullptr, "icl_seeded_assign_ids", [&]() -> int {
+        if (m < 0 || n_merges < 0 || !n_clusters || (m && (!seed_size || !cluster_id || !seed_rank)) || (n_merges && !merges))
+            return icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: m %d, n_merges %d or a null array", m, n_merges);
+        const ward_list_result r = ward_final_list(m, seed_size, min_size, merges, n_merges, cluster_id, seed_rank, n_clusters, nullptr); // (writes nothing unless OK)
+        return r.kind == ward_list_result::OK ? ICL_OK : icl_fail(nullptr, ICL_ERR_ARG, "icl_seeded_assign_ids: %s", ward_list_text(r).c_str());
     });
 }
