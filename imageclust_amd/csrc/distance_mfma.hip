@@ -178,13 +178,14 @@ int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float
     const int dp = (d + 63) / 64 * 64;
     const int K = 3 * std::max(dp, 64);
     const int dpe = K / 3;
-    uint16_t *A = nullptr, *B = nullptr;
-    float *norms = nullptr;
-    void *zero = nullptr;
-    ICL_HIP(ctx, hipMalloc((void **)&A, (size_t)n * K * 2));
-    ICL_HIP(ctx, hipMalloc((void **)&B, (size_t)n * K * 2));
-    ICL_HIP(ctx, hipMalloc((void **)&norms, (size_t)n * 4));
-    ICL_HIP(ctx, hipMalloc(&zero, 256));
+    dev_guard gA, gB, g_norms, g_zero; // (the caller holds ctx->mu and has the device selected)
+    ICL_TRY(icl_dev_alloc(ctx, gA, (size_t)n * K * 2, "distance GEMM: A' (%lld x %d)", (long long)n, K));
+    ICL_TRY(icl_dev_alloc(ctx, gB, (size_t)n * K * 2, "distance GEMM: B' (%lld x %d)", (long long)n, K));
+    ICL_TRY(icl_dev_alloc(ctx, g_norms, (size_t)n * 4, "distance GEMM: norms"));
+    ICL_TRY(icl_dev_alloc(ctx, g_zero, 256, "distance GEMM: zero page"));
+    uint16_t *A = gA.as<uint16_t>(), *B = gB.as<uint16_t>();
+    float *norms = g_norms.as<float>();
+    void *zero = g_zero.p;
     ICL_HIP(ctx, hipMemsetAsync(zero, 0, 256, ctx->stream));
     hipLaunchKernelGGL(dist_split_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, d_E, n, d, dpe, A, B, norms);
     icl_lds_optin(ctx, (const void *)dist_mfma_kernel<0>, (int)dist_lds_bytes());
@@ -202,10 +203,6 @@ int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float
     }
     ICL_HIP(ctx, hipGetLastError());
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(A);
-    (void)hipFree(B);
-    (void)hipFree(norms);
-    (void)hipFree(zero);
     icl_prof_collect(ctx);
     return ICL_OK;
 }

@@ -16,6 +16,27 @@
 
 #define ICL_MAXF 3.40282346638528859811704183484516925e+38f /* math.MaxFloat32 */
 
+struct icl_ctx;
+int icl_fail(icl_ctx *ctx, int code, const char *fmt, ...);
+static inline hipStream_t icl_main_stream(const icl_ctx *ctx); // ctx->stream, defined behind icl_ctx (icl_dev_mem.h is read before icl_ctx is complete)
+
+#define ICL_HIP(ctx, call)                                                                                     \
+    do {                                                                                                       \
+        hipError_t e__ = (call);                                                                               \
+        if (e__ != hipSuccess)                                                                                 \
+            return icl_fail(ctx, ICL_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, \
+                            __LINE__);                                                                         \
+    } while (0)
+
+#define ICL_TRY(expr)            \
+    do {                         \
+        int rc__ = (expr);       \
+        if (rc__) return rc__;   \
+    } while (0)
+
+// dev_guard + icl_dev_alloc, icl_dev_grow, icl_ws_layout: the host side's owners of device memory
+#include "icl_dev_mem.h"
+
 struct icl_prof_slot {
     double ms = 0, flops = 0, bytes = 0;
     int64_t launches = 0;
@@ -29,11 +50,8 @@ struct icl_pending_event {
 struct icl_model;  // resnet_model.h
 struct icl_ward_ws; // ward.hip
 struct icl_ingest_ws; // jpeg_gpu.hip
-struct icl_many_ws; // ward_many.hip
 struct icl_requests_ws; // requests.hip
 struct icl_jenc_ws; // jpeg_encode_gpu.hip
-struct icl_nearest_ws; // nearest.hip
-struct icl_pairs_ws; // pairs.hip
 
 // Strip-sharded merge loop (ward.hip "replicated state, sharded blocks"; multi_gpu.hip): what the G replicas of one group call share.
 #define ICL_SHARD_MAX 16
@@ -138,10 +156,10 @@ struct icl_ctx {
     icl_ward_ws *ward = nullptr;
     icl_ward_shard *shard = nullptr; // set by the group around a sharded cluster call: this context is replica shard_rank of shard->G
     int shard_rank = 0;
-    int64_t *ward_rowoff = nullptr; // row offsets of the packed triangle for ranks that only compute distance rows (ward.hip)
+    icl_dev_grow ward_rowoff; // row offsets of the packed triangle for ranks that only compute distance rows (ward.hip)
     int64_t ward_rowoff_n = 0;
     void *file_batcher = nullptr; // icl_embed_file's coalescing queue (embed_file.hip)
-    icl_many_ws *many = nullptr; // workspace of icl_cluster_many (ward_many.hip; created on first use)
+    icl_dev_grow many; // workspace of icl_cluster_many (ward_many.hip; grown on demand, released by icl_destroy)
     int many_mid = 0;                 // icl_set_many_options: ICL_MANY_MID_AUTO / _OFF / _ON (environment: ICL_MANY_MID=auto|off|on)
     int64_t many_stats[4] = {0, 0, 0, 0}; // last icl_cluster_many[_dev]: problems on the small, mid and large-N routes, mid-route groups
     icl_ingest_ws *ingest = nullptr; // buffers of the batched file path (jpeg_gpu.hip; created on first use)
@@ -152,29 +170,15 @@ struct icl_ctx {
     double requests_ms[3] = {0, 0, 0};   // last icl_cluster_requests: files -> dense rows, assembly, clustering (icl_last_requests_ms)
     icl_jenc_ws *jenc = nullptr;         // buffers of the GPU JPEG encoder (jpeg_encode_gpu.hip; created on first use)
     dz_totals downsize_last;             // last icl_downsize_images[_mem] (icl_last_downsize_stats)
-    icl_nearest_ws *nearest = nullptr;   // device copies of sizes / exclude and the partial lists of icl_nearest (nearest.hip; created on first use)
+    icl_dev_grow nearest;                // device copies of sizes / exclude and the partial lists of icl_nearest (nearest.hip; as many)
     int nearest_splits = 0;              // icl_set_nearest_options: column splits per band of query rows (0: the engine decides)
     int64_t nearest_stats[4] = {0, 0, 0, 0}; // last icl_nearest[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_nearest_stats)
-    icl_pairs_ws *pairs = nullptr;       // row counts, tile flags and row_ptr of icl_pairs_within on the device (pairs.hip; created on first use)
+    icl_dev_grow pairs;                  // row counts, tile flags and row_ptr of icl_pairs_within on the device (pairs.hip; as many)
     int64_t pairs_stats[4] = {0, 0, 0, 0}; // last icl_pairs_within[_dev]: tiles run in pass 1, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 
-int icl_fail(icl_ctx *ctx, int code, const char *fmt, ...);
-
-#define ICL_HIP(ctx, call)                                                                                     \
-    do {                                                                                                       \
-        hipError_t e__ = (call);                                                                               \
-        if (e__ != hipSuccess)                                                                                 \
-            return icl_fail(ctx, ICL_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, \
-                            __LINE__);                                                                         \
-    } while (0)
-
-#define ICL_TRY(expr)            \
-    do {                         \
-        int rc__ = (expr);       \
-        if (rc__) return rc__;   \
-    } while (0)
+static inline hipStream_t icl_main_stream(const icl_ctx *ctx) { return ctx->stream; }
 
 // RAII: select the context's device for the duration of a call without leaking the change to the caller.
 struct icl_device_guard {
@@ -191,15 +195,6 @@ struct icl_device_guard {
     }
 };
 
-// hip_guard releases a HIP resource on every way out of a scope (ICL_HIP / ICL_TRY / icl_fail return early)
-template <class T, hipError_t (*Release)(T)> struct hip_guard {
-    T p = nullptr;
-    ~hip_guard() { if (p) (void)Release(p); }
-};
-using ev_guard = hip_guard<hipEvent_t, hipEventDestroy>;
-using dev_guard = hip_guard<void *, hipFree>;
-using pin_guard = hip_guard<void *, hipHostFree>;
-
 // Profiling bracket: when enabled records two events around a launch and attributes algorithmic work.
 struct icl_prof_scope {
     icl_ctx *c;
@@ -215,11 +210,8 @@ void icl_model_free(icl_ctx *ctx);
 void icl_ward_free(icl_ctx *ctx);
 void icl_file_batcher_free(icl_ctx *ctx);
 void icl_ingest_free(icl_ctx *ctx);
-void icl_many_free(icl_ctx *ctx);
 void icl_requests_free(icl_ctx *ctx);
 void icl_jenc_free(icl_ctx *ctx);
-void icl_nearest_free(icl_ctx *ctx);
-void icl_pairs_free(icl_ctx *ctx);
 
 // The two batched halves icl_cluster_requests (requests.hip) joins; both expect ctx->mu held and the context's device selected.
 // Each tells its caller apart what the return code alone cannot: "the list was processed and an item of it failed" from "the call stopped".

@@ -84,11 +84,11 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     icl_ward_free(ctx);
     icl_file_batcher_free(ctx);
     icl_ingest_free(ctx);
-    icl_many_free(ctx);
+    ctx->many.release();
     icl_requests_free(ctx);
     icl_jenc_free(ctx);
-    icl_nearest_free(ctx);
-    icl_pairs_free(ctx);
+    ctx->nearest.release();
+    ctx->pairs.release();
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

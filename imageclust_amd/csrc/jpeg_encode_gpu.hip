@@ -295,46 +295,25 @@ __global__ void __launch_bounds__(256) jenc_header_kernel(const jenc_img *__rest
     }
 }
 
-template <class T> int grow(icl_ctx *ctx, T *&p, int64_t &cap, int64_t need)
-{
-    if (cap >= need) return ICL_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc((void **)&p, (size_t)need * sizeof(T)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "JPEG encoder: device buffer of %lld bytes", (long long)(need * (int64_t)sizeof(T)));
-    cap = need;
-    return ICL_OK;
-}
-
 } // namespace
 
 // Buffers of the GPU encoder, kept by the context between calls and grown on demand (freed by icl_destroy).
 struct icl_jenc_ws {
-    jenc_img *d_imgs = nullptr;
-    jenc_state *d_state = nullptr;
-    int64_t *d_off = nullptr;
-    int64_t imgs_cap = 0, state_cap = 0, off_cap = 0;
-    jenc_dev_tables *d_tab = nullptr;
+    icl_dev_grow imgs, state, off;                          // jenc_img[n], jenc_state[n], int64_t[n + 1]
+    icl_dev_grow tab;                                       // jenc_dev_tables of tab_quality
     int tab_quality = 0;
-    int16_t *d_coef = nullptr;
-    uint32_t *d_len = nullptr, *d_raw = nullptr, *d_cnt = nullptr;
-    unsigned long long *d_bitoff = nullptr, *d_ffoff = nullptr;
-    uint8_t *d_out = nullptr;
-    int64_t coef_cap = 0, len_cap = 0, raw_cap = 0, cnt_cap = 0, bitoff_cap = 0, ffoff_cap = 0, out_cap = 0;
+    icl_dev_grow coef, len, bitoff, raw, cnt, ffoff, out;   // int16_t[64 blocks], uint32_t[blocks], u64[blocks], uint32_t[words], uint32_t[chunks], u64[chunks], the files
     int64_t *h_off = nullptr; // pinned
     int64_t h_off_cap = 0;
-    ~icl_jenc_ws()
-    {
-        for (void *p : {(void *)d_imgs, (void *)d_state, (void *)d_off, (void *)d_tab, (void *)d_coef, (void *)d_len, (void *)d_raw, (void *)d_cnt, (void *)d_bitoff,
-                        (void *)d_ffoff, (void *)d_out})
-            if (p) (void)hipFree(p);
-        if (h_off) (void)hipHostFree(h_off);
-    }
 };
 
 void icl_jenc_free(icl_ctx *ctx)
 {
-    delete ctx->jenc;
+    if (!ctx->jenc) return;
+    icl_jenc_ws *ws = ctx->jenc;
+    for (icl_dev_grow *b : {&ws->imgs, &ws->state, &ws->off, &ws->tab, &ws->coef, &ws->len, &ws->bitoff, &ws->raw, &ws->cnt, &ws->ffoff, &ws->out}) b->release();
+    if (ws->h_off) (void)hipHostFree(ws->h_off);
+    delete ws;
     ctx->jenc = nullptr;
 }
 
@@ -378,16 +357,17 @@ int icl_jenc_run(icl_ctx *ctx, const uint8_t *d_rgb, const icl_jenc_item *items,
         max_chunks = std::max(max_chunks, I.chunks_cap);
     }
     if (blocks > MAX_BATCH_BLOCKS) return icl_fail(ctx, ICL_ERR_OVERSIZE, "JPEG encoder: %lld blocks in one batch (at most %lld)", (long long)blocks, (long long)MAX_BATCH_BLOCKS);
-    ICL_TRY(grow(ctx, ws->d_imgs, ws->imgs_cap, n));
-    ICL_TRY(grow(ctx, ws->d_state, ws->state_cap, n));
-    ICL_TRY(grow(ctx, ws->d_off, ws->off_cap, n + 1));
-    ICL_TRY(grow(ctx, ws->d_coef, ws->coef_cap, blocks * 64));
-    ICL_TRY(grow(ctx, ws->d_len, ws->len_cap, blocks));
-    ICL_TRY(grow(ctx, ws->d_bitoff, ws->bitoff_cap, blocks));
-    ICL_TRY(grow(ctx, ws->d_raw, ws->raw_cap, words));
-    ICL_TRY(grow(ctx, ws->d_cnt, ws->cnt_cap, chunks));
-    ICL_TRY(grow(ctx, ws->d_ffoff, ws->ffoff_cap, chunks));
-    ICL_TRY(grow(ctx, ws->d_out, ws->out_cap, out_need));
+    const char *what = "JPEG encoder: device buffer";
+    ICL_TRY(ws->imgs.ensure(ctx, (size_t)n * sizeof(jenc_img), what));
+    ICL_TRY(ws->state.ensure(ctx, (size_t)n * sizeof(jenc_state), what));
+    ICL_TRY(ws->off.ensure(ctx, (size_t)(n + 1) * 8, what));
+    ICL_TRY(ws->coef.ensure(ctx, (size_t)blocks * 64 * 2, what));
+    ICL_TRY(ws->len.ensure(ctx, (size_t)blocks * 4, what));
+    ICL_TRY(ws->bitoff.ensure(ctx, (size_t)blocks * 8, what));
+    ICL_TRY(ws->raw.ensure(ctx, (size_t)words * 4, what));
+    ICL_TRY(ws->cnt.ensure(ctx, (size_t)chunks * 4, what));
+    ICL_TRY(ws->ffoff.ensure(ctx, (size_t)chunks * 8, what));
+    ICL_TRY(ws->out.ensure(ctx, (size_t)out_need, what));
     if (ws->h_off_cap < n + 1) {
         if (ws->h_off) (void)hipHostFree(ws->h_off);
         ws->h_off = nullptr;
@@ -395,44 +375,51 @@ int icl_jenc_run(icl_ctx *ctx, const uint8_t *d_rgb, const icl_jenc_item *items,
         if (hipHostMalloc((void **)&ws->h_off, (size_t)(n + 1) * 8, hipHostMallocDefault) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "JPEG encoder: pinned offsets");
         ws->h_off_cap = n + 1;
     }
-    if (!ws->d_tab) {
-        if (hipMalloc((void **)&ws->d_tab, sizeof(jenc_dev_tables)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "JPEG encoder: tables");
-        ws->tab_quality = 0;
-    }
+    if (!ws->tab.p) ws->tab_quality = 0;
+    ICL_TRY(ws->tab.ensure(ctx, sizeof(jenc_dev_tables), "JPEG encoder: tables"));
     if (ws->tab_quality != quality) {
         std::unique_ptr<jenc_dev_tables> t(new jenc_dev_tables());
         memset(t.get(), 0, sizeof *t);
         icl_jenc_make_tables(quality, t->T);
         icl_jenc_write_header(t->T, 0, 0, t->header);
-        ICL_HIP(ctx, hipMemcpyAsync(ws->d_tab, t.get(), sizeof *t, hipMemcpyHostToDevice, st));
+        ICL_HIP(ctx, hipMemcpyAsync(ws->tab.p, t.get(), sizeof *t, hipMemcpyHostToDevice, st));
         ICL_HIP(ctx, hipStreamSynchronize(st)); // (t goes out of scope)
         ws->tab_quality = quality;
     }
-    ICL_HIP(ctx, hipMemcpyAsync(ws->d_imgs, imgs.data(), (size_t)n * sizeof(jenc_img), hipMemcpyHostToDevice, st));
+    const jenc_img *d_imgs = ws->imgs.as<jenc_img>();
+    jenc_state *d_state = ws->state.as<jenc_state>();
+    const jenc_dev_tables *d_tab = ws->tab.as<jenc_dev_tables>();
+    int64_t *d_off = ws->off.as<int64_t>();
+    int16_t *d_coef = ws->coef.as<int16_t>();
+    uint32_t *d_len = ws->len.as<uint32_t>(), *d_raw = ws->raw.as<uint32_t>(), *d_cnt = ws->cnt.as<uint32_t>();
+    unsigned long long *d_bitoff = ws->bitoff.as<unsigned long long>(), *d_ffoff = ws->ffoff.as<unsigned long long>();
+    uint8_t *d_out = ws->out.as<uint8_t>();
+    const int64_t out_cap = (int64_t)ws->out.bytes;
+    ICL_HIP(ctx, hipMemcpyAsync(ws->imgs.p, imgs.data(), (size_t)n * sizeof(jenc_img), hipMemcpyHostToDevice, st));
     const unsigned gb = (unsigned)icl_ceil_div(blocks, JT);
     const int ni = (int)n;
-    hipLaunchKernelGGL(jenc_block_kernel, dim3(gb), dim3(JT), 0, st, (const jenc_img *)ws->d_imgs, ni, (const jenc_dev_tables *)ws->d_tab, d_rgb, ws->d_coef, blocks);
-    hipLaunchKernelGGL(jenc_length_kernel, dim3(gb), dim3(JT), 0, st, (const jenc_img *)ws->d_imgs, ni, (const jenc_dev_tables *)ws->d_tab, (const int16_t *)ws->d_coef,
-                       ws->d_len, blocks);
-    hipLaunchKernelGGL(jenc_scan_kernel, dim3((unsigned)n), dim3(SCAN_T), 0, st, (const jenc_img *)ws->d_imgs, ws->d_state, (const uint32_t *)ws->d_len, ws->d_bitoff, 0);
+    hipLaunchKernelGGL(jenc_block_kernel, dim3(gb), dim3(JT), 0, st, d_imgs, ni, d_tab, d_rgb, d_coef, blocks);
+    hipLaunchKernelGGL(jenc_length_kernel, dim3(gb), dim3(JT), 0, st, d_imgs, ni, d_tab, (const int16_t *)d_coef,
+                       d_len, blocks);
+    hipLaunchKernelGGL(jenc_scan_kernel, dim3((unsigned)n), dim3(SCAN_T), 0, st, d_imgs, d_state, (const uint32_t *)d_len, d_bitoff, 0);
     const unsigned gz = (unsigned)std::min<int64_t>(icl_ceil_div(max_words, 256), 4096), gc = (unsigned)std::min<int64_t>(icl_ceil_div(max_chunks, 256), 4096);
-    hipLaunchKernelGGL(jenc_zero_kernel, dim3(gz, (unsigned)n), dim3(256), 0, st, (const jenc_img *)ws->d_imgs, (const jenc_state *)ws->d_state, ws->d_raw);
-    hipLaunchKernelGGL(jenc_pack_kernel, dim3(gb), dim3(JT), 0, st, (const jenc_img *)ws->d_imgs, ni, (const jenc_state *)ws->d_state, (const jenc_dev_tables *)ws->d_tab,
-                       (const int16_t *)ws->d_coef, (const unsigned long long *)ws->d_bitoff, ws->d_raw, blocks);
-    hipLaunchKernelGGL(jenc_count_kernel, dim3(gc, (unsigned)n), dim3(256), 0, st, (const jenc_img *)ws->d_imgs, (const jenc_state *)ws->d_state,
-                       (const uint32_t *)ws->d_raw, ws->d_cnt);
-    hipLaunchKernelGGL(jenc_scan_kernel, dim3((unsigned)n), dim3(SCAN_T), 0, st, (const jenc_img *)ws->d_imgs, ws->d_state, (const uint32_t *)ws->d_cnt, ws->d_ffoff, 1);
-    hipLaunchKernelGGL(jenc_offsets_kernel, dim3(1), dim3(1), 0, st, (const jenc_state *)ws->d_state, ni, ws->d_off);
-    hipLaunchKernelGGL(jenc_emit_kernel, dim3(gc, (unsigned)n), dim3(256), 0, st, (const jenc_img *)ws->d_imgs, (const jenc_state *)ws->d_state, (const uint32_t *)ws->d_raw,
-                       (const unsigned long long *)ws->d_ffoff, (const int64_t *)ws->d_off, ws->d_out, ws->out_cap);
-    hipLaunchKernelGGL(jenc_header_kernel, dim3((unsigned)n), dim3(256), 0, st, (const jenc_img *)ws->d_imgs, (const jenc_dev_tables *)ws->d_tab, (const int64_t *)ws->d_off,
-                       ws->d_out, ws->out_cap);
+    hipLaunchKernelGGL(jenc_zero_kernel, dim3(gz, (unsigned)n), dim3(256), 0, st, d_imgs, (const jenc_state *)d_state, d_raw);
+    hipLaunchKernelGGL(jenc_pack_kernel, dim3(gb), dim3(JT), 0, st, d_imgs, ni, (const jenc_state *)d_state, d_tab,
+                       (const int16_t *)d_coef, (const unsigned long long *)d_bitoff, d_raw, blocks);
+    hipLaunchKernelGGL(jenc_count_kernel, dim3(gc, (unsigned)n), dim3(256), 0, st, d_imgs, (const jenc_state *)d_state,
+                       (const uint32_t *)d_raw, d_cnt);
+    hipLaunchKernelGGL(jenc_scan_kernel, dim3((unsigned)n), dim3(SCAN_T), 0, st, d_imgs, d_state, (const uint32_t *)d_cnt, d_ffoff, 1);
+    hipLaunchKernelGGL(jenc_offsets_kernel, dim3(1), dim3(1), 0, st, (const jenc_state *)d_state, ni, d_off);
+    hipLaunchKernelGGL(jenc_emit_kernel, dim3(gc, (unsigned)n), dim3(256), 0, st, d_imgs, (const jenc_state *)d_state, (const uint32_t *)d_raw,
+                       (const unsigned long long *)d_ffoff, (const int64_t *)d_off, d_out, out_cap);
+    hipLaunchKernelGGL(jenc_header_kernel, dim3((unsigned)n), dim3(256), 0, st, d_imgs, d_tab, (const int64_t *)d_off,
+                       d_out, out_cap);
     ICL_HIP(ctx, hipGetLastError());
-    ICL_HIP(ctx, hipMemcpyAsync(ws->h_off, ws->d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    ICL_HIP(ctx, hipMemcpyAsync(ws->h_off, d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
     ICL_HIP(ctx, hipStreamSynchronize(st));
     for (int64_t i = 0; i <= n; ++i) off[(size_t)i] = ws->h_off[i];
-    if (off[(size_t)n] > ws->out_cap) return icl_fail(ctx, ICL_ERR_IO, "JPEG encoder: a stream exceeded its proven bound");
-    *d_files = ws->d_out;
+    if (off[(size_t)n] > out_cap) return icl_fail(ctx, ICL_ERR_IO, "JPEG encoder: a stream exceeded its proven bound");
+    *d_files = d_out;
     return ICL_OK;
 }
 

@@ -526,9 +526,8 @@ struct icl_ingest_ws {
     uint8_t *h_slab[2] = {nullptr, nullptr}; // pinned: header (images + planes + scans) then payload
     hipEvent_t ev_up[2] = {nullptr, nullptr};
     uint8_t *d_hdr = nullptr, *d_payload = nullptr, *d_scratch = nullptr, *d_img = nullptr;
-    float *d_emb = nullptr;
+    icl_dev_grow emb; // float[SLAB_IMAGES][head] of the widest head asked for so far (ingest_buffers)
     int32_t *d_rows = nullptr;
-    int emb_head = 0;
     // ICL_ENTROPY_GPU (allocated on first use)
     int16_t *d_coef = nullptr;
     icl_je_sub *d_sub = nullptr;
@@ -551,9 +550,10 @@ struct icl_ingest_ws {
         if (h_accepted) (void)hipHostFree(h_accepted);
         if (h_png_ok) (void)hipHostFree(h_png_ok);
         if (d_png_ok) (void)hipFree(d_png_ok);
-        for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_emb, (void *)d_rows, (void *)d_coef, (void *)d_sub, (void *)d_bound,
+        for (void *p : {(void *)d_hdr, (void *)d_payload, (void *)d_scratch, (void *)d_img, (void *)d_rows, (void *)d_coef, (void *)d_sub, (void *)d_bound,
                         (void *)d_accepted})
             if (p) (void)hipFree(p);
+        emb.release();
     }
 };
 
@@ -873,13 +873,7 @@ static int ingest_buffers(icl_ctx *ctx, const ingest_sink &sink, int entropy, in
 {
     ICL_TRY(ingest_ws(ctx, ws));
     if (entropy == ICL_ENTROPY_GPU) ICL_TRY(entropy_ws(ctx, ws, n));
-    if (sink.embeds() && ws->emb_head < sink.head) {
-        if (ws->d_emb) (void)hipFree(ws->d_emb);
-        ws->d_emb = nullptr;
-        ws->emb_head = 0;
-        if (hipMalloc((void **)&ws->d_emb, (size_t)SLAB_IMAGES * sink.head * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "file ingest: embedding buffer");
-        ws->emb_head = sink.head;
-    }
+    if (sink.embeds()) ICL_TRY(ws->emb.ensure(ctx, (size_t)SLAB_IMAGES * sink.head * 4, "file ingest: embedding buffer"));
     return ICL_OK;
 }
 
@@ -945,11 +939,11 @@ static int slab_deliver(icl_ctx *ctx, icl_ingest_ws *ws, const ingest_sink &sink
                        (const uint8_t *)ws->d_payload, (int64_t)SLAB_PAYLOAD, (const uint8_t *)ws->d_scratch, (int64_t)SLAB_SCRATCH, d_img);
     ICL_HIP(ctx, hipGetLastError());
     if (!sink.embeds()) return ICL_OK;
-    float *d_dst = sink.kind == ingest_sink::EMB_DEV ? (float *)sink.row(R.first) : ws->d_emb;
+    float *d_dst = sink.kind == ingest_sink::EMB_DEV ? (float *)sink.row(R.first) : ws->emb.as<float>();
     ICL_TRY(icl_embed_dev_locked(ctx, ws->d_img, nimg, head, sink.prec, d_dst)); // (ends with the stream synchronised)
     if (sink.kind == ingest_sink::EMB_HOST) {
         float *out = (float *)sink.row(R.first);
-        ICL_HIP(ctx, hipMemcpyAsync(out, ws->d_emb, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
+        ICL_HIP(ctx, hipMemcpyAsync(out, ws->emb.p, (size_t)nimg * head * 4, hipMemcpyDeviceToHost, st));
         ICL_HIP(ctx, hipStreamSynchronize(st));
         for (int32_t j : R.failed) std::fill(out + (int64_t)j * head, out + (int64_t)(j + 1) * head, std::nanf(""));
     } else if (!R.failed.empty()) {
@@ -1031,7 +1025,7 @@ int ingest_files(icl_ctx *ctx, const ingest_src *srcs, int64_t n, int32_t thread
             h_tmp.resize((size_t)nrej * sink.head);
             tmp.dst = h_tmp.data();
         } else {
-            if (hipMalloc(&d_tmp.p, (size_t)nrej * sink.row_bytes()) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: device buffer of the repair pass", what);
+            ICL_TRY(icl_dev_alloc(ctx, d_tmp, (size_t)nrej * sink.row_bytes(), "%s: device buffer of the repair pass", what));
             tmp.dst = d_tmp.p;
         }
         ICL_TRY(ingest_pass(ctx, ingest_job{rp.data(), nrej, threads, rstatus.data(), what}, tmp, MODES_HOST, rres, tot));
@@ -1429,21 +1423,13 @@ struct dz_entry { // one image of a slab, in list order
     int slot[2] = {-1, -1};  // its file in the first / second encoder batch
 };
 
-struct dz_ws { // device buffers of the call
-    dev_guard d_dz, d_tabs, d_rgb;
-    int64_t dz_cap = 0, tabs_cap = 0, rgb_cap = 0;
+struct dz_ws { // device buffers of the call: grown from slab to slab, released when it ends
+    icl_dev_grow dz, tabs, rgb;
+    ~dz_ws()
+    {
+        for (icl_dev_grow *b : {&dz, &tabs, &rgb}) b->release();
+    }
 };
-
-static int dz_grow(icl_ctx *ctx, dev_guard &g, int64_t &cap, int64_t need)
-{
-    if (cap >= need) return ICL_OK;
-    if (g.p) (void)hipFree(g.p);
-    g.p = nullptr;
-    cap = 0;
-    if (hipMalloc(&g.p, (size_t)need) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "downsize: device buffer of %lld bytes", (long long)need);
-    cap = need;
-    return ICL_OK;
-}
 
 // One encoder batch over the entries `which` of a slab at attempt a (0: nw x nh, 1: half of it): gather / upload their RGB, encode, and
 // bring the files to the host.  files / off: the batch's files; entry e's is slot[a].
@@ -1480,7 +1466,7 @@ static int dz_encode_pass(icl_ctx *ctx, icl_ingest_ws *ws, dz_ws &B, std::vector
         }
         rgb_used += align16((int64_t)nw * nh * 3);
     }
-    ICL_TRY(dz_grow(ctx, B.d_rgb, B.rgb_cap, std::max<int64_t>(rgb_used, 16)));
+    ICL_TRY(B.rgb.ensure(ctx, (size_t)std::max<int64_t>(rgb_used, 16), "downsize: RGB buffer"));
     size_t k = 0;
     for (int e : which) { // host-decoded images: their RGB as it stands
         const dz_result &z = *E[(size_t)e].z;
@@ -1492,21 +1478,21 @@ static int dz_encode_pass(icl_ctx *ctx, icl_ingest_ws *ws, dz_ws &B, std::vector
             icl_resize_bilinear_u8(z.orig.data(), z.ow, z.oh, host_rgb.back().data(), it.w, it.h);
             src = host_rgb.back().data();
         }
-        ICL_HIP(ctx, hipMemcpyAsync((uint8_t *)B.d_rgb.p + it.rgb_off, src, (size_t)it.w * it.h * 3, hipMemcpyHostToDevice, st));
+        ICL_HIP(ctx, hipMemcpyAsync((uint8_t *)B.rgb.p + it.rgb_off, src, (size_t)it.w * it.h * 3, hipMemcpyHostToDevice, st));
     }
     if (!dz.empty()) {
-        ICL_TRY(dz_grow(ctx, B.d_dz, B.dz_cap, (int64_t)(dz.size() * sizeof(dz_image))));
-        ICL_TRY(dz_grow(ctx, B.d_tabs, B.tabs_cap, (int64_t)tabs.size()));
-        ICL_HIP(ctx, hipMemcpyAsync(B.d_dz.p, dz.data(), dz.size() * sizeof(dz_image), hipMemcpyHostToDevice, st));
-        ICL_HIP(ctx, hipMemcpyAsync(B.d_tabs.p, tabs.data(), tabs.size(), hipMemcpyHostToDevice, st));
+        ICL_TRY(B.dz.ensure(ctx, dz.size() * sizeof(dz_image), "downsize: image table"));
+        ICL_TRY(B.tabs.ensure(ctx, tabs.size(), "downsize: resize tables"));
+        ICL_HIP(ctx, hipMemcpyAsync(B.dz.p, dz.data(), dz.size() * sizeof(dz_image), hipMemcpyHostToDevice, st));
+        ICL_HIP(ctx, hipMemcpyAsync(B.tabs.p, tabs.data(), tabs.size(), hipMemcpyHostToDevice, st));
         const unsigned gx = (unsigned)std::min<int64_t>(icl_ceil_div(max_px, 256), 8192);
-        hipLaunchKernelGGL(jpeg_gather_resize_var_kernel, dim3(gx, (unsigned)dz.size()), dim3(256), 0, st, (const ingest_image *)ws->dev().imgs, (const dz_image *)B.d_dz.p,
-                           (const uint8_t *)B.d_tabs.p, (int64_t)tabs.size(), (const uint8_t *)ws->d_scratch, (uint8_t *)B.d_rgb.p, B.rgb_cap);
+        hipLaunchKernelGGL(jpeg_gather_resize_var_kernel, dim3(gx, (unsigned)dz.size()), dim3(256), 0, st, (const ingest_image *)ws->dev().imgs, (const dz_image *)B.dz.p,
+                           (const uint8_t *)B.tabs.p, (int64_t)tabs.size(), (const uint8_t *)ws->d_scratch, (uint8_t *)B.rgb.p, (int64_t)B.rgb.bytes);
         ICL_HIP(ctx, hipGetLastError());
     }
     ICL_HIP(ctx, hipStreamSynchronize(st)); // (the host vectors above go out of scope; the encoder synchronises anyway)
     const uint8_t *d_files = nullptr;
-    ICL_TRY(icl_jenc_run(ctx, (const uint8_t *)B.d_rgb.p, items.data(), (int64_t)items.size(), ICL_DOWNSIZE_QUALITY, &d_files, off));
+    ICL_TRY(icl_jenc_run(ctx, (const uint8_t *)B.rgb.p, items.data(), (int64_t)items.size(), ICL_DOWNSIZE_QUALITY, &d_files, off));
     files.resize((size_t)std::max<int64_t>(off.back(), 1));
     if (off.back()) ICL_HIP(ctx, hipMemcpy(files.data(), d_files, (size_t)off.back(), hipMemcpyDeviceToHost));
     return ICL_OK;

@@ -152,40 +152,6 @@ __global__ __launch_bounds__(NR_MERGE_ROWS) void nearest_merge_kernel(const floa
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-struct icl_nearest_ws { // sizes, exclude and the partial lists on the device; kept by the context between calls, grown on demand
-    char *buf = nullptr;
-    size_t bytes = 0;
-};
-
-void icl_nearest_free(icl_ctx *ctx)
-{
-    if (!ctx || !ctx->nearest) return;
-    if (ctx->nearest->buf) (void)hipFree(ctx->nearest->buf);
-    delete ctx->nearest;
-    ctx->nearest = nullptr;
-}
-
-static int nr_ensure(icl_ctx *ctx, size_t bytes, char **out)
-{
-    if (!ctx->nearest) ctx->nearest = new icl_nearest_ws;
-    icl_nearest_ws *w = ctx->nearest;
-    if (w->bytes < bytes) {
-        if (w->buf) { // an earlier call's kernels may still read it
-            ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(w->buf);
-            w->buf = nullptr;
-            w->bytes = 0;
-        }
-        if (hipMalloc((void **)&w->buf, bytes) != hipSuccess) {
-            w->buf = nullptr;
-            return icl_fail(ctx, ICL_ERR_NOMEM, "icl_nearest: %zu bytes of workspace do not fit", bytes);
-        }
-        w->bytes = bytes;
-    }
-    *out = w->buf;
-    return ICL_OK;
-}
-
 // What ICL_ERR_ARG covers apart from the pointers: the reason, or nullptr.
 static const char *nr_bad_arg(int64_t nq, int64_t n, int32_t k, const int32_t *q_size, const int32_t *e_size, const int64_t *exclude)
 {
@@ -220,17 +186,18 @@ static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_s
     const int64_t nbands = icl_ceil_div(nq, DT_TILE), ntiles = icl_ceil_div(n, DT_TILE);
     const int splits = nr_splits(ctx, nbands, ntiles);
     if (nbands * splits > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_nearest: grid too large (nq=%lld)", (long long)nq);
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t b_qs = q_size ? up16((size_t)nq * 4) : 0, b_es = e_size ? up16((size_t)n * 4) : 0, b_ex = exclude ? up16((size_t)nq * 4) : 0;
-    const size_t b_meta = b_qs + b_es + b_ex, b_part = splits > 1 ? up16((size_t)splits * nq * k * 4) : 0;
-    const size_t need = b_meta + 2 * b_part;
-    char *ws = nullptr;
-    if (need) ICL_TRY(nr_ensure(ctx, need, &ws));
+    // [q_size] [e_size] [exclude] [partial values] [partial indices], each on a 16-byte boundary; the first three go up in one copy
+    icl_ws_layout L(16);
+    const size_t o_qs = L.take(q_size ? (size_t)nq * 4 : 0), o_es = L.take(e_size ? (size_t)n * 4 : 0), o_ex = L.take(exclude ? (size_t)nq * 4 : 0);
+    const size_t b_meta = L.total, b_part = splits > 1 ? (size_t)splits * nq * k * 4 : 0;
+    const size_t o_val = L.take(b_part), o_idx = L.take(b_part), need = L.total;
+    if (need) ICL_TRY(ctx->nearest.ensure(ctx, need, "icl_nearest: workspace"));
+    char *ws = ctx->nearest.as<char>(); // (used only where need > 0)
     if (b_meta) {
         std::vector<int32_t> meta(b_meta / 4, 0);
         if (q_size) std::memcpy(meta.data(), q_size, (size_t)nq * 4);
-        if (e_size) std::memcpy(meta.data() + b_qs / 4, e_size, (size_t)n * 4);
-        for (int64_t i = 0; exclude && i < nq; ++i) meta[(b_qs + b_es) / 4 + i] = (int32_t)exclude[i]; // (n < 2^31)
+        if (e_size) std::memcpy(meta.data() + o_es / 4, e_size, (size_t)n * 4);
+        for (int64_t i = 0; exclude && i < nq; ++i) meta[o_ex / 4 + i] = (int32_t)exclude[i]; // (n < 2^31)
         // the caller's arrays and this vector may go away at return: a copy that has finished by then, ordered in front of the launch
         ICL_HIP(ctx, hipMemcpyAsync(ws, meta.data(), b_meta, hipMemcpyHostToDevice, ctx->stream));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -238,9 +205,9 @@ static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_s
     nr_args a;
     a.Q = d_Q;
     a.E = d_E;
-    a.qs = q_size ? (const int32_t *)ws : nullptr;
-    a.es = e_size ? (const int32_t *)(ws + b_qs) : nullptr;
-    a.ex = exclude ? (const int32_t *)(ws + b_qs + b_es) : nullptr;
+    a.qs = q_size ? (const int32_t *)(ws + o_qs) : nullptr;
+    a.es = e_size ? (const int32_t *)(ws + o_es) : nullptr;
+    a.ex = exclude ? (const int32_t *)(ws + o_ex) : nullptr;
     a.nq = nq;
     a.n = n;
     a.d = d;
@@ -250,8 +217,8 @@ static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_s
     a.ntiles = ntiles;
     a.nbands = nbands;
     a.splits = splits;
-    a.val = splits > 1 ? (float *)(ws + b_meta) : d_val;
-    a.idx = splits > 1 ? (int32_t *)(ws + b_meta + b_part) : d_idx;
+    a.val = splits > 1 ? (float *)(ws + o_val) : d_val;
+    a.idx = splits > 1 ? (int32_t *)(ws + o_idx) : d_idx;
     icl_lds_optin(ctx, (const void *)nearest_tile_select_kernel, (int)nr_lds_bytes(NS_KMAX));
     hipLaunchKernelGGL(nearest_tile_select_kernel, dim3((unsigned)(nbands * splits)), dim3(256), nr_lds_bytes(k), ctx->stream, a);
     ICL_HIP(ctx, hipGetLastError());
@@ -303,12 +270,10 @@ extern "C" int icl_nearest(icl_ctx *ctx, const float *Q, const int32_t *q_size, 
         if (nq == 0) return ICL_OK;
         dev_guard dQ, dE, dI, dV;
         const size_t bq = (size_t)nq * d * 4, be = (size_t)n * d * 4, bo = (size_t)nq * k * 4;
-        ICL_HIP(ctx, hipMalloc(&dQ.p, bq));
-        if (n) ICL_HIP(ctx, hipMalloc(&dE.p, be));
-        ICL_HIP(ctx, hipMalloc(&dI.p, bo));
-        ICL_HIP(ctx, hipMalloc(&dV.p, bo));
-        ICL_HIP(ctx, hipMemcpyAsync(dQ.p, Q, bq, hipMemcpyHostToDevice, ctx->stream));
-        if (n) ICL_HIP(ctx, hipMemcpyAsync(dE.p, E, be, hipMemcpyHostToDevice, ctx->stream));
+        ICL_TRY(icl_dev_upload(ctx, dQ, Q, bq, "icl_nearest: Q"));
+        if (n) ICL_TRY(icl_dev_upload(ctx, dE, E, be, "icl_nearest: E"));
+        ICL_TRY(icl_dev_alloc(ctx, dI, bo, "icl_nearest: idx"));
+        ICL_TRY(icl_dev_alloc(ctx, dV, bo, "icl_nearest: val"));
         ICL_TRY(nearest_dev_locked(ctx, (const float *)dQ.p, q_size, nq, (const float *)dE.p, e_size, n, d, k, max_size, exclude, (int32_t *)dI.p,
                                    (float *)dV.p));
         ICL_HIP(ctx, hipMemcpyAsync(idx, dI.p, bo, hipMemcpyDeviceToHost, ctx->stream));

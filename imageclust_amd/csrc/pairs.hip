@@ -186,49 +186,6 @@ __global__ __launch_bounds__(256) void pairs_fill_kernel(pw_args a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-struct icl_pairs_ws { // sizes, row counts, tile flags, row_ptr and the tile-row list on the device; kept by the context, grown on demand
-    char *buf = nullptr;
-    size_t bytes = 0;
-};
-
-void icl_pairs_free(icl_ctx *ctx)
-{
-    if (!ctx || !ctx->pairs) return;
-    if (ctx->pairs->buf) (void)hipFree(ctx->pairs->buf);
-    delete ctx->pairs;
-    ctx->pairs = nullptr;
-}
-
-static int pw_ensure(icl_ctx *ctx, size_t bytes, char **out)
-{
-    if (!ctx->pairs) ctx->pairs = new icl_pairs_ws;
-    icl_pairs_ws *w = ctx->pairs;
-    if (w->bytes < bytes) {
-        if (w->buf) { // an earlier call's kernels may still read it
-            ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(w->buf);
-            w->buf = nullptr;
-            w->bytes = 0;
-        }
-        if (hipMalloc((void **)&w->buf, bytes) != hipSuccess) {
-            w->buf = nullptr;
-            return icl_fail(ctx, ICL_ERR_NOMEM, "icl_pairs_within: %zu bytes of workspace do not fit", bytes);
-        }
-        w->bytes = bytes;
-    }
-    *out = w->buf;
-    return ICL_OK;
-}
-
-// A device buffer of the host form (E, col, val): one that does not fit is ICL_ERR_NOMEM, as the workspace is.
-static int pw_dev_alloc(icl_ctx *ctx, void **p, size_t bytes)
-{
-    if (hipMalloc(p, bytes) == hipSuccess) return ICL_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return icl_fail(ctx, ICL_ERR_NOMEM, "icl_pairs_within: %zu bytes of device memory do not fit", bytes);
-}
-
 // What ICL_ERR_ARG covers for the output side, shared by the three forms: the reason, or nullptr.
 static const char *pw_bad_out(int64_t n, float threshold, const int64_t *row_ptr, const void *col, const void *val, int64_t cap, const int64_t *total)
 {
@@ -267,30 +224,32 @@ static int pw_count_locked(icl_ctx *ctx, const float *d_E, const int32_t *size, 
                            int64_t *total, pw_plan &pl)
 {
     const int64_t T = icl_ceil_div(n, DT_TILE), ntiles = tri_tile_count(0, T);
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t b_sz = size ? up16((size_t)n * 4) : 0, b_cnt = up16((size_t)n * 4), b_tot = 16, b_hit = up16((size_t)ntiles);
-    const size_t b_ptr = up16((size_t)(n + 1) * 8), b_rows = up16((size_t)T * 4);
-    pl.need = b_sz + b_cnt + b_tot + b_hit + b_ptr + b_rows;
+    // [size] [row_count | totals | hit] [row_ptr] [tile rows], each on a 16-byte boundary.  The three pieces the count pass adds to are
+    // taken one after the other, so they are one contiguous range: o_cnt .. o_ptr, cleared by the single memset below.
+    icl_ws_layout L(16);
+    const size_t o_sz = L.take(size ? (size_t)n * 4 : 0), o_cnt = L.take((size_t)n * 4), o_tot = L.take(16), o_hit = L.take((size_t)ntiles);
+    const size_t o_ptr = L.take((size_t)(n + 1) * 8), o_rows = L.take((size_t)T * 4);
+    pl.need = L.total;
     pl.ntiles = ntiles;
-    char *ws = nullptr;
-    ICL_TRY(pw_ensure(ctx, pl.need, &ws));
+    ICL_TRY(ctx->pairs.ensure(ctx, pl.need, "icl_pairs_within: workspace"));
+    char *ws = ctx->pairs.as<char>();
     if (size) { // the caller's array may go away at return: a copy that has finished by then (the read-back below waits for it)
-        ICL_HIP(ctx, hipMemcpyAsync(ws, size, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_HIP(ctx, hipMemcpyAsync(ws + o_sz, size, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-    ICL_HIP(ctx, hipMemsetAsync(ws + b_sz, 0, b_cnt + b_tot + b_hit, ctx->stream));
+    ICL_HIP(ctx, hipMemsetAsync(ws + o_cnt, 0, o_ptr - o_cnt, ctx->stream));
     pw_args &a = pl.a;
     a.E = d_E;
-    a.sz = size ? (const int32_t *)ws : nullptr;
+    a.sz = size ? (const int32_t *)(ws + o_sz) : nullptr;
     a.n = n;
     a.d = d;
     a.vec = (d & 3) == 0 && ((uintptr_t)d_E & 15) == 0;
     a.thr = threshold;
     a.T = T;
-    a.row_count = (int32_t *)(ws + b_sz);
-    a.totals = (unsigned long long *)(ws + b_sz + b_cnt);
-    a.hit = (uint8_t *)(ws + b_sz + b_cnt + b_tot);
-    pl.d_row_ptr = ws + b_sz + b_cnt + b_tot + b_hit;
-    pl.d_rows = pl.d_row_ptr + b_ptr;
+    a.row_count = (int32_t *)(ws + o_cnt);
+    a.totals = (unsigned long long *)(ws + o_tot);
+    a.hit = (uint8_t *)(ws + o_hit);
+    pl.d_row_ptr = ws + o_ptr;
+    pl.d_rows = ws + o_rows;
     a.rows = (const int32_t *)pl.d_rows;
     a.row_ptr = (const int64_t *)pl.d_row_ptr;
     a.col = nullptr;
@@ -374,8 +333,7 @@ extern "C" int icl_pairs_within(icl_ctx *ctx, const float *E, const int32_t *siz
             return ICL_OK;
         }
         dev_guard dE, dC, dV;
-        ICL_TRY(pw_dev_alloc(ctx, &dE.p, (size_t)n * d * 4));
-        ICL_HIP(ctx, hipMemcpyAsync(dE.p, E, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_TRY(icl_dev_upload(ctx, dE, E, (size_t)n * d * 4, "icl_pairs_within: E"));
         pw_plan pl;
         ICL_TRY(pw_count_locked(ctx, (const float *)dE.p, size, n, d, threshold, row_ptr, total, pl));
         if (*total > cap) {
@@ -385,8 +343,8 @@ extern "C" int icl_pairs_within(icl_ctx *ctx, const float *E, const int32_t *siz
         }
         if (*total == 0) return ICL_OK;
         const size_t bo = (size_t)*total * 4;
-        ICL_TRY(pw_dev_alloc(ctx, &dC.p, bo));
-        ICL_TRY(pw_dev_alloc(ctx, &dV.p, bo));
+        ICL_TRY(icl_dev_alloc(ctx, dC, bo, "icl_pairs_within: col"));
+        ICL_TRY(icl_dev_alloc(ctx, dV, bo, "icl_pairs_within: val"));
         ICL_TRY(pw_fill_locked(ctx, row_ptr, n, pl, (int32_t *)dC.p, (float *)dV.p));
         ICL_HIP(ctx, hipMemcpyAsync(col, dC.p, bo, hipMemcpyDeviceToHost, ctx->stream));
         ICL_HIP(ctx, hipMemcpyAsync(val, dV.p, bo, hipMemcpyDeviceToHost, ctx->stream));

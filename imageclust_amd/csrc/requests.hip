@@ -49,48 +49,29 @@ __global__ __launch_bounds__(256) void requests_assemble_kernel(const float *__r
 }
 
 struct icl_requests_ws {
-    void *buf = nullptr;
-    size_t bytes = 0;
+    icl_dev_grow buf; // grow-only, as the workspace of icl_cluster_many
     hipEvent_t ev[4] = {};
 };
 
 void icl_requests_free(icl_ctx *ctx)
 {
     if (!ctx || !ctx->requests) return;
-    if (ctx->requests->buf) (void)hipFree(ctx->requests->buf);
+    ctx->requests->buf.release();
     for (hipEvent_t e : ctx->requests->ev)
         if (e) (void)hipEventDestroy(e);
     delete ctx->requests;
     ctx->requests = nullptr;
 }
 
-// grow-only, as icl_many_ws
 static int rq_ensure(icl_ctx *ctx, size_t bytes, char **out)
 {
     if (!ctx->requests) ctx->requests = new icl_requests_ws;
     icl_requests_ws *w = ctx->requests;
     for (hipEvent_t &e : w->ev)
         if (!e) ICL_HIP(ctx, hipEventCreate(&e));
-    if (w->bytes < bytes) {
-        if (w->buf) {
-            ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(w->buf);
-            w->buf = nullptr;
-            w->bytes = 0;
-        }
-        const size_t b = std::max(bytes, (size_t)1 << 20);
-        if (hipMalloc(&w->buf, b) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_requests: device buffers of %zu bytes", b);
-        w->bytes = b;
-    }
-    *out = (char *)w->buf;
+    ICL_TRY(w->buf.ensure(ctx, bytes, "icl_cluster_requests: device buffers", (size_t)1 << 20));
+    *out = w->buf.as<char>();
     return ICL_OK;
-}
-
-static size_t rq_take(size_t &off, size_t bytes)
-{
-    const size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
 }
 
 // d, e_off, e_len; false when a size is negative or a row length does not fit int32_t
@@ -173,12 +154,11 @@ static int cluster_requests_locked(icl_ctx *ctx, const char *what, int32_t nreq,
     const int64_t rows = img[(size_t)nreq], nlab = rows ? label_off[rows] : 0;
 
     // ---- device buffers: [E] [dense rows] [image table] [label_off] [label_idx]; E first, on the allocation's 256-byte boundary ----
-    size_t off = 0;
-    const size_t o_e = rq_take(off, (size_t)e_len * 4), o_dense = rq_take(off, (size_t)rows * head * 4),
-                 o_tab = rq_take(off, (size_t)rows * sizeof(rq_image)), o_loff = rq_take(off, (size_t)(rows + 1) * 8),
-                 o_lidx = rq_take(off, (size_t)nlab * 4);
+    icl_ws_layout L(256);
+    const size_t o_e = L.take((size_t)e_len * 4), o_dense = L.take((size_t)rows * head * 4), o_tab = L.take((size_t)rows * sizeof(rq_image)),
+                 o_loff = L.take((size_t)(rows + 1) * 8), o_lidx = L.take((size_t)nlab * 4);
     char *ws = nullptr;
-    ICL_TRY(rq_ensure(ctx, off, &ws));
+    ICL_TRY(rq_ensure(ctx, L.total, &ws));
     hipEvent_t *ev = ctx->requests->ev;
     float *d_E = (float *)(ws + o_e), *d_dense = (float *)(ws + o_dense);
     hipStream_t st = ctx->stream;

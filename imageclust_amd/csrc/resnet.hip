@@ -899,14 +899,6 @@ static int launch_conv(icl_ctx *ctx, int prec, const conv_layer &L, const void *
 }
 
 // ---- per-layer entry points of the parity tests: host tensors in, host tensors out -----------------------------------------
-// a device allocation that lives as long as its scope
-struct dev_buf {
-    void *p = nullptr;
-    dev_buf() = default;
-    dev_buf(const dev_buf &) = delete;
-    dev_buf &operator=(const dev_buf &) = delete;
-    ~dev_buf() { if (p) (void)hipFree(p); }
-};
 // n values in the storage format of prec back to fp32 (unpack_storage; the stream that wrote src has been synchronised).  The other
 // direction is upload_as (resnet_model.h), the loader's own.
 static int from_dev(icl_ctx *ctx, int prec, const void *src, size_t n, float *dst)
@@ -917,16 +909,17 @@ static int from_dev(icl_ctx *ctx, int prec, const void *src, size_t n, float *ds
     return ICL_OK;
 }
 // the 256 zero bytes the convolution kernels read for padded taps (the loaded model has its own: icl_model::zero)
-static int zero_page(icl_ctx *ctx, const char *who, dev_buf &dz)
+static int zero_page(icl_ctx *ctx, const char *who, dev_guard &dz)
 {
-    if (hipMalloc(&dz.p, 256) != hipSuccess || hipMemset(dz.p, 0, 256) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "%s: zero page", who);
+    ICL_TRY(icl_dev_alloc(ctx, dz, 256, "%s: zero page", who));
+    ICL_HIP(ctx, hipMemset(dz.p, 0, 256));
     return ICL_OK;
 }
 // What the body of an entry point leaves to run_entry: the device buffers it made, which live until the output has been copied back,
 // and that output: n values in the storage of prec, written on ctx->stream.
 struct entry_io {
-    std::deque<dev_buf> bufs;
-    dev_buf &buf() { return bufs.emplace_back(); }
+    std::deque<dev_guard> bufs;
+    dev_guard &buf() { return bufs.emplace_back(); }
     const void *out = nullptr;
     int prec = ICL_PREC_FP32;
     size_t n = 0;
@@ -964,14 +957,14 @@ extern "C" int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, i
         const size_t nx = (size_t)B * H * H * Cin, ny = (size_t)B * Ho * Ho * Cout;
         std::vector<float> wp;
         pack_ohwi(w, Cout, Cin, k, wp);
-        dev_buf &dx = io.buf(), &dw = io.buf(), &dr = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
+        dev_guard &dx = io.buf(), &dw = io.buf(), &dr = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
         ICL_TRY(upload_as(ctx, prec, &dx.p, x, nx));
         ICL_TRY(zero_page(ctx, "icl_conv2d_fused", dz));
         ICL_TRY(upload_as(ctx, prec, &dw.p, wp.data(), wp.size()));
         if (residual) ICL_TRY(upload_as(ctx, prec, &dr.p, residual, ny));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsc.p, scale, (size_t)Cout));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsh.p, shift, (size_t)Cout));
-        if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_fused: output alloc");
+        ICL_TRY(icl_dev_alloc(ctx, dy, ny * prec_act_bytes(prec), "icl_conv2d_fused: output"));
         io.returns(prec, dy.p, ny);
         return launch_conv_prec(ctx, prec, conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, H, Cin, Cout, k, stride, pad, relu));
     });
@@ -993,14 +986,14 @@ extern "C" int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, in
         const size_t nx = (size_t)B * Ho * Ho * Cin, nx2 = (size_t)B * H2 * H2 * Cin2, ny = (size_t)B * Ho * Ho * Cout;
         std::vector<float> wp;
         pack_row_concat(w1, Cin, w2, Cin2, Cout, wp);
-        dev_buf &dx = io.buf(), &dx2 = io.buf(), &dw = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
+        dev_guard &dx = io.buf(), &dx2 = io.buf(), &dw = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
         ICL_TRY(upload_as(ctx, prec, &dx.p, x, nx));
         ICL_TRY(upload_as(ctx, prec, &dx2.p, x2, nx2));
         ICL_TRY(zero_page(ctx, "icl_conv2d_dual", dz));
         ICL_TRY(upload_as(ctx, prec, &dw.p, wp.data(), wp.size()));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsc.p, scale, (size_t)Cout));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsh.p, shift, (size_t)Cout));
-        if (hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_conv2d_dual: output alloc");
+        ICL_TRY(icl_dev_alloc(ctx, dy, ny * prec_act_bytes(prec), "icl_conv2d_dual: output"));
         conv_args a = conv_plain(dx.p, dw.p, dy.p, nullptr, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, Ho, Cin, Cout, 1, 1, 0, relu);
         conv_add_operand(a, dx2.p, H2, Cin2, stride2);
         io.returns(prec, dy.p, ny);
@@ -1188,9 +1181,9 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
     if (!prec_ok(prec)) return icl_fail(ctx, ICL_ERR_ARG, "bad prec");
     return run_entry(ctx, "icl_stem_pool", true, out, [&](entry_io &io) -> int {
         const size_t ny = (size_t)B * 56 * 56 * 64;
-        dev_buf &dimg = io.buf(), &dy = io.buf();
-        if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess || hipMalloc(&dy.p, ny * prec_act_bytes(prec)) != hipSuccess)
-            return icl_fail(ctx, ICL_ERR_NOMEM, "icl_stem_pool: device buffers");
+        dev_guard &dimg = io.buf(), &dy = io.buf();
+        ICL_TRY(icl_dev_alloc(ctx, dimg, (size_t)B * ICL_IMG_BYTES, "icl_stem_pool: images"));
+        ICL_TRY(icl_dev_alloc(ctx, dy, ny * prec_act_bytes(prec), "icl_stem_pool: output"));
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
         with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, ctx->stream); });
         io.returns(prec, dy.p, ny);
@@ -1228,7 +1221,7 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
             for (int co = 0; co < 256; ++co) h3[(size_t)co] = sh3[co] + shds[co];
         }
         const std::vector<float> &w3p = has_ds ? f3ds : f3;
-        dev_buf &dx = io.buf(), &dy = io.buf(), &dw1 = io.buf(), &dw2 = io.buf(), &dw3 = io.buf(), &d1h = io.buf(), &d2h = io.buf(), &d3h = io.buf();
+        dev_guard &dx = io.buf(), &dy = io.buf(), &dw1 = io.buf(), &dw2 = io.buf(), &dw3 = io.buf(), &d1h = io.buf(), &d2h = io.buf(), &d3h = io.buf();
         ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dx.p, x, nx));
         ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dw1.p, f1.data(), f1.size()));
         ICL_TRY(upload_as(ctx, ICL_PREC_BF16, &dw2.p, f2.data(), f2.size()));
@@ -1236,7 +1229,7 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d1h.p, sh1, 64));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d2h.p, sh2, 64));
         ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &d3h.p, h3.data(), 256));
-        if (hipMalloc(&dy.p, ny * 2) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_bottleneck56: output alloc");
+        ICL_TRY(icl_dev_alloc(ctx, dy, ny * 2, "icl_bottleneck56: output"));
         bneck_args a = {};
         a.X = (const uint16_t *)dx.p; a.Y = (uint16_t *)dy.p; a.W1 = (const uint16_t *)dw1.p; a.W2 = (const uint16_t *)dw2.p; a.W3 = (const uint16_t *)dw3.p;
         a.sh1 = (const float *)d1h.p; a.sh2 = (const float *)d2h.p; a.sh3 = (const float *)d3h.p;
@@ -1263,8 +1256,8 @@ extern "C" int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *img, int B,
                 C = ctx->model->conv[i].rec.cout;
                 ++blk;
             }
-        dev_buf &dimg = io.buf();
-        if (hipMalloc(&dimg.p, (size_t)B * ICL_IMG_BYTES) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_embed_taps: image buffer");
+        dev_guard &dimg = io.buf();
+        ICL_TRY(icl_dev_alloc(ctx, dimg, (size_t)B * ICL_IMG_BYTES, "icl_embed_taps: image buffer"));
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: upload");
         const void *x = nullptr;
         const int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, ICL_HEAD_POOLED, nullptr, 0, ctx->stream, tap, &x); });
@@ -1375,25 +1368,14 @@ extern "C" int icl_embed_u8(icl_ctx *ctx, const uint8_t *img, int64_t n, int hea
     // calling thread busy for the whole copy) while the forward passes of slab i run -- the PCIe-inclusive rate of DESIGN.md 5.
     const int64_t slab = std::min<int64_t>(n, 4096);
     const int nbuf = n > slab ? 2 : 1;
-    uint8_t *d_img[2] = {nullptr, nullptr};
-    float *d_out = nullptr;
-    hipStream_t cs = nullptr;
-    struct cleanup {
-        uint8_t **img;
-        float **out;
-        hipStream_t *cs;
-        ~cleanup()
-        {
-            for (int q = 0; q < 2; ++q)
-                if (img[q]) (void)hipFree(img[q]);
-            if (*out) (void)hipFree(*out);
-            if (*cs) (void)hipStreamDestroy(*cs);
-        }
-    } cl{d_img, &d_out, &cs};
-    ICL_HIP(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    for (int q = 0; q < nbuf; ++q)
-        if (hipMalloc((void **)&d_img[q], (size_t)slab * ICL_IMG_BYTES) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "embed image slab (%lld images)", (long long)slab);
-    if (hipMalloc((void **)&d_out, (size_t)slab * head * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "embed output buffer");
+    hip_guard<hipStream_t, hipStreamDestroy> g_cs; // (declared first: destroyed behind the buffers)
+    dev_guard g_img[2], g_out;
+    ICL_HIP(ctx, hipStreamCreateWithFlags(&g_cs.p, hipStreamNonBlocking));
+    for (int q = 0; q < nbuf; ++q) ICL_TRY(icl_dev_alloc(ctx, g_img[q], (size_t)slab * ICL_IMG_BYTES, "embed image slab (%lld images)", (long long)slab));
+    ICL_TRY(icl_dev_alloc(ctx, g_out, (size_t)slab * head * 4, "embed output buffer"));
+    uint8_t *const d_img[2] = {g_img[0].as<uint8_t>(), g_img[1].as<uint8_t>()};
+    float *const d_out = g_out.as<float>();
+    const hipStream_t cs = g_cs.p;
     auto upload = [&](int64_t i, uint8_t *dst) -> hipError_t {
         const int64_t cnt = std::min(slab, n - i);
         hipError_t e = hipMemcpyAsync(dst, img + i * ICL_IMG_BYTES, (size_t)cnt * ICL_IMG_BYTES, hipMemcpyHostToDevice, cs);

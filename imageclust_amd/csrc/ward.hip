@@ -212,10 +212,7 @@ struct icl_ward_ws {
     int32_t *merges = nullptr; // [2*N]
     ward_state *st = nullptr;
     // find_closest scratch
-    float *fc_min = nullptr;
-    int32_t *fc_nn = nullptr;
-    int64_t fc_cap = 0;
-    int64_t *fc_out = nullptr;
+    icl_dev_grow fc_min, fc_nn, fc_out; // find_closest_locked: float[n], int32_t[n], int64_t[2] (fc_ensure)
     // hipGraph of GRAPH_STEPS merge steps (all step-varying state lives in device memory, so one capture replays)
     hipGraphExec_t graph_exec = nullptr;
     ward_graph_key graph_key;  // what graph_exec was captured for
@@ -234,16 +231,16 @@ struct icl_ward_ws {
 
 void icl_ward_free(icl_ctx *ctx)
 {
-    if (ctx->ward_rowoff) (void)hipFree(ctx->ward_rowoff);
-    ctx->ward_rowoff = nullptr;
+    ctx->ward_rowoff.release();
     ctx->ward_rowoff_n = 0;
     icl_ward_ws *w = ctx->ward;
     if (!w) return;
     void *ptrs[] = {w->CT, w->Crow, w->cnew, w->cnewI, w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid,
-                    w->Dtri, w->merges, w->st, w->fc_min, w->fc_nn, w->fc_out, w->nrm, w->colsum, w->zero, w->mpk, w->bl1, w->bex, w->rowub};
+                    w->Dtri, w->merges, w->st, w->nrm, w->colsum, w->zero, w->mpk, w->bl1, w->bex, w->rowub};
     if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (icl_dev_grow *b : {&w->fc_min, &w->fc_nn, &w->fc_out}) b->release();
     delete w;
     ctx->ward = nullptr;
 }
@@ -4702,17 +4699,16 @@ static int ward_ensure(icl_ctx *ctx, int64_t n, int d)
 // A rank that only computes distance rows needs the row-offset table, not the 8 n^2-byte triangle.
 static int ward_ensure_rowoff(icl_ctx *ctx, int64_t n)
 {
-    if (ctx->ward_rowoff && ctx->ward_rowoff_n >= n) return ICL_OK;
-    if (ctx->ward_rowoff) (void)hipFree(ctx->ward_rowoff);
-    ctx->ward_rowoff = nullptr;
+    if (ctx->ward_rowoff.p && ctx->ward_rowoff_n >= n) return ICL_OK;
+    ctx->ward_rowoff_n = 0; // (nothing valid until the upload below has finished)
     std::vector<int64_t> h((size_t)n + 2);
     int64_t off = 0;
     for (int64_t r = 0; r <= n + 1; ++r) {
         h[(size_t)r] = off;
         off += (r + 3) / 4 * 4;
     }
-    ICL_HIP(ctx, hipMalloc((void **)&ctx->ward_rowoff, h.size() * sizeof(int64_t)));
-    ICL_HIP(ctx, hipMemcpyAsync(ctx->ward_rowoff, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    ICL_TRY(ctx->ward_rowoff.ensure(ctx, h.size() * sizeof(int64_t), "ward row offsets"));
+    ICL_HIP(ctx, hipMemcpyAsync(ctx->ward_rowoff.p, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->ward_rowoff_n = n;
     return ICL_OK;
@@ -4722,17 +4718,10 @@ static int fc_ensure(icl_ctx *ctx, int64_t n)
 {
     if (!ctx->ward) ctx->ward = new icl_ward_ws();
     icl_ward_ws *w = ctx->ward;
-    if (w->fc_cap < n || !w->fc_out) {
-        if (w->fc_min) (void)hipFree(w->fc_min);
-        if (w->fc_nn) (void)hipFree(w->fc_nn);
-        w->fc_min = nullptr;
-        w->fc_nn = nullptr;
-        ICL_HIP(ctx, hipMalloc((void **)&w->fc_min, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
-        ICL_HIP(ctx, hipMalloc((void **)&w->fc_nn, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
-        if (!w->fc_out) ICL_HIP(ctx, hipMalloc((void **)&w->fc_out, 2 * sizeof(int64_t)));
-        w->fc_cap = n;
-    }
-    return ICL_OK;
+    const size_t rows = (size_t)std::max<int64_t>(n, 1);
+    ICL_TRY(w->fc_min.ensure(ctx, rows * sizeof(float), "icl_find_closest: row minima"));
+    ICL_TRY(w->fc_nn.ensure(ctx, rows * sizeof(int32_t), "icl_find_closest: row partners"));
+    return w->fc_out.ensure(ctx, 2 * sizeof(int64_t), "icl_find_closest: result");
 }
 
 extern "C" int icl_calc_optimal_clusters(int64_t total, int64_t min_size, int64_t max_size, int64_t *k) { return ward_optimal_k(total, min_size, max_size, k); }
@@ -4782,29 +4771,17 @@ extern "C" int icl_ward_distance_matrix(icl_ctx *ctx, const float *C, const int3
     return no_throw(ctx, "icl_ward_distance_matrix", [&]() -> int {
     if (!ctx || n < 0 || d < 0 || ld < n || (n && (!C || !D))) return icl_fail(ctx, ICL_ERR_ARG, "icl_ward_distance_matrix: bad argument");
     if (n == 0) return ICL_OK;
-    float *dC = nullptr, *dD = nullptr;
-    int32_t *dS = nullptr;
-    int rc = ICL_OK;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        icl_device_guard g(ctx->device);
-        ICL_HIP(ctx, hipMalloc((void **)&dC, (size_t)std::max<int64_t>(n * d, 1) * 4));
-        ICL_HIP(ctx, hipMalloc((void **)&dD, (size_t)(n * n) * 4));
-        if (sizes) ICL_HIP(ctx, hipMalloc((void **)&dS, (size_t)n * 4));
-        ICL_HIP(ctx, hipMemcpyAsync(dC, C, (size_t)(n * d) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (sizes) ICL_HIP(ctx, hipMemcpyAsync(dS, sizes, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_dist_exact(ctx, dC, dS, n, d, dD, nullptr, n, 1);
-        if (rc == ICL_OK) {
-            hipError_t e = hipMemcpy2DAsync(D, (size_t)ld * 4, dD, (size_t)n * 4, (size_t)n * 4, (size_t)n, hipMemcpyDeviceToHost,
-                                            ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = icl_fail(ctx, ICL_ERR_HIP, "distance matrix copy-back failed: %s", hipGetErrorString(e));
-        }
-        (void)hipFree(dC);
-        (void)hipFree(dD);
-        if (dS) (void)hipFree(dS);
-    }
-    return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    dev_guard dC, dD, dS;
+    ICL_TRY(icl_dev_alloc(ctx, dC, (size_t)std::max<int64_t>(n * d, 1) * 4, "icl_ward_distance_matrix: C"));
+    ICL_TRY(icl_dev_alloc(ctx, dD, (size_t)(n * n) * 4, "icl_ward_distance_matrix: D"));
+    ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, (size_t)(n * d) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (sizes) ICL_TRY(icl_dev_upload(ctx, dS, sizes, (size_t)n * 4, "icl_ward_distance_matrix: sizes"));
+    ICL_TRY(launch_dist_exact(ctx, dC.as<float>(), dS.as<int32_t>(), n, d, dD.as<float>(), nullptr, n, 1));
+    ICL_HIP(ctx, hipMemcpy2DAsync(D, (size_t)ld * 4, dD.p, (size_t)n * 4, (size_t)n * 4, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICL_OK;
     });
 }
 
@@ -4818,12 +4795,12 @@ static int find_closest_locked(icl_ctx *ctx, const float *d_D, int64_t n, int64_
     {
         icl_prof_scope ps(ctx, ICL_K_ROWMIN, 0.0, 4.0 * (double)n * (double)(n - 1) * 0.5);
         const int blocks = (int)std::min<int64_t>(n, 256 * 32);
-        hipLaunchKernelGGL(row_argmin_dense_kernel, dim3(blocks), dim3(n > 4096 ? 1024 : 256), 0, ctx->stream, d_D, n, ld, w->fc_min, w->fc_nn);
+        hipLaunchKernelGGL(row_argmin_dense_kernel, dim3(blocks), dim3(n > 4096 ? 1024 : 256), 0, ctx->stream, d_D, n, ld, w->fc_min.as<float>(), w->fc_nn.as<int32_t>());
     }
-    hipLaunchKernelGGL(select_dense_kernel, dim3(1), dim3(1024), 0, ctx->stream, w->fc_min, w->fc_nn, n, w->fc_out);
+    hipLaunchKernelGGL(select_dense_kernel, dim3(1), dim3(1024), 0, ctx->stream, w->fc_min.as<float>(), w->fc_nn.as<int32_t>(), n, w->fc_out.as<int64_t>());
     ICL_HIP(ctx, hipGetLastError());
     int64_t h[2];
-    ICL_HIP(ctx, hipMemcpyAsync(h, w->fc_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipMemcpyAsync(h, w->fc_out.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *i = h[0];
     *j = h[1];
@@ -4847,13 +4824,9 @@ extern "C" int icl_find_closest(icl_ctx *ctx, const float *D, int64_t n, int64_t
     if (n < 2) return ICL_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    float *dD = nullptr;
-    ICL_HIP(ctx, hipMalloc((void **)&dD, (size_t)(n * ld) * 4));
-    hipError_t e = hipMemcpyAsync(dD, D, (size_t)(n * ld) * 4, hipMemcpyHostToDevice, ctx->stream);
-    int rc = e == hipSuccess ? find_closest_locked(ctx, dD, n, ld, i, j)
-                             : icl_fail(ctx, ICL_ERR_HIP, "find_closest upload failed: %s", hipGetErrorString(e));
-    (void)hipFree(dD);
-    return rc;
+    dev_guard dD;
+    ICL_TRY(icl_dev_upload(ctx, dD, D, (size_t)(n * ld) * 4, "icl_find_closest: D"));
+    return find_closest_locked(ctx, dD.as<float>(), n, ld, i, j);
     });
 }
 
@@ -5100,7 +5073,7 @@ static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const flo
     if (p.fill == WARD_FILL_FAST) {
         ICL_TRY(icl_dist_mfma_launch(ctx, d_E, n, d, w->Dtri, w->rowoff, 0));
     } else if (p.use_bound) {
-        if (hipMalloc(&c.ec.p, (size_t)n * ward_bound_K(d) * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "centred copy of E (%lld x %d floats)", (long long)n, ward_bound_K(d));
+        ICL_TRY(icl_dev_alloc(ctx, c.ec, (size_t)n * ward_bound_K(d) * 4, "centred copy of E (%lld x %d floats)", (long long)n, ward_bound_K(d)));
         ward_centred b{w->colsum, (float *)c.ec.p, w->nrm, w->zero};
         ICL_TRY(ward_centre(ctx, d_E, n, d, &b));
         rf = wrefine{d_E, w->nrm, n, d, b.ceps, b.gam, nullptr, 0.0f};
@@ -5121,11 +5094,9 @@ static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const flo
             hipLaunchKernelGGL(ward_lb_consts_kernel, dim3(1), dim3(1024), 0, ctx->stream, w->nrm, w->colsum, n, d, p.max_size, w->st);
         }
         bool i8 = p.fill == WARD_FILL_BOUND_I8;
-        if (i8 && hipMalloc(&c.pq.p, icl_dist_i8_pq_bytes(n, d)) != hipSuccess) { // (3 D bytes per row of scratch: should it not fit beside a 250 GB matrix -- the f32 GEMM needs none)
-            (void)hipGetLastError();
-            c.pq.p = nullptr;
-            i8 = false;
-        }
+        // (3 D bytes per row of scratch: should it not fit beside a 250 GB matrix -- the f32 GEMM needs none, and the call goes on with it; only the
+        // last-error text tells)
+        if (i8 && icl_dev_alloc(ctx, c.pq, icl_dist_i8_pq_bytes(n, d), "scratch of the integer GEMM") != ICL_OK) i8 = false;
         if (i8) {
             rf.l1 = w->bl1;
             rf.ex = w->bex;
@@ -5477,8 +5448,7 @@ static int ward_run_stages(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d,
     ICL_TRY(ward_ensure(ctx, n, d));
     icl_ward_ws *w = ctx->ward;
     if (seed) {
-        if (hipMalloc(&c.eff.p, (size_t)n * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld seed sizes on the device", (long long)n);
-        ICL_HIP(ctx, hipMemcpyAsync(c.eff.p, seed->h_eff, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_TRY(icl_dev_upload(ctx, c.eff, seed->h_eff, (size_t)n * 4, "icl_cluster_seeded: seed sizes"));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_eff is the caller's to free once this returns, whatever it returns)
         seed->d_eff = (const int32_t *)c.eff.p;
     }
@@ -5563,8 +5533,7 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
         std::vector<int32_t> src((size_t)m, -1);
         for (size_t f = 0; f < finals.size(); f += 2) src[(size_t)finals[f + 1]] = finals[f];
         dev_guard g_src;
-        if (hipMalloc(&g_src.p, (size_t)m * 4) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: C_out table of %lld rows", (long long)m);
-        ICL_HIP(ctx, hipMemcpyAsync(g_src.p, src.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+        ICL_TRY(icl_dev_upload(ctx, g_src, src.data(), (size_t)m * 4, "icl_cluster_seeded: C_out table"));
         hipLaunchKernelGGL(ward_seed_cout_kernel, dim3((unsigned)m), dim3(256), 0, ctx->stream, (const int32_t *)g_src.p, d_C, w ? (const float *)w->Crow : nullptr,
                            w ? (const int32_t *)w->id_slot : nullptr, m, d, w ? w->S : 0, d_C_out);
         ICL_HIP(ctx, hipGetLastError());
@@ -5603,8 +5572,8 @@ extern "C" int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32
     icl_device_guard g(ctx->device);
     const size_t bytes = (size_t)m * (size_t)d * 4;
     dev_guard dC, dO;
-    if (hipMalloc(&dC.p, std::max<size_t>(bytes, 16)) != hipSuccess || (C_out && hipMalloc(&dO.p, std::max<size_t>(bytes, 16)) != hipSuccess))
-        return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_seeded: %lld x %d floats on the device", (long long)m, d);
+    ICL_TRY(icl_dev_alloc(ctx, dC, std::max<size_t>(bytes, 16), "icl_cluster_seeded: C (%lld x %d floats)", (long long)m, d));
+    if (C_out) ICL_TRY(icl_dev_alloc(ctx, dO, std::max<size_t>(bytes, 16), "icl_cluster_seeded: C_out (%lld x %d floats)", (long long)m, d));
     if (bytes) ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, bytes, hipMemcpyHostToDevice, ctx->stream));
     const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p);
     if (C_out && bytes && rc != ICL_ERR_HIP && rc != ICL_ERR_NOMEM) { // (a refused problem's rows are zero)
@@ -5666,17 +5635,18 @@ extern "C" int icl_ward_distance_rows_dev(icl_ctx *ctx, const float *d_E, int64_
         // and constants, so the flagged entries mean on the clustering GPU exactly what they mean here
         const int K = ward_bound_K(d);
         dev_guard ec, nrm, cs, zero;
-        if (hipMalloc(&ec.p, (size_t)n * K * 4) != hipSuccess || hipMalloc(&nrm.p, (size_t)n * 4) != hipSuccess || hipMalloc(&cs.p, icl_dist_colsum_doubles(K) * 8) != hipSuccess ||
-            hipMalloc(&zero.p, 256) != hipSuccess)
-            return icl_fail(ctx, ICL_ERR_NOMEM, "icl_ward_distance_rows_dev: centred copy of E (%lld x %d floats)", (long long)n, K);
+        ICL_TRY(icl_dev_alloc(ctx, ec, (size_t)n * K * 4, "icl_ward_distance_rows_dev: centred copy of E (%lld x %d floats)", (long long)n, K));
+        ICL_TRY(icl_dev_alloc(ctx, nrm, (size_t)n * 4, "icl_ward_distance_rows_dev: centred norms"));
+        ICL_TRY(icl_dev_alloc(ctx, cs, icl_dist_colsum_doubles(K) * 8, "icl_ward_distance_rows_dev: column sums"));
+        ICL_TRY(icl_dev_alloc(ctx, zero, 256, "icl_ward_distance_rows_dev: zero page"));
         ICL_HIP(ctx, hipMemsetAsync(zero.p, 0, 256, ctx->stream));
         ward_centred b{(double *)cs.p, (float *)ec.p, (float *)nrm.p, zero.p};
         ICL_TRY(ward_centre(ctx, d_E, n, d, &b));
-        ICL_TRY(ward_bounds_f32(ctx, b, n, d_span - tri_rowoff(row_lo), ctx->ward_rowoff, row_lo, row_hi));
+        ICL_TRY(ward_bounds_f32(ctx, b, n, d_span - tri_rowoff(row_lo), ctx->ward_rowoff.as<int64_t>(), row_lo, row_hi));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (before the temporaries go)
         return ICL_OK;
     }
-    ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, d_span - tri_rowoff(row_lo), ctx->ward_rowoff, 0, 0, row_lo / DT_TILE,
+    ICL_TRY(launch_dist_exact_rows(ctx, d_E, nullptr, n, d, d_span - tri_rowoff(row_lo), ctx->ward_rowoff.as<int64_t>(), 0, 0, row_lo / DT_TILE,
                                    icl_ceil_div(row_hi, DT_TILE)));
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICL_OK;
@@ -5861,20 +5831,12 @@ extern "C" int icl_cluster(icl_ctx *ctx, const float *E, int64_t n, int32_t d, i
         return icl_fail(ctx, ICL_ERR_ARG, "icl_cluster: bad argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    float *dE = nullptr;
-    if (n * d > 0) {
-        ICL_HIP(ctx, hipMalloc((void **)&dE, (size_t)(n * d) * 4));
-        hipError_t e = hipMemcpyAsync(dE, E, (size_t)(n * d) * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(dE);
-            return icl_fail(ctx, ICL_ERR_HIP, "icl_cluster upload failed: %s", hipGetErrorString(e));
-        }
-    } else if (n > 0) {
-        ICL_HIP(ctx, hipMalloc((void **)&dE, 16));
-    }
-    int rc = cluster_locked(ctx, dE, n, d, min_size, max_size, update, cluster_id, member_rank, n_clusters);
-    if (dE) (void)hipFree(dE);
-    return rc;
+    dev_guard dE;
+    if (n * d > 0)
+        ICL_TRY(icl_dev_upload(ctx, dE, E, (size_t)(n * d) * 4, "icl_cluster: E"));
+    else if (n > 0)
+        ICL_TRY(icl_dev_alloc(ctx, dE, 16, "icl_cluster: E"));
+    return cluster_locked(ctx, dE.as<float>(), n, d, min_size, max_size, update, cluster_id, member_rank, n_clusters);
     });
 }
 
@@ -5892,18 +5854,15 @@ extern "C" int icl_merge_centroid(icl_ctx *ctx, const float *ca, int64_t sa, con
     if (d == 0) return ICL_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    float *buf = nullptr;
-    ICL_HIP(ctx, hipMalloc((void **)&buf, (size_t)d * 12));
-    hipError_t e = hipMemcpyAsync(buf, ca, (size_t)d * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(buf + d, cb, (size_t)d * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(merge_centroid_kernel, dim3((unsigned)icl_ceil_div(d, 256)), dim3(256), 0, ctx->stream, buf, (float)sa,
-                           buf + d, (float)sb, (float)(sa + sb), d, buf + 2 * (int64_t)d);
-        e = hipMemcpyAsync(out, buf + 2 * (int64_t)d, (size_t)d * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_merge_centroid: %s", hipGetErrorString(e));
+    dev_guard g_buf; // [ca] [cb] [out]
+    ICL_TRY(icl_dev_alloc(ctx, g_buf, (size_t)d * 12, "icl_merge_centroid: centroids"));
+    float *buf = g_buf.as<float>();
+    ICL_HIP(ctx, hipMemcpyAsync(buf, ca, (size_t)d * 4, hipMemcpyHostToDevice, ctx->stream));
+    ICL_HIP(ctx, hipMemcpyAsync(buf + d, cb, (size_t)d * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(merge_centroid_kernel, dim3((unsigned)icl_ceil_div(d, 256)), dim3(256), 0, ctx->stream, buf, (float)sa, buf + d, (float)sb,
+                       (float)(sa + sb), d, buf + 2 * (int64_t)d);
+    ICL_HIP(ctx, hipMemcpyAsync(out, buf + 2 * (int64_t)d, (size_t)d * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICL_OK;
 }
 
@@ -5962,13 +5921,11 @@ extern "C" int icl_update_distance_matrix(icl_ctx *ctx, const float *D, int64_t 
     icl_device_guard g(ctx->device);
     const int64_t lo = std::min(r1, r2), hi = std::max(r1, r2), m1 = n - 1;
     dev_guard gD, gC, gS, gO;
-    ICL_HIP(ctx, hipMalloc(&gD.p, (size_t)(n * ld) * 4));
-    ICL_HIP(ctx, hipMalloc(&gC.p, (size_t)std::max<int64_t>(m1 * d, 1) * 4));
-    ICL_HIP(ctx, hipMalloc(&gS.p, (size_t)m1 * 4));
-    ICL_HIP(ctx, hipMalloc(&gO.p, (size_t)(m1 * m1) * 4));
-    ICL_HIP(ctx, hipMemcpyAsync(gD.p, D, (size_t)(n * ld) * 4, hipMemcpyHostToDevice, ctx->stream));
+    ICL_TRY(icl_dev_upload(ctx, gD, D, (size_t)(n * ld) * 4, "icl_update_distance_matrix: D"));
+    ICL_TRY(icl_dev_alloc(ctx, gC, (size_t)std::max<int64_t>(m1 * d, 1) * 4, "icl_update_distance_matrix: C"));
     if (d) ICL_HIP(ctx, hipMemcpyAsync(gC.p, C, (size_t)(m1 * d) * 4, hipMemcpyHostToDevice, ctx->stream));
-    ICL_HIP(ctx, hipMemcpyAsync(gS.p, sizes, (size_t)m1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    ICL_TRY(icl_dev_upload(ctx, gS, sizes, (size_t)m1 * 4, "icl_update_distance_matrix: sizes"));
+    ICL_TRY(icl_dev_alloc(ctx, gO, (size_t)(m1 * m1) * 4, "icl_update_distance_matrix: Dout"));
     if (n > 2)
         hipLaunchKernelGGL(udm_compact_kernel, dim3((unsigned)icl_ceil_div((n - 2) * (n - 2), 256)), dim3(256), 0, ctx->stream, (const float *)gD.p, n, ld,
                            lo, hi, (float *)gO.p, m1);
@@ -6021,9 +5978,10 @@ extern "C" int icl_distance_bounds_check_dev(icl_ctx *ctx, const float *d_E, int
     const int K = ward_bound_K(d);
     const bool i8 = kind == 2 || (kind == 0 && icl_dist_i8_usable(n, d));
     if (i8 && !icl_dist_i8_usable(n, d)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "the integer distance GEMM covers D <= 2048");
-    if (hipMalloc(&g_ec.p, (size_t)n * K * 4) != hipSuccess || hipMalloc(&g_x.p, (size_t)w->dtri_floats * 4) != hipSuccess || hipMalloc(&g_cnt.p, 64) != hipSuccess ||
-        (i8 && hipMalloc(&g_pq.p, icl_dist_i8_pq_bytes(n, d)) != hipSuccess))
-        return icl_fail(ctx, ICL_ERR_NOMEM, "icl_distance_bounds_check_dev: scratch for %lld rows", (long long)n);
+    ICL_TRY(icl_dev_alloc(ctx, g_ec, (size_t)n * K * 4, "icl_distance_bounds_check_dev: centred copy of E (%lld rows)", (long long)n));
+    ICL_TRY(icl_dev_alloc(ctx, g_x, (size_t)w->dtri_floats * 4, "icl_distance_bounds_check_dev: exact triangle (%lld rows)", (long long)n));
+    ICL_TRY(icl_dev_alloc(ctx, g_cnt, 64, "icl_distance_bounds_check_dev: counters"));
+    if (i8) ICL_TRY(icl_dev_alloc(ctx, g_pq, icl_dist_i8_pq_bytes(n, d), "icl_distance_bounds_check_dev: scratch of the integer GEMM"));
     ICL_HIP(ctx, hipMemsetAsync(g_cnt.p, 0, 64, ctx->stream));
     ward_launch_init(w, n, 0, nullptr, 0, ctx->stream);
     ward_centred b{w->colsum, (float *)g_ec.p, w->nrm, w->zero};
@@ -6121,10 +6079,12 @@ extern "C" int icl_ward_dump_pairs_dev(icl_ctx *ctx, const int32_t *ids, int64_t
     }
     const int64_t dd = d > 0 ? d : 1;
     dev_guard g_ids, g_ent, g_mir, g_cent, g_sz;
-    if (hipMalloc(&g_ids.p, (size_t)L * 4) != hipSuccess || hipMalloc(&g_ent.p, (size_t)(L * L) * 4) != hipSuccess || hipMalloc(&g_mir.p, (size_t)(L * L) * 4) != hipSuccess ||
-        hipMalloc(&g_cent.p, (size_t)(L * dd) * 4) != hipSuccess || hipMalloc(&g_sz.p, (size_t)L * 4) != hipSuccess)
-        return icl_fail(ctx, ICL_ERR_NOMEM, "icl_ward_dump_pairs_dev: scratch for %lld ids", (long long)L);
-    ICL_HIP(ctx, hipMemcpyAsync(g_ids.p, ids, (size_t)L * 4, hipMemcpyHostToDevice, ctx->stream));
+    const char *what = "icl_ward_dump_pairs_dev: scratch for %lld ids";
+    ICL_TRY(icl_dev_upload(ctx, g_ids, ids, (size_t)L * 4, "icl_ward_dump_pairs_dev: ids"));
+    ICL_TRY(icl_dev_alloc(ctx, g_ent, (size_t)(L * L) * 4, what, (long long)L));
+    ICL_TRY(icl_dev_alloc(ctx, g_mir, (size_t)(L * L) * 4, what, (long long)L));
+    ICL_TRY(icl_dev_alloc(ctx, g_cent, (size_t)(L * dd) * 4, what, (long long)L));
+    ICL_TRY(icl_dev_alloc(ctx, g_sz, (size_t)L * 4, what, (long long)L));
     const int64_t total = L * L + L * d + L;
     hipLaunchKernelGGL(ward_dump_pairs_kernel, dim3((unsigned)std::min<int64_t>(icl_ceil_div(total, 256), 8192)), dim3(256), 0, ctx->stream, (const int32_t *)g_ids.p, L, d,
                        w->dump.lbm ? 1 : 0, w->dump.wide ? 1 : 0, std::max(w->S, w->M), (const float *)w->Dtri, (const int64_t *)w->rowoff, (const int32_t *)w->mcol,

@@ -304,49 +304,6 @@ static bool wmm_auto_takes(int64_t n, const int64_t *band_count)
     return wmm_auto_min[b] > 0 && band_count[b] >= wmm_auto_min[b];
 }
 
-struct icl_many_ws {
-    void *buf = nullptr;
-    size_t bytes = 0;
-};
-
-void icl_many_free(icl_ctx *ctx)
-{
-    if (!ctx || !ctx->many) return;
-    if (ctx->many->buf) (void)hipFree(ctx->many->buf);
-    delete ctx->many;
-    ctx->many = nullptr;
-}
-
-static int wm_ensure(icl_ctx *ctx, size_t bytes, char **out)
-{
-    if (!ctx->many) ctx->many = new icl_many_ws;
-    icl_many_ws *w = ctx->many;
-    if (w->bytes < bytes) {
-        if (w->buf) {
-            ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(w->buf);
-            w->buf = nullptr;
-            w->bytes = 0;
-        }
-        const size_t b = std::max(bytes, (size_t)1 << 20);
-        if (hipMalloc(&w->buf, b) != hipSuccess) return icl_fail(ctx, ICL_ERR_NOMEM, "icl_cluster_many: workspace of %zu bytes", b);
-        w->bytes = b;
-    }
-    *out = (char *)w->buf;
-    return ICL_OK;
-}
-
-// bump allocation inside the workspace: 256-byte aligned pieces
-struct wm_layout {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    }
-};
-
 // what the ARG check of both entry points covers: nothing is written when it fails
 static int wm_check_args(icl_ctx *ctx, const char *what, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *n,
                          const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
@@ -434,10 +391,10 @@ static const wm_kind wm_kind_mid_seeded = wm_seeded_kind(wm_kind_mid, (const voi
 // centroids + matrix of one problem in a group's data region (256-byte aligned pieces)
 static size_t wm_data_bytes(const wm_kind &k, int64_t n, int64_t d)
 {
-    wm_layout R;
+    icl_ws_layout R(256);
     R.take((size_t)(n * d * 4));
     R.take((size_t)k.mat_bytes(n));
-    return R.off;
+    return R.total;
 }
 
 // A launch group: problems that run as one init launch and one merge launch, one workgroup each in the merge.  The small route is one
@@ -607,7 +564,7 @@ static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t 
     add(A.seeded ? wm_kind_small_seeded : wm_kind_small, small, SIZE_MAX);
     add(A.seeded ? wm_kind_mid_seeded : wm_kind_mid, mid, wmm_budget());
     ctx->many_stats[3] = (int64_t)pl.groups.size() - (small.empty() ? 0 : 1);
-    wm_layout L;
+    icl_ws_layout L(256); // 256-byte aligned pieces
     pl.o_e = upload_e && pl.need_e ? L.take((size_t)e_len * 4) : 0;
     pl.o_al.assign(A.nprob, SIZE_MAX);
     pl.log_at.assign(A.nprob, 0);
@@ -635,7 +592,7 @@ static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t 
     const size_t o_shared = L.take(shared);
     for (wm_group &g : pl.groups)
         if (!g.kind->own_data) g.o_data = o_shared;
-    pl.ws_bytes = L.off;
+    pl.ws_bytes = L.total;
 }
 
 // the group's head (problem table with device addresses, init blocks, order) uploaded, then one init launch and one merge launch
@@ -647,7 +604,7 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g
     int32_t *ord = reinterpret_cast<int32_t *>(g.head.data() + o_ord);
     wm_seed *stab = g.seeded ? reinterpret_cast<wm_seed *>(g.head.data() + g.o_seed()) : nullptr;
     size_t o_eff = g.o_seed() + sizeof(wm_seed) * G; // (of the next problem's effective sizes, in the head)
-    wm_layout R; // the problems' places in the group's data region
+    icl_ws_layout R(256); // the problems' places in the group's data region
     int64_t lds = 0;
     for (size_t i = 0; i < G; ++i) {
         const int32_t p = g.probs[i];
@@ -684,8 +641,8 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g
 static int wm_enqueue(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const float *d_E, const float *h_E, int64_t e_len, std::vector<const float *> &rowsE,
                       std::vector<int32_t> &slab)
 {
-    char *ws = nullptr;
-    ICL_TRY(wm_ensure(ctx, pl.ws_bytes, &ws));
+    ICL_TRY(ctx->many.ensure(ctx, pl.ws_bytes, "icl_cluster_many: workspace", (size_t)1 << 20));
+    char *ws = ctx->many.as<char>();
     if (h_E && pl.need_e) {
         ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_e, h_E, (size_t)e_len * 4, hipMemcpyHostToDevice, ctx->stream));
         d_E = (const float *)(ws + pl.o_e);
@@ -792,7 +749,7 @@ static int wm_cout(icl_ctx *ctx, const wm_args &A, wm_plan &pl, const std::vecto
             crow[(size_t)(pl.img[p] + first)].src = src;
         }
     }
-    char *ws = (char *)ctx->many->buf;
+    char *ws = ctx->many.as<char>();
     float *out = A.cout_host ? (float *)(ws + pl.o_cout) : O.C_out;
     ICL_HIP(ctx, hipMemcpyAsync(ws + pl.o_crow, crow.data(), sizeof(wm_crow) * crow.size(), hipMemcpyHostToDevice, ctx->stream));
     if (A.cout_host) ICL_HIP(ctx, hipMemsetAsync(out, 0, (size_t)e_len * 4, ctx->stream)); // (the padding between problems)
@@ -820,7 +777,7 @@ static int wm_run(icl_ctx *ctx, wm_args A, const float *d_E, const float *h_E, i
     std::vector<int32_t> slab;
     ICL_TRY(wm_enqueue(ctx, A, pl, d_E, h_E, e_len, rowsE, slab));
     if (A.want_cout) { // a problem that took no route: its rows where the call's E lies on the device
-        const float *base = h_E && pl.need_e ? (const float *)((char *)ctx->many->buf + pl.o_e) : d_E;
+        const float *base = h_E && pl.need_e ? (const float *)(ctx->many.as<char>() + pl.o_e) : d_E;
         for (int32_t p = 0; p < A.nprob; ++p)
             if (!rowsE[p]) rowsE[p] = base + A.e_off[p];
     }

@@ -34,7 +34,7 @@ enum {
     ICL_ERR_IO = 5,          /* file missing / unreadable / malformed */
     ICL_ERR_UNSUPPORTED = 6, /* valid request this build cannot serve */
     ICL_ERR_OVERSIZE = 7,    /* a cluster above maxSize was observed (clustering.go:251; unreachable) */
-    ICL_ERR_NOMEM = 8
+    ICL_ERR_NOMEM = 8        /* out of host memory, or a device allocation (workspace, temporary, device copy of a host argument) does not fit */
 };
 
 enum { ICL_HEAD_POOLED = 2048, /* global-average-pool vector (north_star) */
