@@ -381,6 +381,25 @@ func NearestClusters(queries [][]float32, qSizes []int32, clusters []Cluster, k,
 	return iclengine.Nearest(queries, qSizes, centroids, sizes, k, maxSize, nil)
 }
 
+// ClusterFit answers, for images that are clustered already: how well does each sit in the cluster it is in, and which other clusters
+// would take it at what price (iclengine.ClusterFit -> icl_cluster_fit: WardDistance of :136-157 bit for bit on both sides, so "closer
+// to another cluster than to its own" is an exact statement).  rows[i] is a cluster of qSizes[i] items (nil: singletons) that belongs
+// to clusters[clusterOf[i]] (-1: to none); frozen[j] marks a cluster that is measured as an own cluster and never offered as an
+// alternative (nil: none frozen); maxSize > 0 leaves out the clusters the loop would refuse to merge the row with (:228).  The result
+// also names each cluster's representative row (smallest own cost) and worst row.
+func ClusterFit(rows [][]float32, qSizes []int32, clusterOf []int32, clusters []Cluster, frozen []bool, kAlt, maxSize int) (iclengine.FitResult, error) {
+	centroids := make([][]float32, len(clusters))
+	sizes := make([]int32, len(clusters))
+	for i, c := range clusters {
+		centroids[i] = c.Centroid
+		sizes[i] = int32(c.Size)
+		if frozen != nil && frozen[i] {
+			sizes[i] = -sizes[i]
+		}
+	}
+	return iclengine.ClusterFit(rows, qSizes, clusterOf, centroids, sizes, kAlt, maxSize)
+}
+
 // DuplicatePair is one pair of images whose WardDistance as singletons is at most the threshold: A comes before B in the caller's list.
 type DuplicatePair struct {
 	A, B  string

@@ -315,6 +315,103 @@ func Nearest(queries [][]float32, qSizes []int32, library [][]float32, eSizes []
 	return idx, val, nil
 }
 
+// FitResult is what ClusterFit returns: per row its cost against its own cluster and its AltIdx / AltVal alternatives (kAlt entries
+// each; a short row ends in -1, MaxFloat32), per cluster the number of rows that name it, the row of smallest own cost and the row
+// of largest (-1: nobody names the cluster).
+type FitResult struct {
+	Own                []float32
+	AltIdx             [][]int32
+	AltVal             [][]float32
+	Listed, Rep, Worst []int32
+}
+
+// flatRows copies rows of d floats into one contiguous buffer ([][]float32 cannot cross cgo), one spare entry behind them.
+func flatRows(rows [][]float32, d int) []float32 {
+	flat := make([]float32, len(rows)*d+1)
+	for i, row := range rows {
+		copy(flat[i*d:(i+1)*d], row)
+	}
+	return flat
+}
+
+// ClusterFit is icl_cluster_fit: for each clustered row (rows[i], qSizes[i] items; nil sizes: all 1) the WardDistance to its own
+// cluster clusterOf[i] of (centroids, cSizes) -- -1: none, cost MaxFloat32 -- and its kAlt (0 .. 64) nearest other clusters, the
+// reference's values bit for bit throughout.  A negative cSizes entry is a frozen cluster: measured as an own cluster, never offered;
+// maxSize > 0 leaves out the pairs whose sizes add up to more.  No distance matrix is built.
+func ClusterFit(rows [][]float32, qSizes []int32, clusterOf []int32, centroids [][]float32, cSizes []int32, kAlt, maxSize int) (FitResult, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return FitResult{}, e
+	}
+	nq, K, d := len(rows), len(centroids), 0
+	if nq > 0 {
+		d = len(rows[0])
+	} else if K > 0 {
+		d = len(centroids[0])
+	}
+	if (qSizes != nil && len(qSizes) != nq) || (cSizes != nil && len(cSizes) != K) || len(clusterOf) != nq {
+		return FitResult{}, fmt.Errorf("sizes or clusterOf do not match %d rows and %d clusters", nq, K)
+	}
+	if kAlt < 0 {
+		return FitResult{}, fmt.Errorf("kAlt must be 0 .. 64, got %d", kAlt)
+	}
+	flatQ, flatC := flatRows(rows, d), flatRows(centroids, d)
+	own := make([]float32, nq+1)
+	fi := make([]int32, nq*kAlt+1)
+	fv := make([]float32, nq*kAlt+1)
+	listed, rep, worst := make([]int32, K+1), make([]int32, K+1), make([]int32, K+1)
+	i32 := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	f32 := func(s []float32) *C.float { return (*C.float)(unsafe.Pointer(&s[0])) }
+	if rc := C.icl_cluster_fit((*C.icl_ctx)(raw), f32(flatQ), i32(qSizes), i32(clusterOf), C.int64_t(nq), f32(flatC), i32(cSizes), C.int64_t(K),
+		C.int32_t(d), C.int32_t(kAlt), C.int32_t(maxSize), f32(own), i32(fi), f32(fv), i32(listed), i32(rep), i32(worst)); rc != C.ICL_OK {
+		return FitResult{}, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	r := FitResult{Own: own[:nq], AltIdx: make([][]int32, nq), AltVal: make([][]float32, nq), Listed: listed[:K], Rep: rep[:K], Worst: worst[:K]}
+	for i := range r.AltIdx {
+		r.AltIdx[i] = fi[i*kAlt : (i+1)*kAlt : (i+1)*kAlt]
+		r.AltVal[i] = fv[i*kAlt : (i+1)*kAlt : (i+1)*kAlt]
+	}
+	return r, nil
+}
+
+// WardValuesAt is icl_ward_values_at: the exact WardDistance of each listed pair (row qi[p] of rows with qSizes, row ej[p] of library
+// with eSizes; nil sizes: all 1, a negative eSizes entry a frozen cluster's item count), the reference's values bit for bit.
+func WardValuesAt(rows [][]float32, qSizes []int32, library [][]float32, eSizes []int32, qi, ej []int32) ([]float32, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, e
+	}
+	nq, n, np, d := len(rows), len(library), len(qi), 0
+	if nq > 0 {
+		d = len(rows[0])
+	}
+	if (qSizes != nil && len(qSizes) != nq) || (eSizes != nil && len(eSizes) != n) || len(ej) != np {
+		return nil, fmt.Errorf("sizes or pair lists do not match %d rows, %d library rows and %d pairs", nq, n, np)
+	}
+	if np == 0 {
+		return nil, nil
+	}
+	flatQ, flatE := flatRows(rows, d), flatRows(library, d)
+	val := make([]float32, np)
+	i32 := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	if rc := C.icl_ward_values_at((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flatQ[0])), i32(qSizes), C.int64_t(nq),
+		(*C.float)(unsafe.Pointer(&flatE[0])), i32(eSizes), C.int64_t(n), C.int32_t(d), i32(qi), i32(ej), C.int64_t(np),
+		(*C.float)(unsafe.Pointer(&val[0]))); rc != C.ICL_OK {
+		return nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	return val, nil
+}
+
 // PairsWithin is icl_pairs_within: EVERY pair of rows whose WardDistance (sizes[i] items per row; nil: all 1) is at most threshold, the
 // reference's values bit for bit, as a CSR list over the strict lower triangle: col[rowPtr[i]:rowPtr[i+1]] are row i's partners j < i
 // in ascending j, val their values.  No cap on a row's partners and no distance matrix.  The size query and the call proper are both

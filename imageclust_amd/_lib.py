@@ -144,6 +144,12 @@ SYMBOLS = [
     ("icl_nearest_from_matrix", _int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     ("icl_set_nearest_options", _int, [_vp, _i32]),
     ("icl_last_nearest_stats", _int, [_vp, _pi64]),
+    ("icl_cluster_fit", _int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 6),
+    ("icl_cluster_fit_dev", _int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 6),
+    ("icl_cluster_fit_from_matrix", _int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32] + [_vp] * 6),
+    ("icl_last_fit_stats", _int, [_vp, _pi64]),
+    ("icl_ward_values_at", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp]),
+    ("icl_ward_values_at_dev", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     ("icl_pairs_within", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
     ("icl_pairs_within_dev", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
     ("icl_pairs_within_from_matrix", _int, [_vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
@@ -294,6 +300,36 @@ def nearest_from_matrix(D, k, q_size=None, e_size=None, max_size=0, exclude=None
     if rc != ICL_OK:
         raise ICLError(rc, "icl_nearest_from_matrix: bad argument")
     return idx, val
+
+
+def _fit_outputs(nq, K, k_alt):
+    """The output arrays of the icl_cluster_fit family, in argument order: own, alt_idx, alt_val, listed, rep, worst."""
+    kk = max(int(k_alt), 0)
+    return (np.empty(nq, np.float32), np.empty((nq, kk), np.int32), np.empty((nq, kk), np.float32), np.empty(K, np.int32), np.empty(K, np.int32),
+            np.empty(K, np.int32))
+
+
+def _fit_result(out):
+    return dict(zip(("own", "alt_idx", "alt_val", "listed", "rep", "worst"), out))
+
+
+def cluster_fit_from_matrix(D, cluster_of, k_alt, q_size=None, c_size=None, max_size=0, K=None):
+    """icl_cluster_fit_from_matrix (host only, no GPU): the rules of Context.cluster_fit applied to values the caller holds -> the same
+    dict.  D is nq x ld float32; K (default ld) columns of each row are clusters.  Raises ICLError(ICL_ERR_ARG)."""
+    D = np.asarray(D, np.float32)
+    if D.ndim != 2:
+        raise ValueError("D must be 2-D")
+    if not D.flags.c_contiguous:
+        D = np.ascontiguousarray(D)
+    nq, ld = D.shape
+    K = ld if K is None else int(K)
+    qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
+    out = _fit_outputs(nq, max(K, 0), k_alt)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    rc = load().icl_cluster_fit_from_matrix(ptr(D), nq, K, ld, ptr(qs), ptr(cof), ptr(cs), int(k_alt), int(max_size), *[ptr(a) for a in out])
+    if rc != ICL_OK:
+        raise ICLError(rc, "icl_cluster_fit_from_matrix: bad argument")
+    return _fit_result(out)
 
 
 def _pairs_two_calls(n, call, what, cap=None):
@@ -963,6 +999,97 @@ class Context:
         info = (C.c_int64 * 4)()
         check(self.h, self.L.icl_last_nearest_stats(self.h, info))
         return {"splits": info[0], "tiles": info[1], "pairs": info[2], "workspace_bytes": info[3]}
+
+    def cluster_fit(self, Q, cluster_of, C, k_alt=1, q_size=None, c_size=None, max_size=0, dev=False):
+        """icl_cluster_fit: for each row of Q (sizes q_size, None: all 1) its exact WardDistance to its own cluster cluster_of[i] of C
+        (sizes c_size; negative: frozen; -1 in cluster_of: none, cost MaxFloat32) and its k_alt nearest other clusters -- frozen ones
+        and, with max_size > 0, those it would push above max_size left out --, and per cluster the number of rows that name it, the row
+        of smallest own cost and the row of largest -> dict(own float32[nq], alt_idx int32[nq][k_alt], alt_val float32[nq][k_alt],
+        listed, rep, worst int32[K]).  dev=True runs icl_cluster_fit_dev on device copies instead of the host entry point."""
+        Qm, Cm = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(C, np.float32)
+        if Qm.ndim != 2 or Cm.ndim != 2 or Qm.shape[1] != Cm.shape[1]:
+            raise ValueError("Q and C must be 2-D with rows of one length, got %s and %s" % (Qm.shape, Cm.shape))
+        (nq, d), K = Qm.shape, Cm.shape[0]
+        qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
+        out = _fit_outputs(nq, K, k_alt)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        if not dev:
+            check(self.h, self.L.icl_cluster_fit(self.h, ptr(Qm), ptr(qs), ptr(cof), nq, ptr(Cm), ptr(cs), K, d, int(k_alt), int(max_size),
+                                                 *[ptr(a) for a in out]))
+            return _fit_result(out)
+        bufs = []
+        try:
+            for a in (Qm, Cm) + out:
+                bufs.append(self.malloc(max(a.nbytes, 16)))
+            for p, a in zip(bufs, (Qm, Cm)):
+                if a.size:
+                    self.h2d(p, a)
+            self.cluster_fit_dev(bufs[0], cof, nq, bufs[1], K, d, k_alt, *bufs[2:], q_size=qs, c_size=cs, max_size=max_size)
+            self.sync()
+            for p, a in zip(bufs[2:], out):
+                if a.size:
+                    self.d2h(a, p)
+        finally:
+            for p in bufs:
+                self.free(p)
+        return _fit_result(out)
+
+    def cluster_fit_dev(self, d_Q, cluster_of, nq, d_C, K, d, k_alt, d_own, d_alt_idx, d_alt_val, d_listed=None, d_rep=None, d_worst=None,
+                        q_size=None, c_size=None, max_size=0):
+        """icl_cluster_fit_dev: Q (nq x d), C (K x d) and the six outputs are device pointers (the per-cluster ones may be None);
+        cluster_of, q_size and c_size host arrays.  Enqueued on the context's stream: sync() before reading the outputs."""
+        qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        as_vp = lambda p: p if isinstance(p, _vp) or p is None else _vp(p)
+        check(self.h, self.L.icl_cluster_fit_dev(self.h, as_vp(d_Q), ptr(qs), ptr(cof), nq, as_vp(d_C), ptr(cs), K, d, int(k_alt), int(max_size),
+                                                 as_vp(d_own), as_vp(d_alt_idx), as_vp(d_alt_val), as_vp(d_listed), as_vp(d_rep), as_vp(d_worst)))
+
+    def last_fit_stats(self):
+        """The last cluster_fit[_dev]: column splits used, 128 x 128 tiles run, pairs evaluated, workspace bytes."""
+        info = (C.c_int64 * 4)()
+        check(self.h, self.L.icl_last_fit_stats(self.h, info))
+        return {"splits": info[0], "tiles": info[1], "pairs": info[2], "workspace_bytes": info[3]}
+
+    def ward_values_at(self, Q, E, qi, ej, q_size=None, e_size=None, dev=False):
+        """icl_ward_values_at: the exact WardDistance of each listed pair (row qi[p] of Q, row ej[p] of E; sizes None: all 1, a negative
+        e_size a frozen cluster's item count) -> float32[np].  dev=True runs icl_ward_values_at_dev on device copies."""
+        Qm, Em = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(E, np.float32)
+        if Qm.ndim != 2 or Em.ndim != 2 or Qm.shape[1] != Em.shape[1]:
+            raise ValueError("Q and E must be 2-D with rows of one length, got %s and %s" % (Qm.shape, Em.shape))
+        (nq, d), n = Qm.shape, Em.shape[0]
+        a, b = np.ascontiguousarray(np.asarray(qi).reshape(-1), np.int32), np.ascontiguousarray(np.asarray(ej).reshape(-1), np.int32)
+        if len(a) != len(b):
+            raise ValueError("%d row indices for %d column indices" % (len(a), len(b)))
+        qs, es = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size")
+        val = np.empty(len(a), np.float32)
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+        if not dev:
+            check(self.h, self.L.icl_ward_values_at(self.h, ptr(Qm), ptr(qs), nq, ptr(Em), ptr(es), n, d, ptr(a), ptr(b), len(a), ptr(val)))
+            return val
+        bufs = []
+        try:
+            for x in (Qm, Em, val):
+                bufs.append(self.malloc(max(x.nbytes, 16)))
+            for p, x in zip(bufs, (Qm, Em)):
+                if x.size:
+                    self.h2d(p, x)
+            self.ward_values_at_dev(bufs[0], nq, bufs[1], n, d, a, b, bufs[2], q_size=qs, e_size=es)
+            self.sync()
+            if val.size:
+                self.d2h(val, bufs[2])
+        finally:
+            for p in bufs:
+                self.free(p)
+        return val
+
+    def ward_values_at_dev(self, d_Q, nq, d_E, n, d, qi, ej, d_val, q_size=None, e_size=None):
+        """icl_ward_values_at_dev: Q (nq x d), E (n x d) and val (len(qi) floats) are device pointers; the pair list and the sizes host
+        arrays.  Enqueued on the context's stream."""
+        a, b = np.ascontiguousarray(np.asarray(qi).reshape(-1), np.int32), np.ascontiguousarray(np.asarray(ej).reshape(-1), np.int32)
+        qs, es = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size")
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
+        check(self.h, self.L.icl_ward_values_at_dev(self.h, as_vp(d_Q), ptr(qs), nq, as_vp(d_E), ptr(es), n, d, ptr(a), ptr(b), len(a), as_vp(d_val)))
 
     def pairs_within(self, E, threshold, size=None, cap=None):
         """icl_pairs_within: EVERY pair of rows of E whose WardDistance (sizes `size`, None: all 1) is at most threshold, bit for bit the

@@ -196,6 +196,15 @@ def NearestClusters(queries, q_sizes, centroids, sizes, k: int, maxSize: int = 0
     return ctx.nearest(queries, centroids, k, q_size=q_sizes, e_size=sizes, max_size=maxSize)
 
 
+def ClusterFit(queries, q_sizes, cluster_of, centroids, sizes, k: int = 1, maxSize: int = 0, ctx: Optional[_lib.Context] = None):
+    """For each clustered row (centroid queries[i], q_sizes[i] items; None: singletons) its cost against its own cluster cluster_of[i] of
+    (centroids, sizes) and the up to k other clusters that would take it (icl_cluster_fit): WardDistance of clustering.go:136-157 bit for
+    bit throughout.  A negative size is a frozen cluster: measured as an own cluster, never offered; maxSize > 0 leaves out the pairs the
+    loop would ban (:228) -> dict(own, alt_idx, alt_val, listed, rep, worst), as Context.cluster_fit."""
+    ctx = ctx or default_context()
+    return ctx.cluster_fit(queries, cluster_of, centroids, k, q_size=q_sizes, c_size=sizes, max_size=maxSize)
+
+
 def NearDuplicates(embeddings, ids, k: int, threshold: float, ctx: Optional[_lib.Context] = None) -> List[Tuple[str, str, float]]:
     """Pairs of images whose WardDistance as singletons is at most threshold, from a self-join of the embeddings (icl_nearest with
     exclude[i] = i, the k nearest of every image) -> [(id_a, id_b, value), ...], a before b in `ids`, each pair once, ordered by position.
@@ -278,21 +287,24 @@ class Clustering:
         state.as_map()
 
     `engine` replaces the GPU call in tests: engine(C, seed_size, minSize, maxSize, k_target) -> (cluster_id, seed_rank, n_clusters,
-    status, merges, C_out); `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val)."""
+    status, merges, C_out); `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
+    `fit_engine` for fit(), representatives() and misfits(): fit_engine(Q, cluster_of, C, k_alt, q_size, c_size, max_size) -> the dict of
+    Context.cluster_fit."""
 
-    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None):
+    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None, fit_engine=None):
         self.minSize, self.maxSize = int(minSize), int(maxSize)
-        self.ctx, self.engine, self.nearest_engine = ctx, engine, nearest_engine
+        self.ctx, self.engine, self.nearest_engine, self.fit_engine = ctx, engine, nearest_engine, fit_engine
         self.clusters: List[HeldCluster] = []
         self.embeddings: Dict[str, np.ndarray] = {}
         self.ok = True
         self.last_merges = np.zeros((0, 2), np.int32)
 
     @classmethod
-    def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None) -> "Clustering":
+    def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None,
+              fit_engine=None) -> "Clustering":
         """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
         False (and every image is still a singleton) when the constraints cannot be met."""
-        state = cls(minSize, maxSize, ctx, engine, nearest_engine)
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine)
         state.add(embeddings, ids)
         state.recluster()
         return state
@@ -382,6 +394,44 @@ class Clustering:
         else:
             idx, val = (self.ctx or default_context()).nearest(Q, E, k, q_size=qs, e_size=es, max_size=self.maxSize)
         return [[(cand[int(j)].Members[0], float(v)) for j, v in zip(ri, rv) if j >= 0] for ri, rv in zip(idx, val)]
+
+    def _fit_call(self, k: int):
+        """icl_cluster_fit over every held image as a singleton and every held cluster -> (image ids in row order, the call's dict)."""
+        ids = [key for c in self.clusters for key in c.Members]
+        if not ids:
+            return ids, None
+        Q = np.stack([self.embeddings[key] for key in ids]).astype(np.float32)
+        cof = np.array([ci for ci, c in enumerate(self.clusters) for _ in c.Members], np.int32)
+        C, cs = self.seeds()
+        qs = np.ones(len(ids), np.int32)
+        if self.fit_engine is not None:
+            return ids, self.fit_engine(Q, cof, C, k, qs, cs, self.maxSize)
+        return ids, (self.ctx or default_context()).cluster_fit(Q, cof, C, k, q_size=qs, c_size=cs, max_size=self.maxSize)
+
+    def fit(self, k: int = 1) -> Dict[str, Tuple[float, List[Tuple[str, float]]]]:
+        """How well each held image sits where it is: id -> (WardDistance of the image, as a singleton, to its own cluster, [(first
+        member's id of another cluster, WardDistance), ...] nearest first, at most k).  Both are the loop's own cost in the same
+        arithmetic.  Frozen clusters are left out of the alternatives, and so are clusters a further item would push above maxSize; an
+        image's own cluster is measured whether frozen or full.  The state is not changed."""
+        ids, r = self._fit_call(k)
+        if r is None:
+            return {}
+        return {key: (float(r["own"][i]), [(self.clusters[int(j)].Members[0], float(v)) for j, v in zip(r["alt_idx"][i], r["alt_val"][i]) if j >= 0])
+                for i, key in enumerate(ids)}
+
+    def representatives(self) -> Dict[str, str]:
+        """The cover image of each held cluster: first member's id -> the id of the member of smallest cost to the cluster's centroid
+        (ties: the earliest member)."""
+        ids, r = self._fit_call(0)
+        if r is None:
+            return {}
+        return {c.Members[0]: ids[int(r["rep"][ci])] for ci, c in enumerate(self.clusters)}
+
+    def misfits(self) -> List[str]:
+        """The images another cluster would take at a lower cost than their own cluster's: ids whose first alternative costs less than
+        their own cost (an exact comparison: one arithmetic), largest gain first, ties in member order."""
+        found = [(own - alts[0][1], key) for key, (own, alts) in self.fit(1).items() if alts and alts[0][1] < own]
+        return [key for _, key in sorted(found, key=lambda t: -t[0])]
 
     def as_map(self) -> Dict[int, List[str]]:
         """The reference's map[int][]string (clustering.go:265-280): the kept clusters."""

@@ -89,6 +89,7 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     icl_jenc_free(ctx);
     ctx->nearest.release();
     ctx->pairs.release();
+    ctx->fit.release();
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

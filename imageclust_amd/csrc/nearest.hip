@@ -179,6 +179,17 @@ static int nr_splits(const icl_ctx *ctx, int64_t nbands, int64_t ntiles)
     return (int)std::max<int64_t>(1, std::min<int64_t>(slots / nbands, cap));
 }
 
+// For the other unit that walks bands this way (fit.hip): the same split decision, and the merge kernel as it is.
+int nearest_splits(const icl_ctx *ctx, int64_t nbands, int64_t ntiles) { return nr_splits(ctx, nbands, ntiles); }
+
+int nearest_merge_launch(icl_ctx *ctx, const float *d_pv, const int32_t *d_pj, int64_t nq, int k, int splits, float *d_val, int32_t *d_idx)
+{
+    hipLaunchKernelGGL(nearest_merge_kernel, dim3((unsigned)icl_ceil_div(nq, NR_MERGE_ROWS)), dim3(NR_MERGE_ROWS),
+                       (size_t)2 * NR_MERGE_ROWS * (k | 1) * 4, ctx->stream, d_pv, d_pj, nq, k, splits, d_val, d_idx);
+    ICL_HIP(ctx, hipGetLastError());
+    return ICL_OK;
+}
+
 // ctx->mu held, the device selected, the arguments checked, nq > 0.
 static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_E, const int32_t *e_size,
                               int64_t n, int32_t d, int32_t k, int32_t max_size, const int64_t *exclude, int32_t *d_idx, float *d_val)
@@ -222,12 +233,7 @@ static int nearest_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q_s
     icl_lds_optin(ctx, (const void *)nearest_tile_select_kernel, (int)nr_lds_bytes(NS_KMAX));
     hipLaunchKernelGGL(nearest_tile_select_kernel, dim3((unsigned)(nbands * splits)), dim3(256), nr_lds_bytes(k), ctx->stream, a);
     ICL_HIP(ctx, hipGetLastError());
-    if (splits > 1) {
-        hipLaunchKernelGGL(nearest_merge_kernel, dim3((unsigned)icl_ceil_div(nq, NR_MERGE_ROWS)), dim3(NR_MERGE_ROWS),
-                           (size_t)2 * NR_MERGE_ROWS * (k | 1) * 4, ctx->stream, (const float *)a.val, (const int32_t *)a.idx, nq, (int)k, splits,
-                           d_val, d_idx);
-        ICL_HIP(ctx, hipGetLastError());
-    }
+    if (splits > 1) ICL_TRY(nearest_merge_launch(ctx, a.val, a.idx, nq, k, splits, d_val, d_idx));
     ctx->nearest_stats[0] = splits;
     ctx->nearest_stats[1] = nbands * ntiles;
     ctx->nearest_stats[2] = nq * n;

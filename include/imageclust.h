@@ -447,6 +447,55 @@ int icl_nearest_from_matrix(const float *D, int64_t nq, int64_t n, int64_t ld, c
 int icl_set_nearest_options(icl_ctx *ctx, int32_t column_splits);
 /* The last icl_nearest[_dev] of the context: info = splits used, tiles run, pairs evaluated, workspace bytes (all 0 after a call with nq == 0). */
 int icl_last_nearest_stats(icl_ctx *ctx, int64_t info[4]);
+/* ---- cluster fit: each clustered row's exact cost against its own cluster and its nearest alternatives, no distance matrix (DESIGN.md "Cluster fit") ----
+ * Q holds nq rows of d floats (images, or seeds at seed granularity) with item counts q_size[nq] (NULL: all 1); C holds K centroid rows with
+ * item counts c_size[K] in the seeded calls' sign convention: s > 0 a cluster of s items, s < 0 a FROZEN cluster of -s items, NULL: all 1.
+ * cluster_of[nq] names each row's own cluster in C, -1: the row belongs to none.
+ * VALUE of pair (i, j): WardDistance (clustering.go:136-157) of q_size[i] items at Q[i] and |c_size[j]| items at C[j], bit for bit, icl_nearest's
+ * arithmetic.  The own cost and the alternatives are the same quantity: "closer to another cluster than to its own" is an exact statement.
+ * PER ROW: own[i] is the value of pair (i, cluster_of[i]) -- a frozen own cluster included, never subject to the max_size ban --, MaxFloat32 for
+ * cluster_of[i] == -1.  Row i of alt_idx / alt_val (nq x k_alt each) is icl_nearest's result over C with three kinds of pair left out: column
+ * cluster_of[i]; every frozen column; and, when max_size > 0, pairs with q_size[i] + c_size[j] > max_size.  Order, NaN placement, ties by j and
+ * the tails of short rows (-1, MaxFloat32) are icl_nearest's.  k_alt is 0 .. 64; with k_alt == 0 both pointers may be NULL.
+ * PER CLUSTER (each pointer may be NULL): listed[j] = the number of rows that name cluster j; rep[j] = the row of smallest own cost among them
+ * (values compare with `<`, numbers come before NaN, ties go to the lowest row); worst[j] = the row of largest own cost (NaN counts above every
+ * number, ties go to the lowest row); both -1 when no row names the cluster.
+ * The results do not depend on tile order, split count or launch geometry; icl_set_nearest_options' column_splits applies as it does to icl_nearest.
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context; Q, cluster_of, own when nq > 0; alt_idx, alt_val when
+ * nq > 0 and k_alt > 0; C when K > 0), k_alt outside 0..64, d < 1, negative nq or K, nq or K >= 2^31, a q_size <= 0, a c_size of 0, or a cluster_of
+ * entry outside [-1, K) (so K == 0 takes rows of -1 only); nq == 0 is ICL_OK and leaves listed 0 and rep / worst -1; ICL_ERR_UNSUPPORTED on a
+ * context that is a replica of a group; ICL_ERR_NOMEM when the workspace does not fit.
+ * icl_cluster_fit takes host memory throughout: it uploads, runs the _dev body and downloads.  icl_cluster_fit_dev takes Q, C, own, alt_idx,
+ * alt_val, listed, rep and worst on the context's device (consumed and written on the context's stream; Q and C 16-byte aligned take the wide
+ * loads when d % 4 == 0); q_size, cluster_of and c_size stay in host memory and may be reused at return.  With k_alt == 0 no tile is run: the
+ * own costs come from icl_ward_values_at's kernel on the pairs (i, cluster_of[i]).  The workspace is the device copies of the three host
+ * arrays, 8 * nq * k_alt * splits bytes of partial lists when the columns are split, and 16 * K bytes of keys when rep or worst is asked for. */
+int icl_cluster_fit(icl_ctx *ctx, const float *Q, const int32_t *q_size, const int32_t *cluster_of, int64_t nq, const float *C,
+                    const int32_t *c_size, int64_t K, int32_t d, int32_t k_alt, int32_t max_size, float *own, int32_t *alt_idx, float *alt_val,
+                    int32_t *listed, int32_t *rep, int32_t *worst);
+int icl_cluster_fit_dev(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, const int32_t *cluster_of, int64_t nq, const float *d_C,
+                        const int32_t *c_size, int64_t K, int32_t d, int32_t k_alt, int32_t max_size, float *d_own, int32_t *d_alt_idx,
+                        float *d_alt_val, int32_t *d_listed, int32_t *d_rep, int32_t *d_worst);
+/* The same rules applied to values the caller already holds (host only: no context, no GPU): D[i * ld + j] is pair (i, j)'s value, used as
+ * given -- own[i] = D[i * ld + cluster_of[i]] --; the sizes serve the frozen and max_size rules alone.  The leave-out rule and the key order
+ * are the code the device runs (fit_select.h).  ICL_ERR_ARG, with nothing written, as above (D is needed when nq > 0 and K > 0) and for ld < K. */
+int icl_cluster_fit_from_matrix(const float *D, int64_t nq, int64_t K, int64_t ld, const int32_t *q_size, const int32_t *cluster_of,
+                                const int32_t *c_size, int32_t k_alt, int32_t max_size, float *own, int32_t *alt_idx, float *alt_val,
+                                int32_t *listed, int32_t *rep, int32_t *worst);
+/* The last icl_cluster_fit[_dev] of the context: info = column splits used, tiles run (both 0 with k_alt == 0), pairs evaluated, workspace
+ * bytes (all 0 after a call with nq == 0 and K == 0). */
+int icl_last_fit_stats(icl_ctx *ctx, int64_t info[4]);
+/* Exact values of listed pairs: val[p] = WardDistance of q_size[qi[p]] items at row qi[p] of Q (nq x d) and |e_size[ej[p]]| items at row ej[p]
+ * of E (n x d), bit for bit, for p < np (size arrays NULL: all 1; a negative e_size is a frozen cluster's item count).  Pairs may repeat.  One
+ * lane per pair adds the pair's d rounded products in k order; no tile is run, so np pairs cost np * d operations wherever they lie.
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context; Q, E, qi, ej, val when np > 0), d < 1, a negative
+ * count, nq or n >= 2^31, a q_size <= 0, an e_size of 0 or a pair outside [0, nq) x [0, n); np == 0 is ICL_OK; ICL_ERR_UNSUPPORTED on a replica
+ * of a group; ICL_ERR_NOMEM when the device copies do not fit.  icl_ward_values_at_dev takes Q, E and val on the context's device (written on
+ * the context's stream); the sizes and the pair list stay in host memory and may be reused at return. */
+int icl_ward_values_at(icl_ctx *ctx, const float *Q, const int32_t *q_size, int64_t nq, const float *E, const int32_t *e_size, int64_t n, int32_t d,
+                       const int32_t *qi, const int32_t *ej, int64_t np, float *val);
+int icl_ward_values_at_dev(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_E, const int32_t *e_size, int64_t n,
+                           int32_t d, const int32_t *qi, const int32_t *ej, int64_t np, float *d_val);
 /* ---- duplicate pairs: every pair of rows whose WardDistance is at most a threshold, exact and complete, no distance matrix (DESIGN.md "Duplicate pairs") ----
  * E holds n rows of d floats; size[n] are the rows' item counts (NULL: all 1).
  * VALUE of pair (i, j), j < i < n: WardDistance (clustering.go:136-157) of a cluster of size[i] items at E[i] and one of size[j] items at E[j],
