@@ -99,13 +99,32 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     const i32x4_t x2srd = DUAL ? bn56_srd(p.X2, (unsigned)((size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2)) : xsrd;
 
     // ---- LDS-DMA roles: piece j of a slot covers slot rows (j * 8 + wid) * 8 + (lane >> 3), physical 16-byte chunk lane & 7
-    unsigned vx[2][PX], vw[2][PW], vx2[DUAL ? 2 : 1][PX], vmask[TAPS ? 2 : 1][PX];
+    // vmask[j] (TAPS): the 9-bit tap validity masks of piece j's two rows, half h in bits 16 h .. 16 h + 8 (one register for both halves)
+    unsigned vx[2][PX], vw[2][PW], vx2[DUAL ? 2 : 1][PX], vmask[PX];
+    // The weight offsets need no division: they are formed first, and WA(0) is requested before any pixel arithmetic.
 #pragma unroll
-    for (int j = 0; j < PX; ++j) {
+    for (int j = 0; j < PW; ++j) {
         const int sr = (j * 8 + wid) * 8 + (lane >> 3);
         const unsigned ls16 = (unsigned)(((lane & 7) ^ ((sr >> 1) & 7)) << 4); // source-side swizzle: the logical chunk this physical position holds
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
+            const int wrow = n0 + (sr >> 5) * 64 + h * 32 + (sr & 31); // W slot row sr = wc * 32 + r: channel wc * 64 + h * 32 + r
+            vw[h][j] = (unsigned)wrow * (unsigned)p.K * 2u + ls16;
+        }
+    }
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem) + wid * 1024);
+    // X half h: per-lane row offsets and tap masks.  The taps (kh, kw) a row may read form a rectangle: kw is valid iff 0 <= ix0 + kw < W, i.e. for
+    // kw in [clamp(-ix0), clamp(W - ix0)) (clamped to [0, KW]), and likewise kh; so the mask -- bit kh * KW + kw set iff ok, iy0 + kh in [0, H) and
+    // ix0 + kw in [0, W) -- is the column bits repeated once per kernel row (a multiplication by taprep: the copies do not overlap), cut to the
+    // valid kernel rows.  No loop over the taps, any KH * KW <= 9.
+    unsigned taprep = 0;
+    if (TAPS)
+        for (int kh = 0; kh < p.KH; ++kh) taprep |= 1u << (kh * p.KW);
+    auto xrows = [&](int h) {
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const int sr = (j * 8 + wid) * 8 + (lane >> 3);
+            const unsigned ls16 = (unsigned)(((lane & 7) ^ ((sr >> 1) & 7)) << 4);
             const int m = m0 + (sr >> 6) * 128 + h * 64 + (sr & 63); // X slot row sr = wr * 64 + r: tile row wr * 128 + h * 64 + r
             const bool ok = (int64_t)m < p.M;
             const unsigned mm = ok ? (unsigned)m : 0u;
@@ -116,43 +135,19 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
             const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
             const unsigned off = (unsigned)((((b * p.H + iy0) * p.W + ix0) * p.Cin) * 2) + ls16; // (may wrap for padded taps: only used where the tap is valid)
             if (TAPS) {
-                unsigned mk = 0;
-                for (int kh = 0; kh < p.KH; ++kh)
-                    for (int kw = 0; kw < p.KW; ++kw)
-                        if (ok && (unsigned)(iy0 + kh) < (unsigned)p.H && (unsigned)(ix0 + kw) < (unsigned)p.W) mk |= 1u << (kh * p.KW + kw);
-                vmask[h][j] = mk;
+                const int c0 = std::min(std::max(-ix0, 0), p.KW), c1 = std::min(std::max(p.W - ix0, 0), p.KW); // c0 <= c1 (W > 0)
+                const int r0 = std::min(std::max(-iy0, 0), p.KH), r1 = std::min(std::max(p.H - iy0, 0), p.KH);
+                const unsigned cols = ((1u << (c1 - c0)) - 1u) << c0;
+                const unsigned rows = ((1u << ((r1 - r0) * p.KW)) - 1u) << (r0 * p.KW);
+                const unsigned mk = ok ? (cols * taprep) & rows : 0u;
+                vmask[j] = h ? vmask[j] | (mk << 16) : mk;
                 vx[h][j] = off;
             } else {
                 vx[h][j] = ok ? off : BN56_OOB;
             }
-            if (DUAL) vx2[h][j] = ok ? (unsigned)((((b * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * p.Cin2) * 2) + ls16 : BN56_OOB;
+            if (DUAL) vx2[DUAL ? h : 0][j] = ok ? (unsigned)((((b * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * p.Cin2) * 2) + ls16 : BN56_OOB;
         }
-    }
-#pragma unroll
-    for (int j = 0; j < PW; ++j) {
-        const int sr = (j * 8 + wid) * 8 + (lane >> 3);
-        const unsigned ls16 = (unsigned)(((lane & 7) ^ ((sr >> 1) & 7)) << 4);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int wrow = n0 + (sr >> 5) * 64 + h * 32 + (sr & 31); // W slot row sr = wc * 32 + r: channel wc * 64 + h * 32 + r
-            vw[h][j] = (unsigned)wrow * (unsigned)p.K * 2u + ls16;
-        }
-    }
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem) + wid * 1024);
-    // ---- fragment roles: lane (q = lane >> 4, l15 = lane & 15) reads row l15 of a 16-row fragment, logical chunk 4 s + q
-    const int l15 = lane & 15, q = lane >> 4, fsw = (l15 >> 1) & 7;
-    const unsigned char *xrd[2], *wrd[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int ph = ((4 * s + q) ^ fsw) << 4;
-        xrd[s] = smem + (wr * 64 + l15) * 128 + ph;
-        wrd[s] = smem + (wc * 32 + l15) * 128 + ph;
-    }
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    };
 
     const int nt = SPLIT ? p.K / 128 : p.K / 64;  // K-tiles of this workgroup (SPLIT: half of them; conv_p8_split_eligible: K % 256 == 0)
     const int kt0 = (SPLIT && role == 0) ? nt : 0; // its first K-tile
@@ -176,9 +171,10 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
         if (DUAL && xs_t >= nt1) {
             p8_dma<PX>(x2srd, vx2[DUAL ? h : 0], (unsigned)(xs_t - nt1) * 128u, dst);
         } else if (TAPS) {
+            const unsigned bit = h ? xs_bit << 16 : xs_bit;
             unsigned v[PX];
 #pragma unroll
-            for (int j = 0; j < PX; ++j) v[j] = (vmask[TAPS ? h : 0][j] & xs_bit) ? vx[h][j] + xs_off : BN56_OOB;
+            for (int j = 0; j < PX; ++j) v[j] = (vmask[j] & bit) ? vx[h][j] + xs_off : BN56_OOB;
             p8_dma<PX>(xsrd, v, 0u, dst);
         } else {
             p8_dma<PX>(xsrd, vx[h], (unsigned)xs_t * 128u, dst);
@@ -199,6 +195,51 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
             }
         }
     };
+    // prologue: all of K-tile 0, three half-tiles of K-tile 1 (conv_p8_eligible: nt even, >= 2).  The first weight half goes out before any pixel
+    // arithmetic, each X half as soon as its offsets exist, the second weight half between them (both weight halves in front of the X halves
+    // measured slower: every workgroup of a launch then asks for the same few weight rows at the same moment -- DESIGN.md section 4); the
+    // stagings of K-tile 1 stay last and in the loop's order, so that the counted wait below means what it means in the loop: everything but
+    // WA(1), XA(1), WB(1) has landed.
+    stage_w(0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    xrows(0);
+    stage_x(0, 0);
+    stage_w(1, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    xrows(1);
+    stage_x(1, 0);
+    stage_w(0, 1, 1);
+    stage_x(0, 1);
+    stage_w(1, 1, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- fragment roles: lane (q = lane >> 4, l15 = lane & 15) reads row l15 of a 16-row fragment, logical chunk 4 s + q
+    const int l15 = lane & 15, q = lane >> 4, fsw = (l15 >> 1) & 7;
+    const unsigned char *xrd[2], *wrd[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int ph = ((4 * s + q) ^ fsw) << 4;
+        xrd[s] = smem + (wr * 64 + l15) * 128 + ph;
+        wrd[s] = smem + (wc * 32 + l15) * 128 + ph;
+    }
+    f32x4 acc[8][4]; // (zeroed behind the requests, not in front of them)
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the epilogue's folded BN scale / shift of this lane's 2 x 8 channels: requested at the start of the LAST K-tile (ktile, MODE 2), where the
+    // staging offsets are dead; SPLIT: behind the partner sums, whose loads need the registers
+    float4 sc4[2][2], sh4[2][2];
+    auto load_affine = [&]() {
+        const int cb = n0 + wc * 64 + (q & 1) * 16 + (q >> 1) * 8; // (cbl of the epilogue)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            sc4[i][0] = *reinterpret_cast<const float4 *>(p.scale + cb + i * 32);
+            sc4[i][1] = *reinterpret_cast<const float4 *>(p.scale + cb + i * 32 + 4);
+            sh4[i][0] = *reinterpret_cast<const float4 *>(p.shift + cb + i * 32);
+            sh4[i][1] = *reinterpret_cast<const float4 *>(p.shift + cb + i * 32 + 4);
+        }
+    };
+
     uint4 xf[4][2], w0[2][2], w1[2][2];
     auto mma = [&](int hx, int hw, uint4 (&wf)[2][2]) {
         __builtin_amdgcn_s_barrier();
@@ -226,6 +267,10 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     auto ktile = [&](auto bufc, auto modec, int t) {
         constexpr int BUF = decltype(bufc)::value, MODE = decltype(modec)::value;
         const size_t bo = (size_t)BUF * G::BUF;
+        // MODE 2: no LDS-DMA is in flight any more (MODE 1 ended on vmcnt(0)) and none follows, so from here on the VM counter is the compiler's
+        // and the 8 scale / shift loads land under the last 64 MFMAs.  Not earlier: in the loop vmcnt(6) must count LDS-DMA pieces only (loads of
+        // another kind may retire out of order with respect to them: distance_i8.hip, "hi complete").
+        if constexpr (MODE == 2 && !SPLIT && !X3) load_affine();
         // phase 1: W0 (4 reads, retired before the barrier: WA is restaged next phase), X0 (8 reads); stage XB(t + 1)
 #pragma unroll
         for (int n = 0; n < 2; ++n)
@@ -263,14 +308,6 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
         }
         mma(1, 0, w0);
     };
-    // prologue: all of K-tile 0, three half-tiles of K-tile 1 (conv_p8_eligible: nt even, >= 2)
-    stage_w(0, 0, 0);
-    stage_x(0, 0);
-    stage_w(1, 0, 0);
-    stage_x(1, 0);
-    stage_w(0, 1, 1);
-    stage_x(0, 1);
-    stage_w(1, 1, 1);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier(); // the stagger
@@ -326,22 +363,25 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     // No LDS, no barrier: the staging buffers are not touched again.
     //   before the swap lane (q, l15) holds channels 16 n + 4 q + j of pixel l15 (j = 0..3) for tiles n = A, B;
     //   after: even q: channels 4 q .. 4 q + 7 of tile A;  odd q: channels 4 (q - 1) .. 4 (q - 1) + 7 of tile B
+    if constexpr (SPLIT || X3) load_affine(); // (X3: the 24-MFMA phases leave no room for 32 more registers in the last K-tile)
     typedef uint16_t elem;
+    const int cbl = (q & 1) * 16 + (q >> 1) * 8; // this lane's first channel inside a pair of accumulator tiles (32 channels)
     elem *Yg = (elem *)p.Y;
     const elem *Rg = (const elem *)p.R;
-    const int cbl = (q & 1) * 16 + (q >> 1) * 8; // this lane's first channel inside a pair of accumulator tiles (32 channels)
     // row stride and (X3) the split layout's position of channel c: hi at c + (c & ~31), lo 32 elements further
     const int64_t yld = X3 ? 2 * (int64_t)p.Cout : (int64_t)p.Cout;
     auto ycol = [&](int c) { return X3 ? c + (c & ~31) : c; };
-    float sc[2][8], sh[2][8];
+    float sc[2][8], sh[2][8]; // (requested at the start of the last K-tile)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int c = n0 + wc * 64 + i * 32 + cbl;
-        const float4 a0 = *reinterpret_cast<const float4 *>(p.scale + c), a1 = *reinterpret_cast<const float4 *>(p.scale + c + 4);
-        const float4 b0 = *reinterpret_cast<const float4 *>(p.shift + c), b1 = *reinterpret_cast<const float4 *>(p.shift + c + 4);
+        const float4 a0 = sc4[i][0], a1 = sc4[i][1], b0 = sh4[i][0], b1 = sh4[i][1];
         sc[i][0] = a0.x; sc[i][1] = a0.y; sc[i][2] = a0.z; sc[i][3] = a0.w; sc[i][4] = a1.x; sc[i][5] = a1.y; sc[i][6] = a1.z; sc[i][7] = a1.w;
         sh[i][0] = b0.x; sh[i][1] = b0.y; sh[i][2] = b0.z; sh[i][3] = b0.w; sh[i][4] = b1.x; sh[i][5] = b1.y; sh[i][6] = b1.z; sh[i][7] = b1.w;
     }
+    // FULL: every row of the tile lies inside M (decided once, wave-uniform) -- no bounds test around any load or store; a ragged tile tests each row
+    auto epilogue = [&](auto fullc) {
+    constexpr bool FULL = decltype(fullc)::value;
+    auto inside = [&](int64_t mrow) { return FULL || mrow < p.M; };
 #pragma unroll
     for (int hx = 0; hx < 2; ++hx) {
         uint4 rv[4][2], rl[2];
@@ -351,7 +391,7 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
                 const int64_t mrow = (int64_t)m0 + wr * 128 + hx * 64 + m * 16 + l15;
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
-                    rv[m][i] = mrow < p.M ? *reinterpret_cast<const uint4 *>(Rg + mrow * p.Cout + n0 + wc * 64 + i * 32 + cbl) : make_uint4(0, 0, 0, 0);
+                    rv[m][i] = inside(mrow) ? *reinterpret_cast<const uint4 *>(Rg + mrow * p.Cout + n0 + wc * 64 + i * 32 + cbl) : make_uint4(0, 0, 0, 0);
             }
         }
 #pragma unroll
@@ -361,8 +401,8 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const elem *r = Rg + mrow * yld + ycol(n0 + wc * 64 + i * 32 + cbl);
-                    rv[m][i] = mrow < p.M ? *reinterpret_cast<const uint4 *>(r) : make_uint4(0, 0, 0, 0);
-                    rl[i] = mrow < p.M ? *reinterpret_cast<const uint4 *>(r + 32) : make_uint4(0, 0, 0, 0);
+                    rv[m][i] = inside(mrow) ? *reinterpret_cast<const uint4 *>(r) : make_uint4(0, 0, 0, 0);
+                    rl[i] = inside(mrow) ? *reinterpret_cast<const uint4 *>(r + 32) : make_uint4(0, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -403,13 +443,17 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
                     for (int e = 0; e < 8; ++e) oe[e] = BF16::from_f(v[e]);
                 }
                 elem *yo = Yg + mrow * yld + ycol(n0 + wc * 64 + i * 32 + cbl);
-                if (mrow < p.M) {
+                if (inside(mrow)) {
                     *reinterpret_cast<uint4 *>(yo) = ov;
                     if (X3) *reinterpret_cast<uint4 *>(yo + 32) = ol;
                 }
             }
         }
     }
+    };
+    // (X3 and SPLIT keep the one general path: their epilogues are at the register budget, and a second copy costs them spills)
+    if (!X3 && !SPLIT && (int64_t)m0 + G::BM <= p.M) epilogue(std::true_type());
+    else epilogue(std::false_type());
 }
 
 // Which layers take the deep-pipelined kernel (bf16 only): Cout a multiple of 256 (256 x 256 tile) or of 128 (512 x 128 tile), whole

@@ -23,6 +23,10 @@
 //   and the rest of the bound is distance_mfma.hip's: T = (n_a + n_b) / 2 - c in double,
 //       | T - S/2 | <= E_ab := m_ab + 16 u (1 + 64 u)(n_a + n_b)      (computed norms, centring, the conversions; u = 2^-24)
 //       stored  L = max(0, (T - E_ab)(1 - g')) rounded toward zero, sign bit set;   scan side  U(L) = (L (1 + 3 g') + 2 E_ab)(1 + 2 g') >= R
+//   The epilogue evaluates E_ab in separable form (dist_i8_bound.h): s_a (2^-21 L1_b) + s_b (2^-21 L1_a) + s_a s_b C_D + kappa n_a + kappa n_b with
+//   C_D = D 2^-42 + D (2^20 + 2^12) 2^-40 and kappa = 16 u (1 + 64 u) -- the same real number term by term; the scalings by s and 2^-21 and C_D
+//   itself are exact in double, kappa n and the sums round at most six times, all terms are non-negative, so the computed value is within
+//   7 * 2^-53 relative of E_ab and the factor (1 + 1e-12) it is multiplied with keeps it an upper bound, as it did for the nested form.
 //   (ward.hip wupper recomputes E_ab from the rows' s, L1 and n).  For unit-variance Gaussian rows at D = 2048, E_ab ~ 0.03 against 0.25 for
 //   the fmaf-chain bound (whose worst case grows with D u): the integer bound is the TIGHTER one as well as the faster one.
 //
@@ -31,6 +35,7 @@
 // not care in which order an instruction walks K as long as both operands are staged alike.  Lower-triangle tiles only.
 #include "icl_common.h"
 #include "distance.h"
+#include "dist_i8_bound.h"
 #include "mfma_tile.h"
 
 #include <algorithm>
@@ -147,14 +152,6 @@ struct di8_args {
     unsigned int *rowub; // [n] (may be null) per row i: the smallest UPPER bound U(L) over its pairs j < i, as float bits (atomicMin): the threshold the
                          // initial row minima start from -- their first pass over the row is this epilogue (one pass instead of two)
 };
-
-// E_ab of the header, in double (device side of the proof; ward.hip wupper has the float form for the scans).  sa / sb: 2^e or 0.
-__device__ __forceinline__ double di8_eab(double sa, double sb, double l1a, double l1b, double na, double nb, int d)
-{
-    const double t21 = 4.76837158203125e-07; // 2^-21
-    const double m = t21 * (sa * (l1b + (double)d * sb * t21) + sb * l1a) + sa * sb * (double)d * (1048576.0 + 4096.0) * 9.094947017729282e-13; // 2^-40
-    return (m + 16.0 * 5.9604644775390625e-08 * (1.0 + 64.0 * 5.9604644775390625e-08) * (na + nb)) * (1.0 + 1e-12);
-}
 
 __global__ __launch_bounds__(512) void dist_bound_i8_kernel(const di8_args p)
 {
@@ -309,70 +306,97 @@ __global__ __launch_bounds__(512) void dist_bound_i8_kernel(const di8_args p)
     ktile(std::integral_constant<int, 0>(), std::integral_constant<int, 1>(), t);
     ktile(std::integral_constant<int, 1>(), std::integral_constant<int, 2>(), t + 1);
     if (wr == 0) __builtin_amdgcn_s_barrier();
-    // ---- epilogue: I = 128 hi + lo (exact in double), T, E_ab, the flagged bound
-    float um[8]; // smallest upper bound of this lane's entries in row (mt, l15)
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) um[mt] = ICL_MAXF;
-#pragma unroll
-    for (int ntl = 0; ntl < 4; ++ntl) {
-        const int64_t j = n0 + wc * 64 + (ntl >> 1) * 32 + (ntl & 1) * 16 + 4 * q;
-        double sj[4], l1j[4], nj[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = j + e < p.n;
-            const int ej = in ? p.ex[j + e] : INT32_MIN;
-            sj[e] = ej == INT32_MIN ? 0.0 : ldexp(1.0, ej);
-            l1j[e] = in ? (double)p.l1[j + e] : 0.0;
-            nj[e] = in ? (double)p.nrm[j + e] : 0.0;
-        }
+    // ---- epilogue: I = 128 hi + lo (exact in double), T, E_ab, the flagged bound (dist_i8_bound.h).
+    // INTERIOR: the tile lies strictly below the diagonal and inside n (all but the diagonal tiles and the last, ragged tile row: 782 of 76 636
+    // tiles at n = 100 000) -- every row i < n, every column j + e < i: no predicate on any element, float4 stores only.  The other tiles keep
+    // the predicates.  Either way a lane forms the pointers of its 8 rows once, the column constants once per column group, and requests the
+    // parked hi words and the row constants of four row groups together (they do not depend on one another): eight round trips per tile and
+    // one for the row offsets, where each of the 32 (row group, column group) pairs used to wait for two in turn.
+    // The asm statements are fences for the compiler only (no instruction): without them it schedules the whole tile's arithmetic as one block,
+    // converts a column group's integers up front, defers the upper bounds to the end, and spills hundreds of registers.
+    const double cd = di8_cd(p.d), gam = (double)p.gam;
+    auto epilogue = [&](auto interiorc) {
+        constexpr bool INTERIOR = decltype(interiorc)::value;
+        float *rptr[8];
+        float um[8]; // smallest upper bound of this lane's entries in row (mt, l15)
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
             const int64_t i = m0 + wr * 128 + (mt >> 2) * 64 + (mt & 3) * 16 + l15;
-            if (i >= p.n || j >= i) continue;
-            const int ei = p.ex[i];
-            const double si = ei == INT32_MIN ? 0.0 : ldexp(1.0, ei), l1i = (double)p.l1[i], ni = (double)p.nrm[i];
-            float *row = p.out + p.rowoff[i];
-            const di8_i32x4 hi = *reinterpret_cast<const di8_i32x4 *>(row + j);
-            float v[4];
+            rptr[mt] = (INTERIOR || i < p.n) ? p.out + p.rowoff[i] : nullptr;
+            um[mt] = ICL_MAXF;
+        }
+#pragma unroll
+        for (int ntl = 0; ntl < 4; ++ntl) {
+            const int64_t j = n0 + wc * 64 + (ntl >> 1) * 32 + (ntl & 1) * 16 + 4 * q;
+            di8_side cb[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const double I = 128.0 * (double)hi[e] + (double)acc[mt][ntl][e];
-                const double c = si * sj[e] * 1.4901161193847656e-08 * I; // 2^(e_a + e_b - 26) I: powers of two, exact
-                const double ns = ni + nj[e];
-                const double T = 0.5 * ns - c;
-                const double Eab = di8_eab(si, sj[e], l1i, l1j[e], ni, nj[e], p.d);
-                // (T - E_ab)(1 - g'), pushed down against this expression's own double roundings; the conversion rounds toward zero
-                const double Ld = (T - Eab) * (1.0 - (double)p.gam) * (1.0 - 1e-12);
-                const float L = (Ld > 1e-30 && ns < 1e37) ? __double2float_rz(Ld) : 0.0f; // subnormal range / overflowing norms (also NaN): no claim
-                v[e] = __uint_as_float(__float_as_uint(L) | 0x80000000u);
-                if (j + e < i) {
-                    // R <= (T + E_ab)(1 + g') and T - E_ab <= L (1 + 2 g') (or <= 1e-30 where L was clamped to 0): the scans' wupper, in double, rounded up
-                    const double U = ((double)L * (1.0 + 3.0 * (double)p.gam) + 2.0001 * Eab + 2e-30) * (1.0 + 2.0 * (double)p.gam);
-                    const float Uf = U < 3.0e38 ? __double2float_ru(U) : ICL_MAXF; // (inf / NaN: no claim)
-                    um[mt] = fminf(um[mt], Uf);
+                const bool in = INTERIOR || j + e < p.n;
+                cb[e] = di8_side_of(in ? p.ex[j + e] : DI8B_NOEXP, in ? p.l1[j + e] : 0.0f, in ? p.nrm[j + e] : 0.0f);
+            }
+#pragma unroll
+            for (int hx = 0; hx < 2; ++hx) {
+                di8_i32x4 hi[4]; // this lane's own words, parked at K-tile b2
+                int rex[4];
+                float rl1[4], rnr[4];
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int64_t i = m0 + wr * 128 + hx * 64 + m * 16 + l15;
+                    const bool live = INTERIOR || (i < p.n && j < i);
+                    hi[m] = live ? *reinterpret_cast<const di8_i32x4 *>(rptr[hx * 4 + m] + j) : di8_i32x4{0, 0, 0, 0};
+                    rex[m] = live ? p.ex[i] : DI8B_NOEXP;
+                    rl1[m] = live ? p.l1[i] : 0.0f;
+                    rnr[m] = live ? p.nrm[i] : 0.0f;
+                }
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int mt = hx * 4 + m;
+                    const int64_t i = m0 + wr * 128 + hx * 64 + m * 16 + l15;
+                    if (!INTERIOR && (i >= p.n || j >= i)) continue;
+                    di8_i32x4 lo = acc[mt][ntl], hw = hi[m];
+                    asm volatile("" : "+v"(rex[m]), "+v"(rl1[m]), "+v"(rnr[m]), "+v"(lo), "+v"(hw)::"memory");
+                    const di8_side ra = di8_side_of(rex[m], rl1[m], rnr[m]);
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double I = 128.0 * (double)hw[e] + (double)lo[e];
+                        const double Eab = di8_eab(ra, cb[e], cd);
+                        const float L = di8_lower(di8_T(ra, cb[e], I), Eab, ra.n + cb[e].n, gam);
+                        v[e] = __uint_as_float(__float_as_uint(L) | 0x80000000u);
+                        if (INTERIOR || j + e < i) um[mt] = fminf(um[mt], di8_upper(L, Eab, gam));
+                    }
+                    asm volatile("" : "+v"(um[mt]));
+                    if (INTERIOR || j + 3 < i) {
+                        *reinterpret_cast<float4 *>(rptr[mt] + j) = make_float4(v[0], v[1], v[2], v[3]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (j + e < i) rptr[mt][j + e] = v[e];
+                    }
+                    // (complete rows, ward.hip: writing the second copy of the pair from here -- row j + e at column i, 64 contiguous bytes per quarter
+                    // wave and store -- cost this kernel 12 ms at n = 100 000; ward_symmetrize_kernel's tile transposes take 7.8 ms for the same bytes)
                 }
             }
-            if (j + 3 < i) {
-                *reinterpret_cast<float4 *>(row + j) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
+        }
+        if (p.rowub) { // the four quarter waves of a wave hold the same 16 rows: join them, one atomic per row and wave
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j + e < i) row[j + e] = v[e];
+            for (int mt = 0; mt < 8; ++mt) {
+                um[mt] = fminf(um[mt], __shfl_xor(um[mt], 16, 64));
+                um[mt] = fminf(um[mt], __shfl_xor(um[mt], 32, 64));
             }
-            // (complete rows, ward.hip: writing the second copy of the pair from here -- row j + e at column i, 64 contiguous bytes per quarter
-            // wave and store -- cost this kernel 12 ms at n = 100 000; ward_symmetrize_kernel's tile transposes take 7.8 ms for the same bytes)
-        }
-    }
-    if (p.rowub) { // the four quarter waves of a wave hold the same 16 rows: join them, one atomic per row and wave
+            if (q == 0) {
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            float u = um[mt];
-            u = fminf(u, __shfl_xor(u, 16, 64));
-            u = fminf(u, __shfl_xor(u, 32, 64));
-            const int64_t i = m0 + wr * 128 + (mt >> 2) * 64 + (mt & 3) * 16 + l15;
-            if (q == 0 && i < p.n && u < ICL_MAXF) atomicMin(&p.rowub[i], __float_as_uint(u)); // (upper bounds are >= +0: their bits order like the values)
+                for (int mt = 0; mt < 8; ++mt) {
+                    const int64_t i = m0 + wr * 128 + (mt >> 2) * 64 + (mt & 3) * 16 + l15;
+                    // (upper bounds are >= +0: their bits order like the values; INTERIOR: every row has entries, and ICL_MAXF would change nothing)
+                    if (INTERIOR || (i < p.n && um[mt] < ICL_MAXF)) atomicMin(&p.rowub[i], __float_as_uint(um[mt]));
+                }
+            }
         }
-    }
+    };
+    if (tj < ti && m0 + 256 <= p.n) epilogue(std::true_type());
+    else epilogue(std::false_type());
 }
 
 // Usable for this shape?  D <= 2048 keeps hi = 128 S11 + S12 + S21 inside 32 bits.
