@@ -36,6 +36,8 @@ MAX_IMAGE_SIZE, MAX_IMAGE_DIM = 5 * 1024 * 1024, 2048  # rekognition.go: MaxImag
 _vp, _i64, _i32, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_int
 _pi64, _pi32 = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _pd = C.POINTER(C.c_double)
+_ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # a host array's address; None (NULL) for no array or an empty one
+_as_vp = lambda p: p if isinstance(p, _vp) or p is None else _vp(p)  # a device address as the argument type of a *_dev entry point
 SYMBOLS = [
     ("icl_create", _int, [_int, C.POINTER(_vp)]),
     ("icl_destroy", None, [_vp]),
@@ -295,8 +297,7 @@ def nearest_from_matrix(D, k, q_size=None, e_size=None, max_size=0, exclude=None
     qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
     kk = max(int(k), 1)
     idx, val = np.empty((nq, kk), np.int32), np.empty((nq, kk), np.float32)
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-    rc = load().icl_nearest_from_matrix(ptr(D), nq, n, ld, ptr(qs), ptr(es), int(k), int(max_size), ptr(ex), idx.ctypes.data, val.ctypes.data)
+    rc = load().icl_nearest_from_matrix(_ptr(D), nq, n, ld, _ptr(qs), _ptr(es), int(k), int(max_size), _ptr(ex), idx.ctypes.data, val.ctypes.data)
     if rc != ICL_OK:
         raise ICLError(rc, "icl_nearest_from_matrix: bad argument")
     return idx, val
@@ -325,8 +326,7 @@ def cluster_fit_from_matrix(D, cluster_of, k_alt, q_size=None, c_size=None, max_
     K = ld if K is None else int(K)
     qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
     out = _fit_outputs(nq, max(K, 0), k_alt)
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-    rc = load().icl_cluster_fit_from_matrix(ptr(D), nq, K, ld, ptr(qs), ptr(cof), ptr(cs), int(k_alt), int(max_size), *[ptr(a) for a in out])
+    rc = load().icl_cluster_fit_from_matrix(_ptr(D), nq, K, ld, _ptr(qs), _ptr(cof), _ptr(cs), int(k_alt), int(max_size), *[_ptr(a) for a in out])
     if rc != ICL_OK:
         raise ICLError(rc, "icl_cluster_fit_from_matrix: bad argument")
     return _fit_result(out)
@@ -502,6 +502,25 @@ class Context:
 
     def sync(self):
         check(self.h, self.L.icl_sync(self.h))
+
+    def _on_device_copies(self, ins, outs, call):
+        """The dev=True forms of the host methods: call(*device pointers) on device buffers of the arrays ins (uploaded) and outs
+        (downloaded once the call's work has finished); an empty array gets a buffer of 16 bytes and no copy."""
+        bufs = []
+        try:
+            for a in tuple(ins) + tuple(outs):
+                bufs.append(self.malloc(max(a.nbytes, 16)))
+            for p, a in zip(bufs, ins):
+                if a.size:
+                    self.h2d(p, a)
+            call(*bufs)
+            self.sync()
+            for p, a in zip(bufs[len(ins):], outs):
+                if a.size:
+                    self.d2h(a, p)
+        finally:
+            for p in bufs:
+                self.free(p)
 
     def device_info(self):
         buf = C.create_string_buffer(256)
@@ -958,36 +977,19 @@ class Context:
         qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
         kk = max(int(k), 1)
         idx, val = np.empty((nq, kk), np.int32), np.empty((nq, kk), np.float32)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
         if not dev:
-            check(self.h, self.L.icl_nearest(self.h, ptr(Qm), ptr(qs), nq, ptr(Em), ptr(es), n, d, int(k), int(max_size), ptr(ex),
+            check(self.h, self.L.icl_nearest(self.h, _ptr(Qm), _ptr(qs), nq, _ptr(Em), _ptr(es), n, d, int(k), int(max_size), _ptr(ex),
                                              idx.ctypes.data, val.ctypes.data))
             return idx, val
-        bufs = []
-        try:
-            for a in (Qm, Em, idx, val):
-                bufs.append(self.malloc(max(a.nbytes, 16)))
-            if Qm.size:
-                self.h2d(bufs[0], Qm)
-            if Em.size:
-                self.h2d(bufs[1], Em)
-            self.nearest_dev(bufs[0], nq, bufs[1], n, d, k, bufs[2], bufs[3], qs, es, max_size, ex)
-            if idx.size:
-                self.d2h(idx, bufs[2])
-                self.d2h(val, bufs[3])
-        finally:
-            for p in bufs:
-                self.free(p)
+        self._on_device_copies((Qm, Em), (idx, val), lambda dQ, dE, dI, dV: self.nearest_dev(dQ, nq, dE, n, d, k, dI, dV, qs, es, max_size, ex))
         return idx, val
 
     def nearest_dev(self, d_Q, nq, d_E, n, d, k, d_idx, d_val, q_size=None, e_size=None, max_size=0, exclude=None):
         """icl_nearest_dev: Q (nq x d), E (n x d), idx and val (nq x k) are device pointers; q_size, e_size and exclude host arrays
         or None.  Enqueued on the context's stream: sync() before reading the outputs through another stream."""
         qs, es, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size"), _nearest_exclude(nq, exclude)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
-        check(self.h, self.L.icl_nearest_dev(self.h, as_vp(d_Q), ptr(qs), nq, as_vp(d_E), ptr(es), n, d, int(k), int(max_size), ptr(ex),
-                                             as_vp(d_idx), as_vp(d_val)))
+        check(self.h, self.L.icl_nearest_dev(self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_E), _ptr(es), n, d, int(k), int(max_size), _ptr(ex),
+                                             _as_vp(d_idx), _as_vp(d_val)))
 
     def set_nearest_options(self, column_splits=0):
         """icl_set_nearest_options: workgroups per band of 128 query rows the library's column tiles are split over (0: the engine decides
@@ -1012,26 +1014,12 @@ class Context:
         (nq, d), K = Qm.shape, Cm.shape[0]
         qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
         out = _fit_outputs(nq, K, k_alt)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
         if not dev:
-            check(self.h, self.L.icl_cluster_fit(self.h, ptr(Qm), ptr(qs), ptr(cof), nq, ptr(Cm), ptr(cs), K, d, int(k_alt), int(max_size),
-                                                 *[ptr(a) for a in out]))
+            check(self.h, self.L.icl_cluster_fit(self.h, _ptr(Qm), _ptr(qs), _ptr(cof), nq, _ptr(Cm), _ptr(cs), K, d, int(k_alt), int(max_size),
+                                                 *[_ptr(a) for a in out]))
             return _fit_result(out)
-        bufs = []
-        try:
-            for a in (Qm, Cm) + out:
-                bufs.append(self.malloc(max(a.nbytes, 16)))
-            for p, a in zip(bufs, (Qm, Cm)):
-                if a.size:
-                    self.h2d(p, a)
-            self.cluster_fit_dev(bufs[0], cof, nq, bufs[1], K, d, k_alt, *bufs[2:], q_size=qs, c_size=cs, max_size=max_size)
-            self.sync()
-            for p, a in zip(bufs[2:], out):
-                if a.size:
-                    self.d2h(a, p)
-        finally:
-            for p in bufs:
-                self.free(p)
+        self._on_device_copies((Qm, Cm), out, lambda dQ, dC, *d_out: self.cluster_fit_dev(dQ, cof, nq, dC, K, d, k_alt, *d_out, q_size=qs, c_size=cs,
+                                                                                        max_size=max_size))
         return _fit_result(out)
 
     def cluster_fit_dev(self, d_Q, cluster_of, nq, d_C, K, d, k_alt, d_own, d_alt_idx, d_alt_val, d_listed=None, d_rep=None, d_worst=None,
@@ -1039,10 +1027,8 @@ class Context:
         """icl_cluster_fit_dev: Q (nq x d), C (K x d) and the six outputs are device pointers (the per-cluster ones may be None);
         cluster_of, q_size and c_size host arrays.  Enqueued on the context's stream: sync() before reading the outputs."""
         qs, cs, cof = _nearest_side(nq, q_size, "q_size"), _nearest_side(K, c_size, "c_size"), _nearest_side(nq, cluster_of, "cluster_of")
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        as_vp = lambda p: p if isinstance(p, _vp) or p is None else _vp(p)
-        check(self.h, self.L.icl_cluster_fit_dev(self.h, as_vp(d_Q), ptr(qs), ptr(cof), nq, as_vp(d_C), ptr(cs), K, d, int(k_alt), int(max_size),
-                                                 as_vp(d_own), as_vp(d_alt_idx), as_vp(d_alt_val), as_vp(d_listed), as_vp(d_rep), as_vp(d_worst)))
+        check(self.h, self.L.icl_cluster_fit_dev(self.h, _as_vp(d_Q), _ptr(qs), _ptr(cof), nq, _as_vp(d_C), _ptr(cs), K, d, int(k_alt), int(max_size),
+                                                 _as_vp(d_own), _as_vp(d_alt_idx), _as_vp(d_alt_val), _as_vp(d_listed), _as_vp(d_rep), _as_vp(d_worst)))
 
     def last_fit_stats(self):
         """The last cluster_fit[_dev]: column splits used, 128 x 128 tiles run, pairs evaluated, workspace bytes."""
@@ -1062,24 +1048,10 @@ class Context:
             raise ValueError("%d row indices for %d column indices" % (len(a), len(b)))
         qs, es = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size")
         val = np.empty(len(a), np.float32)
-        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
         if not dev:
-            check(self.h, self.L.icl_ward_values_at(self.h, ptr(Qm), ptr(qs), nq, ptr(Em), ptr(es), n, d, ptr(a), ptr(b), len(a), ptr(val)))
+            check(self.h, self.L.icl_ward_values_at(self.h, _ptr(Qm), _ptr(qs), nq, _ptr(Em), _ptr(es), n, d, _ptr(a), _ptr(b), len(a), _ptr(val)))
             return val
-        bufs = []
-        try:
-            for x in (Qm, Em, val):
-                bufs.append(self.malloc(max(x.nbytes, 16)))
-            for p, x in zip(bufs, (Qm, Em)):
-                if x.size:
-                    self.h2d(p, x)
-            self.ward_values_at_dev(bufs[0], nq, bufs[1], n, d, a, b, bufs[2], q_size=qs, e_size=es)
-            self.sync()
-            if val.size:
-                self.d2h(val, bufs[2])
-        finally:
-            for p in bufs:
-                self.free(p)
+        self._on_device_copies((Qm, Em), (val,), lambda dQ, dE, dV: self.ward_values_at_dev(dQ, nq, dE, n, d, a, b, dV, q_size=qs, e_size=es))
         return val
 
     def ward_values_at_dev(self, d_Q, nq, d_E, n, d, qi, ej, d_val, q_size=None, e_size=None):
@@ -1087,9 +1059,7 @@ class Context:
         arrays.  Enqueued on the context's stream."""
         a, b = np.ascontiguousarray(np.asarray(qi).reshape(-1), np.int32), np.ascontiguousarray(np.asarray(ej).reshape(-1), np.int32)
         qs, es = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size")
-        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
-        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
-        check(self.h, self.L.icl_ward_values_at_dev(self.h, as_vp(d_Q), ptr(qs), nq, as_vp(d_E), ptr(es), n, d, ptr(a), ptr(b), len(a), as_vp(d_val)))
+        check(self.h, self.L.icl_ward_values_at_dev(self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_E), _ptr(es), n, d, _ptr(a), _ptr(b), len(a), _as_vp(d_val)))
 
     def pairs_within(self, E, threshold, size=None, cap=None):
         """icl_pairs_within: EVERY pair of rows of E whose WardDistance (sizes `size`, None: all 1) is at most threshold, bit for bit the
@@ -1101,21 +1071,18 @@ class Context:
             raise ValueError("E must be 2-D, got %s" % (Em.shape,))
         n, d = Em.shape
         sz = _nearest_side(n, size, "size")
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        return self._pairs_calls(n, cap, lambda rp, c, v, cp, tot: self.L.icl_pairs_within(self.h, ptr(Em), ptr(sz), n, d, float(threshold),
+        return self._pairs_calls(n, cap, lambda rp, c, v, cp, tot: self.L.icl_pairs_within(self.h, _ptr(Em), _ptr(sz), n, d, float(threshold),
                                                                                           rp, c, v, cp, C.byref(tot)))
 
     def pairs_within_dev(self, d_E, n, d, threshold, size=None, cap=None):
         """icl_pairs_within_dev on rows that are on the device already (d_E: n x d floats) -> (row_ptr, col, val) on the host, as
         pairs_within.  col and val live on the device during the call and are downloaded here."""
         sz = _nearest_side(n, size, "size")
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        as_vp = lambda p: p if isinstance(p, _vp) else _vp(p)
 
         def call(rp, c, v, cp, tot):  # c / v: the host arrays of cp entries; the device call gets device buffers of the same length
             bufs = [self.malloc(cp * 4), self.malloc(cp * 4)] if cp else [None, None]
             try:
-                rc = self.L.icl_pairs_within_dev(self.h, as_vp(d_E), ptr(sz), n, d, float(threshold), rp, bufs[0], bufs[1], cp, C.byref(tot))
+                rc = self.L.icl_pairs_within_dev(self.h, _as_vp(d_E), _ptr(sz), n, d, float(threshold), rp, bufs[0], bufs[1], cp, C.byref(tot))
                 if rc == ICL_OK and 0 < tot.value <= cp:
                     self.sync()
                     check(self.h, self.L.icl_memcpy_d2h(self.h, c, _vp(bufs[0]), tot.value * 4))
@@ -1309,8 +1276,7 @@ class Context:
         cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
         nc = _i32()
         co = np.zeros((m, d), np.float32) if want_centroids else None
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        args = (m, d, ptr(ss), int(min_size), int(max_size), int(k_target), cid.ctypes.data, rank.ctypes.data, C.byref(nc))
+        args = (m, d, _ptr(ss), int(min_size), int(max_size), int(k_target), cid.ctypes.data, rank.ctypes.data, C.byref(nc))
         if dev:
             dE = self.malloc(max(Cs.nbytes, 16))
             dC = self.malloc(max(Cs.nbytes, 16)) if want_centroids else None
@@ -1324,7 +1290,7 @@ class Context:
                 if dC is not None:
                     self.free(dC)
         else:
-            rc = self.L.icl_cluster_seeded(self.h, Cs.ctypes.data if m else None, *args, ptr(co))
+            rc = self.L.icl_cluster_seeded(self.h, Cs.ctypes.data if m else None, *args, _ptr(co))
         if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
             check(self.h, rc)
         merges = self.last_merges() if rc == ICL_OK else np.zeros((0, 2), np.int32)

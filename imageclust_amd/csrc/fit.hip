@@ -1,136 +1,51 @@
 // fit.hip -- icl_cluster_fit: how well each clustered row sits in its own cluster, and which other clusters would take it, exact,
 // with no distance matrix; icl_ward_values_at: exact values of listed pairs.
 //
-// Values are the reference's (clustering.go:136-157; ward_value.h).  The band walk is nearest.hip's: a workgroup owns 128 query rows
-// and walks its share of the library's 128-column tiles (ward_exact_tile.h), each row's k_alt best alternatives stay in LDS, a finished
-// tile goes through LDS a quarter at a time.  One duty more in the epilogue: the lane that selects for row i stores the value of column
+// Values are the reference's (clustering.go:136-157; ward_value.h).  The band walk is band_select.h's, with this unit's policy: a
+// frozen column scales with its item count and is left out, and the lane that selects for row i stores the value of column
 // cluster_of[i] to own[i] before it leaves that column out.  A column lies in exactly one tile and a tile belongs to exactly one
-// split, so own[i] has ONE writer in the whole launch: a plain store, no atomic, no partial array.  The splits' partial lists are
-// joined by nearest.hip's merge kernel.  fit_reduce_kernel then finds each cluster's representative and worst row with integer atomics
-// on packed keys (fit_select.h): a minimum and a maximum over a total order, so arrival order cannot show.
+// split, so own[i] has ONE writer in the whole launch: a plain store, no atomic, no partial array.  fit_reduce_kernel then finds each
+// cluster's representative and worst row with integer atomics on packed keys (fit_select.h): a minimum and a maximum over a total
+// order, so arrival order cannot show.
 // Compiled with -ffp-contract=off -fno-slp-vectorize like nearest.hip: every difference, product and sum is rounded on its own.
 #pragma clang fp contract(off)
 
-#include "icl_common.h"
+#include "band_select.h"
 #include "fit_select.h"
-#include "ward_exact_tile.h" // DT_TILE, DT_KC, DT_LD, ward_exact_tile
-#include "ward_value.h"
 
-#include <algorithm>
-#include <cstring>
+#define FT_ROWS 256       // rows per workgroup of the reduction kernels
+#define VA_PAIRS 64       // pairs per wave of ward_values_at_kernel: one per lane
+#define VA_KC 128         // k per chunk: two coalesced 256-byte loads of each row
+#define VA_LD (VA_KC + 1) // odd pitch: lane p walks row p of the chunk's products, distinct banks
 
-#define FT_STAGE (2 * DT_KC * DT_LD) // floats of the two operand chunks; the finished tile's quarters reuse them
-#define FT_SUB 64                    // a quarter: 64 rows x 64 columns ...
-#define FT_SUB_LD 65                 // ... at an odd pitch: the selecting lanes, one per row, hit distinct banks
-#define FT_ROWS 256                  // rows per workgroup of the reduction kernels
-#define VA_PAIRS 64                  // pairs per wave of ward_values_at_kernel: one per lane
-#define VA_KC 128                    // k per chunk: two coalesced 256-byte loads of each row
-#define VA_LD (VA_KC + 1)            // odd pitch: lane p walks row p of the chunk's products, distinct banks
-
-static_assert(FT_SUB * FT_SUB_LD <= FT_STAGE, "a quarter tile must fit the operand staging area");
-static_assert(FS_KMAX == 64, "the LDS budget below is worked out for k_alt <= 64");
-
-struct ft_args {
-    const float *Q, *C;
-    const int32_t *qs, *cs, *cof; // device copies of q_size, c_size (either may be null: all 1) and cluster_of
-    int64_t nq, K;
-    int d, k, max_size, vec;
-    int64_t ntiles, nbands;
-    int splits;
+struct ft_args : band_args { // E: the clusters' centroids, es: c_size (signed: a frozen column is negative), sel: cluster_of
     float *own;
-    float *val; // [splits][nq][k]: the result itself when splits == 1, else the partial lists
+    float *val;
     int32_t *idx;
 };
 
-// floats of dynamic LDS, as nearest.hip lays them out: operand chunks, the band's lists (pitch k | 1), per-row counts, the band's row
-// sizes, the tile's column sizes (signed: a frozen column is negative)
-static inline size_t ft_lds_bytes(int k) { return (size_t)(FT_STAGE + 2 * DT_TILE * (k | 1) + 3 * DT_TILE) * 4; }
-
-__global__ __launch_bounds__(256) void fit_tile_select_kernel(ft_args a)
-{
-    extern __shared__ __attribute__((aligned(16))) float ft_smem[];
-    float(*As)[DT_LD] = reinterpret_cast<float(*)[DT_LD]>(ft_smem);
-    float(*Bs)[DT_LD] = reinterpret_cast<float(*)[DT_LD]>(ft_smem + DT_KC * DT_LD);
-    float *sub = ft_smem;
-    const int k = a.k, ks = a.k | 1;
-    float *lv = ft_smem + FT_STAGE;
-    int32_t *lj = reinterpret_cast<int32_t *>(lv + DT_TILE * ks);
-    int32_t *cnt = lj + DT_TILE * ks;
-    int32_t *qsz = cnt + DT_TILE;
-    int32_t *csz = qsz + DT_TILE;
-
-    const int64_t band = (int64_t)blockIdx.x % a.nbands, split = (int64_t)blockIdx.x / a.nbands;
-    const int64_t t_lo = split * a.ntiles / a.splits, t_hi = (split + 1) * a.ntiles / a.splits;
-    const int64_t i0 = band * DT_TILE;
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-
-    if (tid < DT_TILE) {
-        cnt[tid] = 0;
-        qsz[tid] = (a.qs && i0 + tid < a.nq) ? a.qs[i0 + tid] : 1;
-        // a row of no cluster meets no own column: split 0 is the one writer of its own cost
-        if (split == 0 && i0 + tid < a.nq && a.cof[i0 + tid] < 0) a.own[i0 + tid] = NS_MAXF;
+struct ft_policy {
+    using args = ft_args;
+    // a row of no cluster meets no own column: split 0 is the one writer of its own cost
+    static __device__ __forceinline__ void band_start(const args &a, int64_t split, int64_t i0, int64_t r)
+    {
+        if (split == 0 && i0 + r < a.nq && a.sel[i0 + r] < 0) a.own[i0 + r] = NS_MAXF;
     }
-    __syncthreads();
-
-    for (int64_t t = t_lo; t < t_hi; ++t) {
-        const int64_t j0 = t * DT_TILE;
-        if (tid < DT_TILE) csz[tid] = (a.cs && j0 + tid < a.K) ? a.cs[j0 + tid] : 1; // (read after the tile's barriers)
-
-        float acc[8][8];
-        ward_exact_tile(a.Q, a.nq, i0, a.C, a.K, j0, a.d, a.vec != 0, As, Bs, acc);
-
-        // The finished tile, a quarter at a time, as in nearest_tile_select_kernel: every thread scales its 4 x 4 values of the quarter
-        // (clustering.go:142-144; a frozen column with its item count) into the staging area, then one lane per row takes the row's
-        // own cost if its column is here and offers the other columns to the row's list.
-#pragma unroll
-        for (int ah = 0; ah < 2; ++ah)
-#pragma unroll
-            for (int bh = 0; bh < 2; ++bh) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int sa = qsz[ah * 64 + ty * 4 + r];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        sub[(ty * 4 + r) * FT_SUB_LD + tx * 4 + c] =
-                            ward_scale(acc[ah * 4 + r][bh * 4 + c], sa, (int)fs_items(csz[bh * 64 + tx * 4 + c]));
-                }
-                __syncthreads();
-                if ((tid & 3) == 0) {
-                    const int row = ah * 64 + (tid >> 2);
-                    const int64_t i = i0 + row;
-                    if (i < a.nq) {
-                        const int sq = qsz[row];
-                        float *rv = lv + row * ks;
-                        int32_t *rj = lj + row * ks;
-                        int c = cnt[row];
-                        const int64_t jb = j0 + bh * 64;
-                        const int ncol = (int)(a.K - jb < FT_SUB ? (a.K - jb > 0 ? a.K - jb : 0) : FT_SUB);
-                        // the row's own column counted from this quarter's first (K < 2^31; negative for a row of no cluster)
-                        const int mine = a.cof[i] < 0 ? -1 : (int)(a.cof[i] - jb);
-                        if (mine >= 0 && mine < ncol) a.own[i] = sub[(tid >> 2) * FT_SUB_LD + mine];
-                        for (int col = 0; col < ncol; ++col) {
-                            if (fs_left_out(col, mine, sq, csz[bh * 64 + col], a.max_size)) continue;
-                            ns_insert(rv, rj, k, c, sub[(tid >> 2) * FT_SUB_LD + col], (int32_t)(jb + col));
-                        }
-                        cnt[row] = c;
-                    }
-                }
-                __syncthreads();
-            }
+    static __device__ __forceinline__ int items(int32_t c_size) { return (int)fs_items(c_size); }
+    static __device__ __forceinline__ int row_key(const args &, int64_t) { return 0; }
+    // the row's own column counted from this quarter's first (K < 2^31; negative for a row of no cluster); its value is the own cost
+    // (ncol by reference: by value it is noundef to the optimiser and the two tests below fold into one, which moves the register allocation)
+    static __device__ __forceinline__ int quarter_key(const args &a, int64_t i, int, int64_t jb, const int &ncol, const float *sub, int srow)
+    {
+        const int mine = a.sel[i] < 0 ? -1 : (int)(a.sel[i] - jb);
+        if (mine >= 0 && mine < ncol) a.own[i] = sub[srow * BAND_SUB_LD + mine];
+        return mine;
     }
-
-    // the band's lists, short rows with their tails
-    float *ov = a.val + (split * a.nq + i0) * k;
-    int32_t *oj = a.idx + (split * a.nq + i0) * k;
-    const int rows = (int)(a.nq - i0 < DT_TILE ? a.nq - i0 : DT_TILE);
-    for (int e = tid; e < rows * k; e += 256) {
-        const int row = e / k, p = e - row * k;
-        const bool have = p < cnt[row];
-        ov[e] = have ? lv[row * ks + p] : NS_MAXF;
-        oj[e] = have ? lj[row * ks + p] : -1;
+    static __device__ __forceinline__ bool left_out(int64_t, int col, int mine, int q_size, int32_t c_size, int32_t max_size)
+    {
+        return fs_left_out(col, mine, q_size, c_size, max_size);
     }
-}
+};
 
 // Exact values of listed pairs: val[p] = WardDistance of row qi[p] of Q and row ej[p] of E.  Each value is one strictly sequential
 // chain of d rounded additions, so the parallelism is over pairs: a workgroup is one wave and takes 64 pairs.  For each chunk of 128 k
@@ -207,32 +122,6 @@ __global__ __launch_bounds__(FT_ROWS) void fit_rows_of_keys_kernel(const unsigne
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-// Host arrays into one workspace: their int32 copies go up in one transfer that has finished at return (the caller's arrays and the
-// staging vector may go away then), ordered in front of the launches.
-struct ft_upload {
-    icl_ws_layout L{16};
-    struct part {
-        size_t at, bytes;
-        const int32_t *host;
-    };
-    std::vector<part> parts;
-    size_t add(const int32_t *host, int64_t count) // -> the array's offset (a null array takes no room)
-    {
-        const size_t at = L.take(host ? (size_t)count * 4 : 0);
-        if (host && count) parts.push_back({at, (size_t)count * 4, host});
-        return at;
-    }
-    int go(icl_ctx *ctx, char *ws, size_t bytes) // bytes: L.total as it was behind the last add
-    {
-        if (!bytes) return ICL_OK;
-        std::vector<char> meta(bytes, 0);
-        for (const part &pt : parts) std::memcpy(meta.data() + pt.at, pt.host, pt.bytes);
-        ICL_HIP(ctx, hipMemcpyAsync(ws, meta.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return ICL_OK;
-    }
-};
-
 static void values_at_launch(icl_ctx *ctx, const float *d_Q, const int32_t *d_qs, const float *d_E, const int32_t *d_es, int d, const int32_t *d_qi,
                              const int32_t *d_ej, int64_t np, float *d_val)
 {
@@ -245,15 +134,13 @@ static int cluster_fit_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t 
                                   const int32_t *c_size, int64_t K, int32_t d, int32_t k_alt, int32_t max_size, float *d_own, int32_t *d_alt_idx,
                                   float *d_alt_val, int32_t *d_listed, int32_t *d_rep, int32_t *d_worst)
 {
-    const int64_t nbands = icl_ceil_div(nq, DT_TILE), ntiles = icl_ceil_div(K, DT_TILE);
     const bool walk = nq > 0 && k_alt > 0, keys = K > 0 && (d_rep || d_worst);
-    const int splits = walk ? nearest_splits(ctx, nbands, ntiles) : 0;
-    if (walk && nbands * splits > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_cluster_fit: grid too large (nq=%lld)", (long long)nq);
+    band_plan plan; // (no walk: no splits, no tiles)
+    if (walk) ICL_TRY(plan.decide(ctx, "icl_cluster_fit", nq, K, k_alt));
     // [q_size] [cluster_of] [c_size] [partial values] [partial indices] [rep keys] [worst keys], each on a 16-byte boundary
-    ft_upload up;
-    const size_t o_qs = up.add(q_size, nq), o_cof = up.add(cluster_of, nq), o_cs = up.add(c_size, K);
-    const size_t b_meta = up.L.total, b_part = splits > 1 ? (size_t)splits * nq * k_alt * 4 : 0;
-    const size_t o_val = up.L.take(b_part), o_idx = up.L.take(b_part);
+    icl_ws_upload up;
+    const size_t o_qs = up.add(q_size, nq), o_cof = up.add(cluster_of, nq), o_cs = up.add(c_size, K), b_meta = up.L.total;
+    const size_t o_val = up.L.take(plan.part_bytes), o_idx = up.L.take(plan.part_bytes);
     const size_t o_kr = up.L.take(keys ? (size_t)K * 8 : 0), o_kw = up.L.take(keys ? (size_t)K * 8 : 0), need = up.L.total;
     if (need) ICL_TRY(ctx->fit.ensure(ctx, need, "icl_cluster_fit: workspace"));
     char *ws = ctx->fit.as<char>(); // (used only where need > 0)
@@ -264,26 +151,17 @@ static int cluster_fit_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t 
     if (walk) {
         ft_args a;
         a.Q = d_Q;
-        a.C = d_C;
+        a.E = d_C;
         a.qs = qs;
-        a.cs = cs;
-        a.cof = cof;
+        a.es = cs;
+        a.sel = cof;
         a.nq = nq;
-        a.K = K;
+        a.n = K;
         a.d = d;
         a.k = k_alt;
         a.max_size = max_size;
-        a.vec = (d & 3) == 0 && (((uintptr_t)d_Q | (uintptr_t)d_C) & 15) == 0;
-        a.ntiles = ntiles;
-        a.nbands = nbands;
-        a.splits = splits;
         a.own = d_own;
-        a.val = splits > 1 ? (float *)(ws + o_val) : d_alt_val;
-        a.idx = splits > 1 ? (int32_t *)(ws + o_idx) : d_alt_idx;
-        icl_lds_optin(ctx, (const void *)fit_tile_select_kernel, (int)ft_lds_bytes(FS_KMAX));
-        hipLaunchKernelGGL(fit_tile_select_kernel, dim3((unsigned)(nbands * splits)), dim3(256), ft_lds_bytes(k_alt), ctx->stream, a);
-        ICL_HIP(ctx, hipGetLastError());
-        if (splits > 1) ICL_TRY(nearest_merge_launch(ctx, a.val, a.idx, nq, k_alt, splits, d_alt_val, d_alt_idx));
+        ICL_TRY(plan.run<ft_policy>(ctx, a, (float *)(ws + o_val), (int32_t *)(ws + o_idx), d_alt_val, d_alt_idx));
         pairs = nq * K;
     } else if (nq > 0) {
         // no list to keep: a band's rows may name up to 128 different column tiles, so the own costs come as listed pairs (i, cluster_of[i])
@@ -309,8 +187,8 @@ static int cluster_fit_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t 
             ICL_HIP(ctx, hipGetLastError());
         }
     }
-    ctx->fit_stats[0] = splits;
-    ctx->fit_stats[1] = walk ? nbands * ntiles : 0;
+    ctx->fit_stats[0] = plan.splits;
+    ctx->fit_stats[1] = plan.nbands * plan.ntiles;
     ctx->fit_stats[2] = pairs;
     ctx->fit_stats[3] = (int64_t)need;
     return ICL_OK;
@@ -417,7 +295,7 @@ static int values_at_dev_locked(icl_ctx *ctx, const float *d_Q, const int32_t *q
                                 int32_t d, const int32_t *qi, const int32_t *ej, int64_t np, float *d_val)
 {
     if (icl_ceil_div(np, VA_PAIRS) > 0x7fffffffLL) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_ward_values_at: grid too large (np=%lld)", (long long)np);
-    ft_upload up; // [q_size] [e_size] [qi] [ej]
+    icl_ws_upload up; // [q_size] [e_size] [qi] [ej]
     const size_t o_qs = up.add(q_size, nq), o_es = up.add(e_size, n), o_qi = up.add(qi, np), o_ej = up.add(ej, np), need = up.L.total;
     ICL_TRY(ctx->fit.ensure(ctx, need, "icl_ward_values_at: workspace"));
     char *ws = ctx->fit.as<char>();

@@ -284,9 +284,8 @@ static inline void icl_ingest_stats_reset(icl_ctx *ctx) { ctx->ingest_last = ing
 int cluster_many_locked(icl_ctx *ctx, int32_t nprob, const float *d_E, const float *h_E, int64_t e_len, const int64_t *e_off, const int32_t *n,
                         const int32_t *d, const int32_t *min_size, const int32_t *max_size, int32_t *cluster_id, int32_t *member_rank,
                         int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, icl_item_failure *lowest = nullptr);
-// nearest.hip, for fit.hip's band walk: icl_nearest's column-split decision (icl_set_nearest_options included) and the launch of
-// nearest_merge_kernel over [splits][nq][k] partial lists on the context's stream.  Both expect ctx->mu held and the device selected.
-int nearest_splits(const icl_ctx *ctx, int64_t nbands, int64_t ntiles);
+// nearest.hip, for every band walk (band_select.h, band_plan::run): the launch of nearest_merge_kernel over [splits][nq][k] partial
+// lists on the context's stream.  Expects ctx->mu held and the device selected.
 int nearest_merge_launch(icl_ctx *ctx, const float *d_pv, const int32_t *d_pj, int64_t nq, int k, int splits, float *d_val, int32_t *d_idx);
 
 // the rules every clustering call shares: CalculateOptimalClusters, the admission of a seeded problem, the final cluster list

@@ -3,11 +3,14 @@
 //   dev_guard + icl_dev_alloc   a buffer that lives for one call
 //   icl_dev_grow                a buffer a context keeps between calls and grows on demand
 //   icl_ws_layout               where the pieces of one such buffer lie (icl_ws_layout.h)
+//   icl_ws_upload               host int32 arrays into the front of one such buffer, in one copy
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
+#include <vector>
 
 #include "icl_ws_layout.h"
 
@@ -73,6 +76,33 @@ struct icl_dev_grow {
         p = g.p;
         g.p = nullptr;
         bytes = b;
+        return ICL_OK;
+    }
+};
+
+// Host int32 arrays into one workspace: add() places each (L goes on to place whatever else the workspace holds), go() sends them up
+// in one transfer that has finished at return (the caller's arrays and the staging vector may go away then), ordered in front of the
+// launches on the context's stream.
+struct icl_ws_upload {
+    icl_ws_layout L{16};
+    struct part {
+        size_t at, bytes;
+        const int32_t *host;
+    };
+    std::vector<part> parts;
+    size_t add(const int32_t *host, int64_t count) // -> the array's offset (a null array takes no room)
+    {
+        const size_t at = L.take(host ? (size_t)count * 4 : 0);
+        if (host && count) parts.push_back({at, (size_t)count * 4, host});
+        return at;
+    }
+    int go(icl_ctx *ctx, char *ws, size_t bytes) // bytes: L.total as it was behind the last add
+    {
+        if (!bytes) return ICL_OK;
+        std::vector<char> meta(bytes, 0);
+        for (const part &pt : parts) std::memcpy(meta.data() + pt.at, pt.host, pt.bytes);
+        ICL_HIP(ctx, hipMemcpyAsync(ws, meta.data(), bytes, hipMemcpyHostToDevice, icl_main_stream(ctx)));
+        ICL_HIP(ctx, hipStreamSynchronize(icl_main_stream(ctx)));
         return ICL_OK;
     }
 };

@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # kernel -> how a trace may spell it (demangled, mangled)
 KERNELS = {"ward_dist_exact_kernel<0>": ["ward_dist_exact_kernel<0>", "ward_dist_exact_kernelILi0E"],
            "ward_dist_exact_kernel<1>": ["ward_dist_exact_kernel<1>", "ward_dist_exact_kernelILi1E"],
-           "nearest_tile_select_kernel": ["nearest_tile_select_kernel"],
+           "nearest_tile_select_kernel": ["nearest_tile_select_kernel", "band_select_kernel<nr_policy>", "band_select_kernelI9nr_policy"],
            "dist_mfma_kernel<0>": ["dist_mfma_kernel<0>", "dist_mfma_kernelILi0E"],
            "dist_mfma_kernel<1>": ["dist_mfma_kernel<1>", "dist_mfma_kernelILi1E"],
            "dist_bound_kernel": ["dist_bound_kernel"]}
@@ -116,7 +116,7 @@ def child_times(n, d, nq, lib_n, reps, lw_reps):
         ctx.set_ward_options(1)
         ctx.ward_distance_rows_dev(dX, n, d, 0, n, dD)  # ward_dist_exact_kernel<0>
         ctx.set_ward_options(0)
-        ctx.nearest_dev(dX, nq, dX, lib_n, d, 10, dI, dV)  # nearest_tile_select_kernel
+        ctx.nearest_dev(dX, nq, dX, lib_n, d, 10, dI, dV)  # band_select_kernel<nr_policy> (a parent build: nearest_tile_select_kernel)
         ctx.sync()
     for _ in range(lw_reps):
         ctx.cluster_dev(dX, n, d, 3, 6, _lib.UPDATE_LW)  # dist_mfma_kernel<0> (the packed matrix of the fast mode)

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Compare two device-only assembly listings kernel by kernel: isa_compare.py parent.s branch.s [more.s ...]
+"""Compare two device-only assembly listings kernel by kernel: isa_compare.py [--pair OLD=NEW ...] parent.s branch.s [more.s ...]
 
 For every .amdhsa_kernel of the first two files: the text from the kernel's label to the end of the function (every s_endpgm) and the
 .amdhsa_* descriptor block (registers, LDS, scratch) must be the same text.  Emission order is ignored.  Every further
-file must hold no kernel at all (host-only units).  Exit status 1 on any difference.
+file must hold no kernel at all (host-only units).  Exit status 1 on any difference.  --pair OLD=NEW compares the parent's kernel
+OLD with the branch's kernel NEW (a kernel that was renamed, or became a template's instantiation): NEW's text is read with the name
+OLD in it.  A name that holds OLD or NEW as a substring is enough, as long as it fits one kernel.
 
 The listings come from
   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include --cuda-device-only -S UNIT.hip -o UNIT.s
@@ -32,13 +34,23 @@ def kernels(path):
             b += 1
         # block labels carry the function's emission index (.LBB<index>_<block>), and so do the loop comments that name them (BB<index>_<block>):
         # drop the index, keep everything else
+        lines[a] = re.sub(r":\s+;", ": ;", lines[a])  # (the comment behind the label is aligned to a column: a longer name moves it)
         out[name] = (re.sub(r"\bBB\d+_", "BB_", re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b]))), desc)
     return out
 
 
 def main():
-    pa, pb, rest = sys.argv[1], sys.argv[2], sys.argv[3:]
+    argv, pairs = sys.argv[1:], []
+    while argv and argv[0] == "--pair":
+        pairs.append(argv[1].split("="))
+        argv = argv[2:]
+    pa, pb, rest = argv[0], argv[1], argv[2:]
     A, B = kernels(pa), kernels(pb)
+    for old, new in pairs:
+        (old,), (new,) = [n for n in A if old in n], [n for n in B if new in n]
+        # (an instantiation has a section of its own; the directive that returns to it behind the descriptor is no code: read it as .text)
+        B[old] = tuple(re.sub(r"(?m)^\t\.section\t\.text\.%s,.*$" % re.escape(old), "\t.text", t.replace(new, old)) for t in B.pop(new))
+        print("paired: %s (parent) with %s" % (old, new))
     bad = 0
     print("%s: %d kernels, %s: %d kernels, same names: %s" % (pa, len(A), pb, len(B), sorted(A) == sorted(B)))
     for name in sorted(set(A) | set(B)):

@@ -107,6 +107,29 @@ def test_every_split_count_gives_the_same_bits_and_one_writer_of_own(ctx, split_
             assert not FC.why(res[s, k], want), "splits=%d k=%d: %s" % (s, k, FC.why(res[s, k], want))
 
 
+def test_the_two_instantiations_of_the_band_walk_agree(ctx):
+    """With no frozen cluster and every row in a cluster, cluster_fit's alternatives ARE nearest's lists with the own cluster excluded,
+    and its own costs the listed pairs (i, cluster_of[i]): one kernel body (band_select.h) under two policies, bit for bit, with one
+    workgroup per band, with three, and with the engine's own split count."""
+    nq, K, d = FC.SPLIT_CASE
+    P = FC.problem(nq, K, d, 77, plain=True)
+    qs, cs, cof = P["q_size"], P["c_size"], P["cluster_of"]
+    assert (cs > 0).all() and (cof >= 0).all()
+    own = ctx.ward_values_at(P["Q"], P["C"], np.arange(nq), cof, qs, cs)
+    try:
+        for s in (1, 3, 0):
+            ctx.set_nearest_options(s)
+            for k in (1, 64):
+                fit = run(ctx, P, k)
+                idx, val = ctx.nearest(P["Q"], P["C"], k, qs, cs, P["max_size"], exclude=cof)
+                assert ctx.last_fit_stats()["splits"] == ctx.last_nearest_stats()["splits"] and (s == 0 or ctx.last_fit_stats()["splits"] == s)
+                assert np.array_equal(fit["alt_idx"], idx), "splits=%d k=%d" % (s, k)
+                assert np.array_equal(fit["alt_val"].view(np.uint32), val.view(np.uint32)), "splits=%d k=%d" % (s, k)
+                assert np.array_equal(fit["own"].view(np.uint32), own.view(np.uint32)), "splits=%d k=%d" % (s, k)
+    finally:
+        ctx.set_nearest_options(0)
+
+
 def test_empty_sides(ctx):
     P = FC.problem(6, 5, 8, 41)
     r = ctx.cluster_fit(np.zeros((0, 8), np.float32), np.zeros(0, np.int32), P["C"], 3, c_size=P["c_size"])   # nq == 0
