@@ -134,6 +134,34 @@ type SeededResult struct {
 // ClusterManySeeded resumes the clustering loop (clustering.go:216-246) from existing clusters for many problems in one
 // icl_cluster_many_seeded call.  The error is the call's own (a bad argument, the device); a problem's failure is its Status.
 func ClusterManySeeded(probs []SeededProblem) ([]SeededResult, error) {
+	return clusterManySeeded(probs, nil)
+}
+
+// ApartProblem is one problem of ClusterManyApart: a SeededProblem with keep-apart constraints.  ApartClass (nil: none) holds one
+// int per seed, 0 meaning none: two different seeds of one non-zero class never share a cluster.  ApartPairs lists seed indices that
+// never share a cluster, either order.  A merged cluster inherits the bans of both parents.
+type ApartProblem struct {
+	SeededProblem
+	ApartClass []int32
+	ApartPairs [][2]int32
+}
+
+// ClusterManyApart is ClusterManySeeded with keep-apart constraints (icl_cluster_many_apart).  The loop may end before KTarget
+// clusters are reached: len(Merges) then tells.  A malformed constraint is the call's error; more than ManySeededMax seeds is the
+// problem's Status (ICL_ERR_UNSUPPORTED).
+func ClusterManyApart(probs []ApartProblem) ([]SeededResult, error) {
+	seeded := make([]SeededProblem, len(probs))
+	for j, pr := range probs {
+		if pr.ApartClass != nil && len(pr.ApartClass) != len(pr.Sizes) {
+			return nil, fmt.Errorf("problem %d: %d classes for %d seeds", j, len(pr.ApartClass), len(pr.Sizes))
+		}
+		seeded[j] = pr.SeededProblem
+	}
+	return clusterManySeeded(seeded, probs)
+}
+
+// the body of both: apart is nil (icl_cluster_many_seeded) or holds every problem's constraints (icl_cluster_many_apart)
+func clusterManySeeded(probs []SeededProblem, apart []ApartProblem) ([]SeededResult, error) {
 	out := make([]SeededResult, len(probs))
 	if len(probs) == 0 {
 		return out, nil
@@ -184,9 +212,30 @@ func ClusterManySeeded(probs []SeededProblem) ([]SeededResult, error) {
 		st[j] = -1 // stays -1 when the call fails before the problems run
 	}
 	i32 := func(p *int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(p)) }
-	rc := C.icl_cluster_many_seeded((*C.icl_ctx)(raw), C.int32_t(np), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(len(flat)),
-		(*C.int64_t)(unsafe.Pointer(&eoff[0])), i32(&m[0]), i32(&d[0]), i32(&ss[0]), i32(&mn[0]), i32(&mx[0]), i32(&kt[0]), i32(&cid[0]),
-		i32(&rank[0]), i32(&nc[0]), i32(&nm[0]), i32(&mg[0]), i32(&st[0]), (*C.float)(unsafe.Pointer(&cout[0])))
+	var rc C.int
+	if apart == nil {
+		rc = C.icl_cluster_many_seeded((*C.icl_ctx)(raw), C.int32_t(np), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(len(flat)),
+			(*C.int64_t)(unsafe.Pointer(&eoff[0])), i32(&m[0]), i32(&d[0]), i32(&ss[0]), i32(&mn[0]), i32(&mx[0]), i32(&kt[0]), i32(&cid[0]),
+			i32(&rank[0]), i32(&nc[0]), i32(&nm[0]), i32(&mg[0]), i32(&st[0]), (*C.float)(unsafe.Pointer(&cout[0])))
+	} else {
+		cls := make([]int32, rows+1) // the seed layout of ss; 0: no class
+		poff := make([]int64, np+1)
+		pairs := []int32{}
+		at = 0
+		for j, pr := range apart {
+			copy(cls[at:], pr.ApartClass)
+			at += int(m[j])
+			for _, q := range pr.ApartPairs {
+				pairs = append(pairs, q[0], q[1])
+			}
+			poff[j+1] = int64(len(pairs) / 2)
+		}
+		pairs = append(pairs, 0) // (never empty: its address is taken)
+		rc = C.icl_cluster_many_apart((*C.icl_ctx)(raw), C.int32_t(np), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(len(flat)),
+			(*C.int64_t)(unsafe.Pointer(&eoff[0])), i32(&m[0]), i32(&d[0]), i32(&ss[0]), i32(&mn[0]), i32(&mx[0]), i32(&kt[0]), i32(&cls[0]),
+			(*C.int64_t)(unsafe.Pointer(&poff[0])), i32(&pairs[0]), i32(&cid[0]), i32(&rank[0]), i32(&nc[0]), i32(&nm[0]), i32(&mg[0]),
+			i32(&st[0]), (*C.float)(unsafe.Pointer(&cout[0])))
+	}
 	for j := range st {
 		if rc != C.ICL_OK && st[j] < 0 {
 			return nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))

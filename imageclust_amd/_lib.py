@@ -138,6 +138,8 @@ SYMBOLS = [
     ("icl_cluster_many_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 11),
     ("icl_cluster_many_seeded", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
     ("icl_cluster_many_seeded_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 14),
+    ("icl_cluster_many_apart", _int, [_vp, _i32, _vp, _i64] + [_vp] * 17),
+    ("icl_cluster_many_apart_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 17),
     ("icl_cluster_seeded", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
@@ -1222,13 +1224,34 @@ class Context:
                                          nc.ctypes.data, nm.ctypes.data, mg.ctypes.data if want_merges else None, st.ctypes.data)
         return self._many_results(rc, pk, outs)
 
-    def cluster_many_seeded(self, problems, want_merges=False, want_centroids=False, raise_on_error=False, dev=False):
+    def cluster_many_apart(self, problems, want_merges=False, want_centroids=False, raise_on_error=False, dev=False):
+        """icl_cluster_many_apart: cluster_many_seeded with keep-apart constraints.  problems = [(C, seed_size, min_size, max_size, k_target,
+        apart_class | None, apart_pairs | None), ...]: apart_class holds one int per seed (0: none; two seeds of one non-zero class are never
+        merged into one cluster), apart_pairs (i, j) seed indices that stay apart; a merged cluster inherits the bans of both parents.
+        Arguments and return value are cluster_many_seeded's; a malformed constraint raises ICLError(ICL_ERR_ARG)."""
+        classes, pairs, off = [], [], [0]
+        for p, pr in enumerate(problems):
+            m = len(np.asarray(pr[1]).reshape(-1))
+            cl = np.zeros(m, np.int32) if len(pr) < 6 or pr[5] is None else np.asarray(pr[5], np.int32).reshape(-1)
+            if len(cl) != m:
+                raise ValueError("problem %d: %d apart_class entries for %d seeds" % (p, len(cl), m))
+            pa = np.zeros((0, 2), np.int32) if len(pr) < 7 or pr[6] is None else np.asarray(pr[6], np.int32).reshape(-1, 2)
+            classes.append(cl)
+            pairs.append(pa)
+            off.append(off[-1] + len(pa))
+        cls = np.ascontiguousarray(np.concatenate(classes + [np.zeros(1, np.int32)]), np.int32)
+        par = np.ascontiguousarray(np.concatenate(pairs + [np.zeros((1, 2), np.int32)]), np.int32)
+        apart = (cls, np.array(off, np.int64), par)
+        return self.cluster_many_seeded(problems, want_merges, want_centroids, raise_on_error, dev, _apart=apart)
+
+    def cluster_many_seeded(self, problems, want_merges=False, want_centroids=False, raise_on_error=False, dev=False, _apart=None):
         """icl_cluster_many_seeded: the clustering loop started from existing clusters.  problems = [(C, seed_size, min_size, max_size[,
         k_target]), ...]: C holds one centroid row per seed, seed_size[i] its item count (negative: frozen, never merged), k_target > 0
         the number of clusters to stop at (else CalculateOptimalClusters of the item total) -> a list of (cluster_id, seed_rank,
         n_clusters, status) per problem at seed granularity, as cluster_many() gives them per image; want_merges appends the merge log
         (seed i has id i, merge t id m + t), want_centroids then appends C_out (m x d: the row of each final cluster's rank-0 seed is
-        the cluster's centroid, every other row zero).  dev=True runs icl_cluster_many_seeded_dev on a device copy (the same result)."""
+        the cluster's centroid, every other row zero).  dev=True runs icl_cluster_many_seeded_dev on a device copy (the same result).
+        (_apart: cluster_many_apart's constraint arrays; the call is then icl_cluster_many_apart[_dev].)"""
         pk = pack_many([(pr[0], pr[2], pr[3]) for pr in problems])
         nprob = len(problems)
         sizes = [np.asarray(pr[1], np.int32).reshape(-1) for pr in problems]
@@ -1241,15 +1264,17 @@ class Context:
         outs = cid, rank, nc, nm, st, mg = _many_outputs(pk, want_merges)
         co = np.zeros(pk["E"].size, np.float32) if want_centroids else None
         ptr = lambda a: a.ctypes.data if a is not None else None
-        tail = (ptr(pk["e_off"]), ptr(pk["n"]), ptr(pk["d"]), ptr(ss), ptr(pk["min_size"]), ptr(pk["max_size"]), ptr(kt), ptr(cid), ptr(rank),
-                ptr(nc), ptr(nm), ptr(mg), ptr(st))
+        tail = (ptr(pk["e_off"]), ptr(pk["n"]), ptr(pk["d"]), ptr(ss), ptr(pk["min_size"]), ptr(pk["max_size"]), ptr(kt)) + \
+               (tuple(ptr(a) for a in _apart) if _apart is not None else ()) + (ptr(cid), ptr(rank), ptr(nc), ptr(nm), ptr(mg), ptr(st))
+        fn_host = self.L.icl_cluster_many_seeded if _apart is None else self.L.icl_cluster_many_apart
+        fn_dev = self.L.icl_cluster_many_seeded_dev if _apart is None else self.L.icl_cluster_many_apart_dev
         if dev:
             dE, dC = self.malloc(max(pk["E"].nbytes, 4)), self.malloc(max(pk["E"].nbytes, 4)) if want_centroids else None
             try:
                 self.h2d(dE, pk["E"])
                 if want_centroids:
                     self.h2d(dC, co)
-                rc = self.L.icl_cluster_many_seeded_dev(self.h, nprob, _vp(dE), pk["E"].size, *tail, _vp(dC) if want_centroids else None)
+                rc = fn_dev(self.h, nprob, _vp(dE), pk["E"].size, *tail, _vp(dC) if want_centroids else None)
                 if want_centroids:
                     self.d2h(co, dC)
             finally:
@@ -1257,7 +1282,7 @@ class Context:
                 if dC is not None:
                     self.free(dC)
         else:
-            rc = self.L.icl_cluster_many_seeded(self.h, nprob, ptr(pk["E"]), pk["E"].size, *tail, ptr(co))
+            rc = fn_host(self.h, nprob, ptr(pk["E"]), pk["E"].size, *tail, ptr(co))
         out = self._many_results(rc, pk, outs, raise_on_error)
         if want_centroids:
             out = [r + (co[int(o):int(o) + int(k) * int(w)].reshape(int(k), int(w)).copy(),)

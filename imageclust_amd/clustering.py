@@ -161,26 +161,40 @@ def PerformClusteringWithConstraintsMany(jobs, ctx: Optional[_lib.Context] = Non
 MANY_SEEDED_MAX = 2048  # icl_cluster_many_seeded's cap on a problem's seeds; above it the seeded call of the large-N engine runs
 
 
-def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target):
+def _constrained(apart_class, apart_pairs) -> bool:
+    """Whether the two optional lists hold a constraint at all."""
+    return (apart_class is not None and bool(np.asarray(apart_class).any())) or (apart_pairs is not None and len(apart_pairs) > 0)
+
+
+def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class=None, apart_pairs=None):
     """One seeded problem -> (cluster_id, seed_rank, n_clusters, status, merges, C_out): icl_cluster_many_seeded up to its cap,
-    icl_cluster_seeded (ward.hip's exact pipeline, no cap) above."""
+    icl_cluster_seeded (ward.hip's exact pipeline, no cap) above.  With a keep-apart constraint: icl_cluster_many_apart, which has the
+    cap and nothing above it (ICL_ERR_UNSUPPORTED)."""
+    if _constrained(apart_class, apart_pairs):
+        if len(sizes) > MANY_SEEDED_MAX:
+            raise _lib.ICLError(_lib.ICL_ERR_UNSUPPORTED, "%d seeds with keep-apart constraints: icl_cluster_many_apart holds at most %d"
+                                % (len(sizes), MANY_SEEDED_MAX))
+        return ctx.cluster_many_apart([(C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs)], want_merges=True, want_centroids=True)[0]
     if len(sizes) > MANY_SEEDED_MAX:
         return ctx.cluster_seeded(C, sizes, minSize, maxSize, k_target, want_centroids=True)
     return ctx.cluster_many_seeded([(C, sizes, minSize, maxSize, k_target)], want_merges=True, want_centroids=True)[0]
 
 
-def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_target: int = 0, ctx: Optional[_lib.Context] = None):
+def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_target: int = 0, ctx: Optional[_lib.Context] = None,
+                            apart_pairs=None, apart_class=None):
     """The loop of clustering.go:216-246 started from existing clusters (icl_cluster_many_seeded, one problem; icl_cluster_seeded above
     2 048 seeds): centroids[i] and
     sizes[i] describe seed cluster i, a negative size a frozen one that is never merged; k_target > 0 is the number of clusters to stop
     at, else CalculateOptimalClusters of the item total decides -> ((cluster_id, seed_rank, n_clusters, merges, C_out), True) at seed
     granularity -- C_out[i] is the centroid of the final cluster whose first seed is i, zero for every other seed -- or (None, False)
-    on impossible constraints."""
+    on impossible constraints.  apart_pairs ((i, j) seed indices) and apart_class (one int per seed, 0: none; the seeds of one non-zero
+    class) name seeds that must never share a cluster (icl_cluster_many_apart: a merged cluster inherits the bans of both parents; up to
+    2 048 seeds, ICLError(ICL_ERR_UNSUPPORTED) above); the loop may then end before k clusters are reached."""
     ctx = ctx or default_context()
     C = np.asarray(centroids, np.float32)
     if C.ndim != 2:
         C = C.reshape(len(sizes), -1)
-    cid, rank, nc, st, mg, co = _seeded_call(ctx, C, sizes, minSize, maxSize, k_target)
+    cid, rank, nc, st, mg, co = _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs)
     if st == _lib.ICL_ERR_CONSTRAINT:
         return None, False
     if st != _lib.ICL_OK:
@@ -283,11 +297,13 @@ class Clustering:
         state = Clustering.start(embeddings, ids, 3, 6)     # what PerformClusteringWithConstraints computes, kept
         state.add(more_embeddings, more_ids)                # new images join as singletons
         state.freeze(["img_4"])                             # the cluster holding img_4 stays as it is
+        state.keep_apart(["img_1", "img_9"])                # these two never share a cluster again (DESIGN.md "Constrained seeded clustering")
         state.recluster()
+        state.absorb_leftovers()                            # the images of dropped clusters join the kept clusters where they may
         state.as_map()
 
     `engine` replaces the GPU call in tests: engine(C, seed_size, minSize, maxSize, k_target) -> (cluster_id, seed_rank, n_clusters,
-    status, merges, C_out); `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
+    status, merges, C_out), called with two more arguments, (..., apart_class, apart_pairs), only when a constraint exists; `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
     `fit_engine` for fit(), representatives() and misfits(): fit_engine(Q, cluster_of, C, k_alt, q_size, c_size, max_size) -> the dict of
     Context.cluster_fit."""
 
@@ -298,6 +314,7 @@ class Clustering:
         self.embeddings: Dict[str, np.ndarray] = {}
         self.ok = True
         self.last_merges = np.zeros((0, 2), np.int32)
+        self.apart: List[List[str]] = []  # keep_apart's groups of image ids: the clusters holding the ids of one group are mutually apart
 
     @classmethod
     def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None,
@@ -341,6 +358,70 @@ class Clustering:
         self.clusters = [c for i, c in enumerate(self.clusters) if i not in set(gone)]
         self.clusters += [HeldCluster([k], self.embeddings[k].copy()) for k in freed]
 
+    def keep_apart(self, keys):
+        """The clusters holding these ids are mutually apart from now on: no recluster() merges two of them, nor clusters that swallowed
+        them.  Held per image id, so it survives merges and dissolve().  ValueError when two of the ids already share a cluster."""
+        keys = list(dict.fromkeys(keys))
+        where = {k: i for i, c in enumerate(self.clusters) for k in c.Members}
+        at = [where[k] for k in keys]
+        if len(set(at)) != len(at):
+            raise ValueError("keep_apart: two of these ids already share a cluster")
+        if len(keys) >= 2:
+            self.apart.append(keys)
+
+    def _apart_pairs(self, clusters=None) -> List[Tuple[int, int]]:
+        """The keep-apart relation over the held clusters: sorted (a, b), a < b, positions in self.clusters."""
+        where = {k: i for i, c in enumerate(self.clusters if clusters is None else clusters) for k in c.Members}
+        found = set()
+        for group in self.apart:
+            at = sorted({where[k] for k in group if k in where})
+            found.update((a, b) for x, a in enumerate(at) for b in at[x + 1:])
+        return sorted(found)
+
+    def keep_together(self, keys):
+        """The clusters holding these ids become one, now, on the host: merged in held order with MergeClusters' rule (clustering.go:
+        31-40: a's members then b's, centroid (float(sa) Ca + float(sb) Cb) / float(sa + sb), each operation rounded to fp32), the new
+        cluster in the first one's place, frozen if any part was.  ValueError, with the state as it was, when a keep-apart constraint
+        forbids it or the cluster would hold more than maxSize items."""
+        at = self._holding(keys)
+        if len(at) < 2:
+            return
+        if any(a in at and b in at for a, b in self._apart_pairs()):
+            raise ValueError("keep_together: a keep-apart constraint holds between two of these clusters")
+        if sum(len(self.clusters[i].Members) for i in at) > self.maxSize:
+            raise ValueError("keep_together: %d items, above maxSize (%d)" % (sum(len(self.clusters[i].Members) for i in at), self.maxSize))
+        first = self.clusters[at[0]]
+        members, cen, frozen = list(first.Members), np.array(first.Centroid, np.float32, copy=True), first.Frozen
+        for i in at[1:]:
+            c = self.clusters[i]
+            sa, sb = len(members), len(c.Members)
+            cen = ((np.float32(sa) * cen + np.float32(sb) * np.asarray(c.Centroid, np.float32)) / np.float32(sa + sb)).astype(np.float32)
+            members, frozen = members + list(c.Members), frozen or c.Frozen
+        self.clusters[at[0]] = HeldCluster(members, cen, frozen)
+        self.clusters = [c for i, c in enumerate(self.clusters) if i not in set(at[1:])]
+        kept = 0  # the report's ids (clustering.go:265-280): dense over the clusters of at least minSize items, in held order
+        for c in self.clusters:
+            c.Id = -1
+            if len(c.Members) >= self.minSize:
+                c.Id, kept = kept, kept + 1
+
+    def absorb_leftovers(self) -> List[str]:
+        """"Put the leftovers somewhere": the loop resumed with every kept, unfrozen cluster (at least minSize items) allowed to take
+        the dropped clusters' images but not another kept cluster -- class 1 of icl_cluster_many_apart -- and k_target = the kept and
+        the frozen clusters.  Returns the ids still unplaced: those no kept cluster could take (sizes, keep_apart, frozen)."""
+        kept = [len(c.Members) >= self.minSize and not c.Frozen for c in self.clusters]
+        k = sum(kept) + sum(c.Frozen for c in self.clusters)
+        if k < len(self.clusters):
+            self.recluster(max(1, k), _anchor=np.array(kept, np.int32))
+        return [key for c in self.clusters if len(c.Members) < self.minSize for key in c.Members]
+
+    def constraints(self) -> Dict[str, list]:
+        """What is held: the keep_apart groups (image ids), the cluster pairs they stand for now (first members' ids), the frozen
+        clusters (first members' ids)."""
+        return {"apart": [list(g) for g in self.apart],
+                "apart_clusters": [(self.clusters[a].Members[0], self.clusters[b].Members[0]) for a, b in self._apart_pairs()],
+                "frozen": [c.Members[0] for c in self.clusters if c.Frozen]}
+
     def seeds(self):
         """The seeded problem the state stands for: (centroids m x d, seed_size m; negative: frozen)."""
         d = len(next(iter(self.embeddings.values()))) if self.embeddings else 0
@@ -348,14 +429,17 @@ class Clustering:
         ss = np.array([-len(c.Members) if c.Frozen else len(c.Members) for c in self.clusters], np.int32)
         return C, ss
 
-    def recluster(self, k_target: int = 0) -> bool:
-        """Resume the loop from the clusters held.  False, with the state as it was, when the constraints cannot be met."""
+    def recluster(self, k_target: int = 0, _anchor=None) -> bool:
+        """Resume the loop from the clusters held, keep_apart's constraints respected.  False, with the state as it was, when the
+        constraints cannot be met.  (_anchor: absorb_leftovers' class per cluster.)"""
         C, ss = self.seeds()
+        pairs = np.array(self._apart_pairs(), np.int32).reshape(-1, 2)
+        extra = (_anchor, pairs) if _constrained(_anchor, pairs) else ()
         if self.engine is not None:
-            cid, rank, nc, st, mg, co = self.engine(C, ss, self.minSize, self.maxSize, k_target)
+            cid, rank, nc, st, mg, co = self.engine(C, ss, self.minSize, self.maxSize, k_target, *extra)
         else:
             ctx = self.ctx or default_context()
-            cid, rank, nc, st, mg, co = _seeded_call(ctx, C, ss, self.minSize, self.maxSize, k_target)
+            cid, rank, nc, st, mg, co = _seeded_call(ctx, C, ss, self.minSize, self.maxSize, k_target, *extra)
         self.ok = st == _lib.ICL_OK
         if st == _lib.ICL_ERR_CONSTRAINT:
             return False

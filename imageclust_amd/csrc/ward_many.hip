@@ -14,8 +14,10 @@
 //     (ComputeInitialDistanceMatrix, clustering.go:61-73), one thread per pair; ward_many_merge_kernel keeps the triangle in LDS when it
 //     fits (n <= 281, WM_LDS_MAX), forms the new cluster's row exactly (:76-96), one row per thread, and a thread rescans a row whose
 //     cached partner died.  Mid route (cap < n <= WMM_CAP): see "the mid-size route" below.
-//   * The four kernels themselves are in ward_many_kernels.h, included twice: as they are for problems that start from singletons,
-//     and once more for problems that start from SEED clusters (icl_cluster_many_seeded, "seeded clustering" at the end of this file).
+//   * The four kernels themselves are in ward_many_kernels.h, included three times: as they are for problems that start from singletons,
+//     once more for problems that start from SEED clusters (icl_cluster_many_seeded, "seeded clustering" at the end of this file), and
+//     a third time for seeded problems with a KEEP-APART relation over their clusters (icl_cluster_many_apart, "constrained seeded
+//     clustering" at the end of this file; the host rules are apart_bits.h).
 // Host.  Every entry point, seeded or not, is wm_entry (checks, lock, device) around wm_run, which runs the stages wm_classify (k, status,
 // wm_route of every problem), wm_make_plan (launch groups -- wm_group: the small route is one, the mid route's are cut under a workspace
 // budget -- and the workspace layout), wm_enqueue (uploads, aligned copies, wm_run_group per group, one read-back of the one log slab),
@@ -24,10 +26,14 @@
 // What the two routes' groups do differently on the host is the table wm_kind.
 // What a seeded call does differently is in two places: wm_classify takes a problem's k, status and effective sizes from
 // ward_seed_admit (ward_seeds.h, icl_cluster_seeded's rule too) and routes by wm_route_seeded, never to the large-N engine.
+// What a constrained call does beyond that is in two places as well: wm_make_plan counts every problem's bit rows into its group's data
+// region (wm_data_bytes), and wm_run_group expands them (ab_expand) and uploads them behind the head; every problem of such a call runs
+// on the constrained kernels, with empty bit rows where it has no constraint.
 // Cluster ids and ranks come from the merge log by ward_final_list (ward_seeds.h) whichever route a problem took: rows of one item
 // each (through ward.hip's icl_ward_assign_ids), or the seeds with their sizes.
 #pragma clang fp contract(off)
 
+#include "apart_bits.h"
 #include "icl_common.h"
 #include "ward_value.h"
 
@@ -242,12 +248,46 @@ __device__ __forceinline__ void wmm_append(bool f, int t, int32_t *count, uint16
     if (f) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)t;
 }
 
-// the kernels: from singletons, then from seeds
+// What a constrained seeded problem (icl_cluster_many_apart, DESIGN.md "Constrained seeded clustering") has beside its wm_prob: wm_seed's
+// two members under the same names, and the keep-apart relation over the slots as bit rows (apart_bits.h) in the global workspace
+struct wm_apart {
+    const int32_t *size; // as wm_seed::size
+    int32_t *fin;        // as wm_seed::fin
+    uint32_t *bits;      // n rows of `words` words: bit u of row t set when the clusters living in slots t and u are apart
+    int32_t words, pad;  // ab_words(n)
+};
+static_assert(sizeof(wm_apart) % 8 == 0, "wm_apart is an array element");
+
+__device__ __forceinline__ bool wm_apart_bit(const uint32_t *row, int u) { return row[u >> 5] >> (u & 31) & 1u; }
+// Row t's side of a merge of slots shi and slo into sn = slo: B(new, t) = B(shi, t) or B(slo, t).  When it holds, the bit for sn is set in
+// row t (it is already unless only shi's was).  Called by the one thread that owns row t in this step; a slot never comes back to life, so
+// nothing is ever cleared.
+__device__ __forceinline__ bool wm_apart_inherit(uint32_t *row, int shi, int slo)
+{
+    const bool hi = wm_apart_bit(row, shi), lo = wm_apart_bit(row, slo);
+    if (hi && !lo) row[slo >> 5] |= 1u << (slo & 31);
+    return hi || lo;
+}
+// ... and the new cluster's side: row(sn) |= row(shi), one word per thread
+template <int THREADS>
+__device__ __forceinline__ void wm_apart_or_row(uint32_t *bits, int words, int sn, int shi)
+{
+    uint32_t *dst = bits + (int64_t)sn * words;
+    const uint32_t *src = bits + (int64_t)shi * words;
+    for (int w = threadIdx.x; w < words; w += THREADS) dst[w] |= src[w];
+}
+
+// the kernels: from singletons, then from seeds, then from seeds with a keep-apart relation
 #define WM_SEEDED 0
+#define WM_APART 0
 #include "ward_many_kernels.h"
 #undef WM_SEEDED
 #define WM_SEEDED 1
 #include "ward_many_kernels.h"
+#undef WM_APART
+#define WM_APART 1
+#include "ward_many_kernels.h"
+#undef WM_APART
 #undef WM_SEEDED
 
 // C_out of the seeded calls: block b copies row src[b] (d[b] floats: a final cluster's centroid, from a problem's seed rows or its
@@ -355,6 +395,7 @@ struct wm_kind {
     const void *init_fn, *merge_fn;
     unsigned init_threads, merge_threads;
     bool own_data; // its group has a data region of its own (the small route); else the groups share one, one after the other
+    bool apart = false; // the constrained kernels: a wm_apart table, and every problem's bit rows in the group's data region
 };
 static const wm_kind wm_kind_small = {
     [](int64_t n) { return wm_tri_len(n) * 4; },
@@ -387,14 +428,29 @@ static wm_kind wm_seeded_kind(wm_kind k, const void *init_fn, const void *merge_
 }
 static const wm_kind wm_kind_small_seeded = wm_seeded_kind(wm_kind_small, (const void *)ward_many_init_seeded_kernel, (const void *)ward_many_merge_seeded_kernel);
 static const wm_kind wm_kind_mid_seeded = wm_seeded_kind(wm_kind_mid, (const void *)ward_many_mid_init_seeded_kernel, (const void *)ward_many_mid_merge_seeded_kernel);
+// the constrained instantiations: the seeded ones with a wm_apart table in the wm_seed table's place
+static wm_kind wm_apart_kind(wm_kind k, const void *init_fn, const void *merge_fn)
+{
+    k = wm_seeded_kind(k, init_fn, merge_fn);
+    k.apart = true;
+    return k;
+}
+static const wm_kind wm_kind_small_apart = wm_apart_kind(wm_kind_small, (const void *)ward_many_init_apart_kernel, (const void *)ward_many_merge_apart_kernel);
+static const wm_kind wm_kind_mid_apart = wm_apart_kind(wm_kind_mid, (const void *)ward_many_mid_init_apart_kernel, (const void *)ward_many_mid_merge_apart_kernel);
 
-// centroids + matrix of one problem in a group's data region (256-byte aligned pieces)
+// centroids + matrix of one problem in a group's data region (256-byte aligned pieces), and its bit rows where the kind has them
+static size_t wm_bits_bytes(const wm_kind &k, int64_t n)
+{
+    icl_ws_layout R(256);
+    if (k.apart) R.take(ab_table_bytes(n));
+    return R.total;
+}
 static size_t wm_data_bytes(const wm_kind &k, int64_t n, int64_t d)
 {
     icl_ws_layout R(256);
     R.take((size_t)(n * d * 4));
     R.take((size_t)k.mat_bytes(n));
-    return R.total;
+    return R.total + wm_bits_bytes(k, n);
 }
 
 // A launch group: problems that run as one init launch and one merge launch, one workgroup each in the merge.  The small route is one
@@ -408,11 +464,15 @@ struct wm_group {
     size_t data_bytes = 0;
     size_t o_head = 0, o_data = 0; // in the workspace; the head: [problem table] [init-block arguments] [order] [init-block problems]
     std::vector<unsigned char> head;
-    bool seeded = false;  // then the head goes on, 8-byte aligned: [wm_seed table] [effective seed sizes, problem after problem]
+    bool seeded = false;  // then the head goes on, 8-byte aligned: [wm_seed or wm_apart table] [effective seed sizes, problem after problem]
     size_t seed_rows = 0; // seeds of all its problems
+    // a constrained group: every problem's bit rows (wm_bits_bytes each), one block at the start of its data region, uploaded behind the head
+    size_t bit_bytes = 0;
+    std::vector<uint32_t> bits;
+    size_t seed_elem() const { return kind->apart ? sizeof(wm_apart) : sizeof(wm_seed); }
     size_t plain_bytes() const { return sizeof(wm_prob) * probs.size() + (size_t)kind->arg_bytes * blk_arg.size() + 4 * (probs.size() + blk_prob.size()); }
     size_t o_seed() const { return (plain_bytes() + 7) / 8 * 8; }
-    size_t head_bytes() const { return seeded ? o_seed() + sizeof(wm_seed) * probs.size() + 4 * seed_rows : plain_bytes(); }
+    size_t head_bytes() const { return seeded ? o_seed() + seed_elem() * probs.size() + 4 * seed_rows : plain_bytes(); }
 };
 
 // the per-problem arguments of every entry point
@@ -425,7 +485,12 @@ struct wm_args {
     bool seeded = false;
     const int32_t *seed_size = nullptr, *k_target = nullptr;
     bool want_cout = false, cout_host = false;
-    const char *what() const { return seeded ? "icl_cluster_many_seeded" : "icl_cluster_many"; } // (in front of a failed problem's reason)
+    // the constrained seeded calls: apart_class (seed layout; may be null), pair_off (nprob + 1 offsets in pairs) and apart_pairs (both may be null)
+    bool apart = false;
+    const int32_t *apart_class = nullptr;
+    const int64_t *pair_off = nullptr;
+    const int32_t *apart_pairs = nullptr;
+    const char *what() const { return apart ? "icl_cluster_many_apart" : seeded ? "icl_cluster_many_seeded" : "icl_cluster_many"; } // (in front of a failed problem's reason)
 };
 // ... and the outputs: rank is member_rank or seed_rank; C_out (seeded calls; may be null) on the device for a _dev call, on the host else;
 // lowest (may be null): see cluster_many_locked in icl_common.h
@@ -558,11 +623,12 @@ static void wm_make_plan(icl_ctx *ctx, const wm_args &A, bool upload_e, int64_t 
             kind.init_blocks((int32_t)g.probs.size(), A.n[p], g.blk_prob, g.blk_arg);
             g.probs.push_back(p);
             g.data_bytes += need;
+            g.bit_bytes += wm_bits_bytes(kind, A.n[p]);
             g.seed_rows += (size_t)A.n[p];
         }
     };
-    add(A.seeded ? wm_kind_small_seeded : wm_kind_small, small, SIZE_MAX);
-    add(A.seeded ? wm_kind_mid_seeded : wm_kind_mid, mid, wmm_budget());
+    add(A.apart ? wm_kind_small_apart : A.seeded ? wm_kind_small_seeded : wm_kind_small, small, SIZE_MAX);
+    add(A.apart ? wm_kind_mid_apart : A.seeded ? wm_kind_mid_seeded : wm_kind_mid, mid, wmm_budget());
     ctx->many_stats[3] = (int64_t)pl.groups.size() - (small.empty() ? 0 : 1);
     icl_ws_layout L(256); // 256-byte aligned pieces
     pl.o_e = upload_e && pl.need_e ? L.take((size_t)e_len * 4) : 0;
@@ -602,9 +668,12 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g
     g.head.resize(g.head_bytes());
     wm_prob *tab = reinterpret_cast<wm_prob *>(g.head.data());
     int32_t *ord = reinterpret_cast<int32_t *>(g.head.data() + o_ord);
-    wm_seed *stab = g.seeded ? reinterpret_cast<wm_seed *>(g.head.data() + g.o_seed()) : nullptr;
-    size_t o_eff = g.o_seed() + sizeof(wm_seed) * G; // (of the next problem's effective sizes, in the head)
+    unsigned char *stab = g.seeded ? g.head.data() + g.o_seed() : nullptr; // wm_seed or wm_apart entries
+    size_t o_eff = g.o_seed() + g.seed_elem() * G; // (of the next problem's effective sizes, in the head)
     icl_ws_layout R(256); // the problems' places in the group's data region
+    const size_t o_bits = g.o_data + R.take(g.bit_bytes);
+    g.bits.resize(g.bit_bytes / 4);
+    size_t bit_at = 0; // (of the next problem's bit rows, in the block)
     int64_t lds = 0;
     for (size_t i = 0; i < G; ++i) {
         const int32_t p = g.probs[i];
@@ -613,7 +682,17 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g
         if (g.seeded) {
             pl.c_dev[p] = C;
             memcpy(g.head.data() + o_eff, pl.eff.data() + pl.img[p], 4 * (size_t)A.n[p]);
-            stab[i] = wm_seed{(const int32_t *)(ws + g.o_head + o_eff), (int32_t *)(ws + pl.o_logs) + pl.log_at[p] + 2 * (int64_t)A.n[p] + 1};
+            const wm_seed sd{(const int32_t *)(ws + g.o_head + o_eff), (int32_t *)(ws + pl.o_logs) + pl.log_at[p] + 2 * (int64_t)A.n[p] + 1};
+            if (g.kind->apart) {
+                const int64_t q0 = A.pair_off ? A.pair_off[p] : 0, q1 = A.pair_off ? A.pair_off[p + 1] : 0;
+                ab_expand(A.n[p], A.apart_class ? A.apart_class + pl.img[p] : nullptr, q1 > q0 ? A.apart_pairs + 2 * q0 : nullptr, q1 - q0,
+                          g.bits.data() + bit_at / 4);
+                const wm_apart ap{sd.size, sd.fin, (uint32_t *)(ws + o_bits + bit_at), (int32_t)ab_words(A.n[p]), 0};
+                memcpy(stab + sizeof ap * i, &ap, sizeof ap);
+                bit_at += wm_bits_bytes(*g.kind, A.n[p]);
+            } else {
+                memcpy(stab + sizeof sd * i, &sd, sizeof sd);
+            }
             o_eff += 4 * (size_t)A.n[p];
         }
         float *mat = (float *)(ws + g.o_data + R.take((size_t)g.kind->mat_bytes(A.n[p])));
@@ -628,6 +707,7 @@ static int wm_run_group(icl_ctx *ctx, const wm_args &A, wm_plan &pl, wm_group &g
     if (!g.blk_prob.empty()) memcpy(ord + G, g.blk_prob.data(), 4 * g.blk_prob.size());
     const char *tab_d = ws + g.o_head, *arg_d = tab_d + o_arg, *ord_d = tab_d + o_ord, *blk_d = ord_d + 4 * G;
     ICL_HIP(ctx, hipMemcpyAsync(ws + g.o_head, g.head.data(), g.head.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (g.bit_bytes) ICL_HIP(ctx, hipMemcpyAsync(ws + o_bits, g.bits.data(), g.bit_bytes, hipMemcpyHostToDevice, ctx->stream));
     const char *seed_d = tab_d + g.o_seed(); // (the seeded kernels' last argument; the others take three and two)
     void *init_args[] = {&tab_d, &blk_d, &arg_d, &seed_d}, *merge_args[] = {&tab_d, &ord_d, &seed_d};
     if (!g.blk_prob.empty())
@@ -843,13 +923,30 @@ static int wm_check_seeds(icl_ctx *ctx, const char *what, int32_t nprob, const i
     return ICL_OK;
 }
 
-// The four entry points: the argument checks, the lock, the device, wm_run.  dev: E (and C_out) are on the device.
+// ... and of the constrained entry points, beyond both (apart_bits.h: ab_bad_arg)
+static int wm_check_apart(icl_ctx *ctx, const char *what, const wm_args &A)
+{
+    if (!A.pair_off && A.apart_pairs) return icl_fail(ctx, ICL_ERR_ARG, "%s: apart_pairs without pair_off", what);
+    int64_t rows = 0;
+    for (int32_t p = 0; p < A.nprob; ++p) {
+        const int64_t q0 = A.pair_off ? A.pair_off[p] : 0, q1 = A.pair_off ? A.pair_off[p + 1] : 0;
+        if (q0 < 0 || q1 < q0) return icl_fail(ctx, ICL_ERR_ARG, "%s: problem %d: pair offsets %lld, %lld", what, p, (long long)q0, (long long)q1);
+        if (q1 > q0 && !A.apart_pairs) return icl_fail(ctx, ICL_ERR_ARG, "%s: null apart_pairs", what);
+        const std::string why = ab_bad_arg(A.n[p], A.apart_class ? A.apart_class + rows : nullptr, q1 > q0 ? A.apart_pairs + 2 * q0 : nullptr, q1 - q0);
+        if (!why.empty()) return icl_fail(ctx, ICL_ERR_ARG, "%s: problem %d: %s", what, p, why.c_str());
+        rows += A.n[p];
+    }
+    return ICL_OK;
+}
+
+// The entry points: the argument checks, the lock, the device, wm_run.  dev: E (and C_out) are on the device.
 static int wm_entry(icl_ctx *ctx, bool dev, const char *what, const wm_args &A, const float *E, int64_t e_len, const wm_out &O)
 {
     return no_throw(ctx, what, [&]() -> int {
         ICL_TRY(wm_check_args(ctx, what, A.nprob, E, e_len, A.e_off, A.n, A.d, A.min_size, A.max_size, O.cluster_id, O.rank, O.n_clusters, O.n_merges, O.status));
         if (A.seeded) {
             ICL_TRY(wm_check_seeds(ctx, what, A.nprob, A.n, A.seed_size));
+            if (A.apart) ICL_TRY(wm_check_apart(ctx, what, A));
             if (A.nprob == 0) return ICL_OK;
         }
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -890,6 +987,37 @@ extern "C" int icl_cluster_many_seeded(icl_ctx *ctx, int32_t nprob, const float 
                                        int32_t *merges, int32_t *status, float *C_out)
 {
     return wm_entry(ctx, false, "icl_cluster_many_seeded", wm_args{nprob, e_off, m, d, min_size, max_size, true, seed_size, k_target}, E, e_len,
+                    wm_out{cluster_id, seed_rank, n_clusters, n_merges, merges, status, C_out});
+}
+
+// ---- constrained seeded clustering: keep-apart pairs and classes (DESIGN.md "Constrained seeded clustering") ---------------------------
+static wm_args wm_apart_args(int32_t nprob, const int64_t *e_off, const int32_t *m, const int32_t *d, const int32_t *seed_size, const int32_t *min_size,
+                             const int32_t *max_size, const int32_t *k_target, const int32_t *apart_class, const int64_t *pair_off, const int32_t *apart_pairs)
+{
+    wm_args A{nprob, e_off, m, d, min_size, max_size, true, seed_size, k_target};
+    A.apart = true;
+    A.apart_class = apart_class, A.pair_off = pair_off, A.apart_pairs = apart_pairs;
+    return A;
+}
+
+extern "C" int icl_cluster_many_apart_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *m,
+                                          const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                                          const int32_t *k_target, const int32_t *apart_class, const int64_t *pair_off, const int32_t *apart_pairs,
+                                          int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
+                                          float *d_C_out)
+{
+    return wm_entry(ctx, true, "icl_cluster_many_apart_dev",
+                    wm_apart_args(nprob, e_off, m, d, seed_size, min_size, max_size, k_target, apart_class, pair_off, apart_pairs), d_E, e_len,
+                    wm_out{cluster_id, seed_rank, n_clusters, n_merges, merges, status, d_C_out});
+}
+
+extern "C" int icl_cluster_many_apart(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *m, const int32_t *d,
+                                      const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size, const int32_t *k_target,
+                                      const int32_t *apart_class, const int64_t *pair_off, const int32_t *apart_pairs, int32_t *cluster_id,
+                                      int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, float *C_out)
+{
+    return wm_entry(ctx, false, "icl_cluster_many_apart",
+                    wm_apart_args(nprob, e_off, m, d, seed_size, min_size, max_size, k_target, apart_class, pair_off, apart_pairs), E, e_len,
                     wm_out{cluster_id, seed_rank, n_clusters, n_merges, merges, status, C_out});
 }
 

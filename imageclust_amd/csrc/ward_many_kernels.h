@@ -1,10 +1,18 @@
 // ward_many_kernels.h -- the four kernels of ward_many.hip's one-workgroup routes.  Not a header of its own: ward_many.hip includes it
-// twice, after everything the kernels share.  WM_SEEDED 0: the kernels behind icl_cluster_many[_dev] and icl_cluster_requests[_mem], every
+// three times, after everything the kernels share.  WM_SEEDED 0: the kernels behind icl_cluster_many[_dev] and icl_cluster_requests[_mem], every
 // problem starting from singletons (ward_many_init_kernel, ...).  WM_SEEDED 1: the same text with the start state taken from a wm_seed
 // table, the kernels' last argument (ward_many_init_seeded_kernel, ...): slot t starts as seed t -- size SD[g].size[t], creation id t,
 // centroid row t of E -- a pair whose sizes exceed max_size is banned from the start, and the merge kernels leave the slots' final
 // creation ids in SD[g].fin.  The first inclusion compiles to the code it was before there were seeds (scratch/isa_compare.py).
-#if WM_SEEDED
+// WM_SEEDED 1 with WM_APART 1: the seeded text with a KEEP-APART relation over the live clusters (ward_many_init_apart_kernel, ...,
+// icl_cluster_many_apart; DESIGN.md "Constrained seeded clustering").  The table is wm_apart: sizes and fin as in wm_seed, and the
+// problem's bit rows in the global workspace -- bit u of row t (W words a row) set when the clusters in slots t and u are apart.  A pair
+// whose bit is set holds MaxFloat32 from the start and is never evaluated; a merged cluster inherits the bans of both parents (wm_apart_
+// inherit below).  The first two inclusions compile to the code they were before there was a relation.
+#if WM_APART
+#define WM_KERNEL(name) name##_apart_kernel
+#define WM_SEED_PARAM , const wm_apart *__restrict__ SD
+#elif WM_SEEDED
 #define WM_KERNEL(name) name##_seeded_kernel
 #define WM_SEED_PARAM , const wm_seed *__restrict__ SD
 #else
@@ -27,7 +35,12 @@ __global__ __launch_bounds__(WM_THREADS) void WM_KERNEL(ward_many_init)(const wm
     const int32_t *ssz = SD[blk_prob[blockIdx.x]].size;
     const int si = ssz[i], sj = ssz[j];
     float v = ICL_MAXF; // a pair whose sizes exceed max_size is banned from the start (clustering.go:228-234) and never evaluated
-    if (si + sj <= p.max_size) v = ward_pair_value(p.E + i * p.d, p.E + j * p.d, p.d, si, sj);
+#if WM_APART
+    if (si + sj <= p.max_size && !wm_apart_bit(SD[blk_prob[blockIdx.x]].bits + i * SD[blk_prob[blockIdx.x]].words, (int)j)) // (nor a pair kept apart)
+#else
+    if (si + sj <= p.max_size)
+#endif
+        v = ward_pair_value(p.E + i * p.d, p.E + j * p.d, p.d, si, sj);
 #else
     float v = ICL_MAXF; // max_size < 2: every pair of singletons is banned (clustering.go:228-234) and never read
     if (p.max_size >= 2) v = ward_pair_value(p.E + i * p.d, p.E + j * p.d, p.d, 1, 1); // WardDistance(clusters[i], clusters[j]) :66
@@ -43,6 +56,10 @@ __global__ __launch_bounds__(WM_THREADS) void WM_KERNEL(ward_many_merge)(const w
     const wm_slots S = wm_carve(wm_lds, n, WM_WAVES);
     uint64_t *const rkey = S.rkey;
     int32_t *const rarg = S.rarg, *const sz = S.sz, *const cid = S.cid;
+#if WM_APART
+    uint32_t *const abits = SD[order[blockIdx.x]].bits;
+    const int aw = SD[order[blockIdx.x]].words;
+#endif
     float *tri = p.tri;
     if (p.lds_tri) {
         float *lt = reinterpret_cast<float *>(wm_lds + wm_meta_bytes(n));
@@ -90,6 +107,9 @@ __global__ __launch_bounds__(WM_THREADS) void WM_KERNEL(ward_many_merge)(const w
         __syncthreads();
         // UpdateDistanceMatrix (:76-96): WardDistance(clusters[t], newCluster) for every live t; the owner of row t updates its cache
         const float *cn = p.C + (int64_t)sn * d;
+#if WM_APART
+        wm_apart_or_row<WM_THREADS>(abits, aw, sn, shi); // (row shi is dead: nobody writes it; the step's closing barrier publishes row sn)
+#endif
         uint64_t nk = ~0ull;
         int nr = -1;
         uint32_t stale = 0; // rows of this thread whose cached partner just died
@@ -97,9 +117,16 @@ __global__ __launch_bounds__(WM_THREADS) void WM_KERNEL(ward_many_merge)(const w
             if (t == sn || sz[t] == 0) continue;
             const int st = sz[t];
             float v = ICL_MAXF; // banned: never selected (:228-234), never evaluated
+#if WM_APART
+            const bool okp = !wm_apart_inherit(abits + (int64_t)t * aw, shi, slo) && st + snew <= maxs; // (the owner of row t: its bit for sn)
+            if (okp) v = ward_pair_value(cent(t), cn, d, st, snew);
+            at(t, sn) = v;
+            const uint64_t k = (okp && v < ICL_MAXF) ? wm_key(v, cid[t], cnew) : ~0ull;
+#else
             if (st + snew <= maxs) v = ward_pair_value(cent(t), cn, d, st, snew);
             at(t, sn) = v;
             const uint64_t k = (st + snew <= maxs && v < ICL_MAXF) ? wm_key(v, cid[t], cnew) : ~0ull;
+#endif
             if (k < nk) {
                 nk = k;
                 nr = t;
@@ -199,7 +226,12 @@ __global__ __launch_bounds__(256) void WM_KERNEL(ward_many_mid_init)(const wm_pr
 #if WM_SEEDED
             const int32_t *ssz = SD[blk_prob[blockIdx.x]].size; // a pair whose sizes exceed max_size is banned from the start
             const int si = ssz[i], sj = ssz[j];
-            const float v = (i != j && si + sj <= p.max_size) ? ward_scale(s[a][b], si, sj) : ICL_MAXF;
+#if WM_APART
+            const bool okp = i != j && si + sj <= p.max_size && !wm_apart_bit(SD[blk_prob[blockIdx.x]].bits + (int64_t)i * SD[blk_prob[blockIdx.x]].words, j);
+#else
+            const bool okp = i != j && si + sj <= p.max_size;
+#endif
+            const float v = okp ? ward_scale(s[a][b], si, sj) : ICL_MAXF;
 #else
             const float v = (p.max_size >= 2 && i != j) ? ward_scale(s[a][b], 1, 1) : ICL_MAXF;
 #endif
@@ -222,6 +254,10 @@ __global__ __launch_bounds__(WMM_THREADS) void WM_KERNEL(ward_many_mid_merge)(co
     uint16_t *ev = reinterpret_cast<uint16_t *>(cnt + 2);
     uint16_t *stl = ev + n;
     float *M = p.tri; // entry (a, b) at a n + b, both orders written
+#if WM_APART
+    uint32_t *const abits = SD[order[blockIdx.x]].bits;
+    const int aw = SD[order[blockIdx.x]].words;
+#endif
     for (int t = tid; t < n; t += WMM_THREADS) {
 #if WM_SEEDED
         sz[t] = SD[order[blockIdx.x]].size[t];
@@ -278,10 +314,17 @@ __global__ __launch_bounds__(WMM_THREADS) void WM_KERNEL(ward_many_mid_merge)(co
         // others go on the list of rows to evaluate; rows whose cached partner just died go on the list of rows to rescan.
         const float *cn = p.C + (int64_t)sn * d;
         float *Mn = M + (int64_t)sn * n;
+#if WM_APART
+        wm_apart_or_row<WMM_THREADS>(abits, aw, sn, shi); // (row shi is dead: nobody writes it; the step's closing barrier publishes row sn)
+#endif
         for (int t0 = 0; t0 < n; t0 += WMM_THREADS) {
             const int t = t0 + tid;
             const bool live = t < n && t != sn && sz[t] != 0;
+#if WM_APART
+            const bool evalp = live && !wm_apart_inherit(abits + (int64_t)t * aw, shi, slo) && sz[t] + snew <= maxs; // (the owner of row t: its bit for sn)
+#else
             const bool evalp = live && sz[t] + snew <= maxs;
+#endif
             if (live && !evalp) {
                 M[(int64_t)t * n + sn] = ICL_MAXF;
                 Mn[t] = ICL_MAXF;

@@ -394,6 +394,31 @@ int icl_cluster_many_seeded_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, i
                                 const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
                                 const int32_t *k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges,
                                 int32_t *merges, int32_t *status, float *d_C_out);
+/* ---- constrained seeded clustering: keep-apart pairs and anchored clusters (DESIGN.md "Constrained seeded clustering") ----
+ * The seeded problem of icl_cluster_many_seeded, unchanged, plus a symmetric relation B, "apart", over the clusters.  Per problem:
+ * apart_class[seed_off(p) + i] (NULL: all 0), one int per seed, 0 meaning none -- two different seeds of one non-zero class are apart; and
+ * the pairs [pair_off[p], pair_off[p + 1]) of apart_pairs, two seed indices of the problem each, either order, duplicates allowed (pair_off
+ * and apart_pairs both NULL: no pairs).  At the start B holds exactly these pairs; every pair in B holds MaxFloat32 in the matrix and is
+ * never evaluated, beside the frozen and the size rule (a pair that names a frozen seed changes nothing).  When a and b merge into c,
+ * B(c, x) = B(a, x) or B(b, x) for every other cluster x: a cluster that swallowed image A still refuses image B.  Where B(c, x) holds, x
+ * is frozen or the size sum exceeds max_size[p], the new entry is MaxFloat32 and is not evaluated; elsewhere it is WardDistance(x, c) as
+ * in the seeded call.  Everything else is the seeded call's: the first strict minimum in row-major order, the merge rule, creation ids,
+ * the log, k, the final list, the drop rule, C_out, and the loop ending early for want of pairs, n_merges[p] then below m[p] - k.
+ * Consequences: with apart_class all 0 (or NULL) and no pairs the results are icl_cluster_many_seeded's, bit for bit; and a run cut
+ * after t merges and resumed -- the surviving clusters as seeds, each one's inherited bans as pairs, k_target as before -- is the same run.
+ * The relation lives in the workspace as bit rows, m[p] x ceil(m[p] / 32) words per problem.  ICL_ERR_ARG, nothing written: a pair index
+ * outside [0, m[p]), a pair (i, i), a negative class, a negative or decreasing pair offset, apart_pairs NULL where a problem has pairs or
+ * given without pair_off.  status[p]: the seeded call's, ICL_ERR_UNSUPPORTED above 2048 seeds included.  The constraint arrays are host
+ * memory in both forms.  The return code, "nothing is written on ICL_ERR_ARG" and icl_last_many_stats are icl_cluster_many_seeded's. */
+int icl_cluster_many_apart(icl_ctx *ctx, int32_t nprob, const float *E, int64_t e_len, const int64_t *e_off, const int32_t *m, const int32_t *d,
+                           const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size, const int32_t *k_target,
+                           const int32_t *apart_class, const int64_t *pair_off, const int32_t *apart_pairs, int32_t *cluster_id,
+                           int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status, float *C_out);
+int icl_cluster_many_apart_dev(icl_ctx *ctx, int32_t nprob, const float *d_E, int64_t e_len, const int64_t *e_off, const int32_t *m,
+                               const int32_t *d, const int32_t *seed_size, const int32_t *min_size, const int32_t *max_size,
+                               const int32_t *k_target, const int32_t *apart_class, const int64_t *pair_off, const int32_t *apart_pairs,
+                               int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, int32_t *n_merges, int32_t *merges, int32_t *status,
+                               float *d_C_out);
 /* ONE seeded problem on the large-N engine (ward.hip), with no cap on the number of seeds other than memory: the semantics above for a single
  * problem of m seeds -- C holds the m centroid rows of d floats, seed_size[m] as above, k = k_target when it is above 0 --, the same creation
  * ids, final list, drop rule and C_out (may be NULL; m x d floats, host memory, device memory for _dev).  The call runs the engine's EXACT

@@ -35,7 +35,9 @@ def kernels(path):
         # block labels carry the function's emission index (.LBB<index>_<block>), and so do the loop comments that name them (BB<index>_<block>):
         # drop the index, keep everything else
         lines[a] = re.sub(r":\s+;", ": ;", lines[a])  # (the comment behind the label is aligned to a column: a longer name moves it)
-        out[name] = (re.sub(r"\bBB\d+_", "BB_", re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b]))), desc)
+        # (... and the comment behind a block label is aligned to a column too: an index of two digits moves it)
+        text = re.sub(r"(?m)^(\.LBB_\d+:)\s+;", r"\1 ;", re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[a:b])))
+        out[name] = (re.sub(r"\bBB\d+_", "BB_", text), desc)
     return out
 
 
