@@ -450,6 +450,32 @@ func DuplicatePairs(embeddings [][]float32, ids []string, threshold float32) ([]
 	return out, nil
 }
 
+// LibraryDuplicate is one pair (new image, held image) whose WardDistance as singletons is at most the threshold.
+type LibraryDuplicate struct {
+	New, Held string
+	Value     float32
+}
+
+// DuplicatesOf lists EVERY pair (new image, held image) whose WardDistance as singletons is at most threshold (iclengine.PairsBetween ->
+// icl_pairs_between: exact values, no cap on an image's partners, no distance matrix, the held images never compared with each other),
+// ordered by the new image's position and then by the held image's.
+func DuplicatesOf(newEmbeddings [][]float32, newIDs []string, embeddings [][]float32, ids []string, threshold float32) ([]LibraryDuplicate, error) {
+	if len(newEmbeddings) != len(newIDs) || len(embeddings) != len(ids) {
+		return nil, fmt.Errorf("%d embeddings for %d new ids, %d for %d held ids", len(newEmbeddings), len(newIDs), len(embeddings), len(ids))
+	}
+	rowPtr, col, val, err := iclengine.PairsBetween(newEmbeddings, nil, embeddings, nil, threshold, nil)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]LibraryDuplicate, 0, len(col))
+	for i := range newIDs {
+		for p := rowPtr[i]; p < rowPtr[i+1]; p++ {
+			out = append(out, LibraryDuplicate{New: newIDs[i], Held: ids[col[p]], Value: val[p]})
+		}
+	}
+	return out, nil
+}
+
 // DuplicateGroups returns the connected components of DuplicatePairs' graph that have at least two members (iclengine.PairGroups ->
 // icl_pair_groups): members in position order, groups ordered by their first member.
 func DuplicateGroups(embeddings [][]float32, ids []string, threshold float32) ([][]string, error) {

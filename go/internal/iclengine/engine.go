@@ -507,6 +507,57 @@ func PairsWithin(rows [][]float32, sizes []int32, threshold float32) (rowPtr []i
 	return rowPtr, col[:t], val[:t], nil
 }
 
+// PairsBetween is icl_pairs_between: EVERY pair (row i of rows, row j of library) whose WardDistance (qSizes[i] and lSizes[j] items; nil:
+// all 1) is at most threshold, Nearest's values bit for bit, as a CSR list over the rows: col[rowPtr[i]:rowPtr[i+1]] are row i's library
+// partners in ascending j, val their values.  exclude[i] (nil: none; -1: none) is left out of row i: rows that are library rows pass
+// their own index.  No cap on a row's partners, no max-size ban and no distance matrix.  The size query and the call proper are both
+// made here.
+func PairsBetween(rows [][]float32, qSizes []int32, library [][]float32, lSizes []int32, threshold float32, exclude []int64) (rowPtr []int64, col []int32, val []float32, err error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, nil, nil, e
+	}
+	nq, n, d := len(rows), len(library), 0
+	if nq > 0 {
+		d = len(rows[0])
+	}
+	if (qSizes != nil && len(qSizes) != nq) || (lSizes != nil && len(lSizes) != n) || (exclude != nil && len(exclude) != nq) {
+		return nil, nil, nil, fmt.Errorf("sizes or exclude do not match %d rows and %d library rows", nq, n)
+	}
+	rowPtr = make([]int64, nq+1)
+	if nq == 0 || n == 0 { // an empty side, no row length to pass: the empty list, as the Python mirror returns it
+		return rowPtr, nil, nil, nil
+	}
+	flatQ, flatL := flatRows(rows, d), flatRows(library, d)
+	i32 := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	var ex *C.int64_t
+	if len(exclude) > 0 {
+		ex = (*C.int64_t)(unsafe.Pointer(&exclude[0]))
+	}
+	total := C.int64_t(-1)
+	call := func(c *C.int32_t, v *C.float, cap int64) C.int {
+		return C.icl_pairs_between((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flatQ[0])), i32(qSizes), C.int64_t(nq),
+			(*C.float)(unsafe.Pointer(&flatL[0])), i32(lSizes), C.int64_t(n), C.int32_t(d), C.float(threshold), ex,
+			(*C.int64_t)(unsafe.Pointer(&rowPtr[0])), c, v, C.int64_t(cap), &total)
+	}
+	if rc := call(nil, nil, 0); rc != C.ICL_OK {
+		return nil, nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	t := int64(total)
+	col, val = make([]int32, t+1), make([]float32, t+1)
+	if t > 0 {
+		if rc := call((*C.int32_t)(unsafe.Pointer(&col[0])), (*C.float)(unsafe.Pointer(&val[0])), t); rc != C.ICL_OK {
+			return nil, nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+		}
+	}
+	return rowPtr, col[:t], val[:t], nil
+}
+
 // PairGroups is icl_pair_groups (host only): the connected components of the pair graph of a CSR list: group[i] is the smallest index
 // of i's component, nGroups the number of components with at least two members.
 func PairGroups(rowPtr []int64, col []int32) (group []int32, nGroups int, err error) {

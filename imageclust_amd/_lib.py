@@ -159,6 +159,10 @@ SYMBOLS = [
     ("icl_pairs_within_from_matrix", _int, [_vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
     ("icl_pair_groups", _int, [_i64, _vp, _vp, _vp, _pi64]),
     ("icl_last_pairs_stats", _int, [_vp, _pi64]),
+    ("icl_pairs_between", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_pairs_between_dev", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_pairs_between_from_matrix", _int, [_vp, _i64, _i64, _i64, C.c_float, _vp, _vp, _vp, _vp, _i64, _pi64]),
+    ("icl_last_pairs_between_stats", _int, [_vp, _pi64]),
     ("icl_set_many_options", _int, [_vp, _int]),
     ("icl_last_many_stats", _int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     ("icl_requests_layout", _int, [_i32, _vp, _vp, _int, _vp, _vp, _pi64]),
@@ -366,6 +370,24 @@ def pairs_within_from_matrix(D, threshold, n=None):
     L = load()
     return _pairs_two_calls(n, lambda rp, c, v, cap, tot: L.icl_pairs_within_from_matrix(D.ctypes.data if D.size else None, n, ld, float(threshold),
                                                                                         rp, c, v, cap, C.byref(tot)), "icl_pairs_within_from_matrix")
+
+
+def pairs_between_from_matrix(D, threshold, exclude=None, n=None):
+    """icl_pairs_between_from_matrix (host only, no GPU): Context.pairs_between's rule and layout applied to values the caller holds: D
+    is nq x ld float32, n (default ld) columns of each row are pairs, exclude[i] (None / -1: none) is left out of row i ->
+    (row_ptr int64[nq + 1], col, val).  Raises ICLError(ICL_ERR_ARG)."""
+    D = np.asarray(D, np.float32)
+    if D.ndim != 2:
+        raise ValueError("D must be 2-D")
+    if not D.flags.c_contiguous:
+        D = np.ascontiguousarray(D)
+    nq, ld = D.shape
+    n = ld if n is None else int(n)
+    ex = _nearest_exclude(nq, exclude)
+    L = load()
+    return _pairs_two_calls(nq, lambda rp, c, v, cap, tot: L.icl_pairs_between_from_matrix(D.ctypes.data if D.size else None, nq, n, ld, float(threshold),
+                                                                                          _ptr(ex), rp, c, v, cap, C.byref(tot)),
+                            "icl_pairs_between_from_matrix")
 
 
 def pair_groups(row_ptr, col):
@@ -1097,9 +1119,52 @@ class Context:
 
         return self._pairs_calls(n, cap, call)
 
-    def _pairs_calls(self, n, cap, call):
+    def pairs_between(self, Q, L, threshold, q_size=None, l_size=None, exclude=None, cap=None):
+        """icl_pairs_between: EVERY pair (row i of Q, row j of L) whose WardDistance (sizes q_size / l_size, None: all 1) is at most
+        threshold, nearest()'s values bit for bit, as a CSR list over the queries -> (row_ptr int64[nq + 1], col int32[total],
+        val float32[total]): query i's library partners, ascending in j, are col[row_ptr[i]:row_ptr[i + 1]].  exclude[i] (None / -1: none)
+        is left out of row i; NaN values are never listed; there is no cap on a query's partners and no max_size ban.  The size query
+        and the call proper are both made here; cap, a guess of the total, saves the query when it is large enough."""
+        Qm, Lm = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(L, np.float32)
+        if Qm.ndim != 2 or Lm.ndim != 2 or Qm.shape[1] != Lm.shape[1]:
+            raise ValueError("Q and L must be 2-D with rows of one length, got %s and %s" % (Qm.shape, Lm.shape))
+        (nq, d), n = Qm.shape, Lm.shape[0]
+        qs, ls, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, l_size, "l_size"), _nearest_exclude(nq, exclude)
+        return self._pairs_calls(nq, cap, lambda rp, c, v, cp, tot: self.L.icl_pairs_between(
+            self.h, _ptr(Qm), _ptr(qs), nq, _ptr(Lm), _ptr(ls), n, d, float(threshold), _ptr(ex), rp, c, v, cp, C.byref(tot)), "icl_pairs_between")
+
+    def pairs_between_dev(self, d_Q, nq, d_L, n, d, threshold, q_size=None, l_size=None, exclude=None, cap=None):
+        """icl_pairs_between_dev on rows that are on the device already (d_Q: nq x d floats, d_L: n x d) -> (row_ptr, col, val) on the
+        host, as pairs_between.  col and val live on the device during the call and are downloaded here."""
+        qs, ls, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, l_size, "l_size"), _nearest_exclude(nq, exclude)
+
+        def call(rp, c, v, cp, tot):  # c / v: the host arrays of cp entries; the device call gets device buffers of the same length
+            bufs = [self.malloc(cp * 4), self.malloc(cp * 4)] if cp else [None, None]
+            try:
+                rc = self.L.icl_pairs_between_dev(self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_L), _ptr(ls), n, d, float(threshold), _ptr(ex), rp,
+                                                  bufs[0], bufs[1], cp, C.byref(tot))
+                if rc == ICL_OK and 0 < tot.value <= cp:
+                    self.sync()
+                    check(self.h, self.L.icl_memcpy_d2h(self.h, c, _vp(bufs[0]), tot.value * 4))
+                    check(self.h, self.L.icl_memcpy_d2h(self.h, v, _vp(bufs[1]), tot.value * 4))
+                return rc
+            finally:
+                for p in bufs:
+                    if p is not None:
+                        self.free(p)
+
+        return self._pairs_calls(nq, cap, call, "icl_pairs_between_dev")
+
+    def last_pairs_between_stats(self):
+        """The last pairs_between[_dev]: column splits used, 128 x 128 tiles the count pass ran, tiles with a hit (the fill pass's), pairs
+        evaluated in both passes, workspace bytes."""
+        info = (C.c_int64 * 5)()
+        check(self.h, self.L.icl_last_pairs_between_stats(self.h, info))
+        return {"splits": info[0], "tiles": info[1], "hit_tiles": info[2], "pairs": info[3], "workspace_bytes": info[4]}
+
+    def _pairs_calls(self, n, cap, call, what="icl_pairs_within"):
         try:
-            return _pairs_two_calls(n, call, "icl_pairs_within", cap)
+            return _pairs_two_calls(n, call, what, cap)
         except ICLError as e:
             msg = self.L.icl_last_error(self.h)
             raise ICLError(e.code, msg.decode() if msg else "") from None

@@ -280,6 +280,35 @@ def DuplicateGroups(embeddings, ids, threshold: float, ctx: Optional[_lib.Contex
     return [m for _, m in sorted(members.items()) if len(m) >= 2]
 
 
+def _rows_of(embeddings, ids):
+    E = np.asarray(embeddings, np.float32)
+    if E.ndim != 2:
+        E = E.reshape(len(ids), -1)
+    if len(E) != len(ids):
+        raise ValueError("%d embeddings for %d ids" % (len(E), len(ids)))
+    return E
+
+
+def _between_csr(Q, L, threshold, ctx, engine):
+    """The complete pair list of the rows of Q against the rows of L (icl_pairs_between; `engine(Q, L, threshold) -> (row_ptr, col, val)`
+    stands in for the GPU call in tests)."""
+    if len(Q) == 0 or len(L) == 0:
+        return np.zeros(len(Q) + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32)
+    if engine is not None:
+        return engine(Q, L, threshold)
+    return (ctx or default_context()).pairs_between(Q, L, threshold)
+
+
+def DuplicatesOf(new_embeddings, new_ids, embeddings, ids, threshold: float, ctx: Optional[_lib.Context] = None,
+                 engine=None) -> List[Tuple[str, str, float]]:
+    """EVERY pair (new image, held image) whose WardDistance as singletons is at most threshold (icl_pairs_between: exact values, no cap
+    on an image's partners, no distance matrix, the held images never compared with each other) -> [(new_id, id, value), ...], ordered
+    by the new image's position and then by the held image's.  NaN values are never reported."""
+    Q, L = _rows_of(new_embeddings, new_ids), _rows_of(embeddings, ids)
+    row_ptr, col, val = _between_csr(Q, L, threshold, ctx, engine)
+    return [(new_ids[i], ids[int(col[p])], float(val[p])) for i in range(len(Q)) for p in range(int(row_ptr[i]), int(row_ptr[i + 1]))]
+
+
 @dataclass
 class HeldCluster:
     """A cluster a Clustering state holds between calls: member ids in the reference's order, the centroid as the loop left it, the
@@ -305,11 +334,14 @@ class Clustering:
     `engine` replaces the GPU call in tests: engine(C, seed_size, minSize, maxSize, k_target) -> (cluster_id, seed_rank, n_clusters,
     status, merges, C_out), called with two more arguments, (..., apart_class, apart_pairs), only when a constraint exists; `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
     `fit_engine` for fit(), representatives() and misfits(): fit_engine(Q, cluster_of, C, k_alt, q_size, c_size, max_size) -> the dict of
-    Context.cluster_fit."""
+    Context.cluster_fit; `between_engine` and `pairs_engine` for duplicates_of() and add(skip_duplicates=): between_engine(Q, L, threshold)
+    and pairs_engine(E, threshold) -> (row_ptr, col, val), as Context.pairs_between and Context.pairs_within."""
 
-    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None, fit_engine=None):
+    def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None, fit_engine=None,
+                 between_engine=None, pairs_engine=None):
         self.minSize, self.maxSize = int(minSize), int(maxSize)
         self.ctx, self.engine, self.nearest_engine, self.fit_engine = ctx, engine, nearest_engine, fit_engine
+        self.between_engine, self.pairs_engine = between_engine, pairs_engine
         self.clusters: List[HeldCluster] = []
         self.embeddings: Dict[str, np.ndarray] = {}
         self.ok = True
@@ -318,26 +350,64 @@ class Clustering:
 
     @classmethod
     def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None,
-              fit_engine=None) -> "Clustering":
+              fit_engine=None, between_engine=None, pairs_engine=None) -> "Clustering":
         """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
         False (and every image is still a singleton) when the constraints cannot be met."""
-        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine)
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine)
         state.add(embeddings, ids)
         state.recluster()
         return state
 
-    def add(self, embeddings, ids):
-        """New images, each a singleton seed behind the clusters held so far."""
-        E = np.asarray(embeddings, np.float32)
-        if E.ndim != 2:
-            E = E.reshape(len(ids), -1)
-        if len(E) != len(ids):
-            raise ValueError("%d embeddings for %d ids" % (len(E), len(ids)))
+    def _duplicate_lists(self, E, threshold):
+        """Per row of E: ([(held position, value), ...] over self.embeddings in the order they were added -- icl_pairs_between --,
+        [(earlier row of E, value), ...] -- icl_pairs_within on E, whose row i lists exactly the j < i), and the held ids by position."""
+        held = list(self.embeddings)
+        if len(E) == 0:
+            return [], held
+        L = np.stack([self.embeddings[k] for k in held]).astype(np.float32) if held else np.zeros((0, E.shape[1]), np.float32)
+        hp, hc, hv = _between_csr(E, L, threshold, self.ctx, self.between_engine)
+        if self.pairs_engine is not None:
+            bp, bc, bv = self.pairs_engine(E, threshold)
+        else:
+            bp, bc, bv = (self.ctx or default_context()).pairs_within(E, threshold)
+        return [([(int(hc[p]), float(hv[p])) for p in range(int(hp[i]), int(hp[i + 1]))],
+                 [(int(bc[p]), float(bv[p])) for p in range(int(bp[i]), int(bp[i + 1]))]) for i in range(len(E))], held
+
+    def duplicates_of(self, embeddings, ids, threshold: float) -> List[List[Tuple[str, float]]]:
+        """For each incoming image, every image it duplicates (WardDistance as singletons at most threshold, exact and complete): its
+        partners among all held images, in the order they were added (icl_pairs_between: the held images are never compared with each
+        other), then its partners at earlier positions of the same batch (icl_pairs_within on the batch) -> one list of (id, value) per
+        incoming image.  The state is not changed."""
+        ids = list(ids)
+        lists, held = self._duplicate_lists(_rows_of(embeddings, ids), threshold)
+        return [[(held[j], v) for j, v in h] + [(ids[j], v) for j, v in b] for h, b in lists]
+
+    def add(self, embeddings, ids, skip_duplicates: Optional[float] = None):
+        """New images, each a singleton seed behind the clusters held so far.  With skip_duplicates = a threshold, an incoming image that
+        has any partner under it (duplicates_of) among the held images or at an earlier position of the batch -- skipped or not -- is not
+        added, and the method returns [(skipped id, partner id, value), ...] in batch order: the partner named is the held partner added
+        first if there is one, otherwise the earliest batch partner.  With None nothing is compared and nothing is returned."""
+        E = _rows_of(embeddings, ids)
+        skipped = []
+        if skip_duplicates is not None:
+            ids = list(ids)
+            clash = [k for k in ids if k in self.embeddings]
+            if clash or len(set(ids)) != len(ids):
+                raise ValueError("id %r is already clustered" % (clash[0],) if clash else "an id is listed twice")
+            lists, held = self._duplicate_lists(E, skip_duplicates)
+            keep = []
+            for i, (h, b) in enumerate(lists):
+                if h or b:
+                    skipped.append((ids[i], held[h[0][0]], h[0][1]) if h else (ids[i], ids[b[0][0]], b[0][1]))
+                else:
+                    keep.append(i)
+            E, ids = E[keep], [ids[i] for i in keep]
         for row, key in zip(E, ids):
             if key in self.embeddings:
                 raise ValueError("id %r is already clustered" % (key,))
             self.embeddings[key] = np.array(row, np.float32, copy=True)
             self.clusters.append(HeldCluster([key], self.embeddings[key].copy()))
+        return skipped if skip_duplicates is not None else None
 
     def _holding(self, keys) -> List[int]:
         where = {k: i for i, c in enumerate(self.clusters) for k in c.Members}

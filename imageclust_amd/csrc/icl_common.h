@@ -177,6 +177,8 @@ struct icl_ctx {
     int64_t pairs_stats[4] = {0, 0, 0, 0}; // last icl_pairs_within[_dev]: tiles run in pass 1, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_stats)
     icl_dev_grow fit;                    // device copies of the host arrays, partial lists and keys of icl_cluster_fit / icl_ward_values_at (fit.hip; as many)
     int64_t fit_stats[4] = {0, 0, 0, 0}; // last icl_cluster_fit[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_fit_stats)
+    icl_dev_grow between;                // device copies of sizes / exclude, segment counts, tile flags and seg_ptr of icl_pairs_between (pairs_between.hip; as many)
+    int64_t between_stats[5] = {0, 0, 0, 0, 0}; // last icl_pairs_between[_dev]: splits used, tiles run in the count pass, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_between_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };
 

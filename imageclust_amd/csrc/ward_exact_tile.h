@@ -1,11 +1,13 @@
 // ward_exact_tile.h -- the bit-exact Ward distance tile, stated once: 128 x 128 pairs per workgroup of 256 threads, k-chunks of both
 // operands staged in LDS, an 8 x 8 block of accumulators per thread, each accumulator one strictly sequential chain of
 // fl(fl(a_k - b_k)^2) (clustering.go:137-141, 152-155).  ward_dist_exact_kernel (ward.hip) and the two passes of pairs.hip run it on
-// the lower triangle of one operand, band_select_kernel (band_select.h: nearest.hip, fit.hip) on a rectangle of two; each keeps its own
-// epilogue.  Every "bit-equal to the oracle" claim of the distance stage rests on the operation order below.
+// the lower triangle of one operand, band_select_kernel (band_select.h: nearest.hip, fit.hip) and pairs_between_kernel
+// (pairs_between.hip) on a rectangle of two; each keeps its own epilogue.  Every "bit-equal to the oracle" claim of the distance stage
+// rests on the operation order below.
 //
 // Only units compiled with -ffp-contract=off -fno-slp-vectorize may include this header (the Makefile's rules of ward.o, nearest.o,
-// pairs.o and fit.o): every difference, product and sum is rounded on its own, and the packed pairs below are the only packing wanted.
+// pairs.o, fit.o and pairs_between.o): every difference, product and sum is rounded on its own, and the packed pairs below are the only
+// packing wanted.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

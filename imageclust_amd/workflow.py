@@ -75,12 +75,14 @@ def RunUploaded(appCtx: AppContext, requests: Sequence[UploadedRequest], prec: i
 
 
 def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int = _lib.PREC_FP32,
-            threads: int = 0) -> Tuple[Optional[Dict[int, List[str]]], bool]:
+            threads: int = 0, dedupe_threshold: Optional[float] = None):
     """More images for a request that has been answered: newRequestImages = (paths, ids, labels_per_image, labelSet) with the
     labelSet of the request `state` came from (the combined rows must be as wide as the state's).  Only the new images are embedded
     and combined (createEmbeddings, workflow.go:149-185); they join the state as singletons and the loop goes on from the clusters
     held (Clustering.add, .recluster) -> (state.as_map(), True), or (None, False) when the constraints cannot be met or a file cannot
-    be read (workflow.go:162-181 fails the request; the state is as it was then)."""
+    be read (workflow.go:162-181 fails the request; the state is as it was then).  With dedupe_threshold, a new image that duplicates a
+    held image or an earlier new image under that threshold does not join (Clustering.add(skip_duplicates=)), and the result has a
+    third entry, the list [(skipped id, partner id, value), ...] (empty where the call fails before the images are compared)."""
     if appCtx.Net is None or appCtx.Net.Empty():
         raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunMore: no model loaded")
     paths, ids, labels_per_image, labelSet = newRequestImages
@@ -89,13 +91,14 @@ def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int =
     ctx = appCtx.Net.ctx
     E, status = ctx.embed_files([str(p) for p in paths], appCtx.Head, prec, threads)
     if (np.asarray(status) != _lib.ICL_OK).any():
-        return None, False
+        return (None, False) if dedupe_threshold is None else (None, False, [])
     lab = np.zeros((len(paths), len(labelSet)), np.float32)
     for i, labels in enumerate(labels_per_image):
         for col in LabelIndices(labels, labelSet):
             if 0 <= col < len(labelSet):
                 lab[i, col] = 1.0  # GenerateLabelVector (embeddings.go:166-174)
-    state.add(np.concatenate([E, lab], axis=1), list(ids))  # CombineEmbeddings (:177-183)
     if state.ctx is None and state.engine is None:
         state.ctx = ctx
-    return (state.as_map(), True) if state.recluster() else (None, False)
+    skipped = state.add(np.concatenate([E, lab], axis=1), list(ids), skip_duplicates=dedupe_threshold)  # CombineEmbeddings (:177-183)
+    out = (state.as_map(), True) if state.recluster() else (None, False)
+    return out if dedupe_threshold is None else out + (skipped,)

@@ -563,6 +563,50 @@ int icl_pair_groups(int64_t n, const int64_t *row_ptr, const int32_t *col, int32
 /* The last icl_pairs_within[_dev] of the context: info = tiles run in the count pass, tiles with a hit, pairs j < i < n evaluated (both
  * passes; the fill pass counts when it ran), workspace bytes (all 0 after a call with n <= 1). */
 int icl_last_pairs_stats(icl_ctx *ctx, int64_t info[4]);
+/* ---- duplicates against a library: every pair (query row, library row) whose WardDistance is at most a threshold, exact and complete, no
+ * distance matrix, no cap on a query's partners (DESIGN.md "Duplicates against a library") ----
+ * Q holds nq query rows and L n library rows of d floats; q_size[nq] / l_size[n] are the rows' item counts (NULL: all 1).
+ * VALUE of pair (i, j): WardDistance (clustering.go:136-157) of q_size[i] items at Q[i] and l_size[j] items at L[j], icl_nearest's value bit for
+ * bit: the exact tile's sum, then (float(sa*sb) / float(sa+sb)) * s.
+ * PAIR SET: every pair with j != exclude[i] and value <= threshold as an fp32 comparison, whatever the sizes (there is no max_size ban: a
+ * duplicate is a duplicate).  exclude may be NULL, -1 means none; queries that are themselves library rows pass their own row.  A NaN value
+ * is never listed; a threshold of -0.0f admits zero values; +Inf admits everything that is not NaN.  A NaN threshold is ICL_ERR_ARG.
+ * ORDER AND LAYOUT (CSR over the queries): col[row_ptr[i] .. row_ptr[i + 1]) are query i's library partners in ascending j and val holds their
+ * values at the same places; row_ptr has nq + 1 entries, row_ptr[0] = 0 and *total = row_ptr[nq].  The result does not depend on split
+ * count, tile order or the order in which workgroups finish.
+ * CAPACITY: as icl_pairs_within.  col and val hold cap entries each; row_ptr and *total are always complete and exact; *total > cap returns
+ * ICL_ERR_ARG with those two filled and col / val unspecified (a bad argument leaves *total untouched); col == NULL && val == NULL && cap == 0
+ * is the size query and returns ICL_OK.
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context, row_ptr, total; Q and L when nq > 0 and n > 0; one
+ * of col / val without the other, or both NULL with cap > 0), d < 1, negative nq or n, n >= 2^31, a size <= 0, an exclude entry outside
+ * [-1, n), a NaN threshold, cap < 0, or a grid (bands of 128 queries x column splits) that does not fit one launch; nq == 0 or n == 0 is ICL_OK
+ * with *total = 0; ICL_ERR_UNSUPPORTED on a context that is a replica of a group; ICL_ERR_NOMEM when the workspace, or in the host form the
+ * device copies of Q, L, col and val, do not fit.
+ * icl_pairs_between takes host memory throughout: it uploads, runs the _dev body and downloads.  icl_pairs_between_dev takes Q, L, col and val
+ * on the context's device (col and val are written on the context's stream; Q and L 16-byte aligned with d % 4 == 0 take the wide loads,
+ * anything else the scalar loads, with equal results); q_size, l_size, exclude and row_ptr stay in host memory, and row_ptr and *total are
+ * final at return.
+ * GEOMETRY AND COST: icl_nearest's band walk for both passes.  A workgroup owns a band of 128 queries and a contiguous range of the library's
+ * 128-column tiles; few bands against a large library are split over several workgroups per band (icl_set_nearest_options' column_splits
+ * applies here too; same results for every count).  A count pass evaluates every tile once and stores one count per (query, split) and one
+ * flag per tile, each with a single writer (no atomics on global memory); the host takes the prefix; a fill pass, launched for the (band,
+ * split) pairs that counted a hit, evaluates the flagged tiles a second time and places each hit by arithmetic alone.  With rare duplicates
+ * the second pass is a negligible share; with threshold = +Inf it is the whole rectangle twice.
+ * The workspace is the device copies of the three host arrays, 4 nq splits bytes of counts, 8 (nq splits + 1) of segment starts, one byte
+ * per tile and 4 bytes per workgroup. */
+int icl_pairs_between(icl_ctx *ctx, const float *Q, const int32_t *q_size, int64_t nq, const float *L, const int32_t *l_size, int64_t n, int32_t d,
+                      float threshold, const int64_t *exclude, int64_t *row_ptr, int32_t *col, float *val, int64_t cap, int64_t *total);
+int icl_pairs_between_dev(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_L, const int32_t *l_size, int64_t n,
+                          int32_t d, float threshold, const int64_t *exclude, int64_t *row_ptr, int32_t *d_col, float *d_val, int64_t cap,
+                          int64_t *total);
+/* The same pair rule, layout and capacity convention applied to values the caller already holds (host only: no context, no GPU), e.g. a block
+ * of icl_ward_distance_matrix: D[i * ld + j] is pair (i, j)'s value, used as given.  The comparison is the code the device runs
+ * (pairs_select.h).  ICL_ERR_ARG, with nothing written, as above (D is needed when nq > 0 and n > 0) and for ld < n. */
+int icl_pairs_between_from_matrix(const float *D, int64_t nq, int64_t n, int64_t ld, float threshold, const int64_t *exclude, int64_t *row_ptr,
+                                  int32_t *col, float *val, int64_t cap, int64_t *total);
+/* The last icl_pairs_between[_dev] of the context: info = column splits used, tiles run in the count pass, tiles with a hit, pairs evaluated
+ * (both passes; the fill pass counts when it ran), workspace bytes (all 0 after a call with nq == 0 or n == 0). */
+int icl_last_pairs_between_stats(icl_ctx *ctx, int64_t info[5]);
 /* ---- a queue of requests, files to cluster ids: replaces workflow.Run (workflow.go:84-94) for nreq requests in ONE call ----
  * Request r is n[r] image files with labels.  Every image gets its embedding row (GetImageEmbedding; head, prec as icl_embed_files), a one-hot
  * vector over the request's label set is appended (GenerateLabelVector + CombineEmbeddings, embeddings.go:166-183: d[r] = head + n_labels[r]
