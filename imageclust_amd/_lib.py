@@ -355,39 +355,40 @@ def _pairs_two_calls(n, call, what, cap=None):
         cap = total.value  # the size query's answer, or a hint that was too small
 
 
-def pairs_within_from_matrix(D, threshold, n=None):
-    """icl_pairs_within_from_matrix (host only, no GPU): Context.pairs_within's rule and layout applied to values the caller holds: the
-    strict lower triangle of the first n (default: all) rows and columns of D -> (row_ptr, col, val).  Raises ICLError(ICL_ERR_ARG)."""
+def _pairs_matrix(D):
+    """The value matrix of a *_from_matrix call -> (C-contiguous 2-D float32 array, its address or None when it is empty)."""
     D = np.asarray(D, np.float32)
     if D.ndim != 2:
         raise ValueError("D must be 2-D")
     if not D.flags.c_contiguous:
         D = np.ascontiguousarray(D)
+    return D, (D.ctypes.data if D.size else None)
+
+
+def pairs_within_from_matrix(D, threshold, n=None):
+    """icl_pairs_within_from_matrix (host only, no GPU): Context.pairs_within's rule and layout applied to values the caller holds: the
+    strict lower triangle of the first n (default: all) rows and columns of D -> (row_ptr, col, val).  Raises ICLError(ICL_ERR_ARG)."""
+    D, Dp = _pairs_matrix(D)
     ld = D.shape[1]
     n = D.shape[0] if n is None else int(n)
     if n > D.shape[0]:
         raise ValueError("n = %d rows asked of a matrix of %d" % (n, D.shape[0]))
     L = load()
-    return _pairs_two_calls(n, lambda rp, c, v, cap, tot: L.icl_pairs_within_from_matrix(D.ctypes.data if D.size else None, n, ld, float(threshold),
-                                                                                        rp, c, v, cap, C.byref(tot)), "icl_pairs_within_from_matrix")
+    return _pairs_two_calls(n, lambda rp, c, v, cap, tot: L.icl_pairs_within_from_matrix(Dp, n, ld, float(threshold), rp, c, v, cap, C.byref(tot)),
+                            "icl_pairs_within_from_matrix")
 
 
 def pairs_between_from_matrix(D, threshold, exclude=None, n=None):
     """icl_pairs_between_from_matrix (host only, no GPU): Context.pairs_between's rule and layout applied to values the caller holds: D
     is nq x ld float32, n (default ld) columns of each row are pairs, exclude[i] (None / -1: none) is left out of row i ->
     (row_ptr int64[nq + 1], col, val).  Raises ICLError(ICL_ERR_ARG)."""
-    D = np.asarray(D, np.float32)
-    if D.ndim != 2:
-        raise ValueError("D must be 2-D")
-    if not D.flags.c_contiguous:
-        D = np.ascontiguousarray(D)
+    D, Dp = _pairs_matrix(D)
     nq, ld = D.shape
     n = ld if n is None else int(n)
     ex = _nearest_exclude(nq, exclude)
     L = load()
-    return _pairs_two_calls(nq, lambda rp, c, v, cap, tot: L.icl_pairs_between_from_matrix(D.ctypes.data if D.size else None, nq, n, ld, float(threshold),
-                                                                                          _ptr(ex), rp, c, v, cap, C.byref(tot)),
-                            "icl_pairs_between_from_matrix")
+    return _pairs_two_calls(nq, lambda rp, c, v, cap, tot: L.icl_pairs_between_from_matrix(Dp, nq, n, ld, float(threshold), _ptr(ex), rp, c, v, cap,
+                                                                                          C.byref(tot)), "icl_pairs_between_from_matrix")
 
 
 def pair_groups(row_ptr, col):
@@ -1102,22 +1103,8 @@ class Context:
         """icl_pairs_within_dev on rows that are on the device already (d_E: n x d floats) -> (row_ptr, col, val) on the host, as
         pairs_within.  col and val live on the device during the call and are downloaded here."""
         sz = _nearest_side(n, size, "size")
-
-        def call(rp, c, v, cp, tot):  # c / v: the host arrays of cp entries; the device call gets device buffers of the same length
-            bufs = [self.malloc(cp * 4), self.malloc(cp * 4)] if cp else [None, None]
-            try:
-                rc = self.L.icl_pairs_within_dev(self.h, _as_vp(d_E), _ptr(sz), n, d, float(threshold), rp, bufs[0], bufs[1], cp, C.byref(tot))
-                if rc == ICL_OK and 0 < tot.value <= cp:
-                    self.sync()
-                    check(self.h, self.L.icl_memcpy_d2h(self.h, c, _vp(bufs[0]), tot.value * 4))
-                    check(self.h, self.L.icl_memcpy_d2h(self.h, v, _vp(bufs[1]), tot.value * 4))
-                return rc
-            finally:
-                for p in bufs:
-                    if p is not None:
-                        self.free(p)
-
-        return self._pairs_calls(n, cap, call)
+        return self._pairs_calls(n, cap, self._pairs_dev_call(lambda rp, dc, dv, cp, tot: self.L.icl_pairs_within_dev(
+            self.h, _as_vp(d_E), _ptr(sz), n, d, float(threshold), rp, dc, dv, cp, C.byref(tot))))
 
     def pairs_between(self, Q, L, threshold, q_size=None, l_size=None, exclude=None, cap=None):
         """icl_pairs_between: EVERY pair (row i of Q, row j of L) whose WardDistance (sizes q_size / l_size, None: all 1) is at most
@@ -1137,12 +1124,24 @@ class Context:
         """icl_pairs_between_dev on rows that are on the device already (d_Q: nq x d floats, d_L: n x d) -> (row_ptr, col, val) on the
         host, as pairs_between.  col and val live on the device during the call and are downloaded here."""
         qs, ls, ex = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, l_size, "l_size"), _nearest_exclude(nq, exclude)
+        return self._pairs_calls(nq, cap, self._pairs_dev_call(lambda rp, dc, dv, cp, tot: self.L.icl_pairs_between_dev(
+            self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_L), _ptr(ls), n, d, float(threshold), _ptr(ex), rp, dc, dv, cp, C.byref(tot))),
+            "icl_pairs_between_dev")
 
-        def call(rp, c, v, cp, tot):  # c / v: the host arrays of cp entries; the device call gets device buffers of the same length
+    def last_pairs_between_stats(self):
+        """The last pairs_between[_dev]: column splits used, 128 x 128 tiles the count pass ran, tiles with a hit (the fill pass's), pairs
+        evaluated in both passes, workspace bytes."""
+        info = (C.c_int64 * 5)()
+        check(self.h, self.L.icl_last_pairs_between_stats(self.h, info))
+        return {"splits": info[0], "tiles": info[1], "hit_tiles": info[2], "pairs": info[3], "workspace_bytes": info[4]}
+
+    def _pairs_dev_call(self, dev_call):
+        """A _dev entry point as _pairs_two_calls' call: dev_call(row_ptr, d_col, d_val, cap, total) -> code gets device buffers of cap
+        entries, and what it lists is downloaded into the host arrays of the same length."""
+        def call(rp, c, v, cp, tot):
             bufs = [self.malloc(cp * 4), self.malloc(cp * 4)] if cp else [None, None]
             try:
-                rc = self.L.icl_pairs_between_dev(self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_L), _ptr(ls), n, d, float(threshold), _ptr(ex), rp,
-                                                  bufs[0], bufs[1], cp, C.byref(tot))
+                rc = dev_call(rp, bufs[0], bufs[1], cp, tot)
                 if rc == ICL_OK and 0 < tot.value <= cp:
                     self.sync()
                     check(self.h, self.L.icl_memcpy_d2h(self.h, c, _vp(bufs[0]), tot.value * 4))
@@ -1153,14 +1152,7 @@ class Context:
                     if p is not None:
                         self.free(p)
 
-        return self._pairs_calls(nq, cap, call, "icl_pairs_between_dev")
-
-    def last_pairs_between_stats(self):
-        """The last pairs_between[_dev]: column splits used, 128 x 128 tiles the count pass ran, tiles with a hit (the fill pass's), pairs
-        evaluated in both passes, workspace bytes."""
-        info = (C.c_int64 * 5)()
-        check(self.h, self.L.icl_last_pairs_between_stats(self.h, info))
-        return {"splits": info[0], "tiles": info[1], "hit_tiles": info[2], "pairs": info[3], "workspace_bytes": info[4]}
+        return call
 
     def _pairs_calls(self, n, cap, call, what="icl_pairs_within"):
         try:

@@ -173,11 +173,10 @@ struct icl_ctx {
     icl_dev_grow nearest;                // device copies of sizes / exclude and the partial lists of icl_nearest (nearest.hip; as many)
     int nearest_splits = 0;              // icl_set_nearest_options: column splits per band of query rows (0: the engine decides)
     int64_t nearest_stats[4] = {0, 0, 0, 0}; // last icl_nearest[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_nearest_stats)
-    icl_dev_grow pairs;                  // row counts, tile flags and row_ptr of icl_pairs_within on the device (pairs.hip; as many)
+    icl_dev_grow pairs;                  // device copies of sizes / exclude, counts, tile flags and seg_ptr of icl_pairs_within and icl_pairs_between, whichever runs under ctx->mu (pairs.hip; as many)
     int64_t pairs_stats[4] = {0, 0, 0, 0}; // last icl_pairs_within[_dev]: tiles run in pass 1, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_stats)
     icl_dev_grow fit;                    // device copies of the host arrays, partial lists and keys of icl_cluster_fit / icl_ward_values_at (fit.hip; as many)
     int64_t fit_stats[4] = {0, 0, 0, 0}; // last icl_cluster_fit[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_fit_stats)
-    icl_dev_grow between;                // device copies of sizes / exclude, segment counts, tile flags and seg_ptr of icl_pairs_between (pairs_between.hip; as many)
     int64_t between_stats[5] = {0, 0, 0, 0, 0}; // last icl_pairs_between[_dev]: splits used, tiles run in the count pass, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_between_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
 };

@@ -90,7 +90,6 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     ctx->nearest.release();
     ctx->pairs.release();
     ctx->fit.release();
-    ctx->between.release();
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

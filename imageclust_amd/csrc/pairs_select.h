@@ -21,8 +21,8 @@ PS_HD bool ps_listed(int64_t i, int64_t j, float v, float threshold)
 }
 
 // icl_pairs_between, the rectangular form: pair (query i, library row j) with value v is listed when j is not the query's excluded
-// column (exclude = exclude[i]; -1: none) and v <= threshold with the same fp32 meaning as above.  Both passes of pairs_between.hip and
-// icl_pairs_between_from_matrix (pairs_between_plan.h) call this function and nothing else.  The sizes play no part: there is no ban.
+// column (exclude = exclude[i]; -1: none) and v <= threshold with the same fp32 meaning as above.  Both of its passes in pairs.hip and
+// icl_pairs_between_from_matrix (pairs_plan.h) call this function and nothing else.  The sizes play no part: there is no ban.
 PS_HD bool ps_listed_between(int64_t j, int64_t exclude, float v, float threshold)
 {
     return j != exclude && v <= threshold;

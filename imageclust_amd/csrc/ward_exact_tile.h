@@ -1,13 +1,12 @@
 // ward_exact_tile.h -- the bit-exact Ward distance tile, stated once: 128 x 128 pairs per workgroup of 256 threads, k-chunks of both
 // operands staged in LDS, an 8 x 8 block of accumulators per thread, each accumulator one strictly sequential chain of
-// fl(fl(a_k - b_k)^2) (clustering.go:137-141, 152-155).  ward_dist_exact_kernel (ward.hip) and the two passes of pairs.hip run it on
-// the lower triangle of one operand, band_select_kernel (band_select.h: nearest.hip, fit.hip) and pairs_between_kernel
-// (pairs_between.hip) on a rectangle of two; each keeps its own epilogue.  Every "bit-equal to the oracle" claim of the distance stage
-// rests on the operation order below.
+// fl(fl(a_k - b_k)^2) (clustering.go:137-141, 152-155).  ward_dist_exact_kernel (ward.hip) and icl_pairs_within's two passes (pairs.hip)
+// run it on the lower triangle of one operand, band_select_kernel (band_select.h: nearest.hip, fit.hip) and icl_pairs_between's two
+// passes (pairs.hip) on a rectangle of two; ward.hip, the band walk and pairs.hip each keep an epilogue of their own.  Every "bit-equal
+// to the oracle" claim of the distance stage rests on the operation order below.
 //
 // Only units compiled with -ffp-contract=off -fno-slp-vectorize may include this header (the Makefile's rules of ward.o, nearest.o,
-// pairs.o, fit.o and pairs_between.o): every difference, product and sum is rounded on its own, and the packed pairs below are the only
-// packing wanted.
+// pairs.o and fit.o): every difference, product and sum is rounded on its own, and the packed pairs below are the only packing wanted.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -20,10 +19,13 @@
 
 typedef float dt_f2 __attribute__((ext_vector_type(2)));
 
-// acc[r][c] = sum over k < d, strictly in k order, of fl(fl(a - b)^2) for the pair of row i0 + (r < 4 ? ty * 4 + r : 64 + ty * 4 + r - 4)
-// of A [na][d] and row j0 + (c < 4 ? tx * 4 + c : 64 + tx * 4 + c - 4) of B [nb][d], tx = thread & 15, ty = thread >> 4.  Called by all
-// 256 threads of the workgroup (it synchronises); As / Bs: DT_KC rows of DT_LD floats each, free for other use on return.  vec: d % 4 == 0
-// and both operands 16-byte aligned (rows are then read 16 bytes at a time).
+// Which row (t = ty) or column (t = tx) of the tile a thread's accumulator index a (0 .. 7) stands for: four neighbours in each half.
+__device__ __forceinline__ int dt_lane_index(int a, int t) { return a < 4 ? t * 4 + a : 64 + t * 4 + (a - 4); }
+
+// acc[r][c] = sum over k < d, strictly in k order, of fl(fl(a - b)^2) for the pair of row i0 + dt_lane_index(r, ty) of A [na][d] and row
+// j0 + dt_lane_index(c, tx) of B [nb][d], tx = thread & 15, ty = thread >> 4.  Called by all 256 threads of the workgroup (it
+// synchronises); As / Bs: DT_KC rows of DT_LD floats each, free for other use on return.  vec: d % 4 == 0 and both operands 16-byte
+// aligned (rows are then read 16 bytes at a time).
 __device__ __forceinline__ void ward_exact_tile(const float *A, int64_t na, int64_t i0, const float *B, int64_t nb, int64_t j0, int d, bool vec,
                                                 float (*As)[DT_LD], float (*Bs)[DT_LD], float (&acc)[8][8])
 {

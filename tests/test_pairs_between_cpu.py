@@ -1,6 +1,6 @@
-"""icl_pairs_between_from_matrix (imageclust_amd/csrc/pairs_between.hip + pairs_between_plan.h + pairs_select.h, host only) against the
-plain-numpy checker of tests/pairs_between_cases.py; tests/pairs_between_main.cpp, the same host code with the prefix and placement
-arithmetic in a stand-alone program under the address and undefined-behaviour sanitizers; and the Python layer over icl_pairs_between
+"""icl_pairs_between_from_matrix (imageclust_amd/csrc/pairs.hip + pairs_plan.h + pairs_select.h, host only) against the
+plain-numpy checker of tests/pairs_between_cases.py; tests/pairs_plan_main.cpp, the same host code of both pairs families with the prefix
+and placement arithmetic in a stand-alone program under the address and undefined-behaviour sanitizers; and the Python layer over icl_pairs_between
 (DuplicatesOf, Clustering.duplicates_of, Clustering.add(skip_duplicates=), workflow.RunMore(dedupe_threshold=)) through engine stand-ins.
 No GPU, no Python in the sanitised process."""
 import ctypes
@@ -17,7 +17,7 @@ from tests import pairs_between_cases as BC
 HERE = os.path.dirname(os.path.abspath(__file__))
 HIPCC = shutil.which(os.environ.get("HIPCC", "hipcc")) or "/opt/rocm/bin/hipcc"
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libsan"]
-RULES = ["rule", "from_matrix sweep", "prefix and placement", "bad arguments"]
+RULES = ["rule", "from_matrix sweep", "prefix and placement", "bad arguments", "within rule", "within from_matrix sweep", "within prefix"]
 LIMIT_S = 300
 INF = np.float32(np.inf)
 
@@ -276,9 +276,9 @@ def test_run_more_dedupe_threshold():
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
     assert os.path.exists(HIPCC), "no hipcc: its clang is the host compiler of the sanitised build"
-    exe = str(tmp_path_factory.mktemp("pairs_between") / "pairs_between")
+    exe = str(tmp_path_factory.mktemp("pairs_plan") / "pairs_plan")
     r = subprocess.run([HIPCC, "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + SAN +
-                       [os.path.join(HERE, "pairs_between_main.cpp"), "-o", exe], capture_output=True, text=True, timeout=LIMIT_S)
+                       [os.path.join(HERE, "pairs_plan_main.cpp"), "-o", exe], capture_output=True, text=True, timeout=LIMIT_S)
     assert r.returncode == 0, r.stderr[-3000:]
     return exe
 

@@ -1,4 +1,4 @@
-"""icl_pairs_between / icl_pairs_between_dev (imageclust_amd/csrc/pairs_between.hip): every pair (query row, library row) whose exact
+"""icl_pairs_between / icl_pairs_between_dev (imageclust_amd/csrc/pairs.hip): every pair (query row, library row) whose exact
 WardDistance is at most a threshold, as a CSR list over the queries, with no distance matrix and no cap on a query's partners.  Bar:
 row_ptr and col equal the checker's (tests/pairs_between_cases.py: the oracle's values thresholded in plain numpy, the excluded column
 left out, pairs in (i, j) order) and val equals it as uint32 bit patterns -- no tolerance anywhere -- for every band and tile edge, both

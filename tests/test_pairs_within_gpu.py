@@ -2,7 +2,7 @@
 threshold, as a CSR list over the strict lower triangle, with no distance matrix and no cap on a row's partners.  Bar: row_ptr and col
 equal the checker's (tests/pairs_cases.py: the oracle's matrix thresholded in plain numpy, pairs in (i, j) order) and val equals it as
 uint32 bit patterns, for every tile edge, both load paths, a second band of tile rows, ties at the threshold, the dense and the empty
-result, sizes, NaN / Inf rows and the capacity convention."""
+result, sizes, NaN / Inf rows and the capacity convention; and a tile row of more than 256 tiles against a CSR that follows from a sort."""
 import ctypes
 import functools
 
@@ -76,6 +76,64 @@ def test_band_order_second_band_and_its_cap(ctx):
     st, (tiles, hit, pairs) = ctx.last_pairs_stats(), PC.tile_stats(V, low[40])
     assert 0 < hit <= 41 and (st["tiles"], st["hit_tiles"], st["pairs"]) == (tiles, hit, pairs)
     assert 0 < st["workspace_bytes"] < 64 * 1300  # O(n + tiles), no n x n array
+
+
+def line_rows(n, quiet_tile_row=100, seed=257):
+    """n rows (x_i, 0, 0, 0) whose expected pairs at threshold 0.5 follow from a sort: x is a permutation of the multiples of 4 below 4 n,
+    then a few dozen rows are overwritten with another row's x plus 1.  All values are integers below 2^24, so a pair with |x_i - x_j| <= 1
+    has the value 0 or 0.5 exactly (the sum is 0 or 1, the sizes' factor 1 * 1 / (1 + 1)) and every other pair is at least 0.5 * 3^2 = 4.5.
+    The last row's partners lie in tile columns 0, 255, 256 and -- where the last tile row has a row below it -- in its diagonal tile; no
+    row of tile row `quiet_tile_row` is a copy or is copied.  -> (E float32[n][4], (row_ptr, col, val) expected, hit tiles expected)"""
+    rng = np.random.default_rng(seed)
+    x = 4 * rng.permutation(n).astype(np.int64)
+    last, first_of_last = n - 1, (n - 1) // 128 * 128
+    copies = [(5, last), (255 * 128 + 77, last), (256 * 128 + 3, last)]  # (the row overwritten, the row whose x it takes)
+    if first_of_last < last:
+        copies.append((first_of_last, last))
+    taken = {r for pair in copies for r in pair}
+    free = [r for r in rng.permutation(n).tolist() if r // 128 != quiet_tile_row and r not in taken][:80]
+    copies += list(zip(free[:40], free[40:]))
+    for dst, src in copies:
+        x[dst] = x[src] + 1
+    assert 0 <= x.min() and x.max() < 1 << 24
+    # rows whose x share x // 4 are each other's partners (x is 0 or 1 mod 4), and nobody else's
+    key = x // 4
+    order = np.argsort(key, kind="stable")
+    ks, start, count = np.unique(key[order], return_index=True, return_counts=True)
+    pairs = []
+    for s, c in zip(start[count > 1], count[count > 1]):
+        rows = np.sort(order[s:s + c])
+        pairs += [(int(i), int(j)) for a, i in enumerate(rows) for j in rows[:a]]
+    pairs.sort()
+    pi, pj = np.array(pairs, np.int64).T
+    row_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(pi, minlength=n), out=row_ptr[1:])
+    val = (np.float32(0.5) * ((x[pi] - x[pj]) ** 2).astype(np.float32)).astype(np.float32)
+    assert set(np.unique(val).tolist()) == {0.0, 0.5}
+    E = np.zeros((n, 4), np.float32)
+    E[:, 0] = x
+    return E, (row_ptr, pj.astype(np.int32), val), len(set(zip((pi // 128).tolist(), (pj // 128).tolist())))
+
+
+@pytest.mark.parametrize("n", [257 * 128 + 1, 257 * 128 + 64])
+def test_a_tile_row_longer_than_256_tiles(ctx, n):
+    """The fill walk reads a band's flags 256 at a time: tile row 257 (258 tiles) crosses that boundary.  n = 257 * 128 + 1 leaves one
+    row in the last tile row, whose diagonal tile then holds no pair j < i at all; the second n gives that tile 64 rows and a pair."""
+    E, want, hit_tiles = line_rows(n)
+    rp, col, _ = want
+    tile_cols = set((col[rp[n - 1]:rp[n]] // 128).tolist())   # of the last row's partners
+    assert tile_cols == ({0, 255, 256, 257} if n > 257 * 128 + 1 else {0, 255, 256}) and (n - 1) // 128 == 257
+    assert rp[101 * 128] == rp[100 * 128] and rp[-1] == 40 + len(tile_cols) * (len(tile_cols) + 1) // 2 and hit_tiles > 40   # (an ordinary tile row without a pair)
+    buf = ctx.malloc(E.nbytes)
+    try:
+        ctx.h2d(buf, E)
+        for size in (None, np.ones(n, np.int32)):             # the two sources of sizes must give the same bits
+            got = ctx.pairs_within_dev(buf, n, 4, 0.5, size=size, cap=int(rp[-1]))
+            assert PC.same(got, want), "size %s: %s" % ("None" if size is None else "ones", PC.why(got, want))
+            st = ctx.last_pairs_stats()
+            assert st["tiles"] == 258 * 259 // 2 and st["hit_tiles"] == hit_tiles
+    finally:
+        ctx.free(buf)
 
 
 def test_exact_ties_at_the_threshold(ctx):
