@@ -98,6 +98,9 @@ SYMBOLS = [
     ("icl_set_batch", _int, [_vp, _int]),
     ("icl_set_conv_options", _int, [_vp, _int]),
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
+    ("icl_set_forward_prune", _int, [_vp, _int]),
+    ("icl_forward_prune_stats", _int, [_vp, _vp]),
+    ("icl_conv1x1_mapped", _int, [_vp, _vp, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _int, _vp]),
     ("icl_conv_split_launches", _int, [_vp, _vp]),
     ("icl_conv2d_fused", _int, [_vp, _int, _vp, _int, _int, _int, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp]),
     ("icl_conv2d_dual", _int, [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _int, _int, _vp, _vp, _int, _vp]),
@@ -659,6 +662,16 @@ class Context:
         """0 never, 1 auto, 2 every supported shape on the deep-pipelined 256x256x64 convolution kernel (include/imageclust.h ICL_CONV_P8_*)."""
         check(self.h, self.L.icl_set_conv_options(self.h, p8_mode))
 
+    def set_forward_prune(self, on=True):
+        """bf16 forward pass: compute only the pixels the next stage's stride reads (icl_set_forward_prune; results are bit-identical)."""
+        check(self.h, self.L.icl_set_forward_prune(self.h, 1 if on else 0))
+
+    def forward_prune_stats(self):
+        """bottlenecks run in the pruned form since the context was created."""
+        a = C.c_int64(0)
+        check(self.h, self.L.icl_forward_prune_stats(self.h, C.byref(a)))
+        return a.value
+
     def embed_u8(self, imgs, head=HEAD_POOLED, prec=PREC_FP32):
         imgs = np.ascontiguousarray(imgs, np.uint8).reshape(-1, IMG_BYTES)
         n = imgs.shape[0]
@@ -932,6 +945,22 @@ class Context:
         check(self.h, self.L.icl_conv2d_fused(self.h, prec, x.ctypes.data, B, H, Cin, w.ctypes.data, Cout, k, stride, pad,
                                               sc.ctypes.data, sh.ctypes.data, None if r is None else r.ctypes.data,
                                               1 if relu else 0, y.ctypes.data))
+        return y
+
+    def conv1x1_mapped(self, x_nhwc, w, scale, shift, y_full, sub, residual=None, relu=True):
+        """The mapped 1x1 launch of a pruned bottleneck's c3 (icl_conv1x1_mapped, bf16): x [B][Ho][Ho][Cin] compact, w [Cout][Cin],
+        residual / y_full [B][H][H][Cout].  Returns a copy of y_full in which the pixels (sub * oy, sub * ox) hold the result."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        x, w, sc, sh = f(x_nhwc), f(w), f(scale), f(shift)
+        y = np.array(y_full, np.float32, order="C", copy=True)
+        B, H, _, Cout = y.shape
+        Ho = (H - 1) // int(sub) + 1
+        Cin = x.shape[3]
+        assert x.shape == (B, Ho, Ho, Cin) and w.shape == (Cout, Cin) and sc.shape == (Cout,) and sh.shape == (Cout,)
+        r = None if residual is None else f(residual)
+        assert r is None or r.shape == y.shape
+        check(self.h, self.L.icl_conv1x1_mapped(self.h, x.ctypes.data, B, H, int(sub), Cin, w.ctypes.data, Cout, sc.ctypes.data, sh.ctypes.data,
+                                                None if r is None else r.ctypes.data, 1 if relu else 0, y.ctypes.data))
         return y
 
     def conv2d_dual(self, x_nhwc, w1, x2_nhwc, w2, stride2, scale, shift, relu=True, prec=PREC_FP32):

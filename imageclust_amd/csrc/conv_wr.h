@@ -13,8 +13,12 @@
 //   residual              requested one tile ahead, 16 bytes per lane in the layout the epilogue ends in
 //   epilogue              in registers (v_permlane16_swap, conv_p8.h): 8 consecutive channels per lane, fp32 scale/shift + residual + ReLU, one rounding
 // The slices of one worker sit on one XCD (blocks b, b + 8, ...): the A tile they share crosses the fabric once.
+// MAP (the c3 of a bottleneck whose output is read at a stride only, prune_map.h): the rows of X are the pixels that are read, compact;
+// the residual and the output stay full-size tensors and row m is their pixel prune_map_pixel(pm, m) -- one offset for the residual load and
+// the store, nothing else differs.  The instantiations without MAP are the code they were before the flag (profiles/r37_isa_compare.txt).
 #pragma once
 #include "mfma_tile.h"
+#include "prune_map.h"
 #include "resnet_fused.h"
 
 // the LDS-DMA pieces (32 rows each: 4 waves x 8 rows x 128 B, 4 KiB apart) of ONE 64-channel chunk of a PT-pixel A image (PT = 64: two pieces,
@@ -52,9 +56,10 @@ struct wr_args {
     const float *scale, *shift; // [N]
     int M, N, relu;
     int nslices, nworkers; // grid = nslices * nworkers, nworkers % 8 == 0
+    prune_map pm;          // MAP kernels: X is compact ([M = B * Ho * Wo][K]); R and Y are full [B][H][W][N] tensors, row m is pixel prune_map_pixel(pm, m)
 };
 
-template <int K, int NS, int MT, bool RES>
+template <int K, int NS, int MT, bool RES, bool MAP = false>
 __global__ __launch_bounds__(256, (K == 256 && MT == 2) ? 3 : 2) void conv_wr_kernel(const wr_args p)
 {
     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -127,11 +132,17 @@ __global__ __launch_bounds__(256, (K == 256 && MT == 2) ? 3 : 2) void conv_wr_ke
     typedef uint16_t elem;
     // residual loads and output stores through buffer descriptors: rows beyond M (and tiles beyond the last) are out-of-range lanes -- no
     // branches, the same number of vector-memory operations every tile; hipcc counts these (builtins), the LDS-DMA above it does not
-    const __amdgpu_buffer_rsrc_t rsrd = __builtin_amdgcn_make_buffer_rsrc((void *)(RES ? p.R : p.Y), 0, (int)((size_t)p.M * p.N * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, (int)((size_t)p.M * p.N * 2), 0x00020000);
+    // (MAP: both descriptors cover the full tensor, whose pixels the rows of this launch are scattered over)
+    const size_t ypix = MAP ? (size_t)(p.M / (p.pm.Ho * p.pm.Wo)) * p.pm.H * p.pm.W : (size_t)p.M;
+    const __amdgpu_buffer_rsrc_t rsrd = __builtin_amdgcn_make_buffer_rsrc((void *)(RES ? p.R : p.Y), 0, (int)(ypix * p.N * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, (int)(ypix * p.N * 2), 0x00020000);
     u32x4_t rv[MT][NT / 2];
     auto row_off = [&](int tile, int mt) -> unsigned { // byte offset of this lane's first chunk of pixel row mt * 16 + l15 of the tile
         const int64_t m = (int64_t)tile * PT + mt * 16 + l15;
+        if constexpr (MAP) { // the same offset serves the residual load and the store: pixel (b, sub * oy, sub * ox) of the full tensor
+            if (!(tile < ntiles && m < p.M)) return BN56_OOB;
+            return (unsigned)((prune_map_pixel(p.pm, (unsigned)m) * p.N + n0 + cbl) * 2);
+        }
         return (tile < ntiles && m < p.M) ? (unsigned)((m * p.N + n0 + cbl) * 2) : BN56_OOB;
     };
     auto load_res = [&](int tile) {
@@ -235,13 +246,26 @@ static bool conv_wr_eligible(const conv_args &a, int mode)
     if (mode == 0 || a.X2 || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.Cin != a.K) return false;
     int ns, pt;
     if (!conv_wr_shape(a, &ns, &pt)) return false;
+    if (a.omap.sub && (a.K > 256 || pt != 64)) return false; // the mapped form exists for the 64-pixel tiles of K = 128 / 256
     if (a.K == 512 && a.Cout > 128 && a.Cout < 2048) return false; // (1024 -> ... K = 512 shapes other than 512 -> 128 / 512 -> 2048 do not occur; stride-2 c1 layers are not eligible anyway)
     if ((size_t)a.M * a.K * 2 >= (1ull << 31) || (size_t)a.M * a.Cout * 2 >= (1ull << 31)) return false; // 32-bit buffer offsets, BN56_OOB = 2^31
+    if (a.omap.sub) { // the mapped form: the compact pixels are those of the map, and the FULL tensor stays below 2^31 bytes
+        const prune_map &pm = a.omap;
+        if (pm.sub < 1 || pm.Ho != prune_extent(pm.H, pm.sub) || pm.Wo != prune_extent(pm.W, pm.sub) || a.Ho != pm.Ho || a.Wo != pm.Wo) return false;
+        if ((size_t)a.B * pm.H * pm.W * a.Cout * 2 >= (1ull << 31)) return false;
+    }
     return true;
 }
 template <int K, int NS, int MT>
 static void launch_conv_wr_t(hipStream_t strm, const wr_args &w, dim3 grid, bool res)
 {
+    if (w.pm.sub) { // (the pruned c3 layers: K = 128 / 256 with a residual; the other mapped forms are not instantiated)
+        if constexpr (K <= 256 && MT == 4) {
+            if (res) hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, true, true>), grid, dim3(256), 0, strm, w);
+            else hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, false, true>), grid, dim3(256), 0, strm, w);
+        }
+        return;
+    }
     if (res) hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, true>), grid, dim3(256), 0, strm, w);
     else hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, false>), grid, dim3(256), 0, strm, w);
 }
@@ -251,6 +275,7 @@ static void launch_conv_wr(icl_ctx *ctx, const conv_args &a)
     wr_args w;
     w.X = (const uint16_t *)a.X; w.W = (const uint16_t *)a.Wt; w.R = (const uint16_t *)a.R; w.Y = (uint16_t *)a.Y;
     w.scale = a.scale; w.shift = a.shift; w.M = (int)a.M; w.N = a.Cout; w.relu = a.relu;
+    w.pm = a.omap;
     int ns = 0, pt = 0;
     (void)conv_wr_shape(a, &ns, &pt);
     w.nslices = a.Cout / ns;

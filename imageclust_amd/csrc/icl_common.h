@@ -140,6 +140,8 @@ struct icl_ctx {
     int conv_sk = 0; // latency mode: the 7 x 7 layers' tiles on two workgroups each (conv_p8.h, SPLIT; icl_set_conv_options | ICL_CONV_SPLIT, ICL_CONV_SK=1)
     int conv_sk_min_k = 2048; // ... for layers with at least this K (the K = 1024 layer loses: 30 -> 37 us; ICL_CONV_SK_MINK = 512 ... for A/B runs)
     int64_t conv_sk_launches = 0;
+    int fwd_prune = 1; // the bf16 forward pass computes only the pixels a strided block 0 reads of the block in front of it (prune_map.h; icl_set_forward_prune, ICL_PRUNE=0)
+    int64_t pruned_blocks = 0; // bottlenecks run in that form (icl_forward_prune_stats)
     icl_sk_slot sk[8];
     int conv_p8 = 1; // icl_set_conv_options: 0 never, 1 auto, 2 every supported shape (conv_p8.h)
     int ward_dist = 0; // icl_set_ward_options: 0 auto, 1 every initial distance by the exact kernel, 2 distance bounds + on-demand exact evaluation

@@ -62,6 +62,7 @@ extern "C" int icl_create(int device, icl_ctx **out)
     }
     if (const char *ew = getenv("ICL_CONV_WR")) c->conv_wr = atoi(ew) != 0;
     if (const char *es = getenv("ICL_CONV_SK")) c->conv_sk = atoi(es) != 0;
+    if (const char *ep = getenv("ICL_PRUNE")) c->fwd_prune = atoi(ep) != 0; // A/B runs: the default of icl_set_forward_prune
     if (const char *ek = getenv("ICL_CONV_SK_MINK")) c->conv_sk_min_k = std::max(512, atoi(ek));
     if (const char *e8 = getenv("ICL_CONV_P8")) { // A/B runs: the default of icl_set_conv_options
         const int v = atoi(e8);
@@ -189,6 +190,22 @@ extern "C" int icl_set_conv_options(icl_ctx *ctx, int p8_mode)
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->conv_p8 = mode;
     ctx->conv_sk = (p8_mode & ICL_CONV_SPLIT) ? 1 : 0;
+    return ICL_OK;
+}
+
+extern "C" int icl_set_forward_prune(icl_ctx *ctx, int on)
+{
+    if (!ctx || on < 0 || on > 1) return icl_fail(ctx, ICL_ERR_ARG, "icl_set_forward_prune: on must be 0 or 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->fwd_prune = on;
+    return ICL_OK;
+}
+
+extern "C" int icl_forward_prune_stats(icl_ctx *ctx, int64_t *pruned_blocks)
+{
+    if (!ctx || !pruned_blocks) return icl_fail(ctx, ICL_ERR_ARG, "icl_forward_prune_stats: NULL argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *pruned_blocks = ctx->pruned_blocks;
     return ICL_OK;
 }
 

@@ -17,6 +17,7 @@
 // performs the reference's RGB/255 scaling (embeddings.go:96).
 #include "icl_common.h"
 #include "mfma_tile.h"
+#include "prune_map.h"
 #include "resnet_model.h"
 
 #include <algorithm>
@@ -48,6 +49,9 @@ struct conv_args {
     void *sk_part;
     int *sk_flag;
     int sk_epoch;
+    // optional output-pixel map (conv_wr_kernel's MAP form only; omap.sub == 0: none): X is the compact [B][Ho][Wo][Cin] tensor, R and Y are
+    // full-size [B][omap.H][omap.W][Cout] tensors in which output pixel (b, oy, ox) is pixel (b, sub * oy, sub * ox) -- prune_map.h
+    prune_map omap;
 };
 
 #include "resnet_fused.h"
@@ -819,6 +823,7 @@ static int launch_conv_t(icl_ctx *ctx, conv_args a)
         ICL_HIP(ctx, hipGetLastError());
         return ICL_OK;
     }
+    if (a.omap.sub) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv: only the streaming 1x1 kernel writes through an output-pixel map (bf16, K = 128 or 256)");
     // the K-heavy layers: 256 x 256 tiles on the deep-pipelined loop (conv_p8.h)
     if ((std::is_same<T, BF16>::value || X3) && conv_p8_eligible(a, ctx->conv_p8)) {
         launch_conv_p8<X3>(ctx, a);
@@ -1001,6 +1006,36 @@ extern "C" int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, in
     });
 }
 
+// The mapped 1x1 launch of a pruned block's c3 on the caller's tensors (bf16 operands): x is the compact [B][Ho][Ho][Cin] tensor,
+// Ho = (H - 1) / sub + 1; residual (or NULL) and y are full-size [B][H][H][Cout] tensors.  y is read AND written: the launch stores the pixels
+// (sub * oy, sub * ox) and every other value of y comes back as it went in (rounded to bf16).  A shape the streaming kernel's mapped form does
+// not take is ICL_ERR_UNSUPPORTED: there is no other kernel behind this entry point.
+extern "C" int icl_conv1x1_mapped(icl_ctx *ctx, const float *x, int B, int H, int sub, int Cin, const float *w, int Cout, const float *scale,
+                                  const float *shift, const float *residual, int relu, float *y)
+{
+    if (!ctx || !x || !w || !scale || !shift || !y || B < 1 || H < 1 || sub < 1 || Cin < 1 || Cout < 1)
+        return icl_fail(ctx, ICL_ERR_ARG, "icl_conv1x1_mapped: bad argument");
+    if ((int64_t)B * H * H * Cout * 2 >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv1x1_mapped: the full tensor exceeds the kernel's 32-bit buffer offsets");
+    return run_entry(ctx, "icl_conv1x1_mapped", false, y, [&](entry_io &io) -> int {
+        const int prec = ICL_PREC_BF16;
+        const prune_map pm = prune_map_make(sub, H, H);
+        const size_t nx = (size_t)B * pm.Ho * pm.Wo * Cin, ny = (size_t)B * H * H * Cout;
+        dev_guard &dx = io.buf(), &dw = io.buf(), &dr = io.buf(), &dy = io.buf(), &dz = io.buf(), &dsc = io.buf(), &dsh = io.buf();
+        ICL_TRY(upload_as(ctx, prec, &dx.p, x, nx));
+        ICL_TRY(zero_page(ctx, "icl_conv1x1_mapped", dz));
+        ICL_TRY(upload_as(ctx, prec, &dw.p, w, (size_t)Cout * Cin));
+        if (residual) ICL_TRY(upload_as(ctx, prec, &dr.p, residual, ny));
+        ICL_TRY(upload_as(ctx, prec, &dy.p, y, ny));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsc.p, scale, (size_t)Cout));
+        ICL_TRY(upload_as(ctx, ICL_PREC_FP32, &dsh.p, shift, (size_t)Cout));
+        conv_args a = conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, pm.Ho, Cin, Cout, 1, 1, 0, relu);
+        a.omap = pm;
+        io.returns(prec, dy.p, ny);
+        if (!ctx->conv_wr || !conv_wr_eligible(a, ctx->conv_p8)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv1x1_mapped: Cin = %d, Cout = %d is no shape of the streaming kernel's mapped form", Cin, Cout);
+        return launch_conv_prec(ctx, prec, a);
+    });
+}
+
 // Block 0 of a stage: y = relu(bn3(conv3(t2)) + bn_ds(conv_ds(x))) as ONE dual-operand launch (BN scales folded into
 // the concatenated weights): the downsample tensor is never written to or read back from HBM.
 static int launch_conv_fused_ds(icl_ctx *ctx, int prec, const conv_layer &c3, const conv_layer &ds, const void *t2, const void *x, void *y, int B)
@@ -1106,6 +1141,30 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     return launch_bneck56_args(ctx, a, ds != nullptr, strm);
 }
 
+// The last identity block in front of a strided block 0 (prune_map.h: s = prune_stride(..) > 1), bf16: c2 as the 3x3 / stride s / pad 1
+// convolution into a compact t2, c3 over that compact tensor with its residual and output at pixel (s oy, s ox) of the full-size x and y;
+// the pixels in between are not written and nobody reads them.  Both launches must land on the kernels and instantiations the unpruned
+// layers take (same k order: the values that are still computed keep their bits); false -- the caller runs the unpruned block -- if not.
+static bool plan_pruned_block(icl_ctx *ctx, const conv_layer &c2, const conv_layer &c3, int s, const void *t1, void *t2, const void *x, void *y, int B,
+                              conv_args *p2, conv_args *p3)
+{
+    if (s <= 1) return false;
+    const int prec = ICL_PREC_BF16;
+    const icl_conv_rec &r2 = c2.rec, &r3 = c3.rec;
+    const void *zero = ctx->model->zero;
+    const conv_args u2 = conv_plain(t1, c2.w[prec], t2, nullptr, c2.scale, c2.shift, zero, B, r2.hin, r2.cin, r2.cout, r2.k, r2.stride, r2.pad, 1);
+    const conv_args u3 = conv_plain(t2, c3.w[prec], y, x, c3.scale, c3.shift, zero, B, r3.hin, r3.cin, r3.cout, 1, 1, 0, 1);
+    *p2 = conv_plain(t1, c2.w[prec], t2, nullptr, c2.scale, c2.shift, zero, B, r2.hin, r2.cin, r2.cout, r2.k, s, r2.pad, 1);
+    *p3 = conv_plain(t2, c3.w[prec], y, x, c3.scale, c3.shift, zero, B, p2->Ho, r3.cin, r3.cout, 1, 1, 0, 1);
+    p3->omap = prune_map_make(s, r3.hout, r3.hout);
+    if (u2.K != c2.K || u3.K != c3.K || p2->Ho != p3->omap.Ho) return false;
+    const int mode = ctx->conv_p8;
+    if (!ctx->conv_wr || !conv_wr_eligible(u3, mode) || !conv_wr_eligible(*p3, mode)) return false;
+    if (!conv_p8_eligible(u2, mode) || !conv_p8_eligible(*p2, mode)) return false;
+    if (conv_p8_split_eligible(ctx, u2) != conv_p8_split_eligible(ctx, *p2)) return false; // (the split form sums K in another order)
+    return true;
+}
+
 // tap >= 0 (icl_embed_taps): the pass ends after the stem + maxpool (0) or after bottleneck `tap` (1..16) and *tap_x is the buffer that
 // holds that tensor; nothing else differs.
 template <typename T>
@@ -1145,6 +1204,18 @@ static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, in
             continue;
         }
         ICL_TRY(launch_conv(ctx, prec, c1, x, t1, nullptr, 1, B));
+        // dead pixels: the block after this one reads its input at stride s only (never the block whose tensor a tap returns)
+        const int cn = ci + (has_ds ? 4 : 3);
+        conv_args p2, p3;
+        if (prec == ICL_PREC_BF16 && ctx->fwd_prune && !has_ds && blk + 1 != tap && cn + 3 < m->nconv &&
+            plan_pruned_block(ctx, c2, c3, prune_stride(c2.rec, c3.rec, &m->conv[cn].rec, &m->conv[cn + 3].rec), t1, t2, x, y, B, &p2, &p3)) {
+            ICL_TRY(launch_conv_prec(ctx, prec, p2)); // 3x3 / stride s: compact [B][h/s][h/s][mid]
+            ICL_TRY(launch_conv_prec(ctx, prec, p3)); // 1x1 over the compact tensor; residual and output at (s oy, s ox) of the full tensors
+            ++ctx->pruned_blocks;
+            std::swap(x, y);
+            ci = cn;
+            continue;
+        }
         ICL_TRY(launch_conv(ctx, prec, c2, t1, t2, nullptr, 1, B));
         if (has_ds)
             ICL_TRY(launch_conv_fused_ds(ctx, prec, c3, m->conv[ci + 3], t2, x, y, B)); // relu(bn3(conv3) + bn_ds(conv_ds))

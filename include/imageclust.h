@@ -209,6 +209,15 @@ int icl_set_batch(icl_ctx *ctx, int batch); /* embed batch size, 1..1024 */
  * pass's -- the embedding is 1.1-1.5 % SLOWER, hence not the default. */
 enum { ICL_CONV_P8_OFF = 0, ICL_CONV_P8_AUTO = 1, ICL_CONV_P8_ALL = 2, ICL_CONV_SPLIT = 16 };
 int icl_set_conv_options(icl_ctx *ctx, int p8_mode);
+/* Dead pixels of the bf16 forward pass (default on; the environment variable ICL_PRUNE = 0/1 overrides the default when the context is
+ * created): block 0 of stages 2-4 reads the tensor in front of it through 1x1 / pad 0 / stride 2 convolutions only, i.e. at the pixels
+ * (2 oy, 2 ox).  With the option on, the bottleneck in front of such a block runs its 3x3 convolution at that stride and its last 1x1
+ * convolution over the quarter of the pixels that is read, written to their places in the full-size tensor; the other pixels of that
+ * tensor are not written.  Every value that is computed is computed by the same kernel in the same order: embeddings and the tensors of
+ * icl_embed_taps (a tapped tensor is always computed whole) are bit-identical with the option on and off.  ICL_PREC_FP32 and
+ * ICL_PREC_BF16X3 are not affected.  icl_forward_prune_stats: bottlenecks run in the pruned form since the context was created. */
+int icl_set_forward_prune(icl_ctx *ctx, int on);
+int icl_forward_prune_stats(icl_ctx *ctx, int64_t *pruned_blocks);
 /* Launches of the split form since the context was created. */
 int icl_conv_split_launches(icl_ctx *ctx, int64_t *launches);
 /* Convolution launches since the context was created: on conv_p8_kernel / on every other convolution kernel (either pointer may be NULL). */
@@ -228,6 +237,13 @@ int icl_conv2d_fused(icl_ctx *ctx, int prec, const float *x, int B, int H, int C
  * is chosen as in the forward pass (icl_set_conv_options); operands are stored as icl_conv2d_fused stores them. */
 int icl_conv2d_dual(icl_ctx *ctx, int prec, const float *x, int B, int Ho, int Cin, const float *w1, const float *x2, int H2, int Cin2,
                     const float *w2, int stride2, int Cout, const float *scale, const float *shift, int relu, float *y);
+/* The mapped launch of a pruned bottleneck's last 1x1 convolution (icl_set_forward_prune), host buffers, bf16 operands, for the per-layer
+ * tests: x [B][Ho][Ho][Cin] with Ho = (H - 1) / sub + 1, w [Cout][Cin], residual (or NULL) and y [B][H][H][Cout], all fp32 NHWC.
+ * y[b][sub oy][sub ox][c] = relu?( (x[b][oy][ox] . w[c]) * scale[c] + shift[c] (+ residual[b][sub oy][sub ox][c]) ); y is read and written:
+ * every other value comes back as it went in, rounded to bf16.  Cin = 128 with Cout % 256 == 0, or Cin = 256 with Cout % 128 == 0
+ * (ICL_ERR_UNSUPPORTED otherwise: no other kernel stands behind this entry point). */
+int icl_conv1x1_mapped(icl_ctx *ctx, const float *x, int B, int H, int sub, int Cin, const float *w, int Cout, const float *scale,
+                       const float *shift, const float *residual, int relu, float *y);
 /* The forward pass of the loaded model on ONE batch of B images (B <= icl_set_batch's batch), ended at a tap, for the per-block parity
  * tests: out receives, as fp32 NHWC, the tensor the pass holds after the stem + maxpool (tap 0: [B][56][56][64]) or after bottleneck
  * tap (1..16: [B][56][56][256] x 3, [B][28][28][512] x 4, [B][14][14][1024] x 6, [B][7][7][2048] x 3).  Same kernels, order and

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Compare two device-only assembly listings kernel by kernel: isa_compare.py [--pair OLD=NEW ...] parent.s branch.s [more.s ...]
+"""Compare two device-only assembly listings kernel by kernel: isa_compare.py [--kernarg-size] [--pair OLD=NEW ...] parent.s branch.s [more.s ...]
 
 For every .amdhsa_kernel of the first two files: the text from the kernel's label to the end of the function (every s_endpgm) and the
 .amdhsa_* descriptor block (registers, LDS, scratch) must be the same text.  Emission order is ignored.  Every further
 file must hold no kernel at all (host-only units).  Exit status 1 on any difference.  --pair OLD=NEW compares the parent's kernel
 OLD with the branch's kernel NEW (a kernel that was renamed, or became a template's instantiation): NEW's text is read with the name
-OLD in it.  A name that holds OLD or NEW as a substring is enough, as long as it fits one kernel.
+OLD in it.  A name that holds OLD or NEW as a substring is enough, as long as it fits one kernel.  --kernarg-size (first): the
+.amdhsa_kernarg_size line is left out of the comparison -- an argument struct that grew at its END moves no load of the fields in front.
 
 The listings come from
   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include --cuda-device-only -S UNIT.hip -o UNIT.s
@@ -15,8 +16,13 @@ import re
 import sys
 
 
+KERNARG_SIZE = False
+
+
 def kernels(path):
     lines = open(path).read().split("\n")
+    if KERNARG_SIZE:
+        lines = [ln for ln in lines if not ln.strip().startswith(".amdhsa_kernarg_size")]
     out = {}
     label = {ln.split(";")[0].strip(): i for i, ln in enumerate(lines) if ln[:1] not in (" ", "\t", "")}
     for i, ln in enumerate(lines):
@@ -42,7 +48,10 @@ def kernels(path):
 
 
 def main():
+    global KERNARG_SIZE
     argv, pairs = sys.argv[1:], []
+    if argv and argv[0] == "--kernarg-size":
+        KERNARG_SIZE, argv = True, argv[1:]
     while argv and argv[0] == "--pair":
         pairs.append(argv[1].split("="))
         argv = argv[2:]
