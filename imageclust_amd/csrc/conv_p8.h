@@ -22,6 +22,7 @@
 //   epilogue  in registers: pairs of accumulator tiles trade lane rows (v_permlane16_swap) so that a lane holds 8 consecutive channels of
 //             one pixel; y = relu(acc * scale + shift (+ residual)) in fp32, one rounding; 16-byte residual loads and stores
 #pragma once
+#include "conv_select.h"
 #include "mfma_tile.h"
 #include "resnet_fused.h"
 
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
         }
     };
 
-    const int nt = SPLIT ? p.K / 128 : p.K / 64;  // K-tiles of this workgroup (SPLIT: half of them; conv_p8_split_eligible: K % 256 == 0)
+    const int nt = SPLIT ? p.K / 128 : p.K / 64;  // K-tiles of this workgroup (SPLIT: half of them; conv_select.h, conv_p8_split_eligible: K % 256 == 0)
     const int kt0 = (SPLIT && role == 0) ? nt : 0; // its first K-tile
     const int nt1 = (p.KH * p.KW * p.Cin) / 64; // K-tiles of the first operand (== nt unless DUAL)
     // running position of the X half-tile being staged (XA(u), XB(u), XA(u + 1), ... in this order): uniform scalars
@@ -456,39 +457,6 @@ __global__ __launch_bounds__(512) void conv_p8_kernel(const conv_args p)
     else epilogue(std::false_type());
 }
 
-// Which layers take the deep-pipelined kernel (bf16 only): Cout a multiple of 256 (256 x 256 tile) or of 128 (512 x 128 tile), whole
-// K-tiles of 64 channels and an even number >= 4 of them.  ICL_CONV_P8_AUTO: K >= 512, whatever the tile count: with two forward passes
-// in flight (the timed configuration) fewer, longer tiles leave CUs to the other pass -- the 7 x 7 layers (98 tiles) take longer as
-// single launches than on the 128 x 128 kernels (293 vs 225 us for the three 3x3 layers) and the embedding as a whole is faster
-// (profiles/r05_ab_conv_p8_*.json).
-#ifndef P8_AUTO_MIN_NT
-#define P8_AUTO_MIN_NT 4 /* ICL_CONV_P8_AUTO: layers with K >= 256 (measured with two passes in flight: scratch/r5_batch*.sh) */
-#endif
-static int conv_p8_layout(const conv_args &a) { return a.Cout % 256 == 0 ? 1 : (a.Cout % 128 == 0 ? 2 : 0); } // 1: 2 x 4 waves, 2: 4 x 2 waves
-static bool conv_p8_eligible(const conv_args &a, int mode /* ctx->conv_p8: ICL_CONV_P8_* */)
-{
-    if (mode == 0) return false;
-    const int lay = conv_p8_layout(a);
-    if (!lay || a.Cin % 64 || (a.X2 && a.Cin2 % 64)) return false;
-    if (a.KH * a.KW > 9 || a.KH * a.KW * a.Cin + (a.X2 ? a.Cin2 : 0) != a.K) return false;
-    if (a.X2 && (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0)) return false;
-    const int nt = a.K / 64;
-    if (a.K % 128) return false; // an even number of K-tiles (the loop is unrolled by two buffers); nt == 2 runs the prologue and the two peeled tiles only
-    if ((size_t)a.B * a.H * a.W * a.Cin * 2 >= (1ull << 31) || (size_t)a.Cout * a.K * 2 >= (1ull << 31)) return false; // 32-bit buffer offsets, BN56_OOB = 2^31
-    if (a.X2 && (size_t)a.B * a.H2 * a.W2 * a.Cin2 * 2 >= (1ull << 31)) return false;
-    if (a.M >= (1ll << 31) - 512) return false;
-    if (mode >= 2) return true;
-    return nt >= P8_AUTO_MIN_NT;
-}
-
-// The split form (opt-in: ICL_CONV_SPLIT / ICL_CONV_SK=1): a rule on the LAYER's shape only (never on the batch: an image's embedding must not depend
-// on the images beside it) -- the 7 x 7 layers, whose 256 x 256 tiles number 0.38 per image.  It shortens a lone forward pass (3 476 -> 3 277 us per
-// batch of 256; the three 3x3 layers 321 -> 227 us) and costs the throughput configuration 1.1-1.5 % (two passes in flight: the CUs a 98-tile
-// launch leaves idle are the other pass's, and two half-K workgroups take more CU-time than one), hence off by default.
-static bool conv_p8_split_eligible(const icl_ctx *ctx, const conv_args &a)
-{
-    return ctx->conv_sk && !a.X2 && a.Ho * a.Wo <= 49 && a.K % 256 == 0 && a.K >= ctx->conv_sk_min_k && a.Cout % 256 == 0;
-}
 // the per-stream scratch of the split form: 256 KiB of partner sums + a flag per tile (flags compare against a per-slot launch counter: never reset)
 static int conv_p8_split_scratch(icl_ctx *ctx, hipStream_t strm, int tiles, conv_args &a)
 {
@@ -523,31 +491,28 @@ static int conv_p8_split_scratch(icl_ctx *ctx, hipStream_t strm, int tiles, conv
     return ICL_OK;
 }
 
+// c: conv_select's choice (family CONV_P8) for a, whose gx and gy are the choice's.  Returns whether the split form ran: it is what the choice
+// wanted AND its scratch could be had (otherwise: one workgroup per tile).
 template <int MW, int NWV, bool X3>
-static void launch_conv_p8_t(icl_ctx *ctx, conv_args &a)
+static bool launch_conv_p8_t(icl_ctx *ctx, conv_args &a, const conv_choice &c)
 {
-    typedef p8_geom<MW, NWV> G;
     hipStream_t strm = ctx->cur_stream ? ctx->cur_stream : ctx->stream;
-    a.gx = (int)icl_ceil_div(a.M, G::BM);
-    a.gy = a.Cout / G::BN;
-    const bool taps = a.KH * a.KW > 1 || a.pad != 0;
-    if constexpr (NWV == 4 && !X3) { // (the split form is bf16 only: under BF16X3 it is ignored)
-        if (conv_p8_split_eligible(ctx, a) && conv_p8_split_scratch(ctx, strm, a.gx * a.gy, a) == ICL_OK) {
-            const dim3 grid2((unsigned)(2 * a.gx * a.gy));
-            if (taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, true>), grid2, dim3(512), 0, strm, a);
+    if constexpr (NWV == 4 && !X3) {
+        if (c.split && conv_p8_split_scratch(ctx, strm, (int)c.blocks, a) == ICL_OK) {
+            const dim3 grid2(2 * c.blocks);
+            if (c.taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, true>), grid2, dim3(512), 0, strm, a);
             else hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, false, true>), grid2, dim3(512), 0, strm, a);
-            ++ctx->conv_sk_launches;
-            return;
+            return true;
         }
     }
-    const dim3 grid((unsigned)(a.gx * a.gy));
-    if (a.X2) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, true, false, X3>), grid, dim3(512), 0, strm, a);
-    else if (taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, false, X3>), grid, dim3(512), 0, strm, a);
+    const dim3 grid(c.blocks);
+    if (c.dual) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, true, false, X3>), grid, dim3(512), 0, strm, a);
+    else if (c.taps) hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, true, false, false, X3>), grid, dim3(512), 0, strm, a);
     else hipLaunchKernelGGL((conv_p8_kernel<MW, NWV, false, false, false, X3>), grid, dim3(512), 0, strm, a);
+    return false;
 }
 template <bool X3 = false>
-static void launch_conv_p8(icl_ctx *ctx, conv_args &a)
+static bool launch_conv_p8(icl_ctx *ctx, conv_args &a, const conv_choice &c)
 {
-    if (conv_p8_layout(a) == 1) launch_conv_p8_t<2, 4, X3>(ctx, a);
-    else launch_conv_p8_t<4, 2, X3>(ctx, a);
+    return c.layout == 1 ? launch_conv_p8_t<2, 4, X3>(ctx, a, c) : launch_conv_p8_t<4, 2, X3>(ctx, a, c);
 }

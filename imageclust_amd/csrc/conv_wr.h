@@ -17,6 +17,7 @@
 // the residual and the output stay full-size tensors and row m is their pixel prune_map_pixel(pm, m) -- one offset for the residual load and
 // the store, nothing else differs.  The instantiations without MAP are the code they were before the flag (profiles/r37_isa_compare.txt).
 #pragma once
+#include "conv_select.h"
 #include "mfma_tile.h"
 #include "prune_map.h"
 #include "resnet_fused.h"
@@ -227,35 +228,6 @@ __global__ __launch_bounds__(256, (K == 256 && MT == 2) ? 3 : 2) void conv_wr_ke
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (LDS-DMA of tiles past the end: zeros into LDS nobody reads; drained before the wave ends)
 }
 
-// The HBM-bound 1x1 layers (stride 1, pad 0, no second operand): the identity bottlenecks' c3 (K = 128 / 256 / 512, Cout = 4 K, residual) and
-// stage 2's c1 (K = 512, Cout = 128).  Slice width / tile height by K so that the weights fit 64-128 VGPRs and two workgroups fit a CU's LDS.
-static bool conv_wr_shape(const conv_args &a, int *ns, int *pt)
-{
-    static const int pt256 = [] { // A/B knob: tile height of the K = 256 layers (ICL_WR_PT256 = 32 | 64)
-        const char *e = getenv("ICL_WR_PT256");
-        return e && atoi(e) == 32 ? 32 : 64;
-    }();
-    if (a.K == 128) { *ns = 256; *pt = 64; }
-    else if (a.K == 256) { *ns = 128; *pt = pt256; }
-    else if (a.K == 512) { *ns = 128; *pt = 32; }
-    else return false;
-    return a.Cout % *ns == 0;
-}
-static bool conv_wr_eligible(const conv_args &a, int mode)
-{
-    if (mode == 0 || a.X2 || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.Cin != a.K) return false;
-    int ns, pt;
-    if (!conv_wr_shape(a, &ns, &pt)) return false;
-    if (a.omap.sub && (a.K > 256 || pt != 64)) return false; // the mapped form exists for the 64-pixel tiles of K = 128 / 256
-    if (a.K == 512 && a.Cout > 128 && a.Cout < 2048) return false; // (1024 -> ... K = 512 shapes other than 512 -> 128 / 512 -> 2048 do not occur; stride-2 c1 layers are not eligible anyway)
-    if ((size_t)a.M * a.K * 2 >= (1ull << 31) || (size_t)a.M * a.Cout * 2 >= (1ull << 31)) return false; // 32-bit buffer offsets, BN56_OOB = 2^31
-    if (a.omap.sub) { // the mapped form: the compact pixels are those of the map, and the FULL tensor stays below 2^31 bytes
-        const prune_map &pm = a.omap;
-        if (pm.sub < 1 || pm.Ho != prune_extent(pm.H, pm.sub) || pm.Wo != prune_extent(pm.W, pm.sub) || a.Ho != pm.Ho || a.Wo != pm.Wo) return false;
-        if ((size_t)a.B * pm.H * pm.W * a.Cout * 2 >= (1ull << 31)) return false;
-    }
-    return true;
-}
 template <int K, int NS, int MT>
 static void launch_conv_wr_t(hipStream_t strm, const wr_args &w, dim3 grid, bool res)
 {
@@ -269,25 +241,19 @@ static void launch_conv_wr_t(hipStream_t strm, const wr_args &w, dim3 grid, bool
     if (res) hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, true>), grid, dim3(256), 0, strm, w);
     else hipLaunchKernelGGL((conv_wr_kernel<K, NS, MT, false>), grid, dim3(256), 0, strm, w);
 }
-static void launch_conv_wr(icl_ctx *ctx, const conv_args &a)
+// c: conv_select's choice (family CONV_WR) for a
+static void launch_conv_wr(icl_ctx *ctx, const conv_args &a, const conv_choice &c)
 {
     hipStream_t strm = ctx->cur_stream ? ctx->cur_stream : ctx->stream;
     wr_args w;
     w.X = (const uint16_t *)a.X; w.W = (const uint16_t *)a.Wt; w.R = (const uint16_t *)a.R; w.Y = (uint16_t *)a.Y;
     w.scale = a.scale; w.shift = a.shift; w.M = (int)a.M; w.N = a.Cout; w.relu = a.relu;
     w.pm = a.omap;
-    int ns = 0, pt = 0;
-    (void)conv_wr_shape(a, &ns, &pt);
-    w.nslices = a.Cout / ns;
-    const int ntiles = (int)icl_ceil_div(a.M, pt);
-    const int per_cu = (a.K == 256 && pt == 32) ? 3 : 2; // workgroups per CU the LDS (2 x image) and the registers allow
-    const int slots = per_cu * ctx->prop.multiProcessorCount;
-    int nworkers = std::max(8, (slots / w.nslices) & ~7);
-    nworkers = std::min(nworkers, (int)icl_ceil_div(ntiles, 8) * 8);
-    w.nworkers = nworkers;
-    const dim3 grid((unsigned)(w.nslices * nworkers));
-    if (a.K == 128) launch_conv_wr_t<128, 256, 4>(strm, w, grid, a.R != nullptr);
-    else if (a.K == 256 && pt == 64) launch_conv_wr_t<256, 128, 4>(strm, w, grid, a.R != nullptr);
-    else if (a.K == 256) launch_conv_wr_t<256, 128, 2>(strm, w, grid, a.R != nullptr);
-    else launch_conv_wr_t<512, 128, 2>(strm, w, grid, a.R != nullptr);
+    w.nslices = c.slices;
+    w.nworkers = c.workers;
+    const dim3 grid(c.blocks);
+    if (c.wr_k == 128) launch_conv_wr_t<128, 256, 4>(strm, w, grid, c.res);
+    else if (c.wr_k == 256 && c.wr_mt == 4) launch_conv_wr_t<256, 128, 4>(strm, w, grid, c.res);
+    else if (c.wr_k == 256) launch_conv_wr_t<256, 128, 2>(strm, w, grid, c.res);
+    else launch_conv_wr_t<512, 128, 2>(strm, w, grid, c.res);
 }

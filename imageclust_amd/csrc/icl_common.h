@@ -135,7 +135,7 @@ struct icl_ctx {
     std::string err;
     hipDeviceProp_t prop;
     int batch = 256;
-    int64_t conv_launches[2] = {0, 0}; // [0] conv_p8_kernel, [1] the other convolution kernels (icl_conv_stats)
+    int64_t conv_launches[2] = {0, 0}; // [0] conv_wr_kernel and conv_p8_kernel, [1] the 128 x BN kernels (conv_choice::counter; icl_conv_stats)
     int conv_wr = 1; // the streaming kernel for the HBM-bound c3 layers (conv_wr.h); ICL_CONV_WR=0 turns it off for A/B runs
     int conv_sk = 0; // latency mode: the 7 x 7 layers' tiles on two workgroups each (conv_p8.h, SPLIT; icl_set_conv_options | ICL_CONV_SPLIT, ICL_CONV_SK=1)
     int conv_sk_min_k = 2048; // ... for layers with at least this K (the K = 1024 layer loses: 30 -> 37 us; ICL_CONV_SK_MINK = 512 ... for A/B runs)

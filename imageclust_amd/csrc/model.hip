@@ -3,6 +3,7 @@
 //
 // Replaces LoadPretrainedModelONNX (internal/embeddings/embeddings.go:28-43); the ONNX graph itself is read by onnx_reader.hip.
 #include "icl_common.h"
+#include "resnet50_topology.h"
 #include "resnet_model.h"
 
 #include <cmath>
@@ -11,27 +12,6 @@
 #include <memory>
 #include <new>
 #include <vector>
-
-static int resnet50_topology(icl_conv_rec *out)
-{
-    static const int nblocks[4] = {3, 4, 6, 3};
-    int n = 0;
-    out[n++] = icl_conv_rec{3, 64, 7, 2, 3, 224, 112, 0, 0, 0};
-    int h = 56, cin = 64;
-    for (int s = 0; s < 4; ++s) {
-        const int cout = 256 << s, mid = cout / 4;
-        for (int b = 0; b < nblocks[s]; ++b) {
-            const int stride = (b == 0 && s > 0) ? 2 : 1, ho = h / stride;
-            out[n++] = icl_conv_rec{cin, mid, 1, stride, 0, h, ho, 1, s + 1, b};
-            out[n++] = icl_conv_rec{mid, mid, 3, 1, 1, ho, ho, 2, s + 1, b};
-            out[n++] = icl_conv_rec{mid, cout, 1, 1, 0, ho, ho, 3, s + 1, b};
-            if (b == 0) out[n++] = icl_conv_rec{cin, cout, 1, stride, 0, h, ho, 4, s + 1, b};
-            cin = cout;
-            h = ho;
-        }
-    }
-    return n;
-}
 
 static int64_t blob_floats(const icl_blob_header &h)
 {

@@ -12,6 +12,7 @@
 // .op_type=4, .attribute=5; AttributeProto.name=1, .f=2, .i=3, .floats=7, .ints=8; TensorProto.dims=1, .data_type=2,
 // .float_data=4, .name=8, .raw_data=9.
 #include "icl_common.h"
+#include "resnet50_topology.h"
 
 #include <cstring>
 #include <map>
@@ -192,27 +193,6 @@ static bool parse_node(const span &s, onnx_node &n)
     return r.ok;
 }
 
-static int resnet50_topology_onnx(icl_conv_rec *out)
-{
-    static const int nblocks[4] = {3, 4, 6, 3};
-    int n = 0;
-    out[n++] = icl_conv_rec{3, 64, 7, 2, 3, 224, 112, 0, 0, 0};
-    int h = 56, cin = 64;
-    for (int s = 0; s < 4; ++s) {
-        const int cout = 256 << s, mid = cout / 4;
-        for (int b = 0; b < nblocks[s]; ++b) {
-            const int stride = (b == 0 && s > 0) ? 2 : 1, ho = h / stride;
-            out[n++] = icl_conv_rec{cin, mid, 1, stride, 0, h, ho, 1, s + 1, b};
-            out[n++] = icl_conv_rec{mid, mid, 3, 1, 1, ho, ho, 2, s + 1, b};
-            out[n++] = icl_conv_rec{mid, cout, 1, 1, 0, ho, ho, 3, s + 1, b};
-            if (b == 0) out[n++] = icl_conv_rec{cin, cout, 1, stride, 0, h, ho, 4, s + 1, b};
-            cin = cout;
-            h = ho;
-        }
-    }
-    return n;
-}
-
 } // namespace
 
 static int onnx_to_blob_impl(icl_ctx *ctx, const char *path, std::vector<char> &blob);
@@ -296,7 +276,7 @@ static int onnx_to_blob_impl(icl_ctx *ctx, const char *path, std::vector<char> &
         for (size_t q = 0; q < ndata; ++q) cons.insert({n.in[q], &n});
     }
     icl_conv_rec topo[ICL_RESNET50_NCONV];
-    const int nconv = resnet50_topology_onnx(topo);
+    const int nconv = resnet50_topology(topo);
     if ((int)n_conv_nodes != nconv || !gemm)
         return icl_fail(ctx, ICL_ERR_IO, "%s: expected a ResNet50-v1 graph (53 Conv + 1 Gemm), found %zu Conv%s", path, n_conv_nodes, gemm ? "" : ", no Gemm");
     auto readers = [&](const std::string &t, const char *op) {

@@ -6,9 +6,11 @@
 // PreprocessImage (:46-116) is image_io.hip.  This unit holds the kernels, the launch dispatch, the forward pass and the embed drivers;
 // the model and its loader are model.hip, icl_embed_file's coalescing queue is embed_file.hip, what they share is resnet_model.h.
 //
-// Layout: activations NHWC (channels contiguous) in bf16 (throughput) or f32 (parity); weights re-packed once
+// Layout: activations NHWC (channels contiguous) in bf16 (throughput), split bf16 or f32 (parity); weights re-packed once
 // at load to [Cout][KH][KW][Cin] so every implicit-GEMM K-chunk is a contiguous run of input channels of ONE
-// filter tap.  Every convolution is one launch of conv_igemm_kernel: a 128(pixels) x BN(channels) output tile
+// filter tap.  Which kernel a convolution takes is decided in conv_select.h (conv_wr_kernel, conv_p8_kernel, conv3x3_halo_kernel or
+// conv_igemm_kernel, in that order of precedence); launch_conv_t is that choice followed by one switch.  The kernels of this file are the
+// 128 x BN ones: conv_igemm_kernel computes a 128(pixels) x BN(channels) output tile
 // per 256-thread workgroup, K staged through XOR-swizzled LDS in 64-byte row chunks, v_mfma_f32_32x32x16_bf16
 // (or v_mfma_f32_32x32x2_f32 in parity mode) with the WEIGHTS as the MFMA A operand so that each lane ends up
 // holding 4 consecutive output channels of one pixel -> contiguous NHWC stores; BatchNorm (folded to
@@ -17,7 +19,6 @@
 // performs the reference's RGB/255 scaling (embeddings.go:96).
 #include "icl_common.h"
 #include "mfma_tile.h"
-#include "prune_map.h"
 #include "resnet_model.h"
 
 #include <algorithm>
@@ -29,30 +30,9 @@
 #include <type_traits>
 #include <vector>
 
-struct conv_args {
-    const void *X;      // [B][H][W][Cin]
-    const void *Wt;     // [Cout][KH][KW][Cin]
-    void *Y;            // [B][Ho][Wo][Cout]
-    const void *R;      // residual, same shape as Y, or nullptr
-    const float *scale; // [Cout] folded BN scale
-    const float *shift; // [Cout] folded BN shift (+ conv bias)
-    const void *zero;   // >= 16 zero bytes: the source of padded taps / rows beyond M for the LDS-DMA loads
-    int B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, relu;
-    int64_t M;          // B*Ho*Wo
-    int K;              // KH*KW*Cin
-    int gx, gy;         // tiles along M and along Cout
-    // optional second operand (DUAL kernels): a 1x1 / stride2 convolution over X2 accumulated into the SAME tile, i.e.
-    // the K axis is [KH*KW*Cin of X | Cin2 of X2].  Used to fuse a bottleneck's downsample branch into its last conv.
-    const void *X2;     // [B][H2][W2][Cin2]
-    int H2, W2, Cin2, stride2;
-    // split form of conv_p8_kernel (conv_p8.h): partner sums, one flag per tile, the value the flags are raised to by this launch
-    void *sk_part;
-    int *sk_flag;
-    int sk_epoch;
-    // optional output-pixel map (conv_wr_kernel's MAP form only; omap.sub == 0: none): X is the compact [B][Ho][Wo][Cin] tensor, R and Y are
-    // full-size [B][omap.H][omap.W][Cout] tensors in which output pixel (b, oy, ox) is pixel (b, sub * oy, sub * ox) -- prune_map.h
-    prune_map omap;
-};
+#include "conv_select.h" // conv_args, the kernel choice
+static_assert(CONV_PREC_FP32 == ICL_PREC_FP32 && CONV_PREC_BF16 == ICL_PREC_BF16 && CONV_PREC_BF16X3 == ICL_PREC_BF16X3 && CONV_TILE_M == CV_BM && CONV_ROW_BYTES == CV_ROWB,
+              "conv_select.h restates these constants");
 
 #include "resnet_fused.h"
 #include "conv_p8.h"
@@ -379,7 +359,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const conv_args p)
 //   rows of a neighbouring IMAGE that fall into the halo are loaded like any other row; a lane whose output row is the first /
 //   last of its image reads the three "zero pixels" behind the image instead (the conv's zero padding).
 // ------------------------------------------------------------------------------------------------------------
-#define HALO_MAXP 12 /* halo pieces (8 pixels x 128 B) a wave fetches per channel chunk: tiles of up to 384 halo pixels */
+// (HALO_MAXP, conv_select.h: halo pieces of 8 pixels x 128 B a wave fetches per channel chunk, i.e. tiles of up to 384 halo pixels)
 // HALO_WS weight stages: 3 (two k-steps of weights in flight) where two workgroups still fit a CU's 160 KB of LDS, else 2 --
 // measured (W = 28, Cin = 128: 81 KB with three stages): one workgroup per CU costs 37 % on that layer, the third stage gains 0-2 % elsewhere
 template <typename T, int BN, int HALO_WS>
@@ -526,39 +506,12 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const conv_args p, in
     conv_epilogue<T, BN>(p, smem, acc, m0, n0, tid, wm, wn, fr, fh, conv_resid<T, BN>());
 }
 
-// halo pieces per wave for an image width (0: the shape does not fit the halo kernel)
-static int conv3x3_halo_npw(int W)
+// c: conv_select's choice (family CONV_HALO) for a, whose gx and gy are the choice's
+template <typename T, int BN, int RING>
+static void launch_conv3x3_halo(icl_ctx *ctx, const conv_args &a, const conv_choice &c)
 {
-    const int rows = (W - 1 + CV_BM - 1) / W + 1 + 2; // image rows a run of 128 pixels can touch, plus one above and below
-    const int pieces = (rows * (W + 2) + 7) / 8;
-    const int npw = (pieces + 3) / 4;
-    return npw <= HALO_MAXP ? npw : 0;
-}
-template <int BN>
-static size_t conv3x3_halo_lds(int npw, int ws)
-{
-    const size_t body = (size_t)4 * npw * 1024 + 512 + (size_t)ws * BN * CV_ROWB, ep = (size_t)64 * (BN + 4) * 4;
-    return body > ep ? body : ep;
-}
-template <typename T, int BN>
-static void launch_conv3x3_halo(icl_ctx *ctx, conv_args &a, int npw)
-{
-    hipStream_t strm = ctx->cur_stream ? ctx->cur_stream : ctx->stream;
-    a.gy = a.Cout / BN;
-    if (conv3x3_halo_lds<BN>(npw, 3) <= 80 * 1024) {
-        icl_lds_optin(ctx, (const void *)conv3x3_halo_kernel<T, BN, 3>, (int)conv3x3_halo_lds<BN>(HALO_MAXP, 3));
-        hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, 3>), dim3((unsigned)(a.gx * a.gy)), dim3(256), conv3x3_halo_lds<BN>(npw, 3), strm, a, npw);
-    } else {
-        icl_lds_optin(ctx, (const void *)conv3x3_halo_kernel<T, BN, 2>, (int)conv3x3_halo_lds<BN>(HALO_MAXP, 2));
-        hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, 2>), dim3((unsigned)(a.gx * a.gy)), dim3(256), conv3x3_halo_lds<BN>(npw, 2), strm, a, npw);
-    }
-}
-
-template <int BN>
-static constexpr size_t conv_lds_bytes(int nstages = 2)
-{
-    const size_t stages = (size_t)nstages * (BN + CV_BM) * CV_ROWB, ep = (size_t)64 * (BN + 4) * 4;
-    return stages > ep ? stages : ep;
+    icl_lds_optin(ctx, (const void *)conv3x3_halo_kernel<T, BN, RING>, (int)conv3x3_halo_lds(BN, HALO_MAXP, RING));
+    hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, RING>), dim3(c.blocks), dim3(c.threads), c.lds, ctx->cur_stream ? ctx->cur_stream : ctx->stream, a, c.npw);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -780,108 +733,79 @@ __global__ __launch_bounds__(256) void fc_kernel(const float *__restrict__ x, co
 // ------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------
-template <typename T, int BN, bool DUAL, int NST, bool EARLY = false>
-static void launch_conv_variant(icl_ctx *ctx, conv_args &a, int nst_lds)
+// c: conv_select's choice (family CONV_IGEMM) for a, whose gx and gy are the choice's
+template <typename T, int BN, bool DUAL, bool EARLY>
+static void launch_conv_igemm(icl_ctx *ctx, const conv_args &a, const conv_choice &c)
 {
-    icl_lds_optin(ctx, (const void *)conv_igemm_kernel<T, BN, DUAL, NST, EARLY>, (int)conv_lds_bytes<BN>(NST)); // > 64 KiB of dynamic LDS
-    a.gy = a.Cout / BN;
-    hipLaunchKernelGGL((conv_igemm_kernel<T, BN, DUAL, NST, EARLY>), dim3((unsigned)(a.gx * a.gy)), dim3(256), conv_lds_bytes<BN>(nst_lds), ctx->cur_stream ? ctx->cur_stream : ctx->stream,
-                       a);
+    icl_lds_optin(ctx, (const void *)conv_igemm_kernel<T, BN, DUAL, 2, EARLY>, (int)conv_igemm_lds(BN, 2)); // > 64 KiB of dynamic LDS
+    hipLaunchKernelGGL((conv_igemm_kernel<T, BN, DUAL, 2, EARLY>), dim3(c.blocks), dim3(c.threads), c.lds, ctx->cur_stream ? ctx->cur_stream : ctx->stream, a);
 }
 
-// Tile / pipeline choice (B=256 shapes of ResNet50, measured with scratch/layer_report.py): 128x128 tile (128x64 for
-// Cout = 64), two stages, two workgroups per CU, everything requested up front (EARLY).  ICL_CONV_MODE=0 selects the
-// plain two-stage loop (one k-step staged ahead) for A/B comparisons.  Deeper rings (three / four stages, one workgroup
-// per CU), 128x64 tiles for the 128-wide layers, weights in registers and dedicated loader waves were all measured
-// slower.
-// BF16X3: a is given in real channels; the kernels see the split layout as bf16 tensors of twice the channels (Cin, Cin2 and K doubled,
-// Cout -- the rows of the weights and of the accumulator tile -- unchanged).  Every layer goes to conv_p8_kernel or the 128 x 128 kernels,
-// chosen by shape as for bf16; conv_wr_kernel has no split form ("Split bf16").
+// What conv_select reads besides the shape, from the context and the environment.  ICL_CONV_MODE, ICL_FUSE and ICL_WR_PT256 (A/B measurements
+// and the tests that compare the forms) are read here, once per process, and nowhere else.
+//   ICL_CONV_MODE  0 = plain two-stage loop, 2 = no halo kernel for the 3x3 layers (default 1)
+//   ICL_WR_PT256   tile height of conv_wr_kernel's K = 256 layers, 32 | 64 (default 64)
+//   ICL_FUSE       bit 0 stem + maxpool in one launch, bit 1 the identity bottlenecks of stage 1 in one launch each, bit 2 stage 1's first
+//                  bottleneck (downsample branch), bit 3 (with bit 0, bf16) the stem that reads its B operand straight from a bf16 patch
+//                  (stem2_pool_kernel).  Default: all.
+struct fwd_env {
+    int conv_mode, wr_pt256, fuse;
+};
+static const fwd_env &forward_env()
+{
+    static const fwd_env e = [] {
+        const char *m = getenv("ICL_CONV_MODE"), *p = getenv("ICL_WR_PT256"), *f = getenv("ICL_FUSE");
+        return fwd_env{m ? atoi(m) : 1, p && atoi(p) == 32 ? 32 : 64, f ? atoi(f) : 15};
+    }();
+    return e;
+}
+static int fuse_mask() { return forward_env().fuse; }
+static conv_opts conv_opts_of(const icl_ctx *ctx)
+{
+    const fwd_env &e = forward_env();
+    return conv_opts{ctx->conv_p8, ctx->conv_wr, ctx->conv_sk, ctx->conv_sk_min_k, e.conv_mode, e.wr_pt256, ctx->prop.multiProcessorCount};
+}
+
+// One convolution by its choice (conv_select.h): one switch over the family.  a is given in real channels; the kernels get their own view of it
+// (conv_kernel_view: the split layout of BF16X3 as bf16 tensors of twice the channels) with the choice's tile counts.
 template <typename T>
-static int launch_conv_t(icl_ctx *ctx, conv_args a)
+static int launch_conv_t(icl_ctx *ctx, int prec, const conv_args &real, const conv_choice &c)
 {
     constexpr bool X3 = is_x3<T>::value;
-    const double flops = 2.0 * (double)a.M * a.Cout * a.K;
-    if (X3) {
-        a.Cin *= 2;
-        a.Cin2 *= 2;
-        a.K *= 2;
+    if (c.family == CONV_UNSUPPORTED) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "%s", c.why);
+    conv_args a = conv_kernel_view(prec, real);
+    a.gx = c.gx;
+    a.gy = c.gy;
+    icl_prof_scope ps(ctx, a.Cout % 128 == 0 ? ICL_K_CONV : ICL_K_CONV64, 2.0 * (double)real.M * real.Cout * real.K, 0.0);
+    bool split = false;
+    switch (c.family) {
+    case CONV_WR:
+        launch_conv_wr(ctx, a, c);
+        break;
+    case CONV_P8:
+        if constexpr (std::is_same<T, BF16>::value || X3) split = launch_conv_p8<X3>(ctx, a, c);
+        break;
+    case CONV_HALO:
+        if (c.bn == 128) c.ring == 3 ? launch_conv3x3_halo<T, 128, 3>(ctx, a, c) : launch_conv3x3_halo<T, 128, 2>(ctx, a, c);
+        else c.ring == 3 ? launch_conv3x3_halo<T, 64, 3>(ctx, a, c) : launch_conv3x3_halo<T, 64, 2>(ctx, a, c);
+        break;
+    default: // CONV_IGEMM
+        if (c.dual) c.early ? launch_conv_igemm<T, 128, true, true>(ctx, a, c) : launch_conv_igemm<T, 128, true, false>(ctx, a, c);
+        else if (c.bn == 128) c.early ? launch_conv_igemm<T, 128, false, true>(ctx, a, c) : launch_conv_igemm<T, 128, false, false>(ctx, a, c);
+        else c.early ? launch_conv_igemm<T, 64, false, true>(ctx, a, c) : launch_conv_igemm<T, 64, false, false>(ctx, a, c);
     }
-    a.gx = (int)icl_ceil_div(a.M, CV_BM);
-    const int nk = a.K / T::BK;
-    static const int mode = [] { // ICL_CONV_MODE (A/B measurements): 0 = plain two-stage loop, 2 = no halo kernel for the 3x3 layers
-        const char *e = getenv("ICL_CONV_MODE");
-        return e ? atoi(e) : 1;
-    }();
-    const bool early = mode != 0;
-    const bool wide = a.Cout % 128 == 0;
-    icl_prof_scope ps(ctx, wide ? ICL_K_CONV : ICL_K_CONV64, flops, 0.0);
-    // the HBM-bound c3 layers of the identity bottlenecks: weights in registers, streaming tiles (conv_wr.h)
-    if (std::is_same<T, BF16>::value && ctx->conv_wr && conv_wr_eligible(a, ctx->conv_p8)) {
-        launch_conv_wr(ctx, a);
-        ++ctx->conv_launches[0];
-        ICL_HIP(ctx, hipGetLastError());
-        return ICL_OK;
-    }
-    if (a.omap.sub) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv: only the streaming 1x1 kernel writes through an output-pixel map (bf16, K = 128 or 256)");
-    // the K-heavy layers: 256 x 256 tiles on the deep-pipelined loop (conv_p8.h)
-    if ((std::is_same<T, BF16>::value || X3) && conv_p8_eligible(a, ctx->conv_p8)) {
-        launch_conv_p8<X3>(ctx, a);
-        ++ctx->conv_launches[0];
-        ICL_HIP(ctx, hipGetLastError());
-        return ICL_OK;
-    }
-    ++ctx->conv_launches[1];
-    // (Cin = 64, stage 1: one channel chunk, 9 short k-steps per tile -- nothing to hide the halo fetch behind, the implicit-GEMM
-    // kernel's fully pipelined staging is 3-5 % faster there although it moves three times the bytes)
-    if (mode == 1 && !a.X2 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Ho == a.H && a.Wo == a.W && a.Cin >= 128) {
-        const int npw = conv3x3_halo_npw(a.W); // every 3x3 layer of ResNet50 (W = 56, 28, 14, 7) fits
-        if (npw) {
-            if (wide) launch_conv3x3_halo<T, 128>(ctx, a, npw);
-            else launch_conv3x3_halo<T, 64>(ctx, a, npw);
-            ICL_HIP(ctx, hipGetLastError());
-            return ICL_OK;
-        }
-    }
-    const int nst = nk > 1 ? 2 : 1; // single-k-step layers need one stage only -> more workgroups per CU
-    if (a.X2) {
-        if (early) launch_conv_variant<T, 128, true, 2, true>(ctx, a, 2);
-        else launch_conv_variant<T, 128, true, 2>(ctx, a, 2);
-    } else if (wide) {
-        if (early) launch_conv_variant<T, 128, false, 2, true>(ctx, a, nst);
-        else launch_conv_variant<T, 128, false, 2>(ctx, a, nst);
-    } else {
-        if (early) launch_conv_variant<T, 64, false, 2, true>(ctx, a, nst);
-        else launch_conv_variant<T, 64, false, 2>(ctx, a, nst);
-    }
+    ++ctx->conv_launches[c.counter];
+    ctx->conv_sk_launches += split;
     ICL_HIP(ctx, hipGetLastError());
     return ICL_OK;
 }
 
 static int launch_conv_prec(icl_ctx *ctx, int prec, const conv_args &a)
 {
-    return with_prec(prec, [&](auto t) { return launch_conv_t<decltype(t)>(ctx, a); });
+    const conv_choice c = conv_select(prec, a, conv_opts_of(ctx));
+    return with_prec(prec, [&](auto t) { return launch_conv_t<decltype(t)>(ctx, prec, a, c); });
 }
 
-// A plain k x k convolution over square B x H x H x Cin images: no second operand; the launchers set the tile counts (gx, gy) and
-// the split-form fields.
-static inline conv_args conv_plain(const void *X, const void *Wt, void *Y, const void *R, const float *scale, const float *shift, const void *zero, int B,
-                                   int H, int Cin, int Cout, int k, int stride, int pad, int relu)
-{
-    conv_args a = {};
-    a.X = X; a.Wt = Wt; a.Y = Y; a.R = R; a.scale = scale; a.shift = shift; a.zero = zero;
-    a.B = B; a.H = a.W = H; a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = k; a.stride = stride; a.pad = pad; a.relu = relu;
-    a.Ho = a.Wo = (H + 2 * pad - k) / stride + 1;
-    a.M = (int64_t)B * a.Ho * a.Wo;
-    a.K = k * k * Cin;
-    return a;
-}
-// ... plus a 1x1 / stride2 convolution over X2 ([B][H2][H2][Cin2]) accumulated into the same tiles: K = [k*k*Cin of X | Cin2 of X2]
-static inline void conv_add_operand(conv_args &a, const void *X2, int H2, int Cin2, int stride2)
-{
-    a.X2 = X2; a.H2 = a.W2 = H2; a.Cin2 = Cin2; a.stride2 = stride2;
-    a.K += Cin2;
-}
 // the 7x7/2 stem of the loaded model (Y: the 112 x 112 x 64 tensor, or the pooled one of the fused kernels), gx work units
 static inline conv_args conv_stem(const icl_model *m, const void *Wt, void *Y, int B, int gx)
 {
@@ -891,16 +815,6 @@ static inline conv_args conv_stem(const icl_model *m, const void *Wt, void *Y, i
     a.gx = gx;
     a.gy = 1;
     return a;
-}
-
-static int launch_conv(icl_ctx *ctx, int prec, const conv_layer &L, const void *X, void *Y, const void *R, int relu, int B)
-{
-    const icl_conv_rec &r = L.rec;
-    const conv_args a = conv_plain(X, L.w[prec], Y, R, L.scale, L.shift, ctx->model->zero, B, r.hin, r.cin, r.cout, r.k, r.stride, r.pad, relu);
-    if (a.M >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv: %lld output pixels exceed the kernel's 32-bit pixel index", (long long)a.M);
-    if (a.Ho != r.hout || a.Cin % prec_bk(prec) || a.Cout % 64 || a.K != L.K)
-        return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "conv shape cin=%d cout=%d k=%d not supported by the implicit-GEMM kernel", a.Cin, a.Cout, a.KH);
-    return launch_conv_prec(ctx, prec, a);
 }
 
 // ---- per-layer entry points of the parity tests: host tensors in, host tensors out -----------------------------------------
@@ -1031,44 +945,33 @@ extern "C" int icl_conv1x1_mapped(icl_ctx *ctx, const float *x, int B, int H, in
         conv_args a = conv_plain(dx.p, dw.p, dy.p, dr.p, (const float *)dsc.p, (const float *)dsh.p, dz.p, B, pm.Ho, Cin, Cout, 1, 1, 0, relu);
         a.omap = pm;
         io.returns(prec, dy.p, ny);
-        if (!ctx->conv_wr || !conv_wr_eligible(a, ctx->conv_p8)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv1x1_mapped: Cin = %d, Cout = %d is no shape of the streaming kernel's mapped form", Cin, Cout);
+        if (conv_select(prec, a, conv_opts_of(ctx)).family != CONV_WR) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "icl_conv1x1_mapped: Cin = %d, Cout = %d is no shape of the streaming kernel's mapped form", Cin, Cout);
         return launch_conv_prec(ctx, prec, a);
     });
 }
 
-// Block 0 of a stage: y = relu(bn3(conv3(t2)) + bn_ds(conv_ds(x))) as ONE dual-operand launch (BN scales folded into
-// the concatenated weights): the downsample tensor is never written to or read back from HBM.
-static int launch_conv_fused_ds(icl_ctx *ctx, int prec, const conv_layer &c3, const conv_layer &ds, const void *t2, const void *x, void *y, int B)
+// workgroups per CU of the stem kernel a precision takes under an ICL_FUSE mask (forward_make_plan: stem2_pool_kernel, stem_pool_kernel or stem_conv_kernel)
+static int stem_per_cu(int prec, int fuse)
 {
-    conv_args a = conv_plain(t2, c3.wfused[prec], y, nullptr, ctx->model->ones, c3.shift_fused, ctx->model->zero, B, c3.rec.hout, c3.rec.cin, c3.rec.cout, 1, 1, 0, 1);
-    conv_add_operand(a, x, ds.rec.hin, ds.rec.cin, ds.rec.stride);
-    const int bk = prec_bk(prec);
-    if (a.Cin % bk || a.Cin2 % bk || a.Cout % 128) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused downsample shape not supported");
-    return launch_conv_prec(ctx, prec, a);
+    const size_t cu_lds = (size_t)160 * 1024;
+    if (prec == ICL_PREC_BF16 && (fuse & 1) && (fuse & 8)) return std::max<int>(1, std::min<int>(5, (int)(cu_lds / stem2_lds_bytes())));
+    if (prec == ICL_PREC_BF16X3 || (fuse & 1)) return std::max<int>(1, (int)(cu_lds / (prec == ICL_PREC_BF16 ? stem_pool_lds_bytes<BF16>() : stem_pool_lds_bytes<F32>())));
+    return std::max<int>(1, (int)(cu_lds / (prec == ICL_PREC_BF16 ? stem_lds_bytes<BF16>() : stem_lds_bytes<F32>())));
+}
+static fwd_opts forward_opts_of(const icl_ctx *ctx, int prec)
+{
+    return fwd_opts{conv_opts_of(ctx), fuse_mask(), ctx->fwd_prune, stem_per_cu(prec, fuse_mask())};
 }
 
-// ICL_FUSE (A/B measurements and the fused == unfused tests): bit 0 stem + maxpool in one launch, bit 1 the identity
-// bottlenecks of stage 1 in one launch each, bit 2 stage 1's first bottleneck (downsample branch), bit 3 (with bit 0, bf16) the
-// stem that reads its B operand straight from a bf16 patch (stem2_pool_kernel).  Default: all.
-static int fuse_mask()
-{
-    static const int m = [] {
-        const char *e = getenv("ICL_FUSE");
-        return e ? atoi(e) : 15;
-    }();
-    return m;
-}
-
+// grid: fwd_stem_blocks over the B * SP_STRIPS strips
 template <typename T>
-static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, void *pooled, hipStream_t strm)
+static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, void *pooled, unsigned grid, hipStream_t strm)
 {
     icl_model *m = ctx->model;
     if (prec == ICL_PREC_BF16 && (fuse_mask() & 8)) { // no im2col staging: B fragments straight from the bf16 patch
         const conv_layer &L0 = m->conv[0];
         icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)B * 112 * 112 * 64 * 147, 0.0);
         const int nunits = B * SP_STRIPS;
-        const int per_cu = std::max<int>(1, std::min<int>(5, (int)((size_t)160 * 1024 / stem2_lds_bytes())));
-        const unsigned grid = (unsigned)std::min<int64_t>(nunits, (int64_t)per_cu * ctx->prop.multiProcessorCount);
         hipLaunchKernelGGL(stem2_pool_kernel, dim3(grid), dim3(256), stem2_lds_bytes(), strm, d_img, (const uint16_t *)L0.wfold, L0.shift, (uint16_t *)pooled, nunits);
         return;
     }
@@ -1079,8 +982,6 @@ static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B
     const conv_args a = conv_stem(m, m->conv[0].w[SPLIT ? ICL_PREC_FP32 : prec], pooled, B, B * SP_STRIPS * SP_TILES);
     icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
     const int nunits = B * SP_STRIPS;
-    const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_pool_lds_bytes<TS>()));
-    const unsigned grid = (unsigned)std::min<int64_t>(nunits, (int64_t)per_cu * ctx->prop.multiProcessorCount);
     hipLaunchKernelGGL((stem_pool_kernel<TS, SPLIT>), dim3(grid), dim3(256), stem_pool_lds_bytes<TS>(), strm, d_img, a, nunits);
 }
 
@@ -1090,8 +991,7 @@ static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, hipStream_t
 {
     const int B = a.B;
     if ((int64_t)B * a.H * a.W * 512 >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused bottleneck: batch of %d images exceeds the 32-bit buffer offsets", B);
-    a.nstrips = (a.W + BN56_COLS - 1) / BN56_COLS;
-    a.ngroups = std::max(1, std::min(B, ctx->prop.multiProcessorCount / a.nstrips));
+    bneck56_grid(B, a.W, ctx->prop.multiProcessorCount, &a.nstrips, &a.ngroups);
 #ifdef BN56_TIMERS
     static unsigned long long *dbg = nullptr;
     if (!dbg) (void)hipMalloc((void **)&dbg, 16 * 8);
@@ -1141,104 +1041,74 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     return launch_bneck56_args(ctx, a, ds != nullptr, strm);
 }
 
-// The last identity block in front of a strided block 0 (prune_map.h: s = prune_stride(..) > 1), bf16: c2 as the 3x3 / stride s / pad 1
-// convolution into a compact t2, c3 over that compact tensor with its residual and output at pixel (s oy, s ox) of the full-size x and y;
-// the pixels in between are not written and nobody reads them.  Both launches must land on the kernels and instantiations the unpruned
-// layers take (same k order: the values that are still computed keep their bits); false -- the caller runs the unpruned block -- if not.
-static bool plan_pruned_block(icl_ctx *ctx, const conv_layer &c2, const conv_layer &c3, int s, const void *t1, void *t2, const void *x, void *y, int B,
-                              conv_args *p2, conv_args *p3)
+// The plan of one forward pass of B images of the loaded model under the context's options as they are now (forward_make_plan, conv_select.h).
+static int forward_plan_of(icl_ctx *ctx, int prec, int B, int head, int tap, fwd_plan *plan)
 {
-    if (s <= 1) return false;
-    const int prec = ICL_PREC_BF16;
-    const icl_conv_rec &r2 = c2.rec, &r3 = c3.rec;
-    const void *zero = ctx->model->zero;
-    const conv_args u2 = conv_plain(t1, c2.w[prec], t2, nullptr, c2.scale, c2.shift, zero, B, r2.hin, r2.cin, r2.cout, r2.k, r2.stride, r2.pad, 1);
-    const conv_args u3 = conv_plain(t2, c3.w[prec], y, x, c3.scale, c3.shift, zero, B, r3.hin, r3.cin, r3.cout, 1, 1, 0, 1);
-    *p2 = conv_plain(t1, c2.w[prec], t2, nullptr, c2.scale, c2.shift, zero, B, r2.hin, r2.cin, r2.cout, r2.k, s, r2.pad, 1);
-    *p3 = conv_plain(t2, c3.w[prec], y, x, c3.scale, c3.shift, zero, B, p2->Ho, r3.cin, r3.cout, 1, 1, 0, 1);
-    p3->omap = prune_map_make(s, r3.hout, r3.hout);
-    if (u2.K != c2.K || u3.K != c3.K || p2->Ho != p3->omap.Ho) return false;
-    const int mode = ctx->conv_p8;
-    if (!ctx->conv_wr || !conv_wr_eligible(u3, mode) || !conv_wr_eligible(*p3, mode)) return false;
-    if (!conv_p8_eligible(u2, mode) || !conv_p8_eligible(*p2, mode)) return false;
-    if (conv_p8_split_eligible(ctx, u2) != conv_p8_split_eligible(ctx, *p2)) return false; // (the split form sums K in another order)
-    return true;
+    const icl_model *m = ctx->model;
+    icl_conv_rec recs[ICL_RESNET50_NCONV];
+    for (int i = 0; i < m->nconv; ++i) recs[i] = m->conv[i].rec;
+    *plan = forward_make_plan(recs, m->nconv, prec, B, head == ICL_HEAD_DENSE0, tap, forward_opts_of(ctx, prec));
+    if (plan->err) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "forward pass, convolution %d (cin=%d cout=%d k=%d): %s", plan->err_layer, recs[plan->err_layer].cin, recs[plan->err_layer].cout, recs[plan->err_layer].k, plan->err);
+    return ICL_OK;
 }
 
-// tap >= 0 (icl_embed_taps): the pass ends after the stem + maxpool (0) or after bottleneck `tap` (1..16) and *tap_x is the buffer that
-// holds that tensor; nothing else differs.
+// Runs a plan on lane `lane` and stream strm: each step's pointers are the lane's buffers and the model's weights.  d_out: the embeddings
+// (no tap plan); a tap plan leaves its tensor in the lane's buffer plan.out.
 template <typename T>
-static int forward_batch(icl_ctx *ctx, int prec, const uint8_t *d_img, int B, int head, float *d_out, int lane, hipStream_t strm, int tap = -1,
-                         const void **tap_x = nullptr)
+static int forward_batch(icl_ctx *ctx, int prec, const fwd_plan &plan, const uint8_t *d_img, int head, float *d_out, int lane, hipStream_t strm)
 {
     typedef typename T::elem elem;
     icl_model *m = ctx->model;
     ctx->cur_stream = strm;
-    const int grid = 256 * 8;
-    elem *x = (elem *)m->buf[lane][0], *t1 = (elem *)m->buf[lane][1], *t2 = (elem *)m->buf[lane][2], *ds = (elem *)m->buf[lane][3],
-         *y = (elem *)m->buf[lane][4];
-    if ((fuse_mask() & 1) || is_x3<T>::value) { // (BF16X3 has the fused stem only)
-        launch_stem_pool<T>(ctx, prec, d_img, B, x, strm); // conv0 + BN + ReLU + maxpool: the 112x112 tensor stays on the CU
-    } else if constexpr (!is_x3<T>::value) {
-        {
-            icl_lds_optin(ctx, (const void *)stem_conv_kernel<T>, (int)stem_lds_bytes<T>());
-            const conv_args a = conv_stem(m, m->conv[0].w[prec], y, B, B * 98); // 8x16-pixel tiles: 14 x 7 per image
-            icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
-            const int per_cu = std::max<int>(1, (int)((size_t)160 * 1024 / stem_lds_bytes<T>()));
-            const unsigned stem_grid = (unsigned)std::min<int64_t>(a.gx, (int64_t)per_cu * ctx->prop.multiProcessorCount);
-            hipLaunchKernelGGL((stem_conv_kernel<T>), dim3(stem_grid), dim3(256), stem_lds_bytes<T>(), strm, d_img, a);
-        }
-        {
-            icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * (802816.0 + 200704.0) * sizeof(elem));
-            hipLaunchKernelGGL((maxpool_kernel<T>), dim3(grid), dim3(256), 0, strm, y, B, 112, 64, x);
-        }
-    }
-    int ci = 1;
-    for (int blk = 0; ci < m->nconv && blk != tap; ++blk) {
-        const conv_layer &c1 = m->conv[ci], &c2 = m->conv[ci + 1], &c3 = m->conv[ci + 2];
-        const bool has_ds = c1.rec.block == 0;
-        if (prec == ICL_PREC_BF16 && c1.rec.stage == 1 && (fuse_mask() & (has_ds ? 4 : 2))) { // the whole bottleneck in one launch
-            ICL_TRY(launch_bneck56(ctx, c1, c2, c3, has_ds ? &m->conv[ci + 3] : nullptr, x, y, B, strm));
-            std::swap(x, y);
-            ci += has_ds ? 4 : 3;
-            continue;
-        }
-        ICL_TRY(launch_conv(ctx, prec, c1, x, t1, nullptr, 1, B));
-        // dead pixels: the block after this one reads its input at stride s only (never the block whose tensor a tap returns)
-        const int cn = ci + (has_ds ? 4 : 3);
-        conv_args p2, p3;
-        if (prec == ICL_PREC_BF16 && ctx->fwd_prune && !has_ds && blk + 1 != tap && cn + 3 < m->nconv &&
-            plan_pruned_block(ctx, c2, c3, prune_stride(c2.rec, c3.rec, &m->conv[cn].rec, &m->conv[cn + 3].rec), t1, t2, x, y, B, &p2, &p3)) {
-            ICL_TRY(launch_conv_prec(ctx, prec, p2)); // 3x3 / stride s: compact [B][h/s][h/s][mid]
-            ICL_TRY(launch_conv_prec(ctx, prec, p3)); // 1x1 over the compact tensor; residual and output at (s oy, s ox) of the full tensors
-            ++ctx->pruned_blocks;
-            std::swap(x, y);
-            ci = cn;
-            continue;
-        }
-        ICL_TRY(launch_conv(ctx, prec, c2, t1, t2, nullptr, 1, B));
-        if (has_ds)
-            ICL_TRY(launch_conv_fused_ds(ctx, prec, c3, m->conv[ci + 3], t2, x, y, B)); // relu(bn3(conv3) + bn_ds(conv_ds))
-        else
-            ICL_TRY(launch_conv(ctx, prec, c3, t2, y, x, 1, B)); // relu(bn(conv) + residual)
-        std::swap(x, y);
-        ci += has_ds ? 4 : 3;
-    }
-    if (tap >= 0) {
-        *tap_x = x;
-        ICL_HIP(ctx, hipGetLastError());
-        return ICL_OK;
-    }
+    const int B = plan.B;
+    void *const *buf = m->buf[lane];
     float *pooled = head == ICL_HEAD_POOLED ? d_out : m->pooled[lane];
-    {
-        icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * 49.0 * 2048.0 * (is_x3<T>::value ? 4 : sizeof(elem)));
-        hipLaunchKernelGGL((avgpool_kernel<T>), dim3((unsigned)icl_ceil_div((int64_t)B * 2048, 256)), dim3(256), 0, strm, x, B, 49,
-                           ICL_FEAT_DIM, pooled, (int64_t)ICL_FEAT_DIM);
-    }
-    if (head == ICL_HEAD_DENSE0) {
-        icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 2.0 * B * 2048.0 * 1000.0, 0.0);
-        hipLaunchKernelGGL(fc_kernel, dim3((unsigned)std::min<int64_t>(icl_ceil_div((int64_t)B * ICL_FC_OUT, 4), 4096)), dim3(256), 0,
-                           strm, pooled, m->fcw, m->fcb, B, ICL_FEAT_DIM, ICL_FC_OUT, d_out);
+    for (const fwd_step &s : plan.steps) {
+        const conv_layer &L = m->conv[s.layer];
+        switch (s.kind) {
+        case FWD_STEM2_POOL:
+        case FWD_STEM_POOL: // conv0 + BN + ReLU + maxpool: the 112x112 tensor stays on the CU
+            launch_stem_pool<T>(ctx, prec, d_img, B, buf[s.y], s.blocks, strm);
+            break;
+        case FWD_STEM:
+            if constexpr (!is_x3<T>::value) {
+                icl_lds_optin(ctx, (const void *)stem_conv_kernel<T>, (int)stem_lds_bytes<T>());
+                const conv_args a = conv_stem(m, L.w[prec], buf[s.y], B, B * 98); // 8x16-pixel tiles: 14 x 7 per image
+                icl_prof_scope ps(ctx, ICL_K_CONV64, 2.0 * (double)a.M * 64 * 147, 0.0);
+                hipLaunchKernelGGL((stem_conv_kernel<T>), dim3(s.blocks), dim3(s.threads), stem_lds_bytes<T>(), strm, d_img, a);
+            }
+            break;
+        case FWD_MAXPOOL:
+            if constexpr (!is_x3<T>::value) {
+                icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * (802816.0 + 200704.0) * sizeof(elem));
+                hipLaunchKernelGGL((maxpool_kernel<T>), dim3(s.blocks), dim3(s.threads), 0, strm, (const elem *)buf[s.x], B, 112, 64, (elem *)buf[s.y]);
+            }
+            break;
+        case FWD_BNECK56: // the whole bottleneck in one launch
+            ICL_TRY(launch_bneck56(ctx, L, m->conv[s.layer + 1], m->conv[s.layer + 2], s.ds ? &m->conv[s.layer + 3] : nullptr, buf[s.x], buf[s.y], B, strm));
+            break;
+        case FWD_CONV: {
+            conv_args a = s.a;
+            a.X = buf[s.x]; a.Y = buf[s.y]; a.R = s.r != FWD_NONE ? buf[s.r] : nullptr; a.zero = m->zero;
+            if (s.ds) { // both BN scales are folded into the concatenated weights
+                a.Wt = L.wfused[prec]; a.scale = m->ones; a.shift = L.shift_fused; a.X2 = buf[s.x2];
+            } else {
+                a.Wt = L.w[prec]; a.scale = L.scale; a.shift = L.shift;
+            }
+            ICL_TRY(launch_conv_t<T>(ctx, prec, a, s.c));
+            ctx->pruned_blocks += s.pruned;
+            break;
+        }
+        case FWD_AVGPOOL: {
+            icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 0.0, (double)B * 49.0 * 2048.0 * (is_x3<T>::value ? 4 : sizeof(elem)));
+            hipLaunchKernelGGL((avgpool_kernel<T>), dim3(s.blocks), dim3(s.threads), 0, strm, (const elem *)buf[s.x], B, 49, ICL_FEAT_DIM, pooled, (int64_t)ICL_FEAT_DIM);
+            break;
+        }
+        default: { // FWD_FC
+            icl_prof_scope ps(ctx, ICL_K_EMBED_OTHER, 2.0 * B * 2048.0 * 1000.0, 0.0);
+            hipLaunchKernelGGL(fc_kernel, dim3(s.blocks), dim3(s.threads), 0, strm, pooled, m->fcw, m->fcb, B, ICL_FEAT_DIM, ICL_FC_OUT, d_out);
+        }
+        }
     }
     ICL_HIP(ctx, hipGetLastError());
     return ICL_OK;
@@ -1256,7 +1126,8 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
         ICL_TRY(icl_dev_alloc(ctx, dimg, (size_t)B * ICL_IMG_BYTES, "icl_stem_pool: images"));
         ICL_TRY(icl_dev_alloc(ctx, dy, ny * prec_act_bytes(prec), "icl_stem_pool: output"));
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
-        with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, ctx->stream); });
+        const unsigned grid = fwd_stem_blocks((int64_t)B * SP_STRIPS, stem_per_cu(prec, fuse_mask() | 1), ctx->prop.multiProcessorCount);
+        with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, grid, ctx->stream); });
         io.returns(prec, dy.p, ny);
         const hipError_t e = hipGetLastError();
         return e == hipSuccess ? ICL_OK : icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: %s", hipGetErrorString(e));
@@ -1320,20 +1191,14 @@ extern "C" int icl_embed_taps(icl_ctx *ctx, int prec, const uint8_t *img, int B,
     return run_entry(ctx, "icl_embed_taps", true, out, [&](entry_io &io) -> int {
         if (B > ctx->batch) return icl_fail(ctx, ICL_ERR_ARG, "icl_embed_taps: %d images exceed the batch of %d", B, ctx->batch);
         ICL_TRY(icl_model_ensure_ws(ctx, B, prec, 1));
-        int H = 56, C = 64; // the tapped tensor: the output of the block's last convolution
-        for (int i = 1, blk = 0; i < ctx->model->nconv && blk < tap; ++i)
-            if (ctx->model->conv[i].rec.role == 3) {
-                H = ctx->model->conv[i].rec.hout;
-                C = ctx->model->conv[i].rec.cout;
-                ++blk;
-            }
+        fwd_plan plan; // ends at the tapped block, whose tensor ([B][H][H][C]) it leaves in the lane's buffer plan.out
+        ICL_TRY(forward_plan_of(ctx, prec, B, ICL_HEAD_POOLED, tap, &plan));
         dev_guard &dimg = io.buf();
         ICL_TRY(icl_dev_alloc(ctx, dimg, (size_t)B * ICL_IMG_BYTES, "icl_embed_taps: image buffer"));
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_embed_taps: upload");
-        const void *x = nullptr;
-        const int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, ICL_HEAD_POOLED, nullptr, 0, ctx->stream, tap, &x); });
+        const int rc = with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, plan, (const uint8_t *)dimg.p, ICL_HEAD_POOLED, nullptr, 0, ctx->stream); });
         ctx->cur_stream = nullptr;
-        io.returns(prec, x, (size_t)B * H * H * C);
+        io.returns(prec, ctx->model->buf[0][plan.out], (size_t)B * plan.H * plan.H * plan.C);
         return rc; // (run_entry synchronises also after a failed launch: dimg is freed on its return)
     });
 }
@@ -1355,6 +1220,9 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
     int lanes = (ctx->prof_mask || lanes_env < 2) ? 1 : std::min(lanes_env, ICL_MAX_LANES);
     lanes = (int)std::min<int64_t>(lanes, (n + batch - 1) / batch);
     ICL_TRY(icl_model_ensure_ws(ctx, batch, prec, lanes));
+    fwd_plan full, rest; // one plan for the full batches and, for a ragged call, one for the last
+    ICL_TRY(forward_plan_of(ctx, prec, batch, head, -1, &full));
+    if (n % batch) ICL_TRY(forward_plan_of(ctx, prec, (int)(n % batch), head, -1, &rest));
     // whatever the exit: the events of this call are destroyed and no launch stream stays selected
     constexpr int DEPTH = 16;
     hipEvent_t ring[DEPTH + 2] = {}; // one per batch in flight, then the two that time the call
@@ -1399,7 +1267,7 @@ int icl_embed_dev_locked(icl_ctx *ctx, const uint8_t *d_img, int64_t n, int head
         hipEvent_t &ev = ring[bi % DEPTH];
         if (ev) ICL_HIP(ctx, hipEventSynchronize(ev)); // batch bi-DEPTH has finished
         else ICL_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        ICL_TRY(with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, d_img + i * ICL_IMG_BYTES, B, head, d_out + i * head, lane, strm); }));
+        ICL_TRY(with_prec(prec, [&](auto t) { return forward_batch<decltype(t)>(ctx, prec, B == batch ? full : rest, d_img + i * ICL_IMG_BYTES, head, d_out + i * head, lane, strm); }));
         ICL_HIP(ctx, hipEventRecord(ev, strm));
         if (ctx->embed_hook) { // rows [i, i + B) of d_out are complete once ev has fired
             const int hrc = ctx->embed_hook(i, B, ev);

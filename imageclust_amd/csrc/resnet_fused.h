@@ -8,6 +8,7 @@
 //   bneck56_kernel    one whole stage-1 bottleneck (1x1 -> 3x3 -> 1x1 (+ residual | + downsample branch) + ReLU) per
 //                     launch: reads the block input once, writes the block output once (1 645 -> 822 MB per block).
 #pragma once
+#include "conv_select.h"
 #include "mfma_tile.h"
 #include "resnet_model.h" // (resnet_pack.h:) STEM_K, STEM_ROWK, ST2_K, the weight layouts the loader packs
 
@@ -556,7 +557,7 @@ struct bneck_args {
 #endif
 };
 
-#define BN56_COLS 14                                 /* output columns per strip */
+/* BN56_COLS (conv_select.h, where the forward plan sizes the grid): 14 output columns per strip */
 #define BN56_ROWS 4                                  /* virtual rows per step: one x tile, 4 new t1 rows, 4 t2 rows, two quarters of output */
 #define BN56_ROW_BYTES (16 * 128)                    /* one tile row: 16 pixels x 64 channels */
 #define BN56_XCH_BYTES (BN56_ROWS * BN56_ROW_BYTES)  /* one 64-channel chunk of an x tile */

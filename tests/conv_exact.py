@@ -47,7 +47,7 @@ def conv_id(c):
 # ---- the cases of tests/test_conv_exact_gpu.py, by the route they are meant for (test_conv_exact_cpu.py checks exact_ref's conditions on each) ----
 IGEMM_CASES = [conv(3, 7, 64, 64, 3), conv(2, 9, 64, 192, 1, relu=False), conv(1, 14, 256, 128, 1, 2), conv(2, 7, 128, 256, 1, res=True, relu=False)]
 HALO_CASES = [conv(3, 7, 128, 128, 3), conv(2, 9, 256, 128, 3, relu=False), conv(1, 28, 192, 128, 3)]
-# (2, 23, 256, 128, 1): bf16 takes conv_wr_kernel (K = 256, Cout = 128 is its shape too, and launch_conv_t asks it first), bf16x3
+# (2, 23, 256, 128, 1): bf16 takes conv_wr_kernel (K = 256, Cout = 128 is its shape too, and conv_select asks it first), bf16x3
 # conv_p8_kernel's 512 x 128 layout; (2, 23, 384, 128, 1) is the same hazard at a K conv_wr_kernel does not take
 P8_CASES = [conv(2, 23, 256, 128, 1, res=True), conv(2, 23, 384, 128, 1, res=True), conv(3, 14, 128, 384, 3, relu=False),
             conv(11, 7, 128, 256, 3, res=True), conv(7, 14, 512, 768, 1, relu=False), conv(3, 12, 384, 256, 1, res=True), conv(2, 14, 512, 256, 1, 2)]
@@ -61,7 +61,7 @@ BNECK_CASES = [(3, 9, 20), (1, 7, 14), (2, 16, 3)]  # (B, H, W), each in both fo
 
 
 def wr_rule(K, cout, ncu, M):
-    """launch_conv_wr's rule (conv_wr.h) -> (pixels per tile, workers) for a K -> cout layer of M pixels on ncu compute units."""
+    """conv_select's rule for conv_wr_kernel (conv_select.h) -> (pixels per tile, workers) for a K -> cout layer of M pixels on ncu compute units."""
     ns, pt = {128: (256, 64), 256: (128, 64), 512: (128, 32)}[K]
     nslices = cout // ns
     nworkers = max(8, (2 * ncu // nslices) & ~7)
@@ -82,10 +82,11 @@ def wr_walk_case(K, ncu):
 
 
 def route(c, prec, mode, split=False):
-    """The kernel launch_conv_t (resnet.hip) picks for convolution c in `prec` under ICL_CONV_P8_* `mode` (0 off, 1 auto, 2 all; split:
-    | ICL_CONV_SPLIT), restated from conv_wr_eligible, conv_p8_eligible, conv_p8_split_eligible and the halo rule.  The GPU tests
-    check it against the launch counters (conv_stats: [0] conv_wr_kernel and conv_p8_kernel, [1] the 128 x 128 kernels;
-    conv_split_launches), which cannot tell the kernels of one counter apart."""
+    """The kernel conv_select (imageclust_amd/csrc/conv_select.h; launch_conv_t and the forward plan launch what it chooses) picks for
+    convolution c in `prec` under ICL_CONV_P8_* `mode` (0 off, 1 auto, 2 all; split: | ICL_CONV_SPLIT), restated independently from its
+    conv_wr_eligible, conv_p8_eligible, conv_p8_split_eligible and halo rule.  tests/test_conv_select_cpu.py checks the header's choice
+    against it without a GPU; the GPU tests check it against the launch counters (conv_stats: [0] conv_wr_kernel and conv_p8_kernel,
+    [1] the 128 x 128 kernels; conv_split_launches), which cannot tell the kernels of one counter apart."""
     x3 = prec == "bf16x3"
     K, Ho = c.k * c.k * c.cin, (c.H + 2 * (c.k // 2) - c.k) // c.stride + 1
     if prec == "bf16" and mode and c.k == 1 and c.stride == 1 and K in (128, 256, 512) and c.cout % (256 if K == 128 else 128) == 0 \

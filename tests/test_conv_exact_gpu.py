@@ -112,7 +112,7 @@ def test_conv_wr_kernel(ctx, L, c):
 
 @pytest.mark.parametrize("K", [128, 256, 512])
 def test_conv_wr_kernel_multi_tile_walk(ctx, L, K):
-    """Every worker walks at least three tiles and the last tile is ragged (sized from launch_conv_wr's rule and the device's CU count):
+    """Every worker walks at least three tiles and the last tile is ragged (sized from conv_select's rule and the device's CU count):
     the double buffer is reused, the prefetched residual is used and a tile past the end is requested."""
     run_conv(ctx, L, CE.wr_walk_case(K, ctx.device_info()[1]), "bf16", AUTO, family="conv_wr")
 

@@ -7,7 +7,7 @@ equal it); each pixel that is not a multiple of s must come back holding the sen
 
 Shapes, for K = 128 / Cout = 512 and K = 256 / Cout = 1024: one image whose compact pixels are exactly one 64-pixel tile; three images of
 full height 10 (M = 75: an image boundary inside a tile and a ragged last tile); an odd full height (7 -> 4); s = 1 (the map is the
-identity: equal to the unmapped kernel everywhere).  One case (K = 256) has more tiles than launch_conv_wr starts workers for, so that a
+identity: equal to the unmapped kernel everywhere).  One case (K = 256) has more tiles than conv_select starts workers for, so that a
 worker's second tile, the refilled LDS buffer and the residual requested one tile ahead run through the map: the smallest square image
 with more than 64 * workers compact pixels (conv_exact.wr_rule restates the worker rule)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The identity under a pruned bottleneck's c2 (resnet.hip plan_pruned_block): on conv_p8_kernel, the 3x3 / stride 2 / pad 1 convolution
+"""The identity under a pruned bottleneck's c2 (conv_select.h plan_pruned_block): on conv_p8_kernel, the 3x3 / stride 2 / pad 1 convolution
 equals the 3x3 / stride 1 / pad 1 convolution sampled at the pixels (2 oy, 2 ox), BIT FOR BIT -- same taps, same zero padding, same k
 order (iy0 = 2 oy - 1).  Inputs are Gaussian, rounded to bf16, so that another summation order would show.  Both layouts of the kernel
 (Cout = 128: 4 x 2 waves, Cout = 256: 2 x 4 waves), an even and an odd height each, several images, so that the strided launch's tile rows

@@ -10,7 +10,10 @@ kernel in the same k order: everything below is equality of bits, on the synthet
   * the launch counters: the option moves no launch between the kernel families (every pruned launch is still counted under
     conv_p8_kernel / conv_wr_kernel), and icl_forward_prune_stats counts the blocks the records say (stages 2 and 3 of this model; stage 1
     runs as fused bottlenecks), none in fp32 / bf16x3, none where the unpruned layers would take other kernels (ICL_CONV_P8_OFF), and not
-    stage 3's under ICL_CONV_SPLIT (its quartered 3x3 layer would take the split form, another summation order)."""
+    stage 3's under ICL_CONV_SPLIT (its quartered 3x3 layer would take the split form, another summation order);
+  * 9 images at a batch of 4 (batches of 4, 4 and 1 on two lanes: the plan of the full batch and the plan of the remainder) in every
+    precision and both heads: each row equals that image's embedding in a call of its own, and the launch counters move by what
+    conv_exact.route says of the model's records."""
 import numpy as np
 import pytest
 
@@ -127,3 +130,51 @@ def test_only_where_both_forms_take_the_same_kernels(ctx, L, imgs, mode, pruned)
         assert k % 2 == 0 and (k > 0) == (mode == "split")  # the same number of split launches with the option on and off
     finally:
         ctx.set_conv_options(L.CONV_P8_AUTO)
+
+
+@pytest.fixture(scope="module")
+def nine(L):
+    return np.concatenate([L.synth_images(7, 40, 5, L.SYNTH_NOISE), L.synth_images(20250217, 9, 4, L.SYNTH_STRUCTURED)])
+
+
+def launches_of_a_pass(prec, B):
+    """The convolutions one forward pass of B images hands to the selector (conv_select.h), from the model's records: in bf16
+    stage 1 runs in bneck56_kernel; the c3 of a block 0 is ONE launch over K = [mid | cin of the downsample branch]; a pruned block's two
+    launches stay in the families of the unpruned layers, whose shapes stand here."""
+    from tests import conv_exact as X
+    from tests import resnet_blocks as RB
+
+    recs, out = RB.topology(), []
+    for i, r in enumerate(recs):
+        if r.role in (0, 4) or (prec == "bf16" and r.stage == 1):
+            continue
+        cin = r.cin + (recs[i + 1].cin if r.role == 3 and r.block == 0 else 0)
+        out.append(X.conv(B, r.hin, cin, r.cout, r.k, r.stride, res=r.role == 3 and r.block > 0))
+    return out
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x3"])
+def test_ragged_batches_on_two_lanes_take_the_right_plans(ctx, L, nine, prec):
+    """9 images at a batch of 4: batches of 4, 4 and 1 over two lanes -- a plan for the full batch and one for the remainder.  Every row is
+    the embedding that image has in a call of its own, bit for bit, in both heads; the launch counters move by what conv_exact.route says
+    of the model's records for the three batches, and 2 blocks per batch are pruned in bf16, none otherwise."""
+    from tests import conv_exact as X
+
+    p = {"fp32": L.PREC_FP32, "bf16": L.PREC_BF16, "bf16x3": L.PREC_BF16X3}[prec]
+    want = np.zeros(3, np.int64)
+    for B in (4, 4, 1):
+        for c in launches_of_a_pass(prec, B):
+            want += X.counters_of(X.route(c, prec, 1))
+    try:
+        ctx.set_batch(4)
+        for head in (L.HEAD_POOLED, L.HEAD_DENSE0):
+            s0, k0, p0 = ctx.conv_stats(), ctx.conv_split_launches(), ctx.forward_prune_stats()
+            e = ctx.embed_u8(nine, head, p)
+            s1, k1, p1 = ctx.conv_stats(), ctx.conv_split_launches(), ctx.forward_prune_stats()
+            print("%s head %d: conv_stats +%s, split +%d, pruned +%d; route says %s" % (prec, head, tuple(a - b for a, b in zip(s1, s0)), k1 - k0, p1 - p0, tuple(want)))
+            assert (s1[0] - s0[0], s1[1] - s0[1], k1 - k0) == tuple(want)
+            assert p1 - p0 == (6 if prec == "bf16" else 0)
+            for i in range(len(nine)):
+                assert same_bits(ctx.embed_u8(nine[i:i + 1], head, p)[0], e[i]), "%s head %d: image %d differs from its embedding alone" % (prec, head, i)
+    finally:
+        ctx.set_batch(256)
