@@ -229,17 +229,29 @@ struct icl_ward_ws {
     } dump;
 };
 
+// Gives back what ward_ensure_impl allocated for a shape -- the 23 device arrays and the graph captured over them -- and leaves the
+// workspace empty (capN = 0); the find_closest scratch (fc_*) grows on its own and stays.
+static void ward_ws_release(icl_ward_ws *w)
+{
+    if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
+    w->graph_exec = nullptr;
+    auto drop = [](auto *&p) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    };
+    drop(w->CT), drop(w->Crow), drop(w->cnew), drop(w->cnewI), drop(w->slot_id), drop(w->id_slot), drop(w->asz), drop(w->rowmin), drop(w->rownn);
+    drop(w->rowoff), drop(w->mcol), drop(w->msz), drop(w->mcid), drop(w->Dtri), drop(w->merges), drop(w->st), drop(w->nrm), drop(w->colsum);
+    drop(w->zero), drop(w->mpk), drop(w->bl1), drop(w->bex), drop(w->rowub);
+    w->capN = 0;
+}
+
 void icl_ward_free(icl_ctx *ctx)
 {
     ctx->ward_rowoff.release();
     ctx->ward_rowoff_n = 0;
     icl_ward_ws *w = ctx->ward;
     if (!w) return;
-    void *ptrs[] = {w->CT, w->Crow, w->cnew, w->cnewI, w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid,
-                    w->Dtri, w->merges, w->st, w->nrm, w->colsum, w->zero, w->mpk, w->bl1, w->bex, w->rowub};
-    if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    ward_ws_release(w);
     for (icl_dev_grow *b : {&w->fc_min, &w->fc_nn, &w->fc_out}) b->release();
     delete w;
     ctx->ward = nullptr;
@@ -536,7 +548,7 @@ __device__ __forceinline__ void scan_row_m(const float *__restrict__ row, int64_
 // two embeddings -- every flagged entry whose lower bound does not exceed that threshold, writes the values back, and returns the
 // first minimum among values only.  An entry left flagged is strictly above the threshold, hence strictly above the minimum: it
 // can neither win nor tie.  Nothing a comparison sees is ever a bound.
-__device__ __forceinline__ bool wflagged_bits(float v) { return (__float_as_uint(v) >> 31) != 0; }
+__device__ __forceinline__ bool wflagged(float v) { return (__float_as_uint(v) >> 31) != 0; }
 struct wrefine {
     const float *E;   // [n][d] the embeddings = the singletons' centroids (they never change); nullptr: rows hold values only
     const float *nrm; // [n] computed |E[r] - mu|^2 (dist_center_kernel)
@@ -569,9 +581,8 @@ struct wrefine {
 __device__ __forceinline__ int64_t ward_row_len_rf(int64_t r, int64_t n, const wrefine &rf) { return rf.wide ? r : ward_row_len(r, n); } // complete rows: the columns ARE creation ids
 __device__ __forceinline__ void wcheck_bound(const wrefine &rf, float old_entry, float val)
 {
-    if (rf.viol && wflagged_bits(old_entry) && val < fabsf(old_entry)) atomicAdd(rf.viol, 1u);
+    if (rf.viol && wflagged(old_entry) && val < fabsf(old_entry)) atomicAdd(rf.viol, 1u);
 }
-__device__ __forceinline__ bool wflagged(float v) { return (__float_as_uint(v) >> 31) != 0; }
 // upper bound of the value behind a flagged entry L of the two singletons a, b
 __device__ __forceinline__ float wupper(float L, int a, int b, const wrefine &rf)
 {
@@ -1476,19 +1487,17 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
 // exact (min, argmin) replaces the bound and the selection is repeated.  When the winner is clean, every other row's
 // bound is lexicographically >= it, hence so is its true minimum: the pick equals the reference's full scan
 // (clustering.go:119-133), ties included.
-__device__ __forceinline__ void ward_preselect(int64_t n, const int32_t *__restrict__ asz, float *__restrict__ rowmin,
-                                               int32_t *__restrict__ rownn, float *__restrict__ Dtri,
-                                               const int64_t *__restrict__ rowoff, const int32_t *__restrict__ msz,
-                                               const int32_t *__restrict__ mcid, int max_size, ward_state *__restrict__ st,
-                                               float *sv, int *si, int *sh, const wrefine &rf)
+// ONE body for every loop (ward_preselect below, the single pick of the two batched finish kernels).  A row whose cache is stale -- its partner
+// has died, or it was never scanned (WB_NN_BOUND, bound rows) -- is re-minimised over the row length of its layout (ward_row_len_rf) and
+// written back.  mpk: the packed column words (null: the scans read msz / mcid); sv / si / flag / scr: the caller's LDS (block_argmin's
+// tables, one word, ward_sqdist_wave's scratch).  Every thread of the workgroup calls it; (bv, bi) is uniform; bi < 0: no pair is left.
+// The partner of the pick is rownn[bi].
+__device__ __forceinline__ void ward_lazy_pick(int64_t n, int t, const int32_t *__restrict__ asz, float *__restrict__ rowmin, int32_t *__restrict__ rownn,
+                                               float *__restrict__ Dtri, const int64_t *__restrict__ rowoff, const int32_t *__restrict__ msz,
+                                               const int32_t *__restrict__ mcid, const uint32_t *__restrict__ mpk, int max_size, const wrefine &rf,
+                                               float *sv, int *si, int *flag, float *scr, float &bv, int &bi)
 {
-    __shared__ __attribute__((aligned(16))) float pre_scr[16][256]; // ward_sqdist_wave's scratch
-    if (st->done) return;
-    const int t = st->t;
-    if (t >= st->target) return;
     const int64_t nvec = (n + t + 3) >> 2; // rowmin is padded with MaxFloat32 up to a multiple of 4
-    float bv;
-    int bi;
     for (;;) {
         // rows are read 4 at a time, 4 loads in flight per lane, ascending row order per lane
         bv = ICL_MAXF;
@@ -1516,28 +1525,43 @@ __device__ __forceinline__ void ward_preselect(int64_t n, const int32_t *__restr
         if (bi < 0) break;
         if (threadIdx.x == 0) {
             const int nn = rownn[bi];
-            sh[0] = asz[nn] > 0 ? 0 : 1; // cached partner dead -> the cached value is only a bound
-            sh[1] = nn;
+            *flag = (nn >= 0 && asz[nn] > 0) ? 0 : 1; // cached partner dead, or never scanned (WB_NN_BOUND) -> the cached value is only a bound
         }
         __syncthreads();
-        const int dirty = sh[0];
+        const int dirty = *flag;
         __syncthreads();
         if (!dirty) break;
         float rv;
         int ri;
         {
             const int noex[1] = {-1};
-            scan_row_min(Dtri + rowoff[bi], ward_row_len(bi, n), msz, mcid, bi, asz[bi], max_size, noex, 0, rv, ri, sv, si, rf, &pre_scr[0][0]);
+            scan_row_min(Dtri + rowoff[bi], ward_row_len_rf(bi, n, rf), msz, mcid, bi, asz[bi], max_size, noex, 0, rv, ri, sv, si, rf, scr, mpk);
         }
         if (threadIdx.x == 0) {
             rowmin[bi] = rv;
             rownn[bi] = ri;
         }
+        __threadfence_block();
         __syncthreads();
     }
+}
+
+__device__ __forceinline__ void ward_preselect(int64_t n, const int32_t *__restrict__ asz, float *__restrict__ rowmin,
+                                               int32_t *__restrict__ rownn, float *__restrict__ Dtri,
+                                               const int64_t *__restrict__ rowoff, const int32_t *__restrict__ msz,
+                                               const int32_t *__restrict__ mcid, int max_size, ward_state *__restrict__ st,
+                                               float *sv, int *si, int *sh, const wrefine &rf)
+{
+    __shared__ __attribute__((aligned(16))) float pre_scr[16][256]; // ward_sqdist_wave's scratch
+    if (st->done) return;
+    const int t = st->t;
+    if (t >= st->target) return;
+    float bv;
+    int bi;
+    ward_lazy_pick(n, t, asz, rowmin, rownn, Dtri, rowoff, msz, mcid, nullptr, max_size, rf, sv, si, &sh[0], &pre_scr[0][0], bv, bi);
     if (threadIdx.x == 0) {
         st->pre_row = bi;
-        st->pre_nn = bi >= 0 ? sh[1] : -1;
+        st->pre_nn = bi >= 0 ? rownn[bi] : -1;
         st->pre_val = bv;
     }
 }
@@ -1930,10 +1954,9 @@ static inline int64_t wb_groups(int d) { return (((int64_t)d + 3) / 4 + WB_SG - 
 // shuffles and appends a SENTINEL (a lower bound for everything it did not report); wave 0 then walks the <= 50
 // entries in ascending order and stops at the first sentinel, so whatever it saw before is exact.
 #define WB_MAXOV 8
-__device__ __forceinline__ unsigned long long wave_umin64(unsigned long long k);
 // (every lane active; wave-uniform result.  Until round 4 a 6-step __shfl_xor tree: twelve dependent ds_bpermute round trips per pop --
 // the 8 + 12 pops of a slice and the preselection's walk sit on the update launch's critical chain)
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k) { return wave_umin64(k); }
+__device__ __forceinline__ unsigned long long wave_umin64(unsigned long long k);
 
 // Pops the WB_WTOP smallest keys of a wave (every lane offers k1 < k2, its two smallest; a key with bit 0 set is a SENTINEL:
 // a lower bound of entries that are not listed) into out[0..WB_WTOP), then out[WB_WTOP] = a sentinel for whatever the wave
@@ -1947,7 +1970,7 @@ __device__ __forceinline__ void wave_pop_top(unsigned long long k1, unsigned lon
     int stg = 0; // 0: head = k1, 1: head = k2, 2: head = sentinel(k2)
     bool ended = false;
     for (int q = 0; q < ntop; ++q) {
-        const unsigned long long m = ended ? ~0ull : wave_min_u64(head);
+        const unsigned long long m = ended ? ~0ull : wave_umin64(head);
         if (lane == 0) out[q] = m;
         if (kept && lane == q) *kept = m;
         if (m == ~0ull || (m & 1ull)) { // nothing left / a lane ran out of known entries: the wave's list ends here
@@ -1959,7 +1982,7 @@ __device__ __forceinline__ void wave_pop_top(unsigned long long k1, unsigned lon
             head = stg == 1 ? k2 : ((k2 == ~0ull || !has_rest) ? ~0ull : (k2 | 1ull));
         }
     }
-    const unsigned long long rest = ended ? ~0ull : wave_min_u64(head);
+    const unsigned long long rest = ended ? ~0ull : wave_umin64(head);
     if (lane == 0) out[ntop] = rest == ~0ull ? rest : (rest | 1ull);
 }
 
@@ -2269,7 +2292,7 @@ __device__ __forceinline__ void ward_preselect_batch(int nsp, int64_t n, const i
         if (wave == 0) {
             int action = 0, arow = -1, alane = -1; // 0 stop, 2 rescan + write back, 3 speculative rescan (override)
             while (npick < K && t_after + npick < target) {
-                const unsigned long long m = wave_min_u64(key);
+                const unsigned long long m = wave_umin64(key);
                 if (m == ~0ull || (m & 1ull)) { // exhausted / coverage ends
                     WB_TIMER(if (lane == 0) atomicAdd(&g_walk_dbg[m == ~0ull ? 0 : 1], 1ull);)
                     break;
@@ -3212,9 +3235,7 @@ __global__ __launch_bounds__(1024) void ward_lb_consts_kernel(const float *__res
 }
 
 #ifndef WL_THREADS
-#ifndef WL_THREADS
 #define WL_THREADS 768
-#endif
 #endif
 #ifndef WL_REVERSE
 #define WL_REVERSE 1 /* main workgroups take the creation-id blocks from the YOUNGEST down: the dense blocks (merged clusters, all alive) start first, the sparse ones
@@ -3522,7 +3543,10 @@ __global__ __launch_bounds__(WL_THREADS) void ward_update_lb_kernel(int64_t S, c
 }
 
 #define WB_FIN_THREADS 512
-// Row storage of the cluster that merge q will create, K spare rows (ward_new_row below, for a batch width of K)
+// Row storage of the cluster that merge q will create, for a batch width of K (file header): one of the K spare rows, or the storage of a_{q-K},
+// the higher-position member of the merge committed K merges earlier.  t0 / a0: the merges [t0, t0 + J) were committed by the
+// calling kernel itself (their log entries may not be readable yet): a0[i] is the a of merge t0 + i.  q - K < t0 + J always
+// holds: a batch starts at the committed count and holds at most K picks.
 template <int K>
 __device__ __forceinline__ int64_t ward_new_row_k(int64_t n, int64_t ld, int q, int t0, const int32_t *a0, const int32_t *merges, const int64_t *rowoff)
 {
@@ -3530,6 +3554,148 @@ __device__ __forceinline__ int64_t ward_new_row_k(int64_t n, int64_t ld, int q, 
     const int p = q - K;
     const int a = p >= t0 ? a0[p - t0] : merges[3 * p];
     return rowoff[a];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The steps the two batched finish kernels share (ward_finish_lb_kernel: bound rows, K = WL_K; ward_finish_batch_kernel: exact and FAST rows,
+// K = WB_K), each written once.  ls: the kernel's LDS snapshot of the state; lane: of wave 0, which runs every step but the last; J: the
+// number of committed picks; nbp: the picks of the batch (ls.B.nb); the state's tables hold WB_KMAX entries whatever K is.
+// ------------------------------------------------------------------------------------------------------------
+// the state at kernel entry, by dwords (the spare workgroups' phase-A tables -- flags, matched rows, key streams: 12 of the state's 15 KB, last in
+// the struct -- are not read by a finish kernel); the caller's barrier follows
+__device__ __forceinline__ void wfin_snapshot(ward_state *ls, const ward_state *__restrict__ st)
+{
+    constexpr int NW = (int)((offsetof(ward_state, B) + offsetof(ward_batch_state, pa_flag)) / 4);
+    static_assert((offsetof(ward_state, B) + offsetof(ward_batch_state, pa_flag)) % 4 == 0, "snapshot by dwords");
+    for (int q = threadIdx.x; q < NW; q += WB_FIN_THREADS) reinterpret_cast<int *>(ls)[q] = reinterpret_cast<const int *>(st)[q];
+}
+// validate: J = the longest prefix of the batch in which no pair of an earlier new cluster can precede the pick.  Lane j holds the smallest
+// row minimum (or lower bound of it) of c_0..c_{j-1}, an exclusive prefix minimum by shuffles.
+template <int K>
+__device__ __forceinline__ int wfin_validate(const ward_state &ls, int lane, int nbp)
+{
+    static_assert(K <= WB_KMAX && K <= 32, "one lane per pick, state tables of WB_KMAX entries");
+    float cm = ICL_MAXF;
+    if (lane < nbp) {
+        const unsigned long long k = ls.B.ckey[lane];
+        if (k != ~0ull) cm = __uint_as_float((unsigned)(k >> 32));
+    }
+    float pm = __shfl_up(cm, 1, 64); // exclusive
+    if (lane == 0) pm = ICL_MAXF;
+#pragma unroll
+    for (int off = 1; off < K; off <<= 1) {
+        const float o = __shfl_up(pm, off, 64);
+        if (lane >= off) pm = fminf(pm, o);
+    }
+    const bool bad = lane >= 1 && lane < nbp && pm < ls.B.val[lane < WB_KMAX ? lane : 0];
+    const unsigned long long bm = __ballot(bad);
+    return bm ? __ffsll((long long)bm) - 1 : nbp;
+}
+// commit of pick j (one lane each, j < J): the bookkeeping of MergeClusters / RemoveClusters (clustering.go:29-58,:240-241) but for the new
+// row's cached partner, which differs (the caller writes rownn[c] from the key returned: the row's minimum, ~0: no entry).  ca, cb: the
+// columns of the members.  Recycled storage (file header): c takes over a's column, b's column dies -- complete rows (rf.wide): c has the
+// column of its creation id, both members' columns die.  The picks of a batch are pairwise disjoint, so the lanes touch different entries.
+__device__ __forceinline__ unsigned long long wfin_commit_pick(const ward_state &ls, int j, int J, int nbp, int64_t n, int t0, int ca, int cb, const wrefine &rf,
+                                                               int max_size, int32_t *__restrict__ merges, int32_t *__restrict__ asz, int32_t *__restrict__ mcol,
+                                                               int32_t *__restrict__ msz, int32_t *__restrict__ mcid, uint32_t *__restrict__ mpk,
+                                                               float *__restrict__ rowmin)
+{
+    const int a = ls.B.a[j], b = ls.B.b[j], c = (int)(n + t0 + j);
+    const int sc = ls.B.sa[j] + ls.B.sb[j];
+    const unsigned long long key = J == nbp ? ls.B.ckey2[j] : ls.B.ckey[j]; // full commit: the batch's members are all gone
+    merges[3 * (t0 + j)] = a;
+    merges[3 * (t0 + j) + 1] = b;
+    merges[3 * (t0 + j) + 2] = (int)__float_as_uint(ls.B.val[j]); // the pair's Ward distance: the dendrogram height
+    asz[a] = 0;
+    asz[b] = 0;
+    asz[c] = sc;
+    const int cc = rf.wide ? c : ca;
+    mcol[c] = cc;
+    if (rf.wide) msz[ca] = 0;
+    msz[cc] = sc;
+    mcid[cc] = c;
+    msz[cb] = 0;
+    if (mpk) { // the packed copy the row scans read (scan_row_m)
+        if (rf.wide) mpk[ca] = 0u;
+        mpk[cc] = ((uint32_t)c << wpk_bits(max_size)) | (uint32_t)sc;
+        mpk[cb] = 0u;
+    }
+    rowmin[a] = ICL_MAXF;
+    rowmin[b] = ICL_MAXF;
+    rowmin[c] = key == ~0ull ? ICL_MAXF : __uint_as_float((unsigned)(key >> 32));
+    return key;
+}
+// after the commits (J > 0): the caches of the rows that were re-minimised without the (now dead) members -- by the preselection (ov_*, full0:
+// the whole batch committed and the preselection was made for it) and by the spare workgroups (spec_*, whole batch committed) --, then the counters
+__device__ __forceinline__ void wfin_install_reminimised(ward_state *__restrict__ st, const ward_state &ls, int lane, int J, int nbp, bool full0,
+                                                         float *__restrict__ rowmin, int32_t *__restrict__ rownn)
+{
+    if (full0 && lane < ls.B.ov_n) {
+        rowmin[ls.B.ov_row[lane]] = ls.B.ov_val[lane];
+        rownn[ls.B.ov_row[lane]] = ls.B.ov_nn[lane];
+    }
+#pragma unroll
+    for (int e = 0; e < WB_RL; ++e) {
+        const int sw = lane + 64 * e; // spare workgroup
+        if (J == nbp && sw < WB_R && ls.B.spec_done[sw] == ls.B.epoch) {
+#pragma unroll
+            for (int m = 0; m < WB_RM; ++m) {
+                const int sr = ls.B.spec_row[m * WB_R + sw];
+                if (sr >= 0) {
+                    rowmin[sr] = ls.B.spec_val[m * WB_R + sw];
+                    rownn[sr] = ls.B.spec_nn[m * WB_R + sw];
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        st->nlive = ls.nlive - J;
+        st->t = ls.t + J;
+        st->B.steps = ls.B.steps + 1;
+        st->B.commits = ls.B.commits + J;
+    }
+}
+// how many of the preselected pairs (sorted by value) are certainly the next picks: those whose value does not exceed the smallest minimum (or
+// lower bound) of the rows just created -- old rows win ties, clustering.go:123-131; a new-row pair may come before the others, which stay in
+// the caches for later.  At most K of them.
+template <int K>
+__device__ __forceinline__ int wfin_safe_prefix(const ward_state &ls, int lane, int J)
+{
+    float cmin = ICL_MAXF;
+    if (lane < J) {
+        const unsigned long long key = ls.B.ckey[lane];
+        if (key != ~0ull) cmin = __uint_as_float((unsigned)(key >> 32));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cmin = fminf(cmin, __shfl_xor(cmin, off, 64));
+    const bool safe = lane < ls.B.pre_n && lane < K && ls.B.pre_val[lane < WB_KMAX ? lane : 0] <= cmin; // (sorted: a prefix)
+    return __popcll(__ballot(safe));
+}
+// the record of the next batch, np picks starting at merge t (threads j < K of the workgroup call it): pick j = (pa[j], pb[j]) of sizes psa[j],
+// psb[j] and value pv[j]; ro: the row storage of the cluster it creates (ward_new_row_k; read for j < np only).  live: clusters alive now.
+__device__ __forceinline__ void wfin_batch_record(ward_state *__restrict__ st, const ward_state &ls, int j, int np, const int *pa, const int *pb, const int *psa,
+                                                  const int *psb, const float *pv, int64_t c0, int64_t ro, int live, float *__restrict__ rowmin,
+                                                  int64_t *__restrict__ rowoff)
+{
+    if (j < np) {
+        st->B.a[j] = pa[j];
+        st->B.b[j] = pb[j];
+        st->B.sa[j] = psa[j];
+        st->B.sb[j] = psb[j];
+        st->B.val[j] = pv[j];
+        st->B.ckey[j] = st->B.ckey2[j] = ~0ull;
+        rowmin[c0 + j] = ICL_MAXF; // rows being created are not selectable yet
+        rowoff[c0 + j] = ro;
+    }
+    if (j == 0) {
+        st->B.nb = np;
+        st->B.sum_live = ls.B.sum_live + (unsigned long long)live;
+        st->B.sum_live_nb = ls.B.sum_live_nb + (unsigned long long)live * np;
+        st->B.epoch = ls.B.epoch + 1;
+        st->B.pre_n = 0;
+        st->B.ov_n = 0;
+        st->B.pre_for_nb = -1;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3551,7 +3717,6 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_lb_kernel(int64_t 
                                                                        int max_size, ward_state *__restrict__ st, const wrefine rf,
                                                                        uint32_t *__restrict__ mpk)
 {
-    static_assert(K <= WB_KMAX && K <= 32, "one lane per pick, state tables of WB_KMAX entries");
     __shared__ float sv[16];
     __shared__ int si[16];
     __shared__ int sh[8];
@@ -3572,104 +3737,31 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_lb_kernel(int64_t 
         st->B.dbg3[3] = 0;
         st->B.dbg4[3] = ~0ull;
     })
-    {
-        constexpr int NW = (int)((offsetof(ward_state, B) + offsetof(ward_batch_state, pa_flag)) / 4);
-        for (int q = threadIdx.x; q < NW; q += WB_FIN_THREADS) reinterpret_cast<int *>(&ls)[q] = reinterpret_cast<const int *>(st)[q];
-        if (threadIdx.x == 0) {
-            npk = 0;
-        }
-    }
+    wfin_snapshot(&ls, st);
+    if (threadIdx.x == 0) npk = 0;
     __syncthreads();
     if (ls.done) return;
     const int nbp = ls.B.nb, t0 = ls.t, nlive0 = ls.nlive, target = ls.target;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave == 0) {
-        // ---- (1) validate: the longest prefix in which no pair of an earlier new cluster can precede the pick (lower bounds of the new rows' minima)
-        int J = nbp;
-        {
-            float cm = ICL_MAXF;
-            if (lane < nbp) {
-                const unsigned long long k = ls.B.ckey[lane < WB_KMAX ? lane : 0];
-                if (k != ~0ull) cm = __uint_as_float((unsigned)(k >> 32));
-            }
-            float pm = __shfl_up(cm, 1, 64); // exclusive prefix minimum
-            if (lane == 0) pm = ICL_MAXF;
-#pragma unroll
-            for (int off = 1; off < K; off <<= 1) {
-                const float o = __shfl_up(pm, off, 64);
-                if (lane >= off) pm = fminf(pm, o);
-            }
-            const bool bad = lane >= 1 && lane < nbp && pm < ls.B.val[lane < WB_KMAX ? lane : 0];
-            const unsigned long long bm = __ballot(bad);
-            if (bm) J = __ffsll((long long)bm) - 1;
-        }
+        // ---- (1) validate (the keys are lower bounds of the new rows' minima)
+        const int J = wfin_validate<K>(ls, lane, nbp);
         if (lane == 0) sh[0] = J;
         const bool full0 = J == nbp && ls.B.pre_for_nb == nbp && nbp > 0;
         // ---- (2) commit
-        if (lane < J) {
-            const int j = lane;
-            const int a = ls.B.a[j], b = ls.B.b[j], c = (int)(n + t0 + j);
-            const unsigned long long key = J == nbp ? ls.B.ckey2[j] : ls.B.ckey[j]; // full commit: the batch's members are all gone
-            merges[3 * (t0 + j)] = a;
-            merges[3 * (t0 + j) + 1] = b;
-            merges[3 * (t0 + j) + 2] = (int)__float_as_uint(ls.B.val[j]); // the pair's Ward distance: the dendrogram height
-            asz[a] = 0;
-            asz[b] = 0;
-            asz[c] = ls.B.sa[j] + ls.B.sb[j];
-            const int ca = mcol[a], cb = mcol[b]; // recycled storage: c takes over a's column, b's column dies
-            const int cc = rf.wide ? c : ca;      // complete rows: a column per creation id, both members' columns die
-            mcol[c] = cc;
-            if (rf.wide) msz[ca] = 0;
-            msz[cc] = ls.B.sa[j] + ls.B.sb[j];
-            mcid[cc] = c;
-            msz[cb] = 0;
-            if (mpk) {
-                if (rf.wide) mpk[ca] = 0u;
-                mpk[cc] = ((uint32_t)c << wpk_bits(max_size)) | (uint32_t)(ls.B.sa[j] + ls.B.sb[j]);
-                mpk[cb] = 0u;
+        if (J > 0) {
+            if (lane < J) {
+                const int c = (int)(n + t0 + lane);
+                const unsigned long long key = wfin_commit_pick(ls, lane, J, nbp, n, t0, mcol[ls.B.a[lane]], mcol[ls.B.b[lane]], rf, max_size, merges, asz, mcol, msz, mcid, mpk, rowmin);
+                rownn[c] = key == ~0ull ? -1 : WB_NN_BOUND; // a lower bound of the row's minimum: re-minimised before it can be a pick
             }
-            rowmin[a] = ICL_MAXF;
-            rowmin[b] = ICL_MAXF;
-            rowmin[c] = key == ~0ull ? ICL_MAXF : __uint_as_float((unsigned)(key >> 32));
-            rownn[c] = key == ~0ull ? -1 : WB_NN_BOUND; // a lower bound of the row's minimum: re-minimised before it can be a pick
-        }
-        if (full0 && lane < ls.B.ov_n) { // rows re-minimised by the preselection without the (now dead) members
-            rowmin[ls.B.ov_row[lane]] = ls.B.ov_val[lane];
-            rownn[ls.B.ov_row[lane]] = ls.B.ov_nn[lane];
-        }
-#pragma unroll
-        for (int e = 0; e < WB_RL; ++e) {
-            const int sw = lane + 64 * e; // spare workgroup
-            if (J == nbp && J > 0 && sw < WB_R && ls.B.spec_done[sw] == ls.B.epoch) { // ... and by the spare workgroups
-#pragma unroll
-                for (int m = 0; m < WB_RM; ++m) {
-                    const int sr = ls.B.spec_row[m * WB_R + sw];
-                    if (sr >= 0) {
-                        rowmin[sr] = ls.B.spec_val[m * WB_R + sw];
-                        rownn[sr] = ls.B.spec_nn[m * WB_R + sw];
-                    }
-                }
-            }
-        }
-        if (lane == 0 && J > 0) {
-            st->nlive = nlive0 - J;
-            st->t = t0 + J;
-            st->B.steps = ls.B.steps + 1;
-            st->B.commits = ls.B.commits + J;
+            wfin_install_reminimised(st, ls, lane, J, nbp, full0, rowmin, rownn);
         }
         // ---- (3) the next batch out of the preselection: its leading pairs whose value does not exceed any new row's bound
         const int t1 = t0 + J, pn0 = ls.B.pre_n;
         int np = 0;
         if (full0 && t1 < target && pn0 > 0) {
-            float cmin = ICL_MAXF;
-            if (lane < J) {
-                const unsigned long long key = ls.B.ckey[lane];
-                if (key != ~0ull) cmin = __uint_as_float((unsigned)(key >> 32));
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) cmin = fminf(cmin, __shfl_xor(cmin, off, 64));
-            const bool safe = lane < pn0 && lane < K && ls.B.pre_val[lane < WB_KMAX ? lane : 0] <= cmin; // (sorted: a prefix)
-            const int nsafe = __popcll(__ballot(safe));
+            const int nsafe = wfin_safe_prefix<K>(ls, lane, J);
             np = nsafe < target - t1 ? nsafe : target - t1;
             if (lane < np) {
                 pk_a[lane] = ls.B.pre_row[lane];
@@ -3698,54 +3790,9 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_lb_kernel(int64_t 
     }
     if (npk == 0) {
         // ONE pick by the lazy selection over all rows (first step, truncated batch, stale preselection, a new row first)
-        const int64_t nvec = (n + t + 3) >> 2;
         float bv;
         int bi;
-        for (;;) {
-            bv = ICL_MAXF;
-            bi = -1;
-            for (int64_t q0 = threadIdx.x; q0 < nvec; q0 += 4 * (int64_t)blockDim.x) {
-                float4 v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int64_t q = q0 + (int64_t)j * blockDim.x;
-                    v[j] = q < nvec ? reinterpret_cast<const float4 *>(rowmin)[q] : make_float4(ICL_MAXF, ICL_MAXF, ICL_MAXF, ICL_MAXF);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int64_t q = q0 + (int64_t)j * blockDim.x;
-                    const float e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (e[i] < bv) {
-                            bv = e[i];
-                            bi = (int)(q * 4 + i);
-                        }
-                }
-            }
-            block_argmin(bv, bi, sv, si);
-            if (bi < 0) break;
-            if (threadIdx.x == 0) {
-                const int nn0 = rownn[bi];
-                sh[1] = (nn0 >= 0 && asz[nn0] > 0) ? 0 : 1; // (WB_NN_BOUND: never scanned)
-            }
-            __syncthreads();
-            const int dirty = sh[1];
-            __syncthreads();
-            if (!dirty) break;
-            float rv;
-            int ri;
-            {
-                const int noex[1] = {-1};
-                scan_row_min(Dtri + rowoff[bi], ward_row_len_rf(bi, n, rf), msz, mcid, bi, asz[bi], max_size, noex, 0, rv, ri, sv, si, rf, &fin_scr[0][0], mpk);
-            }
-            if (threadIdx.x == 0) {
-                rowmin[bi] = rv;
-                rownn[bi] = ri;
-            }
-            __threadfence_block();
-            __syncthreads();
-        }
+        ward_lazy_pick(n, t, asz, rowmin, rownn, Dtri, rowoff, msz, mcid, mpk, max_size, rf, sv, si, &sh[1], &fin_scr[0][0], bv, bi);
         if (threadIdx.x == 0) {
             st->B.slow = ls.B.slow + 1;
             if (bi < 0) {
@@ -3768,25 +3815,8 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_lb_kernel(int64_t 
     const int np = npk;
     if (threadIdx.x < K) {
         const int j = threadIdx.x;
-        if (j < np) {
-            st->B.a[j] = pk_a[j];
-            st->B.b[j] = pk_b[j];
-            st->B.sa[j] = pk_sa[j];
-            st->B.sb[j] = pk_sb[j];
-            st->B.val[j] = pk_v[j];
-            st->B.ckey[j] = st->B.ckey2[j] = ~0ull;
-            rowmin[n + t + j] = ICL_MAXF; // rows being created are not selectable yet
-            rowoff[n + t + j] = ward_new_row_k<K>(n, ld, t + j, t0, ls.B.a, merges, rowoff);
-        }
-        if (j == 0) {
-            st->B.nb = np;
-            st->B.sum_live = ls.B.sum_live + (unsigned long long)(nlive0 - J);
-            st->B.sum_live_nb = ls.B.sum_live_nb + (unsigned long long)(nlive0 - J) * np;
-            st->B.epoch = ls.B.epoch + 1;
-            st->B.pre_n = 0;
-            st->B.ov_n = 0;
-            st->B.pre_for_nb = -1;
-        }
+        const int64_t ro = j < np ? ward_new_row_k<K>(n, ld, t + j, t0, ls.B.a, merges, rowoff) : 0;
+        wfin_batch_record(st, ls, j, np, pk_a, pk_b, pk_sa, pk_sb, pk_v, n + t, ro, nlive0 - J, rowmin, rowoff);
     }
     WB_TIMER(if (threadIdx.x == 0) st->B.dbg[5] += wall_clock64() - tf0;)
 }
@@ -3822,18 +3852,6 @@ struct wb_map { // a tiny associative array spread over the lanes of a wave
     }
 };
 
-// Row storage of the cluster that merge q will create (file header): one of the WB_K spare rows, or the storage of a_{q-WB_K},
-// the higher-position member of the merge committed WB_K merges earlier.  t0 / a0: the merges [t0, t0 + J) were committed by the
-// calling kernel itself (their log entries may not be readable yet): a0[i] is the a of merge t0 + i.  q - WB_K < t0 + J always
-// holds: a batch starts at the committed count and holds at most WB_K picks.
-__device__ __forceinline__ int64_t ward_new_row(int64_t n, int64_t ld, int q, int t0, const int32_t *a0, const int32_t *merges, const int64_t *rowoff)
-{
-    if (q < WB_K) return (n + q) * ld;
-    const int p = q - WB_K;
-    const int a = p >= t0 ? a0[p - t0] : merges[3 * p];
-    return rowoff[a];
-}
-
 __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64_t n, int d, int64_t S, float *__restrict__ CT, float *__restrict__ Crow,
                                                                 float *__restrict__ cnewK, int64_t cn_stride, int32_t *__restrict__ slot_id,
                                                                 int32_t *__restrict__ id_slot, int32_t *__restrict__ asz,
@@ -3867,43 +3885,22 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
         st->B.dbg3[3] = 0;
         st->B.dbg4[3] = ~0ull;
     })
-    {
-        // (the spare workgroups' phase-A tables -- flags, matched rows, key streams: 12 of the state's 15 KB, last in the struct -- are not read here)
-        constexpr int NW = (int)((offsetof(ward_state, B) + offsetof(ward_batch_state, pa_flag)) / 4);
-        static_assert((offsetof(ward_state, B) + offsetof(ward_batch_state, pa_flag)) % 4 == 0, "snapshot by dwords");
-        for (int q = threadIdx.x; q < NW; q += WB_FIN_THREADS) reinterpret_cast<int *>(&ls)[q] = reinterpret_cast<const int *>(st)[q];
-        if (threadIdx.x == 0) npk = 0;
-    }
+    wfin_snapshot(&ls, st);
+    if (threadIdx.x == 0) npk = 0;
     __syncthreads();
     if (ls.done) return;
     const int nbp = ls.B.nb, t0 = ls.t, nlive0 = ls.nlive, target = ls.target;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // ---- (1) validate: commit the longest prefix in which no pair of an earlier new cluster precedes the pick ----
-    // (wave 0: lane j holds the smallest row minimum of c_0..c_{j-1}, an exclusive prefix minimum by shuffles)
-    static_assert(WB_K <= 32, "one lane per pick");
+    // ---- (1) validate (the keys are the new rows' minima) ----
     int J = nbp;
     if (wave == 0) {
-        float cm = ICL_MAXF;
-        if (lane < nbp) {
-            const unsigned long long k = ls.B.ckey[lane];
-            if (k != ~0ull) cm = __uint_as_float((unsigned)(k >> 32));
-        }
-        float pm = __shfl_up(cm, 1, 64); // exclusive
-        if (lane == 0) pm = ICL_MAXF;
-#pragma unroll
-        for (int off = 1; off < WB_K; off <<= 1) {
-            const float o = __shfl_up(pm, off, 64);
-            if (lane >= off) pm = fminf(pm, o);
-        }
-        const bool bad = lane >= 1 && lane < nbp && pm < ls.B.val[lane < WB_K ? lane : 0];
-        const unsigned long long bm = __ballot(bad);
-        if (bm) J = __ffsll((long long)bm) - 1;
+        J = wfin_validate<WB_K>(ls, lane, nbp);
         if (lane == 0) sh[0] = J;
     }
     // wave 0's later dependent global loads, requested NOW (their addresses only need the snapshot): the columns of the picks' members
     // (commit bookkeeping), the slots of the preselected next picks (express path; entries this kernel's commits move are overridden
     // from the lane map, as before) and the row storage the next picks inherit after a full commit of WB_K merges
-    // (ward_new_row: q - WB_K is then this batch's own merge j, whose a is ls.B.a[j]).  ~1.5 us each when waited for in turn.
+    // (ward_new_row_k: q - WB_K is then this batch's own merge j, whose a is ls.B.a[j]).  ~1.5 us each when waited for in turn.
     int pf_mca = 0, pf_mcb = 0, pf_gs = -1;
     int64_t pf_ro = 0;
     if (wave == 0) {
@@ -3989,57 +3986,11 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
             if (lane == 0) st->B.dirty_n = __popcll(lm);
         }
         if (lane < J) {
-            const int j = lane;
-            const int a = ls.B.a[j], b = ls.B.b[j], c = (int)(n + t0 + j);
-            const unsigned long long key = J == nbp ? ls.B.ckey2[j] : ls.B.ckey[j]; // full commit: the batch's members are all gone
-            merges[3 * (t0 + j)] = a;
-            merges[3 * (t0 + j) + 1] = b;
-            merges[3 * (t0 + j) + 2] = (int)__float_as_uint(ls.B.val[j]); // the pair's Ward distance: the dendrogram height
-            asz[a] = 0;
-            asz[b] = 0;
-            asz[c] = ls.B.sa[j] + ls.B.sb[j];
-            {
-                // recycled storage (file header): c takes over a's column, b's column dies.  The picks of a batch are pairwise
-                // disjoint, so the lanes touch different columns.
-                const int ca = pf_mca, cb = pf_mcb; // (= mcol[a], mcol[b]: requested at the top)
-                mcol[c] = ca;
-                msz[ca] = ls.B.sa[j] + ls.B.sb[j];
-                mcid[ca] = c;
-                msz[cb] = 0;
-                if (mpk) { // the packed copy the row scans read (scan_row_m)
-                    mpk[ca] = ((uint32_t)c << wpk_bits(max_size)) | (uint32_t)(ls.B.sa[j] + ls.B.sb[j]);
-                    mpk[cb] = 0u;
-                }
-            }
-            rowmin[a] = ICL_MAXF;
-            rowmin[b] = ICL_MAXF;
-            rowmin[c] = key == ~0ull ? ICL_MAXF : __uint_as_float((unsigned)(key >> 32));
-            rownn[c] = key == ~0ull ? -1 : rf.lb ? WB_NN_BOUND : (int)(key & 0xffffffffu); // (lb mode: the key's value is a lower bound of the row's minimum)
+            const int c = (int)(n + t0 + lane);
+            const unsigned long long key = wfin_commit_pick(ls, lane, J, nbp, n, t0, pf_mca, pf_mcb, rf, max_size, merges, asz, mcol, msz, mcid, mpk, rowmin); // (the columns were requested at the top)
+            rownn[c] = key == ~0ull ? -1 : (int)(key & 0xffffffffu); // the row's exact first minimum (the update kernel's atomicMin)
         }
-        if (full0 && lane < ls.B.ov_n) { // rows re-minimised by the preselection without the (now dead) members
-            rowmin[ls.B.ov_row[lane]] = ls.B.ov_val[lane];
-            rownn[ls.B.ov_row[lane]] = ls.B.ov_nn[lane];
-        }
-#pragma unroll
-        for (int e = 0; e < WB_RL; ++e) {
-            const int sw = lane + 64 * e; // spare workgroup
-            if (J == nbp && sw < WB_R && ls.B.spec_done[sw] == ls.B.epoch) { // ... and by the spare workgroups
-#pragma unroll
-                for (int m = 0; m < WB_RM; ++m) {
-                    const int sr = ls.B.spec_row[m * WB_R + sw];
-                    if (sr >= 0) {
-                        rowmin[sr] = ls.B.spec_val[m * WB_R + sw];
-                        rownn[sr] = ls.B.spec_nn[m * WB_R + sw];
-                    }
-                }
-            }
-        }
-        if (lane == 0) {
-            st->nlive = nlive0 - J;
-            st->t = t0 + J;
-            st->B.steps = ls.B.steps + 1;
-            st->B.commits = ls.B.commits + J;
-        }
+        wfin_install_reminimised(st, ls, lane, J, nbp, full0, rowmin, rownn);
     }
     // ---- express path (the common case), decided by wave 0: the whole batch committed, the preselection's
     // assumption held and no pair of a row just created can precede the last preselected pair -> the next batch is the
@@ -4049,20 +4000,7 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
         const int t1 = t0 + J;
         const int pn0 = ls.B.pre_n;
         if (full0 && t1 < target && pn0 > 0 && (d & 3) == 0 && (d >> 2) <= WB_FIN_THREADS) {
-            float cmin = ICL_MAXF;
-            if (lane < J) {
-                const unsigned long long key = ls.B.ckey[lane];
-                if (key != ~0ull) cmin = __uint_as_float((unsigned)(key >> 32));
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) cmin = fminf(cmin, __shfl_xor(cmin, off, 64));
-            // the preselected pairs are sorted: those whose value is <= every new row's minimum are certainly next
-            // (old rows win ties); a new-row pair may come before the others, which stay in the caches for later
-            int nsafe = 0;
-            {
-                const bool safe = lane < pn0 && ls.B.pre_val[lane < WB_K ? lane : 0] <= cmin;
-                nsafe = __popcll(__ballot(safe));
-            }
+            const int nsafe = wfin_safe_prefix<WB_K>(ls, lane, J);
             if (nsafe > 0) {
                 express = 1;
                 const int np = nsafe < target - t1 ? nsafe : target - t1;
@@ -4110,25 +4048,14 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
                         pk_sa[j] = ls.B.pre_sa[j];
                         pk_sb[j] = ls.B.pre_sb[j];
                         pk_sla[j] = srcsel;
-                        st->B.a[j] = ls.B.pre_row[j];
-                        st->B.b[j] = ls.B.pre_nn[j];
-                        st->B.sa[j] = ls.B.pre_sa[j];
-                        st->B.sb[j] = ls.B.pre_sb[j];
-                        st->B.val[j] = ls.B.pre_val[j];
-                        st->B.ckey[j] = st->B.ckey2[j] = ~0ull;
-                        rowmin[n + t1 + j] = ICL_MAXF; // rows being created are not selectable yet
-                        rowoff[n + t1 + j] = (J == WB_K && t1 + j >= WB_K) ? pf_ro : ward_new_row(n, ld, t1 + j, t0, ls.B.a, merges, rowoff);
                     } else if (lane >= WB_K && lane < WB_K + np)
                         pk_slb[lane - WB_K] = srcsel;
+                    if (lane < WB_K) { // the record, straight from the preselected list; after a full commit of WB_K merges the picks inherit this batch's own rows (requested at the top)
+                        const int64_t ro = lane >= np ? 0 : (J == WB_K && t1 + lane >= WB_K) ? pf_ro : ward_new_row_k<WB_K>(n, ld, t1 + lane, t0, ls.B.a, merges, rowoff);
+                        wfin_batch_record(st, ls, lane, np, ls.B.pre_row, ls.B.pre_nn, ls.B.pre_sa, ls.B.pre_sb, ls.B.pre_val, n + t1, ro, nlive0 - J, rowmin, rowoff);
+                    }
                     if (lane == 0) {
                         npk = np;
-                        st->B.nb = np;
-                        st->B.sum_live = ls.B.sum_live + (unsigned long long)(nlive0 - J);
-                        st->B.sum_live_nb = ls.B.sum_live_nb + (unsigned long long)(nlive0 - J) * np;
-                        st->B.epoch = ls.B.epoch + 1;
-                        st->B.pre_n = 0;
-                        st->B.ov_n = 0;
-                        st->B.pre_for_nb = -1;
                         WB_TIMER(st->B.dbg2[0] += wall_clock64() - tf0;)
                     }
                 }
@@ -4269,7 +4196,7 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
                     bool died = false;
                     for (int i = j + 1; i < J; ++i) died |= (x == ls.B.a[i]) | (x == ls.B.b[i]); // its minimum partner was merged later in the same batch
                     crow[j] = (int)(n + t0 + j);
-                    cnn[j] = (died || rf.lb) ? -2 : x; // (lb mode: a lower bound, never a pick: the batch ends where it would come first)
+                    cnn[j] = died ? -2 : x;
                     cval[j] = __uint_as_float((unsigned)(key >> 32));
                     cused[j] = false;
                 }
@@ -4397,53 +4324,9 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
     }
     if (npk == 0) {
         // slow path (first step, truncated batch, or nothing usable): ONE pick by the lazy selection over all rows
-        const int64_t nvec = (n + t + 3) >> 2;
         float bv;
         int bi;
-        for (;;) {
-            bv = ICL_MAXF;
-            bi = -1;
-            for (int64_t q0 = threadIdx.x; q0 < nvec; q0 += 4 * (int64_t)blockDim.x) {
-                float4 v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int64_t q = q0 + (int64_t)j * blockDim.x;
-                    v[j] = q < nvec ? reinterpret_cast<const float4 *>(rowmin)[q] : make_float4(ICL_MAXF, ICL_MAXF, ICL_MAXF, ICL_MAXF);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int64_t q = q0 + (int64_t)j * blockDim.x;
-                    const float e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (e[i] < bv) {
-                            bv = e[i];
-                            bi = (int)(q * 4 + i);
-                        }
-                }
-            }
-            block_argmin(bv, bi, sv, si);
-            if (bi < 0) break;
-            if (threadIdx.x == 0) {
-                const int nn0 = rownn[bi];
-                sh[1] = (nn0 >= 0 && asz[nn0] > 0) ? 0 : 1; // (WB_NN_BOUND: never scanned)
-            }
-            __syncthreads();
-            const int dirty = sh[1];
-            __syncthreads();
-            if (!dirty) break;
-            float rv;
-            int ri;
-            {
-                const int noex[1] = {-1};
-                scan_row_min(Dtri + rowoff[bi], ward_row_len(bi, n), msz, mcid, bi, asz[bi], max_size, noex, 0, rv, ri, sv, si, rf, &fin_scr[0][0], mpk);
-            }
-            if (threadIdx.x == 0) {
-                rowmin[bi] = rv;
-                rownn[bi] = ri;
-            }
-            __syncthreads();
-        }
+        ward_lazy_pick(n, t, asz, rowmin, rownn, Dtri, rowoff, msz, mcid, mpk, max_size, rf, sv, si, &sh[1], &fin_scr[0][0], bv, bi);
         if (threadIdx.x == 0) {
             st->B.slow = ls.B.slow + 1;
             if (bi < 0) {
@@ -4468,25 +4351,8 @@ __global__ __launch_bounds__(WB_FIN_THREADS) void ward_finish_batch_kernel(int64
     const int np = npk;
     if (threadIdx.x < WB_K) {
         const int j = threadIdx.x;
-        if (j < np) {
-            st->B.a[j] = pk_a[j];
-            st->B.b[j] = pk_b[j];
-            st->B.sa[j] = pk_sa[j];
-            st->B.sb[j] = pk_sb[j];
-            st->B.val[j] = pk_v[j];
-            st->B.ckey[j] = st->B.ckey2[j] = ~0ull;
-            rowmin[n + t + j] = ICL_MAXF; // rows being created are not selectable yet
-            rowoff[n + t + j] = ward_new_row(n, ld, t + j, t0, ls.B.a, merges, rowoff);
-        }
-        if (j == 0) {
-            st->B.nb = np;
-            st->B.sum_live = ls.B.sum_live + (unsigned long long)(nlive0 - J);
-            st->B.sum_live_nb = ls.B.sum_live_nb + (unsigned long long)(nlive0 - J) * np;
-            st->B.epoch = ls.B.epoch + 1;
-            st->B.pre_n = 0;
-            st->B.ov_n = 0;
-            st->B.pre_for_nb = -1;
-        }
+        const int64_t ro = j < np ? ward_new_row_k<WB_K>(n, ld, t + j, t0, ls.B.a, merges, rowoff) : 0;
+        wfin_batch_record(st, ls, j, np, pk_a, pk_b, pk_sa, pk_sb, pk_v, n + t, ro, nlive0 - J, rowmin, rowoff);
     }
     if (!lw) {
         // MergeClusters centroid (clustering.go:37-40): (float(sa)*Ca + float(sb)*Cb) / float(sa+sb), each op rounded
@@ -4615,23 +4481,7 @@ static int ward_ensure_impl(icl_ctx *ctx, int64_t n, int d)
     const bool wide = ward_wide_alloc(ctx, n, d);
     if (w->capN != n || w->capD != d || w->wide_alloc != wide) {
         // (re)allocate for exactly this shape
-        void *ptrs[] = {w->CT, w->Crow, w->cnew, w->cnewI, w->slot_id, w->id_slot, w->asz, w->rowmin, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid,
-                        w->Dtri, w->merges, w->st, w->nrm, w->colsum, w->zero, w->mpk, w->bl1, w->bex, w->rowub};
-        w->bl1 = nullptr;
-        w->bex = nullptr;
-        w->rowub = nullptr;
-        w->nrm = nullptr;
-        w->colsum = nullptr;
-        w->zero = nullptr;
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-        if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
-        w->graph_exec = nullptr;
-        w->CT = w->Crow = w->cnew = w->cnewI = w->rowmin = w->Dtri = nullptr;
-        w->slot_id = w->id_slot = w->asz = w->rownn = w->merges = w->mcol = w->msz = w->mcid = nullptr;
-        w->rowoff = nullptr;
-        w->st = nullptr;
-        w->capN = 0;
+        ward_ws_release(w);
         w->S = (n + 63) / 64 * 64;
         if (w->S == 0) w->S = 64;
         w->M = 2 * n + 4; // creation ids: n singletons + at most n - 1 merged clusters (padded: rowmin is read in groups of four)
@@ -4670,7 +4520,6 @@ static int ward_ensure_impl(icl_ctx *ctx, int64_t n, int d)
         WS_ALLOC(colsum, double, icl_dist_colsum_doubles((int)dd));
         WS_ALLOC(zero, char, 256);
         ICL_HIP(ctx, hipMemsetAsync(w->zero, 0, 256, ctx->stream));
-        w->mpk = nullptr;
         WS_ALLOC(mpk, uint32_t, w->ld);
         WS_ALLOC(msz, int32_t, w->ld);
         WS_ALLOC(mcid, int32_t, w->ld);
