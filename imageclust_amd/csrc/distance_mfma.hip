@@ -5,7 +5,7 @@
 // It replaces the arithmetic of ComputeInitialDistanceMatrix (/root/reference/internal/clustering/clustering.go:61-73)
 // only approximately: the GEMM form sums in a different order and cancels, so its low bits differ from the reference's
 // sequential sum (clustering.go:137-141,152-155).  The bit-exact tile is ward_dist_exact_kernel (ward.hip); cluster
-// ids produced from D~ are reported, never asserted, against the reference.
+// ids produced from D~ are reported, never asserted, against the reference.  Entries are stored clamped to >= +0 (NaN kept).
 //
 // Precision: fp32 operands are split e = hi + lo with hi = bf16(e), lo = bf16(e - hi) and the dot product is
 // hi.hi + hi.lo + lo.hi (the lo.lo term is below fp32 resolution): the three products are ONE bf16 GEMM over the
@@ -162,7 +162,12 @@ __global__ __launch_bounds__(256) void dist_mfma_kernel(const dist_args p)
     tri_decode32(blockIdx.x, ti, tj);
     const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * DG_BN;
     dist_gemm_tile<BF16>(p.A, p.B, p.n, p.K, p.zero, i0, j0, smem);
-    dist_store_rows<MODE>(smem, p.norms, p.n, i0, j0, p.out, p.rowoff, p.ld, [](float ni, float nj, float c) { return 0.5f * (ni + nj) - c; });
+    // the true value is >= 0; the estimate of (near-)duplicate rows is rounding noise of either sign.  Negative and -0 are stored as +0, a NaN stays
+    // a NaN: the merge loop's (value bits, id) keys then order every entry of the matrix as its value does (ward.hip, ward_lw_value)
+    dist_store_rows<MODE>(smem, p.norms, p.n, i0, j0, p.out, p.rowoff, p.ld, [](float ni, float nj, float c) {
+        const float v = 0.5f * (ni + nj) - c;
+        return v > 0.0f ? v : (v == v ? 0.0f : v);
+    });
 }
 
 static size_t dist_lds_bytes()

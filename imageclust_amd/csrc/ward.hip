@@ -1906,7 +1906,7 @@ __global__ __launch_bounds__(UPD_THREADS) void ward_update_lw_kernel(const int32
     if (act) {
         const float dax = tri_at(Dtri, rowoff, mcol, a, x), dbx = tri_at(Dtri, rowoff, mcol, b, x), dab = tri_at(Dtri, rowoff, mcol, a, b);
         float v = ((float)(sa + sx) * dax + (float)(sb + sx) * dbx - (float)sx * dab) / (float)(sa + sb + sx);
-        v = v > 0.0f ? v : 0.0f; // keeps the (bits, column) key order == value order
+        v = v > 0.0f ? v : (v == v ? 0.0f : v); // keeps the (bits, column) key order == value order; a NaN stays a NaN, out of the keys below
         Dtri[rowoff[c] + mcol[x]] = v;
         if (v < ICL_MAXF) key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)x;
     }
@@ -3035,7 +3035,7 @@ __global__ __launch_bounds__(64) void ward_pull_rows_kernel(const ward_peers pe,
 __device__ __forceinline__ float ward_lw_value(float dax, float dbx, float dab, int sa, int sb, int sx)
 {
     const float v = ((float)(sa + sx) * dax + (float)(sb + sx) * dbx - (float)sx * dab) / (float)(sa + sb + sx);
-    return v > 0.0f ? v : 0.0f; // keeps the (bits, column) key order == value order
+    return v > 0.0f ? v : (v == v ? 0.0f : v); // keeps the (bits, column) key order == value order; a NaN stays a NaN (no key: v < ICL_MAXF is false)
 }
 
 __global__ __launch_bounds__(WB_THREADS) void ward_update_batch_lw_kernel(int64_t S, const int32_t *__restrict__ slot_id,
@@ -4785,7 +4785,7 @@ struct ward_plan {
     int rows, fill;               // ICL_ROWS_* (icl_last_ward_mode); WARD_FILL_*: what the call WANTS -- should the int8 scratch not fit, ward_fill takes the f32 GEMM
     bool use_rowub;               // the integer GEMM's epilogue leaves every row's smallest upper bound for the initial minima (ICL_DIST_ROWUB=0: A/B switch, they make their own first pass)
     // the row scans read size + creation id of a column as ONE word (w->mpk; null: off) when 2 n + 4 creation ids fit beside the bits of max_size
-    // (not in FAST mode: the packed scans compare (value bits, id) keys, which needs values >= +0 -- exact Ward values are, the MFMA estimates need not be)
+    // (not in FAST mode: the packed scans compare (value bits, id) keys, which needs values >= +0 -- exact Ward values are; the MFMA estimates are since dist_mfma_kernel clamps them, FAST mode keeps the unpacked scans)
     int pk_bits;
     uint32_t *mpk;
     icl_ward_shard *sh;           // strip-sharded loop (a group's replicas, multi_gpu.hip): this replica's main workgroups take the blocks == sh_rank (mod sh_n)

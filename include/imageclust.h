@@ -757,7 +757,9 @@ int64_t icl_last_merges(icl_ctx *ctx, int32_t *pairs, int64_t cap_pairs);
  * value FindClosestClusters found (:123-131).  Returns the number of merges; fills min(cap, merges) values. */
 int64_t icl_last_merge_values(icl_ctx *ctx, float *vals, int64_t cap);
 /* MFMA distance tile alone (north_star K6): D~[i][j] = 0.5*(|e_i|^2+|e_j|^2-2 e_i.e_j), bf16x3 split operands,
- * fp32 accumulate; lower triangle incl. diagonal written, packed row-major with leading dimension ld. */
+ * fp32 accumulate; lower triangle incl. diagonal written, packed row-major with leading dimension ld.  An estimate that
+ * comes out negative or -0 (rounding noise of near-duplicate rows) is stored as +0, a NaN stays a NaN: this is, entry for
+ * entry, the matrix ICL_UPDATE_LW clusters. */
 int icl_distance_mfma_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, float *d_D, int64_t ld);
 
 /* ---- synthetic inputs ---------------------------------------------------------------------- */

@@ -1,5 +1,7 @@
 """Child process of test_ward_gpu.py::test_config2_full_size_two_pipelines_agree_100k: clusters the same synthetic E with
-whatever ICL_WARD_* switches the parent put into the environment (they are read once per process) and prints digests."""
+whatever ICL_WARD_* switches the parent put into the environment (they are read once per process) and prints digests.
+With --npy it clusters the matrix of a file and saves ids, member order, merge log and heights: exact mode, or FAST mode
+(ICL_UPDATE_LW) with ICL_CHILD_UPDATE=1 in the environment (test_fast_mode_gpu.py)."""
 import hashlib
 import json
 import os
@@ -49,7 +51,8 @@ if __name__ == "__main__":
     if sys.argv[1] == "--npy":  # E from a file, results into an npz: small cases the parent compares with the oracle
         E = np.load(sys.argv[2])
         mn, mx = int(sys.argv[4]), int(sys.argv[5])
-        cid, rank, nc = ctx.cluster(E, mn, mx)
+        update = _lib.UPDATE_LW if os.environ.get("ICL_CHILD_UPDATE") == "1" else _lib.UPDATE_EXACT  # 1: FAST mode (test_fast_mode_gpu.py)
+        cid, rank, nc = ctx.cluster(E, mn, mx, update)
         np.savez(sys.argv[3], cid=cid, rank=rank, nc=nc, merges=ctx.last_merges(), values=ctx.last_merge_values())
     else:
         n, d, seed, mn, mx = (int(x) for x in sys.argv[1:6])
