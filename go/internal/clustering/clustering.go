@@ -348,11 +348,12 @@ func ResumeClustering(centroids [][]float32, sizes []int32, minSize, maxSize, kT
 	return ResumeClusteringApart(centroids, sizes, minSize, maxSize, kTarget, nil, nil)
 }
 
-// ResumeClusteringApart is ResumeClustering with keep-apart constraints (iclengine.ClusterManyApart, icl_cluster_many_apart): apartPairs
+// ResumeClusteringApart is ResumeClustering with keep-apart constraints (iclengine.ClusterManyApart, icl_cluster_many_apart; above
+// iclengine.ManySeededMax clusters iclengine.ClusterApart, icl_cluster_apart on the large-N engine): apartPairs
 // lists cluster indices that must never share a cluster, apartClass (one int per cluster, 0: none) classes whose members must not --
 // class 1 on every kept cluster, with kTarget their number, lets the kept clusters take the leftovers but not each other.  A merged
 // cluster inherits the bans of both parents, so the loop may end before kTarget clusters are reached.  With both lists empty it is
-// ResumeClustering; with constraints above iclengine.ManySeededMax clusters the result's Status is ICL_ERR_UNSUPPORTED (6) and ok false.
+// ResumeClustering, whatever the number of clusters.
 func ResumeClusteringApart(centroids [][]float32, sizes []int32, minSize, maxSize, kTarget int, apartPairs [][2]int32,
 	apartClass []int32) (iclengine.SeededResult, bool) {
 	pr := iclengine.SeededProblem{Centroids: centroids, Sizes: sizes, MinSize: minSize, MaxSize: maxSize, KTarget: kTarget}
@@ -362,7 +363,11 @@ func ResumeClusteringApart(centroids [][]float32, sizes []int32, minSize, maxSiz
 	for _, c := range apartClass {
 		constrained = constrained || c != 0
 	}
-	if constrained { // (the call refuses more than ManySeededMax seeds itself, as the problem's status)
+	if constrained && len(sizes) > iclengine.ManySeededMax { // above the one-workgroup routes' cap: the large-N engine's constrained call
+		var one iclengine.SeededResult
+		one, err = iclengine.ClusterApart(iclengine.ApartProblem{SeededProblem: pr, ApartClass: apartClass, ApartPairs: apartPairs})
+		res = []iclengine.SeededResult{one}
+	} else if constrained {
 		res, err = iclengine.ClusterManyApart([]iclengine.ApartProblem{{SeededProblem: pr, ApartClass: apartClass, ApartPairs: apartPairs}})
 	} else if len(sizes) > iclengine.ManySeededMax { // above the one-workgroup routes' cap: the large-N engine's seeded call
 		var one iclengine.SeededResult

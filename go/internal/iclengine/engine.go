@@ -260,13 +260,29 @@ func clusterManySeeded(probs []SeededProblem, apart []ApartProblem) ([]SeededRes
 	return out, nil
 }
 
-// ManySeededMax is icl_cluster_many_seeded's cap on the seeds of one problem; ClusterSeeded has none.
+// ManySeededMax is the cap of icl_cluster_many_seeded and icl_cluster_many_apart on the seeds of one problem; ClusterSeeded and
+// ClusterApart have none.
 const ManySeededMax = 2048
 
 // ClusterSeeded runs ONE seeded problem on the large-N engine (icl_cluster_seeded: the exact pipeline of ward.hip, any number of seeds).
 // The result is ClusterManySeeded's for the same problem, bit for bit; the merge log comes from icl_last_merges.  The error is the call's
 // own; ICL_ERR_CONSTRAINT and ICL_ERR_UNSUPPORTED are the result's Status.
 func ClusterSeeded(pr SeededProblem) (SeededResult, error) {
+	return clusterSeeded(pr, nil)
+}
+
+// ClusterApart runs ONE constrained seeded problem on the large-N engine (icl_cluster_apart: the one-merge-per-step exact loop of
+// ward.hip under a keep-apart relation, any number of seeds).  The result is ClusterManyApart's for the same problem, bit for bit, and
+// with no constraint ClusterSeeded's.  A malformed constraint is the call's error.
+func ClusterApart(pr ApartProblem) (SeededResult, error) {
+	if pr.ApartClass != nil && len(pr.ApartClass) != len(pr.Sizes) {
+		return SeededResult{}, fmt.Errorf("%d classes for %d seeds", len(pr.ApartClass), len(pr.Sizes))
+	}
+	return clusterSeeded(pr.SeededProblem, &pr)
+}
+
+// the body of both: apart is nil (icl_cluster_seeded) or holds the problem's constraints (icl_cluster_apart)
+func clusterSeeded(pr SeededProblem, apart *ApartProblem) (SeededResult, error) {
 	raw, e := Ctx()
 	if e != nil {
 		return SeededResult{}, e
@@ -288,9 +304,24 @@ func ClusterSeeded(pr SeededProblem) (SeededResult, error) {
 	rank := make([]int32, m+1)
 	var nc C.int32_t
 	i32 := func(p *int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(p)) }
-	rc := C.icl_cluster_seeded((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
-		C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cid[0]), i32(&rank[0]), &nc,
-		(*C.float)(unsafe.Pointer(&cout[0])))
+	var rc C.int
+	if apart == nil {
+		rc = C.icl_cluster_seeded((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
+			C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cid[0]), i32(&rank[0]), &nc,
+			(*C.float)(unsafe.Pointer(&cout[0])))
+	} else {
+		cls := make([]int32, m+1) // 0: no class
+		copy(cls, apart.ApartClass)
+		pairs := make([]int32, 0, 2*len(apart.ApartPairs)+1)
+		for _, q := range apart.ApartPairs {
+			pairs = append(pairs, q[0], q[1])
+		}
+		npairs := len(pairs) / 2
+		pairs = append(pairs, 0) // (never empty: its address is taken)
+		rc = C.icl_cluster_apart((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
+			C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cls[0]), C.int64_t(npairs), i32(&pairs[0]),
+			i32(&cid[0]), i32(&rank[0]), &nc, (*C.float)(unsafe.Pointer(&cout[0])))
+	}
 	if rc != C.ICL_OK && rc != C.ICL_ERR_CONSTRAINT && rc != C.ICL_ERR_UNSUPPORTED {
 		return SeededResult{}, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
 	}

@@ -21,7 +21,7 @@ TILES_AUTO, TILES_LOCAL, TILES_DISTRIBUTED = 0, 1, 2
 MERGE_GPU0, MERGE_SHARDED = 0, 1
 CONV_P8_OFF, CONV_P8_AUTO, CONV_P8_ALL = 0, 1, 2
 CONV_SPLIT = 16
-ROWS_SINGLE, ROWS_EXACT_BATCH, ROWS_LW_BOUND, ROWS_LW_FAST = 0, 1, 2, 3
+ROWS_SINGLE, ROWS_EXACT_BATCH, ROWS_LW_BOUND, ROWS_LW_FAST, ROWS_SINGLE_APART = 0, 1, 2, 3, 4
 FILE_FAIL_NEXT_LEADER = 0x100
 MANY_MID_AUTO, MANY_MID_OFF, MANY_MID_ON = 0, 1, 2  # icl_set_many_options: the mid-size route (257 to 2048 rows) of icl_cluster_many
 PNG_HOST, PNG_GPU = 0, 1  # icl_set_png_options: where a qualifying PNG of a batched file call is inflated and unfiltered
@@ -145,6 +145,8 @@ SYMBOLS = [
     ("icl_cluster_many_apart_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 17),
     ("icl_cluster_seeded", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
+    ("icl_cluster_apart", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _pi32, _vp]),
+    ("icl_cluster_apart_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _pi32, _vp]),
     ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
     ("icl_nearest", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("icl_nearest_dev", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -1375,10 +1377,31 @@ class Context:
                    for r, o, k, w in zip(out, pk["e_off"], pk["n"], pk["d"])]
         return out
 
-    def cluster_seeded(self, C_, seed_size, min_size, max_size, k_target=0, want_centroids=True, dev=False):
+    @staticmethod
+    def _apart_args(m, apart_class, apart_pairs):
+        """the constraint arguments of icl_cluster_apart[_dev] -> (the arrays to keep alive, (apart_class, n_pairs, apart_pairs))"""
+        cl = None if apart_class is None else np.ascontiguousarray(np.asarray(apart_class, np.int32).reshape(-1))
+        if cl is not None and len(cl) != m:
+            raise ValueError("%d apart_class entries for %d seeds" % (len(cl), m))
+        pa = np.zeros((0, 2), np.int32) if apart_pairs is None else np.ascontiguousarray(np.asarray(apart_pairs, np.int32).reshape(-1, 2))
+        return (cl, pa), (cl.ctypes.data if cl is not None and m else None, len(pa), pa.ctypes.data if len(pa) else None)
+
+    def cluster_apart(self, C_, seed_size, min_size, max_size, k_target=0, apart_class=None, apart_pairs=None, want_centroids=True, dev=False):
+        """icl_cluster_apart: ONE constrained seeded problem (cluster_many_apart's semantics: apart_class one int per seed, apart_pairs (i, j)
+        seed indices, merged clusters inherit both parents' bans) on the large-N engine, any number of seeds.  Arguments and return value
+        are cluster_seeded's; a malformed constraint raises ICLError(ICL_ERR_ARG).  dev=True runs icl_cluster_apart_dev on a device copy."""
+        m = len(np.asarray(seed_size).reshape(-1))
+        return self.cluster_seeded(C_, seed_size, min_size, max_size, k_target, want_centroids, dev, _apart=self._apart_args(m, apart_class, apart_pairs))
+
+    def cluster_apart_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, apart_class=None, apart_pairs=None, d_C_out=None):
+        """icl_cluster_apart_dev on m x d device floats: cluster_seeded_dev with the constraints of cluster_apart (host arrays)."""
+        return self.cluster_seeded_dev(d_C, m, d, seed_size, min_size, max_size, k_target, d_C_out, _apart=self._apart_args(m, apart_class, apart_pairs))
+
+    def cluster_seeded(self, C_, seed_size, min_size, max_size, k_target=0, want_centroids=True, dev=False, _apart=None):
         """icl_cluster_seeded: ONE seeded problem (cluster_many_seeded's semantics) on the large-N engine, any number of seeds -> (cluster_id,
         seed_rank, n_clusters, status, merges, C_out); C_out is None without want_centroids.  status is ICL_OK, ICL_ERR_CONSTRAINT or
-        ICL_ERR_UNSUPPORTED (rows of -1, C_out zero); every other error raises.  dev=True runs icl_cluster_seeded_dev on a device copy."""
+        ICL_ERR_UNSUPPORTED (rows of -1, C_out zero); every other error raises.  dev=True runs icl_cluster_seeded_dev on a device copy.
+        (_apart: cluster_apart's constraint arguments; the call is then icl_cluster_apart[_dev].)"""
         Cs = np.ascontiguousarray(C_, np.float32)
         m, d = Cs.shape
         ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
@@ -1387,13 +1410,15 @@ class Context:
         cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
         nc = _i32()
         co = np.zeros((m, d), np.float32) if want_centroids else None
-        args = (m, d, _ptr(ss), int(min_size), int(max_size), int(k_target), cid.ctypes.data, rank.ctypes.data, C.byref(nc))
+        args = (m, d, _ptr(ss), int(min_size), int(max_size), int(k_target)) + (_apart[1] if _apart else ()) + (cid.ctypes.data, rank.ctypes.data, C.byref(nc))
+        fn_host = self.L.icl_cluster_apart if _apart else self.L.icl_cluster_seeded
+        fn_dev = self.L.icl_cluster_apart_dev if _apart else self.L.icl_cluster_seeded_dev
         if dev:
             dE = self.malloc(max(Cs.nbytes, 16))
             dC = self.malloc(max(Cs.nbytes, 16)) if want_centroids else None
             try:
                 self.h2d(dE, Cs)
-                rc = self.L.icl_cluster_seeded_dev(self.h, _vp(dE), *args, _vp(dC) if want_centroids else None)
+                rc = fn_dev(self.h, _vp(dE), *args, _vp(dC) if want_centroids else None)
                 if want_centroids and Cs.size and rc in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
                     self.d2h(co, dC)
             finally:
@@ -1401,20 +1426,21 @@ class Context:
                 if dC is not None:
                     self.free(dC)
         else:
-            rc = self.L.icl_cluster_seeded(self.h, Cs.ctypes.data if m else None, *args, _ptr(co))
+            rc = fn_host(self.h, Cs.ctypes.data if m else None, *args, _ptr(co))
         if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
             check(self.h, rc)
         merges = self.last_merges() if rc == ICL_OK else np.zeros((0, 2), np.int32)
         return cid[:m], rank[:m], nc.value, rc, merges, co
 
-    def cluster_seeded_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, d_C_out=None):
+    def cluster_seeded_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, d_C_out=None, _apart=None):
         """icl_cluster_seeded_dev on m x d device floats (d_C_out: m x d device floats, or None) -> (cluster_id, seed_rank, n_clusters,
-        status); the log is last_merges()."""
+        status); the log is last_merges().  (_apart: as cluster_seeded's.)"""
         ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
         cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
         nc = _i32()
-        rc = self.L.icl_cluster_seeded_dev(self.h, _vp(d_C), m, d, ss.ctypes.data if m else None, int(min_size), int(max_size), int(k_target),
-                                           cid.ctypes.data, rank.ctypes.data, C.byref(nc), _vp(d_C_out) if d_C_out is not None else None)
+        fn = self.L.icl_cluster_apart_dev if _apart else self.L.icl_cluster_seeded_dev
+        rc = fn(self.h, _vp(d_C), m, d, ss.ctypes.data if m else None, int(min_size), int(max_size), int(k_target), *(_apart[1] if _apart else ()),
+                cid.ctypes.data, rank.ctypes.data, C.byref(nc), _vp(d_C_out) if d_C_out is not None else None)
         if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
             check(self.h, rc)
         return cid[:m], rank[:m], nc.value, rc

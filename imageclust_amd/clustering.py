@@ -168,12 +168,16 @@ def _constrained(apart_class, apart_pairs) -> bool:
 
 def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class=None, apart_pairs=None):
     """One seeded problem -> (cluster_id, seed_rank, n_clusters, status, merges, C_out): icl_cluster_many_seeded up to its cap,
-    icl_cluster_seeded (ward.hip's exact pipeline, no cap) above.  With a keep-apart constraint: icl_cluster_many_apart, which has the
-    cap and nothing above it (ICL_ERR_UNSUPPORTED)."""
+    icl_cluster_seeded (ward.hip's exact pipeline, no cap) above.  With a keep-apart constraint: icl_cluster_many_apart up to the same
+    cap, icl_cluster_apart (ward.hip's one-merge-per-step exact loop, no cap) above -- ICLError(ICL_ERR_UNSUPPORTED) where the handle
+    has no such call.  An unconstrained problem never takes a constrained call, whatever the two cost."""
     if _constrained(apart_class, apart_pairs):
         if len(sizes) > MANY_SEEDED_MAX:
-            raise _lib.ICLError(_lib.ICL_ERR_UNSUPPORTED, "%d seeds with keep-apart constraints: icl_cluster_many_apart holds at most %d"
-                                % (len(sizes), MANY_SEEDED_MAX))
+            large = getattr(ctx, "cluster_apart", None)
+            if large is None:  # a handle without the large-N constrained call (a _lib.Group: group contexts are not covered)
+                raise _lib.ICLError(_lib.ICL_ERR_UNSUPPORTED, "%d seeds with keep-apart constraints: icl_cluster_many_apart holds at most %d and "
+                                    "this handle has no icl_cluster_apart" % (len(sizes), MANY_SEEDED_MAX))
+            return large(C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs, want_centroids=True)
         return ctx.cluster_many_apart([(C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs)], want_merges=True, want_centroids=True)[0]
     if len(sizes) > MANY_SEEDED_MAX:
         return ctx.cluster_seeded(C, sizes, minSize, maxSize, k_target, want_centroids=True)
@@ -188,8 +192,8 @@ def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_targ
     at, else CalculateOptimalClusters of the item total decides -> ((cluster_id, seed_rank, n_clusters, merges, C_out), True) at seed
     granularity -- C_out[i] is the centroid of the final cluster whose first seed is i, zero for every other seed -- or (None, False)
     on impossible constraints.  apart_pairs ((i, j) seed indices) and apart_class (one int per seed, 0: none; the seeds of one non-zero
-    class) name seeds that must never share a cluster (icl_cluster_many_apart: a merged cluster inherits the bans of both parents; up to
-    2 048 seeds, ICLError(ICL_ERR_UNSUPPORTED) above); the loop may then end before k clusters are reached."""
+    class) name seeds that must never share a cluster (icl_cluster_many_apart: a merged cluster inherits the bans of both parents;
+    icl_cluster_apart above 2 048 seeds); the loop may then end before k clusters are reached."""
     ctx = ctx or default_context()
     C = np.asarray(centroids, np.float32)
     if C.ndim != 2:
@@ -430,7 +434,8 @@ class Clustering:
 
     def keep_apart(self, keys):
         """The clusters holding these ids are mutually apart from now on: no recluster() merges two of them, nor clusters that swallowed
-        them.  Held per image id, so it survives merges and dissolve().  ValueError when two of the ids already share a cluster."""
+        them.  Held per image id, so it survives merges and dissolve().  ValueError when two of the ids already share a cluster.  The
+        state may hold any number of clusters (icl_cluster_many_apart up to 2 048, icl_cluster_apart on the large-N engine above)."""
         keys = list(dict.fromkeys(keys))
         where = {k: i for i, c in enumerate(self.clusters) for k in c.Members}
         at = [where[k] for k in keys]
@@ -477,7 +482,8 @@ class Clustering:
 
     def absorb_leftovers(self) -> List[str]:
         """"Put the leftovers somewhere": the loop resumed with every kept, unfrozen cluster (at least minSize items) allowed to take
-        the dropped clusters' images but not another kept cluster -- class 1 of icl_cluster_many_apart -- and k_target = the kept and
+        the dropped clusters' images but not another kept cluster -- class 1 of icl_cluster_many_apart, of icl_cluster_apart above
+        2 048 held clusters -- and k_target = the kept and
         the frozen clusters.  Returns the ids still unplaced: those no kept cluster could take (sizes, keep_apart, frozen)."""
         kept = [len(c.Members) >= self.minSize and not c.Frozen for c in self.clusters]
         k = sum(kept) + sum(c.Frozen for c in self.clusters)
@@ -500,8 +506,8 @@ class Clustering:
         return C, ss
 
     def recluster(self, k_target: int = 0, _anchor=None) -> bool:
-        """Resume the loop from the clusters held, keep_apart's constraints respected.  False, with the state as it was, when the
-        constraints cannot be met.  (_anchor: absorb_leftovers' class per cluster.)"""
+        """Resume the loop from the clusters held, keep_apart's constraints respected at any number of clusters (_seeded_call picks
+        the engine).  False, with the state as it was, when the constraints cannot be met.  (_anchor: absorb_leftovers' class per cluster.)"""
         C, ss = self.seeds()
         pairs = np.array(self._apart_pairs(), np.int32).reshape(-1, 2)
         extra = (_anchor, pairs) if _constrained(_anchor, pairs) else ()

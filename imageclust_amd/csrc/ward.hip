@@ -42,6 +42,7 @@
 #include "resnet_model.h" // icl_embed_dev_locked
 #include "ward_exact_tile.h" // DT_TILE, ward_exact_tile (shared with nearest.hip)
 #include "ward_value.h" // ward_sqdist_thread, ward_pair_value, ward_scale, ward_merge_elem (shared with ward_many.hip)
+#include "apart_bits.h" // ab_bad_arg, ab_words, ab_table_bytes: the host rules of the keep-apart relation (shared with ward_many.hip)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #include <algorithm>
@@ -217,6 +218,10 @@ struct icl_ward_ws {
     hipGraphExec_t graph_exec = nullptr;
     ward_graph_key graph_key;  // what graph_exec was captured for
     size_t upd_attr_bytes = 0; // the kernels' > 64 KB dynamic-LDS opt-in made on this context's device
+    size_t upd_apart_attr_bytes = 0; // ... and ward_update_apart_kernel's
+    // the keep-apart relation of a constrained call (icl_cluster_apart): capN rows of ab_words(capN) words over the column slots, allocated by the
+    // first such call on the shape and released with it (the captured graph of constrained steps holds its address)
+    icl_dev_grow abits;
     bool wx_attr = false;
     // what the tables and the matrix above hold, for the test hook icl_ward_dump_pairs_dev: the shape of the clustering call that ran last on this
     // workspace.  state 0: none (fresh workspace, or something re-initialised the tables since: ward_launch_init), 1: a finished call the hook can
@@ -242,6 +247,7 @@ static void ward_ws_release(icl_ward_ws *w)
     drop(w->CT), drop(w->Crow), drop(w->cnew), drop(w->cnewI), drop(w->slot_id), drop(w->id_slot), drop(w->asz), drop(w->rowmin), drop(w->rownn);
     drop(w->rowoff), drop(w->mcol), drop(w->msz), drop(w->mcid), drop(w->Dtri), drop(w->merges), drop(w->st), drop(w->nrm), drop(w->colsum);
     drop(w->zero), drop(w->mpk), drop(w->bl1), drop(w->bex), drop(w->rowub);
+    w->abits.release();
     w->capN = 0;
 }
 
@@ -1437,6 +1443,16 @@ __global__ void ward_init_kernel(int64_t n, int64_t S, int64_t M, int64_t ld, in
 __global__ void ward_seed_sizes_kernel(int64_t n, const int32_t *__restrict__ eff, int32_t *__restrict__ asz, int32_t *__restrict__ msz, uint32_t *__restrict__ mpk, int szb);
 __global__ void ward_seed_cout_kernel(const int32_t *__restrict__ src, const float *__restrict__ C, const float *__restrict__ Crow, const int32_t *__restrict__ id_slot,
                                       int64_t n, int d, int64_t S, float *__restrict__ out);
+// the constrained call's kernels (icl_cluster_apart): likewise, behind the seeded ones
+__global__ void ward_apart_class_kernel(int64_t n, int64_t aw, const int32_t *__restrict__ cls, uint32_t *__restrict__ abits);
+__global__ void ward_apart_pairs_kernel(int64_t npairs, int64_t aw, const int32_t *__restrict__ pairs, uint32_t *__restrict__ abits);
+__global__ void ward_apart_mask_kernel(int64_t n, int64_t aw, const uint32_t *__restrict__ abits, const int64_t *__restrict__ rowoff, float *__restrict__ Dtri);
+__global__ void ward_update_apart_kernel(int d, int dqp, int64_t S, float *__restrict__ CT, float *__restrict__ Crow, const float *__restrict__ cnew,
+                                         const int32_t *__restrict__ slot_id, const int32_t *__restrict__ asz, const int32_t *__restrict__ rownn,
+                                         const int64_t *__restrict__ rowoff, const int32_t *__restrict__ mcol, const int32_t *__restrict__ msz,
+                                         const int32_t *__restrict__ mcid, float *__restrict__ Dtri, ward_state *__restrict__ st, int max_size, int64_t n,
+                                         float *__restrict__ rowmin, int32_t *__restrict__ rownn_w, const wrefine rf, uint32_t *__restrict__ abits, int64_t aw);
+__global__ void ward_apart_commit_kernel(const ward_state *__restrict__ st, const int32_t *__restrict__ mcol, int64_t aw, uint32_t *__restrict__ abits);
 
 // Centroid store used by the update kernel: CT4[g][slot][4] = centroid(slot)[4g .. 4g+3]  (k-groups of 4 are
 // contiguous per slot, slots contiguous per group): one dwordx4 per lane streams 4 consecutive k of the lane's slot
@@ -1715,157 +1731,11 @@ __global__ __launch_bounds__(1024) void ward_finish_kernel(int64_t n, int d, int
 #define UPD_PAD_G (4 * UPD_SG)        /* zero groups past the end: the unrolled-by-3 loop may prefetch up to 4 stages beyond */
 static inline int64_t upd_groups(int d) { return (((int64_t)d + 3) / 4 + UPD_SG - 1) / UPD_SG * UPD_SG; } // whole stages
 
-__global__ __launch_bounds__(UPD_THREADS) void ward_update_exact_kernel(int d, int dqp, int64_t S, float *__restrict__ CT,
-                                                               float *__restrict__ Crow, const float *__restrict__ cnew,
-                                                               const int32_t *__restrict__ slot_id,
-                                                               const int32_t *__restrict__ asz, const int32_t *__restrict__ rownn,
-                                                               const int64_t *__restrict__ rowoff, const int32_t *__restrict__ mcol,
-                                                               const int32_t *__restrict__ msz, const int32_t *__restrict__ mcid,
-                                                               float *__restrict__ Dtri, ward_state *__restrict__ st,
-                                                               int max_size, int64_t n, float *__restrict__ rowmin,
-                                                               int32_t *__restrict__ rownn_w, const wrefine rf)
-{
-    extern __shared__ __attribute__((aligned(16))) float4 upd_lds[]; // [2][UPD_SG][64] p ring, then the new centroid image
-    float4 (*ring)[UPD_SG][64] = reinterpret_cast<float4 (*)[UPD_SG][64]>(upd_lds);
-    if (blockIdx.x == gridDim.x - 2) { // preselect(t+1) rides along as one workgroup: it never touches row c / ckey
-        float *sv = reinterpret_cast<float *>(upd_lds);
-        int *si = reinterpret_cast<int *>(sv + 16);
-        int *sh = si + 16;
-        ward_preselect(n, asz, rowmin, rownn_w, Dtri, rowoff, msz, mcid, max_size, st, sv, si, sh, rf);
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // provably wave-uniform: role and addresses stay scalar
-    // ---- every load that does not depend on the step's state is issued FIRST, so the kernel pays two dependent
-    // memory round trips (state -> sizes) before its pipeline runs instead of six ----
-    const int done = st->done, valid = st->cur_valid, nlive = st->nlive;
-    const int a = st->cur_a, b = st->cur_b, c = st->cur_c, sa = st->cur_sa, sb = st->cur_sb, mv_from = st->mv_from, mv_to = st->mv_to;
-    const bool mover = blockIdx.x == gridDim.x - 1;
-    const int64_t slot = mover ? 0 : (int64_t)blockIdx.x * 64 + lane; // S is a multiple of 64
-    const int xraw = slot_id[slot];
-    // column loads use a scalar row base + one per-lane 32-bit byte offset (the CT4 image is < 4 GiB)
-    const char *ctb = reinterpret_cast<const char *>(CT);
-    const unsigned voff = (unsigned)slot * 16u;
-    const int64_t row_bytes = S * 16;
-    const int pj = wave - 1;
-    float4 va[UPD_GP], vb[UPD_GP], vc[UPD_GP];
-    auto load = [&](float4 (&v)[UPD_GP], int stage) {
-        const char *rb = ctb + (int64_t)(stage * UPD_SG + pj * UPD_GP) * row_bytes; // wave-uniform
-#pragma unroll
-        for (int u = 0; u < UPD_GP; ++u) v[u] = *reinterpret_cast<const float4 *>(rb + (int64_t)u * row_bytes + voff);
-    };
-    constexpr int CNR = 2; // new-centroid float4s staged per thread per pass
-    float4 cnr[CNR];
-#pragma unroll
-    for (int i = 0; i < CNR; ++i) {
-        const int g = threadIdx.x + i * UPD_THREADS;
-        cnr[i] = g < dqp + UPD_PAD_G ? reinterpret_cast<const float4 *>(cnew)[g] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (wave > 0 && !mover) { // speculative: harmless when the workgroup turns out to have nothing to do
-        load(va, 0);
-        load(vb, 1);
-    }
-    if (done || !valid) return;
-    if (mover) { // compaction copy (disjoint from every column read below: mv_to is a free slot)
-        if (mv_to < 0) return;
-        const int dq = (d + 3) >> 2;
-        for (int g = threadIdx.x; g < dq; g += UPD_THREADS)
-            *reinterpret_cast<float4 *>(CT + ct4_off(g, S, mv_to)) = *reinterpret_cast<const float4 *>(CT + ct4_off(g, S, mv_from));
-        for (int k = threadIdx.x; k < d; k += UPD_THREADS) Crow[(int64_t)mv_to * d + k] = Crow[(int64_t)mv_from * d + k];
-        return;
-    }
-    if ((int64_t)blockIdx.x * 64 >= nlive) return;
-    const int x = slot < nlive ? xraw : -1;
-    bool live = x >= 0 && x != c;
-    const int sx = live ? asz[x] : 0;
-    const int mx = live ? mcol[x] : 0; // the column of this lane's cluster
-    live = live && sx > 0;
-    const int sc = sa + sb; // == asz[c]
-    const bool act = live && (sx + sc <= max_size); // else: banned for good (static mask); value never read
-    if (!__any(act)) return;                         // same 64 slots in every wave: a workgroup-uniform exit
-    // CT4 and cnew carry dqp + UPD_PAD_G zero-padded groups: padded k contribute (0-0)^2 = +0 exactly and no load
-    // in the pipeline needs a guard.
-    // the new centroid is staged once into LDS: scalar loads would share lgkmcnt with the ring's ds_writes and, being
-    // unordered against them, force lgkmcnt(0) (a full LDS round trip) on every k-group
-    float4 *cn4 = upd_lds + 2 * UPD_SG * 64;
-#pragma unroll
-    for (int i = 0; i < CNR; ++i) {
-        const int g = threadIdx.x + i * UPD_THREADS;
-        if (g < dqp + UPD_PAD_G) cn4[g] = cnr[i];
-    }
-    for (int g = threadIdx.x + CNR * UPD_THREADS; g < dqp + UPD_PAD_G; g += UPD_THREADS) cn4[g] = reinterpret_cast<const float4 *>(cnew)[g];
-    __syncthreads();
-    float s = 0.0f;
-    auto produce = [&](const float4 (&v)[UPD_GP], int stage, int buf) {
-        const int g0 = stage * UPD_SG + pj * UPD_GP;
-#pragma unroll
-        for (int u = 0; u < UPD_GP; ++u) {
-            const float4 cv = cn4[g0 + u]; // broadcast ds_read_b128
-            const f2 xa = {v[u].x, v[u].y}, xb = {v[u].z, v[u].w}, ca = {cv.x, cv.y}, cb = {cv.z, cv.w};
-            const f2 da = xa - ca, db = xb - cb; // clustering.go:139 via :84 (v_pk_add_f32 with neg)
-            const f2 pa = da * da, pb = db * db; // :154 products, each rounded (v_pk_mul_f32)
-            ring[buf][pj * UPD_GP + u][lane] = make_float4(pa.x, pa.y, pb.x, pb.y);
-        }
-    };
-    auto consume = [&](int buf) {
-        // all of the stage's reads are issued at once, right behind the barrier, so they sit in the LDS queue AHEAD of the
-        // producers' next 24 KiB of ds_write_b128 (measured: reads issued later wait ~300 cycles behind those writes)
-        float4 p[UPD_SG];
-#pragma unroll
-        for (int g = 0; g < UPD_SG; ++g) p[g] = ring[buf][g][lane];
-#pragma unroll
-        for (int g = 0; g < UPD_SG; ++g) {
-            s = s + p[g].x; // :154 the running sum, strictly in k order
-            s = s + p[g].y;
-            s = s + p[g].z;
-            s = s + p[g].w;
-        }
-    };
-    // producers keep TWO stages of column loads in flight (3 register sets) so a stage's arithmetic never waits on
-    // the memory latency; the p ring in LDS is double-buffered (stage parity)
-    const int nstage = dqp / UPD_SG; // the loop is unrolled by 3 (register rotation): stages >= nstage are skipped
-    for (int i = 0; i < nstage; i += 3) {
-        if (wave > 0) {
-            load(vc, i + 2); // loads past the last stage read the zero padding and are never consumed
-            produce(va, i, i & 1);
-        }
-        __syncthreads();
-        if (wave == 0) consume(i & 1);
-        if (i + 1 < nstage) {
-            if (wave > 0) {
-                load(va, i + 3);
-                produce(vb, i + 1, (i + 1) & 1);
-            }
-            __syncthreads();
-            if (wave == 0) consume((i + 1) & 1);
-        }
-        if (i + 2 < nstage) {
-            if (wave > 0) {
-                load(vb, i + 4);
-                produce(vc, i + 2, i & 1);
-            }
-            __syncthreads();
-            if (wave == 0) consume(i & 1);
-        }
-    }
-    if (wave != 0) return;
-    const float num = (float)((int64_t)sx * (int64_t)sc);
-    const float den = (float)(sx + sc);
-    const float val = (num / den) * s;
-    unsigned long long key = ~0ull;
-    if (act) {
-        Dtri[rowoff[c] + mx] = val;
-        // values are >= +0 (a sum of squares scaled by a positive ratio): their bit patterns order like the floats,
-        // so min over (bits<<32 | x) is "smallest value, then smallest column" == the row scan's first strict minimum
-        if (val < ICL_MAXF) key = ((unsigned long long)__float_as_uint(val) << 32) | (unsigned)x;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(key, off, 64);
-        key = o < key ? o : key;
-    }
-    if (lane == 0 && key != ~0ull) atomicMin(&st->ckey, key);
-}
+// The kernel's text is ward_update_exact_body.h, included twice: here as it is, and at the end of this file with a KEEP-APART relation over
+// the clusters (ward_update_apart_kernel, icl_cluster_apart).
+#define WU_APART 0
+#include "ward_update_exact_body.h"
+#undef WU_APART
 
 // update(t), FAST mode (ICL_UPDATE_LW): the new cluster's row by the Lance-Williams recurrence for Ward,
 //   d(c,x) = [ (sa+sx) d(a,x) + (sb+sx) d(b,x) - sx d(a,b) ] / (sa+sb+sx),
@@ -4753,7 +4623,8 @@ static int ward_nspare(const icl_ctx *ctx, bool lb_rows, bool sharded) { return 
 
 // ---- the clustering call's host driver: ward_run_stages (below) = ward_make_plan -> ward_init_ws -> ward_fill -> ward_run_single / ward_run_batched ->
 // ward_collect, for cluster_locked (ward_check_args in front, icl_ward_assign_ids behind) and cluster_seeded_locked (ward_seed_admit in front,
-// ward_final_list behind); every decision of a call is made once, in its ward_plan.
+// ward_final_list behind; with a ward_apart record the constrained call, icl_cluster_apart: ward_apart_build in front of the plan); every decision of
+// a call is made once, in its ward_plan.
 // what one clustering call holds beside the workspace: all of it until ward_run_stages returns (a hipFree / hipHostFree in mid-call would wait for the device)
 struct ward_call {
     struct shard_guard { // a replica of a sharded group call that leaves early releases the replicas waiting for it (icl_ward_shard::wait)
@@ -4765,6 +4636,7 @@ struct ward_call {
     pin_guard pin;              // ... and their pinned memory
     dev_guard ec, pq;           // distance bounds: the centred copy of E, the integer GEMM's scratch
     dev_guard eff;              // a seeded call's effective sizes (ward_seed::d_eff)
+    dev_guard acls, apairs;     // a constrained call's class array and pair list (ward_apart), until the bit table is built from them
 };
 
 constexpr int GRAPH_STEPS = 64;
@@ -4775,6 +4647,16 @@ struct ward_seed {
     const int32_t *h_eff; // [n] effective sizes (ward_seed_admit)
     int64_t T;            // merges asked for: max(0, n - k), k from k_target or CalculateOptimalClusters(items)
     const int32_t *d_eff; // ... on the device: ward_run_stages' copy (ward_call::eff)
+};
+// A CONSTRAINED seeded call (icl_cluster_apart, DESIGN.md "Constrained seeded clustering, large N"): a keep-apart relation over the seeds that
+// merged clusters inherit, as arguments ab_bad_arg accepted.  Such a call runs the one-merge-per-step exact loop only, whatever ICL_WARD_BATCH says:
+// ward_update_apart_kernel, ward_apart_commit_kernel, and the finish kernel as it is.
+struct ward_apart {
+    const int32_t *h_cls;   // [n] classes (may be null: all 0)
+    const int32_t *h_pairs; // [2 * npairs] seed indices
+    int64_t npairs;
+    uint32_t *bits;         // the bit rows over the column slots (icl_ward_ws::abits), built by ward_run_stages ...
+    int64_t aw;             // ... of ab_words(n) words each
 };
 enum { WARD_FILL_EXACT, WARD_FILL_BOUND_F32, WARD_FILL_BOUND_I8, WARD_FILL_FAST }; // how a call fills its own rows of the initial matrix
 struct ward_plan {
@@ -4793,6 +4675,8 @@ struct ward_plan {
     int32_t *fdrec;               // the express step's data phase runs in ward_finish_data_kernel from a record the finish kernel leaves behind cnewI (null: it does not)
     bool prof_update, use_graph;
     const ward_seed *seed;        // null: the rows are singletons
+    const ward_apart *apart;      // null: no keep-apart relation (else: a seeded call, one merge per step, exact fill)
+    unsigned apart_blocks;        // ward_apart_commit_kernel's grid
     // launch shapes.  One merge per step: 64 slots per workgroup + preselect + compaction workgroups; LDS = new centroid image + p ring
     // batched: main workgroups are persistent, at most one per CU (they draw blocks from a counter), fewer when the input has fewer blocks; lb: WL_U creation ids per lane
     unsigned upd_blocks, lw_blocks, wx_blocks, lw_blocks_b, lb_blocks, fd_blocks, il_blocks, pull_blocks;
@@ -4813,7 +4697,7 @@ static int ward_check_args(icl_ctx *ctx, int64_t n, int32_t min_size, int32_t ma
 
 // (arguments that passed ward_check_args, n > 0, the workspace of ward_ensure(ctx, n, d) in place)
 static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi, ward_plan *out,
-                          const ward_seed *seed = nullptr)
+                          const ward_seed *seed = nullptr, const ward_apart *apart = nullptr)
 {
     const icl_ward_ws *w = ctx->ward;
     ward_plan p{};
@@ -4821,8 +4705,9 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
     (void)icl_calc_optimal_clusters(n, min_size, max_size, &k);
     p.n = n, p.T = seed ? seed->T : n - k, p.d = d, p.max_size = max_size;
     p.seed = seed;
+    p.apart = apart;
     p.lw = update == ICL_UPDATE_LW;
-    p.batched = ward_batch_env();
+    p.batched = ward_batch_env() && !apart; // (the relation is kept by the one-merge-per-step loop only)
     if (own_hi < 0) own_hi = n;
     if (own_lo < 0 || own_lo > own_hi || own_hi > n || own_lo % DT_TILE || (own_hi % DT_TILE && own_hi != n))
         return icl_fail(ctx, ICL_ERR_ARG, "own rows [%lld, %lld) must be whole 128-row tile rows of [0, %lld)", (long long)own_lo, (long long)own_hi, (long long)n);
@@ -4836,7 +4721,7 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
     p.use_bound = !seed && !p.lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
     p.lbm = p.use_bound && p.mpk && ward_lb_rows(ctx, n, d);
     p.wide = p.lbm && w->wide_alloc;
-    p.rows = !p.batched ? ICL_ROWS_SINGLE : p.lw ? ICL_ROWS_LW_FAST : p.lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH;
+    p.rows = apart ? ICL_ROWS_SINGLE_APART : !p.batched ? ICL_ROWS_SINGLE : p.lw ? ICL_ROWS_LW_FAST : p.lbm ? ICL_ROWS_LW_BOUND : ICL_ROWS_EXACT_BATCH;
     p.fill = p.lw ? WARD_FILL_FAST : WARD_FILL_EXACT;
     if (p.use_bound) {
         // the bounds themselves: from the integer GEMM (distance_i8.hip: exact int8 matrix-core arithmetic on a fixed-point image of the rows, 3x
@@ -4853,6 +4738,7 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
     p.prof_update = (ctx->prof_mask >> ICL_K_UPDATE) & 1;
     p.use_graph = !(p.batched && p.sh) && !p.prof_update && p.T >= 2 * GRAPH_STEPS;
     p.upd_blocks = (unsigned)(w->S / 64) + 2;
+    p.apart_blocks = (unsigned)icl_ceil_div(std::max<int64_t>(ab_words(n), 1), 256);
     p.lw_blocks = (unsigned)icl_ceil_div(w->S, UPD_THREADS) + 1;
     p.dqp = (int)upd_groups(d), p.dqb = (int)wb_groups(d);
     p.upd_lds = (size_t)(p.dqp + UPD_PAD_G) * 16 + (size_t)2 * UPD_SG * 64 * 16;
@@ -4955,6 +4841,8 @@ static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const flo
             ICL_TRY(ward_bounds_f32(ctx, b, n, w->Dtri, w->rowoff, own_lo, own_hi));
     } else
         ICL_TRY(launch_dist_exact_rows(ctx, d_E, p.seed ? p.seed->d_eff : nullptr, n, d, w->Dtri, w->rowoff, 0, 0, own_lo / DT_TILE, icl_ceil_div(own_hi, DT_TILE)));
+    if (p.apart) // every pair of the relation holds MaxFloat32 from the start: no scan below or in the loop takes such an entry for a value
+        hipLaunchKernelGGL(ward_apart_mask_kernel, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, ctx->stream, n, p.apart->aw, p.apart->bits, w->rowoff, w->Dtri);
     // (rows computed on other GPUs were laid out into the matrix by icl_ward_unpack_spans_dev before this call: flagged bounds under the same rule
     // as the rows above -- icl_ward_distance_rows_dev -- so the scans below treat them like this GPU's own)
     if (!p.use_bound && !p.lw && (own_lo > 0 || own_hi < n)) { // foreign rows taken as VALUES: a flagged entry would be read as a negative distance
@@ -5027,7 +4915,12 @@ static void ward_step_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, c
         if (p.lw)
             hipLaunchKernelGGL(ward_update_lw_kernel, dim3(p.lw_blocks), dim3(UPD_THREADS), 0, ctx->stream, w->slot_id, w->asz, w->rowoff, w->mcol, w->msz,
                                w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn);
-        else
+        else if (p.apart) { // the same kernel under the relation, then row(ca) |= row(cb): the launch order publishes it to the next step
+            hipLaunchKernelGGL(ward_update_apart_kernel, dim3(p.upd_blocks), dim3(UPD_THREADS), p.upd_lds, ctx->stream, p.d, p.dqp, w->S, w->CT, w->Crow,
+                               w->cnew, w->slot_id, w->asz, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, rf,
+                               p.apart->bits, p.apart->aw);
+            hipLaunchKernelGGL(ward_apart_commit_kernel, dim3(p.apart_blocks), dim3(256), 0, ctx->stream, w->st, w->mcol, p.apart->aw, p.apart->bits);
+        } else
             hipLaunchKernelGGL(ward_update_exact_kernel, dim3(p.upd_blocks), dim3(UPD_THREADS), p.upd_lds, ctx->stream, p.d, p.dqp, w->S, w->CT, w->Crow,
                                w->cnew, w->slot_id, w->asz, w->rownn, w->rowoff, w->mcol, w->msz, w->mcid, w->Dtri, w->st, p.max_size, p.n, w->rowmin, w->rownn, rf);
     }
@@ -5035,12 +4928,14 @@ static void ward_step_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, c
 }
 static int ward_run_single(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const wrefine &rf)
 {
-    if (p.upd_lds > 64 * 1024 && w->upd_attr_bytes < p.upd_lds) { // per context, i.e. per device
+    const void *upd_fn = p.apart ? (const void *)ward_update_apart_kernel : (const void *)ward_update_exact_kernel;
+    size_t &attr_bytes = p.apart ? w->upd_apart_attr_bytes : w->upd_attr_bytes;
+    if (p.upd_lds > 64 * 1024 && attr_bytes < p.upd_lds) { // per context, i.e. per device
         hipFuncAttributes fa;
-        ICL_HIP(ctx, hipFuncGetAttributes(&fa, (const void *)ward_update_exact_kernel));
+        ICL_HIP(ctx, hipFuncGetAttributes(&fa, upd_fn));
         if (p.upd_lds + fa.sharedSizeBytes > 160 * 1024) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "embedding dimension %d too large for the update kernel's LDS image", p.d);
-        ICL_HIP(ctx, hipFuncSetAttribute((const void *)ward_update_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.upd_lds));
-        w->upd_attr_bytes = p.upd_lds;
+        ICL_HIP(ctx, hipFuncSetAttribute(upd_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.upd_lds));
+        attr_bytes = p.upd_lds;
     }
     hipLaunchKernelGGL(ward_presel_kernel, dim3(1), dim3(1024), 0, ctx->stream, p.n, w->asz, w->rowmin, w->rownn, w->Dtri, w->rowoff, w->msz, w->mcid,
                        p.max_size, w->st, rf); // merge 0 has no update in front of it
@@ -5287,22 +5182,46 @@ static int ward_collect(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const 
     return ICL_OK;
 }
 
+// The keep-apart relation of a constrained call as bit rows in the workspace (w->abits: n rows of ab_words(n) words, ICL_ERR_NOMEM where they do not
+// fit): the classes expanded and the pairs set ON THE DEVICE -- anchors over 11 000 clusters are 60 M pairs --, symmetric, zero diagonal, the same
+// table whatever the order of the pairs (integer OR).  The host arrays are the caller's again when this returns.
+static int ward_apart_build(icl_ctx *ctx, icl_ward_ws *w, int64_t n, ward_apart *ap, ward_call &c)
+{
+    ap->aw = ab_words(n);
+    ICL_TRY(w->abits.ensure(ctx, std::max<size_t>(ab_table_bytes(n), 16), "icl_cluster_apart: the keep-apart bit rows"));
+    ap->bits = w->abits.as<uint32_t>();
+    ICL_HIP(ctx, hipMemsetAsync(ap->bits, 0, ab_table_bytes(n), ctx->stream));
+    if (ap->h_cls) {
+        ICL_TRY(icl_dev_upload(ctx, c.acls, ap->h_cls, (size_t)n * 4, "icl_cluster_apart: classes"));
+        hipLaunchKernelGGL(ward_apart_class_kernel, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, ctx->stream, n, ap->aw, (const int32_t *)c.acls.p, ap->bits);
+    }
+    if (ap->npairs > 0) {
+        ICL_TRY(icl_dev_upload(ctx, c.apairs, ap->h_pairs, (size_t)ap->npairs * 8, "icl_cluster_apart: pairs"));
+        hipLaunchKernelGGL(ward_apart_pairs_kernel, dim3((unsigned)std::min<int64_t>(icl_ceil_div(ap->npairs, 256), 65535)), dim3(256), 0, ctx->stream, ap->npairs, ap->aw,
+                           (const int32_t *)c.apairs.p, ap->bits);
+    }
+    ICL_HIP(ctx, hipGetLastError());
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICL_OK;
+}
+
 // The stages of one clustering call on n > 0 rows that passed the caller's checks, up to ctx->last (its merges: the log).  seed (may be null):
-// the rows are seed clusters, and max_size is the clamped one (ward_admission::kmax).
+// the rows are seed clusters, and max_size is the clamped one (ward_admission::kmax).  apart (may be null; with a seed only): the relation.
 static int ward_run_stages(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, int32_t min_size, int32_t max_size, int update, int64_t own_lo, int64_t own_hi,
-                           ward_seed *seed = nullptr)
+                           ward_seed *seed = nullptr, ward_apart *apart = nullptr)
 {
     ward_call c;
     c.shard.s = ctx->shard;
     ICL_TRY(ward_ensure(ctx, n, d));
     icl_ward_ws *w = ctx->ward;
+    if (apart) ICL_TRY(ward_apart_build(ctx, w, n, apart, c));
     if (seed) {
         ICL_TRY(icl_dev_upload(ctx, c.eff, seed->h_eff, (size_t)n * 4, "icl_cluster_seeded: seed sizes"));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_eff is the caller's to free once this returns, whatever it returns)
         seed->d_eff = (const int32_t *)c.eff.p;
     }
     ward_plan p;
-    ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p, seed));
+    ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p, seed, apart));
     ICL_HIP(ctx, hipEventCreate(&c.e0.p));
     ICL_HIP(ctx, hipEventCreate(&c.e1.p));
     ICL_HIP(ctx, hipEventCreate(&c.e2.p));
@@ -5339,15 +5258,17 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
 // ONE problem of m seed clusters with icl_cluster_many_seeded's semantics (ward_seed_admit) and no cap on m: ward_run_stages with a ward_seed, the
 // final list from the seeds' real sizes.  d_C: the seed centroids on the device; seed_size on the host (no entry 0: checked by the entry points);
 // d_C_out: device, or null.  A problem the call refuses (ICL_ERR_UNSUPPORTED / ICL_ERR_CONSTRAINT) gets rows of -1 and a C_out of zeros, as the many-call's.
+// apart (may be null): the keep-apart relation of icl_cluster_apart[_dev] -- arguments that ab_bad_arg accepted --, `what` the entry point's name.
 static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
-                                 int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
+                                 int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out, ward_apart *apart = nullptr,
+                                 const char *what = "icl_cluster_seeded")
 {
     ctx->last.merges.clear();
     ctx->last.merge_vals.clear();
     *n_clusters = 0;
     auto no_loop = [&] { // what the icl_last_* reports say of a call that ran no merge loop
         ctx->last.bound_viol = 0;
-        ctx->last.mode[0] = ward_batch_env() ? ICL_ROWS_EXACT_BATCH : ICL_ROWS_SINGLE;
+        ctx->last.mode[0] = apart ? ICL_ROWS_SINGLE_APART : ward_batch_env() ? ICL_ROWS_EXACT_BATCH : ICL_ROWS_SINGLE;
         ctx->last.mode[1] = 0;
         ctx->last.stats[0] = ctx->last.stats[1] = ctx->last.stats[2] = ctx->last.stats[3] = 0;
         ctx->last.dist_ms = ctx->last.merge_ms = 0;
@@ -5361,15 +5282,15 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
             return (int)ICL_ERR_HIP;
         return code;
     };
-    if (ctx->shard) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "icl_cluster_seeded: not on a replica of a group");
+    if (ctx->shard) return icl_fail(ctx, refuse(ICL_ERR_UNSUPPORTED), "%s: not on a replica of a group", what);
     std::vector<int32_t> eff((size_t)m);
     const ward_admission ad = ward_seed_admit(m, seed_size, min_size, max_size, k_target, eff.data());
     if (ad.status != ICL_OK) // (the reference's own message goes without the call's name, as icl_cluster's)
-        return icl_fail(ctx, refuse(ad.status), "%s%s", ad.status == ICL_ERR_CONSTRAINT ? "" : "icl_cluster_seeded: ", ad.why.c_str());
+        return icl_fail(ctx, refuse(ad.status), "%s%s%s", ad.status == ICL_ERR_CONSTRAINT ? "" : what, ad.status == ICL_ERR_CONSTRAINT ? "" : ": ", ad.why.c_str());
     icl_ward_ws *w = nullptr;
     if (m - ad.k > 0) {
         ward_seed sd{eff.data(), m - ad.k, nullptr};
-        ICL_TRY(ward_run_stages(ctx, d_C, m, d, min_size, ad.kmax, ICL_UPDATE_EXACT, 0, -1, &sd));
+        ICL_TRY(ward_run_stages(ctx, d_C, m, d, min_size, ad.kmax, ICL_UPDATE_EXACT, 0, -1, &sd, apart));
         w = ctx->ward;
     } else // nothing to merge: every seed is a final cluster
         no_loop();
@@ -5377,7 +5298,7 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
     const ward_list_result r = ward_final_list(m, seed_size, min_size, ctx->last.merges.data(), (int64_t)ctx->last.merges.size() / 2, cluster_id, seed_rank,
                                                n_clusters, &finals);
     if (r.kind != ward_list_result::OK) // (the engine's own log: the sizes were checked with the arguments)
-        return icl_fail(ctx, refuse(ICL_ERR_HIP), "icl_cluster_seeded: %s", ward_list_text(r).c_str());
+        return icl_fail(ctx, refuse(ICL_ERR_HIP), "%s: %s", what, ward_list_text(r).c_str());
     if (d_C_out && out_bytes) {
         std::vector<int32_t> src((size_t)m, -1);
         for (size_t f = 0; f < finals.size(); f += 2) src[(size_t)finals[f + 1]] = finals[f];
@@ -5401,14 +5322,45 @@ static int seeded_check_args(icl_ctx *ctx, const char *what, const float *C, int
     return ICL_OK;
 }
 
+// the relation's ARG check (icl_cluster_apart[_dev]): ab_bad_arg's cases, behind seeded_check_args
+static int apart_check_args(icl_ctx *ctx, const char *what, int64_t m, const int32_t *apart_class, int64_t n_pairs, const int32_t *apart_pairs)
+{
+    const std::string bad = ab_bad_arg(m, apart_class, apart_pairs, n_pairs);
+    return bad.empty() ? ICL_OK : icl_fail(ctx, ICL_ERR_ARG, "%s: %s", what, bad.c_str());
+}
+
+// The two forms of a seeded call behind their ARG checks -- centroids on the device, centroids in host memory --, with or without a relation.
+static int seeded_call_dev(icl_ctx *ctx, const char *what, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                           int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out, ward_apart *apart)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    return cluster_seeded_locked(ctx, d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, apart, what);
+}
+static int seeded_call_host(icl_ctx *ctx, const char *what, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out, ward_apart *apart)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    const size_t bytes = (size_t)m * (size_t)d * 4;
+    dev_guard dC, dO;
+    ICL_TRY(icl_dev_alloc(ctx, dC, std::max<size_t>(bytes, 16), "%s: C (%lld x %d floats)", what, (long long)m, d));
+    if (C_out) ICL_TRY(icl_dev_alloc(ctx, dO, std::max<size_t>(bytes, 16), "%s: C_out (%lld x %d floats)", what, (long long)m, d));
+    if (bytes) ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p, apart, what);
+    if (C_out && bytes && rc != ICL_ERR_HIP && rc != ICL_ERR_NOMEM) { // (a refused problem's rows are zero)
+        ICL_HIP(ctx, hipMemcpyAsync(C_out, dO.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
+}
+
 extern "C" int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
                                       int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
 {
     return no_throw(ctx, "icl_cluster_seeded_dev", [&]() -> int {
     ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded_dev", d_C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    icl_device_guard g(ctx->device);
-    return cluster_seeded_locked(ctx, d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out);
+    return seeded_call_dev(ctx, "icl_cluster_seeded", d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, nullptr);
     });
 }
 
@@ -5417,19 +5369,35 @@ extern "C" int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32
 {
     return no_throw(ctx, "icl_cluster_seeded", [&]() -> int {
     ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded", C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    icl_device_guard g(ctx->device);
-    const size_t bytes = (size_t)m * (size_t)d * 4;
-    dev_guard dC, dO;
-    ICL_TRY(icl_dev_alloc(ctx, dC, std::max<size_t>(bytes, 16), "icl_cluster_seeded: C (%lld x %d floats)", (long long)m, d));
-    if (C_out) ICL_TRY(icl_dev_alloc(ctx, dO, std::max<size_t>(bytes, 16), "icl_cluster_seeded: C_out (%lld x %d floats)", (long long)m, d));
-    if (bytes) ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p);
-    if (C_out && bytes && rc != ICL_ERR_HIP && rc != ICL_ERR_NOMEM) { // (a refused problem's rows are zero)
-        ICL_HIP(ctx, hipMemcpyAsync(C_out, dO.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    return seeded_call_host(ctx, "icl_cluster_seeded", C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, C_out, nullptr);
+    });
+}
+
+// ---- constrained seeded clustering on this engine (icl_cluster_apart[_dev]; DESIGN.md "Constrained seeded clustering, large N") ---------------
+// icl_cluster_seeded with icl_cluster_many_apart's relation and no cap on m: the same admission, final list and C_out, the relation as bit rows
+// in the workspace (ward_apart_build), the one-merge-per-step loop with ward_update_apart_kernel + ward_apart_commit_kernel in place of
+// ward_update_exact_kernel.  The constraint arrays are host memory in both forms.
+extern "C" int icl_cluster_apart_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                     int32_t k_target, const int32_t *apart_class, int64_t n_pairs, const int32_t *apart_pairs, int32_t *cluster_id,
+                                     int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
+{
+    return no_throw(ctx, "icl_cluster_apart_dev", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_apart_dev", d_C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    ICL_TRY(apart_check_args(ctx, "icl_cluster_apart_dev", m, apart_class, n_pairs, apart_pairs));
+    ward_apart ap{apart_class, apart_pairs, n_pairs, nullptr, 0};
+    return seeded_call_dev(ctx, "icl_cluster_apart", d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, &ap);
+    });
+}
+
+extern "C" int icl_cluster_apart(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                 int32_t k_target, const int32_t *apart_class, int64_t n_pairs, const int32_t *apart_pairs, int32_t *cluster_id,
+                                 int32_t *seed_rank, int32_t *n_clusters, float *C_out)
+{
+    return no_throw(ctx, "icl_cluster_apart", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_apart", C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    ICL_TRY(apart_check_args(ctx, "icl_cluster_apart", m, apart_class, n_pairs, apart_pairs));
+    ward_apart ap{apart_class, apart_pairs, n_pairs, nullptr, 0};
+    return seeded_call_host(ctx, "icl_cluster_apart", C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, C_out, &ap);
     });
 }
 
@@ -6037,3 +6005,63 @@ __global__ __launch_bounds__(256) void ward_seed_cout_kernel(const int32_t *__re
     }
     for (int k = threadIdx.x; k < d; k += blockDim.x) out[i * d + k] = row ? row[k] : 0.0f;
 }
+
+// ---- the constrained call's kernels (icl_cluster_apart; ward_update_apart_kernel's comment says how the loop keeps the relation) ----------------
+// Build, classes: one workgroup per seed row i of a non-zero class; bit j is set for every other seed j of the class, 64 columns per wave and pass
+// (a ballot is the two words).  Runs on the zeroed table, in front of the pairs: plain stores, rows of class 0 stay zero.
+__global__ __launch_bounds__(256) void ward_apart_class_kernel(int64_t n, int64_t aw, const int32_t *__restrict__ cls, uint32_t *__restrict__ abits)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int32_t ci = cls[i];
+        if (ci == 0) continue;
+        for (int64_t j0 = (int64_t)(threadIdx.x - lane); j0 < n; j0 += blockDim.x) { // j0: the wave's first column, a multiple of 64
+            const int64_t j = j0 + lane;
+            const unsigned long long bal = __ballot(j < n && j != i && cls[j] == ci);
+            const int64_t wq = (j0 >> 5) + lane; // lanes 0 and 1 store the two words
+            if (lane < 2 && wq < aw) abits[i * aw + wq] = (uint32_t)(bal >> (32 * lane));
+        }
+    }
+}
+
+// Build, pairs: one thread per pair (i, j), either order, duplicates allowed: both bits by integer atomicOr, whose result no order changes.
+__global__ __launch_bounds__(256) void ward_apart_pairs_kernel(int64_t npairs, int64_t aw, const int32_t *__restrict__ pairs, uint32_t *__restrict__ abits)
+{
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = pairs[2 * q], j = pairs[2 * q + 1]; // (in [0, n) and different: ab_bad_arg)
+        atomicOr(&abits[i * aw + (j >> 5)], 1u << (j & 31));
+        atomicOr(&abits[j * aw + (i >> 5)], 1u << (i & 31));
+    }
+}
+
+// Mask: MaxFloat32 at (i, j), i > j, for every pair of the relation, into the filled rows of the seeds (seed j sits in column j).
+__global__ __launch_bounds__(256) void ward_apart_mask_kernel(int64_t n, int64_t aw, const uint32_t *__restrict__ abits, const int64_t *__restrict__ rowoff,
+                                                              float *__restrict__ Dtri)
+{
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        float *row = Dtri + rowoff[i];
+        for (int64_t wq = threadIdx.x; wq * 32 < i; wq += blockDim.x) {
+            uint32_t bits = abits[i * aw + wq];
+            while (bits) {
+                const int64_t j = wq * 32 + (__ffs((int)bits) - 1);
+                bits &= bits - 1;
+                if (j < i) row[j] = ICL_MAXF;
+            }
+        }
+    }
+}
+
+// Commit, between update(t) and finish(t+1): the cluster of merge t holds column ca and what its two parents refused, row(ca) |= row(cb).  The
+// state is the one the update kernel in front read (a step that has nothing to update has nothing to commit); column cb is never occupied again.
+__global__ __launch_bounds__(256) void ward_apart_commit_kernel(const ward_state *__restrict__ st, const int32_t *__restrict__ mcol, int64_t aw,
+                                                                uint32_t *__restrict__ abits)
+{
+    if (st->done || !st->cur_valid) return;
+    const int64_t ca = mcol[st->cur_c], cb = mcol[st->cur_b];
+    for (int64_t wq = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; wq < aw; wq += (int64_t)gridDim.x * blockDim.x) abits[ca * aw + wq] |= abits[cb * aw + wq];
+}
+
+// the update kernel under the relation: ward_update_exact_kernel's text a second time
+#define WU_APART 1
+#include "ward_update_exact_body.h"
+#undef WU_APART

@@ -79,7 +79,8 @@ def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int =
     """More images for a request that has been answered: newRequestImages = (paths, ids, labels_per_image, labelSet) with the
     labelSet of the request `state` came from (the combined rows must be as wide as the state's).  Only the new images are embedded
     and combined (createEmbeddings, workflow.go:149-185); they join the state as singletons and the loop goes on from the clusters
-    held (Clustering.add, .recluster) -> (state.as_map(), True), or (None, False) when the constraints cannot be met or a file cannot
+    held (Clustering.add, .recluster; a state with keep_apart constraints keeps them whatever its size: icl_cluster_many_apart up to
+    2 048 held clusters, icl_cluster_apart above) -> (state.as_map(), True), or (None, False) when the constraints cannot be met or a file cannot
     be read (workflow.go:162-181 fails the request; the state is as it was then).  With dedupe_threshold, a new image that duplicates a
     held image or an earlier new image under that threshold does not join (Clustering.add(skip_duplicates=)), and the result has a
     third entry, the list [(skipped id, partner id, value), ...] (empty where the call fails before the images are compared)."""

@@ -451,6 +451,26 @@ int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const
                        int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out);
 int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out);
+/* ONE constrained seeded problem on the large-N engine (DESIGN.md "Constrained seeded clustering, large N"): icl_cluster_many_apart's semantics
+ * for a single problem of m seeds with no cap on m other than memory.  The relation B starts from apart_class[m] (NULL: all 0; two different
+ * seeds of one non-zero class are apart) and the n_pairs pairs of apart_pairs (two seed indices each, either order, duplicates allowed; NULL
+ * with n_pairs 0), both host memory in both forms; a pair in B holds MaxFloat32 and is never picked; when a and b merge into c,
+ * B(c, x) = B(a, x) or B(b, x).  Everything else is icl_cluster_seeded's: selection order, values, ids, the log, k, the final list, the drop
+ * rule, C_out, and the loop ending early for want of pairs.  With no constraint the results equal icl_cluster_seeded's, and for m <= 2048
+ * icl_cluster_many_apart's, bit for bit.  The relation lives in the engine's workspace as m x ceil(m / 32) words over the matrix's column slots
+ * (1.25 GB at m = 100 000), built on the device from the two arrays.  The call runs the ONE-MERGE-PER-STEP exact loop only, whatever
+ * ICL_WARD_BATCH says.  Not covered: the batched loops, the distance bounds and FAST mode, group and replica contexts (ICL_ERR_UNSUPPORTED),
+ * icl_cluster_requests; the exact fill evaluates banned pairs too before they are masked.
+ * ICL_ERR_ARG, nothing written: icl_cluster_seeded's cases, a negative n_pairs, apart_pairs NULL with n_pairs above 0, a negative class, a
+ * pair index outside [0, m) or a pair (i, i).  Every other status is icl_cluster_seeded's; ICL_ERR_NOMEM also where the bit rows do not fit.
+ * The icl_last_* reports behave as after icl_cluster_seeded, icl_last_ward_mode gives ICL_ROWS_SINGLE_APART, and icl_ward_dump_pairs_dev
+ * refuses the workspace afterwards (ICL_ERR_UNSUPPORTED). */
+int icl_cluster_apart(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                      int32_t k_target, const int32_t *apart_class, int64_t n_pairs, const int32_t *apart_pairs, int32_t *cluster_id,
+                      int32_t *seed_rank, int32_t *n_clusters, float *C_out);
+int icl_cluster_apart_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                          int32_t k_target, const int32_t *apart_class, int64_t n_pairs, const int32_t *apart_pairs, int32_t *cluster_id,
+                          int32_t *seed_rank, int32_t *n_clusters, float *d_C_out);
 /* The id rule above for one problem, on the host (no GPU, no context): m seeds, their sizes (the sign is ignored), min_size and a merge
  * log of n_merges pairs -> cluster_id[m], seed_rank[m], n_clusters.  ICL_ERR_ARG for a size of 0 or a log that names a cluster that does
  * not exist (any more); nothing is written then. */
@@ -795,7 +815,8 @@ int icl_last_ward_stats(icl_ctx *ctx, int64_t *merges, int64_t *steps, int64_t *
 enum { ICL_ROWS_SINGLE = 0,      /* one merge per step, exact rows (ward_update_exact_kernel) */
        ICL_ROWS_EXACT_BATCH = 1, /* batched, exact rows: 3 D unfused operations per entry (ward_update_batch2_kernel) */
        ICL_ROWS_LW_BOUND = 2,    /* batched, Lance-Williams lower bounds + exact evaluation on demand (ward_update_lb_kernel) */
-       ICL_ROWS_LW_FAST = 3 };   /* ICL_UPDATE_LW: Lance-Williams values, not bit-identical (ward_update_batch_lw_kernel) */
+       ICL_ROWS_LW_FAST = 3,     /* ICL_UPDATE_LW: Lance-Williams values, not bit-identical (ward_update_batch_lw_kernel) */
+       ICL_ROWS_SINGLE_APART = 4 }; /* icl_cluster_apart: one merge per step, exact rows under a keep-apart relation (ward_update_apart_kernel) */
 int icl_last_ward_mode(icl_ctx *ctx, int32_t *row_mode, int32_t *init_bounds);
 /* Layout of the distance matrix of the last merge loop.  complete_rows = 1: one column per CREATION ID (row pitch 2 n + 4 floats, 8 n^2 bytes) and
  * every live row holds the pair (x, y) for every live y -- the bound-rows loop (ICL_ROWS_LW_BOUND) then reads two contiguous rows per merge instead
