@@ -603,7 +603,7 @@ class Context:
 
     def distance_bounds_check(self, E, kind=0):
         """Every pair's distance bound against its exact value (include/imageclust.h icl_distance_bounds_check_dev):
-        dict(below, above, unflagged, mean_gap, mean_val).  E: float32 [n][d] (host array or CUDA tensor)."""
+        dict(below, above, unflagged, mean_gap, mean_val, sum_gap, sum_val).  E: float32 [n][d] (host array or CUDA tensor)."""
         import numpy as np
         import torch
 
@@ -614,7 +614,7 @@ class Context:
         g, v = C.c_double(0), C.c_double(0)
         check(self.h, self.L.icl_distance_bounds_check_dev(self.h, C.c_void_p(t.data_ptr()), n, d, kind, C.byref(a), C.byref(b), C.byref(u), C.byref(g), C.byref(v)))
         pairs = n * (n - 1) / 2
-        return {"below": a.value, "above": b.value, "unflagged": u.value, "mean_gap": g.value / pairs, "mean_val": v.value / pairs}
+        return {"below": a.value, "above": b.value, "unflagged": u.value, "mean_gap": g.value / pairs, "mean_val": v.value / pairs, "sum_gap": g.value, "sum_val": v.value}
 
     def ward_dump_pairs(self, ids, d):
         """The working matrix of the last cluster() call for the pairs of the creation ids `ids` (include/imageclust.h icl_ward_dump_pairs_dev):

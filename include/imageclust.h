@@ -779,7 +779,8 @@ int64_t icl_last_merge_values(icl_ctx *ctx, float *vals, int64_t cap);
 /* MFMA distance tile alone (north_star K6): D~[i][j] = 0.5*(|e_i|^2+|e_j|^2-2 e_i.e_j), bf16x3 split operands,
  * fp32 accumulate; lower triangle incl. diagonal written, packed row-major with leading dimension ld.  An estimate that
  * comes out negative or -0 (rounding noise of near-duplicate rows) is stored as +0, a NaN stays a NaN: this is, entry for
- * entry, the matrix ICL_UPDATE_LW clusters. */
+ * entry, the matrix ICL_UPDATE_LW clusters.  d_D must be 16-byte aligned (rows are written with 16-byte stores when ld % 4 == 0);
+ * cells above the diagonal and in the pad columns n..ld are not written. */
 int icl_distance_mfma_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, float *d_D, int64_t ld);
 
 /* ---- synthetic inputs ---------------------------------------------------------------------- */
