@@ -348,6 +348,31 @@ func ResumeClustering(centroids [][]float32, sizes []int32, minSize, maxSize, kT
 	return ResumeClusteringApart(centroids, sizes, minSize, maxSize, kTarget, nil, nil)
 }
 
+// The update choice of ResumeClusteringUpdate: the exact pipeline (ResumeClustering), or FAST mode (ICL_UPDATE_LW).
+const (
+	UpdateExact = 0
+	UpdateLW    = 1
+)
+
+// ResumeClusteringUpdate is ResumeClustering with the update mode chosen: UpdateExact is ResumeClustering; UpdateLW resumes in FAST mode
+// (iclengine.ClusterSeededFast, icl_cluster_seeded_fast on the large-N engine whatever the number of clusters: the one-workgroup routes
+// have no FAST form).  A FAST run resumed from its clusters is not the uncut FAST run, and FAST mode takes no keep-apart constraints.
+func ResumeClusteringUpdate(centroids [][]float32, sizes []int32, minSize, maxSize, kTarget, update int) (iclengine.SeededResult, bool) {
+	if update != UpdateLW {
+		return ResumeClustering(centroids, sizes, minSize, maxSize, kTarget)
+	}
+	res, err := iclengine.ClusterSeededFast(iclengine.SeededProblem{Centroids: centroids, Sizes: sizes, MinSize: minSize, MaxSize: maxSize, KTarget: kTarget})
+	if err != nil {
+		log.Printf("Clustering engine error: %v", err)
+		return iclengine.SeededResult{}, false
+	}
+	if res.Status != 0 {
+		log.Printf("Seeded clustering failed with status %d: %s", res.Status, iclengine.LastError())
+		return res, false
+	}
+	return res, true
+}
+
 // ResumeClusteringApart is ResumeClustering with keep-apart constraints (iclengine.ClusterManyApart, icl_cluster_many_apart; above
 // iclengine.ManySeededMax clusters iclengine.ClusterApart, icl_cluster_apart on the large-N engine): apartPairs
 // lists cluster indices that must never share a cluster, apartClass (one int per cluster, 0: none) classes whose members must not --

@@ -268,7 +268,14 @@ const ManySeededMax = 2048
 // The result is ClusterManySeeded's for the same problem, bit for bit; the merge log comes from icl_last_merges.  The error is the call's
 // own; ICL_ERR_CONSTRAINT and ICL_ERR_UNSUPPORTED are the result's Status.
 func ClusterSeeded(pr SeededProblem) (SeededResult, error) {
-	return clusterSeeded(pr, nil)
+	return clusterSeeded(pr, nil, false)
+}
+
+// ClusterSeededFast runs the same problem in FAST mode (icl_cluster_seeded_fast: the matrix-core distance matrix scaled by the seeds'
+// item counts, Lance-Williams rows; any number of seeds).  Defined by its own restatement, not bit-comparable with ClusterSeeded; a run
+// cut and resumed is not the uncut run.  COut is MergeClusters' centroid along the call's own merge log.  No constrained form exists.
+func ClusterSeededFast(pr SeededProblem) (SeededResult, error) {
+	return clusterSeeded(pr, nil, true)
 }
 
 // ClusterApart runs ONE constrained seeded problem on the large-N engine (icl_cluster_apart: the one-merge-per-step exact loop of
@@ -278,11 +285,12 @@ func ClusterApart(pr ApartProblem) (SeededResult, error) {
 	if pr.ApartClass != nil && len(pr.ApartClass) != len(pr.Sizes) {
 		return SeededResult{}, fmt.Errorf("%d classes for %d seeds", len(pr.ApartClass), len(pr.Sizes))
 	}
-	return clusterSeeded(pr.SeededProblem, &pr)
+	return clusterSeeded(pr.SeededProblem, &pr, false)
 }
 
-// the body of both: apart is nil (icl_cluster_seeded) or holds the problem's constraints (icl_cluster_apart)
-func clusterSeeded(pr SeededProblem, apart *ApartProblem) (SeededResult, error) {
+// the body of the three: apart is nil (icl_cluster_seeded; icl_cluster_seeded_fast with fast) or holds the problem's constraints
+// (icl_cluster_apart, never with fast)
+func clusterSeeded(pr SeededProblem, apart *ApartProblem, fast bool) (SeededResult, error) {
 	raw, e := Ctx()
 	if e != nil {
 		return SeededResult{}, e
@@ -305,7 +313,11 @@ func clusterSeeded(pr SeededProblem, apart *ApartProblem) (SeededResult, error) 
 	var nc C.int32_t
 	i32 := func(p *int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(p)) }
 	var rc C.int
-	if apart == nil {
+	if apart == nil && fast {
+		rc = C.icl_cluster_seeded_fast((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
+			C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cid[0]), i32(&rank[0]), &nc,
+			(*C.float)(unsafe.Pointer(&cout[0])))
+	} else if apart == nil {
 		rc = C.icl_cluster_seeded((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), C.int64_t(m), C.int32_t(d), i32(&ss[0]),
 			C.int32_t(pr.MinSize), C.int32_t(pr.MaxSize), C.int32_t(pr.KTarget), i32(&cid[0]), i32(&rank[0]), &nc,
 			(*C.float)(unsafe.Pointer(&cout[0])))

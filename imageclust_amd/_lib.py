@@ -145,6 +145,8 @@ SYMBOLS = [
     ("icl_cluster_many_apart_dev", _int, [_vp, _i32, _vp, _i64] + [_vp] * 17),
     ("icl_cluster_seeded", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
+    ("icl_cluster_seeded_fast", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
+    ("icl_cluster_seeded_fast_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_apart", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _pi32, _vp]),
     ("icl_cluster_apart_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _pi32, _vp]),
     ("icl_seeded_assign_ids", _int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _pi32]),
@@ -176,6 +178,7 @@ SYMBOLS = [
     ("icl_last_merges", _i64, [_vp, _vp, _i64]),
     ("icl_last_merge_values", _i64, [_vp, _vp, _i64]),
     ("icl_distance_mfma_dev", _int, [_vp, _vp, _i64, _i32, _vp, _i64]),
+    ("icl_distance_mfma_seeded_dev", _int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64]),
     ("icl_synth_images", _int, [C.c_uint64, _i64, _i64, _int, _vp]),
     ("icl_synth_images_dev", _int, [_vp, C.c_uint64, _i64, _i64, _int, _vp]),
     ("icl_prof_enable", _int, [_vp, _int]),
@@ -1397,11 +1400,24 @@ class Context:
         """icl_cluster_apart_dev on m x d device floats: cluster_seeded_dev with the constraints of cluster_apart (host arrays)."""
         return self.cluster_seeded_dev(d_C, m, d, seed_size, min_size, max_size, k_target, d_C_out, _apart=self._apart_args(m, apart_class, apart_pairs))
 
-    def cluster_seeded(self, C_, seed_size, min_size, max_size, k_target=0, want_centroids=True, dev=False, _apart=None):
+    def _seeded_fns(self, update, _apart):
+        """(host call, _dev call) of a seeded problem: icl_cluster_seeded, icl_cluster_seeded_fast for UPDATE_LW, icl_cluster_apart under constraints"""
+        if update not in (UPDATE_EXACT, UPDATE_LW):
+            raise ValueError("unknown update mode %r" % (update,))
+        if _apart:
+            if update == UPDATE_LW:
+                raise ICLError(ICL_ERR_UNSUPPORTED, "FAST mode (UPDATE_LW) keeps no keep-apart constraints")
+            return self.L.icl_cluster_apart, self.L.icl_cluster_apart_dev
+        if update == UPDATE_LW:
+            return self.L.icl_cluster_seeded_fast, self.L.icl_cluster_seeded_fast_dev
+        return self.L.icl_cluster_seeded, self.L.icl_cluster_seeded_dev
+
+    def cluster_seeded(self, C_, seed_size, min_size, max_size, k_target=0, want_centroids=True, dev=False, _apart=None, update=UPDATE_EXACT):
         """icl_cluster_seeded: ONE seeded problem (cluster_many_seeded's semantics) on the large-N engine, any number of seeds -> (cluster_id,
         seed_rank, n_clusters, status, merges, C_out); C_out is None without want_centroids.  status is ICL_OK, ICL_ERR_CONSTRAINT or
         ICL_ERR_UNSUPPORTED (rows of -1, C_out zero); every other error raises.  dev=True runs icl_cluster_seeded_dev on a device copy.
-        (_apart: cluster_apart's constraint arguments; the call is then icl_cluster_apart[_dev].)"""
+        update=UPDATE_LW: icl_cluster_seeded_fast[_dev], the same problem in FAST mode (MFMA matrix scaled by the sizes, Lance-Williams rows).
+        (_apart: cluster_apart's constraint arguments; the call is then icl_cluster_apart[_dev], exact only.)"""
         Cs = np.ascontiguousarray(C_, np.float32)
         m, d = Cs.shape
         ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
@@ -1411,8 +1427,7 @@ class Context:
         nc = _i32()
         co = np.zeros((m, d), np.float32) if want_centroids else None
         args = (m, d, _ptr(ss), int(min_size), int(max_size), int(k_target)) + (_apart[1] if _apart else ()) + (cid.ctypes.data, rank.ctypes.data, C.byref(nc))
-        fn_host = self.L.icl_cluster_apart if _apart else self.L.icl_cluster_seeded
-        fn_dev = self.L.icl_cluster_apart_dev if _apart else self.L.icl_cluster_seeded_dev
+        fn_host, fn_dev = self._seeded_fns(update, _apart)
         if dev:
             dE = self.malloc(max(Cs.nbytes, 16))
             dC = self.malloc(max(Cs.nbytes, 16)) if want_centroids else None
@@ -1432,13 +1447,13 @@ class Context:
         merges = self.last_merges() if rc == ICL_OK else np.zeros((0, 2), np.int32)
         return cid[:m], rank[:m], nc.value, rc, merges, co
 
-    def cluster_seeded_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, d_C_out=None, _apart=None):
+    def cluster_seeded_dev(self, d_C, m, d, seed_size, min_size, max_size, k_target=0, d_C_out=None, _apart=None, update=UPDATE_EXACT):
         """icl_cluster_seeded_dev on m x d device floats (d_C_out: m x d device floats, or None) -> (cluster_id, seed_rank, n_clusters,
-        status); the log is last_merges().  (_apart: as cluster_seeded's.)"""
+        status); the log is last_merges().  update=UPDATE_LW: icl_cluster_seeded_fast_dev.  (_apart: as cluster_seeded's.)"""
         ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
         cid, rank = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), -1, np.int32)
         nc = _i32()
-        fn = self.L.icl_cluster_apart_dev if _apart else self.L.icl_cluster_seeded_dev
+        fn = self._seeded_fns(update, _apart)[1]
         rc = fn(self.h, _vp(d_C), m, d, ss.ctypes.data if m else None, int(min_size), int(max_size), int(k_target), *(_apart[1] if _apart else ()),
                 cid.ctypes.data, rank.ctypes.data, C.byref(nc), _vp(d_C_out) if d_C_out is not None else None)
         if rc not in (ICL_OK, ICL_ERR_CONSTRAINT, ICL_ERR_UNSUPPORTED):
@@ -1502,6 +1517,29 @@ class Context:
             self.d2h(out, dD)
         finally:
             self.free(dE)
+            self.free(dD)
+        return np.tril(out)
+
+    def distance_mfma_seeded_dev(self, d_C, m, d, seed_size, d_D, ld=None):
+        """icl_distance_mfma_seeded_dev: the matrix icl_cluster_seeded_fast clusters -- distance_mfma's entries scaled by the two seeds' item
+        counts (seed_size: host, sign ignored) -- into m rows of pitch ld (default m) of device floats; lower triangle and zero diagonal."""
+        ss = np.ascontiguousarray(np.asarray(seed_size, np.int32).reshape(-1))
+        if len(ss) != m:
+            raise ValueError("%d seed sizes for %d rows" % (len(ss), m))
+        check(self.h, self.L.icl_distance_mfma_seeded_dev(self.h, _vp(d_C), m, d, ss.ctypes.data if m else None, _vp(d_D), m if ld is None else ld))
+
+    def distance_mfma_seeded(self, C_, seed_size):
+        """distance_mfma_seeded_dev on host rows -> m x m fp32, lower triangle incl. the zero diagonal."""
+        Cs = np.ascontiguousarray(C_, np.float32)
+        m, d = Cs.shape
+        dC, dD = self.malloc(max(Cs.nbytes, 16)), self.malloc(max(m * m * 4, 16))
+        try:
+            self.h2d(dC, Cs)
+            self.distance_mfma_seeded_dev(dC, m, d, seed_size, dD)
+            out = np.zeros((m, m), np.float32)
+            self.d2h(out, dD)
+        finally:
+            self.free(dC)
             self.free(dD)
         return np.tril(out)
 

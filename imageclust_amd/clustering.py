@@ -166,11 +166,16 @@ def _constrained(apart_class, apart_pairs) -> bool:
     return (apart_class is not None and bool(np.asarray(apart_class).any())) or (apart_pairs is not None and len(apart_pairs) > 0)
 
 
-def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class=None, apart_pairs=None):
+def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class=None, apart_pairs=None, update: int = _lib.UPDATE_EXACT):
     """One seeded problem -> (cluster_id, seed_rank, n_clusters, status, merges, C_out): icl_cluster_many_seeded up to its cap,
     icl_cluster_seeded (ward.hip's exact pipeline, no cap) above.  With a keep-apart constraint: icl_cluster_many_apart up to the same
     cap, icl_cluster_apart (ward.hip's one-merge-per-step exact loop, no cap) above -- ICLError(ICL_ERR_UNSUPPORTED) where the handle
-    has no such call.  An unconstrained problem never takes a constrained call, whatever the two cost."""
+    has no such call.  An unconstrained problem never takes a constrained call, whatever the two cost.  update=UPDATE_LW (FAST mode):
+    icl_cluster_seeded_fast at every seed count -- ward_many.hip has no FAST route --, and a constraint raises ICLError(ICL_ERR_UNSUPPORTED)."""
+    if update == _lib.UPDATE_LW:
+        if _constrained(apart_class, apart_pairs):
+            raise _lib.ICLError(_lib.ICL_ERR_UNSUPPORTED, "FAST mode (UPDATE_LW) keeps no keep-apart constraints")
+        return ctx.cluster_seeded(C, sizes, minSize, maxSize, k_target, want_centroids=True, update=_lib.UPDATE_LW)
     if _constrained(apart_class, apart_pairs):
         if len(sizes) > MANY_SEEDED_MAX:
             large = getattr(ctx, "cluster_apart", None)
@@ -185,7 +190,7 @@ def _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class=None, ap
 
 
 def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_target: int = 0, ctx: Optional[_lib.Context] = None,
-                            apart_pairs=None, apart_class=None):
+                            apart_pairs=None, apart_class=None, update: int = _lib.UPDATE_EXACT):
     """The loop of clustering.go:216-246 started from existing clusters (icl_cluster_many_seeded, one problem; icl_cluster_seeded above
     2 048 seeds): centroids[i] and
     sizes[i] describe seed cluster i, a negative size a frozen one that is never merged; k_target > 0 is the number of clusters to stop
@@ -193,12 +198,13 @@ def PerformClusteringSeeded(centroids, sizes, minSize: int, maxSize: int, k_targ
     granularity -- C_out[i] is the centroid of the final cluster whose first seed is i, zero for every other seed -- or (None, False)
     on impossible constraints.  apart_pairs ((i, j) seed indices) and apart_class (one int per seed, 0: none; the seeds of one non-zero
     class) name seeds that must never share a cluster (icl_cluster_many_apart: a merged cluster inherits the bans of both parents;
-    icl_cluster_apart above 2 048 seeds); the loop may then end before k clusters are reached."""
+    icl_cluster_apart above 2 048 seeds); the loop may then end before k clusters are reached.  update=UPDATE_LW runs the problem in
+    FAST mode (icl_cluster_seeded_fast, any seed count; DESIGN.md "Seeded clustering in FAST mode"): the default is the exact pipeline."""
     ctx = ctx or default_context()
     C = np.asarray(centroids, np.float32)
     if C.ndim != 2:
         C = C.reshape(len(sizes), -1)
-    cid, rank, nc, st, mg, co = _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs)
+    cid, rank, nc, st, mg, co = _seeded_call(ctx, C, sizes, minSize, maxSize, k_target, apart_class, apart_pairs, update)
     if st == _lib.ICL_ERR_CONSTRAINT:
         return None, False
     if st != _lib.ICL_OK:
@@ -339,11 +345,15 @@ class Clustering:
     status, merges, C_out), called with two more arguments, (..., apart_class, apart_pairs), only when a constraint exists; `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
     `fit_engine` for fit(), representatives() and misfits(): fit_engine(Q, cluster_of, C, k_alt, q_size, c_size, max_size) -> the dict of
     Context.cluster_fit; `between_engine` and `pairs_engine` for duplicates_of() and add(skip_duplicates=): between_engine(Q, L, threshold)
-    and pairs_engine(E, threshold) -> (row_ptr, col, val), as Context.pairs_between and Context.pairs_within."""
+    and pairs_engine(E, threshold) -> (row_ptr, col, val), as Context.pairs_between and Context.pairs_within.
+
+    update=UPDATE_LW keeps the state in FAST mode: every recluster() is icl_cluster_seeded_fast, whatever the number of clusters held, and a
+    state with keep_apart constraints raises ICLError(ICL_ERR_UNSUPPORTED) there.  A FAST state cut and resumed is not the uncut FAST run."""
 
     def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None, fit_engine=None,
-                 between_engine=None, pairs_engine=None):
+                 between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT):
         self.minSize, self.maxSize = int(minSize), int(maxSize)
+        self.update = int(update)
         self.ctx, self.engine, self.nearest_engine, self.fit_engine = ctx, engine, nearest_engine, fit_engine
         self.between_engine, self.pairs_engine = between_engine, pairs_engine
         self.clusters: List[HeldCluster] = []
@@ -354,10 +364,10 @@ class Clustering:
 
     @classmethod
     def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None,
-              fit_engine=None, between_engine=None, pairs_engine=None) -> "Clustering":
+              fit_engine=None, between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT) -> "Clustering":
         """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
         False (and every image is still a singleton) when the constraints cannot be met."""
-        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine)
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine, update)
         state.add(embeddings, ids)
         state.recluster()
         return state
@@ -511,11 +521,13 @@ class Clustering:
         C, ss = self.seeds()
         pairs = np.array(self._apart_pairs(), np.int32).reshape(-1, 2)
         extra = (_anchor, pairs) if _constrained(_anchor, pairs) else ()
+        if extra and self.update == _lib.UPDATE_LW:
+            raise _lib.ICLError(_lib.ICL_ERR_UNSUPPORTED, "FAST mode (UPDATE_LW) keeps no keep-apart constraints")
         if self.engine is not None:
             cid, rank, nc, st, mg, co = self.engine(C, ss, self.minSize, self.maxSize, k_target, *extra)
         else:
             ctx = self.ctx or default_context()
-            cid, rank, nc, st, mg, co = _seeded_call(ctx, C, ss, self.minSize, self.maxSize, k_target, *extra)
+            cid, rank, nc, st, mg, co = _seeded_call(ctx, C, ss, self.minSize, self.maxSize, k_target, *extra, update=self.update)
         self.ok = st == _lib.ICL_OK
         if st == _lib.ICL_ERR_CONSTRAINT:
             return False

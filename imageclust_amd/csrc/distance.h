@@ -9,6 +9,9 @@
 // D~ of every pair into the packed lower triangle (d_rowoff) or, with d_rowoff null, into dense rows of pitch ld.  Scratch is allocated
 // per call and released after the stream drains.
 int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float *d_out, const int64_t *d_rowoff, int64_t ld);
+// The same for m clusters of d_items[i] >= 1 items (device) with centroid rows d_C: WardDistance's scaling of 2 D~ by the two item counts, clamped
+// (the sized tile: FAST mode from seeds).  Same layouts, scratch and synchronisation.
+int icl_dist_mfma_sized_launch(icl_ctx *ctx, const float *d_C, int64_t m, int d, const int32_t *d_items, float *d_out, const int64_t *d_rowoff, int64_t ld);
 // Centred copy Ec [n][K] and computed norms of E (caller-owned), enqueued on strm.  d_colsum: icl_dist_colsum_doubles(d) doubles -- the
 // column sums, then the fixed-order partial sums they are made of.
 int icl_dist_center_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, int K, double *d_colsum, float *d_Ec, float *d_nrm, hipStream_t strm);

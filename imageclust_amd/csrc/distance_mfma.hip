@@ -176,8 +176,12 @@ static size_t dist_lds_bytes()
     return std::max(stages, ep);
 }
 
-// Shared by icl_distance_mfma_dev and the LW clustering mode (ward.hip).  Scratch: A', B', norms, the zero page.
-int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float *d_out, const int64_t *d_rowoff, int64_t ld)
+// (the sized tile, at the end of this file)
+static void dist_sized_enqueue(icl_ctx *ctx, const dist_args &a, const int32_t *d_items, unsigned nblocks);
+
+// Shared by icl_distance_mfma_dev and the LW clustering mode (ward.hip).  Scratch: A', B', norms, the zero page.  d_items (may be null): the
+// rows are clusters of that many items and the sized tile runs (icl_dist_mfma_sized_launch).
+static int dist_mfma_run(icl_ctx *ctx, const float *d_E, int64_t n, int d, const int32_t *d_items, float *d_out, const int64_t *d_rowoff, int64_t ld)
 {
     if (n <= 0) return ICL_OK;
     const int dp = (d + 63) / 64 * 64;
@@ -201,7 +205,9 @@ int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float
     {
         const double pairs = (double)n * (double)(n + 1) * 0.5;
         icl_prof_scope ps(ctx, ICL_K_DIST_MFMA, 2.0 * pairs * d, 4.0 * pairs + 4.0 * (double)n * d);
-        if (d_rowoff)
+        if (d_items)
+            dist_sized_enqueue(ctx, a, d_items, (unsigned)nblocks);
+        else if (d_rowoff)
             hipLaunchKernelGGL(dist_mfma_kernel<0>, dim3((unsigned)nblocks), dim3(256), dist_lds_bytes(), ctx->stream, a);
         else
             hipLaunchKernelGGL(dist_mfma_kernel<1>, dim3((unsigned)nblocks), dim3(256), dist_lds_bytes(), ctx->stream, a);
@@ -210,6 +216,14 @@ int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float
     ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     icl_prof_collect(ctx);
     return ICL_OK;
+}
+int icl_dist_mfma_launch(icl_ctx *ctx, const float *d_E, int64_t n, int d, float *d_out, const int64_t *d_rowoff, int64_t ld)
+{
+    return dist_mfma_run(ctx, d_E, n, d, nullptr, d_out, d_rowoff, ld);
+}
+int icl_dist_mfma_sized_launch(icl_ctx *ctx, const float *d_C, int64_t m, int d, const int32_t *d_items, float *d_out, const int64_t *d_rowoff, int64_t ld)
+{
+    return dist_mfma_run(ctx, d_C, m, d, d_items, d_out, d_rowoff, ld);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -374,4 +388,106 @@ extern "C" int icl_distance_mfma_dev(icl_ctx *ctx, const float *d_E, int64_t n, 
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
     return icl_dist_mfma_launch(ctx, d_E, n, d, d_D, nullptr, ld);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The SIZED tile (FAST mode from seeds: icl_cluster_seeded_fast, icl_distance_mfma_seeded_dev).  Row i is a cluster of items[i] >= 1 items
+// with centroid E[i]; the entry of i > j is WardDistance's scaling (ward_value.h, ward_scale: fl(f32(s_i s_j) / f32(s_i + s_j)) on the real
+// item counts) of the squared distance 2 D~(i, j), D~ the entry dist_mfma_kernel stores for the same two rows:
+//     V0(i, j) = clamp0( fl( ward_scale(s_i, s_j) * fl(2 * D~(i, j)) ) ).
+// The scale is positive, so the clamp commutes with it; with s_i = s_j = 1 the entry is D~(i, j) itself (num / den = 1/2 and the factor 2 are
+// exact below 2^127).  Same split operands, GEMM tile and store geometry as dist_mfma_kernel; defined behind every other kernel of the unit.
+// ------------------------------------------------------------------------------------------------------------
+// D~'s entry, the expression of dist_mfma_kernel's lambda under the unit's own contraction rule (in front of ward_value.h's pragma)
+__device__ __forceinline__ float dist_mfma_entry(float ni, float nj, float c)
+{
+    const float v = 0.5f * (ni + nj) - c;
+    return v > 0.0f ? v : (v == v ? 0.0f : v);
+}
+#include "ward_value.h"
+
+struct dist_sized_args {
+    dist_args g;          // operands, norms, output and its layout: dist_mfma_kernel's
+    const int32_t *items; // [n] item counts, >= 1
+};
+
+// dist_store_rows with the two rows' item counts beside their norms (MODE: as there)
+template <int MODE>
+__device__ __forceinline__ void dist_store_rows_sized(const unsigned char *smem, const float *nrm, const int32_t *items, int64_t n, int64_t i0, int64_t j0,
+                                                      float *out, const int64_t *rowoff, int64_t ld)
+{
+    const float *ep = reinterpret_cast<const float *>(smem);
+    const int tid = threadIdx.x, nl = (tid & 31) * 4;
+    float nj[4];
+    int sj[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const bool in = (j0 + nl + q) < n;
+        nj[q] = in ? nrm[j0 + nl + q] : 0.0f;
+        sj[q] = in ? items[j0 + nl + q] : 1;
+    }
+    for (int ml = tid >> 5; ml < CV_BM; ml += 8) {
+        const int64_t i = i0 + ml;
+        if (i >= n) break;
+        const float ni = nrm[i];
+        const int si = items[i];
+        const float4 t = *reinterpret_cast<const float4 *>(ep + ml * DG_EP_LD + nl);
+        const float c[4] = {t.x, t.y, t.z, t.w};
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float w = ward_scale(2.0f * dist_mfma_entry(ni, nj[q], c[q]), si, sj[q]);
+            v[q] = w > 0.0f ? w : (w == w ? 0.0f : w);
+        }
+        const int64_t jb = j0 + nl;
+        const int64_t lim = MODE == 0 ? i : i + 1; // columns j < lim are written
+        float *row = MODE == 0 ? out + rowoff[i] : out + i * ld;
+        if (jb + 3 < i && ((MODE == 0) || ((ld & 3) == 0))) { // strictly below the diagonal: one 16-byte store
+            *reinterpret_cast<float4 *>(row + jb) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (jb + q < lim) row[jb + q] = (MODE == 1 && jb + q == i) ? 0.0f : v[q];
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void dist_mfma_sized_kernel(const dist_sized_args p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int ti, tj;
+    tri_decode32(blockIdx.x, ti, tj);
+    const int64_t i0 = (int64_t)ti * CV_BM, j0 = (int64_t)tj * DG_BN;
+    dist_gemm_tile<BF16>(p.g.A, p.g.B, p.g.n, p.g.K, p.g.zero, i0, j0, smem);
+    dist_store_rows_sized<MODE>(smem, p.g.norms, p.items, p.g.n, i0, j0, p.g.out, p.g.rowoff, p.g.ld);
+}
+
+static void dist_sized_enqueue(icl_ctx *ctx, const dist_args &a, const int32_t *d_items, unsigned nblocks)
+{
+    icl_lds_optin(ctx, (const void *)dist_mfma_sized_kernel<0>, (int)dist_lds_bytes());
+    icl_lds_optin(ctx, (const void *)dist_mfma_sized_kernel<1>, (int)dist_lds_bytes());
+    const dist_sized_args s{a, d_items};
+    if (a.rowoff)
+        hipLaunchKernelGGL(dist_mfma_sized_kernel<0>, dim3(nblocks), dim3(256), dist_lds_bytes(), ctx->stream, s);
+    else
+        hipLaunchKernelGGL(dist_mfma_sized_kernel<1>, dim3(nblocks), dim3(256), dist_lds_bytes(), ctx->stream, s);
+}
+
+extern "C" int icl_distance_mfma_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, float *d_D, int64_t ld)
+{
+    if (!ctx || m < 0 || d < 0 || ld < m || (m && (!d_C || !d_D || !seed_size))) return icl_fail(ctx, ICL_ERR_ARG, "icl_distance_mfma_seeded_dev: bad argument");
+    std::vector<int32_t> items((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t s = seed_size[i] < 0 ? -(int64_t)seed_size[i] : seed_size[i];
+        if (s < 1 || s >= ((int64_t)1 << 30)) // (two counts must add up inside an int: ward_scale)
+            return icl_fail(ctx, ICL_ERR_ARG, "icl_distance_mfma_seeded_dev: seed_size[%lld] is %d", (long long)i, seed_size[i]);
+        items[(size_t)i] = (int32_t)s;
+    }
+    if (!m) return ICL_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    icl_device_guard g(ctx->device);
+    dev_guard g_items;
+    ICL_TRY(icl_dev_upload(ctx, g_items, items.data(), (size_t)m * 4, "icl_distance_mfma_seeded_dev: item counts"));
+    return icl_dist_mfma_sized_launch(ctx, d_C, m, d, g_items.as<int32_t>(), d_D, nullptr, ld); // (synchronised: items may go)
 }

@@ -1453,6 +1453,15 @@ __global__ void ward_update_apart_kernel(int d, int dqp, int64_t S, float *__res
                                          const int32_t *__restrict__ mcid, float *__restrict__ Dtri, ward_state *__restrict__ st, int max_size, int64_t n,
                                          float *__restrict__ rowmin, int32_t *__restrict__ rownn_w, const wrefine rf, uint32_t *__restrict__ abits, int64_t aw);
 __global__ void ward_apart_commit_kernel(const ward_state *__restrict__ st, const int32_t *__restrict__ mcol, int64_t aw, uint32_t *__restrict__ abits);
+// C_out of a seeded FAST call (icl_cluster_seeded_fast): likewise, behind the constrained ones.  One merge of the log as ward_fast_cout_kernel reads it:
+// parents a, b and the cluster c they make (creation ids), the item counts of a, b and c as floats
+struct wfc_merge {
+    int32_t a, b, c;
+    float fa, fb, fs;
+};
+__global__ void ward_fast_cout_kernel(const wfc_merge *__restrict__ mg, const float *C, float *scr, int64_t m, int d);
+__global__ void ward_fast_gather_kernel(const int32_t *__restrict__ src, const float *__restrict__ C, const float *__restrict__ scr, int64_t m, int d,
+                                        float *__restrict__ out);
 
 // Centroid store used by the update kernel: CT4[g][slot][4] = centroid(slot)[4g .. 4g+3]  (k-groups of 4 are
 // contiguous per slot, slots contiguous per group): one dwordx4 per lane streams 4 consecutive k of the lane's slot
@@ -4635,18 +4644,21 @@ struct ward_call {
     ev_guard e0, e1, e2, ev[2]; // call start, distance stage enqueued, merge loop enqueued; the batched loop's two state snapshots ...
     pin_guard pin;              // ... and their pinned memory
     dev_guard ec, pq;           // distance bounds: the centred copy of E, the integer GEMM's scratch
-    dev_guard eff;              // a seeded call's effective sizes (ward_seed::d_eff)
+    dev_guard eff, items;       // a seeded call's effective sizes (ward_seed::d_eff) and, in FAST mode, its item counts (ward_seed::d_items)
     dev_guard acls, apairs;     // a constrained call's class array and pair list (ward_apart), until the bit table is built from them
 };
 
 constexpr int GRAPH_STEPS = 64;
 // A SEEDED call (icl_cluster_seeded, DESIGN.md "Seeded clustering"): the n rows are seed clusters with sizes of their own.  The kernels see
 // EFFECTIVE sizes -- the seed's items, or max_size for a frozen seed, the largest size the ban still refuses with every partner --, the host
-// keeps the real ones for the final list.  Such a call runs the exact fill and the exact rows only: the bounds are proven for singletons.
+// keeps the real ones for the final list.  Such a call runs the exact fill and the exact rows -- the bounds are proven for singletons --, or, in
+// FAST mode (icl_cluster_seeded_fast), the sized MFMA tile on the REAL item counts and the Lance-Williams loops on the effective sizes.
 struct ward_seed {
     const int32_t *h_eff; // [n] effective sizes (ward_seed_admit)
     int64_t T;            // merges asked for: max(0, n - k), k from k_target or CalculateOptimalClusters(items)
     const int32_t *d_eff; // ... on the device: ward_run_stages' copy (ward_call::eff)
+    const int32_t *h_items = nullptr; // FAST mode: [n] the seeds' item counts, |seed_size| ...
+    const int32_t *d_items = nullptr; // ... and ward_run_stages' copy (ward_call::items)
 };
 // A CONSTRAINED seeded call (icl_cluster_apart, DESIGN.md "Constrained seeded clustering, large N"): a keep-apart relation over the seeds that
 // merged clusters inherit, as arguments ab_bad_arg accepted.  Such a call runs the one-merge-per-step exact loop only, whatever ICL_WARD_BATCH says:
@@ -4712,12 +4724,14 @@ static int ward_make_plan(icl_ctx *ctx, int64_t n, int32_t d, int32_t min_size, 
     if (own_lo < 0 || own_lo > own_hi || own_hi > n || own_lo % DT_TILE || (own_hi % DT_TILE && own_hi != n))
         return icl_fail(ctx, ICL_ERR_ARG, "own rows [%lld, %lld) must be whole 128-row tile rows of [0, %lld)", (long long)own_lo, (long long)own_hi, (long long)n);
     if (p.lw && (own_lo != 0 || own_hi != n)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "FAST mode builds the whole distance matrix on one GPU");
+    if (p.lw && apart) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "FAST mode keeps no keep-apart relation");
     p.own_lo = own_lo, p.own_hi = own_hi;
     p.pk_bits = max_size >= 1 ? 32 - __builtin_clz((unsigned)max_size) : 32;
     p.mpk = (!p.lw && p.pk_bits < 32 && (uint64_t)(2 * n + 4) <= (1ull << (32 - p.pk_bits))) ? w->mpk : nullptr;
     // Exact mode, the rows this call computes itself: by default PROVEN LOWER BOUNDS from the matrix cores, made exact on demand by the row scans (distance_mfma.hip
     // "Distance BOUNDS", scan_row_refine above); ctx->ward_dist == 1 (icl_set_ward_options) or shapes the bound does not cover: every value by ward_dist_exact_kernel.
-    // (a seeded call: exact values whatever the options, n and the workspace's layout say -- the bounds' proofs take num/den = 1/2 and the nrm table)
+    // (a seeded call: exact values whatever the options, n and the workspace's layout say -- the bounds' proofs take num/den = 1/2 and the nrm table;
+    // a seeded FAST call: the sized MFMA tile, values as in every FAST call)
     p.use_bound = !seed && !p.lw && own_hi > own_lo && ward_rows_use_bound(ctx, n, d);
     p.lbm = p.use_bound && p.mpk && ward_lb_rows(ctx, n, d);
     p.wide = p.lbm && w->wide_alloc;
@@ -4806,7 +4820,10 @@ static int ward_fill(icl_ctx *ctx, icl_ward_ws *w, const ward_plan &p, const flo
     wrefine rf{nullptr, nullptr, 0, 0, 0.0f, 0.0f, nullptr, 0.0f};
     bool have_rowub = false; // the bounds kernel has left every row's smallest upper bound (w->rowub)
     if (p.fill == WARD_FILL_FAST) {
-        ICL_TRY(icl_dist_mfma_launch(ctx, d_E, n, d, w->Dtri, w->rowoff, 0));
+        if (p.seed) // the seeds' real item counts scale the entries; the loop's masks see the effective sizes (ward_init_ws)
+            ICL_TRY(icl_dist_mfma_sized_launch(ctx, d_E, n, d, p.seed->d_items, w->Dtri, w->rowoff, 0));
+        else
+            ICL_TRY(icl_dist_mfma_launch(ctx, d_E, n, d, w->Dtri, w->rowoff, 0));
     } else if (p.use_bound) {
         ICL_TRY(icl_dev_alloc(ctx, c.ec, (size_t)n * ward_bound_K(d) * 4, "centred copy of E (%lld x %d floats)", (long long)n, ward_bound_K(d)));
         ward_centred b{w->colsum, (float *)c.ec.p, w->nrm, w->zero};
@@ -5217,8 +5234,10 @@ static int ward_run_stages(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d,
     if (apart) ICL_TRY(ward_apart_build(ctx, w, n, apart, c));
     if (seed) {
         ICL_TRY(icl_dev_upload(ctx, c.eff, seed->h_eff, (size_t)n * 4, "icl_cluster_seeded: seed sizes"));
-        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_eff is the caller's to free once this returns, whatever it returns)
+        if (seed->h_items) ICL_TRY(icl_dev_upload(ctx, c.items, seed->h_items, (size_t)n * 4, "icl_cluster_seeded_fast: item counts"));
+        ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_eff and h_items are the caller's to free once this returns, whatever it returns)
         seed->d_eff = (const int32_t *)c.eff.p;
+        seed->d_items = (const int32_t *)c.items.p;
     }
     ward_plan p;
     ICL_TRY(ward_make_plan(ctx, n, d, min_size, max_size, update, own_lo, own_hi, &p, seed, apart));
@@ -5259,16 +5278,65 @@ static int cluster_locked(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, 
 // final list from the seeds' real sizes.  d_C: the seed centroids on the device; seed_size on the host (no entry 0: checked by the entry points);
 // d_C_out: device, or null.  A problem the call refuses (ICL_ERR_UNSUPPORTED / ICL_ERR_CONSTRAINT) gets rows of -1 and a C_out of zeros, as the many-call's.
 // apart (may be null): the keep-apart relation of icl_cluster_apart[_dev] -- arguments that ab_bad_arg accepted --, `what` the entry point's name.
+// C_out of a seeded FAST call.  The Lance-Williams loops keep no centroids, so the centroid of every merged cluster is evaluated here, along the
+// call's own log (pairs of creation ids, seeds 0 .. m - 1, merge t makes m + t) with the seeds' real item counts: MergeClusters' expression per
+// element, what the exact call would hold had it made the same merges.  A merge's level is 1 + the larger of its parents' levels (seeds: 0); one
+// launch per level into a scratch of (merges) x d floats, then the gather by src (ward_fast_gather_kernel).  Each element is one fixed expression
+// tree, so the schedule changes no bit.
+static int ward_fast_cout(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, const std::vector<int32_t> &log,
+                          const std::vector<int32_t> &src, float *d_C_out)
+{
+    const int64_t T = (int64_t)log.size() / 2;
+    std::vector<int64_t> items((size_t)(m + T));
+    std::vector<int32_t> level((size_t)(m + T), 0);
+    for (int64_t i = 0; i < m; ++i) items[(size_t)i] = std::llabs((long long)seed_size[i]);
+    int32_t top = 0;
+    for (int64_t t = 0; t < T; ++t) { // (a log ward_final_list has accepted: every id exists)
+        const int32_t a = log[(size_t)(2 * t)], b = log[(size_t)(2 * t + 1)];
+        items[(size_t)(m + t)] = items[(size_t)a] + items[(size_t)b];
+        level[(size_t)(m + t)] = 1 + std::max(level[(size_t)a], level[(size_t)b]);
+        top = std::max(top, level[(size_t)(m + t)]);
+    }
+    std::vector<int64_t> first((size_t)top + 2, 0); // first[L]: where level L's merges start in the sorted list
+    for (int64_t t = 0; t < T; ++t) ++first[(size_t)level[(size_t)(m + t)] + 1];
+    for (int32_t L = 1; L <= top + 1; ++L) first[(size_t)L] += first[(size_t)L - 1];
+    std::vector<wfc_merge> mg((size_t)T);
+    std::vector<int64_t> at(first.begin(), first.end());
+    for (int64_t t = 0; t < T; ++t) {
+        const int32_t a = log[(size_t)(2 * t)], b = log[(size_t)(2 * t + 1)];
+        mg[(size_t)at[(size_t)level[(size_t)(m + t)]]++] =
+            wfc_merge{a, b, (int32_t)(m + t), (float)items[(size_t)a], (float)items[(size_t)b], (float)(items[(size_t)a] + items[(size_t)b])};
+    }
+    dev_guard g_src, g_mg, g_scr;
+    ICL_TRY(icl_dev_upload(ctx, g_src, src.data(), (size_t)m * 4, "icl_cluster_seeded_fast: C_out table"));
+    if (T) {
+        ICL_TRY(icl_dev_upload(ctx, g_mg, mg.data(), (size_t)T * sizeof(wfc_merge), "icl_cluster_seeded_fast: C_out merges"));
+        ICL_TRY(icl_dev_alloc(ctx, g_scr, (size_t)T * (size_t)d * 4, "icl_cluster_seeded_fast: centroids of %lld merges (x %d floats)", (long long)T, d));
+    }
+    const unsigned chunks = (unsigned)icl_ceil_div(d, 256);
+    for (int32_t L = 1; L <= top; ++L) {
+        const int64_t lo = first[(size_t)L], cnt = first[(size_t)L + 1] - lo;
+        if (cnt > 0)
+            hipLaunchKernelGGL(ward_fast_cout_kernel, dim3((unsigned)cnt, chunks), dim3(256), 0, ctx->stream, g_mg.as<wfc_merge>() + lo, d_C, g_scr.as<float>(), m, d);
+    }
+    hipLaunchKernelGGL(ward_fast_gather_kernel, dim3((unsigned)m), dim3(256), 0, ctx->stream, g_src.as<int32_t>(), d_C, g_scr.as<float>(), m, d, d_C_out);
+    ICL_HIP(ctx, hipGetLastError());
+    ICL_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (before the host arrays and the scratch go)
+    return ICL_OK;
+}
+
+// update: ICL_UPDATE_EXACT, or ICL_UPDATE_LW for icl_cluster_seeded_fast[_dev] (DESIGN.md "Seeded clustering in FAST mode"; no relation then).
 static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
                                  int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out, ward_apart *apart = nullptr,
-                                 const char *what = "icl_cluster_seeded")
+                                 const char *what = "icl_cluster_seeded", int update = ICL_UPDATE_EXACT)
 {
+    const bool lw = update == ICL_UPDATE_LW;
     ctx->last.merges.clear();
     ctx->last.merge_vals.clear();
     *n_clusters = 0;
     auto no_loop = [&] { // what the icl_last_* reports say of a call that ran no merge loop
         ctx->last.bound_viol = 0;
-        ctx->last.mode[0] = apart ? ICL_ROWS_SINGLE_APART : ward_batch_env() ? ICL_ROWS_EXACT_BATCH : ICL_ROWS_SINGLE;
+        ctx->last.mode[0] = apart ? ICL_ROWS_SINGLE_APART : !ward_batch_env() ? ICL_ROWS_SINGLE : lw ? ICL_ROWS_LW_FAST : ICL_ROWS_EXACT_BATCH;
         ctx->last.mode[1] = 0;
         ctx->last.stats[0] = ctx->last.stats[1] = ctx->last.stats[2] = ctx->last.stats[3] = 0;
         ctx->last.dist_ms = ctx->last.merge_ms = 0;
@@ -5289,8 +5357,13 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
         return icl_fail(ctx, refuse(ad.status), "%s%s%s", ad.status == ICL_ERR_CONSTRAINT ? "" : what, ad.status == ICL_ERR_CONSTRAINT ? "" : ": ", ad.why.c_str());
     icl_ward_ws *w = nullptr;
     if (m - ad.k > 0) {
-        ward_seed sd{eff.data(), m - ad.k, nullptr};
-        ICL_TRY(ward_run_stages(ctx, d_C, m, d, min_size, ad.kmax, ICL_UPDATE_EXACT, 0, -1, &sd, apart));
+        std::vector<int32_t> items;
+        if (lw) { // (below 2^30 in all: admitted)
+            items.resize((size_t)m);
+            for (int64_t i = 0; i < m; ++i) items[(size_t)i] = seed_size[i] < 0 ? -seed_size[i] : seed_size[i];
+        }
+        ward_seed sd{eff.data(), m - ad.k, nullptr, lw ? items.data() : nullptr};
+        ICL_TRY(ward_run_stages(ctx, d_C, m, d, min_size, ad.kmax, update, 0, -1, &sd, apart));
         w = ctx->ward;
     } else // nothing to merge: every seed is a final cluster
         no_loop();
@@ -5302,6 +5375,7 @@ static int cluster_seeded_locked(icl_ctx *ctx, const float *d_C, int64_t m, int3
     if (d_C_out && out_bytes) {
         std::vector<int32_t> src((size_t)m, -1);
         for (size_t f = 0; f < finals.size(); f += 2) src[(size_t)finals[f + 1]] = finals[f];
+        if (lw) return ward_fast_cout(ctx, d_C, m, d, seed_size, ctx->last.merges, src, d_C_out);
         dev_guard g_src;
         ICL_TRY(icl_dev_upload(ctx, g_src, src.data(), (size_t)m * 4, "icl_cluster_seeded: C_out table"));
         hipLaunchKernelGGL(ward_seed_cout_kernel, dim3((unsigned)m), dim3(256), 0, ctx->stream, (const int32_t *)g_src.p, d_C, w ? (const float *)w->Crow : nullptr,
@@ -5331,14 +5405,16 @@ static int apart_check_args(icl_ctx *ctx, const char *what, int64_t m, const int
 
 // The two forms of a seeded call behind their ARG checks -- centroids on the device, centroids in host memory --, with or without a relation.
 static int seeded_call_dev(icl_ctx *ctx, const char *what, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
-                           int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out, ward_apart *apart)
+                           int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out, ward_apart *apart,
+                           int update = ICL_UPDATE_EXACT)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
-    return cluster_seeded_locked(ctx, d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, apart, what);
+    return cluster_seeded_locked(ctx, d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, apart, what, update);
 }
 static int seeded_call_host(icl_ctx *ctx, const char *what, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
-                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out, ward_apart *apart)
+                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out, ward_apart *apart,
+                            int update = ICL_UPDATE_EXACT)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
     icl_device_guard g(ctx->device);
@@ -5347,7 +5423,7 @@ static int seeded_call_host(icl_ctx *ctx, const char *what, const float *C, int6
     ICL_TRY(icl_dev_alloc(ctx, dC, std::max<size_t>(bytes, 16), "%s: C (%lld x %d floats)", what, (long long)m, d));
     if (C_out) ICL_TRY(icl_dev_alloc(ctx, dO, std::max<size_t>(bytes, 16), "%s: C_out (%lld x %d floats)", what, (long long)m, d));
     if (bytes) ICL_HIP(ctx, hipMemcpyAsync(dC.p, C, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p, apart, what);
+    const int rc = cluster_seeded_locked(ctx, (const float *)dC.p, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, (float *)dO.p, apart, what, update);
     if (C_out && bytes && rc != ICL_ERR_HIP && rc != ICL_ERR_NOMEM) { // (a refused problem's rows are zero)
         ICL_HIP(ctx, hipMemcpyAsync(C_out, dO.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         ICL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -5370,6 +5446,29 @@ extern "C" int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32
     return no_throw(ctx, "icl_cluster_seeded", [&]() -> int {
     ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded", C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
     return seeded_call_host(ctx, "icl_cluster_seeded", C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, C_out, nullptr);
+    });
+}
+
+// ---- seeded clustering in FAST mode (icl_cluster_seeded_fast[_dev]; DESIGN.md "Seeded clustering in FAST mode") -----------------------------------
+// icl_cluster_seeded's arguments, admission and final list on the Lance-Williams loops: the sized MFMA tile for the initial matrix (ward_fill), the
+// loops of icl_cluster(update = ICL_UPDATE_LW) as they are on the effective sizes, C_out by ward_fast_cout.
+extern "C" int icl_cluster_seeded_fast_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                           int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out)
+{
+    return no_throw(ctx, "icl_cluster_seeded_fast_dev", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded_fast_dev", d_C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    return seeded_call_dev(ctx, "icl_cluster_seeded_fast", d_C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, d_C_out, nullptr,
+                           ICL_UPDATE_LW);
+    });
+}
+
+extern "C" int icl_cluster_seeded_fast(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                                       int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out)
+{
+    return no_throw(ctx, "icl_cluster_seeded_fast", [&]() -> int {
+    ICL_TRY(seeded_check_args(ctx, "icl_cluster_seeded_fast", C, m, d, seed_size, cluster_id, seed_rank, n_clusters));
+    return seeded_call_host(ctx, "icl_cluster_seeded_fast", C, m, d, seed_size, min_size, max_size, k_target, cluster_id, seed_rank, n_clusters, C_out, nullptr,
+                            ICL_UPDATE_LW);
     });
 }
 
@@ -6065,3 +6164,28 @@ __global__ __launch_bounds__(256) void ward_apart_commit_kernel(const ward_state
 #define WU_APART 1
 #include "ward_update_exact_body.h"
 #undef WU_APART
+
+// ---- C_out of a seeded FAST call (ward_fast_cout) ------------------------------------------------------------------------------------------
+// The merges of ONE dependency level of the log: workgroup (x, y) makes elements [256 y, 256 y + 256) of the centroid of merge mg[x] by
+// MergeClusters' expression (ward_merge_elem) from its parents' rows -- the input row C[id] of a seed (id < m), the scratch row scr[id - m] of a
+// cluster an earlier level made -- into scr[c - m].  Rows of one level are written by their own workgroups only and read by later launches.
+__global__ __launch_bounds__(256) void ward_fast_cout_kernel(const wfc_merge *__restrict__ mg, const float *C, float *scr, int64_t m, int d)
+{
+    const wfc_merge g = mg[blockIdx.x];
+    const int k = (int)blockIdx.y * 256 + (int)threadIdx.x;
+    if (k >= d) return;
+    const float *ra = g.a < m ? C + (int64_t)g.a * d : scr + ((int64_t)g.a - m) * d;
+    const float *rb = g.b < m ? C + (int64_t)g.b * d : scr + ((int64_t)g.b - m) * d;
+    scr[((int64_t)g.c - m) * d + k] = ward_merge_elem(g.fa, ra[k], g.fb, rb[k], g.fs);
+}
+
+// ward_seed_cout_kernel's gather over that scratch: src[i] = the creation id of the final cluster whose rank-0 seed is i (below m: the input row;
+// else the scratch row id - m), or -1: a row of zeros.  scr may be null when no id >= m occurs.
+__global__ __launch_bounds__(256) void ward_fast_gather_kernel(const int32_t *__restrict__ src, const float *__restrict__ C, const float *__restrict__ scr,
+                                                               int64_t m, int d, float *__restrict__ out)
+{
+    const int64_t i = blockIdx.x;
+    const int32_t c = src[i];
+    const float *row = c < 0 ? nullptr : c < m ? C + (int64_t)c * d : scr + ((int64_t)c - m) * d;
+    for (int k = threadIdx.x; k < d; k += blockDim.x) out[i * d + k] = row ? row[k] : 0.0f;
+}

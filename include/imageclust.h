@@ -451,6 +451,25 @@ int icl_cluster_seeded(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const
                        int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out);
 int icl_cluster_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *d_C_out);
+/* The seeded problem above in FAST mode (ICL_UPDATE_LW; DESIGN.md "Seeded clustering in FAST mode"): the same arguments, admission (N, k,
+ * frozen seeds, an unfrozen seed above max_size), creation ids, final list, drop rule and seed_rank, on the Lance-Williams loop of
+ * icl_cluster(update = ICL_UPDATE_LW).  The initial matrix comes from the matrix cores: entry (i, j), i > j, is
+ * clamp0(fl(fl(f32(|s_i| |s_j|) / f32(|s_i| + |s_j|)) * fl(2 D~(i, j)))) with D~ icl_distance_mfma_dev's matrix of the m centroid rows
+ * (icl_distance_mfma_seeded_dev is that matrix alone); selection, new rows, clamp and the NaN rule are FAST mode's, on the effective sizes (a
+ * frozen seed counts max_size).  The engine keeps no centroids in this mode: C_out (may be NULL) is MergeClusters' centroid evaluated along
+ * the call's own log with the real item counts -- what the exact call would hold had it made the same merges -- at the row of each final
+ * cluster's rank-0 seed; a never-merged seed keeps its input row, every other row is zero.  NOT an identity: a FAST run cut after t merges
+ * and resumed from its clusters rebuilds the matrix from centroids, where the uncut run carried Lance-Williams values forward; only the
+ * exact calls have the restart identity.  With every size 1 and no k_target the results equal icl_cluster(update = ICL_UPDATE_LW)'s, bit
+ * for bit.  Statuses, "nothing written on ICL_ERR_ARG", the rows of -1 and the zero C_out of a refused problem are icl_cluster_seeded's;
+ * ICL_ERR_UNSUPPORTED also on a replica of a group.  icl_last_merges, icl_last_merge_values and icl_last_ward_stats report the call,
+ * icl_last_ward_mode gives ICL_ROWS_LW_FAST (ICL_ROWS_SINGLE under ICL_WARD_BATCH=0), icl_ward_dump_pairs_dev refuses the workspace
+ * afterwards.  Not covered: keep-apart constraints, the ward_many routes and icl_cluster_requests, distance bounds, group contexts. */
+int icl_cluster_seeded_fast(icl_ctx *ctx, const float *C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size, int32_t max_size,
+                            int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters, float *C_out);
+int icl_cluster_seeded_fast_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, int32_t min_size,
+                                int32_t max_size, int32_t k_target, int32_t *cluster_id, int32_t *seed_rank, int32_t *n_clusters,
+                                float *d_C_out);
 /* ONE constrained seeded problem on the large-N engine (DESIGN.md "Constrained seeded clustering, large N"): icl_cluster_many_apart's semantics
  * for a single problem of m seeds with no cap on m other than memory.  The relation B starts from apart_class[m] (NULL: all 0; two different
  * seeds of one non-zero class are apart) and the n_pairs pairs of apart_pairs (two seed indices each, either order, duplicates allowed; NULL
@@ -782,6 +801,11 @@ int64_t icl_last_merge_values(icl_ctx *ctx, float *vals, int64_t cap);
  * entry, the matrix ICL_UPDATE_LW clusters.  d_D must be 16-byte aligned (rows are written with 16-byte stores when ld % 4 == 0);
  * cells above the diagonal and in the pad columns n..ld are not written. */
 int icl_distance_mfma_dev(icl_ctx *ctx, const float *d_E, int64_t n, int32_t d, float *d_D, int64_t ld);
+/* The same tile for m seed clusters of |seed_size[i]| items each (host memory, the sign is ignored): entry (i, j), i > j, is
+ * clamp0(fl(fl(f32(s_i s_j) / f32(s_i + s_j)) * fl(2 D~(i, j)))), D~ the entry icl_distance_mfma_dev gives for the same rows -- entry for
+ * entry the matrix icl_cluster_seeded_fast clusters; with every size 1 it is D~ itself.  Layout, diagonal (0), alignment and the cells that
+ * are not written are icl_distance_mfma_dev's.  ICL_ERR_ARG also for a size of 0 or of 2^30 items and more. */
+int icl_distance_mfma_seeded_dev(icl_ctx *ctx, const float *d_C, int64_t m, int32_t d, const int32_t *seed_size, float *d_D, int64_t ld);
 
 /* ---- synthetic inputs ---------------------------------------------------------------------- */
 /* Images first..first+n-1 of the seeded synthetic set, u8 HWC RGB 224x224x3. */
