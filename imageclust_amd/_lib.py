@@ -100,6 +100,9 @@ SYMBOLS = [
     ("icl_conv_stats", _int, [_vp, _vp, _vp]),
     ("icl_set_forward_prune", _int, [_vp, _int]),
     ("icl_forward_prune_stats", _int, [_vp, _vp]),
+    ("icl_set_forward_prune_fused", _int, [_vp, _int]),
+    ("icl_forward_prune_fused_stats", _int, [_vp, _vp]),
+    ("icl_bottleneck56_sub", _int, [_vp, _vp, _int, _int, _int] + [_vp] * 9 + [_int, _int, _vp]),
     ("icl_conv1x1_mapped", _int, [_vp, _vp, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _int, _vp]),
     ("icl_conv_split_launches", _int, [_vp, _vp]),
     ("icl_conv2d_fused", _int, [_vp, _int, _vp, _int, _int, _int, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp]),
@@ -677,6 +680,16 @@ class Context:
         check(self.h, self.L.icl_forward_prune_stats(self.h, C.byref(a)))
         return a.value
 
+    def set_forward_prune_fused(self, on=True):
+        """The same for stage 1's last block, which runs as one fused launch (icl_set_forward_prune_fused; only with set_forward_prune on)."""
+        check(self.h, self.L.icl_set_forward_prune_fused(self.h, 1 if on else 0))
+
+    def forward_prune_fused_stats(self):
+        """launches of the fused bottleneck's pruned instantiation by the forward pass since the context was created."""
+        a = C.c_int64(0)
+        check(self.h, self.L.icl_forward_prune_fused_stats(self.h, C.byref(a)))
+        return a.value
+
     def embed_u8(self, imgs, head=HEAD_POOLED, prec=PREC_FP32):
         imgs = np.ascontiguousarray(imgs, np.uint8).reshape(-1, IMG_BYTES)
         n = imgs.shape[0]
@@ -1007,6 +1020,19 @@ class Context:
         keep += [None, None, None] if wds is None else [f(wds), f(bnds[0]), f(bnds[1])]
         ptr = [None if a is None else a.ctypes.data for a in keep]
         check(self.h, self.L.icl_bottleneck56(self.h, ptr[0], B, H, W, Cin, *ptr[1:], y.ctypes.data))
+        return y
+
+    def bottleneck56_sub(self, x_nhwc, w1, bn1, w2_oihw, bn2, w3, bn3, sub, fill):
+        """bottleneck56's identity form with the launch's sub (1: whole, 2: the pruned instantiation, pixels (2 oy, 2 ox) only) on an output
+        tensor preset to the 16-bit pattern `fill`: what the launch does not write comes back as fill << 16 (fp32 bits)."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        x = f(x_nhwc)
+        B, H, W, Cin = x.shape
+        assert Cin == 256
+        y = np.empty((B, H, W, 256), np.float32)
+        keep = [x, f(w1), f(bn1[0]), f(bn1[1]), f(w2_oihw), f(bn2[0]), f(bn2[1]), f(w3), f(bn3[0]), f(bn3[1])]
+        ptr = [a.ctypes.data for a in keep]
+        check(self.h, self.L.icl_bottleneck56_sub(self.h, ptr[0], B, H, W, *ptr[1:], int(sub), int(fill), y.ctypes.data))
         return y
 
     def synth_images_dev(self, seed, first, n, mode, d_out):

@@ -300,6 +300,7 @@ struct fwd_opts {
     int fuse;        // ICL_FUSE mask: bit 0 stem + maxpool in one launch, bit 1 / 2 stage 1's identity / first bottleneck in one launch, bit 3 stem2_pool_kernel
     int prune;       // icl_set_forward_prune
     int stem_per_cu; // workgroups per CU of the stem kernel this precision and mask take
+    int prune_fused = 1; // icl_set_forward_prune_fused: with `prune` on, the rule also prunes a bottleneck that runs as ONE fused launch
 };
 
 enum fwd_kind { FWD_STEM2_POOL, FWD_STEM_POOL, FWD_STEM, FWD_MAXPOOL, FWD_BNECK56, FWD_CONV, FWD_AVGPOOL, FWD_FC };
@@ -310,6 +311,7 @@ struct fwd_step {
     int layer;     // record of the step's (first) convolution: whose weights it reads
     bool ds;       // FWD_BNECK56: the form with the downsample branch; FWD_CONV: the dual-operand c3 of a block 0 (fused weights, second operand x2)
     bool pruned;   // FWD_CONV: the launch that completes a pruned block (icl_forward_prune_stats)
+    int sub;       // FWD_BNECK56: 1, or 2 -- the pruned instantiation, which writes the pixels (2 oy, 2 ox) only (icl_forward_prune_fused_stats)
     conv_args a;   // FWD_CONV: shapes and relu; the pointers are the lane's and the model's, patched in when the step runs
     conv_choice c; // FWD_CONV
     int x, y, r, x2; // roles of the lane's buffers: input, output, residual, second operand (FWD_NONE: none)
@@ -407,6 +409,8 @@ static inline fwd_plan forward_make_plan(const icl_conv_rec *recs, int nconv, in
         if (bf16 && c1.stage == 1 && (o.fuse & (has_ds ? 4 : 2))) { // the whole bottleneck in one launch
             fwd_step &st = add(FWD_BNECK56, ci, x, y);
             st.ds = has_ds;
+            // dead pixels (the rule of the layer-by-layer path below, on the same records): the block after this one reads at stride 2 only
+            st.sub = (o.prune && o.prune_fused && !has_ds && blk + 1 != tap && cn + 3 < nconv && prune_stride(c2, c3, &recs[cn], &recs[cn + 3]) == 2) ? 2 : 1;
             int nstrips, ngroups;
             bneck56_grid(B, c2.hin, o.conv.ncu, &nstrips, &ngroups);
             st.blocks = (unsigned)(nstrips * ngroups);

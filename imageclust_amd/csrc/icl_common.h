@@ -181,6 +181,8 @@ struct icl_ctx {
     int64_t fit_stats[4] = {0, 0, 0, 0}; // last icl_cluster_fit[_dev]: splits used, tiles run, pairs evaluated, workspace bytes (icl_last_fit_stats)
     int64_t between_stats[5] = {0, 0, 0, 0, 0}; // last icl_pairs_between[_dev]: splits used, tiles run in the count pass, tiles with a hit, pairs evaluated, workspace bytes (icl_last_pairs_between_stats)
     std::vector<const void *> lds_optin; // kernels whose > 64 KiB dynamic-LDS opt-in has been made on this context's device
+    int fwd_prune_fused = 1;   // with fwd_prune: the fused stage-1 bottleneck in front of stage 2 runs as bneck56_kernel<false, 2> (icl_set_forward_prune_fused, ICL_PRUNE_FUSED=0)
+    int64_t pruned_fused = 0;  // launches of that instantiation by the forward pass (icl_forward_prune_fused_stats)
 };
 
 static inline hipStream_t icl_main_stream(const icl_ctx *ctx) { return ctx->stream; }

@@ -63,6 +63,7 @@ extern "C" int icl_create(int device, icl_ctx **out)
     if (const char *ew = getenv("ICL_CONV_WR")) c->conv_wr = atoi(ew) != 0;
     if (const char *es = getenv("ICL_CONV_SK")) c->conv_sk = atoi(es) != 0;
     if (const char *ep = getenv("ICL_PRUNE")) c->fwd_prune = atoi(ep) != 0; // A/B runs: the default of icl_set_forward_prune
+    if (const char *ef = getenv("ICL_PRUNE_FUSED")) c->fwd_prune_fused = atoi(ef) != 0; // A/B runs: the default of icl_set_forward_prune_fused
     if (const char *ek = getenv("ICL_CONV_SK_MINK")) c->conv_sk_min_k = std::max(512, atoi(ek));
     if (const char *e8 = getenv("ICL_CONV_P8")) { // A/B runs: the default of icl_set_conv_options
         const int v = atoi(e8);
@@ -206,6 +207,22 @@ extern "C" int icl_forward_prune_stats(icl_ctx *ctx, int64_t *pruned_blocks)
     if (!ctx || !pruned_blocks) return icl_fail(ctx, ICL_ERR_ARG, "icl_forward_prune_stats: NULL argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     *pruned_blocks = ctx->pruned_blocks;
+    return ICL_OK;
+}
+
+extern "C" int icl_set_forward_prune_fused(icl_ctx *ctx, int on)
+{
+    if (!ctx || on < 0 || on > 1) return icl_fail(ctx, ICL_ERR_ARG, "icl_set_forward_prune_fused: on must be 0 or 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->fwd_prune_fused = on;
+    return ICL_OK;
+}
+
+extern "C" int icl_forward_prune_fused_stats(icl_ctx *ctx, int64_t *pruned_launches)
+{
+    if (!ctx || !pruned_launches) return icl_fail(ctx, ICL_ERR_ARG, "icl_forward_prune_fused_stats: NULL argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *pruned_launches = ctx->pruned_fused;
     return ICL_OK;
 }
 

@@ -10,8 +10,10 @@
 
 #ifdef __HIPCC__
 #define PRUNE_HD __host__ __device__
+#define PRUNE_FI __host__ __device__ __forceinline__
 #else
 #define PRUNE_HD
+#define PRUNE_FI inline
 #endif
 
 // Output-pixel map of a convolution launch: compact pixel (b, oy, ox) of [B][Ho][Wo] lives at pixel (b, sub * oy, sub * ox) of [B][H][W].
@@ -52,4 +54,57 @@ inline int prune_stride(const icl_conv_rec &c2, const icl_conv_rec &c3, const ic
     if (c2.role != 2 || c2.k != 3 || c2.stride != 1 || c2.pad != 1 || c2.hout != c3.hin || c2.hin != c2.hout) return 0;
     // 3 x 3 / pad 1 / stride s and 1 x 1 / pad 0 / stride s give the same extent: (h + 2 - 3) / s + 1 == (h - 1) / s + 1
     return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The same rule inside the fused stage-1 bottleneck (bneck56_kernel<false, 2>, resnet_fused.h): the kernel walks a strip of a RUN of images
+// stacked with one padding row between them (VH = H + 1 virtual rows per image, row H = padding) in steps of 4 virtual rows, so which rows
+// of a step are read by the strided reader follows from the row cursor alone -- never from the step index: the parity of a virtual row
+// flips from one image of a run to the next.  tests/bneck56_needed_main.cpp walks these functions on the host against the triple loop.
+// ------------------------------------------------------------------------------------------------------------
+// (image, row) of a virtual row cursor, advanced without divisions (VH = H + 1 rows per image, row H = padding)
+struct bn56_row {
+    int b, r, p; // image, row inside the image (H = the padding row), physical row b * H + r of the tensor
+    PRUNE_FI void step(int VH)
+    {
+        ++p;
+        if (++r == VH) {
+            r = 0;
+            ++b;
+            --p; // the padding row is not in memory
+        }
+    }
+};
+// row r of an image of H rows (r == H: the padding row) / column c of its W columns is read by a 1 x 1, pad 0, stride sub reader
+PRUNE_FI bool bn56_row_needed(int r, int H, int sub) { return r < H && r % sub == 0; }
+PRUNE_FI bool bn56_col_needed(int c, int W, int sub) { return c < W && c % sub == 0; }
+// Front waves, sub >= 2: the needed rows among the 4 virtual rows from t on, as row indices 0..3 of the step.  Two rows that follow each
+// other are never both needed (inside an image their parities differ, the padding row is never needed), so there are at most two: {a, b},
+// a < b when both are needed.  With fewer, the spare index names another, unneeded row of the step (a != b always): conv2 computes two
+// rows per step without a branch, and what it leaves in an unneeded row of t2 nobody reads.
+struct bn56_rows2 {
+    int a, b;
+};
+PRUNE_FI bn56_rows2 bn56_step_rows(bn56_row t, int H, int VH, int sub)
+{
+    int a = -1, b = -1;
+    for (int m = 0; m < 4; ++m) {
+        if (bn56_row_needed(t.r, H, sub)) {
+            if (a < 0) a = m;
+            else b = m;
+        }
+        t.step(VH);
+    }
+    if (a < 0) a = 0;
+    if (b < 0) b = a ^ 2;
+    return bn56_rows2{a, b};
+}
+// Back waves: which of a quarter's two rows (t0 and the row behind it) is stored -- needed, and a row of the run's images [b0, b1):
+// 0, 1, or -1 (neither: the quarter does nothing).
+PRUNE_FI int bn56_quarter_row(bn56_row t0, int b0, int b1, int H, int VH, int sub)
+{
+    if (t0.b >= b0 && t0.b < b1 && bn56_row_needed(t0.r, H, sub)) return 0;
+    t0.step(VH);
+    if (t0.b >= b0 && t0.b < b1 && bn56_row_needed(t0.r, H, sub)) return 1;
+    return -1;
 }

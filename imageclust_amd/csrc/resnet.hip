@@ -960,7 +960,7 @@ static int stem_per_cu(int prec, int fuse)
 }
 static fwd_opts forward_opts_of(const icl_ctx *ctx, int prec)
 {
-    return fwd_opts{conv_opts_of(ctx), fuse_mask(), ctx->fwd_prune, stem_per_cu(prec, fuse_mask())};
+    return fwd_opts{conv_opts_of(ctx), fuse_mask(), ctx->fwd_prune, stem_per_cu(prec, fuse_mask()), ctx->fwd_prune_fused};
 }
 
 // grid: fwd_stem_blocks over the B * SP_STRIPS strips
@@ -986,9 +986,11 @@ static void launch_stem_pool(icl_ctx *ctx, int prec, const uint8_t *d_img, int B
 }
 
 // One stage-1 bottleneck in one launch (bf16): c1 -> c2 -> c3 (+ residual x | + downsample branch ds) + ReLU.  a: tensors, weights
-// and B, H, W; the grid is decided here.
-static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, hipStream_t strm)
+// and B, H, W; the grid is decided here.  sub == 2 (identity form only): the pruned instantiation -- Y's pixels (2 oy, 2 ox) are written, the
+// others keep what the buffer held (forward_make_plan decides when; prune_map.h).
+static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, int sub, hipStream_t strm)
 {
+    if (sub != 1 && (sub != 2 || ds)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused bottleneck: no kernel for sub = %d%s", sub, ds ? " with a downsample branch" : "");
     const int B = a.B;
     if ((int64_t)B * a.H * a.W * 512 >= (1LL << 31)) return icl_fail(ctx, ICL_ERR_UNSUPPORTED, "fused bottleneck: batch of %d images exceeds the 32-bit buffer offsets", B);
     bneck56_grid(B, a.W, ctx->prop.multiProcessorCount, &a.nstrips, &a.ngroups);
@@ -997,12 +999,16 @@ static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, hipStream_t
     if (!dbg) (void)hipMalloc((void **)&dbg, 16 * 8);
     a.dbg = dbg;
 #endif
-    const double px = (double)B * a.H * a.W;
-    icl_prof_scope ps(ctx, ICL_K_CONV, 2.0 * px * (64.0 * (ds ? 64 : 256) + 64.0 * 576 + 256.0 * (ds ? 128 : 64)), 0.0);
+    // the flops the result needs: conv1 on every pixel, conv2 and conv3 on the pixels that are read
+    const double px = (double)B * a.H * a.W, px23 = (double)B * prune_extent(a.H, sub) * prune_extent(a.W, sub);
+    icl_prof_scope ps(ctx, ICL_K_CONV, 2.0 * (px * 64.0 * (ds ? 64 : 256) + px23 * (64.0 * 576 + 256.0 * (ds ? 128 : 64))), 0.0);
     const dim3 grid((unsigned)(a.nstrips * a.ngroups));
     if (ds) {
         icl_lds_optin(ctx, (const void *)bneck56_kernel<true>, (int)bneck56_lds_bytes<true>());
         hipLaunchKernelGGL((bneck56_kernel<true>), grid, dim3(512), bneck56_lds_bytes<true>(), strm, a);
+    } else if (sub == 2) {
+        icl_lds_optin(ctx, (const void *)bneck56_kernel<false, 2>, (int)bneck56_lds_bytes<false>());
+        hipLaunchKernelGGL((bneck56_kernel<false, 2>), grid, dim3(512), bneck56_lds_bytes<false>(), strm, a);
     } else {
         icl_lds_optin(ctx, (const void *)bneck56_kernel<false>, (int)bneck56_lds_bytes<false>());
         hipLaunchKernelGGL((bneck56_kernel<false>), grid, dim3(512), bneck56_lds_bytes<false>(), strm, a);
@@ -1027,7 +1033,7 @@ static int launch_bneck56_args(icl_ctx *ctx, bneck_args &a, bool ds, hipStream_t
 }
 
 static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &c2, const conv_layer &c3, const conv_layer *ds, const void *x, void *y,
-                          int B, hipStream_t strm)
+                          int B, int sub, hipStream_t strm)
 {
     bneck_args a = {};
     a.X = (const uint16_t *)x;
@@ -1038,7 +1044,7 @@ static int launch_bneck56(icl_ctx *ctx, const conv_layer &c1, const conv_layer &
     a.sh1 = c1.shift; a.sh2 = c2.shift;
     a.sh3 = ds ? c3.shift_fused : c3.shift;
     a.B = B; a.H = c2.rec.hin; a.W = c2.rec.hin;
-    return launch_bneck56_args(ctx, a, ds != nullptr, strm);
+    return launch_bneck56_args(ctx, a, ds != nullptr, sub, strm);
 }
 
 // The plan of one forward pass of B images of the loaded model under the context's options as they are now (forward_make_plan, conv_select.h).
@@ -1085,7 +1091,8 @@ static int forward_batch(icl_ctx *ctx, int prec, const fwd_plan &plan, const uin
             }
             break;
         case FWD_BNECK56: // the whole bottleneck in one launch
-            ICL_TRY(launch_bneck56(ctx, L, m->conv[s.layer + 1], m->conv[s.layer + 2], s.ds ? &m->conv[s.layer + 3] : nullptr, buf[s.x], buf[s.y], B, strm));
+            ICL_TRY(launch_bneck56(ctx, L, m->conv[s.layer + 1], m->conv[s.layer + 2], s.ds ? &m->conv[s.layer + 3] : nullptr, buf[s.x], buf[s.y], B, s.sub, strm));
+            ctx->pruned_fused += s.sub == 2;
             break;
         case FWD_CONV: {
             conv_args a = s.a;
@@ -1138,9 +1145,10 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
 //   identity (wds == NULL, Cin = 256): y = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x))))))) + x)
 //   downsample (wds != NULL, Cin = 64): y = relu(bn3(conv3(t2)) + bn_ds(conv_ds(x)))  (both BN scales folded into the weights)
 // x: [B][H][W][Cin] NHWC, w1: [64][Cin], w2: [64][64][3][3] (OIHW), w3: [256][64], wds: [256][Cin]; y: [B][H][W][256].
-extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int W, int Cin, const float *w1, const float *sc1, const float *sh1,
-                                const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
-                                const float *wds, const float *scds, const float *shds, float *y)
+// sub == 2 (icl_bottleneck56_sub): the pruned instantiation; every 16-bit element of y is set to `fill` before the launch.
+static int bottleneck56_entry(icl_ctx *ctx, const float *x, int B, int H, int W, int Cin, const float *w1, const float *sc1, const float *sh1,
+                              const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
+                              const float *wds, const float *scds, const float *shds, int sub, const uint16_t *fill, float *y)
 {
     if (!ctx || !x || !w1 || !sc1 || !sh1 || !w2 || !sc2 || !sh2 || !w3 || !sc3 || !sh3 || !y || B < 1 || H < 1 || W < 1)
         return icl_fail(ctx, ICL_ERR_ARG, "icl_bottleneck56: bad argument");
@@ -1177,8 +1185,25 @@ extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int 
         a.sh1 = (const float *)d1h.p; a.sh2 = (const float *)d2h.p; a.sh3 = (const float *)d3h.p;
         a.B = B; a.H = H; a.W = W;
         io.returns(ICL_PREC_BF16, dy.p, ny);
-        return launch_bneck56_args(ctx, a, has_ds, ctx->stream); // the launch code of the forward pass
+        if (fill && hipMemsetD16Async((hipDeviceptr_t)dy.p, *fill, ny, ctx->stream) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_bottleneck56: fill");
+        return launch_bneck56_args(ctx, a, has_ds, sub, ctx->stream); // the launch code of the forward pass
     });
+}
+extern "C" int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int W, int Cin, const float *w1, const float *sc1, const float *sh1,
+                                const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
+                                const float *wds, const float *scds, const float *shds, float *y)
+{
+    return bottleneck56_entry(ctx, x, B, H, W, Cin, w1, sc1, sh1, w2, sc2, sh2, w3, sc3, sh3, wds, scds, shds, 1, nullptr, y);
+}
+// The identity form with the launch's `sub` (1: every pixel; 2: the pruned instantiation, which writes the pixels (2 oy, 2 ox) only) on a y
+// whose every 16-bit element holds `fill` when the kernel starts: the pixels a launch does not write come back as that pattern.
+extern "C" int icl_bottleneck56_sub(icl_ctx *ctx, const float *x, int B, int H, int W, const float *w1, const float *sc1, const float *sh1,
+                                    const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
+                                    int sub, int fill, float *y)
+{
+    if (sub < 1 || sub > 2 || fill < 0 || fill > 0xffff) return icl_fail(ctx, ICL_ERR_ARG, "icl_bottleneck56_sub: sub must be 1 or 2, fill a 16-bit pattern");
+    const uint16_t f16 = (uint16_t)fill;
+    return bottleneck56_entry(ctx, x, B, H, W, 256, w1, sc1, sh1, w2, sc2, sh2, w3, sc3, sh3, nullptr, nullptr, nullptr, sub, &f16, y);
 }
 
 // The forward pass of the loaded model up to a tap, for the per-block parity tests: forward_batch on lane 0 for ONE batch of B images

@@ -516,6 +516,25 @@ __global__ __launch_bounds__(256) void stem2_pool_kernel(const uint8_t *__restri
 //     Whatever LDS held there, NaN patterns included, stays in that row: a B column of the MFMA is one pixel, and columns do not mix.)
 //   k order per output element: channels ascending for the 1x1s, (row, kw, channel) for the 3x3, [t2 | x] for conv3: fixed,
 //   so results do not depend on the batch, on the strip decomposition or on the step height.
+//   * The PRUNED form, bneck56_kernel<false, 2> (the last identity block in front of a block 0 that reads at stride 2: forward_make_plan,
+//     prune_map.h): only the pixels (2 oy, 2 ox) of y are computed behind conv1 and stored; every other pixel of y keeps what the buffer held.
+//     Strip walk, ring, barriers (D | E | C | D, 3 nsteps + 3 in both wave groups), the WAR / RAW argument, the DMA and conv1 with its t1
+//     epilogue are the code above, unchanged.
+//       rows     a virtual row is needed if its image row t.r is even and t.r < H (bn56_row_needed), read off the bn56_row cursor -- never
+//                off the step index: images are stacked at H + 1 rows, so the parity of a virtual row flips from one image of a run to the
+//                next, and around an image boundary the pattern inside a step shifts.  Two rows in a row are never both needed, so a step
+//                has at most two needed rows (bn56_step_rows) and a quarter at most one (bn56_quarter_row); both are wave-uniform.
+//       front    conv2 accumulates and writes t2 for the step's two rows only: units (kh, k half) of 3 fragments (kw) per row, i.e. the sum
+//                order (kh, k half, kw) of the unpruned loop; 36 MFMAs instead of 72.  With fewer than two needed rows the spare index
+//                names an unneeded row, whose t2 nobody reads: no branch in the loop.  The other t2 rows hold what an earlier step left.
+//       back     a quarter computes conv3, the selector-MFMA residual, the ReLU and the OT write for its needed row (12 MFMAs instead of
+//                24; none and no store for a quarter without one, e.g. (row 55, padding)); the barriers stand outside the quarter.
+//       columns  c0 = 14 strip is even, so the even image columns are the even strip columns.  OT holds the row with the even columns first
+//                (see aoff2 below), and ONE buffer_store_dwordx4 carries them: 8 lanes per pixel's 128 B, strip columns 0, 2, .. 12, lanes
+//                56..63 ("column 14") and columns outside the image out of range (BN56_OOB) -- one store per quarter instead of four, each
+//                lane group a whole 128-byte line of a pixel that is read.
+//     The values that are stored are the unpruned kernel's bit for bit (tests/test_bneck56_pruned_gpu.py); which pixels those are is walked on
+//     the host against the triple loop (tests/bneck56_needed_main.cpp).
 // ------------------------------------------------------------------------------------------------------------
 // in-kernel segment timers for tuning (a separate diagnostic build: -DBN56_TIMERS; launch_bneck56 prints them when BN56_PRINT is set)
 #ifdef BN56_TIMERS
@@ -574,24 +593,13 @@ static constexpr size_t bneck56_lds_bytes()
 // workgroup barrier that waits for this wave's LDS traffic only (the front waves' LDS-DMA stays in flight across it; their own
 // vmcnt(0) covers it before the barrier that publishes the tile)
 __device__ __forceinline__ void bn56_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// (image, row) of a virtual row cursor, advanced without divisions (VH = H + 1 rows per image, row H = padding)
-struct bn56_row {
-    int b, r, p; // image, row inside the image (H = the padding row), physical row b * H + r of the tensor
-    __device__ __forceinline__ void step(int VH)
-    {
-        ++p;
-        if (++r == VH) {
-            r = 0;
-            ++b;
-            --p; // the padding row is not in memory
-        }
-    }
-};
+// (bn56_row, the (image, row) cursor of a virtual row, and the rules of the pruned form: prune_map.h)
 
-template <bool DS>
+template <bool DS, int SUB = 1>
 __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
 {
     static_assert(BN56_ROWS == 4, "the quarters below are rows {-1, 0} and {1, 2} of a 4-row step");
+    static_assert(SUB == 1 || (SUB == 2 && !DS && BN56_COLS % 2 == 0), "the pruned form: an identity block read at stride 2; a strip starts at an even column");
     constexpr int CIN = DS ? 64 : 256;
     constexpr int NCH = CIN / 64;       // 64-channel chunks of x
     constexpr int K3 = DS ? 128 : 64;   // conv3's K: [t2 | x] or t2
@@ -663,6 +671,7 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
         bn56_row cur{b0, 0, b0 * H}; // virtual row S + 4j: the first new t1 row of step j
         bn56_row dma = cur;          // ... + w: this wave's DMA row
         for (int i = 0; i < w; ++i) dma.step(VH);
+        [[maybe_unused]] bn56_row o2{b0 - 1, H, b0 * H}; // SUB == 2: virtual row S + 4j - 1, the first t2 row of step j (the back waves' `out`)
         reinterpret_cast<uint4 *>(T1)[tid] = make_uint4(0, 0, 0, 0); // the two kept t1 rows of step 0: padding
         stage_x(dma, 0u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -718,37 +727,74 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
             BN56_STAMP(3); // wait at C
             // ---- conv2: t2 = relu(W2' * t1 + shift2): every t1 fragment (row R, kw, k half) is read once and feeds the taps kh = R - m;
             // the 3 fragments of the next unit are requested before the MFMAs of this one
-            f32x4 a2[BN56_ROWS];
-            {
-                // units of 3 fragments (t1 row R, k half ks, kw = 0..2: up to 9 MFMAs), requested one unit ahead
-                constexpr int NU = 2 * (BN56_ROWS + 2);
-                uint4 f[2][3];
+            if constexpr (SUB == 2) {
+                // Pruned form: t2 for the step's needed rows only -- at most two, bn56_step_rows (prune_map.h), from the cursor o2.  Row m of
+                // the step takes the t1 rows m + kh: units (kh, k half) of 3 fragments (kw) per row, both rows' requested one unit ahead, so
+                // an output element still sums in the order (kh, k half, kw) of the loop over u = (R, ks) below.  36 MFMAs instead of 72.
+                const bn56_rows2 nr = bn56_step_rows(o2, H, VH, SUB);
+                for (int i = 0; i < BN56_ROWS; ++i) o2.step(VH);
+                const unsigned rowb[2] = {(unsigned)nr.a * (unsigned)RB, (unsigned)nr.b * (unsigned)RB};
+                f32x4 a2[2];
+                constexpr int NU = 6;
+                uint4 f[2][2][3];
+                auto ld = [&](int u, uint4 (&d)[2][3]) {
 #pragma unroll
-                for (int kw = 0; kw < 3; ++kw) f[0][kw] = *reinterpret_cast<const uint4 *>(T1 + t1off[kw][0]);
+                    for (int s = 0; s < 2; ++s)
+#pragma unroll
+                        for (int kw = 0; kw < 3; ++kw) d[s][kw] = *reinterpret_cast<const uint4 *>(T1 + rowb[s] + (u >> 1) * RB + t1off[kw][u & 1]);
+                };
+                ld(0, f[0]);
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
-                    const int R = u >> 1, ks = u & 1;
-                    if (u + 1 < NU) {
-#pragma unroll
-                        for (int kw = 0; kw < 3; ++kw) f[(u + 1) & 1][kw] = *reinterpret_cast<const uint4 *>(T1 + ((u + 1) >> 1) * RB + t1off[kw][(u + 1) & 1]);
-                    }
+                    const int kh = u >> 1, ks = u & 1;
+                    if (u + 1 < NU) ld(u + 1, f[(u + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-                        for (int kh = 0; kh < 3; ++kh) {
-                            const int m = R - kh;
-                            if (m >= 0 && m < BN56_ROWS) a2[m] = mfma16(w2r[(kh * 3 + kw) * 2 + ks], f[u & 1][kw], (kh == 0 && kw == 0 && ks == 0) ? h2 : a2[m]);
-                        }
+                        for (int s = 0; s < 2; ++s) a2[s] = mfma16(w2r[(kh * 3 + kw) * 2 + ks], f[u & 1][s][kw], (u == 0 && kw == 0) ? h2 : a2[s]);
                 }
-            }
-            unsigned char *T2w = T2 + (j & 1) * BN56_T2_BYTES;
+                unsigned char *T2w = T2 + (j & 1) * BN56_T2_BYTES;
 #pragma unroll
-            for (int m = 0; m < BN56_ROWS; ++m) {
-                uint2 o;
-                o.x = pack_relu_bf16x2(a2[m][0], a2[m][1]);
-                o.y = pack_relu_bf16x2(a2[m][2], a2[m][3]);
-                *reinterpret_cast<uint2 *>(T2w + m * RB + toff) = o;
+                for (int s = 0; s < 2; ++s) {
+                    uint2 o;
+                    o.x = pack_relu_bf16x2(a2[s][0], a2[s][1]);
+                    o.y = pack_relu_bf16x2(a2[s][2], a2[s][3]);
+                    *reinterpret_cast<uint2 *>(T2w + rowb[s] + toff) = o;
+                }
+            } else {
+                f32x4 a2[BN56_ROWS];
+                {
+                    // units of 3 fragments (t1 row R, k half ks, kw = 0..2: up to 9 MFMAs), requested one unit ahead
+                    constexpr int NU = 2 * (BN56_ROWS + 2);
+                    uint4 f[2][3];
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) f[0][kw] = *reinterpret_cast<const uint4 *>(T1 + t1off[kw][0]);
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) {
+                        const int R = u >> 1, ks = u & 1;
+                        if (u + 1 < NU) {
+#pragma unroll
+                            for (int kw = 0; kw < 3; ++kw) f[(u + 1) & 1][kw] = *reinterpret_cast<const uint4 *>(T1 + ((u + 1) >> 1) * RB + t1off[kw][(u + 1) & 1]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+                            for (int kh = 0; kh < 3; ++kh) {
+                                const int m = R - kh;
+                                if (m >= 0 && m < BN56_ROWS) a2[m] = mfma16(w2r[(kh * 3 + kw) * 2 + ks], f[u & 1][kw], (kh == 0 && kw == 0 && ks == 0) ? h2 : a2[m]);
+                            }
+                    }
+                }
+                unsigned char *T2w = T2 + (j & 1) * BN56_T2_BYTES;
+#pragma unroll
+                for (int m = 0; m < BN56_ROWS; ++m) {
+                    uint2 o;
+                    o.x = pack_relu_bf16x2(a2[m][0], a2[m][1]);
+                    o.y = pack_relu_bf16x2(a2[m][2], a2[m][3]);
+                    *reinterpret_cast<uint2 *>(T2w + m * RB + toff) = o;
+                }
             }
             BN56_STAMP(4); // conv2 + t2 epilogue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's pieces of the next x tile have landed
@@ -828,9 +874,60 @@ __global__ __launch_bounds__(512, 2) void bneck56_kernel(const bneck_args p)
             yvoff[i] = ok ? (unsigned)(c * 256 + chunk * 8) * 2u : BN56_OOB;
         }
         auto row_ok = [&](const bn56_row &t) { return t.b >= b0 && t.b < b1 && t.r < H; };
+        // Pruned form (SUB == 2): a quarter stores ONE row at most (bn56_quarter_row), and of it the even image columns -- the even strip
+        // columns, c0 = 14 * strip being even.  OT holds that row with the even columns first: pixel r16 at (r16 >> 1) * 128, the odd ones 1 KiB
+        // behind; 16-byte chunk k of a pixel sits in slot k ^ (r16 >> 1) ^ (r16 & 1).  Writes: the 32 lanes of a ds_write_b64 group (r16, q & 1
+        // at fixed q >> 1) fall on 16 distinct 16-byte slots of the 256 bank bytes -- (r16 >> 1) & 1 picks the half, and within a half the even
+        // and the odd columns take slots of opposite parity.  Read-back: lane l reads OT + 16 l, i.e. slot l & 7 of strip column 2 (l >> 3) --
+        // contiguous, conflict-free -- and ONE store instruction carries the 7 needed columns' whole 128-byte lines of this wave's channels
+        // (lanes 56 .. 63, "column 14", and columns outside the image: out of range).
+        [[maybe_unused]] unsigned aoff2[4], yvoff2 = BN56_OOB;
+        if constexpr (SUB == 2) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                aoff2[g] = (unsigned)((r16 >> 1) * 128 + (r16 & 1) * 1024 + ((((2 * g + (q >> 1)) ^ (r16 >> 1) ^ (r16 & 1)) & 7) << 4) + 8 * (q & 1));
+            const int c = SUB * lcol, chunk = (lps ^ lcol) & 7;
+            if (c < BN56_COLS && bn56_col_needed(c0 + c, Wd, SUB)) yvoff2 = (unsigned)(c * 256 + chunk * 8) * 2u;
+        }
         BN56_TIMER_DECL;
         // T2q: the quarter's two t2 rows; S0, S1: the x-tile rows (this wave's chunk) of its two rows; t0: its first virtual row
         auto quarter = [&](const unsigned char *T2q, const unsigned char *S0, const unsigned char *S1, bn56_row t0) {
+            if constexpr (SUB == 2) {
+                const int mm = bn56_quarter_row(t0, b0, b1, H, VH, SUB); // wave-uniform
+                if (mm < 0) return;
+                if (mm) t0.step(VH);
+                const unsigned char *Tq = T2q + mm * RB, *S = mm ? S1 : S0;
+                uint4 tb[2], xb[2];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    tb[ks] = *reinterpret_cast<const uint4 *>(Tq + xoff[ks]);
+                    xb[ks] = *reinterpret_cast<const uint4 *>(S + soff[ks]);
+                }
+                BN56_STAMP(0);
+                f32x4 a3[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    a3[g] = mfma16(w3r[g * NW3 + 0], tb[0], h3[g]);
+                    a3[g] = mfma16(w3r[g * NW3 + 1], tb[1], a3[g]);
+                }
+#pragma unroll
+                for (int g = 0; g < 4; ++g) a3[g] = mfma16(sel[g & 1], xb[g >> 1], a3[g]); // + residual
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    uint2 o;
+                    o.x = pack_relu_bf16x2(a3[g][0], a3[g][1]);
+                    o.y = pack_relu_bf16x2(a3[g][2], a3[g][3]);
+                    *reinterpret_cast<uint2 *>(OT + aoff2[g]) = o;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's OT writes are done (the tile is private to the wave)
+                __builtin_amdgcn_sched_barrier(0);
+                BN56_STAMP(1);
+                const uint4 v = *reinterpret_cast<const uint4 *>(OT + lane * 16);
+                bstore16_asm(ysrd, yvoff2, (unsigned)t0.p * yrow_bytes + ybase, v);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // OT is read: the next quarter may overwrite it
+                BN56_STAMP(2);
+                return;
+            }
             uint4 tb[2][2], xb[2][2];
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm)

@@ -218,6 +218,12 @@ int icl_set_conv_options(icl_ctx *ctx, int p8_mode);
  * ICL_PREC_BF16X3 are not affected.  icl_forward_prune_stats: bottlenecks run in the pruned form since the context was created. */
 int icl_set_forward_prune(icl_ctx *ctx, int on);
 int icl_forward_prune_stats(icl_ctx *ctx, int64_t *pruned_blocks);
+/* The same rule on a bottleneck that runs as ONE fused launch (stage 1's last block, in front of stage 2's block 0): the launch takes the
+ * instantiation that computes the 3x3 and the last 1x1 convolution for the pixels (2 oy, 2 ox) only and stores only those; bit-identical
+ * results.  Default on (environment: ICL_PRUNE_FUSED = 0/1); in effect only while icl_set_forward_prune is on, which turns both parts off.
+ * icl_forward_prune_fused_stats: such launches of the forward pass since the context was created (icl_forward_prune_stats does not count them). */
+int icl_set_forward_prune_fused(icl_ctx *ctx, int on);
+int icl_forward_prune_fused_stats(icl_ctx *ctx, int64_t *pruned_launches);
 /* Launches of the split form since the context was created. */
 int icl_conv_split_launches(icl_ctx *ctx, int64_t *launches);
 /* Convolution launches since the context was created: on conv_p8_kernel / on every other convolution kernel (either pointer may be NULL). */
@@ -262,6 +268,12 @@ int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *hwc_rgb, int B, float *
 int icl_bottleneck56(icl_ctx *ctx, const float *x, int B, int H, int W, int Cin, const float *w1, const float *sc1, const float *sh1,
                      const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
                      const float *wds, const float *scds, const float *shds, float *y);
+/* icl_bottleneck56's identity form (Cin = 256) with the launch's sub: 1 computes every pixel, 2 is the pruned instantiation, which writes the
+ * pixels (2 oy, 2 ox) only.  Every 16-bit element of the device tensor y holds `fill` (0 .. 0xffff, a bf16 bit pattern) when the kernel
+ * starts, so a pixel the launch does not write comes back as that pattern (widened to fp32). */
+int icl_bottleneck56_sub(icl_ctx *ctx, const float *x, int B, int H, int W, const float *w1, const float *sc1, const float *sh1,
+                         const float *w2, const float *sc2, const float *sh2, const float *w3, const float *sc3, const float *sh3,
+                         int sub, int fill, float *y);
 
 /* ---- several GPUs behind one handle ------------------------------------------------------------------
  * workflow.go:89,161 run in ONE process: a group drives ndev contexts from ndev host threads.  embed shards the images by
