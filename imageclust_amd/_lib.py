@@ -102,6 +102,7 @@ SYMBOLS = [
     ("icl_forward_prune_stats", _int, [_vp, _vp]),
     ("icl_set_forward_prune_fused", _int, [_vp, _int]),
     ("icl_forward_prune_fused_stats", _int, [_vp, _vp]),
+    ("icl_set_stem_max_blocks", _int, [_vp, _int]),
     ("icl_bottleneck56_sub", _int, [_vp, _vp, _int, _int, _int] + [_vp] * 9 + [_int, _int, _vp]),
     ("icl_conv1x1_mapped", _int, [_vp, _vp, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _int, _vp]),
     ("icl_conv_split_launches", _int, [_vp, _vp]),
@@ -683,6 +684,10 @@ class Context:
     def set_forward_prune_fused(self, on=True):
         """The same for stage 1's last block, which runs as one fused launch (icl_set_forward_prune_fused; only with set_forward_prune on)."""
         check(self.h, self.L.icl_set_forward_prune_fused(self.h, 1 if on else 0))
+
+    def set_stem_max_blocks(self, max_blocks=0):
+        """Tests only: cap the persistent grid of the stem kernels (icl_set_stem_max_blocks; 0 = no cap, the default)."""
+        check(self.h, self.L.icl_set_stem_max_blocks(self.h, int(max_blocks)))
 
     def forward_prune_fused_stats(self):
         """launches of the fused bottleneck's pruned instantiation by the forward pass since the context was created."""

@@ -292,8 +292,13 @@ static inline void bneck56_grid(int B, int W, int ncu, int *nstrips, int *ngroup
     const int g = ncu / *nstrips < B ? ncu / *nstrips : B;
     *ngroups = g < 1 ? 1 : g;
 }
-// the persistent grid of a stem kernel: units of work, at most per_cu workgroups on each compute unit
-static inline unsigned fwd_stem_blocks(int64_t units, int per_cu, int ncu) { return (unsigned)(units < (int64_t)per_cu * ncu ? units : (int64_t)per_cu * ncu); }
+// the persistent grid of a stem kernel: units of work, at most per_cu workgroups on each compute unit; max_blocks > 0 (icl_set_stem_max_blocks,
+// tests only) caps it further, so that a workgroup walks several units at a batch of a few images
+static inline unsigned fwd_stem_blocks(int64_t units, int per_cu, int ncu, int max_blocks = 0)
+{
+    const int64_t g = units < (int64_t)per_cu * ncu ? units : (int64_t)per_cu * ncu;
+    return (unsigned)(max_blocks > 0 && max_blocks < g ? max_blocks : g);
+}
 
 struct fwd_opts {
     conv_opts conv;
@@ -301,6 +306,7 @@ struct fwd_opts {
     int prune;       // icl_set_forward_prune
     int stem_per_cu; // workgroups per CU of the stem kernel this precision and mask take
     int prune_fused = 1; // icl_set_forward_prune_fused: with `prune` on, the rule also prunes a bottleneck that runs as ONE fused launch
+    int stem_max_blocks = 0; // icl_set_stem_max_blocks (tests only): cap on the stem kernel's persistent grid, 0 = none
 };
 
 enum fwd_kind { FWD_STEM2_POOL, FWD_STEM_POOL, FWD_STEM, FWD_MAXPOOL, FWD_BNECK56, FWD_CONV, FWD_AVGPOOL, FWD_FC };
@@ -389,11 +395,11 @@ static inline fwd_plan forward_make_plan(const icl_conv_rec *recs, int nconv, in
     // ---- stem: conv0 + BN + ReLU + maxpool in one launch (BF16X3 has the fused stem only), or the two kernels
     if ((o.fuse & 1) || x3) {
         fwd_step &st = add(bf16 && (o.fuse & 8) ? FWD_STEM2_POOL : FWD_STEM_POOL, 0, FWD_NONE, x);
-        st.blocks = fwd_stem_blocks((int64_t)B * FWD_STEM_STRIPS, o.stem_per_cu, o.conv.ncu);
+        st.blocks = fwd_stem_blocks((int64_t)B * FWD_STEM_STRIPS, o.stem_per_cu, o.conv.ncu, o.stem_max_blocks);
         st.threads = 256;
     } else {
         fwd_step &st = add(FWD_STEM, 0, FWD_NONE, y);
-        st.blocks = fwd_stem_blocks((int64_t)B * 98, o.stem_per_cu, o.conv.ncu); // 8x16-pixel tiles: 14 x 7 per image
+        st.blocks = fwd_stem_blocks((int64_t)B * 98, o.stem_per_cu, o.conv.ncu, o.stem_max_blocks); // 8x16-pixel tiles: 14 x 7 per image
         st.threads = 256;
         fwd_step &mp = add(FWD_MAXPOOL, 0, y, x);
         mp.blocks = 256 * 8;

@@ -218,6 +218,14 @@ extern "C" int icl_set_forward_prune_fused(icl_ctx *ctx, int on)
     return ICL_OK;
 }
 
+extern "C" int icl_set_stem_max_blocks(icl_ctx *ctx, int max_blocks)
+{
+    if (!ctx || max_blocks < 0) return icl_fail(ctx, ICL_ERR_ARG, "icl_set_stem_max_blocks: max_blocks must be 0 (no cap) or positive");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->stem_max_blocks = max_blocks;
+    return ICL_OK;
+}
+
 extern "C" int icl_forward_prune_fused_stats(icl_ctx *ctx, int64_t *pruned_launches)
 {
     if (!ctx || !pruned_launches) return icl_fail(ctx, ICL_ERR_ARG, "icl_forward_prune_fused_stats: NULL argument");

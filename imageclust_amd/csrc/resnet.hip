@@ -960,7 +960,7 @@ static int stem_per_cu(int prec, int fuse)
 }
 static fwd_opts forward_opts_of(const icl_ctx *ctx, int prec)
 {
-    return fwd_opts{conv_opts_of(ctx), fuse_mask(), ctx->fwd_prune, stem_per_cu(prec, fuse_mask()), ctx->fwd_prune_fused};
+    return fwd_opts{conv_opts_of(ctx), fuse_mask(), ctx->fwd_prune, stem_per_cu(prec, fuse_mask()), ctx->fwd_prune_fused, ctx->stem_max_blocks};
 }
 
 // grid: fwd_stem_blocks over the B * SP_STRIPS strips
@@ -1133,7 +1133,7 @@ extern "C" int icl_stem_pool(icl_ctx *ctx, int prec, const uint8_t *img, int B, 
         ICL_TRY(icl_dev_alloc(ctx, dimg, (size_t)B * ICL_IMG_BYTES, "icl_stem_pool: images"));
         ICL_TRY(icl_dev_alloc(ctx, dy, ny * prec_act_bytes(prec), "icl_stem_pool: output"));
         if (hipMemcpy(dimg.p, img, (size_t)B * ICL_IMG_BYTES, hipMemcpyHostToDevice) != hipSuccess) return icl_fail(ctx, ICL_ERR_HIP, "icl_stem_pool: upload");
-        const unsigned grid = fwd_stem_blocks((int64_t)B * SP_STRIPS, stem_per_cu(prec, fuse_mask() | 1), ctx->prop.multiProcessorCount);
+        const unsigned grid = fwd_stem_blocks((int64_t)B * SP_STRIPS, stem_per_cu(prec, fuse_mask() | 1), ctx->prop.multiProcessorCount, ctx->stem_max_blocks);
         with_prec(prec, [&](auto t) { launch_stem_pool<decltype(t)>(ctx, prec, (const uint8_t *)dimg.p, B, dy.p, grid, ctx->stream); });
         io.returns(prec, dy.p, ny);
         const hipError_t e = hipGetLastError();

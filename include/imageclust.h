@@ -224,6 +224,11 @@ int icl_forward_prune_stats(icl_ctx *ctx, int64_t *pruned_blocks);
  * icl_forward_prune_fused_stats: such launches of the forward pass since the context was created (icl_forward_prune_stats does not count them). */
 int icl_set_forward_prune_fused(icl_ctx *ctx, int on);
 int icl_forward_prune_fused_stats(icl_ctx *ctx, int64_t *pruned_launches);
+/* For the tests of the stem kernels (stem2_pool_kernel, stem_pool_kernel, stem_conv_kernel): at most max_blocks workgroups in their
+ * persistent grid, in icl_stem_pool and in the forward pass alike, so that a workgroup walks several work units -- the unit-to-unit
+ * transition, the carried conv row, the prefetch across an image boundary -- at a batch of one to three images.  0 (the default): no cap,
+ * every launch is what it is without this call.  Results do not depend on the grid. */
+int icl_set_stem_max_blocks(icl_ctx *ctx, int max_blocks);
 /* Launches of the split form since the context was created. */
 int icl_conv_split_launches(icl_ctx *ctx, int64_t *launches);
 /* Convolution launches since the context was created: on conv_p8_kernel / on every other convolution kernel (either pointer may be NULL). */

@@ -4,7 +4,7 @@
 // launch listing.  The kernel names are formatted here: the header holds no strings.
 //   topo                                  the records of ResNet50-v1, one per line
 //   choose FILE                           FILE: lines "prec B H cin cout k stride pad res p8 split ncu" -> one choice per line
-//   plan prec B ncu dense tap fuse prune p8 split stem_per_cu   -> one step per line, then "out <buffer> <H> <C> pruned <n>"
+//   plan prec B ncu dense tap fuse prune p8 split stem_per_cu [stem_max_blocks]   -> one step per line, then "out <buffer> <H> <C> pruned <n>"
 //   refuse                                conv_same_arithmetic on choices that differ in one parameter each
 #include "../imageclust_amd/csrc/conv_select.h"
 #include "../imageclust_amd/csrc/prune_map.h"
@@ -73,10 +73,11 @@ static int choose(const char *path)
     return 0;
 }
 
-static int plan(char **v)
+static int plan(char **v, int stem_max_blocks)
 {
     const int prec = atoi(v[0]), B = atoi(v[1]), ncu = atoi(v[2]), dense = atoi(v[3]), tap = atoi(v[4]);
     fwd_opts o = {opts(atoi(v[7]), atoi(v[8]), ncu), atoi(v[5]), atoi(v[6]), atoi(v[9])};
+    o.stem_max_blocks = stem_max_blocks;
     icl_conv_rec recs[ICL_RESNET50_NCONV];
     const int n = resnet50_topology(recs);
     const fwd_plan p = forward_make_plan(recs, n, prec, B, dense != 0, tap, o);
@@ -162,7 +163,7 @@ int main(int argc, char **argv)
         return 0;
     }
     if (argc == 3 && !strcmp(argv[1], "choose")) return choose(argv[2]);
-    if (argc == 12 && !strcmp(argv[1], "plan")) return plan(argv + 2);
+    if ((argc == 12 || argc == 13) && !strcmp(argv[1], "plan")) return plan(argv + 2, argc == 13 ? atoi(argv[12]) : 0);
     if (argc == 2 && !strcmp(argv[1], "refuse")) return refuse();
     fprintf(stderr, "usage: see the head of conv_select_main.cpp\n");
     return 2;

@@ -10,8 +10,9 @@ names the kernel (the counters tell conv_wr_kernel / conv_p8_kernel from the 128
 fp32 always runs on the 128 x 128 kernels, and conv_wr_kernel and the split form are bf16 only (bf16x3 runs on the 128 x 128 kernels
 and on conv_p8_kernel: those two get the split-operand cases).
 
-Left out: the stem (it reads the loaded model, whose folded BatchNorm scale is not a power of two), and conv_wr_kernel's
-ICL_WR_PT256=32 instantiation (the variable is read once per process)."""
+The stem reads the loaded model, so it has a module of its own, tests/test_stem_exact_gpu.py, which loads models whose conv0 folds
+exactly (tests/stem_exact.py) and also walks the stem kernels' persistent grid.  Left out: conv_wr_kernel's ICL_WR_PT256=32 instantiation
+(the variable is read once per process)."""
 import time
 
 import numpy as np

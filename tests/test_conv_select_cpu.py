@@ -83,8 +83,8 @@ def test_choice_equals_route_and_wr_rule(program, tmp_path):
     assert seen == {"wr", "p8", "p8/split", "halo", "igemm"}, seen
 
 
-def plan(program, prec, B=256, ncu=256, dense=0, tap=-1, fuse=15, prune=1, p8=1, split=0, stem_per_cu=5):
-    lines = run(program, "plan", PRECS.index(prec), B, ncu, dense, tap, fuse, prune, p8, split, stem_per_cu)
+def plan(program, prec, B=256, ncu=256, dense=0, tap=-1, fuse=15, prune=1, p8=1, split=0, stem_per_cu=5, stem_cap=None):
+    lines = run(program, "plan", PRECS.index(prec), B, ncu, dense, tap, fuse, prune, p8, split, stem_per_cu, *(() if stem_cap is None else (stem_cap,)))
     steps = [ln.split("|") for ln in lines[:-1]]
     m = re.fullmatch(r"out (\d) (\d+) (\d+) pruned (\d+)", lines[-1])
     return steps, tuple(int(v) for v in m.groups())
@@ -138,6 +138,18 @@ def test_plan_structure(program):
             assert fused[0] == "bneck56_kernel<true>" and set(fused[1:]) <= {"bneck56_kernel<false>"}
     assert kernels(plan(program, "fp32", fuse=0)[0])[:2] == ["stem_conv_kernel", "maxpool_kernel"]
     assert kernels(plan(program, "bf16x3", fuse=0)[0])[0] == "stem_pool_kernel"  # (split bf16 has the fused stem only)
+
+
+def test_stem_grid_cap_changes_the_stem_grid_only(program):
+    """icl_set_stem_max_blocks (tests only): the stem step's grid is min(cap, the production grid) in both stem forms, every other step is
+    unchanged, and cap 0 is the plan without the option."""
+    for prec, fuse, B, units in (("bf16", 15, 3, 24), ("bf16", 7, 2, 16), ("fp32", 15, 1, 8), ("bf16x3", 0, 3, 24), ("bf16", 0, 3, 294), ("bf16", 15, 256, 1280)):
+        base = plan(program, prec, B=B, fuse=fuse)
+        assert plan(program, prec, B=B, fuse=fuse, stem_cap=0) == base and int(base[0][0][1]) == 256 * units
+        for cap in (1, 5, 8, 100000):
+            got = plan(program, prec, B=B, fuse=fuse, stem_cap=cap)
+            assert got[1] == base[1] and got[0][1:] == base[0][1:] and got[0][0][2:] == base[0][0][2:]
+            assert got[0][0][0] == "stem" and int(got[0][0][1]) == 256 * min(cap, units)
 
 
 def test_pruning_is_refused_where_the_arithmetic_would_differ(program):
