@@ -446,6 +446,29 @@ func ClusterFit(rows [][]float32, qSizes []int32, clusterOf []int32, clusters []
 	return iclengine.ClusterFit(rows, qSizes, clusterOf, centroids, sizes, kAlt, maxSize)
 }
 
+// FoldCentroids builds clusters from member lists: groups[g] lists positions in embeddings, and cluster g gets those Indices, their
+// count as Size and the Centroid MergeClusters (:29-47) leaves after merging the members one at a time in list order
+// (iclengine.FoldCentroids -> icl_fold_centroids, bit for bit).  It is what editing a held clustering needs -- a cluster after an image
+// was deleted or moved, a partition adopted from elsewhere (DESIGN.md "Editing a held clustering").
+func FoldCentroids(embeddings [][]float32, groups [][]int) ([]Cluster, error) {
+	lists := make([][]int32, len(groups))
+	for g, list := range groups {
+		lists[g] = make([]int32, len(list))
+		for i, m := range list {
+			lists[g][i] = int32(m)
+		}
+	}
+	cen, total, err := iclengine.FoldCentroids(embeddings, nil, lists)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]Cluster, len(groups))
+	for g := range groups {
+		out[g] = Cluster{Indices: append([]int(nil), groups[g]...), Size: int(total[g]), Centroid: cen[g]}
+	}
+	return out, nil
+}
+
 // DuplicatePair is one pair of images whose WardDistance as singletons is at most the threshold: A comes before B in the caller's list.
 type DuplicatePair struct {
 	A, B  string

@@ -471,6 +471,53 @@ func ClusterFit(rows [][]float32, qSizes []int32, clusterOf []int32, centroids [
 	return r, nil
 }
 
+// FoldCentroids gives each cluster listed by its members the centroid the reference holds after merging them one at a time in list
+// order (icl_fold_centroids: MergeClusters of clustering.go:29-47 folded, bit for bit).  groups[g] lists rows of `rows`; sizes[i] is
+// row i's item count (nil: all 1).  Returns one centroid and one item total per group; an empty group gives zeros and 0.
+func FoldCentroids(rows [][]float32, sizes []int32, groups [][]int32) ([][]float32, []int32, error) {
+	raw, e := Ctx()
+	if e != nil {
+		return nil, nil, e
+	}
+	n, K, d := len(rows), len(groups), 0
+	if n > 0 {
+		d = len(rows[0])
+	}
+	if sizes != nil && len(sizes) != n {
+		return nil, nil, fmt.Errorf("%d sizes for %d rows", len(sizes), n)
+	}
+	if K == 0 {
+		return nil, nil, nil
+	}
+	if d == 0 {
+		return nil, nil, fmt.Errorf("no rows to fold")
+	}
+	rowPtr := make([]int64, K+1)
+	member := make([]int32, 0, n)
+	for g, list := range groups {
+		member = append(member, list...)
+		rowPtr[g+1] = int64(len(member))
+	}
+	flat := flatRows(rows, d)
+	out := make([]float32, K*d)
+	total := make([]int32, K)
+	i32 := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	if rc := C.icl_fold_centroids((*C.icl_ctx)(raw), (*C.float)(unsafe.Pointer(&flat[0])), i32(sizes), C.int64_t(n), C.int32_t(d),
+		(*C.int64_t)(unsafe.Pointer(&rowPtr[0])), i32(member), C.int64_t(K), (*C.float)(unsafe.Pointer(&out[0])), i32(total)); rc != C.ICL_OK {
+		return nil, nil, fmt.Errorf("%s", C.GoString(C.icl_last_error((*C.icl_ctx)(raw))))
+	}
+	cen := make([][]float32, K)
+	for g := range cen {
+		cen[g] = out[g*d : (g+1)*d]
+	}
+	return cen, total, nil
+}
+
 // WardValuesAt is icl_ward_values_at: the exact WardDistance of each listed pair (row qi[p] of rows with qSizes, row ej[p] of library
 // with eSizes; nil sizes: all 1, a negative eSizes entry a frozen cluster's item count), the reference's values bit for bit.
 func WardValuesAt(rows [][]float32, qSizes []int32, library [][]float32, eSizes []int32, qi, ej []int32) ([]float32, error) {

@@ -165,6 +165,9 @@ SYMBOLS = [
     ("icl_last_fit_stats", _int, [_vp, _pi64]),
     ("icl_ward_values_at", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     ("icl_ward_values_at_dev", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp]),
+    ("icl_fold_centroids", _int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    ("icl_fold_centroids_dev", _int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    ("icl_last_fold_stats", _int, [_vp, _pi64]),
     ("icl_pairs_within", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
     ("icl_pairs_within_dev", _int, [_vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
     ("icl_pairs_within_from_matrix", _int, [_vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _i64, _pi64]),
@@ -319,6 +322,23 @@ def nearest_from_matrix(D, k, q_size=None, e_size=None, max_size=0, exclude=None
     if rc != ICL_OK:
         raise ICLError(rc, "icl_nearest_from_matrix: bad argument")
     return idx, val
+
+
+def _fold_lists(row_ptr, member):
+    """row_ptr of icl_fold_centroids as contiguous int64[K + 1]; its last entry must be the length of member (the library cannot see that)."""
+    rp = np.ascontiguousarray(np.asarray(row_ptr).reshape(-1), np.int64)
+    if len(rp) < 1:
+        raise ValueError("row_ptr must hold K + 1 entries")
+    if int(rp[-1]) != np.asarray(member).size:
+        raise ValueError("row_ptr ends at %d for %d members" % (int(rp[-1]), np.asarray(member).size))
+    return rp
+
+
+def groups_as_csr(groups):
+    """Lists of row indices -> (row_ptr int64[K + 1], member int32[total]), the member-list form of Context.fold_centroids."""
+    rp = np.zeros(len(groups) + 1, np.int64)
+    np.cumsum(np.array([len(g) for g in groups], np.int64), out=rp[1:])
+    return rp, np.array([i for g in groups for i in g], np.int64).astype(np.int32).reshape(-1)
 
 
 def _fit_outputs(nq, K, k_alt):
@@ -1150,6 +1170,39 @@ class Context:
         a, b = np.ascontiguousarray(np.asarray(qi).reshape(-1), np.int32), np.ascontiguousarray(np.asarray(ej).reshape(-1), np.int32)
         qs, es = _nearest_side(nq, q_size, "q_size"), _nearest_side(n, e_size, "e_size")
         check(self.h, self.L.icl_ward_values_at_dev(self.h, _as_vp(d_Q), _ptr(qs), nq, _as_vp(d_E), _ptr(es), n, d, _ptr(a), _ptr(b), len(a), _as_vp(d_val)))
+
+    def fold_centroids(self, E, row_ptr, member, size=None, dev=False):
+        """icl_fold_centroids: the centroid of each group of rows of E -- group g is the rows member[row_ptr[g]:row_ptr[g + 1]], in that
+        order, with item counts size (None: all 1) -- as the reference holds it after merging the members one at a time (MergeClusters,
+        clustering.go:29-47, bit for bit) -> (C float32[K][d], size_out int32[K]); an empty group gives a row of +0.0 and size 0.
+        dev=True runs icl_fold_centroids_dev on device copies instead of the host entry point."""
+        Em = np.ascontiguousarray(E, np.float32)
+        if Em.ndim != 2:
+            raise ValueError("E must be 2-D, got %s" % (Em.shape,))
+        n, d = Em.shape
+        rp, mb, sz = _fold_lists(row_ptr, member), np.ascontiguousarray(np.asarray(member).reshape(-1), np.int32), _nearest_side(n, size, "size")
+        K = len(rp) - 1
+        Cm, so = np.empty((K, d), np.float32), np.empty(K, np.int32)
+        if not dev:
+            check(self.h, self.L.icl_fold_centroids(self.h, _ptr(Em), _ptr(sz), n, d, _ptr(rp), _ptr(mb), K, _ptr(Cm), _ptr(so)))
+            return Cm, so
+        self._on_device_copies((Em,), (Cm,), lambda dE, dC: so.__setitem__(slice(None), self.fold_centroids_dev(dE, n, d, rp, mb, dC, size=sz)))
+        return Cm, so
+
+    def fold_centroids_dev(self, d_E, n, d, row_ptr, member, d_C, size=None):
+        """icl_fold_centroids_dev: E (n x d) and C (K x d) are device pointers; row_ptr, member and size host arrays -> size_out int32[K].
+        Enqueued on the context's stream: sync() before reading C through another stream."""
+        rp, mb, sz = _fold_lists(row_ptr, member), np.ascontiguousarray(np.asarray(member).reshape(-1), np.int32), _nearest_side(n, size, "size")
+        K = len(rp) - 1
+        so = np.empty(K, np.int32)
+        check(self.h, self.L.icl_fold_centroids_dev(self.h, _as_vp(d_E), _ptr(sz), n, d, _ptr(rp), _ptr(mb), K, _as_vp(d_C), _ptr(so)))
+        return so
+
+    def last_fold_stats(self):
+        """The last fold_centroids[_dev]: groups, member rows read, the longest group's length, workspace bytes."""
+        info = (C.c_int64 * 4)()
+        check(self.h, self.L.icl_last_fold_stats(self.h, info))
+        return {"groups": info[0], "rows": info[1], "longest": info[2], "workspace_bytes": info[3]}
 
     def pairs_within(self, E, threshold, size=None, cap=None):
         """icl_pairs_within: EVERY pair of rows of E whose WardDistance (sizes `size`, None: all 1) is at most threshold, bit for bit the

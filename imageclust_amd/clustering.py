@@ -229,6 +229,27 @@ def ClusterFit(queries, q_sizes, cluster_of, centroids, sizes, k: int = 1, maxSi
     return ctx.cluster_fit(queries, cluster_of, centroids, k, q_size=q_sizes, c_size=sizes, max_size=maxSize)
 
 
+def FoldCentroids(embeddings, groups, sizes=None, ctx: Optional[_lib.Context] = None):
+    """The centroid of each cluster given as a list of row indices (icl_fold_centroids): what the reference holds after merging the
+    listed rows one at a time in list order (MergeClusters, clustering.go:29-47, bit for bit; sizes: the rows' item counts, None:
+    singletons) -> (centroids float32[len(groups)][d], item totals int32[len(groups)]).  An empty list gives a row of +0.0 and 0."""
+    ctx = ctx or default_context()
+    E = np.asarray(embeddings, np.float32)
+    if E.ndim != 2:
+        E = E.reshape(len(embeddings), -1)
+    row_ptr, member = _lib.groups_as_csr(groups)
+    return ctx.fold_centroids(E, row_ptr, member, size=sizes)
+
+
+def _final_seed_lists(m: int, merges) -> List[List[int]]:
+    """The final list of a seeded run over m seeds from its merge log, each cluster as its seed sequence: surviving seeds in seed order,
+    then merged clusters in creation order, a's seeds before b's."""
+    seq = {i: [i] for i in range(m)}
+    for t, (a, b) in enumerate(np.asarray(merges).reshape(-1, 2)):
+        seq[m + t] = seq.pop(int(a)) + seq.pop(int(b))
+    return [seq[c] for c in sorted(seq)]
+
+
 def NearDuplicates(embeddings, ids, k: int, threshold: float, ctx: Optional[_lib.Context] = None) -> List[Tuple[str, str, float]]:
     """Pairs of images whose WardDistance as singletons is at most threshold, from a self-join of the embeddings (icl_nearest with
     exclude[i] = i, the k nearest of every image) -> [(id_a, id_b, value), ...], a before b in `ids`, each pair once, ordered by position.
@@ -321,8 +342,8 @@ def DuplicatesOf(new_embeddings, new_ids, embeddings, ids, threshold: float, ctx
 
 @dataclass
 class HeldCluster:
-    """A cluster a Clustering state holds between calls: member ids in the reference's order, the centroid as the loop left it, the
-    frozen flag, and its id in as_map() (-1: below minSize, so the reference's report drops it -- the state keeps it)."""
+    """A cluster a Clustering state holds between calls: member ids in the reference's order, the centroid as the loop left it (after
+    an edit: the fold of MergeClusters over the members in list order), the frozen flag, and its id in as_map() (-1: below minSize, so the reference's report drops it -- the state keeps it)."""
     Members: List[str]
     Centroid: np.ndarray
     Frozen: bool = False
@@ -345,17 +366,24 @@ class Clustering:
     status, merges, C_out), called with two more arguments, (..., apart_class, apart_pairs), only when a constraint exists; `nearest_engine` likewise for nearest(): nearest_engine(Q, E, k, q_size, e_size, max_size) -> (idx, val); and
     `fit_engine` for fit(), representatives() and misfits(): fit_engine(Q, cluster_of, C, k_alt, q_size, c_size, max_size) -> the dict of
     Context.cluster_fit; `between_engine` and `pairs_engine` for duplicates_of() and add(skip_duplicates=): between_engine(Q, L, threshold)
-    and pairs_engine(E, threshold) -> (row_ptr, col, val), as Context.pairs_between and Context.pairs_within.
+    and pairs_engine(E, threshold) -> (row_ptr, col, val), as Context.pairs_between and Context.pairs_within; `fold_engine` for the edits
+    below: fold_engine(E, row_ptr, member, size) -> (C, size_out), as Context.fold_centroids.
+
+    A held clustering can be edited (DESIGN.md "Editing a held clustering"): remove(ids) deletes images, move(ids, to_key) puts images
+    into another cluster, Clustering.from_partition(...) adopts a partition computed elsewhere, oversized() lists the clusters above
+    maxSize and split(keys) divides clusters with the state's own engine.  An edited cluster's centroid is the fold of MergeClusters over
+    its members in list order (icl_fold_centroids); a cluster no edit touched keeps the centroid the loop left it, so a state may hold
+    both kinds.
 
     update=UPDATE_LW keeps the state in FAST mode: every recluster() is icl_cluster_seeded_fast, whatever the number of clusters held, and a
     state with keep_apart constraints raises ICLError(ICL_ERR_UNSUPPORTED) there.  A FAST state cut and resumed is not the uncut FAST run."""
 
     def __init__(self, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None, fit_engine=None,
-                 between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT):
+                 between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT, fold_engine=None):
         self.minSize, self.maxSize = int(minSize), int(maxSize)
         self.update = int(update)
         self.ctx, self.engine, self.nearest_engine, self.fit_engine = ctx, engine, nearest_engine, fit_engine
-        self.between_engine, self.pairs_engine = between_engine, pairs_engine
+        self.between_engine, self.pairs_engine, self.fold_engine = between_engine, pairs_engine, fold_engine
         self.clusters: List[HeldCluster] = []
         self.embeddings: Dict[str, np.ndarray] = {}
         self.ok = True
@@ -364,13 +392,184 @@ class Clustering:
 
     @classmethod
     def start(cls, embeddings, ids, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None, nearest_engine=None,
-              fit_engine=None, between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT) -> "Clustering":
+              fit_engine=None, between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT, fold_engine=None) -> "Clustering":
         """A seeded run from singletons: the clusters of PerformClusteringWithConstraints(embeddings, ids, minSize, maxSize); .ok is
         False (and every image is still a singleton) when the constraints cannot be met."""
-        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine, update)
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine, update, fold_engine)
         state.add(embeddings, ids)
         state.recluster()
         return state
+
+    @classmethod
+    def from_partition(cls, embeddings, ids, groups, minSize: int, maxSize: int, ctx: Optional[_lib.Context] = None, engine=None,
+                       nearest_engine=None, fit_engine=None, between_engine=None, pairs_engine=None, update: int = _lib.UPDATE_EXACT,
+                       fold_engine=None) -> "Clustering":
+        """A state from a partition it did not compute (a user's albums, a clustering saved as id lists): `groups` is a list of
+        non-empty id lists, each id at most once; the ids in no group follow as singletons, in `ids` order.  No clustering runs: every
+        centroid is the fold of MergeClusters over the cluster's members in list order (one icl_fold_centroids call; a one-member
+        cluster holds its row's bits).  A group above maxSize is held as it is -- oversized() lists it, split() divides it, and
+        recluster() refuses the state while it is there.  ValueError for an empty group, an unknown id or an id listed twice."""
+        ids = list(ids)
+        E = _rows_of(embeddings, ids)
+        at = {k: i for i, k in enumerate(ids)}
+        if len(at) != len(ids):
+            raise ValueError("from_partition: an id is listed twice")
+        groups = [list(g) for g in groups]
+        seen = set()
+        for g in groups:
+            if not g:
+                raise ValueError("from_partition: an empty group")
+            for k in g:
+                if k not in at or k in seen:
+                    raise ValueError("from_partition: id %r is %s" % (k, "in two groups or twice in one" if k in at else "unknown"))
+                seen.add(k)
+        lists = groups + [[k] for k in ids if k not in seen]
+        state = cls(minSize, maxSize, ctx, engine, nearest_engine, fit_engine, between_engine, pairs_engine, update, fold_engine)
+        C = state._fold_rows(E, [[at[k] for k in g] for g in lists])
+        state.embeddings = {k: np.array(E[i], np.float32, copy=True) for i, k in enumerate(ids)}
+        state.clusters = [HeldCluster(g, np.array(C[j], np.float32, copy=True)) for j, g in enumerate(lists)]
+        state._renumber()
+        return state
+
+    def _fold_rows(self, E, groups) -> np.ndarray:
+        """The centroids of the clusters given as lists of rows of E, singletons throughout (icl_fold_centroids; `fold_engine(E, row_ptr,
+        member, size) -> (C, size_out)` stands in for the GPU call in tests)."""
+        row_ptr, member = _lib.groups_as_csr(groups)
+        if self.fold_engine is not None:
+            return np.asarray(self.fold_engine(E, row_ptr, member, None)[0], np.float32)
+        return (self.ctx or default_context()).fold_centroids(E, row_ptr, member)[0]
+
+    def _fold_members(self, lists: List[List[str]]) -> List[np.ndarray]:
+        """The centroids of clusters given as member id lists, all in one fold call over the rows they name."""
+        if not lists:
+            return []
+        rows = list(dict.fromkeys(k for g in lists for k in g))
+        at = {k: i for i, k in enumerate(rows)}
+        E = np.stack([self.embeddings[k] for k in rows]).astype(np.float32)
+        C = self._fold_rows(E, [[at[k] for k in g] for g in lists])
+        return [np.array(C[j], np.float32, copy=True) for j in range(len(lists))]
+
+    def _renumber(self):
+        """The report's ids (clustering.go:265-280; keep_together's rule): dense over the clusters of at least minSize items, in held
+        order, -1 otherwise."""
+        kept = 0
+        for c in self.clusters:
+            c.Id = -1
+            if len(c.Members) >= self.minSize:
+                c.Id, kept = kept, kept + 1
+
+    def _where(self, keys, what: str) -> Dict[str, int]:
+        """id -> position of its cluster, after checking that every key is held and listed once (ValueError otherwise)."""
+        where = {k: i for i, c in enumerate(self.clusters) for k in c.Members}
+        seen = set()
+        for k in keys:
+            if k not in where or k in seen:
+                raise ValueError("%s: id %r is %s" % (what, k, "listed twice" if k in where else "not held"))
+            seen.add(k)
+        return where
+
+    def remove(self, ids):
+        """The images leave the state: embeddings, member lists and the keep_apart groups (a group left with fewer than two ids is
+        dropped).  A cluster that lost members gets the fold of MergeClusters over what remains, as singletons in member order (all
+        rebuilt clusters in one icl_fold_centroids call); an emptied cluster disappears; a frozen cluster stays frozen.  ValueError,
+        with the state as it was, for an id that is not held or is listed twice."""
+        ids = list(ids)
+        where = self._where(ids, "remove")
+        gone, touched = set(ids), sorted({where[k] for k in ids})
+        left = {i: [k for k in self.clusters[i].Members if k not in gone] for i in touched}
+        rebuilt = [i for i in touched if left[i]]
+        cen = dict(zip(rebuilt, self._fold_members([left[i] for i in rebuilt])))
+        held = []
+        for i, c in enumerate(self.clusters):
+            if i not in left:
+                held.append(c)
+            elif left[i]:
+                held.append(HeldCluster(left[i], cen[i], c.Frozen))
+        self.clusters = held
+        for k in ids:
+            del self.embeddings[k]
+        self.apart = [g for g in ([k for k in grp if k not in gone] for grp in self.apart) if len(g) >= 2]
+        self._renumber()
+
+    def move(self, ids, to_key=None):
+        """The images change cluster: all are taken out first, then appended, in the order given, to the cluster holding to_key; with
+        to_key=None each becomes a singleton at the end, its centroid a copy of its embedding (as add() leaves it).  Every cluster that
+        lost or gained members gets the fold of MergeClusters over its new member list (one icl_fold_centroids call); a cluster left
+        empty disappears.  ValueError, with the state as it was, when an id is not held or listed twice, an id is already in the
+        target, a source or the target is frozen, the target would exceed maxSize, or two ids of one keep_apart group would share it."""
+        ids = list(ids)
+        where = self._where(ids, "move")
+        target = None
+        if to_key is not None:
+            if to_key not in where:
+                raise ValueError("move: id %r is not held" % (to_key,))
+            target = where[to_key]
+            if self.clusters[target].Frozen:
+                raise ValueError("move: the target cluster is frozen")
+            if any(where[k] == target for k in ids):
+                raise ValueError("move: an id is already in the target cluster")
+        if any(self.clusters[where[k]].Frozen for k in ids):
+            raise ValueError("move: a source cluster is frozen")
+        if not ids:
+            return  # nobody moves: the target keeps the centroid it holds
+        gone, touched = set(ids), sorted({where[k] for k in ids})
+        left = {i: [k for k in self.clusters[i].Members if k not in gone] for i in touched}
+        if target is not None:
+            left[target] = list(self.clusters[target].Members) + ids
+            if len(left[target]) > self.maxSize:
+                raise ValueError("move: %d items, above maxSize (%d)" % (len(left[target]), self.maxSize))
+            inside = set(left[target])
+            if any(sum(k in inside for k in grp) >= 2 for grp in self.apart):
+                raise ValueError("move: a keep-apart constraint holds between two of these images")
+        rebuilt = [i for i in sorted(left) if left[i]]
+        cen = dict(zip(rebuilt, self._fold_members([left[i] for i in rebuilt])))
+        held = []
+        for i, c in enumerate(self.clusters):
+            if i not in left:
+                held.append(c)
+            elif left[i]:
+                held.append(HeldCluster(left[i], cen[i], c.Frozen))
+        if target is None:
+            held += [HeldCluster([k], self.embeddings[k].copy()) for k in ids]
+        self.clusters = held
+        self._renumber()
+
+    def oversized(self) -> List[str]:
+        """The clusters above maxSize (from_partition may hold some), by their first members' ids.  recluster() raises
+        ICLError(ICL_ERR_UNSUPPORTED) while there is one; split() divides them."""
+        return [c.Members[0] for c in self.clusters if len(c.Members) > self.maxSize]
+
+    def split(self, keys, k_target: int = 0):
+        """Each unfrozen cluster of at least 2 members holding one of these ids is divided, in held order: the state's own engine and mode
+        run the reference's loop on the members' embeddings alone -- singletons, minSize 1, the state's maxSize, no constraints -- and the
+        parts (the sub-run's final list: a's members before b's, centroids as the loop left them) take the cluster's place, unfrozen.
+        This is the reference's splitCluster (clustering.go:295-349) made reachable.  k_target = 0 stops where it does, at
+        CalculateOptimalClusters(n, 1, maxSize) = (ceil(n / maxSize) + n) / 2 parts (:303) -- a little over n / 2 of them, since a minimum
+        of 1 puts the upper end of the range at n; ceil(n / maxSize) is the usual choice for "as few parts as maxSize allows".  ValueError, with the state as it was, for an
+        id that is not held, a frozen cluster, or a sub-run that cannot meet its constraints."""
+        keys = list(dict.fromkeys(keys))
+        where = self._where(keys, "split")
+        at = sorted({where[k] for k in keys})
+        if any(self.clusters[i].Frozen for i in at):
+            raise ValueError("split: a cluster holding one of these ids is frozen")
+        parts = {}
+        for i in at:
+            members = self.clusters[i].Members
+            if len(members) < 2:
+                continue
+            C = np.stack([self.embeddings[k] for k in members]).astype(np.float32)
+            ss = np.ones(len(members), np.int32)
+            if self.engine is not None:
+                _, _, _, st, mg, co = self.engine(C, ss, 1, self.maxSize, k_target)
+            else:
+                _, _, _, st, mg, co = _seeded_call(self.ctx or default_context(), C, ss, 1, self.maxSize, k_target, update=self.update)
+            if st == _lib.ICL_ERR_CONSTRAINT:
+                raise ValueError("split: the cluster of %r cannot be divided under these constraints" % (members[0],))
+            if st != _lib.ICL_OK:
+                raise _lib.ICLError(st, "split: the sub-run failed with code %d" % st)
+            parts[i] = [HeldCluster([members[s] for s in seq], np.array(co[seq[0]], np.float32, copy=True)) for seq in _final_seed_lists(len(members), mg)]
+        self.clusters = [p for i, c in enumerate(self.clusters) for p in parts.get(i, [c])]
+        self._renumber()
 
     def _duplicate_lists(self, E, threshold):
         """Per row of E: ([(held position, value), ...] over self.embeddings in the order they were added -- icl_pairs_between --,
@@ -534,16 +733,12 @@ class Clustering:
         if st != _lib.ICL_OK:
             raise _lib.ICLError(st, "seeded clustering: the problem failed with code %d" % st)
         # the final list from the merge log: surviving seeds in seed order, then merged clusters in creation order, a's seeds before b's
-        m = len(self.clusters)
-        seq = {i: [i] for i in range(m)}
-        for t, (a, b) in enumerate(np.asarray(mg).reshape(-1, 2)):
-            seq[m + t] = seq.pop(int(a)) + seq.pop(int(b))
         held = []
-        for c in sorted(seq):
-            first = seq[c][0]
+        for seq in _final_seed_lists(len(self.clusters), mg):
+            first = seq[0]
             # an image's rank: the items of the seeds before its own, plus its place in its own seed
-            members = [k for s in seq[c] for k in self.clusters[s].Members]
-            held.append(HeldCluster(members, np.array(co[first], np.float32, copy=True), c < m and self.clusters[c].Frozen, int(cid[first])))
+            members = [k for s in seq for k in self.clusters[s].Members]
+            held.append(HeldCluster(members, np.array(co[first], np.float32, copy=True), len(seq) == 1 and self.clusters[first].Frozen, int(cid[first])))
         self.clusters = held
         self.last_merges = np.asarray(mg, np.int32).reshape(-1, 2).copy()
         return True

@@ -184,6 +184,8 @@ struct icl_ctx {
     int fwd_prune_fused = 1;   // with fwd_prune: the fused stage-1 bottleneck in front of stage 2 runs as bneck56_kernel<false, 2> (icl_set_forward_prune_fused, ICL_PRUNE_FUSED=0)
     int64_t pruned_fused = 0;  // launches of that instantiation by the forward pass (icl_forward_prune_fused_stats)
     int stem_max_blocks = 0;   // tests only (icl_set_stem_max_blocks): at most this many workgroups in a stem kernel's persistent grid, 0 = no cap
+    icl_dev_grow fold;                   // device copies of row_ptr, the member list and the members' sizes of icl_fold_centroids (fold.hip)
+    int64_t fold_stats[4] = {0, 0, 0, 0}; // last icl_fold_centroids[_dev]: groups, member rows read, longest group, workspace bytes (icl_last_fold_stats)
 };
 
 static inline hipStream_t icl_main_stream(const icl_ctx *ctx) { return ctx->stream; }

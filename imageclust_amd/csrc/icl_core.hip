@@ -92,6 +92,7 @@ extern "C" void icl_destroy(icl_ctx *ctx)
     ctx->nearest.release();
     ctx->pairs.release();
     ctx->fit.release();
+    ctx->fold.release();
     for (auto &p : ctx->pending) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

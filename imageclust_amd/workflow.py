@@ -75,7 +75,7 @@ def RunUploaded(appCtx: AppContext, requests: Sequence[UploadedRequest], prec: i
 
 
 def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int = _lib.PREC_FP32,
-            threads: int = 0, dedupe_threshold: Optional[float] = None, update: Optional[int] = None):
+            threads: int = 0, dedupe_threshold: Optional[float] = None, update: Optional[int] = None, remove_ids=None):
     """More images for a request that has been answered: newRequestImages = (paths, ids, labels_per_image, labelSet) with the
     labelSet of the request `state` came from (the combined rows must be as wide as the state's).  Only the new images are embedded
     and combined (createEmbeddings, workflow.go:149-185); they join the state as singletons and the loop goes on from the clusters
@@ -85,7 +85,8 @@ def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int =
     held image or an earlier new image under that threshold does not join (Clustering.add(skip_duplicates=)), and the result has a
     third entry, the list [(skipped id, partner id, value), ...] (empty where the call fails before the images are compared).  update
     (UPDATE_EXACT / UPDATE_LW; None: as the state was made) sets the state's mode from this call on: UPDATE_LW resumes in FAST mode
-    (icl_cluster_seeded_fast), where a state with keep_apart constraints raises ICLError(ICL_ERR_UNSUPPORTED)."""
+    (icl_cluster_seeded_fast), where a state with keep_apart constraints raises ICLError(ICL_ERR_UNSUPPORTED).  remove_ids (None: nothing)
+    names held images that leave the state (Clustering.remove) once the new files have been read and before the new images are added."""
     if appCtx.Net is None or appCtx.Net.Empty():
         raise _lib.ICLError(_lib.ICL_ERR_NOMODEL, "RunMore: no model loaded")
     paths, ids, labels_per_image, labelSet = newRequestImages
@@ -104,6 +105,8 @@ def RunMore(appCtx: AppContext, state: Clustering, newRequestImages, prec: int =
         state.ctx = ctx
     if update is not None:
         state.update = int(update)
+    if remove_ids is not None:
+        state.remove(remove_ids)
     skipped = state.add(np.concatenate([E, lab], axis=1), list(ids), skip_duplicates=dedupe_threshold)  # CombineEmbeddings (:177-183)
     out = (state.as_map(), True) if state.recluster() else (None, False)
     return out if dedupe_threshold is None else out + (skipped,)

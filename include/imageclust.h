@@ -593,6 +593,29 @@ int icl_ward_values_at(icl_ctx *ctx, const float *Q, const int32_t *q_size, int6
                        const int32_t *qi, const int32_t *ej, int64_t np, float *val);
 int icl_ward_values_at_dev(icl_ctx *ctx, const float *d_Q, const int32_t *q_size, int64_t nq, const float *d_E, const int32_t *e_size, int64_t n,
                            int32_t d, const int32_t *qi, const int32_t *ej, int64_t np, float *d_val);
+/* ---- fold centroids: the centroid of every cluster given as a member list (DESIGN.md "Editing a held clustering") ----
+ * E holds n rows of d floats with item counts size[n] (NULL: all 1).  Group g, g < K, is the rows member[row_ptr[g] .. row_ptr[g + 1]) of E, in
+ * that order; a row may appear in several groups, several times in one group, or in none.
+ * VALUE: what the reference holds after merging the members one at a time in member order (MergeClusters, clustering.go:29-47).  The first
+ * member's row is copied; member t then gives, per column k,
+ *     c[k] = (float(S) * c[k] + float(s_t) * E[m_t][k]) / float(S + s_t),    S += s_t
+ * with S the integer item total so far and each product, the sum and the quotient rounded to fp32 on its own (no contraction).  The fold is
+ * not associative: the order is the list's.  Row g of C_out (K x d, no pitch) receives group g's centroid, size_out[g] (may be NULL) its item
+ * total; an empty group gives a row of +0.0 and size 0.  The result does not depend on launch geometry.
+ * Returns ICL_ERR_ARG, with nothing written, for a null pointer that is needed (the context; row_ptr and C_out when K > 0; member and E when a
+ * group has a member), n < 0, d < 1, K < 0 or K >= 2^31, row_ptr[0] != 0, a decreasing row_ptr, a member outside [0, n), a size below 1, or a
+ * group whose item total exceeds INT32_MAX; K == 0 is ICL_OK with no launch; ICL_ERR_UNSUPPORTED on a context that is a replica of a group;
+ * ICL_ERR_NOMEM when the device copies do not fit.
+ * icl_fold_centroids takes host memory throughout: it uploads E, runs the _dev body and downloads C_out.  icl_fold_centroids_dev takes E and
+ * C_out on the context's device (read and written on the context's stream; both 16-byte aligned take 16-byte loads and stores when
+ * d % 4 == 0); size, row_ptr, member and size_out stay in host memory and may be reused at return. */
+int icl_fold_centroids(icl_ctx *ctx, const float *E, const int32_t *size, int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *member,
+                       int64_t K, float *C_out, int32_t *size_out);
+int icl_fold_centroids_dev(icl_ctx *ctx, const float *d_E, const int32_t *size, int64_t n, int32_t d, const int64_t *row_ptr,
+                           const int32_t *member, int64_t K, float *d_C_out, int32_t *size_out);
+/* The last icl_fold_centroids[_dev] of the context: info = groups, member rows read, the longest group's length, workspace bytes (all 0 after
+ * a call with K == 0). */
+int icl_last_fold_stats(icl_ctx *ctx, int64_t info[4]);
 /* ---- duplicate pairs: every pair of rows whose WardDistance is at most a threshold, exact and complete, no distance matrix (DESIGN.md "Duplicate pairs") ----
  * E holds n rows of d floats; size[n] are the rows' item counts (NULL: all 1).
  * VALUE of pair (i, j), j < i < n: WardDistance (clustering.go:136-157) of a cluster of size[i] items at E[i] and one of size[j] items at E[j],
